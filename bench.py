@@ -115,7 +115,50 @@ def parse_args():
                          "through it — the RCCL code path on a 1-GPU box")
     ap.add_argument("--same-device", action="store_true",
                     help="dry run of the N>1 code path on a 1-GPU box: every rank uses cuda:0 (use with --backend gloo)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step of every slot computed as DIR/<name>.npy "
+                         "(rank 0; <= 64 MB in all, a fixed seeded sample of the rows beyond that)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 64 << 20
+DUMP_SEED = 20240901
+
+
+def dump_outputs(torch, scan, mode, out_dir):
+    """What the timed path's caller receives from the last step of every slot, one file per pose batch (slot k always
+    scans batch k, so the files do not depend on how many bursts the timing took): the ranges in global pose order
+    as (poses, beams) float32 — ``ranges_batch<k>.npy`` —, or for the reduced modes the per-step result
+    (``crash_index_batch<k>.npy``: int32 first crashed pose of every roll-out, as float64;
+    ``steer_angle_batch<k>.npy``: float32 steering angle of every pose).  Above DUMP_BYTES in all, the same
+    DUMP_SEED-seeded sample of rows is written for every batch."""
+    scan.finish()
+    torch.cuda.synchronize()
+    outs = []
+    for k, sl in enumerate(scan.slots):
+        if scan.reduced:
+            r = scan.results(sl)
+            if r is None:
+                continue
+            v = r[:, -1].reshape(-1)
+            name = "crash_index" if mode == "crash" else "steer_angle"
+            outs.append(("%s_batch%d" % (name, k), v.reshape(-1, 1), torch.float64 if mode == "crash" else torch.float32))
+        else:
+            if scan.gather and sl.gathered is None:
+                return                                   # ('root': only the consumer rank holds the ranges)
+            outs.append(("ranges_batch%d" % k, scan.global_order(sl).reshape(-1, scan.num_rays), torch.float32))
+    if not outs:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES // len(outs)
+    for name, t, dt in outs:
+        row_bytes = t.shape[1] * (8 if dt == torch.float64 else 4)
+        keep = min(t.shape[0], max(1, budget // row_bytes))
+        if keep < t.shape[0]:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(t.shape[0], keep, replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        arr = t.to(dt).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr[:, 0] if arr.shape[1] == 1 else arr)
 
 
 def spawn_ranks(a):
@@ -535,6 +578,9 @@ def main():
     runs = timed_scan(scan, a.steps, a.warmup, a.bursts)
     res = summarise(runs, a.steps, rays_per_step)
     step_ms = res["dev_ms"]
+    if a.dump_outputs and rank == 0:
+        # (before anything below reuses the slot buffers: verification, side legs, the other schedules)
+        dump_outputs(torch, scan, mode, a.dump_outputs)
 
     # ---------------------------------------------------------------- verification (untimed)
     # (1) every slot's buffer == a serial, one-ray-per-lane, whole-machine launch of the same poses;
