@@ -254,6 +254,51 @@ int rl_car_rollout_check(rl_car *c, rl_method *h, const double *states_in, const
                          int num_rays, const double *edge, double crash_thresh, int *first_crashed,
                          double *states_out_or_null, double *velocities_out_or_null);
 
+/* ---- closed-loop Follow-the-Gap roll-outs ---------------------------------------------------
+ * The reference's driving loop, where each tick's steering angle comes from that tick's scan: the simulator
+ * tick (scripts/ros_interface.py:119-148: updatePose(), runScan(), checkCollision() >= 0 is a crash) answered
+ * by the driver (scripts/two_player/simple_driver.py:31,48-53, scripts/follow_the_gap.py:
+ * PyFollowGap(10, 15.0, max_steer, 0.004).eval(ranges), then drive(VELOCITY, angle)); MCTS.act runs the same
+ * tick with generateActionFromFG (scripts/mcts.py:187-200,262-267).  R cars, T ticks, nothing leaves the device
+ * between ticks.
+ *
+ * Inputs per car: a start state (11 doubles, getState layout), a constant speed (simple_driver.py's VELOCITY)
+ * and an initial steer (steer0_or_null; null = 0).  dt is the step (0.01 in racecar_simulator_v2.py:126),
+ * scan_dist_to_base where the lidar sits (0.275, params.yaml:36), fov / num_rays / edge / crash_thresh the
+ * scan and crash test.  c, h and g are ordinary handles on ONE device (multi-device handles are refused).
+ *
+ * Tick t = 0 ... T-1, for every car still alive:
+ *   1. Car::control + Car::updatePosition(dt) with (speed, steer) — car_kernels.h car_step;
+ *   2. the lidar pose of Car::getScanPose (racecar.cpp:378-387): (x + d cos th, y + d sin th, th) in f64,
+ *      cast to f32 as ScanSimulator2D.scan does;
+ *   3. the scan of that pose with h: any kind, its options and its noise, the noise keyed by the global ray
+ *      id with ray offset h.ray_offset + (t R + r) num_rays (so T ticks in one call equal T/2 + T/2 with the
+ *      offset advanced by T/2 R num_rays, the states and the last steer chained);
+ *   4. Car::isCrashed on that one scan (racecar.cpp:305-328): a beam with (double)range - edge[j] <
+ *      crash_thresh sets first_crashed[r] = t and freezes the car — it is not stepped again;
+ *   5. otherwise steer = FollowGap::eval(ranges, num_rays), bit-identical to rl_followgap_eval, cast to
+ *      double for the next tick's control.
+ * simple_driver.py clips the angle to +-0.4189 before drive(); with g's max_angle <= the car's MAX_STEER_ANG
+ * (as the reference builds it) that clip never acts, and it is not applied here.  mcts.py:195 tests
+ * checkCollision() > 0, which a single scan never returns (0 or -2); the loop follows ros_interface.py:144
+ * (>= 0).
+ *
+ * Outputs: first_crashed[R] = the crash tick or -(T+1) (isCrashed's convention); states_out (optional) =
+ * the state after the last step taken (the crash tick's for a crashed car).  Optional per-tick traces, row
+ * r t of [R, T]: velocities (state[3] after the step, MCTS's reward), steers (f32; NaN on the crash tick),
+ * scan_poses (3 f32), states_trace (11 f64).  Rows after a car's crash tick are NaN.
+ *
+ * Errors (RL_ERR_INVALID, all three handles stay usable): null pointers, n_ticks <= 0, num_rays outside
+ * [10, 1280] (the one-bit-per-beam FollowGap kernel), R num_rays >= 2^31, handles on different devices,
+ * multi-device handles.  R = 0 does nothing.  Synchronous; h's options and noise offset read the same after
+ * the call.  Per tick: the fan launch sequence of h's planner, then one drive_tick_kernel (drive_kernels.h). */
+int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in,
+                           const double *speeds, const float *steer0_or_null, int n_rollouts, int n_ticks,
+                           double dt, double scan_dist_to_base, float fov, int num_rays, const double *edge,
+                           double crash_thresh, int *first_crashed, double *states_out_or_null,
+                           double *velocities_or_null, float *steers_or_null, float *scan_poses_or_null,
+                           double *states_trace_or_null);
+
 /* Car::setCarEdgeDistances (racecar/src/racecar.cpp:239-292; called at
  * scripts/racecar_simulator_v2.py:47-50): distance from the lidar to the car's outline along each of
  * num_rays beams starting one increment after min_ang — the table every crash test above takes as

@@ -111,6 +111,9 @@ SYMBOLS = {
     "rl_car_rollout_check": (C.c_int, [C.c_void_p, C.c_void_p, f64p, f64p, C.c_int, C.c_int, C.c_int,
                                        C.c_double, C.c_float, C.c_int, f64p, C.c_double,
                                        C.POINTER(C.c_int), f64p, f64p]),
+    "rl_car_drive_followgap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, f64p, f64p, f32p, C.c_int, C.c_int,
+                                         C.c_double, C.c_double, C.c_float, C.c_int, f64p, C.c_double,
+                                         C.POINTER(C.c_int), f64p, f64p, f32p, f32p, f64p]),
     "rl_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "rl_host_free": (C.c_int, [C.c_void_p]),
     "rl_car_edge_distances": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,

@@ -6,6 +6,7 @@
 #include <utility>
 #include "car_kernels.h"
 #include "consumer_kernels.h"
+#include "drive_kernels.h"
 #include "probe_kernels.h"
 
 struct rl_car {
@@ -15,6 +16,7 @@ struct rl_car {
     CarParams P{};
     hipStream_t stream = nullptr;
     DevBuf states, actions, poses, states_out, vel, ranges, edge, first;
+    DevBuf speeds, steer0, tr_steers, tr_poses, tr_states;     // rl_car_drive_followgap
     std::mutex mu;
 };
 
@@ -76,7 +78,8 @@ extern "C" void rl_car_destroy(rl_car *c)
     }
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (DevBuf *b : {&c->states, &c->actions, &c->poses, &c->states_out, &c->vel, &c->ranges, &c->edge, &c->first})
+    for (DevBuf *b : {&c->states, &c->actions, &c->poses, &c->states_out, &c->vel, &c->ranges, &c->edge, &c->first,
+                      &c->speeds, &c->steer0, &c->tr_steers, &c->tr_poses, &c->tr_states})
         b->release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -310,6 +313,112 @@ extern "C" int rl_followgap_eval_device(rl_followgap *g, const float *d_scans, i
     std::lock_guard<std::mutex> lk(g->mu);
     HIPCHK(hipSetDevice(g->device));
     return followgap_launch(g, d_scans, n_scans, size, d_angles, (hipStream_t)hip_stream);
+}
+
+// ---------------------------------------------------------------- closed-loop FollowGap roll-outs (drive_kernels.h)
+// drive_tick_kernel<ROWS>, ROWS = 1 ... FG_ROWS
+typedef void (*drive_tick_fn)(DriveParams, DriveBufs, int);
+template <int... R>
+static constexpr std::array<drive_tick_fn, sizeof...(R)> drive_tick_make(std::integer_sequence<int, R...>)
+{
+    return {{drive_tick_kernel<R + 1>...}};
+}
+static const std::array<drive_tick_fn, FG_ROWS> drive_tick_table = drive_tick_make(std::make_integer_sequence<int, FG_ROWS>());
+
+static int drive_args(rl_car *c, rl_method *h, rl_followgap *g, int R, int n_ticks, float fov, int num_rays)
+{
+    if (!c->reps.empty() || !h->reps.empty())
+        return fail(RL_ERR_INVALID, "rl_car_drive_followgap is single-device only: pass ordinary (not multi-device) handles");
+    if (c->device != h->map->device || g->device != c->device)
+        return fail(RL_ERR_INVALID, "car (device %d), range method (device %d) and FollowGap (device %d) must share one device",
+                    c->device, h->map->device, g->device);
+    if (R < 0 || n_ticks <= 0) return fail(RL_ERR_INVALID, "n_rollouts >= 0 and n_ticks > 0 required (got %d, %d)", R, n_ticks);
+    if (num_rays < 10 || num_rays > 64 * FG_ROWS)
+        return fail(RL_ERR_INVALID, "num_rays must lie in [10, %d] (got %d)", 64 * FG_ROWS, num_rays);
+    if ((long)R * num_rays >= (1L << 31)) return fail(RL_ERR_INVALID, "n_rollouts * num_rays must stay below 2^31");
+    return check_fan_args(h, R, fov, num_rays);
+}
+
+extern "C" int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in,
+                                      const double *speeds, const float *steer0_or_null, int R, int n_ticks, double dt,
+                                      double scan_dist_to_base, float fov, int num_rays, const double *edge,
+                                      double crash_thresh, int *first_crashed, double *states_out_or_null,
+                                      double *velocities_or_null, float *steers_or_null, float *scan_poses_or_null,
+                                      double *states_trace_or_null)
+{
+    if (!c || !h || !g || (R > 0 && (!states_in || !speeds || !edge || !first_crashed)))
+        return fail(RL_ERR_INVALID, "rl_car_drive_followgap: null pointer");
+    int rc = drive_args(c, h, g, R, n_ticks, fov, num_rays);
+    if (rc || R == 0) return rc;
+    std::scoped_lock lk(c->mu, h->mu, g->mu);
+    std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
+    HIPCHK(hipSetDevice(c->device));
+    const size_t rows = (size_t)R * n_ticks, n_rays = (size_t)R * num_rays;
+    if ((rc = c->states.ensure((size_t)R * 11 * 8)) || (rc = c->speeds.ensure((size_t)R * 8)) ||
+        (rc = c->steer0.ensure((size_t)R * 4)) || (rc = c->first.ensure((size_t)R * 4)) ||
+        (rc = c->poses.ensure((size_t)R * 12)) || (rc = c->ranges.ensure(n_rays * 4)) ||
+        (rc = c->edge.ensure((size_t)num_rays * 8)) ||
+        (velocities_or_null && (rc = c->vel.ensure(rows * 8))) || (steers_or_null && (rc = c->tr_steers.ensure(rows * 4))) ||
+        (scan_poses_or_null && (rc = c->tr_poses.ensure(rows * 12))) ||
+        (states_trace_or_null && (rc = c->tr_states.ensure(rows * 88))))
+        return rc;
+    hipStream_t st = c->stream;
+    HIPCHK(hipMemcpyAsync(c->states.p, states_in, (size_t)R * 11 * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->speeds.p, speeds, (size_t)R * 8, hipMemcpyHostToDevice, st));
+    if (steer0_or_null) HIPCHK(hipMemcpyAsync(c->steer0.p, steer0_or_null, (size_t)R * 4, hipMemcpyHostToDevice, st));
+    else HIPCHK(hipMemsetAsync(c->steer0.p, 0, (size_t)R * 4, st));
+    HIPCHK(hipMemcpyAsync(c->edge.p, edge, (size_t)num_rays * 8, hipMemcpyHostToDevice, st));
+    // trace rows a car never reaches (after its crash tick; the steer of the crash tick) read NaN: all-ones bytes
+    if (velocities_or_null) HIPCHK(hipMemsetAsync(c->vel.p, 0xff, rows * 8, st));
+    if (steers_or_null) HIPCHK(hipMemsetAsync(c->tr_steers.p, 0xff, rows * 4, st));
+    if (scan_poses_or_null) HIPCHK(hipMemsetAsync(c->tr_poses.p, 0xff, rows * 12, st));
+    if (states_trace_or_null) HIPCHK(hipMemsetAsync(c->tr_states.p, 0xff, rows * 88, st));
+
+    DriveParams dp{};
+    dp.P = c->P;
+    dp.fg = g->P;
+    dp.fg.size = num_rays;
+    dp.dt = dt;
+    dp.scan_dist_to_base = scan_dist_to_base;
+    dp.crash_thresh = crash_thresh;
+    dp.n_cars = R;
+    dp.n_ticks = n_ticks;
+    DriveBufs b{(double *)c->states.p, (const double *)c->speeds.p, (const float *)c->steer0.p, (const double *)c->edge.p,
+                (int *)c->first.p, (float *)c->poses.p, (const float *)c->ranges.p,
+                velocities_or_null ? (double *)c->vel.p : nullptr, steers_or_null ? (float *)c->tr_steers.p : nullptr,
+                scan_poses_or_null ? (float *)c->tr_poses.p : nullptr,
+                states_trace_or_null ? (double *)c->tr_states.p : nullptr};
+    hipLaunchKernelGGL(drive_start_kernel, dim3((R + 63) / 64), dim3(64), 0, st, dp, b);
+    HIPCHK(hipGetLastError());
+    // the consumer reads the ranges right after the scan: plain stores (the handle's setting comes back below, as does
+    // its noise offset, which walks the global ray id t R num_rays + r num_rays of every tick)
+    const uint64_t base_off = h->ray_offset;
+    const int nt_store = h->nt_store;
+    h->nt_store = 0;
+    const drive_tick_fn tick = drive_tick_table[(num_rays + 63) / 64 - 1];
+    for (int t = 0; t < n_ticks && rc == RL_OK; ++t) {
+        h->ray_offset = base_off + (uint64_t)t * n_rays;
+        rc = launch_fan(h, (const float *)c->poses.p, R, fov, num_rays, (float *)c->ranges.p, nullptr, nullptr, nullptr, st);
+        if (rc == RL_OK) {
+            tick<<<dim3((R + DRIVE_CARS - 1) / DRIVE_CARS), dim3(64 * DRIVE_CARS), 0, st>>>(dp, b, t);
+            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "drive_tick_kernel launch failed");
+        }
+    }
+    h->ray_offset = base_off;
+    h->nt_store = nt_store;
+    if (rc) {
+        (void)hipStreamSynchronize(st);           // nothing of this call is left in flight on the handles' buffers
+        return rc;
+    }
+    HIPCHK(hipMemcpyAsync(first_crashed, c->first.p, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+    if (states_out_or_null) HIPCHK(hipMemcpyAsync(states_out_or_null, c->states.p, (size_t)R * 88, hipMemcpyDeviceToHost, st));
+    if (velocities_or_null) HIPCHK(hipMemcpyAsync(velocities_or_null, c->vel.p, rows * 8, hipMemcpyDeviceToHost, st));
+    if (steers_or_null) HIPCHK(hipMemcpyAsync(steers_or_null, c->tr_steers.p, rows * 4, hipMemcpyDeviceToHost, st));
+    if (scan_poses_or_null) HIPCHK(hipMemcpyAsync(scan_poses_or_null, c->tr_poses.p, rows * 12, hipMemcpyDeviceToHost, st));
+    if (states_trace_or_null)
+        HIPCHK(hipMemcpyAsync(states_trace_or_null, c->tr_states.p, rows * 88, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
 }
 
 // ---------------------------------------------------------------- diagnostics: HBM stream probe

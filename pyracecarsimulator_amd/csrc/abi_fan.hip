@@ -941,9 +941,6 @@ static LiteralParams make_literal(const rl_map *m)
     return lt;
 }
 
-static int launch_fan(rl_method *h, const float *d_poses, int n_poses, float fov, int num_rays,
-                      float *d_out, int32_t *d_hits, uint16_t *d_steps, const CrashParams *crash,
-                      hipStream_t stream);
 
 // what a method family's launch function needs: the call's arguments, the plan, the launch context
 struct FanLaunch {
@@ -1260,9 +1257,9 @@ static int launch_fan_sliced(rl_method *h, const rl_launch_plan &pl, const float
     return rc;
 }
 
-static int launch_fan(rl_method *h, const float *d_poses, int n_poses, float fov, int num_rays,
-                      float *d_out, int32_t *d_hits, uint16_t *d_steps, const CrashParams *crash,
-                      hipStream_t stream)
+int launch_fan(rl_method *h, const float *d_poses, int n_poses, float fov, int num_rays,
+               float *d_out, int32_t *d_hits, uint16_t *d_steps, const CrashParams *crash,
+               hipStream_t stream)
 {
     if (n_poses == 0) return RL_OK;
     const rl_map *m = h->map;

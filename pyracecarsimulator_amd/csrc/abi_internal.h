@@ -4,7 +4,8 @@
 //   abi_fan.hip    rl_method_*: options, derived tables, the launch planner's C ABI, every fan / ray launch, the
 //                  device-pointer entry points, the single-device host-pointer paths, the fused crash test
 //   abi_multi.hip  the host-pointer entry points and their multi-device forms (one pose block per device)
-//   abi_car.hip    roll-out generator, FollowGap, 16-bit ranges, probes, the car-outline table
+//   abi_car.hip    roll-out generator, FollowGap, closed-loop FollowGap roll-outs, 16-bit ranges, probes, the
+//                  car-outline table
 #pragma once
 // (the units are built with -fvisibility=hidden: only the C ABI leaves the library)
 #pragma GCC visibility push(default)
@@ -398,6 +399,11 @@ void host_sincosf(float x, float &s, float &c);      // host twin of scan::det_s
 // abi_fan.hip, called from abi_multi.hip / abi_car.hip
 // ------------------------------------------------------------------------------
 int check_fan_args(const rl_method *h, int n_poses, float fov, int num_rays);
+namespace scan { struct CrashParams; }
+// one fan launch sequence on `stream` as the planner picks it (noise keyed by h->ray_offset; the caller holds h->mu and
+// the map's tables_mu and has checked the arguments)
+int launch_fan(rl_method *h, const float *d_poses, int n_poses, float fov, int num_rays, float *d_out, int32_t *d_hits,
+               uint16_t *d_steps, const CrashParams *crash, hipStream_t stream);
 int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_rays, float *outs, int32_t *hits,
              uint16_t *steps, const double *edge, double crash_thresh, int *first_crashed);
 int crash_groups_device(rl_method *h, const float *d_poses, int n_groups, int group, float fov, int num_rays,

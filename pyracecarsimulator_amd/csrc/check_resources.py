@@ -23,6 +23,9 @@ BOUNDS = [
     ("scan::cddt_fan_bins_kernel", {"vgpr": 64, "sgpr": 80, "occupancy": 8, "scratch": 0}),
     ("scan::bl_fan_stream_kernel<false, 1024>", {"vgpr": 56, "sgpr": 96, "occupancy": 8, "scratch": 0}),
     ("scan::rm_leftover_kernel<", {"vgpr": 48, "occupancy": 8, "scratch": 0}),
+    # closed-loop FollowGap roll-outs: scan, crash compare, FollowGap and the f64 car step in one wave per car, no spills
+    ("scan::drive_tick_kernel<", {"scratch": 0}),
+    ("scan::drive_start_kernel", {"scratch": 0}),
 ]
 KEYS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy"}
 

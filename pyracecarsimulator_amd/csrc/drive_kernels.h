@@ -1,0 +1,139 @@
+// drive_kernels.h — closed-loop Follow-the-Gap roll-outs (rl_car_drive_followgap, include/scanlib.h): the reference's
+// simulator tick (scripts/ros_interface.py:119-148: updatePose, runScan, checkCollision >= 0) driven by the
+// FollowGap answer to every scan (scripts/two_player/simple_driver.py:31,48-53), for many cars at once with
+// nothing crossing PCIe between ticks.  Per tick the host enqueues two things on one stream:
+//   1. the scan of every car's lidar pose through the ordinary fan planner (launch_fan, abi_fan.hip);
+//   2. drive_tick_kernel: one wave per car — the scan into registers, Car::isCrashed's f64 compare
+//      (racecar.cpp:305-328) as a ballot, FollowGap's four passes (followgap_bits_eval, consumer_kernels.h) —,
+//      then one lane per car: the car step of the NEXT tick with the new steering angle and that tick's lidar pose.
+// drive_start_kernel (one lane per car) is the prologue: tick 0's step with the initial steer.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "car_kernels.h"
+#include "consumer_kernels.h"
+
+namespace scan {
+
+struct DriveParams {
+    CarParams P;
+    FollowGapParams fg;          // fg.size = num_rays
+    double dt, scan_dist_to_base, crash_thresh;
+    int n_cars, n_ticks;
+};
+
+struct DriveBufs {
+    double *state;               // [R, 11] getState layout: the state after the last step taken
+    const double *speed;         // [R] commanded speed (constant over the roll-out)
+    const float *steer0;         // [R] steering input of tick 0's step
+    const double *edge;          // [num_rays] car-outline table
+    int *first;                  // [R] crash tick, -(T+1) while alive
+    float *pose;                 // [R, 3] f32 lidar pose the next scan reads
+    const float *ranges;         // [R, num_rays] this tick's scans
+    double *vel;                 // optional traces [R, T] (pre-filled with NaN by the host)
+    float *steers;
+    float *scan_poses;           // [R, T, 3]
+    double *states_trace;        // [R, T, 11]
+};
+
+__device__ inline CarState drive_load_state(const double *s)
+{
+    CarState cs;
+    cs.x = s[0]; cs.y = s[1]; cs.theta = s[2]; cs.velocity = s[3]; cs.steer_angle = s[4];
+    cs.angular_velocity = s[5]; cs.slip_angle = s[6]; cs.st_dyn = s[7] > 0.0;
+    cs.travel_dist = s[8]; cs.total_velo = s[9]; cs.update_count = (int)s[10];
+    return cs;
+}
+
+__device__ inline void drive_store_state(const CarState &cs, double *o)
+{
+    o[0] = cs.x; o[1] = cs.y; o[2] = cs.theta; o[3] = cs.velocity; o[4] = cs.steer_angle;
+    o[5] = cs.angular_velocity; o[6] = cs.slip_angle; o[7] = cs.st_dyn ? 1.0 : 0.0;
+    o[8] = cs.travel_dist; o[9] = cs.total_velo; o[10] = (double)cs.update_count;
+}
+
+// Car::control + updatePosition for tick t of car r, then Car::getScanPose (racecar.cpp:378-387) in f64 cast to f32 as
+// ScanSimulator2D.scan does, and the trace rows of tick t.  One lane.
+__device__ inline void drive_step(const DriveParams &dp, const DriveBufs &b, int r, int t, double steer)
+{
+    double *s = b.state + (size_t)r * 11;
+    CarState cs = drive_load_state(s);
+    car_step(dp.P, cs, b.speed[r], steer, dp.dt);
+    drive_store_state(cs, s);
+    const float px = (float)(cs.x + dp.scan_dist_to_base * cos(cs.theta));
+    const float py = (float)(cs.y + dp.scan_dist_to_base * sin(cs.theta));
+    const float pt = (float)cs.theta;
+    b.pose[3 * r + 0] = px;
+    b.pose[3 * r + 1] = py;
+    b.pose[3 * r + 2] = pt;
+    const size_t row = (size_t)r * dp.n_ticks + t;
+    if (b.vel) b.vel[row] = cs.velocity;
+    if (b.scan_poses) {
+        b.scan_poses[3 * row + 0] = px;
+        b.scan_poses[3 * row + 1] = py;
+        b.scan_poses[3 * row + 2] = pt;
+    }
+    if (b.states_trace) drive_store_state(cs, b.states_trace + 11 * row);
+}
+
+// tick 0's step, one lane per car (b.state holds the start states)
+__global__ __launch_bounds__(64) void drive_start_kernel(DriveParams dp, DriveBufs b)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= dp.n_cars) return;
+    b.first[r] = -(dp.n_ticks + 1);
+    drive_step(dp, b, r, 0, (double)b.steer0[r]);
+}
+
+// tick t after its scan: crash test, FollowGap, and the step of tick t + 1.  A workgroup holds DRIVE_CARS cars, one wave
+// each for the scan-wide work (ROWS = ceil(num_rays / 64)); the f64 steps of the workgroup's cars then run one lane per
+// car in wave 0.  (One step on lane 0 of every wave cost the full wave's f64 issue per car: at 4096 cars that was most
+// of the kernel's time.)  A frozen car (crashed at an earlier tick) was scanned at its last pose with the others; its
+// wave skips the work.
+constexpr int DRIVE_CARS = 8;
+
+template <int ROWS>
+__global__ __launch_bounds__(64 * DRIVE_CARS) void drive_tick_kernel(DriveParams dp, DriveBufs b, int t)
+{
+    __shared__ uint32_t bits[DRIVE_CARS][2 * ROWS + 4];
+    __shared__ float steer_next[DRIVE_CARS];
+    __shared__ int step_next[DRIVE_CARS];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * DRIVE_CARS + w;
+    const int size = dp.fg.size;
+    bool go = false;
+    float angle = 0.0f;
+    if (r < dp.n_cars && b.first[r] < 0) {                // (wave-uniform)
+        const float *lidar = b.ranges + (size_t)r * size;
+        float raw[ROWS];
+        double edge[ROWS];
+#pragma unroll
+        for (int u = 0; u < ROWS; ++u) {
+            const bool in = u < ROWS - 1 || 64 * u + lane < size;
+            raw[u] = in ? lidar[64 * u + lane] : 0.0f;
+            edge[u] = in ? b.edge[64 * u + lane] : 0.0;
+        }
+        // Car::isCrashed on one scan: (double)range - edge[j] < CRASH_THRESH for any beam (NaN never crashes)
+        bool hit = false;
+#pragma unroll
+        for (int u = 0; u < ROWS; ++u)
+            if (u < ROWS - 1 || 64 * u + lane < size) hit |= ((double)raw[u] - edge[u]) < dp.crash_thresh;
+        if (__ballot(hit)) {
+            if (lane == 0) b.first[r] = t;                // frozen from here: its trace rows after t stay NaN
+        } else {
+            angle = followgap_bits_eval<ROWS>(raw, dp.fg, bits[w]);
+            if (lane == 0 && b.steers) b.steers[(size_t)r * dp.n_ticks + t] = angle;
+            go = t + 1 < dp.n_ticks;
+        }
+    }
+    if (lane == 0) {
+        steer_next[w] = angle;
+        step_next[w] = go;
+    }
+    __syncthreads();
+    if (threadIdx.x < DRIVE_CARS && step_next[threadIdx.x])
+        drive_step(dp, b, blockIdx.x * DRIVE_CARS + threadIdx.x, t + 1, (double)steer_next[threadIdx.x]);
+}
+
+}  // namespace scan

@@ -13,7 +13,8 @@ on the GPU:
   ``edge_distances`` (host table, same quirks) + the fused device test in ``range_libc``.
 
 ``CarBatch.rollout_check`` chains roll-outs -> poses -> scan -> per-roll-out crash index on the
-device (poses and ranges never cross PCIe).
+device (poses and ranges never cross PCIe).  ``CarBatch.drive_followgap`` closes the loop: each tick's
+steering angle is FollowGap's answer to that tick's scan, all on the device.
 """
 from __future__ import annotations
 
@@ -116,6 +117,57 @@ class CarBatch:
             edge.ctypes.data_as(f64p), float(crash_thresh), first.ctypes.data_as(C.POINTER(C.c_int)),
             out.ctypes.data_as(f64p), vel.ctypes.data_as(f64p)))
         return first, out, vel
+
+    def drive_followgap(self, method, followgap, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
+                        scan_dist_to_base=0.275, dt=0.01, steer0=None, trace=False):
+        """Closed-loop Follow-the-Gap roll-outs (``rl_car_drive_followgap``): every tick steps each live car,
+        scans from its lidar pose with ``method``, tests the scan for a crash (a crashed car freezes) and
+        steers the next tick with ``followgap``'s answer to that scan — the reference's simulator tick
+        (scripts/ros_interface.py:119-148) driven by scripts/two_player/simple_driver.py, for R cars at once.
+
+        states float64 (R, 11) in getState layout; speed a scalar or float64 (R,); steer0 None (0) or
+        float32 (R,); edge float64 (num_rays,).  Returns (first crash tick int32 (R,) or -(n_ticks+1),
+        final states (R, 11), velocities float64 (R, n_ticks), steers float32 (R, n_ticks)) and with
+        ``trace=True`` also (lidar poses float32 (R, n_ticks, 3), states float64 (R, n_ticks, 11)).  Trace
+        rows after a car's crash tick, and its steer at that tick, are NaN."""
+        states = np.asarray(states)
+        if states.dtype != np.float64 or states.ndim != 2 or states.shape[1] != 11:
+            raise ValueError("states must be float64 (R, 11)")
+        states = np.ascontiguousarray(states)
+        R, n_ticks = states.shape[0], int(n_ticks)
+        speeds = np.asarray(speed, dtype=np.float64)
+        if speeds.ndim == 0:
+            speeds = np.full(R, float(speeds))
+        if speeds.shape != (R,):
+            raise ValueError("speed must be a scalar or float64 (R,)")
+        speeds = np.ascontiguousarray(speeds)
+        st0 = None
+        if steer0 is not None:
+            st0 = np.asarray(steer0)
+            if st0.dtype != np.float32 or st0.shape != (R,):
+                raise ValueError("steer0 must be float32 (R,)")
+            st0 = np.ascontiguousarray(st0)
+        edge = np.asarray(edge)
+        if edge.dtype != np.float64 or edge.shape != (int(num_rays),):
+            raise ValueError("edge must be float64 (num_rays,)")
+        edge = np.ascontiguousarray(edge)
+        T = max(n_ticks, 0)
+        first = np.zeros(R, dtype=np.int32)
+        out = np.empty((R, 11), dtype=np.float64)
+        vel = np.empty((R, T), dtype=np.float64)
+        steers = np.empty((R, T), dtype=np.float32)
+        poses = np.empty((R, T, 3), dtype=np.float32) if trace else None
+        trace_st = np.empty((R, T, 11), dtype=np.float64) if trace else None
+        ptr = lambda a, t: a.ctypes.data_as(t) if a is not None else None
+        _lib.check(_lib.lib().rl_car_drive_followgap(
+            self._h, method._h, followgap._h, states.ctypes.data_as(f64p), speeds.ctypes.data_as(f64p),
+            ptr(st0, f32p), R, n_ticks, float(dt), float(scan_dist_to_base), float(fov), int(num_rays),
+            edge.ctypes.data_as(f64p), float(crash_thresh), first.ctypes.data_as(C.POINTER(C.c_int)),
+            out.ctypes.data_as(f64p), vel.ctypes.data_as(f64p), steers.ctypes.data_as(f32p), ptr(poses, f32p),
+            ptr(trace_st, f64p)))
+        if trace:
+            return first, out, vel, steers, poses, trace_st
+        return first, out, vel, steers
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

@@ -12,7 +12,8 @@ it unchanged.  The two native pieces behind it are on the GPU:
   ``checkCollisionMany`` moves 12 B per pose down and one int back.
 
 ``rolloutMany`` is the batched form of ``MCTS.rollout`` + ``checkCollisionMany``
-(scripts/mcts.py:202-245) for any number of roll-outs per call.
+(scripts/mcts.py:202-245) for any number of roll-outs per call; ``driveFollowGapMany`` the closed
+loop of the simulator tick and simple_driver.py's FollowGap answer to every scan.
 """
 from __future__ import annotations
 
@@ -52,6 +53,8 @@ class RacecarSimulator:
         # car object: racecar.PyCar(...) in the reference (:37-44)
         self.car_params = {k: config[k] for k in RC.CAR_PARAM_ORDER}
         self.car = RC.CarBatch(self.car_params, device=device)
+        self._device = device
+        self._followgap = None      # driveFollowGapMany's driver, built at its first call
         self._state = np.zeros(11, dtype=np.float64)
         # where the lidar beams leave the car body: setCarEdgeDistances (:47-50)
         self.edge_distances = RC.edge_distances(self.num_rays, -self.scan_fov / 2.0,
@@ -143,6 +146,20 @@ class RacecarSimulator:
         return self.car.rollout_check(self.scan_simulator.scan_method, states, actions, self.scan_fov,
                                       self.num_rays, self.edge_distances, self.ttc_thresh,
                                       n_steps=n_steps, action_every=action_every, dt=dt)
+
+    def driveFollowGapMany(self, states, n_ticks, speed=2.0):
+        """R closed-loop roll-outs of the reference's tick (scripts/ros_interface.py:119-148: updatePose, runScan,
+        checkCollision() >= 0) steered by ``PyFollowGap(10, 15.0, max_steer_ang, 0.004)`` as
+        scripts/two_player/simple_driver.py:31 builds it, on this simulator's range method, edge table and
+        ttc_thresh.  Returns ``CarBatch.drive_followgap``'s (first crash tick or -(n_ticks+1), final states,
+        velocities, steers); ranges never leave the GPU."""
+        if self._followgap is None:
+            from .followgap import PyFollowGap
+            self._followgap = PyFollowGap(10, 15.0, self.max_steer_ang, 0.004, device=self._device)
+        return self.car.drive_followgap(self.scan_simulator.scan_method, self._followgap,
+                                        np.asarray(states, dtype=np.float64).reshape(-1, 11), n_ticks, speed,
+                                        self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
+                                        scan_dist_to_base=self.scan_dist_to_base)
 
     def stop(self):
         state = self.getState()

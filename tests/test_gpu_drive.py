@@ -1,0 +1,374 @@
+"""Closed-loop Follow-the-Gap roll-outs (rl_car_drive_followgap, CarBatch.drive_followgap,
+RacecarSimulator.driveFollowGapMany) on the MI355X: every link of the loop — step, lidar pose, scan, crash test,
+steering — pinned against the reference's compiled Car and FollowGap and against the same loop composed from
+the existing public calls."""
+import ctypes as C
+import math
+import os
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from pyracecarsimulator_amd import RacecarSimulator, _lib, maps, range_libc
+from pyracecarsimulator_amd import racecar as RC
+from pyracecarsimulator_amd.followgap import PyFollowGap
+
+pytestmark = pytest.mark.gpu
+
+FOV, B, THRESH, D_BASE = 4.71, 1081, 0.001, 0.275
+MAX_STEER = RC.DEFAULT_CAR["max_steer_ang"]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _gpu(need_gpu):
+    yield
+
+
+def _edge(num_rays=B):
+    return RC.edge_distances(num_rays, -FOV / 2, FOV / num_rays, D_BASE, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
+
+
+def _starts(g, dt, n, seed, clear_px, speed_hi=7.0):
+    rng = np.random.default_rng(seed)
+    states = np.zeros((n, 11))
+    states[:, :3] = maps.sample_free_poses(g, n, seed, clear_px, dt)
+    speeds = rng.uniform(1.0, speed_hi, n)
+    states[:, 3] = rng.uniform(0.0, 1.0, n) * speeds
+    return states, speeds
+
+
+def _within_one_ulp(a, b):
+    a = np.asarray(a, np.float32)
+    b = np.asarray(b, np.float32)
+    d = np.abs(a.astype(np.float64) - b.astype(np.float64))
+    return bool((d <= np.spacing(np.maximum(np.abs(a), np.abs(b)))).all())
+
+
+def _same_bits(a, b):
+    return np.asarray(a).tobytes() == np.asarray(b).tobytes()
+
+
+def _ref_libs():
+    car_so = os.path.join(ROOT, "oracle/_ref/libracecar_ref.so")
+    fg_so = os.path.join(ROOT, "oracle/_ref/libfollowgap_ref.so")
+    missing = [p for p in (car_so, fg_so) if not os.path.exists(p)]
+    if missing:
+        pytest.fail("reference builds missing (build() makes them): %s" % missing)
+    L = C.CDLL(car_so)
+    d, vp, dp = C.c_double, C.c_void_p, C.POINTER(C.c_double)
+    L.ref_car_create.restype = vp
+    L.ref_car_create.argtypes = [dp]
+    L.ref_car_destroy.argtypes = [vp]
+    L.ref_car_control.argtypes = [vp, d, d]
+    L.ref_car_update_position.argtypes = [vp, d]
+    L.ref_car_get_state.argtypes = [vp, dp]
+    L.ref_car_set_state.argtypes = [vp, dp]
+    L.ref_car_get_scan_pose.argtypes = [vp, d, dp]
+    L.ref_car_set_edge_distances.argtypes = [vp, C.c_int, d, d, d]
+    L.ref_car_is_crashed.restype = C.c_int
+    L.ref_car_is_crashed.argtypes = [vp, C.POINTER(C.c_float), C.c_int, C.c_int]
+    F = C.CDLL(fg_so)
+    F.ref_followgap_eval.restype = C.c_float
+    F.ref_followgap_eval.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]
+    return L, F
+
+
+def test_drive_teacher_forced_vs_reference(oracle_mod):
+    """Colombia, RMGPU, 32 cars x 150 ticks: at every live tick each link of the loop, fed the GPU's own state of
+    the tick before, agrees with the reference's compiled Car / FollowGap and the oracle scan."""
+    L, F = _ref_libs()
+    g = maps.load_colombia()
+    mrx = 300
+    om = oracle_mod.OracleMap.from_gridmap(g, mrx)
+    m = range_libc.PyRayMarchingGPU(range_libc.PyOMap(g), mrx)
+    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    R, T = 32, 150
+    states, speeds = _starts(g, om.dt, R, 3, 6.0, speed_hi=4.0)
+    edge = _edge()
+    cars = RC.CarBatch()
+    first, final, vel, steers, sp, st = cars.drive_followgap(m, fg, states, T, speeds, FOV, B, edge, THRESH, trace=True)
+    assert first.shape == (R,) and vel.shape == (R, T) and steers.shape == (R, T) and sp.shape == (R, T, 3)
+    assert st.shape == (R, T, 11)
+    last = np.where(first >= 0, first, T - 1)
+    live = [(r, t) for r in range(R) for t in range(last[r] + 1)]
+    want_r, _, _ = om.rm_fan(np.ascontiguousarray(np.array([sp[r, t] for r, t in live], np.float32)), FOV, B,
+                             step_coeff=1.0, nthreads=8)
+    want_r = want_r.reshape(len(live), B)
+    ref = L.ref_car_create((C.c_double * 17)(*[RC.DEFAULT_CAR[k] for k in RC.CAR_PARAM_ORDER]))
+    L.ref_car_set_edge_distances(ref, B, -FOV / 2, FOV / B, D_BASE)
+    buf, pose = (C.c_double * 11)(), (C.c_double * 3)()
+    n_crash = 0
+    try:
+        for k, (r, t) in enumerate(live):
+            prev = states[r] if t == 0 else st[r, t - 1]
+            steer_in = 0.0 if t == 0 else float(steers[r, t - 1])
+            L.ref_car_set_state(ref, (C.c_double * 11)(*prev))
+            L.ref_car_control(ref, float(speeds[r]), steer_in)
+            L.ref_car_update_position(ref, 0.01)
+            L.ref_car_get_state(ref, buf)
+            assert np.allclose(st[r, t], np.array(buf), rtol=1e-9, atol=1e-9), (r, t)
+            assert vel[r, t] == st[r, t, 3]
+            L.ref_car_set_state(ref, (C.c_double * 11)(*st[r, t]))
+            L.ref_car_get_scan_pose(ref, D_BASE, pose)
+            assert _within_one_ulp(np.array(pose, np.float64).astype(np.float32), sp[r, t]), (r, t)
+            rays = np.ascontiguousarray(want_r[k])
+            crashed = L.ref_car_is_crashed(ref, rays.ctypes.data_as(C.POINTER(C.c_float)), B, 1) >= 0
+            assert crashed == (first[r] == t), (r, t)
+            if crashed:
+                n_crash += 1
+                assert np.isnan(steers[r, t])
+                continue
+            a = F.ref_followgap_eval(rays.ctypes.data_as(C.POINTER(C.c_float)), B, 10, 15.0, MAX_STEER, 0.004)
+            assert np.float32(a).tobytes() == steers[r, t].tobytes(), (r, t)
+    finally:
+        L.ref_car_destroy(ref)
+    # the states out are the last trace rows
+    assert _same_bits(final, st[np.arange(R), last])
+    assert n_crash == int((first >= 0).sum())
+
+
+def _maze_methods(omap, mrx):
+    return [("RM", range_libc.PyRayMarching(omap, mrx), 0.0),
+            ("RMGPU", range_libc.PyRayMarchingGPU(omap, mrx), 0.05),
+            ("CDDT", range_libc.PyCDDTCast(omap, mrx, 112), 0.0),
+            ("GiantLUT", range_libc.PyGiantLUTCast(omap, mrx, 112), 0.0),
+            ("Bresenham", range_libc.PyBresenhamsLine(omap, mrx), 0.0)]
+
+
+def test_drive_equals_composed_public_calls(oracle_mod):
+    """A 512^2 maze, 256 cars x 40 ticks, five range methods (noise on for RMGPU): the loop equals the same loop
+    built from calc_range_fan, eval_many, is_crashed and rollout(n_steps=1), bit for bit."""
+    g = maps.make_maze(512, cell=40, wall=3, p=0.45, seed=11)
+    mrx = 300
+    om = oracle_mod.OracleMap.from_gridmap(g, mrx)
+    omap = range_libc.PyOMap(g)
+    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    R, T = 256, 40
+    far, sp_far = _starts(g, om.dt, R - 32, 21, 8.0)
+    near, sp_near = _starts(g, om.dt, 32, 22, 1.0)         # next to walls: some crash at once
+    states, speeds = np.concatenate([far, near]), np.concatenate([sp_far, sp_near])
+    steer0 = np.random.default_rng(5).uniform(-0.3, 0.3, R).astype(np.float32)
+    edge = _edge()
+    cars = RC.CarBatch()
+    for name, m, std in _maze_methods(omap, mrx):
+        base = 7 * R * B
+        m.set_noise(std, 99, base)
+        first, final, vel, steers, sp, st = cars.drive_followgap(m, fg, states, T, speeds, FOV, B, edge, THRESH,
+                                                                 steer0=steer0, trace=True)
+        assert (first >= 0).any() and (first < 0).any(), name
+        assert ((first >= 0) | (first == -(T + 1))).all(), name
+        # lidar poses: numpy's f64 formula within one f32 ulp
+        alive_t = np.arange(T)[None, :] <= np.where(first >= 0, first, T)[:, None]
+        x, y, th = st[..., 0][alive_t], st[..., 1][alive_t], st[..., 2][alive_t]
+        want_p = np.stack([x + D_BASE * np.cos(th), y + D_BASE * np.sin(th), th], -1).astype(np.float32)
+        assert _within_one_ulp(want_p, sp[alive_t]), name
+        cur = states.copy()
+        steer = steer0.astype(np.float64)
+        alive = np.ones(R, bool)
+        last_pose = np.zeros((R, 3), np.float32)
+        for t in range(T):
+            # step: rollout(n_steps=1) of the live cars
+            idx = np.nonzero(alive)[0]
+            _, out, v1 = cars.rollout(cur[idx], np.stack([speeds[idx], steer[idx]], -1)[:, None, :], n_steps=1,
+                                      action_every=1)
+            assert _same_bits(out, st[idx, t]) and _same_bits(v1[:, 0], vel[idx, t]), (name, t)
+            cur[idx] = out
+            last_pose[idx] = sp[idx, t]
+            # scan: every car, the frozen ones at their last pose, noise at this tick's ray offset
+            ranges = np.empty(R * B, np.float32)
+            m.set_noise(std, 99, base + t * R * B)
+            m.calc_range_fan(last_pose, ranges, FOV, B)
+            ranges = ranges.reshape(R, B)
+            crashed = np.array([RC.is_crashed(ranges[r], B, 1, edge, THRESH) >= 0 for r in idx])
+            assert (first[idx] == t).tolist() == crashed.tolist(), (name, t)
+            go = idx[~crashed]
+            a = fg.eval_many(np.ascontiguousarray(ranges[go]))
+            assert _same_bits(a, steers[go, t]), (name, t)
+            assert np.isnan(steers[idx[crashed], t]).all()
+            steer[go] = a
+            alive[idx[crashed]] = False
+        m.set_noise(0.0, 0, 0)
+        assert _same_bits(final, cur), name
+
+
+def test_drive_chunking_is_invariant():
+    """T ticks in one call == T/2 + T/2 with the states, the last steer and the noise offset chained."""
+    g = maps.load_colombia()
+    dt = range_libc.PyOMap(g).distance_transform()
+    omap = range_libc.PyOMap(g)
+    m = range_libc.PyRayMarchingGPU(omap, 300)
+    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    R, T, H = 64, 60, 30
+    states, speeds = _starts(g, dt, R, 8, 3.0)
+    edge = _edge()
+    cars = RC.CarBatch()
+    base = 12345
+    m.set_noise(0.05, 4, base)
+    whole = cars.drive_followgap(m, fg, states, T, speeds, FOV, B, edge, THRESH, trace=True)
+    a = cars.drive_followgap(m, fg, states, H, speeds, FOV, B, edge, THRESH, trace=True)
+    ok = a[0] < 0                                               # alive after the first half
+    st0 = np.where(ok, a[3][:, -1], np.float32(0.0)).astype(np.float32)
+    m.set_noise(0.05, 4, base + H * R * B)
+    b = cars.drive_followgap(m, fg, a[1], T - H, speeds, FOV, B, edge, THRESH, steer0=st0, trace=True)
+    m.set_noise(0.0, 0, 0)
+    assert ok.any()
+    # first half: identical for every car
+    for k in range(2, 6):
+        assert _same_bits(whole[k][:, :H], a[k]), k
+    assert (np.where(a[0] >= 0, a[0], -(T + 1)) == np.where(whole[0] < H, whole[0], -(T + 1))).all()
+    # second half: identical for the cars alive at its start
+    assert _same_bits(whole[1][ok], b[1][ok])
+    for k in range(2, 6):
+        assert _same_bits(whole[k][ok, H:], b[k][ok]), k
+    want_first = np.where(b[0][ok] >= 0, b[0][ok] + H, -(T + 1))
+    assert (whole[0][ok] == want_first).all()
+
+
+def test_drive_crash_and_freeze(oracle_mod):
+    """Three hand-built cars in an empty 10 m room: into a wall at 7 m/s, inside the margin, in open space."""
+    g = maps.make_room(200)
+    mrx = 300
+    om = oracle_mod.OracleMap.from_gridmap(g, mrx)
+    m = range_libc.PyRayMarchingGPU(range_libc.PyOMap(g), mrx)
+    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    T = 60
+    states = np.zeros((3, 11))
+    states[0, :4] = (9.1, 5.0, 0.0, 7.0)                         # 0.6 m from the east wall, heading at it
+    states[1, :3] = (0.09, 5.0, math.pi / 2)                     # 4 cm from the west wall: inside the outline
+    states[2, :3] = (5.0, 5.0, 0.3)                              # the middle of the room
+    speeds = np.array([7.0, 1.0, 1.0])
+    edge = _edge()
+    first, final, vel, steers, sp, st = RC.CarBatch().drive_followgap(m, fg, states, T, speeds, FOV, B, edge,
+                                                                      THRESH, trace=True)
+    assert first[1] == 0 and first[2] == -(T + 1) and 0 < first[0] < T, first
+    # the wall car's crash tick from its own trace: the first lidar pose whose oracle scan is inside the outline
+    k = int(first[0])
+    want_r, _, _ = om.rm_fan(np.ascontiguousarray(sp[0, :k + 1]), FOV, B, step_coeff=1.0)
+    assert oracle_mod.is_crashed(want_r, B, k + 1, edge, THRESH) == k
+    for r in (0, 1):
+        t = int(first[r])
+        assert np.isnan(steers[r, t]) and np.isfinite(vel[r, t]) and np.isfinite(st[r, t]).all()
+        assert np.isfinite(steers[r, :t]).all()
+        for arr in (vel, steers, sp, st):
+            assert np.isnan(arr[r, t + 1:]).all()
+        assert _same_bits(final[r], st[r, t])
+    assert np.isfinite(steers[2]).all() and np.isfinite(st[2]).all() and _same_bits(final[2], st[2, -1])
+    assert st[0, first[0], 0] > 9.1                              # it did drive into the wall
+
+
+def test_drive_errors_leave_handles_usable():
+    g = maps.make_maze(512, cell=40, wall=3, p=0.45, seed=11)
+    omap = range_libc.PyOMap(g)
+    dt = omap.distance_transform()
+    m = range_libc.PyRayMarchingGPU(omap, 300)
+    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    cars = RC.CarBatch()
+    R, T = 8, 10
+    states, speeds = _starts(g, dt, R, 2, 8.0)
+    edge = _edge()
+    poses = maps.sample_free_poses(g, 16, 3, 4.0, dt)
+    m.set_noise(0.05, 7, 321)
+    m.set_option("nt_store", 1)
+    scan0 = np.empty(16 * B, np.float32)
+    m.calc_range_fan(poses, scan0, FOV, B)
+    steer0 = fg.eval_many(scan0, B)
+    drive0 = cars.drive_followgap(m, fg, states, T, speeds, FOV, B, edge, THRESH)
+
+    def still_usable():
+        again = np.empty_like(scan0)
+        m.calc_range_fan(poses, again, FOV, B)
+        assert _same_bits(again, scan0)                          # same noise offset, same ranges
+        assert _same_bits(fg.eval_many(scan0, B), steer0)
+        assert m.get_info("nt_store") == 1
+
+    Lb = _lib.lib()
+    f64p, f32p = _lib.f64p, _lib.f32p
+
+    def raw(R_, T_, nr, st_=states, sp_=speeds, ed=edge, h_car=cars._h, h_m=m._h, h_fg=fg._h, first=True):
+        fst = np.zeros(max(R_, 1), np.int32)
+        return Lb.rl_car_drive_followgap(h_car, h_m, h_fg, st_.ctypes.data_as(f64p) if st_ is not None else None,
+                                         sp_.ctypes.data_as(f64p), None, R_, T_, 0.01, D_BASE, FOV, nr,
+                                         ed.ctypes.data_as(f64p), THRESH,
+                                         fst.ctypes.data_as(C.POINTER(C.c_int)) if first else None,
+                                         None, None, None, None, None)
+
+    def expect_error(rc):
+        assert rc != 0
+        with pytest.raises(_lib.ScanLibError):
+            _lib.check(rc)
+        still_usable()
+
+    expect_error(raw(R, T, B, st_=None))                         # null states
+    expect_error(raw(R, T, B, first=False))                      # null first_crashed
+    expect_error(raw(R, T, B, h_fg=None))                        # null handle
+    for T_bad in (0, -3):
+        expect_error(raw(R, T_bad, B))
+        with pytest.raises(_lib.ScanLibError):
+            cars.drive_followgap(m, fg, states, T_bad, speeds, FOV, B, edge, THRESH)
+        still_usable()
+    for nr in (9, 1281):
+        with pytest.raises(_lib.ScanLibError):
+            cars.drive_followgap(m, fg, states, T, speeds, FOV, nr, _edge(nr), THRESH)
+        still_usable()
+    # R num_rays >= 2^31 (refused before anything is read or launched)
+    big = (1 << 31) // 1000 + 1
+    expect_error(raw(big, 1, 1000, st_=np.zeros((big, 11)), sp_=np.ones(big), ed=_edge(1000)))
+    # multi-device handles: refused (single-device only)
+    multi = RC.CarBatch(device=[0])
+    with pytest.raises(_lib.ScanLibError, match="single-device"):
+        multi.drive_followgap(m, fg, states, T, speeds, FOV, B, edge, THRESH)
+    still_usable()
+    # handles on different devices (where a second device exists)
+    if _lib.lib().rl_device_count() >= 2:
+        fg1 = PyFollowGap(10, 15.0, MAX_STEER, 0.004, device=1)
+        with pytest.raises(_lib.ScanLibError, match="device"):
+            cars.drive_followgap(m, fg1, states, T, speeds, FOV, B, edge, THRESH)
+        still_usable()
+    # python-side validation
+    with pytest.raises(ValueError):
+        cars.drive_followgap(m, fg, states.astype(np.float32), T, speeds, FOV, B, edge, THRESH)
+    with pytest.raises(ValueError):
+        cars.drive_followgap(m, fg, states, T, speeds, FOV, B, edge[:-1], THRESH)
+    with pytest.raises(ValueError):
+        cars.drive_followgap(m, fg, states, T, speeds, FOV, B, edge, THRESH, steer0=np.zeros(R))
+    # R = 0 does nothing; the handles still drive as before
+    f0 = cars.drive_followgap(m, fg, states[:0], T, speeds[:0], FOV, B, edge, THRESH)
+    assert f0[0].shape == (0,)
+    again = cars.drive_followgap(m, fg, states, T, speeds, FOV, B, edge, THRESH)
+    for x, y in zip(drive0, again):
+        assert _same_bits(x, y)
+    still_usable()
+
+
+def test_drive_facade_matches_manual_ticks():
+    """RacecarSimulator.driveFollowGapMany (R = 1, 100 ticks) against the reference's tick on the same façade:
+    drive(2.0, s); updatePose(); runScan(); checkCollision() >= 0; s = fg.eval(getScan())."""
+    g = maps.load_colombia()
+    cfg = dict(RC.DEFAULT_CAR)
+    cfg.update(scan_dist_to_base=0.275, batch_size=40, scan_beams=1080, scan_fov=4.71, scan_std=0.01,
+               scan_max_range=15.0, free_thresh=0.8)              # params.yaml:28-39,44-47
+    sim = RacecarSimulator(cfg)
+    omap = range_libc.PyOMap(g)
+    sim.setMap(omap, g.resolution, g.origin)
+    sim.setRaytracingMethod("RMGPU")
+    dt = omap.distance_transform()
+    T = 100
+    for seed in (21, 22, 23):
+        st0 = np.zeros(11)
+        st0[:3] = maps.sample_free_poses(g, 1, seed, 10.0, dt)[0]
+        first, final, vel, steers = sim.driveFollowGapMany(st0[None, :], T, speed=2.0)
+        fg = PyFollowGap(10, 15.0, cfg["max_steer_ang"], 0.004)
+        sim.setState(st0)
+        s, crash = 0.0, -(T + 1)
+        for t in range(T):
+            sim.drive(2.0, s)
+            sim.updatePose()
+            sim.runScan()
+            if sim.checkCollision() >= 0:
+                crash = t
+                break
+            s = fg.eval(sim.getScan(), cfg["scan_beams"])
+        assert first[0] == crash, seed
+        assert np.abs(final[0, :2] - sim.getState()[:2]).max() < 1e-6, seed
+        assert vel.shape == (1, T) and steers.shape == (1, T)
