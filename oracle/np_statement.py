@@ -316,3 +316,51 @@ def cddt_fan(table, resolution, origin, max_range_px, poses, fov, num_rays):
     th = (thg[:, None] + alpha[None, :]).astype(f32).ravel()
     r = table.query(np.repeat(gx, num_rays), np.repeat(gy, num_rays), th, max_range_px)
     return (r * f32(resolution)).astype(f32)
+
+
+# ---- row a15: the Gaussian range noise (csrc/scan_device.h gauss_noise) ----------------------------------------
+PHILOX_M = 0xD256D193
+PHILOX_W = 0x9E3779B9
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def noise_key(seed):
+    """The 64-bit seed folded to the 32-bit Philox key: lo ^ (hi * 0x85EBCA6B) mod 2^32."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return ((seed & 0xFFFFFFFF) ^ (((seed >> 32) * 0x85EBCA6B) & 0xFFFFFFFF)) & 0xFFFFFFFF
+
+
+def philox2x32_10(c0, c1, key):
+    """Philox-2x32 with 10 rounds (Salmon et al. 2011) on arrays of counters; the key is used as is.
+    Returns the two output words as uint64 arrays holding 32-bit values."""
+    c0 = np.asarray(c0, np.uint64) & _M32
+    c1 = np.asarray(c1, np.uint64) & _M32
+    k = int(key) & 0xFFFFFFFF
+    for _ in range(10):
+        prod = np.uint64(PHILOX_M) * c0                      # < 2^64: exact in uint64
+        c0, c1 = (prod >> np.uint64(32)) ^ np.uint64(k) ^ c1, prod & _M32
+        k = (k + PHILOX_W) & 0xFFFFFFFF
+    return c0, c1
+
+
+def box_muller(c0, c1):
+    """The device's uniforms (exact in float32) and Box-Muller in float64:
+    u1 = ((c0 >> 8) + 1) 2^-24 in (0, 1], u2 = (c1 >> 8) 2^-24 in [0, 1), g = sqrt(-2 ln u1) cos(2 pi u2)."""
+    u1 = ((np.asarray(c0, np.uint64) >> np.uint64(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+    u2 = (np.asarray(c1, np.uint64) >> np.uint64(8)).astype(np.float64) * 2.0 ** -24
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+
+def gauss_noise_ref(seed, ray_ids, return_counters=False):
+    """The normal the device adds to ray ``ray_id``'s range (times the noise std): counter = the 64-bit ray id
+    (wrapping mod 2^64, as the device's uint64 sum does), key = the folded seed.  float64 array; with
+    ``return_counters`` also the Philox output words (c0, c1)."""
+    ids = np.asarray(ray_ids, np.uint64)
+    c0, c1 = philox2x32_10(ids & _M32, ids >> np.uint64(32), noise_key(seed))
+    g = box_muller(c0, c1)
+    return (g, (c0, c1)) if return_counters else g
+
+
+def fan_ray_ids(ray_offset, n_poses, num_rays):
+    """Global ray ids of a fan launch: ray_offset + pose * num_rays + j (mod 2^64), pose-major."""
+    return np.uint64(int(ray_offset) & 0xFFFFFFFFFFFFFFFF) + np.arange(int(n_poses) * int(num_rays), dtype=np.uint64)

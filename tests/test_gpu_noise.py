@@ -1,0 +1,481 @@
+"""Gaussian range noise against an independent statement of the generator.
+
+Every kernel that adds noise computes ``gauss_noise(seed, ray_id)`` (csrc/scan_device.h) with its own
+global ray id.  The contract: a fan's ray ``j`` of the caller's pose ``p`` is ``ray_offset + p * num_rays + j``,
+the many-rays calls' row ``i`` is ``ray_offset + i`` (mod 2^64).  ``check_noise`` scans clean (bit-equal to
+the CPU oracle), then with std 1 and 0.01, and requires every noisy range to be the clean range plus
+``std * g`` for the oracle's Philox-2x32-10 / Box-Muller normal ``g`` of that id (oracle/np_statement.py
+``gauss_noise_ref``), up to the rounding of the sum and ``EPS_G`` for the device's log / cos estimates.
+A ray keyed by any other id is off by ~1 at std 1.  NOISE_SITES names the case that reaches each call site;
+tests/test_host.py keeps it in step with the sources."""
+import numpy as np
+import pytest
+
+from oracle import np_statement as N
+from pyracecarsimulator_amd import _lib, maps, range_libc, workloads
+
+#: bound on |g_device - g_ref| (the hardware log2 / cos estimates in Box-Muller): the MI355X was observed at
+#: 2.0e-6 over this module, the schedules and the fuzz (``max_dg``); a ray keyed by a wrong id is off by ~1
+EPS_G = 2e-5
+
+#: every ``gauss_noise(`` call under csrc/: (file, kernel, the case here that asserts it ran that kernel)
+NOISE_SITES = [
+    ("rm_kernels.h", "rm_fan_kernel", "test_noise_rm_chunk_and_rays_kernels; test_gpu_parity schedules variant 0"),
+    ("rm_kernels.h", "rm_rays_kernel", "test_noise_many_rays_entry_points (RMGPU variant 0)"),
+    ("rm_kernels.h", "rm_fan_stream_kernel (2-3 slots)", "test_gpu_parity::test_every_kernel_schedule_is_bit_identical slots 2/3"),
+    ("rm_kernels.h", "rm_fan_stream_kernel (1 slot)", "test_gpu_parity schedules variant 1; test_noise_literal_kernels"),
+    ("rm_kernels.h", "rm_leftover_kernel", "test_gpu_parity schedules handoff; test_noise_consumers_of_noisy_ranges"),
+    ("bl_kernels.h", "bl_fan_kernel", "test_noise_bresenham_kernels (bl_lds, mrx 300 / 700)"),
+    ("bl_kernels.h", "occ_fan_lds_kernel", "test_noise_bresenham_kernels (occ_lds)"),
+    ("bl_kernels.h", "bl_fan_stream_kernel", "test_noise_bresenham_kernels (bl_stream)"),
+    ("bl_kernels.h", "bl_rays_kernel", "test_noise_many_rays_entry_points (Bresenham)"),
+    ("lut_kernels.h", "lut_fan_kernel", "test_noise_giant_lut_kernels (lut_fan)"),
+    ("lut_kernels.h", "lut_fan_lds_kernel (general statement)", "test_noise_giant_lut_kernels (lut_lds)"),
+    ("lut_kernels.h", "lut_rays_kernel", "test_noise_many_rays_entry_points (GiantLUT)"),
+    ("cddt_kernels.h", "cddt_fan_bins_kernel", "test_noise_cddt_kernels (cddt_bins, cddt_sort 0 / 1)"),
+    ("cddt_kernels.h", "cddt_theta_fan_group", "test_noise_cddt_kernels (cddt_theta, aligned / +4 B output)"),
+    ("cddt_kernels.h", "cddt_fan_kernel", "test_noise_cddt_kernels (cddt_rays)"),
+    ("cddt_kernels.h", "cddt_rays_kernel", "test_noise_many_rays_entry_points (CDDT)"),
+    ("literal_kernels.h", "rm_literal_kernel", "test_noise_literal_kernels; test_noise_many_rays_entry_points (variant 3)"),
+]
+
+pytestmark = pytest.mark.gpu
+
+SEED_HI = 0x9E3779B97F4A7C15           # a seed whose high word matters (the fold)
+_MAX_DG = [0.0]
+
+
+def max_dg():
+    """The largest |g_device - g_ref| seen so far (beyond the rounding of range + std g), over every check_noise."""
+    return _MAX_DG[0]
+
+
+def noise_mismatch(noisy, clean, std, g_ref, eps_g=EPS_G):
+    """Indices of rays whose noise is not std * g_ref (NaN positions must match, finite ones agree to
+    ulp(noisy) + std * eps_g); records the observed excess in units of g."""
+    noisy = np.asarray(noisy, np.float32)
+    clean = np.asarray(clean, np.float32)
+    nan = np.isnan(noisy)
+    bad = np.flatnonzero(nan != np.isnan(clean))
+    if bad.size:
+        return bad
+    ok = ~nan
+    d = np.abs(noisy[ok].astype(np.float64) - clean[ok].astype(np.float64) - std * g_ref[ok])
+    ulp = np.spacing(np.abs(noisy[ok])).astype(np.float64)
+    if d.size:
+        _MAX_DG[0] = max(_MAX_DG[0], float(np.max(np.maximum(d - ulp, 0.0)) / std))
+    return np.flatnonzero(ok)[d > ulp + std * eps_g]
+
+
+def check_noise(m, poses, fov, num_rays, want, seed, offset, stds=(1.0, 0.01), scan=None, ids=None,
+                kernel=None, name=None, what=""):
+    """Noise of handle ``m`` on one launch shape against the reference.
+
+    ``scan()`` launches with the handle's current noise and returns the float32 ranges (default: calc_range_fan of
+    ``poses``); ``want`` the oracle's clean ranges (None: only for the approximate occ_lds kernel); ``ids`` the global
+    ray id of every output (default ``offset + arange``); ``kernel`` / ``name`` what last_plan() must report after
+    each launch.  Returns the clean ranges."""
+    if scan is None:
+        P = len(poses)
+
+        def scan():
+            out = np.full(P * num_rays, -7.0, np.float32)
+            m.calc_range_fan(poses, out, fov, num_rays)
+            return out
+
+    def ran(tag):
+        if kernel is None and name is None:
+            return
+        pl = m.last_plan()
+        assert kernel is None or pl["kernel"] == kernel, (what, tag, pl["kernel"], pl["name"])
+        assert name is None or name in pl["name"], (what, tag, pl["name"])
+
+    m.set_noise(0.0, seed, offset)
+    clean = scan()
+    ran("clean")
+    if want is not None:
+        assert np.array_equal(clean.view(np.uint32), np.asarray(want, np.float32).view(np.uint32)), \
+            (what, "clean ranges differ from the oracle", int((clean != want).sum()))
+    if ids is None:
+        ids = N.fan_ray_ids(offset, clean.size, 1)
+    g = N.gauss_noise_ref(seed, ids)
+    try:
+        for std in stds:
+            m.set_noise(std, seed, offset)
+            noisy = scan()
+            ran("std %g" % std)
+            bad = noise_mismatch(noisy, clean, std, g)
+            assert bad.size == 0, (what, "std %g seed %#x offset %#x: %d rays off, first %s: got %r clean %r ref %r"
+                                   % (std, seed, offset, bad.size, bad[:4].tolist(), noisy[bad[:4]].tolist(),
+                                      clean[bad[:4]].tolist(), (std * g[bad[:4]]).tolist()))
+    finally:
+        m.set_noise(0.0, 0, 0)
+    return clean
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _gpu(need_gpu):
+    yield
+    print("\nnoise: max |g_device - g_ref| beyond rounding over this module: %.3g (EPS_G %.3g)" % (max_dg(), EPS_G))
+
+
+def _maze(oracle_mod, mrx=300):
+    g = maps.make_maze(400, cell=40, wall=3, p=0.45, seed=21, origin=(-7.0, 3.0, -0.4))
+    om = oracle_mod.OracleMap.from_gridmap(g, mrx)
+    poses = maps.sample_free_poses(g, 301, 4, dt=om.dt)
+    poses[17] = [np.nan, 0, 0]
+    poses[200] = [1e6, 1e6, 1.0]                          # outside the map
+    return g, om, range_libc.PyOMap(g), poses
+
+
+def _fan(m, poses, fov, B, aux):
+    n = len(poses) * B
+    out = np.full(n, -7.0, np.float32)
+    if aux:
+        m.calc_range_fan(poses, out, fov, B, hit_cells=np.empty((n, 2), np.int32), steps=np.empty(n, np.uint16))
+    else:
+        m.calc_range_fan(poses, out, fov, B)
+    return out
+
+
+def test_noise_rm_chunk_and_rays_kernels(oracle_mod):
+    g, om, omap, poses = _maze(oracle_mod)
+    want = om.rm_fan(poses, 4.71, 1081, step_coeff=1.0, nthreads=4)[0]
+    m = range_libc.PyRayMarchingGPU(omap, 300)
+    m.set_option("variant", 0)
+    for aux in (False, True):
+        check_noise(m, poses, 4.71, 1081, want, SEED_HI, 12345, scan=lambda: _fan(m, poses, 4.71, 1081, aux),
+                    kernel="rm_chunk", name="rm_fan_kernel<%s" % ("true" if aux else "false"), what="rm_chunk")
+
+
+def test_noise_many_rays_entry_points(oracle_mod):
+    """The 2-argument calc_range_many (row i -> ray_offset + i) and the fork's sparse 4-argument form (pose p in row
+    p * num_rays): rm_rays_kernel, rm_literal_kernel<.., true>, the stream kernel, bl / lut / cddt rays kernels."""
+    g, om, omap, poses = _maze(oracle_mod)
+    rng = np.random.default_rng(5)
+    ins = poses[rng.integers(0, len(poses), 20000)].copy()
+    ins[:, 2] = rng.uniform(-8, 8, len(ins)).astype(np.float32)
+    P, B, fov = 40, 257, 4.71
+    sparse = np.zeros((P * B, 3), np.float32)
+    sparse[::B] = poses[:P]
+
+    def rows(m):
+        out = np.full(len(ins), -7.0, np.float32)
+        m.calc_range_many(ins, out)
+        return out
+
+    def fan_rows(m):
+        out = np.full(P * B, -7.0, np.float32)
+        m.calc_range_many(sparse, out, fov, B)
+        return out
+
+    small = maps.make_maze(56, cell=14, wall=2, p=0.5, seed=3, origin=(2.0, -1.5, -0.3))
+    oms = oracle_mod.OracleMap.from_gridmap(small, 60)
+    smap = range_libc.PyOMap(small)
+    sposes = maps.sample_free_poses(small, P, 6)
+    sins = sposes[rng.integers(0, P, 5000)].copy()
+    sins[:, 2] = rng.uniform(-8, 8, len(sins)).astype(np.float32)
+    lut = oms.lut_build(180, nthreads=oracle_mod.max_threads())
+    cases = [
+        ("RMGPU v0", range_libc.PyRayMarchingGPU(omap, 300), {"variant": 0}, om.rm_rays(ins, 1.0)[0],
+         om.rm_fan(poses[:P], fov, B, 1.0)[0]),
+        ("RMGPU v1", range_libc.PyRayMarchingGPU(omap, 300), {"variant": 1}, om.rm_rays(ins, 1.0)[0],
+         om.rm_fan(poses[:P], fov, B, 1.0)[0]),
+        ("RM literal", range_libc.PyRayMarching(omap, 300), {}, om.rm_rays_libm(ins, 0.999),
+         om.rm_fan_libm(poses[:P], fov, B, 0.999)[0]),
+        ("BL", range_libc.PyBresenhamsLine(omap, 300), {}, om.bl_rays(ins)[0], om.bl_fan(poses[:P], fov, B)[0]),
+        ("CDDT", range_libc.PyCDDTCast(omap, 300, 112), {}, om.cddt_rays(112, ins), om.cddt_fan(112, poses[:P], fov, B)),
+    ]
+    for what, m, opts, want_rows, want_fan in cases:
+        for k, v in opts.items():
+            m.set_option(k, v)
+        check_noise(m, None, None, None, want_rows, SEED_HI, 2 ** 32 - 7000, scan=lambda: rows(m), what=what + " rows")
+        if what == "RMGPU v1":
+            assert m.last_plan()["kernel"] == "rm_stream"             # (a ray is a one-beam fan)
+        check_noise(m, None, None, None, want_fan, 77, 999, scan=lambda: fan_rows(m), what=what + " sparse fan")
+        m.close()
+    m = range_libc.PyGiantLUTCast(smap, 60, 180)
+    out = np.empty(len(sins), np.float32)
+
+    def lut_rows():
+        m.calc_range_many(sins, out)
+        return out.copy()
+    check_noise(m, None, None, None, oms.lut_rays(lut, sins), SEED_HI, 5, scan=lut_rows, what="LUT rows")
+    sp = np.zeros((P * B, 3), np.float32)
+    sp[::B] = sposes
+    o2 = np.empty(P * B, np.float32)
+
+    def lut_fan_rows():
+        m.calc_range_many(sp, o2, fov, B)
+        return o2.copy()
+    check_noise(m, None, None, None, oms.lut_fan(lut, sposes, fov, B), SEED_HI, 3, scan=lut_fan_rows, what="LUT sparse")
+
+
+def test_noise_literal_kernels(oracle_mod):
+    """PyRayMarching's default arithmetic (variant 3): rm_literal_kernel for fans below 64 beams and with diagnostics,
+    the stream form rm_stream_literal (one and two rays per lane), and a batch beyond one INLINE launch in pose slices
+    of 4096 (the host shifts ray_offset per slice)."""
+    g, om, omap, poses = _maze(oracle_mod)
+    m = range_libc.PyRayMarching(omap, 300)
+    assert m.get_info("variant") == 3
+    w40 = om.rm_fan_libm(poses, 4.71, 40, step_coeff=0.999)[0]
+    check_noise(m, poses, 4.71, 40, w40, SEED_HI, 2 ** 32 - 6000, kernel="rm_literal", what="literal B<64")
+    w = om.rm_fan_libm(poses, 4.71, 1081, step_coeff=0.999)[0]
+    check_noise(m, poses, 4.71, 1081, w, 31, 1 << 40, scan=lambda: _fan(m, poses, 4.71, 1081, True),
+                kernel="rm_literal", name="rm_literal_kernel<true", what="literal aux")
+    for slots in (1, 2):
+        m.set_option("slots", slots)
+        check_noise(m, poses, 4.71, 1081, w, SEED_HI, 2 ** 32 - 150000, kernel="rm_stream_literal",
+                    name=", %d, true" % slots, what="literal stream slots %d" % slots)
+    m.close()
+    wl = workloads.cfg2()
+    big = range_libc.PyOMap(wl.gmap)
+    omb = oracle_mod.OracleMap.from_gridmap(wl.gmap, wl.max_range_px)
+    n, Bs = 9000, 64
+    bp = np.ascontiguousarray(workloads.make_poses(wl, dt=omb.dt, n_poses=n, seed=78))
+    m = range_libc.PyRayMarchingGPU(big, wl.max_range_px)
+    m.set_option("variant", 3)
+    pl = m.plan_fan(n, Bs)
+    assert pl["kernel"] == "rm_stream_literal" and pl["slices"] == 3 and pl["slice_poses"] == 4096, pl
+    check_noise(m, bp, 2.0, Bs, omb.rm_fan_libm(bp, 2.0, Bs, step_coeff=1.0)[0], SEED_HI, 2 ** 32 - n * Bs // 2,
+                kernel="rm_stream_literal", what="literal INLINE slices")
+    m.close()
+
+
+def test_noise_bresenham_kernels(oracle_mod):
+    for mrx in (300, 700):                                 # 700: the window exceeds the LDS
+        g = maps.make_maze(300, cell=30, wall=2, p=0.5, seed=mrx, origin=(2.0, -1.0, 0.35))
+        om = oracle_mod.OracleMap.from_gridmap(g, mrx)
+        omap = range_libc.PyOMap(g)
+        poses = maps.sample_free_poses(g, 299, 3)
+        poses[3] = [np.nan, 0, 0]
+        poses[5] = [g.origin[0] - 0.01, g.origin[1] - 0.01, 0.8]
+        want = om.bl_fan(poses, 4.71, 1081)[0]
+        m = range_libc.PyBresenhamsLine(omap, mrx)
+        for variant, kernel in ((0, "bl_lds"), (1, "bl_stream")):
+            m.set_option("variant", variant)
+            for aux in (False, True):
+                check_noise(m, poses, 4.71, 1081, want, SEED_HI, 2 ** 32 - 160000,
+                            scan=lambda: _fan(m, poses, 4.71, 1081, aux), kernel=kernel,
+                            what="BL v%d mrx %d aux %d" % (variant, mrx, aux))
+        m.close()
+    # occ_lds (variant 2, approximate: within one cell of ray marching) — the north-star shape; its noise is still exact
+    from conftest import load_golden
+    g, z = load_golden("rm_maze256")
+    m = range_libc.PyRayMarchingGPU(range_libc.PyOMap(g), 300)
+    m.set_option("variant", 2)
+    check_noise(m, z["poses"], 4.71, 1081, None, SEED_HI, 2 ** 64 - 1000, kernel="occ_lds", what="occ_lds")
+    m.close()
+
+
+def test_noise_giant_lut_kernels(oracle_mod):
+    """lut_fan (rows wider than three 16-B loads per lane) and lut_lds, whose noisy launch leaves the fast path for the
+    general statement — with a pose outside the map, which takes that path with noise off too."""
+    g = maps.make_maze(56, cell=14, wall=2, p=0.5, seed=9, origin=(2.0, -1.5, -0.3))
+    om = oracle_mod.OracleMap.from_gridmap(g, 60)
+    omap = range_libc.PyOMap(g)
+    poses = maps.sample_free_poses(g, 299, 7)
+    for td, kernel in ((180, "lut_lds"), (720, "lut_lds"), (2000, "lut_fan")):
+        m = range_libc.PyGiantLUTCast(omap, 60, td)
+        lut = om.lut_build(td, nthreads=oracle_mod.max_threads())
+        for outside in (False, True):
+            p = poses.copy()
+            if outside:
+                p[0] = [-50.0, 0.0, 0.0]
+                p[1] = [np.nan, 0.0, 0.0]
+            check_noise(m, p, 4.71, 1081, om.lut_fan(lut, p, 4.71, 1081), SEED_HI, 2 ** 32 - 150000 - td,
+                        kernel=kernel, what="LUT td %d outside %d" % (td, outside))
+        m.close()
+
+
+def test_noise_cddt_kernels(oracle_mod):
+    """cddt_bins (pose taken from the binning order, sorted and not), cddt_theta's fan group on an aligned output
+    (16-B run stores) and on an output 4 B off alignment (beam by beam; through the device-pointer entry, as a host
+    output may be staged through an aligned buffer), search + fan fused, and the per-ray cddt_fan_kernel."""
+    torch = pytest.importorskip("torch")
+    g, om, omap, poses = _maze(oracle_mod)
+    B, fov, td = 1081, 4.71, 112
+    want = om.cddt_fan(td, poses, fov, B)
+    m = range_libc.PyCDDTCast(omap, 300, td)
+    for sort in (1, 0):
+        m.set_option("cddt_sort", sort)
+        check_noise(m, poses, fov, B, want, SEED_HI, 2 ** 32 - 160000, kernel="cddt_bins", what="cddt_bins sort %d" % sort)
+    m.set_option("cddt_sort", 1)
+    m.set_option("cddt_theta_min", 1)
+    d_poses = torch.from_numpy(np.ascontiguousarray(poses)).cuda()
+    n = len(poses) * B
+    d_out = torch.empty(n + 8, dtype=torch.float32, device="cuda")
+    for search, kname in ((1, "cddt_theta_search2_kernel"), (2, "cddt_theta_fused_kernel")):
+        m.set_option("cddt_search", search)
+        check_noise(m, poses, fov, B, want, SEED_HI, 2 ** 32 - 160000, kernel="cddt_theta", name=kname,
+                    what="cddt_theta host")
+        for shift in (0, 1):                           # (torch's allocation is 256-B aligned: +0 aligned, +4 B not)
+            assert (d_out.data_ptr() + 4 * shift) % 16 == 4 * shift
+
+            def dev_scan():
+                d_out.fill_(-7.0)
+                m.calc_range_fan_device(d_poses.data_ptr(), len(poses), fov, B, d_out.data_ptr() + 4 * shift)
+                torch.cuda.synchronize()
+                return d_out[shift:shift + n].cpu().numpy()
+            check_noise(m, poses, fov, B, want, 0xFFFFFFFF00000001, 2 ** 32 - 1000 * shift - 7, scan=dev_scan,
+                        kernel="cddt_theta", name=kname, what="cddt_theta device +%d B" % (4 * shift))
+    m.set_option("cddt_theta_min", 32768)
+    m.set_option("cddt_bins", 0)                       # the per-ray fan kernel (cddt_rays)
+    check_noise(m, poses, fov, B, want, SEED_HI, 2 ** 32 - 160000, kernel="cddt_rays", name="cddt_fan_kernel",
+                what="cddt_fan_kernel")
+    m.set_option("cddt_bins", 1)                       # ... and where theta_disc exceeds the fan's beams
+    w64 = om.cddt_fan(td, poses, fov, 64)
+    check_noise(m, poses, fov, 64, w64, SEED_HI, 11, kernel="cddt_rays", what="cddt_rays td > B")
+    m.close()
+
+
+def test_noise_host_slicing(oracle_mod):
+    """Host bookkeeping of ray_offset: pose slices (slice_log2), the pinned / overlap path's four slices (pageable and
+    pinned outputs), pose counts that do not divide by four."""
+    g, om, omap, poses = _maze(oracle_mod)
+    m = range_libc.PyRayMarchingGPU(omap, 300)
+    want = om.rm_fan(poses, 4.71, 1081, step_coeff=1.0, nthreads=4)[0]
+    for sl in (14, 13):
+        m.set_option("slice_log2", sl)
+        assert m.plan_fan(len(poses), 1081)["slices"] > 1
+        check_noise(m, poses, 4.71, 1081, want, SEED_HI, 2 ** 32 - 160000, kernel="rm_stream", what="slice_log2 %d" % sl)
+    m.set_option("slice_log2", 30)
+    m.set_option("direct_max_rays", 0)
+    m.set_option("overlap_min_rays", 1)
+    for n in (301, 7, 5):
+        p = poses[:n]
+        w = want[:n * 1081]
+        for pinned in (False, True):
+            out = _lib.pinned_zeros(n * 1081, np.float32) if pinned else np.zeros(n * 1081, np.float32)
+
+            def scan():
+                out[:] = -7.0
+                m.calc_range_fan(p, out, 4.71, 1081)
+                return out.copy()
+            check_noise(m, p, 4.71, 1081, w, SEED_HI, 2 ** 32 - n * 540, scan=scan, what="overlap n %d pinned %d" % (n, pinned))
+    m.close()
+
+
+def test_noise_id_and_seed_edges(oracle_mod):
+    """Ids that straddle 2^32 (the counter's high word), ids that wrap past 2^64, seeds that differ in the high word
+    only, and std 0 / -0 / negative / NaN (no noise: the clean bits)."""
+    g, om, omap, poses = _maze(oracle_mod)
+    n = len(poses) * 1081
+    for cls, sc in ((range_libc.PyRayMarchingGPU, 1.0), (range_libc.PyRayMarching, 0.999)):
+        want = om.rm_fan(poses, 4.71, 1081, step_coeff=sc, nthreads=4)[0]
+        m = cls(omap, 300)
+        if cls is range_libc.PyRayMarching:
+            m.set_option("variant", 1)
+            m.set_option("slots", 2)
+        for seed, off in ((SEED_HI, 2 ** 32 - n // 2), (SEED_HI, 2 ** 64 - n // 2), (0, 0), (1 << 32, 0),
+                          (2 << 32, 0), (0xFFFFFFFFFFFFFFFF, 2 ** 64 - 1)):
+            check_noise(m, poses, 4.71, 1081, want, seed, off, kernel="rm_stream", what="%s seed %#x off %#x" % (cls.__name__, seed, off))
+        for std in (0.0, -0.0, -0.5, float("nan")):
+            m.set_noise(std, SEED_HI, 2 ** 32 - n // 2)
+            out = _fan(m, poses, 4.71, 1081, False)
+            assert np.array_equal(out.view(np.uint32), want.view(np.uint32)), (cls.__name__, std)
+        m.set_noise(0.0)
+        m.close()
+    # the fold: seeds equal in the low word but not the high word give different noise
+    m = range_libc.PyRayMarchingGPU(omap, 300)
+    outs = []
+    for seed in (5, 5 + (1 << 32)):
+        m.set_noise(1.0, seed, 0)
+        outs.append(_fan(m, poses, 4.71, 1081, False))
+    assert float(np.mean(outs[0] != outs[1])) > 0.99
+    m.close()
+
+
+def test_noise_consumers_of_noisy_ranges(oracle_mod):
+    """check_collision_many / check_collision_groups with noise on (RMGPU one and two rays per lane, with and without
+    the hand-off, and the literal stream form): the ranges they return are the noisy calc_range_fan at the same offset,
+    their crash indices the oracle's f64 isCrashed over those ranges; rl_car_rollout_check equals rollout, then a noisy
+    calc_range_fan at the same offset, then isCrashed."""
+    from pyracecarsimulator_amd import racecar as RC
+    g, om, omap, _ = _maze(oracle_mod)
+    B, fov, grp = 1081, 4.71, 20
+    poses = np.concatenate([maps.sample_free_poses(g, 150, 12, 6.0, om.dt), maps.sample_free_poses(g, 150, 13, 0.5, om.dt)])
+    edge = RC.edge_distances(B, -fov / 2, fov / B, 0.275, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
+    thr = 0.001
+    for cls, opts, sc in ((range_libc.PyRayMarchingGPU, {"slots": 1}, 1.0), (range_libc.PyRayMarchingGPU, {"slots": 2}, 1.0),
+                          (range_libc.PyRayMarchingGPU, {"slots": 2, "handoff": 1, "handoff_cap": 8}, 1.0),
+                          (range_libc.PyRayMarching, {"slots": 2}, 0.999)):
+        m = cls(omap, 300)
+        for k, v in opts.items():
+            m.set_option(k, v)
+        want = (om.rm_fan_libm(poses, fov, B, step_coeff=sc)[0] if cls is range_libc.PyRayMarching
+                else om.rm_fan(poses, fov, B, step_coeff=sc, nthreads=4)[0])
+        kernel = "rm_stream_literal" if cls is range_libc.PyRayMarching else "rm_stream"
+        check_noise(m, poses, fov, B, want, SEED_HI, 2 ** 32 - 160000, kernel=kernel, what="consumer fan %s" % opts)
+        for std in (1.0, 0.01):
+            m.set_noise(std, SEED_HI, 2 ** 32 - 160000)
+            fan = _fan(m, poses, fov, B, False)
+            r1 = np.full(fan.size, -7.0, np.float32)
+            code = m.check_collision_many(poses, fov, B, edge, thr, ranges=r1)
+            assert np.array_equal(r1.view(np.uint32), fan.view(np.uint32)), (opts, std)
+            assert code == oracle_mod.is_crashed(fan, B, len(poses), edge, thr), (opts, std)
+            r2 = np.full(fan.size, -7.0, np.float32)
+            first = m.check_collision_groups(poses, grp, fov, B, edge, thr, ranges=r2)
+            assert np.array_equal(r2.view(np.uint32), fan.view(np.uint32)), (opts, std)
+            ref = [oracle_mod.is_crashed(fan[q * grp * B:(q + 1) * grp * B], B, grp, edge, thr) for q in range(len(poses) // grp)]
+            assert first.tolist() == ref, (opts, std)
+        m.set_noise(0.0)
+        m.close()
+    # roll-outs: integrate, scan with noise, test — one call
+    m = range_libc.PyRayMarchingGPU(omap, 300)
+    rng = np.random.default_rng(9)
+    R, n_steps = 6, 50
+    states = np.zeros((R, 11))
+    states[:, :3] = maps.sample_free_poses(g, R, 5, 4.0, om.dt)
+    states[:, 3] = rng.uniform(0, 3, R)
+    actions = np.stack([rng.uniform(0, 7, (R, 5)), rng.uniform(-0.4189, 0.4189, (R, 5))], -1)
+    cars = RC.CarBatch()
+    p, _, _ = cars.rollout(states, actions, n_steps=n_steps)
+    p = p.reshape(-1, 3)
+    clean = check_noise(m, p, fov, B, om.rm_fan(p, fov, B, step_coeff=1.0, nthreads=4)[0], SEED_HI, 2 ** 32 - 100000,
+                        what="roll-out poses")
+    for std in (0.0, 1.0, 0.05):
+        m.set_noise(std, SEED_HI, 2 ** 32 - 100000)
+        first, _, _ = cars.rollout_check(m, states, actions, fov, B, edge, thr, n_steps=n_steps)
+        fan = _fan(m, p, fov, B, False)
+        if std == 0.0:
+            assert np.array_equal(fan, clean)
+        want = [oracle_mod.is_crashed(fan[r * n_steps * B:(r + 1) * n_steps * B], B, n_steps, edge, thr) for r in range(R)]
+        assert first.tolist() == want, std
+    m.set_noise(0.0)
+    m.close()
+
+
+def test_noise_multi_device_blocks(oracle_mod):
+    """One handle over device 0 three times: the batch cut into pose blocks, each replica's ray offset the parent's plus
+    its block's first ray — fans, the sparse 4-argument rows, ids across 2^32."""
+    g, om, _, poses = _maze(oracle_mod)
+    multi = range_libc.PyOMap(g, device=[0, 0, 0])
+    B, fov = 1081, 4.71
+    for cls, ofun in ((range_libc.PyRayMarchingGPU, lambda p, b: om.rm_fan(p, fov, b, step_coeff=1.0, nthreads=4)[0]),
+                      (range_libc.PyBresenhamsLine, lambda p, b: om.bl_fan(p, fov, b)[0])):
+        m = cls(multi, 300)
+        m.set_option("multi_min_poses", 64)
+        assert m.n_devices == 3
+        check_noise(m, poses, fov, B, ofun(poses, B), SEED_HI, 2 ** 32 - 160000, what="multi %s" % cls.__name__)
+        P, Bs = 200, 65
+        sparse = np.zeros((P * Bs, 3), np.float32)
+        sparse[::Bs] = poses[:P]
+
+        def rows():
+            out = np.full(P * Bs, -7.0, np.float32)
+            m.calc_range_many(sparse, out, fov, Bs)
+            return out
+        check_noise(m, None, None, None, ofun(poses[:P], Bs), SEED_HI, 2 ** 64 - 6500, scan=rows,
+                    what="multi sparse %s" % cls.__name__)
+        ins = sparse[::5].copy()
+        ins[:, 2] = np.linspace(-6.0, 6.0, len(ins), dtype=np.float32)
+
+        def rays():
+            out = np.full(len(ins), -7.0, np.float32)
+            m.calc_range_many(ins, out)
+            return out
+        want_rays = om.rm_rays(ins, 1.0)[0] if cls is range_libc.PyRayMarchingGPU else om.bl_rays(ins)[0]
+        check_noise(m, None, None, None, want_rays, SEED_HI, 2 ** 32 - 1000, scan=rays, what="multi rays %s" % cls.__name__)
+        m.close()
+    multi.close()

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLD, load_golden
+from test_gpu_noise import SEED_HI, check_noise
 from pyracecarsimulator_amd import ScanSimulator2D, _lib, maps, range_libc, workloads
 
 pytestmark = pytest.mark.gpu
@@ -120,6 +121,12 @@ def test_every_kernel_schedule_is_bit_identical(oracle_mod, opts):
         r1 = np.empty_like(r)
         m.calc_range_fan(poses, r1, 4.71, 1081)
         assert np.array_equal(r1, r0)
+        # ... and its noise, and that of the diagnostics launch, keyed by the caller's global ray id (ids across 2^32)
+        kernel = "rm_chunk" if opts["variant"] == 0 else "rm_stream"
+        off = 2 ** 32 - len(r0) // 2
+        check_noise(m, poses, 4.71, 1081, r0, SEED_HI, off, kernel=kernel, what=("ranges-only", opts))
+        check_noise(m, poses, 4.71, 1081, r0, SEED_HI, off, scan=lambda: _fan(m, poses, 4.71, 1081)[0],
+                    kernel=kernel, what=("aux", opts))
         # small batches take the unsorted single-band path
         r, h, s = _fan(m, poses[:5], 4.71, 70)
         r0, h0, s0 = om.rm_fan(poses[:5], 4.71, 70, step_coeff=sc)

@@ -466,3 +466,25 @@ def test_kernel_register_budgets_are_a_build_gate(tmp_path):
         (d / f).write_text(open(os.path.join(obj, f), errors="replace").read())
     r = subprocess.run([sys.executable, chk, str(d)], capture_output=True, text=True)
     assert r.returncode == 1 and "vgpr = 65" in r.stderr and "occupancy = 7" in r.stderr, r.stderr[-1500:]
+
+
+def test_every_noise_call_site_has_a_gpu_case():
+    """tests/test_gpu_noise.py NOISE_SITES names the case that checks each gauss_noise( call against the reference
+    generator: a kernel that adds noise anywhere else must add a row (and a case) there."""
+    from test_gpu_noise import NOISE_SITES
+    csrc = os.path.join(ROOT, "pyracecarsimulator_amd", "csrc")
+    found = {}
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".h", ".hip", ".cpp")):
+            continue
+        with open(os.path.join(csrc, name), errors="replace") as f:
+            for line in f:
+                code = line.split("//")[0]
+                if "gauss_noise(" in code and "float gauss_noise(" not in code:
+                    found[name] = found.get(name, 0) + code.count("gauss_noise(")
+    table = {}
+    for fname, kernel, case in NOISE_SITES:
+        table[fname] = table.get(fname, 0) + 1
+        assert case.strip() and kernel.strip()
+    assert sum(found.values()) == len(NOISE_SITES)
+    assert found == table

@@ -516,3 +516,63 @@ def test_committed_bresenham_literal_vectors_match_this_hosts_libm(oracle_mod):
         r2, h2, s2 = om.bl_rays_libm(ins)
         assert np.abs(r2 - L[name + "_rays_ranges"]).max() <= 1e-3 * g.resolution, name
         assert np.array_equal(h2, L[name + "_rays_hits"].astype(np.int32)) and np.array_equal(s2, L[name + "_rays_steps"]), name
+
+
+# ---------------------------------------------------------------- row a15: the noise generator's reference
+@pytest.mark.parametrize("ctr, key, out", [
+    ((0x00000000, 0x00000000), 0x00000000, (0xff1dae59, 0x6cd10df2)),
+    ((0xffffffff, 0xffffffff), 0xffffffff, (0x2c3f628b, 0xab4fd7ad)),
+    ((0x243f6a88, 0x85a308d3), 0x13198a2e, (0xdd7ce038, 0xf62a4c12)),
+])
+def test_philox2x32_10_known_answers(ctr, key, out):
+    """Random123's published known-answer vectors for philox2x32, 10 rounds (kat_vectors)."""
+    c0, c1 = N.philox2x32_10(np.array([ctr[0]], np.uint64), np.array([ctr[1]], np.uint64), key)
+    assert (int(c0[0]), int(c1[0])) == out
+
+
+def test_noise_seed_fold():
+    for seed in (0, 1, 6, 0xDEADBEEF, 0xFFFFFFFF):
+        assert N.noise_key(seed) == seed                       # below 2^32: the key is the seed
+    assert N.noise_key(1 << 32) == 0x85EBCA6B
+    assert N.noise_key((3 << 32) | 5) == (5 ^ ((3 * 0x85EBCA6B) & 0xFFFFFFFF))
+    ids = np.arange(4096, dtype=np.uint64)
+    a = N.gauss_noise_ref(5, ids)
+    for hi in (1, 2, 0xFFFFFFFF):                              # same low word, other high word: another stream
+        b = N.gauss_noise_ref(5 + (hi << 32), ids)
+        assert np.mean(a == b) < 0.01
+        assert abs(np.corrcoef(a, b)[0, 1]) < 0.08
+    assert np.array_equal(a, N.gauss_noise_ref(5, ids))
+
+
+def test_noise_uniform_endpoints():
+    """u1 = ((c0 >> 8) + 1) 2^-24 in (0, 1]: its top value gives ln 1 = 0 exactly, its bottom one the largest |g|,
+    sqrt(48 ln 2) ~ 5.77; u2 = (c1 >> 8) 2^-24 in [0, 1)."""
+    top = np.array([0xFFFFFF00, 0xFFFFFFFF], np.uint64)
+    assert np.all(N.box_muller(top, np.array([0, 0x80000000], np.uint64)) == 0.0)
+    bottom = np.array([0, 0xFF], np.uint64)
+    g = N.box_muller(bottom, np.array([0, 0xFF], np.uint64))
+    assert np.allclose(g, math.sqrt(48.0 * math.log(2.0)), rtol=0, atol=1e-12) and 5.76 < g[0] < 5.78
+    assert N.box_muller(np.array([0], np.uint64), np.array([0x80000000], np.uint64))[0] == -g[0]   # u2 = 1/2: cos = -1
+    g = N.gauss_noise_ref(123, np.arange(1 << 16, dtype=np.uint64))
+    assert np.abs(g).max() <= math.sqrt(48.0 * math.log(2.0))
+
+
+def test_noise_moments_over_a_million_ids():
+    g = N.gauss_noise_ref(0x0123456789ABCDEF, np.arange(1 << 20, dtype=np.uint64))
+    assert abs(g.mean()) < 5e-3 and abs(g.var() - 1.0) < 7e-3
+    assert abs((g ** 3).mean()) < 0.015 and abs((g ** 4).mean() - 3.0) < 0.03
+    assert abs(np.mean(g < 0) - 0.5) < 3e-3 and abs(np.mean(np.abs(g) < 1.0) - 0.682689) < 3e-3
+
+
+@pytest.mark.parametrize("first", [0, 2 ** 32 - (1 << 17), 2 ** 64 - (1 << 17)])
+def test_noise_neighbouring_ids_uncorrelated(first):
+    """Lag-1 correlation of consecutive ids, including a block across 2^32 (the counter's high word c1 changes) and
+    one that wraps past 2^64; and ids 2^32 apart (same c0, other c1)."""
+    ids = N.fan_ray_ids(first, 1 << 18, 1)
+    g = N.gauss_noise_ref(6, ids)
+    assert abs(np.corrcoef(g[:-1], g[1:])[0, 1]) < 0.01
+    h = N.gauss_noise_ref(6, ids + np.uint64(1 << 32))
+    assert abs(np.corrcoef(g, h)[0, 1]) < 0.01
+    if first:                                    # the block does cross the high word (or wrap)
+        assert int(ids[0]) == first and (int(ids[-1]) >> 32) != (first >> 32)
+    assert abs(g.std() - 1.0) < 0.01
