@@ -9,6 +9,9 @@
 #include "crash_kernels.h"
 #include "launch_plan.h"
 
+#include <array>
+#include <utility>
+
 static_assert(plan::WG == scan::WG && plan::STREAM_HDR == scan::STREAM_HDR && plan::STRIPE_BINS == scan::STRIPE_BINS &&
                   plan::STRIPE_MAX_PER_LANE == scan::STRIPE_MAX_PER_LANE && plan::DRAIN_CAP == scan::DRAIN_CAP &&
                   plan::DRAIN_FIELDS == scan::DRAIN_FIELDS && plan::INLINE_REC_BYTES == (int)sizeof(scan::BlockRec),
@@ -34,7 +37,8 @@ extern "C" int rl_method_create(rl_map *m, int kind, float max_range_px, int the
     h->max_range = max_range_px;
     h->theta_disc = theta_disc;
     h->step_coeff = kind == RL_RM_GPU ? 1.0f : 0.999f;   // kernels.cu STEP_COEFF vs RayMarching (also seeds the LUT)
-    h->variant = plan::default_variant(kind);             // RL_RM: the upstream-literal arithmetic; the others canonical
+    plan::default_opts(h->opt);
+    h->opt.variant = plan::default_variant(kind);         // RL_RM: the upstream-literal arithmetic; the others canonical
     if (!m->reps.empty()) {
         // multi-device: one ordinary method per device replica of the map + one worker thread per extra device
         std::vector<int> devs;
@@ -158,6 +162,77 @@ extern "C" int rl_set_noise(rl_method *h, float std, uint64_t seed, uint64_t ray
     return RL_OK;
 }
 
+// Every option of a handle: where its value lives — a planner option (rl_plan_opts field) or a tunable of the handle
+// itself — and how rl_method_set_option brings a value into range (nullptr: stored as given).  get_info reads the same
+// field back.
+struct OptionRow {
+    const char *name;
+    int rl_plan_opts::*plan;
+    int rl_method::*own;
+    int (*clamp)(int);
+};
+static int clamp_int(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+static int as_bool(int v) { return v != 0; }
+static const OptionRow OPTIONS[] = {
+    {"variant", &rl_plan_opts::variant, nullptr, nullptr},            // (< 0: the kind's default, rl_method_set_option)
+    {"grid_mult", &rl_plan_opts::grid_mult, nullptr, [](int v) { return std::max(v, 1); }},
+    {"wg_threads", &rl_plan_opts::wg_threads, nullptr, [](int v) { return v >= 1024 ? 1024 : (v >= 512 ? 512 : 256); }},
+    {"low_water", &rl_plan_opts::low_water, nullptr, [](int v) { return v < 0 ? -1 : std::min(v, 63); }},
+    {"sort_poses", &rl_plan_opts::sort_poses, nullptr, as_bool},
+    {"xcd_bands", &rl_plan_opts::xcd_bands, nullptr, [](int v) { return std::max(v, 1); }},
+    {"slots", &rl_plan_opts::slots, nullptr, [](int v) { return v >= 3 ? 3 : std::max(v, 0); }},
+    {"tiled", &rl_plan_opts::tiled, nullptr, as_bool},
+    {"inline_prep", &rl_plan_opts::inline_prep, nullptr, as_bool},
+    {"inline_max", &rl_plan_opts::inline_max, nullptr, nullptr},
+    {"inline_map_kb", &rl_plan_opts::inline_map_kb, nullptr, [](int v) { return std::max(v, 0); }},
+    {"stripe_max", &rl_plan_opts::stripe_max, nullptr, [](int v) { return std::max(v, 0); }},
+    {"order_inline", &rl_plan_opts::order_inline, nullptr, as_bool},
+    {"bin_multi_min", &rl_plan_opts::bin_multi_min, nullptr, nullptr},
+    {"bin_generic", &rl_plan_opts::bin_generic, nullptr, as_bool},
+    {"run_log2", &rl_plan_opts::run_log2, nullptr, [](int v) { return v < 0 ? -1 : std::min(v, 8); }},
+    {"cddt_bins", &rl_plan_opts::cddt_bins, nullptr, as_bool},
+    {"cddt_sort", &rl_plan_opts::cddt_sort, nullptr, as_bool},
+    {"lut_debug", &rl_plan_opts::lut_debug, nullptr, nullptr},        // (also LutParams / CddtParams debug)
+    {"debug_stamps", &rl_plan_opts::debug_stamps, nullptr, as_bool},
+    {"slice_log2", &rl_plan_opts::slice_log2, nullptr, [](int v) { return clamp_int(v, 8, 30); }},
+    {"cddt_theta_min", &rl_plan_opts::cddt_theta_min, nullptr, [](int v) { return std::max(v, 0); }},
+    {"cddt_search", &rl_plan_opts::cddt_search, nullptr, [](int v) { return clamp_int(v, 0, 2); }},
+    {"code_map", &rl_plan_opts::code_map, nullptr, [](int v) { return v == 2 ? 2 : 0; }},
+    {"code_min_rays", &rl_plan_opts::code_min_rays, nullptr, [](int v) { return std::max(v, 0); }},
+    {"tail_pct", &rl_plan_opts::tail_pct, nullptr, [](int v) { return clamp_int(v, 0, 75); }},
+    {"tail_wg_pct", &rl_plan_opts::tail_wg_pct, nullptr, [](int v) { return clamp_int(v, 10, 400); }},
+    {"timing", nullptr, &rl_method::timing, [](int v) { return clamp_int(v, 0, 2); }},
+    {"drain_prio", nullptr, &rl_method::drain_prio, as_bool},
+    {"spec_drain", nullptr, &rl_method::spec_drain, [](int v) { return clamp_int(v, 0, 64); }},
+    {"spec_stretch", nullptr, &rl_method::spec_stretch, [](int v) { return clamp_int(v, 1, 4096); }},
+    {"drain_cap", nullptr, &rl_method::drain_cap, [](int v) { return clamp_int(v, 1, 64); }},
+    {"drain_stretch", nullptr, &rl_method::drain_stretch, [](int v) { return clamp_int(v, 1, 4096); }},
+    {"group_drain", nullptr, &rl_method::group_drain, [](int v) { return clamp_int(v, 0, 16); }},
+    {"handoff", nullptr, &rl_method::handoff, as_bool},
+    {"handoff_cap", nullptr, &rl_method::handoff_cap, [](int v) { return v >= 64 ? 64 : (v >= 32 ? 32 : (v >= 16 ? 16 : 8)); }},
+    {"handoff_wg", nullptr, &rl_method::handoff_wg, [](int v) { return v >= 256 ? 256 : (v >= 128 ? 128 : 64); }},
+    {"nt_store", nullptr, &rl_method::nt_store, as_bool},
+    {"bin_ppw", nullptr, &rl_method::bin_ppw, [](int v) { return clamp_int(v, 256, 8192); }},
+    {"tile_stripe", nullptr, &rl_method::tile_stripe, [](int v) { return v < 0 ? -1 : std::min(v, 4096); }},
+    {"pinned_max_rays", nullptr, &rl_method::pinned_max_rays, [](int v) { return std::max(v, 0); }},
+    {"direct_max_rays", nullptr, &rl_method::direct_max_rays, [](int v) { return std::max(v, 0); }},
+    {"overlap_min_rays", nullptr, &rl_method::overlap_min_rays, [](int v) { return std::max(v, 0); }},
+    // (a power of two in [128, CDDT_LDS_SORT]: the bitonic network pads to one)
+    {"cddt_lds_sort", nullptr, &rl_method::cddt_lds_sort, [](int v) {
+         int p = 128;
+         while (p * 2 <= v && p * 2 <= (int)CDDT_LDS_SORT) p *= 2;
+         return p;
+     }},
+};
+
+static const OptionRow *find_option(const char *name)
+{
+    for (const OptionRow &r : OPTIONS)
+        if (!strcmp(name, r.name)) return &r;
+    return nullptr;
+}
+static int &option_value(rl_method *h, const OptionRow &r) { return r.plan ? h->opt.*r.plan : h->*r.own; }
+
 extern "C" int rl_method_set_option(rl_method *h, const char *name, int value)
 {
     if (!h || !name) return fail(RL_ERR_INVALID, "rl_method_set_option: null pointer");
@@ -174,56 +249,12 @@ extern "C" int rl_method_set_option(rl_method *h, const char *name, int value)
         return RL_OK;
     }
     std::lock_guard<std::mutex> lk(h->mu);
-    if (!strcmp(name, "variant")) h->variant = value < 0 ? plan::default_variant(h->kind) : value;
-    else if (!strcmp(name, "grid_mult")) h->grid_mult = value < 1 ? 1 : value;
-    else if (!strcmp(name, "low_water")) h->low_water = value < 0 ? -1 : (value > 63 ? 63 : value);
-    else if (!strcmp(name, "sort_poses")) h->sort_poses = value != 0;
-    else if (!strcmp(name, "debug_stamps")) h->debug_stamps = value != 0;
-    else if (!strcmp(name, "drain_prio")) h->drain_prio = value != 0;
-    else if (!strcmp(name, "spec_drain")) h->spec_drain = value < 0 ? 0 : (value > 64 ? 64 : value);
-    else if (!strcmp(name, "spec_stretch")) h->spec_stretch = value < 1 ? 1 : (value > 4096 ? 4096 : value);
-    else if (!strcmp(name, "drain_cap")) h->drain_cap = value < 1 ? 1 : (value > 64 ? 64 : value);
-    else if (!strcmp(name, "group_drain")) h->group_drain = value < 0 ? 0 : (value > 16 ? 16 : value);
-    else if (!strcmp(name, "handoff")) h->handoff = value != 0;
-    else if (!strcmp(name, "handoff_cap")) h->handoff_cap = value >= 64 ? 64 : (value >= 32 ? 32 : (value >= 16 ? 16 : 8));
-    else if (!strcmp(name, "handoff_wg")) h->handoff_wg = value >= 256 ? 256 : (value >= 128 ? 128 : 64);
-    else if (!strcmp(name, "drain_stretch")) h->drain_stretch = value < 1 ? 1 : (value > 4096 ? 4096 : value);
-    else if (!strcmp(name, "nt_store")) h->nt_store = value != 0;
-    else if (!strcmp(name, "timing")) h->timing = value < 0 ? 0 : (value > 2 ? 2 : value);
-    else if (!strcmp(name, "bin_multi_min")) h->bin_multi_min = value;
-    else if (!strcmp(name, "bin_ppw")) h->bin_ppw = value < 256 ? 256 : (value > 8192 ? 8192 : value);
-    else if (!strcmp(name, "tile_stripe")) h->tile_stripe = value < 0 ? -1 : (value > 4096 ? 4096 : value);
-    else if (!strcmp(name, "inline_prep")) h->inline_prep = value != 0;
-    else if (!strcmp(name, "bin_generic")) h->bin_generic = value != 0;
-    else if (!strcmp(name, "tiled")) h->tiled = value != 0;
-    else if (!strcmp(name, "code_map")) h->code_map = value == 2 ? 2 : 0;
-    else if (!strcmp(name, "code_min_rays")) h->code_min_rays = value < 0 ? 0 : value;
-    else if (!strcmp(name, "tail_pct")) h->tail_pct = value < 0 ? 0 : (value > 75 ? 75 : value);
-    else if (!strcmp(name, "tail_wg_pct")) h->tail_wg_pct = value < 10 ? 10 : (value > 400 ? 400 : value);
-    else if (!strcmp(name, "pinned_max_rays")) h->pinned_max_rays = value < 0 ? 0 : value;
-    else if (!strcmp(name, "direct_max_rays")) h->direct_max_rays = value < 0 ? 0 : value;
-    else if (!strcmp(name, "overlap_min_rays")) h->overlap_min_rays = value < 0 ? 0 : value;
-    else if (!strcmp(name, "inline_map_kb")) h->inline_map_kb = value < 0 ? 0 : value;
-    else if (!strcmp(name, "stripe_max")) h->stripe_max = value < 0 ? 0 : value;
-    else if (!strcmp(name, "order_inline")) h->order_inline = value != 0;
-    else if (!strcmp(name, "run_log2")) h->run_log2 = value < 0 ? -1 : value > 8 ? 8 : value;
-    else if (!strcmp(name, "slice_log2")) h->slice_log2 = value < 8 ? 8 : (value > 30 ? 30 : value);
-    else if (!strcmp(name, "inline_max")) h->inline_max = value;
-    else if (!strcmp(name, "lut_debug")) { h->lut_debug = value; h->lp.debug = value; h->cdp.debug = value; }
-    else if (!strcmp(name, "wg_threads")) h->wg_threads = value >= 1024 ? 1024 : (value >= 512 ? 512 : 256);
-    else if (!strcmp(name, "xcd_bands")) h->xcd_bands = value < 1 ? 1 : value;
-    else if (!strcmp(name, "slots")) h->slots = value >= 3 ? 3 : (value == 2 ? 2 : (value == 1 ? 1 : 0));
-    else if (!strcmp(name, "cddt_bins")) h->cddt_bins_kernel = value != 0;
-    else if (!strcmp(name, "cddt_search")) h->cddt_search = value < 0 ? 0 : value > 2 ? 2 : value;
-    else if (!strcmp(name, "cddt_sort")) h->cddt_sort = value != 0;
-    else if (!strcmp(name, "cddt_theta_min")) h->cddt_theta_min = value < 0 ? 0 : value;
-    else if (!strcmp(name, "cddt_lds_sort")) {
-        int v = 128;                                   // a power of two in [128, CDDT_LDS_SORT]: the bitonic network pads to one
-        while (v * 2 <= value && v * 2 <= (int)CDDT_LDS_SORT) v *= 2;
-        h->cddt_lds_sort = v;
-        h->cddt_epoch = ~0ull;
-    }
-    else return fail(RL_ERR_INVALID, "unknown option '%s'", name);
+    const OptionRow *row = find_option(name);
+    if (!row) return fail(RL_ERR_INVALID, "unknown option '%s'", name);
+    if (!strcmp(name, "variant") && value < 0) value = plan::default_variant(h->kind);
+    if (!strcmp(name, "lut_debug")) h->lp.debug = h->cdp.debug = value;
+    if (!strcmp(name, "cddt_lds_sort")) h->cddt_epoch = ~0ull;       // (the table is rebuilt with the new bound)
+    option_value(h, *row) = row->clamp ? row->clamp(value) : value;
     return RL_OK;
 }
 
@@ -237,54 +268,13 @@ extern "C" int rl_method_get_info(rl_method *h, const char *name, int64_t *value
     }
     if (!strcmp(name, "cddt_values") || !strcmp(name, "cddt_buckets") || !strcmp(name, "cddt_nonempty_buckets"))
         return cddt_table_stats(h, name, value_out);
+    // (read-only)
     if (!strcmp(name, "n_cu")) *value_out = h->map->n_cu;
     else if (!strcmp(name, "clock_khz")) *value_out = h->map->clock_khz;
-    else if (!strcmp(name, "variant")) *value_out = h->variant;
-    else if (!strcmp(name, "grid_mult")) *value_out = h->grid_mult;
-    else if (!strcmp(name, "low_water")) *value_out = h->low_water;
-    else if (!strcmp(name, "sort_poses")) *value_out = h->sort_poses;
-    else if (!strcmp(name, "debug_stamps")) *value_out = h->debug_stamps;
-    else if (!strcmp(name, "drain_prio")) *value_out = h->drain_prio;
-    else if (!strcmp(name, "spec_drain")) *value_out = h->spec_drain;
-    else if (!strcmp(name, "spec_stretch")) *value_out = h->spec_stretch;
-    else if (!strcmp(name, "drain_cap")) *value_out = h->drain_cap;
-    else if (!strcmp(name, "group_drain")) *value_out = h->group_drain;
-    else if (!strcmp(name, "handoff")) *value_out = h->handoff;
-    else if (!strcmp(name, "handoff_cap")) *value_out = h->handoff_cap;
-    else if (!strcmp(name, "handoff_wg")) *value_out = h->handoff_wg;
-    else if (!strcmp(name, "drain_stretch")) *value_out = h->drain_stretch;
-    else if (!strcmp(name, "nt_store")) *value_out = h->nt_store;
-    else if (!strcmp(name, "timing")) *value_out = h->timing;
-    else if (!strcmp(name, "bin_multi_min")) *value_out = h->bin_multi_min;
-    else if (!strcmp(name, "bin_ppw")) *value_out = h->bin_ppw;
-    else if (!strcmp(name, "tile_stripe")) *value_out = h->tile_stripe;
-    else if (!strcmp(name, "inline_prep")) *value_out = h->inline_prep;
-    else if (!strcmp(name, "bin_generic")) *value_out = h->bin_generic;
-    else if (!strcmp(name, "tiled")) *value_out = h->tiled;
-    else if (!strcmp(name, "code_map")) *value_out = h->code_map;
-    else if (!strcmp(name, "code_min_rays")) *value_out = h->code_min_rays;
-    else if (!strcmp(name, "tail_pct")) *value_out = h->tail_pct;
-    else if (!strcmp(name, "tail_wg_pct")) *value_out = h->tail_wg_pct;
     else if (!strcmp(name, "code_entries")) *value_out = h->code_n;
-    else if (!strcmp(name, "pinned_max_rays")) *value_out = h->pinned_max_rays;
-    else if (!strcmp(name, "direct_max_rays")) *value_out = h->direct_max_rays;
-    else if (!strcmp(name, "overlap_min_rays")) *value_out = h->overlap_min_rays;
-    else if (!strcmp(name, "inline_map_kb")) *value_out = h->inline_map_kb;
-    else if (!strcmp(name, "stripe_max")) *value_out = h->stripe_max;
-    else if (!strcmp(name, "order_inline")) *value_out = h->order_inline;
-    else if (!strcmp(name, "run_log2")) *value_out = h->run_log2;
-    else if (!strcmp(name, "slice_log2")) *value_out = h->slice_log2;
-    else if (!strcmp(name, "inline_max")) *value_out = h->inline_max;
-    else if (!strcmp(name, "wg_threads")) *value_out = h->wg_threads;
     else if (!strcmp(name, "last_grid")) *value_out = h->last_grid;
-    else if (!strcmp(name, "xcd_bands")) *value_out = h->xcd_bands;
-    else if (!strcmp(name, "slots")) *value_out = h->slots;
-    else if (!strcmp(name, "cddt_bins")) *value_out = h->cddt_bins_kernel;
-    else if (!strcmp(name, "cddt_search")) *value_out = h->cddt_search;
-    else if (!strcmp(name, "cddt_sort")) *value_out = h->cddt_sort;
-    else if (!strcmp(name, "cddt_theta_min")) *value_out = h->cddt_theta_min;
-    else if (!strcmp(name, "cddt_lds_sort")) *value_out = h->cddt_lds_sort;
     else if (!strcmp(name, "map_epoch")) *value_out = (int64_t)h->map->epoch;
+    else if (const OptionRow *row = find_option(name)) *value_out = option_value(h, *row);
     else return fail(RL_ERR_INVALID, "unknown info '%s'", name);
     return RL_OK;
 }
@@ -419,7 +409,7 @@ static int ensure_lut(rl_method *h, hipStream_t stream)
     lp.bin_width = 6.283185307179586f / (float)h->theta_disc;
     lp.quant = 65535.0f / h->max_range;
     lp.dequant = h->max_range / 65535.0f;
-    lp.debug = h->lut_debug;
+    lp.debug = h->opt.lut_debug;
     const long cells = (long)m->rows * m->cols;
     const int grid = (int)std::min(cells, (long)m->n_cu * 16);
     hipLaunchKernelGGL(lut_build_kernel, dim3(grid), dim3(256), 0, stream, m->mp, lp, h->max_range,
@@ -498,7 +488,7 @@ static int ensure_cddt(rl_method *h, hipStream_t stream)
     cp.hdr = (uint2 *)h->cd_hdr.p;
     cp.tab = (float *)h->cd_tab.p;
     cp.bins_per_rad = (float)td * 0.15915494309189535f;
-    cp.debug = h->lut_debug;
+    cp.debug = h->opt.lut_debug;
     if ((rc = h->cd_tmp.ensure(((size_t)nbk + 2 * nb + 64) * 4))) return rc;   // big-bucket count, bin totals (values, lines), list
     if (!h->cd_sort_attr) {
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&cddt_sort_kernel),
@@ -643,13 +633,13 @@ static int bin_poses(rl_method *h, LaunchCtx &cx, const float *d_poses, int n_po
     if ((rc = cx.order.ensure((size_t)n_poses * sizeof(uint32_t)))) return rc;
     if ((rc = cx.keys.ensure((size_t)n_poses * sizeof(uint32_t)))) return rc;
     if ((rc = cx.rec_sorted.ensure((size_t)n_poses * sizeof(PoseRec)))) return rc;
-    const int do_sort = (binning == RL_BIN_GRID_UNSORTED || (binning == RL_BIN_GENERIC && !(h->sort_poses && n_poses >= 64))) ? 0 : 1;
+    const int do_sort = (binning == RL_BIN_GRID_UNSORTED || (binning == RL_BIN_GENERIC && !(h->opt.sort_poses && n_poses >= 64))) ? 0 : 1;
     int shift = 6;
     while ((long)((m->cols >> shift) + 1) * ((m->rows >> shift) + 1) > 8192) ++shift;
     // (tile_key: tile rows in stripes walked column by column; -1: as many tile rows as an XCD band of evenly spread poses holds)
     auto striped = [&](int tx, int sh) {
         const int tiles_y = (m->rows >> sh) + 1;
-        int rps = h->tile_stripe < 0 ? std::max(1, (m->rows >> sh) / std::max(1, h->xcd_bands)) : h->tile_stripe;
+        int rps = h->tile_stripe < 0 ? std::max(1, (m->rows >> sh) / std::max(1, h->opt.xcd_bands)) : h->tile_stripe;
         if (rps >= tiles_y || !do_sort) rps = 0;
         return tx | (rps << 16);
     };
@@ -721,36 +711,8 @@ static FastDiv make_fastdiv(uint32_t d)
 // the options of a handle that shape a launch, as the planner takes them
 static rl_plan_opts opts_of(const rl_method *h)
 {
-    rl_plan_opts o;
-    plan::default_opts(o);
-    o.variant = h->variant;
-    o.grid_mult = h->grid_mult;
-    o.wg_threads = h->wg_threads;
-    o.low_water = h->low_water;
-    o.sort_poses = h->sort_poses;
-    o.xcd_bands = h->xcd_bands;
-    o.slots = h->slots;
-    o.tiled = h->tiled;
-    o.inline_prep = h->inline_prep;
-    o.inline_max = h->inline_max;
-    o.inline_map_kb = h->inline_map_kb;
-    o.stripe_max = h->stripe_max;
-    o.order_inline = h->order_inline;
-    o.bin_multi_min = h->bin_multi_min;
-    o.bin_generic = h->bin_generic;
-    o.run_log2 = h->run_log2;
-    o.cddt_bins = h->cddt_bins_kernel;
-    o.cddt_sort = h->cddt_sort;
-    o.cddt_theta_min = h->cddt_theta_min;
-    o.cddt_search = h->cddt_search;
-    o.lut_debug = h->lut_debug;
-    o.debug_stamps = h->debug_stamps;
-    o.slice_log2 = h->slice_log2;
-    o.code_map = h->code_map;
-    o.code_min_rays = h->code_min_rays;
-    o.tail_pct = h->tail_pct;
-    o.tail_wg_pct = h->tail_wg_pct;
-    o.code_entries = (h->code_map && h->code_built == h->code_map && h->pdt_epoch == h->map->epoch) ? h->code_n : 0;
+    rl_plan_opts o = h->opt;
+    o.code_entries = (o.code_map && h->code_built == o.code_map && h->pdt_epoch == h->map->epoch) ? h->code_n : 0;
     return o;
 }
 
@@ -780,8 +742,8 @@ static int ensure_step_map(rl_method *h, hipStream_t stream)
     // (the planner marches on the row-major copy when the tiled geometry does not fit the address arithmetic:
     //  plan::tiled_fit — elongated maps whose pitch would need K > 24, tables beyond 4 GiB)
     const plan::TiledFit fit = plan::tiled_fit(m->rows, m->cols, h->max_range);
-    const int want_tiled = (h->tiled && fit.ok) ? 1 : 0;
-    if (h->pdt_epoch == m->epoch && h->pdt.p && h->pdt_tiled == want_tiled && h->code_built == h->code_map)
+    const int want_tiled = (h->opt.tiled && fit.ok) ? 1 : 0;
+    if (h->pdt_epoch == m->epoch && h->pdt.p && h->pdt_tiled == want_tiled && h->code_built == h->opt.code_map)
         return table_wait(h->pdt_dep, stream);
     if (h->pdt.p) HIPCHK(hipDeviceSynchronize());   // launches of other streams may still read the old copy
     h->pad = (int)std::ceil(h->max_range) + 2;
@@ -820,7 +782,7 @@ static int ensure_step_map(rl_method *h, hipStream_t stream)
     // The palette size decides the launches' LDS, so the host reads it back here (a map build, not a scan).
     h->code_n = 0;
     const plan::CodeFit cf = plan::code_fit(m->rows, m->cols, h->max_range, 1);
-    if (h->code_map == 2 && want_tiled && cf.ok) {
+    if (h->opt.code_map == 2 && want_tiled && cf.ok) {
         const uint32_t cap = (uint32_t)plan::CODE_MAX_ENTRIES;
         if ((rc = h->cval.ensure((size_t)cf.nb * sizeof(float)))) return rc;
         if ((rc = h->cidx.ensure((size_t)cf.nb * sizeof(uint32_t)))) return rc;
@@ -854,76 +816,42 @@ static int ensure_step_map(rl_method *h, hipStream_t stream)
             h->code_n = (int)h->pin_cnum[0];
         }
     }
-    h->code_built = h->code_map;
+    h->code_built = h->opt.code_map;
     h->pdt_epoch = m->epoch;
     h->pdt_tiled = want_tiled;
     return table_built(h->pdt_dep, stream);
 }
 
-// the stream-kernel instantiation a plan names
-template <bool A, bool C, int N, bool I, bool T, int S, bool L = false, int CD = 0>
-static void launch_rm_stream(const rl_launch_plan &pl, hipStream_t stream, const PadMap &pm, const FanParams &f,
-                             const StreamParams &sp, float *d_out, int32_t *d_hits, uint16_t *d_steps,
-                             const CrashParams &cp)
+// rm_fan_stream_kernel by plan::stream_index: every instance of plan::stream_instance, nullptr in the other slots
+typedef void (*rm_stream_fn)(PadMap, FanParams, StreamParams, float *, int32_t *, uint16_t *, CrashParams);
+template <int I>
+static constexpr rm_stream_fn rm_stream_at()
 {
-    // (more dynamic LDS than HIP's default cap — fans of several thousand beams, with the crash table —: opt in,
-    //  as the BL / occ / CDDT kernels do; the attribute is sticky per function and device, the call is cheap)
-    if (pl.lds_bytes > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&rm_fan_stream_kernel<A, C, N, I, T, S, L, CD>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_bytes);
-    hipLaunchKernelGGL((rm_fan_stream_kernel<A, C, N, I, T, S, L, CD>), dim3(pl.grid), dim3(N), (size_t)pl.lds_bytes, stream,
-                       pm, f, sp, d_out, d_hits, d_steps, cp);
+    constexpr plan::StreamKey k = plan::stream_key_at(I);
+    if constexpr (plan::stream_instance(k)) return rm_fan_stream_kernel<k.a, k.c, k.n, k.inl, k.t, k.s, k.lit, k.code>;
+    else return nullptr;
 }
+template <int... I>
+static constexpr std::array<rm_stream_fn, sizeof...(I)> rm_stream_make(std::integer_sequence<int, I...>)
+{
+    return {{rm_stream_at<I>()...}};
+}
+static const std::array<rm_stream_fn, plan::STREAM_KEYS> rm_stream_table =
+    rm_stream_make(std::make_integer_sequence<int, plan::STREAM_KEYS>());
 
 static int dispatch_rm_stream(const rl_launch_plan &pl, hipStream_t stream, const PadMap &pm, const FanParams &f,
                               const StreamParams &sp, float *d_out, int32_t *d_hits, uint16_t *d_steps,
                               const CrashParams &cp)
 {
-    const bool inl = pl.record_source != 0, tiled = pl.tiled != 0, aux = pl.aux != 0, crash = pl.crash != 0;
-    const int nt = pl.block;
-#define RM_ARGS pl, stream, pm, f, sp, d_out, d_hits, d_steps, cp
-    if (pl.kernel == RL_K_RM_STREAM_LIT) {     // upstream-literal arithmetic (variant 3): INLINE records, tiled step map
-        if (pl.slots >= 2 && pl.code == 2) { if (crash) launch_rm_stream<false, true, 1024, true, true, 2, true, 2>(RM_ARGS);
-                                             else launch_rm_stream<false, false, 1024, true, true, 2, true, 2>(RM_ARGS); }
-        else if (pl.slots >= 2) { if (crash) launch_rm_stream<false, true, 1024, true, true, 2, true>(RM_ARGS);
-                             else launch_rm_stream<false, false, 1024, true, true, 2, true>(RM_ARGS); }
-        else               { if (crash) launch_rm_stream<false, true, 1024, true, true, 1, true>(RM_ARGS);
-                             else launch_rm_stream<false, false, 1024, true, true, 1, true>(RM_ARGS); }
-    } else if (pl.code == 2 && pl.slots == 2 && tiled && !aux && nt == 1024) {     // two rays per lane on the u16 code map
-        if (inl) { if (crash) launch_rm_stream<false, true, 1024, true, true, 2, false, 2>(RM_ARGS);
-                   else launch_rm_stream<false, false, 1024, true, true, 2, false, 2>(RM_ARGS); }
-        else     { if (crash) launch_rm_stream<false, true, 1024, false, true, 2, false, 2>(RM_ARGS);
-                   else launch_rm_stream<false, false, 1024, false, true, 2, false, 2>(RM_ARGS); }
-    } else if (pl.slots == 3) {                // three rays per lane: plain ranges, 1024 lanes
-        if (!inl) launch_rm_stream<false, false, 1024, false, true, 3>(RM_ARGS);
-        else if (tiled) launch_rm_stream<false, false, 1024, true, true, 3>(RM_ARGS);
-        else launch_rm_stream<false, false, 1024, true, false, 3>(RM_ARGS);
-    } else if (pl.slots == 2) {                // two rays per lane: ranges / fused crash test, tiled step map
-#define RM_S2(C)                                                                     \
-    do {                                                                             \
-        if (inl) launch_rm_stream<false, C, 1024, true, true, 2>(RM_ARGS);           \
-        else if (nt == 1024) launch_rm_stream<false, C, 1024, false, true, 2>(RM_ARGS); \
-        else if (nt == 512) launch_rm_stream<false, C, 512, false, true, 2>(RM_ARGS);   \
-        else launch_rm_stream<false, C, 256, false, true, 2>(RM_ARGS);               \
-    } while (0)
-        if (inl && nt == 512 && !crash) launch_rm_stream<false, false, 512, true, true, 2>(RM_ARGS);   // (A/B: wg_threads 512)
-        else if (crash) RM_S2(true); else RM_S2(false);
-#undef RM_S2
-    } else {
-#define RM_S1(A, C, T)                                                               \
-    do {                                                                             \
-        if (inl) launch_rm_stream<A, C, 1024, true, T, 1>(RM_ARGS);                  \
-        else if (nt == 1024) launch_rm_stream<A, C, 1024, false, T, 1>(RM_ARGS);     \
-        else if (nt == 512) launch_rm_stream<A, C, 512, false, T, 1>(RM_ARGS);       \
-        else launch_rm_stream<A, C, 256, false, T, 1>(RM_ARGS);                      \
-    } while (0)
-#define RM_S1_T(A, C) do { if (tiled) RM_S1(A, C, true); else RM_S1(A, C, false); } while (0)
-        if (crash) { if (aux) RM_S1_T(true, true); else RM_S1_T(false, true); }
-        else       { if (aux) RM_S1_T(true, false); else RM_S1_T(false, false); }
-#undef RM_S1_T
-#undef RM_S1
-    }
-#undef RM_ARGS
+    const int i = plan::stream_index(plan::stream_key(pl));
+    const rm_stream_fn kernel = i >= 0 ? rm_stream_table[i] : nullptr;
+    if (!kernel) return fail(RL_ERR_INVALID, "internal: plan names an uninstantiated kernel (%s)", pl.name);
+    // (more dynamic LDS than HIP's default cap — fans of several thousand beams, with the crash table —: opt in,
+    //  as the BL / occ / CDDT kernels do; the attribute is sticky per function and device, the call is cheap)
+    if (pl.lds_bytes > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  pl.lds_bytes);
+    kernel<<<dim3(pl.grid), dim3(pl.block), (size_t)pl.lds_bytes, stream>>>(pm, f, sp, d_out, d_hits, d_steps, cp);
     return RL_OK;
 }
 
@@ -959,164 +887,168 @@ struct FanLaunch {
     const CrashParams *crash;
     hipStream_t stream;
     bool aux;
+    dim3 grid, block;            // (the plan's)
+    size_t lds;
 };
-#define FAN_LAUNCH_LOCALS                                                                                              \
-    rl_method *h = L.h; const rl_map *m = L.m; const rl_launch_plan &pl = L.pl; LaunchCtx *cx = L.cx;                   \
-    const FanParams &f = L.f; const float *d_poses = L.d_poses; const int n_poses = L.n_poses; const float fov = L.fov; \
-    const int num_rays = L.num_rays; float *d_out = L.d_out; int32_t *d_hits = L.d_hits; uint16_t *d_steps = L.d_steps; \
-    const CrashParams *crash = L.crash; hipStream_t stream = L.stream; const bool aux = L.aux;                          \
-    const dim3 grid(pl.grid), block(pl.block); const size_t lds = (size_t)pl.lds_bytes; int rc = RL_OK;                \
-    (void)h; (void)m; (void)cx; (void)f; (void)d_poses; (void)n_poses; (void)fov; (void)num_rays; (void)d_out;           \
-    (void)d_hits; (void)d_steps; (void)crash; (void)stream; (void)aux; (void)grid; (void)block; (void)lds; (void)rc
 
-// RL_K_LUT_LDS, RL_K_LUT_FAN
+// RL_K_LUT_LDS (lut_fan_lds_kernel<NL, CH>), RL_K_LUT_FAN (lut_fan_kernel<CH>): NL 1..3, CH 12 | 17
+typedef void (*lut_fn)(MapParams, FanParams, LutParams, const float *, float *);
+static const lut_fn lut_lds_table[3][2] = {{lut_fan_lds_kernel<1, 12>, lut_fan_lds_kernel<1, 17>},
+                                           {lut_fan_lds_kernel<2, 12>, lut_fan_lds_kernel<2, 17>},
+                                           {lut_fan_lds_kernel<3, 12>, lut_fan_lds_kernel<3, 17>}};
+static const lut_fn lut_fan_table[2] = {lut_fan_kernel<12>, lut_fan_kernel<17>};
+
 static int launch_lut(const FanLaunch &L)
 {
-    FAN_LAUNCH_LOCALS;
-    if ((rc = ensure_lut(h, stream))) return rc;
-    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, stream));
-#define LAUNCH_LL(N, C) hipLaunchKernelGGL((lut_fan_lds_kernel<N, C>), grid, block, lds, stream, m->mp, f, h->lp, d_poses, d_out)
-    if (pl.kernel == RL_K_LUT_LDS) {
-        if (pl.ch == 12) { if (pl.nl == 1) LAUNCH_LL(1, 12); else if (pl.nl == 2) LAUNCH_LL(2, 12); else LAUNCH_LL(3, 12); }
-        else             { if (pl.nl == 1) LAUNCH_LL(1, 17); else if (pl.nl == 2) LAUNCH_LL(2, 17); else LAUNCH_LL(3, 17); }
-    } else if (pl.ch == 12)
-        hipLaunchKernelGGL((lut_fan_kernel<12>), grid, block, 0, stream, m->mp, f, h->lp, d_poses, d_out);
-    else
-        hipLaunchKernelGGL((lut_fan_kernel<17>), grid, block, 0, stream, m->mp, f, h->lp, d_poses, d_out);
-#undef LAUNCH_LL
+    const rl_launch_plan &pl = L.pl;
+    const int ch = pl.ch == 12 ? 0 : (pl.ch == 17 ? 1 : -1);
+    lut_fn kernel = nullptr;
+    if (ch >= 0 && pl.kernel == RL_K_LUT_FAN) kernel = lut_fan_table[ch];
+    if (ch >= 0 && pl.kernel == RL_K_LUT_LDS && pl.nl >= 1 && pl.nl <= 3) kernel = lut_lds_table[pl.nl - 1][ch];
+    if (!kernel) return fail(RL_ERR_INVALID, "internal: plan names an uninstantiated kernel (%s)", pl.name);
+    int rc;
+    if ((rc = ensure_lut(L.h, L.stream))) return rc;
+    if (L.h->timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
+    kernel<<<L.grid, L.block, L.lds, L.stream>>>(L.m->mp, L.f, L.h->lp, L.d_poses, L.d_out);
     return RL_OK;
 }
 
 // RL_K_CDDT_BINS
 static int launch_cddt_bins(const FanLaunch &L)
 {
-    FAN_LAUNCH_LOCALS;
-    if ((rc = ensure_cddt(h, stream))) return rc;
+    rl_method *h = L.h;
+    int rc;
+    if ((rc = ensure_cddt(h, L.stream))) return rc;
     // tile-ordered poses in XCD bands: neighbouring origins hit neighbouring buckets (L2 reuse)
     const uint32_t *d_order = nullptr;
-    if (pl.binning != RL_BIN_NONE) {
-        if ((rc = bin_poses(h, *cx, d_poses, n_poses, 0, stream, pl.binning))) return rc;
-        d_order = (const uint32_t *)cx->order.p;
+    if (L.pl.binning != RL_BIN_NONE) {
+        if ((rc = bin_poses(h, *L.cx, L.d_poses, L.n_poses, 0, L.stream, L.pl.binning))) return rc;
+        d_order = (const uint32_t *)L.cx->order.p;
     }
-    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, stream));
-    hipLaunchKernelGGL(cddt_fan_bins_kernel, grid, block, lds, stream, m->mp, f, h->cdp, d_poses, d_out, d_order,
-                       pl.bands, pl.nl, pl.ch);
+    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
+    hipLaunchKernelGGL(cddt_fan_bins_kernel, L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, h->cdp, L.d_poses, L.d_out,
+                       d_order, L.pl.bands, L.pl.nl, L.pl.ch);
     return RL_OK;
 }
 
 // RL_K_CDDT_THETA
 static int launch_cddt_theta(const FanLaunch &L)
 {
-    FAN_LAUNCH_LOCALS;
-    if ((rc = ensure_cddt(h, stream))) return rc;
+    rl_method *h = L.h;
+    const int form = plan::cddt_theta_form(L.pl);
+    if (form < 0) return fail(RL_ERR_INVALID, "internal: plan names an uninstantiated kernel (%s)", L.pl.name);
+    const bool fused = form == plan::CDDT_THETA_FUSED;
+    int rc;
+    if ((rc = ensure_cddt(h, L.stream))) return rc;
     // scratch of the launch context: R[raw bin][pose] behind the per-pose records {gx, gy, first bin, bins}
-    const bool fused = !strcmp(pl.name, "scan::cddt_theta_fused_kernel");     // (the planner's decision: cddt_search 2 and the tile fits LDS)
-    const size_t prep_bytes = (((size_t)n_poses * 16) + 255) & ~(size_t)255;
-    if ((rc = cx->cddt_r.ensure(prep_bytes + (fused ? 0 : (size_t)h->cdp.theta_disc * (size_t)n_poses * sizeof(float))))) return rc;
-    float4 *d_prep = (float4 *)cx->cddt_r.p;
-    float *d_r = (float *)((char *)cx->cddt_r.p + prep_bytes);
-    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, stream));
-    hipLaunchKernelGGL(cddt_theta_prep_kernel, dim3((unsigned)std::max(1, std::min((n_poses + 255) / 256, m->n_cu * 8))),
-                       dim3(256), 0, stream, m->mp, f, h->cdp, d_poses, d_prep);
+    const size_t prep_bytes = (((size_t)L.n_poses * 16) + 255) & ~(size_t)255;
+    if ((rc = L.cx->cddt_r.ensure(prep_bytes + (fused ? 0 : (size_t)h->cdp.theta_disc * (size_t)L.n_poses * sizeof(float)))))
+        return rc;
+    float4 *d_prep = (float4 *)L.cx->cddt_r.p;
+    float *d_r = (float *)((char *)L.cx->cddt_r.p + prep_bytes);
+    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
+    hipLaunchKernelGGL(cddt_theta_prep_kernel, dim3((unsigned)std::max(1, std::min((L.n_poses + 255) / 256, L.m->n_cu * 8))),
+                       dim3(256), 0, L.stream, L.m->mp, L.f, h->cdp, L.d_poses, d_prep);
     if (fused) {
-        hipLaunchKernelGGL(cddt_theta_fused_kernel, grid, block, lds, stream, m->mp, f, h->cdp, d_poses,
-                           (const float4 *)d_prep, d_out, pl.nl);
+        hipLaunchKernelGGL(cddt_theta_fused_kernel, L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, h->cdp, L.d_poses,
+                           (const float4 *)d_prep, L.d_out, L.pl.nl);
         return RL_OK;
     }
-    if (h->cddt_search)
-        hipLaunchKernelGGL(cddt_theta_search2_kernel, grid, block, 0, stream, m->mp, f, h->cdp, d_poses,
-                           (const float4 *)d_prep, d_r, pl.bands);
+    if (form == plan::CDDT_THETA_SEARCH2)
+        hipLaunchKernelGGL(cddt_theta_search2_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f, h->cdp, L.d_poses,
+                           (const float4 *)d_prep, d_r, L.pl.bands);
     else
-        hipLaunchKernelGGL(cddt_theta_search_kernel, grid, block, 0, stream, m->mp, f, h->cdp, d_poses,
-                           (const float4 *)d_prep, d_r, pl.bands);
-    const int n_grp = (n_poses + (1 << pl.ch) - 1) >> pl.ch;
-    hipLaunchKernelGGL(cddt_theta_fan_kernel, dim3((unsigned)std::max(1, std::min(n_grp, m->n_cu * 8))), block, lds,
-                       stream, m->mp, f, h->cdp, d_poses, (const float *)d_r, d_out, pl.ch, pl.nl);
+        hipLaunchKernelGGL(cddt_theta_search_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f, h->cdp, L.d_poses,
+                           (const float4 *)d_prep, d_r, L.pl.bands);
+    const int n_grp = (L.n_poses + (1 << L.pl.ch) - 1) >> L.pl.ch;
+    hipLaunchKernelGGL(cddt_theta_fan_kernel, dim3((unsigned)std::max(1, std::min(n_grp, L.m->n_cu * 8))), L.block, L.lds,
+                       L.stream, L.m->mp, L.f, h->cdp, L.d_poses, (const float *)d_r, L.d_out, L.pl.ch, L.pl.nl);
     return RL_OK;
 }
 
 // RL_K_CDDT_RAYS
 static int launch_cddt_rays(const FanLaunch &L)
 {
-    FAN_LAUNCH_LOCALS;
-    if ((rc = ensure_cddt(h, stream))) return rc;
-    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, stream));
-    hipLaunchKernelGGL(cddt_fan_kernel, grid, block, 0, stream, m->mp, f, h->cdp, d_poses, d_out);
+    int rc;
+    if ((rc = ensure_cddt(L.h, L.stream))) return rc;
+    if (L.h->timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
+    hipLaunchKernelGGL(cddt_fan_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f, L.h->cdp, L.d_poses, L.d_out);
     return RL_OK;
 }
 
 // RL_K_BL_STREAM
 static int launch_bl_stream(const FanLaunch &L)
 {
-    FAN_LAUNCH_LOCALS;
+    rl_method *h = L.h;
+    int rc;
     // K2b: stream schedule on the cache-resident bit map
-    if ((rc = ensure_blpad(h, stream))) return rc;
-    if ((rc = bin_poses(h, *cx, d_poses, n_poses, 1, stream, pl.binning))) return rc;
+    if ((rc = ensure_blpad(h, L.stream))) return rc;
+    if ((rc = bin_poses(h, *L.cx, L.d_poses, L.n_poses, 1, L.stream, L.pl.binning))) return rc;
     StreamParams sp{};
-    sp.rec = (const PoseRec *)cx->rec_sorted.p;
-    sp.order = (const uint32_t *)cx->order.p;
-    sp.div_B = make_fastdiv((uint32_t)num_rays);
-    sp.low_water = h->low_water >= 0 ? h->low_water : 12;
-    sp.n_bands = pl.bands;
+    sp.rec = (const PoseRec *)L.cx->rec_sorted.p;
+    sp.order = (const uint32_t *)L.cx->order.p;
+    sp.div_B = make_fastdiv((uint32_t)L.num_rays);
+    sp.low_water = h->opt.low_water >= 0 ? h->opt.low_water : 12;
+    sp.n_bands = L.pl.bands;
     sp.plain_store = !h->nt_store;
-    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, stream));
-    if (aux)
-        hipLaunchKernelGGL((bl_fan_stream_kernel<true, 1024>), grid, block, lds, stream, m->mp, f, sp, h->blp, d_out,
-                           d_hits, d_steps);
+    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
+    if (L.aux)
+        hipLaunchKernelGGL((bl_fan_stream_kernel<true, 1024>), L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, sp, h->blp,
+                           L.d_out, L.d_hits, L.d_steps);
     else
-        hipLaunchKernelGGL((bl_fan_stream_kernel<false, 1024>), grid, block, lds, stream, m->mp, f, sp, h->blp, d_out,
-                           d_hits, d_steps);
+        hipLaunchKernelGGL((bl_fan_stream_kernel<false, 1024>), L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, sp, h->blp,
+                           L.d_out, L.d_hits, L.d_steps);
     return RL_OK;
 }
 
 // RL_K_BL_LDS, RL_K_OCC_LDS
 static int launch_bl_lds(const FanLaunch &L)
 {
-    FAN_LAUNCH_LOCALS;
     size_t lds_bl = 0;
-    BlParams bp = make_bl(h, num_rays, lds_bl);
+    BlParams bp = make_bl(L.h, L.num_rays, lds_bl);
+    const bool bl = L.pl.kernel == RL_K_BL_LDS;
     if (lds_bl > 48 * 1024) {          // more dynamic LDS than the default cap: opt in
-        const void *fa = pl.kernel == RL_K_BL_LDS ? reinterpret_cast<const void *>(&bl_fan_kernel<true>)
-                                                  : reinterpret_cast<const void *>(&occ_fan_lds_kernel<true>);
-        const void *fb = pl.kernel == RL_K_BL_LDS ? reinterpret_cast<const void *>(&bl_fan_kernel<false>)
-                                                  : reinterpret_cast<const void *>(&occ_fan_lds_kernel<false>);
+        const void *fa = bl ? reinterpret_cast<const void *>(&bl_fan_kernel<true>)
+                            : reinterpret_cast<const void *>(&occ_fan_lds_kernel<true>);
+        const void *fb = bl ? reinterpret_cast<const void *>(&bl_fan_kernel<false>)
+                            : reinterpret_cast<const void *>(&occ_fan_lds_kernel<false>);
         HIPCHK(hipFuncSetAttribute(fa, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bl));
         HIPCHK(hipFuncSetAttribute(fb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bl));
     }
-    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, stream));
-    if (pl.kernel == RL_K_BL_LDS) {
-        if (aux) hipLaunchKernelGGL((bl_fan_kernel<true>), grid, block, lds_bl, stream, m->mp, f, bp, d_poses, d_out, d_hits, d_steps);
-        else     hipLaunchKernelGGL((bl_fan_kernel<false>), grid, block, lds_bl, stream, m->mp, f, bp, d_poses, d_out, d_hits, d_steps);
-    } else {
-        // occ_fan_lds: unit-step march on an LDS-resident occupancy window (A/B partner, approximate)
-        if (aux) hipLaunchKernelGGL((occ_fan_lds_kernel<true>), grid, block, lds_bl, stream, m->mp, f, bp, d_poses, d_out, d_hits, d_steps);
-        else     hipLaunchKernelGGL((occ_fan_lds_kernel<false>), grid, block, lds_bl, stream, m->mp, f, bp, d_poses, d_out, d_hits, d_steps);
-    }
+    if (L.h->timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
+#define LAUNCH_BL(K) hipLaunchKernelGGL((K), L.grid, L.block, lds_bl, L.stream, L.m->mp, L.f, bp, L.d_poses, L.d_out, L.d_hits, L.d_steps)
+    // (occ_fan_lds: unit-step march on an LDS-resident occupancy window — A/B partner, approximate)
+    if (bl) { if (L.aux) LAUNCH_BL(bl_fan_kernel<true>); else LAUNCH_BL(bl_fan_kernel<false>); }
+    else    { if (L.aux) LAUNCH_BL(occ_fan_lds_kernel<true>); else LAUNCH_BL(occ_fan_lds_kernel<false>); }
+#undef LAUNCH_BL
     return RL_OK;
 }
 
 // RL_K_RM_LITERAL
 static int launch_rm_literal(const FanLaunch &L)
 {
-    FAN_LAUNCH_LOCALS;
-    const LiteralParams lt = make_literal(m);
-    const long n_rays = (long)n_poses * num_rays;
-    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, stream));
-    if (aux) hipLaunchKernelGGL((rm_literal_kernel<true, false>), grid, block, 0, stream, m->mp, f, lt, d_poses, n_rays, d_out, d_hits, d_steps);
-    else     hipLaunchKernelGGL((rm_literal_kernel<false, false>), grid, block, 0, stream, m->mp, f, lt, d_poses, n_rays, d_out, d_hits, d_steps);
+    const LiteralParams lt = make_literal(L.m);
+    const long n_rays = (long)L.n_poses * L.num_rays;
+    if (L.h->timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
+    if (L.aux)
+        hipLaunchKernelGGL((rm_literal_kernel<true, false>), L.grid, L.block, 0, L.stream, L.m->mp, L.f, lt, L.d_poses, n_rays,
+                           L.d_out, L.d_hits, L.d_steps);
+    else
+        hipLaunchKernelGGL((rm_literal_kernel<false, false>), L.grid, L.block, 0, L.stream, L.m->mp, L.f, lt, L.d_poses, n_rays,
+                           L.d_out, L.d_hits, L.d_steps);
     return RL_OK;
 }
 
 // RL_K_RM_CHUNK
 static int launch_rm_chunk(const FanLaunch &L)
 {
-    FAN_LAUNCH_LOCALS;
     CrashParams cp{nullptr, 0.0, nullptr, 1};
-    if (crash) cp = *crash;
-    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, stream));
-#define LAUNCH_CHUNK(A, C) hipLaunchKernelGGL((rm_fan_kernel<A, C>), grid, block, lds, stream, m->mp, f, d_poses, d_out, d_hits, d_steps, cp)
-    if (crash) { if (aux) LAUNCH_CHUNK(true, true); else LAUNCH_CHUNK(false, true); }
-    else       { if (aux) LAUNCH_CHUNK(true, false); else LAUNCH_CHUNK(false, false); }
+    if (L.crash) cp = *L.crash;
+    if (L.h->timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
+#define LAUNCH_CHUNK(A, C) hipLaunchKernelGGL((rm_fan_kernel<A, C>), L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, L.d_poses, \
+                                              L.d_out, L.d_hits, L.d_steps, cp)
+    if (L.crash) { if (L.aux) LAUNCH_CHUNK(true, true); else LAUNCH_CHUNK(false, true); }
+    else         { if (L.aux) LAUNCH_CHUNK(true, false); else LAUNCH_CHUNK(false, false); }
 #undef LAUNCH_CHUNK
     return RL_OK;
 }
@@ -1124,16 +1056,18 @@ static int launch_rm_chunk(const FanLaunch &L)
 // RL_K_RM_STREAM_LIT, RL_K_RM_STREAM
 static int launch_rm_stream_family(const FanLaunch &L)
 {
-    FAN_LAUNCH_LOCALS;
+    rl_method *h = L.h;
+    const rl_launch_plan &pl = L.pl;
+    int rc;
     // (1) per-pose records + tile-ordered permutation, (2) banded lane-refill march
     CrashParams cp{nullptr, 0.0, nullptr, 1};
-    if (crash) cp = *crash;
-    if ((rc = cx->rec.ensure((size_t)n_poses * sizeof(PoseRec)))) return rc;
-    if ((rc = cx->order.ensure((size_t)n_poses * sizeof(uint32_t)))) return rc;
-    if ((rc = cx->keys.ensure((size_t)n_poses * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure_step_map(h, stream))) return rc;
+    if (L.crash) cp = *L.crash;
+    if ((rc = L.cx->rec.ensure((size_t)L.n_poses * sizeof(PoseRec)))) return rc;
+    if ((rc = L.cx->order.ensure((size_t)L.n_poses * sizeof(uint32_t)))) return rc;
+    if ((rc = L.cx->keys.ensure((size_t)L.n_poses * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure_step_map(h, L.stream))) return rc;
     if (pl.binning != RL_BIN_NONE &&
-        (rc = bin_poses(h, *cx, d_poses, n_poses, 0, stream, pl.binning)))
+        (rc = bin_poses(h, *L.cx, L.d_poses, L.n_poses, 0, L.stream, pl.binning)))
         return rc;
     PadMap pm{};
     pm.pdt = (const float *)((const char *)h->pdt.p + h->pdt_base_off);
@@ -1142,7 +1076,7 @@ static int launch_rm_stream_family(const FanLaunch &L)
     pm.pad = h->pad;
     pm.k4 = h->pdt_k4;
     pm.div_stride = make_fastdiv((uint32_t)h->pstride);
-    pm.res = m->res;
+    pm.res = L.m->res;
     if (pl.code) {                               // the march reads the map of palette codes: its base and address constants
         if (h->code_n <= 0 || pl.code_entries != h->code_n)
             return fail(RL_ERR_INVALID, "internal: code-map plan (%d entries) without a matching palette (%d)", pl.code_entries, h->code_n);
@@ -1155,18 +1089,18 @@ static int launch_rm_stream_family(const FanLaunch &L)
     sp.code_tab = (const float *)h->ctab.p;
     sp.code_n = pl.code ? h->code_n : 0;
     sp.tail_g1 = pl.gen1 > 0 ? pl.gen1 / std::max(pl.bands, 1) : 0;
-    sp.tail_pct = std::min(h->tail_pct, h->tail_wg_pct);
-    sp.rec = (const PoseRec *)cx->rec_sorted.p;
-    sp.order = (const uint32_t *)cx->order.p;
-    sp.d0 = (const float *)cx->d0.p;
-    if ((rc = ensure_fan_table(h, f, fov, stream, &sp.fan_tab))) return rc;
-    sp.div_B = make_fastdiv((uint32_t)num_rays);
-    sp.low_water = h->low_water >= 0 ? h->low_water : ((pl.record_source != 0 && pl.slots >= 2) ? 20 : 12);
+    sp.tail_pct = std::min(h->opt.tail_pct, h->opt.tail_wg_pct);
+    sp.rec = (const PoseRec *)L.cx->rec_sorted.p;
+    sp.order = (const uint32_t *)L.cx->order.p;
+    sp.d0 = (const float *)L.cx->d0.p;
+    if ((rc = ensure_fan_table(h, L.f, L.fov, L.stream, &sp.fan_tab))) return rc;
+    sp.div_B = make_fastdiv((uint32_t)L.num_rays);
+    sp.low_water = h->opt.low_water >= 0 ? h->opt.low_water : ((pl.record_source != 0 && pl.slots >= 2) ? 20 : 12);
     sp.n_bands = pl.bands;
-    sp.raw_poses = d_poses;
-    sp.map = m->d_mp;
+    sp.raw_poses = L.d_poses;
+    sp.map = L.m->d_mp;
     sp.k_max = pl.k_max;
-    sp.cpp = (uint32_t)((num_rays + 63) / 64);
+    sp.cpp = (uint32_t)((L.num_rays + 63) / 64);
     sp.div_cpp = make_fastdiv(sp.cpp);
     sp.drain_prio = h->drain_prio;
     sp.spec_drain = h->spec_drain;
@@ -1174,14 +1108,14 @@ static int launch_rm_stream_family(const FanLaunch &L)
     sp.drain_cap = h->drain_cap;
     sp.drain_stretch = h->drain_stretch;
     sp.group_drain = h->group_drain;
-    if (pl.kernel == RL_K_RM_STREAM_LIT) sp.lit = make_literal(m);
+    if (pl.kernel == RL_K_RM_STREAM_LIT) sp.lit = make_literal(L.m);
     sp.plain_store = !h->nt_store;
     sp.dbg = nullptr;
     const int waves_per_wg = pl.block / 64;
-    if (h->debug_stamps) {
-        if ((rc = cx->dbg.ensure((size_t)pl.grid * waves_per_wg * 4 * sizeof(uint64_t)))) return rc;
-        sp.dbg = (unsigned long long *)cx->dbg.p;
-        h->last_dbg = cx->dbg.p;
+    if (h->opt.debug_stamps) {
+        if ((rc = L.cx->dbg.ensure((size_t)pl.grid * waves_per_wg * 4 * sizeof(uint64_t)))) return rc;
+        sp.dbg = (unsigned long long *)L.cx->dbg.p;
+        h->last_dbg = L.cx->dbg.p;
     }
     sp.stripe = pl.record_source == 2 ? 1 : pl.record_source == 3 ? 2 : 0;
     sp.run_log2 = pl.run_log2;
@@ -1189,31 +1123,31 @@ static int launch_rm_stream_family(const FanLaunch &L)
     // hand-off march (several rays per lane on the tiled step map): dry waves leave their last rays in the launch
     // context's leftover list — one region of handoff_cap records per wave of the main grid —, the second launch
     // finishes them
-    const bool handoff = h->handoff && pl.slots >= 2 && pl.tiled && h->spec_drain > 0 && !h->debug_stamps &&
+    const bool handoff = h->handoff && pl.slots >= 2 && pl.tiled && h->spec_drain > 0 && !h->opt.debug_stamps &&
                          pl.kernel == RL_K_RM_STREAM && !pl.code;   // (the leftover kernel marches the canonical arithmetic on the float32 map)
     int cap_log2 = 4;
     const int n_src = pl.grid * waves_per_wg;
     if (handoff) {
         cap_log2 = h->handoff_cap >= 64 ? 6 : (h->handoff_cap >= 32 ? 5 : (h->handoff_cap >= 16 ? 4 : 3));
-        if ((rc = cx->left_rec.ensure(((size_t)n_src << cap_log2) * sizeof(LeftoverRec)))) return rc;
-        if ((rc = cx->left_cnt.ensure((size_t)n_src * sizeof(uint32_t)))) return rc;
-        sp.left_rec = (LeftoverRec *)cx->left_rec.p;
-        sp.left_cnt = (uint32_t *)cx->left_cnt.p;
+        if ((rc = L.cx->left_rec.ensure(((size_t)n_src << cap_log2) * sizeof(LeftoverRec)))) return rc;
+        if ((rc = L.cx->left_cnt.ensure((size_t)n_src * sizeof(uint32_t)))) return rc;
+        sp.left_rec = (LeftoverRec *)L.cx->left_rec.p;
+        sp.left_cnt = (uint32_t *)L.cx->left_cnt.p;
         sp.left_cap_log2 = cap_log2;
         sp.drain_cap = std::min(sp.drain_cap, 1 << cap_log2);
     }
-    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, stream));   // march kernel(s) alone
-    if ((rc = dispatch_rm_stream(pl, stream, pm, f, sp, d_out, d_hits, d_steps, cp))) return rc;
+    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));   // march kernel(s) alone
+    if ((rc = dispatch_rm_stream(pl, L.stream, pm, L.f, sp, L.d_out, L.d_hits, L.d_steps, cp))) return rc;
     if (handoff) {
         const int lw = h->handoff_wg / 64;                              // leftover waves per workgroup
         const int n_lw = (n_src + (64 >> cap_log2) - 1) / (64 >> cap_log2);
         const dim3 lgrid((unsigned)((n_lw + lw - 1) / lw)), lblock((unsigned)h->handoff_wg);
-        if (crash)
-            hipLaunchKernelGGL((rm_leftover_kernel<true>), lgrid, lblock, 0, stream, pm, f, (const LeftoverRec *)sp.left_rec,
-                               (const uint32_t *)sp.left_cnt, n_src, cap_log2, h->drain_stretch, sp.plain_store, d_out, cp);
+        if (L.crash)
+            hipLaunchKernelGGL((rm_leftover_kernel<true>), lgrid, lblock, 0, L.stream, pm, L.f, (const LeftoverRec *)sp.left_rec,
+                               (const uint32_t *)sp.left_cnt, n_src, cap_log2, h->drain_stretch, sp.plain_store, L.d_out, cp);
         else
-            hipLaunchKernelGGL((rm_leftover_kernel<false>), lgrid, lblock, 0, stream, pm, f, (const LeftoverRec *)sp.left_rec,
-                               (const uint32_t *)sp.left_cnt, n_src, cap_log2, h->drain_stretch, sp.plain_store, d_out, cp);
+            hipLaunchKernelGGL((rm_leftover_kernel<false>), lgrid, lblock, 0, L.stream, pm, L.f, (const LeftoverRec *)sp.left_rec,
+                               (const uint32_t *)sp.left_cnt, n_src, cap_log2, h->drain_stretch, sp.plain_store, L.d_out, cp);
     }
     return RL_OK;
 }
@@ -1272,11 +1206,11 @@ int launch_fan(rl_method *h, const float *d_poses, int n_poses, float fov, int n
     rl_launch_plan pl;
     int rc = RL_OK;
     // (a code-map handle plans with its palette size: the step map and the palette are built before the plan)
-    if (h->code_map && (h->kind == RL_RM || h->kind == RL_RM_GPU) && h->variant >= 1 && (rc = ensure_step_map(h, stream))) return rc;
+    if (h->opt.code_map && (h->kind == RL_RM || h->kind == RL_RM_GPU) && h->opt.variant >= 1 && (rc = ensure_step_map(h, stream))) return rc;
     rc = plan_for(h, n_poses, num_rays, aux, crash != nullptr, &pl);
     if (rc == RL_ERR_UNSUPPORTED)
-        return fail(rc, (h->variant >= 2 && crash) ? "the fused crash test needs variant 0 or 1 (not the occupancy-window or the audit kernel)"
-                        : h->variant == 2 ? "occupancy window of max_range %g does not fit LDS (num_rays %d)"
+        return fail(rc, (h->opt.variant >= 2 && crash) ? "the fused crash test needs variant 0 or 1 (not the occupancy-window or the audit kernel)"
+                        : h->opt.variant == 2 ? "occupancy window of max_range %g does not fit LDS (num_rays %d)"
                                           : "the beam tables of max_range %g, num_rays %d exceed a workgroup's LDS (160 KB)",
                     h->max_range, num_rays);
     if (rc) return fail(rc, "launch planning failed");
@@ -1286,7 +1220,8 @@ int launch_fan(rl_method *h, const float *d_poses, int n_poses, float fov, int n
     h->last_plan = pl;
     FanParams f = make_fan(h, n_poses, fov, num_rays);
     if (h->timing == 1) HIPCHK(hipEventRecord(h->ev0, stream));
-    const FanLaunch L{h, m, pl, cx, f, d_poses, n_poses, fov, num_rays, d_out, d_hits, d_steps, crash, stream, aux};
+    const FanLaunch L{h, m, pl, cx, f, d_poses, n_poses, fov, num_rays, d_out, d_hits, d_steps, crash, stream, aux,
+                      dim3(pl.grid), dim3(pl.block), (size_t)pl.lds_bytes};
     switch (pl.kernel) {
     case RL_K_LUT_LDS:
     case RL_K_LUT_FAN:
@@ -1334,7 +1269,7 @@ static int launch_rays(rl_method *h, const float *d_ins, long n, float *d_out, i
     const rl_map *m = h->map;
     FanParams f = make_fan(h, 0, 0.0f, 1);
     long want = (n + WG - 1) / WG;
-    long cap = (long)m->n_cu * h->grid_mult;
+    long cap = (long)m->n_cu * h->opt.grid_mult;
     int grid = (int)std::max(1L, std::min(want, cap));
     if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
     int rc;
@@ -1349,14 +1284,14 @@ static int launch_rays(rl_method *h, const float *d_ins, long n, float *d_out, i
     } else if (h->kind == RL_BRESENHAM) {
         hipLaunchKernelGGL(bl_rays_kernel, dim3(grid), dim3(256), 0, stream, m->mp, f, d_ins, n,
                            d_out);
-    } else if (h->variant == 3) {
+    } else if (h->opt.variant == 3) {
         // audit mode: the upstream 2-argument form stated literally, one lane per row
         const LiteralParams lt = make_literal(m);
         if (d_hits || d_steps)
             hipLaunchKernelGGL((rm_literal_kernel<true, true>), dim3(grid), dim3(256), 0, stream, m->mp, f, lt, d_ins, n, d_out, d_hits, d_steps);
         else
             hipLaunchKernelGGL((rm_literal_kernel<false, true>), dim3(grid), dim3(256), 0, stream, m->mp, f, lt, d_ins, n, d_out, d_hits, d_steps);
-    } else if (h->variant >= 1 && n <= INT_MAX) {
+    } else if (h->opt.variant >= 1 && n <= INT_MAX) {
         // a ray is a pose with one beam at alpha = 0: fan(num_rays = 1, fov = 0) gives exactly
         // (cos, sin) of the heading as direction, and the stream kernel packs 64 rays per block
         return launch_fan(h, d_ins, (int)n, 0.0f, 1, d_out, d_hits, d_steps, nullptr, stream);
@@ -1418,7 +1353,7 @@ extern "C" int rl_method_plan_fan(rl_method *h, int n_poses, int num_rays, int w
     }
     std::lock_guard<std::mutex> lk(h->mu);
     int rc = RL_OK;
-    if (h->code_map && (h->kind == RL_RM || h->kind == RL_RM_GPU) && h->variant >= 1) {
+    if (h->opt.code_map && (h->kind == RL_RM || h->kind == RL_RM_GPU) && h->opt.variant >= 1) {
         if ((rc = set_device(h->map))) return rc;
         std::shared_lock<std::shared_mutex> tl(h->map->tables_mu);
         if ((rc = ensure_step_map(h, h->stream))) return rc;

@@ -268,16 +268,10 @@ struct rl_method {
     int theta_disc = 0;
     float noise_std = 0;
     uint64_t noise_seed = 0, ray_offset = 0;
-    int variant = 1;             // 0: chunk kernel (K1); 1: binned + banded + lane-refill stream kernel (K1b)
-    int grid_mult = 8;           // workgroups per CU for the persistent launches (8 resident: <= 80 SGPRs, <= 64 VGPRs)
-    int low_water = -1;          // stream kernel: refill when <= this many lanes (per ray slot) still march.  -1 = auto: 12, and 20
-                                 // for the several-rays-per-lane launches that derive their records in LDS (small and mid-size
-                                 // batches: +3 % with four in flight; big batches lose 3-6 % above 12: profiles/r03/ab_low_water.txt)
-    int sort_poses = 1;          // stream kernel: order poses by map tile
-    int xcd_bands = 8;           // stream kernel: bands of the sorted list, one per XCD
+    rl_plan_opts opt{};          // the planner's options: plan::default_opts with variant = the kind's default (opts_of adds
+                                 // code_entries); rl_method_set_option's option table names which of them an option sets
     int timing = 0;              // 1: HIP events around every launch sequence (rl_last_kernel_ms);
                                  // 2: around the march kernel only (pose binning excluded)
-    int lut_debug = 0;
     int drain_prio = 0;
     int spec_drain = 8;          // one ray per lane: value-speculating drain loop once <= this many lanes are live (0 = off)
     int spec_stretch = 16;       //   ... after this many plain samples, and between two attempts whose first prediction failed
@@ -289,7 +283,6 @@ struct rl_method {
     int handoff_cap = 16;        //   ... rays per wave handed over (8, 16, 32 or 64)
     int handoff_wg = 256;        //   ... workgroup size of the leftover launch (64, 128 or 256)
     int nt_store = 1;            // ranges leave the stream kernels with non-temporal stores (0: plain — a consumer kernel reads them next)
-    int wg_threads = 1024;       // stream kernel: workgroup size (256/512/1024) sharing one ray stream
     // GiantLUT (K3)
     DevBuf lut;
     uint64_t lut_epoch = ~0ull;
@@ -305,17 +298,7 @@ struct rl_method {
     int cd_geom_rows = -1, cd_geom_cols = -1;              // map shape the constants were made for
     bool cd_sort_attr = false;
     bool cd_counts_clean = false;                          // bucket counters are all zero (see ensure_cddt)
-    int slots = 0;               // stream kernel: rays per lane; 2 (3: inline form only) = plain-range launches on the tiled step
-                                 // map keep two loads in flight per lane and compact a dry wave's last rays into one slot;
-                                 // 0 = auto (launch_plan.h: 2 from 2^23 rays per launch up, from 2^20 on maps beyond the
-                                 // small-map bound; callers that keep several launches in flight set 2: +15..30 %)
-    int cddt_theta_min = 32768;                            // poses per launch from which the CDDT look-ups run theta-major (0: never)
-    int cddt_search = 1;                                   // theta-major search kernel: 1 = look-ups prepared once per pose (round 5), 0 = round 4's
-    int cddt_sort = 0;                                     // per-bin fan kernel walks the poses in map-tile order, XCD bands
-                                                           // (measured: -13 % at 4096 poses - the binning launch and no
-                                                           // reuse at that density -, +3 % at 32768: off by default)
     int cddt_lds_sort = (int)CDDT_LDS_SORT;                // buckets up to this size are sorted in LDS (diagnostics: lower it)
-    int cddt_bins_kernel = 1;                              // 1: one query per (pose, theta bin); 0: per ray
     DevBuf blpad;                // K2b: padded normal + transposed bit maps (bl_pad_bits_kernel)
     BlPad blp{};
     uint64_t blpad_epoch = ~0ull;
@@ -354,24 +337,14 @@ struct rl_method {
                                   // profiles/r04/host_pointer_rate.txt)
     std::vector<double> edge_host; // the car-outline table last uploaded to `edge` (re-sent only when it changes)
     int *pin_flag = nullptr;       // pinned landing slot for the crash index
-    int bin_multi_min = 8192;    // batches at least this large bin poses with grid-wide kernels
     int tile_stripe = -1;        // binning order: tile rows per stripe walked column-major (rm_kernels.h tile_key); 0: row-major, -1: by xcd_bands
     int bin_ppw = POSES_PER_WG;  // ... poses per workgroup of those kernels
-    int order_inline = 1;        // big maps, stripe_max..8192 poses: keys-only binning launch + INLINE march
-    int stripe_max = 1536;       // big maps, inline_max..stripe_max poses: no binning launch, workgroups compact
-                                 // their own row-stripe band of the pose list (0 = off)
-    int inline_map_kb = 2048;    // maps up to this size (f32 cells) never take the binning launch while the records fit LDS
-    int run_log2 = -1;           // stream interleave granularity: runs of 2^run_log2 blocks; -1 = by batch size
-    int tiled = 1;               // step map with 4 rows interleaved (a 128-B line = 4x8 cells); 0 = row-major
     int pdt_tiled = -1;          // layout the padded copy was built with
     uint32_t pdt_k4 = 0, pdt_mask = 0;
     size_t pdt_base_off = 0;     // tiled: the column bias (pad << 4 bytes) folded into the base address
     // the CODE map (option code_map = 2): the step map as u16 palette codes + the palette (rm_kernels.h), built next to
     // the float32 step map by ensure_step_map; code_n = palette entries with the two stop codes, 0 = none (option off,
     // geometry does not fit, or more distinct steps than plan::CODE_MAX_ENTRIES)
-    int code_map = 2;
-    int code_min_rays = 1 << 22;
-    int tail_pct = 0, tail_wg_pct = 50;
     DevBuf cmap, cval, cidx, ctab, cnum;
     uint32_t *pin_cnum = nullptr;
     int code_n = 0;
@@ -379,11 +352,6 @@ struct rl_method {
     int cstride = 0;             // M of the code map's address
     uint32_t ck4 = 0, cmask = 0;
     size_t cbase_off = 0;
-    int slice_log2 = 30;         // launches are cut into pose slices below 2^slice_log2 rays
-    int bin_generic = 0;         // diagnostics: force the generic single-workgroup binning kernel
-    int inline_prep = 1;         // tiny batches: no binning launch, workgroups derive their own records
-    int inline_max = 512;        //   ... below this many poses (measured: wins below ~512, loses above)
-    int debug_stamps = 0;        // diagnostics: per-wave start/end stamps of the stream kernel
     int last_grid = 0;
     void *last_dbg = nullptr;    // stamps buffer of the last launch (in its context)
     rl_launch_plan last_plan{};  // what the last fan launch of this handle was planned as (plan::plan_fan)

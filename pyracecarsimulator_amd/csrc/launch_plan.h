@@ -43,33 +43,43 @@ struct In {
 // else has one form.  Option "variant" overrides either way.
 inline int default_variant(int kind) { return kind == RL_RM ? 3 : 1; }
 
+// The defaults of every planner option: rl_plan_default_opts, and every handle's options at rl_method_create (with
+// variant set to the kind's default there).  rl_method_set_option's clamps are abi_fan.hip's option table.
 inline void default_opts(rl_plan_opts &o)
 {
     std::memset(&o, 0, sizeof o);
-    o.variant = -1;           // the default of the kind (default_variant): resolved by plan_fan
-    o.grid_mult = 8;          // workgroups (x256 threads) per CU of a persistent launch
-    o.wg_threads = 1024;
-    o.low_water = -1;                          // (auto: abi_fan.hip)
-    o.sort_poses = 1;
-    o.xcd_bands = 8;
-    o.slots = 0;              // auto
-    o.tiled = 1;
-    o.inline_prep = 1;
-    o.inline_max = 512;
-    o.inline_map_kb = 2048;
-    o.stripe_max = 1536;      // (profiles/r03/plan_sweep.txt: row stripes tie with the keys-only binning launch at 1024
-                              //  poses and lose 8..20 % at 2048..2560 on both big maps)
-    o.order_inline = 1;
-    o.bin_multi_min = 8192;
-    o.bin_generic = 0;
-    o.run_log2 = -1;
-    o.cddt_bins = 1;
-    o.cddt_sort = 0;
-    o.cddt_theta_min = 32768;
-    o.cddt_search = 1;
+    o.variant = -1;           // the default of the kind (default_variant): resolved by plan_fan.  0: chunk kernel (K1);
+                              // 1: binned + banded + lane-refill stream kernel (K1b)
+    o.grid_mult = 8;          // workgroups (x256 threads) per CU of a persistent launch (8 resident: <= 80 SGPRs, <= 64 VGPRs)
+    o.wg_threads = 1024;      // stream kernel: workgroup size (256/512/1024) sharing one ray stream
+    o.low_water = -1;         // stream kernel: refill when <= this many lanes (per ray slot) still march.  -1 = auto: 12, and 20
+                              // for the several-rays-per-lane launches that derive their records in LDS (small and mid-size
+                              // batches: +3 % with four in flight; big batches lose 3-6 % above 12: profiles/r03/ab_low_water.txt)
+    o.sort_poses = 1;         // stream kernel: order poses by map tile
+    o.xcd_bands = 8;          // stream kernel: bands of the sorted list, one per XCD
+    o.slots = 0;              // stream kernel: rays per lane; 2 (3: inline form only) = plain-range launches on the tiled step
+                              // map keep two loads in flight per lane and compact a dry wave's last rays into one slot;
+                              // 0 = auto (plan_one: 2 from 2^23 rays per launch up, from 2^20 on maps beyond the small-map
+                              // bound; callers that keep several launches in flight set 2: +15..30 %)
+    o.tiled = 1;              // step map with 4 rows interleaved (a 128-B line = 4x8 cells); 0 = row-major
+    o.inline_prep = 1;        // tiny batches: no binning launch, workgroups derive their own records
+    o.inline_max = 512;       //   ... below this many poses (measured: wins below ~512, loses above)
+    o.inline_map_kb = 2048;   // maps up to this size (f32 cells) never take the binning launch while the records fit LDS
+    o.stripe_max = 1536;      // big maps, inline_max..stripe_max poses: no binning launch, workgroups compact their own
+                              // row-stripe band of the pose list (0 = off) (profiles/r03/plan_sweep.txt: row stripes tie with
+                              // the keys-only binning launch at 1024 poses and lose 8..20 % at 2048..2560 on both big maps)
+    o.order_inline = 1;       // big maps, stripe_max..8192 poses: keys-only binning launch + INLINE march
+    o.bin_multi_min = 8192;   // batches at least this large bin poses with grid-wide kernels
+    o.bin_generic = 0;        // diagnostics: force the generic single-workgroup binning kernel
+    o.run_log2 = -1;          // stream interleave granularity: runs of 2^run_log2 blocks; -1 = by batch size
+    o.cddt_bins = 1;          // CDDT, 1: one query per (pose, theta bin); 0: per ray
+    o.cddt_sort = 0;          // CDDT per-bin fan kernel walks the poses in map-tile order, XCD bands (measured: -13 % at 4096
+                              // poses - the binning launch and no reuse at that density -, +3 % at 32768: off by default)
+    o.cddt_theta_min = 32768; // poses per launch from which the CDDT look-ups run theta-major (0: never)
+    o.cddt_search = 1;        // theta-major search kernel: 1 = look-ups prepared once per pose (round 5), 0 = round 4's
     o.lut_debug = 0;
-    o.debug_stamps = 0;
-    o.slice_log2 = 30;
+    o.debug_stamps = 0;       // diagnostics: per-wave start/end stamps of the stream kernel
+    o.slice_log2 = 30;        // launches are cut into pose slices below 2^slice_log2 rays
     o.code_map = 2;           // u16 palette codes wherever the palette fits (profiles/r06/ab_code_map.txt)
     o.code_min_rays = 1 << 22;   // (cfg2's 4096 x 1081 and up)
     o.code_entries = 0;       // (a handle fills in its map's palette size)
@@ -196,6 +206,66 @@ inline void bl_window(float max_range, int num_rays, int &R, int &ww, bool &use_
 
 inline const char *tf(bool b) { return b ? "true" : "false"; }
 
+// The rm_fan_stream_kernel<AUX, CRASH, NT, INLINE, TILED, SLOTS, LIT, CODE> instances the library compiles: abi_fan.hip
+// builds its dispatch table from this predicate and the planner names nothing outside it.
+struct StreamKey {
+    bool a, c;
+    int n;
+    bool inl, t;
+    int s;
+    bool lit;
+    int code;
+};
+constexpr bool stream_instance(const StreamKey &k)
+{
+    return (k.n == 256 || k.n == 512 || k.n == 1024) && k.s >= 1 && k.s <= 3 && (k.code == 0 || k.code == 2) &&
+           (!k.lit || (!k.a && k.n == 1024 && k.inl && k.t && k.s <= 2)) &&     // upstream-literal: INLINE, tiled map
+           (k.code == 0 || (k.s == 2 && !k.a && k.t && k.n == 1024)) &&          // u16 code map: two rays per lane
+           (k.s == 1 || (!k.a && k.t)) &&                                        // several rays per lane: tiled, no aux
+           (k.s != 3 || (!k.c && k.n == 1024 && k.code == 0)) &&                 // three: plain ranges, 1024 lanes
+           (!k.inl || k.n == 1024 ||                                             // INLINE: 1024 lanes, and the 512-lane
+            (k.n == 512 && !k.c && k.t && k.s == 2 && !k.lit && k.code == 0));   //   A/B form of round 5
+}
+// the tuple as a table index (mixed radix, 576 slots) and back; -1 outside the instance set
+constexpr int STREAM_KEYS = 2 * 2 * 3 * 2 * 2 * 3 * 2 * 2;
+constexpr int stream_index(const StreamKey &k)
+{
+    return !stream_instance(k) ? -1
+        : ((((((k.a * 2 + k.c) * 3 + (k.n == 1024 ? 2 : k.n == 512)) * 2 + k.inl) * 2 + k.t) * 3 + k.s - 1) * 2 + k.lit) * 2 +
+              (k.code == 2);
+}
+constexpr StreamKey stream_key_at(int i)
+{
+    return {i / 288 % 2 != 0, i / 144 % 2 != 0, 256 << (i / 48 % 3), i / 24 % 2 != 0, i / 12 % 2 != 0, i / 4 % 3 + 1,
+            i / 2 % 2 != 0, i % 2 ? 2 : 0};
+}
+inline StreamKey stream_key(const rl_launch_plan &p)
+{
+    return {p.aux != 0, p.crash != 0, p.block, p.record_source != 0, p.tiled != 0, p.slots, p.kernel == RL_K_RM_STREAM_LIT,
+            p.code};
+}
+// the name of a stream plan (the real symbol: all eight template arguments, as rocprofv3's kernel trace prints them);
+// RL_ERR_INVALID when the plan names an instance that is not compiled
+inline int name_stream(rl_launch_plan *p)
+{
+    const StreamKey k = stream_key(*p);
+    std::snprintf(p->name, sizeof p->name, "scan::rm_fan_stream_kernel<%s, %s, %d, %s, %s, %d, %s, %d>", tf(k.a), tf(k.c), k.n,
+                  tf(k.inl), tf(k.t), k.s, tf(k.lit), k.code);
+    return stream_instance(k) ? RL_OK : RL_ERR_INVALID;
+}
+
+// The theta-major CDDT launch forms (RL_K_CDDT_THETA): the planner names one, launch_cddt_theta reads it back from
+// the plan's name (rl_launch_plan has no field of its own for it).
+enum CddtTheta { CDDT_THETA_SEARCH, CDDT_THETA_SEARCH2, CDDT_THETA_FUSED, CDDT_THETA_FORMS };
+constexpr const char *CDDT_THETA_NAMES[CDDT_THETA_FORMS] = {
+    "scan::cddt_theta_search_kernel", "scan::cddt_theta_search2_kernel", "scan::cddt_theta_fused_kernel"};
+inline int cddt_theta_form(const rl_launch_plan &p)
+{
+    for (int i = 0; i < CDDT_THETA_FORMS; ++i)
+        if (!std::strcmp(p.name, CDDT_THETA_NAMES[i])) return i;
+    return -1;
+}
+
 inline int plan_one(const In &in, rl_launch_plan *p)
 {
     const rl_plan_opts &o = in.o;
@@ -254,7 +324,7 @@ inline int plan_one(const In &in, rl_launch_plan *p)
                 const int per_cu = std::max(1, std::min(8, (160 * 1024) / std::max(p->lds_bytes, 1)));
                 p->grid = (int)std::max(1L, std::min((long)(n_poses + 63) / 64, (long)n_cu * per_cu));
                 p->bands = 1;
-                std::snprintf(p->name, sizeof p->name, "scan::cddt_theta_fused_kernel");
+                std::snprintf(p->name, sizeof p->name, "%s", CDDT_THETA_NAMES[CDDT_THETA_FUSED]);
                 return RL_OK;
             }
             const int unit_poses = o.cddt_search ? 256 : 128;
@@ -263,7 +333,7 @@ inline int plan_one(const In &in, rl_launch_plan *p)
             p->ch = ppb_log2;
             p->nl = in.theta_disc | 1;                 // LDS row stride of the fan kernel
             p->lds_bytes = ((p->nl + 1) << ppb_log2) * (int)sizeof(float);      // R rows of ppb poses + their headings
-            std::snprintf(p->name, sizeof p->name, o.cddt_search ? "scan::cddt_theta_search2_kernel" : "scan::cddt_theta_search_kernel");
+            std::snprintf(p->name, sizeof p->name, "%s", CDDT_THETA_NAMES[o.cddt_search ? CDDT_THETA_SEARCH2 : CDDT_THETA_SEARCH]);
             return RL_OK;
         }
         if (o.cddt_bins && in.theta_disc <= num_rays && in.theta_disc <= 8192) {
@@ -331,13 +401,12 @@ inline int plan_one(const In &in, rl_launch_plan *p)
             if (as_stream.o.slots == 3) as_stream.o.slots = 2;
             rl_launch_plan q;
             std::memset(&q, 0, sizeof q);
-            if (plan_one(as_stream, &q) == RL_OK && q.kernel == RL_K_RM_STREAM && q.record_source != 0 && q.tiled &&
-                q.block == 1024 && q.slots <= 2) {
+            const int rc = plan_one(as_stream, &q);
+            if (rc == RL_ERR_INVALID) return rc;
+            if (rc == RL_OK && q.kernel == RL_K_RM_STREAM && q.record_source != 0 && q.tiled && q.block == 1024 && q.slots <= 2) {
                 *p = q;
                 p->kernel = RL_K_RM_STREAM_LIT;
-                std::snprintf(p->name, sizeof p->name, "scan::rm_fan_stream_kernel<false, %s, 1024, true, true, %d, true, %d>",
-                              tf(in.crash), q.slots, q.code);
-                return RL_OK;
+                return name_stream(p);
             }
         }
         if (in.crash) return RL_ERR_UNSUPPORTED;
@@ -474,7 +543,7 @@ inline int plan_one(const In &in, rl_launch_plan *p)
     p->bands = bands;
     p->k_max = inl ? k_max : 0;
     const int slots = slots_req;
-    bool a = in.aux, c = in.crash, t = tiled_opt;
+    const bool t = tiled_opt;
     int s = 1;
     if (slots == 3 && !in.aux && !in.crash && tiled_opt && (inl || nt == 1024)) {
         s = 3;
@@ -492,9 +561,7 @@ inline int plan_one(const In &in, rl_launch_plan *p)
     p->lds_bytes = (int)(inl ? inl_tables + (size_t)k_max * INLINE_REC_BYTES + lds_extra
                              : (s >= 2 ? tables_b + drain_bytes(p->block)
                                        : ((size_t)STREAM_HDR + (in.crash ? 4 : 2) * (size_t)num_rays) * sizeof(float)));
-    // (the label is the real symbol: all eight template arguments, as rocprofv3's kernel trace prints them)
-    std::snprintf(p->name, sizeof p->name, "scan::rm_fan_stream_kernel<%s, %s, %d, %s, %s, %d, false, %d>", tf(a), tf(c),
-                  p->block, tf(inl), tf(t), s, p->code);
+    if (name_stream(p) != RL_OK) return RL_ERR_INVALID;
     // (a fan of ~20 000 beams: the beam tables alone exceed a workgroup's LDS — say so instead of failing the launch)
     if (p->lds_bytes > DEVICE_LDS_BYTES) return RL_ERR_UNSUPPORTED;
     return RL_OK;

@@ -381,6 +381,53 @@ def test_launch_plan_survives_zeroed_and_out_of_range_options():
     assert L.rl_plan_fan(_lib.RL_RM_GPU, 256, 2049, 2049, 300.0, 0, C.byref(o), 4096, 32, 0, 1, C.byref(pl2)) == -4       # RL_ERR_UNSUPPORTED
 
 
+def _stream_instance(a, c, n, inl, t, s, lit, code):
+    """csrc/launch_plan.h stream_instance, restated: the rm_fan_stream_kernel<AUX, CRASH, NT, INLINE, TILED, SLOTS, LIT,
+    CODE> instances the library compiles."""
+    return (n in (256, 512, 1024) and 1 <= s <= 3 and code in (0, 2)
+            and (not lit or (not a and n == 1024 and inl and t and s <= 2))
+            and (code == 0 or (s == 2 and not a and t and n == 1024))
+            and (s == 1 or (not a and t))
+            and (s != 3 or (not c and n == 1024 and code == 0))
+            and (not inl or n == 1024 or (n == 512 and not c and t and s == 2 and not lit and code == 0)))
+
+
+def test_every_stream_plan_names_a_compiled_instance_and_every_instance_is_reached():
+    """The planner names only instances of the set abi_fan.hip compiles its dispatch table from (53 of them), and a
+    sweep over batch, slots, wg_threads, tiled, inline_prep, code map, aux and crash reaches every one.  Every plan
+    succeeds, or is RL_ERR_UNSUPPORTED where it is today: the fused crash test of the upstream-literal arithmetic
+    where its stream form cannot run."""
+    import ctypes as C
+    import itertools
+    tf = lambda b: "true" if b else "false"
+    instances = {"scan::rm_fan_stream_kernel<%s, %s, %d, %s, %s, %d, %s, %d>" % (tf(a), tf(c), n, tf(i), tf(t), s, tf(l), cd)
+                 for a, c, i, t, l in itertools.product((0, 1), repeat=5) for n in (256, 512, 1024) for s in (1, 2, 3)
+                 for cd in (0, 2) if _stream_instance(a, c, n, i, t, s, l, cd)}
+    assert len(instances) == 53
+    L = _lib.lib()
+    o0 = _lib.PlanOpts()
+    _lib.check(L.rl_plan_default_opts(C.byref(o0)))
+    pl = _lib.LaunchPlan()
+    seen, unsupported = set(), 0
+    for kind, n, slots, wg, tiled, inl, code_n, aux, crash in itertools.product(
+            (_lib.RL_RM, _lib.RL_RM_GPU), (1, 200, 1537, 8192), (0, 1, 2, 3), (1024, 512, 256), (0, 1), (0, 1), (0, 626),
+            (0, 1), (0, 1)):
+        o = _lib.PlanOpts.from_buffer_copy(o0)
+        o.slots, o.wg_threads, o.tiled, o.inline_prep, o.code_entries, o.code_min_rays = slots, wg, tiled, inl, code_n, 0
+        rc = L.rl_plan_fan(kind, 256, 2049, 2049, 300.0, 0, C.byref(o), n, 1081, aux, crash, C.byref(pl))
+        if rc == -4:                                                    # RL_ERR_UNSUPPORTED
+            assert kind == _lib.RL_RM and crash, (kind, n, slots, wg, tiled, inl, code_n, aux)
+            unsupported += 1
+            continue
+        assert rc == 0, (rc, kind, n, slots, wg, tiled, inl, code_n, aux, crash)
+        name = pl.name.decode()
+        if "rm_fan_stream_kernel" in name:
+            assert name in instances, name
+            seen.add(name)
+    assert seen == instances, sorted(instances - seen)
+    assert unsupported == 672                # (the count before the stream instance set was written down)
+
+
 def test_launch_plan_falls_back_when_the_tiled_step_map_or_the_lds_does_not_fit():
     """A very elongated map (padded side > 2^20) would need a tiled pitch of K > 24, beyond the 24-bit multiply
     of the march's address: the plan marches on the row-major step map with one ray per lane instead; a fan
