@@ -167,7 +167,9 @@ __global__ __launch_bounds__(256) void cddt_edges_kernel(const uint8_t *__restri
 }
 
 // rl_map_stamp_cells: occupied cells laid over the map (the other car's outline of the two-player tick,
-// scripts/two_player/rcs_two_player.py:110-116): indices outside the grid are skipped, as the reference's guard skips them
+// scripts/two_player/rcs_two_player.py:110-116): indices outside the grid are skipped.  For idx >= rows * cols that is the
+// reference's guard; a negative index is a deliberate divergence (the reference's numpy map wraps -size <= idx < 0 to a
+// cell from the end, this skips it).  PyOMap.stamp_cells filters on the caller's integer values before narrowing to int32.
 // ONE workgroup: the previous stamp's cells go back to the base map's values, then the new cells are set, and the new
 // list is kept (device side) as the next call's "previous" — a tick costs one launch, not a copy of the grid
 __global__ __launch_bounds__(1024) void stamp_swap_kernel(uint8_t *__restrict__ occ, const uint8_t *__restrict__ base,

@@ -43,6 +43,18 @@ def _yaw_from_quaternion(q) -> float:
     return math.atan2(2.0 * (w * z + x * y), 1.0 - 2.0 * (y * y + z * z))
 
 
+def stamp_indices(flat_idx, n_cells):
+    """The cells ``PyOMap.stamp_cells`` stamps: the indices ``0 <= idx < n_cells`` of ``flat_idx`` as C-contiguous
+    int32, compared on their original integer value (an int64 ``2**32 + 5`` is skipped, not wrapped to cell 5).
+    An empty input of any dtype gives no cells; a non-empty input that is not integer raises ``TypeError``."""
+    a = np.asarray(flat_idx).ravel()
+    if a.size == 0:
+        return np.zeros(0, dtype=np.int32)
+    if not np.issubdtype(a.dtype, np.integer):
+        raise TypeError("stamp_cells: cell indices must be integers, got dtype %s" % a.dtype)
+    return np.ascontiguousarray(a[(a >= 0) & (a < n_cells)], dtype=np.int32)
+
+
 class PyOMap:
     """Occupancy grid + world transform, resident on one MI355X.
 
@@ -118,16 +130,20 @@ class PyOMap:
 
     def stamp_cells(self, flat_idx, value=255):
         """The two-player tick without re-uploading the grid (rl_map_stamp_cells): the occupancy becomes the BASE map
-        (as constructed / last ``update``d) with the cells ``flat_idx`` (row * width + col; out-of-range ones are
-        skipped like the reference's guard, scripts/two_player/rcs_two_player.py:113) occupied, tables rebuilt on the
-        device.  Each stamp replaces the previous one; an empty list restores the base map."""
-        idx = np.ascontiguousarray(flat_idx, dtype=np.int32).ravel()
+        (as constructed / last ``update``d) with the cells ``flat_idx`` (row * width + col) set, tables rebuilt on the
+        device.  Each stamp replaces the previous one; an empty list restores the base map.
+
+        Indices are filtered on their integer value before they are narrowed to int32: cells with
+        ``0 <= idx < rows * cols`` are stamped, every other index is skipped.  For ``idx >= rows * cols`` that is the
+        reference's guard (scripts/two_player/rcs_two_player.py:113).  Negative indices are a deliberate divergence:
+        the reference's guard lets them through and its numpy map wraps ``-size <= idx < 0`` to a cell from the end;
+        here they are skipped.  A non-empty input that is not an integer array raises ``TypeError``."""
+        idx = stamp_indices(flat_idx, self.occ.size)
         if getattr(self, "_base_occ", None) is None:
             self._base_occ = self.occ.copy()
         _lib.check(_lib.lib().rl_map_stamp_cells(self._h, idx.ctypes.data_as(_lib.i32p), int(idx.size), int(value) & 0xff))
         occ = self._base_occ.copy()
-        ok = idx[(idx >= 0) & (idx < occ.size)]
-        occ.reshape(-1)[ok] = 1 if (int(value) & 0xff) else 0
+        occ.reshape(-1)[idx] = 1 if (int(value) & 0xff) else 0
         self.occ = occ
 
     def distance_transform(self):

@@ -219,6 +219,32 @@ def one_case(seed):
             out = np.empty(n, np.float32); m.calc_range_fan(poses, out, fov, B)
             assert np.array_equal(out, om2.rm_fan_libm(poses, fov, B, step_coeff=0.999)[0]), "after map update"
             m.close(); omap.update(occ)
+            # stamp a random outline under warm handles (drawn from their own stream: the other draws stay what they were)
+            rs = np.random.default_rng(seed ^ 0x57A)
+            sub = poses[:64]; ns = len(sub) * B
+            warm = [("RMGPU code map", range_libc.PyRayMarchingGPU(omap, mrx), lambda o: o.rm_fan(sub, fov, B, 1.0)[0]),
+                    ("BL stamp", range_libc.PyBresenhamsLine(omap, mrx), lambda o: o.bl_fan(sub, fov, B)[0])]
+            warm[0][1].set_option("code_map", 2); warm[0][1].set_option("code_min_rays", 0); warm[0][1].set_option("slots", 2)
+            if rows * cols <= 6000:
+                warm.append(("LUT stamp", range_libc.PyGiantLUTCast(omap, mrx, 30), lambda o: o.lut_fan(o.lut_build(30, nthreads=8), sub, fov, B)))
+            elif rows * cols <= 20000:
+                warm.append(("CDDT stamp", range_libc.PyCDDTCast(omap, mrx, 16), lambda o: o.cddt_fan(16, sub, fov, B)))
+            for _, m, _ in warm:
+                out = np.empty(ns, np.float32); m.calc_range_fan(sub, out, fov, B)
+            r0_, c0_ = int(rs.integers(0, rows)), int(rs.integers(0, cols))
+            hh, hw = int(rs.integers(0, 6)), int(rs.integers(0, 6))
+            cells = [(r_, c_) for r_ in range(r0_ - hh, r0_ + hh + 1) for c_ in range(c0_ - hw, c0_ + hw + 1)
+                     if (abs(r_ - r0_) == hh or abs(c_ - c0_) == hw) and 0 <= r_ < rows and 0 <= c_ < cols]
+            idx = np.array([r_ * cols + c_ for r_, c_ in cells], np.int64)
+            omap.stamp_cells(idx)
+            occ3 = occ.copy(); occ3.reshape(-1)[idx] = 1
+            om3 = O.OracleMap(occ3, res, origin, mrx)
+            assert np.array_equal(omap.distance_transform(), om3.dt), "EDT after stamp"
+            for what, m, ref in warm:
+                out = np.empty(ns, np.float32); m.calc_range_fan(sub, out, fov, B)
+                assert np.array_equal(out, ref(om3)), "%s after stamp %s" % (what, m.last_plan()["name"])
+                m.close()
+            omap.stamp_cells([])
             if r.random() < 0.25:
                 # one handle over several devices (the box has one GPU: device 0 two or three times): the batch cut into
                 # pose blocks, ranges with noise-free parity against the oracle, crash indices global

@@ -110,3 +110,33 @@ def test_map_update_in_place_does_not_grow_memory():
         tick()
     leaked = base - _free_bytes(torch)
     assert leaked <= 4 << 20, "%.1f MB grown over 300 ticks" % (leaked / 2**20)
+
+
+def test_stamp_growth_cycles_return_device_memory():
+    """rl_map_stamp_cells growing its index buffers (n past stamp_cap) and shrinking back, over and over, then the map
+    destroyed: the device memory is back at its starting level."""
+    torch = pytest.importorskip("torch")
+    g = maps.make_maze(200, cell=25, wall=2, p=0.4, seed=9)
+    B, fov = 180, 6.2
+    poses = maps.sample_free_poses(g, 8, 4)
+    out = np.empty(len(poses) * B, np.float32)
+    rng = np.random.default_rng(2)
+
+    def life(cycles):
+        omap = range_libc.PyOMap(g)
+        m = range_libc.PyRayMarchingGPU(omap, 120)
+        for _ in range(cycles):
+            for n in (10, 5000, 10):
+                omap.stamp_cells(rng.choice(g.occ.size, n, replace=False))
+                m.calc_range_fan(poses, out, fov, B)
+        m.close()
+        omap.close()
+
+    life(2)                                            # warm-up: runtime pools, code objects
+    gc.collect()
+    base = _free_bytes(torch)
+    for _ in range(20):                                # each life grows the buffers once, then reuses them
+        life(3)
+    gc.collect()
+    leaked = base - _free_bytes(torch)
+    assert leaked <= 4 << 20, "%.1f MB not returned after 20 maps of stamp growth cycles" % (leaked / 2**20)

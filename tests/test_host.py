@@ -535,3 +535,80 @@ def test_every_noise_call_site_has_a_gpu_case():
         assert case.strip() and kernel.strip()
     assert sum(found.values()) == len(NOISE_SITES)
     assert found == table
+
+
+def test_every_table_cache_guard_has_a_gpu_case():
+    """tests/test_gpu_map_mutation.py TABLE_CACHES names the case that checks each lazily rebuilt per-handle table
+    (a ``*_epoch == <map>->epoch`` guard under csrc/) after a map mutation: a new cache must add a row (and a case)."""
+    from test_gpu_map_mutation import TABLE_CACHES
+    csrc = os.path.join(ROOT, "pyracecarsimulator_amd", "csrc")
+    guard = re.compile(r"\b(\w+_epoch)\s*==\s*(?:\w+->)?(?:m|map)->epoch\b")
+    found = {}
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".h", ".hip", ".cpp")):
+            continue
+        with open(os.path.join(csrc, name), errors="replace") as f:
+            for line in f:
+                for field in guard.findall(line.split("//")[0]):
+                    found[(name, field)] = found.get((name, field), 0) + 1
+    table = {}
+    for fname, field, what, case in TABLE_CACHES:
+        table[(fname, field)] = table.get((fname, field), 0) + 1
+        assert what.strip() and case.strip()
+    assert found, "no epoch guard found under csrc/"
+    assert found == table
+
+
+def test_stamp_indices_filter_on_the_integer_value():
+    """PyOMap.stamp_cells' index filter: 0 <= idx < size on the caller's values, before the int32 narrowing (2**32 + 5
+    is skipped, not cell 5); negative indices are skipped; duplicates and lists pass; empty inputs of any dtype give no
+    cells; non-integer input raises."""
+    size = 50 * 61
+    vals = [-1, -size, size, 2**31, 2**32 + 5, 2**63 - 1, 7, 12, 12, size - 1, 0]
+    keep = [7, 12, 12, size - 1, 0]
+    for idx in (np.array(vals, np.int64), vals, np.array(vals, np.int64).reshape(-1, 1)):
+        got = range_libc.stamp_indices(idx, size)
+        assert got.dtype == np.int32 and got.flags.c_contiguous and got.tolist() == keep
+    assert range_libc.stamp_indices(np.array([3, 2**64 - 1], np.uint64), size).tolist() == [3]
+    assert range_libc.stamp_indices(np.array([3, -4, 30000], np.int16), size).tolist() == [3]
+    for empty in ([], (), np.zeros(0), np.zeros((0, 3), np.int8), np.zeros(0, np.uint64)):
+        got = range_libc.stamp_indices(empty, size)
+        assert got.dtype == np.int32 and got.size == 0
+    for bad in (np.array([1.0]), [1.5, 2.0], np.array([True]), ["3"]):
+        with pytest.raises(TypeError):
+            range_libc.stamp_indices(bad, size)
+
+
+def test_stamp_cells_host_mirror_and_c_arguments(monkeypatch):
+    """stamp_cells with the C call stubbed: the host mirror is the base map with exactly the in-range cells set (or
+    cleared with value 0), the C side gets the filtered int32 list, and an empty list restores the base."""
+    import ctypes as C
+    calls = []
+
+    class Stub:
+        def rl_map_stamp_cells(self, h, p, n, value):
+            calls.append((np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.int32), n, value))
+            return 0
+
+    monkeypatch.setattr(range_libc._lib, "lib", lambda: Stub())
+    rows, cols = 50, 61
+    size = rows * cols
+    base = np.zeros((rows, cols), np.uint8)
+    base[-1, :] = base[:, 0] = 1                                  # (cell 5 is free: a wrapped 2**32 + 5 would show)
+    omap = object.__new__(range_libc.PyOMap)
+    omap.occ, omap.height, omap.width, omap._h = base.copy(), rows, cols, C.c_void_p()
+    vals = [-1, -size, size, 2**31, 2**32 + 5, 2**63 - 1, 7 * cols + 9, 3 * cols + 4, 3 * cols + 4]
+    omap.stamp_cells(np.array(vals, np.int64))
+    want = base.copy()
+    want.reshape(-1)[[7 * cols + 9, 3 * cols + 4]] = 1
+    assert np.array_equal(omap.occ, want) and omap.occ.reshape(-1)[5] == 0
+    assert calls[-1][0].tolist() == [7 * cols + 9, 3 * cols + 4, 3 * cols + 4] and calls[-1][2] == 255
+    omap.stamp_cells([0, cols, 2 * cols + 5], value=0)           # erase: the previous stamp is gone, two walls cleared
+    want = base.copy()
+    want.reshape(-1)[[0, cols]] = 0
+    assert np.array_equal(omap.occ, want) and calls[-1][2] == 0
+    omap.stamp_cells([])
+    assert np.array_equal(omap.occ, base) and calls[-1][1] == 0
+    with pytest.raises(TypeError):
+        omap.stamp_cells(np.array([3.0]))
+    omap._h = None
