@@ -299,6 +299,53 @@ int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, const doubl
                            double *velocities_or_null, float *steers_or_null, float *scan_poses_or_null,
                            double *states_trace_or_null);
 
+/* ---- the steering policy network ---------------------------------------------------------------
+ * The reference's second steering source (scripts/policy.py:17-33, Policy.predict_action; driven at
+ * scripts/policy_driver.py:30-49 and used by MCTS at scripts/mcts.py:252-256): a dense ReLU chain over the
+ * window scan[in_start, in_start + dims[0]) of each scan, one steering angle out.  The reference's network is
+ * 720 -> 64 -> 128 -> 128 -> 64 -> 1 with a ReLU after every layer but the last, in_start 180, clip = scale = 15.
+ *
+ * The canonical float32 form (every path is bit-identical to it: rl_policy_eval, rl_policy_eval_device,
+ * rl_car_drive_policy, and the host statement tests/policy_statement.py):
+ *   x_k   = (r <= clip) ? r / scale : 1.0f for r = scan[in_start + k]   (a correctly rounded f32 division; NaN and
+ *           +inf give 1.0, as policy.py's `x if x <= 15.0 else 15.0`; equal to its f64 i/15.0 cast to f32)
+ *   acc_j = +0.0f, then acc_j = fmaf(x_k, W[k][j], acc_j) for k = 0, 1, ..., K-1 in ascending order
+ *   y_j   = acc_j + b_j (a separate rounding: MatMul then BiasAdd);  ReLU: y_j > 0 ? y_j : 0.0f
+ *   steer = y_0 of the last layer.
+ * No split-K, no tree sums.  TF sums in an unspecified order, so the reference's bits cannot be pinned; against a
+ * float64 forward pass of the reference's weights this form differs by at most 3.8e-6 rad (p99 2.1e-6) over 20 000
+ * synthetic scans (gated at 1e-5 in tests/test_policy_host.py).
+ *
+ * rl_policy_create: weights[l] is dims[l] x dims[l+1] row-major float32 (TF's MatMul operand), biases[l] has
+ * dims[l+1] values, relu[l] != 0 puts a ReLU after layer l.  Caps (RL_ERR_UNSUPPORTED beyond them): 8 layers,
+ * input width 1024, hidden widths 256, one output.  The weights are copied to the device.
+ * rl_policy_eval: n_scans rows of `size` float32 ranges on the host in, n_scans steers out (synchronous).
+ * rl_policy_eval_device: the same on device pointers, enqueued on the given stream (null = the null stream).
+ * Errors (RL_ERR_INVALID; the handle stays usable): null pointers, n_scans < 0, size < in_start + dims[0].
+ * Kernel: policy_mlp_kernel (policy_kernels.h), the whole chain in one launch.                           */
+typedef struct rl_policy rl_policy;
+int rl_policy_create(int device, int n_layers, const int *dims, const float *const *weights,
+                     const float *const *biases, const unsigned char *relu, int in_start, float clip, float scale,
+                     rl_policy **out);
+void rl_policy_destroy(rl_policy *p);
+int rl_policy_eval(rl_policy *p, const float *scans, int n_scans, int size, float *steers);
+int rl_policy_eval_device(rl_policy *p, const float *d_scans, int n_scans, int size, float *d_steers,
+                          void *stream_or_null);
+
+/* closed-loop policy roll-outs: rl_car_drive_followgap's loop (same arguments, same outputs, same noise offsets
+ * and chunking) with step 5 replaced by the network: steer = rl_policy_eval of the tick's scan.  steers_or_null
+ * records that raw f32 output (NaN on the crash tick).  The car gets clamp((double)steer, -steer_clip,
+ * steer_clip) with steer_clip > 0 (scripts/policy_driver.py:33, +-0.4189), otherwise (double)steer, which
+ * Car::control clamps later (as scripts/mcts.py passes the raw output to drive()).  Errors (RL_ERR_INVALID, the
+ * handles stay usable): those of rl_car_drive_followgap with p in g's place, and num_rays < in_start + dims[0].
+ * Per tick: the fan launch sequence of h's planner, policy_mlp_kernel over every car's scan, then one
+ * policy_tick_kernel (crash ballot and car step, drive_kernels.h).                                           */
+int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const double *states_in, const double *speeds,
+                        const float *steer0_or_null, int n_rollouts, int n_ticks, double dt, double scan_dist_to_base,
+                        float fov, int num_rays, const double *edge, double crash_thresh, double steer_clip,
+                        int *first_crashed, double *states_out_or_null, double *velocities_or_null,
+                        float *steers_or_null, float *scan_poses_or_null, double *states_trace_or_null);
+
 /* Car::setCarEdgeDistances (racecar/src/racecar.cpp:239-292; called at
  * scripts/racecar_simulator_v2.py:47-50): distance from the lidar to the car's outline along each of
  * num_rays beams starting one increment after min_ang — the table every crash test above takes as

@@ -7,5 +7,6 @@ HIP kernels for gfx950 behind the C ABI in ``include/scanlib.h``.
 from . import maps, racecar, range_libc             # noqa: F401
 from .scan_simulator import ScanSimulator2D          # noqa: F401
 from .racecar_simulator import RacecarSimulator      # noqa: F401
+from .policy import Policy                           # noqa: F401
 
-__all__ = ["maps", "racecar", "range_libc", "ScanSimulator2D", "RacecarSimulator"]
+__all__ = ["maps", "racecar", "range_libc", "ScanSimulator2D", "RacecarSimulator", "Policy"]

@@ -7,6 +7,7 @@
 #include "car_kernels.h"
 #include "consumer_kernels.h"
 #include "drive_kernels.h"
+#include "policy_kernels.h"
 #include "probe_kernels.h"
 
 struct rl_car {
@@ -16,7 +17,8 @@ struct rl_car {
     CarParams P{};
     hipStream_t stream = nullptr;
     DevBuf states, actions, poses, states_out, vel, ranges, edge, first;
-    DevBuf speeds, steer0, tr_steers, tr_poses, tr_states;     // rl_car_drive_followgap
+    DevBuf speeds, steer0, tr_steers, tr_poses, tr_states;     // rl_car_drive_followgap, rl_car_drive_policy
+    DevBuf mlp;                                                // rl_car_drive_policy: the network's steers of a tick
     std::mutex mu;
 };
 
@@ -79,7 +81,7 @@ extern "C" void rl_car_destroy(rl_car *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (DevBuf *b : {&c->states, &c->actions, &c->poses, &c->states_out, &c->vel, &c->ranges, &c->edge, &c->first,
-                      &c->speeds, &c->steer0, &c->tr_steers, &c->tr_poses, &c->tr_states})
+                      &c->speeds, &c->steer0, &c->tr_steers, &c->tr_poses, &c->tr_states, &c->mlp})
         b->release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -408,6 +410,241 @@ extern "C" int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, 
     h->nt_store = nt_store;
     if (rc) {
         (void)hipStreamSynchronize(st);           // nothing of this call is left in flight on the handles' buffers
+        return rc;
+    }
+    HIPCHK(hipMemcpyAsync(first_crashed, c->first.p, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+    if (states_out_or_null) HIPCHK(hipMemcpyAsync(states_out_or_null, c->states.p, (size_t)R * 88, hipMemcpyDeviceToHost, st));
+    if (velocities_or_null) HIPCHK(hipMemcpyAsync(velocities_or_null, c->vel.p, rows * 8, hipMemcpyDeviceToHost, st));
+    if (steers_or_null) HIPCHK(hipMemcpyAsync(steers_or_null, c->tr_steers.p, rows * 4, hipMemcpyDeviceToHost, st));
+    if (scan_poses_or_null) HIPCHK(hipMemcpyAsync(scan_poses_or_null, c->tr_poses.p, rows * 12, hipMemcpyDeviceToHost, st));
+    if (states_trace_or_null)
+        HIPCHK(hipMemcpyAsync(states_trace_or_null, c->tr_states.p, rows * 88, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
+}
+
+// ---------------------------------------------------------------- the steering policy network (policy_kernels.h)
+struct rl_policy {
+    int device = 0;
+    PolicyParams P{};                  // device pointers into `weights`
+    hipStream_t stream = nullptr;
+    DevBuf weights, scans, steers;
+    std::mutex mu;
+};
+
+extern "C" int rl_policy_create(int device, int n_layers, const int *dims, const float *const *weights,
+                                const float *const *biases, const unsigned char *relu, int in_start, float clip,
+                                float scale, rl_policy **out)
+{
+    if (!dims || !weights || !biases || !relu || !out) return fail(RL_ERR_INVALID, "rl_policy_create: null pointer");
+    if (n_layers < 1) return fail(RL_ERR_INVALID, "rl_policy_create: n_layers must be >= 1 (got %d)", n_layers);
+    if (n_layers > PM_MAX_LAYERS)
+        return fail(RL_ERR_UNSUPPORTED, "rl_policy_create: at most %d layers (got %d)", PM_MAX_LAYERS, n_layers);
+    for (int l = 0; l <= n_layers; ++l)
+        if (dims[l] < 1) return fail(RL_ERR_INVALID, "rl_policy_create: dims[%d] = %d must be >= 1", l, dims[l]);
+    for (int l = 0; l < n_layers; ++l)
+        if (!weights[l] || !biases[l]) return fail(RL_ERR_INVALID, "rl_policy_create: null pointer (layer %d)", l);
+    if (dims[0] > PM_MAX_IN) return fail(RL_ERR_UNSUPPORTED, "rl_policy_create: input width %d > %d", dims[0], PM_MAX_IN);
+    for (int l = 1; l < n_layers; ++l)
+        if (dims[l] > PM_MAX_W)
+            return fail(RL_ERR_UNSUPPORTED, "rl_policy_create: width %d of layer %d > %d", dims[l], l, PM_MAX_W);
+    if (dims[n_layers] != 1)
+        return fail(RL_ERR_UNSUPPORTED, "rl_policy_create: one output only (got %d)", dims[n_layers]);
+    if (in_start < 0) return fail(RL_ERR_INVALID, "rl_policy_create: in_start must be >= 0 (got %d)", in_start);
+    int ndev = rl_device_count();
+    if (ndev <= 0) return fail(RL_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(RL_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
+    // one block: per layer W [K][ceil4(N)] then b [ceil4(N)], zero-padded (16-byte rows for the float4 loads)
+    std::vector<float> host;
+    std::vector<size_t> offW(n_layers), offB(n_layers);
+    for (int l = 0; l < n_layers; ++l) {
+        const int K = dims[l], N = dims[l + 1], Np = (N + 3) & ~3;
+        offW[l] = host.size();
+        host.resize(host.size() + (size_t)K * Np, 0.0f);
+        for (int k = 0; k < K; ++k)
+            std::memcpy(&host[offW[l] + (size_t)k * Np], weights[l] + (size_t)k * N, (size_t)N * sizeof(float));
+        offB[l] = host.size();
+        host.resize(host.size() + Np, 0.0f);
+        std::memcpy(&host[offB[l]], biases[l], (size_t)N * sizeof(float));
+    }
+    rl_policy *p = new (std::nothrow) rl_policy();
+    if (!p) return fail(RL_ERR_NOMEM, "out of host memory");
+    p->device = device;
+    int rc;
+    if (hipSetDevice(device) != hipSuccess ||
+        hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess) {
+        delete p;
+        return fail(RL_ERR_HIP, "stream creation failed");
+    }
+    if ((rc = p->weights.ensure(host.size() * sizeof(float))) ||
+        hipMemcpy(p->weights.p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        rl_policy_destroy(p);
+        return rc ? rc : fail(RL_ERR_HIP, "rl_policy_create: weight upload failed");
+    }
+    p->P.n_layers = n_layers;
+    p->P.relu = 0;
+    for (int l = 0; l <= n_layers; ++l) p->P.dims[l] = dims[l];
+    for (int l = 0; l < n_layers; ++l) {
+        p->P.W[l] = (const float *)p->weights.p + offW[l];
+        p->P.b[l] = (const float *)p->weights.p + offB[l];
+        if (relu[l]) p->P.relu |= 1u << l;
+    }
+    p->P.in_start = in_start;
+    p->P.clip = clip;
+    p->P.scale = scale;
+    *out = p;
+    return RL_OK;
+}
+
+extern "C" void rl_policy_destroy(rl_policy *p)
+{
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    if (p->stream) (void)hipStreamSynchronize(p->stream);
+    p->weights.release();
+    p->scans.release();
+    p->steers.release();
+    if (p->stream) (void)hipStreamDestroy(p->stream);
+    delete p;
+}
+
+static int policy_args(const rl_policy *p, int n_scans, int size)
+{
+    if (n_scans < 0) return fail(RL_ERR_INVALID, "n_scans must be >= 0 (got %d)", n_scans);
+    if (size < p->P.in_start + p->P.dims[0])
+        return fail(RL_ERR_INVALID, "scans of %d beams do not hold the policy's window [%d, %d)", size, p->P.in_start,
+                    p->P.in_start + p->P.dims[0]);
+    return RL_OK;
+}
+
+static int policy_launch(rl_policy *p, const float *d_scans, int n_scans, int size, float *d_steers, hipStream_t st)
+{
+    if (n_scans == 0) return RL_OK;
+    hipLaunchKernelGGL(policy_mlp_kernel, dim3((n_scans + PM_CARS - 1) / PM_CARS), dim3(64), 0, st, p->P, d_scans,
+                       n_scans, size, d_steers);
+    HIPCHK(hipGetLastError());
+    return RL_OK;
+}
+
+extern "C" int rl_policy_eval(rl_policy *p, const float *scans, int n_scans, int size, float *steers)
+{
+    if (!p || (n_scans > 0 && (!scans || !steers))) return fail(RL_ERR_INVALID, "rl_policy_eval: null pointer");
+    int rc = policy_args(p, n_scans, size);
+    if (rc || n_scans == 0) return rc;
+    std::lock_guard<std::mutex> lk(p->mu);
+    HIPCHK(hipSetDevice(p->device));
+    const size_t bytes = (size_t)n_scans * size * sizeof(float);
+    if ((rc = p->scans.ensure(bytes)) || (rc = p->steers.ensure((size_t)n_scans * sizeof(float)))) return rc;
+    HIPCHK(hipMemcpyAsync(p->scans.p, scans, bytes, hipMemcpyHostToDevice, p->stream));
+    if ((rc = policy_launch(p, (const float *)p->scans.p, n_scans, size, (float *)p->steers.p, p->stream))) {
+        (void)hipStreamSynchronize(p->stream);
+        return rc;
+    }
+    HIPCHK(hipMemcpyAsync(steers, p->steers.p, (size_t)n_scans * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return RL_OK;
+}
+
+extern "C" int rl_policy_eval_device(rl_policy *p, const float *d_scans, int n_scans, int size, float *d_steers,
+                                     void *hip_stream)
+{
+    if (!p || (n_scans > 0 && (!d_scans || !d_steers)))
+        return fail(RL_ERR_INVALID, "rl_policy_eval_device: null pointer");
+    int rc = policy_args(p, n_scans, size);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(p->mu);
+    HIPCHK(hipSetDevice(p->device));
+    return policy_launch(p, d_scans, n_scans, size, d_steers, (hipStream_t)hip_stream);
+}
+
+// ---------------------------------------------------------------- closed-loop policy roll-outs
+// policy_tick_kernel<ROWS>, ROWS = 1 ... FG_ROWS (the crash ballot holds ROWS beams per lane)
+typedef void (*policy_tick_fn)(DriveParams, DriveBufs, const float *, double, int);
+template <int... R>
+static constexpr std::array<policy_tick_fn, sizeof...(R)> policy_tick_make(std::integer_sequence<int, R...>)
+{
+    return {{policy_tick_kernel<R + 1>...}};
+}
+static const std::array<policy_tick_fn, FG_ROWS> policy_tick_table =
+    policy_tick_make(std::make_integer_sequence<int, FG_ROWS>());
+
+extern "C" int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const double *states_in,
+                                   const double *speeds, const float *steer0_or_null, int R, int n_ticks, double dt,
+                                   double scan_dist_to_base, float fov, int num_rays, const double *edge,
+                                   double crash_thresh, double steer_clip, int *first_crashed,
+                                   double *states_out_or_null, double *velocities_or_null, float *steers_or_null,
+                                   float *scan_poses_or_null, double *states_trace_or_null)
+{
+    if (!c || !h || !p || (R > 0 && (!states_in || !speeds || !edge || !first_crashed)))
+        return fail(RL_ERR_INVALID, "rl_car_drive_policy: null pointer");
+    if (!c->reps.empty() || !h->reps.empty())
+        return fail(RL_ERR_INVALID, "rl_car_drive_policy is single-device only: pass ordinary (not multi-device) handles");
+    if (c->device != h->map->device || p->device != c->device)
+        return fail(RL_ERR_INVALID, "car (device %d), range method (device %d) and policy (device %d) must share one device",
+                    c->device, h->map->device, p->device);
+    if (R < 0 || n_ticks <= 0) return fail(RL_ERR_INVALID, "n_rollouts >= 0 and n_ticks > 0 required (got %d, %d)", R, n_ticks);
+    if (num_rays < 10 || num_rays > 64 * FG_ROWS)
+        return fail(RL_ERR_INVALID, "num_rays must lie in [10, %d] (got %d)", 64 * FG_ROWS, num_rays);
+    if ((long)R * num_rays >= (1L << 31)) return fail(RL_ERR_INVALID, "n_rollouts * num_rays must stay below 2^31");
+    int rc = policy_args(p, R, num_rays);
+    if (rc || (rc = check_fan_args(h, R, fov, num_rays)) || R == 0) return rc;
+    std::scoped_lock lk(c->mu, h->mu, p->mu);
+    std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
+    HIPCHK(hipSetDevice(c->device));
+    const size_t rows = (size_t)R * n_ticks, n_rays = (size_t)R * num_rays;
+    if ((rc = c->states.ensure((size_t)R * 11 * 8)) || (rc = c->speeds.ensure((size_t)R * 8)) ||
+        (rc = c->steer0.ensure((size_t)R * 4)) || (rc = c->first.ensure((size_t)R * 4)) ||
+        (rc = c->poses.ensure((size_t)R * 12)) || (rc = c->ranges.ensure(n_rays * 4)) ||
+        (rc = c->edge.ensure((size_t)num_rays * 8)) || (rc = c->mlp.ensure((size_t)R * 4)) ||
+        (velocities_or_null && (rc = c->vel.ensure(rows * 8))) || (steers_or_null && (rc = c->tr_steers.ensure(rows * 4))) ||
+        (scan_poses_or_null && (rc = c->tr_poses.ensure(rows * 12))) ||
+        (states_trace_or_null && (rc = c->tr_states.ensure(rows * 88))))
+        return rc;
+    hipStream_t st = c->stream;
+    HIPCHK(hipMemcpyAsync(c->states.p, states_in, (size_t)R * 11 * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->speeds.p, speeds, (size_t)R * 8, hipMemcpyHostToDevice, st));
+    if (steer0_or_null) HIPCHK(hipMemcpyAsync(c->steer0.p, steer0_or_null, (size_t)R * 4, hipMemcpyHostToDevice, st));
+    else HIPCHK(hipMemsetAsync(c->steer0.p, 0, (size_t)R * 4, st));
+    HIPCHK(hipMemcpyAsync(c->edge.p, edge, (size_t)num_rays * 8, hipMemcpyHostToDevice, st));
+    if (velocities_or_null) HIPCHK(hipMemsetAsync(c->vel.p, 0xff, rows * 8, st));
+    if (steers_or_null) HIPCHK(hipMemsetAsync(c->tr_steers.p, 0xff, rows * 4, st));
+    if (scan_poses_or_null) HIPCHK(hipMemsetAsync(c->tr_poses.p, 0xff, rows * 12, st));
+    if (states_trace_or_null) HIPCHK(hipMemsetAsync(c->tr_states.p, 0xff, rows * 88, st));
+
+    DriveParams dp{};
+    dp.P = c->P;
+    dp.fg.size = num_rays;                        // (the crash ballot's beam count; FollowGap is not run)
+    dp.dt = dt;
+    dp.scan_dist_to_base = scan_dist_to_base;
+    dp.crash_thresh = crash_thresh;
+    dp.n_cars = R;
+    dp.n_ticks = n_ticks;
+    DriveBufs b{(double *)c->states.p, (const double *)c->speeds.p, (const float *)c->steer0.p, (const double *)c->edge.p,
+                (int *)c->first.p, (float *)c->poses.p, (const float *)c->ranges.p,
+                velocities_or_null ? (double *)c->vel.p : nullptr, steers_or_null ? (float *)c->tr_steers.p : nullptr,
+                scan_poses_or_null ? (float *)c->tr_poses.p : nullptr,
+                states_trace_or_null ? (double *)c->tr_states.p : nullptr};
+    hipLaunchKernelGGL(drive_start_kernel, dim3((R + 63) / 64), dim3(64), 0, st, dp, b);
+    HIPCHK(hipGetLastError());
+    // as rl_car_drive_followgap: plain stores for the ranges, the noise offset walks t R num_rays
+    const uint64_t base_off = h->ray_offset;
+    const int nt_store = h->nt_store;
+    h->nt_store = 0;
+    const policy_tick_fn tick = policy_tick_table[(num_rays + 63) / 64 - 1];
+    for (int t = 0; t < n_ticks && rc == RL_OK; ++t) {
+        h->ray_offset = base_off + (uint64_t)t * n_rays;
+        rc = launch_fan(h, (const float *)c->poses.p, R, fov, num_rays, (float *)c->ranges.p, nullptr, nullptr, nullptr, st);
+        if (rc == RL_OK) rc = policy_launch(p, (const float *)c->ranges.p, R, num_rays, (float *)c->mlp.p, st);
+        if (rc == RL_OK) {
+            tick<<<dim3((R + DRIVE_CARS - 1) / DRIVE_CARS), dim3(64 * DRIVE_CARS), 0, st>>>(dp, b, (const float *)c->mlp.p,
+                                                                                          steer_clip, t);
+            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "policy_tick_kernel launch failed");
+        }
+    }
+    h->ray_offset = base_off;
+    h->nt_store = nt_store;
+    if (rc) {
+        (void)hipStreamSynchronize(st);
         return rc;
     }
     HIPCHK(hipMemcpyAsync(first_crashed, c->first.p, (size_t)R * 4, hipMemcpyDeviceToHost, st));

@@ -4,8 +4,8 @@
 //   abi_fan.hip    rl_method_*: options, derived tables, the launch planner's C ABI, every fan / ray launch, the
 //                  device-pointer entry points, the single-device host-pointer paths, the fused crash test
 //   abi_multi.hip  the host-pointer entry points and their multi-device forms (one pose block per device)
-//   abi_car.hip    roll-out generator, FollowGap, closed-loop FollowGap roll-outs, 16-bit ranges, probes, the
-//                  car-outline table
+//   abi_car.hip    roll-out generator, FollowGap, the policy network, closed-loop FollowGap / policy roll-outs,
+//                  16-bit ranges, probes, the car-outline table
 #pragma once
 // (the units are built with -fvisibility=hidden: only the C ABI leaves the library)
 #pragma GCC visibility push(default)

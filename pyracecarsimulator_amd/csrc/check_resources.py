@@ -26,6 +26,9 @@ BOUNDS = [
     # closed-loop FollowGap roll-outs: scan, crash compare, FollowGap and the f64 car step in one wave per car, no spills
     ("scan::drive_tick_kernel<", {"scratch": 0}),
     ("scan::drive_start_kernel", {"scratch": 0}),
+    # the policy network: the micro-tile accumulators stay in registers; its drive tick as drive_tick_kernel's
+    ("scan::policy_mlp_kernel", {"scratch": 0}),
+    ("scan::policy_tick_kernel<", {"scratch": 0}),
 ]
 KEYS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy"}
 

@@ -77,6 +77,27 @@ __device__ inline void drive_step(const DriveParams &dp, const DriveBufs &b, int
     if (b.states_trace) drive_store_state(cs, b.states_trace + 11 * row);
 }
 
+// Car::isCrashed on car r's scan of this tick, one wave: (double)range - edge[j] < CRASH_THRESH for any beam (NaN never
+// crashes), as a ballot (wave-uniform).  raw: the scan, ROWS beams per lane (zero past num_rays).
+template <int ROWS>
+__device__ inline bool drive_crashed(const DriveParams &dp, const DriveBufs &b, int r, int lane, float (&raw)[ROWS])
+{
+    const int size = dp.fg.size;
+    const float *lidar = b.ranges + (size_t)r * size;
+    double edge[ROWS];
+#pragma unroll
+    for (int u = 0; u < ROWS; ++u) {
+        const bool in = u < ROWS - 1 || 64 * u + lane < size;
+        raw[u] = in ? lidar[64 * u + lane] : 0.0f;
+        edge[u] = in ? b.edge[64 * u + lane] : 0.0;
+    }
+    bool hit = false;
+#pragma unroll
+    for (int u = 0; u < ROWS; ++u)
+        if (u < ROWS - 1 || 64 * u + lane < size) hit |= ((double)raw[u] - edge[u]) < dp.crash_thresh;
+    return __ballot(hit) != 0;
+}
+
 // tick 0's step, one lane per car (b.state holds the start states)
 __global__ __launch_bounds__(64) void drive_start_kernel(DriveParams dp, DriveBufs b)
 {
@@ -101,25 +122,11 @@ __global__ __launch_bounds__(64 * DRIVE_CARS) void drive_tick_kernel(DriveParams
     __shared__ int step_next[DRIVE_CARS];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x * DRIVE_CARS + w;
-    const int size = dp.fg.size;
     bool go = false;
     float angle = 0.0f;
     if (r < dp.n_cars && b.first[r] < 0) {                // (wave-uniform)
-        const float *lidar = b.ranges + (size_t)r * size;
         float raw[ROWS];
-        double edge[ROWS];
-#pragma unroll
-        for (int u = 0; u < ROWS; ++u) {
-            const bool in = u < ROWS - 1 || 64 * u + lane < size;
-            raw[u] = in ? lidar[64 * u + lane] : 0.0f;
-            edge[u] = in ? b.edge[64 * u + lane] : 0.0;
-        }
-        // Car::isCrashed on one scan: (double)range - edge[j] < CRASH_THRESH for any beam (NaN never crashes)
-        bool hit = false;
-#pragma unroll
-        for (int u = 0; u < ROWS; ++u)
-            if (u < ROWS - 1 || 64 * u + lane < size) hit |= ((double)raw[u] - edge[u]) < dp.crash_thresh;
-        if (__ballot(hit)) {
+        if (drive_crashed<ROWS>(dp, b, r, lane, raw)) {
             if (lane == 0) b.first[r] = t;                // frozen from here: its trace rows after t stay NaN
         } else {
             angle = followgap_bits_eval<ROWS>(raw, dp.fg, bits[w]);
@@ -134,6 +141,41 @@ __global__ __launch_bounds__(64 * DRIVE_CARS) void drive_tick_kernel(DriveParams
     __syncthreads();
     if (threadIdx.x < DRIVE_CARS && step_next[threadIdx.x])
         drive_step(dp, b, blockIdx.x * DRIVE_CARS + threadIdx.x, t + 1, (double)steer_next[threadIdx.x]);
+}
+
+// closed-loop policy roll-outs (rl_car_drive_policy): tick t after its scan and policy_mlp_kernel's answer to it (mlp[R],
+// every car's scan, frozen ones included): the crash test and the step of tick t + 1, as drive_tick_kernel with the
+// network's steer in place of FollowGap's.  steer_clip > 0: the car gets clamp((double)steer, -clip, clip)
+// (scripts/policy_driver.py:33); otherwise (double)steer, clamped later by Car::control (scripts/mcts.py).
+template <int ROWS>
+__global__ __launch_bounds__(64 * DRIVE_CARS) void policy_tick_kernel(DriveParams dp, DriveBufs b, const float *mlp,
+                                                                      double steer_clip, int t)
+{
+    __shared__ double steer_next[DRIVE_CARS];
+    __shared__ int step_next[DRIVE_CARS];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * DRIVE_CARS + w;
+    bool go = false;
+    double steer = 0.0;
+    if (r < dp.n_cars && b.first[r] < 0) {                // (wave-uniform)
+        float raw[ROWS];
+        if (drive_crashed<ROWS>(dp, b, r, lane, raw)) {
+            if (lane == 0) b.first[r] = t;
+        } else {
+            const float a = mlp[r];
+            if (lane == 0 && b.steers) b.steers[(size_t)r * dp.n_ticks + t] = a;
+            steer = (double)a;
+            if (steer_clip > 0.0) steer = fmin(fmax(steer, -steer_clip), steer_clip);
+            go = t + 1 < dp.n_ticks;
+        }
+    }
+    if (lane == 0) {
+        steer_next[w] = steer;
+        step_next[w] = go;
+    }
+    __syncthreads();
+    if (threadIdx.x < DRIVE_CARS && step_next[threadIdx.x])
+        drive_step(dp, b, blockIdx.x * DRIVE_CARS + threadIdx.x, t + 1, steer_next[threadIdx.x]);
 }
 
 }  // namespace scan

@@ -1,0 +1,143 @@
+// policy_kernels.h — the steering policy network (rl_policy_*, rl_car_drive_policy; include/scanlib.h): a dense ReLU
+// chain over a window of each scan, the MLP of the reference's scripts/policy.py (720 -> 64 -> 128 -> 128 -> 64 -> 1),
+// for R scans in one launch, in the project's canonical float32 form (scanlib.h):
+//   x_k   = (r <= clip) ? r / scale : 1.0f,  r = scan[in_start + k]        (correctly rounded division)
+//   acc_j = +0.0f;  acc_j = fmaf(x_k, W[k][j], acc_j) for k = 0, 1, ..., K-1 in ascending order
+//   y_j   = acc_j + b_j;  ReLU: y_j > 0 ? y_j : 0.0f
+// No split-K, no tree sums: every output is one k-ordered fmaf chain, so any tiling of cars x neurons gives the same
+// bits.
+//
+// Shape: one wave per workgroup owns PM_CARS cars and runs the whole chain for them.  Each lane holds micro-tiles of
+// PM_MC cars x 4 neurons in registers (PM_MC * 4 v_fma_f32 per k for one ds_read of PM_MC activations and one
+// 16-byte weight load).  The activations stay in LDS (k-major, [K][PM_CARS], one buffer: a layer's outputs wait in
+// registers until every lane has read its inputs); only the steers are written.  Layer 1's 184 KB of weights exceed
+// LDS, so every layer's weights are staged in k-blocks of PM_KB rows (at most 16 KB): each lane issues its share of a
+// block's loads before its first store, served by L2 (every workgroup reads the same 313 KB in the same order), and
+// the k-steps then read LDS.  (Reading the rows straight from L1/L2 inside the k loop, one dependent load per k-step,
+// measured ~230 us per launch at any R; staging with a load-wait-store loop ~180 us: latency-bound both.)  Layer 1's inputs come in the same k-blocks straight from the range
+// buffer, the input transform fused in.  Zero padding (neurons to a multiple
+// of 4, cars to PM_CARS) never enters a kept output's chain.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace scan {
+
+constexpr int PM_MAX_LAYERS = 8;       // caps of rl_policy_create (RL_ERR_UNSUPPORTED beyond them)
+constexpr int PM_MAX_IN = 1024;
+constexpr int PM_MAX_W = 256;
+constexpr int PM_CARS = 8;             // cars per workgroup (one wave)
+constexpr int PM_MC = 2;               // cars per lane micro-tile
+constexpr int PM_KB = 16;              // k-block: weight rows (every layer) and inputs (layer 1) staged in LDS
+constexpr int PM_MT = (PM_CARS / PM_MC) * (PM_MAX_W / 4) / 64;   // micro-tiles per lane at the widest layer
+
+struct PolicyParams {
+    int n_layers;
+    int dims[PM_MAX_LAYERS + 1];       // dims[0] = input width, dims[n_layers] = 1
+    const float *W[PM_MAX_LAYERS];     // [dims[l]][ceil4(dims[l+1])] row-major, zero-padded columns
+    const float *b[PM_MAX_LAYERS];     // [ceil4(dims[l+1])], zero-padded
+    uint32_t relu;                     // bit l: layer l ends in a ReLU
+    int in_start;
+    float clip, scale;
+};
+
+__device__ inline float policy_input(float r, float clip, float scale)
+{
+    return (r <= clip) ? r / scale : 1.0f;      // NaN and +inf: 1.0 (scripts/policy.py's `x if x <= 15.0 else 15.0`)
+}
+
+// scans [n][size] (row stride `size`) -> out [n]
+__global__ __launch_bounds__(64) void policy_mlp_kernel(PolicyParams p, const float *__restrict__ scans, int n, int size,
+                                                        float *__restrict__ out)
+{
+    __shared__ float xin[PM_KB * PM_CARS];
+    __shared__ float act[PM_MAX_W * PM_CARS];
+    __shared__ float4 wl[PM_KB * (PM_MAX_W / 4)];
+    const int lane = threadIdx.x;
+    const int car0 = blockIdx.x * PM_CARS;
+    constexpr int CG = PM_CARS / PM_MC;
+    for (int l = 0; l < p.n_layers; ++l) {
+        const int K = p.dims[l], N = p.dims[l + 1], ng = (N + 3) >> 2, n_mt = CG * ng;
+        const float4 *__restrict__ W4 = reinterpret_cast<const float4 *>(p.W[l]);
+        int jg[PM_MT], cg[PM_MT];
+        float acc[PM_MT][PM_MC][4];
+#pragma unroll
+        for (int m = 0; m < PM_MT; ++m) {
+            const int mt = lane + 64 * m;
+            jg[m] = mt % ng;                   // neighbouring lanes: neighbouring neuron groups (conflict-free LDS rows)
+            cg[m] = mt / ng;
+#pragma unroll
+            for (int i = 0; i < PM_MC; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[m][i][j] = 0.0f;
+        }
+        for (int kb = 0; kb < K; kb += PM_KB) {
+            const int kn = min(PM_KB, K - kb);
+            __syncthreads();                   // (every lane is done with the previous block's wl / xin)
+            // the block's weight rows and inputs: every load issued before the first store (one latency per block)
+            // (indices clamped into the block, not branched on: the loads stay unconditional and back to back)
+            const int ne = kn * ng;
+            float4 wv[PM_KB];
+#pragma unroll
+            for (int u = 0; u < PM_KB; ++u) wv[u] = W4[(size_t)kb * ng + min(lane + 64 * u, ne - 1)];
+            float xv[PM_CARS];
+            if (l == 0) {
+                const int kk = p.in_start + kb + min(lane, kn - 1);
+#pragma unroll
+                for (int c = 0; c < PM_CARS; ++c) xv[c] = scans[(size_t)min(car0 + c, n - 1) * size + kk];
+            }
+#pragma unroll
+            for (int u = 0; u < PM_KB; ++u) wl[lane + 64 * u] = wv[u];    // (entries past ne: never read)
+            if (l == 0 && lane < kn) {
+#pragma unroll
+                for (int c = 0; c < PM_CARS; ++c)
+                    xin[lane * PM_CARS + c] = car0 + c < n ? policy_input(xv[c], p.clip, p.scale) : 0.0f;
+            }
+            __syncthreads();
+            const float *src = l == 0 ? xin : act + kb * PM_CARS;
+            for (int k = 0; k < kn; ++k) {
+#pragma unroll
+                for (int m = 0; m < PM_MT; ++m) {
+                    if (lane + 64 * m < n_mt) {
+                        const float *a = src + k * PM_CARS + cg[m] * PM_MC;
+                        const float4 w = wl[k * ng + jg[m]];
+#pragma unroll
+                        for (int i = 0; i < PM_MC; ++i) {
+                            const float x = a[i];
+                            acc[m][i][0] = fmaf(x, w.x, acc[m][i][0]);
+                            acc[m][i][1] = fmaf(x, w.y, acc[m][i][1]);
+                            acc[m][i][2] = fmaf(x, w.z, acc[m][i][2]);
+                            acc[m][i][3] = fmaf(x, w.w, acc[m][i][3]);
+                        }
+                    }
+                }
+            }
+        }
+        const bool relu = (p.relu >> l) & 1u, last = l == p.n_layers - 1;
+        const float4 *B4 = reinterpret_cast<const float4 *>(p.b[l]);
+        if (!last) __syncthreads();            // every lane is done reading act: the outputs overwrite it in place
+#pragma unroll
+        for (int m = 0; m < PM_MT; ++m) {
+            if (lane + 64 * m >= n_mt) continue;
+            const float4 bv = B4[jg[m]];
+            const float bb[4] = {bv.x, bv.y, bv.z, bv.w};
+#pragma unroll
+            for (int i = 0; i < PM_MC; ++i) {
+                const int c = cg[m] * PM_MC + i;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float y = acc[m][i][j] + bb[j];
+                    if (relu) y = y > 0.0f ? y : 0.0f;
+                    if (last) {
+                        if (jg[m] == 0 && j == 0 && car0 + c < n) out[car0 + c] = y;
+                    } else {
+                        act[(4 * jg[m] + j) * PM_CARS + c] = y;
+                    }
+                }
+            }
+        }
+        if (!last) __syncthreads();
+    }
+}
+
+}  // namespace scan

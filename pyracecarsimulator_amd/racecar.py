@@ -130,6 +130,44 @@ class CarBatch:
         final states (R, 11), velocities float64 (R, n_ticks), steers float32 (R, n_ticks)) and with
         ``trace=True`` also (lidar poses float32 (R, n_ticks, 3), states float64 (R, n_ticks, 11)).  Trace
         rows after a car's crash tick, and its steer at that tick, are NaN."""
+        R, n_ticks, states, speeds, st0, edge, first, out, vel, steers, poses, trace_st = self._drive_args(
+            states, n_ticks, speed, num_rays, edge, steer0, trace)
+        ptr = lambda a, t: a.ctypes.data_as(t) if a is not None else None
+        _lib.check(_lib.lib().rl_car_drive_followgap(
+            self._h, method._h, followgap._h, states.ctypes.data_as(f64p), speeds.ctypes.data_as(f64p),
+            ptr(st0, f32p), R, n_ticks, float(dt), float(scan_dist_to_base), float(fov), int(num_rays),
+            edge.ctypes.data_as(f64p), float(crash_thresh), first.ctypes.data_as(C.POINTER(C.c_int)),
+            out.ctypes.data_as(f64p), vel.ctypes.data_as(f64p), steers.ctypes.data_as(f32p), ptr(poses, f32p),
+            ptr(trace_st, f64p)))
+        if trace:
+            return first, out, vel, steers, poses, trace_st
+        return first, out, vel, steers
+
+    def drive_policy(self, method, policy, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
+                     scan_dist_to_base=0.275, dt=0.01, steer0=None, steer_clip=None, trace=False):
+        """Closed-loop policy roll-outs (``rl_car_drive_policy``): ``drive_followgap``'s loop with the steer of
+        every tick from ``policy`` (a ``policy.Policy``) — scripts/policy_driver.py's driver for R cars at once.
+        ``steer_clip`` None: the car gets the raw output (as scripts/mcts.py passes it to drive()); a value: the
+        output clamped to +-steer_clip (policy_driver.py uses 0.4189).  The steers returned are the raw network
+        outputs.  Arguments and results as ``drive_followgap``."""
+        R, n_ticks, states, speeds, st0, edge, first, out, vel, steers, poses, trace_st = self._drive_args(
+            states, n_ticks, speed, num_rays, edge, steer0, trace)
+        clip = 0.0 if steer_clip is None else float(steer_clip)
+        if steer_clip is not None and not clip > 0:
+            raise ValueError("steer_clip must be None or > 0")
+        ptr = lambda x, t: x.ctypes.data_as(t) if x is not None else None
+        _lib.check(_lib.lib().rl_car_drive_policy(
+            self._h, method._h, policy._h, states.ctypes.data_as(f64p), speeds.ctypes.data_as(f64p),
+            ptr(st0, f32p), R, n_ticks, float(dt), float(scan_dist_to_base), float(fov), int(num_rays),
+            edge.ctypes.data_as(f64p), float(crash_thresh), clip, first.ctypes.data_as(C.POINTER(C.c_int)),
+            out.ctypes.data_as(f64p), vel.ctypes.data_as(f64p), steers.ctypes.data_as(f32p), ptr(poses, f32p),
+            ptr(trace_st, f64p)))
+        if trace:
+            return first, out, vel, steers, poses, trace_st
+        return first, out, vel, steers
+
+    @staticmethod
+    def _drive_args(states, n_ticks, speed, num_rays, edge, steer0, trace):
         states = np.asarray(states)
         if states.dtype != np.float64 or states.ndim != 2 or states.shape[1] != 11:
             raise ValueError("states must be float64 (R, 11)")
@@ -158,16 +196,7 @@ class CarBatch:
         steers = np.empty((R, T), dtype=np.float32)
         poses = np.empty((R, T, 3), dtype=np.float32) if trace else None
         trace_st = np.empty((R, T, 11), dtype=np.float64) if trace else None
-        ptr = lambda a, t: a.ctypes.data_as(t) if a is not None else None
-        _lib.check(_lib.lib().rl_car_drive_followgap(
-            self._h, method._h, followgap._h, states.ctypes.data_as(f64p), speeds.ctypes.data_as(f64p),
-            ptr(st0, f32p), R, n_ticks, float(dt), float(scan_dist_to_base), float(fov), int(num_rays),
-            edge.ctypes.data_as(f64p), float(crash_thresh), first.ctypes.data_as(C.POINTER(C.c_int)),
-            out.ctypes.data_as(f64p), vel.ctypes.data_as(f64p), steers.ctypes.data_as(f32p), ptr(poses, f32p),
-            ptr(trace_st, f64p)))
-        if trace:
-            return first, out, vel, steers, poses, trace_st
-        return first, out, vel, steers
+        return R, n_ticks, states, speeds, st0, edge, first, out, vel, steers, poses, trace_st
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

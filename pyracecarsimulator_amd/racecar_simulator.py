@@ -13,7 +13,8 @@ it unchanged.  The two native pieces behind it are on the GPU:
 
 ``rolloutMany`` is the batched form of ``MCTS.rollout`` + ``checkCollisionMany``
 (scripts/mcts.py:202-245) for any number of roll-outs per call; ``driveFollowGapMany`` the closed
-loop of the simulator tick and simple_driver.py's FollowGap answer to every scan.
+loop of the simulator tick and simple_driver.py's FollowGap answer to every scan; ``drivePolicyMany`` the same loop
+steered by the policy network (scripts/policy_driver.py).
 """
 from __future__ import annotations
 
@@ -160,6 +161,16 @@ class RacecarSimulator:
                                         np.asarray(states, dtype=np.float64).reshape(-1, 11), n_ticks, speed,
                                         self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
                                         scan_dist_to_base=self.scan_dist_to_base)
+
+    def drivePolicyMany(self, states, n_ticks, policy, speed=2.0, steer_clip=None):
+        """``driveFollowGapMany`` with the steer of every tick from ``policy`` (a ``policy.Policy``, e.g.
+        ``Policy('model/frozen_model.pb')``): scripts/policy_driver.py's driver with ``steer_clip=0.4189``, MCTS's
+        roll-out policy (scripts/mcts.py:252-256, the raw output) with None.  Returns
+        ``CarBatch.drive_policy``'s tuple."""
+        return self.car.drive_policy(self.scan_simulator.scan_method, policy,
+                                     np.asarray(states, dtype=np.float64).reshape(-1, 11), n_ticks, speed,
+                                     self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
+                                     scan_dist_to_base=self.scan_dist_to_base, steer_clip=steer_clip)
 
     def stop(self):
         state = self.getState()
