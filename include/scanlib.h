@@ -346,6 +346,87 @@ int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const double *sta
                         int *first_crashed, double *states_out_or_null, double *velocities_or_null,
                         float *steers_or_null, float *scan_poses_or_null, double *states_trace_or_null);
 
+/* ---- the MCTS planner ----------------------------------------------------------------------------
+ * scripts/mcts.py's tree search (MCTS.mcts / mctsIteration / act / rollout, :109-245) for K independent trees in
+ * lock step on one device: every iteration adds exactly one node to every tree, so each iteration is one batched
+ * act and one batched roll-out with no host synchronisation in between.  The tree is the reference's, bit for bit,
+ * as tests/mcts_statement.py restates it:
+ *   - iteration (mctsIteration :150-185): a terminal node returns before it is visited; visits start at 1;
+ *     sum_of_visits is the children's visit sum; the selected child maximises reward/visits +
+ *     C sqrt(log(sum)/visits), the first strict maximum in insertion order (Python's max); the search descends
+ *     while sqrt(sum) < n_children; when the level below reports "not expanded" the new child goes under the
+ *     current node — a terminal child just descended into included (it gets a child and is not visited);
+ *     Node.propagate runs at every recursion level: the new child receives rv once, its j-th ancestor (j = 1:
+ *     the node it was added under) j + 1 times — j times when that node is terminal — as repeated adds; the root
+ *     none;
+ *   - the new action: source RL_MCTS_FG / RL_MCTS_NN: uniSample(children[0].action, uni_dev) when the node has
+ *     children, otherwise the node's stored answer (FollowGap::eval of the node's own scan as rl_followgap_eval
+ *     computes it, or rl_policy_eval's f32 output, widened to double, not clipped); RL_MCTS_RANDOM:
+ *     uniSample(0, 0.41) always.  The reference's Node.scan aliases the simulator's one scan buffer, so its
+ *     generateActionFromFG reads the LAST scan taken, not the node's; the node's own scan is used here (the
+ *     evident intent), evaluated once when the node is created;
+ *   - act (:187-200): Car::control + updatePosition(dt) with (speed, action) from the node's state, the lidar pose
+ *     of Car::getScanPose in f64 cast to f32, the scan with h, terminal = isCrashed(scan) >= 0.  mcts.py:195 tests
+ *     > 0, which a single scan never returns (0 or -2); the planner follows ros_interface.py:144 (>= 0), as
+ *     rl_car_drive_followgap does;
+ *   - rollout (:202-245), for non-terminal children (terminal ones take rv = crash_pen): L steps from the child's
+ *     state, a new (speed, steer) every action_every steps, steer = uniform(-max_steer, max_steer) drawn before
+ *     speed = uniform(0, max_speed); the car poses (not the lidar poses) scanned and tested as
+ *     rl_car_rollout_check does; rv = sum(vel[:index] or all L) / |action| with IEEE inf / NaN.
+ *   - root: the caller's state and recent action, never terminal, its scan taken at reset; the answer is the root
+ *     child with the most visits (the first of equals, :126-131).
+ * Exactness:
+ *   - draws: Philox-2x32-10 (scan_device.h's rounds) with key = noise_key(seeds[k]) (the noise seed fold), counter
+ *     (d, i) with i the iteration since reset: d = 0 the expansion draw, d = 1 + 2m / 2 + 2m roll-out action m's
+ *     steer / speed; u = ((out0 << 32 | out1) >> 11) 2^-53; uniform(lo, hi) = lo + (hi - lo) u (NumPy's formula,
+ *     each operation rounded); uniSample's lo = prediction - dev and hi = prediction + dev are rounded first;
+ *   - the reward sum is numpy.sum of the contiguous float64 velocities, bit for bit: 0.0 + P(v, n) with P NumPy's
+ *     pairwise_sum: a sequential sum from 0.0 for n < 8; for n <= 128 eight accumulators r[j] = v[j] + v[8+j] + ...
+ *     over the multiple-of-8 prefix, folded ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the tail added in order;
+ *     above 128, P(v, n2) + P(v + n2, n - n2) with n2 = n/2 - (n/2) % 8 (pinned by tests/test_mcts_host.py);
+ *   - UCB: separately rounded f64 operations, log(sum) from a table of the host's log(n) (Python's math.log) built
+ *     at create, the correctly rounded f64 sqrt (rl_mcts_probe_ucb pins it);
+ *   - noise: h's settings; ray ids with base = h's ray offset at reset: root scans base + k B; iteration i's act
+ *     scan of tree k base + (K + i K (1 + L) + k) B; its roll-out pose s base + (K + i K (1 + L) + K + k L + s) B
+ *     (B = num_rays).  h's options and ray offset read the same after every call.
+ *
+ * rl_mcts_create: c, h and the source's handle (g for FG, p for NN; borrowed, they must outlive the planner) on ONE
+ * device, multi-device handles refused.  edge: num_rays doubles (rl_car_edge_distances).  Errors (RL_ERR_INVALID):
+ * null pointers, K < 1, max_nodes < 1, L outside [1, 512], action_every < 1, an unknown source or one without its
+ * handle, num_rays outside [10, 1280], num_rays < in_start + dims[0] for NN, K L num_rays >= 2^31, handles on
+ * different devices.
+ * rl_mcts_reset: the K roots (states K x 11, recent actions K, one 64-bit seed per tree); takes the root scans.
+ * rl_mcts_run: n_iterations iterations, synchronous; n iterations equal n/2 followed by n/2.  Refused before any
+ * launch (RL_ERR_INVALID) without a reset, or when 1 + the iterations since reset would exceed max_nodes; a
+ * failed launch leaves the planner needing a reset.  The range method's own refusals (those of
+ * rl_car_rollout_check) come back with the same code.
+ * rl_mcts_best: per tree the best root action (NaN and visits -1 before the first iteration), its visits, and the
+ * node count.  rl_mcts_read_tree: tree `tree`'s node arrays in creation order (node 0 = root, parent -1, sibling /
+ * child links -1 = none), any output pointer may be null; crash = the roll-out's crash index (-(L+1): none), -1
+ * for the root and terminal nodes; answer = the stored expansion answer (NaN for RANDOM); n_nodes_out = how many.
+ * rl_mcts_probe_ucb: the device's UCB key of n (reward, visits >= 1, 1 <= sum <= 2^24) triples.
+ * Kernels: mcts_kernels.h.                                                                                    */
+typedef struct rl_mcts rl_mcts;
+typedef enum rl_mcts_source { RL_MCTS_FG = 0, RL_MCTS_NN = 1, RL_MCTS_RANDOM = 2 } rl_mcts_source;
+typedef struct rl_mcts_params {
+    int n_trees, max_nodes, rollout_steps, action_every, source;
+    double speed, dt, scan_dist_to_base, C, crash_pen, uni_dev, max_steer, max_speed;
+    float fov;
+    int num_rays;
+    double crash_thresh;
+} rl_mcts_params;
+int rl_mcts_create(rl_car *c, rl_method *h, rl_followgap *g_or_null, rl_policy *p_or_null,
+                   const rl_mcts_params *params, const double *edge, rl_mcts **out);
+void rl_mcts_destroy(rl_mcts *m);
+int rl_mcts_reset(rl_mcts *m, const double *root_states, const double *root_actions, const uint64_t *seeds);
+int rl_mcts_run(rl_mcts *m, int n_iterations);
+int rl_mcts_best(rl_mcts *m, double *actions, int *visits, int *n_nodes);
+int rl_mcts_read_tree(rl_mcts *m, int tree, int *parent, int *first_child, int *next_sibling, int *n_children,
+                      int *visits, int *child_visits, double *reward, double *action, int *terminal, double *state,
+                      float *scan_pose, float *answer, int *crash, int *n_nodes_out);
+int rl_mcts_probe_ucb(int device, const double *reward, const int *visits, const int *sum, size_t n, double C,
+                      double *out);
+
 /* Car::setCarEdgeDistances (racecar/src/racecar.cpp:239-292; called at
  * scripts/racecar_simulator_v2.py:47-50): distance from the lidar to the car's outline along each of
  * num_rays beams starting one increment after min_ang — the table every crash test above takes as

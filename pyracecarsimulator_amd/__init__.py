@@ -8,5 +8,6 @@ from . import maps, racecar, range_libc             # noqa: F401
 from .scan_simulator import ScanSimulator2D          # noqa: F401
 from .racecar_simulator import RacecarSimulator      # noqa: F401
 from .policy import Policy                           # noqa: F401
+from .mcts import MCTS                               # noqa: F401
 
-__all__ = ["maps", "racecar", "range_libc", "ScanSimulator2D", "RacecarSimulator", "Policy"]
+__all__ = ["maps", "racecar", "range_libc", "ScanSimulator2D", "RacecarSimulator", "Policy", "MCTS"]

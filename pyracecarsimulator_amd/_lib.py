@@ -49,6 +49,16 @@ class LaunchPlan(C.Structure):
         return d
 
 
+class MctsParams(C.Structure):
+    """rl_mcts_params (include/scanlib.h)."""
+    _fields_ = [("n_trees", C.c_int), ("max_nodes", C.c_int), ("rollout_steps", C.c_int), ("action_every", C.c_int),
+                ("source", C.c_int)] + [(n, C.c_double) for n in (
+                    "speed", "dt", "scan_dist_to_base", "C", "crash_pen", "uni_dev", "max_steer", "max_speed")] + [
+                ("fov", C.c_float), ("num_rays", C.c_int), ("crash_thresh", C.c_double)]
+
+
+RL_MCTS_FG, RL_MCTS_NN, RL_MCTS_RANDOM = 0, 1, 2
+
 KERNEL_IDS = {0: "none", 1: "rm_chunk", 2: "rm_stream", 3: "occ_lds", 4: "bl_stream", 5: "bl_lds", 6: "lut_lds",
               7: "lut_fan", 8: "cddt_bins", 9: "cddt_rays", 10: "cddt_theta", 11: "rm_literal", 12: "rm_stream_literal"}
 BINNINGS = {0: "none", 1: "small_keys", 2: "small_records", 3: "grid_sort", 4: "grid_unsorted", 5: "generic"}
@@ -122,6 +132,15 @@ SYMBOLS = {
     "rl_car_drive_policy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, f64p, f64p, f32p, C.c_int, C.c_int,
                                       C.c_double, C.c_double, C.c_float, C.c_int, f64p, C.c_double, C.c_double,
                                       C.POINTER(C.c_int), f64p, f64p, f32p, f32p, f64p]),
+    "rl_mcts_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MctsParams), f64p,
+                                 C.POINTER(C.c_void_p)]),
+    "rl_mcts_destroy": (None, [C.c_void_p]),
+    "rl_mcts_reset": (C.c_int, [C.c_void_p, f64p, f64p, C.POINTER(C.c_uint64)]),
+    "rl_mcts_run": (C.c_int, [C.c_void_p, C.c_int]),
+    "rl_mcts_best": (C.c_int, [C.c_void_p, f64p, i32p, i32p]),
+    "rl_mcts_read_tree": (C.c_int, [C.c_void_p, C.c_int, i32p, i32p, i32p, i32p, i32p, i32p, f64p, f64p, i32p, f64p,
+                                    f32p, f32p, i32p, i32p]),
+    "rl_mcts_probe_ucb": (C.c_int, [C.c_int, f64p, i32p, i32p, C.c_size_t, C.c_double, f64p]),
     "rl_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "rl_host_free": (C.c_int, [C.c_void_p]),
     "rl_car_edge_distances": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,

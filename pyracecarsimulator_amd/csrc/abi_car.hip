@@ -7,6 +7,7 @@
 #include "car_kernels.h"
 #include "consumer_kernels.h"
 #include "drive_kernels.h"
+#include "mcts_kernels.h"
 #include "policy_kernels.h"
 #include "probe_kernels.h"
 
@@ -905,3 +906,386 @@ extern "C" int rl_car_is_crashed(const float *ranges, int num_rays, int n_scans,
     return RL_OK;
 }
 
+
+// ---------------------------------------------------------------- the MCTS planner (mcts_kernels.h)
+// mcts_act_kernel<ROWS>, ROWS = 1 ... FG_ROWS
+typedef void (*mcts_act_fn)(MctsParams, MctsBufs, int);
+template <int... R>
+static constexpr std::array<mcts_act_fn, sizeof...(R)> mcts_act_make(std::integer_sequence<int, R...>)
+{
+    return {{mcts_act_kernel<R + 1>...}};
+}
+static const std::array<mcts_act_fn, FG_ROWS> mcts_act_table = mcts_act_make(std::make_integer_sequence<int, FG_ROWS>());
+
+struct rl_mcts {
+    rl_car *c = nullptr;
+    rl_method *h = nullptr;
+    rl_followgap *g = nullptr;
+    rl_policy *p = nullptr;
+    rl_mcts_params prm{};
+    MctsParams mp{};
+    int device = 0;
+    // node arrays and per-tree scratch (MctsBufs)
+    DevBuf parent, first_child, next_sibling, last_child, n_children, visits, child_visits, terminal, crash;
+    DevBuf reward, action, state, pose, answer, n_nodes, child, exp_term, keys, logtab;
+    DevBuf cstate, cpose, actions, ranges, edge, mlp, rposes, vel, first, rranges, roots, best_a, best_v, best_n;
+    bool ready = false;            // reset done and no launch failed since
+    long iters = 0;                // iterations since reset
+    uint64_t base = 0;             // h's ray offset at reset
+    std::mutex mu;
+};
+
+// math.log(n) for n = 0 ... n_max (log(0) = -inf, never read: a node with children has a visit sum >= 1)
+static std::vector<double> mcts_log_table(int n_max)
+{
+    std::vector<double> t((size_t)n_max + 1);
+    for (int n = 0; n <= n_max; ++n) t[n] = std::log((double)n);
+    return t;
+}
+
+static MctsBufs mcts_bufs(rl_mcts *m)
+{
+    MctsBufs b{};
+    b.parent = (int *)m->parent.p;
+    b.first_child = (int *)m->first_child.p;
+    b.next_sibling = (int *)m->next_sibling.p;
+    b.last_child = (int *)m->last_child.p;
+    b.n_children = (int *)m->n_children.p;
+    b.visits = (int *)m->visits.p;
+    b.child_visits = (int *)m->child_visits.p;
+    b.terminal = (int *)m->terminal.p;
+    b.crash = (int *)m->crash.p;
+    b.reward = (double *)m->reward.p;
+    b.action = (double *)m->action.p;
+    b.state = (double *)m->state.p;
+    b.pose = (float *)m->pose.p;
+    b.answer = (float *)m->answer.p;
+    b.n_nodes = (int *)m->n_nodes.p;
+    b.child = (int *)m->child.p;
+    b.exp_term = (int *)m->exp_term.p;
+    b.keys = (const uint32_t *)m->keys.p;
+    b.logtab = (const double *)m->logtab.p;
+    b.cstate = (double *)m->cstate.p;
+    b.cpose = (float *)m->cpose.p;
+    b.actions = (double *)m->actions.p;
+    b.ranges = (const float *)m->ranges.p;
+    b.edge = (const double *)m->edge.p;
+    b.mlp = (const float *)m->mlp.p;
+    b.vel = (const double *)m->vel.p;
+    b.first = (const int *)m->first.p;
+    return b;
+}
+
+extern "C" void rl_mcts_destroy(rl_mcts *m)
+{
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    if (m->c && m->c->stream) (void)hipStreamSynchronize(m->c->stream);
+    for (DevBuf *b : {&m->parent, &m->first_child, &m->next_sibling, &m->last_child, &m->n_children, &m->visits,
+                      &m->child_visits, &m->terminal, &m->crash, &m->reward, &m->action, &m->state, &m->pose,
+                      &m->answer, &m->n_nodes, &m->child, &m->exp_term, &m->keys, &m->logtab, &m->cstate, &m->cpose,
+                      &m->actions, &m->ranges, &m->edge, &m->mlp, &m->rposes, &m->vel, &m->first, &m->rranges,
+                      &m->roots, &m->best_a, &m->best_v, &m->best_n})
+        b->release();
+    delete m;
+}
+
+extern "C" int rl_mcts_create(rl_car *c, rl_method *h, rl_followgap *g, rl_policy *p, const rl_mcts_params *params,
+                              const double *edge, rl_mcts **out)
+{
+    if (!c || !h || !params || !edge || !out) return fail(RL_ERR_INVALID, "rl_mcts_create: null pointer");
+    const rl_mcts_params q = *params;
+    if (!c->reps.empty() || !h->reps.empty())
+        return fail(RL_ERR_INVALID, "rl_mcts_create is single-device only: pass ordinary (not multi-device) handles");
+    if (q.source == RL_MCTS_FG && !g) return fail(RL_ERR_INVALID, "rl_mcts_create: the FG source needs a FollowGap handle");
+    if (q.source == RL_MCTS_NN && !p) return fail(RL_ERR_INVALID, "rl_mcts_create: the NN source needs a policy handle");
+    if (q.source != RL_MCTS_FG && q.source != RL_MCTS_NN && q.source != RL_MCTS_RANDOM)
+        return fail(RL_ERR_INVALID, "rl_mcts_create: unknown source %d", q.source);
+    if (c->device != h->map->device || (q.source == RL_MCTS_FG && g->device != c->device) ||
+        (q.source == RL_MCTS_NN && p->device != c->device))
+        return fail(RL_ERR_INVALID, "rl_mcts_create: car, range method and the source's handle must share one device");
+    if (q.n_trees < 1 || q.max_nodes < 1 || q.action_every < 1 || q.rollout_steps < 1 || q.rollout_steps > MCTS_MAX_STEPS)
+        return fail(RL_ERR_INVALID, "rl_mcts_create: n_trees >= 1, max_nodes >= 1, action_every >= 1 and 1 <= "
+                    "rollout_steps <= %d required (got %d, %d, %d, %d)", MCTS_MAX_STEPS, q.n_trees, q.max_nodes,
+                    q.action_every, q.rollout_steps);
+    if (q.num_rays < 10 || q.num_rays > 64 * FG_ROWS)
+        return fail(RL_ERR_INVALID, "num_rays must lie in [10, %d] (got %d)", 64 * FG_ROWS, q.num_rays);
+    if (q.source == RL_MCTS_NN) {
+        const int rc = policy_args(p, q.n_trees, q.num_rays);
+        if (rc) return rc;
+    }
+    if ((long)q.n_trees * q.rollout_steps * q.num_rays >= (1L << 31) || (long)q.n_trees * q.max_nodes >= (1L << 31) / 11)
+        return fail(RL_ERR_INVALID, "rl_mcts_create: n_trees * rollout_steps * num_rays and the node arrays must stay below 2^31");
+    rl_mcts *m = new (std::nothrow) rl_mcts();
+    if (!m) return fail(RL_ERR_NOMEM, "out of host memory");
+    m->c = c;
+    m->h = h;
+    m->g = q.source == RL_MCTS_FG ? g : nullptr;
+    m->p = q.source == RL_MCTS_NN ? p : nullptr;
+    m->prm = q;
+    m->device = c->device;
+    MctsParams &mp = m->mp;
+    mp.P = c->P;
+    if (m->g) mp.fg = g->P;
+    mp.fg.size = q.num_rays;
+    mp.K = q.n_trees;
+    mp.N = q.max_nodes;
+    mp.L = q.rollout_steps;
+    mp.every = q.action_every;
+    mp.n_act = (q.rollout_steps + q.action_every - 1) / q.action_every;
+    mp.source = q.source;
+    mp.speed = q.speed;
+    mp.dt = q.dt;
+    mp.scan_dist_to_base = q.scan_dist_to_base;
+    mp.C = q.C;
+    mp.crash_pen = q.crash_pen;
+    mp.uni_dev = q.uni_dev;
+    mp.max_steer = q.max_steer;
+    mp.max_speed = q.max_speed;
+    mp.crash_thresh = q.crash_thresh;
+    const size_t K = q.n_trees, N = (size_t)q.n_trees * q.max_nodes, B = q.num_rays;
+    int rc = RL_OK;
+    if (hipSetDevice(m->device) != hipSuccess) rc = fail(RL_ERR_HIP, "rl_mcts_create: hipSetDevice failed");
+    for (DevBuf *b : {&m->parent, &m->first_child, &m->next_sibling, &m->last_child, &m->n_children, &m->visits,
+                      &m->child_visits, &m->terminal, &m->crash})
+        if (!rc) rc = b->ensure(N * 4);
+    if (!rc) rc = m->reward.ensure(N * 8);
+    if (!rc) rc = m->action.ensure(N * 8);
+    if (!rc) rc = m->state.ensure(N * 88);
+    if (!rc) rc = m->pose.ensure(N * 12);
+    if (!rc) rc = m->answer.ensure(N * 4);
+    for (DevBuf *b : {&m->n_nodes, &m->child, &m->exp_term, &m->keys, &m->first, &m->mlp, &m->best_v, &m->best_n})
+        if (!rc) rc = b->ensure(K * 4);
+    if (!rc) rc = m->best_a.ensure(K * 8);
+    if (!rc) rc = m->logtab.ensure(((size_t)q.max_nodes + 1) * 8);
+    if (!rc) rc = m->cstate.ensure(K * 88);
+    if (!rc) rc = m->roots.ensure(K * 96);
+    if (!rc) rc = m->cpose.ensure(K * 12);
+    if (!rc) rc = m->actions.ensure(K * mp.n_act * 16);
+    if (!rc) rc = m->ranges.ensure(K * B * 4);
+    if (!rc) rc = m->edge.ensure(B * 8);
+    if (!rc) rc = m->rposes.ensure(K * q.rollout_steps * 12);
+    if (!rc) rc = m->vel.ensure(K * q.rollout_steps * 8);
+    if (!rc) {
+        const std::vector<double> lt = mcts_log_table(q.max_nodes);
+        if (hipMemcpy(m->logtab.p, lt.data(), lt.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(m->edge.p, edge, B * 8, hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(RL_ERR_HIP, "rl_mcts_create: upload failed");
+    }
+    if (rc) {
+        rl_mcts_destroy(m);
+        return rc;
+    }
+    *out = m;
+    return RL_OK;
+}
+
+// the act scans of the K nodes in m->cpose at ray offset `off`, the network for NN, then mcts_act_kernel
+static int mcts_act(rl_mcts *m, uint64_t off, int root, hipStream_t st)
+{
+    rl_method *h = m->h;
+    const int K = m->prm.n_trees, B = m->prm.num_rays;
+    h->ray_offset = off;
+    int rc = launch_fan(h, (const float *)m->cpose.p, K, m->prm.fov, B, (float *)m->ranges.p, nullptr, nullptr,
+                        nullptr, st);
+    if (rc) return rc;
+    if (m->prm.source == RL_MCTS_NN &&
+        (rc = policy_launch(m->p, (const float *)m->ranges.p, K, B, (float *)m->mlp.p, st)))
+        return rc;
+    mcts_act_table[(B + 63) / 64 - 1]<<<dim3((K + MCTS_TREES - 1) / MCTS_TREES), dim3(64 * MCTS_TREES), 0, st>>>(
+        m->mp, mcts_bufs(m), root);
+    if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "mcts_act_kernel launch failed");
+    return RL_OK;
+}
+
+// the handles every launching call locks, in one order; h's options that the planner changes come back afterwards
+struct MctsLock {
+    rl_mcts *m;
+    std::unique_lock<std::mutex> lm, lc, lh, lx;
+    std::shared_lock<std::shared_mutex> ml;
+    uint64_t off;
+    int nt;
+    explicit MctsLock(rl_mcts *m_)
+        : m(m_), lm(m_->mu), lc(m_->c->mu), lh(m_->h->mu), ml(m_->h->map->tables_mu)
+    {
+        if (m->g) lx = std::unique_lock<std::mutex>(m->g->mu);
+        if (m->p) lx = std::unique_lock<std::mutex>(m->p->mu);
+        off = m->h->ray_offset;
+        nt = m->h->nt_store;
+        m->h->nt_store = 0;                 // the act kernel reads the ranges right after the scan: plain stores
+    }
+    ~MctsLock()
+    {
+        m->h->ray_offset = off;
+        m->h->nt_store = nt;
+    }
+};
+
+extern "C" int rl_mcts_reset(rl_mcts *m, const double *root_states, const double *root_actions, const uint64_t *seeds)
+{
+    if (!m || !root_states || !root_actions || !seeds) return fail(RL_ERR_INVALID, "rl_mcts_reset: null pointer");
+    const int K = m->prm.n_trees;
+    int rc = check_fan_args(m->h, K, m->prm.fov, m->prm.num_rays);
+    if (rc) return rc;
+    MctsLock lk(m);
+    HIPCHK(hipSetDevice(m->device));
+    hipStream_t st = m->c->stream;
+    m->ready = false;
+    std::vector<uint32_t> keys(K);
+    for (int k = 0; k < K; ++k)
+        keys[k] = (uint32_t)seeds[k] ^ ((uint32_t)(seeds[k] >> 32) * 0x85EBCA6Bu);     // np_statement.noise_key
+    double *d_states = (double *)m->roots.p, *d_actions = d_states + (size_t)K * 11;
+    HIPCHK(hipMemcpyAsync(m->keys.p, keys.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_states, root_states, (size_t)K * 88, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_actions, root_actions, (size_t)K * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(mcts_start_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, mcts_bufs(m),
+                       (const double *)d_states, (const double *)d_actions);
+    if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_start_kernel launch failed");
+    const uint64_t base = lk.off;
+    if (!rc) rc = mcts_act(m, base, 1, st);
+    const hipError_t e = hipStreamSynchronize(st);            // (the host's root arrays are the caller's)
+    if (!rc && e != hipSuccess) rc = fail(RL_ERR_HIP, "rl_mcts_reset: %s", hipGetErrorString(e));
+    if (rc) return rc;
+    m->base = base;
+    m->iters = 0;
+    m->ready = true;
+    return RL_OK;
+}
+
+extern "C" int rl_mcts_run(rl_mcts *m, int n_iterations)
+{
+    if (!m) return fail(RL_ERR_INVALID, "rl_mcts_run: null pointer");
+    if (n_iterations < 0) return fail(RL_ERR_INVALID, "rl_mcts_run: n_iterations must be >= 0 (got %d)", n_iterations);
+    std::unique_lock<std::mutex> pre(m->mu);
+    if (!m->ready) return fail(RL_ERR_INVALID, "rl_mcts_run: reset the planner first (rl_mcts_reset)");
+    if (1 + m->iters + (long)n_iterations > m->prm.max_nodes)
+        return fail(RL_ERR_INVALID, "rl_mcts_run: %d more iterations exceed max_nodes = %d (%ld done since reset)",
+                    n_iterations, m->prm.max_nodes, m->iters);
+    pre.unlock();
+    const int K = m->prm.n_trees, L = m->prm.rollout_steps, B = m->prm.num_rays;
+    int rc;
+    if ((rc = check_fan_args(m->h, K, m->prm.fov, B)) || (rc = check_fan_args(m->h, K * L, m->prm.fov, B))) return rc;
+    if (n_iterations == 0) return RL_OK;
+    MctsLock lk(m);
+    if (!m->ready) return fail(RL_ERR_INVALID, "rl_mcts_run: reset the planner first (rl_mcts_reset)");
+    HIPCHK(hipSetDevice(m->device));
+    if ((rc = m->rranges.ensure((size_t)K * L * B * 4))) return rc;
+    hipStream_t st = m->c->stream;
+    const MctsBufs b = mcts_bufs(m);
+    const uint64_t KB = (uint64_t)K * B, per_it = (uint64_t)K * (1 + L) * B;
+    for (int t = 0; t < n_iterations && rc == RL_OK; ++t) {
+        const long it = m->iters + t;
+        const uint64_t off = m->base + KB + (uint64_t)it * per_it;
+        hipLaunchKernelGGL(mcts_select_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, (int)it);
+        if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_select_kernel launch failed");
+        if (!rc) rc = mcts_act(m, off, 0, st);
+        if (!rc) {
+            hipLaunchKernelGGL(rollout_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, (const double *)m->cstate.p,
+                               (const double *)m->actions.p, K, L, m->prm.action_every, m->prm.dt, (float *)m->rposes.p,
+                               (double *)nullptr, (double *)m->vel.p);
+            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "rollout_kernel launch failed");
+        }
+        if (!rc) {
+            m->h->ray_offset = off + KB;
+            rc = crash_groups_device(m->h, (const float *)m->rposes.p, K, L, m->prm.fov, B, (const double *)m->edge.p,
+                                     m->prm.crash_thresh, (int *)m->first.p, (float *)m->rranges.p, true, st);
+        }
+        if (!rc) {
+            hipLaunchKernelGGL(mcts_backup_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b);
+            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_backup_kernel launch failed");
+        }
+    }
+    const hipError_t e = hipStreamSynchronize(st);
+    if (!rc && e != hipSuccess) rc = fail(RL_ERR_HIP, "rl_mcts_run: %s", hipGetErrorString(e));
+    if (rc) {
+        m->ready = false;                   // part of an iteration may have run: the trees need a reset
+        return rc;
+    }
+    m->iters += n_iterations;
+    return RL_OK;
+}
+
+extern "C" int rl_mcts_best(rl_mcts *m, double *actions, int *visits, int *n_nodes)
+{
+    if (!m || !actions || !visits || !n_nodes) return fail(RL_ERR_INVALID, "rl_mcts_best: null pointer");
+    std::scoped_lock lk(m->mu, m->c->mu);
+    if (!m->ready) return fail(RL_ERR_INVALID, "rl_mcts_best: reset the planner first (rl_mcts_reset)");
+    HIPCHK(hipSetDevice(m->device));
+    hipStream_t st = m->c->stream;
+    const int K = m->prm.n_trees;
+    hipLaunchKernelGGL(mcts_best_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, mcts_bufs(m),
+                       (double *)m->best_a.p, (int *)m->best_v.p, (int *)m->best_n.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(actions, m->best_a.p, (size_t)K * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(visits, m->best_v.p, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(n_nodes, m->best_n.p, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
+}
+
+extern "C" int rl_mcts_read_tree(rl_mcts *m, int tree, int *parent, int *first_child, int *next_sibling,
+                                 int *n_children, int *visits, int *child_visits, double *reward, double *action,
+                                 int *terminal, double *state, float *scan_pose, float *answer, int *crash,
+                                 int *n_nodes_out)
+{
+    if (!m || !n_nodes_out) return fail(RL_ERR_INVALID, "rl_mcts_read_tree: null pointer");
+    if (tree < 0 || tree >= m->prm.n_trees)
+        return fail(RL_ERR_INVALID, "rl_mcts_read_tree: tree %d outside [0, %d)", tree, m->prm.n_trees);
+    std::scoped_lock lk(m->mu, m->c->mu);
+    if (!m->ready) return fail(RL_ERR_INVALID, "rl_mcts_read_tree: reset the planner first (rl_mcts_reset)");
+    HIPCHK(hipSetDevice(m->device));
+    hipStream_t st = m->c->stream;
+    int n = 0;
+    HIPCHK(hipMemcpyAsync(&n, (const int *)m->n_nodes.p + tree, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    n = std::min(std::max(n, 0), m->prm.max_nodes);
+    const size_t t0 = (size_t)tree * m->prm.max_nodes;
+    struct Out { void *dst; const DevBuf *src; size_t w; };
+    const Out outs[] = {{parent, &m->parent, 4}, {first_child, &m->first_child, 4}, {next_sibling, &m->next_sibling, 4},
+                        {n_children, &m->n_children, 4}, {visits, &m->visits, 4}, {child_visits, &m->child_visits, 4},
+                        {reward, &m->reward, 8}, {action, &m->action, 8}, {terminal, &m->terminal, 4},
+                        {state, &m->state, 88}, {scan_pose, &m->pose, 12}, {answer, &m->answer, 4},
+                        {crash, &m->crash, 4}};
+    for (const Out &o : outs)
+        if (o.dst && n > 0)
+            HIPCHK(hipMemcpyAsync(o.dst, (const char *)o.src->p + t0 * o.w, (size_t)n * o.w, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *n_nodes_out = n;
+    return RL_OK;
+}
+
+extern "C" int rl_mcts_probe_ucb(int device, const double *reward, const int *visits, const int *sum, size_t n,
+                                 double C, double *out)
+{
+    if (n > 0 && (!reward || !visits || !sum || !out)) return fail(RL_ERR_INVALID, "rl_mcts_probe_ucb: null pointer");
+    int s_max = 1;
+    for (size_t i = 0; i < n; ++i) {
+        if (visits[i] < 1 || sum[i] < 1 || sum[i] > (1 << 24))
+            return fail(RL_ERR_INVALID, "rl_mcts_probe_ucb: visits >= 1 and 1 <= sum <= 2^24 required (entry %zu)", i);
+        s_max = std::max(s_max, sum[i]);
+    }
+    int ndev = rl_device_count();
+    if (ndev <= 0) return fail(RL_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(RL_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
+    if (n == 0) return RL_OK;
+    HIPCHK(hipSetDevice(device));
+    const std::vector<double> lt = mcts_log_table(s_max);
+    DevBuf dr, dv, ds, dl, dout;
+    int rc;
+    if ((rc = dr.ensure(n * 8)) || (rc = dv.ensure(n * 4)) || (rc = ds.ensure(n * 4)) || (rc = dl.ensure(lt.size() * 8)) ||
+        (rc = dout.ensure(n * 8))) {
+    } else if (hipMemcpy(dr.p, reward, n * 8, hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(dv.p, visits, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(ds.p, sum, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(dl.p, lt.data(), lt.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        rc = fail(RL_ERR_HIP, "rl_mcts_probe_ucb: upload failed");
+    } else {
+        const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
+        hipLaunchKernelGGL(mcts_ucb_probe_kernel, dim3(grid), dim3(256), 0, nullptr, (const double *)dr.p,
+                           (const int *)dv.p, (const int *)ds.p, (const double *)dl.p, (long)n, C, (double *)dout.p);
+        if (hipMemcpy(out, dout.p, n * 8, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(RL_ERR_HIP, "rl_mcts_probe_ucb: kernel or download failed");
+    }
+    for (DevBuf *b : {&dr, &dv, &ds, &dl, &dout}) b->release();
+    return rc;
+}

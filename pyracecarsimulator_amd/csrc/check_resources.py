@@ -29,6 +29,13 @@ BOUNDS = [
     # the policy network: the micro-tile accumulators stay in registers; its drive tick as drive_tick_kernel's
     ("scan::policy_mlp_kernel", {"scratch": 0}),
     ("scan::policy_tick_kernel<", {"scratch": 0}),
+    # the MCTS planner: the descent, the act wave, the backup's pairwise sum and the walks keep nothing in scratch
+    ("scan::mcts_start_kernel", {"scratch": 0}),
+    ("scan::mcts_select_kernel", {"scratch": 0}),
+    ("scan::mcts_act_kernel<", {"scratch": 0}),
+    ("scan::mcts_backup_kernel", {"scratch": 0}),
+    ("scan::mcts_best_kernel", {"scratch": 0}),
+    ("scan::mcts_ucb_probe_kernel", {"scratch": 0}),
 ]
 KEYS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy"}
 

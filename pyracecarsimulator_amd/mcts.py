@@ -1,0 +1,211 @@
+"""The MCTS planner on the GPU (``rl_mcts_*``, include/scanlib.h; kernels csrc/mcts_kernels.h).
+
+``MCTSPlanner`` advances K independent trees of scripts/mcts.py's search in lock step: one node per tree per
+iteration, each iteration one batched act (step, scan, crash test, expansion answer) and one batched roll-out,
+nothing leaving the device between iterations.  The trees are the reference's bit for bit (tests/mcts_statement.py).
+
+``MCTS`` is a drop-in for the reference class (scripts/mcts.py:83-148) on a ``RacecarSimulator``: ``mcts()`` plans
+from the simulator's state and returns the most visited root action; ``root`` holds the tree read back from the
+device as ``Node`` objects.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import time
+
+import numpy as np
+
+from . import _lib
+from ._lib import f32p, f64p, i32p
+
+SOURCES = {"fg": _lib.RL_MCTS_FG, "nn": _lib.RL_MCTS_NN, "random": _lib.RL_MCTS_RANDOM}
+TREE_FIELDS = ("parent", "first_child", "next_sibling", "n_children", "visits", "child_visits", "reward", "action",
+               "terminal", "state", "scan_pose", "answer", "crash")
+
+
+class MCTSPlanner:
+    """K trees of at most ``max_nodes`` nodes on one device.  ``method`` scans, ``source`` ("fg", "nn" or "random")
+    picks the expansion answer: ``followgap`` (a ``PyFollowGap``) for "fg", ``policy`` (a ``Policy``) for "nn".
+    The handles are borrowed: keep them alive as long as the planner."""
+
+    def __init__(self, car, method, n_trees, max_nodes, fov, num_rays, edge, crash_thresh, source="fg",
+                 followgap=None, policy=None, rollout_steps=200, action_every=10, speed=2.0, dt=0.01,
+                 scan_dist_to_base=0.275, C_ucb=0.5, crash_pen=-10.0, uni_dev=0.05, max_steer=None, max_speed=None):
+        if source not in SOURCES:
+            raise ValueError("source must be one of %s" % sorted(SOURCES))
+        edge = np.asarray(edge)
+        if edge.dtype != np.float64 or edge.shape != (int(num_rays),):
+            raise ValueError("edge must be float64 (num_rays,)")
+        self._edge = np.ascontiguousarray(edge)
+        p = _lib.MctsParams()
+        p.n_trees, p.max_nodes, p.rollout_steps = int(n_trees), int(max_nodes), int(rollout_steps)
+        p.action_every, p.source = int(action_every), SOURCES[source]
+        p.speed, p.dt, p.scan_dist_to_base, p.C = float(speed), float(dt), float(scan_dist_to_base), float(C_ucb)
+        p.crash_pen, p.uni_dev = float(crash_pen), float(uni_dev)
+        p.max_steer = float(car.params["max_steer_ang"] if max_steer is None else max_steer)
+        p.max_speed = float(car.params["max_speed"] if max_speed is None else max_speed)
+        p.fov, p.num_rays, p.crash_thresh = float(fov), int(num_rays), float(crash_thresh)
+        self.params = p
+        self.n_trees, self.max_nodes, self.source = int(n_trees), int(max_nodes), source
+        self._keep = (car, method, followgap, policy)
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().rl_mcts_create(car._h, method._h, followgap._h if followgap is not None else None,
+                                             policy._h if policy is not None else None, C.byref(p),
+                                             self._edge.ctypes.data_as(f64p), C.byref(self._h)))
+
+    def reset(self, root_states, root_actions, seeds):
+        """The K roots: states float64 (K, 11) in getState layout, recent actions (K,), one 64-bit seed per tree."""
+        K = self.n_trees
+        st = np.ascontiguousarray(np.asarray(root_states, np.float64).reshape(K, 11))
+        ac = np.ascontiguousarray(np.broadcast_to(np.asarray(root_actions, np.float64), (K,)))
+        sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, np.uint64), (K,)))
+        _lib.check(_lib.lib().rl_mcts_reset(self._h, st.ctypes.data_as(f64p), ac.ctypes.data_as(f64p),
+                                            sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+
+    def run(self, n_iterations):
+        _lib.check(_lib.lib().rl_mcts_run(self._h, int(n_iterations)))
+
+    def best(self):
+        """(best root action float64 (K,), its visits int32 (K,), nodes per tree int32 (K,))."""
+        K = self.n_trees
+        a, v, n = np.empty(K), np.empty(K, np.int32), np.empty(K, np.int32)
+        _lib.check(_lib.lib().rl_mcts_best(self._h, a.ctypes.data_as(f64p), v.ctypes.data_as(i32p),
+                                           n.ctypes.data_as(i32p)))
+        return a, v, n
+
+    def read_tree(self, tree):
+        """Tree ``tree``'s node arrays in creation order, a dict keyed by TREE_FIELDS (state (n, 11), scan_pose (n, 3))."""
+        N = self.max_nodes
+        out = {f: np.empty(N, np.int32) for f in ("parent", "first_child", "next_sibling", "n_children", "visits",
+                                                  "child_visits", "terminal", "crash")}
+        out.update(reward=np.empty(N), action=np.empty(N), state=np.empty((N, 11)),
+                   scan_pose=np.empty((N, 3), np.float32), answer=np.empty(N, np.float32))
+        n = C.c_int(0)
+        ptr = lambda f, t: out[f].ctypes.data_as(t)
+        _lib.check(_lib.lib().rl_mcts_read_tree(
+            self._h, int(tree), ptr("parent", i32p), ptr("first_child", i32p), ptr("next_sibling", i32p),
+            ptr("n_children", i32p), ptr("visits", i32p), ptr("child_visits", i32p), ptr("reward", f64p),
+            ptr("action", f64p), ptr("terminal", i32p), ptr("state", f64p), ptr("scan_pose", f32p),
+            ptr("answer", f32p), ptr("crash", i32p), C.byref(n)))
+        return {f: a[:n.value] for f, a in out.items()}
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            _lib.lib().rl_mcts_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Node:
+    """A node of a tree read back from the device, with the reference Node's fields (scripts/mcts.py:16-31)."""
+
+    def __init__(self, state, action, terminal, parent, visits, reward, scan_pose, answer, index):
+        self.state, self.action, self.terminal, self.parent = state, action, terminal, parent
+        self.visits, self.reward, self.scan_pose, self.answer, self.index = visits, reward, scan_pose, answer, index
+        self.children = []
+
+    def isTerminal(self):
+        return self.terminal
+
+    def hasChildren(self):
+        return len(self.children) > 0
+
+    def size(self):
+        return len(self.children)
+
+    def getState(self):
+        return self.state
+
+
+def build_nodes(arrays):
+    """The Node tree of one ``read_tree`` dict (children in insertion order); returns the root."""
+    n = len(arrays["parent"])
+    nodes = []
+    for i in range(n):
+        par = int(arrays["parent"][i])
+        node = Node(arrays["state"][i].copy(), float(arrays["action"][i]), bool(arrays["terminal"][i]),
+                    nodes[par] if par >= 0 else None, int(arrays["visits"][i]), float(arrays["reward"][i]),
+                    arrays["scan_pose"][i].copy(), float(arrays["answer"][i]), i)
+        nodes.append(node)
+        if par >= 0:
+            nodes[par].children.append(node)      # nodes are created in order: siblings append in insertion order
+    return nodes[0] if nodes else None
+
+
+class MCTS:
+    """Drop-in for scripts/mcts.py's MCTS on a ``RacecarSimulator``: ``mcts()`` searches from the simulator's state
+    with ``recent_action`` at the root and returns (and keeps in ``self.action``) the most visited root child's
+    action; ``root`` is the searched tree (``Node`` objects read back from the device).
+
+    ``budget`` seconds of wall clock run chunks of iterations until the time is spent or ``max_nodes`` is reached,
+    at least one iteration; ``n_iterations`` runs exactly that many instead (deterministic).  ``seed`` keys the
+    draws.  ``source``: "fg" (the reference's live generateActionFromFG, PyFollowGap(10, 15.0, max_steer, 0.004)),
+    "nn" (``policy_session``, a ``Policy``) or "random".  ``track_point`` and ``with_global`` are accepted and have
+    no effect: their only use, the waypoint reward, is commented out in the reference (mcts.py:233-234)."""
+
+    def __init__(self, simulator, policy_session, recent_action, roll_out_itr, budget=1.0, track_point=None,
+                 with_global=False, *, seed=0, n_iterations=None, source="fg", max_nodes=4097):
+        self.point_to_follow = track_point
+        self.with_global = with_global
+        self.simulator = simulator
+        self.policy_session = policy_session
+        self.budget = budget
+        self.max_iterations = int(roll_out_itr)
+        self.action = recent_action
+        self.root = None
+        self.C = 0.5
+        self.crash_pen = -10.0
+        self.speed = 2.0
+        self.seed = seed
+        self.n_iterations = n_iterations
+        self.source = source
+        self.max_nodes = int(max_nodes if n_iterations is None else max(max_nodes, int(n_iterations) + 1))
+        self.iterations = 0
+        self.fg = None
+        if source == "fg":
+            from .followgap import PyFollowGap
+            self.fg = PyFollowGap(10, 15.0, simulator.config["max_steer_ang"], 0.004, device=simulator._device)
+        self._planner = None
+
+    def _make_planner(self):
+        sim = self.simulator
+        return MCTSPlanner(sim.car, sim.scan_simulator.scan_method, 1, self.max_nodes, sim.scan_fov, sim.num_rays,
+                           sim.edge_distances, sim.ttc_thresh, source=self.source, followgap=self.fg,
+                           policy=self.policy_session if self.source == "nn" else None,
+                           rollout_steps=self.max_iterations, speed=self.speed, C_ucb=self.C, crash_pen=self.crash_pen,
+                           scan_dist_to_base=sim.scan_dist_to_base, max_steer=sim.config["max_steer_ang"],
+                           max_speed=sim.config["max_speed"])
+
+    def mcts(self):
+        if self._planner is None:
+            self._planner = self._make_planner()
+        pl = self._planner
+        pl.reset(self.simulator.getState()[None, :], [self.action], [self.seed])
+        cap = self.max_nodes - 1
+        if self.n_iterations is not None:
+            pl.run(int(self.n_iterations))
+            done = int(self.n_iterations)
+        else:
+            t_start = time.time()
+            pl.run(1)
+            done = 1
+            per_it = max(time.time() - t_start, 1e-6)
+            while done < cap:
+                left = t_start + self.budget - time.time()
+                n = min(cap - done, int(0.5 * left / per_it))
+                if n < 1:
+                    break
+                t0 = time.time()
+                pl.run(n)
+                done += n
+                per_it = max((time.time() - t0) / n, 1e-6)
+        self.iterations = done
+        a, _, _ = pl.best()
+        self.root = build_nodes(pl.read_tree(0))
+        self.action = None if np.isnan(a[0]) else float(a[0])
+        return self.action

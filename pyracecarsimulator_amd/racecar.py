@@ -14,7 +14,8 @@ on the GPU:
 
 ``CarBatch.rollout_check`` chains roll-outs -> poses -> scan -> per-roll-out crash index on the
 device (poses and ranges never cross PCIe).  ``CarBatch.drive_followgap`` closes the loop: each tick's
-steering angle is FollowGap's answer to that tick's scan, all on the device.
+steering angle is FollowGap's answer to that tick's scan, all on the device.  ``CarBatch.plan_mcts`` runs
+scripts/mcts.py's tree search for many trees at once on the device (``mcts.MCTSPlanner``).
 """
 from __future__ import annotations
 
@@ -165,6 +166,39 @@ class CarBatch:
         if trace:
             return first, out, vel, steers, poses, trace_st
         return first, out, vel, steers
+
+    def plan_mcts(self, method, followgap_or_policy, root_states, n_iterations, seeds, fov, num_rays, edge,
+                  crash_thresh, root_actions=0.0, source=None, rollout_steps=200, action_every=10, speed=2.0,
+                  dt=0.01, scan_dist_to_base=0.275, C_ucb=0.5, crash_pen=-10.0, uni_dev=0.05, max_nodes=None,
+                  trees=False):
+        """scripts/mcts.py's search for K trees at once (``rl_mcts_*``, one tree per root state): ``n_iterations``
+        iterations each, every tree adding one node per iteration.  ``followgap_or_policy``: a ``PyFollowGap``
+        (source "fg"), a ``Policy`` ("nn") or None ("random"); ``source`` overrides the choice.  root_states float64
+        (K, 11), root_actions scalar or (K,), seeds uint64 (K,).  Returns (best root action float64 (K,), its visits
+        int32 (K,), nodes per tree int32 (K,)) and with ``trees=True`` also the K node-array dicts of
+        ``MCTSPlanner.read_tree``."""
+        from .mcts import MCTSPlanner
+        from .policy import Policy
+        if source is None:
+            source = "random" if followgap_or_policy is None else ("nn" if isinstance(followgap_or_policy, Policy)
+                                                                   else "fg")
+        root_states = np.asarray(root_states, np.float64).reshape(-1, 11)
+        K = root_states.shape[0]
+        n_iterations = int(n_iterations)
+        pl = MCTSPlanner(self, method, K, max_nodes or n_iterations + 1, fov, num_rays, edge, crash_thresh,
+                         source=source, followgap=followgap_or_policy if source == "fg" else None,
+                         policy=followgap_or_policy if source == "nn" else None, rollout_steps=rollout_steps,
+                         action_every=action_every, speed=speed, dt=dt, scan_dist_to_base=scan_dist_to_base,
+                         C_ucb=C_ucb, crash_pen=crash_pen, uni_dev=uni_dev)
+        try:
+            pl.reset(root_states, root_actions, seeds)
+            pl.run(n_iterations)
+            res = pl.best()
+            if trees:
+                res = res + ([pl.read_tree(k) for k in range(K)],)
+        finally:
+            pl.close()
+        return res
 
     @staticmethod
     def _drive_args(states, n_ticks, speed, num_rays, edge, steer0, trace):

@@ -14,7 +14,8 @@ it unchanged.  The two native pieces behind it are on the GPU:
 ``rolloutMany`` is the batched form of ``MCTS.rollout`` + ``checkCollisionMany``
 (scripts/mcts.py:202-245) for any number of roll-outs per call; ``driveFollowGapMany`` the closed
 loop of the simulator tick and simple_driver.py's FollowGap answer to every scan; ``drivePolicyMany`` the same loop
-steered by the policy network (scripts/policy_driver.py).
+steered by the policy network (scripts/policy_driver.py); ``planMCTSMany`` scripts/mcts.py's tree search from many
+start states at once.
 """
 from __future__ import annotations
 
@@ -171,6 +172,30 @@ class RacecarSimulator:
                                      np.asarray(states, dtype=np.float64).reshape(-1, 11), n_ticks, speed,
                                      self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
                                      scan_dist_to_base=self.scan_dist_to_base, steer_clip=steer_clip)
+
+    def planMCTSMany(self, states, n_iterations, seeds=None, source="fg", policy=None, root_actions=0.0):
+        """scripts/mcts.py's search from each of R start states at once (one tree each, ``n_iterations`` iterations,
+        roll-outs of ``batch_size`` steps) on this simulator's range method, edge table and ttc_thresh; ``source``
+        "fg" (PyFollowGap(10, 15.0, max_steer_ang, 0.004)), "nn" (``policy``) or "random".  seeds: one per tree
+        (default 0 ... R-1).  Returns ``CarBatch.plan_mcts``'s (best actions, their visits, nodes per tree)."""
+        states = np.asarray(states, dtype=np.float64).reshape(-1, 11)
+        R = states.shape[0]
+        seeds = np.arange(R, dtype=np.uint64) if seeds is None else np.asarray(seeds, np.uint64)
+        if source == "fg":
+            if self._followgap is None:
+                from .followgap import PyFollowGap
+                self._followgap = PyFollowGap(10, 15.0, self.max_steer_ang, 0.004, device=self._device)
+            handle = self._followgap
+        elif source == "nn":
+            if policy is None:
+                raise ValueError("source 'nn' needs a policy")
+            handle = policy
+        else:
+            handle = None
+        return self.car.plan_mcts(self.scan_simulator.scan_method, handle, states, n_iterations, seeds,
+                                  self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
+                                  root_actions=root_actions, source=source, rollout_steps=self.batch_size,
+                                  scan_dist_to_base=self.scan_dist_to_base)
 
     def stop(self):
         state = self.getState()
