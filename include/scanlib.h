@@ -299,6 +299,81 @@ int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, const doubl
                            double *velocities_or_null, float *steers_or_null, float *scan_poses_or_null,
                            double *states_trace_or_null);
 
+/* ---- batched multi-car races ----------------------------------------------------------------------------
+ * The reference's second simulator (scripts/two_player/): every car steps, then every car scans
+ * (ros_interface_two_player.py:156-187), each scan with the other car's outline written into a copy of the grid and
+ * the tables rebuilt (rcs_two_player.py:99-126); simple_driver.py steers each car with FollowGap.  Here R independent
+ * races of `group` = P cars (1 <= P <= 8) share one static map: N = R P cars, race-major (car k of race r is car r P + k).
+ *
+ * Exactness.  The EDT is sqrtf((float)d2) of the integer squared distance to the nearest occupied cell, so for extra
+ * cells S stamped on the grid  dt_{grid u S}(q) = min(dt_grid(q), sqrtf((float)min_{c in S} |q - c|^2))  bit for bit.
+ * The march reads the map only through dt[row, col]; the race kernel (race_kernels.h, one workgroup per race, the
+ * race's outline cells in LDS) replaces that read with the min above.  Ranges, hit cells and step counts equal "stamp
+ * the other cars (rl_map_stamp_cells), rebuild, scan" bit for bit, with no per-race table.
+ *
+ * The canonical car outline (rl_car_outline_cells; the race kernel rasterises with the same device function; the host
+ * statement is tests/race_statement.py).  The rectangle Car::getBound means to trace (racecar.cpp:389-459), centred on
+ * the state's (x, y), LENGTH along the heading and WIDTH across it, at half-cell spacing:
+ *   (s, c) = det_sincosf((float)theta) widened to double (oracle.sincosf on the host);
+ *   corners in the car frame (L/2, W/2), (-L/2, W/2), (-L/2, -W/2), (L/2, -W/2); edge e runs from corner e to corner
+ *   e+1 mod 4 with n_e points k = 0 ... n_e-1 at u = k / n_e, n_e = max(1, ceil(len_e / (0.5 res))) on the host in
+ *   double (len_e = L for edges 0 and 2, W for 1 and 3); a = a0 + (a1 - a0) u, b likewise;
+ *   xw = x + (c a - s b), yw = y + (s a + c b);
+ *   gx0 = (xw - ox) inv_res, gy0 = (yw - oy) inv_res with inv_res = 1.0 / res in double and the map's float32
+ *   res, ox, oy widened; gx = wa_cos gx0 - wa_sin gy0, gy = wa_sin gx0 + wa_cos gy0 (MapParams' wa_cos / wa_sin);
+ *   col = floor(gx), row = floor(gy), kept inside the grid; non-finite points are skipped.
+ * Every operation is a separately rounded IEEE double (the library is built with -ffp-contract=off).  The outline is
+ * a set of cells: order and duplicates carry no meaning.  At most 512 points per car (RL_ERR_UNSUPPORTED beyond): the
+ * default 0.4064 x 0.2032 m car takes 2 (17 + 9) = 52 at 0.05 m per cell.  Maps of 32768 or more cells a side are
+ * refused (RL_ERR_UNSUPPORTED).
+ *
+ * Deliberate divergences from the reference:
+ *   - each car sees the others, not itself: rcs_two_player.py:105-116 stamps the scanned player's own bound too,
+ *     which would put its lidar inside an obstacle;
+ *   - getBound's defects are not reproduced: bound[i] / bound[i+1] overwrite each other, the points are not
+ *     translated to the car's position, and floatPosToPix adds +width / +height;
+ *   - races run on ray marching only (RM, RMGPU);
+ *   - a crashed car stays in the map as a wreck at its crash-tick state.
+ *
+ * rl_car_outline_cells: n cars (x, y, theta rows in double) on m with c's LENGTH / WIDTH -> per car its cells
+ * row * cols + col (points whose cell repeats the point before dropped), counts[i] of them, -1 past the count in a row
+ * of max_cells.  Errors (RL_ERR_INVALID): null pointers, n < 0, max_cells below the car's point count, handles on
+ * different devices or multi-device.
+ *
+ * rl_calc_range_fan_cars (+ _device on device pointers, asynchronous on `hip_stream`): pose i of group g (poses_p3 row
+ * g group + i, float32 world x, y, theta as rl_calc_range_fan takes them) is scanned as h scans it on the grid with the
+ * outline cells (length x width) of the OTHER group - 1 cars of group g stamped: cars_p3 rows g group + k, k != i, each
+ * (x, y, theta) in double.  outs / hits / steps as rl_calc_range_fan's, n_groups group num_rays rays.  Kinds RL_RM and
+ * RL_RM_GPU; variant 3 (RL_RM's default) marches with the upstream-literal arithmetic (rm_literal_kernel), variants 0
+ * and 1 with the canonical one (rm_march); h's step coefficient, max range and noise apply, the noise keyed by the
+ * global ray id h.ray_offset + p num_rays + j as in the plain fan.  K1b planner options (slots, code map, tiles, ...)
+ * do not apply and are ignored.  A group of 1 equals rl_calc_range_fan of the same poses bit for bit.
+ * Errors (the handle stays usable): RL_ERR_INVALID for null pointers, group outside [1, 8], num_rays outside
+ * [10, 1280], n_groups group num_rays >= 2^31, multi-device handles, a non-positive length or width;
+ * RL_ERR_UNSUPPORTED for RL_CDDT, RL_GIANT_LUT and RL_BRESENHAM (their tables cover the whole map: the single-race
+ * two_player.ScanSimulator2D with a stamp stays their path), variant 2, and outlines of more than 512 points.
+ *
+ * rl_car_race_followgap: rl_car_drive_followgap's loop (same arguments with n_rollouts = n_races group, same outputs,
+ * traces, NaN rows, noise offsets per tick, chunking and option restore) in which every tick's scan is the race scan
+ * above: every car of every race steps, then every car scans with the other cars of its race in the map, read from
+ * their f64 states on the device (c's LENGTH / WIDTH).  Then the unchanged drive_tick_kernel: the crash ballot,
+ * FollowGap, the next step.  A crashed car freezes and stays in the map; a car that drives into another crashes
+ * through its own scan, since the other car's cells fall inside its edge distances.  Nothing leaves the device
+ * between ticks.  Errors: those of rl_calc_range_fan_cars and rl_car_drive_followgap, n_races < 0.               */
+int rl_car_outline_cells(rl_car *c, rl_map *m, const double *cars_p3, int n, int max_cells, int32_t *cells,
+                         int *counts);
+int rl_calc_range_fan_cars(rl_method *h, const float *poses_p3, const double *cars_p3, int n_groups, int group,
+                           double length, double width, float fov, int num_rays, float *outs,
+                           int32_t *hit_cells_or_null, uint16_t *steps_or_null);
+int rl_calc_range_fan_cars_device(rl_method *h, const float *d_poses_p3, const double *d_cars_p3, int n_groups,
+                                  int group, double length, double width, float fov, int num_rays, float *d_outs,
+                                  int32_t *d_hit_cells_or_null, uint16_t *d_steps_or_null, void *hip_stream);
+int rl_car_race_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in, const double *speeds,
+                          const float *steer0_or_null, int n_races, int group, int n_ticks, double dt,
+                          double scan_dist_to_base, float fov, int num_rays, const double *edge, double crash_thresh,
+                          int *first_crashed, double *states_out_or_null, double *velocities_or_null,
+                          float *steers_or_null, float *scan_poses_or_null, double *states_trace_or_null);
+
 /* ---- the steering policy network ---------------------------------------------------------------
  * The reference's second steering source (scripts/policy.py:17-33, Policy.predict_action; driven at
  * scripts/policy_driver.py:30-49 and used by MCTS at scripts/mcts.py:252-256): a dense ReLU chain over the

@@ -124,6 +124,15 @@ SYMBOLS = {
     "rl_car_drive_followgap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, f64p, f64p, f32p, C.c_int, C.c_int,
                                          C.c_double, C.c_double, C.c_float, C.c_int, f64p, C.c_double,
                                          C.POINTER(C.c_int), f64p, f64p, f32p, f32p, f64p]),
+    "rl_car_outline_cells": (C.c_int, [C.c_void_p, C.c_void_p, f64p, C.c_int, C.c_int, i32p, C.POINTER(C.c_int)]),
+    "rl_calc_range_fan_cars": (C.c_int, [C.c_void_p, f32p, f64p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_float,
+                                         C.c_int, f32p, i32p, u16p]),
+    "rl_calc_range_fan_cars_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                                C.c_double, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]),
+    "rl_car_race_followgap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, f64p, f64p, f32p, C.c_int, C.c_int, C.c_int,
+                                        C.c_double, C.c_double, C.c_float, C.c_int, f64p, C.c_double,
+                                        C.POINTER(C.c_int), f64p, f64p, f32p, f32p, f64p]),
     "rl_policy_create": (C.c_int, [C.c_int, C.c_int, i32p, C.POINTER(f32p), C.POINTER(f32p), u8p, C.c_int,
                                    C.c_float, C.c_float, C.POINTER(C.c_void_p)]),
     "rl_policy_destroy": (None, [C.c_void_p]),

@@ -10,6 +10,7 @@
 #include "mcts_kernels.h"
 #include "policy_kernels.h"
 #include "probe_kernels.h"
+#include "race_kernels.h"
 
 struct rl_car {
     std::vector<rl_car *> reps;          // multi-device (rl_car_create_multi): one ordinary handle per device
@@ -20,6 +21,7 @@ struct rl_car {
     DevBuf states, actions, poses, states_out, vel, ranges, edge, first;
     DevBuf speeds, steer0, tr_steers, tr_poses, tr_states;     // rl_car_drive_followgap, rl_car_drive_policy
     DevBuf mlp;                                                // rl_car_drive_policy: the network's steers of a tick
+    DevBuf o_cars, o_cells, o_counts;                          // rl_car_outline_cells
     std::mutex mu;
 };
 
@@ -82,7 +84,8 @@ extern "C" void rl_car_destroy(rl_car *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (DevBuf *b : {&c->states, &c->actions, &c->poses, &c->states_out, &c->vel, &c->ranges, &c->edge, &c->first,
-                      &c->speeds, &c->steer0, &c->tr_steers, &c->tr_poses, &c->tr_states, &c->mlp})
+                      &c->speeds, &c->steer0, &c->tr_steers, &c->tr_poses, &c->tr_states, &c->mlp, &c->o_cars,
+                      &c->o_cells, &c->o_counts})
         b->release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -328,10 +331,11 @@ static constexpr std::array<drive_tick_fn, sizeof...(R)> drive_tick_make(std::in
 }
 static const std::array<drive_tick_fn, FG_ROWS> drive_tick_table = drive_tick_make(std::make_integer_sequence<int, FG_ROWS>());
 
-static int drive_args(rl_car *c, rl_method *h, rl_followgap *g, int R, int n_ticks, float fov, int num_rays)
+static int drive_args(rl_car *c, rl_method *h, rl_followgap *g, int R, int n_ticks, float fov, int num_rays,
+                      const char *name = "rl_car_drive_followgap")
 {
     if (!c->reps.empty() || !h->reps.empty())
-        return fail(RL_ERR_INVALID, "rl_car_drive_followgap is single-device only: pass ordinary (not multi-device) handles");
+        return fail(RL_ERR_INVALID, "%s is single-device only: pass ordinary (not multi-device) handles", name);
     if (c->device != h->map->device || g->device != c->device)
         return fail(RL_ERR_INVALID, "car (device %d), range method (device %d) and FollowGap (device %d) must share one device",
                     c->device, h->map->device, g->device);
@@ -342,17 +346,24 @@ static int drive_args(rl_car *c, rl_method *h, rl_followgap *g, int R, int n_tic
     return check_fan_args(h, R, fov, num_rays);
 }
 
-extern "C" int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in,
-                                      const double *speeds, const float *steer0_or_null, int R, int n_ticks, double dt,
-                                      double scan_dist_to_base, float fov, int num_rays, const double *edge,
-                                      double crash_thresh, int *first_crashed, double *states_out_or_null,
-                                      double *velocities_or_null, float *steers_or_null, float *scan_poses_or_null,
-                                      double *states_trace_or_null)
+static int race_args(rl_method *h, long n_groups, int group, int num_rays);
+static int race_outline(const rl_map *m, double length, double width, OutlineParams &o);
+static int launch_race(rl_method *h, const float *d_poses, const double *d_cars, int car_stride, int n_groups, int group,
+                       const OutlineParams &o, float fov, int num_rays, float *d_out, int32_t *d_hits, uint16_t *d_steps,
+                       hipStream_t stream);
+
+// rl_car_drive_followgap (group 0: every car scans alone with h's planner) and rl_car_race_followgap (group >= 1: the
+// cars scan in races of `group`, race_fan_kernel); the caller has checked the arguments
+static int drive_followgap_loop(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in, const double *speeds,
+                                const float *steer0_or_null, int R, int group, int n_ticks, double dt,
+                                double scan_dist_to_base, float fov, int num_rays, const double *edge,
+                                double crash_thresh, int *first_crashed, double *states_out_or_null,
+                                double *velocities_or_null, float *steers_or_null, float *scan_poses_or_null,
+                                double *states_trace_or_null)
 {
-    if (!c || !h || !g || (R > 0 && (!states_in || !speeds || !edge || !first_crashed)))
-        return fail(RL_ERR_INVALID, "rl_car_drive_followgap: null pointer");
-    int rc = drive_args(c, h, g, R, n_ticks, fov, num_rays);
-    if (rc || R == 0) return rc;
+    int rc = RL_OK;
+    OutlineParams op{};
+    if (group > 0 && (rc = race_outline(h->map, c->P.LENGTH, c->P.WIDTH, op))) return rc;
     std::scoped_lock lk(c->mu, h->mu, g->mu);
     std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
     HIPCHK(hipSetDevice(c->device));
@@ -401,7 +412,11 @@ extern "C" int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, 
     const drive_tick_fn tick = drive_tick_table[(num_rays + 63) / 64 - 1];
     for (int t = 0; t < n_ticks && rc == RL_OK; ++t) {
         h->ray_offset = base_off + (uint64_t)t * n_rays;
-        rc = launch_fan(h, (const float *)c->poses.p, R, fov, num_rays, (float *)c->ranges.p, nullptr, nullptr, nullptr, st);
+        // (a race reads every car's outline from its f64 state after this tick's step: all cars step, then all scan)
+        rc = group > 0 ? launch_race(h, (const float *)c->poses.p, (const double *)c->states.p, 11, R / group, group, op,
+                                     fov, num_rays, (float *)c->ranges.p, nullptr, nullptr, st)
+                       : launch_fan(h, (const float *)c->poses.p, R, fov, num_rays, (float *)c->ranges.p, nullptr,
+                                    nullptr, nullptr, st);
         if (rc == RL_OK) {
             tick<<<dim3((R + DRIVE_CARS - 1) / DRIVE_CARS), dim3(64 * DRIVE_CARS), 0, st>>>(dp, b, t);
             if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "drive_tick_kernel launch failed");
@@ -422,6 +437,199 @@ extern "C" int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, 
         HIPCHK(hipMemcpyAsync(states_trace_or_null, c->tr_states.p, rows * 88, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return RL_OK;
+}
+
+extern "C" int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in,
+                                      const double *speeds, const float *steer0_or_null, int R, int n_ticks, double dt,
+                                      double scan_dist_to_base, float fov, int num_rays, const double *edge,
+                                      double crash_thresh, int *first_crashed, double *states_out_or_null,
+                                      double *velocities_or_null, float *steers_or_null, float *scan_poses_or_null,
+                                      double *states_trace_or_null)
+{
+    if (!c || !h || !g || (R > 0 && (!states_in || !speeds || !edge || !first_crashed)))
+        return fail(RL_ERR_INVALID, "rl_car_drive_followgap: null pointer");
+    int rc = drive_args(c, h, g, R, n_ticks, fov, num_rays);
+    if (rc || R == 0) return rc;
+    return drive_followgap_loop(c, h, g, states_in, speeds, steer0_or_null, R, 0, n_ticks, dt, scan_dist_to_base, fov,
+                                num_rays, edge, crash_thresh, first_crashed, states_out_or_null, velocities_or_null,
+                                steers_or_null, scan_poses_or_null, states_trace_or_null);
+}
+
+// ---------------------------------------------------------------- batched races (race_kernels.h)
+// the canonical outline's host-side constants (include/scanlib.h)
+static int race_outline(const rl_map *m, double length, double width, OutlineParams &o)
+{
+    if (!(length > 0.0 && width > 0.0 && std::isfinite(length) && std::isfinite(width)))
+        return fail(RL_ERR_INVALID, "car length and width must be finite and > 0 (got %g, %g)", length, width);
+    if (m->rows > 32767 || m->cols > 32767)
+        return fail(RL_ERR_UNSUPPORTED, "races need a map below 32768 cells a side (got %d x %d)", m->rows, m->cols);
+    const double res = (double)m->mp.res, spacing = 0.5 * res;
+    const double n_l = std::max(1.0, std::ceil(length / spacing)), n_w = std::max(1.0, std::ceil(width / spacing));
+    if (2.0 * (n_l + n_w) > RACE_MAX_POINTS)
+        return fail(RL_ERR_UNSUPPORTED, "a %g x %g m car at %g m per cell takes %.0f outline points (at most %d)", length,
+                    width, res, 2.0 * (n_l + n_w), RACE_MAX_POINTS);
+    o.half_l = length / 2.0;
+    o.half_w = width / 2.0;
+    o.n_l = (int)n_l;
+    o.n_w = (int)n_w;
+    o.ox = (double)m->mp.ox;
+    o.oy = (double)m->mp.oy;
+    o.inv_res = 1.0 / res;
+    o.wa_cos = (double)m->mp.wa_cos;
+    o.wa_sin = (double)m->mp.wa_sin;
+    o.rows = m->rows;
+    o.cols = m->cols;
+    return RL_OK;
+}
+
+static int race_args(rl_method *h, long n_groups, int group, int num_rays)
+{
+    if (!h->reps.empty()) return fail(RL_ERR_INVALID, "races are single-device only: pass an ordinary (not multi-device) method");
+    if (group < 1 || group > RACE_MAX_GROUP)
+        return fail(RL_ERR_INVALID, "group must lie in [1, %d] cars (got %d)", RACE_MAX_GROUP, group);
+    if (n_groups < 0) return fail(RL_ERR_INVALID, "n_groups must be >= 0 (got %ld)", n_groups);
+    if (num_rays < 10 || num_rays > RACE_MAX_RAYS)
+        return fail(RL_ERR_INVALID, "num_rays must lie in [10, %d] (got %d)", RACE_MAX_RAYS, num_rays);
+    if (n_groups * group * num_rays >= (1L << 31)) return fail(RL_ERR_INVALID, "n_groups * group * num_rays must stay below 2^31");
+    if (h->kind != RL_RM && h->kind != RL_RM_GPU)
+        return fail(RL_ERR_UNSUPPORTED, "races run on ray marching only (RM, RMGPU): a CDDT, GiantLUT or Bresenham table "
+                                        "covers the whole map and cannot see the other cars");
+    if (h->opt.variant == 2)
+        return fail(RL_ERR_UNSUPPORTED, "races need the canonical (variant 0 / 1) or the upstream-literal (3) arithmetic, "
+                                        "not the occupancy window (2)");
+    return RL_OK;
+}
+
+typedef void (*race_fn)(MapParams, FanParams, LiteralParams, RaceParams, const float *, float *, int32_t *, uint16_t *);
+static const race_fn race_table[2][2] = {{race_fan_kernel<false, false>, race_fan_kernel<false, true>},
+                                         {race_fan_kernel<true, false>, race_fan_kernel<true, true>}};
+
+// one race_fan_kernel launch on `stream`: the caller holds h->mu and the map's tables_mu and has checked the arguments
+static int launch_race(rl_method *h, const float *d_poses, const double *d_cars, int car_stride, int n_groups, int group,
+                       const OutlineParams &o, float fov, int num_rays, float *d_out, int32_t *d_hits, uint16_t *d_steps,
+                       hipStream_t stream)
+{
+    if (n_groups == 0) return RL_OK;
+    const bool lit = h->opt.variant == 3, aux = d_hits || d_steps;
+    const FanParams f = make_fan(h, n_groups * group, fov, num_rays);
+    const LiteralParams lp = lit ? make_literal(h->map) : LiteralParams{};
+    const RaceParams rp{o, d_cars, car_stride, group, n_groups};
+    if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
+    race_table[lit][aux]<<<dim3(n_groups), dim3(RACE_WG), 0, stream>>>(h->map->mp, f, lp, rp, d_poses, d_out, d_hits,
+                                                                       d_steps);
+    HIPCHK(hipGetLastError());
+    if (h->timing) {
+        HIPCHK(hipEventRecord(h->ev1, stream));
+        h->timed = true;
+    }
+    return RL_OK;
+}
+
+static int fan_cars_checks(rl_method *h, int n_groups, int group, float fov, int num_rays, double length, double width,
+                           OutlineParams &o)
+{
+    int rc = race_args(h, n_groups, group, num_rays);
+    if (rc) return rc;
+    if ((rc = check_fan_args(h, n_groups * group, fov, num_rays))) return rc;
+    return race_outline(h->map, length, width, o);
+}
+
+extern "C" int rl_calc_range_fan_cars_device(rl_method *h, const float *d_poses, const double *d_cars, int n_groups,
+                                             int group, double length, double width, float fov, int num_rays,
+                                             float *d_outs, int32_t *d_hits, uint16_t *d_steps, void *hip_stream)
+{
+    if (!h || (n_groups > 0 && (!d_poses || !d_cars || !d_outs)))
+        return fail(RL_ERR_INVALID, "rl_calc_range_fan_cars_device: null pointer");
+    OutlineParams o{};
+    int rc = fan_cars_checks(h, n_groups, group, fov, num_rays, length, width, o);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
+    if ((rc = set_device(h->map))) return rc;
+    return launch_race(h, d_poses, d_cars, 3, n_groups, group, o, fov, num_rays, d_outs, d_hits, d_steps,
+                       (hipStream_t)hip_stream);
+}
+
+extern "C" int rl_calc_range_fan_cars(rl_method *h, const float *poses, const double *cars, int n_groups, int group,
+                                      double length, double width, float fov, int num_rays, float *outs,
+                                      int32_t *hits_or_null, uint16_t *steps_or_null)
+{
+    if (!h || (n_groups > 0 && (!poses || !cars || !outs))) return fail(RL_ERR_INVALID, "rl_calc_range_fan_cars: null pointer");
+    OutlineParams o{};
+    int rc = fan_cars_checks(h, n_groups, group, fov, num_rays, length, width, o);
+    if (rc || n_groups == 0) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
+    if ((rc = set_device(h->map))) return rc;
+    const size_t n = (size_t)n_groups * group, n_rays = n * num_rays;
+    if ((rc = h->poses.ensure(n * 12)) || (rc = h->cars.ensure(n * 24)) || (rc = h->outs.ensure(n_rays * 4)) ||
+        (hits_or_null && (rc = h->hits.ensure(n_rays * 8))) || (steps_or_null && (rc = h->steps.ensure(n_rays * 2))))
+        return rc;
+    hipStream_t st = h->stream;
+    HIPCHK(hipMemcpyAsync(h->poses.p, poses, n * 12, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->cars.p, cars, n * 24, hipMemcpyHostToDevice, st));
+    rc = launch_race(h, (const float *)h->poses.p, (const double *)h->cars.p, 3, n_groups, group, o, fov, num_rays,
+                     (float *)h->outs.p, hits_or_null ? (int32_t *)h->hits.p : nullptr,
+                     steps_or_null ? (uint16_t *)h->steps.p : nullptr, st);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    HIPCHK(hipMemcpyAsync(outs, h->outs.p, n_rays * 4, hipMemcpyDeviceToHost, st));
+    if (hits_or_null) HIPCHK(hipMemcpyAsync(hits_or_null, h->hits.p, n_rays * 8, hipMemcpyDeviceToHost, st));
+    if (steps_or_null) HIPCHK(hipMemcpyAsync(steps_or_null, h->steps.p, n_rays * 2, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
+}
+
+extern "C" int rl_car_outline_cells(rl_car *c, rl_map *m, const double *cars_p3, int n, int max_cells, int32_t *cells,
+                                    int *counts)
+{
+    if (!c || !m || (n > 0 && (!cars_p3 || !cells || !counts))) return fail(RL_ERR_INVALID, "rl_car_outline_cells: null pointer");
+    if (!c->reps.empty() || !m->reps.empty())
+        return fail(RL_ERR_INVALID, "rl_car_outline_cells is single-device only: pass ordinary (not multi-device) handles");
+    if (c->device != m->device) return fail(RL_ERR_INVALID, "car and map live on different devices");
+    if (n < 0) return fail(RL_ERR_INVALID, "n must be >= 0 (got %d)", n);
+    OutlineParams o{};
+    int rc = race_outline(m, c->P.LENGTH, c->P.WIDTH, o);
+    if (rc) return rc;
+    const int n_pts = 2 * (o.n_l + o.n_w);
+    if (max_cells < n_pts) return fail(RL_ERR_INVALID, "max_cells must be >= the %d outline points of a car (got %d)", n_pts, max_cells);
+    if (n == 0) return RL_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    const size_t n_cells = (size_t)n * max_cells;
+    if ((rc = c->o_cars.ensure((size_t)n * 24)) || (rc = c->o_cells.ensure(n_cells * 4)) ||
+        (rc = c->o_counts.ensure((size_t)n * 4)))
+        return rc;
+    hipStream_t st = c->stream;
+    HIPCHK(hipMemcpyAsync(c->o_cars.p, cars_p3, (size_t)n * 24, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(outline_cells_kernel, dim3((n + 3) / 4), dim3(256), 0, st, o, (const double *)c->o_cars.p, n,
+                       max_cells, (int32_t *)c->o_cells.p, (int *)c->o_counts.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(cells, c->o_cells.p, n_cells * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(counts, c->o_counts.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
+}
+
+extern "C" int rl_car_race_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in,
+                                     const double *speeds, const float *steer0_or_null, int n_races, int group,
+                                     int n_ticks, double dt, double scan_dist_to_base, float fov, int num_rays,
+                                     const double *edge, double crash_thresh, int *first_crashed,
+                                     double *states_out_or_null, double *velocities_or_null, float *steers_or_null,
+                                     float *scan_poses_or_null, double *states_trace_or_null)
+{
+    if (!c || !h || !g || (n_races > 0 && (!states_in || !speeds || !edge || !first_crashed)))
+        return fail(RL_ERR_INVALID, "rl_car_race_followgap: null pointer");
+    if (n_races < 0) return fail(RL_ERR_INVALID, "n_races must be >= 0 (got %d)", n_races);
+    int rc = race_args(h, n_races, group, num_rays);
+    if (rc) return rc;
+    const int R = n_races * group;          // (< 2^31 / num_rays: race_args)
+    if ((rc = drive_args(c, h, g, R, n_ticks, fov, num_rays, "rl_car_race_followgap")) || R == 0) return rc;
+    return drive_followgap_loop(c, h, g, states_in, speeds, steer0_or_null, R, group, n_ticks, dt, scan_dist_to_base,
+                                fov, num_rays, edge, crash_thresh, first_crashed, states_out_or_null, velocities_or_null,
+                                steers_or_null, scan_poses_or_null, states_trace_or_null);
 }
 
 // ---------------------------------------------------------------- the steering policy network (policy_kernels.h)

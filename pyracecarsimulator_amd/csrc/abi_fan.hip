@@ -100,6 +100,7 @@ extern "C" void rl_method_destroy(rl_method *h)
     h->steps.release();
     h->edge.release();
     h->flag.release();
+    h->cars.release();
     if (h->pin) (void)hipHostFree(h->pin);
     if (h->pin_flag) (void)hipHostFree(h->pin_flag);
     for (LaunchCtx &c : h->ctx) c.release();
@@ -282,7 +283,7 @@ extern "C" int rl_method_get_info(rl_method *h, const char *name, int64_t *value
 // ------------------------------------------------------------------------------
 // launches
 // ------------------------------------------------------------------------------
-static FanParams make_fan(const rl_method *h, int n_poses, float fov, int num_rays)
+FanParams make_fan(const rl_method *h, int n_poses, float fov, int num_rays)
 {
     FanParams f{};
     f.n_poses = n_poses;
@@ -859,7 +860,7 @@ static int dispatch_rm_stream(const rl_launch_plan &pl, hipStream_t stream, cons
 // plan::plan_fan (launch_plan.h); this function only executes the plan.
 // audit mode (variant 3): the per-map constants of range_libc's RangeMethod, double arithmetic with the host's libm
 // (as the CPU checker's upstream-literal statement computes them)
-static LiteralParams make_literal(const rl_map *m)
+LiteralParams make_literal(const rl_map *m)
 {
     LiteralParams lt;
     const double wa = (double)m->mp.wa;

@@ -5,13 +5,14 @@
 //                  device-pointer entry points, the single-device host-pointer paths, the fused crash test
 //   abi_multi.hip  the host-pointer entry points and their multi-device forms (one pose block per device)
 //   abi_car.hip    roll-out generator, FollowGap, the policy network, closed-loop FollowGap / policy roll-outs,
-//                  16-bit ranges, probes, the car-outline table
+//                  batched races, 16-bit ranges, probes, the car-outline table
 #pragma once
 // (the units are built with -fvisibility=hidden: only the C ABI leaves the library)
 #pragma GCC visibility push(default)
 #include "../../include/scanlib.h"
 #pragma GCC visibility pop
 #include "scan_params.h"
+#include "literal_math.h"
 
 #include <hip/hip_runtime.h>
 
@@ -313,6 +314,7 @@ struct rl_method {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     DevBuf poses, outs, hits, steps, edge, flag;
+    DevBuf cars;                 // rl_calc_range_fan_cars: the cars' (x, y, theta) rows
     LaunchCtx ctx[N_LAUNCH_CTX];
     uint64_t use_clock = 0;
     TableDep pdt_dep, lut_dep, cddt_dep;
@@ -367,6 +369,8 @@ void host_sincosf(float x, float &s, float &c);      // host twin of scan::det_s
 // abi_fan.hip, called from abi_multi.hip / abi_car.hip
 // ------------------------------------------------------------------------------
 int check_fan_args(const rl_method *h, int n_poses, float fov, int num_rays);
+FanParams make_fan(const rl_method *h, int n_poses, float fov, int num_rays);   // the handle's range, coefficient, noise
+LiteralParams make_literal(const rl_map *m);                                     // variant 3's per-map constants
 namespace scan { struct CrashParams; }
 // one fan launch sequence on `stream` as the planner picks it (noise keyed by h->ray_offset; the caller holds h->mu and
 // the map's tables_mu and has checked the arguments)

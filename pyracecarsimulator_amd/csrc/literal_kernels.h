@@ -19,9 +19,10 @@
 
 namespace scan {
 
-// one upstream-literal cast from a world pose (the checker's rm_cast_libm)
-__device__ __forceinline__ RayResult literal_cast(const MapParams &m, const LiteralParams &lp, float max_range,
-                                                  float step_coeff, float xw, float yw, float thw)
+// one upstream-literal cast from a world pose (the checker's rm_cast_libm); `dist(row, col)` as rm_march_dist's
+template <class DIST>
+__device__ __forceinline__ RayResult literal_cast_dist(const MapParams &m, const LiteralParams &lp, float max_range,
+                                                       float step_coeff, float xw, float yw, float thw, DIST dist)
 {
     RayResult res;
     res.range_px = max_range;
@@ -43,7 +44,7 @@ __device__ __forceinline__ RayResult literal_cast(const MapParams &m, const Lite
         if (fx != fx || fy != fy) break;
         const int px = (int)fx, py = (int)fy;
         if (px >= m.rows || px < 0 || py < 0 || py >= m.cols) break;
-        const float d = m.dt[(size_t)px * m.cols + py];
+        const float d = dist(px, py);
         ++res.steps;
         if (d <= 0.0f) {
             const float xd = (float)px - x0, yd = (float)py - y0;
@@ -56,6 +57,20 @@ __device__ __forceinline__ RayResult literal_cast(const MapParams &m, const Lite
         t += st > 1.0f ? st : 1.0f;
     }
     return res;
+}
+
+__device__ __forceinline__ RayResult literal_cast(const MapParams &m, const LiteralParams &lp, float max_range,
+                                                  float step_coeff, float xw, float yw, float thw)
+{
+    return literal_cast_dist(m, lp, max_range, step_coeff, xw, yw, thw,
+                             [&m](int px, int py) { return m.dt[(size_t)px * m.cols + py]; });
+}
+
+// the range noise of global ray id i (f.noise_std > 0): the one generator call the fan kernels of this file and the
+// race kernel (race_kernels.h) share
+__device__ __forceinline__ float fan_noise(const FanParams &f, uint64_t i)
+{
+    return f.noise_std * gauss_noise(f.noise_seed, f.ray_offset + i);
 }
 
 // fan form (the fork's 4-argument calc_range_many): beam j of pose p at theta_p + (amin + j * inc), the sum and the
@@ -80,7 +95,7 @@ __global__ __launch_bounds__(256) void rm_literal_kernel(MapParams m, FanParams 
         }
         const RayResult r = literal_cast(m, lp, f.max_range, f.step_coeff, xw, yw, th);
         float v = r.range_px * m.res;
-        if (f.noise_std > 0.0f) v += f.noise_std * gauss_noise(f.noise_seed, f.ray_offset + (uint64_t)i);
+        if (f.noise_std > 0.0f) v += fan_noise(f, (uint64_t)i);
         if (out) out[i] = v;
         if (AUX) {
             if (hits) { hits[2 * i] = r.hit_c; hits[2 * i + 1] = r.hit_r; }

@@ -150,9 +150,11 @@ struct RayResult {
     unsigned steps;
 };
 
-__device__ __forceinline__ RayResult rm_march(const MapParams &m, float max_range,
-                                              float step_coeff, float gx, float gy, float dx,
-                                              float dy)
+// `dist(row, col)` is the distance the march reads at an in-grid cell: the map's EDT for rm_march, the EDT with other
+// cars' outline cells folded in for the race kernel (race_kernels.h).
+template <class DIST>
+__device__ __forceinline__ RayResult rm_march_dist(const MapParams &m, float max_range, float step_coeff, float gx,
+                                                   float gy, float dx, float dy, DIST dist)
 {
     RayResult res;
     res.range_px = max_range;
@@ -166,7 +168,7 @@ __device__ __forceinline__ RayResult rm_march(const MapParams &m, float max_rang
         // same cell set as (int)fx in [0,cols) && (int)fy in [0,rows); NaN/huge -> miss
         if (!(fx > -1.0f && fx < m.fcols && fy > -1.0f && fy < m.frows)) break;
         int pc = (int)fx, pr = (int)fy;
-        float d = m.dt[(size_t)pr * m.cols + pc];
+        float d = dist(pr, pc);
         ++res.steps;
         if (d <= 0.0f) {
             float xd = (float)pc - gx;
@@ -179,6 +181,14 @@ __device__ __forceinline__ RayResult rm_march(const MapParams &m, float max_rang
         t += __builtin_fmaxf(d * step_coeff, 1.0f);
     }
     return res;
+}
+
+__device__ __forceinline__ RayResult rm_march(const MapParams &m, float max_range,
+                                              float step_coeff, float gx, float gy, float dx,
+                                              float dy)
+{
+    return rm_march_dist(m, max_range, step_coeff, gx, gy, dx, dy,
+                         [&m](int pr, int pc) { return m.dt[(size_t)pr * m.cols + pc]; });
 }
 
 }  // namespace scan

@@ -16,6 +16,8 @@ on the GPU:
 device (poses and ranges never cross PCIe).  ``CarBatch.drive_followgap`` closes the loop: each tick's
 steering angle is FollowGap's answer to that tick's scan, all on the device.  ``CarBatch.plan_mcts`` runs
 scripts/mcts.py's tree search for many trees at once on the device (``mcts.MCTSPlanner``).
+``CarBatch.race_followgap`` runs many races of up to 8 cars at once, each car's scan seeing the other cars of its
+race (scripts/two_player/); ``CarBatch.outline_cells`` gives the canonical outline cells of the cars.
 """
 from __future__ import annotations
 
@@ -143,6 +145,51 @@ class CarBatch:
         if trace:
             return first, out, vel, steers, poses, trace_st
         return first, out, vel, steers
+
+    def outline_cells(self, omap, car_poses):
+        """The canonical outline cells of each car (``rl_car_outline_cells``, include/scanlib.h) on ``omap`` (a
+        ``range_libc.PyOMap``) with this batch's length and width.  car_poses float64 (n, 3) as (x, y, theta).
+        Returns (cells int32 (n, max count) as row * cols + col, -1 padded; counts int32 (n,))."""
+        cars = np.ascontiguousarray(car_poses, dtype=np.float64).reshape(-1, 3)
+        n = cars.shape[0]
+        cells = np.empty((n, 512), dtype=np.int32)
+        counts = np.zeros(n, dtype=np.int32)
+        _lib.check(_lib.lib().rl_car_outline_cells(self._h, omap._h, cars.ctypes.data_as(f64p), n, 512,
+                                                    cells.ctypes.data_as(_lib.i32p),
+                                                    counts.ctypes.data_as(C.POINTER(C.c_int))))
+        width = int(counts.max()) if n else 0
+        return np.ascontiguousarray(cells[:, :width]), counts
+
+    def race_followgap(self, method, followgap, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
+                       steer0=None, dt=0.01, trace=False, scan_dist_to_base=0.275):
+        """Batched closed-loop races (``rl_car_race_followgap``): ``drive_followgap``'s loop in which every car's scan
+        sees the other cars of its race (scripts/two_player/: ros_interface_two_player.py's tick, simple_driver.py's
+        FollowGap).  states float64 (R, P, 11) — R races of P <= 8 cars —; speed a scalar or float64 (R, P); steer0
+        None (0) or float32 (R, P).  Returns ``drive_followgap``'s tuple with R P reshaped to (R, P): first crash tick
+        (R, P), final states (R, P, 11), velocities and steers (R, P, n_ticks), with ``trace=True`` also lidar poses
+        (R, P, n_ticks, 3) and states (R, P, n_ticks, 11).  A crashed car stays in its race as a wreck."""
+        st = np.asarray(states)
+        if st.dtype != np.float64 or st.ndim != 3 or st.shape[2] != 11:
+            raise ValueError("states must be float64 (R, P, 11)")
+        n_races, group = st.shape[0], st.shape[1]
+        spd = np.asarray(speed, dtype=np.float64)
+        spd = float(spd) if spd.ndim == 0 else spd.reshape(-1)
+        st0 = None if steer0 is None else np.asarray(steer0).reshape(-1)
+        R, n_ticks, states_f, speeds, st0, edge, first, out, vel, steers, poses, trace_st = self._drive_args(
+            st.reshape(-1, 11), n_ticks, spd, num_rays, edge, st0, trace)
+        ptr = lambda a, t: a.ctypes.data_as(t) if a is not None else None
+        _lib.check(_lib.lib().rl_car_race_followgap(
+            self._h, method._h, followgap._h, states_f.ctypes.data_as(f64p), speeds.ctypes.data_as(f64p),
+            ptr(st0, f32p), n_races, group, n_ticks, float(dt), float(scan_dist_to_base), float(fov), int(num_rays),
+            edge.ctypes.data_as(f64p), float(crash_thresh), first.ctypes.data_as(C.POINTER(C.c_int)),
+            out.ctypes.data_as(f64p), vel.ctypes.data_as(f64p), steers.ctypes.data_as(f32p), ptr(poses, f32p),
+            ptr(trace_st, f64p)))
+        T = vel.shape[1]
+        res = (first.reshape(n_races, group), out.reshape(n_races, group, 11), vel.reshape(n_races, group, T),
+               steers.reshape(n_races, group, T))
+        if trace:
+            res += (poses.reshape(n_races, group, T, 3), trace_st.reshape(n_races, group, T, 11))
+        return res
 
     def drive_policy(self, method, policy, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
                      scan_dist_to_base=0.275, dt=0.01, steer0=None, steer_clip=None, trace=False):

@@ -15,7 +15,7 @@ it unchanged.  The two native pieces behind it are on the GPU:
 (scripts/mcts.py:202-245) for any number of roll-outs per call; ``driveFollowGapMany`` the closed
 loop of the simulator tick and simple_driver.py's FollowGap answer to every scan; ``drivePolicyMany`` the same loop
 steered by the policy network (scripts/policy_driver.py); ``planMCTSMany`` scripts/mcts.py's tree search from many
-start states at once.
+start states at once; ``raceFollowGapMany`` many races of up to 8 cars that see each other (scripts/two_player/).
 """
 from __future__ import annotations
 
@@ -162,6 +162,19 @@ class RacecarSimulator:
                                         np.asarray(states, dtype=np.float64).reshape(-1, 11), n_ticks, speed,
                                         self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
                                         scan_dist_to_base=self.scan_dist_to_base)
+
+    def raceFollowGapMany(self, states, n_ticks, speed=2.0):
+        """R batched races of P cars (states float64 (R, P, 11)) under ``driveFollowGapMany``'s driver, method, edge
+        table and ttc_thresh: scripts/two_player/'s tick (every car steps, then every car scans with the others in the
+        map) for many races at once.  Returns ``CarBatch.race_followgap``'s (first crash tick or -(n_ticks+1) (R, P),
+        final states, velocities, steers); ranges never leave the GPU."""
+        if self._followgap is None:
+            from .followgap import PyFollowGap
+            self._followgap = PyFollowGap(10, 15.0, self.max_steer_ang, 0.004, device=self._device)
+        return self.car.race_followgap(self.scan_simulator.scan_method, self._followgap,
+                                       np.asarray(states, dtype=np.float64), n_ticks, speed, self.scan_fov,
+                                       self.num_rays, self.edge_distances, self.ttc_thresh,
+                                       scan_dist_to_base=self.scan_dist_to_base)
 
     def drivePolicyMany(self, states, n_ticks, policy, speed=2.0, steer_clip=None):
         """``driveFollowGapMany`` with the steer of every tick from ``policy`` (a ``policy.Policy``, e.g.

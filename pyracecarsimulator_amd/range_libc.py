@@ -257,6 +257,44 @@ class _RangeMethod:
             steps.ctypes.data_as(u16p) if steps is not None else None))
         return None
 
+    def calc_range_fan_cars(self, poses, car_poses, group, fov, num_rays, outs=None, length=0.4064, width=0.2032,
+                            hit_cells=None, steps=None):
+        """The scan of N = n_groups * group poses in races of ``group`` cars (``rl_calc_range_fan_cars``): pose i of
+        group g is scanned on the grid with the outlines (length x width, the reference car by default) of the OTHER
+        cars of group g stamped, car k at ``car_poses`` row g * group + k.  poses float32 (N, 3) lidar poses; car_poses
+        float64 (N, 3) car states (x, y, theta).  RM and RMGPU only.  Returns outs float32 (N * num_rays,)."""
+        poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
+        cars = np.ascontiguousarray(car_poses, dtype=np.float64).reshape(-1, 3)
+        group = int(group)
+        if cars.shape[0] != poses.shape[0]:
+            raise ValueError("car_poses needs one (x, y, theta) row per pose")
+        if group < 1 or poses.shape[0] % group:
+            raise ValueError("the number of poses must be a multiple of group >= 1")
+        n = poses.shape[0] * int(num_rays)
+        if outs is None:
+            outs = np.empty(n, dtype=np.float32)
+        if outs.dtype != np.float32 or not outs.flags.c_contiguous or outs.size < n:
+            raise ValueError("outs must be C-contiguous float32 with N*num_rays elements")
+        if hit_cells is not None and (hit_cells.dtype != np.int32 or hit_cells.size < 2 * n
+                                      or not hit_cells.flags.c_contiguous):
+            raise ValueError("hit_cells must be C-contiguous int32 (N*num_rays, 2)")
+        if steps is not None and (steps.dtype != np.uint16 or steps.size < n or not steps.flags.c_contiguous):
+            raise ValueError("steps must be C-contiguous uint16 (N*num_rays,)")
+        _lib.check(_lib.lib().rl_calc_range_fan_cars(
+            self._h, poses.ctypes.data_as(f32p), cars.ctypes.data_as(f64p), poses.shape[0] // group, group,
+            float(length), float(width), float(fov), int(num_rays), outs.ctypes.data_as(f32p),
+            hit_cells.ctypes.data_as(i32p) if hit_cells is not None else None,
+            steps.ctypes.data_as(u16p) if steps is not None else None))
+        return outs
+
+    def calc_range_fan_cars_device(self, d_poses_ptr, d_cars_ptr, n_groups, group, fov, num_rays, d_outs_ptr,
+                                   length=0.4064, width=0.2032, d_hits_ptr=0, d_steps_ptr=0, stream=0):
+        """``calc_range_fan_cars`` on device pointers (ints, e.g. torch ``tensor.data_ptr()``): asynchronous."""
+        _lib.check(_lib.lib().rl_calc_range_fan_cars_device(
+            self._h, C.c_void_p(d_poses_ptr), C.c_void_p(d_cars_ptr), int(n_groups), int(group), float(length),
+            float(width), float(fov), int(num_rays), C.c_void_p(d_outs_ptr), C.c_void_p(d_hits_ptr or None),
+            C.c_void_p(d_steps_ptr or None), C.c_void_p(stream or None)))
+
     def calc_range_fan_device(self, d_poses_ptr, n_poses, fov, num_rays, d_outs_ptr,
                               d_hits_ptr=0, d_steps_ptr=0, stream=0):
         """Asynchronous launch on device pointers (ints), e.g. torch ``tensor.data_ptr()``."""
