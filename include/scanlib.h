@@ -291,7 +291,8 @@ int rl_car_rollout_check(rl_car *c, rl_method *h, const double *states_in, const
  * Errors (RL_ERR_INVALID, all three handles stay usable): null pointers, n_ticks <= 0, num_rays outside
  * [10, 1280] (the one-bit-per-beam FollowGap kernel), R num_rays >= 2^31, handles on different devices,
  * multi-device handles.  R = 0 does nothing.  Synchronous; h's options and noise offset read the same after
- * the call.  Per tick: the fan launch sequence of h's planner, then one drive_tick_kernel (drive_kernels.h). */
+ * the call.  Per tick: the fan launch sequence of h's planner, then one drive_tick_kernel with FollowGap as the
+ * steering source (drive_kernels.h).                                                                          */
 int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in,
                            const double *speeds, const float *steer0_or_null, int n_rollouts, int n_ticks,
                            double dt, double scan_dist_to_base, float fov, int num_rays, const double *edge,
@@ -356,10 +357,10 @@ int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, const doubl
  * rl_car_race_followgap: rl_car_drive_followgap's loop (same arguments with n_rollouts = n_races group, same outputs,
  * traces, NaN rows, noise offsets per tick, chunking and option restore) in which every tick's scan is the race scan
  * above: every car of every race steps, then every car scans with the other cars of its race in the map, read from
- * their f64 states on the device (c's LENGTH / WIDTH).  Then the unchanged drive_tick_kernel: the crash ballot,
- * FollowGap, the next step.  A crashed car freezes and stays in the map; a car that drives into another crashes
- * through its own scan, since the other car's cells fall inside its edge distances.  Nothing leaves the device
- * between ticks.  Errors: those of rl_calc_range_fan_cars and rl_car_drive_followgap, n_races < 0.               */
+ * their f64 states on the device (c's LENGTH / WIDTH).  Then rl_car_drive_followgap's drive_tick_kernel: the crash
+ * ballot, FollowGap, the next step.  A crashed car freezes and stays in the map; a car that drives into another
+ * crashes through its own scan, since the other car's cells fall inside its edge distances.  Nothing leaves the
+ * device between ticks.  Errors: those of rl_calc_range_fan_cars and rl_car_drive_followgap, n_races < 0.        */
 int rl_car_outline_cells(rl_car *c, rl_map *m, const double *cars_p3, int n, int max_cells, int32_t *cells,
                          int *counts);
 int rl_calc_range_fan_cars(rl_method *h, const float *poses_p3, const double *cars_p3, int n_groups, int group,
@@ -414,7 +415,7 @@ int rl_policy_eval_device(rl_policy *p, const float *d_scans, int n_scans, int s
  * Car::control clamps later (as scripts/mcts.py passes the raw output to drive()).  Errors (RL_ERR_INVALID, the
  * handles stay usable): those of rl_car_drive_followgap with p in g's place, and num_rays < in_start + dims[0].
  * Per tick: the fan launch sequence of h's planner, policy_mlp_kernel over every car's scan, then one
- * policy_tick_kernel (crash ballot and car step, drive_kernels.h).                                           */
+ * drive_tick_kernel with the network as the steering source (drive_kernels.h).                              */
 int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const double *states_in, const double *speeds,
                         const float *steer0_or_null, int n_rollouts, int n_ticks, double dt, double scan_dist_to_base,
                         float fov, int num_rays, const double *edge, double crash_thresh, double steer_clip,

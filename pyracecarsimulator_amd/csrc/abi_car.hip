@@ -262,14 +262,21 @@ extern "C" void rl_followgap_destroy(rl_followgap *g)
     delete g;
 }
 
-// followgap_bits_kernel<ROWS>, ROWS = 1 ... FG_ROWS
-typedef void (*fg_bits_fn)(const float *, int, FollowGapParams, float *);
-template <int... R>
-static constexpr std::array<fg_bits_fn, sizeof...(R)> fg_bits_make(std::integer_sequence<int, R...>)
+// a kernel's ROWS = 1 ... FG_ROWS instantiations, indexed by ROWS - 1: make(std::integral_constant<int, ROWS>) names one
+template <class Fn, class Make, int... R>
+static std::array<Fn, sizeof...(R)> rows_table(Make make, std::integer_sequence<int, R...>)
 {
-    return {{followgap_bits_kernel<R + 1>...}};
+    return {{make(std::integral_constant<int, R + 1>())...}};
 }
-static const std::array<fg_bits_fn, FG_ROWS> fg_bits_table = fg_bits_make(std::make_integer_sequence<int, FG_ROWS>());
+template <class Fn, class Make>
+static std::array<Fn, FG_ROWS> rows_table(Make make)
+{
+    return rows_table<Fn>(make, std::make_integer_sequence<int, FG_ROWS>());
+}
+
+typedef void (*fg_bits_fn)(const float *, int, FollowGapParams, float *);
+static const std::array<fg_bits_fn, FG_ROWS> fg_bits_table =
+    rows_table<fg_bits_fn>([](auto rows) { return followgap_bits_kernel<rows>; });
 
 static int followgap_launch(rl_followgap *g, const float *d_scans, int n_scans, int size,
                             float *d_angles, hipStream_t stream)
@@ -319,140 +326,6 @@ extern "C" int rl_followgap_eval_device(rl_followgap *g, const float *d_scans, i
     std::lock_guard<std::mutex> lk(g->mu);
     HIPCHK(hipSetDevice(g->device));
     return followgap_launch(g, d_scans, n_scans, size, d_angles, (hipStream_t)hip_stream);
-}
-
-// ---------------------------------------------------------------- closed-loop FollowGap roll-outs (drive_kernels.h)
-// drive_tick_kernel<ROWS>, ROWS = 1 ... FG_ROWS
-typedef void (*drive_tick_fn)(DriveParams, DriveBufs, int);
-template <int... R>
-static constexpr std::array<drive_tick_fn, sizeof...(R)> drive_tick_make(std::integer_sequence<int, R...>)
-{
-    return {{drive_tick_kernel<R + 1>...}};
-}
-static const std::array<drive_tick_fn, FG_ROWS> drive_tick_table = drive_tick_make(std::make_integer_sequence<int, FG_ROWS>());
-
-static int drive_args(rl_car *c, rl_method *h, rl_followgap *g, int R, int n_ticks, float fov, int num_rays,
-                      const char *name = "rl_car_drive_followgap")
-{
-    if (!c->reps.empty() || !h->reps.empty())
-        return fail(RL_ERR_INVALID, "%s is single-device only: pass ordinary (not multi-device) handles", name);
-    if (c->device != h->map->device || g->device != c->device)
-        return fail(RL_ERR_INVALID, "car (device %d), range method (device %d) and FollowGap (device %d) must share one device",
-                    c->device, h->map->device, g->device);
-    if (R < 0 || n_ticks <= 0) return fail(RL_ERR_INVALID, "n_rollouts >= 0 and n_ticks > 0 required (got %d, %d)", R, n_ticks);
-    if (num_rays < 10 || num_rays > 64 * FG_ROWS)
-        return fail(RL_ERR_INVALID, "num_rays must lie in [10, %d] (got %d)", 64 * FG_ROWS, num_rays);
-    if ((long)R * num_rays >= (1L << 31)) return fail(RL_ERR_INVALID, "n_rollouts * num_rays must stay below 2^31");
-    return check_fan_args(h, R, fov, num_rays);
-}
-
-static int race_args(rl_method *h, long n_groups, int group, int num_rays);
-static int race_outline(const rl_map *m, double length, double width, OutlineParams &o);
-static int launch_race(rl_method *h, const float *d_poses, const double *d_cars, int car_stride, int n_groups, int group,
-                       const OutlineParams &o, float fov, int num_rays, float *d_out, int32_t *d_hits, uint16_t *d_steps,
-                       hipStream_t stream);
-
-// rl_car_drive_followgap (group 0: every car scans alone with h's planner) and rl_car_race_followgap (group >= 1: the
-// cars scan in races of `group`, race_fan_kernel); the caller has checked the arguments
-static int drive_followgap_loop(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in, const double *speeds,
-                                const float *steer0_or_null, int R, int group, int n_ticks, double dt,
-                                double scan_dist_to_base, float fov, int num_rays, const double *edge,
-                                double crash_thresh, int *first_crashed, double *states_out_or_null,
-                                double *velocities_or_null, float *steers_or_null, float *scan_poses_or_null,
-                                double *states_trace_or_null)
-{
-    int rc = RL_OK;
-    OutlineParams op{};
-    if (group > 0 && (rc = race_outline(h->map, c->P.LENGTH, c->P.WIDTH, op))) return rc;
-    std::scoped_lock lk(c->mu, h->mu, g->mu);
-    std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
-    HIPCHK(hipSetDevice(c->device));
-    const size_t rows = (size_t)R * n_ticks, n_rays = (size_t)R * num_rays;
-    if ((rc = c->states.ensure((size_t)R * 11 * 8)) || (rc = c->speeds.ensure((size_t)R * 8)) ||
-        (rc = c->steer0.ensure((size_t)R * 4)) || (rc = c->first.ensure((size_t)R * 4)) ||
-        (rc = c->poses.ensure((size_t)R * 12)) || (rc = c->ranges.ensure(n_rays * 4)) ||
-        (rc = c->edge.ensure((size_t)num_rays * 8)) ||
-        (velocities_or_null && (rc = c->vel.ensure(rows * 8))) || (steers_or_null && (rc = c->tr_steers.ensure(rows * 4))) ||
-        (scan_poses_or_null && (rc = c->tr_poses.ensure(rows * 12))) ||
-        (states_trace_or_null && (rc = c->tr_states.ensure(rows * 88))))
-        return rc;
-    hipStream_t st = c->stream;
-    HIPCHK(hipMemcpyAsync(c->states.p, states_in, (size_t)R * 11 * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(c->speeds.p, speeds, (size_t)R * 8, hipMemcpyHostToDevice, st));
-    if (steer0_or_null) HIPCHK(hipMemcpyAsync(c->steer0.p, steer0_or_null, (size_t)R * 4, hipMemcpyHostToDevice, st));
-    else HIPCHK(hipMemsetAsync(c->steer0.p, 0, (size_t)R * 4, st));
-    HIPCHK(hipMemcpyAsync(c->edge.p, edge, (size_t)num_rays * 8, hipMemcpyHostToDevice, st));
-    // trace rows a car never reaches (after its crash tick; the steer of the crash tick) read NaN: all-ones bytes
-    if (velocities_or_null) HIPCHK(hipMemsetAsync(c->vel.p, 0xff, rows * 8, st));
-    if (steers_or_null) HIPCHK(hipMemsetAsync(c->tr_steers.p, 0xff, rows * 4, st));
-    if (scan_poses_or_null) HIPCHK(hipMemsetAsync(c->tr_poses.p, 0xff, rows * 12, st));
-    if (states_trace_or_null) HIPCHK(hipMemsetAsync(c->tr_states.p, 0xff, rows * 88, st));
-
-    DriveParams dp{};
-    dp.P = c->P;
-    dp.fg = g->P;
-    dp.fg.size = num_rays;
-    dp.dt = dt;
-    dp.scan_dist_to_base = scan_dist_to_base;
-    dp.crash_thresh = crash_thresh;
-    dp.n_cars = R;
-    dp.n_ticks = n_ticks;
-    DriveBufs b{(double *)c->states.p, (const double *)c->speeds.p, (const float *)c->steer0.p, (const double *)c->edge.p,
-                (int *)c->first.p, (float *)c->poses.p, (const float *)c->ranges.p,
-                velocities_or_null ? (double *)c->vel.p : nullptr, steers_or_null ? (float *)c->tr_steers.p : nullptr,
-                scan_poses_or_null ? (float *)c->tr_poses.p : nullptr,
-                states_trace_or_null ? (double *)c->tr_states.p : nullptr};
-    hipLaunchKernelGGL(drive_start_kernel, dim3((R + 63) / 64), dim3(64), 0, st, dp, b);
-    HIPCHK(hipGetLastError());
-    // the consumer reads the ranges right after the scan: plain stores (the handle's setting comes back below, as does
-    // its noise offset, which walks the global ray id t R num_rays + r num_rays of every tick)
-    const uint64_t base_off = h->ray_offset;
-    const int nt_store = h->nt_store;
-    h->nt_store = 0;
-    const drive_tick_fn tick = drive_tick_table[(num_rays + 63) / 64 - 1];
-    for (int t = 0; t < n_ticks && rc == RL_OK; ++t) {
-        h->ray_offset = base_off + (uint64_t)t * n_rays;
-        // (a race reads every car's outline from its f64 state after this tick's step: all cars step, then all scan)
-        rc = group > 0 ? launch_race(h, (const float *)c->poses.p, (const double *)c->states.p, 11, R / group, group, op,
-                                     fov, num_rays, (float *)c->ranges.p, nullptr, nullptr, st)
-                       : launch_fan(h, (const float *)c->poses.p, R, fov, num_rays, (float *)c->ranges.p, nullptr,
-                                    nullptr, nullptr, st);
-        if (rc == RL_OK) {
-            tick<<<dim3((R + DRIVE_CARS - 1) / DRIVE_CARS), dim3(64 * DRIVE_CARS), 0, st>>>(dp, b, t);
-            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "drive_tick_kernel launch failed");
-        }
-    }
-    h->ray_offset = base_off;
-    h->nt_store = nt_store;
-    if (rc) {
-        (void)hipStreamSynchronize(st);           // nothing of this call is left in flight on the handles' buffers
-        return rc;
-    }
-    HIPCHK(hipMemcpyAsync(first_crashed, c->first.p, (size_t)R * 4, hipMemcpyDeviceToHost, st));
-    if (states_out_or_null) HIPCHK(hipMemcpyAsync(states_out_or_null, c->states.p, (size_t)R * 88, hipMemcpyDeviceToHost, st));
-    if (velocities_or_null) HIPCHK(hipMemcpyAsync(velocities_or_null, c->vel.p, rows * 8, hipMemcpyDeviceToHost, st));
-    if (steers_or_null) HIPCHK(hipMemcpyAsync(steers_or_null, c->tr_steers.p, rows * 4, hipMemcpyDeviceToHost, st));
-    if (scan_poses_or_null) HIPCHK(hipMemcpyAsync(scan_poses_or_null, c->tr_poses.p, rows * 12, hipMemcpyDeviceToHost, st));
-    if (states_trace_or_null)
-        HIPCHK(hipMemcpyAsync(states_trace_or_null, c->tr_states.p, rows * 88, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return RL_OK;
-}
-
-extern "C" int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in,
-                                      const double *speeds, const float *steer0_or_null, int R, int n_ticks, double dt,
-                                      double scan_dist_to_base, float fov, int num_rays, const double *edge,
-                                      double crash_thresh, int *first_crashed, double *states_out_or_null,
-                                      double *velocities_or_null, float *steers_or_null, float *scan_poses_or_null,
-                                      double *states_trace_or_null)
-{
-    if (!c || !h || !g || (R > 0 && (!states_in || !speeds || !edge || !first_crashed)))
-        return fail(RL_ERR_INVALID, "rl_car_drive_followgap: null pointer");
-    int rc = drive_args(c, h, g, R, n_ticks, fov, num_rays);
-    if (rc || R == 0) return rc;
-    return drive_followgap_loop(c, h, g, states_in, speeds, steer0_or_null, R, 0, n_ticks, dt, scan_dist_to_base, fov,
-                                num_rays, edge, crash_thresh, first_crashed, states_out_or_null, velocities_or_null,
-                                steers_or_null, scan_poses_or_null, states_trace_or_null);
 }
 
 // ---------------------------------------------------------------- batched races (race_kernels.h)
@@ -613,25 +486,6 @@ extern "C" int rl_car_outline_cells(rl_car *c, rl_map *m, const double *cars_p3,
     return RL_OK;
 }
 
-extern "C" int rl_car_race_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in,
-                                     const double *speeds, const float *steer0_or_null, int n_races, int group,
-                                     int n_ticks, double dt, double scan_dist_to_base, float fov, int num_rays,
-                                     const double *edge, double crash_thresh, int *first_crashed,
-                                     double *states_out_or_null, double *velocities_or_null, float *steers_or_null,
-                                     float *scan_poses_or_null, double *states_trace_or_null)
-{
-    if (!c || !h || !g || (n_races > 0 && (!states_in || !speeds || !edge || !first_crashed)))
-        return fail(RL_ERR_INVALID, "rl_car_race_followgap: null pointer");
-    if (n_races < 0) return fail(RL_ERR_INVALID, "n_races must be >= 0 (got %d)", n_races);
-    int rc = race_args(h, n_races, group, num_rays);
-    if (rc) return rc;
-    const int R = n_races * group;          // (< 2^31 / num_rays: race_args)
-    if ((rc = drive_args(c, h, g, R, n_ticks, fov, num_rays, "rl_car_race_followgap")) || R == 0) return rc;
-    return drive_followgap_loop(c, h, g, states_in, speeds, steer0_or_null, R, group, n_ticks, dt, scan_dist_to_base,
-                                fov, num_rays, edge, crash_thresh, first_crashed, states_out_or_null, velocities_or_null,
-                                steers_or_null, scan_poses_or_null, states_trace_or_null);
-}
-
 // ---------------------------------------------------------------- the steering policy network (policy_kernels.h)
 struct rl_policy {
     int device = 0;
@@ -766,45 +620,65 @@ extern "C" int rl_policy_eval_device(rl_policy *p, const float *d_scans, int n_s
     return policy_launch(p, d_scans, n_scans, size, d_steers, (hipStream_t)hip_stream);
 }
 
-// ---------------------------------------------------------------- closed-loop policy roll-outs
-// policy_tick_kernel<ROWS>, ROWS = 1 ... FG_ROWS (the crash ballot holds ROWS beams per lane)
-typedef void (*policy_tick_fn)(DriveParams, DriveBufs, const float *, double, int);
-template <int... R>
-static constexpr std::array<policy_tick_fn, sizeof...(R)> policy_tick_make(std::integer_sequence<int, R...>)
-{
-    return {{policy_tick_kernel<R + 1>...}};
-}
-static const std::array<policy_tick_fn, FG_ROWS> policy_tick_table =
-    policy_tick_make(std::make_integer_sequence<int, FG_ROWS>());
+// ---------------------------------------------------------------- closed-loop roll-outs (drive_kernels.h)
+typedef void (*drive_tick_fn)(DriveParams, DriveBufs, int);
+static const std::array<drive_tick_fn, FG_ROWS> fg_tick_table =
+    rows_table<drive_tick_fn>([](auto rows) { return drive_tick_kernel<rows, FollowGapSteer>; });
+static const std::array<drive_tick_fn, FG_ROWS> policy_tick_table =
+    rows_table<drive_tick_fn>([](auto rows) { return drive_tick_kernel<rows, PolicySteer>; });
 
-extern "C" int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const double *states_in,
-                                   const double *speeds, const float *steer0_or_null, int R, int n_ticks, double dt,
-                                   double scan_dist_to_base, float fov, int num_rays, const double *edge,
-                                   double crash_thresh, double steer_clip, int *first_crashed,
-                                   double *states_out_or_null, double *velocities_or_null, float *steers_or_null,
-                                   float *scan_poses_or_null, double *states_trace_or_null)
+// the options of h that a closed loop overrides, restored on every exit: its consumer kernels read the ranges right after
+// the scan (plain stores), and it walks the noise offset from the value saved here
+struct HandleOverride {
+    rl_method *h;
+    const uint64_t ray_offset;
+    const int nt_store;
+    explicit HandleOverride(rl_method *h_) : h(h_), ray_offset(h_->ray_offset), nt_store(h_->nt_store) { h->nt_store = 0; }
+    ~HandleOverride()
+    {
+        h->ray_offset = ray_offset;
+        h->nt_store = nt_store;
+    }
+    HandleOverride(const HandleOverride &) = delete;
+    HandleOverride &operator=(const HandleOverride &) = delete;
+};
+
+// the checks every closed loop makes; the steering source is exactly one of g and p
+static int drive_args(const char *name, rl_car *c, rl_method *h, const rl_followgap *g, const rl_policy *p, int R,
+                      int n_ticks, int num_rays)
 {
-    if (!c || !h || !p || (R > 0 && (!states_in || !speeds || !edge || !first_crashed)))
-        return fail(RL_ERR_INVALID, "rl_car_drive_policy: null pointer");
     if (!c->reps.empty() || !h->reps.empty())
-        return fail(RL_ERR_INVALID, "rl_car_drive_policy is single-device only: pass ordinary (not multi-device) handles");
-    if (c->device != h->map->device || p->device != c->device)
-        return fail(RL_ERR_INVALID, "car (device %d), range method (device %d) and policy (device %d) must share one device",
-                    c->device, h->map->device, p->device);
+        return fail(RL_ERR_INVALID, "%s is single-device only: pass ordinary (not multi-device) handles", name);
+    const int src_device = g ? g->device : p->device;
+    if (c->device != h->map->device || src_device != c->device)
+        return fail(RL_ERR_INVALID, "car (device %d), range method (device %d) and %s (device %d) must share one device",
+                    c->device, h->map->device, g ? "FollowGap" : "policy", src_device);
     if (R < 0 || n_ticks <= 0) return fail(RL_ERR_INVALID, "n_rollouts >= 0 and n_ticks > 0 required (got %d, %d)", R, n_ticks);
     if (num_rays < 10 || num_rays > 64 * FG_ROWS)
         return fail(RL_ERR_INVALID, "num_rays must lie in [10, %d] (got %d)", 64 * FG_ROWS, num_rays);
     if ((long)R * num_rays >= (1L << 31)) return fail(RL_ERR_INVALID, "n_rollouts * num_rays must stay below 2^31");
-    int rc = policy_args(p, R, num_rays);
-    if (rc || (rc = check_fan_args(h, R, fov, num_rays)) || R == 0) return rc;
-    std::scoped_lock lk(c->mu, h->mu, p->mu);
+    return RL_OK;
+}
+
+// R cars for n_ticks ticks, steered by FollowGap (g) or the policy network (p, steer_clip); group 0: every car scans alone
+// with h's planner, group >= 1: the cars scan in races of `group` (race_fan_kernel).  The caller has checked the arguments.
+static int drive_loop(rl_car *c, rl_method *h, rl_followgap *g, rl_policy *p, double steer_clip, const double *states_in,
+                      const double *speeds, const float *steer0_or_null, int R, int group, int n_ticks, double dt,
+                      double scan_dist_to_base, float fov, int num_rays, const double *edge, double crash_thresh,
+                      int *first_crashed, double *states_out_or_null, double *velocities_or_null, float *steers_or_null,
+                      float *scan_poses_or_null, double *states_trace_or_null)
+{
+    int rc = RL_OK;
+    OutlineParams op{};
+    if (group > 0 && (rc = race_outline(h->map, c->P.LENGTH, c->P.WIDTH, op))) return rc;
+    std::scoped_lock lk(c->mu, h->mu, g ? g->mu : p->mu);
     std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
     HIPCHK(hipSetDevice(c->device));
     const size_t rows = (size_t)R * n_ticks, n_rays = (size_t)R * num_rays;
     if ((rc = c->states.ensure((size_t)R * 11 * 8)) || (rc = c->speeds.ensure((size_t)R * 8)) ||
         (rc = c->steer0.ensure((size_t)R * 4)) || (rc = c->first.ensure((size_t)R * 4)) ||
         (rc = c->poses.ensure((size_t)R * 12)) || (rc = c->ranges.ensure(n_rays * 4)) ||
-        (rc = c->edge.ensure((size_t)num_rays * 8)) || (rc = c->mlp.ensure((size_t)R * 4)) ||
+        (rc = c->edge.ensure((size_t)num_rays * 8)) || (p && (rc = c->mlp.ensure((size_t)R * 4))) ||
         (velocities_or_null && (rc = c->vel.ensure(rows * 8))) || (steers_or_null && (rc = c->tr_steers.ensure(rows * 4))) ||
         (scan_poses_or_null && (rc = c->tr_poses.ensure(rows * 12))) ||
         (states_trace_or_null && (rc = c->tr_states.ensure(rows * 88))))
@@ -815,6 +689,7 @@ extern "C" int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const 
     if (steer0_or_null) HIPCHK(hipMemcpyAsync(c->steer0.p, steer0_or_null, (size_t)R * 4, hipMemcpyHostToDevice, st));
     else HIPCHK(hipMemsetAsync(c->steer0.p, 0, (size_t)R * 4, st));
     HIPCHK(hipMemcpyAsync(c->edge.p, edge, (size_t)num_rays * 8, hipMemcpyHostToDevice, st));
+    // trace rows a car never reaches (after its crash tick; the steer of the crash tick) read NaN: all-ones bytes
     if (velocities_or_null) HIPCHK(hipMemsetAsync(c->vel.p, 0xff, rows * 8, st));
     if (steers_or_null) HIPCHK(hipMemsetAsync(c->tr_steers.p, 0xff, rows * 4, st));
     if (scan_poses_or_null) HIPCHK(hipMemsetAsync(c->tr_poses.p, 0xff, rows * 12, st));
@@ -822,38 +697,41 @@ extern "C" int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const 
 
     DriveParams dp{};
     dp.P = c->P;
-    dp.fg.size = num_rays;                        // (the crash ballot's beam count; FollowGap is not run)
+    if (g) dp.fg = g->P;
+    dp.fg.size = num_rays;                        // (for the policy only the crash ballot's beam count)
     dp.dt = dt;
     dp.scan_dist_to_base = scan_dist_to_base;
     dp.crash_thresh = crash_thresh;
     dp.n_cars = R;
     dp.n_ticks = n_ticks;
+    dp.steer_clip = steer_clip;
     DriveBufs b{(double *)c->states.p, (const double *)c->speeds.p, (const float *)c->steer0.p, (const double *)c->edge.p,
                 (int *)c->first.p, (float *)c->poses.p, (const float *)c->ranges.p,
                 velocities_or_null ? (double *)c->vel.p : nullptr, steers_or_null ? (float *)c->tr_steers.p : nullptr,
                 scan_poses_or_null ? (float *)c->tr_poses.p : nullptr,
-                states_trace_or_null ? (double *)c->tr_states.p : nullptr};
+                states_trace_or_null ? (double *)c->tr_states.p : nullptr, p ? (const float *)c->mlp.p : nullptr};
     hipLaunchKernelGGL(drive_start_kernel, dim3((R + 63) / 64), dim3(64), 0, st, dp, b);
     HIPCHK(hipGetLastError());
-    // as rl_car_drive_followgap: plain stores for the ranges, the noise offset walks t R num_rays
-    const uint64_t base_off = h->ray_offset;
-    const int nt_store = h->nt_store;
-    h->nt_store = 0;
-    const policy_tick_fn tick = policy_tick_table[(num_rays + 63) / 64 - 1];
-    for (int t = 0; t < n_ticks && rc == RL_OK; ++t) {
-        h->ray_offset = base_off + (uint64_t)t * n_rays;
-        rc = launch_fan(h, (const float *)c->poses.p, R, fov, num_rays, (float *)c->ranges.p, nullptr, nullptr, nullptr, st);
-        if (rc == RL_OK) rc = policy_launch(p, (const float *)c->ranges.p, R, num_rays, (float *)c->mlp.p, st);
-        if (rc == RL_OK) {
-            tick<<<dim3((R + DRIVE_CARS - 1) / DRIVE_CARS), dim3(64 * DRIVE_CARS), 0, st>>>(dp, b, (const float *)c->mlp.p,
-                                                                                          steer_clip, t);
-            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "policy_tick_kernel launch failed");
+    {
+        // the noise offset walks the global ray id t R num_rays + r num_rays of every tick
+        const HandleOverride ov(h);
+        const drive_tick_fn tick = (g ? fg_tick_table : policy_tick_table)[(num_rays + 63) / 64 - 1];
+        for (int t = 0; t < n_ticks && rc == RL_OK; ++t) {
+            h->ray_offset = ov.ray_offset + (uint64_t)t * n_rays;
+            // (a race reads every car's outline from its f64 state after this tick's step: all cars step, then all scan)
+            rc = group > 0 ? launch_race(h, (const float *)c->poses.p, (const double *)c->states.p, 11, R / group, group,
+                                         op, fov, num_rays, (float *)c->ranges.p, nullptr, nullptr, st)
+                           : launch_fan(h, (const float *)c->poses.p, R, fov, num_rays, (float *)c->ranges.p, nullptr,
+                                        nullptr, nullptr, st);
+            if (rc == RL_OK && p) rc = policy_launch(p, (const float *)c->ranges.p, R, num_rays, (float *)c->mlp.p, st);
+            if (rc == RL_OK) {
+                tick<<<dim3((R + DRIVE_CARS - 1) / DRIVE_CARS), dim3(64 * DRIVE_CARS), 0, st>>>(dp, b, t);
+                if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "drive_tick_kernel launch failed");
+            }
         }
     }
-    h->ray_offset = base_off;
-    h->nt_store = nt_store;
     if (rc) {
-        (void)hipStreamSynchronize(st);
+        (void)hipStreamSynchronize(st);           // nothing of this call is left in flight on the handles' buffers
         return rc;
     }
     HIPCHK(hipMemcpyAsync(first_crashed, c->first.p, (size_t)R * 4, hipMemcpyDeviceToHost, st));
@@ -865,6 +743,63 @@ extern "C" int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const 
         HIPCHK(hipMemcpyAsync(states_trace_or_null, c->tr_states.p, rows * 88, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return RL_OK;
+}
+
+extern "C" int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in,
+                                      const double *speeds, const float *steer0_or_null, int R, int n_ticks, double dt,
+                                      double scan_dist_to_base, float fov, int num_rays, const double *edge,
+                                      double crash_thresh, int *first_crashed, double *states_out_or_null,
+                                      double *velocities_or_null, float *steers_or_null, float *scan_poses_or_null,
+                                      double *states_trace_or_null)
+{
+    if (!c || !h || !g || (R > 0 && (!states_in || !speeds || !edge || !first_crashed)))
+        return fail(RL_ERR_INVALID, "rl_car_drive_followgap: null pointer");
+    int rc;
+    if ((rc = drive_args("rl_car_drive_followgap", c, h, g, nullptr, R, n_ticks, num_rays)) ||
+        (rc = check_fan_args(h, R, fov, num_rays)) || R == 0)
+        return rc;
+    return drive_loop(c, h, g, nullptr, 0.0, states_in, speeds, steer0_or_null, R, 0, n_ticks, dt, scan_dist_to_base,
+                      fov, num_rays, edge, crash_thresh, first_crashed, states_out_or_null, velocities_or_null,
+                      steers_or_null, scan_poses_or_null, states_trace_or_null);
+}
+
+extern "C" int rl_car_race_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in,
+                                     const double *speeds, const float *steer0_or_null, int n_races, int group,
+                                     int n_ticks, double dt, double scan_dist_to_base, float fov, int num_rays,
+                                     const double *edge, double crash_thresh, int *first_crashed,
+                                     double *states_out_or_null, double *velocities_or_null, float *steers_or_null,
+                                     float *scan_poses_or_null, double *states_trace_or_null)
+{
+    if (!c || !h || !g || (n_races > 0 && (!states_in || !speeds || !edge || !first_crashed)))
+        return fail(RL_ERR_INVALID, "rl_car_race_followgap: null pointer");
+    if (n_races < 0) return fail(RL_ERR_INVALID, "n_races must be >= 0 (got %d)", n_races);
+    int rc = race_args(h, n_races, group, num_rays);
+    if (rc) return rc;
+    const int R = n_races * group;          // (< 2^31 / num_rays: race_args)
+    if ((rc = drive_args("rl_car_race_followgap", c, h, g, nullptr, R, n_ticks, num_rays)) ||
+        (rc = check_fan_args(h, R, fov, num_rays)) || R == 0)
+        return rc;
+    return drive_loop(c, h, g, nullptr, 0.0, states_in, speeds, steer0_or_null, R, group, n_ticks, dt, scan_dist_to_base,
+                      fov, num_rays, edge, crash_thresh, first_crashed, states_out_or_null, velocities_or_null,
+                      steers_or_null, scan_poses_or_null, states_trace_or_null);
+}
+
+extern "C" int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const double *states_in,
+                                   const double *speeds, const float *steer0_or_null, int R, int n_ticks, double dt,
+                                   double scan_dist_to_base, float fov, int num_rays, const double *edge,
+                                   double crash_thresh, double steer_clip, int *first_crashed,
+                                   double *states_out_or_null, double *velocities_or_null, float *steers_or_null,
+                                   float *scan_poses_or_null, double *states_trace_or_null)
+{
+    if (!c || !h || !p || (R > 0 && (!states_in || !speeds || !edge || !first_crashed)))
+        return fail(RL_ERR_INVALID, "rl_car_drive_policy: null pointer");
+    int rc;
+    if ((rc = drive_args("rl_car_drive_policy", c, h, nullptr, p, R, n_ticks, num_rays)) ||
+        (rc = policy_args(p, R, num_rays)) || (rc = check_fan_args(h, R, fov, num_rays)) || R == 0)
+        return rc;
+    return drive_loop(c, h, nullptr, p, steer_clip, states_in, speeds, steer0_or_null, R, 0, n_ticks, dt,
+                      scan_dist_to_base, fov, num_rays, edge, crash_thresh, first_crashed, states_out_or_null,
+                      velocities_or_null, steers_or_null, scan_poses_or_null, states_trace_or_null);
 }
 
 // ---------------------------------------------------------------- diagnostics: HBM stream probe
@@ -1116,14 +1051,9 @@ extern "C" int rl_car_is_crashed(const float *ranges, int num_rays, int n_scans,
 
 
 // ---------------------------------------------------------------- the MCTS planner (mcts_kernels.h)
-// mcts_act_kernel<ROWS>, ROWS = 1 ... FG_ROWS
 typedef void (*mcts_act_fn)(MctsParams, MctsBufs, int);
-template <int... R>
-static constexpr std::array<mcts_act_fn, sizeof...(R)> mcts_act_make(std::integer_sequence<int, R...>)
-{
-    return {{mcts_act_kernel<R + 1>...}};
-}
-static const std::array<mcts_act_fn, FG_ROWS> mcts_act_table = mcts_act_make(std::make_integer_sequence<int, FG_ROWS>());
+static const std::array<mcts_act_fn, FG_ROWS> mcts_act_table =
+    rows_table<mcts_act_fn>([](auto rows) { return mcts_act_kernel<rows>; });
 
 struct rl_mcts {
     rl_car *c = nullptr;
@@ -1306,26 +1236,16 @@ static int mcts_act(rl_mcts *m, uint64_t off, int root, hipStream_t st)
     return RL_OK;
 }
 
-// the handles every launching call locks, in one order; h's options that the planner changes come back afterwards
+// the handles every launching call locks, in one order; h's options that the planner changes come back afterwards,
+// before the locks are released (the act kernel reads the ranges right after the scan)
 struct MctsLock {
-    rl_mcts *m;
     std::unique_lock<std::mutex> lm, lc, lh, lx;
     std::shared_lock<std::shared_mutex> ml;
-    uint64_t off;
-    int nt;
-    explicit MctsLock(rl_mcts *m_)
-        : m(m_), lm(m_->mu), lc(m_->c->mu), lh(m_->h->mu), ml(m_->h->map->tables_mu)
+    HandleOverride ov;
+    explicit MctsLock(rl_mcts *m) : lm(m->mu), lc(m->c->mu), lh(m->h->mu), ml(m->h->map->tables_mu), ov(m->h)
     {
         if (m->g) lx = std::unique_lock<std::mutex>(m->g->mu);
         if (m->p) lx = std::unique_lock<std::mutex>(m->p->mu);
-        off = m->h->ray_offset;
-        nt = m->h->nt_store;
-        m->h->nt_store = 0;                 // the act kernel reads the ranges right after the scan: plain stores
-    }
-    ~MctsLock()
-    {
-        m->h->ray_offset = off;
-        m->h->nt_store = nt;
     }
 };
 
@@ -1349,7 +1269,7 @@ extern "C" int rl_mcts_reset(rl_mcts *m, const double *root_states, const double
     hipLaunchKernelGGL(mcts_start_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, mcts_bufs(m),
                        (const double *)d_states, (const double *)d_actions);
     if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_start_kernel launch failed");
-    const uint64_t base = lk.off;
+    const uint64_t base = lk.ov.ray_offset;
     if (!rc) rc = mcts_act(m, base, 1, st);
     const hipError_t e = hipStreamSynchronize(st);            // (the host's root arrays are the caller's)
     if (!rc && e != hipSuccess) rc = fail(RL_ERR_HIP, "rl_mcts_reset: %s", hipGetErrorString(e));

@@ -103,6 +103,14 @@ __device__ inline void car_step(const CarParams &P, CarState &cs, double input_s
     cs.steer_angle = clampd(cs.steer_angle, -P.MAX_STEER_ANG, P.MAX_STEER_ANG);
 }
 
+// Car::getScanPose (racecar.cpp:378-387) in f64, cast to the f32 lidar pose (x, y, theta) as ScanSimulator2D.scan does
+__device__ inline void car_scan_pose(const CarState &cs, double scan_dist_to_base, float *out)
+{
+    out[0] = (float)(cs.x + scan_dist_to_base * cos(cs.theta));
+    out[1] = (float)(cs.y + scan_dist_to_base * sin(cs.theta));
+    out[2] = (float)cs.theta;
+}
+
 // One lane per roll-out.  states: 11 doubles per roll-out (getState layout), updated in place when
 // states_out != nullptr.  actions: (speed, steer) pairs, one per `action_every` steps
 // (scripts/mcts.py:216-222 draws a new pair every 10th step).  poses_out: float32 (x, y, theta) per

@@ -23,12 +23,12 @@ BOUNDS = [
     ("scan::cddt_fan_bins_kernel", {"vgpr": 64, "sgpr": 80, "occupancy": 8, "scratch": 0}),
     ("scan::bl_fan_stream_kernel<false, 1024>", {"vgpr": 56, "sgpr": 96, "occupancy": 8, "scratch": 0}),
     ("scan::rm_leftover_kernel<", {"vgpr": 48, "occupancy": 8, "scratch": 0}),
-    # closed-loop FollowGap roll-outs: scan, crash compare, FollowGap and the f64 car step in one wave per car, no spills
+    # closed-loop roll-outs, both steering sources: scan, crash compare, FollowGap or the network's answer and the f64
+    # car step in one wave per car, no spills
     ("scan::drive_tick_kernel<", {"scratch": 0}),
     ("scan::drive_start_kernel", {"scratch": 0}),
-    # the policy network: the micro-tile accumulators stay in registers; its drive tick as drive_tick_kernel's
+    # the policy network: the micro-tile accumulators stay in registers
     ("scan::policy_mlp_kernel", {"scratch": 0}),
-    ("scan::policy_tick_kernel<", {"scratch": 0}),
     # the MCTS planner: the descent, the act wave, the backup's pairwise sum and the walks keep nothing in scratch
     ("scan::mcts_start_kernel", {"scratch": 0}),
     ("scan::mcts_select_kernel", {"scratch": 0}),

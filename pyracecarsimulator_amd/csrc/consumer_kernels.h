@@ -194,7 +194,8 @@ __device__ __forceinline__ void fg_wave_sync()
 
 // The four passes over one scan already in registers: raw[u] = beam 64 u + lane (0 past the end), `bits` = 2 ROWS + 4 words
 // of LDS owned by this wave.  Every lane returns the steering angle.  Shared by followgap_bits_kernel and
-// drive_tick_kernel (drive_kernels.h); wave-local, so a workgroup may hold several scans.
+// drive_tick_kernel's FollowGap source (drive_kernels.h) and mcts_act_kernel (mcts_kernels.h); wave-local, so a
+// workgroup may hold several scans.
 // ROWS = ceil(size / 64): the rows below ROWS - 2 hold 64 beams that all exist and are all clamped (size - 10 > 64 (ROWS - 2))
 template <int ROWS>
 __device__ __forceinline__ float followgap_bits_eval(const float (&raw)[ROWS], const FollowGapParams &p, uint32_t *bits)

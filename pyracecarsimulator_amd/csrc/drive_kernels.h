@@ -1,11 +1,14 @@
-// drive_kernels.h — closed-loop Follow-the-Gap roll-outs (rl_car_drive_followgap, include/scanlib.h): the reference's
-// simulator tick (scripts/ros_interface.py:119-148: updatePose, runScan, checkCollision >= 0) driven by the
-// FollowGap answer to every scan (scripts/two_player/simple_driver.py:31,48-53), for many cars at once with
-// nothing crossing PCIe between ticks.  Per tick the host enqueues two things on one stream:
-//   1. the scan of every car's lidar pose through the ordinary fan planner (launch_fan, abi_fan.hip);
-//   2. drive_tick_kernel: one wave per car — the scan into registers, Car::isCrashed's f64 compare
-//      (racecar.cpp:305-328) as a ballot, FollowGap's four passes (followgap_bits_eval, consumer_kernels.h) —,
-//      then one lane per car: the car step of the NEXT tick with the new steering angle and that tick's lidar pose.
+// drive_kernels.h — closed-loop roll-outs (rl_car_drive_followgap, rl_car_race_followgap, rl_car_drive_policy;
+// include/scanlib.h): the reference's simulator tick (scripts/ros_interface.py:119-148: updatePose, runScan,
+// checkCollision >= 0) driven by a steering source's answer to every scan — FollowGap (scripts/two_player/
+// simple_driver.py:31,48-53) or the policy network (scripts/policy_driver.py) — for many cars at once with nothing
+// crossing PCIe between ticks.  Per tick the host enqueues on one stream:
+//   1. the scan of every car's lidar pose: the ordinary fan planner (launch_fan, abi_fan.hip) or, in races,
+//      race_fan_kernel (race_kernels.h); for the policy, then policy_mlp_kernel over every scan (policy_kernels.h);
+//   2. drive_tick_kernel<ROWS, Steer>: one wave per car — the scan into registers, Car::isCrashed's f64 compare
+//      (racecar.cpp:305-328) as a ballot, the source's answer (FollowGapSteer: followgap_bits_eval's four passes,
+//      consumer_kernels.h; PolicySteer: the network's output) —, then one lane per car: the car step of the NEXT
+//      tick with the new steering angle and that tick's lidar pose.
 // drive_start_kernel (one lane per car) is the prologue: tick 0's step with the initial steer.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,9 +21,10 @@ namespace scan {
 
 struct DriveParams {
     CarParams P;
-    FollowGapParams fg;          // fg.size = num_rays
+    FollowGapParams fg;          // fg.size = num_rays (the policy source sets nothing else)
     double dt, scan_dist_to_base, crash_thresh;
     int n_cars, n_ticks;
+    double steer_clip;           // policy source: > 0 clamps the network's steer to +-steer_clip
 };
 
 struct DriveBufs {
@@ -35,6 +39,7 @@ struct DriveBufs {
     float *steers;
     float *scan_poses;           // [R, T, 3]
     double *states_trace;        // [R, T, 11]
+    const float *mlp;            // policy source: [R] the network's answers to this tick's scans
 };
 
 __device__ inline CarState drive_load_state(const double *s)
@@ -53,48 +58,47 @@ __device__ inline void drive_store_state(const CarState &cs, double *o)
     o[8] = cs.travel_dist; o[9] = cs.total_velo; o[10] = (double)cs.update_count;
 }
 
-// Car::control + updatePosition for tick t of car r, then Car::getScanPose (racecar.cpp:378-387) in f64 cast to f32 as
-// ScanSimulator2D.scan does, and the trace rows of tick t.  One lane.
+// Car::control + updatePosition for tick t of car r, then its lidar pose (car_scan_pose) and the trace rows of tick t.
+// One lane.
 __device__ inline void drive_step(const DriveParams &dp, const DriveBufs &b, int r, int t, double steer)
 {
     double *s = b.state + (size_t)r * 11;
     CarState cs = drive_load_state(s);
     car_step(dp.P, cs, b.speed[r], steer, dp.dt);
     drive_store_state(cs, s);
-    const float px = (float)(cs.x + dp.scan_dist_to_base * cos(cs.theta));
-    const float py = (float)(cs.y + dp.scan_dist_to_base * sin(cs.theta));
-    const float pt = (float)cs.theta;
-    b.pose[3 * r + 0] = px;
-    b.pose[3 * r + 1] = py;
-    b.pose[3 * r + 2] = pt;
+    float pose[3];
+    car_scan_pose(cs, dp.scan_dist_to_base, pose);
+    b.pose[3 * r + 0] = pose[0];
+    b.pose[3 * r + 1] = pose[1];
+    b.pose[3 * r + 2] = pose[2];
     const size_t row = (size_t)r * dp.n_ticks + t;
     if (b.vel) b.vel[row] = cs.velocity;
     if (b.scan_poses) {
-        b.scan_poses[3 * row + 0] = px;
-        b.scan_poses[3 * row + 1] = py;
-        b.scan_poses[3 * row + 2] = pt;
+        b.scan_poses[3 * row + 0] = pose[0];
+        b.scan_poses[3 * row + 1] = pose[1];
+        b.scan_poses[3 * row + 2] = pose[2];
     }
     if (b.states_trace) drive_store_state(cs, b.states_trace + 11 * row);
 }
 
-// Car::isCrashed on car r's scan of this tick, one wave: (double)range - edge[j] < CRASH_THRESH for any beam (NaN never
-// crashes), as a ballot (wave-uniform).  raw: the scan, ROWS beams per lane (zero past num_rays).
+// Car::isCrashed on one scan of `size` beams (lidar) against the outline table, one wave: (double)range - edge[j] <
+// crash_thresh for any beam (NaN never crashes), as a ballot (wave-uniform).  raw: the scan, ROWS beams per lane
+// (zero past size).
 template <int ROWS>
-__device__ inline bool drive_crashed(const DriveParams &dp, const DriveBufs &b, int r, int lane, float (&raw)[ROWS])
+__device__ inline bool drive_crashed(const float *lidar, const double *edge_tab, int size, double crash_thresh, int lane,
+                                     float (&raw)[ROWS])
 {
-    const int size = dp.fg.size;
-    const float *lidar = b.ranges + (size_t)r * size;
     double edge[ROWS];
 #pragma unroll
     for (int u = 0; u < ROWS; ++u) {
         const bool in = u < ROWS - 1 || 64 * u + lane < size;
         raw[u] = in ? lidar[64 * u + lane] : 0.0f;
-        edge[u] = in ? b.edge[64 * u + lane] : 0.0;
+        edge[u] = in ? edge_tab[64 * u + lane] : 0.0;
     }
     bool hit = false;
 #pragma unroll
     for (int u = 0; u < ROWS; ++u)
-        if (u < ROWS - 1 || 64 * u + lane < size) hit |= ((double)raw[u] - edge[u]) < dp.crash_thresh;
+        if (u < ROWS - 1 || 64 * u + lane < size) hit |= ((double)raw[u] - edge[u]) < crash_thresh;
     return __ballot(hit) != 0;
 }
 
@@ -107,75 +111,67 @@ __global__ __launch_bounds__(64) void drive_start_kernel(DriveParams dp, DriveBu
     drive_step(dp, b, r, 0, (double)b.steer0[r]);
 }
 
-// tick t after its scan: crash test, FollowGap, and the step of tick t + 1.  A workgroup holds DRIVE_CARS cars, one wave
-// each for the scan-wide work (ROWS = ceil(num_rays / 64)); the f64 steps of the workgroup's cars then run one lane per
-// car in wave 0.  (One step on lane 0 of every wave cost the full wave's f64 issue per car: at 4096 cars that was most
-// of the kernel's time.)  A frozen car (crashed at an earlier tick) was scanned at its last pose with the others; its
-// wave skips the work.
+// The steering sources of drive_tick_kernel.  answer(): car r's f32 answer to its scan of this tick (the steers trace),
+// in every lane of the car's wave; steer(): the f64 steer the car gets from it, in the lane of wave 0 that steps it.
+struct FollowGapSteer {
+    template <int ROWS>
+    __device__ static float answer(const DriveParams &dp, const DriveBufs &, int, const float (&raw)[ROWS], uint32_t *bits)
+    {
+        return followgap_bits_eval<ROWS>(raw, dp.fg, bits);
+    }
+    __device__ static double steer(const DriveParams &, float a) { return (double)a; }
+};
+
+// policy_mlp_kernel's output (every car's scan, frozen ones included).  steer_clip > 0: the car gets
+// clamp((double)a, -clip, clip) (scripts/policy_driver.py:33); otherwise (double)a, clamped later by Car::control
+// (scripts/mcts.py).
+struct PolicySteer {
+    template <int ROWS>
+    __device__ static float answer(const DriveParams &, const DriveBufs &b, int r, const float (&)[ROWS], uint32_t *)
+    {
+        return b.mlp[r];
+    }
+    __device__ static double steer(const DriveParams &dp, float a)
+    {
+        const double s = (double)a;
+        return dp.steer_clip > 0.0 ? fmin(fmax(s, -dp.steer_clip), dp.steer_clip) : s;
+    }
+};
+
+// tick t after its scan: crash test, the source's answer, and the step of tick t + 1.  A workgroup holds DRIVE_CARS
+// cars, one wave each for the scan-wide work (ROWS = ceil(num_rays / 64)); the f64 steps of the workgroup's cars then
+// run one lane per car in wave 0.  (One step on lane 0 of every wave cost the full wave's f64 issue per car: at 4096
+// cars that was most of the kernel's time.)  A frozen car (crashed at an earlier tick) was scanned at its last pose with
+// the others; its wave skips the work.
 constexpr int DRIVE_CARS = 8;
 
-template <int ROWS>
+template <int ROWS, class Steer>
 __global__ __launch_bounds__(64 * DRIVE_CARS) void drive_tick_kernel(DriveParams dp, DriveBufs b, int t)
 {
-    __shared__ uint32_t bits[DRIVE_CARS][2 * ROWS + 4];
-    __shared__ float steer_next[DRIVE_CARS];
+    __shared__ uint32_t bits[DRIVE_CARS][2 * ROWS + 4];   // (FollowGap's bit rows: PolicySteer never touches them)
+    __shared__ float answer_next[DRIVE_CARS];
     __shared__ int step_next[DRIVE_CARS];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x * DRIVE_CARS + w;
     bool go = false;
-    float angle = 0.0f;
+    float answer = 0.0f;
     if (r < dp.n_cars && b.first[r] < 0) {                // (wave-uniform)
         float raw[ROWS];
-        if (drive_crashed<ROWS>(dp, b, r, lane, raw)) {
+        if (drive_crashed<ROWS>(b.ranges + (size_t)r * dp.fg.size, b.edge, dp.fg.size, dp.crash_thresh, lane, raw)) {
             if (lane == 0) b.first[r] = t;                // frozen from here: its trace rows after t stay NaN
         } else {
-            angle = followgap_bits_eval<ROWS>(raw, dp.fg, bits[w]);
-            if (lane == 0 && b.steers) b.steers[(size_t)r * dp.n_ticks + t] = angle;
+            answer = Steer::template answer<ROWS>(dp, b, r, raw, bits[w]);
+            if (lane == 0 && b.steers) b.steers[(size_t)r * dp.n_ticks + t] = answer;
             go = t + 1 < dp.n_ticks;
         }
     }
     if (lane == 0) {
-        steer_next[w] = angle;
+        answer_next[w] = answer;
         step_next[w] = go;
     }
     __syncthreads();
     if (threadIdx.x < DRIVE_CARS && step_next[threadIdx.x])
-        drive_step(dp, b, blockIdx.x * DRIVE_CARS + threadIdx.x, t + 1, (double)steer_next[threadIdx.x]);
-}
-
-// closed-loop policy roll-outs (rl_car_drive_policy): tick t after its scan and policy_mlp_kernel's answer to it (mlp[R],
-// every car's scan, frozen ones included): the crash test and the step of tick t + 1, as drive_tick_kernel with the
-// network's steer in place of FollowGap's.  steer_clip > 0: the car gets clamp((double)steer, -clip, clip)
-// (scripts/policy_driver.py:33); otherwise (double)steer, clamped later by Car::control (scripts/mcts.py).
-template <int ROWS>
-__global__ __launch_bounds__(64 * DRIVE_CARS) void policy_tick_kernel(DriveParams dp, DriveBufs b, const float *mlp,
-                                                                      double steer_clip, int t)
-{
-    __shared__ double steer_next[DRIVE_CARS];
-    __shared__ int step_next[DRIVE_CARS];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = blockIdx.x * DRIVE_CARS + w;
-    bool go = false;
-    double steer = 0.0;
-    if (r < dp.n_cars && b.first[r] < 0) {                // (wave-uniform)
-        float raw[ROWS];
-        if (drive_crashed<ROWS>(dp, b, r, lane, raw)) {
-            if (lane == 0) b.first[r] = t;
-        } else {
-            const float a = mlp[r];
-            if (lane == 0 && b.steers) b.steers[(size_t)r * dp.n_ticks + t] = a;
-            steer = (double)a;
-            if (steer_clip > 0.0) steer = fmin(fmax(steer, -steer_clip), steer_clip);
-            go = t + 1 < dp.n_ticks;
-        }
-    }
-    if (lane == 0) {
-        steer_next[w] = steer;
-        step_next[w] = go;
-    }
-    __syncthreads();
-    if (threadIdx.x < DRIVE_CARS && step_next[threadIdx.x])
-        drive_step(dp, b, blockIdx.x * DRIVE_CARS + threadIdx.x, t + 1, steer_next[threadIdx.x]);
+        drive_step(dp, b, blockIdx.x * DRIVE_CARS + threadIdx.x, t + 1, Steer::steer(dp, answer_next[threadIdx.x]));
 }
 
 }  // namespace scan

@@ -3,8 +3,8 @@
 //   1. mcts_select_kernel (one lane per tree): the literal descent of MCTS.mctsIteration (:150-185) with its visit
 //      increments, the expansion action, the roll-out draws, the act step from the expanded node and the new child;
 //   2. the act scans (launch_fan over the K children's lidar poses), policy_mlp_kernel for the NN source;
-//   3. mcts_act_kernel<ROWS> (one wave per tree): drive_crashed's f64 crash ballot -> the terminal flag, and the
-//      child's expansion answer (followgap_bits_eval or the network's output);
+//   3. mcts_act_kernel<ROWS> (one wave per tree): drive_crashed's f64 crash ballot (drive_kernels.h) -> the terminal
+//      flag, and the child's expansion answer (followgap_bits_eval or the network's output);
 //   4. rollout_kernel + crash_groups_device over the K x L roll-out poses (MCTS.rollout, :202-245);
 //   5. mcts_backup_kernel (one lane per tree): the reward sum in NumPy's pairwise order, or crash_pen, and the
 //      repeated adds of Node.propagate at every recursion level.
@@ -115,14 +115,6 @@ __device__ inline double mcts_pairwise_sum(const double *a, int n)
     return 0.0 + mcts_pairwise<3>(a, n);      // depth 3: exact up to ~920 elements (MCTS_MAX_STEPS = 512)
 }
 
-// the f32 lidar pose of Car::getScanPose (racecar.cpp:378-387) in f64 cast to f32, drive_step's formula
-__device__ inline void mcts_scan_pose(const MctsParams &p, const CarState &cs, float *o)
-{
-    o[0] = (float)(cs.x + p.scan_dist_to_base * cos(cs.theta));
-    o[1] = (float)(cs.y + p.scan_dist_to_base * sin(cs.theta));
-    o[2] = (float)cs.theta;
-}
-
 // reset: node 0 of every tree is the caller's state and recent action (visits 1, never terminal); its lidar pose goes
 // to the act-scan buffer so that the root scan and answer come from the ordinary act launches
 __global__ __launch_bounds__(64) void mcts_start_kernel(MctsParams p, MctsBufs b, const double *__restrict__ states,
@@ -145,8 +137,8 @@ __global__ __launch_bounds__(64) void mcts_start_kernel(MctsParams p, MctsBufs b
     b.answer[n] = __builtin_nanf("");
     const CarState cs = drive_load_state(states + 11 * (size_t)k);
     drive_store_state(cs, b.state + 11 * n);
-    mcts_scan_pose(p, cs, b.pose + 3 * n);
-    mcts_scan_pose(p, cs, b.cpose + 3 * k);
+    car_scan_pose(cs, p.scan_dist_to_base, b.pose + 3 * n);
+    car_scan_pose(cs, p.scan_dist_to_base, b.cpose + 3 * k);
     b.n_nodes[k] = 1;
     b.child[k] = 0;
     b.exp_term[k] = 0;
@@ -220,8 +212,8 @@ __global__ __launch_bounds__(64) void mcts_select_kernel(MctsParams p, MctsBufs 
     car_step(p.P, cs, p.speed, a, p.dt);
     drive_store_state(cs, b.state + 11 * (t0 + c));
     drive_store_state(cs, b.cstate + 11 * (size_t)k);
-    mcts_scan_pose(p, cs, b.pose + 3 * (t0 + c));
-    mcts_scan_pose(p, cs, b.cpose + 3 * (size_t)k);
+    car_scan_pose(cs, p.scan_dist_to_base, b.pose + 3 * (t0 + c));
+    car_scan_pose(cs, p.scan_dist_to_base, b.cpose + 3 * (size_t)k);
     parent[c] = node;
     first_child[c] = -1;
     next_sibling[c] = -1;
@@ -255,14 +247,9 @@ __global__ __launch_bounds__(64 * MCTS_TREES) void mcts_act_kernel(MctsParams p,
     if (k >= p.K) return;                           // (wave-uniform; no block barrier below)
     const int c = b.child[k];
     if (c < 0) return;
-    DriveParams dp{};
-    dp.fg = p.fg;
-    dp.crash_thresh = p.crash_thresh;
-    DriveBufs db{};
-    db.ranges = b.ranges;
-    db.edge = b.edge;
     float raw[ROWS];
-    const bool crashed = drive_crashed<ROWS>(dp, db, k, lane, raw);
+    const bool crashed =
+        drive_crashed<ROWS>(b.ranges + (size_t)k * p.fg.size, b.edge, p.fg.size, p.crash_thresh, lane, raw);
     float ans = __builtin_nanf("");
     if (p.source == RL_MCTS_FG) ans = followgap_bits_eval<ROWS>(raw, p.fg, bits[w]);
     else if (p.source == RL_MCTS_NN) ans = b.mlp[k];

@@ -133,18 +133,8 @@ class CarBatch:
         final states (R, 11), velocities float64 (R, n_ticks), steers float32 (R, n_ticks)) and with
         ``trace=True`` also (lidar poses float32 (R, n_ticks, 3), states float64 (R, n_ticks, 11)).  Trace
         rows after a car's crash tick, and its steer at that tick, are NaN."""
-        R, n_ticks, states, speeds, st0, edge, first, out, vel, steers, poses, trace_st = self._drive_args(
-            states, n_ticks, speed, num_rays, edge, steer0, trace)
-        ptr = lambda a, t: a.ctypes.data_as(t) if a is not None else None
-        _lib.check(_lib.lib().rl_car_drive_followgap(
-            self._h, method._h, followgap._h, states.ctypes.data_as(f64p), speeds.ctypes.data_as(f64p),
-            ptr(st0, f32p), R, n_ticks, float(dt), float(scan_dist_to_base), float(fov), int(num_rays),
-            edge.ctypes.data_as(f64p), float(crash_thresh), first.ctypes.data_as(C.POINTER(C.c_int)),
-            out.ctypes.data_as(f64p), vel.ctypes.data_as(f64p), steers.ctypes.data_as(f32p), ptr(poses, f32p),
-            ptr(trace_st, f64p)))
-        if trace:
-            return first, out, vel, steers, poses, trace_st
-        return first, out, vel, steers
+        return self._drive(_lib.lib().rl_car_drive_followgap, method, followgap, None, (), states, n_ticks, speed, fov,
+                           num_rays, edge, crash_thresh, scan_dist_to_base, dt, steer0, trace)
 
     def outline_cells(self, omap, car_poses):
         """The canonical outline cells of each car (``rl_car_outline_cells``, include/scanlib.h) on ``omap`` (a
@@ -175,21 +165,10 @@ class CarBatch:
         spd = np.asarray(speed, dtype=np.float64)
         spd = float(spd) if spd.ndim == 0 else spd.reshape(-1)
         st0 = None if steer0 is None else np.asarray(steer0).reshape(-1)
-        R, n_ticks, states_f, speeds, st0, edge, first, out, vel, steers, poses, trace_st = self._drive_args(
-            st.reshape(-1, 11), n_ticks, spd, num_rays, edge, st0, trace)
-        ptr = lambda a, t: a.ctypes.data_as(t) if a is not None else None
-        _lib.check(_lib.lib().rl_car_race_followgap(
-            self._h, method._h, followgap._h, states_f.ctypes.data_as(f64p), speeds.ctypes.data_as(f64p),
-            ptr(st0, f32p), n_races, group, n_ticks, float(dt), float(scan_dist_to_base), float(fov), int(num_rays),
-            edge.ctypes.data_as(f64p), float(crash_thresh), first.ctypes.data_as(C.POINTER(C.c_int)),
-            out.ctypes.data_as(f64p), vel.ctypes.data_as(f64p), steers.ctypes.data_as(f32p), ptr(poses, f32p),
-            ptr(trace_st, f64p)))
-        T = vel.shape[1]
-        res = (first.reshape(n_races, group), out.reshape(n_races, group, 11), vel.reshape(n_races, group, T),
-               steers.reshape(n_races, group, T))
-        if trace:
-            res += (poses.reshape(n_races, group, T, 3), trace_st.reshape(n_races, group, T, 11))
-        return res
+        res = self._drive(_lib.lib().rl_car_race_followgap, method, followgap, (n_races, group), (), st.reshape(-1, 11),
+                          n_ticks, spd, fov, num_rays, edge, crash_thresh, scan_dist_to_base, dt, st0, trace)
+        # every array's leading R P becomes (R, P)
+        return tuple(a.reshape((n_races, group) + a.shape[1:]) for a in res)
 
     def drive_policy(self, method, policy, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
                      scan_dist_to_base=0.275, dt=0.01, steer0=None, steer_clip=None, trace=False):
@@ -198,21 +177,11 @@ class CarBatch:
         ``steer_clip`` None: the car gets the raw output (as scripts/mcts.py passes it to drive()); a value: the
         output clamped to +-steer_clip (policy_driver.py uses 0.4189).  The steers returned are the raw network
         outputs.  Arguments and results as ``drive_followgap``."""
-        R, n_ticks, states, speeds, st0, edge, first, out, vel, steers, poses, trace_st = self._drive_args(
-            states, n_ticks, speed, num_rays, edge, steer0, trace)
         clip = 0.0 if steer_clip is None else float(steer_clip)
         if steer_clip is not None and not clip > 0:
             raise ValueError("steer_clip must be None or > 0")
-        ptr = lambda x, t: x.ctypes.data_as(t) if x is not None else None
-        _lib.check(_lib.lib().rl_car_drive_policy(
-            self._h, method._h, policy._h, states.ctypes.data_as(f64p), speeds.ctypes.data_as(f64p),
-            ptr(st0, f32p), R, n_ticks, float(dt), float(scan_dist_to_base), float(fov), int(num_rays),
-            edge.ctypes.data_as(f64p), float(crash_thresh), clip, first.ctypes.data_as(C.POINTER(C.c_int)),
-            out.ctypes.data_as(f64p), vel.ctypes.data_as(f64p), steers.ctypes.data_as(f32p), ptr(poses, f32p),
-            ptr(trace_st, f64p)))
-        if trace:
-            return first, out, vel, steers, poses, trace_st
-        return first, out, vel, steers
+        return self._drive(_lib.lib().rl_car_drive_policy, method, policy, None, (clip,), states, n_ticks, speed, fov,
+                           num_rays, edge, crash_thresh, scan_dist_to_base, dt, steer0, trace)
 
     def plan_mcts(self, method, followgap_or_policy, root_states, n_iterations, seeds, fov, num_rays, edge,
                   crash_thresh, root_actions=0.0, source=None, rollout_steps=200, action_every=10, speed=2.0,
@@ -246,6 +215,24 @@ class CarBatch:
         finally:
             pl.close()
         return res
+
+    def _drive(self, fn, method, source, counts, after_thresh, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
+               scan_dist_to_base, dt, steer0, trace):
+        """The one ctypes call of the closed loops: ``fn`` is rl_car_drive_followgap, rl_car_race_followgap or
+        rl_car_drive_policy, ``source`` the steering source's wrapper.  ``counts`` replaces (R,) as the car-count
+        arguments (races: (n_races, group)); ``after_thresh`` goes after crash_thresh (the policy's steer_clip)."""
+        R, n_ticks, states, speeds, st0, edge, first, out, vel, steers, poses, trace_st = self._drive_args(
+            states, n_ticks, speed, num_rays, edge, steer0, trace)
+        ptr = lambda a, t: a.ctypes.data_as(t) if a is not None else None
+        _lib.check(fn(
+            self._h, method._h, source._h, states.ctypes.data_as(f64p), speeds.ctypes.data_as(f64p), ptr(st0, f32p),
+            *(counts or (R,)), n_ticks, float(dt), float(scan_dist_to_base), float(fov), int(num_rays),
+            edge.ctypes.data_as(f64p), float(crash_thresh), *after_thresh, first.ctypes.data_as(C.POINTER(C.c_int)),
+            out.ctypes.data_as(f64p), vel.ctypes.data_as(f64p), steers.ctypes.data_as(f32p), ptr(poses, f32p),
+            ptr(trace_st, f64p)))
+        if trace:
+            return first, out, vel, steers, poses, trace_st
+        return first, out, vel, steers
 
     @staticmethod
     def _drive_args(states, n_ticks, speed, num_rays, edge, steer0, trace):

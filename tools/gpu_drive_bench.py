@@ -4,7 +4,8 @@ the public calls, and against the serial scan floor, in one process.
 
 Per map (cfg2's 2049^2 maze, colombia) and car count R (1, 64, 4096), T ticks (200) at simple_driver.py's
 VELOCITY (2 m/s), RMGPU, 1081 beams:
-  closed    CarBatch.drive_followgap: every tick one fan launch sequence + one drive_tick_kernel, no host sync
+  closed    CarBatch.drive_followgap: every tick one fan launch sequence + one drive_tick_kernel (FollowGap source),
+            no host sync
   composed  per tick: CarBatch.rollout(n_steps=1) of the live cars -> lidar poses in numpy -> calc_range_fan to the
             host -> Car::isCrashed on the host (numpy, vectorised) -> eval_many (the ranges go back to the GPU)
   floor     T serial calc_range_fan_device launches of the R start poses (the scan alone, device buffers)

@@ -3,7 +3,7 @@
 
 Per map (cfg2's 2049^2 maze, colombia) and car count R (1, 64, 4096), T ticks (200) at 2 m/s, RMGPU, 1081 beams:
   policy    CarBatch.drive_policy (steer_clip 0.4189): every tick one fan launch sequence, one policy_mlp_kernel and
-            one policy_tick_kernel, no host sync
+            one drive_tick_kernel (policy source), no host sync
   followgap CarBatch.drive_followgap on the same starts (DESIGN section 7a's loop)
   composed  per tick: rollout(n_steps=1) of the live cars -> lidar poses in numpy -> calc_range_fan to the host ->
             the crash test on the host -> Policy.predict_many (the ranges go back to the GPU)
