@@ -91,15 +91,21 @@ extern "C" void rl_car_destroy(rl_car *c)
     delete c;
 }
 
+static int check_rollout_args(int R, int n_steps, int every)
+{
+    if (R < 0 || n_steps <= 0 || every <= 0) return fail(RL_ERR_INVALID, "n_rollouts >= 0, n_steps > 0, action_every > 0 required");
+    return RL_OK;
+}
+
 static int car_rollout_device(rl_car *c, const double *states_in, const double *actions, int R,
                               int n_steps, int every, double dt, bool want_states, bool want_vel)
 {
-    if (R < 0 || n_steps <= 0 || every <= 0) return fail(RL_ERR_INVALID, "n_rollouts >= 0, n_steps > 0, action_every > 0 required");
+    int rc = check_rollout_args(R, n_steps, every);
+    if (rc) return rc;
     if ((long)R * n_steps > INT_MAX / 4) return fail(RL_ERR_INVALID, "too many roll-out poses");
     HIPCHK(hipSetDevice(c->device));
     if (R == 0) return RL_OK;
     const int n_act = (n_steps + every - 1) / every;
-    int rc;
     if ((rc = c->states.ensure((size_t)R * 11 * 8)) || (rc = c->actions.ensure((size_t)R * n_act * 16)) ||
         (rc = c->poses.ensure((size_t)R * n_steps * 12)) || (rc = c->states_out.ensure((size_t)R * 11 * 8)) ||
         (rc = c->vel.ensure((size_t)R * n_steps * 8)))
@@ -120,23 +126,18 @@ extern "C" int rl_car_rollout(rl_car *c, const double *states_in, const double *
 {
     if (!c || (R > 0 && (!states_in || !actions || !poses_out))) return fail(RL_ERR_INVALID, "rl_car_rollout: null pointer");
     if (!c->reps.empty()) {
-        // roll-outs are independent: contiguous blocks of them, one per device
-        if (R < 0 || n_steps <= 0 || every <= 0) return fail(RL_ERR_INVALID, "n_rollouts >= 0, n_steps > 0, action_every > 0 required");
+        // roll-outs are independent: contiguous blocks of them, one per device (a device per 64 roll-outs)
+        const int rc = check_rollout_args(R, n_steps, every);
+        if (rc) return rc;
         std::lock_guard<std::mutex> lk(c->mu);
         const int k = (int)std::max<long>(1, std::min<long>((long)c->reps.size(), (long)R / 64));
         const size_t n_act = (size_t)(n_steps + every - 1) / every;
-        std::vector<std::function<int()>> jobs;
-        for (int i = 0; i < k; ++i) {
-            long lo, hi;
-            block_of(R, i, k, lo, hi);
-            rl_car *r = c->reps[i];
-            jobs.push_back([=]() {
-                return rl_car_rollout(r, states_in + 11 * lo, actions + 2 * n_act * lo, (int)(hi - lo), n_steps, every, dt,
-                                      poses_out + (size_t)3 * n_steps * lo, states_out ? states_out + 11 * lo : nullptr,
-                                      vel_out ? vel_out + (size_t)n_steps * lo : nullptr);
-            });
-        }
-        return c->pool->run(jobs);
+        return run_blocks(*c->pool, R, k, 0, [=](const MultiBlock &b) {
+            const long lo = b.lo;
+            return rl_car_rollout(c->reps[b.replica], states_in + 11 * lo, actions + 2 * n_act * lo, (int)(b.hi - lo), n_steps, every,
+                                  dt, poses_out + (size_t)3 * n_steps * lo, states_out ? states_out + 11 * lo : nullptr,
+                                  vel_out ? vel_out + (size_t)n_steps * lo : nullptr);
+        });
     }
     std::lock_guard<std::mutex> lk(c->mu);
     int rc = car_rollout_device(c, states_in, actions, R, n_steps, every, dt, states_out != nullptr, vel_out != nullptr);
@@ -160,34 +161,21 @@ extern "C" int rl_car_rollout_check(rl_car *c, rl_method *h, const double *state
     if (!c->reps.empty()) {
         // MCTS.rollout + checkCollisionMany for R roll-outs over several devices: contiguous blocks of roll-outs,
         // each device integrates, scans and tests its own (nothing but the crash indices comes back)
-        if (R < 0 || n_steps <= 0 || every <= 0) return fail(RL_ERR_INVALID, "n_rollouts >= 0, n_steps > 0, action_every > 0 required");
+        const int rc = check_rollout_args(R, n_steps, every);
+        if (rc) return rc;
         for (size_t i = 0; i < c->reps.size(); ++i)
             if (c->reps[i]->device != h->reps[i]->map->device)
                 return fail(RL_ERR_INVALID, "car and range method replicas live on different devices");
-        std::scoped_lock lk(c->mu, h->mu);
-        std::shared_lock<std::shared_mutex> ml(h->map->multi_mu);
-        if (h->map->broken.load()) return fail(RL_ERR_INVALID, "multi-device map is inconsistent after a failed update: destroy it");
+        MultiCall mc(h, c->mu);
         const int k = (int)std::max<long>(1, std::min<long>(multi_parts(h, (long)R * n_steps), std::max(R, 1)));
         const size_t n_act = (size_t)(n_steps + every - 1) / every;
-        const float nstd = h->noise_std;
-        const uint64_t seed = h->noise_seed, off = h->ray_offset;
-        std::vector<std::function<int()>> jobs;
-        for (int i = 0; i < k; ++i) {
-            long lo, hi;
-            block_of(R, i, k, lo, hi);
-            rl_car *cr = c->reps[i];
-            rl_method *hr = h->reps[i];
-            jobs.push_back([=]() {
-                if (hi <= lo) return (int)RL_OK;
-                int rc = rl_set_noise(hr, nstd, seed, off + (uint64_t)lo * n_steps * num_rays);
-                if (rc) return rc;
-                return rl_car_rollout_check(cr, hr, states_in + 11 * lo, actions + 2 * n_act * lo, (int)(hi - lo), n_steps,
-                                            every, dt, fov, num_rays, edge, crash_thresh, first_crashed + lo,
-                                            states_out ? states_out + 11 * lo : nullptr,
-                                            vel_out ? vel_out + (size_t)n_steps * lo : nullptr);
-            });
-        }
-        return c->pool->run(jobs);
+        return mc.run(*c->pool, R, k, 0, (uint64_t)n_steps * num_rays, [=](const MultiBlock &b) {
+            const long lo = b.lo;
+            return rl_car_rollout_check(c->reps[b.replica], h->reps[b.replica], states_in + 11 * lo, actions + 2 * n_act * lo,
+                                        (int)(b.hi - lo), n_steps, every, dt, fov, num_rays, edge, crash_thresh, first_crashed + lo,
+                                        states_out ? states_out + 11 * lo : nullptr,
+                                        vel_out ? vel_out + (size_t)n_steps * lo : nullptr);
+        });
     }
     if (c->device != h->map->device) return fail(RL_ERR_INVALID, "car and range method live on different devices");
     std::scoped_lock lk(c->mu, h->mu);
@@ -202,7 +190,7 @@ extern "C" int rl_car_rollout_check(rl_car *c, rl_method *h, const double *state
     HIPCHK(hipMemcpyAsync(c->edge.p, edge, (size_t)num_rays * 8, hipMemcpyHostToDevice, c->stream));
     rc = crash_groups_device(h, (const float *)c->poses.p, R, n_steps, fov, num_rays,
                              (const double *)c->edge.p, crash_thresh, (int *)c->first.p,
-                             (float *)c->ranges.p, true, c->stream);
+                             (float *)c->ranges.p, c->stream);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(first_crashed, c->first.p, (size_t)R * 4, hipMemcpyDeviceToHost, c->stream));
     if (states_out) HIPCHK(hipMemcpyAsync(states_out, c->states_out.p, (size_t)R * 11 * 8, hipMemcpyDeviceToHost, c->stream));
@@ -1316,7 +1304,7 @@ extern "C" int rl_mcts_run(rl_mcts *m, int n_iterations)
         if (!rc) {
             m->h->ray_offset = off + KB;
             rc = crash_groups_device(m->h, (const float *)m->rposes.p, K, L, m->prm.fov, B, (const double *)m->edge.p,
-                                     m->prm.crash_thresh, (int *)m->first.p, (float *)m->rranges.p, true, st);
+                                     m->prm.crash_thresh, (int *)m->first.p, (float *)m->rranges.p, st);
         }
         if (!rc) {
             hipLaunchKernelGGL(mcts_backup_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b);

@@ -1646,14 +1646,19 @@ extern "C" int rl_debug_read_stamps(rl_method *h, uint64_t *out, int max_words)
 // ------------------------------------------------------------------------------
 // grouped crash test and the roll-out generator ("next" rows)
 // ------------------------------------------------------------------------------
-// d_first[g] <- first crashed pose of group g, or INT_MAX when none (finalize = false), or
-// -(group+1) (finalize = true).  Ray-marching methods fuse the test into the march kernel; the
-// others scan into d_ranges (required then) and run one pass over the ranges.
+int check_groups_args(int n_groups, int group)
+{
+    if (n_groups < 0 || group <= 0) return fail(RL_ERR_INVALID, "n_groups >= 0 and group > 0 required");
+    if ((long)n_groups * group > INT_MAX) return fail(RL_ERR_INVALID, "too many poses");
+    return RL_OK;
+}
+
+// d_first[g] <- first crashed pose of group g, or -(group+1) when none.  Ray-marching methods fuse the
+// test into the march kernel; the others scan into d_ranges (required then) and run one pass over the ranges.
 int crash_groups_device(rl_method *h, const float *d_poses, int n_groups, int group, float fov,
                                int num_rays, const double *d_edge, double thresh, int *d_first,
-                               float *d_ranges, bool finalize, hipStream_t stream)
+                               float *d_ranges, hipStream_t stream)
 {
-    (void)finalize;
     const int n_poses = n_groups * group;
     // the kernels mark crashed POSES (one word each, no contended atomics); groups are reduced after
     int rc;
@@ -1685,10 +1690,8 @@ extern "C" int rl_check_collision_groups_device(rl_method *h, const float *d_pos
                                                 int *d_first_crashed, float *d_ranges_or_null,
                                                 void *hip_stream)
 {
-    if (n_groups < 0 || group <= 0) return fail(RL_ERR_INVALID, "n_groups >= 0 and group > 0 required");
-    if ((long)n_groups * group > INT_MAX) return fail(RL_ERR_INVALID, "too many poses");
-    int rc = check_fan_args(h, n_groups * group, fov, num_rays);
-    if (rc) return rc;
+    int rc = check_groups_args(n_groups, group);
+    if (rc || (rc = check_fan_args(h, n_groups * group, fov, num_rays))) return rc;
     if (n_groups == 0) return RL_OK;
     if (!h->reps.empty()) return multi_needs_replica("rl_check_collision_groups_device");
     if (!d_poses || !d_edge || !d_first_crashed)
@@ -1697,7 +1700,7 @@ extern "C" int rl_check_collision_groups_device(rl_method *h, const float *d_pos
     std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
     if ((rc = set_device(h->map))) return rc;
     return crash_groups_device(h, d_poses, n_groups, group, fov, num_rays, d_edge, crash_thresh,
-                               d_first_crashed, d_ranges_or_null, true, (hipStream_t)hip_stream);
+                               d_first_crashed, d_ranges_or_null, (hipStream_t)hip_stream);
 }
 
 

@@ -3,7 +3,7 @@
 //   abi_map.hip    errors, pinned host blocks, rl_map_* (EDT, bit map, edge list)
 //   abi_fan.hip    rl_method_*: options, derived tables, the launch planner's C ABI, every fan / ray launch, the
 //                  device-pointer entry points, the single-device host-pointer paths, the fused crash test
-//   abi_multi.hip  the host-pointer entry points and their multi-device forms (one pose block per device)
+//   abi_multi.hip  the host-pointer entry points and their multi-device forms (run_blocks below: one block per device)
 //   abi_car.hip    roll-out generator, FollowGap, the policy network, closed-loop FollowGap / policy roll-outs,
 //                  batched races, 16-bit ranges, probes, the car-outline table
 #pragma once
@@ -41,6 +41,7 @@ using namespace scan;
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 const std::string &last_error();
 void set_last_error(const std::string &msg);
+int fail_map_broken();           // RL_ERR_INVALID: what every call on a multi-device map answers once `broken` is set
 
 #define HIPCHK(expr)                                                                      \
     do {                                                                                  \
@@ -158,17 +159,19 @@ struct TableDep {
 // ------------------------------------------------------------------------------
 // Several devices behind one handle (rl_map_create_multi): a single-process caller — the reference's
 // scanMany / checkCollisionMany callers are ONE Python process (scripts/mcts.py:237,
-// scripts/scan_simulator.py:113-135) — hands over one pose batch and every device scans a contiguous
-// block of it.  One persistent worker thread per device (bound to it with hipSetDevice once) runs the
-// ordinary single-device entry point on that device's replica handle; job 0 runs on the calling thread.
+// scripts/scan_simulator.py:113-135) — hands over one batch and every device takes a contiguous block of
+// it.  One persistent worker thread per device (bound to it with hipSetDevice once) runs the ordinary
+// single-device entry point on that device's replica handle; replica 0's block runs on the calling thread.
 // Threads and streams only: nothing is forked or re-executed after the GPU has been initialised.
+// run_blocks (below) is the one place that says which replica takes which block; how many blocks a batch
+// is cut into is decided where it is called (multi_parts and its kin).
 // ------------------------------------------------------------------------------
 struct MultiPool {
     struct Worker {
         std::thread th;
         std::mutex mu;
         std::condition_variable cv;
-        std::function<int()> job;
+        const std::function<int()> *job = nullptr;
         bool has = false, done = false, stop = false;
         int rc = 0;
         std::string err;
@@ -178,7 +181,7 @@ struct MultiPool {
 
     void start(const std::vector<int> &devices)
     {
-        for (size_t i = 1; i < devices.size(); ++i) {       // (block 0 is the caller's)
+        for (size_t i = 1; i < devices.size(); ++i) {       // (replica 0 has the caller's thread)
             auto wk = std::make_unique<Worker>();
             wk->device = devices[i];
             Worker *raw = wk.get();
@@ -190,7 +193,7 @@ struct MultiPool {
                     if (raw->stop) return;
                     raw->has = false;
                     lk.unlock();
-                    const int rc = raw->job();
+                    const int rc = (*raw->job)();
                     std::string msg = rc ? last_error() : std::string();
                     lk.lock();
                     raw->rc = rc;
@@ -203,24 +206,25 @@ struct MultiPool {
         }
     }
 
-    // jobs[0] on the caller, jobs[i] on worker i-1; the first failure (lowest block) is reported, its message
-    // becomes the caller's rl_last_error
-    int run(std::vector<std::function<int()>> &jobs)
+    // jobs[i], where there is one, runs on replica i's thread (jobs[0] on the caller's; a replica without a job is
+    // not woken); the failure of the lowest replica index is reported, its message becomes the caller's rl_last_error
+    int run(const std::vector<std::function<int()>> &jobs)
     {
         if (jobs.size() > w.size() + 1)
             return fail(RL_ERR_INVALID, "internal: %zu pose blocks for %zu devices", jobs.size(), w.size() + 1);
-        const size_t k = jobs.size();
-        for (size_t i = 1; i < k; ++i) {
+        for (size_t i = 1; i < jobs.size(); ++i) {
+            if (!jobs[i]) continue;
             Worker &x = *w[i - 1];
             std::lock_guard<std::mutex> lk(x.mu);
-            x.job = std::move(jobs[i]);
+            x.job = &jobs[i];
             x.has = true;
             x.done = false;
             x.cv.notify_all();
         }
-        int rc = jobs.empty() ? RL_OK : jobs[0]();
+        int rc = !jobs.empty() && jobs[0] ? jobs[0]() : (int)RL_OK;
         std::string err = rc ? last_error() : std::string();
-        for (size_t i = 1; i < k; ++i) {
+        for (size_t i = 1; i < jobs.size(); ++i) {
+            if (!jobs[i]) continue;
             Worker &x = *w[i - 1];
             std::unique_lock<std::mutex> lk(x.mu);
             x.cv.wait(lk, [&x]() { return x.done; });
@@ -252,6 +256,27 @@ static inline void block_of(long n, int rank, int parts, long &lo, long &hi)
     const long base = n / parts, rem = n % parts;
     lo = rank * base + std::min<long>(rank, rem);
     hi = lo + base + (rank < rem ? 1 : 0);
+}
+
+// THE block scheduler of every multi-device entry point: n_units are cut into k contiguous blocks (k <= replicas) and
+// job(block) runs for every block that is not empty, replica i's on replica i's thread.  Block 0 goes to replica
+// `first` — 0, or the consumer of a device-resident call, so that a batch too small for every device stays where it
+// is wanted — and the following blocks to the remaining replicas in index order.  Errors as MultiPool::run.
+struct MultiBlock {
+    int index, replica;
+    long lo, hi;                 // the block's units [lo, hi)
+};
+
+template <class Job>
+static inline int run_blocks(MultiPool &pool, long n_units, int k, int first, const Job &job)
+{
+    std::vector<std::function<int()>> jobs(std::max<size_t>(pool.w.size() + 1, (size_t)k));
+    for (int b = 0; b < k; ++b) {
+        MultiBlock blk{b, b == 0 ? first : (b <= first ? b - 1 : b), 0, 0};
+        block_of(n_units, b, k, blk.lo, blk.hi);
+        if (blk.hi > blk.lo) jobs[blk.replica] = [&job, blk]() { return job(blk); };
+    }
+    return pool.run(jobs);
 }
 
 struct rl_method {
@@ -361,6 +386,32 @@ struct rl_method {
     std::mutex mu;
 };
 
+// A multi-device method for the length of one batch: h->mu (together with the mutexes of `also`, e.g. the car's of a
+// roll-out chain) and the map's multi_mu (shared) are held while it lives, the handle's noise is read once, and run()
+// refuses a broken map, then hands the batch to run_blocks with the replica's noise set before each block's job — keyed
+// by the GLOBAL ray id: the parent's offset + the rays before the block (rays_per_unit each unit).
+template <class... Also>
+struct MultiCall {
+    rl_method *const h;
+    std::scoped_lock<Also..., std::mutex> lk;
+    std::shared_lock<std::shared_mutex> ml;
+    const float nstd;
+    const uint64_t seed, off;
+    explicit MultiCall(rl_method *m, Also &...also)
+        : h(m), lk(also..., m->mu), ml(m->map->multi_mu), nstd(m->noise_std), seed(m->noise_seed), off(m->ray_offset)
+    {
+    }
+    template <class Job>
+    int run(MultiPool &pool, long n_units, int k, int first, uint64_t rays_per_unit, const Job &job) const
+    {
+        if (h->map->broken.load()) return fail_map_broken();
+        return run_blocks(pool, n_units, k, first, [&](const MultiBlock &b) {
+            const int rc = rl_set_noise(h->reps[b.replica], nstd, seed, off + (uint64_t)b.lo * rays_per_unit);
+            return rc ? rc : job(b);
+        });
+    }
+};
+
 int set_device(const rl_map *m);
 int map_build_tables(rl_map *m);                    // EDT + bit map (+ edge list once a CDDT method exists); abi_map.hip
 void host_sincosf(float x, float &s, float &c);      // host twin of scan::det_sincosf (abi_map.hip)
@@ -379,8 +430,8 @@ int launch_fan(rl_method *h, const float *d_poses, int n_poses, float fov, int n
 int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_rays, float *outs, int32_t *hits,
              uint16_t *steps, const double *edge, double crash_thresh, int *first_crashed);
 int crash_groups_device(rl_method *h, const float *d_poses, int n_groups, int group, float fov, int num_rays,
-                        const double *d_edge, double thresh, int *d_first, float *d_ranges, bool finalize,
-                        hipStream_t stream);
+                        const double *d_edge, double thresh, int *d_first, float *d_ranges, hipStream_t stream);
 int upload_edge(rl_method *h, const double *edge, int num_rays);
 int rays_host(rl_method *h, const float *ins, float *outs, int n);
+int check_groups_args(int n_groups, int group);     // the grouped crash tests' first two checks
 int multi_parts(const rl_method *h, long n_poses);

@@ -22,6 +22,7 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
+int fail_map_broken() { return fail(RL_ERR_INVALID, "multi-device map is inconsistent after a failed update: destroy it"); }
 const std::string &last_error() { return g_err; }
 void set_last_error(const std::string &msg) { g_err = msg; }
 
@@ -280,7 +281,7 @@ extern "C" int rl_map_update(rl_map *m, const uint8_t *occ)
         std::lock_guard<std::mutex> lk(m->mu);
         // exclusive against every multi_* call in progress: a batch sees ONE occupancy on all of its devices
         std::unique_lock<std::shared_mutex> wl(m->multi_mu);
-        if (m->broken.load()) return fail(RL_ERR_INVALID, "multi-device map is inconsistent after a failed update: destroy it");
+        if (m->broken.load()) return fail_map_broken();
         for (size_t i = 0; i < m->reps.size(); ++i) {
             const int rc = rl_map_update(m->reps[i], occ);
             if (rc) {
@@ -328,7 +329,7 @@ extern "C" int rl_map_stamp_cells(rl_map *m, const int32_t *flat_idx, int n, uin
     if (!m->reps.empty()) {
         std::lock_guard<std::mutex> lk(m->mu);
         std::unique_lock<std::shared_mutex> wl(m->multi_mu);
-        if (m->broken.load()) return fail(RL_ERR_INVALID, "multi-device map is inconsistent after a failed update: destroy it");
+        if (m->broken.load()) return fail_map_broken();
         for (size_t i = 0; i < m->reps.size(); ++i) {
             const int rc = rl_map_stamp_cells(m->reps[i], flat_idx, n, value);
             if (rc) {

@@ -1,10 +1,11 @@
-// abi_multi.hip — the host-pointer entry points of libscan_amd.so (C ABI: include/scanlib.h) and their multi-device forms:
-// one contiguous pose block per device of a handle made by rl_map_create_multi, a worker thread per device.
+// abi_multi.hip — the host-pointer entry points of libscan_amd.so (C ABI: include/scanlib.h) and their multi-device forms
+// on a handle made by rl_map_create_multi: each says what a block is and how many there are; MultiCall / run_blocks
+// (abi_internal.h) say under which locks, with which noise offset, and which replica's thread takes which block.
 // (scripts/scan_simulator.py:113-135 scanMany, scripts/mcts.py:237 checkCollisionMany: ONE Python process hands over a batch.)
 #include "abi_internal.h"
 
 // ------------------------------------------------------------------------------
-// multi-device forms of the host-pointer entry points: contiguous pose blocks, one per device, each
+// multi-device forms of the host-pointer entry points: contiguous blocks, one per device, each
 // device writing its block of the results straight into the caller's buffer (in a pinned block of
 // rl_host_alloc the kernels write it directly: 4 B per ray over that device's own PCIe link).  Noise
 // stays keyed by the GLOBAL ray id (the replica's ray offset is the parent's + the block's first ray),
@@ -13,96 +14,61 @@
 static int multi_fan(rl_method *h, const float *poses, const float *rows3, int n_poses, float fov, int num_rays,
                      float *outs, int32_t *hits, uint16_t *steps)
 {
-    std::lock_guard<std::mutex> lk(h->mu);
-    std::shared_lock<std::shared_mutex> ml(h->map->multi_mu);
-    if (h->map->broken.load()) return fail(RL_ERR_INVALID, "multi-device map is inconsistent after a failed update: destroy it");
-    const int k = multi_parts(h, n_poses);
-    const float nstd = h->noise_std;
-    const uint64_t seed = h->noise_seed, off = h->ray_offset;
-    std::vector<std::function<int()>> jobs;
-    for (int i = 0; i < k; ++i) {
-        long lo, hi;
-        block_of(n_poses, i, k, lo, hi);
-        rl_method *r = h->reps[i];
-        const size_t r0 = (size_t)lo * num_rays;
-        jobs.push_back([=]() {
-            int rc = rl_set_noise(r, nstd, seed, off + r0);
-            if (rc) return rc;
-            if (rows3)          // the fork's sparse 4-argument layout: pose p in row p * num_rays
-                return rl_calc_range_many_fan(r, rows3 + r0 * 3, outs + r0, (int)(hi - lo) * num_rays, fov, num_rays);
-            return rl_calc_range_fan(r, poses + 3 * lo, (int)(hi - lo), fov, num_rays, outs + r0,
-                                     hits ? hits + 2 * r0 : nullptr, steps ? steps + r0 : nullptr);
-        });
-    }
-    return h->pool->run(jobs);
+    MultiCall mc(h);
+    return mc.run(*h->pool, n_poses, multi_parts(h, n_poses), 0, num_rays, [=](const MultiBlock &b) {
+        rl_method *r = h->reps[b.replica];
+        const int np = (int)(b.hi - b.lo);
+        const size_t r0 = (size_t)b.lo * num_rays;
+        if (rows3)          // the fork's sparse 4-argument layout: pose p in row p * num_rays
+            return rl_calc_range_many_fan(r, rows3 + r0 * 3, outs + r0, np * num_rays, fov, num_rays);
+        return rl_calc_range_fan(r, poses + 3 * b.lo, np, fov, num_rays, outs + r0, hits ? hits + 2 * r0 : nullptr,
+                                 steps ? steps + r0 : nullptr);
+    });
 }
+
+// A per-ray call has no poses to hold against multi_min_poses: MULTI_RAYS_PER_POSE rays count as one (and a device is
+// brought in per multi_min_poses of those).
+constexpr long MULTI_RAYS_PER_POSE = 64L * 16;
 
 static int multi_rays(rl_method *h, const float *ins, float *outs, int n)
 {
-    std::lock_guard<std::mutex> lk(h->mu);
-    std::shared_lock<std::shared_mutex> ml(h->map->multi_mu);
-    if (h->map->broken.load()) return fail(RL_ERR_INVALID, "multi-device map is inconsistent after a failed update: destroy it");
-    const int k = (int)std::max<long>(1, std::min<long>((long)h->reps.size(), (long)n / (64L * std::max(h->multi_min_poses, 1) * 16)));
-    const float nstd = h->noise_std;
-    const uint64_t seed = h->noise_seed, off = h->ray_offset;
-    std::vector<std::function<int()>> jobs;
-    for (int i = 0; i < k; ++i) {
-        long lo, hi;
-        block_of(n, i, k, lo, hi);
-        rl_method *r = h->reps[i];
-        jobs.push_back([=]() {
-            int rc = rl_set_noise(r, nstd, seed, off + (uint64_t)lo);
-            if (rc) return rc;
-            return rl_calc_range_many(r, ins + 3 * lo, outs + lo, (int)(hi - lo));
-        });
-    }
-    return h->pool->run(jobs);
+    MultiCall mc(h);
+    const long by_size = (long)n / (MULTI_RAYS_PER_POSE * std::max(h->multi_min_poses, 1));
+    const int k = (int)std::max<long>(1, std::min<long>((long)h->reps.size(), by_size));
+    return mc.run(*h->pool, n, k, 0, 1, [=](const MultiBlock &b) {
+        return rl_calc_range_many(h->reps[b.replica], ins + 3 * b.lo, outs + b.lo, (int)(b.hi - b.lo));
+    });
 }
 
 // groups of `group` poses (group == n_poses, n_groups == 1 with `single`: rl_check_collision_many's one index)
 static int multi_crash(rl_method *h, const float *poses, int n_groups, int group, float fov, int num_rays,
                        const double *edge, double thresh, int *first_crashed, float *ranges, bool single)
 {
-    std::lock_guard<std::mutex> lk(h->mu);
-    std::shared_lock<std::shared_mutex> ml(h->map->multi_mu);
-    if (h->map->broken.load()) return fail(RL_ERR_INVALID, "multi-device map is inconsistent after a failed update: destroy it");
+    MultiCall mc(h);
     const long n_units = single ? group : n_groups;              // what is cut: poses of the one batch | roll-outs
     const long poses_per_unit = single ? 1 : group;
     const int k = (int)std::max<long>(1, std::min<long>(multi_parts(h, n_units * poses_per_unit), n_units));
-    const float nstd = h->noise_std;
-    const uint64_t seed = h->noise_seed, off = h->ray_offset;
-    std::vector<int> part(k, 0);
-    std::vector<long> los(k, 0), his(k, 0);
-    std::vector<std::function<int()>> jobs;
-    for (int i = 0; i < k; ++i) {
-        long lo, hi;
-        block_of(n_units, i, k, lo, hi);
-        los[i] = lo;
-        his[i] = hi;
-        rl_method *r = h->reps[i];
-        const size_t p0 = (size_t)lo * poses_per_unit, r0 = p0 * num_rays;
-        int *res = single ? &part[i] : first_crashed + lo;
-        jobs.push_back([=]() {
-            if (hi <= lo) return (int)RL_OK;
-            int rc = rl_set_noise(r, nstd, seed, off + r0);
-            if (rc) return rc;
-            if (single)
-                return rl_check_collision_many(r, poses + 3 * p0, (int)(hi - lo), fov, num_rays, edge, thresh, res,
-                                               ranges ? ranges + r0 : nullptr);
-            return rl_check_collision_groups(r, poses + 3 * p0, (int)(hi - lo), group, fov, num_rays, edge, thresh, res,
-                                             ranges ? ranges + r0 : nullptr);
-        });
-    }
-    const int rc = h->pool->run(jobs);
-    if (rc) return rc;
-    if (single) {
-        *first_crashed = -(group + 1);                            // Car::isCrashed: -(poses + 1) when none crashed
-        for (int i = 0; i < k; ++i)
-            if (his[i] > los[i] && part[i] >= 0) {
-                *first_crashed = (int)los[i] + part[i];
-                break;
-            }
-    }
+    std::vector<int> part(k, -1);                                // single: block i's first crashed pose (global index), < 0: none
+    int *const part_p = part.data();
+    const int rc = mc.run(*h->pool, n_units, k, 0, (uint64_t)poses_per_unit * num_rays, [=](const MultiBlock &b) {
+        rl_method *r = h->reps[b.replica];
+        const int n = (int)(b.hi - b.lo);
+        const size_t p0 = (size_t)b.lo * poses_per_unit, r0 = p0 * num_rays;
+        float *rg = ranges ? ranges + r0 : nullptr;
+        if (!single)
+            return rl_check_collision_groups(r, poses + 3 * p0, n, group, fov, num_rays, edge, thresh, first_crashed + b.lo, rg);
+        int &first = part_p[b.index];
+        const int rc1 = rl_check_collision_many(r, poses + 3 * p0, n, fov, num_rays, edge, thresh, &first, rg);
+        if (rc1 == RL_OK && first >= 0) first += (int)b.lo;
+        return rc1;
+    });
+    if (rc || !single) return rc;
+    *first_crashed = -(group + 1);                                // Car::isCrashed: -(poses + 1) when none crashed
+    for (int first : part)
+        if (first >= 0) {
+            *first_crashed = first;
+            break;
+        }
     return RL_OK;
 }
 
@@ -133,10 +99,10 @@ static void try_peer(int from, int to)
     (void)hipGetLastError();                            // ("already enabled" is not an error worth keeping)
 }
 
+// (run from a MultiCall: the replica's noise stands at the block's first ray, off0; every further chunk moves it on)
 static int replica_fan_to_consumer(rl_method *r, const float *poses_blk, int np, float fov, int num_rays, float nstd,
                                    uint64_t seed, uint64_t off0, bool is_consumer, int consumer_dev, float *d_dst, int chunks)
 {
-    if (np <= 0) return RL_OK;
     int rc = set_device(r->map);
     if (rc) return rc;
     const int dev = r->map->device;
@@ -157,7 +123,7 @@ static int replica_fan_to_consumer(rl_method *r, const float *poses_blk, int np,
         long lo, hi;
         block_of(np, c, k, lo, hi);
         const size_t r0 = (size_t)lo * num_rays, nr = (size_t)(hi - lo) * num_rays;
-        if ((rc = rl_set_noise(r, nstd, seed, off0 + r0))) return rc;
+        if (c > 0 && (rc = rl_set_noise(r, nstd, seed, off0 + r0))) return rc;
         if ((rc = rl_calc_range_fan_device(r, d_poses + 3 * lo, (int)(hi - lo), fov, num_rays, d_local + r0, nullptr, nullptr,
                                            (void *)r->stream)))
             return rc;
@@ -174,10 +140,8 @@ static int replica_fan_to_consumer(rl_method *r, const float *poses_blk, int np,
 }
 
 static int replica_crash_to_consumer(rl_method *r, const float *poses_blk, int n_groups, int group, float fov, int num_rays,
-                                     const double *edge, double thresh, float nstd, uint64_t seed, uint64_t off0,
-                                     bool is_consumer, int consumer_dev, int *d_dst)
+                                     const double *edge, double thresh, bool is_consumer, int consumer_dev, int *d_dst)
 {
-    if (n_groups <= 0) return RL_OK;
     int rc = set_device(r->map);
     if (rc) return rc;
     const int dev = r->map->device;
@@ -196,7 +160,6 @@ static int replica_crash_to_consumer(rl_method *r, const float *poses_blk, int n
     }
     if (!is_consumer) try_peer(dev, consumer_dev);
     HIPCHK(hipMemcpyAsync(d_poses, poses_blk, np * 12, hipMemcpyHostToDevice, r->stream));
-    if ((rc = rl_set_noise(r, nstd, seed, off0))) return rc;
     if ((rc = rl_check_collision_groups_device(r, d_poses, n_groups, group, fov, num_rays, d_edge, thresh, d_local, nullptr,
                                                (void *)r->stream)))
         return rc;
@@ -224,74 +187,35 @@ extern "C" int rl_calc_range_fan_multi_device(rl_method *h, const float *poses, 
     if (n_poses == 0) return RL_OK;
     if ((rc = multi_device_check(h, consumer, d_outs_on_consumer, "rl_calc_range_fan_multi_device"))) return rc;
     if (!poses) return fail(RL_ERR_INVALID, "rl_calc_range_fan_multi_device: null pose pointer");
-    std::lock_guard<std::mutex> lk(h->mu);
-    std::shared_lock<std::shared_mutex> ml(h->map->multi_mu);
-    if (h->map->broken.load()) return fail(RL_ERR_INVALID, "multi-device map is inconsistent after a failed update: destroy it");
+    MultiCall mc(h);
+    const int consumer_dev = h->reps[consumer]->map->device, ch = chunks > 0 ? chunks : 4;
+    const float nstd = mc.nstd;
+    const uint64_t seed = mc.seed, off = mc.off;
     // (every device takes part from multi_min_poses poses per device up; the consumer always owns a block — block 0 is its own)
-    const int k = multi_parts(h, n_poses);
-    const int consumer_dev = h->reps[consumer]->map->device;
-    const float nstd = h->noise_std;
-    const uint64_t seed = h->noise_seed, off = h->ray_offset;
-    // block i goes to replica order[i]: the consumer first, so that a batch too small for every device stays where it is wanted
-    std::vector<int> order;
-    order.push_back(consumer);
-    for (int i = 0; i < (int)h->reps.size(); ++i)
-        if (i != consumer) order.push_back(i);
-    // (jobs[0] runs on the calling thread, jobs[i] on the worker of replica i: hand replica order[b]'s block to ITS thread)
-    std::vector<std::function<int()>> jobs(h->reps.size(), []() { return (int)RL_OK; });
-    for (int b = 0; b < k; ++b) {
-        long lo, hi;
-        block_of(n_poses, b, k, lo, hi);
-        rl_method *r = h->reps[order[b]];
-        const size_t r0 = (size_t)lo * num_rays;
-        const bool is_c = order[b] == consumer;
-        const int ch = chunks > 0 ? chunks : 4;
-        jobs[order[b]] = [=]() {
-            return replica_fan_to_consumer(r, poses + 3 * lo, (int)(hi - lo), fov, num_rays, nstd, seed, off + r0, is_c,
-                                           consumer_dev, d_outs_on_consumer + r0, ch);
-        };
-    }
-    while (jobs.size() > 1 && std::find(order.begin(), order.begin() + k, (int)jobs.size() - 1) == order.begin() + k) jobs.pop_back();
-    return h->pool->run(jobs);
+    return mc.run(*h->pool, n_poses, multi_parts(h, n_poses), consumer, num_rays, [=](const MultiBlock &b) {
+        const size_t r0 = (size_t)b.lo * num_rays;
+        return replica_fan_to_consumer(h->reps[b.replica], poses + 3 * b.lo, (int)(b.hi - b.lo), fov, num_rays, nstd, seed, off + r0,
+                                       b.replica == consumer, consumer_dev, d_outs_on_consumer + r0, ch);
+    });
 }
 
 extern "C" int rl_check_collision_groups_multi_device(rl_method *h, const float *poses, int n_groups, int group, float fov,
                                                       int num_rays, const double *edge, double crash_thresh, int consumer,
                                                       int *d_first_on_consumer)
 {
-    if (n_groups < 0 || group <= 0) return fail(RL_ERR_INVALID, "n_groups >= 0 and group > 0 required");
-    if ((long)n_groups * group > INT_MAX) return fail(RL_ERR_INVALID, "too many poses");
-    int rc = check_fan_args(h, n_groups * group, fov, num_rays);
-    if (rc) return rc;
+    int rc = check_groups_args(n_groups, group);
+    if (rc || (rc = check_fan_args(h, n_groups * group, fov, num_rays))) return rc;
     if (n_groups == 0) return RL_OK;
     if ((rc = multi_device_check(h, consumer, d_first_on_consumer, "rl_check_collision_groups_multi_device"))) return rc;
     if (!poses || !edge) return fail(RL_ERR_INVALID, "rl_check_collision_groups_multi_device: null pointer");
     if (h->kind != RL_RM && h->kind != RL_RM_GPU) return fail(RL_ERR_UNSUPPORTED, "fused crash test needs a ray-marching method");
-    std::lock_guard<std::mutex> lk(h->mu);
-    std::shared_lock<std::shared_mutex> ml(h->map->multi_mu);
-    if (h->map->broken.load()) return fail(RL_ERR_INVALID, "multi-device map is inconsistent after a failed update: destroy it");
-    const int k = (int)std::max<long>(1, std::min<long>(multi_parts(h, (long)n_groups * group), n_groups));
+    MultiCall mc(h);
     const int consumer_dev = h->reps[consumer]->map->device;
-    const float nstd = h->noise_std;
-    const uint64_t seed = h->noise_seed, off = h->ray_offset;
-    std::vector<int> order;
-    order.push_back(consumer);
-    for (int i = 0; i < (int)h->reps.size(); ++i)
-        if (i != consumer) order.push_back(i);
-    std::vector<std::function<int()>> jobs(h->reps.size(), []() { return (int)RL_OK; });
-    for (int b = 0; b < k; ++b) {
-        long lo, hi;
-        block_of(n_groups, b, k, lo, hi);
-        rl_method *r = h->reps[order[b]];
-        const size_t p0 = (size_t)lo * group;
-        const bool is_c = order[b] == consumer;
-        jobs[order[b]] = [=]() {
-            return replica_crash_to_consumer(r, poses + 3 * p0, (int)(hi - lo), group, fov, num_rays, edge, crash_thresh, nstd, seed,
-                                             off + p0 * num_rays, is_c, consumer_dev, d_first_on_consumer + lo);
-        };
-    }
-    while (jobs.size() > 1 && std::find(order.begin(), order.begin() + k, (int)jobs.size() - 1) == order.begin() + k) jobs.pop_back();
-    return h->pool->run(jobs);
+    const int k = (int)std::max<long>(1, std::min<long>(multi_parts(h, (long)n_groups * group), n_groups));
+    return mc.run(*h->pool, n_groups, k, consumer, (uint64_t)group * num_rays, [=](const MultiBlock &b) {
+        return replica_crash_to_consumer(h->reps[b.replica], poses + 3 * (size_t)b.lo * group, (int)(b.hi - b.lo), group, fov, num_rays,
+                                         edge, crash_thresh, b.replica == consumer, consumer_dev, d_first_on_consumer + b.lo);
+    });
 }
 
 extern "C" int rl_calc_range_fan(rl_method *h, const float *poses, int n_poses, float fov,
@@ -374,12 +298,10 @@ extern "C" int rl_check_collision_groups(rl_method *h, const float *poses, int n
                                          float fov, int num_rays, const double *edge,
                                          double crash_thresh, int *first_crashed, float *ranges_or_null)
 {
-    if (n_groups < 0 || group <= 0) return fail(RL_ERR_INVALID, "n_groups >= 0 and group > 0 required");
-    const long n_poses_l = (long)n_groups * group;
-    if (n_poses_l > INT_MAX) return fail(RL_ERR_INVALID, "too many poses");
-    const int n_poses = (int)n_poses_l;
-    int rc = check_fan_args(h, n_poses, fov, num_rays);
+    int rc = check_groups_args(n_groups, group);
     if (rc) return rc;
+    const int n_poses = n_groups * group;
+    if ((rc = check_fan_args(h, n_poses, fov, num_rays))) return rc;
     if (n_groups == 0) return RL_OK;
     if (!poses || !edge || !first_crashed) return fail(RL_ERR_INVALID, "rl_check_collision_groups: null pointer");
     if (!h->reps.empty())
@@ -394,7 +316,7 @@ extern "C" int rl_check_collision_groups(rl_method *h, const float *poses, int n
     HIPCHK(hipMemcpyAsync(h->poses.p, poses, (size_t)n_poses * 12, hipMemcpyHostToDevice, h->stream));
     rc = crash_groups_device(h, (const float *)h->poses.p, n_groups, group, fov, num_rays,
                              (const double *)h->edge.p, crash_thresh, (int *)h->flag.p,
-                             (float *)h->outs.p, true, h->stream);
+                             (float *)h->outs.p, h->stream);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(first_crashed, h->flag.p, (size_t)n_groups * 4, hipMemcpyDeviceToHost, h->stream));
     if (ranges_or_null)
