@@ -481,6 +481,36 @@ int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const double *sta
  * child links -1 = none), any output pointer may be null; crash = the roll-out's crash index (-(L+1): none), -1
  * for the root and terminal nodes; answer = the stored expansion answer (NaN for RANDOM); n_nodes_out = how many.
  * rl_mcts_probe_ucb: the device's UCB key of n (reward, visits >= 1, 1 <= sum <= 2^24) triples.
+ *
+ * rl_mcts_drive: the closed loop of scripts/mcts_driver.py:207-264 (createActionCallback) for the K = n_trees cars
+ * of m: every action tick sets the simulator to the car's state (:214), builds a fresh MCTS with the recent action
+ * at the root (:230-232), takes its answer (:234), drives and steps the car with it (:249-250) and keeps the answer
+ * clipped as the next recent action (:254).  Synchronous, on c's stream; states_in (K x 11), recent_in (K) and the
+ * K x D Philox keys go up once, before decision 0, and between decisions there is no host synchronisation and no
+ * host-to-device copy.  D = n_decisions, I = n_iterations, S = steps_per_decision, L = rollout_steps, B = num_rays.
+ * Per decision d = 0 ... D-1, for every car k:
+ *   1. reset: tree k is re-rooted as rl_mcts_reset does it, with the car's current state as the root state, its
+ *      recent action as the root action and the seed (seeds[k] + d) mod 2^64 (key = noise_key of it); the root scan
+ *      and answer come from the ordinary act launch; the ray offset is base + d stride with base = h's ray offset at
+ *      entry and stride = K B (1 + I (1 + L)), the rays one rl_mcts_reset plus rl_mcts_run(I) consume;
+ *   2. the car's crash test: Car::isCrashed(root scan) >= 0 (ros_interface.py:144, as rl_car_drive_followgap).  A car
+ *      crashed at decision d gets first[k] = d and freezes: its state and recent action no longer change,
+ *      actions[k][d...] and the trace rows from d on are NaN, visits[k][d...] are -1.  Its tree is searched with the
+ *      others from the frozen state and ignored.  The root node itself is never terminal, as in the reference;
+ *   3. I iterations, exactly rl_mcts_run's;
+ *   4. the answer, rl_mcts_best's rule: the most visited root child, the first of equals -> actions[k][d] (raw, not
+ *      clipped) and visits[k][d];
+ *   5. the step: S times Car::control(speed, a) + updatePosition(dt) in float64 with the raw action (:249), the
+ *      state of rl_car_rollout holding (speed, a) for S steps, bit for bit; the next recent action is a clamped to
+ *      +-steer_clip when steer_clip > 0 (:254), raw when it is 0; trace_states[k][d] is the state the decision was
+ *      planned from.
+ * Afterwards first[k] = -(D+1) for a car that never crashed; states_out / recent_out are the final states and recent
+ * actions (the state after the last step is not scanned); m is ready and holds the last decision's trees
+ * (rl_mcts_read_tree and rl_mcts_best work, I iterations done since its reset); h's options and ray offset read the
+ * same as before the call.  A failed launch leaves the planner needing a reset.  n_decisions = 0: RL_OK, first = -1,
+ * states_out = states_in, recent_out = recent_in, the planner untouched.  Errors (RL_ERR_INVALID, nothing launched,
+ * the handles usable as before): a null required pointer, n_decisions < 0, n_iterations < 1, n_iterations + 1 >
+ * max_nodes, steps_per_decision < 1, steer_clip negative or NaN, and the range method's refusals as in rl_mcts_run.
  * Kernels: mcts_kernels.h.                                                                                    */
 typedef struct rl_mcts rl_mcts;
 typedef enum rl_mcts_source { RL_MCTS_FG = 0, RL_MCTS_NN = 1, RL_MCTS_RANDOM = 2 } rl_mcts_source;
@@ -497,6 +527,11 @@ void rl_mcts_destroy(rl_mcts *m);
 int rl_mcts_reset(rl_mcts *m, const double *root_states, const double *root_actions, const uint64_t *seeds);
 int rl_mcts_run(rl_mcts *m, int n_iterations);
 int rl_mcts_best(rl_mcts *m, double *actions, int *visits, int *n_nodes);
+int rl_mcts_drive(rl_mcts *m, const double *states_in, const double *recent_in, const uint64_t *seeds,
+                  int n_decisions, int n_iterations, int steps_per_decision, double steer_clip,
+                  int *first, double *states_out, double *recent_out,
+                  double *actions, int *visits,            /* [K][n_decisions]                */
+                  double *trace_states_or_null);           /* [K][n_decisions][11] or NULL    */
 int rl_mcts_read_tree(rl_mcts *m, int tree, int *parent, int *first_child, int *next_sibling, int *n_children,
                       int *visits, int *child_visits, double *reward, double *action, int *terminal, double *state,
                       float *scan_pose, float *answer, int *crash, int *n_nodes_out);

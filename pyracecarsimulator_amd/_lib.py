@@ -147,6 +147,8 @@ SYMBOLS = {
     "rl_mcts_reset": (C.c_int, [C.c_void_p, f64p, f64p, C.POINTER(C.c_uint64)]),
     "rl_mcts_run": (C.c_int, [C.c_void_p, C.c_int]),
     "rl_mcts_best": (C.c_int, [C.c_void_p, f64p, i32p, i32p]),
+    "rl_mcts_drive": (C.c_int, [C.c_void_p, f64p, f64p, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, C.c_double,
+                                i32p, f64p, f64p, f64p, i32p, f64p]),
     "rl_mcts_read_tree": (C.c_int, [C.c_void_p, C.c_int, i32p, i32p, i32p, i32p, i32p, i32p, f64p, f64p, i32p, f64p,
                                     f32p, f32p, i32p, i32p]),
     "rl_mcts_probe_ucb": (C.c_int, [C.c_int, f64p, i32p, i32p, C.c_size_t, C.c_double, f64p]),

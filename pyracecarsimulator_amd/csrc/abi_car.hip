@@ -1055,6 +1055,8 @@ struct rl_mcts {
     DevBuf parent, first_child, next_sibling, last_child, n_children, visits, child_visits, terminal, crash;
     DevBuf reward, action, state, pose, answer, n_nodes, child, exp_term, keys, logtab;
     DevBuf cstate, cpose, actions, ranges, edge, mlp, rposes, vel, first, rranges, roots, best_a, best_v, best_n;
+    // rl_mcts_drive: the root crash flags, the K x D keys and the per-decision outputs
+    DevBuf root_crash, dr_keys, dr_first, dr_actions, dr_visits, dr_trace;
     bool ready = false;            // reset done and no launch failed since
     long iters = 0;                // iterations since reset
     uint64_t base = 0;             // h's ray offset at reset
@@ -1111,7 +1113,8 @@ extern "C" void rl_mcts_destroy(rl_mcts *m)
                       &m->child_visits, &m->terminal, &m->crash, &m->reward, &m->action, &m->state, &m->pose,
                       &m->answer, &m->n_nodes, &m->child, &m->exp_term, &m->keys, &m->logtab, &m->cstate, &m->cpose,
                       &m->actions, &m->ranges, &m->edge, &m->mlp, &m->rposes, &m->vel, &m->first, &m->rranges,
-                      &m->roots, &m->best_a, &m->best_v, &m->best_n})
+                      &m->roots, &m->best_a, &m->best_v, &m->best_n, &m->root_crash, &m->dr_keys, &m->dr_first,
+                      &m->dr_actions, &m->dr_visits, &m->dr_trace})
         b->release();
     delete m;
 }
@@ -1206,8 +1209,8 @@ extern "C" int rl_mcts_create(rl_car *c, rl_method *h, rl_followgap *g, rl_polic
     return RL_OK;
 }
 
-// the act scans of the K nodes in m->cpose at ray offset `off`, the network for NN, then mcts_act_kernel
-static int mcts_act(rl_mcts *m, uint64_t off, int root, hipStream_t st)
+// the act scans of the K nodes in m->cpose at ray offset `off`, the network for NN, then mcts_act_kernel on b
+static int mcts_act(rl_mcts *m, const MctsBufs &b, uint64_t off, int root, hipStream_t st)
 {
     rl_method *h = m->h;
     const int K = m->prm.n_trees, B = m->prm.num_rays;
@@ -1219,7 +1222,7 @@ static int mcts_act(rl_mcts *m, uint64_t off, int root, hipStream_t st)
         (rc = policy_launch(m->p, (const float *)m->ranges.p, K, B, (float *)m->mlp.p, st)))
         return rc;
     mcts_act_table[(B + 63) / 64 - 1]<<<dim3((K + MCTS_TREES - 1) / MCTS_TREES), dim3(64 * MCTS_TREES), 0, st>>>(
-        m->mp, mcts_bufs(m), root);
+        m->mp, b, root);
     if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "mcts_act_kernel launch failed");
     return RL_OK;
 }
@@ -1258,7 +1261,7 @@ extern "C" int rl_mcts_reset(rl_mcts *m, const double *root_states, const double
                        (const double *)d_states, (const double *)d_actions);
     if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_start_kernel launch failed");
     const uint64_t base = lk.ov.ray_offset;
-    if (!rc) rc = mcts_act(m, base, 1, st);
+    if (!rc) rc = mcts_act(m, mcts_bufs(m), base, 1, st);
     const hipError_t e = hipStreamSynchronize(st);            // (the host's root arrays are the caller's)
     if (!rc && e != hipSuccess) rc = fail(RL_ERR_HIP, "rl_mcts_reset: %s", hipGetErrorString(e));
     if (rc) return rc;
@@ -1266,6 +1269,38 @@ extern "C" int rl_mcts_reset(rl_mcts *m, const double *root_states, const double
     m->iters = 0;
     m->ready = true;
     return RL_OK;
+}
+
+// iterations it0 ... it0 + n - 1 of every tree, enqueued on st: select, the act, the roll-outs and their crash
+// test, the backup.  base: the ray offset of the trees' reset.  The caller holds MctsLock and has sized m->rranges.
+static int mcts_iterations(rl_mcts *m, const MctsBufs &b, uint64_t base, long it0, int n, hipStream_t st)
+{
+    const int K = m->prm.n_trees, L = m->prm.rollout_steps, B = m->prm.num_rays;
+    const uint64_t KB = (uint64_t)K * B, per_it = (uint64_t)K * (1 + L) * B;
+    int rc = RL_OK;
+    for (int t = 0; t < n && rc == RL_OK; ++t) {
+        const long it = it0 + t;
+        const uint64_t off = base + KB + (uint64_t)it * per_it;
+        hipLaunchKernelGGL(mcts_select_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, (int)it);
+        if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_select_kernel launch failed");
+        if (!rc) rc = mcts_act(m, b, off, 0, st);
+        if (!rc) {
+            hipLaunchKernelGGL(rollout_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, (const double *)m->cstate.p,
+                               (const double *)m->actions.p, K, L, m->prm.action_every, m->prm.dt, (float *)m->rposes.p,
+                               (double *)nullptr, (double *)m->vel.p);
+            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "rollout_kernel launch failed");
+        }
+        if (!rc) {
+            m->h->ray_offset = off + KB;
+            rc = crash_groups_device(m->h, (const float *)m->rposes.p, K, L, m->prm.fov, B, (const double *)m->edge.p,
+                                     m->prm.crash_thresh, (int *)m->first.p, (float *)m->rranges.p, st);
+        }
+        if (!rc) {
+            hipLaunchKernelGGL(mcts_backup_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b);
+            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_backup_kernel launch failed");
+        }
+    }
+    return rc;
 }
 
 extern "C" int rl_mcts_run(rl_mcts *m, int n_iterations)
@@ -1287,30 +1322,7 @@ extern "C" int rl_mcts_run(rl_mcts *m, int n_iterations)
     HIPCHK(hipSetDevice(m->device));
     if ((rc = m->rranges.ensure((size_t)K * L * B * 4))) return rc;
     hipStream_t st = m->c->stream;
-    const MctsBufs b = mcts_bufs(m);
-    const uint64_t KB = (uint64_t)K * B, per_it = (uint64_t)K * (1 + L) * B;
-    for (int t = 0; t < n_iterations && rc == RL_OK; ++t) {
-        const long it = m->iters + t;
-        const uint64_t off = m->base + KB + (uint64_t)it * per_it;
-        hipLaunchKernelGGL(mcts_select_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, (int)it);
-        if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_select_kernel launch failed");
-        if (!rc) rc = mcts_act(m, off, 0, st);
-        if (!rc) {
-            hipLaunchKernelGGL(rollout_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, (const double *)m->cstate.p,
-                               (const double *)m->actions.p, K, L, m->prm.action_every, m->prm.dt, (float *)m->rposes.p,
-                               (double *)nullptr, (double *)m->vel.p);
-            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "rollout_kernel launch failed");
-        }
-        if (!rc) {
-            m->h->ray_offset = off + KB;
-            rc = crash_groups_device(m->h, (const float *)m->rposes.p, K, L, m->prm.fov, B, (const double *)m->edge.p,
-                                     m->prm.crash_thresh, (int *)m->first.p, (float *)m->rranges.p, st);
-        }
-        if (!rc) {
-            hipLaunchKernelGGL(mcts_backup_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b);
-            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_backup_kernel launch failed");
-        }
-    }
+    rc = mcts_iterations(m, mcts_bufs(m), m->base, m->iters, n_iterations, st);
     const hipError_t e = hipStreamSynchronize(st);
     if (!rc && e != hipSuccess) rc = fail(RL_ERR_HIP, "rl_mcts_run: %s", hipGetErrorString(e));
     if (rc) {
@@ -1318,6 +1330,92 @@ extern "C" int rl_mcts_run(rl_mcts *m, int n_iterations)
         return rc;
     }
     m->iters += n_iterations;
+    return RL_OK;
+}
+
+// The closed loop of scripts/mcts_driver.py:207-264 (contract: include/scanlib.h).  Everything goes up before
+// decision 0; between decisions the stream carries kernels only (mcts_advance_kernel ends one decision and writes
+// the next one's roots), and the host waits once, for the downloads.
+extern "C" int rl_mcts_drive(rl_mcts *m, const double *states_in, const double *recent_in, const uint64_t *seeds,
+                             int n_decisions, int n_iterations, int steps_per_decision, double steer_clip, int *first,
+                             double *states_out, double *recent_out, double *actions, int *visits,
+                             double *trace_states_or_null)
+{
+    if (!m || !states_in || !recent_in || !seeds || !first || !states_out || !recent_out ||
+        (n_decisions > 0 && (!actions || !visits)))
+        return fail(RL_ERR_INVALID, "rl_mcts_drive: null pointer");
+    if (n_decisions < 0) return fail(RL_ERR_INVALID, "rl_mcts_drive: n_decisions must be >= 0 (got %d)", n_decisions);
+    if (n_iterations < 1) return fail(RL_ERR_INVALID, "rl_mcts_drive: n_iterations must be >= 1 (got %d)", n_iterations);
+    if ((long)n_iterations + 1 > m->prm.max_nodes)
+        return fail(RL_ERR_INVALID, "rl_mcts_drive: %d iterations exceed max_nodes = %d", n_iterations, m->prm.max_nodes);
+    if (steps_per_decision < 1)
+        return fail(RL_ERR_INVALID, "rl_mcts_drive: steps_per_decision must be >= 1 (got %d)", steps_per_decision);
+    if (!(steer_clip >= 0.0)) return fail(RL_ERR_INVALID, "rl_mcts_drive: steer_clip must be >= 0 (0: no clamp)");
+    const int K = m->prm.n_trees, L = m->prm.rollout_steps, B = m->prm.num_rays, D = n_decisions, I = n_iterations;
+    int rc;
+    if ((rc = check_fan_args(m->h, K, m->prm.fov, B)) || (rc = check_fan_args(m->h, K * L, m->prm.fov, B))) return rc;
+    if (D == 0) {
+        for (int k = 0; k < K; ++k) first[k] = -1;
+        if (states_out != states_in) memmove(states_out, states_in, (size_t)K * 88);
+        if (recent_out != recent_in) memmove(recent_out, recent_in, (size_t)K * 8);
+        return RL_OK;
+    }
+    const size_t rows = (size_t)K * D;
+    MctsLock lk(m);
+    HIPCHK(hipSetDevice(m->device));
+    if ((rc = m->rranges.ensure((size_t)K * L * B * 4)) || (rc = m->root_crash.ensure((size_t)K * 4)) ||
+        (rc = m->dr_keys.ensure(rows * 4)) || (rc = m->dr_first.ensure((size_t)K * 4)) ||
+        (rc = m->dr_actions.ensure(rows * 8)) || (rc = m->dr_visits.ensure(rows * 4)) ||
+        (trace_states_or_null && (rc = m->dr_trace.ensure(rows * 88))))
+        return rc;
+    hipStream_t st = m->c->stream;
+    m->ready = false;
+    std::vector<uint32_t> keys(rows);                  // [D][K]: decision d's seed is seeds[k] + d mod 2^64
+    for (int d = 0; d < D; ++d)
+        for (int k = 0; k < K; ++k) {
+            const uint64_t s = seeds[k] + (uint64_t)d;
+            keys[(size_t)d * K + k] = (uint32_t)s ^ ((uint32_t)(s >> 32) * 0x85EBCA6Bu);     // np_statement.noise_key
+        }
+    double *d_states = (double *)m->roots.p, *d_recent = d_states + (size_t)K * 11;
+    HIPCHK(hipMemcpyAsync(m->dr_keys.p, keys.data(), rows * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_states, states_in, (size_t)K * 88, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_recent, recent_in, (size_t)K * 8, hipMemcpyHostToDevice, st));
+    MctsBufs b = mcts_bufs(m);
+    b.root_crash = (int *)m->root_crash.p;
+    const MctsDrive dv{d_states, d_recent, (int *)m->dr_first.p, (double *)m->dr_actions.p, (int *)m->dr_visits.p,
+                       trace_states_or_null ? (double *)m->dr_trace.p : nullptr, D, steps_per_decision, steer_clip};
+    const uint64_t stride = (uint64_t)K * B * (1 + (uint64_t)I * (1 + L));
+    hipLaunchKernelGGL(mcts_start_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, (const double *)d_states,
+                       (const double *)d_recent);
+    if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_start_kernel launch failed");
+    uint64_t base = lk.ov.ray_offset;
+    for (int d = 0; d < D && rc == RL_OK; ++d) {
+        base = lk.ov.ray_offset + (uint64_t)d * stride;
+        b.keys = (const uint32_t *)m->dr_keys.p + (size_t)d * K;
+        rc = mcts_act(m, b, base, 1, st);
+        if (!rc) rc = mcts_iterations(m, b, base, 0, I, st);
+        if (!rc) {
+            hipLaunchKernelGGL(mcts_advance_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, dv, d);
+            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_advance_kernel launch failed");
+        }
+    }
+    if (rc) {
+        (void)hipStreamSynchronize(st);                // nothing of this call is left in flight; the trees need a reset
+        return rc;
+    }
+    // the planner keeps the last decision's trees: its keys, ray offset and iteration count are that decision's
+    HIPCHK(hipMemcpyAsync(m->keys.p, b.keys, (size_t)K * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(first, m->dr_first.p, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(states_out, d_states, (size_t)K * 88, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(recent_out, d_recent, (size_t)K * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(actions, m->dr_actions.p, rows * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(visits, m->dr_visits.p, rows * 4, hipMemcpyDeviceToHost, st));
+    if (trace_states_or_null)
+        HIPCHK(hipMemcpyAsync(trace_states_or_null, m->dr_trace.p, rows * 88, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    m->base = base;
+    m->iters = I;
+    m->ready = true;
     return RL_OK;
 }
 

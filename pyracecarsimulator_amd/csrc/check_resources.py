@@ -35,6 +35,7 @@ BOUNDS = [
     ("scan::mcts_act_kernel<", {"scratch": 0}),
     ("scan::mcts_backup_kernel", {"scratch": 0}),
     ("scan::mcts_best_kernel", {"scratch": 0}),
+    ("scan::mcts_advance_kernel", {"scratch": 0}),
     ("scan::mcts_ucb_probe_kernel", {"scratch": 0}),
     # batched races: the outline raster, and the race scan's march with the other cars' cells folded into each sample
     ("scan::outline_cells_kernel", {"scratch": 0}),

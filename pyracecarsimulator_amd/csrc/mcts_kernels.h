@@ -9,6 +9,9 @@
 //   5. mcts_backup_kernel (one lane per tree): the reward sum in NumPy's pairwise order, or crash_pen, and the
 //      repeated adds of Node.propagate at every recursion level.
 // mcts_start_kernel writes the roots at reset; mcts_best_kernel answers MCTS.mcts (:126-131).
+// The closed loop (rl_mcts_drive; scripts/mcts_driver.py:207-264) adds mcts_advance_kernel between two decisions (one
+// lane per car): the car's crash test from the root act's ballot, the best root child, the car's steps with that
+// action, the per-decision outputs and the next decision's root.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -48,6 +51,19 @@ struct MctsBufs {
     const float *mlp;                  // [K] the network's answers (NN)
     const double *vel;                 // [K][L] roll-out velocities
     const int *first;                  // [K] roll-out crash indices
+    int *root_crash;                   // [K] or null: isCrashed(root scan) >= 0, kept by the root act (rl_mcts_drive)
+};
+
+// rl_mcts_drive's per-car arrays (D decisions)
+struct MctsDrive {
+    double *state;                     // [K][11] the cars' current states
+    double *recent;                    // [K] their recent actions
+    int *first;                        // [K] crash decision, -(D+1) while alive
+    double *actions;                   // [K][D] best root action of every decision (NaN once crashed)
+    int *visits;                       // [K][D] its visits (-1 once crashed)
+    double *trace;                     // [K][D][11] or null: the state every decision was planned from
+    int D, S;                          // decisions; car steps per decision
+    double steer_clip;                 // > 0: the next recent action is the best action clamped to +-steer_clip
 };
 
 // Philox-2x32-10 of counter (d, i) under `key` (scan_device.h gauss_noise's rounds), as a double in [0, 1):
@@ -115,13 +131,10 @@ __device__ inline double mcts_pairwise_sum(const double *a, int n)
     return 0.0 + mcts_pairwise<3>(a, n);      // depth 3: exact up to ~920 elements (MCTS_MAX_STEPS = 512)
 }
 
-// reset: node 0 of every tree is the caller's state and recent action (visits 1, never terminal); its lidar pose goes
-// to the act-scan buffer so that the root scan and answer come from the ordinary act launches
-__global__ __launch_bounds__(64) void mcts_start_kernel(MctsParams p, MctsBufs b, const double *__restrict__ states,
-                                                        const double *__restrict__ actions)
+// node 0 of tree k is the state `state` (getState layout) and the recent action `action` (visits 1, never terminal);
+// its lidar pose goes to the act-scan buffer so that the root scan and answer come from the ordinary act launches
+__device__ inline void mcts_write_root(const MctsParams &p, const MctsBufs &b, int k, const double *state, double action)
 {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= p.K) return;
     const size_t n = (size_t)k * p.N;
     b.parent[n] = -1;
     b.first_child[n] = -1;
@@ -133,15 +146,24 @@ __global__ __launch_bounds__(64) void mcts_start_kernel(MctsParams p, MctsBufs b
     b.terminal[n] = 0;
     b.crash[n] = -1;
     b.reward[n] = 0.0;
-    b.action[n] = actions[k];
+    b.action[n] = action;
     b.answer[n] = __builtin_nanf("");
-    const CarState cs = drive_load_state(states + 11 * (size_t)k);
+    const CarState cs = drive_load_state(state);
     drive_store_state(cs, b.state + 11 * n);
     car_scan_pose(cs, p.scan_dist_to_base, b.pose + 3 * n);
     car_scan_pose(cs, p.scan_dist_to_base, b.cpose + 3 * k);
     b.n_nodes[k] = 1;
     b.child[k] = 0;
     b.exp_term[k] = 0;
+}
+
+// reset: the roots are the caller's states and recent actions
+__global__ __launch_bounds__(64) void mcts_start_kernel(MctsParams p, MctsBufs b, const double *__restrict__ states,
+                                                        const double *__restrict__ actions)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= p.K) return;
+    mcts_write_root(p, b, k, states + 11 * (size_t)k, actions[k]);
 }
 
 // iteration `it` (counted from reset) of tree k: the descent of mctsIteration with its visits, then the new child
@@ -257,6 +279,7 @@ __global__ __launch_bounds__(64 * MCTS_TREES) void mcts_act_kernel(MctsParams p,
         const size_t n = (size_t)k * p.N + c;
         b.answer[n] = ans;
         b.terminal[n] = root ? 0 : (crashed ? 1 : 0);
+        if (root && b.root_crash) b.root_crash[k] = crashed ? 1 : 0;
     }
 }
 
@@ -289,22 +312,61 @@ __global__ __launch_bounds__(64) void mcts_backup_kernel(MctsParams p, MctsBufs 
 }
 
 // MCTS.mcts's answer (:125-131): the root child with the most visits, the first of equals (NaN / -1 without children)
-__global__ __launch_bounds__(64) void mcts_best_kernel(MctsParams p, MctsBufs b, double *actions, int *visits,
-                                                       int *n_nodes)
+__device__ inline void mcts_best_child(const MctsBufs &b, size_t t0, double &a, int &v)
 {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= p.K) return;
-    const size_t t0 = (size_t)k * p.N;
-    double a = __builtin_nan("");
-    int v = -1;
+    a = __builtin_nan("");
+    v = -1;
     for (int c = b.first_child[t0]; c >= 0; c = b.next_sibling[t0 + c])
         if (b.visits[t0 + c] > v) {
             v = b.visits[t0 + c];
             a = b.action[t0 + c];
         }
+}
+
+__global__ __launch_bounds__(64) void mcts_best_kernel(MctsParams p, MctsBufs b, double *actions, int *visits,
+                                                       int *n_nodes)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= p.K) return;
+    double a;
+    int v;
+    mcts_best_child(b, (size_t)k * p.N, a, v);
     actions[k] = a;
     visits[k] = v;
     n_nodes[k] = b.n_nodes[k];
+}
+
+// the end of decision d of the closed loop (mcts_driver.py:207-264), one lane per car.  A car whose root scan crashed
+// (Car::isCrashed >= 0, drive_tick_kernel's convention) freezes at d: first = d, NaN / -1 rows from d on, its state and
+// recent action stay.  A live car takes the best root child's raw action for S steps of Car::control + updatePosition
+// (car_step, as rollout_kernel runs it; mcts_driver.py:249), and its next recent action is that action clamped to
+// +-steer_clip (:254).  Then, unless d is the last decision, node 0 becomes the car's state and recent action: the
+// next decision's reset.  A frozen car's tree is re-rooted at its frozen state and searched with the others.
+__global__ __launch_bounds__(64) void mcts_advance_kernel(MctsParams p, MctsBufs b, MctsDrive dv, int d)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= p.K) return;
+    double *s = dv.state + 11 * (size_t)k;
+    int f = d == 0 ? -(dv.D + 1) : dv.first[k];
+    if (f < 0 && b.root_crash[k]) f = d;
+    const size_t row = (size_t)k * dv.D + d;
+    double a = __builtin_nan("");
+    int v = -1;
+    if (f < 0) {
+        mcts_best_child(b, (size_t)k * p.N, a, v);
+        if (dv.trace)
+            for (int j = 0; j < 11; ++j) dv.trace[11 * row + j] = s[j];
+        CarState cs = drive_load_state(s);
+        for (int i = 0; i < dv.S; ++i) car_step(p.P, cs, p.speed, a, p.dt);
+        drive_store_state(cs, s);
+        dv.recent[k] = dv.steer_clip > 0.0 ? clampd(a, -dv.steer_clip, dv.steer_clip) : a;
+    } else if (dv.trace) {
+        for (int j = 0; j < 11; ++j) dv.trace[11 * row + j] = __builtin_nan("");
+    }
+    dv.first[k] = f;
+    dv.actions[row] = a;
+    dv.visits[row] = v;
+    if (d + 1 < dv.D) mcts_write_root(p, b, k, s, dv.recent[k]);
 }
 
 // rl_mcts_probe_ucb: the device UCB of n (reward, visits, sum) triples

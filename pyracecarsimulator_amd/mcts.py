@@ -4,6 +4,10 @@
 iteration, each iteration one batched act (step, scan, crash test, expansion answer) and one batched roll-out,
 nothing leaving the device between iterations.  The trees are the reference's bit for bit (tests/mcts_statement.py).
 
+``MCTSPlanner.drive`` closes the loop of scripts/mcts_driver.py:207-264 for the K cars (``rl_mcts_drive``): at every
+decision a fresh tree from the car's state, the search, the most visited root action, the car's steps with it — all
+decisions enqueued at once, nothing leaving the device in between.
+
 ``MCTS`` is a drop-in for the reference class (scripts/mcts.py:83-148) on a ``RacecarSimulator``: ``mcts()`` plans
 from the simulator's state and returns the most visited root action; ``root`` holds the tree read back from the
 device as ``Node`` objects.
@@ -21,6 +25,61 @@ from ._lib import f32p, f64p, i32p
 SOURCES = {"fg": _lib.RL_MCTS_FG, "nn": _lib.RL_MCTS_NN, "random": _lib.RL_MCTS_RANDOM}
 TREE_FIELDS = ("parent", "first_child", "next_sibling", "n_children", "visits", "child_visits", "reward", "action",
                "terminal", "state", "scan_pose", "answer", "crash")
+
+
+# ---------------------------------------------------------------- the decision loop's host-side definitions
+def drive_seeds(seeds, d):
+    """The seeds of decision ``d``: (seeds + d) mod 2^64 (the tree's Philox key is ``noise_key`` of it)."""
+    s = np.asarray(seeds, np.uint64)
+    return (np.atleast_1d(s) + np.uint64(int(d) % (1 << 64))).reshape(s.shape)      # (uint64 array addition wraps)
+
+
+def drive_stride(n_trees, num_rays, n_iterations, rollout_steps):
+    """Rays one decision consumes, K B (1 + I (1 + L)): the root scans, then per iteration the act scans and the
+    roll-out scans of every tree.  Decision d's ray offset is the handle's offset at entry + d * stride."""
+    return int(n_trees) * int(num_rays) * (1 + int(n_iterations) * (1 + int(rollout_steps)))
+
+
+def drive_recent(action, steer_clip):
+    """The recent action after a decision (mcts_driver.py:254): the raw best action clamped to +-steer_clip, or
+    the raw action when steer_clip is None.  The car itself is driven with the raw action (:249)."""
+    a = np.asarray(action, np.float64)
+    return a.copy() if steer_clip is None else np.clip(a, -float(steer_clip), float(steer_clip))
+
+
+def drive_dead_rows(first, n_decisions):
+    """Which (car, decision) rows of ``drive``'s outputs a crash blanks, bool (K, D): a car with crash decision
+    ``first`` >= 0 has actions NaN, visits -1 and trace rows NaN from that decision on; ``first`` = -(D+1): never."""
+    first = np.asarray(first)
+    return (first[:, None] >= 0) & (np.arange(int(n_decisions))[None, :] >= first[:, None])
+
+
+def drive_args(n_trees, states, recent_actions, seeds, n_decisions, n_iterations, steps_per_decision, steer_clip):
+    """``MCTSPlanner.drive``'s arguments checked and laid out for ``rl_mcts_drive`` (no library call): states float64
+    (K, 11), recent actions scalar or (K,), seeds integers >= 0 scalar or (K,); returns (states, recent, seeds, D, I,
+    S, clip) with clip = 0.0 for ``steer_clip=None``."""
+    K = int(n_trees)
+    st = np.asarray(states)
+    if st.dtype != np.float64 or st.shape != (K, 11):
+        raise ValueError("states must be float64 (%d, 11)" % K)
+    ac = np.asarray(recent_actions)
+    if ac.dtype.kind not in "fiu" or ac.shape not in ((), (K,)):
+        raise ValueError("recent_actions must be a real scalar or (%d,)" % K)
+    sd = np.asarray(seeds)
+    if sd.dtype.kind not in "iu" or sd.shape not in ((), (K,)):
+        raise ValueError("seeds must be an integer scalar or (%d,)" % K)
+    if sd.dtype.kind == "i" and (sd < 0).any():
+        raise ValueError("seeds must be >= 0")
+    D, I, S = int(n_decisions), int(n_iterations), int(steps_per_decision)
+    if (D, I, S) != (n_decisions, n_iterations, steps_per_decision):
+        raise ValueError("n_decisions, n_iterations and steps_per_decision must be integers")
+    if D < 0 or I < 1 or S < 1:
+        raise ValueError("n_decisions >= 0, n_iterations >= 1 and steps_per_decision >= 1 required")
+    clip = 0.0 if steer_clip is None else float(steer_clip)
+    if steer_clip is not None and not clip > 0:
+        raise ValueError("steer_clip must be None or > 0")
+    return (np.ascontiguousarray(st), np.ascontiguousarray(np.broadcast_to(ac.astype(np.float64), (K,))),
+            np.ascontiguousarray(np.broadcast_to(sd.astype(np.uint64), (K,))), D, I, S, clip)
 
 
 class MCTSPlanner:
@@ -88,6 +147,28 @@ class MCTSPlanner:
             ptr("action", f64p), ptr("terminal", i32p), ptr("state", f64p), ptr("scan_pose", f32p),
             ptr("answer", f32p), ptr("crash", i32p), C.byref(n)))
         return {f: a[:n.value] for f, a in out.items()}
+
+    def drive(self, states, recent_actions, seeds, n_decisions, n_iterations, steps_per_decision=1, steer_clip=None,
+              trace=False):
+        """The closed loop of scripts/mcts_driver.py:207-264 for the K cars (``rl_mcts_drive``): ``n_decisions``
+        times a fresh tree from the car's state with its recent action at the root and seed ``seeds + d``,
+        ``n_iterations`` iterations, the most visited root action, ``steps_per_decision`` car steps at the planner's
+        speed with it; the next recent action is that action clamped to +-``steer_clip`` (None: raw).  A car whose
+        root scan crashes at decision d freezes there.  Returns (first crash decision or -(D+1) int32 (K,), final
+        states (K, 11), recent actions (K,), best actions float64 (K, D) — NaN from the crash on —, their visits
+        int32 (K, D) — -1 from the crash on) and with ``trace=True`` also the states every decision was planned
+        from, (K, D, 11).  The planner keeps the last decision's trees (``read_tree``, ``best``)."""
+        K = self.n_trees
+        st, ac, sd, D, I, S, clip = drive_args(K, states, recent_actions, seeds, n_decisions, n_iterations,
+                                               steps_per_decision, steer_clip)
+        first, out, recent = np.empty(K, np.int32), np.empty((K, 11)), np.empty(K)
+        actions, visits = np.empty((K, D)), np.empty((K, D), np.int32)
+        tr = np.empty((K, D, 11)) if trace else None
+        _lib.check(_lib.lib().rl_mcts_drive(
+            self._h, st.ctypes.data_as(f64p), ac.ctypes.data_as(f64p), sd.ctypes.data_as(C.POINTER(C.c_uint64)), D, I,
+            S, clip, first.ctypes.data_as(i32p), out.ctypes.data_as(f64p), recent.ctypes.data_as(f64p),
+            actions.ctypes.data_as(f64p), visits.ctypes.data_as(i32p), tr.ctypes.data_as(f64p) if trace else None))
+        return (first, out, recent, actions, visits) + ((tr,) if trace else ())
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

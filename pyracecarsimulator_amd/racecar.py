@@ -15,7 +15,8 @@ on the GPU:
 ``CarBatch.rollout_check`` chains roll-outs -> poses -> scan -> per-roll-out crash index on the
 device (poses and ranges never cross PCIe).  ``CarBatch.drive_followgap`` closes the loop: each tick's
 steering angle is FollowGap's answer to that tick's scan, all on the device.  ``CarBatch.plan_mcts`` runs
-scripts/mcts.py's tree search for many trees at once on the device (``mcts.MCTSPlanner``).
+scripts/mcts.py's tree search for many trees at once on the device (``mcts.MCTSPlanner``), ``CarBatch.drive_mcts``
+scripts/mcts_driver.py's closed loop of it: every car replans at every decision.
 ``CarBatch.race_followgap`` runs many races of up to 8 cars at once, each car's scan seeing the other cars of its
 race (scripts/two_player/); ``CarBatch.outline_cells`` gives the canonical outline cells of the cars.
 """
@@ -215,6 +216,33 @@ class CarBatch:
         finally:
             pl.close()
         return res
+
+    def drive_mcts(self, method, followgap_or_policy, states, n_decisions, n_iterations, seeds, fov, num_rays, edge,
+                   crash_thresh, recent_actions=0.0, source=None, steps_per_decision=1, steer_clip=None,
+                   rollout_steps=200, action_every=10, speed=2.0, dt=0.01, scan_dist_to_base=0.275, C_ucb=0.5,
+                   crash_pen=-10.0, uni_dev=0.05, trace=False):
+        """scripts/mcts_driver.py's closed loop for K cars at once (``rl_mcts_drive``): every car replans at each of
+        ``n_decisions`` decisions (a fresh tree of ``n_iterations`` iterations from its state) and takes
+        ``steps_per_decision`` steps with the most visited root action.  Source and handles as ``plan_mcts``; states
+        float64 (K, 11), recent_actions scalar or (K,), seeds integers (K,).  Returns ``MCTSPlanner.drive``'s tuple."""
+        from .mcts import MCTSPlanner
+        from .policy import Policy
+        if source is None:
+            source = "random" if followgap_or_policy is None else ("nn" if isinstance(followgap_or_policy, Policy)
+                                                                   else "fg")
+        states = np.asarray(states)
+        if states.dtype != np.float64 or states.ndim != 2 or states.shape[1] != 11:
+            raise ValueError("states must be float64 (K, 11)")
+        pl = MCTSPlanner(self, method, states.shape[0], int(n_iterations) + 1, fov, num_rays, edge, crash_thresh,
+                         source=source, followgap=followgap_or_policy if source == "fg" else None,
+                         policy=followgap_or_policy if source == "nn" else None, rollout_steps=rollout_steps,
+                         action_every=action_every, speed=speed, dt=dt, scan_dist_to_base=scan_dist_to_base,
+                         C_ucb=C_ucb, crash_pen=crash_pen, uni_dev=uni_dev)
+        try:
+            return pl.drive(states, recent_actions, seeds, n_decisions, n_iterations,
+                            steps_per_decision=steps_per_decision, steer_clip=steer_clip, trace=trace)
+        finally:
+            pl.close()
 
     def _drive(self, fn, method, source, counts, after_thresh, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
                scan_dist_to_base, dt, steer0, trace):

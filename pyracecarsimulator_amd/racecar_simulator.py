@@ -186,6 +186,18 @@ class RacecarSimulator:
                                      self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
                                      scan_dist_to_base=self.scan_dist_to_base, steer_clip=steer_clip)
 
+    def _mcts_source(self, source, policy):
+        if source == "fg":
+            if self._followgap is None:
+                from .followgap import PyFollowGap
+                self._followgap = PyFollowGap(10, 15.0, self.max_steer_ang, 0.004, device=self._device)
+            return self._followgap
+        if source == "nn":
+            if policy is None:
+                raise ValueError("source 'nn' needs a policy")
+            return policy
+        return None
+
     def planMCTSMany(self, states, n_iterations, seeds=None, source="fg", policy=None, root_actions=0.0):
         """scripts/mcts.py's search from each of R start states at once (one tree each, ``n_iterations`` iterations,
         roll-outs of ``batch_size`` steps) on this simulator's range method, edge table and ttc_thresh; ``source``
@@ -194,21 +206,29 @@ class RacecarSimulator:
         states = np.asarray(states, dtype=np.float64).reshape(-1, 11)
         R = states.shape[0]
         seeds = np.arange(R, dtype=np.uint64) if seeds is None else np.asarray(seeds, np.uint64)
-        if source == "fg":
-            if self._followgap is None:
-                from .followgap import PyFollowGap
-                self._followgap = PyFollowGap(10, 15.0, self.max_steer_ang, 0.004, device=self._device)
-            handle = self._followgap
-        elif source == "nn":
-            if policy is None:
-                raise ValueError("source 'nn' needs a policy")
-            handle = policy
-        else:
-            handle = None
+        handle = self._mcts_source(source, policy)
         return self.car.plan_mcts(self.scan_simulator.scan_method, handle, states, n_iterations, seeds,
                                   self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
                                   root_actions=root_actions, source=source, rollout_steps=self.batch_size,
                                   scan_dist_to_base=self.scan_dist_to_base)
+
+    def driveMCTSMany(self, states, n_decisions, n_iterations, seeds=None, source="fg", policy=None, steer_clip=0.4189,
+                      steps_per_decision=1, recent_actions=0.0):
+        """scripts/mcts_driver.py's action callback (:207-264) for R cars at once: at each of ``n_decisions``
+        decisions every car plans a fresh tree from its state (``planMCTSMany``'s search and source, seed
+        ``seeds + d``), then takes ``steps_per_decision`` steps with the most visited root action; the recent action
+        at the next root is that action clamped to +-``steer_clip`` (the driver's 0.4189; None: raw).  Returns
+        ``CarBatch.drive_mcts``'s (first crash decision or -(n_decisions+1), final states, recent actions, actions
+        (R, n_decisions), visits (R, n_decisions)); nothing leaves the GPU between decisions."""
+        states = np.asarray(states, dtype=np.float64).reshape(-1, 11)
+        R = states.shape[0]
+        seeds = np.arange(R, dtype=np.uint64) if seeds is None else np.asarray(seeds, np.uint64)
+        handle = self._mcts_source(source, policy)
+        return self.car.drive_mcts(self.scan_simulator.scan_method, handle, states, n_decisions, n_iterations, seeds,
+                                   self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
+                                   recent_actions=recent_actions, source=source, steps_per_decision=steps_per_decision,
+                                   steer_clip=steer_clip, rollout_steps=self.batch_size,
+                                   scan_dist_to_base=self.scan_dist_to_base)
 
     def stop(self):
         state = self.getState()
