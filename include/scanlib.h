@@ -375,6 +375,69 @@ int rl_car_race_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double
                           int *first_crashed, double *states_out_or_null, double *velocities_or_null,
                           float *steers_or_null, float *scan_poses_or_null, double *states_trace_or_null);
 
+/* ---- particle-filter weights --------------------------------------------------------------------
+ * The calls range_libc was written for, Monte-Carlo localisation: every particle casts the SAME n_angles beams and
+ * is weighted by a sensor model.  range_libc's source is not on the reference mount; what is said about upstream here
+ * is recollection ([UPSTREAM-RECALL]) of RangeLibc.pyx: calc_range_repeat_angles, set_sensor_model,
+ * eval_sensor_model, calc_range_repeat_angles_eval_sensor_model.  The contract below is what this library pins.
+ *
+ * Ray layout.  Ray j of particle p is outs[p * n_angles + j], cast from the world pose ins_p3 row p (x, y, theta) at
+ * heading theta_p + angles[j]; angles: n_angles float32, shared by all particles [UPSTREAM-RECALL:
+ * numpy_calc_range_angles].
+ *
+ * Arithmetic.  Each kind keeps the arithmetic of its fan with the fan's alpha_j replaced by angles[j]:
+ *   RL_RM / RL_RM_GPU, variants 0 and 1 (canonical): (sa, ca) = det_sincosf(angles[j]), (st, ct) = det_sincosf(thg),
+ *     dx = fma(ct, ca, -(st sa)), dy = fma(st, ca, ct sa), then the canonical march (rm_march);
+ *   RL_RM / RL_RM_GPU, variant 3 (literal): the upstream-literal cast at theta_p + angles[j], the sum rounded to
+ *     float32 once;
+ *   RL_CDDT: the CDDT query at thg + angles[j];   RL_GIANT_LUT: the table bin of thg + angles[j];
+ *   RL_BRESENHAM and variant 2: RL_ERR_UNSUPPORTED.
+ * Fan equivalence — the pin to the oracle: a repeat-angle scan is bit-identical to rl_calc_range_fan of the same poses
+ * when angles[j] = fma((float)j, inc, amin) for the canonical and table kinds, and angles[j] = amin + (float)j * inc,
+ * each operation rounded to float32, for the literal kind (amin = -0.5f fov, inc = fov / (float)num_rays) — ranges,
+ * and hit cells / steps where given (RL_RM / RL_RM_GPU only; RL_ERR_UNSUPPORTED for the table kinds).
+ * The handle's step coefficient, max range, variant and noise apply; the noise key is the global ray id
+ * h.ray_offset + p * n_angles + j.  K1b planner options (slots, code map, tiles, ...) do not apply and are ignored,
+ * as for the race scan; the GiantLUT / CDDT debug bits (option lut_debug) are ignored too.
+ *
+ * Sensor model [UPSTREAM-RECALL: eval_sensor_model].  rl_set_sensor_model copies `table`, width x width doubles,
+ * row = observed bin, column = expected bin, to h's device (synchronous).  Setting a table again replaces and frees
+ * the old one (after the device has drained); the table dies with the method handle.  For a float32 value v in metres
+ *   bin(v) = (int) fminf(fmaxf(v * inv_res, 0.0f), (float)(width - 1)),
+ * inv_res the map's float32 (float)(1.0 / res) that the world -> grid transform uses.  NaN gives bin 0 (fmaxf returns
+ * its other argument); upstream's behaviour there is undefined.  The weight of particle p:
+ *   w = 1.0;  for j = 0 ... n_angles - 1 in ascending order:  w *= table[bin(obs[j]) * width + bin(range[p, j])]
+ * — each product its own IEEE double rounding, no tree, no log domain.  obs: n_angles float32 (the observed scan);
+ * rl_eval_sensor_model reads ranges laid out as above (n_particles * n_angles float32) and writes n_particles doubles.
+ * rl_calc_range_repeat_angles_eval_sensor_model is the scan and the evaluation in one call: it uses exactly the float32
+ * value the unfused scan would have stored (range_px * res, plus noise if set), so fused and unfused weights are the
+ * same bits.  Which path each kind takes: RL_RM / RL_RM_GPU run ONE kernel (pf_weight_kernel: march, table lookup, the
+ * factors parked in LDS, one lane per particle forming the product; the only global write is 8 B per particle);
+ * RL_CDDT / RL_GIANT_LUT run the repeat-angle scan into scratch owned by the handle and then the evaluation kernel.
+ * rl_method_last_plan is not touched by these calls.
+ *
+ * The *_device forms take device pointers and only enqueue on `hip_stream` (NULL: the default stream); the others
+ * take host pointers and are synchronous.
+ * Errors (the handle stays usable).  RL_ERR_INVALID: null pointers, n_particles < 0, n_angles outside [1, 2048],
+ * n_particles * n_angles >= 2^31, width outside [2, 2048], evaluating before a table is set, multi-device handles
+ * (use rl_method_replica).  n_particles = 0 does nothing.                                                              */
+int rl_calc_range_repeat_angles(rl_method *h, const float *ins_p3, int n_particles, const float *angles, int n_angles,
+                                float *outs, int32_t *hit_cells_or_null, uint16_t *steps_or_null);
+int rl_calc_range_repeat_angles_device(rl_method *h, const float *d_ins_p3, int n_particles, const float *d_angles,
+                                       int n_angles, float *d_outs, int32_t *d_hit_cells_or_null,
+                                       uint16_t *d_steps_or_null, void *hip_stream);
+int rl_set_sensor_model(rl_method *h, const double *table, int width);
+int rl_eval_sensor_model(rl_method *h, const float *obs, const float *ranges, int n_angles, int n_particles,
+                         double *weights);
+int rl_eval_sensor_model_device(rl_method *h, const float *d_obs, const float *d_ranges, int n_angles, int n_particles,
+                                double *d_weights, void *hip_stream);
+int rl_calc_range_repeat_angles_eval_sensor_model(rl_method *h, const float *ins_p3, int n_particles,
+                                                  const float *angles, const float *obs, int n_angles,
+                                                  double *weights);
+int rl_calc_range_repeat_angles_eval_sensor_model_device(rl_method *h, const float *d_ins_p3, int n_particles,
+                                                         const float *d_angles, const float *d_obs, int n_angles,
+                                                         double *d_weights, void *hip_stream);
+
 /* ---- the steering policy network ---------------------------------------------------------------
  * The reference's second steering source (scripts/policy.py:17-33, Policy.predict_action; driven at
  * scripts/policy_driver.py:30-49 and used by MCTS at scripts/mcts.py:252-256): a dense ReLU chain over the

@@ -96,6 +96,16 @@ SYMBOLS = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rl_calc_range_many_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                             C.c_void_p]),
+    "rl_calc_range_repeat_angles": (C.c_int, [C.c_void_p, f32p, C.c_int, f32p, C.c_int, f32p, i32p, u16p]),
+    "rl_calc_range_repeat_angles_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rl_set_sensor_model": (C.c_int, [C.c_void_p, f64p, C.c_int]),
+    "rl_eval_sensor_model": (C.c_int, [C.c_void_p, f32p, f32p, C.c_int, C.c_int, f64p]),
+    "rl_eval_sensor_model_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                              C.c_void_p]),
+    "rl_calc_range_repeat_angles_eval_sensor_model": (C.c_int, [C.c_void_p, f32p, C.c_int, f32p, f32p, C.c_int, f64p]),
+    "rl_calc_range_repeat_angles_eval_sensor_model_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "rl_set_noise": (C.c_int, [C.c_void_p, C.c_float, C.c_uint64, C.c_uint64]),
     "rl_check_collision_many": (C.c_int, [C.c_void_p, f32p, C.c_int, C.c_float, C.c_int, f64p,
                                           C.c_double, C.POINTER(C.c_int), f32p]),

@@ -7,6 +7,7 @@
 #include "abi_internal.h"
 #include "scan_kernels.h"
 #include "crash_kernels.h"
+#include "pf_kernels.h"
 #include "launch_plan.h"
 
 #include <array>
@@ -101,6 +102,8 @@ extern "C" void rl_method_destroy(rl_method *h)
     h->edge.release();
     h->flag.release();
     h->cars.release();
+    for (DevBuf *b : {&h->pf_ang, &h->pf_obs, &h->pf_w}) b->release();
+    if (h->sensor) (void)hipFree(h->sensor);
     if (h->pin) (void)hipHostFree(h->pin);
     if (h->pin_flag) (void)hipHostFree(h->pin_flag);
     for (LaunchCtx &c : h->ctx) c.release();
@@ -218,6 +221,7 @@ static const OptionRow OPTIONS[] = {
     {"pinned_max_rays", nullptr, &rl_method::pinned_max_rays, [](int v) { return std::max(v, 0); }},
     {"direct_max_rays", nullptr, &rl_method::direct_max_rays, [](int v) { return std::max(v, 0); }},
     {"overlap_min_rays", nullptr, &rl_method::overlap_min_rays, [](int v) { return std::max(v, 0); }},
+    {"pf_block", nullptr, &rl_method::pf_block, [](int v) { return clamp_int(v, 0, PF_WG); }},
     // (a power of two in [128, CDDT_LDS_SORT]: the bitonic network pads to one)
     {"cddt_lds_sort", nullptr, &rl_method::cddt_lds_sort, [](int v) {
          int p = 128;
@@ -1606,6 +1610,269 @@ int rays_host(rl_method *h, const float *ins, float *outs, int n)
                           h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return RL_OK;
+}
+
+// ------------------------------------------------------------------------------
+// particle-filter weights (include/scanlib.h "particle-filter weights"; kernels: pf_kernels.h)
+// ------------------------------------------------------------------------------
+static int check_pf_shape(const rl_method *h, const char *fn, int n_particles, int n_angles)
+{
+    if (!h) return fail(RL_ERR_INVALID, "%s: null method handle", fn);
+    if (!h->reps.empty()) return fail(RL_ERR_INVALID, "%s: multi-device handles are not served (call it on rl_method_replica(h, i))", fn);
+    if (n_particles < 0) return fail(RL_ERR_INVALID, "%s: n_particles must be >= 0", fn);
+    if (n_angles < 1 || n_angles > PF_MAX_ANGLES)
+        return fail(RL_ERR_INVALID, "%s: n_angles must be in [1, %d] (got %d)", fn, PF_MAX_ANGLES, n_angles);
+    if ((long)n_particles * n_angles > (long)INT_MAX)
+        return fail(RL_ERR_INVALID, "%s: n_particles * n_angles must stay below 2^31", fn);
+    return RL_OK;
+}
+
+// which arithmetic the handle's kind and variant cast a repeat-angle ray with (PF_* of pf_kernels.h)
+static int pf_kind_of(const rl_method *h, int *kind)
+{
+    if (h->kind == RL_CDDT || h->kind == RL_GIANT_LUT) {
+        *kind = h->kind == RL_CDDT ? PF_CDDT : PF_LUT;
+        return RL_OK;
+    }
+    if (h->kind != RL_RM && h->kind != RL_RM_GPU)
+        return fail(RL_ERR_UNSUPPORTED, "repeat-angle scans are not served by Bresenham's line");
+    if (h->opt.variant == 2) return fail(RL_ERR_UNSUPPORTED, "repeat-angle scans need variant 0, 1 or 3 (not the occupancy window)");
+    *kind = h->opt.variant == 3 ? PF_RM_LITERAL : PF_RM;
+    return RL_OK;
+}
+
+static PfParams make_pf(const rl_method *h, int n_particles, int n_angles)
+{
+    // tiles of about PF_TILE_RAYS rays when there are enough particles for four tiles per CU, smaller ones down to one
+    // pass of the workgroup otherwise (a 4000-particle update still fills the device); option pf_block forces a size
+    int block = pf_block(n_particles, n_angles);
+    const int spread = (int)(((long)n_particles + 4L * h->map->n_cu - 1) / (4L * h->map->n_cu));
+    block = std::max(std::max(1, PF_WG / n_angles), std::min(block, spread));
+    if (h->pf_block > 0) block = h->pf_block;
+    block = std::max(1, std::min(std::min(block, PF_WG), std::max(n_particles, 1)));
+    while (block > 1 && pf_lds_bytes(block, n_angles) > 65536) --block;
+    return PfParams{n_particles, n_angles, block, h->sensor, h->sensor_w, (float)(h->sensor_w - 1)};
+}
+
+#define PF_ANGLES(K, A) hipLaunchKernelGGL((pf_angles_kernel<K, A>), dim3(grid), dim3(PF_WG), 0, stream, m->mp, f, lt, h->cdp, \
+                                           h->lp, d_poses, d_angles, n, d_out, d_hits, d_steps)
+static int launch_pf_angles(rl_method *h, int kind, const float *d_poses, int n_particles, const float *d_angles,
+                            int n_angles, float *d_out, int32_t *d_hits, uint16_t *d_steps, hipStream_t stream)
+{
+    const rl_map *m = h->map;
+    const bool aux = d_hits || d_steps;
+    if (aux && (kind == PF_CDDT || kind == PF_LUT))
+        return fail(RL_ERR_UNSUPPORTED, "hit cells / step counts exist only for the ray-marching methods");
+    int rc;
+    if (kind == PF_LUT && (rc = ensure_lut(h, stream))) return rc;
+    if (kind == PF_CDDT && (rc = ensure_cddt(h, stream))) return rc;
+    const FanParams f = make_fan(h, n_particles, 0.0f, n_angles);
+    const LiteralParams lt = make_literal(m);
+    const long n = (long)n_particles * n_angles;
+    const int grid = (int)std::max(1L, std::min((n + PF_WG - 1) / PF_WG, (long)m->n_cu * 16));
+    switch (kind) {
+    case PF_RM:
+        if (aux) PF_ANGLES(PF_RM, true); else PF_ANGLES(PF_RM, false);
+        break;
+    case PF_RM_LITERAL:
+        if (aux) PF_ANGLES(PF_RM_LITERAL, true); else PF_ANGLES(PF_RM_LITERAL, false);
+        break;
+    case PF_CDDT:
+        PF_ANGLES(PF_CDDT, false);
+        break;
+    default:
+        PF_ANGLES(PF_LUT, false);
+        break;
+    }
+    HIPCHK(hipGetLastError());
+    return RL_OK;
+}
+#undef PF_ANGLES
+
+static int launch_pf_eval(rl_method *h, const float *d_obs, const float *d_ranges, int n_angles, int n_particles,
+                          double *d_weights, hipStream_t stream)
+{
+    const PfParams pp = make_pf(h, n_particles, n_angles);
+    const int tiles = (n_particles + pp.block - 1) / pp.block;
+    const int grid = std::max(1, std::min(tiles, h->map->n_cu * 8));
+    hipLaunchKernelGGL(pf_eval_kernel, dim3(grid), dim3(PF_WG), pf_lds_bytes(pp.block, n_angles), stream, h->map->mp, pp,
+                       d_obs, d_ranges, d_weights);
+    HIPCHK(hipGetLastError());
+    return RL_OK;
+}
+
+// the fused call.  RM / RMGPU: pf_weight_kernel, nothing but the weights leaves the kernel.  CDDT / GiantLUT:
+// pf_angles_kernel into the launch context's scratch, then pf_eval_kernel — the same contract, 4 B per ray through HBM
+static int launch_pf_weights(rl_method *h, int kind, const float *d_poses, int n_particles, const float *d_angles,
+                             const float *d_obs, int n_angles, double *d_weights, hipStream_t stream)
+{
+    int rc;
+    if (kind == PF_CDDT || kind == PF_LUT) {
+        LaunchCtx *cx = nullptr;
+        if ((rc = acquire_ctx(h, stream, &cx))) return rc;
+        if ((rc = cx->pf_r.ensure((size_t)n_particles * n_angles * sizeof(float)))) return rc;
+        if ((rc = launch_pf_angles(h, kind, d_poses, n_particles, d_angles, n_angles, (float *)cx->pf_r.p, nullptr, nullptr, stream)))
+            return rc;
+        return launch_pf_eval(h, d_obs, (const float *)cx->pf_r.p, n_angles, n_particles, d_weights, stream);
+    }
+    const rl_map *m = h->map;
+    const PfParams pp = make_pf(h, n_particles, n_angles);
+    const FanParams f = make_fan(h, n_particles, 0.0f, n_angles);
+    const LiteralParams lt = make_literal(m);
+    const int tiles = (n_particles + pp.block - 1) / pp.block;
+    const dim3 grid(std::max(1, std::min(tiles, m->n_cu * 8)));
+    const size_t lds = pf_lds_bytes(pp.block, n_angles);
+    if (kind == PF_RM_LITERAL)
+        hipLaunchKernelGGL((pf_weight_kernel<true>), grid, dim3(PF_WG), lds, stream, m->mp, f, lt, pp, d_poses, d_angles, d_obs, d_weights);
+    else
+        hipLaunchKernelGGL((pf_weight_kernel<false>), grid, dim3(PF_WG), lds, stream, m->mp, f, lt, pp, d_poses, d_angles, d_obs, d_weights);
+    HIPCHK(hipGetLastError());
+    return RL_OK;
+}
+
+extern "C" int rl_set_sensor_model(rl_method *h, const double *table, int width)
+{
+    if (!h || !table) return fail(RL_ERR_INVALID, "rl_set_sensor_model: null pointer");
+    if (!h->reps.empty()) return fail(RL_ERR_INVALID, "rl_set_sensor_model: multi-device handles are not served (call it on rl_method_replica(h, i))");
+    if (width < 2 || width > PF_MAX_WIDTH)
+        return fail(RL_ERR_INVALID, "rl_set_sensor_model: width must be in [2, %d] (got %d)", PF_MAX_WIDTH, width);
+    std::lock_guard<std::mutex> lk(h->mu);
+    int rc = set_device(h->map);
+    if (rc) return rc;
+    const size_t bytes = (size_t)width * width * sizeof(double);
+    double *fresh = nullptr;
+    if (hipMalloc((void **)&fresh, bytes) != hipSuccess) return fail(RL_ERR_NOMEM, "hipMalloc(%zu) failed", bytes);
+    if (hipMemcpy(fresh, table, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(fresh);
+        return fail(RL_ERR_HIP, "rl_set_sensor_model: the copy of the table failed");
+    }
+    if (h->sensor) {
+        HIPCHK(hipDeviceSynchronize());      // launches of other streams may still read the old table
+        (void)hipFree(h->sensor);
+    }
+    h->sensor = fresh;
+    h->sensor_w = width;
+    return RL_OK;
+}
+
+extern "C" int rl_calc_range_repeat_angles_device(rl_method *h, const float *d_ins_p3, int n_particles,
+                                                  const float *d_angles, int n_angles, float *d_outs,
+                                                  int32_t *d_hit_cells_or_null, uint16_t *d_steps_or_null,
+                                                  void *hip_stream)
+{
+    int rc = check_pf_shape(h, "rl_calc_range_repeat_angles_device", n_particles, n_angles), kind = 0;
+    if (rc) return rc;
+    if (!d_ins_p3 || !d_angles || !d_outs) return fail(RL_ERR_INVALID, "rl_calc_range_repeat_angles_device: null device pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
+    if ((rc = pf_kind_of(h, &kind)) || n_particles == 0 || (rc = set_device(h->map))) return rc;
+    return launch_pf_angles(h, kind, d_ins_p3, n_particles, d_angles, n_angles, d_outs, d_hit_cells_or_null,
+                            d_steps_or_null, (hipStream_t)hip_stream);
+}
+
+extern "C" int rl_eval_sensor_model_device(rl_method *h, const float *d_obs, const float *d_ranges, int n_angles,
+                                           int n_particles, double *d_weights, void *hip_stream)
+{
+    int rc = check_pf_shape(h, "rl_eval_sensor_model_device", n_particles, n_angles);
+    if (rc) return rc;
+    if (!d_obs || !d_ranges || !d_weights) return fail(RL_ERR_INVALID, "rl_eval_sensor_model_device: null device pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->sensor_w) return fail(RL_ERR_INVALID, "rl_eval_sensor_model_device: no sensor model set (rl_set_sensor_model)");
+    if (n_particles == 0 || (rc = set_device(h->map))) return rc;
+    return launch_pf_eval(h, d_obs, d_ranges, n_angles, n_particles, d_weights, (hipStream_t)hip_stream);
+}
+
+extern "C" int rl_calc_range_repeat_angles_eval_sensor_model_device(rl_method *h, const float *d_ins_p3, int n_particles,
+                                                                    const float *d_angles, const float *d_obs,
+                                                                    int n_angles, double *d_weights, void *hip_stream)
+{
+    int rc = check_pf_shape(h, "rl_calc_range_repeat_angles_eval_sensor_model_device", n_particles, n_angles), kind = 0;
+    if (rc) return rc;
+    if (!d_ins_p3 || !d_angles || !d_obs || !d_weights)
+        return fail(RL_ERR_INVALID, "rl_calc_range_repeat_angles_eval_sensor_model_device: null device pointer");
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
+    if ((rc = pf_kind_of(h, &kind))) return rc;
+    if (!h->sensor_w) return fail(RL_ERR_INVALID, "rl_calc_range_repeat_angles_eval_sensor_model_device: no sensor model set (rl_set_sensor_model)");
+    if (n_particles == 0 || (rc = set_device(h->map))) return rc;
+    return launch_pf_weights(h, kind, d_ins_p3, n_particles, d_angles, d_obs, n_angles, d_weights, (hipStream_t)hip_stream);
+}
+
+// host-pointer forms: staged through the handle's device buffers on its own stream, synchronous
+struct PfHost {
+    const float *ins, *angles, *obs, *ranges;      // host inputs (null: not part of the call)
+    float *outs;                                   // host outputs
+    int32_t *hits;
+    uint16_t *steps;
+    double *weights;
+};
+
+static int pf_host(rl_method *h, const char *fn, const PfHost &a, int n_particles, int n_angles)
+{
+    int rc = check_pf_shape(h, fn, n_particles, n_angles), kind = 0;
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
+    if (a.ins && (rc = pf_kind_of(h, &kind))) return rc;
+    if (a.weights && !h->sensor_w) return fail(RL_ERR_INVALID, "%s: no sensor model set (rl_set_sensor_model)", fn);
+    if (n_particles == 0 || (rc = set_device(h->map))) return rc;
+    const size_t n = (size_t)n_particles * n_angles, fa = (size_t)n_angles * sizeof(float);
+    hipStream_t s = h->stream;
+    if (a.ins) {
+        if ((rc = h->poses.ensure((size_t)n_particles * 3 * sizeof(float))) || (rc = h->pf_ang.ensure(fa))) return rc;
+        HIPCHK(hipMemcpyAsync(h->poses.p, a.ins, (size_t)n_particles * 3 * sizeof(float), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h->pf_ang.p, a.angles, fa, hipMemcpyHostToDevice, s));
+    }
+    if (a.obs) {
+        if ((rc = h->pf_obs.ensure(fa)) || (rc = h->pf_w.ensure((size_t)n_particles * sizeof(double)))) return rc;
+        HIPCHK(hipMemcpyAsync(h->pf_obs.p, a.obs, fa, hipMemcpyHostToDevice, s));
+    }
+    if (a.outs || a.ranges) {
+        if ((rc = h->outs.ensure(n * sizeof(float)))) return rc;
+        if (a.ranges) HIPCHK(hipMemcpyAsync(h->outs.p, a.ranges, n * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+    if (a.hits && (rc = h->hits.ensure(n * 2 * sizeof(int32_t)))) return rc;
+    if (a.steps && (rc = h->steps.ensure(n * sizeof(uint16_t)))) return rc;
+    if (a.outs)
+        rc = launch_pf_angles(h, kind, (const float *)h->poses.p, n_particles, (const float *)h->pf_ang.p, n_angles, (float *)h->outs.p,
+                              a.hits ? (int32_t *)h->hits.p : nullptr, a.steps ? (uint16_t *)h->steps.p : nullptr, s);
+    else if (a.ranges)
+        rc = launch_pf_eval(h, (const float *)h->pf_obs.p, (const float *)h->outs.p, n_angles, n_particles, (double *)h->pf_w.p, s);
+    else
+        rc = launch_pf_weights(h, kind, (const float *)h->poses.p, n_particles, (const float *)h->pf_ang.p,
+                               (const float *)h->pf_obs.p, n_angles, (double *)h->pf_w.p, s);
+    if (rc) return rc;
+    if (a.outs) HIPCHK(hipMemcpyAsync(a.outs, h->outs.p, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (a.hits) HIPCHK(hipMemcpyAsync(a.hits, h->hits.p, n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (a.steps) HIPCHK(hipMemcpyAsync(a.steps, h->steps.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
+    if (a.weights) HIPCHK(hipMemcpyAsync(a.weights, h->pf_w.p, (size_t)n_particles * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return RL_OK;
+}
+
+extern "C" int rl_calc_range_repeat_angles(rl_method *h, const float *ins_p3, int n_particles, const float *angles,
+                                           int n_angles, float *outs, int32_t *hit_cells_or_null, uint16_t *steps_or_null)
+{
+    if (!ins_p3 || !angles || !outs) return fail(RL_ERR_INVALID, "rl_calc_range_repeat_angles: null pointer");
+    return pf_host(h, "rl_calc_range_repeat_angles", PfHost{ins_p3, angles, nullptr, nullptr, outs, hit_cells_or_null, steps_or_null, nullptr},
+                   n_particles, n_angles);
+}
+
+extern "C" int rl_eval_sensor_model(rl_method *h, const float *obs, const float *ranges, int n_angles, int n_particles,
+                                    double *weights)
+{
+    if (!obs || !ranges || !weights) return fail(RL_ERR_INVALID, "rl_eval_sensor_model: null pointer");
+    return pf_host(h, "rl_eval_sensor_model", PfHost{nullptr, nullptr, obs, ranges, nullptr, nullptr, nullptr, weights}, n_particles, n_angles);
+}
+
+extern "C" int rl_calc_range_repeat_angles_eval_sensor_model(rl_method *h, const float *ins_p3, int n_particles,
+                                                             const float *angles, const float *obs, int n_angles,
+                                                             double *weights)
+{
+    if (!ins_p3 || !angles || !obs || !weights)
+        return fail(RL_ERR_INVALID, "rl_calc_range_repeat_angles_eval_sensor_model: null pointer");
+    return pf_host(h, "rl_calc_range_repeat_angles_eval_sensor_model", PfHost{ins_p3, angles, obs, nullptr, nullptr, nullptr, nullptr, weights},
+                   n_particles, n_angles);
 }
 
 extern "C" int rl_method_read_lut(rl_method *h, int row0, int row1, uint16_t *out)

@@ -139,10 +139,11 @@ struct LaunchCtx {
     uint64_t last_use = 0;
     DevBuf rec, rec_sorted, order, keys, hist, pose_first, dbg, d0, cddt_r;   // cddt_r: theta-major CDDT, R[raw bin][pose]
     DevBuf left_rec, left_cnt;     // hand-off march: the leftover list (rm_leftover_kernel), one region per wave of the main grid
+    DevBuf pf_r;                   // particle-filter weights of the table kinds: the ranges between pf_angles_kernel and pf_eval_kernel
     int crash_epoch = 0;           // mark value of the last per-pose crash launch (pose_marks)
     void release()
     {
-        for (DevBuf *b : {&rec, &rec_sorted, &order, &keys, &hist, &pose_first, &dbg, &d0, &cddt_r, &left_rec, &left_cnt}) b->release();
+        for (DevBuf *b : {&rec, &rec_sorted, &order, &keys, &hist, &pose_first, &dbg, &d0, &cddt_r, &left_rec, &left_cnt, &pf_r}) b->release();
     }
 };
 constexpr int N_LAUNCH_CTX = 8;      // (HIP's default 4 hardware queues carry 4 concurrent streams; GPU_MAX_HW_QUEUES=8 carries 8)
@@ -340,6 +341,12 @@ struct rl_method {
     bool timed = false;
     DevBuf poses, outs, hits, steps, edge, flag;
     DevBuf cars;                 // rl_calc_range_fan_cars: the cars' (x, y, theta) rows
+    // particle-filter weights (pf_kernels.h): the sensor-model table (rl_set_sensor_model; width 0 = none set) and the
+    // host-pointer forms' staging of angles, observation and weights
+    double *sensor = nullptr;
+    int sensor_w = 0;
+    DevBuf pf_ang, pf_obs, pf_w;
+    int pf_block = 0;            // particles per tile of the weight kernels (0: sized from the shape, make_pf)
     LaunchCtx ctx[N_LAUNCH_CTX];
     uint64_t use_clock = 0;
     TableDep pdt_dep, lut_dep, cddt_dep;

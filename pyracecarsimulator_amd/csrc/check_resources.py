@@ -40,6 +40,10 @@ BOUNDS = [
     # batched races: the outline raster, and the race scan's march with the other cars' cells folded into each sample
     ("scan::outline_cells_kernel", {"scratch": 0}),
     ("scan::race_fan_kernel<", {"scratch": 0}),
+    # particle-filter weights: the fused march + sensor-model product spills nothing; eight waves per SIMD in the
+    # canonical form, seven in the literal one (its libm-exact trig holds 106 SGPRs)
+    ("scan::pf_weight_kernel<false>", {"scratch": 0, "occupancy": 8}),
+    ("scan::pf_weight_kernel<true>", {"scratch": 0, "occupancy": 7}),
 ]
 KEYS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy"}
 

@@ -10,7 +10,10 @@ and in-place/None-returning behaviour):
 * ``obj.calc_range_many(ins, outs, fov, num_rays)`` scripts/scan_simulator.py:103-106,130-133
 * ``obj.calc_range_many(ins, outs)``                scripts/two_player/scan.py:69-70
 
-plus range_libc's remaining casters (``PyBresenhamsLine``, ``PyGiantLUTCast``).
+plus range_libc's remaining casters (``PyBresenhamsLine``, ``PyGiantLUTCast``) and its particle-filter calls
+(``calc_range_repeat_angles``, ``set_sensor_model``, ``eval_sensor_model``,
+``calc_range_repeat_angles_eval_sensor_model``: what a particle filter — the odometry source
+scripts/mcts_driver.py:62 keeps commented out — calls per update).
 Array contract: ``ins`` float32 C-contiguous (n,3), ``outs`` float32
 C-contiguous (n,); anything else raises ``ValueError`` like the Cython
 ``np.ndarray[float, ndim=2, mode="c"]`` signature does.
@@ -188,6 +191,42 @@ def _check_ranges_out(ranges, n):
         raise ValueError("ranges must be a C-contiguous float32 array with n_poses*num_rays elements")
 
 
+def _check_f32_vector(name, a, n=None):
+    """A C-contiguous float32 1-D array (of n elements when n is given), as the Cython signatures take them."""
+    if not isinstance(a, np.ndarray):
+        raise TypeError("%s must be a numpy array" % name)
+    if a.dtype != np.float32:
+        raise ValueError("Buffer dtype mismatch, expected 'float' (%s)" % name)
+    if a.ndim != 1:
+        raise ValueError("Buffer has wrong number of dimensions (expected 1) (%s)" % name)
+    if not a.flags.c_contiguous:
+        raise ValueError("ndarray is not C-contiguous (%s)" % name)
+    if n is not None and a.shape[0] != n:
+        raise ValueError("%s must have %d elements, got %d" % (name, n, a.shape[0]))
+
+
+def _check_particles(ins):
+    if not isinstance(ins, np.ndarray):
+        raise TypeError("ins must be a numpy array")
+    if ins.dtype != np.float32:
+        raise ValueError("Buffer dtype mismatch, expected 'float' (ins)")
+    if ins.ndim != 2 or ins.shape[1] != 3:
+        raise ValueError("ins must have shape (n, 3)")
+    if not ins.flags.c_contiguous:
+        raise ValueError("ndarray is not C-contiguous (ins)")
+
+
+def _check_weights(weights, n):
+    if not isinstance(weights, np.ndarray):
+        raise TypeError("weights must be a numpy array")
+    if weights.dtype != np.float64:
+        raise ValueError("Buffer dtype mismatch, expected 'double' (weights)")
+    if weights.ndim != 1 or not weights.flags.c_contiguous:
+        raise ValueError("weights must be a C-contiguous 1-D array")
+    if weights.shape[0] != n:
+        raise ValueError("weights must have %d elements, got %d" % (n, weights.shape[0]))
+
+
 class _RangeMethod:
     KIND = None
 
@@ -307,6 +346,81 @@ class _RangeMethod:
         _lib.check(_lib.lib().rl_calc_range_many_device(
             self._h, C.c_void_p(d_ins_ptr), C.c_void_p(d_outs_ptr), int(n),
             C.c_void_p(stream or None)))
+
+    # -- particle-filter weights (range_libc's Monte-Carlo localisation calls) -------
+    def calc_range_repeat_angles(self, ins, angles, outs, hit_cells=None, steps=None):
+        """In-place, returns None: every particle ``ins[p]`` (x, y, theta) casts the same ``angles`` (float32 (A,)),
+        ray j of particle p at ``theta_p + angles[j]`` lands in ``outs[p*A + j]`` (rl_calc_range_repeat_angles)."""
+        _check_particles(ins)
+        _check_f32_vector("angles", angles)
+        n = ins.shape[0] * angles.shape[0]
+        _check_f32_vector("outs", outs, n)
+        if hit_cells is not None and (not isinstance(hit_cells, np.ndarray) or hit_cells.dtype != np.int32
+                                      or hit_cells.size != 2 * n or not hit_cells.flags.c_contiguous):
+            raise ValueError("hit_cells must be C-contiguous int32 (P*A, 2)")
+        if steps is not None and (not isinstance(steps, np.ndarray) or steps.dtype != np.uint16 or steps.size != n
+                                  or not steps.flags.c_contiguous):
+            raise ValueError("steps must be C-contiguous uint16 (P*A,)")
+        _lib.check(_lib.lib().rl_calc_range_repeat_angles(
+            self._h, ins.ctypes.data_as(f32p), ins.shape[0], angles.ctypes.data_as(f32p), angles.shape[0],
+            outs.ctypes.data_as(f32p), hit_cells.ctypes.data_as(i32p) if hit_cells is not None else None,
+            steps.ctypes.data_as(u16p) if steps is not None else None))
+        return None
+
+    def set_sensor_model(self, table):
+        """The sensor model: a square float64 2-D table, row = observed bin, column = expected bin
+        (rl_set_sensor_model; a later call replaces it)."""
+        if not isinstance(table, np.ndarray):
+            raise TypeError("table must be a numpy array")
+        if table.dtype != np.float64 or table.ndim != 2 or table.shape[0] != table.shape[1]:
+            raise ValueError("the sensor model must be a square 2-D float64 array")
+        table = np.ascontiguousarray(table)
+        _lib.check(_lib.lib().rl_set_sensor_model(self._h, table.ctypes.data_as(f64p), table.shape[0]))
+        return None
+
+    def eval_sensor_model(self, obs, ranges, outs, num_rays, num_particles):
+        """``outs[p]`` (float64) = the ascending product over j of ``table[bin(obs[j]), bin(ranges[p*num_rays + j])]``
+        (rl_eval_sensor_model).  In-place, returns None."""
+        num_rays, num_particles = int(num_rays), int(num_particles)
+        _check_f32_vector("obs", obs, num_rays)
+        _check_f32_vector("ranges", ranges, num_rays * num_particles)
+        _check_weights(outs, num_particles)
+        _lib.check(_lib.lib().rl_eval_sensor_model(self._h, obs.ctypes.data_as(f32p), ranges.ctypes.data_as(f32p),
+                                                   num_rays, num_particles, outs.ctypes.data_as(f64p)))
+        return None
+
+    def calc_range_repeat_angles_eval_sensor_model(self, ins, angles, obs, weights):
+        """``calc_range_repeat_angles`` and ``eval_sensor_model`` in one call; the ranges stay on the device
+        (rl_calc_range_repeat_angles_eval_sensor_model).  In-place on ``weights`` (float64 (P,)), returns None."""
+        _check_particles(ins)
+        _check_f32_vector("angles", angles)
+        _check_f32_vector("obs", obs, angles.shape[0])
+        _check_weights(weights, ins.shape[0])
+        _lib.check(_lib.lib().rl_calc_range_repeat_angles_eval_sensor_model(
+            self._h, ins.ctypes.data_as(f32p), ins.shape[0], angles.ctypes.data_as(f32p), obs.ctypes.data_as(f32p),
+            angles.shape[0], weights.ctypes.data_as(f64p)))
+        return None
+
+    def calc_range_repeat_angles_device(self, d_ins_ptr, n_particles, d_angles_ptr, n_angles, d_outs_ptr,
+                                        d_hits_ptr=0, d_steps_ptr=0, stream=0):
+        """``calc_range_repeat_angles`` on device pointers (ints, e.g. torch ``tensor.data_ptr()``): asynchronous."""
+        _lib.check(_lib.lib().rl_calc_range_repeat_angles_device(
+            self._h, C.c_void_p(d_ins_ptr), int(n_particles), C.c_void_p(d_angles_ptr), int(n_angles),
+            C.c_void_p(d_outs_ptr), C.c_void_p(d_hits_ptr or None), C.c_void_p(d_steps_ptr or None),
+            C.c_void_p(stream or None)))
+
+    def eval_sensor_model_device(self, d_obs_ptr, d_ranges_ptr, d_outs_ptr, num_rays, num_particles, stream=0):
+        """``eval_sensor_model`` on device pointers: asynchronous."""
+        _lib.check(_lib.lib().rl_eval_sensor_model_device(
+            self._h, C.c_void_p(d_obs_ptr), C.c_void_p(d_ranges_ptr), int(num_rays), int(num_particles),
+            C.c_void_p(d_outs_ptr), C.c_void_p(stream or None)))
+
+    def calc_range_repeat_angles_eval_sensor_model_device(self, d_ins_ptr, n_particles, d_angles_ptr, d_obs_ptr,
+                                                          n_angles, d_weights_ptr, stream=0):
+        """``calc_range_repeat_angles_eval_sensor_model`` on device pointers: asynchronous."""
+        _lib.check(_lib.lib().rl_calc_range_repeat_angles_eval_sensor_model_device(
+            self._h, C.c_void_p(d_ins_ptr), int(n_particles), C.c_void_p(d_angles_ptr), C.c_void_p(d_obs_ptr),
+            int(n_angles), C.c_void_p(d_weights_ptr), C.c_void_p(stream or None)))
 
     def check_collision_many(self, poses, fov, num_rays, edge_distances, crash_thresh,
                              ranges=None):
