@@ -438,6 +438,65 @@ int rl_calc_range_repeat_angles_eval_sensor_model_device(rl_method *h, const flo
                                                          const float *d_angles, const float *d_obs, int n_angles,
                                                          double *d_weights, void *hip_stream);
 
+/* ---- particle-filter localisation -----------------------------------------------------------------
+ * The consumer of the calls above: a Monte-Carlo-localisation filter (mit-racecar's particle_filter.py, the program
+ * range_libc's PF calls were written for) kept on the device.  rl_pf_run makes n_steps whole updates — motion,
+ * likelihood, weights, estimate, resampling — with the odometry and the observations of all steps sent up once and no
+ * host synchronisation or host-to-device copy between steps.  Every operation named below is one separately rounded
+ * IEEE double unless it is marked f32 (the library is built with -ffp-contract=off); tests/mcl_statement.py is the same
+ * step in NumPy and the device is bit-identical to it.
+ *
+ * rl_pf_create: a filter of n_particles particles casting the n_angles beams `angles` (float32, copied) on `h`.
+ * h is borrowed and must outlive the filter; it needs a sensor model (rl_set_sensor_model) and a kind the fused weight
+ * call serves (RL_RM, RL_RM_GPU, RL_CDDT, RL_GIANT_LUT; otherwise that call's RL_ERR_UNSUPPORTED).  The filter works on
+ * h's stream; every call is synchronous; h's options and ray offset read the same after every call.
+ * rl_pf_reset: X[p] = particles_p3 row p (x, y, theta; f64), w[p] = 1.0 / (double)P or the caller's weights taken as
+ * given, t = 0, key = noise_key(seed) (the fold of rl_mcts_reset's seeds).  U(d, i) below is the planner's 53-bit
+ * uniform: Philox-2x32-10 of counter (d, i) under key, ((out0 << 32 | out1) >> 11) 2^-53.
+ *
+ * One step.  t counts steps since the reset, so run(3) equals run(1) followed by run(2) bit for bit.
+ *  1. Motion.  (dx, dy, dth) = odom row t, in the car frame.  (s, c) = det_sincosf((float)theta) widened to double;
+ *       x' = (x + (c dx - s dy)) + std0 g0,   y' = (y + (s dx + c dy)) + std1 g1,   theta' = (theta + dth) + std2 g2
+ *     with g_a = (sum of U(p, 64 t + 1 + 12 a + k) for k = 0 .. 11, ascending from 0.0) - 6.0: the twelve-uniform normal
+ *     of Probabilistic Robotics, Table 5.4, whose bits a host reproduces.  An axis with std = 0 draws nothing
+ *     and adds nothing.  Angles are not wrapped.
+ *  2. Likelihood.  q[p] = ((float)x', (float)y', (float)theta'); L[p] is exactly
+ *     rl_calc_range_repeat_angles_eval_sensor_model of q, angles and obs row t, with the ray offset h's offset at entry
+ *     plus t P A (scan noise, when set, is fresh every step).
+ *  3. omega[p] = w[p] L[p].
+ *  4. Blocked sums, chunk size 256.  T_b = the sequential ascending sum of chunk b; bs(v) = the sequential ascending
+ *     sum of the T_b; cum(v)[i] = B_b + s_i with B_b the sequential sum of T_0 .. T_(b-1) and s_i the inclusive partial
+ *     sum inside the chunk.  W = bs(omega).  W NaN, +inf or not > 0: the step is degenerate, w[p] = 1 / P and bit 1 of
+ *     the flags is set; otherwise w[p] = omega[p] / W.  The order is part of the contract (any other order gives other
+ *     bits); at most 4096 chunk totals are summed by one lane.
+ *  5. Estimate, before resampling.  neff = 1.0 / bs(w^2);  est = (bs(w x'), bs(w y'), bs(w ch), bs(w sh)) with
+ *     (sh, ch) = det_sincosf((float)theta') widened.  The heading is atan2(est[3], est[2]), left to the caller: no atan2
+ *     and no pow run on the device (a squash exponent is applied by the caller to the table, T ** (1 / squash)).
+ *  6. Resample when neff < resample_ratio (double)P (ratio 0: never; ratio >= 2: always).  c = cum(w), S = its last
+ *     element, u = U(0, 64 t), tau_i = ((u + (double)i) / (double)P) S, a_i = min(P - 1, number of k with c[k] <= tau_i)
+ *     (c is non-decreasing for the non-negative weights of a sensor model: a bisection).  Then X <- X'[a], w <- 1 / P
+ *     and bit 0 of the flags is set.  Otherwise a_i = i, X <- X', w stays.
+ * rl_pf_run writes one row per step: est_t4 (n_steps x 4), neff_t, flags_t.  rl_pf_read returns the state after the
+ * last step (particles, weights), that step's ancestors, c and L; each output pointer may be null.
+ *
+ * Errors (RL_ERR_INVALID; the handles stay usable): null required pointers, n_particles outside [1, 2^20], n_angles
+ * outside [1, 2048], a negative or NaN std or ratio, n_steps < 0, t + n_steps > 2^26, rl_pf_run or rl_pf_read before a
+ * reset, no sensor model set, multi-device handles.  n_steps = 0 does nothing.
+ * Kernels: mcl_kernels.h (motion, weight multiply + chunk totals, normalise + estimate + in-chunk sums, chunk bases +
+ * decision, ancestor search + gather) around launch_pf_weights; T steps are enqueued on one stream.             */
+typedef struct rl_pf rl_pf;
+typedef struct rl_pf_params {
+    int n_particles, n_angles;
+    double motion_std[3];
+    double resample_ratio;
+} rl_pf_params;
+int rl_pf_create(rl_method *h, const rl_pf_params *p, const float *angles, rl_pf **out);
+void rl_pf_destroy(rl_pf *f);
+int rl_pf_reset(rl_pf *f, const double *particles_p3, const double *weights_or_null, uint64_t seed);
+int rl_pf_run(rl_pf *f, int n_steps, const double *odom_t3, const float *obs_tA, double *est_t4, double *neff_t,
+              int *flags_t);
+int rl_pf_read(rl_pf *f, double *particles_p3, double *weights, int32_t *ancestors, double *cum, double *likelihood);
+
 /* ---- the steering policy network ---------------------------------------------------------------
  * The reference's second steering source (scripts/policy.py:17-33, Policy.predict_action; driven at
  * scripts/policy_driver.py:30-49 and used by MCTS at scripts/mcts.py:252-256): a dense ReLU chain over the

@@ -9,5 +9,7 @@ from .scan_simulator import ScanSimulator2D          # noqa: F401
 from .racecar_simulator import RacecarSimulator      # noqa: F401
 from .policy import Policy                           # noqa: F401
 from .mcts import MCTS                               # noqa: F401
+from .particle_filter import ParticleFilter          # noqa: F401
 
-__all__ = ["maps", "racecar", "range_libc", "ScanSimulator2D", "RacecarSimulator", "Policy", "MCTS"]
+__all__ = ["maps", "racecar", "range_libc", "ScanSimulator2D", "RacecarSimulator", "Policy", "MCTS",
+           "ParticleFilter"]

@@ -57,6 +57,12 @@ class MctsParams(C.Structure):
                 ("fov", C.c_float), ("num_rays", C.c_int), ("crash_thresh", C.c_double)]
 
 
+class PfParams(C.Structure):
+    """rl_pf_params (include/scanlib.h)."""
+    _fields_ = [("n_particles", C.c_int), ("n_angles", C.c_int), ("motion_std", C.c_double * 3),
+                ("resample_ratio", C.c_double)]
+
+
 RL_MCTS_FG, RL_MCTS_NN, RL_MCTS_RANDOM = 0, 1, 2
 
 KERNEL_IDS = {0: "none", 1: "rm_chunk", 2: "rm_stream", 3: "occ_lds", 4: "bl_stream", 5: "bl_lds", 6: "lut_lds",
@@ -106,6 +112,11 @@ SYMBOLS = {
     "rl_calc_range_repeat_angles_eval_sensor_model": (C.c_int, [C.c_void_p, f32p, C.c_int, f32p, f32p, C.c_int, f64p]),
     "rl_calc_range_repeat_angles_eval_sensor_model_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                                        C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "rl_pf_create": (C.c_int, [C.c_void_p, C.POINTER(PfParams), f32p, C.POINTER(C.c_void_p)]),
+    "rl_pf_destroy": (None, [C.c_void_p]),
+    "rl_pf_reset": (C.c_int, [C.c_void_p, f64p, f64p, C.c_uint64]),
+    "rl_pf_run": (C.c_int, [C.c_void_p, C.c_int, f64p, f32p, f64p, f64p, i32p]),
+    "rl_pf_read": (C.c_int, [C.c_void_p, f64p, f64p, i32p, f64p, f64p]),
     "rl_set_noise": (C.c_int, [C.c_void_p, C.c_float, C.c_uint64, C.c_uint64]),
     "rl_check_collision_many": (C.c_int, [C.c_void_p, f32p, C.c_int, C.c_float, C.c_int, f64p,
                                           C.c_double, C.POINTER(C.c_int), f32p]),

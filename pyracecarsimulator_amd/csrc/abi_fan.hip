@@ -8,6 +8,7 @@
 #include "scan_kernels.h"
 #include "crash_kernels.h"
 #include "pf_kernels.h"
+#include "mcl_kernels.h"
 #include "launch_plan.h"
 
 #include <array>
@@ -1873,6 +1874,181 @@ extern "C" int rl_calc_range_repeat_angles_eval_sensor_model(rl_method *h, const
         return fail(RL_ERR_INVALID, "rl_calc_range_repeat_angles_eval_sensor_model: null pointer");
     return pf_host(h, "rl_calc_range_repeat_angles_eval_sensor_model", PfHost{ins_p3, angles, obs, nullptr, nullptr, nullptr, nullptr, weights},
                    n_particles, n_angles);
+}
+
+// ------------------------------------------------------------------------------
+// particle-filter localisation (include/scanlib.h "particle-filter localisation"; kernels: mcl_kernels.h): T whole MCL
+// updates per call on the handle's stream, the likelihood through launch_pf_weights
+// ------------------------------------------------------------------------------
+struct rl_pf {
+    rl_method *h = nullptr;        // borrowed
+    int device = 0;
+    int P = 0, A = 0, NB = 0;
+    double std[3] = {0, 0, 0}, ratio = 0;
+    uint32_t key = 0;
+    long t = 0;                    // steps since the reset
+    bool ready = false;            // a reset has been made
+    // state: X (cur), X' (prop), the float32 poses of the scan, w, L, omega, the in-chunk sums, cum, ancestors; the chunk
+    // totals ([1 + MCL_SUMS][NB]: omega's, then the six of the estimate), the chunk bases, W; a call's inputs and outputs
+    DevBuf ang, cur, prop, q, w, lik, omega, part, cum, anc, tot, base, scal, odom, obs, est, neff, flags;
+    std::mutex mu;
+};
+
+static bool bad_std(double v) { return !(v >= 0.0); }      // negative or NaN
+
+extern "C" int rl_pf_create(rl_method *h, const rl_pf_params *p, const float *angles, rl_pf **out)
+{
+    if (out) *out = nullptr;
+    if (!h || !p || !angles || !out) return fail(RL_ERR_INVALID, "rl_pf_create: null pointer");
+    int rc = check_pf_shape(h, "rl_pf_create", p->n_particles, p->n_angles), kind = 0;
+    if (rc) return rc;
+    if (p->n_particles < 1 || p->n_particles > MCL_MAX_PARTICLES)
+        return fail(RL_ERR_INVALID, "rl_pf_create: n_particles must be in [1, %d] (got %d)", MCL_MAX_PARTICLES, p->n_particles);
+    if (bad_std(p->motion_std[0]) || bad_std(p->motion_std[1]) || bad_std(p->motion_std[2]) || bad_std(p->resample_ratio))
+        return fail(RL_ERR_INVALID, "rl_pf_create: motion_std and resample_ratio must be >= 0");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if ((rc = pf_kind_of(h, &kind))) return rc;
+    if (!h->sensor_w) return fail(RL_ERR_INVALID, "rl_pf_create: no sensor model set (rl_set_sensor_model)");
+    if ((rc = set_device(h->map))) return rc;
+    std::unique_ptr<rl_pf> f(new (std::nothrow) rl_pf);
+    if (!f) return fail(RL_ERR_NOMEM, "rl_pf_create: out of memory");
+    f->h = h;
+    f->device = h->map->device;
+    f->P = p->n_particles;
+    f->A = p->n_angles;
+    f->NB = (f->P + MCL_CHUNK - 1) / MCL_CHUNK;
+    for (int a = 0; a < 3; ++a) f->std[a] = p->motion_std[a];
+    f->ratio = p->resample_ratio;
+    const size_t P = (size_t)f->P, NB = (size_t)f->NB;
+    struct { DevBuf *b; size_t bytes; } need[] = {
+        {&f->ang, (size_t)f->A * 4}, {&f->cur, P * 24}, {&f->prop, P * 24}, {&f->q, P * 12}, {&f->w, P * 8}, {&f->lik, P * 8},
+        {&f->omega, P * 8}, {&f->part, P * 8}, {&f->cum, P * 8}, {&f->anc, P * 4}, {&f->tot, (1 + MCL_SUMS) * NB * 8},
+        {&f->base, NB * 8}, {&f->scal, 8}};
+    for (auto &n : need)
+        if ((rc = n.b->ensure(n.bytes))) break;
+    if (!rc && hipMemcpy(f->ang.p, angles, (size_t)f->A * 4, hipMemcpyHostToDevice) != hipSuccess)
+        rc = fail(RL_ERR_HIP, "rl_pf_create: the copy of the angles failed");
+    if (rc) {
+        rl_pf_destroy(f.release());
+        return rc;
+    }
+    *out = f.release();
+    return RL_OK;
+}
+
+extern "C" void rl_pf_destroy(rl_pf *f)
+{
+    if (!f) return;
+    (void)hipSetDevice(f->device);       // (every call is synchronous: nothing of the filter's is in flight, h is not touched)
+    for (DevBuf *b : {&f->ang, &f->cur, &f->prop, &f->q, &f->w, &f->lik, &f->omega, &f->part, &f->cum, &f->anc, &f->tot,
+                      &f->base, &f->scal, &f->odom, &f->obs, &f->est, &f->neff, &f->flags})
+        b->release();
+    delete f;
+}
+
+extern "C" int rl_pf_reset(rl_pf *f, const double *particles_p3, const double *weights_or_null, uint64_t seed)
+{
+    if (!f || !particles_p3) return fail(RL_ERR_INVALID, "rl_pf_reset: null pointer");
+    std::scoped_lock lk(f->mu, f->h->mu);
+    int rc = set_device(f->h->map);
+    if (rc) return rc;
+    hipStream_t s = f->h->stream;
+    const size_t P = (size_t)f->P;
+    std::vector<double> uniform;
+    if (!weights_or_null) uniform.assign(P, 1.0 / (double)f->P);
+    HIPCHK(hipMemcpyAsync(f->cur.p, particles_p3, P * 24, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(f->w.p, weights_or_null ? weights_or_null : uniform.data(), P * 8, hipMemcpyHostToDevice, s));
+    for (DevBuf *b : {&f->prop, &f->lik, &f->omega, &f->part, &f->cum, &f->anc}) HIPCHK(hipMemsetAsync(b->p, 0, b->cap, s));
+    HIPCHK(hipStreamSynchronize(s));
+    f->key = (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x85EBCA6Bu);     // np_statement.noise_key
+    f->t = 0;
+    f->ready = true;
+    return RL_OK;
+}
+
+// one update, enqueued on `s`: step `k` of this call (its odometry and observation rows), step f->t + k since the reset
+static int launch_mcl_step(rl_pf *f, int kind, const MclParams &mp, int k, hipStream_t s)
+{
+    rl_method *h = f->h;
+    const uint32_t t = (uint32_t)(f->t + k);
+    const int grid = (f->P + MCL_WG - 1) / MCL_WG;
+    double *tot = (double *)f->tot.p, *tot6 = tot + f->NB;
+    hipLaunchKernelGGL(mcl_motion_kernel, dim3(grid), dim3(MCL_WG), 0, s, mp, (const double *)f->odom.p + 3 * (size_t)k, t,
+                       (const double *)f->cur.p, (double *)f->prop.p, (float *)f->q.p);
+    int rc = launch_pf_weights(h, kind, (const float *)f->q.p, f->P, (const float *)f->ang.p,
+                               (const float *)f->obs.p + (size_t)k * f->A, f->A, (double *)f->lik.p, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(mcl_weight_kernel, dim3((f->NB + MCL_GROUP - 1) / MCL_GROUP), dim3(MCL_WG), 0, s, mp,
+                       (const double *)f->w.p, (const double *)f->lik.p, (double *)f->omega.p, tot);
+    hipLaunchKernelGGL(mcl_norm_kernel, dim3((f->NB + MCL_NGROUP - 1) / MCL_NGROUP), dim3(MCL_WG), 0, s, mp, (const double *)tot,
+                       (const double *)f->omega.p, (const double *)f->prop.p, (double *)f->w.p, (double *)f->part.p, tot6,
+                       (double *)f->scal.p);
+    hipLaunchKernelGGL(mcl_base_kernel, dim3(1), dim3(64 * MCL_SUMS), 0, s, mp, (const double *)tot6, (const double *)f->scal.p,
+                       (double *)f->base.p, (double *)f->est.p + 4 * (size_t)k, (double *)f->neff.p + k, (int *)f->flags.p + k);
+    hipLaunchKernelGGL(mcl_resample_kernel, dim3(grid), dim3(MCL_WG), 0, s, mp, t, (const int *)f->flags.p + k,
+                       (const double *)f->base.p, (const double *)f->part.p, (const double *)f->prop.p, (double *)f->cur.p,
+                       (double *)f->w.p, (int32_t *)f->anc.p, (double *)f->cum.p);
+    HIPCHK(hipGetLastError());
+    return RL_OK;
+}
+
+extern "C" int rl_pf_run(rl_pf *f, int n_steps, const double *odom_t3, const float *obs_tA, double *est_t4, double *neff_t,
+                         int *flags_t)
+{
+    if (!f) return fail(RL_ERR_INVALID, "rl_pf_run: null filter handle");
+    if (n_steps < 0) return fail(RL_ERR_INVALID, "rl_pf_run: n_steps must be >= 0");
+    std::scoped_lock lk(f->mu, f->h->mu);
+    if (!f->ready) return fail(RL_ERR_INVALID, "rl_pf_run: the filter has not been reset (rl_pf_reset)");
+    if (f->t + (long)n_steps > (1L << 26)) return fail(RL_ERR_INVALID, "rl_pf_run: more than 2^26 steps since the reset");
+    if (n_steps == 0) return RL_OK;
+    if (!odom_t3 || !obs_tA || !est_t4 || !neff_t || !flags_t) return fail(RL_ERR_INVALID, "rl_pf_run: null pointer");
+    rl_method *h = f->h;
+    std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
+    int rc, kind = 0;
+    if ((rc = pf_kind_of(h, &kind)) || (rc = set_device(h->map))) return rc;
+    const size_t T = (size_t)n_steps;
+    if ((rc = f->odom.ensure(T * 24)) || (rc = f->obs.ensure(T * f->A * 4)) || (rc = f->est.ensure(T * 32)) ||
+        (rc = f->neff.ensure(T * 8)) || (rc = f->flags.ensure(T * 4)))
+        return rc;
+    hipStream_t s = h->stream;
+    HIPCHK(hipMemcpyAsync(f->odom.p, odom_t3, T * 24, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(f->obs.p, obs_tA, T * f->A * 4, hipMemcpyHostToDevice, s));
+    MclParams mp{f->P, f->NB, 1.0 / (double)f->P, {f->std[0], f->std[1], f->std[2]}, f->ratio * (double)f->P, f->key};
+    const uint64_t off = h->ray_offset;          // the scans' noise: step t's rays are off + t P A + p A + j
+    for (int k = 0; k < n_steps && !rc; ++k) {
+        h->ray_offset = off + (uint64_t)(f->t + k) * (uint64_t)f->P * (uint64_t)f->A;
+        rc = launch_mcl_step(f, kind, mp, k, s);
+    }
+    h->ray_offset = off;
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        f->ready = false;                         // part of the steps may have run: the state is no step's; reset again
+        return rc;
+    }
+    HIPCHK(hipMemcpyAsync(est_t4, f->est.p, T * 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(neff_t, f->neff.p, T * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(flags_t, f->flags.p, T * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    f->t += n_steps;
+    return RL_OK;
+}
+
+extern "C" int rl_pf_read(rl_pf *f, double *particles_p3, double *weights, int32_t *ancestors, double *cum, double *likelihood)
+{
+    if (!f) return fail(RL_ERR_INVALID, "rl_pf_read: null filter handle");
+    std::scoped_lock lk(f->mu, f->h->mu);
+    if (!f->ready) return fail(RL_ERR_INVALID, "rl_pf_read: the filter has not been reset (rl_pf_reset)");
+    int rc = set_device(f->h->map);
+    if (rc) return rc;
+    hipStream_t s = f->h->stream;
+    const size_t P = (size_t)f->P;
+    if (particles_p3) HIPCHK(hipMemcpyAsync(particles_p3, f->cur.p, P * 24, hipMemcpyDeviceToHost, s));
+    if (weights) HIPCHK(hipMemcpyAsync(weights, f->w.p, P * 8, hipMemcpyDeviceToHost, s));
+    if (ancestors) HIPCHK(hipMemcpyAsync(ancestors, f->anc.p, P * 4, hipMemcpyDeviceToHost, s));
+    if (cum) HIPCHK(hipMemcpyAsync(cum, f->cum.p, P * 8, hipMemcpyDeviceToHost, s));
+    if (likelihood) HIPCHK(hipMemcpyAsync(likelihood, f->lik.p, P * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return RL_OK;
 }
 
 extern "C" int rl_method_read_lut(rl_method *h, int row0, int row1, uint16_t *out)

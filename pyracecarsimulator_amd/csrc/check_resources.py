@@ -44,6 +44,12 @@ BOUNDS = [
     # canonical form, seven in the literal one (its libm-exact trig holds 106 SGPRs)
     ("scan::pf_weight_kernel<false>", {"scratch": 0, "occupancy": 8}),
     ("scan::pf_weight_kernel<true>", {"scratch": 0, "occupancy": 7}),
+    # particle-filter localisation: the passes around the weight call are short f64 loops, none of them spills
+    ("scan::mcl_motion_kernel", {"scratch": 0}),
+    ("scan::mcl_weight_kernel", {"scratch": 0}),
+    ("scan::mcl_norm_kernel", {"scratch": 0}),
+    ("scan::mcl_base_kernel", {"scratch": 0}),
+    ("scan::mcl_resample_kernel", {"scratch": 0}),
 ]
 KEYS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy"}
 

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "scan_device.h"
 #include "car_kernels.h"
 #include "consumer_kernels.h"
 #include "drive_kernels.h"
@@ -66,20 +67,7 @@ struct MctsDrive {
     double steer_clip;                 // > 0: the next recent action is the best action clamped to +-steer_clip
 };
 
-// Philox-2x32-10 of counter (d, i) under `key` (scan_device.h gauss_noise's rounds), as a double in [0, 1):
-// ((out0 << 32 | out1) >> 11) 2^-53
-__device__ inline double mcts_uniform01(uint32_t key, uint32_t d, uint32_t i)
-{
-    uint32_t c0 = d, c1 = i, k = key;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t prod = (uint64_t)0xD256D193u * c0;
-        c0 = (uint32_t)(prod >> 32) ^ k ^ c1;
-        c1 = (uint32_t)prod;
-        k += 0x9E3779B9u;
-    }
-    return (double)((((uint64_t)c0 << 32) | c1) >> 11) * 0x1.0p-53;
-}
+// (mcts_uniform01, the 53-bit Philox uniform of every draw, lives in scan_device.h: the particle filter draws with it too)
 
 // numpy.random.uniform(lo, hi): lo + (hi - lo) u, each operation rounded
 __device__ inline double mcts_uniform(double lo, double hi, double u)

@@ -99,6 +99,21 @@ __device__ __forceinline__ float gauss_noise(uint64_t seed, uint64_t ray_id)
     return __builtin_amdgcn_sqrtf(-2.0f * __logf(u1)) * __cosf(6.283185307179586f * u2);
 }
 
+// the planner's and the particle filter's 53-bit uniform: Philox-2x32-10 of counter (d, i) under `key` (gauss_noise's rounds), as a double in [0, 1):
+// ((out0 << 32 | out1) >> 11) 2^-53
+__device__ inline double mcts_uniform01(uint32_t key, uint32_t d, uint32_t i)
+{
+    uint32_t c0 = d, c1 = i, k = key;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t prod = (uint64_t)0xD256D193u * c0;
+        c0 = (uint32_t)(prod >> 32) ^ k ^ c1;
+        c1 = (uint32_t)prod;
+        k += 0x9E3779B9u;
+    }
+    return (double)((((uint64_t)c0 << 32) | c1) >> 11) * 0x1.0p-53;
+}
+
 // ---- sphere tracing on the float32 distance transform (rows a8 / a11) -------------
 // Correctly rounded sqrt for the hit distance sqrt(xd^2 + yd^2): the argument is 0 or >= 2^-46
 // (xd, yd are differences of cell indices and in-map coordinates), never denormal, never inf, so the

@@ -230,6 +230,21 @@ class RacecarSimulator:
                                    steer_clip=steer_clip, rollout_steps=self.batch_size,
                                    scan_dist_to_base=self.scan_dist_to_base)
 
+    def particleFilter(self, n_particles, angles=None, motion_std=(0.05, 0.05, 0.02), resample_ratio=0.5,
+                       sensor_model=None):
+        """A ``ParticleFilter`` on this simulator's range method: ``n_particles`` particles casting ``angles`` (default:
+        every 20th beam of this simulator's fan, the sparse scan mit-racecar's particle_filter.py localises with).
+        ``sensor_model``: a (W, W) table for ``set_sensor_model`` (None: the method's table as already set).  Run it with
+        ``reset(particles)`` and ``run(odom, obs)``; nothing leaves the GPU between the steps of a run."""
+        from .particle_filter import ParticleFilter
+        if angles is None:
+            j = np.arange(0, self.num_rays, 20, dtype=np.float32)
+            angles = (np.float32(-0.5 * self.scan_fov) + j * np.float32(self.scan_fov / self.num_rays)).astype(np.float32)
+        method = self.scan_simulator.scan_method
+        if sensor_model is not None:
+            method.set_sensor_model(sensor_model)
+        return ParticleFilter(method, angles, n_particles, motion_std=motion_std, resample_ratio=resample_ratio)
+
     def stop(self):
         state = self.getState()
         state[:11] = 0.0
