@@ -304,6 +304,27 @@ def check(code: int) -> None:
         raise ScanLibError(code, lib().rl_last_error().decode("utf-8", "replace"))
 
 
+class Handle:
+    """Base of every wrapper of a C handle: ``_h`` (a ``ctypes.c_void_p``) and ``_destroy``, the ``rl_*_destroy``
+    symbol that gives it back.  ``close()`` may be called any number of times; a handle marked ``_borrowed`` (the
+    per-device replica of a multi-device parent) is left to its owner."""
+    _destroy = None
+    _h = None                 # (until __init__ has made the handle)
+    _borrowed = False
+
+    def close(self):
+        h = self._h
+        if h is not None and h.value and not self._borrowed:
+            self._h = C.c_void_p()
+            getattr(lib(), self._destroy)(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:     # (interpreter shutdown: the module globals may be gone)
+            pass
+
+
 class _PinnedOwner:
     """Keeps one rl_host_alloc block alive for the NumPy array built on it."""
 

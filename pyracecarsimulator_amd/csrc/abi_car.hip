@@ -17,7 +17,7 @@ struct rl_car {
     std::unique_ptr<MultiPool> pool;
     int device = 0;
     CarParams P{};
-    hipStream_t stream = nullptr;
+    Stream stream;
     DevBuf states, actions, poses, states_out, vel, ranges, edge, first;
     DevBuf speeds, steer0, tr_steers, tr_poses, tr_states;     // rl_car_drive_followgap, rl_car_drive_policy
     DevBuf mlp;                                                // rl_car_drive_policy: the network's steers of a tick
@@ -28,20 +28,15 @@ struct rl_car {
 extern "C" int rl_car_create(int device, const double *p, rl_car **out)
 {
     if (!p || !out) return fail(RL_ERR_INVALID, "rl_car_create: null pointer");
-    int ndev = rl_device_count();
-    if (ndev <= 0) return fail(RL_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
-    rl_car *c = new (std::nothrow) rl_car();
+    int rc = check_device(device);
+    if (rc) return rc;
+    std::unique_ptr<rl_car, decltype(&rl_car_destroy)> c(new (std::nothrow) rl_car(), rl_car_destroy);
     if (!c) return fail(RL_ERR_NOMEM, "out of host memory");
     c->device = device;
     c->P = CarParams{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], p[11], p[12],
                      p[13], p[14], p[15], p[16]};
-    if (hipSetDevice(device) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete c;
-        return fail(RL_ERR_HIP, "stream creation failed");
-    }
-    *out = c;
+    if (hipSetDevice(device) != hipSuccess || c->stream.create() != hipSuccess) return fail(RL_ERR_HIP, "stream creation failed");
+    *out = c.release();
     return RL_OK;
 }
 
@@ -49,15 +44,15 @@ extern "C" int rl_car_create_multi(const int *devices, int n_devices, const doub
 {
     if (!p || !out || !devices) return fail(RL_ERR_INVALID, "rl_car_create_multi: null pointer");
     if (n_devices < 1 || n_devices > 64) return fail(RL_ERR_INVALID, "rl_car_create_multi: 1..64 devices (got %d)", n_devices);
-    rl_car *c = new (std::nothrow) rl_car();
+    std::unique_ptr<rl_car, decltype(&rl_car_destroy)> c(new (std::nothrow) rl_car(), rl_car_destroy);
     if (!c) return fail(RL_ERR_NOMEM, "out of host memory");
     std::vector<int> devs;
     for (int i = 0; i < n_devices; ++i) {
         rl_car *r = nullptr;
         const int rc = rl_car_create(devices[i], p, &r);
         if (rc) {
-            const std::string keep = last_error();
-            rl_car_destroy(c);
+            const std::string keep = last_error();     // (the failing replica's message outlives the clean-up)
+            c.reset();
             set_last_error(keep);
             return rc;
         }
@@ -68,7 +63,7 @@ extern "C" int rl_car_create_multi(const int *devices, int n_devices, const doub
     c->P = c->reps[0]->P;
     c->pool = std::make_unique<MultiPool>();
     c->pool->start(devs);
-    *out = c;
+    *out = c.release();
     return RL_OK;
 }
 
@@ -83,11 +78,6 @@ extern "C" void rl_car_destroy(rl_car *c)
     }
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (DevBuf *b : {&c->states, &c->actions, &c->poses, &c->states_out, &c->vel, &c->ranges, &c->edge, &c->first,
-                      &c->speeds, &c->steer0, &c->tr_steers, &c->tr_poses, &c->tr_states, &c->mlp, &c->o_cars,
-                      &c->o_cells, &c->o_counts})
-        b->release();
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -207,7 +197,7 @@ struct rl_followgap {
     int window_size = 0;           // kept for the caller; FollowGap::eval never reads it
     int n_cu = 256;                // (queried once: hipGetDeviceProperties costs the host tens of microseconds per call)
     bool walk_kernel = false;      // diagnostics (environment RL_FOLLOWGAP_WALK=1 at create): followgap_kernel at every size
-    hipStream_t stream = nullptr;
+    Stream stream;
     DevBuf scans, angles;
     std::mutex mu;
 };
@@ -216,10 +206,9 @@ extern "C" int rl_followgap_create(int device, int window_size, float max_distan
                                    float angle_inc, rl_followgap **out)
 {
     if (!out) return fail(RL_ERR_INVALID, "rl_followgap_create: null pointer");
-    int ndev = rl_device_count();
-    if (ndev <= 0) return fail(RL_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
-    rl_followgap *g = new (std::nothrow) rl_followgap();
+    int rc = check_device(device);
+    if (rc) return rc;
+    std::unique_ptr<rl_followgap, decltype(&rl_followgap_destroy)> g(new (std::nothrow) rl_followgap(), rl_followgap_destroy);
     if (!g) return fail(RL_ERR_NOMEM, "out of host memory");
     g->device = device;
     g->window_size = window_size;
@@ -228,14 +217,10 @@ extern "C" int rl_followgap_create(int device, int window_size, float max_distan
     g->P.angle_inc = angle_inc;
     const char *walk = getenv("RL_FOLLOWGAP_WALK");
     g->walk_kernel = walk && walk[0] == '1';
-    if (hipSetDevice(device) != hipSuccess ||
-        hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete g;
-        return fail(RL_ERR_HIP, "stream creation failed");
-    }
+    if (hipSetDevice(device) != hipSuccess || g->stream.create() != hipSuccess) return fail(RL_ERR_HIP, "stream creation failed");
     int n_cu = 0;
     if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n_cu > 0) g->n_cu = n_cu;
-    *out = g;
+    *out = g.release();
     return RL_OK;
 }
 
@@ -244,9 +229,6 @@ extern "C" void rl_followgap_destroy(rl_followgap *g)
     if (!g) return;
     (void)hipSetDevice(g->device);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
-    g->scans.release();
-    g->angles.release();
-    if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
 
@@ -478,7 +460,7 @@ extern "C" int rl_car_outline_cells(rl_car *c, rl_map *m, const double *cars_p3,
 struct rl_policy {
     int device = 0;
     PolicyParams P{};                  // device pointers into `weights`
-    hipStream_t stream = nullptr;
+    Stream stream;
     DevBuf weights, scans, steers;
     std::mutex mu;
 };
@@ -502,9 +484,8 @@ extern "C" int rl_policy_create(int device, int n_layers, const int *dims, const
     if (dims[n_layers] != 1)
         return fail(RL_ERR_UNSUPPORTED, "rl_policy_create: one output only (got %d)", dims[n_layers]);
     if (in_start < 0) return fail(RL_ERR_INVALID, "rl_policy_create: in_start must be >= 0 (got %d)", in_start);
-    int ndev = rl_device_count();
-    if (ndev <= 0) return fail(RL_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
+    int rc = check_device(device);
+    if (rc) return rc;
     // one block: per layer W [K][ceil4(N)] then b [ceil4(N)], zero-padded (16-byte rows for the float4 loads)
     std::vector<float> host;
     std::vector<size_t> offW(n_layers), offB(n_layers);
@@ -518,20 +499,13 @@ extern "C" int rl_policy_create(int device, int n_layers, const int *dims, const
         host.resize(host.size() + Np, 0.0f);
         std::memcpy(&host[offB[l]], biases[l], (size_t)N * sizeof(float));
     }
-    rl_policy *p = new (std::nothrow) rl_policy();
+    std::unique_ptr<rl_policy, decltype(&rl_policy_destroy)> p(new (std::nothrow) rl_policy(), rl_policy_destroy);
     if (!p) return fail(RL_ERR_NOMEM, "out of host memory");
     p->device = device;
-    int rc;
-    if (hipSetDevice(device) != hipSuccess ||
-        hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete p;
-        return fail(RL_ERR_HIP, "stream creation failed");
-    }
-    if ((rc = p->weights.ensure(host.size() * sizeof(float))) ||
-        hipMemcpy(p->weights.p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        rl_policy_destroy(p);
-        return rc ? rc : fail(RL_ERR_HIP, "rl_policy_create: weight upload failed");
-    }
+    if (hipSetDevice(device) != hipSuccess || p->stream.create() != hipSuccess) return fail(RL_ERR_HIP, "stream creation failed");
+    if ((rc = p->weights.ensure(host.size() * sizeof(float)))) return rc;
+    if (hipMemcpy(p->weights.p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(RL_ERR_HIP, "rl_policy_create: weight upload failed");
     p->P.n_layers = n_layers;
     p->P.relu = 0;
     for (int l = 0; l <= n_layers; ++l) p->P.dims[l] = dims[l];
@@ -543,7 +517,7 @@ extern "C" int rl_policy_create(int device, int n_layers, const int *dims, const
     p->P.in_start = in_start;
     p->P.clip = clip;
     p->P.scale = scale;
-    *out = p;
+    *out = p.release();
     return RL_OK;
 }
 
@@ -552,10 +526,6 @@ extern "C" void rl_policy_destroy(rl_policy *p)
     if (!p) return;
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
-    p->weights.release();
-    p->scans.release();
-    p->steers.release();
-    if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
 }
 
@@ -806,71 +776,53 @@ extern "C" int rl_probe_hbm_nt(int device, size_t bytes, double *gbs_out3)
 extern "C" int rl_probe_literal_sincosf(int device, const float *x, size_t n, float *sin_out, float *cos_out)
 {
     if (!x || !sin_out || !cos_out) return fail(RL_ERR_INVALID, "rl_probe_literal_sincosf: null pointer");
-    int ndev = rl_device_count();
-    if (ndev <= 0) return fail(RL_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
-    if (n == 0) return RL_OK;
+    const int rc = check_device(device);
+    if (rc || n == 0) return rc;
     HIPCHK(hipSetDevice(device));
-    float *d = nullptr;
-    if (hipMalloc((void **)&d, 3 * n * sizeof(float)) != hipSuccess) return fail(RL_ERR_NOMEM, "rl_probe_literal_sincosf: %zu floats", 3 * n);
-    int rc = RL_OK;
-    if (hipMemcpy(d, x, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) rc = fail(RL_ERR_HIP, "upload failed");
-    if (rc == RL_OK) {
-        const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
-        hipLaunchKernelGGL(literal_sincosf_kernel, dim3(grid), dim3(256), 0, nullptr, d, (long)n, d + n, d + 2 * n);
-        if (hipMemcpy(sin_out, d + n, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(cos_out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(RL_ERR_HIP, "rl_probe_literal_sincosf: kernel or download failed");
-    }
-    (void)hipFree(d);
-    return rc;
+    DevPtr<float> buf;
+    if (buf.alloc(3 * n * sizeof(float))) return fail(RL_ERR_NOMEM, "rl_probe_literal_sincosf: %zu floats", 3 * n);
+    float *const d = buf;
+    if (hipMemcpy(d, x, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(RL_ERR_HIP, "upload failed");
+    const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(literal_sincosf_kernel, dim3(grid), dim3(256), 0, nullptr, d, (long)n, d + n, d + 2 * n);
+    if (hipMemcpy(sin_out, d + n, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(cos_out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(RL_ERR_HIP, "rl_probe_literal_sincosf: kernel or download failed");
+    return RL_OK;
 }
 
 static int probe_hbm_modes(int device, size_t bytes, double *gbs_out5, int mode_lo, int mode_hi)
 {
     if (!gbs_out5) return fail(RL_ERR_INVALID, "rl_probe_hbm: null pointer");
     if (bytes < ((size_t)1 << 20)) return fail(RL_ERR_INVALID, "rl_probe_hbm: at least 1 MiB per buffer");
-    int ndev = rl_device_count();
-    if (ndev <= 0) return fail(RL_ERR_NO_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
+    const int rc = check_device(device);
+    if (rc) return rc;
     HIPCHK(hipSetDevice(device));
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
-    uint4 *a = nullptr, *b = nullptr;
-    uint32_t *sink = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipStream_t st = nullptr;
-    int rc = RL_OK;
+    Stream st;                          // (declared first: the buffers go before it, and freeing them drains the device)
+    Event e0, e1;
+    DevPtr<uint4> a, b;
+    DevPtr<uint32_t> sink;
     const size_t n16 = bytes / 16;
-    if (hipMalloc((void **)&a, n16 * 16) != hipSuccess || hipMalloc((void **)&b, n16 * 16) != hipSuccess ||
-        hipMalloc((void **)&sink, 4) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
-        hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess || hipMemsetAsync(a, 1, n16 * 16, st) != hipSuccess ||
-        hipMemsetAsync(b, 2, n16 * 16, st) != hipSuccess) {
-        rc = fail(RL_ERR_NOMEM, "rl_probe_hbm: setup failed (2 x %zu bytes)", n16 * 16);
-    } else {
-        const int grid = prop.multiProcessorCount * 8, reps = 10;
-        for (int mode = mode_lo; mode < mode_hi && rc == RL_OK; ++mode) {
-            hipLaunchKernelGGL(hbm_probe_kernel, dim3(grid), dim3(256), 0, st, a, b, n16, mode, sink);     // warm
-            (void)hipEventRecord(e0, st);
-            for (int r = 0; r < reps; ++r)
-                hipLaunchKernelGGL(hbm_probe_kernel, dim3(grid), dim3(256), 0, st, a, b, n16, mode, sink);
-            (void)hipEventRecord(e1, st);
-            float ms = 0.f;
-            if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess || !(ms > 0.f)) {
-                rc = fail(RL_ERR_HIP, "rl_probe_hbm: launch failed");
-                break;
-            }
-            const double moved = (double)n16 * 16.0 * ((mode == 0 || mode == 3 || mode == 6 || mode == 7) ? 2.0 : 1.0);
-            gbs_out5[mode - mode_lo] = moved * reps / ((double)ms * 1e-3) / 1e9;
-        }
+    if (a.alloc(n16 * 16) || b.alloc(n16 * 16) || sink.alloc(4) || e0.create() != hipSuccess || e1.create() != hipSuccess ||
+        st.create() != hipSuccess || hipMemsetAsync(a, 1, n16 * 16, st) != hipSuccess ||
+        hipMemsetAsync(b, 2, n16 * 16, st) != hipSuccess)
+        return fail(RL_ERR_NOMEM, "rl_probe_hbm: setup failed (2 x %zu bytes)", n16 * 16);
+    const int grid = prop.multiProcessorCount * 8, reps = 10;
+    for (int mode = mode_lo; mode < mode_hi; ++mode) {
+        hipLaunchKernelGGL(hbm_probe_kernel, dim3(grid), dim3(256), 0, st, a, b, n16, mode, sink);     // warm
+        (void)hipEventRecord(e0, st);
+        for (int r = 0; r < reps; ++r)
+            hipLaunchKernelGGL(hbm_probe_kernel, dim3(grid), dim3(256), 0, st, a, b, n16, mode, sink);
+        (void)hipEventRecord(e1, st);
+        float ms = 0.f;
+        if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess || !(ms > 0.f))
+            return fail(RL_ERR_HIP, "rl_probe_hbm: launch failed");
+        const double moved = (double)n16 * 16.0 * ((mode == 0 || mode == 3 || mode == 6 || mode == 7) ? 2.0 : 1.0);
+        gbs_out5[mode - mode_lo] = moved * reps / ((double)ms * 1e-3) / 1e9;
     }
-    if (a) (void)hipFree(a);
-    if (b) (void)hipFree(b);
-    if (sink) (void)hipFree(sink);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (st) (void)hipStreamDestroy(st);
-    return rc;
+    return RL_OK;
 }
 
 // ---------------------------------------------------------------- 16-bit ranges for the xGMI exchange (opt-in, lossy)
@@ -878,10 +830,7 @@ static int u16_args(int device, size_t n, float max_range_m, const void *a, cons
 {
     if (!(max_range_m > 0.0f)) return fail(RL_ERR_INVALID, "max_range_m must be > 0");
     if (n > 0 && (!a || !b)) return fail(RL_ERR_INVALID, "null device pointer");
-    int ndev = rl_device_count();
-    if (ndev <= 0) return fail(RL_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
-    return RL_OK;
+    return check_device(device);
 }
 
 // leading elements until the u16 pointer is 16-B aligned, and whether the f32 pointer is aligned there too
@@ -930,27 +879,17 @@ extern "C" int rl_probe_gather_rate(int device, int active_lanes, double *lanes_
 {
     if (!lanes_per_clk_per_cu) return fail(RL_ERR_INVALID, "rl_probe_gather_rate: null pointer");
     if (active_lanes < 1 || active_lanes > 64) return fail(RL_ERR_INVALID, "active_lanes must be in [1,64]");
-    int ndev = rl_device_count();
-    if (ndev <= 0) return fail(RL_ERR_NO_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
+    const int rc = check_device(device);
+    if (rc) return rc;
     HIPCHK(hipSetDevice(device));
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     const int n_cu = prop.multiProcessorCount;
     const double clk = (double)prop.clockRate * 1e3;
-    float *tab = nullptr, *sink = nullptr;
-    int *d_off = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipStream_t st = nullptr;
-    int rc = RL_OK;
-    auto cleanup = [&]() {
-        if (tab) (void)hipFree(tab);
-        if (sink) (void)hipFree(sink);
-        if (d_off) (void)hipFree(d_off);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (st) (void)hipStreamDestroy(st);
-    };
+    Stream st;                          // (declared first: the buffers go before it, and freeing them drains the device)
+    Event e0, e1;
+    DevPtr<float> tab, sink;
+    DevPtr<int> d_off;
     // random cells of a 32x32 window in the 4-row-interleaved layout of the step map, fixed seed
     int off[64];
     uint32_t lcg = 12345u;
@@ -963,22 +902,17 @@ extern "C" int rl_probe_gather_rate(int device, int active_lanes, double *lanes_
     while (__builtin_popcountll(mask) < active_lanes) mask |= 1ull << (rnd() % 64);
     const int iters = 2000, grid = n_cu * 2;
     float ms = 0.f;
-    if (hipMalloc((void **)&tab, 4 * 2048 * sizeof(float)) != hipSuccess || hipMalloc((void **)&sink, 4) != hipSuccess ||
-        hipMalloc((void **)&d_off, sizeof off) != hipSuccess || hipEventCreate(&e0) != hipSuccess ||
-        hipEventCreate(&e1) != hipSuccess || hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess ||
+    if (tab.alloc(4 * 2048 * sizeof(float)) || sink.alloc(4) || d_off.alloc(sizeof off) || e0.create() != hipSuccess ||
+        e1.create() != hipSuccess || st.create() != hipSuccess ||
         hipMemsetAsync(tab, 0, 4 * 2048 * sizeof(float), st) != hipSuccess ||
-        hipMemcpyAsync(d_off, off, sizeof off, hipMemcpyHostToDevice, st) != hipSuccess) {
-        rc = fail(RL_ERR_HIP, "gather probe: setup failed");
-    } else {
-        hipLaunchKernelGGL(gather_probe_kernel, dim3(grid), dim3(1024), 0, st, tab, d_off, mask, 10, sink);
-        (void)hipEventRecord(e0, st);
-        hipLaunchKernelGGL(gather_probe_kernel, dim3(grid), dim3(1024), 0, st, tab, d_off, mask, iters, sink);
-        (void)hipEventRecord(e1, st);
-        if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess || !(ms > 0.f))
-            rc = fail(RL_ERR_HIP, "gather probe: launch failed");
-    }
-    cleanup();
-    if (rc) return rc;
+        hipMemcpyAsync(d_off, off, sizeof off, hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(RL_ERR_HIP, "gather probe: setup failed");
+    hipLaunchKernelGGL(gather_probe_kernel, dim3(grid), dim3(1024), 0, st, tab, d_off, mask, 10, sink);
+    (void)hipEventRecord(e0, st);
+    hipLaunchKernelGGL(gather_probe_kernel, dim3(grid), dim3(1024), 0, st, tab, d_off, mask, iters, sink);
+    (void)hipEventRecord(e1, st);
+    if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess || !(ms > 0.f))
+        return fail(RL_ERR_HIP, "gather probe: launch failed");
     // 2 workgroups x 16 waves per CU, each iters x 8 wave-loads
     const double clk_per_wave_load = (double)ms * 1e-3 * clk / (2.0 * 16 * iters * 8);
     *lanes_per_clk_per_cu = (double)active_lanes / clk_per_wave_load;
@@ -1109,13 +1043,6 @@ extern "C" void rl_mcts_destroy(rl_mcts *m)
     if (!m) return;
     (void)hipSetDevice(m->device);
     if (m->c && m->c->stream) (void)hipStreamSynchronize(m->c->stream);
-    for (DevBuf *b : {&m->parent, &m->first_child, &m->next_sibling, &m->last_child, &m->n_children, &m->visits,
-                      &m->child_visits, &m->terminal, &m->crash, &m->reward, &m->action, &m->state, &m->pose,
-                      &m->answer, &m->n_nodes, &m->child, &m->exp_term, &m->keys, &m->logtab, &m->cstate, &m->cpose,
-                      &m->actions, &m->ranges, &m->edge, &m->mlp, &m->rposes, &m->vel, &m->first, &m->rranges,
-                      &m->roots, &m->best_a, &m->best_v, &m->best_n, &m->root_crash, &m->dr_keys, &m->dr_first,
-                      &m->dr_actions, &m->dr_visits, &m->dr_trace})
-        b->release();
     delete m;
 }
 
@@ -1145,7 +1072,7 @@ extern "C" int rl_mcts_create(rl_car *c, rl_method *h, rl_followgap *g, rl_polic
     }
     if ((long)q.n_trees * q.rollout_steps * q.num_rays >= (1L << 31) || (long)q.n_trees * q.max_nodes >= (1L << 31) / 11)
         return fail(RL_ERR_INVALID, "rl_mcts_create: n_trees * rollout_steps * num_rays and the node arrays must stay below 2^31");
-    rl_mcts *m = new (std::nothrow) rl_mcts();
+    std::unique_ptr<rl_mcts, decltype(&rl_mcts_destroy)> m(new (std::nothrow) rl_mcts(), rl_mcts_destroy);
     if (!m) return fail(RL_ERR_NOMEM, "out of host memory");
     m->c = c;
     m->h = h;
@@ -1173,39 +1100,24 @@ extern "C" int rl_mcts_create(rl_car *c, rl_method *h, rl_followgap *g, rl_polic
     mp.max_speed = q.max_speed;
     mp.crash_thresh = q.crash_thresh;
     const size_t K = q.n_trees, N = (size_t)q.n_trees * q.max_nodes, B = q.num_rays;
-    int rc = RL_OK;
-    if (hipSetDevice(m->device) != hipSuccess) rc = fail(RL_ERR_HIP, "rl_mcts_create: hipSetDevice failed");
-    for (DevBuf *b : {&m->parent, &m->first_child, &m->next_sibling, &m->last_child, &m->n_children, &m->visits,
-                      &m->child_visits, &m->terminal, &m->crash})
-        if (!rc) rc = b->ensure(N * 4);
-    if (!rc) rc = m->reward.ensure(N * 8);
-    if (!rc) rc = m->action.ensure(N * 8);
-    if (!rc) rc = m->state.ensure(N * 88);
-    if (!rc) rc = m->pose.ensure(N * 12);
-    if (!rc) rc = m->answer.ensure(N * 4);
-    for (DevBuf *b : {&m->n_nodes, &m->child, &m->exp_term, &m->keys, &m->first, &m->mlp, &m->best_v, &m->best_n})
-        if (!rc) rc = b->ensure(K * 4);
-    if (!rc) rc = m->best_a.ensure(K * 8);
-    if (!rc) rc = m->logtab.ensure(((size_t)q.max_nodes + 1) * 8);
-    if (!rc) rc = m->cstate.ensure(K * 88);
-    if (!rc) rc = m->roots.ensure(K * 96);
-    if (!rc) rc = m->cpose.ensure(K * 12);
-    if (!rc) rc = m->actions.ensure(K * mp.n_act * 16);
-    if (!rc) rc = m->ranges.ensure(K * B * 4);
-    if (!rc) rc = m->edge.ensure(B * 8);
-    if (!rc) rc = m->rposes.ensure(K * q.rollout_steps * 12);
-    if (!rc) rc = m->vel.ensure(K * q.rollout_steps * 8);
-    if (!rc) {
-        const std::vector<double> lt = mcts_log_table(q.max_nodes);
-        if (hipMemcpy(m->logtab.p, lt.data(), lt.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(m->edge.p, edge, B * 8, hipMemcpyHostToDevice) != hipSuccess)
-            rc = fail(RL_ERR_HIP, "rl_mcts_create: upload failed");
-    }
-    if (rc) {
-        rl_mcts_destroy(m);
-        return rc;
-    }
-    *out = m;
+    if (hipSetDevice(m->device) != hipSuccess) return fail(RL_ERR_HIP, "rl_mcts_create: hipSetDevice failed");
+    const size_t L = q.rollout_steps;
+    struct { DevBuf *b; size_t bytes; } need[] = {
+        {&m->parent, N * 4}, {&m->first_child, N * 4}, {&m->next_sibling, N * 4}, {&m->last_child, N * 4},
+        {&m->n_children, N * 4}, {&m->visits, N * 4}, {&m->child_visits, N * 4}, {&m->terminal, N * 4}, {&m->crash, N * 4},
+        {&m->reward, N * 8}, {&m->action, N * 8}, {&m->state, N * 88}, {&m->pose, N * 12}, {&m->answer, N * 4},
+        {&m->n_nodes, K * 4}, {&m->child, K * 4}, {&m->exp_term, K * 4}, {&m->keys, K * 4}, {&m->first, K * 4},
+        {&m->mlp, K * 4}, {&m->best_v, K * 4}, {&m->best_n, K * 4}, {&m->best_a, K * 8},
+        {&m->logtab, ((size_t)q.max_nodes + 1) * 8}, {&m->cstate, K * 88}, {&m->roots, K * 96}, {&m->cpose, K * 12},
+        {&m->actions, K * mp.n_act * 16}, {&m->ranges, K * B * 4}, {&m->edge, B * 8}, {&m->rposes, K * L * 12},
+        {&m->vel, K * L * 8}};
+    for (auto &n : need)
+        if (int rc = n.b->ensure(n.bytes)) return rc;
+    const std::vector<double> lt = mcts_log_table(q.max_nodes);
+    if (hipMemcpy(m->logtab.p, lt.data(), lt.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(m->edge.p, edge, B * 8, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(RL_ERR_HIP, "rl_mcts_create: upload failed");
+    *out = m.release();
     return RL_OK;
 }
 
@@ -1478,28 +1390,23 @@ extern "C" int rl_mcts_probe_ucb(int device, const double *reward, const int *vi
             return fail(RL_ERR_INVALID, "rl_mcts_probe_ucb: visits >= 1 and 1 <= sum <= 2^24 required (entry %zu)", i);
         s_max = std::max(s_max, sum[i]);
     }
-    int ndev = rl_device_count();
-    if (ndev <= 0) return fail(RL_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
-    if (n == 0) return RL_OK;
+    int rc = check_device(device);
+    if (rc || n == 0) return rc;
     HIPCHK(hipSetDevice(device));
     const std::vector<double> lt = mcts_log_table(s_max);
     DevBuf dr, dv, ds, dl, dout;
-    int rc;
     if ((rc = dr.ensure(n * 8)) || (rc = dv.ensure(n * 4)) || (rc = ds.ensure(n * 4)) || (rc = dl.ensure(lt.size() * 8)) ||
-        (rc = dout.ensure(n * 8))) {
-    } else if (hipMemcpy(dr.p, reward, n * 8, hipMemcpyHostToDevice) != hipSuccess ||
-               hipMemcpy(dv.p, visits, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-               hipMemcpy(ds.p, sum, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-               hipMemcpy(dl.p, lt.data(), lt.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-        rc = fail(RL_ERR_HIP, "rl_mcts_probe_ucb: upload failed");
-    } else {
-        const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
-        hipLaunchKernelGGL(mcts_ucb_probe_kernel, dim3(grid), dim3(256), 0, nullptr, (const double *)dr.p,
-                           (const int *)dv.p, (const int *)ds.p, (const double *)dl.p, (long)n, C, (double *)dout.p);
-        if (hipMemcpy(out, dout.p, n * 8, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(RL_ERR_HIP, "rl_mcts_probe_ucb: kernel or download failed");
-    }
-    for (DevBuf *b : {&dr, &dv, &ds, &dl, &dout}) b->release();
-    return rc;
+        (rc = dout.ensure(n * 8)))
+        return rc;
+    if (hipMemcpy(dr.p, reward, n * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dv.p, visits, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(ds.p, sum, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dl.p, lt.data(), lt.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(RL_ERR_HIP, "rl_mcts_probe_ucb: upload failed");
+    const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(mcts_ucb_probe_kernel, dim3(grid), dim3(256), 0, nullptr, (const double *)dr.p,
+                       (const int *)dv.p, (const int *)ds.p, (const double *)dl.p, (long)n, C, (double *)dout.p);
+    if (hipMemcpy(out, dout.p, n * 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(RL_ERR_HIP, "rl_mcts_probe_ucb: kernel or download failed");
+    return RL_OK;
 }

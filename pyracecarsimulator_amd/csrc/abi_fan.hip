@@ -32,7 +32,8 @@ extern "C" int rl_method_create(rl_map *m, int kind, float max_range_px, int the
     if ((kind == RL_CDDT || kind == RL_GIANT_LUT) && (theta_disc < 2 || theta_disc > 65536))
         return fail(RL_ERR_INVALID, "theta_disc must be in [2, 65536] for CDDT / GiantLUT (got %d)",
                     theta_disc);
-    rl_method *h = new (std::nothrow) rl_method();
+    std::unique_ptr<rl_method, decltype(&rl_method_destroy)> own(new (std::nothrow) rl_method(), rl_method_destroy);
+    rl_method *h = own.get();
     if (!h) return fail(RL_ERR_NOMEM, "out of host memory");
     h->map = m;
     h->kind = kind;
@@ -48,8 +49,8 @@ extern "C" int rl_method_create(rl_map *m, int kind, float max_range_px, int the
             rl_method *r = nullptr;
             const int rc = rl_method_create(rm, kind, max_range_px, theta_disc, &r);
             if (rc) {
-                const std::string keep = last_error();
-                rl_method_destroy(h);
+                const std::string keep = last_error();     // (the failing replica's message outlives the clean-up)
+                own.reset();
                 set_last_error(keep);
                 return rc;
             }
@@ -58,7 +59,7 @@ extern "C" int rl_method_create(rl_map *m, int kind, float max_range_px, int the
         }
         h->pool = std::make_unique<MultiPool>();
         h->pool->start(devs);
-        *out = h;
+        *out = own.release();
         return RL_OK;
     }
     if (kind == RL_CDDT) {
@@ -70,18 +71,14 @@ extern "C" int rl_method_create(rl_map *m, int kind, float max_range_px, int the
             int rc_ = hipSetDevice(m->device) == hipSuccess ? map_build_tables(m) : fail(RL_ERR_HIP, "hipSetDevice failed");
             if (rc_) {
                 m->want_edges = false;
-                delete h;
                 return rc_;
             }
         }
     }
-    if (hipSetDevice(m->device) != hipSuccess ||
-        hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
-        rl_method_destroy(h);
+    if (hipSetDevice(m->device) != hipSuccess || h->stream.create() != hipSuccess || h->ev0.create() != hipSuccess ||
+        h->ev1.create() != hipSuccess)
         return fail(RL_ERR_HIP, "stream/event creation failed");
-    }
-    *out = h;
+    *out = own.release();
     return RL_OK;
 }
 
@@ -96,38 +93,6 @@ extern "C" void rl_method_destroy(rl_method *h)
     }
     if (h->map) (void)hipSetDevice(h->map->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->poses.release();
-    h->outs.release();
-    h->hits.release();
-    h->steps.release();
-    h->edge.release();
-    h->flag.release();
-    h->cars.release();
-    for (DevBuf *b : {&h->pf_ang, &h->pf_obs, &h->pf_w}) b->release();
-    if (h->sensor) (void)hipFree(h->sensor);
-    if (h->pin) (void)hipHostFree(h->pin);
-    if (h->pin_flag) (void)hipHostFree(h->pin_flag);
-    for (LaunchCtx &c : h->ctx) c.release();
-    for (TableDep *d : {&h->pdt_dep, &h->lut_dep, &h->cddt_dep, &h->blpad_dep})
-        if (d->ev) (void)hipEventDestroy(d->ev);
-    for (auto &ft : h->fan_tabs) {
-        if (ft.dep.ev) (void)hipEventDestroy(ft.dep.ev);
-        ft.tab.release();
-    }
-    h->pdt.release();
-    for (DevBuf *b : {&h->cmap, &h->cval, &h->cidx, &h->ctab, &h->cnum}) b->release();
-    if (h->pin_cnum) (void)hipHostFree(h->pin_cnum);
-    h->blpad.release();
-    h->lut.release();
-    for (DevBuf *b : {&h->cd_cos, &h->cd_sin, &h->cd_trans, &h->cd_width, &h->cd_boff, &h->cd_offsets,
-                      &h->cd_xs2, &h->cd_cursor, &h->cd_tmp, &h->cd_hdr, &h->cd_tab})
-        b->release();
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    for (hipEvent_t e : h->slice_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
@@ -345,7 +310,7 @@ static int acquire_ctx(rl_method *h, hipStream_t stream, LaunchCtx **out)
 // after (re)building a table on `stream`
 static int table_built(TableDep &d, hipStream_t stream)
 {
-    if (!d.ev) HIPCHK(hipEventCreateWithFlags(&d.ev, hipEventDisableTiming));
+    HIPCHK(d.ev.create(hipEventDisableTiming));
     HIPCHK(hipEventRecord(d.ev, stream));
     d.built_on = stream;
     d.pending = true;
@@ -794,7 +759,7 @@ static int ensure_step_map(rl_method *h, hipStream_t stream)
         if ((rc = h->cidx.ensure((size_t)cf.nb * sizeof(uint32_t)))) return rc;
         if ((rc = h->ctab.ensure((size_t)cap * sizeof(float)))) return rc;
         if ((rc = h->cnum.ensure(2 * sizeof(uint32_t)))) return rc;
-        if (!h->pin_cnum) HIPCHK(hipHostMalloc((void **)&h->pin_cnum, 2 * sizeof(uint32_t)));
+        if (!h->pin_cnum) HIPCHK(h->pin_cnum.alloc(2 * sizeof(uint32_t)));
         HIPCHK(hipMemsetAsync(h->cval.p, 0, (size_t)cf.nb * sizeof(float), stream));
         const size_t n_cells = (size_t)m->rows * m->cols;
         hipLaunchKernelGGL(code_mark_kernel, dim3((unsigned)std::min<size_t>((n_cells + 255) / 256, (size_t)m->n_cu * 8)), dim3(256),
@@ -1436,11 +1401,8 @@ static int pose_marks(rl_method *h, int n_poses, hipStream_t stream, int &mark, 
 static int pin_ensure(rl_method *h, size_t bytes)
 {
     if (bytes <= h->pin_cap) return RL_OK;
-    if (h->pin) (void)hipHostFree(h->pin);
-    h->pin = nullptr;
     h->pin_cap = 0;
-    if (hipHostMalloc(&h->pin, bytes * 2, hipHostMallocDefault) != hipSuccess)
-        return fail(RL_ERR_NOMEM, "hipHostMalloc(%zu) failed", bytes * 2);
+    if (h->pin.alloc(bytes * 2) != hipSuccess) return fail(RL_ERR_NOMEM, "pinned allocation of %zu bytes failed", bytes * 2);
     h->pin_cap = bytes * 2;
     return RL_OK;
 }
@@ -1490,14 +1452,14 @@ int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_r
         HIPCHK(hipMemcpyAsync(h->poses.p, poses, (size_t)n_poses * 3 * sizeof(float),
                               hipMemcpyHostToDevice, h->stream));
     }
-    const float *d_poses = zc ? (const float *)h->pin : (const float *)h->poses.p;
+    char *const pin = h->pin;
+    const float *d_poses = zc ? (const float *)pin : (const float *)h->poses.p;
     CrashParams cp{nullptr, 0.0, nullptr, 1, 0};
     const bool crash_direct = first_crashed && n_poses <= 512;
     if (first_crashed) {
         if ((rc = upload_edge(h, edge, num_rays))) return rc;
         if ((rc = h->flag.ensure(sizeof(int)))) return rc;
-        if (!h->pin_flag && hipHostMalloc((void **)&h->pin_flag, 64, hipHostMallocDefault) != hipSuccess)
-            return fail(RL_ERR_NOMEM, "hipHostMalloc(64) failed");
+        if (!h->pin_flag && h->pin_flag.alloc(64) != hipSuccess) return fail(RL_ERR_NOMEM, "pinned allocation of 64 bytes failed");
         cp.edge = (const double *)h->edge.p;
         cp.thresh = crash_thresh;
         if (crash_direct) {
@@ -1513,7 +1475,7 @@ int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_r
         }
     }
     float *d_out = (outs || !first_crashed)
-                       ? (direct_out ? outs : zc ? (float *)((char *)h->pin + off_out) : (float *)h->outs.p)
+                       ? (direct_out ? outs : zc ? (float *)(pin + off_out) : (float *)h->outs.p)
                        : nullptr;
     if (outs && !zc && !first_crashed && !hits && !steps && h->overlap_min_rays > 0 &&
         n_rays >= (size_t)h->overlap_min_rays && n_poses >= 4 && !h->timing &&
@@ -1523,7 +1485,7 @@ int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_r
         // methods keep one launch: their kernels take 2-4 % of the call, and the theta-major CDDT search wants the
         // whole batch (>= 32768 poses) in one launch
         constexpr int S = 4;
-        if (!h->copy_stream) HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+        HIPCHK(h->copy_stream.create());
         const int per = (n_poses + S - 1) / S;
         const uint64_t base_off = h->ray_offset;
         rc = RL_OK;
@@ -1533,7 +1495,7 @@ int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_r
             h->ray_offset = base_off + r0;               // noise stays keyed by the global ray id
             rc = launch_fan(h, d_poses + (size_t)p0 * 3, np, fov, num_rays, d_out + r0, nullptr, nullptr, nullptr, h->stream);
             if (rc) break;
-            if (!h->slice_ev[k] && hipEventCreateWithFlags(&h->slice_ev[k], hipEventDisableTiming) != hipSuccess) {
+            if (h->slice_ev[k].create(hipEventDisableTiming) != hipSuccess) {
                 rc = fail(RL_ERR_HIP, "hipEventCreate failed");
                 break;
             }
@@ -1576,7 +1538,7 @@ int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_r
     int flag = first_crashed ? *h->pin_flag : 0;
     if (crash_direct && flag == INT_MAX) flag = -(n_poses + 1);
     if (zc && !direct_out) {
-        if (outs) memcpy(outs, (char *)h->pin + off_out, n_rays * sizeof(float));
+        if (outs) memcpy(outs, pin + off_out, n_rays * sizeof(float));
     }
     if (first_crashed) *first_crashed = flag;      // first crashed pose, or -(n_poses + 1)
     return RL_OK;
@@ -1594,8 +1556,9 @@ int rays_host(rl_method *h, const float *ins, float *outs, int n)
         const size_t off_out = ((size_t)n * 3 * sizeof(float) + 255) & ~(size_t)255;
         if ((rc = pin_ensure(h, off_out + (size_t)n * sizeof(float)))) return rc;
         memcpy(h->pin, ins, (size_t)n * 3 * sizeof(float));
-        float *p_out = (float *)((char *)h->pin + off_out);
-        if ((rc = launch_rays(h, (const float *)h->pin, n, p_out, nullptr, nullptr, h->stream))) return rc;
+        char *const pin = h->pin;
+        float *p_out = (float *)(pin + off_out);
+        if ((rc = launch_rays(h, (const float *)pin, n, p_out, nullptr, nullptr, h->stream))) return rc;
         HIPCHK(hipStreamSynchronize(h->stream));
         memcpy(outs, p_out, (size_t)n * sizeof(float));
         return RL_OK;
@@ -1741,17 +1704,12 @@ extern "C" int rl_set_sensor_model(rl_method *h, const double *table, int width)
     int rc = set_device(h->map);
     if (rc) return rc;
     const size_t bytes = (size_t)width * width * sizeof(double);
-    double *fresh = nullptr;
-    if (hipMalloc((void **)&fresh, bytes) != hipSuccess) return fail(RL_ERR_NOMEM, "hipMalloc(%zu) failed", bytes);
-    if (hipMemcpy(fresh, table, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(fresh);
+    DevPtr<double> fresh;
+    if ((rc = fresh.alloc(bytes))) return rc;
+    if (hipMemcpy(fresh, table, bytes, hipMemcpyHostToDevice) != hipSuccess)
         return fail(RL_ERR_HIP, "rl_set_sensor_model: the copy of the table failed");
-    }
-    if (h->sensor) {
-        HIPCHK(hipDeviceSynchronize());      // launches of other streams may still read the old table
-        (void)hipFree(h->sensor);
-    }
-    h->sensor = fresh;
+    if (h->sensor) HIPCHK(hipDeviceSynchronize());      // launches of other streams may still read the old table
+    h->sensor = std::move(fresh);
     h->sensor_w = width;
     return RL_OK;
 }
@@ -1910,7 +1868,7 @@ extern "C" int rl_pf_create(rl_method *h, const rl_pf_params *p, const float *an
     if ((rc = pf_kind_of(h, &kind))) return rc;
     if (!h->sensor_w) return fail(RL_ERR_INVALID, "rl_pf_create: no sensor model set (rl_set_sensor_model)");
     if ((rc = set_device(h->map))) return rc;
-    std::unique_ptr<rl_pf> f(new (std::nothrow) rl_pf);
+    std::unique_ptr<rl_pf, decltype(&rl_pf_destroy)> f(new (std::nothrow) rl_pf, rl_pf_destroy);
     if (!f) return fail(RL_ERR_NOMEM, "rl_pf_create: out of memory");
     f->h = h;
     f->device = h->map->device;
@@ -1925,13 +1883,9 @@ extern "C" int rl_pf_create(rl_method *h, const rl_pf_params *p, const float *an
         {&f->omega, P * 8}, {&f->part, P * 8}, {&f->cum, P * 8}, {&f->anc, P * 4}, {&f->tot, (1 + MCL_SUMS) * NB * 8},
         {&f->base, NB * 8}, {&f->scal, 8}};
     for (auto &n : need)
-        if ((rc = n.b->ensure(n.bytes))) break;
-    if (!rc && hipMemcpy(f->ang.p, angles, (size_t)f->A * 4, hipMemcpyHostToDevice) != hipSuccess)
-        rc = fail(RL_ERR_HIP, "rl_pf_create: the copy of the angles failed");
-    if (rc) {
-        rl_pf_destroy(f.release());
-        return rc;
-    }
+        if ((rc = n.b->ensure(n.bytes))) return rc;
+    if (hipMemcpy(f->ang.p, angles, (size_t)f->A * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(RL_ERR_HIP, "rl_pf_create: the copy of the angles failed");
     *out = f.release();
     return RL_OK;
 }
@@ -1940,9 +1894,6 @@ extern "C" void rl_pf_destroy(rl_pf *f)
 {
     if (!f) return;
     (void)hipSetDevice(f->device);       // (every call is synchronous: nothing of the filter's is in flight, h is not touched)
-    for (DevBuf *b : {&f->ang, &f->cur, &f->prop, &f->q, &f->w, &f->lik, &f->omega, &f->part, &f->cum, &f->anc, &f->tot,
-                      &f->base, &f->scal, &f->odom, &f->obs, &f->est, &f->neff, &f->flags})
-        b->release();
     delete f;
 }
 

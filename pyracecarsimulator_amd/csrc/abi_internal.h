@@ -1,11 +1,14 @@
-// abi_internal.h — what the translation units of libscan_amd.so share: the handles behind include/scanlib.h's opaque
-// pointers, the error slot, and the few internal entry points one unit calls in another.
-//   abi_map.hip    errors, pinned host blocks, rl_map_* (EDT, bit map, edge list)
+// abi_internal.h — what the translation units of libscan_amd.so share: the owners of every device resource (DevBuf,
+// DevPtr, Pinned, Stream, Event), the handles behind include/scanlib.h's opaque pointers, the error slot, and the few
+// internal entry points one unit calls in another.
+//   abi_map.hip    errors, check_device, the caller's pinned host blocks, rl_map_* (EDT, bit map, edge list, stamps)
 //   abi_fan.hip    rl_method_*: options, derived tables, the launch planner's C ABI, every fan / ray launch, the
-//                  device-pointer entry points, the single-device host-pointer paths, the fused crash test
+//                  device-pointer entry points, the single-device host-pointer paths, the fused crash test; the
+//                  particle-filter weights (repeat-angle scans, sensor model) and localisation (rl_pf_*)
 //   abi_multi.hip  the host-pointer entry points and their multi-device forms (run_blocks below: one block per device)
 //   abi_car.hip    roll-out generator, FollowGap, the policy network, closed-loop FollowGap / policy roll-outs,
-//                  batched races, 16-bit ranges, probes, the car-outline table
+//                  batched races and the race scan, the MCTS planner and its closed-loop drive (rl_mcts_*), 16-bit
+//                  ranges, probes, the car-outline table and cells
 #pragma once
 // (the units are built with -fvisibility=hidden: only the C ABI leaves the library)
 #pragma GCC visibility push(default)
@@ -31,6 +34,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 using namespace scan;
@@ -56,6 +60,114 @@ int fail_map_broken();           // RL_ERR_INVALID: what every call on a multi-d
 bool in_host_block(const void *p, size_t bytes, int device = -1);
 
 // ------------------------------------------------------------------------------
+// owners: every device buffer, pinned block, stream and event of a handle is held by one of these.  Move-only; each
+// gives back what it holds in its destructor, so a handle is freed by `delete` and a failed create by leaving scope.
+// None of them calls hipSetDevice: a *_destroy makes the handle's device current (and synchronises its streams) BEFORE
+// it deletes.  This header is the only place that frees device memory, streams or events.
+// ------------------------------------------------------------------------------
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p, cap = o.cap;
+            o.p = nullptr, o.cap = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    // exactly `bytes` (what was held is freed first): tables whose size is known
+    int alloc(size_t bytes)
+    {
+        release();
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return fail(RL_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+        }
+        cap = bytes;
+        return RL_OK;
+    }
+    // at least `bytes`, grown by a quarter when too small: per-call staging (`cap` changes when the buffer was replaced)
+    int ensure(size_t bytes) { return bytes <= cap ? (int)RL_OK : alloc(bytes + bytes / 4 + 256); }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+// a device array of T of exactly the size asked for; reads as the T* the launches take
+template <class T>
+struct DevPtr {
+    DevBuf buf;
+    int alloc(size_t bytes) { return buf.alloc(bytes); }
+    void release() { buf.release(); }
+    operator T *() const { return (T *)buf.p; }
+};
+
+// one raw handle and the call that gives it back (pinned blocks, streams, events)
+template <class H, hipError_t (*Free)(H)>
+struct Owned {
+    H h = nullptr;
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    Owned(Owned &&o) noexcept : h(o.h) { o.h = nullptr; }
+    Owned &operator=(Owned &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            h = o.h;
+            o.h = nullptr;
+        }
+        return *this;
+    }
+    ~Owned() { release(); }
+    void release()
+    {
+        if (h) (void)Free(h);
+        h = nullptr;
+    }
+};
+static inline hipError_t free_pinned(void *p) { return hipHostFree(p); }
+static inline hipError_t free_stream(hipStream_t s) { return hipStreamDestroy(s); }
+static inline hipError_t free_event(hipEvent_t e) { return hipEventDestroy(e); }
+
+// pinned host memory of T, hipHostMallocDefault as at every site of the handles (what was held is freed first)
+template <class T>
+struct Pinned : Owned<void *, free_pinned> {
+    hipError_t alloc(size_t bytes)
+    {
+        release();
+        const hipError_t e = hipHostMalloc(&h, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) h = nullptr;
+        return e;
+    }
+    operator T *() const { return (T *)h; }
+};
+// create() makes the stream / event on the first call and is a pointer test afterwards (those made on first use)
+struct Stream : Owned<hipStream_t, free_stream> {
+    hipError_t create() { return h ? hipSuccess : hipStreamCreateWithFlags(&h, hipStreamNonBlocking); }
+    operator hipStream_t() const { return h; }
+};
+struct Event : Owned<hipEvent_t, free_event> {
+    hipError_t create(unsigned flags = hipEventDefault) { return h ? hipSuccess : hipEventCreateWithFlags(&h, flags); }
+    operator hipEvent_t() const { return h; }
+};
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_constructible<DevPtr<float>>::value &&
+                  !std::is_copy_constructible<Pinned<int>>::value && !std::is_copy_constructible<Stream>::value &&
+                  !std::is_copy_constructible<Event>::value,
+              "an owner frees what it holds exactly once");
+
+// ------------------------------------------------------------------------------
 // handles
 // ------------------------------------------------------------------------------
 struct rl_map {
@@ -66,25 +178,25 @@ struct rl_map {
     int clock_khz = 0;
     int rows = 0, cols = 0;
     float res = 0, ox = 0, oy = 0, oyaw = 0;
-    uint8_t *d_occ = nullptr;
-    uint8_t *d_occ_base = nullptr;   // rl_map_stamp_cells: the occupancy as created / last rl_map_update'd (made at the first stamp)
-    int32_t *d_stamp = nullptr;      // ... the cell indices of the stamp in place (restored by the next one)
-    int32_t *pin_stamp = nullptr;    // ... pinned, device-mapped landing buffer of a call's indices (no staging copy)
+    DevPtr<uint8_t> d_occ;
+    DevPtr<uint8_t> d_occ_base;      // rl_map_stamp_cells: the occupancy as created / last rl_map_update'd (made at the first stamp)
+    DevPtr<int32_t> d_stamp;         // ... the cell indices of the stamp in place (restored by the next one)
+    Pinned<int32_t> pin_stamp;       // ... pinned, device-mapped landing buffer of a call's indices (no staging copy)
     int stamp_cap = 0, n_stamped = 0;
-    int *d_g = nullptr;          // EDT pass-1 scratch
-    float *d_dt = nullptr;
-    uint32_t *d_bits = nullptr;
+    DevPtr<int> d_g;             // EDT pass-1 scratch
+    DevPtr<float> d_dt;
+    DevPtr<uint32_t> d_bits;
     int bits_stride = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;
     std::atomic<uint64_t> epoch{0};   // bumped by rl_map_update; derived tables rebuild lazily
     MapParams mp{};
-    MapParams *d_mp = nullptr;   // device copy (kernels that take the map by pointer)
+    DevPtr<MapParams> d_mp;      // device copy (kernels that take the map by pointer)
     // edge cells (occupied with a free 4-neighbour), the input of every CDDT table of this map: built
     // with the other map tables once a CDDT method exists, so that a table rebuild knows the count on
     // the host without a read-back of its own (rl_map_update synchronises anyway)
     bool want_edges = false;
-    uint32_t *d_edges = nullptr, *d_n_edges = nullptr;
-    uint32_t *pin_n_edges = nullptr;
+    DevPtr<uint32_t> d_edges, d_n_edges;
+    Pinned<uint32_t> pin_n_edges;
     uint32_t n_edges = 0;
     int n_cu = 256;
     std::mutex mu;
@@ -102,30 +214,6 @@ struct rl_map {
     std::atomic<bool> broken{false};
 };
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes)
-    {
-        if (bytes <= cap) return RL_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes + bytes / 4 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) return fail(RL_ERR_NOMEM, "hipMalloc(%zu) failed: %s", want,
-                                         hipGetErrorString(e));
-        cap = want;
-        return RL_OK;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 // Per-launch scratch of a method (pose records, tile order, binning histograms, crash marks) is
 // kept PER STREAM: a *_device call only enqueues work, so a second call on another stream may run
 // concurrently with the first on the GPU (bench.py pipelines consecutive batches on two streams so
@@ -141,17 +229,13 @@ struct LaunchCtx {
     DevBuf left_rec, left_cnt;     // hand-off march: the leftover list (rm_leftover_kernel), one region per wave of the main grid
     DevBuf pf_r;                   // particle-filter weights of the table kinds: the ranges between pf_angles_kernel and pf_eval_kernel
     int crash_epoch = 0;           // mark value of the last per-pose crash launch (pose_marks)
-    void release()
-    {
-        for (DevBuf *b : {&rec, &rec_sorted, &order, &keys, &hist, &pose_first, &dbg, &d0, &cddt_r, &left_rec, &left_cnt, &pf_r}) b->release();
-    }
 };
 constexpr int N_LAUNCH_CTX = 8;      // (HIP's default 4 hardware queues carry 4 concurrent streams; GPU_MAX_HW_QUEUES=8 carries 8)
 
 // A derived table (step map, GiantLUT, CDDT) is built lazily on the stream of the call that needs
 // it first; launches on OTHER streams must not start before the build has finished.
 struct TableDep {
-    hipEvent_t ev = nullptr;
+    Event ev;                    // (made by the first build)
     hipStream_t built_on = nullptr;
     bool pending = false;
 };
@@ -333,17 +417,17 @@ struct rl_method {
     DevBuf pdt;                  // EDT with a border of `pad` cells of -1 (stream kernel)
     int pad = 0, pstride = 0;    // pstride: elements per row (row-major) | M (tiled, see pdt_tiled_byte)
     uint64_t pdt_epoch = ~0ull;  // map epoch the padded copy was built from
-    hipStream_t stream = nullptr;
-    hipStream_t copy_stream = nullptr;   // big host-pointer calls: the D2H copy of pose slice k overlaps the march of slice k+1
-    hipEvent_t slice_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Stream stream;
+    Stream copy_stream;                  // big host-pointer calls (made by the first one): the D2H copy of pose slice k overlaps the march of slice k+1
+    Event slice_ev[4];
     int overlap_min_rays = 1 << 24;      // ... from this many rays per call (0 = never); below ~16 k poses the slices cost more than they hide
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Event ev0, ev1;
     bool timed = false;
     DevBuf poses, outs, hits, steps, edge, flag;
     DevBuf cars;                 // rl_calc_range_fan_cars: the cars' (x, y, theta) rows
     // particle-filter weights (pf_kernels.h): the sensor-model table (rl_set_sensor_model; width 0 = none set) and the
     // host-pointer forms' staging of angles, observation and weights
-    double *sensor = nullptr;
+    DevPtr<double> sensor;
     int sensor_w = 0;
     DevBuf pf_ang, pf_obs, pf_w;
     int pf_block = 0;            // particles per tile of the weight kernels (0: sized from the shape, make_pf)
@@ -361,7 +445,7 @@ struct rl_method {
     uint64_t fan_clock = 0;
     // small host calls (scan(): one pose, scanMany(): a roll-out): poses and ranges go through ONE
     // pinned, device-mapped host buffer the kernels read / write directly — no staging copies
-    void *pin = nullptr;
+    Pinned<char> pin;
     size_t pin_cap = 0;
     int pinned_max_rays = 262144; // 0 = always stage through device buffers
     int direct_max_rays = 1 << 21; // a result buffer in a pinned block of rl_host_alloc is written by the kernel itself
@@ -370,7 +454,7 @@ struct rl_method {
                                   // kernel's stores over PCIe (4096 poses: 394 vs 449 us; a tie at 2048:
                                   // profiles/r04/host_pointer_rate.txt)
     std::vector<double> edge_host; // the car-outline table last uploaded to `edge` (re-sent only when it changes)
-    int *pin_flag = nullptr;       // pinned landing slot for the crash index
+    Pinned<int> pin_flag;          // pinned landing slot for the crash index
     int tile_stripe = -1;        // binning order: tile rows per stripe walked column-major (rm_kernels.h tile_key); 0: row-major, -1: by xcd_bands
     int bin_ppw = POSES_PER_WG;  // ... poses per workgroup of those kernels
     int pdt_tiled = -1;          // layout the padded copy was built with
@@ -380,7 +464,7 @@ struct rl_method {
     // the float32 step map by ensure_step_map; code_n = palette entries with the two stop codes, 0 = none (option off,
     // geometry does not fit, or more distinct steps than plan::CODE_MAX_ENTRIES)
     DevBuf cmap, cval, cidx, ctab, cnum;
-    uint32_t *pin_cnum = nullptr;
+    Pinned<uint32_t> pin_cnum;   // (made with the first code map)
     int code_n = 0;
     int code_built = -1;         // code_map value the tables were built for
     int cstride = 0;             // M of the code map's address
@@ -420,6 +504,7 @@ struct MultiCall {
 };
 
 int set_device(const rl_map *m);
+int check_device(int device);                       // RL_ERR_NO_DEVICE unless `device` names a visible HIP device; abi_map.hip
 int map_build_tables(rl_map *m);                    // EDT + bit map (+ edge list once a CDDT method exists); abi_map.hip
 void host_sincosf(float x, float &s, float &c);      // host twin of scan::det_sincosf (abi_map.hip)
 

@@ -64,6 +64,7 @@ extern "C" int rl_host_alloc(size_t bytes, void **out)
     if (!out || bytes == 0) return fail(RL_ERR_INVALID, "rl_host_alloc: bad arguments");
     if (rl_device_count() <= 0) return fail(RL_ERR_NO_DEVICE, "no HIP device available");
     void *p = nullptr;
+    // (this block and its hipHostFree in rl_host_free are the caller's: the one allocation of the library no owner holds)
     // (portable + mapped: every device of a multi-device handle writes its pose block's ranges straight into it)
     if (hipHostMalloc(&p, bytes, hipHostMallocPortable | hipHostMallocMapped) != hipSuccess)
         return fail(RL_ERR_NOMEM, "hipHostMalloc(%zu) failed", bytes);
@@ -108,6 +109,14 @@ int set_device(const rl_map *m)
     return RL_OK;
 }
 
+int check_device(int device)
+{
+    const int ndev = rl_device_count();
+    if (ndev <= 0) return fail(RL_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(RL_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
+    return RL_OK;
+}
+
 // ------------------------------------------------------------------------------
 // map
 // ------------------------------------------------------------------------------
@@ -137,6 +146,14 @@ void host_sincosf(float x, float &s, float &c)
     c = cc;
 }
 
+// The map's later allocations (edge list, stamp base, stamp indices) went through HIPCHK before the owners held them:
+// their failure stays RL_ERR_HIP, not the RL_ERR_NOMEM DevBuf::alloc answers, with alloc's message behind `what`.
+static int alloc_failed(const char *what)
+{
+    const std::string why = last_error();
+    return fail(RL_ERR_HIP, "%s: %s", what, why.c_str());
+}
+
 int map_build_tables(rl_map *m)
 {
     // K0: exact EDT + bit-packed occupancy, all on the device
@@ -148,10 +165,10 @@ int map_build_tables(rl_map *m)
     hipLaunchKernelGGL(pack_bits_kernel, dim3((m->bits_stride + 255) / 256, rows), dim3(256), 0,
                        m->stream, m->d_occ, rows, cols, m->bits_stride, m->d_bits);
     if (m->want_edges) {
-        if (!m->d_edges) {
-            HIPCHK(hipMalloc((void **)&m->d_edges, (size_t)rows * cols * sizeof(uint32_t)));
-            HIPCHK(hipMalloc((void **)&m->d_n_edges, 256));
-            HIPCHK(hipHostMalloc((void **)&m->pin_n_edges, 64, hipHostMallocDefault));
+        if (!m->pin_n_edges) {                       // (the last of the three: a failure before it starts over)
+            if (m->d_edges.alloc((size_t)rows * cols * sizeof(uint32_t)) || m->d_n_edges.alloc(256))
+                return alloc_failed("device allocation for the edge list failed");
+            HIPCHK(m->pin_n_edges.alloc(64));
         }
         HIPCHK(hipMemsetAsync(m->d_n_edges, 0, 4, m->stream));
         hipLaunchKernelGGL(cddt_edges_kernel, dim3((cols + 255) / 256, (rows + EDGE_ROWS_PER_WG - 1) / EDGE_ROWS_PER_WG),
@@ -173,12 +190,10 @@ extern "C" int rl_map_create(const uint8_t *occ, int rows, int cols, float res, 
         return fail(RL_ERR_INVALID, "rl_map_create: rows/cols must be in [1,16384] (got %dx%d)",
                     rows, cols);
     if (!(res > 0.0f)) return fail(RL_ERR_INVALID, "rl_map_create: resolution must be > 0");
-    int ndev = rl_device_count();
-    if (ndev <= 0)
-        return fail(RL_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev)
-        return fail(RL_ERR_NO_DEVICE, "device %d out of range (have %d)", device, ndev);
-    rl_map *m = new (std::nothrow) rl_map();
+    int rc = check_device(device);
+    if (rc) return rc;
+    std::unique_ptr<rl_map, decltype(&rl_map_destroy)> own(new (std::nothrow) rl_map(), rl_map_destroy);
+    rl_map *m = own.get();
     if (!m) return fail(RL_ERR_NOMEM, "out of host memory");
     m->device = device;
     m->rows = rows;
@@ -188,28 +203,19 @@ extern "C" int rl_map_create(const uint8_t *occ, int rows, int cols, float res, 
     m->oy = oy;
     m->oyaw = oyaw;
     m->bits_stride = (cols + 31) / 32;
-    auto bail = [&](int code) {
-        rl_map_destroy(m);
-        return code;
-    };
-    if (hipSetDevice(device) != hipSuccess) return bail(fail(RL_ERR_HIP, "hipSetDevice failed"));
+    if (hipSetDevice(device) != hipSuccess) return fail(RL_ERR_HIP, "hipSetDevice failed");
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
         m->n_cu = prop.multiProcessorCount;
         m->clock_khz = prop.clockRate;
     }
     const size_t n = (size_t)rows * cols;
-    if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc((void **)&m->d_occ, n) != hipSuccess ||
-        hipMalloc((void **)&m->d_g, n * sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&m->d_dt, n * sizeof(float)) != hipSuccess ||
-        hipMalloc((void **)&m->d_bits, (size_t)rows * m->bits_stride * sizeof(uint32_t)) !=
-            hipSuccess)
-        return bail(fail(RL_ERR_NOMEM, "device allocation for a %dx%d map failed", rows, cols));
+    if (m->stream.create() != hipSuccess || m->d_occ.alloc(n) || m->d_g.alloc(n * sizeof(int)) ||
+        m->d_dt.alloc(n * sizeof(float)) || m->d_bits.alloc((size_t)rows * m->bits_stride * sizeof(uint32_t)))
+        return fail(RL_ERR_NOMEM, "device allocation for a %dx%d map failed", rows, cols);
     if (hipMemcpyAsync(m->d_occ, occ, n, hipMemcpyHostToDevice, m->stream) != hipSuccess)
-        return bail(fail(RL_ERR_HIP, "map upload failed"));
-    int rc = map_build_tables(m);
-    if (rc != RL_OK) return bail(rc);
+        return fail(RL_ERR_HIP, "map upload failed");
+    if ((rc = map_build_tables(m))) return rc;
 
     MapParams &p = m->mp;
     p.dt = m->d_dt;
@@ -225,10 +231,9 @@ extern "C" int rl_map_create(const uint8_t *occ, int rows, int cols, float res, 
     p.oy = oy;
     p.wa = -oyaw;                                   // PyOMap: world_angle = -yaw
     host_sincosf(p.wa, p.wa_sin, p.wa_cos);
-    if (hipMalloc((void **)&m->d_mp, sizeof(MapParams)) != hipSuccess ||
-        hipMemcpy(m->d_mp, &m->mp, sizeof(MapParams), hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(RL_ERR_NOMEM, "map parameter upload failed"));
-    *out = m;
+    if (m->d_mp.alloc(sizeof(MapParams)) || hipMemcpy(m->d_mp, &m->mp, sizeof(MapParams), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(RL_ERR_NOMEM, "map parameter upload failed");
+    *out = own.release();
     return RL_OK;
 }
 
@@ -237,14 +242,15 @@ extern "C" int rl_map_create_multi(const uint8_t *occ, int rows, int cols, float
 {
     if (!occ || !out || !devices) return fail(RL_ERR_INVALID, "rl_map_create_multi: null pointer");
     if (n_devices < 1 || n_devices > 64) return fail(RL_ERR_INVALID, "rl_map_create_multi: 1..64 devices (got %d)", n_devices);
-    rl_map *m = new (std::nothrow) rl_map();
+    std::unique_ptr<rl_map, decltype(&rl_map_destroy)> own(new (std::nothrow) rl_map(), rl_map_destroy);
+    rl_map *m = own.get();
     if (!m) return fail(RL_ERR_NOMEM, "out of host memory");
     for (int i = 0; i < n_devices; ++i) {
         rl_map *r = nullptr;
         const int rc = rl_map_create(occ, rows, cols, res, ox, oy, oyaw, devices[i], &r);
         if (rc) {
-            const std::string keep = g_err;
-            rl_map_destroy(m);
+            const std::string keep = g_err;          // (the failing replica's message outlives the clean-up)
+            own.reset();
             g_err = keep;
             return rc;
         }
@@ -261,7 +267,7 @@ extern "C" int rl_map_create_multi(const uint8_t *occ, int rows, int cols, float
     m->n_cu = r0->n_cu;
     m->clock_khz = r0->clock_khz;
     m->mp = r0->mp;
-    *out = m;
+    *out = own.release();
     return RL_OK;
 }
 
@@ -347,7 +353,7 @@ extern "C" int rl_map_stamp_cells(rl_map *m, const int32_t *flat_idx, int n, uin
     HIPCHK(hipDeviceSynchronize());                  // launches the *_device entry points left in flight still read the tables
     const size_t cells = (size_t)m->rows * m->cols;
     if (!m->d_occ_base) {                            // (first stamp: the map as it stands is the base)
-        HIPCHK(hipMalloc((void **)&m->d_occ_base, cells));
+        if (m->d_occ_base.alloc(cells)) return alloc_failed("rl_map_stamp_cells");
         HIPCHK(hipMemcpyAsync(m->d_occ_base, m->d_occ, cells, hipMemcpyDeviceToDevice, m->stream));
         m->n_stamped = 0;
     }
@@ -355,13 +361,10 @@ extern "C" int rl_map_stamp_cells(rl_map *m, const int32_t *flat_idx, int n, uin
         // (the list in place is lost with its buffer: restore the whole grid once)
         HIPCHK(hipMemcpyAsync(m->d_occ, m->d_occ_base, cells, hipMemcpyDeviceToDevice, m->stream));
         HIPCHK(hipStreamSynchronize(m->stream));
-        if (m->d_stamp) (void)hipFree(m->d_stamp);
-        if (m->pin_stamp) (void)hipHostFree(m->pin_stamp);
-        m->d_stamp = m->pin_stamp = nullptr;
         m->stamp_cap = m->n_stamped = 0;
         const int cap = std::max(n + 256, 1024);
-        HIPCHK(hipMalloc((void **)&m->d_stamp, (size_t)cap * sizeof(int32_t)));
-        HIPCHK(hipHostMalloc((void **)&m->pin_stamp, (size_t)cap * sizeof(int32_t), hipHostMallocDefault));
+        if (m->d_stamp.alloc((size_t)cap * sizeof(int32_t))) return alloc_failed("rl_map_stamp_cells");
+        HIPCHK(m->pin_stamp.alloc((size_t)cap * sizeof(int32_t)));
         m->stamp_cap = cap;
     }
     // the indices land in pinned memory the kernel reads directly; ONE launch puts the previous outline's cells back
@@ -386,18 +389,6 @@ extern "C" void rl_map_destroy(rl_map *m)
         return;
     }
     (void)hipSetDevice(m->device);
-    if (m->d_occ) (void)hipFree(m->d_occ);
-    if (m->d_occ_base) (void)hipFree(m->d_occ_base);
-    if (m->d_stamp) (void)hipFree(m->d_stamp);
-    if (m->pin_stamp) (void)hipHostFree(m->pin_stamp);
-    if (m->d_g) (void)hipFree(m->d_g);
-    if (m->d_dt) (void)hipFree(m->d_dt);
-    if (m->d_bits) (void)hipFree(m->d_bits);
-    if (m->d_mp) (void)hipFree(m->d_mp);
-    if (m->d_edges) (void)hipFree(m->d_edges);
-    if (m->d_n_edges) (void)hipFree(m->d_n_edges);
-    if (m->pin_n_edges) (void)hipHostFree(m->pin_n_edges);
-    if (m->stream) (void)hipStreamDestroy(m->stream);
     delete m;
 }
 

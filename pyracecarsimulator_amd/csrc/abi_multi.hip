@@ -84,9 +84,8 @@ static int multi_crash(rl_method *h, const float *poses, int n_groups, int group
 // ------------------------------------------------------------------------------
 static int ensure_copy_stream(rl_method *r)
 {
-    if (!r->copy_stream) HIPCHK(hipStreamCreateWithFlags(&r->copy_stream, hipStreamNonBlocking));
-    for (hipEvent_t &e : r->slice_ev)
-        if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIPCHK(r->copy_stream.create());
+    for (Event &e : r->slice_ev) HIPCHK(e.create(hipEventDisableTiming));
     return RL_OK;
 }
 

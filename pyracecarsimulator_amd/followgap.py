@@ -20,9 +20,11 @@ from . import _lib
 from ._lib import f32p
 
 
-class PyFollowGap:
+class PyFollowGap(_lib.Handle):
     """``PyFollowGap(window_size, max_distance, max_angle, angle_inc)`` (followgap.pyx:23-25).
     ``window_size`` is stored and unused, as in the reference (FollowGap::eval never reads it)."""
+
+    _destroy = "rl_followgap_destroy"
 
     def __init__(self, ws, md, ma, angle_inc, device=0):
         self.window_size, self.max_distance = int(ws), float(md)
@@ -30,14 +32,6 @@ class PyFollowGap:
         self._h = C.c_void_p()
         _lib.check(_lib.lib().rl_followgap_create(int(device), self.window_size, self.max_distance,
                                                   self.max_angle, self.angle_inc, C.byref(self._h)))
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _lib.lib().rl_followgap_destroy(h)
-            except Exception:
-                pass
 
     @staticmethod
     def _f32c(a, what):

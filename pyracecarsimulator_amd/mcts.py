@@ -82,10 +82,11 @@ def drive_args(n_trees, states, recent_actions, seeds, n_decisions, n_iterations
             np.ascontiguousarray(np.broadcast_to(sd.astype(np.uint64), (K,))), D, I, S, clip)
 
 
-class MCTSPlanner:
+class MCTSPlanner(_lib.Handle):
     """K trees of at most ``max_nodes`` nodes on one device.  ``method`` scans, ``source`` ("fg", "nn" or "random")
     picks the expansion answer: ``followgap`` (a ``PyFollowGap``) for "fg", ``policy`` (a ``Policy``) for "nn".
     The handles are borrowed: keep them alive as long as the planner."""
+    _destroy = "rl_mcts_destroy"
 
     def __init__(self, car, method, n_trees, max_nodes, fov, num_rays, edge, crash_thresh, source="fg",
                  followgap=None, policy=None, rollout_steps=200, action_every=10, speed=2.0, dt=0.01,
@@ -169,17 +170,6 @@ class MCTSPlanner:
             S, clip, first.ctypes.data_as(i32p), out.ctypes.data_as(f64p), recent.ctypes.data_as(f64p),
             actions.ctypes.data_as(f64p), visits.ctypes.data_as(i32p), tr.ctypes.data_as(f64p) if trace else None))
         return (first, out, recent, actions, visits) + ((tr,) if trace else ())
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _lib.lib().rl_mcts_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Node:

@@ -18,7 +18,7 @@ f32p, f64p, i32p = _lib.f32p, _lib.f64p, _lib.i32p
 RESAMPLED, DEGENERATE = 1, 2        # bits of a step's flags
 
 
-class ParticleFilter:
+class ParticleFilter(_lib.Handle):
     """A filter of ``n_particles`` particles casting the beams ``angles`` (radians, float32, relative to the heading) on
     ``method`` (a ``range_libc`` RayMarching, RayMarchingGPU, CDDTCast or GiantLUTCast object on one device whose sensor
     model has been set with ``set_sensor_model``; it must outlive the filter).
@@ -30,6 +30,8 @@ class ParticleFilter:
     The sensor-model table is used as it is set: a squash exponent (particle_filter.py's ``squash_factor``) is applied by
     the caller to the table, ``table ** (1 / squash)``, before ``set_sensor_model`` — no ``pow`` runs on the device.
     """
+
+    _destroy = "rl_pf_destroy"
 
     def __init__(self, method, angles, n_particles, motion_std=(0.0, 0.0, 0.0), resample_ratio=0.5):
         self._h = C.c_void_p()
@@ -92,14 +94,3 @@ class ParticleFilter:
                                          out["ancestors"].ctypes.data_as(i32p), out["cum"].ctypes.data_as(f64p),
                                          out["likelihood"].ctypes.data_as(f64p)))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _lib.lib().rl_pf_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

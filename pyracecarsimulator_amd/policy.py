@@ -227,11 +227,13 @@ class _Layers(list):
 
 
 # ---------------------------------------------------------------- the network on the GPU
-class Policy:
+class Policy(_lib.Handle):
     """``Policy(graph_path)`` (scripts/policy.py:17-28) on the GPU.  ``predict_action(lidar)`` returns the
     steering angle of one scan as ``np.float32`` (the reference's ``sess.run(...)[0][0]``); ``predict_many``
     and ``predict_device`` evaluate batches in one launch.  The input window is ``scan[in_start : in_start +
     K]`` with ``x = r / scale if r <= clip else 1.0`` (policy.py:30,34)."""
+
+    _destroy = "rl_policy_destroy"
 
     def __init__(self, graph_path=None, device=0, in_start=180, clip=15.0, scale=15.0, layers=None, relu=None):
         if layers is None:
@@ -270,14 +272,6 @@ class Policy:
     def window(self):
         """(first beam, beams read) of each scan."""
         return self.in_start, self.dims[0]
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _lib.lib().rl_policy_destroy(h)
-            except Exception:
-                pass
 
     def predict_action(self, lidar):
         """Steering angle (np.float32) for one scan: ``Policy.predict_action(lidar)`` (policy.py:33-35)."""

@@ -66,8 +66,9 @@ def is_crashed(rays, num_rays, poses, edge, crash_thresh):
     return int(first.value)
 
 
-class CarBatch:
+class CarBatch(_lib.Handle):
     """Many ``Car`` objects stepped together on one MI355X, or on several (``device=[...]``) (no CPU path)."""
+    _destroy = "rl_car_destroy"
 
     def __init__(self, params=None, device=0):
         p = dict(DEFAULT_CAR)
@@ -293,14 +294,3 @@ class CarBatch:
         poses = np.empty((R, T, 3), dtype=np.float32) if trace else None
         trace_st = np.empty((R, T, 11), dtype=np.float64) if trace else None
         return R, n_ticks, states, speeds, st0, edge, first, out, vel, steers, poses, trace_st
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _lib.lib().rl_car_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

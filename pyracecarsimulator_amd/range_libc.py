@@ -58,7 +58,7 @@ def stamp_indices(flat_idx, n_cells):
     return np.ascontiguousarray(a[(a >= 0) & (a < n_cells)], dtype=np.int32)
 
 
-class PyOMap:
+class PyOMap(_lib.Handle):
     """Occupancy grid + world transform, resident on one MI355X.
 
     Accepts what the reference passes — a ``nav_msgs/OccupancyGrid``-like object with
@@ -73,6 +73,8 @@ class PyOMap:
     one calling process — the reference's ``scanMany`` / ``checkCollisionMany`` callers
     (scripts/scan_simulator.py:113-135, scripts/mcts.py:237) get all the GPUs of the node unchanged.
     """
+
+    _destroy = "rl_map_destroy"
 
     def __init__(self, arg1, arg2=None, resolution=None, origin=None, device=0):
         occ, res, org = self._ingest(arg1, arg2, resolution, origin)
@@ -155,17 +157,6 @@ class PyOMap:
         _lib.check(_lib.lib().rl_map_get_dt(self._h, out.ctypes.data_as(f32p)))
         return out
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _lib.lib().rl_map_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _check_ins_outs(ins, outs):
     if not isinstance(ins, np.ndarray) or not isinstance(outs, np.ndarray):
@@ -227,8 +218,9 @@ def _check_weights(weights, n):
         raise ValueError("weights must have %d elements, got %d" % (n, weights.shape[0]))
 
 
-class _RangeMethod:
+class _RangeMethod(_lib.Handle):
     KIND = None
+    _destroy = "rl_method_destroy"
 
     def __init__(self, omap, max_range_px, theta_disc=0):
         if not isinstance(omap, PyOMap):
@@ -505,7 +497,7 @@ class _RangeMethod:
             return self
         r = object.__new__(type(self))
         r.__dict__.update(omap=self.omap, max_range_px=self.max_range_px, theta_disc=self.theta_disc,
-                          _h=C.c_void_p(p), _fan_raw=self._fan_raw, _fan_dense_raw=self._fan_dense_raw, _parent=self)   # (_parent: borrowed handle)
+                          _h=C.c_void_p(p), _fan_raw=self._fan_raw, _fan_dense_raw=self._fan_dense_raw, _parent=self, _borrowed=True)   # (_parent keeps the owner alive)
         return r
 
     def set_noise(self, std, seed=0, ray_offset=0):
@@ -547,19 +539,6 @@ class _RangeMethod:
         ms = C.c_float(0)
         _lib.check(_lib.lib().rl_last_kernel_ms(self._h, C.byref(ms)))
         return float(ms.value)
-
-    def close(self):
-        if getattr(self, "_parent", None) is not None:       # a borrowed replica: the parent owns the handle
-            return
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _lib.lib().rl_method_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class PyRayMarching(_RangeMethod):

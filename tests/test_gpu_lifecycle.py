@@ -8,7 +8,11 @@ import numpy as np
 import pytest
 
 from pyracecarsimulator_amd import _lib, maps, range_libc
+from pyracecarsimulator_amd import racecar as RC
 from pyracecarsimulator_amd.followgap import PyFollowGap
+from pyracecarsimulator_amd.mcts import MCTSPlanner
+from pyracecarsimulator_amd.particle_filter import ParticleFilter
+from pyracecarsimulator_amd.policy import Policy
 from pyracecarsimulator_amd.racecar import CarBatch
 from pyracecarsimulator_amd.scan_simulator import ScanSimulator2D
 
@@ -140,3 +144,95 @@ def test_stamp_growth_cycles_return_device_memory():
     gc.collect()
     leaked = base - _free_bytes(torch)
     assert leaked <= 4 << 20, "%.1f MB not returned after 20 maps of stamp growth cycles" % (leaked / 2**20)
+
+
+def _every_handle_life(g, poses, B, fov):
+    """One life of what the first test leaves out: policy, closed-loop drives and races, the race scan, roll-outs,
+    outline cells, the MCTS planner and its drive, sensor model + repeat-angle calls + particle filter, and multi-device
+    handles — each created, used once and dropped.  Returns (16 ranges of one scan, the planner's chosen actions)."""
+    rng = np.random.default_rng(3)
+    edge = RC.edge_distances(B, -fov / 2, fov / B, 0.275, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
+    states = np.zeros((4, 11))
+    states[:, :3] = poses[:4]
+    omap = range_libc.PyOMap(g)
+    m = range_libc.PyRayMarchingGPU(omap, 120)
+    cars = CarBatch()
+    fg = PyFollowGap(10, 15.0, 0.4189, fov / B)
+    # the smallest network of tests/test_gpu_policy.py: 3 -> 1, window [7, 10)
+    pol = Policy.from_arrays([(rng.standard_normal((3, 1)).astype(np.float32), np.zeros(1, np.float32))], (False,),
+                             in_start=7, clip=12.5, scale=7.0)
+    pol.predict_many(np.ones((2, 10), np.float32))
+    cars.drive_followgap(m, fg, states[:2], 4, 2.0, fov, B, edge, 0.001)
+    cars.drive_policy(m, pol, states[:2], 4, 2.0, fov, B, edge, 0.001, steer_clip=0.4189)
+    cars.race_followgap(m, fg, states.reshape(2, 2, 11), 4, 2.0, fov, B, edge, 0.001)
+    ranges = m.calc_range_fan_cars(poses[:4], states[:, :3], 2, fov, B)[:16].copy()
+    cars.rollout(states, np.tile([2.0, 0.1], (4, 2, 1)), n_steps=8, action_every=4)
+    cars.outline_cells(omap, states[:, :3])
+    pl = MCTSPlanner(cars, m, 4, 16, fov, B, edge, 0.001, source="fg", followgap=fg, rollout_steps=8, action_every=4)
+    pl.reset(states, 0.0, np.arange(4, dtype=np.uint64))
+    pl.run(6)
+    chosen = pl.best()[0].copy()
+    pl.read_tree(0)
+    pl.close()
+    cars.drive_mcts(m, fg, states, 2, 6, np.arange(4), fov, B, edge, 0.001, rollout_steps=8, action_every=4)
+    # particle-filter weights: two tables of two widths on one method (the first one is freed), the three repeat-angle
+    # calls on ray marching and on CDDT (whose fused call takes the launch context's scratch), then a filter
+    P, A = 64, 16
+    parts = np.ascontiguousarray(np.resize(poses, (P, 3)), np.float32)
+    angles = np.linspace(-2.0, 2.0, A).astype(np.float32)
+    obs = np.full(A, 1.5, np.float32)
+    cd = range_libc.PyCDDTCast(omap, 120, 108)
+    for h in (m, cd):
+        for width in (32, 48):
+            h.set_sensor_model(np.ascontiguousarray(rng.uniform(0.1, 1.0, (width, width))))
+        r, w = np.empty(P * A, np.float32), np.empty(P)
+        h.calc_range_repeat_angles(parts, angles, r)
+        h.eval_sensor_model(obs, r, w, A, P)
+        h.calc_range_repeat_angles_eval_sensor_model(parts, angles, obs, w)
+    pf = ParticleFilter(m, angles, P, motion_std=(0.02, 0.02, 0.01))
+    pf.reset(parts.astype(np.float64), seed=1)
+    pf.run(np.tile([0.05, 0.0, 0.01], (2, 1)), np.tile(obs, (2, 1)))
+    pf.read()
+    pf.close()
+    cd.close()
+    # several devices behind one handle (device 0 named twice), the batch cut in two
+    mmap = range_libc.PyOMap(g, device=[0, 0])
+    mm = range_libc.PyRayMarchingGPU(mmap, 120)
+    mcar = CarBatch(device=[0, 0])
+    mm.set_option("multi_min_poses", 1)
+    out = np.empty(8 * B, np.float32)
+    mm.calc_range_fan(poses[:8], out, fov, B)
+    mcar.close()
+    mm.close()
+    mmap.close()
+    for h in (pol, fg):                                # (close() twice: the second call finds nothing to give back)
+        h.close()
+        h.close()
+        assert not h._h.value
+    cars.close()
+    m.close()
+    omap.close()
+    return ranges, chosen
+
+
+def test_every_handle_kind_returns_all_device_memory():
+    """The handles the first test does not reach, 20 lives of each: the same bound on what is not returned.  At these
+    shapes most buffers of the planner, the filter and the car are a few KB, so the bound catches a leaked map, table or
+    scan buffer, not every member: that no member can be forgotten is what the owners of csrc/abi_internal.h and
+    tests/test_host.py::test_housekeeping_gates guarantee."""
+    torch = pytest.importorskip("torch")
+    g = maps.make_maze(160, cell=20, wall=2, p=0.4, seed=5, origin=(-1.0, 0.5, 0.2))
+    B, fov = 271, 4.71
+    poses = maps.sample_free_poses(g, 96, 11)
+    first = _every_handle_life(g, poses, B, fov)       # warm-up: runtime pools, code objects, torch context
+    _every_handle_life(g, poses, B, fov)
+    gc.collect()
+    base = _free_bytes(torch)
+    for _ in range(20):
+        again = _every_handle_life(g, poses, B, fov)
+        for a, b in zip(first, again):
+            assert a.tobytes() == b.tobytes()          # and fresh handles compute the same bits
+    gc.collect()
+    leaked = base - _free_bytes(torch)
+    print("not returned after 20 lives: %.2f MB" % (leaked / 2**20))
+    assert leaked <= 8 << 20, "%.1f MB of device memory not returned after 20 create/destroy cycles" % (leaked / 2**20)

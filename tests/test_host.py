@@ -468,7 +468,8 @@ def test_multi_device_entry_points_exist_and_fail_loudly_without_a_device():
 def test_housekeeping_gates():
     """VERDICT r04 #9, kept as a gate: DESIGN.md stays below 40 KB (history lives in docs/history/), the library's host
     side stays in its four translation units, and no launch function of abi_fan.hip grows past 100 lines (one function
-    per kernel family instead of one 220-line launch_fan)."""
+    per kernel family instead of one 220-line launch_fan); and device memory, pinned memory, streams and events are
+    allocated and freed by the owners of abi_internal.h alone."""
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     assert os.path.getsize(os.path.join(root, "DESIGN.md")) <= 40000
@@ -481,6 +482,29 @@ def test_housekeeping_gates():
     for i in starts:
         j = next(k for k in range(i, len(src)) if src[k] == "}")
         assert j - i + 1 <= 100, (src[i], j - i + 1)
+    # ownership lives in abi_internal.h: its owners (DevBuf, DevPtr, Pinned, Stream, Event) are the only code that frees
+    # device memory, pinned memory, streams or events, and the only code that allocates the first two — a handle is
+    # freed by `delete`, so no unit can forget a member.  The one exception is the caller's block of rl_host_alloc /
+    # rl_host_free, which belongs to the caller and stays hand-managed.
+    text = {u: open(os.path.join(csrc, u)).read() for u in units}
+    for u, t in text.items():
+        for call in ("hipFree(", "hipEventDestroy(", "hipStreamDestroy(", "hipMalloc("):
+            assert call not in t, (u, call)
+    amap = text["abi_map.hip"]
+
+    def body(name):
+        i = amap.index('extern "C" int %s(' % name)
+        return i, amap.index("\n}\n", i)
+    assert sum(t.count("hipHostFree(") for t in text.values()) == 1
+    lo, hi = body("rl_host_free")
+    assert lo < amap.index("hipHostFree(") < hi
+    lo, hi = body("rl_host_alloc")
+    for u, t in text.items():
+        at = [m.start() for m in re.finditer(re.escape("hipHostMalloc("), t)]
+        assert all(u == "abi_map.hip" and lo < k < hi for k in at), (u, at)
+    hdr = open(os.path.join(csrc, "abi_internal.h")).read()
+    for call in ("hipFree(", "hipHostFree(", "hipEventDestroy(", "hipStreamDestroy(", "hipMalloc(", "hipHostMalloc("):
+        assert call in hdr, call
 
 
 def test_kernel_register_budgets_are_a_build_gate(tmp_path):
