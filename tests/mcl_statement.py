@@ -155,6 +155,28 @@ def peaked_table(width, sigma=1.0, floor=1e-3):
 
 
 # ---------------------------------------------------------------- the GPU tests' input
+def statement_likelihood(g, om, max_range_px, form, angles, table, theta_disc=None, lut=None):
+    """The statement's L for one arithmetic — "literal" (step coefficient 0.999), "canonical" (1.0), "cddt", "lut" — as a
+    Filter likelihood: the kind's ranges by the oracle map ``om`` / tests/pf_statement.py and the ascending product.
+    ``lut``: the GiantLUT handle's own table (the oracle reads it; the other forms need no device)."""
+    import pf_statement as PS
+    inv_res = PS.inv_res_of(g.resolution)
+
+    def lik(q, obs, t):
+        if form == "canonical":
+            r = PS.repeat_angles(g.occ, g.resolution, g.origin, max_range_px, q, angles, step_coeff=1.0, dt=om.dt)[0]
+        else:
+            rows = PS.expand_rows(q, angles)
+            if form == "literal":
+                r = om.rm_rays_libm(rows, step_coeff=0.999)
+            elif form == "cddt":
+                r = om.cddt_rays(theta_disc, rows)
+            else:
+                r = om.lut_rays(lut, rows)
+        return PS.weights(table, obs, r, inv_res)
+    return lik
+
+
 def localisation_case(g, dt, max_range_px, fov, P, A, T, seed=5):
     """A car driving a gentle arc through golden map ``g`` and P particles scattered around its start (3 cells, 0.1 rad;
     particle 0 on it): (particles (P, 3) f64, angles (A,) f32, odom (T, 3) f64, obs (T, A) f32 — the canonical march from
@@ -173,3 +195,46 @@ def localisation_case(g, dt, max_range_px, fov, P, A, T, seed=5):
         X = motion(X, odom[t], (0.0, 0.0, 0.0), 0, t)
         obs.append(PS.repeat_angles(g.occ, g.resolution, g.origin, max_range_px, X.astype(f32), angles, dt=dt)[0])
     return particles, angles, odom, np.array(obs, f32), peaked_table(int(max_range_px) + 1)
+
+
+# ---------------------------------------------------------------- the inputs of tests/test_gpu_pf_scale.py
+#: (P, A, T, kinds, ratios, dead, most): the localisation rows beyond one workgroup round.  ``dead`` / ``most``: with ratio
+#: 2.0 the ancestors of the LAST step leave at least that share of the particles without a descendant and give some
+#: particle at least that many.  A single beam tells few particles apart: at A = 1 the second step's resampling of the
+#: already resampled cloud leaves 21-23 % dead and no particle more than two descendants, so the two-step rows at A = 1
+#: take (0.20, 2); the others the (0.25, 3) of tests/test_gpu_mcl.py.  tests/test_mcl_host.py holds the statement to every bar.
+SCALE_ROWS = [
+    (2500, 7, 2, ("RM-3", "RMGPU-1", "CDDT", "GLT"), (2.0, 0.5, 0.0), 0.25, 3),
+    (65793, 1, 2, ("RMGPU-1", "CDDT"), (2.0, 0.5), 0.20, 2),
+    (131072, 1, 2, ("RM-3",), (2.0,), 0.20, 2),
+    (131073, 1, 2, ("RM-3",), (2.0, 0.5), 0.20, 2),
+    (140001, 1, 2, ("RM-3", "RMGPU-1", "CDDT", "GLT"), (2.0, 0.5), 0.20, 2),
+    (1 << 20, 1, 1, ("RM-3",), (2.0,), 0.25, 3),
+]
+#: the flags of a row's steps by ratio: a peaked table always falls below 2 P, never below 0; below P / 2 at every step
+#: with 7 beams, at the first step only with one (neff 0.40 P, then 0.76 P)
+def scale_flags(A, T, ratio):
+    if ratio == 2.0:
+        return [RESAMPLED] * T
+    if ratio == 0.0:
+        return [0] * T
+    return [RESAMPLED] * T if A > 1 else [RESAMPLED, 0][:T]
+
+
+def overflow_table(table):
+    """With weights of 1e308 the first step's omega overflows: W = +inf."""
+    return table * 300.0
+
+
+def nan_table(table):
+    """NaN planted in one entry of 35: some particle meets one at every step, and W is NaN."""
+    t = table.copy()
+    t[::5, ::7] = np.nan
+    return t
+
+
+def plateau_table(table):
+    """Every entry below 1e-2 exactly zero: most particles get a zero weight, cum(w) has long flat stretches."""
+    t = table.copy()
+    t[t < 1e-2] = 0.0
+    return t

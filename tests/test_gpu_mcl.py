@@ -71,21 +71,10 @@ class World:
         form = KINDS[kind][3]
         m = self.method(kind)
 
-        def lik(q, obs, t):
-            rows = PS.expand_rows(q, angles)
-            if form == "literal":
-                r = self.om.rm_rays_libm(rows, step_coeff=0.999)
-            elif form == "canonical":
-                r = PS.repeat_angles(self.g.occ, self.g.resolution, self.g.origin, self.mrx, q, angles, step_coeff=1.0,
-                                     dt=self.om.dt)[0]
-            elif float(self.g.origin[2]) != 0.0:
-                return _fused(m, q, angles, obs)
-            elif form == "cddt":
-                r = self.om.cddt_rays(THETA, rows)
-            else:
-                r = self.om.lut_rays(m.table(), rows)
-            return PS.weights(table, obs, r, self.inv_res)
-        return lik
+        if form in ("cddt", "lut") and float(self.g.origin[2]) != 0.0:
+            return lambda q, obs, t: _fused(m, q, angles, obs)
+        return MS.statement_likelihood(self.g, self.om, self.mrx, form, angles, table, THETA,
+                                       m.table() if form == "lut" else None)
 
 
 @pytest.fixture(scope="module")
@@ -125,9 +114,10 @@ def _assert_equal_to_statement(pf, out, st, want, what):
     assert _same(rd["particles"], st.X), (what, int((rd["particles"] != st.X).sum()))
 
 
-def _both(w, kind, P, A, ratio, std=STD, seed=3, weights=None):
-    """The device filter and the statement after the same T steps of case (P, A)."""
-    parts, angles, odom, obs, table = w.case(P, A)
+def _both(w, kind, P, A, ratio, std=STD, seed=3, weights=None, n_steps=T, table=None):
+    """The device filter and the statement after the same n_steps steps of case (P, A); ``table`` replaces the case's."""
+    parts, angles, odom, obs, case_table = w.case(P, A, n_steps)
+    table = case_table if table is None else table
     m = w.method(kind)
     m.set_sensor_model(table)
     pf = ParticleFilter(m, angles, P, motion_std=std, resample_ratio=ratio)
@@ -161,8 +151,9 @@ def test_runs_equal_the_statement(worlds, kind, name):
 
 
 def test_multi_pass_tiles_and_given_weights(worlds):
-    """pf_block forced to 2 (the weight kernel's tiles take several passes per workgroup), and a reset with the caller's
-    weights, taken as given (they need not sum to one)."""
+    """pf_block forced to 2 (the weight launch has several tiles: 128 at P = 256, on a grid of min(128, 8 n_cu), so on a
+    part of 16 CUs or more every workgroup still takes one; tests/test_gpu_pf_scale.py has workgroups take a second and a
+    third), and a reset with the caller's weights, taken as given (they need not sum to one)."""
     w = worlds(MAPS[0])
     m = w.method("RMGPU-1")
     m.set_option("pf_block", 2)

@@ -187,10 +187,11 @@ def test_out_of_map_and_huge_heading_particles(worlds):
 
 
 # ---------------------------------------------------------------- 3. eval_sensor_model
-def _planted_ranges(w, m, A, P, seed):
-    """Ranges of a real scan with planted values: negative, NaN, above the table, on and next to bin edges."""
+def _planted_ranges(w, m, A, P, seed, poses=None):
+    """Ranges of a real scan (of ``poses``, else the world's first P) with planted values: negative, NaN, above the
+    table, on and next to bin edges."""
     angles = _wild_angles(A, seed)
-    r = _scan(m, np.ascontiguousarray(w.poses[:P]), angles).copy()
+    r = _scan(m, np.ascontiguousarray(w.poses[:P] if poses is None else poses[:P]), angles).copy()
     rng = np.random.default_rng(seed)
     res = f32(w.g.resolution)
     for v in (f32(-0.3), f32(np.nan), f32(1e5), f32(np.inf), f32(-np.inf), f32(-0.0)):

@@ -90,12 +90,7 @@ def test_blocked_sums_spelt_out():
 
 
 def _march_likelihood(g, om, mrx, angles, table):
-    inv = PS.inv_res_of(g.resolution)
-
-    def lik(q, obs, t):
-        r = PS.repeat_angles(g.occ, g.resolution, g.origin, mrx, q, angles, step_coeff=1.0, dt=om.dt)[0]
-        return PS.weights(table, obs, r, inv)
-    return lik
+    return MS.statement_likelihood(g, om, mrx, "canonical", angles, table)
 
 
 def test_gpu_input_condition(oracle_mod):
@@ -114,6 +109,64 @@ def test_gpu_input_condition(oracle_mod):
         assert flags == MS.RESAMPLED and (n == 0).mean() >= 0.25 and n.max() >= 3, (t, neff)
         assert n.sum() == P and (np.diff(f.anc) >= 0).all()
         assert f.w.tobytes() == np.full(P, 1.0 / P).tobytes()
+
+
+#: the arithmetic of the kinds the host can state (GiantLUT's statement reads the device's table)
+_HOST_FORMS = {"RM-3": "literal", "RMGPU-1": "canonical", "CDDT": "cddt"}
+_STD = (0.02, 0.02, 0.01)
+
+
+def test_gpu_scale_input_condition(oracle_mod):
+    """What tests/test_gpu_pf_scale.py relies on, in the statement alone.  Every row of MS.SCALE_ROWS, for every kind
+    the host can state: with ratio 2.0 every step resamples and the last step's ancestors clear the row's (dead, most)
+    bar — and the first step's the (0.25, 3) bar, 54-55 % and 4 at one beam —, the flags by ratio are MS.scale_flags,
+    and at 131 073, 140 001 and 2^20 particles the blocked total of omega is not the sequential one, so the pinned order
+    is still told apart from np.cumsum's.  Then the three inputs of the degenerate / dead-particle tests at 600 x 7."""
+    g, z = load_golden("rm_maze256")
+    fov, mrx = float(z["fov"]), int(z["max_range_px"])
+    om = oracle_mod.OracleMap.from_gridmap(g, mrx)
+
+    def run(P, A, T, form, ratio, table=None, weights=None):
+        parts, angles, odom, obs, tb = MS.localisation_case(g, om.dt, mrx, fov, P, A, T)
+        f = MS.Filter(MS.statement_likelihood(g, om, mrx, form, angles, tb if table is None else table(tb), 112), P, _STD, ratio)
+        f.reset(parts, weights=weights, seed=3)
+        rows = []
+        with np.errstate(over="ignore", invalid="ignore"):
+            for t in range(T):
+                _, neff, flags = f.step(odom[t], obs[t])
+                rows.append((flags, neff, np.bincount(f.anc, minlength=P)))
+        return f, rows
+
+    for P, A, T, kinds, ratios, dead, most in MS.SCALE_ROWS:
+        for i, kind in enumerate(k for k in kinds if k in _HOST_FORMS):
+            f, rows = run(P, A, T, _HOST_FORMS[kind], 2.0)          # (each shape once: 2^20 takes seconds)
+            assert [r[0] for r in rows] == MS.scale_flags(A, T, 2.0), (P, kind)
+            n = rows[0][2]
+            assert (n == 0).mean() >= 0.25 and n.max() >= 3, (P, kind, (n == 0).mean(), n.max())
+            n = rows[-1][2]
+            assert (n == 0).mean() >= dead and n.max() >= most and n.sum() == P, (P, kind, (n == 0).mean(), n.max())
+            if P > 131072:
+                assert MS.bs(f.omega) != float(np.cumsum(f.omega)[-1]), (P, kind)
+            for ratio in ratios[1:] if i == 0 else ():
+                _, rows = run(P, A, T, _HOST_FORMS[kind], ratio)
+                assert [r[0] for r in rows] == MS.scale_flags(A, T, ratio), (P, kind, ratio, [r[1] for r in rows])
+    assert {r[0] for r in MS.SCALE_ROWS} >= {131073, 140001, 1 << 20}
+
+    P, A = 600, 7
+    # W = +inf at step 0 (degenerate, uniform weights), usable afterwards
+    f, rows = run(P, A, 3, "canonical", 0.0, MS.overflow_table, np.full(P, 1e308))
+    assert [r[0] for r in rows] == [MS.DEGENERATE, 0, 0]
+    assert abs(rows[0][1] - 600.0) < 1e-6 and abs(rows[1][1] - 3.58) < 0.01 and abs(rows[2][1] - 1.04) < 0.01
+    # W = NaN at every step, whatever the ratio; about 13 % of the likelihoods are NaN
+    for ratio, flag in ((0.0, MS.DEGENERATE), (2.0, MS.DEGENERATE | MS.RESAMPLED)):
+        f, rows = run(P, A, 3, "canonical", ratio, MS.nan_table)
+        assert [r[0] for r in rows] == [flag] * 3 and 0.05 < np.isnan(f.L).mean() < 0.5
+        assert np.isnan(MS.bs(f.omega)) and f.w.tobytes() == np.full(P, 1.0 / P).tobytes()
+    # plateaus: most likelihoods are exactly zero, most steps of cum(w) are flat, and no ancestor had a zero weight
+    f, rows = run(P, A, 3, "canonical", 2.0, MS.plateau_table)
+    assert [r[0] for r in rows] == [MS.RESAMPLED] * 3
+    assert (f.L == 0).mean() >= 0.5 and (np.diff(f.cum) == 0).mean() >= 0.5
+    assert (f.omega[f.anc] > 0).all()
 
 
 def test_estimate_converges_for_a_stationary_car(oracle_mod):
