@@ -46,29 +46,32 @@ def _roots(g, dt, K, seed):
     return states, rng.uniform(-0.3, 0.3, K), rng.integers(0, 2 ** 63, K, dtype=np.uint64) * np.uint64(2) + np.uint64(1)
 
 
-def _answers(source, h, ranges):
+def _answers(source, h, ranges, num_rays=B):
     if source == "fg":
-        return h.eval_many(np.ascontiguousarray(ranges), B).astype(np.float32)
+        return h.eval_many(np.ascontiguousarray(ranges), num_rays).astype(np.float32)
     if source == "nn":
         return h.predict_many(np.ascontiguousarray(ranges)).astype(np.float32)
     return np.full(len(ranges), np.nan, np.float32)
 
 
-def _scan(m, std, base, poses):
+def _scan(m, std, base, poses, num_rays=B):
     m.set_noise(std, 99, base)
-    out = np.empty(len(poses) * B, np.float32)
-    m.calc_range_fan(np.ascontiguousarray(poses, np.float32), out, FOV, B)
-    return out.reshape(len(poses), B)
+    out = np.empty(len(poses) * num_rays, np.float32)
+    m.calc_range_fan(np.ascontiguousarray(poses, np.float32), out, FOV, num_rays)
+    return out.reshape(len(poses), num_rays)
 
 
-def _replay(cars, m, std, base, source, h, states, actions, seeds, n_it, dev_trees, snapshots):
+def _replay(cars, m, std, base, source, h, states, actions, seeds, n_it, dev_trees, snapshots, *, num_rays=B,
+            rollout_steps=L, action_every=EVERY, edge=None, is_crashed=RC.is_crashed, rollouts=None):
     """The statement of K trees replayed with the public calls; scan poses from the device dump (dev_trees: the
-    read_tree dicts of a run of >= n_it iterations)."""
-    K = len(states)
-    edge = _edge()
-    n_act = (L + EVERY - 1) // EVERY
+    read_tree dicts of a run of >= n_it iterations).  edge: the planner's outline table (the car's by default);
+    is_crashed: the crash test of the act scans; rollouts: a list that receives every roll-out the statement asks
+    for, (crash index, velocities)."""
+    K, nb, L_ = len(states), num_rays, rollout_steps
+    edge = _edge(nb) if edge is None else edge
+    n_act = (L_ + action_every - 1) // action_every
     pose0 = np.stack([dev_trees[k]["scan_pose"][0] for k in range(K)])
-    ans0 = _answers(source, h, _scan(m, std, base, pose0))
+    ans0 = _answers(source, h, _scan(m, std, base, pose0, nb), nb)
     trees = [S.Tree(states[k].copy(), pose0[k], float(ans0[k]) if source != "random" else math.nan, float(actions[k]),
                     int(seeds[k]), source=source) for k in range(K)]
     last = {}
@@ -78,17 +81,19 @@ def _replay(cars, m, std, base, source, h, states, actions, seeds, n_it, dev_tre
         ac = np.array([[SPEED, a] for _, _, a in reqs])[:, None, :]
         _, out, _ = cars.rollout(st, ac, n_steps=1, action_every=1)
         poses = np.stack([dev_trees[k]["scan_pose"][i + 1] for k in range(K)])
-        ranges = _scan(m, std, base + (K + i * K * (1 + L)) * B, poses)
-        ans = _answers(source, h, ranges)
+        ranges = _scan(m, std, base + (K + i * K * (1 + L_)) * nb, poses, nb)
+        ans = _answers(source, h, ranges, nb)
         last["states"] = out
         return [(out[k], poses[k], float(ans[k]) if source != "random" else math.nan,
-                 RC.is_crashed(ranges[k], B, 1, edge, THRESH) >= 0) for k in range(K)]
+                 is_crashed(ranges[k], nb, 1, edge, THRESH) >= 0) for k in range(K)]
 
     def rollout_many(i, reqs, acts):
         acts_ro = np.stack([S.rollout_actions(int(seeds[k]), i, n_act, MAX_STEER, MAX_SPEED) for k in range(K)])
-        m.set_noise(std, 99, base + (K + i * K * (1 + L) + K) * B)
-        first, _, vel = cars.rollout_check(m, last["states"], acts_ro, FOV, B, edge, THRESH, n_steps=L,
-                                           action_every=EVERY)
+        m.set_noise(std, 99, base + (K + i * K * (1 + L_) + K) * nb)
+        first, _, vel = cars.rollout_check(m, last["states"], acts_ro, FOV, nb, edge, THRESH, n_steps=L_,
+                                           action_every=action_every)
+        if rollouts is not None:
+            rollouts.extend((int(first[k]), vel[k].copy()) for k, _ in reqs)
         return [(int(first[k]), vel[k]) for k, _ in reqs]
 
     snaps = S.run_lockstep(trees, n_it, act_many, rollout_many, snapshots=snapshots)
@@ -96,10 +101,13 @@ def _replay(cars, m, std, base, source, h, states, actions, seeds, n_it, dev_tre
     return trees, snaps
 
 
-def _device(cars, m, std, base, source, h, states, actions, seeds, n_it, max_nodes=None):
+def _device(cars, m, std, base, source, h, states, actions, seeds, n_it, max_nodes=None, *, num_rays=B,
+            rollout_steps=L, action_every=EVERY, edge=None):
     m.set_noise(std, 99, base)
-    pl = MCTSPlanner(cars, m, len(states), max_nodes or n_it + 1, FOV, B, _edge(), THRESH, source=source,
-                     followgap=h if source == "fg" else None, policy=h if source == "nn" else None)
+    pl = MCTSPlanner(cars, m, len(states), max_nodes or n_it + 1, FOV, num_rays,
+                     _edge(num_rays) if edge is None else edge, THRESH, source=source,
+                     followgap=h if source == "fg" else None, policy=h if source == "nn" else None,
+                     rollout_steps=rollout_steps, action_every=action_every)
     pl.reset(states, actions, seeds)
     pl.run(n_it)
     return pl, [pl.read_tree(k) for k in range(len(states))], pl.best()

@@ -45,20 +45,22 @@ def world():
             "cars": RC.CarBatch()}
 
 
-def _planner(cars, m, K, I, source, h):
-    return MCTSPlanner(cars, m, K, I + 1, FOV, B, _edge(), THRESH, source=source,
-                       followgap=h if source == "fg" else None, policy=h if source == "nn" else None,
-                       rollout_steps=L, action_every=EVERY)
+def _planner(cars, m, K, I, source, h, *, num_rays=B, rollout_steps=L, action_every=EVERY, edge=None):
+    return MCTSPlanner(cars, m, K, I + 1, FOV, num_rays, _edge(num_rays) if edge is None else edge, THRESH,
+                       source=source, followgap=h if source == "fg" else None, policy=h if source == "nn" else None,
+                       rollout_steps=rollout_steps, action_every=action_every)
 
 
-def _host_loop(cars, m, pl, std, base, states, recent, seeds, D, I, S, clip):
-    """The D decisions composed on the host from the public calls; leaves pl holding the last decision's trees."""
-    K = len(states)
-    stride = M.drive_stride(K, B, I, L)
+def _host_loop(cars, m, pl, std, base, states, recent, seeds, D, I, S, clip, *, num_rays=B, rollout_steps=L, edge=None,
+               is_crashed=RC.is_crashed):
+    """The D decisions composed on the host from the public calls; leaves pl holding the last decision's trees.
+    edge: the planner's outline table (the car's by default); is_crashed: the crash test of the root scans."""
+    K, nb = len(states), num_rays
+    stride = M.drive_stride(K, nb, I, rollout_steps)
     states, recent = states.copy(), np.array(recent, np.float64)
     first = np.full(K, -(D + 1), np.int32)
     actions, visits, trace = np.full((K, D), np.nan), np.full((K, D), -1, np.int32), np.full((K, D, 11), np.nan)
-    edge = _edge()
+    edge = _edge(nb) if edge is None else edge
     for d in range(D):
         off = base + d * stride
         m.set_noise(std, 99, off)
@@ -66,9 +68,9 @@ def _host_loop(cars, m, pl, std, base, states, recent, seeds, D, I, S, clip):
         pl.run(I)
         a, v, _ = pl.best()
         poses = np.stack([pl.read_tree(k)["scan_pose"][0] for k in range(K)])
-        ranges = _scan(m, std, off, poses)
+        ranges = _scan(m, std, off, poses, nb)
         for k in range(K):
-            if first[k] < 0 and RC.is_crashed(ranges[k], B, 1, edge, THRESH) >= 0:
+            if first[k] < 0 and is_crashed(ranges[k], nb, 1, edge, THRESH) >= 0:
                 first[k] = d
         live = first < 0
         trace[live, d], actions[live, d], visits[live, d] = states[live], a[live], v[live]
@@ -89,16 +91,20 @@ def _assert_drive(got, want, what):
 
 
 # ---------------------------------------------------------------- 1. the loop equals the host-composed loop
-def _loop_case(world, m, std, source, h, K, S, D, I):
+def _loop_case(world, m, std, source, h, K, S, D, I, *, num_rays=B, rollout_steps=L, action_every=EVERY, edge=None,
+               starts=None, is_crashed=RC.is_crashed):
+    """starts: (states, recent actions, seeds) of the K cars (drawn on the world's map by default)."""
     cars, base = world["cars"], 777
-    states, recent, seeds = _roots(world["g"], world["dt"], K, 31 + K)
-    host_pl, dev_pl = _planner(cars, m, K, I, source, h), _planner(cars, m, K, I, source, h)
+    states, recent, seeds = starts if starts is not None else _roots(world["g"], world["dt"], K, 31 + K)
+    shape = dict(num_rays=num_rays, rollout_steps=rollout_steps, action_every=action_every, edge=edge)
+    host_pl, dev_pl = _planner(cars, m, K, I, source, h, **shape), _planner(cars, m, K, I, source, h, **shape)
     try:
-        want = _host_loop(cars, m, host_pl, std, base, states, recent, seeds, D, I, S, CLIP)
+        want = _host_loop(cars, m, host_pl, std, base, states, recent, seeds, D, I, S, CLIP, num_rays=num_rays,
+                          rollout_steps=rollout_steps, edge=edge, is_crashed=is_crashed)
         print("first (host loop):", want[0])
         m.set_noise(std, 99, base)
         probe = states[:2, :3].astype(np.float32)
-        before = _scan_keep(m, probe)
+        before = _scan_keep(m, probe, num_rays)
         nt = m.get_info("nt_store")
         got = dev_pl.drive(states, recent, seeds, D, I, steps_per_decision=S, steer_clip=CLIP, trace=True)
         _assert_drive(got, want, (source, K, S))
@@ -110,7 +116,7 @@ def _loop_case(world, m, std, source, h, K, S, D, I):
         # the handle reads as before the call: the option the planner overrides, and the noise offset (a plain scan
         # draws the noise of the same ray ids)
         assert m.get_info("nt_store") == nt
-        assert _same_bits(_scan_keep(m, probe), before)
+        assert _same_bits(_scan_keep(m, probe, num_rays), before)
     finally:
         host_pl.close()
         dev_pl.close()
@@ -118,10 +124,10 @@ def _loop_case(world, m, std, source, h, K, S, D, I):
     return want
 
 
-def _scan_keep(m, poses):
+def _scan_keep(m, poses, num_rays=B):
     """A plain scan with the handle's noise settings as they stand."""
-    out = np.empty(len(poses) * B, np.float32)
-    m.calc_range_fan(np.ascontiguousarray(poses, np.float32), out, FOV, B)
+    out = np.empty(len(poses) * num_rays, np.float32)
+    m.calc_range_fan(np.ascontiguousarray(poses, np.float32), out, FOV, num_rays)
     return out
 
 
