@@ -544,6 +544,85 @@ int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const double *sta
                         int *first_crashed, double *states_out_or_null, double *velocities_or_null,
                         float *steers_or_null, float *scan_poses_or_null, double *states_trace_or_null);
 
+/* ---- the driving environment -------------------------------------------------------------------
+ * The closed loops above with the steering source left to the caller: a vectorised, device-resident environment.
+ * Every call takes one (speed, steer) pair per env and, for n_envs cars at once, steps them, scans them, tests them
+ * for a crash, computes a reward and writes the observation; episode ends, truncation and re-spawning happen on the
+ * device.  rl_car_drive_followgap and rl_car_drive_policy are closed special cases: fed FollowGap's or the network's
+ * answers to its observations the environment reproduces their traces bit for bit (with their noise base set
+ * n_envs num_rays above the environment's: the reset takes slot 0).  tests/env_statement.py restates this section.
+ *
+ * c and h are borrowed (keep them alive as long as the env) and sit on ONE device; h may be any kind, with its
+ * options and its noise.  edge: num_rays doubles (rl_car_edge_distances).  starts_m11: the pool of start states,
+ * n_starts rows in getState layout, copied at create.  The observation of an env is obs_count floats: beam
+ * obs_start + i obs_stride of its scan for i < obs_count, raw metres (obs_scale = 0) or the policy network's input
+ * form (r <= obs_clip) ? r / obs_scale : 1.0f (obs_scale > 0).
+ *
+ * Every f64 operation below is separately rounded (the library is built with -ffp-contract=off).
+ * Counters: k counts the calls since the last reset (the reset itself is slot 0, the first step slot 1).  Per env:
+ *   tick[e], episode[e], start_index[e] and done[e] in {0 running, 1 crashed, 2 truncated, 3 invalid action}.
+ * Spawn of env e at episode q: state = starts[idx] with idx = start_index[e] when the caller gave start indices and
+ *   q = 0, otherwise idx = min(M-1, (int)(U(e, q) * (double)M)), U the planner's 53-bit uniform (Philox-2x32-10
+ *   under noise_key(seed) with counter (e, q), as in the MCTS section).
+ * Reset: every env spawns with q = 0, tick = 0; then the f32 lidar pose of Car::getScanPose (as in the closed
+ *   loops), the scan at ray offset base + e num_rays, and phase B below with every env "fresh".  A start inside the
+ *   crash margin reads done = 1 at once.  base is h's ray offset at the reset.
+ * Step k, phase A (env_step_kernel, one lane per env):
+ *   done[e] != 0 and auto_reset: spawn with q = episode[e] + 1, tick = 0, the action is ignored, done = 0, the env
+ *     is "fresh";
+ *   done[e] != 0 without auto_reset: nothing changes (rl_car_drive_followgap's frozen car): it is scanned again at
+ *     its last pose with this slot's noise;
+ *   otherwise speed = (double)a[0], steer = (double)a[1]; if either is not finite: done = 3, the state is left as it
+ *     is (no non-finite value reaches the car step or a lidar pose); else steer is clamped to +-steer_clip when
+ *     steer_clip > 0 (fmin(fmax(steer, -clip), clip), as rl_car_drive_policy), `substeps` times Car::control +
+ *     Car::updatePosition(dt) with (speed, steer), tick += 1, moved = travel_dist after - travel_dist before;
+ *   every env then writes its f32 lidar pose.
+ * Scan: all n_envs lidar poses with ray offset base + (k n_envs + e) num_rays.
+ * Phase B (env_observe_kernel, one wave per env): Car::isCrashed on the scan; for an env that stepped or is fresh a
+ *   hit sets done = 1; otherwise a stepped env with max_ticks > 0 and tick == max_ticks gets done = 2 (a crash on
+ *   the max_ticks step reads 1).  reward (f32): (float)moved for a stepped env that did not crash; (float)crash_reward
+ *   where this call's action set done to 1 (a stepped env) or 3; 0.0f for fresh envs (their action was ignored, also
+ *   where the start lies inside the crash margin) and frozen ones.  obs: row e of [n_envs, obs_count].  aux
+ *   (optional): row e of [n_envs, 4] = (velocity, steer_angle, angular_velocity, slip_angle) of the state, cast to f32.
+ *
+ * rl_env_reset / rl_env_step: host pointers, synchronous on c's stream.  start_index_or_null: n_envs indices into
+ * the pool.  actions_n2: [n_envs, 2] f32.  rl_env_reset_device / rl_env_step_device: device pointers; they only
+ * enqueue on the given stream (null = the null stream) and never wait for the device; the device form clamps start
+ * indices to [0, M).  A host form (and rl_env_read) that follows device-form calls waits for the whole device first,
+ * so the two may be mixed.  rl_env_read: the states [n_envs, 11] and the counters, each pointer optional.  h's
+ * options and ray offset read the same after every call.
+ *
+ * Errors (RL_ERR_INVALID, nothing launched, the handles usable as before): null required pointers, n_envs < 1,
+ * substeps outside [1, 512], num_rays outside [10, 1280], an observation window that leaves [0, num_rays), obs_count
+ * or obs_stride < 1, negative or NaN steer_clip / obs_clip / obs_scale, NaN crash_reward, non-finite dt, max_ticks
+ * < 0, n_starts < 1, a non-finite start state, n_envs num_rays >= 2^31, a start_index outside [0, M) (host form),
+ * handles on different devices or multi-device handles, a step or read before a reset; the range method's own
+ * refusals come back with their code.  After a failed launch the env needs a reset.
+ * Out of scope: races inside the environment (a car re-spawned alone into a running race has no obvious rule),
+ * multi-device handles, graph capture (a step advances host-side counters).
+ * Per call: env_step_kernel, the fan launch sequence of h's planner, env_observe_kernel (env_kernels.h).       */
+typedef struct rl_env rl_env;
+typedef struct rl_env_params {
+    int n_envs, substeps, num_rays;
+    int obs_start, obs_count, obs_stride;   /* observation = beams obs_start + i*obs_stride, i < obs_count */
+    float obs_clip, obs_scale;              /* obs_scale > 0: policy_input(r, clip, scale); 0: raw metres  */
+    int max_ticks;                          /* 0: never truncate                                           */
+    int auto_reset;                         /* 0: a finished env freezes; 1: it re-spawns on the next step */
+    double dt, scan_dist_to_base, crash_thresh, steer_clip, crash_reward;
+    float fov;
+} rl_env_params;
+int  rl_env_create(rl_car *c, rl_method *h, const rl_env_params *p, const double *edge,
+                   const double *starts_m11, int n_starts, rl_env **out);
+void rl_env_destroy(rl_env *e);
+int  rl_env_reset(rl_env *e, uint64_t seed, const int *start_index_or_null,
+                  float *obs, float *aux_or_null, int *done);
+int  rl_env_step(rl_env *e, const float *actions_n2, float *obs, float *reward, int *done, float *aux_or_null);
+int  rl_env_reset_device(rl_env *e, uint64_t seed, const int *d_start_index_or_null,
+                         float *d_obs, float *d_aux_or_null, int *d_done, void *hip_stream);
+int  rl_env_step_device(rl_env *e, const float *d_actions_n2, float *d_obs, float *d_reward, int *d_done,
+                        float *d_aux_or_null, void *hip_stream);
+int  rl_env_read(rl_env *e, double *states_n11, int *ticks, int *episodes, int *start_index, int *done);
+
 /* ---- the MCTS planner ----------------------------------------------------------------------------
  * scripts/mcts.py's tree search (MCTS.mcts / mctsIteration / act / rollout, :109-245) for K independent trees in
  * lock step on one device: every iteration adds exactly one node to every tree, so each iteration is one batched

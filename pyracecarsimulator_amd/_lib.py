@@ -63,6 +63,14 @@ class PfParams(C.Structure):
                 ("resample_ratio", C.c_double)]
 
 
+class EnvParams(C.Structure):
+    """rl_env_params (include/scanlib.h)."""
+    _fields_ = [(n, C.c_int) for n in ("n_envs", "substeps", "num_rays", "obs_start", "obs_count", "obs_stride")] + [
+        ("obs_clip", C.c_float), ("obs_scale", C.c_float), ("max_ticks", C.c_int), ("auto_reset", C.c_int)] + [
+        (n, C.c_double) for n in ("dt", "scan_dist_to_base", "crash_thresh", "steer_clip", "crash_reward")] + [
+        ("fov", C.c_float)]
+
+
 RL_MCTS_FG, RL_MCTS_NN, RL_MCTS_RANDOM = 0, 1, 2
 
 KERNEL_IDS = {0: "none", 1: "rm_chunk", 2: "rm_stream", 3: "occ_lds", 4: "bl_stream", 5: "bl_lds", 6: "lut_lds",
@@ -162,6 +170,13 @@ SYMBOLS = {
     "rl_car_drive_policy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, f64p, f64p, f32p, C.c_int, C.c_int,
                                       C.c_double, C.c_double, C.c_float, C.c_int, f64p, C.c_double, C.c_double,
                                       C.POINTER(C.c_int), f64p, f64p, f32p, f32p, f64p]),
+    "rl_env_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(EnvParams), f64p, f64p, C.c_int, C.POINTER(C.c_void_p)]),
+    "rl_env_destroy": (None, [C.c_void_p]),
+    "rl_env_reset": (C.c_int, [C.c_void_p, C.c_uint64, i32p, f32p, f32p, i32p]),
+    "rl_env_step": (C.c_int, [C.c_void_p, f32p, f32p, f32p, i32p, f32p]),
+    "rl_env_reset_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rl_env_step_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rl_env_read": (C.c_int, [C.c_void_p, f64p, i32p, i32p, i32p, i32p]),
     "rl_mcts_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MctsParams), f64p,
                                  C.POINTER(C.c_void_p)]),
     "rl_mcts_destroy": (None, [C.c_void_p]),

@@ -1,12 +1,13 @@
 // abi_car.hip — what sits in front of and behind the scan path in libscan_amd.so (C ABI: include/scanlib.h; SURVEY.md
-// section 8f): the MCTS roll-out generator, FollowGap, 16-bit ranges for the xGMI exchange, diagnostics probes, the
-// car-outline table and Car::isCrashed on the host.
+// section 8f): the MCTS roll-out generator, FollowGap, the closed loops and the driving environment, 16-bit ranges for
+// the xGMI exchange, diagnostics probes, the car-outline table and Car::isCrashed on the host.
 #include "abi_internal.h"
 #include <array>
 #include <utility>
 #include "car_kernels.h"
 #include "consumer_kernels.h"
 #include "drive_kernels.h"
+#include "env_kernels.h"
 #include "mcts_kernels.h"
 #include "policy_kernels.h"
 #include "probe_kernels.h"
@@ -758,6 +759,286 @@ extern "C" int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const 
     return drive_loop(c, h, nullptr, p, steer_clip, states_in, speeds, steer0_or_null, R, 0, n_ticks, dt,
                       scan_dist_to_base, fov, num_rays, edge, crash_thresh, first_crashed, states_out_or_null,
                       velocities_or_null, steers_or_null, scan_poses_or_null, states_trace_or_null);
+}
+
+// ---------------------------------------------------------------- the driving environment (env_kernels.h)
+typedef void (*env_observe_fn)(EnvParams, EnvBufs, float *, float *, int *, float *);
+static const std::array<env_observe_fn, FG_ROWS> env_observe_table =
+    rows_table<env_observe_fn>([](auto rows) { return env_observe_kernel<rows>; });
+
+struct rl_env {
+    rl_car *c = nullptr;
+    rl_method *h = nullptr;
+    rl_env_params prm{};
+    EnvParams ep{};
+    int device = 0, n_starts = 0;
+    DevBuf state, starts, edge, tick, episode, start_index, done, phase, moved, pose, ranges;
+    // the host forms' staging: actions and start indices in, observation, reward, done and aux out
+    DevBuf h_actions, h_sidx, h_obs, h_reward, h_done, h_aux;
+    bool ready = false;            // reset done and no launch failed since
+    bool foreign = false;          // the last launches went to a caller's stream: a host form waits for the device first
+    uint64_t k = 0;                // calls since the last reset (the reset is slot 0)
+    uint64_t base = 0;             // h's ray offset at the last reset
+    std::mutex mu;
+};
+
+static EnvBufs env_bufs(rl_env *e)
+{
+    return EnvBufs{(double *)e->state.p, (const double *)e->starts.p, (const double *)e->edge.p, (int *)e->tick.p,
+                   (int *)e->episode.p, (int *)e->start_index.p, (int *)e->done.p, (int *)e->phase.p,
+                   (double *)e->moved.p, (float *)e->pose.p, (const float *)e->ranges.p};
+}
+
+extern "C" void rl_env_destroy(rl_env *e)
+{
+    if (!e) return;
+    (void)hipSetDevice(e->device);
+    if (e->foreign) (void)hipDeviceSynchronize();
+    else if (e->c && e->c->stream) (void)hipStreamSynchronize(e->c->stream);
+    delete e;
+}
+
+extern "C" int rl_env_create(rl_car *c, rl_method *h, const rl_env_params *params, const double *edge,
+                             const double *starts_m11, int n_starts, rl_env **out)
+{
+    if (!c || !h || !params || !edge || !starts_m11 || !out) return fail(RL_ERR_INVALID, "rl_env_create: null pointer");
+    const rl_env_params q = *params;
+    if (!c->reps.empty() || !h->reps.empty())
+        return fail(RL_ERR_INVALID, "%s is single-device only: pass ordinary (not multi-device) handles", "rl_env_create");
+    if (c->device != h->map->device)
+        return fail(RL_ERR_INVALID, "car (device %d) and range method (device %d) must share one device", c->device,
+                    h->map->device);
+    if (q.n_envs < 1) return fail(RL_ERR_INVALID, "rl_env_create: n_envs must be >= 1 (got %d)", q.n_envs);
+    if (q.substeps < 1 || q.substeps > 512)
+        return fail(RL_ERR_INVALID, "rl_env_create: substeps must lie in [1, 512] (got %d)", q.substeps);
+    if (q.num_rays < 10 || q.num_rays > 64 * FG_ROWS)
+        return fail(RL_ERR_INVALID, "num_rays must lie in [10, %d] (got %d)", 64 * FG_ROWS, q.num_rays);
+    if (q.obs_count < 1 || q.obs_stride < 1 || q.obs_start < 0 ||
+        (long)q.obs_start + ((long)q.obs_count - 1) * q.obs_stride >= q.num_rays)
+        return fail(RL_ERR_INVALID, "rl_env_create: the observation window (start %d, count %d, stride %d) must lie in "
+                    "[0, %d) with count and stride >= 1", q.obs_start, q.obs_count, q.obs_stride, q.num_rays);
+    if (!(q.steer_clip >= 0.0) || !(q.obs_clip >= 0.0f) || !(q.obs_scale >= 0.0f))
+        return fail(RL_ERR_INVALID, "rl_env_create: steer_clip, obs_clip and obs_scale must be >= 0 and not NaN");
+    if (q.crash_reward != q.crash_reward || !std::isfinite(q.dt))
+        return fail(RL_ERR_INVALID, "rl_env_create: crash_reward must not be NaN and dt must be finite");
+    if (q.max_ticks < 0) return fail(RL_ERR_INVALID, "rl_env_create: max_ticks must be >= 0 (got %d)", q.max_ticks);
+    if (n_starts < 1) return fail(RL_ERR_INVALID, "rl_env_create: n_starts must be >= 1 (got %d)", n_starts);
+    if (n_starts > INT_MAX / 11) return fail(RL_ERR_INVALID, "rl_env_create: too many start states (%d)", n_starts);
+    for (size_t i = 0; i < (size_t)n_starts * 11; ++i)
+        if (!std::isfinite(starts_m11[i]))
+            return fail(RL_ERR_INVALID, "rl_env_create: start state %zu holds a non-finite value", i / 11);
+    if ((long)q.n_envs * q.num_rays >= (1L << 31)) return fail(RL_ERR_INVALID, "n_envs * num_rays must stay below 2^31");
+    int rc = check_fan_args(h, q.n_envs, q.fov, q.num_rays);
+    if (rc) return rc;
+    std::unique_ptr<rl_env, decltype(&rl_env_destroy)> e(new (std::nothrow) rl_env(), rl_env_destroy);
+    if (!e) return fail(RL_ERR_NOMEM, "out of host memory");
+    e->c = c;
+    e->h = h;
+    e->prm = q;
+    e->device = c->device;
+    e->n_starts = n_starts;
+    EnvParams &ep = e->ep;
+    ep.P = c->P;
+    ep.dt = q.dt;
+    ep.scan_dist_to_base = q.scan_dist_to_base;
+    ep.crash_thresh = q.crash_thresh;
+    ep.steer_clip = q.steer_clip;
+    ep.crash_reward = q.crash_reward;
+    ep.n_envs = q.n_envs;
+    ep.substeps = q.substeps;
+    ep.num_rays = q.num_rays;
+    ep.obs_start = q.obs_start;
+    ep.obs_count = q.obs_count;
+    ep.obs_stride = q.obs_stride;
+    ep.obs_clip = q.obs_clip;
+    ep.obs_scale = q.obs_scale;
+    ep.max_ticks = q.max_ticks;
+    ep.auto_reset = q.auto_reset != 0;
+    ep.n_starts = n_starts;
+    if (hipSetDevice(e->device) != hipSuccess) return fail(RL_ERR_HIP, "rl_env_create: hipSetDevice failed");
+    const size_t N = q.n_envs, B = q.num_rays, M = n_starts;
+    struct { DevBuf *b; size_t bytes; } need[] = {
+        {&e->state, N * 88}, {&e->starts, M * 88}, {&e->edge, B * 8}, {&e->tick, N * 4}, {&e->episode, N * 4},
+        {&e->start_index, N * 4}, {&e->done, N * 4}, {&e->phase, N * 4}, {&e->moved, N * 8}, {&e->pose, N * 12},
+        {&e->ranges, N * B * 4}, {&e->h_actions, N * 8}, {&e->h_sidx, N * 4}, {&e->h_obs, N * q.obs_count * 4},
+        {&e->h_reward, N * 4}, {&e->h_done, N * 4}, {&e->h_aux, N * 16}};
+    for (auto &n : need)
+        if ((rc = n.b->ensure(n.bytes))) return rc;
+    if (hipMemcpy(e->starts.p, starts_m11, M * 88, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(e->edge.p, edge, B * 8, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(RL_ERR_HIP, "rl_env_create: upload failed");
+    *out = e.release();
+    return RL_OK;
+}
+
+// the handles every launching call locks, in one order; h's options and ray offset come back before the locks go
+struct EnvLock {
+    std::unique_lock<std::mutex> le, lc, lh;
+    std::shared_lock<std::shared_mutex> ml;
+    HandleOverride ov;
+    explicit EnvLock(rl_env *e) : le(e->mu), lc(e->c->mu), lh(e->h->mu), ml(e->h->map->tables_mu), ov(e->h) {}
+};
+
+// one call's launches on st: phase A (reset: the spawn), the scan at slot k, phase B.  The caller holds EnvLock.
+static int env_launch(rl_env *e, bool reset, uint64_t k, const float *d_actions, const int *d_start_index, float *d_obs,
+                      float *d_reward, int *d_done, float *d_aux, hipStream_t st)
+{
+    const int N = e->prm.n_envs, B = e->prm.num_rays;
+    const EnvBufs b = env_bufs(e);
+    hipLaunchKernelGGL(env_step_kernel, dim3((N + 63) / 64), dim3(64), 0, st, e->ep, b, d_actions, d_start_index,
+                       reset ? 1 : 0);
+    if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "env_step_kernel launch failed");
+    e->h->ray_offset = e->base + k * (uint64_t)N * (uint64_t)B;
+    const int rc = launch_fan(e->h, (const float *)e->pose.p, N, e->prm.fov, B, (float *)e->ranges.p, nullptr, nullptr,
+                              nullptr, st);
+    if (rc) return rc;
+    env_observe_table[(B + 63) / 64 - 1]<<<dim3((N + DRIVE_CARS - 1) / DRIVE_CARS), dim3(64 * DRIVE_CARS), 0, st>>>(
+        e->ep, b, d_obs, d_reward, d_done, d_aux);
+    if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "env_observe_kernel launch failed");
+    return RL_OK;
+}
+
+// a host form after launches on a caller's stream: c's stream is not ordered behind that one
+static int env_settle(rl_env *e)
+{
+    if (e->foreign) {
+        HIPCHK(hipDeviceSynchronize());
+        e->foreign = false;
+    }
+    return RL_OK;
+}
+
+static int env_reset_locked(rl_env *e, const EnvLock &lk, uint64_t seed, const int *d_start_index, float *d_obs,
+                            float *d_aux, int *d_done, hipStream_t st)
+{
+    e->ready = false;
+    e->ep.key = (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x85EBCA6Bu);     // np_statement.noise_key
+    e->base = lk.ov.ray_offset;
+    const int rc = env_launch(e, true, 0, nullptr, d_start_index, d_obs, nullptr, d_done, d_aux, st);
+    if (rc) return rc;
+    e->k = 0;
+    e->ready = true;
+    return RL_OK;
+}
+
+static int env_step_locked(rl_env *e, const float *d_actions, float *d_obs, float *d_reward, int *d_done, float *d_aux,
+                           hipStream_t st)
+{
+    const int rc = env_launch(e, false, e->k + 1, d_actions, nullptr, d_obs, d_reward, d_done, d_aux, st);
+    if (rc) {
+        e->ready = false;                   // part of the step may have run: the env needs a reset
+        return rc;
+    }
+    e->k += 1;
+    return RL_OK;
+}
+
+extern "C" int rl_env_reset_device(rl_env *e, uint64_t seed, const int *d_start_index_or_null, float *d_obs,
+                                   float *d_aux_or_null, int *d_done, void *hip_stream)
+{
+    if (!e || !d_obs || !d_done) return fail(RL_ERR_INVALID, "rl_env_reset_device: null pointer");
+    int rc = check_fan_args(e->h, e->prm.n_envs, e->prm.fov, e->prm.num_rays);
+    if (rc) return rc;
+    EnvLock lk(e);
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (st != (hipStream_t)e->c->stream) e->foreign = true;
+    return env_reset_locked(e, lk, seed, d_start_index_or_null, d_obs, d_aux_or_null, d_done, st);
+}
+
+extern "C" int rl_env_step_device(rl_env *e, const float *d_actions_n2, float *d_obs, float *d_reward, int *d_done,
+                                  float *d_aux_or_null, void *hip_stream)
+{
+    if (!e || !d_actions_n2 || !d_obs || !d_reward || !d_done) return fail(RL_ERR_INVALID, "rl_env_step_device: null pointer");
+    if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_step_device: reset the environment first (rl_env_reset)");
+    int rc = check_fan_args(e->h, e->prm.n_envs, e->prm.fov, e->prm.num_rays);
+    if (rc) return rc;
+    EnvLock lk(e);
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (st != (hipStream_t)e->c->stream) e->foreign = true;
+    return env_step_locked(e, d_actions_n2, d_obs, d_reward, d_done, d_aux_or_null, st);
+}
+
+// the host forms' way back: the staged results to the caller, then the wait
+static int env_download(rl_env *e, float *obs, float *reward, int *done, float *aux, hipStream_t st)
+{
+    const size_t N = e->prm.n_envs;
+    HIPCHK(hipMemcpyAsync(obs, e->h_obs.p, N * e->prm.obs_count * 4, hipMemcpyDeviceToHost, st));
+    if (reward) HIPCHK(hipMemcpyAsync(reward, e->h_reward.p, N * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(done, e->h_done.p, N * 4, hipMemcpyDeviceToHost, st));
+    if (aux) HIPCHK(hipMemcpyAsync(aux, e->h_aux.p, N * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
+}
+
+extern "C" int rl_env_reset(rl_env *e, uint64_t seed, const int *start_index_or_null, float *obs, float *aux_or_null,
+                            int *done)
+{
+    if (!e || !obs || !done) return fail(RL_ERR_INVALID, "rl_env_reset: null pointer");
+    const int N = e->prm.n_envs;
+    if (start_index_or_null)
+        for (int i = 0; i < N; ++i)
+            if (start_index_or_null[i] < 0 || start_index_or_null[i] >= e->n_starts)
+                return fail(RL_ERR_INVALID, "rl_env_reset: start_index[%d] = %d lies outside [0, %d)", i,
+                            start_index_or_null[i], e->n_starts);
+    int rc = check_fan_args(e->h, N, e->prm.fov, e->prm.num_rays);
+    if (rc) return rc;
+    EnvLock lk(e);
+    HIPCHK(hipSetDevice(e->device));
+    if ((rc = env_settle(e))) return rc;
+    hipStream_t st = e->c->stream;
+    if (start_index_or_null)
+        HIPCHK(hipMemcpyAsync(e->h_sidx.p, start_index_or_null, (size_t)N * 4, hipMemcpyHostToDevice, st));
+    rc = env_reset_locked(e, lk, seed, start_index_or_null ? (const int *)e->h_sidx.p : nullptr, (float *)e->h_obs.p,
+                          aux_or_null ? (float *)e->h_aux.p : nullptr, (int *)e->h_done.p, st);
+    if (rc) {
+        (void)hipStreamSynchronize(st);           // nothing of this call is left in flight
+        return rc;
+    }
+    if ((rc = env_download(e, obs, nullptr, done, aux_or_null, st))) e->ready = false;
+    return rc;
+}
+
+extern "C" int rl_env_step(rl_env *e, const float *actions_n2, float *obs, float *reward, int *done, float *aux_or_null)
+{
+    if (!e || !actions_n2 || !obs || !reward || !done) return fail(RL_ERR_INVALID, "rl_env_step: null pointer");
+    if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_step: reset the environment first (rl_env_reset)");
+    const int N = e->prm.n_envs;
+    int rc = check_fan_args(e->h, N, e->prm.fov, e->prm.num_rays);
+    if (rc) return rc;
+    EnvLock lk(e);
+    HIPCHK(hipSetDevice(e->device));
+    if ((rc = env_settle(e))) return rc;
+    hipStream_t st = e->c->stream;
+    HIPCHK(hipMemcpyAsync(e->h_actions.p, actions_n2, (size_t)N * 8, hipMemcpyHostToDevice, st));
+    rc = env_step_locked(e, (const float *)e->h_actions.p, (float *)e->h_obs.p, (float *)e->h_reward.p,
+                         (int *)e->h_done.p, aux_or_null ? (float *)e->h_aux.p : nullptr, st);
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    if ((rc = env_download(e, obs, reward, done, aux_or_null, st))) e->ready = false;
+    return rc;
+}
+
+extern "C" int rl_env_read(rl_env *e, double *states_n11, int *ticks, int *episodes, int *start_index, int *done)
+{
+    if (!e) return fail(RL_ERR_INVALID, "rl_env_read: null pointer");
+    if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_read: reset the environment first (rl_env_reset)");
+    std::scoped_lock lk(e->mu, e->c->mu);
+    HIPCHK(hipSetDevice(e->device));
+    int rc = env_settle(e);
+    if (rc) return rc;
+    hipStream_t st = e->c->stream;
+    const size_t N = e->prm.n_envs;
+    if (states_n11) HIPCHK(hipMemcpyAsync(states_n11, e->state.p, N * 88, hipMemcpyDeviceToHost, st));
+    if (ticks) HIPCHK(hipMemcpyAsync(ticks, e->tick.p, N * 4, hipMemcpyDeviceToHost, st));
+    if (episodes) HIPCHK(hipMemcpyAsync(episodes, e->episode.p, N * 4, hipMemcpyDeviceToHost, st));
+    if (start_index) HIPCHK(hipMemcpyAsync(start_index, e->start_index.p, N * 4, hipMemcpyDeviceToHost, st));
+    if (done) HIPCHK(hipMemcpyAsync(done, e->done.p, N * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return RL_OK;
 }
 
 // ---------------------------------------------------------------- diagnostics: HBM stream probe

@@ -7,7 +7,7 @@
 //                  particle-filter weights (repeat-angle scans, sensor model) and localisation (rl_pf_*)
 //   abi_multi.hip  the host-pointer entry points and their multi-device forms (run_blocks below: one block per device)
 //   abi_car.hip    roll-out generator, FollowGap, the policy network, closed-loop FollowGap / policy roll-outs,
-//                  batched races and the race scan, the MCTS planner and its closed-loop drive (rl_mcts_*), 16-bit
+//                  the driving environment (rl_env_*), batched races and the race scan, the MCTS planner and its closed-loop drive (rl_mcts_*), 16-bit
 //                  ranges, probes, the car-outline table and cells
 #pragma once
 // (the units are built with -fvisibility=hidden: only the C ABI leaves the library)

@@ -27,6 +27,9 @@ BOUNDS = [
     # car step in one wave per car, no spills
     ("scan::drive_tick_kernel<", {"scratch": 0}),
     ("scan::drive_start_kernel", {"scratch": 0}),
+    # the driving environment: the spawn / step lane and the observe wave keep nothing in scratch
+    ("scan::env_step_kernel", {"scratch": 0}),
+    ("scan::env_observe_kernel<", {"scratch": 0}),
     # the policy network: the micro-tile accumulators stay in registers
     ("scan::policy_mlp_kernel", {"scratch": 0}),
     # the MCTS planner: the descent, the act wave, the backup's pairwise sum and the walks keep nothing in scratch

@@ -1,0 +1,154 @@
+// env_kernels.h — the driving environment (rl_env_*; include/scanlib.h): the closed loop of drive_kernels.h opened at
+// the steering source.  Every call takes one (speed, steer) pair per env from the caller and, for N envs with nothing
+// crossing PCIe in between, enqueues on one stream:
+//   A. env_step_kernel, one lane per env: re-spawn (auto_reset) or the action check, the steer clamp and `substeps`
+//      car steps in f64, then the f32 lidar pose.  One lane per env from the start: a step on lane 0 of a wave each
+//      spends the whole wave's f64 issue on one car (drive_tick_kernel's comment has the figure).
+//   -. the scan of all N lidar poses: the ordinary fan planner (launch_fan, abi_fan.hip).
+//   B. env_observe_kernel<ROWS>, one wave per env: Car::isCrashed as a ballot (drive_crashed), truncation, the reward,
+//      the observation window (lane-contiguous stores), the optional aux row.
+// A reset is the same sequence with env_step_kernel in spawn mode.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "car_kernels.h"
+#include "drive_kernels.h"
+#include "policy_kernels.h"
+#include "scan_device.h"
+
+namespace scan {
+
+// what a call did to an env (EnvBufs::phase), phase A's message to phase B
+enum : int { ENV_FROZEN = 0, ENV_STEPPED = 1, ENV_FRESH = 2, ENV_INVALID = 3 };
+// done codes (include/scanlib.h)
+enum : int { ENV_RUNNING = 0, ENV_CRASHED = 1, ENV_TRUNCATED = 2, ENV_BAD_ACTION = 3 };
+
+struct EnvParams {
+    CarParams P;
+    double dt, scan_dist_to_base, crash_thresh, steer_clip, crash_reward;
+    int n_envs, substeps, num_rays;
+    int obs_start, obs_count, obs_stride;
+    float obs_clip, obs_scale;
+    int max_ticks, auto_reset;
+    int n_starts;
+    uint32_t key;                // noise_key(seed) of the last reset: the spawn draws
+};
+
+struct EnvBufs {
+    double *state;               // [N, 11] getState layout
+    const double *starts;        // [M, 11] the start pool
+    const double *edge;          // [num_rays] car-outline table
+    int *tick, *episode, *start_index, *done;     // [N] each
+    int *phase;                  // [N] ENV_* of this call
+    double *moved;               // [N] travel_dist gained by this call's steps
+    float *pose;                 // [N, 3] f32 lidar pose the scan reads
+    const float *ranges;         // [N, num_rays] this call's scans
+};
+
+// env e's start of episode q: the caller's index (clamped to the pool) or the planner's uniform at counter (e, q)
+__device__ inline int env_spawn_index(const EnvParams &p, int e, int q, const int *given)
+{
+    if (given) return min(max(given[e], 0), p.n_starts - 1);
+    const double u = mcts_uniform01(p.key, (uint32_t)e, (uint32_t)q);
+    return min(p.n_starts - 1, (int)(u * (double)p.n_starts));
+}
+
+__device__ inline void env_spawn(const EnvParams &p, const EnvBufs &b, int e, int q, const int *given, CarState &cs)
+{
+    const int idx = env_spawn_index(p, e, q, given);
+    const double *s = b.starts + (size_t)idx * 11;
+    double *o = b.state + (size_t)e * 11;
+#pragma unroll
+    for (int i = 0; i < 11; ++i) o[i] = s[i];
+    cs = drive_load_state(s);
+    b.tick[e] = 0;
+    b.episode[e] = q;
+    b.start_index[e] = idx;
+    b.done[e] = ENV_RUNNING;
+    b.phase[e] = ENV_FRESH;
+    b.moved[e] = 0.0;
+}
+
+// phase A.  reset != 0: every env spawns with q = 0 (start_index: the caller's indices or null); otherwise one step
+// of the state machine with actions [N, 2] f32 (speed, steer).
+__global__ __launch_bounds__(64) void env_step_kernel(EnvParams p, EnvBufs b, const float *__restrict__ actions,
+                                                      const int *__restrict__ start_index, int reset)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= p.n_envs) return;
+    double *s = b.state + (size_t)e * 11;
+    CarState cs;
+    if (reset) {
+        env_spawn(p, b, e, 0, start_index, cs);
+    } else if (b.done[e] != ENV_RUNNING) {
+        if (p.auto_reset) {
+            env_spawn(p, b, e, b.episode[e] + 1, nullptr, cs);
+        } else {
+            cs = drive_load_state(s);            // frozen: scanned again where it stands
+            b.phase[e] = ENV_FROZEN;
+            b.moved[e] = 0.0;
+        }
+    } else {
+        cs = drive_load_state(s);
+        const double speed = (double)actions[2 * e + 0];
+        double steer = (double)actions[2 * e + 1];
+        if (!(isfinite(speed) && isfinite(steer))) {
+            b.done[e] = ENV_BAD_ACTION;          // the state stays as it is: nothing non-finite reaches car_step
+            b.phase[e] = ENV_INVALID;
+            b.moved[e] = 0.0;
+        } else {
+            if (p.steer_clip > 0.0) steer = fmin(fmax(steer, -p.steer_clip), p.steer_clip);   // PolicySteer::steer
+            const double before = cs.travel_dist;
+            for (int i = 0; i < p.substeps; ++i) car_step(p.P, cs, speed, steer, p.dt);
+            drive_store_state(cs, s);
+            b.tick[e] += 1;
+            b.phase[e] = ENV_STEPPED;
+            b.moved[e] = cs.travel_dist - before;
+        }
+    }
+    float pose[3];
+    car_scan_pose(cs, p.scan_dist_to_base, pose);
+    b.pose[3 * e + 0] = pose[0];
+    b.pose[3 * e + 1] = pose[1];
+    b.pose[3 * e + 2] = pose[2];
+}
+
+// phase B: DRIVE_CARS envs per workgroup, one wave each (ROWS = ceil(num_rays / 64)).  reward may be null (a reset
+// has none), aux too.
+template <int ROWS>
+__global__ __launch_bounds__(64 * DRIVE_CARS) void env_observe_kernel(EnvParams p, EnvBufs b, float *__restrict__ obs,
+                                                                      float *__restrict__ reward,
+                                                                      int *__restrict__ done_out,
+                                                                      float *__restrict__ aux)
+{
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int e = blockIdx.x * DRIVE_CARS + w;
+    if (e >= p.n_envs) return;                                  // (wave-uniform; no block barrier below)
+    const float *row = b.ranges + (size_t)e * p.num_rays;
+    float raw[ROWS];
+    const bool hit = drive_crashed<ROWS>(row, b.edge, p.num_rays, p.crash_thresh, lane, raw);
+    const int phase = b.phase[e];
+    int done = b.done[e];
+    const bool stepped = phase == ENV_STEPPED;
+    if ((stepped || phase == ENV_FRESH) && hit) done = ENV_CRASHED;
+    else if (stepped && p.max_ticks > 0 && b.tick[e] == p.max_ticks) done = ENV_TRUNCATED;
+    // the distance of a step that did not crash; crash_reward where this call's action ended the episode with 1 or 3;
+    // 0 for fresh envs (their action was ignored, even where the start lies inside the crash margin) and frozen ones
+    float r = 0.0f;
+    if (stepped) r = done == ENV_CRASHED ? (float)p.crash_reward : (float)b.moved[e];
+    else if (phase == ENV_INVALID) r = (float)p.crash_reward;
+    if (lane == 0) {
+        b.done[e] = done;
+        done_out[e] = done;
+        if (reward) reward[e] = r;
+    }
+    float *o = obs + (size_t)e * p.obs_count;
+    for (int i = lane; i < p.obs_count; i += 64) {              // lane i of a round stores word i: whole lines
+        const float v = row[p.obs_start + i * p.obs_stride];
+        o[i] = p.obs_scale > 0.0f ? policy_input(v, p.obs_clip, p.obs_scale) : v;
+    }
+    if (aux && lane < 4) aux[4 * (size_t)e + lane] = (float)b.state[(size_t)e * 11 + 3 + lane];
+}
+
+}  // namespace scan

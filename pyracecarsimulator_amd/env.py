@@ -1,0 +1,220 @@
+"""``DriveEnv`` — a batched, device-resident driving environment (``rl_env_*``, include/scanlib.h).
+
+The closed loops of ``racecar.CarBatch`` (``drive_followgap``, ``drive_policy``, ``drive_mcts``) have their steering
+source compiled in.  ``DriveEnv`` is the same loop opened at that point: every ``step`` takes one (speed, steer) pair
+per env from the caller — a PyTorch policy being trained, another planner, a heuristic — and, for ``n_envs`` cars at
+once on the GPU, steps the cars, scans them, tests them for a crash, computes a reward and writes the observation.
+Episode ends, truncation after ``max_ticks`` steps and re-spawning from a pool of start states happen on the device.
+
+Two forms, picked by what ``step`` is given:
+
+* a NumPy ``(n_envs, 2)`` float32 array takes the host form: synchronous, returns NumPy arrays;
+* a torch tensor on the env's device takes the device form: the launches are enqueued on
+  ``torch.cuda.current_stream()`` and nothing waits for the GPU.  It returns torch tensors that the env allocated
+  once: THE NEXT CALL OVERWRITES THEM (clone what must be kept).
+
+The interface follows the usual vectorised-environment shape (``reset`` -> obs, ``step`` -> obs, reward, done) but
+depends on no environment toolkit.  ``done`` codes: 0 running, 1 crashed, 2 truncated, 3 invalid (non-finite) action.
+The reward of a step is the distance travelled (float32), ``crash_reward`` for a step that crashes or an invalid
+action, 0 for an env that was re-spawned by this call or that stands frozen.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import f32p, f64p, i32p
+
+
+def env_args(n_envs, num_rays, starts, edge, substeps=1, obs_window=None, obs_clip=0, obs_scale=0, max_ticks=0,
+             steer_clip=0, crash_reward=0, dt=0.01):
+    """``DriveEnv``'s arguments checked and laid out for ``rl_env_create`` (no library call): returns (starts float64
+    (M, 11), edge float64 (num_rays,), (obs_start, obs_count, obs_stride)).  ``obs_window`` None: every beam."""
+    N, B = int(n_envs), int(num_rays)
+    if (N, B) != (n_envs, num_rays) or int(substeps) != substeps or int(max_ticks) != max_ticks:
+        raise ValueError("n_envs, num_rays, substeps and max_ticks must be integers")
+    if N < 1:
+        raise ValueError("n_envs must be >= 1")
+    if not 1 <= int(substeps) <= 512:
+        raise ValueError("substeps must lie in [1, 512]")
+    if not 10 <= B <= 1280:
+        raise ValueError("num_rays must lie in [10, 1280]")
+    if N * B >= 1 << 31:
+        raise ValueError("n_envs * num_rays must stay below 2^31")
+    if int(max_ticks) < 0:
+        raise ValueError("max_ticks must be >= 0")
+    st = np.asarray(starts)
+    if st.dtype != np.float64 or st.ndim != 2 or st.shape[1] != 11 or st.shape[0] < 1:
+        raise ValueError("starts must be float64 (M, 11) with M >= 1")
+    if not np.isfinite(st).all():
+        raise ValueError("starts must be finite")
+    ed = np.asarray(edge)
+    if ed.dtype != np.float64 or ed.shape != (B,):
+        raise ValueError("edge must be float64 (num_rays,)")
+    win = (0, B, 1) if obs_window is None else tuple(obs_window)
+    if len(win) != 3 or any(int(v) != v for v in win):
+        raise ValueError("obs_window must be None or three integers (start, count, stride)")
+    start, count, stride = (int(v) for v in win)
+    if count < 1 or stride < 1 or start < 0 or start + (count - 1) * stride >= B:
+        raise ValueError("obs_window (start, count, stride) must lie in [0, num_rays) with count and stride >= 1")
+    for name, v in (("steer_clip", steer_clip), ("obs_clip", obs_clip), ("obs_scale", obs_scale)):
+        if not float(v) >= 0:
+            raise ValueError("%s must be >= 0" % name)
+    if float(crash_reward) != float(crash_reward):
+        raise ValueError("crash_reward must not be NaN")
+    if not np.isfinite(float(dt)):
+        raise ValueError("dt must be finite")
+    return np.ascontiguousarray(st), np.ascontiguousarray(ed), (start, count, stride)
+
+
+class DriveEnv(_lib.Handle):
+    """``n_envs`` cars on one device, driven by the caller's actions.  ``method`` scans (any kind, with its options and
+    noise), ``starts`` float64 (M, 11) is the pool of start states (getState layout), ``edge`` the car-outline table
+    (``racecar.edge_distances``).  ``obs_window`` (start, count, stride) picks the beams of the observation (None:
+    all); ``obs_scale`` > 0 gives them in the policy network's input form, (r <= obs_clip) ? r / obs_scale : 1.
+    ``car``: a ``CarBatch`` on the method's device (None: one with the default parameters).  The handles are
+    borrowed: the env keeps them alive."""
+    _destroy = "rl_env_destroy"
+
+    def __init__(self, method, starts, n_envs, num_rays, fov, edge, crash_thresh, *, substeps=1, obs_window=None,
+                 obs_clip=0, obs_scale=0, max_ticks=0, auto_reset=True, steer_clip=0, crash_reward=0, car=None,
+                 dt=0.01, scan_dist_to_base=0.275):
+        st, ed, win = env_args(n_envs, num_rays, starts, edge, substeps, obs_window, obs_clip, obs_scale, max_ticks,
+                               steer_clip, crash_reward, dt)
+        if car is None:
+            from .racecar import CarBatch
+            car = CarBatch(device=self._method_device(method))
+        p = _lib.EnvParams()
+        p.n_envs, p.substeps, p.num_rays = int(n_envs), int(substeps), int(num_rays)
+        p.obs_start, p.obs_count, p.obs_stride = win
+        p.obs_clip, p.obs_scale = float(obs_clip), float(obs_scale)
+        p.max_ticks, p.auto_reset = int(max_ticks), int(bool(auto_reset))
+        p.dt, p.scan_dist_to_base, p.crash_thresh = float(dt), float(scan_dist_to_base), float(crash_thresh)
+        p.steer_clip, p.crash_reward, p.fov = float(steer_clip), float(crash_reward), float(fov)
+        self.params = p
+        self.n_starts = st.shape[0]
+        self._keep = (car, method)
+        self._n, self._count = int(n_envs), win[1]
+        self._torch = None            # the device form's tensors, made at its first call
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().rl_env_create(car._h, method._h, C.byref(p), ed.ctypes.data_as(f64p),
+                                            st.ctypes.data_as(f64p), st.shape[0], C.byref(self._h)))
+        self.device = self._method_device(method)
+
+    @staticmethod
+    def _method_device(method):
+        omap = getattr(method, "omap", None)
+        dev = getattr(omap, "device", 0)
+        return dev if isinstance(dev, int) else 0
+
+    @property
+    def n_envs(self):
+        return self._n
+
+    @property
+    def obs_shape(self):
+        return (self._n, self._count)
+
+    # -- the device form's buffers ----------------------------------------------------
+    def _tensors(self):
+        if self._torch is None:
+            import torch
+            dev = torch.device("cuda", self.device)
+            self._torch = dict(obs=torch.empty(self.obs_shape, dtype=torch.float32, device=dev),
+                               reward=torch.zeros(self._n, dtype=torch.float32, device=dev),
+                               done=torch.zeros(self._n, dtype=torch.int32, device=dev),
+                               aux=torch.empty((self._n, 4), dtype=torch.float32, device=dev))
+        return self._torch
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _is_tensor(self, x):
+        return x is not None and not isinstance(x, np.ndarray) and type(x).__module__.split(".")[0] == "torch"
+
+    def _check_tensor(self, x, shape, dtype_name, what):
+        import torch
+        if (not x.is_cuda or x.device.index != self.device or x.dtype != getattr(torch, dtype_name)
+                or tuple(x.shape) != shape or not x.is_contiguous()):
+            raise ValueError("%s must be a contiguous %s tensor of shape %s on cuda:%d" % (what, dtype_name, shape,
+                                                                                           self.device))
+
+    # -- calls ------------------------------------------------------------------------
+    def reset(self, seed=0, start_index=None, *, aux=False, on_device=False):
+        """Spawn every env (episode 0) and scan it: returns the observation (n_envs, obs_count) float32, plus the aux
+        rows with ``aux=True``.  ``start_index`` None: each env draws its start from the pool with the counter-based
+        uniform of ``seed``; int32 (n_envs,): the given pool rows.  A torch ``start_index`` or ``on_device=True``
+        takes the device form (see the module text: its tensors are overwritten by the next call).  ``read()['done']``
+        shows the starts that lie inside the crash margin."""
+        seed = int(seed)
+        if seed < 0 or seed >= 1 << 64:
+            raise ValueError("seed must lie in [0, 2^64)")
+        if self._is_tensor(start_index) or on_device:
+            t = self._tensors()
+            sidx = None
+            if start_index is not None:
+                if not self._is_tensor(start_index):
+                    raise ValueError("on_device=True takes start_index as a torch tensor (or None)")
+                self._check_tensor(start_index, (self._n,), "int32", "start_index")
+                sidx = start_index.data_ptr()
+            _lib.check(_lib.lib().rl_env_reset_device(
+                self._h, seed, C.c_void_p(sidx), C.c_void_p(t["obs"].data_ptr()),
+                C.c_void_p(t["aux"].data_ptr()) if aux else None, C.c_void_p(t["done"].data_ptr()),
+                C.c_void_p(self._stream())))
+            return (t["obs"], t["aux"]) if aux else t["obs"]
+        sidx = None
+        if start_index is not None:
+            sidx = np.asarray(start_index)
+            if sidx.dtype.kind not in "iu" or sidx.shape != (self._n,):
+                raise ValueError("start_index must be integers (n_envs,)")
+            if ((sidx < 0) | (sidx >= self.n_starts)).any():
+                raise ValueError("start_index must lie in [0, %d)" % self.n_starts)
+            sidx = np.ascontiguousarray(sidx, dtype=np.int32)
+        obs = np.empty(self.obs_shape, np.float32)
+        done = np.empty(self._n, np.int32)
+        ax = np.empty((self._n, 4), np.float32) if aux else None
+        _lib.check(_lib.lib().rl_env_reset(self._h, seed, sidx.ctypes.data_as(i32p) if sidx is not None else None,
+                                           obs.ctypes.data_as(f32p), ax.ctypes.data_as(f32p) if aux else None,
+                                           done.ctypes.data_as(i32p)))
+        return (obs, ax) if aux else obs
+
+    def step(self, actions, aux=False):
+        """One call of the state machine with ``actions`` (n_envs, 2) float32 as (speed, steer): returns (obs
+        (n_envs, obs_count) float32, reward (n_envs,) float32, done (n_envs,) int32) and with ``aux=True`` also
+        (n_envs, 4) float32 = (velocity, steer_angle, angular_velocity, slip_angle).  NumPy in, NumPy out
+        (synchronous); a torch tensor on the env's device in, the env's own torch tensors out (enqueued on the
+        current stream; overwritten by the next call)."""
+        if self._is_tensor(actions):
+            self._check_tensor(actions, (self._n, 2), "float32", "actions")
+            t = self._tensors()
+            _lib.check(_lib.lib().rl_env_step_device(
+                self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(t["obs"].data_ptr()),
+                C.c_void_p(t["reward"].data_ptr()), C.c_void_p(t["done"].data_ptr()),
+                C.c_void_p(t["aux"].data_ptr()) if aux else None, C.c_void_p(self._stream())))
+            return (t["obs"], t["reward"], t["done"]) + ((t["aux"],) if aux else ())
+        a = np.asarray(actions)
+        if a.dtype != np.float32 or a.shape != (self._n, 2):
+            raise ValueError("actions must be float32 (n_envs, 2)")
+        a = np.ascontiguousarray(a)
+        obs = np.empty(self.obs_shape, np.float32)
+        reward = np.empty(self._n, np.float32)
+        done = np.empty(self._n, np.int32)
+        ax = np.empty((self._n, 4), np.float32) if aux else None
+        _lib.check(_lib.lib().rl_env_step(self._h, a.ctypes.data_as(f32p), obs.ctypes.data_as(f32p),
+                                          reward.ctypes.data_as(f32p), done.ctypes.data_as(i32p),
+                                          ax.ctypes.data_as(f32p) if aux else None))
+        return (obs, reward, done) + ((ax,) if aux else ())
+
+    def read(self):
+        """The envs as they stand (waits for the device): a dict of ``states`` float64 (n_envs, 11) and ``ticks``,
+        ``episodes``, ``start_index``, ``done`` int32 (n_envs,)."""
+        out = dict(states=np.empty((self._n, 11)), ticks=np.empty(self._n, np.int32),
+                   episodes=np.empty(self._n, np.int32), start_index=np.empty(self._n, np.int32),
+                   done=np.empty(self._n, np.int32))
+        _lib.check(_lib.lib().rl_env_read(self._h, out["states"].ctypes.data_as(f64p), out["ticks"].ctypes.data_as(i32p),
+                                          out["episodes"].ctypes.data_as(i32p),
+                                          out["start_index"].ctypes.data_as(i32p), out["done"].ctypes.data_as(i32p)))
+        return out

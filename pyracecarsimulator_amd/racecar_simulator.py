@@ -15,7 +15,8 @@ it unchanged.  The two native pieces behind it are on the GPU:
 (scripts/mcts.py:202-245) for any number of roll-outs per call; ``driveFollowGapMany`` the closed
 loop of the simulator tick and simple_driver.py's FollowGap answer to every scan; ``drivePolicyMany`` the same loop
 steered by the policy network (scripts/policy_driver.py); ``planMCTSMany`` scripts/mcts.py's tree search from many
-start states at once; ``raceFollowGapMany`` many races of up to 8 cars that see each other (scripts/two_player/).
+start states at once; ``raceFollowGapMany`` many races of up to 8 cars that see each other (scripts/two_player/);
+``driveEnv`` the same tick with the steering left to the caller (``env.DriveEnv``).
 """
 from __future__ import annotations
 
@@ -244,6 +245,17 @@ class RacecarSimulator:
         if sensor_model is not None:
             method.set_sensor_model(sensor_model)
         return ParticleFilter(method, angles, n_particles, motion_std=motion_std, resample_ratio=resample_ratio)
+
+    def driveEnv(self, n_envs, starts, **kw):
+        """A ``DriveEnv`` of ``n_envs`` cars on this simulator's range method, car, fan, edge table, ttc_thresh and
+        scan_dist_to_base, spawning from ``starts`` float64 (M, 11): the tick of ``driveFollowGapMany`` with the (speed,
+        steer) of every step supplied by the caller.  ``kw``: ``DriveEnv``'s keyword arguments (substeps, obs_window,
+        obs_clip, obs_scale, max_ticks, auto_reset, steer_clip, crash_reward, dt)."""
+        from .env import DriveEnv
+        kw.setdefault("car", self.car)
+        kw.setdefault("scan_dist_to_base", self.scan_dist_to_base)
+        return DriveEnv(self.scan_simulator.scan_method, np.asarray(starts, dtype=np.float64).reshape(-1, 11), n_envs,
+                        self.num_rays, self.scan_fov, self.edge_distances, self.ttc_thresh, **kw)
 
     def stop(self):
         state = self.getState()
