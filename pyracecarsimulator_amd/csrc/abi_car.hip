@@ -1,6 +1,7 @@
 // abi_car.hip — what sits in front of and behind the scan path in libscan_amd.so (C ABI: include/scanlib.h; SURVEY.md
-// section 8f): the MCTS roll-out generator, FollowGap, the closed loops and the driving environment, 16-bit ranges for
-// the xGMI exchange, diagnostics probes, the car-outline table and Car::isCrashed on the host.
+// section 8f): the MCTS roll-out generator, FollowGap, the policy network, the race scan; the closed-loop session (loop_args
+// and Loop: handle checks, locks, option override, scan-then-consume) with its users drive_loop, rl_env_* and rl_mcts_*;
+// 16-bit ranges for the xGMI exchange, diagnostics probes, the car-outline table and Car::isCrashed on the host.
 #include "abi_internal.h"
 #include <array>
 #include <utility>
@@ -579,12 +580,10 @@ extern "C" int rl_policy_eval_device(rl_policy *p, const float *d_scans, int n_s
     return policy_launch(p, d_scans, n_scans, size, d_steers, (hipStream_t)hip_stream);
 }
 
-// ---------------------------------------------------------------- closed-loop roll-outs (drive_kernels.h)
-typedef void (*drive_tick_fn)(DriveParams, DriveBufs, int);
-static const std::array<drive_tick_fn, FG_ROWS> fg_tick_table =
-    rows_table<drive_tick_fn>([](auto rows) { return drive_tick_kernel<rows, FollowGapSteer>; });
-static const std::array<drive_tick_fn, FG_ROWS> policy_tick_table =
-    rows_table<drive_tick_fn>([](auto rows) { return drive_tick_kernel<rows, PolicySteer>; });
+// ---------------------------------------------------------------- the closed-loop session
+// What the closed loops share on the host.  The roll-outs (drive_loop), the driving environment (rl_env_*) and the MCTS
+// planner (rl_mcts_*) check their handles with loop_args, and each of their launching calls lives inside one Loop: its
+// locks, the override of the method's options, and the scan-then-consume step every one of them is made of.
 
 // the options of h that a closed loop overrides, restored on every exit: its consumer kernels read the ranges right after
 // the scan (plain stores), and it walks the noise offset from the value saved here
@@ -602,104 +601,169 @@ struct HandleOverride {
     HandleOverride &operator=(const HandleOverride &) = delete;
 };
 
-// the checks every closed loop makes; the steering source is exactly one of g and p
-static int drive_args(const char *name, rl_car *c, rl_method *h, const rl_followgap *g, const rl_policy *p, int R,
-                      int n_ticks, int num_rays)
+// the handle checks of every closed loop: `units` cars / envs / poses scan num_rays beams each; the steering source is
+// g, p or neither (the environment, the planner's random source)
+static int loop_args(const char *name, const rl_car *c, const rl_method *h, const rl_followgap *g, const rl_policy *p,
+                     long units, int num_rays)
 {
     if (!c->reps.empty() || !h->reps.empty())
         return fail(RL_ERR_INVALID, "%s is single-device only: pass ordinary (not multi-device) handles", name);
-    const int src_device = g ? g->device : p->device;
-    if (c->device != h->map->device || src_device != c->device)
-        return fail(RL_ERR_INVALID, "car (device %d), range method (device %d) and %s (device %d) must share one device",
-                    c->device, h->map->device, g ? "FollowGap" : "policy", src_device);
-    if (R < 0 || n_ticks <= 0) return fail(RL_ERR_INVALID, "n_rollouts >= 0 and n_ticks > 0 required (got %d, %d)", R, n_ticks);
+    const int src_device = g ? g->device : p ? p->device : c->device;
+    if (c->device != h->map->device || src_device != c->device) {
+        char src[48] = "";
+        if (g || p) snprintf(src, sizeof src, " and %s (device %d)", g ? "FollowGap" : "policy", src_device);
+        return fail(RL_ERR_INVALID, "%s: car (device %d)%s range method (device %d)%s must share one device", name, c->device,
+                    g || p ? "," : " and", h->map->device, src);
+    }
     if (num_rays < 10 || num_rays > 64 * FG_ROWS)
         return fail(RL_ERR_INVALID, "num_rays must lie in [10, %d] (got %d)", 64 * FG_ROWS, num_rays);
-    if ((long)R * num_rays >= (1L << 31)) return fail(RL_ERR_INVALID, "n_rollouts * num_rays must stay below 2^31");
+    if (units * num_rays >= (1L << 31))
+        return fail(RL_ERR_INVALID, "%s: %ld scans of %d beams: their product must stay below 2^31", name, units, num_rays);
     return RL_OK;
 }
 
-// R cars for n_ticks ticks, steered by FollowGap (g) or the policy network (p, steer_clip); group 0: every car scans alone
-// with h's planner, group >= 1: the cars scan in races of `group` (race_fan_kernel).  The caller has checked the arguments.
-static int drive_loop(rl_car *c, rl_method *h, rl_followgap *g, rl_policy *p, double steer_clip, const double *states_in,
-                      const double *speeds, const float *steer0_or_null, int R, int group, int n_ticks, double dt,
-                      double scan_dist_to_base, float fov, int num_rays, const double *edge, double crash_thresh,
-                      int *first_crashed, double *states_out_or_null, double *velocities_or_null, float *steers_or_null,
-                      float *scan_poses_or_null, double *states_trace_or_null)
+// one scan of a closed loop: n poses (a race: n / group races over the cars' f64 states, 11 doubles a car) into `ranges`,
+// and into `mlp` the policy's answers when the loop's source is one
+struct LoopScan {
+    const float *poses;
+    int n;
+    float fov;
+    int num_rays;
+    float *ranges, *mlp;
+    int group;                      // 0: every pose scans alone with the method's planner
+    const double *cars;
+    const OutlineParams *outline;
+};
+
+// One launching call of a closed loop.  Locks in ONE order: the owner's mutex (rl_env::mu, rl_mcts::mu; none for the
+// roll-outs), the car's, the method's, the steering source's (if any), then the map's tables_mu shared; the method's
+// options are overridden last and come back first.  `ready` of an owner is read and written inside only.
+struct Loop {
+    rl_method *const h;
+    rl_policy *const p;
+    std::unique_lock<std::mutex> lo, lc, lh, ls;
+    std::shared_lock<std::shared_mutex> ml;
+    const HandleOverride ov;
+    static std::unique_lock<std::mutex> held(std::mutex *m) { return m ? std::unique_lock(*m) : std::unique_lock<std::mutex>(); }
+    Loop(std::mutex *owner, rl_car *c, rl_method *h_, rl_followgap *g, rl_policy *p_)
+        : h(h_), p(p_), lo(held(owner)), lc(c->mu), lh(h_->mu), ls(held(g ? &g->mu : p_ ? &p_->mu : nullptr)),
+          ml(h_->map->tables_mu), ov(h_)
+    {
+    }
+
+    // scan-then-consume on st: the scan at noise offset `off`, the network when the source is a policy, then the ROWS
+    // instantiation of `table` for num_rays, one wave per unit and per_wg units per workgroup
+    template <class Fn, class... Args>
+    int scan_then(const LoopScan &s, uint64_t off, const std::array<Fn, FG_ROWS> &table, int per_wg, const char *kernel,
+                  hipStream_t st, const Args &...args) const
+    {
+        h->ray_offset = off;
+        int rc = s.group > 0 ? launch_race(h, s.poses, s.cars, 11, s.n / s.group, s.group, *s.outline, s.fov, s.num_rays,
+                                           s.ranges, nullptr, nullptr, st)
+                             : launch_fan(h, s.poses, s.n, s.fov, s.num_rays, s.ranges, nullptr, nullptr, nullptr, st);
+        if (rc == RL_OK && p) rc = policy_launch(p, s.ranges, s.n, s.num_rays, s.mlp, st);
+        if (rc) return rc;
+        table[(s.num_rays + 63) / 64 - 1]<<<dim3((s.n + per_wg - 1) / per_wg), dim3(64 * per_wg), 0, st>>>(args...);
+        if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "%s launch failed", kernel);
+        return RL_OK;
+    }
+};
+
+// ---------------------------------------------------------------- closed-loop roll-outs (drive_kernels.h)
+typedef void (*drive_tick_fn)(DriveParams, DriveBufs, int);
+static const std::array<drive_tick_fn, FG_ROWS> fg_tick_table =
+    rows_table<drive_tick_fn>([](auto rows) { return drive_tick_kernel<rows, FollowGapSteer>; });
+static const std::array<drive_tick_fn, FG_ROWS> policy_tick_table =
+    rows_table<drive_tick_fn>([](auto rows) { return drive_tick_kernel<rows, PolicySteer>; });
+
+// what the three roll-out entry points share of their arguments (include/scanlib.h names them)
+struct DriveCall {
+    const double *states_in, *speeds;
+    const float *steer0;
+    int n_ticks;
+    double dt, scan_dist_to_base;
+    float fov;
+    int num_rays;
+    const double *edge;
+    double crash_thresh;
+    int *first_crashed;
+    double *states_out, *velocities;
+    float *steers, *scan_poses;
+    double *states_trace;
+};
+
+// n cars for n_ticks ticks, steered by FollowGap (g) or the policy network (p, steer_clip), each scanning alone with h's
+// planner; race: n races of `group` cars, which see each other in every scan (race_fan_kernel)
+static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g, rl_policy *p, double steer_clip, int n,
+                      bool race, int group, const DriveCall &a)
 {
-    int rc = RL_OK;
+    if (!c || !h || !(g || p) || (n > 0 && (!a.states_in || !a.speeds || !a.edge || !a.first_crashed)))
+        return fail(RL_ERR_INVALID, "%s: null pointer", name);
+    const int n_ticks = a.n_ticks, num_rays = a.num_rays;
+    int rc;
+    if (race && n < 0) return fail(RL_ERR_INVALID, "n_races must be >= 0 (got %d)", n);
+    if (race && (rc = race_args(h, n, group, num_rays))) return rc;
+    const int R = race ? n * group : n;          // (a race: < 2^31 / num_rays, race_args)
+    if ((rc = loop_args(name, c, h, g, p, R, num_rays))) return rc;
+    if (R < 0 || n_ticks <= 0) return fail(RL_ERR_INVALID, "n_rollouts >= 0 and n_ticks > 0 required (got %d, %d)", R, n_ticks);
+    if ((p && (rc = policy_args(p, R, num_rays))) || (rc = check_fan_args(h, R, a.fov, num_rays)) || R == 0) return rc;
     OutlineParams op{};
-    if (group > 0 && (rc = race_outline(h->map, c->P.LENGTH, c->P.WIDTH, op))) return rc;
-    std::scoped_lock lk(c->mu, h->mu, g ? g->mu : p->mu);
-    std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
+    if (race && (rc = race_outline(h->map, c->P.LENGTH, c->P.WIDTH, op))) return rc;
+    const Loop lp(nullptr, c, h, g, p);
     HIPCHK(hipSetDevice(c->device));
     const size_t rows = (size_t)R * n_ticks, n_rays = (size_t)R * num_rays;
     if ((rc = c->states.ensure((size_t)R * 11 * 8)) || (rc = c->speeds.ensure((size_t)R * 8)) ||
         (rc = c->steer0.ensure((size_t)R * 4)) || (rc = c->first.ensure((size_t)R * 4)) ||
         (rc = c->poses.ensure((size_t)R * 12)) || (rc = c->ranges.ensure(n_rays * 4)) ||
         (rc = c->edge.ensure((size_t)num_rays * 8)) || (p && (rc = c->mlp.ensure((size_t)R * 4))) ||
-        (velocities_or_null && (rc = c->vel.ensure(rows * 8))) || (steers_or_null && (rc = c->tr_steers.ensure(rows * 4))) ||
-        (scan_poses_or_null && (rc = c->tr_poses.ensure(rows * 12))) ||
-        (states_trace_or_null && (rc = c->tr_states.ensure(rows * 88))))
+        (a.velocities && (rc = c->vel.ensure(rows * 8))) || (a.steers && (rc = c->tr_steers.ensure(rows * 4))) ||
+        (a.scan_poses && (rc = c->tr_poses.ensure(rows * 12))) || (a.states_trace && (rc = c->tr_states.ensure(rows * 88))))
         return rc;
     hipStream_t st = c->stream;
-    HIPCHK(hipMemcpyAsync(c->states.p, states_in, (size_t)R * 11 * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(c->speeds.p, speeds, (size_t)R * 8, hipMemcpyHostToDevice, st));
-    if (steer0_or_null) HIPCHK(hipMemcpyAsync(c->steer0.p, steer0_or_null, (size_t)R * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->states.p, a.states_in, (size_t)R * 11 * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->speeds.p, a.speeds, (size_t)R * 8, hipMemcpyHostToDevice, st));
+    if (a.steer0) HIPCHK(hipMemcpyAsync(c->steer0.p, a.steer0, (size_t)R * 4, hipMemcpyHostToDevice, st));
     else HIPCHK(hipMemsetAsync(c->steer0.p, 0, (size_t)R * 4, st));
-    HIPCHK(hipMemcpyAsync(c->edge.p, edge, (size_t)num_rays * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->edge.p, a.edge, (size_t)num_rays * 8, hipMemcpyHostToDevice, st));
     // trace rows a car never reaches (after its crash tick; the steer of the crash tick) read NaN: all-ones bytes
-    if (velocities_or_null) HIPCHK(hipMemsetAsync(c->vel.p, 0xff, rows * 8, st));
-    if (steers_or_null) HIPCHK(hipMemsetAsync(c->tr_steers.p, 0xff, rows * 4, st));
-    if (scan_poses_or_null) HIPCHK(hipMemsetAsync(c->tr_poses.p, 0xff, rows * 12, st));
-    if (states_trace_or_null) HIPCHK(hipMemsetAsync(c->tr_states.p, 0xff, rows * 88, st));
+    if (a.velocities) HIPCHK(hipMemsetAsync(c->vel.p, 0xff, rows * 8, st));
+    if (a.steers) HIPCHK(hipMemsetAsync(c->tr_steers.p, 0xff, rows * 4, st));
+    if (a.scan_poses) HIPCHK(hipMemsetAsync(c->tr_poses.p, 0xff, rows * 12, st));
+    if (a.states_trace) HIPCHK(hipMemsetAsync(c->tr_states.p, 0xff, rows * 88, st));
 
     DriveParams dp{};
     dp.P = c->P;
     if (g) dp.fg = g->P;
     dp.fg.size = num_rays;                        // (for the policy only the crash ballot's beam count)
-    dp.dt = dt;
-    dp.scan_dist_to_base = scan_dist_to_base;
-    dp.crash_thresh = crash_thresh;
+    dp.dt = a.dt;
+    dp.scan_dist_to_base = a.scan_dist_to_base;
+    dp.crash_thresh = a.crash_thresh;
     dp.n_cars = R;
     dp.n_ticks = n_ticks;
     dp.steer_clip = steer_clip;
     DriveBufs b{(double *)c->states.p, (const double *)c->speeds.p, (const float *)c->steer0.p, (const double *)c->edge.p,
                 (int *)c->first.p, (float *)c->poses.p, (const float *)c->ranges.p,
-                velocities_or_null ? (double *)c->vel.p : nullptr, steers_or_null ? (float *)c->tr_steers.p : nullptr,
-                scan_poses_or_null ? (float *)c->tr_poses.p : nullptr,
-                states_trace_or_null ? (double *)c->tr_states.p : nullptr, p ? (const float *)c->mlp.p : nullptr};
+                a.velocities ? (double *)c->vel.p : nullptr, a.steers ? (float *)c->tr_steers.p : nullptr,
+                a.scan_poses ? (float *)c->tr_poses.p : nullptr, a.states_trace ? (double *)c->tr_states.p : nullptr,
+                p ? (const float *)c->mlp.p : nullptr};
     hipLaunchKernelGGL(drive_start_kernel, dim3((R + 63) / 64), dim3(64), 0, st, dp, b);
     HIPCHK(hipGetLastError());
-    {
-        // the noise offset walks the global ray id t R num_rays + r num_rays of every tick
-        const HandleOverride ov(h);
-        const drive_tick_fn tick = (g ? fg_tick_table : policy_tick_table)[(num_rays + 63) / 64 - 1];
-        for (int t = 0; t < n_ticks && rc == RL_OK; ++t) {
-            h->ray_offset = ov.ray_offset + (uint64_t)t * n_rays;
-            // (a race reads every car's outline from its f64 state after this tick's step: all cars step, then all scan)
-            rc = group > 0 ? launch_race(h, (const float *)c->poses.p, (const double *)c->states.p, 11, R / group, group,
-                                         op, fov, num_rays, (float *)c->ranges.p, nullptr, nullptr, st)
-                           : launch_fan(h, (const float *)c->poses.p, R, fov, num_rays, (float *)c->ranges.p, nullptr,
-                                        nullptr, nullptr, st);
-            if (rc == RL_OK && p) rc = policy_launch(p, (const float *)c->ranges.p, R, num_rays, (float *)c->mlp.p, st);
-            if (rc == RL_OK) {
-                tick<<<dim3((R + DRIVE_CARS - 1) / DRIVE_CARS), dim3(64 * DRIVE_CARS), 0, st>>>(dp, b, t);
-                if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "drive_tick_kernel launch failed");
-            }
-        }
-    }
+    // the noise offset walks the global ray id t R num_rays + r num_rays of every tick
+    // (a race reads every car's outline from its f64 state after this tick's step: all cars step, then all scan)
+    const LoopScan scan{b.pose, R, a.fov, num_rays, (float *)c->ranges.p, (float *)c->mlp.p, race ? group : 0, b.state, &op};
+    for (int t = 0; t < n_ticks && rc == RL_OK; ++t)
+        rc = lp.scan_then(scan, lp.ov.ray_offset + (uint64_t)t * n_rays, g ? fg_tick_table : policy_tick_table, DRIVE_CARS,
+                          "drive_tick_kernel", st, dp, b, t);
     if (rc) {
         (void)hipStreamSynchronize(st);           // nothing of this call is left in flight on the handles' buffers
         return rc;
     }
-    HIPCHK(hipMemcpyAsync(first_crashed, c->first.p, (size_t)R * 4, hipMemcpyDeviceToHost, st));
-    if (states_out_or_null) HIPCHK(hipMemcpyAsync(states_out_or_null, c->states.p, (size_t)R * 88, hipMemcpyDeviceToHost, st));
-    if (velocities_or_null) HIPCHK(hipMemcpyAsync(velocities_or_null, c->vel.p, rows * 8, hipMemcpyDeviceToHost, st));
-    if (steers_or_null) HIPCHK(hipMemcpyAsync(steers_or_null, c->tr_steers.p, rows * 4, hipMemcpyDeviceToHost, st));
-    if (scan_poses_or_null) HIPCHK(hipMemcpyAsync(scan_poses_or_null, c->tr_poses.p, rows * 12, hipMemcpyDeviceToHost, st));
-    if (states_trace_or_null)
-        HIPCHK(hipMemcpyAsync(states_trace_or_null, c->tr_states.p, rows * 88, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(a.first_crashed, c->first.p, (size_t)R * 4, hipMemcpyDeviceToHost, st));
+    if (a.states_out) HIPCHK(hipMemcpyAsync(a.states_out, c->states.p, (size_t)R * 88, hipMemcpyDeviceToHost, st));
+    if (a.velocities) HIPCHK(hipMemcpyAsync(a.velocities, c->vel.p, rows * 8, hipMemcpyDeviceToHost, st));
+    if (a.steers) HIPCHK(hipMemcpyAsync(a.steers, c->tr_steers.p, rows * 4, hipMemcpyDeviceToHost, st));
+    if (a.scan_poses) HIPCHK(hipMemcpyAsync(a.scan_poses, c->tr_poses.p, rows * 12, hipMemcpyDeviceToHost, st));
+    if (a.states_trace) HIPCHK(hipMemcpyAsync(a.states_trace, c->tr_states.p, rows * 88, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return RL_OK;
 }
@@ -711,15 +775,10 @@ extern "C" int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, 
                                       double *velocities_or_null, float *steers_or_null, float *scan_poses_or_null,
                                       double *states_trace_or_null)
 {
-    if (!c || !h || !g || (R > 0 && (!states_in || !speeds || !edge || !first_crashed)))
-        return fail(RL_ERR_INVALID, "rl_car_drive_followgap: null pointer");
-    int rc;
-    if ((rc = drive_args("rl_car_drive_followgap", c, h, g, nullptr, R, n_ticks, num_rays)) ||
-        (rc = check_fan_args(h, R, fov, num_rays)) || R == 0)
-        return rc;
-    return drive_loop(c, h, g, nullptr, 0.0, states_in, speeds, steer0_or_null, R, 0, n_ticks, dt, scan_dist_to_base,
-                      fov, num_rays, edge, crash_thresh, first_crashed, states_out_or_null, velocities_or_null,
-                      steers_or_null, scan_poses_or_null, states_trace_or_null);
+    const DriveCall a{states_in, speeds, steer0_or_null, n_ticks, dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh,
+                      first_crashed, states_out_or_null, velocities_or_null, steers_or_null, scan_poses_or_null,
+                      states_trace_or_null};
+    return drive_loop("rl_car_drive_followgap", c, h, g, nullptr, 0.0, R, false, 0, a);
 }
 
 extern "C" int rl_car_race_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in,
@@ -729,18 +788,10 @@ extern "C" int rl_car_race_followgap(rl_car *c, rl_method *h, rl_followgap *g, c
                                      double *states_out_or_null, double *velocities_or_null, float *steers_or_null,
                                      float *scan_poses_or_null, double *states_trace_or_null)
 {
-    if (!c || !h || !g || (n_races > 0 && (!states_in || !speeds || !edge || !first_crashed)))
-        return fail(RL_ERR_INVALID, "rl_car_race_followgap: null pointer");
-    if (n_races < 0) return fail(RL_ERR_INVALID, "n_races must be >= 0 (got %d)", n_races);
-    int rc = race_args(h, n_races, group, num_rays);
-    if (rc) return rc;
-    const int R = n_races * group;          // (< 2^31 / num_rays: race_args)
-    if ((rc = drive_args("rl_car_race_followgap", c, h, g, nullptr, R, n_ticks, num_rays)) ||
-        (rc = check_fan_args(h, R, fov, num_rays)) || R == 0)
-        return rc;
-    return drive_loop(c, h, g, nullptr, 0.0, states_in, speeds, steer0_or_null, R, group, n_ticks, dt, scan_dist_to_base,
-                      fov, num_rays, edge, crash_thresh, first_crashed, states_out_or_null, velocities_or_null,
-                      steers_or_null, scan_poses_or_null, states_trace_or_null);
+    const DriveCall a{states_in, speeds, steer0_or_null, n_ticks, dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh,
+                      first_crashed, states_out_or_null, velocities_or_null, steers_or_null, scan_poses_or_null,
+                      states_trace_or_null};
+    return drive_loop("rl_car_race_followgap", c, h, g, nullptr, 0.0, n_races, true, group, a);
 }
 
 extern "C" int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const double *states_in,
@@ -750,15 +801,10 @@ extern "C" int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const 
                                    double *states_out_or_null, double *velocities_or_null, float *steers_or_null,
                                    float *scan_poses_or_null, double *states_trace_or_null)
 {
-    if (!c || !h || !p || (R > 0 && (!states_in || !speeds || !edge || !first_crashed)))
-        return fail(RL_ERR_INVALID, "rl_car_drive_policy: null pointer");
-    int rc;
-    if ((rc = drive_args("rl_car_drive_policy", c, h, nullptr, p, R, n_ticks, num_rays)) ||
-        (rc = policy_args(p, R, num_rays)) || (rc = check_fan_args(h, R, fov, num_rays)) || R == 0)
-        return rc;
-    return drive_loop(c, h, nullptr, p, steer_clip, states_in, speeds, steer0_or_null, R, 0, n_ticks, dt,
-                      scan_dist_to_base, fov, num_rays, edge, crash_thresh, first_crashed, states_out_or_null,
-                      velocities_or_null, steers_or_null, scan_poses_or_null, states_trace_or_null);
+    const DriveCall a{states_in, speeds, steer0_or_null, n_ticks, dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh,
+                      first_crashed, states_out_or_null, velocities_or_null, steers_or_null, scan_poses_or_null,
+                      states_trace_or_null};
+    return drive_loop("rl_car_drive_policy", c, h, nullptr, p, steer_clip, R, false, 0, a);
 }
 
 // ---------------------------------------------------------------- the driving environment (env_kernels.h)
@@ -772,10 +818,13 @@ struct rl_env {
     rl_env_params prm{};
     EnvParams ep{};
     int device = 0, n_starts = 0;
-    DevBuf state, starts, edge, tick, episode, start_index, done, phase, moved, pose, ranges;
+    DevPtr<double> state, starts, edge, moved;
+    DevPtr<int> tick, episode, start_index, done, phase;
+    DevPtr<float> pose, ranges;
     // the host forms' staging: actions and start indices in, observation, reward, done and aux out
-    DevBuf h_actions, h_sidx, h_obs, h_reward, h_done, h_aux;
-    bool ready = false;            // reset done and no launch failed since
+    DevPtr<float> h_actions, h_obs, h_reward, h_aux;
+    DevPtr<int> h_sidx, h_done;
+    bool ready = false;            // reset done and no launch failed since (read and written under mu only)
     bool foreign = false;          // the last launches went to a caller's stream: a host form waits for the device first
     uint64_t k = 0;                // calls since the last reset (the reset is slot 0)
     uint64_t base = 0;             // h's ray offset at the last reset
@@ -784,9 +833,8 @@ struct rl_env {
 
 static EnvBufs env_bufs(rl_env *e)
 {
-    return EnvBufs{(double *)e->state.p, (const double *)e->starts.p, (const double *)e->edge.p, (int *)e->tick.p,
-                   (int *)e->episode.p, (int *)e->start_index.p, (int *)e->done.p, (int *)e->phase.p,
-                   (double *)e->moved.p, (float *)e->pose.p, (const float *)e->ranges.p};
+    return EnvBufs{e->state, e->starts, e->edge, e->tick, e->episode, e->start_index, e->done, e->phase, e->moved, e->pose,
+                   e->ranges};
 }
 
 extern "C" void rl_env_destroy(rl_env *e)
@@ -803,16 +851,11 @@ extern "C" int rl_env_create(rl_car *c, rl_method *h, const rl_env_params *param
 {
     if (!c || !h || !params || !edge || !starts_m11 || !out) return fail(RL_ERR_INVALID, "rl_env_create: null pointer");
     const rl_env_params q = *params;
-    if (!c->reps.empty() || !h->reps.empty())
-        return fail(RL_ERR_INVALID, "%s is single-device only: pass ordinary (not multi-device) handles", "rl_env_create");
-    if (c->device != h->map->device)
-        return fail(RL_ERR_INVALID, "car (device %d) and range method (device %d) must share one device", c->device,
-                    h->map->device);
+    int rc = loop_args("rl_env_create", c, h, nullptr, nullptr, q.n_envs, q.num_rays);
+    if (rc) return rc;
     if (q.n_envs < 1) return fail(RL_ERR_INVALID, "rl_env_create: n_envs must be >= 1 (got %d)", q.n_envs);
     if (q.substeps < 1 || q.substeps > 512)
         return fail(RL_ERR_INVALID, "rl_env_create: substeps must lie in [1, 512] (got %d)", q.substeps);
-    if (q.num_rays < 10 || q.num_rays > 64 * FG_ROWS)
-        return fail(RL_ERR_INVALID, "num_rays must lie in [10, %d] (got %d)", 64 * FG_ROWS, q.num_rays);
     if (q.obs_count < 1 || q.obs_stride < 1 || q.obs_start < 0 ||
         (long)q.obs_start + ((long)q.obs_count - 1) * q.obs_stride >= q.num_rays)
         return fail(RL_ERR_INVALID, "rl_env_create: the observation window (start %d, count %d, stride %d) must lie in "
@@ -827,9 +870,7 @@ extern "C" int rl_env_create(rl_car *c, rl_method *h, const rl_env_params *param
     for (size_t i = 0; i < (size_t)n_starts * 11; ++i)
         if (!std::isfinite(starts_m11[i]))
             return fail(RL_ERR_INVALID, "rl_env_create: start state %zu holds a non-finite value", i / 11);
-    if ((long)q.n_envs * q.num_rays >= (1L << 31)) return fail(RL_ERR_INVALID, "n_envs * num_rays must stay below 2^31");
-    int rc = check_fan_args(h, q.n_envs, q.fov, q.num_rays);
-    if (rc) return rc;
+    if ((rc = check_fan_args(h, q.n_envs, q.fov, q.num_rays))) return rc;
     std::unique_ptr<rl_env, decltype(&rl_env_destroy)> e(new (std::nothrow) rl_env(), rl_env_destroy);
     if (!e) return fail(RL_ERR_NOMEM, "out of host memory");
     e->c = c;
@@ -858,44 +899,32 @@ extern "C" int rl_env_create(rl_car *c, rl_method *h, const rl_env_params *param
     if (hipSetDevice(e->device) != hipSuccess) return fail(RL_ERR_HIP, "rl_env_create: hipSetDevice failed");
     const size_t N = q.n_envs, B = q.num_rays, M = n_starts;
     struct { DevBuf *b; size_t bytes; } need[] = {
-        {&e->state, N * 88}, {&e->starts, M * 88}, {&e->edge, B * 8}, {&e->tick, N * 4}, {&e->episode, N * 4},
-        {&e->start_index, N * 4}, {&e->done, N * 4}, {&e->phase, N * 4}, {&e->moved, N * 8}, {&e->pose, N * 12},
-        {&e->ranges, N * B * 4}, {&e->h_actions, N * 8}, {&e->h_sidx, N * 4}, {&e->h_obs, N * q.obs_count * 4},
-        {&e->h_reward, N * 4}, {&e->h_done, N * 4}, {&e->h_aux, N * 16}};
+        {&e->state.buf, N * 88}, {&e->starts.buf, M * 88}, {&e->edge.buf, B * 8}, {&e->tick.buf, N * 4},
+        {&e->episode.buf, N * 4}, {&e->start_index.buf, N * 4}, {&e->done.buf, N * 4}, {&e->phase.buf, N * 4},
+        {&e->moved.buf, N * 8}, {&e->pose.buf, N * 12}, {&e->ranges.buf, N * B * 4}, {&e->h_actions.buf, N * 8},
+        {&e->h_sidx.buf, N * 4}, {&e->h_obs.buf, N * q.obs_count * 4}, {&e->h_reward.buf, N * 4}, {&e->h_done.buf, N * 4},
+        {&e->h_aux.buf, N * 16}};
     for (auto &n : need)
         if ((rc = n.b->ensure(n.bytes))) return rc;
-    if (hipMemcpy(e->starts.p, starts_m11, M * 88, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(e->edge.p, edge, B * 8, hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(e->starts, starts_m11, M * 88, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(e->edge, edge, B * 8, hipMemcpyHostToDevice) != hipSuccess)
         return fail(RL_ERR_HIP, "rl_env_create: upload failed");
     *out = e.release();
     return RL_OK;
 }
 
-// the handles every launching call locks, in one order; h's options and ray offset come back before the locks go
-struct EnvLock {
-    std::unique_lock<std::mutex> le, lc, lh;
-    std::shared_lock<std::shared_mutex> ml;
-    HandleOverride ov;
-    explicit EnvLock(rl_env *e) : le(e->mu), lc(e->c->mu), lh(e->h->mu), ml(e->h->map->tables_mu), ov(e->h) {}
-};
-
-// one call's launches on st: phase A (reset: the spawn), the scan at slot k, phase B.  The caller holds EnvLock.
-static int env_launch(rl_env *e, bool reset, uint64_t k, const float *d_actions, const int *d_start_index, float *d_obs,
-                      float *d_reward, int *d_done, float *d_aux, hipStream_t st)
+// one call's launches on st: phase A (reset: the spawn), the scan at slot k, phase B.  lp: the call's Loop, owner e.
+static int env_launch(rl_env *e, const Loop &lp, bool reset, uint64_t k, const float *d_actions, const int *d_start_index,
+                      float *d_obs, float *d_reward, int *d_done, float *d_aux, hipStream_t st)
 {
     const int N = e->prm.n_envs, B = e->prm.num_rays;
     const EnvBufs b = env_bufs(e);
     hipLaunchKernelGGL(env_step_kernel, dim3((N + 63) / 64), dim3(64), 0, st, e->ep, b, d_actions, d_start_index,
                        reset ? 1 : 0);
     if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "env_step_kernel launch failed");
-    e->h->ray_offset = e->base + k * (uint64_t)N * (uint64_t)B;
-    const int rc = launch_fan(e->h, (const float *)e->pose.p, N, e->prm.fov, B, (float *)e->ranges.p, nullptr, nullptr,
-                              nullptr, st);
-    if (rc) return rc;
-    env_observe_table[(B + 63) / 64 - 1]<<<dim3((N + DRIVE_CARS - 1) / DRIVE_CARS), dim3(64 * DRIVE_CARS), 0, st>>>(
-        e->ep, b, d_obs, d_reward, d_done, d_aux);
-    if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "env_observe_kernel launch failed");
-    return RL_OK;
+    const LoopScan scan{e->pose, N, e->prm.fov, B, e->ranges, nullptr, 0, nullptr, nullptr};
+    return lp.scan_then(scan, e->base + k * (uint64_t)N * (uint64_t)B, env_observe_table, DRIVE_CARS, "env_observe_kernel",
+                        st, e->ep, b, d_obs, d_reward, d_done, d_aux);
 }
 
 // a host form after launches on a caller's stream: c's stream is not ordered behind that one
@@ -908,23 +937,23 @@ static int env_settle(rl_env *e)
     return RL_OK;
 }
 
-static int env_reset_locked(rl_env *e, const EnvLock &lk, uint64_t seed, const int *d_start_index, float *d_obs,
+static int env_reset_locked(rl_env *e, const Loop &lp, uint64_t seed, const int *d_start_index, float *d_obs,
                             float *d_aux, int *d_done, hipStream_t st)
 {
     e->ready = false;
-    e->ep.key = (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x85EBCA6Bu);     // np_statement.noise_key
-    e->base = lk.ov.ray_offset;
-    const int rc = env_launch(e, true, 0, nullptr, d_start_index, d_obs, nullptr, d_done, d_aux, st);
+    e->ep.key = noise_key(seed);
+    e->base = lp.ov.ray_offset;
+    const int rc = env_launch(e, lp, true, 0, nullptr, d_start_index, d_obs, nullptr, d_done, d_aux, st);
     if (rc) return rc;
     e->k = 0;
     e->ready = true;
     return RL_OK;
 }
 
-static int env_step_locked(rl_env *e, const float *d_actions, float *d_obs, float *d_reward, int *d_done, float *d_aux,
-                           hipStream_t st)
+static int env_step_locked(rl_env *e, const Loop &lp, const float *d_actions, float *d_obs, float *d_reward, int *d_done,
+                           float *d_aux, hipStream_t st)
 {
-    const int rc = env_launch(e, false, e->k + 1, d_actions, nullptr, d_obs, d_reward, d_done, d_aux, st);
+    const int rc = env_launch(e, lp, false, e->k + 1, d_actions, nullptr, d_obs, d_reward, d_done, d_aux, st);
     if (rc) {
         e->ready = false;                   // part of the step may have run: the env needs a reset
         return rc;
@@ -939,35 +968,35 @@ extern "C" int rl_env_reset_device(rl_env *e, uint64_t seed, const int *d_start_
     if (!e || !d_obs || !d_done) return fail(RL_ERR_INVALID, "rl_env_reset_device: null pointer");
     int rc = check_fan_args(e->h, e->prm.n_envs, e->prm.fov, e->prm.num_rays);
     if (rc) return rc;
-    EnvLock lk(e);
+    const Loop lp(&e->mu, e->c, e->h, nullptr, nullptr);
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)hip_stream;
     if (st != (hipStream_t)e->c->stream) e->foreign = true;
-    return env_reset_locked(e, lk, seed, d_start_index_or_null, d_obs, d_aux_or_null, d_done, st);
+    return env_reset_locked(e, lp, seed, d_start_index_or_null, d_obs, d_aux_or_null, d_done, st);
 }
 
 extern "C" int rl_env_step_device(rl_env *e, const float *d_actions_n2, float *d_obs, float *d_reward, int *d_done,
                                   float *d_aux_or_null, void *hip_stream)
 {
     if (!e || !d_actions_n2 || !d_obs || !d_reward || !d_done) return fail(RL_ERR_INVALID, "rl_env_step_device: null pointer");
+    const Loop lp(&e->mu, e->c, e->h, nullptr, nullptr);
     if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_step_device: reset the environment first (rl_env_reset)");
     int rc = check_fan_args(e->h, e->prm.n_envs, e->prm.fov, e->prm.num_rays);
     if (rc) return rc;
-    EnvLock lk(e);
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)hip_stream;
     if (st != (hipStream_t)e->c->stream) e->foreign = true;
-    return env_step_locked(e, d_actions_n2, d_obs, d_reward, d_done, d_aux_or_null, st);
+    return env_step_locked(e, lp, d_actions_n2, d_obs, d_reward, d_done, d_aux_or_null, st);
 }
 
 // the host forms' way back: the staged results to the caller, then the wait
 static int env_download(rl_env *e, float *obs, float *reward, int *done, float *aux, hipStream_t st)
 {
     const size_t N = e->prm.n_envs;
-    HIPCHK(hipMemcpyAsync(obs, e->h_obs.p, N * e->prm.obs_count * 4, hipMemcpyDeviceToHost, st));
-    if (reward) HIPCHK(hipMemcpyAsync(reward, e->h_reward.p, N * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(done, e->h_done.p, N * 4, hipMemcpyDeviceToHost, st));
-    if (aux) HIPCHK(hipMemcpyAsync(aux, e->h_aux.p, N * 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(obs, e->h_obs, N * e->prm.obs_count * 4, hipMemcpyDeviceToHost, st));
+    if (reward) HIPCHK(hipMemcpyAsync(reward, e->h_reward, N * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(done, e->h_done, N * 4, hipMemcpyDeviceToHost, st));
+    if (aux) HIPCHK(hipMemcpyAsync(aux, e->h_aux, N * 16, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return RL_OK;
 }
@@ -984,14 +1013,13 @@ extern "C" int rl_env_reset(rl_env *e, uint64_t seed, const int *start_index_or_
                             start_index_or_null[i], e->n_starts);
     int rc = check_fan_args(e->h, N, e->prm.fov, e->prm.num_rays);
     if (rc) return rc;
-    EnvLock lk(e);
+    const Loop lp(&e->mu, e->c, e->h, nullptr, nullptr);
     HIPCHK(hipSetDevice(e->device));
     if ((rc = env_settle(e))) return rc;
     hipStream_t st = e->c->stream;
-    if (start_index_or_null)
-        HIPCHK(hipMemcpyAsync(e->h_sidx.p, start_index_or_null, (size_t)N * 4, hipMemcpyHostToDevice, st));
-    rc = env_reset_locked(e, lk, seed, start_index_or_null ? (const int *)e->h_sidx.p : nullptr, (float *)e->h_obs.p,
-                          aux_or_null ? (float *)e->h_aux.p : nullptr, (int *)e->h_done.p, st);
+    if (start_index_or_null) HIPCHK(hipMemcpyAsync(e->h_sidx, start_index_or_null, (size_t)N * 4, hipMemcpyHostToDevice, st));
+    rc = env_reset_locked(e, lp, seed, start_index_or_null ? (int *)e->h_sidx : nullptr, e->h_obs,
+                          aux_or_null ? (float *)e->h_aux : nullptr, e->h_done, st);
     if (rc) {
         (void)hipStreamSynchronize(st);           // nothing of this call is left in flight
         return rc;
@@ -1003,17 +1031,17 @@ extern "C" int rl_env_reset(rl_env *e, uint64_t seed, const int *start_index_or_
 extern "C" int rl_env_step(rl_env *e, const float *actions_n2, float *obs, float *reward, int *done, float *aux_or_null)
 {
     if (!e || !actions_n2 || !obs || !reward || !done) return fail(RL_ERR_INVALID, "rl_env_step: null pointer");
+    const Loop lp(&e->mu, e->c, e->h, nullptr, nullptr);
     if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_step: reset the environment first (rl_env_reset)");
     const int N = e->prm.n_envs;
     int rc = check_fan_args(e->h, N, e->prm.fov, e->prm.num_rays);
     if (rc) return rc;
-    EnvLock lk(e);
     HIPCHK(hipSetDevice(e->device));
     if ((rc = env_settle(e))) return rc;
     hipStream_t st = e->c->stream;
-    HIPCHK(hipMemcpyAsync(e->h_actions.p, actions_n2, (size_t)N * 8, hipMemcpyHostToDevice, st));
-    rc = env_step_locked(e, (const float *)e->h_actions.p, (float *)e->h_obs.p, (float *)e->h_reward.p,
-                         (int *)e->h_done.p, aux_or_null ? (float *)e->h_aux.p : nullptr, st);
+    HIPCHK(hipMemcpyAsync(e->h_actions, actions_n2, (size_t)N * 8, hipMemcpyHostToDevice, st));
+    rc = env_step_locked(e, lp, e->h_actions, e->h_obs, e->h_reward, e->h_done, aux_or_null ? (float *)e->h_aux : nullptr,
+                         st);
     if (rc) {
         (void)hipStreamSynchronize(st);
         return rc;
@@ -1025,18 +1053,18 @@ extern "C" int rl_env_step(rl_env *e, const float *actions_n2, float *obs, float
 extern "C" int rl_env_read(rl_env *e, double *states_n11, int *ticks, int *episodes, int *start_index, int *done)
 {
     if (!e) return fail(RL_ERR_INVALID, "rl_env_read: null pointer");
-    if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_read: reset the environment first (rl_env_reset)");
     std::scoped_lock lk(e->mu, e->c->mu);
+    if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_read: reset the environment first (rl_env_reset)");
     HIPCHK(hipSetDevice(e->device));
     int rc = env_settle(e);
     if (rc) return rc;
     hipStream_t st = e->c->stream;
     const size_t N = e->prm.n_envs;
-    if (states_n11) HIPCHK(hipMemcpyAsync(states_n11, e->state.p, N * 88, hipMemcpyDeviceToHost, st));
-    if (ticks) HIPCHK(hipMemcpyAsync(ticks, e->tick.p, N * 4, hipMemcpyDeviceToHost, st));
-    if (episodes) HIPCHK(hipMemcpyAsync(episodes, e->episode.p, N * 4, hipMemcpyDeviceToHost, st));
-    if (start_index) HIPCHK(hipMemcpyAsync(start_index, e->start_index.p, N * 4, hipMemcpyDeviceToHost, st));
-    if (done) HIPCHK(hipMemcpyAsync(done, e->done.p, N * 4, hipMemcpyDeviceToHost, st));
+    if (states_n11) HIPCHK(hipMemcpyAsync(states_n11, e->state, N * 88, hipMemcpyDeviceToHost, st));
+    if (ticks) HIPCHK(hipMemcpyAsync(ticks, e->tick, N * 4, hipMemcpyDeviceToHost, st));
+    if (episodes) HIPCHK(hipMemcpyAsync(episodes, e->episode, N * 4, hipMemcpyDeviceToHost, st));
+    if (start_index) HIPCHK(hipMemcpyAsync(start_index, e->start_index, N * 4, hipMemcpyDeviceToHost, st));
+    if (done) HIPCHK(hipMemcpyAsync(done, e->done, N * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return RL_OK;
 }
@@ -1267,12 +1295,16 @@ struct rl_mcts {
     MctsParams mp{};
     int device = 0;
     // node arrays and per-tree scratch (MctsBufs)
-    DevBuf parent, first_child, next_sibling, last_child, n_children, visits, child_visits, terminal, crash;
-    DevBuf reward, action, state, pose, answer, n_nodes, child, exp_term, keys, logtab;
-    DevBuf cstate, cpose, actions, ranges, edge, mlp, rposes, vel, first, rranges, roots, best_a, best_v, best_n;
+    DevPtr<int> parent, first_child, next_sibling, last_child, n_children, visits, child_visits, terminal, crash;
+    DevPtr<double> reward, action, state, logtab, cstate, actions, edge, vel, roots, best_a;
+    DevPtr<float> pose, answer, cpose, ranges, mlp, rposes, rranges;
+    DevPtr<int> n_nodes, child, exp_term, first, best_v, best_n;
+    DevPtr<uint32_t> keys;
     // rl_mcts_drive: the root crash flags, the K x D keys and the per-decision outputs
-    DevBuf root_crash, dr_keys, dr_first, dr_actions, dr_visits, dr_trace;
-    bool ready = false;            // reset done and no launch failed since
+    DevPtr<int> root_crash, dr_first, dr_visits;
+    DevPtr<uint32_t> dr_keys;
+    DevPtr<double> dr_actions, dr_trace;
+    bool ready = false;            // reset done and no launch failed since (read and written under mu only)
     long iters = 0;                // iterations since reset
     uint64_t base = 0;             // h's ray offset at reset
     std::mutex mu;
@@ -1286,37 +1318,12 @@ static std::vector<double> mcts_log_table(int n_max)
     return t;
 }
 
-static MctsBufs mcts_bufs(rl_mcts *m)
+static MctsBufs mcts_bufs(rl_mcts *m)      // (root_crash: rl_mcts_drive sets it)
 {
-    MctsBufs b{};
-    b.parent = (int *)m->parent.p;
-    b.first_child = (int *)m->first_child.p;
-    b.next_sibling = (int *)m->next_sibling.p;
-    b.last_child = (int *)m->last_child.p;
-    b.n_children = (int *)m->n_children.p;
-    b.visits = (int *)m->visits.p;
-    b.child_visits = (int *)m->child_visits.p;
-    b.terminal = (int *)m->terminal.p;
-    b.crash = (int *)m->crash.p;
-    b.reward = (double *)m->reward.p;
-    b.action = (double *)m->action.p;
-    b.state = (double *)m->state.p;
-    b.pose = (float *)m->pose.p;
-    b.answer = (float *)m->answer.p;
-    b.n_nodes = (int *)m->n_nodes.p;
-    b.child = (int *)m->child.p;
-    b.exp_term = (int *)m->exp_term.p;
-    b.keys = (const uint32_t *)m->keys.p;
-    b.logtab = (const double *)m->logtab.p;
-    b.cstate = (double *)m->cstate.p;
-    b.cpose = (float *)m->cpose.p;
-    b.actions = (double *)m->actions.p;
-    b.ranges = (const float *)m->ranges.p;
-    b.edge = (const double *)m->edge.p;
-    b.mlp = (const float *)m->mlp.p;
-    b.vel = (const double *)m->vel.p;
-    b.first = (const int *)m->first.p;
-    return b;
+    return MctsBufs{m->parent, m->first_child, m->next_sibling, m->last_child, m->n_children, m->visits, m->child_visits,
+                    m->terminal, m->crash, m->reward, m->action, m->state, m->pose, m->answer, m->n_nodes, m->child,
+                    m->exp_term, m->keys, m->logtab, m->cstate, m->cpose, m->actions, m->ranges, m->edge, m->mlp, m->vel,
+                    m->first, nullptr};
 }
 
 extern "C" void rl_mcts_destroy(rl_mcts *m)
@@ -1332,38 +1339,31 @@ extern "C" int rl_mcts_create(rl_car *c, rl_method *h, rl_followgap *g, rl_polic
 {
     if (!c || !h || !params || !edge || !out) return fail(RL_ERR_INVALID, "rl_mcts_create: null pointer");
     const rl_mcts_params q = *params;
-    if (!c->reps.empty() || !h->reps.empty())
-        return fail(RL_ERR_INVALID, "rl_mcts_create is single-device only: pass ordinary (not multi-device) handles");
     if (q.source == RL_MCTS_FG && !g) return fail(RL_ERR_INVALID, "rl_mcts_create: the FG source needs a FollowGap handle");
     if (q.source == RL_MCTS_NN && !p) return fail(RL_ERR_INVALID, "rl_mcts_create: the NN source needs a policy handle");
     if (q.source != RL_MCTS_FG && q.source != RL_MCTS_NN && q.source != RL_MCTS_RANDOM)
         return fail(RL_ERR_INVALID, "rl_mcts_create: unknown source %d", q.source);
-    if (c->device != h->map->device || (q.source == RL_MCTS_FG && g->device != c->device) ||
-        (q.source == RL_MCTS_NN && p->device != c->device))
-        return fail(RL_ERR_INVALID, "rl_mcts_create: car, range method and the source's handle must share one device");
+    g = q.source == RL_MCTS_FG ? g : nullptr;
+    p = q.source == RL_MCTS_NN ? p : nullptr;
     if (q.n_trees < 1 || q.max_nodes < 1 || q.action_every < 1 || q.rollout_steps < 1 || q.rollout_steps > MCTS_MAX_STEPS)
         return fail(RL_ERR_INVALID, "rl_mcts_create: n_trees >= 1, max_nodes >= 1, action_every >= 1 and 1 <= "
                     "rollout_steps <= %d required (got %d, %d, %d, %d)", MCTS_MAX_STEPS, q.n_trees, q.max_nodes,
                     q.action_every, q.rollout_steps);
-    if (q.num_rays < 10 || q.num_rays > 64 * FG_ROWS)
-        return fail(RL_ERR_INVALID, "num_rays must lie in [10, %d] (got %d)", 64 * FG_ROWS, q.num_rays);
-    if (q.source == RL_MCTS_NN) {
-        const int rc = policy_args(p, q.n_trees, q.num_rays);
-        if (rc) return rc;
-    }
-    if ((long)q.n_trees * q.rollout_steps * q.num_rays >= (1L << 31) || (long)q.n_trees * q.max_nodes >= (1L << 31) / 11)
-        return fail(RL_ERR_INVALID, "rl_mcts_create: n_trees * rollout_steps * num_rays and the node arrays must stay below 2^31");
+    int rc = loop_args("rl_mcts_create", c, h, g, p, (long)q.n_trees * q.rollout_steps, q.num_rays);      // (the roll-out scans)
+    if (rc || (p && (rc = policy_args(p, q.n_trees, q.num_rays)))) return rc;
+    if ((long)q.n_trees * q.max_nodes >= (1L << 31) / 11)
+        return fail(RL_ERR_INVALID, "rl_mcts_create: the node arrays (n_trees * max_nodes * 11) must stay below 2^31");
     std::unique_ptr<rl_mcts, decltype(&rl_mcts_destroy)> m(new (std::nothrow) rl_mcts(), rl_mcts_destroy);
     if (!m) return fail(RL_ERR_NOMEM, "out of host memory");
     m->c = c;
     m->h = h;
-    m->g = q.source == RL_MCTS_FG ? g : nullptr;
-    m->p = q.source == RL_MCTS_NN ? p : nullptr;
+    m->g = g;
+    m->p = p;
     m->prm = q;
     m->device = c->device;
     MctsParams &mp = m->mp;
     mp.P = c->P;
-    if (m->g) mp.fg = g->P;
+    if (g) mp.fg = g->P;
     mp.fg.size = q.num_rays;
     mp.K = q.n_trees;
     mp.N = q.max_nodes;
@@ -1384,54 +1384,46 @@ extern "C" int rl_mcts_create(rl_car *c, rl_method *h, rl_followgap *g, rl_polic
     if (hipSetDevice(m->device) != hipSuccess) return fail(RL_ERR_HIP, "rl_mcts_create: hipSetDevice failed");
     const size_t L = q.rollout_steps;
     struct { DevBuf *b; size_t bytes; } need[] = {
-        {&m->parent, N * 4}, {&m->first_child, N * 4}, {&m->next_sibling, N * 4}, {&m->last_child, N * 4},
-        {&m->n_children, N * 4}, {&m->visits, N * 4}, {&m->child_visits, N * 4}, {&m->terminal, N * 4}, {&m->crash, N * 4},
-        {&m->reward, N * 8}, {&m->action, N * 8}, {&m->state, N * 88}, {&m->pose, N * 12}, {&m->answer, N * 4},
-        {&m->n_nodes, K * 4}, {&m->child, K * 4}, {&m->exp_term, K * 4}, {&m->keys, K * 4}, {&m->first, K * 4},
-        {&m->mlp, K * 4}, {&m->best_v, K * 4}, {&m->best_n, K * 4}, {&m->best_a, K * 8},
-        {&m->logtab, ((size_t)q.max_nodes + 1) * 8}, {&m->cstate, K * 88}, {&m->roots, K * 96}, {&m->cpose, K * 12},
-        {&m->actions, K * mp.n_act * 16}, {&m->ranges, K * B * 4}, {&m->edge, B * 8}, {&m->rposes, K * L * 12},
-        {&m->vel, K * L * 8}};
+        {&m->parent.buf, N * 4}, {&m->first_child.buf, N * 4}, {&m->next_sibling.buf, N * 4}, {&m->last_child.buf, N * 4},
+        {&m->n_children.buf, N * 4}, {&m->visits.buf, N * 4}, {&m->child_visits.buf, N * 4}, {&m->terminal.buf, N * 4}, {&m->crash.buf, N * 4},
+        {&m->reward.buf, N * 8}, {&m->action.buf, N * 8}, {&m->state.buf, N * 88}, {&m->pose.buf, N * 12}, {&m->answer.buf, N * 4},
+        {&m->n_nodes.buf, K * 4}, {&m->child.buf, K * 4}, {&m->exp_term.buf, K * 4}, {&m->keys.buf, K * 4}, {&m->first.buf, K * 4},
+        {&m->mlp.buf, K * 4}, {&m->best_v.buf, K * 4}, {&m->best_n.buf, K * 4}, {&m->best_a.buf, K * 8},
+        {&m->logtab.buf, ((size_t)q.max_nodes + 1) * 8}, {&m->cstate.buf, K * 88}, {&m->roots.buf, K * 96}, {&m->cpose.buf, K * 12},
+        {&m->actions.buf, K * mp.n_act * 16}, {&m->ranges.buf, K * B * 4}, {&m->edge.buf, B * 8}, {&m->rposes.buf, K * L * 12},
+        {&m->vel.buf, K * L * 8}};
     for (auto &n : need)
-        if (int rc = n.b->ensure(n.bytes)) return rc;
+        if ((rc = n.b->ensure(n.bytes))) return rc;
     const std::vector<double> lt = mcts_log_table(q.max_nodes);
-    if (hipMemcpy(m->logtab.p, lt.data(), lt.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(m->edge.p, edge, B * 8, hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(m->logtab, lt.data(), lt.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(m->edge, edge, B * 8, hipMemcpyHostToDevice) != hipSuccess)
         return fail(RL_ERR_HIP, "rl_mcts_create: upload failed");
     *out = m.release();
     return RL_OK;
 }
 
 // the act scans of the K nodes in m->cpose at ray offset `off`, the network for NN, then mcts_act_kernel on b
-static int mcts_act(rl_mcts *m, const MctsBufs &b, uint64_t off, int root, hipStream_t st)
+static int mcts_act(rl_mcts *m, const Loop &lp, const MctsBufs &b, uint64_t off, int root, hipStream_t st)
 {
-    rl_method *h = m->h;
-    const int K = m->prm.n_trees, B = m->prm.num_rays;
-    h->ray_offset = off;
-    int rc = launch_fan(h, (const float *)m->cpose.p, K, m->prm.fov, B, (float *)m->ranges.p, nullptr, nullptr,
-                        nullptr, st);
-    if (rc) return rc;
-    if (m->prm.source == RL_MCTS_NN &&
-        (rc = policy_launch(m->p, (const float *)m->ranges.p, K, B, (float *)m->mlp.p, st)))
-        return rc;
-    mcts_act_table[(B + 63) / 64 - 1]<<<dim3((K + MCTS_TREES - 1) / MCTS_TREES), dim3(64 * MCTS_TREES), 0, st>>>(
-        m->mp, b, root);
-    if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "mcts_act_kernel launch failed");
-    return RL_OK;
+    const LoopScan scan{m->cpose, m->prm.n_trees, m->prm.fov, m->prm.num_rays, m->ranges, m->mlp, 0, nullptr, nullptr};
+    return lp.scan_then(scan, off, mcts_act_table, MCTS_TREES, "mcts_act_kernel", st, m->mp, b, root);
 }
 
-// the handles every launching call locks, in one order; h's options that the planner changes come back afterwards,
-// before the locks are released (the act kernel reads the ranges right after the scan)
-struct MctsLock {
-    std::unique_lock<std::mutex> lm, lc, lh, lx;
-    std::shared_lock<std::shared_mutex> ml;
-    HandleOverride ov;
-    explicit MctsLock(rl_mcts *m) : lm(m->mu), lc(m->c->mu), lh(m->h->mu), ml(m->h->map->tables_mu), ov(m->h)
-    {
-        if (m->g) lx = std::unique_lock<std::mutex>(m->g->mu);
-        if (m->p) lx = std::unique_lock<std::mutex>(m->p->mu);
-    }
-};
+// how rl_mcts_reset and rl_mcts_drive begin: the keys go up to d_keys, the K root states and root (recent) actions into
+// m->roots, then mcts_start_kernel makes the root nodes
+static int mcts_start(rl_mcts *m, const MctsBufs &b, uint32_t *d_keys, const std::vector<uint32_t> &keys, const double *states,
+                      const double *actions, hipStream_t st)
+{
+    const size_t K = m->prm.n_trees;
+    double *d_states = m->roots, *d_actions = d_states + K * 11;
+    HIPCHK(hipMemcpyAsync(d_keys, keys.data(), keys.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_states, states, K * 88, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_actions, actions, K * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(mcts_start_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, (const double *)d_states,
+                       (const double *)d_actions);
+    if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "mcts_start_kernel launch failed");
+    return RL_OK;
+}
 
 extern "C" int rl_mcts_reset(rl_mcts *m, const double *root_states, const double *root_actions, const uint64_t *seeds)
 {
@@ -1439,22 +1431,15 @@ extern "C" int rl_mcts_reset(rl_mcts *m, const double *root_states, const double
     const int K = m->prm.n_trees;
     int rc = check_fan_args(m->h, K, m->prm.fov, m->prm.num_rays);
     if (rc) return rc;
-    MctsLock lk(m);
+    const Loop lp(&m->mu, m->c, m->h, m->g, m->p);
     HIPCHK(hipSetDevice(m->device));
     hipStream_t st = m->c->stream;
     m->ready = false;
     std::vector<uint32_t> keys(K);
-    for (int k = 0; k < K; ++k)
-        keys[k] = (uint32_t)seeds[k] ^ ((uint32_t)(seeds[k] >> 32) * 0x85EBCA6Bu);     // np_statement.noise_key
-    double *d_states = (double *)m->roots.p, *d_actions = d_states + (size_t)K * 11;
-    HIPCHK(hipMemcpyAsync(m->keys.p, keys.data(), (size_t)K * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_states, root_states, (size_t)K * 88, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_actions, root_actions, (size_t)K * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(mcts_start_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, mcts_bufs(m),
-                       (const double *)d_states, (const double *)d_actions);
-    if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_start_kernel launch failed");
-    const uint64_t base = lk.ov.ray_offset;
-    if (!rc) rc = mcts_act(m, mcts_bufs(m), base, 1, st);
+    for (int k = 0; k < K; ++k) keys[k] = noise_key(seeds[k]);
+    const uint64_t base = lp.ov.ray_offset;
+    rc = mcts_start(m, mcts_bufs(m), m->keys, keys, root_states, root_actions, st);
+    if (!rc) rc = mcts_act(m, lp, mcts_bufs(m), base, 1, st);
     const hipError_t e = hipStreamSynchronize(st);            // (the host's root arrays are the caller's)
     if (!rc && e != hipSuccess) rc = fail(RL_ERR_HIP, "rl_mcts_reset: %s", hipGetErrorString(e));
     if (rc) return rc;
@@ -1465,8 +1450,8 @@ extern "C" int rl_mcts_reset(rl_mcts *m, const double *root_states, const double
 }
 
 // iterations it0 ... it0 + n - 1 of every tree, enqueued on st: select, the act, the roll-outs and their crash
-// test, the backup.  base: the ray offset of the trees' reset.  The caller holds MctsLock and has sized m->rranges.
-static int mcts_iterations(rl_mcts *m, const MctsBufs &b, uint64_t base, long it0, int n, hipStream_t st)
+// test, the backup.  base: the ray offset of the trees' reset.  lp: the call's Loop; the caller has sized m->rranges.
+static int mcts_iterations(rl_mcts *m, const Loop &lp, const MctsBufs &b, uint64_t base, long it0, int n, hipStream_t st)
 {
     const int K = m->prm.n_trees, L = m->prm.rollout_steps, B = m->prm.num_rays;
     const uint64_t KB = (uint64_t)K * B, per_it = (uint64_t)K * (1 + L) * B;
@@ -1476,17 +1461,17 @@ static int mcts_iterations(rl_mcts *m, const MctsBufs &b, uint64_t base, long it
         const uint64_t off = base + KB + (uint64_t)it * per_it;
         hipLaunchKernelGGL(mcts_select_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, (int)it);
         if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_select_kernel launch failed");
-        if (!rc) rc = mcts_act(m, b, off, 0, st);
+        if (!rc) rc = mcts_act(m, lp, b, off, 0, st);
         if (!rc) {
-            hipLaunchKernelGGL(rollout_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, (const double *)m->cstate.p,
-                               (const double *)m->actions.p, K, L, m->prm.action_every, m->prm.dt, (float *)m->rposes.p,
-                               (double *)nullptr, (double *)m->vel.p);
+            hipLaunchKernelGGL(rollout_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, (const double *)m->cstate,
+                               (const double *)m->actions, K, L, m->prm.action_every, m->prm.dt, (float *)m->rposes,
+                               (double *)nullptr, (double *)m->vel);
             if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "rollout_kernel launch failed");
         }
         if (!rc) {
             m->h->ray_offset = off + KB;
-            rc = crash_groups_device(m->h, (const float *)m->rposes.p, K, L, m->prm.fov, B, (const double *)m->edge.p,
-                                     m->prm.crash_thresh, (int *)m->first.p, (float *)m->rranges.p, st);
+            rc = crash_groups_device(m->h, m->rposes, K, L, m->prm.fov, B, m->edge, m->prm.crash_thresh, m->first,
+                                     m->rranges, st);
         }
         if (!rc) {
             hipLaunchKernelGGL(mcts_backup_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b);
@@ -1500,22 +1485,19 @@ extern "C" int rl_mcts_run(rl_mcts *m, int n_iterations)
 {
     if (!m) return fail(RL_ERR_INVALID, "rl_mcts_run: null pointer");
     if (n_iterations < 0) return fail(RL_ERR_INVALID, "rl_mcts_run: n_iterations must be >= 0 (got %d)", n_iterations);
-    std::unique_lock<std::mutex> pre(m->mu);
+    const Loop lp(&m->mu, m->c, m->h, m->g, m->p);
     if (!m->ready) return fail(RL_ERR_INVALID, "rl_mcts_run: reset the planner first (rl_mcts_reset)");
     if (1 + m->iters + (long)n_iterations > m->prm.max_nodes)
         return fail(RL_ERR_INVALID, "rl_mcts_run: %d more iterations exceed max_nodes = %d (%ld done since reset)",
                     n_iterations, m->prm.max_nodes, m->iters);
-    pre.unlock();
     const int K = m->prm.n_trees, L = m->prm.rollout_steps, B = m->prm.num_rays;
     int rc;
     if ((rc = check_fan_args(m->h, K, m->prm.fov, B)) || (rc = check_fan_args(m->h, K * L, m->prm.fov, B))) return rc;
     if (n_iterations == 0) return RL_OK;
-    MctsLock lk(m);
-    if (!m->ready) return fail(RL_ERR_INVALID, "rl_mcts_run: reset the planner first (rl_mcts_reset)");
     HIPCHK(hipSetDevice(m->device));
     if ((rc = m->rranges.ensure((size_t)K * L * B * 4))) return rc;
     hipStream_t st = m->c->stream;
-    rc = mcts_iterations(m, mcts_bufs(m), m->base, m->iters, n_iterations, st);
+    rc = mcts_iterations(m, lp, mcts_bufs(m), m->base, m->iters, n_iterations, st);
     const hipError_t e = hipStreamSynchronize(st);
     if (!rc && e != hipSuccess) rc = fail(RL_ERR_HIP, "rl_mcts_run: %s", hipGetErrorString(e));
     if (rc) {
@@ -1554,7 +1536,7 @@ extern "C" int rl_mcts_drive(rl_mcts *m, const double *states_in, const double *
         return RL_OK;
     }
     const size_t rows = (size_t)K * D;
-    MctsLock lk(m);
+    const Loop lp(&m->mu, m->c, m->h, m->g, m->p);
     HIPCHK(hipSetDevice(m->device));
     if ((rc = m->rranges.ensure((size_t)K * L * B * 4)) || (rc = m->root_crash.ensure((size_t)K * 4)) ||
         (rc = m->dr_keys.ensure(rows * 4)) || (rc = m->dr_first.ensure((size_t)K * 4)) ||
@@ -1565,28 +1547,20 @@ extern "C" int rl_mcts_drive(rl_mcts *m, const double *states_in, const double *
     m->ready = false;
     std::vector<uint32_t> keys(rows);                  // [D][K]: decision d's seed is seeds[k] + d mod 2^64
     for (int d = 0; d < D; ++d)
-        for (int k = 0; k < K; ++k) {
-            const uint64_t s = seeds[k] + (uint64_t)d;
-            keys[(size_t)d * K + k] = (uint32_t)s ^ ((uint32_t)(s >> 32) * 0x85EBCA6Bu);     // np_statement.noise_key
-        }
-    double *d_states = (double *)m->roots.p, *d_recent = d_states + (size_t)K * 11;
-    HIPCHK(hipMemcpyAsync(m->dr_keys.p, keys.data(), rows * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_states, states_in, (size_t)K * 88, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_recent, recent_in, (size_t)K * 8, hipMemcpyHostToDevice, st));
+        for (int k = 0; k < K; ++k) keys[(size_t)d * K + k] = noise_key(seeds[k] + (uint64_t)d);
+    double *d_states = m->roots, *d_recent = d_states + (size_t)K * 11;
     MctsBufs b = mcts_bufs(m);
-    b.root_crash = (int *)m->root_crash.p;
-    const MctsDrive dv{d_states, d_recent, (int *)m->dr_first.p, (double *)m->dr_actions.p, (int *)m->dr_visits.p,
-                       trace_states_or_null ? (double *)m->dr_trace.p : nullptr, D, steps_per_decision, steer_clip};
+    b.root_crash = m->root_crash;
+    const MctsDrive dv{d_states, d_recent, m->dr_first, m->dr_actions, m->dr_visits,
+                       trace_states_or_null ? (double *)m->dr_trace : nullptr, D, steps_per_decision, steer_clip};
     const uint64_t stride = (uint64_t)K * B * (1 + (uint64_t)I * (1 + L));
-    hipLaunchKernelGGL(mcts_start_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, (const double *)d_states,
-                       (const double *)d_recent);
-    if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_start_kernel launch failed");
-    uint64_t base = lk.ov.ray_offset;
+    rc = mcts_start(m, b, m->dr_keys, keys, states_in, recent_in, st);
+    uint64_t base = lp.ov.ray_offset;
     for (int d = 0; d < D && rc == RL_OK; ++d) {
-        base = lk.ov.ray_offset + (uint64_t)d * stride;
-        b.keys = (const uint32_t *)m->dr_keys.p + (size_t)d * K;
-        rc = mcts_act(m, b, base, 1, st);
-        if (!rc) rc = mcts_iterations(m, b, base, 0, I, st);
+        base = lp.ov.ray_offset + (uint64_t)d * stride;
+        b.keys = m->dr_keys + (size_t)d * K;
+        rc = mcts_act(m, lp, b, base, 1, st);
+        if (!rc) rc = mcts_iterations(m, lp, b, base, 0, I, st);
         if (!rc) {
             hipLaunchKernelGGL(mcts_advance_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, dv, d);
             if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_advance_kernel launch failed");
@@ -1597,14 +1571,14 @@ extern "C" int rl_mcts_drive(rl_mcts *m, const double *states_in, const double *
         return rc;
     }
     // the planner keeps the last decision's trees: its keys, ray offset and iteration count are that decision's
-    HIPCHK(hipMemcpyAsync(m->keys.p, b.keys, (size_t)K * 4, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(first, m->dr_first.p, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(m->keys, b.keys, (size_t)K * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(first, m->dr_first, (size_t)K * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(states_out, d_states, (size_t)K * 88, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(recent_out, d_recent, (size_t)K * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(actions, m->dr_actions.p, rows * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(visits, m->dr_visits.p, rows * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(actions, m->dr_actions, rows * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(visits, m->dr_visits, rows * 4, hipMemcpyDeviceToHost, st));
     if (trace_states_or_null)
-        HIPCHK(hipMemcpyAsync(trace_states_or_null, m->dr_trace.p, rows * 88, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(trace_states_or_null, m->dr_trace, rows * 88, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     m->base = base;
     m->iters = I;
@@ -1621,11 +1595,11 @@ extern "C" int rl_mcts_best(rl_mcts *m, double *actions, int *visits, int *n_nod
     hipStream_t st = m->c->stream;
     const int K = m->prm.n_trees;
     hipLaunchKernelGGL(mcts_best_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, mcts_bufs(m),
-                       (double *)m->best_a.p, (int *)m->best_v.p, (int *)m->best_n.p);
+                       (double *)m->best_a, (int *)m->best_v, (int *)m->best_n);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(actions, m->best_a.p, (size_t)K * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(visits, m->best_v.p, (size_t)K * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(n_nodes, m->best_n.p, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(actions, m->best_a, (size_t)K * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(visits, m->best_v, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(n_nodes, m->best_n, (size_t)K * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return RL_OK;
 }
@@ -1643,16 +1617,16 @@ extern "C" int rl_mcts_read_tree(rl_mcts *m, int tree, int *parent, int *first_c
     HIPCHK(hipSetDevice(m->device));
     hipStream_t st = m->c->stream;
     int n = 0;
-    HIPCHK(hipMemcpyAsync(&n, (const int *)m->n_nodes.p + tree, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&n, m->n_nodes + tree, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     n = std::min(std::max(n, 0), m->prm.max_nodes);
     const size_t t0 = (size_t)tree * m->prm.max_nodes;
     struct Out { void *dst; const DevBuf *src; size_t w; };
-    const Out outs[] = {{parent, &m->parent, 4}, {first_child, &m->first_child, 4}, {next_sibling, &m->next_sibling, 4},
-                        {n_children, &m->n_children, 4}, {visits, &m->visits, 4}, {child_visits, &m->child_visits, 4},
-                        {reward, &m->reward, 8}, {action, &m->action, 8}, {terminal, &m->terminal, 4},
-                        {state, &m->state, 88}, {scan_pose, &m->pose, 12}, {answer, &m->answer, 4},
-                        {crash, &m->crash, 4}};
+    const Out outs[] = {{parent, &m->parent.buf, 4}, {first_child, &m->first_child.buf, 4}, {next_sibling, &m->next_sibling.buf, 4},
+                        {n_children, &m->n_children.buf, 4}, {visits, &m->visits.buf, 4}, {child_visits, &m->child_visits.buf, 4},
+                        {reward, &m->reward.buf, 8}, {action, &m->action.buf, 8}, {terminal, &m->terminal.buf, 4},
+                        {state, &m->state.buf, 88}, {scan_pose, &m->pose.buf, 12}, {answer, &m->answer.buf, 4},
+                        {crash, &m->crash.buf, 4}};
     for (const Out &o : outs)
         if (o.dst && n > 0)
             HIPCHK(hipMemcpyAsync(o.dst, (const char *)o.src->p + t0 * o.w, (size_t)n * o.w, hipMemcpyDeviceToHost, st));

@@ -1911,7 +1911,7 @@ extern "C" int rl_pf_reset(rl_pf *f, const double *particles_p3, const double *w
     HIPCHK(hipMemcpyAsync(f->w.p, weights_or_null ? weights_or_null : uniform.data(), P * 8, hipMemcpyHostToDevice, s));
     for (DevBuf *b : {&f->prop, &f->lik, &f->omega, &f->part, &f->cum, &f->anc}) HIPCHK(hipMemsetAsync(b->p, 0, b->cap, s));
     HIPCHK(hipStreamSynchronize(s));
-    f->key = (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x85EBCA6Bu);     // np_statement.noise_key
+    f->key = noise_key(seed);
     f->t = 0;
     f->ready = true;
     return RL_OK;

@@ -6,9 +6,11 @@
 //                  device-pointer entry points, the single-device host-pointer paths, the fused crash test; the
 //                  particle-filter weights (repeat-angle scans, sensor model) and localisation (rl_pf_*)
 //   abi_multi.hip  the host-pointer entry points and their multi-device forms (run_blocks below: one block per device)
-//   abi_car.hip    roll-out generator, FollowGap, the policy network, closed-loop FollowGap / policy roll-outs,
-//                  the driving environment (rl_env_*), batched races and the race scan, the MCTS planner and its closed-loop drive (rl_mcts_*), 16-bit
-//                  ranges, probes, the car-outline table and cells
+//   abi_car.hip    roll-out generator, FollowGap, the policy network, batched races and the race scan; the closed-loop
+//                  session (loop_args, Loop: the checks, locks, handle override and scan-then-consume step of every
+//                  closed loop) and its three users: FollowGap / policy / race roll-outs (drive_loop), the driving
+//                  environment (rl_env_*), the MCTS planner and its closed-loop drive (rl_mcts_*); 16-bit ranges,
+//                  probes, the car-outline table and cells
 #pragma once
 // (the units are built with -fvisibility=hidden: only the C ABI leaves the library)
 #pragma GCC visibility push(default)
@@ -104,11 +106,12 @@ struct DevBuf {
     }
 };
 
-// a device array of T of exactly the size asked for; reads as the T* the launches take
+// a device array of T, sized in bytes as DevBuf sizes it; reads as the T* the launches take
 template <class T>
 struct DevPtr {
     DevBuf buf;
     int alloc(size_t bytes) { return buf.alloc(bytes); }
+    int ensure(size_t bytes) { return buf.ensure(bytes); }
     void release() { buf.release(); }
     operator T *() const { return (T *)buf.p; }
 };
@@ -502,6 +505,10 @@ struct MultiCall {
         });
     }
 };
+
+// the 64-bit seed of a Philox stream folded to its 32-bit key (np_statement.noise_key; scan_device.h folds the scan
+// noise's seed the same way on the device)
+static inline uint32_t noise_key(uint64_t seed) { return (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x85EBCA6Bu); }
 
 int set_device(const rl_map *m);
 int check_device(int device);                       // RL_ERR_NO_DEVICE unless `device` names a visible HIP device; abi_map.hip

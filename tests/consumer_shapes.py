@@ -8,7 +8,7 @@ import numpy as np
 
 FOV, THRESH, D_BASE = 4.71, 0.001, 0.275
 FG_ROWS = 20                                  # consumer_kernels.h: one instantiation per ROWS = 1 ... FG_ROWS
-MIN_RAYS, MAX_RAYS = 10, 64 * FG_ROWS         # drive_args / rl_mcts_create: num_rays in [10, 1280]
+MIN_RAYS, MAX_RAYS = 10, 64 * FG_ROWS         # loop_args (every closed loop): num_rays in [10, 1280]
 DRIVE_CARS = 8                                # drive_kernels.h: cars (waves) per workgroup of drive_tick_kernel
 
 

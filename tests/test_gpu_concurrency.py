@@ -7,7 +7,11 @@ import threading
 import numpy as np
 import pytest
 
-from pyracecarsimulator_amd import maps, range_libc
+import test_gpu_env as TE
+from pyracecarsimulator_amd import DriveEnv, maps, range_libc
+from pyracecarsimulator_amd import racecar as RC
+from pyracecarsimulator_amd.followgap import PyFollowGap
+from pyracecarsimulator_amd.mcts import MCTSPlanner
 from pyracecarsimulator_amd.pipeline import concurrent_streams
 
 pytestmark = pytest.mark.gpu
@@ -211,3 +215,71 @@ def test_map_update_thread_races_scan_threads(oracle_mod):
     up.join(60)
     assert not errors, errors[:3]
     assert seen[0] == {"a", "b"} or seen[1] == {"a", "b"}     # the updates really interleaved with scans
+
+
+def test_closed_loops_share_their_handles_across_threads():
+    """One CarBatch, one RMGPU method with noise on and one PyFollowGap, used at once by a FollowGap roll-out, a driving
+    environment (reset + 6 steps) and an MCTS planner (reset, run(2), best) in three threads: every call holds the
+    method's mutex from its first launch to its last and puts the ray offset and nt_store back before it lets go, so
+    every output equals the serial run's bit for bit and the method is left as it was.  9 units (one past DRIVE_CARS =
+    8: a second workgroup with one live wave), 65 beams (two beam rows, the second holding one beam), 6 ticks."""
+    N, B, T, base = 9, 65, 6, 4242
+    g, states, actions = TE.maze_case(lambda g_: range_libc.PyOMap(g_).distance_transform())
+    states = np.ascontiguousarray(states[[0, 1, 2, 3, 4, 5, 46, 47, 48]])       # six in the open, three near a wall
+    actions = np.ascontiguousarray(actions[:T, :N])
+    speeds = np.linspace(1.0, 5.0, N)
+    m = range_libc.PyRayMarchingGPU(range_libc.PyOMap(g), 300)
+    m.set_noise(0.01, 77, base)
+    cars, fg, edge = RC.CarBatch(), PyFollowGap(10, 15.0, TE.MAX_STEER, 0.004), TE._edge(B)
+    env = DriveEnv(m, states, N, B, TE.FOV, edge, TE.THRESH, car=cars)
+    pl = MCTSPlanner(cars, m, N, 4, TE.FOV, B, edge, TE.THRESH, source="fg", followgap=fg, rollout_steps=4,
+                     action_every=2)
+    seeds = np.arange(N, dtype=np.uint64) * np.uint64(2 ** 33 + 7) + np.uint64(1)
+    poses = np.ascontiguousarray(states[:, :3], np.float32)
+
+    def fan():
+        out = np.empty(N * B, np.float32)
+        m.calc_range_fan(poses, out, TE.FOV, B)
+        return out
+
+    def drive():
+        return cars.drive_followgap(m, fg, states, T, speeds, TE.FOV, B, edge, TE.THRESH, trace=True)
+
+    def drive_env():
+        out = [env.reset(seed=5, start_index=np.arange(N, dtype=np.int32))]
+        for k in range(T):
+            out.extend(env.step(actions[k]))
+        return out + [env.read()["states"]]
+
+    def plan():
+        pl.reset(states, np.linspace(-0.2, 0.2, N), seeds)
+        pl.run(2)
+        return pl.best()
+
+    work = [drive, drive_env, plan]
+    before = fan()
+    serial = [[np.array(a) for a in w()] for w in work]
+    got, errors = [None] * len(work), []
+
+    def runner(i):
+        try:
+            got[i] = [np.array(a) for a in work[i]()]
+        except Exception as e:                                  # noqa: BLE001
+            errors.append((i, repr(e)))
+
+    threads = [threading.Thread(target=runner, args=(i,), daemon=True) for i in range(len(work))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(60)
+    assert not any(t.is_alive() for t in threads), "a closed loop did not return within 60 s"
+    assert not errors, errors
+    for i, w in enumerate(work):
+        assert len(got[i]) == len(serial[i]), w.__name__
+        for j, (a, b) in enumerate(zip(got[i], serial[i])):
+            assert TE._same_bits(a, b), (w.__name__, j)
+    assert m.get_info("nt_store") == 1
+    assert TE._same_bits(fan(), before)
+    pl.close()
+    env.close()
+    m.set_noise(0.0, 0, 0)
