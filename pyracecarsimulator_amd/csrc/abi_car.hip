@@ -1,6 +1,6 @@
 // abi_car.hip — what sits in front of and behind the scan path in libscan_amd.so (C ABI: include/scanlib.h; SURVEY.md
 // section 8f): the MCTS roll-out generator, FollowGap, the policy network, the race scan; the closed-loop session (loop_args
-// and Loop: handle checks, locks, option override, scan-then-consume) with its users drive_loop, rl_env_* and rl_mcts_*;
+// and Loop: handle checks, locks, launch arguments, scan-then-consume) with its users drive_loop, rl_env_* and rl_mcts_*;
 // 16-bit ranges for the xGMI exchange, diagnostics probes, the car-outline table and Car::isCrashed on the host.
 #include "abi_internal.h"
 #include <array>
@@ -180,7 +180,7 @@ extern "C" int rl_car_rollout_check(rl_car *c, rl_method *h, const double *state
         (rc = c->first.ensure((size_t)R * 4)))
         return rc;
     HIPCHK(hipMemcpyAsync(c->edge.p, edge, (size_t)num_rays * 8, hipMemcpyHostToDevice, c->stream));
-    rc = crash_groups_device(h, (const float *)c->poses.p, R, n_steps, fov, num_rays,
+    rc = crash_groups_device(h, LaunchArgs::of(h), (const float *)c->poses.p, R, n_steps, fov, num_rays,
                              (const double *)c->edge.p, crash_thresh, (int *)c->first.p,
                              (float *)c->ranges.p, c->stream);
     if (rc) return rc;
@@ -350,20 +350,20 @@ static const race_fn race_table[2][2] = {{race_fan_kernel<false, false>, race_fa
                                          {race_fan_kernel<true, false>, race_fan_kernel<true, true>}};
 
 // one race_fan_kernel launch on `stream`: the caller holds h->mu and the map's tables_mu and has checked the arguments
-static int launch_race(rl_method *h, const float *d_poses, const double *d_cars, int car_stride, int n_groups, int group,
-                       const OutlineParams &o, float fov, int num_rays, float *d_out, int32_t *d_hits, uint16_t *d_steps,
-                       hipStream_t stream)
+static int launch_race(rl_method *h, const LaunchArgs &a, const float *d_poses, const double *d_cars, int car_stride, int n_groups,
+                       int group, const OutlineParams &o, float fov, int num_rays, float *d_out, int32_t *d_hits,
+                       uint16_t *d_steps, hipStream_t stream)
 {
     if (n_groups == 0) return RL_OK;
     const bool lit = h->opt.variant == 3, aux = d_hits || d_steps;
-    const FanParams f = make_fan(h, n_groups * group, fov, num_rays);
+    const FanParams f = make_fan(h, n_groups * group, fov, num_rays, a.ray_offset);
     const LiteralParams lp = lit ? make_literal(h->map) : LiteralParams{};
     const RaceParams rp{o, d_cars, car_stride, group, n_groups};
-    if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
+    if (a.timing) HIPCHK(hipEventRecord(h->ev0, stream));
     race_table[lit][aux]<<<dim3(n_groups), dim3(RACE_WG), 0, stream>>>(h->map->mp, f, lp, rp, d_poses, d_out, d_hits,
                                                                        d_steps);
     HIPCHK(hipGetLastError());
-    if (h->timing) {
+    if (a.timing) {
         HIPCHK(hipEventRecord(h->ev1, stream));
         h->timed = true;
     }
@@ -391,7 +391,7 @@ extern "C" int rl_calc_range_fan_cars_device(rl_method *h, const float *d_poses,
     std::lock_guard<std::mutex> lk(h->mu);
     std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
     if ((rc = set_device(h->map))) return rc;
-    return launch_race(h, d_poses, d_cars, 3, n_groups, group, o, fov, num_rays, d_outs, d_hits, d_steps,
+    return launch_race(h, LaunchArgs::of(h), d_poses, d_cars, 3, n_groups, group, o, fov, num_rays, d_outs, d_hits, d_steps,
                        (hipStream_t)hip_stream);
 }
 
@@ -413,7 +413,7 @@ extern "C" int rl_calc_range_fan_cars(rl_method *h, const float *poses, const do
     hipStream_t st = h->stream;
     HIPCHK(hipMemcpyAsync(h->poses.p, poses, n * 12, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(h->cars.p, cars, n * 24, hipMemcpyHostToDevice, st));
-    rc = launch_race(h, (const float *)h->poses.p, (const double *)h->cars.p, 3, n_groups, group, o, fov, num_rays,
+    rc = launch_race(h, LaunchArgs::of(h), (const float *)h->poses.p, (const double *)h->cars.p, 3, n_groups, group, o, fov, num_rays,
                      (float *)h->outs.p, hits_or_null ? (int32_t *)h->hits.p : nullptr,
                      steps_or_null ? (uint16_t *)h->steps.p : nullptr, st);
     if (rc) {
@@ -583,23 +583,7 @@ extern "C" int rl_policy_eval_device(rl_policy *p, const float *d_scans, int n_s
 // ---------------------------------------------------------------- the closed-loop session
 // What the closed loops share on the host.  The roll-outs (drive_loop), the driving environment (rl_env_*) and the MCTS
 // planner (rl_mcts_*) check their handles with loop_args, and each of their launching calls lives inside one Loop: its
-// locks, the override of the method's options, and the scan-then-consume step every one of them is made of.
-
-// the options of h that a closed loop overrides, restored on every exit: its consumer kernels read the ranges right after
-// the scan (plain stores), and it walks the noise offset from the value saved here
-struct HandleOverride {
-    rl_method *h;
-    const uint64_t ray_offset;
-    const int nt_store;
-    explicit HandleOverride(rl_method *h_) : h(h_), ray_offset(h_->ray_offset), nt_store(h_->nt_store) { h->nt_store = 0; }
-    ~HandleOverride()
-    {
-        h->ray_offset = ray_offset;
-        h->nt_store = nt_store;
-    }
-    HandleOverride(const HandleOverride &) = delete;
-    HandleOverride &operator=(const HandleOverride &) = delete;
-};
+// locks, what it tells its launches, and the scan-then-consume step every one of them is made of.
 
 // the handle checks of every closed loop: `units` cars / envs / poses scan num_rays beams each; the steering source is
 // g, p or neither (the environment, the planner's random source)
@@ -636,20 +620,23 @@ struct LoopScan {
 };
 
 // One launching call of a closed loop.  Locks in ONE order: the owner's mutex (rl_env::mu, rl_mcts::mu; none for the
-// roll-outs), the car's, the method's, the steering source's (if any), then the map's tables_mu shared; the method's
-// options are overridden last and come back first.  `ready` of an owner is read and written inside only.
+// roll-outs), the car's, the method's, the steering source's (if any), then the map's tables_mu shared.  The method's
+// settings are read under its mutex and never written: `base` is the noise offset the loop walks from, and every launch
+// is told its own offset and plain stores (the consumer kernels read the ranges right after the scan).  `ready` of an
+// owner is read and written inside only.
 struct Loop {
     rl_method *const h;
     rl_policy *const p;
     std::unique_lock<std::mutex> lo, lc, lh, ls;
     std::shared_lock<std::shared_mutex> ml;
-    const HandleOverride ov;
+    const uint64_t base;
     static std::unique_lock<std::mutex> held(std::mutex *m) { return m ? std::unique_lock(*m) : std::unique_lock<std::mutex>(); }
     Loop(std::mutex *owner, rl_car *c, rl_method *h_, rl_followgap *g, rl_policy *p_)
         : h(h_), p(p_), lo(held(owner)), lc(c->mu), lh(h_->mu), ls(held(g ? &g->mu : p_ ? &p_->mu : nullptr)),
-          ml(h_->map->tables_mu), ov(h_)
+          ml(h_->map->tables_mu), base(h_->ray_offset)
     {
     }
+    LaunchArgs at(uint64_t off) const { return {off, true, h->timing}; }
 
     // scan-then-consume on st: the scan at noise offset `off`, the network when the source is a policy, then the ROWS
     // instantiation of `table` for num_rays, one wave per unit and per_wg units per workgroup
@@ -657,10 +644,10 @@ struct Loop {
     int scan_then(const LoopScan &s, uint64_t off, const std::array<Fn, FG_ROWS> &table, int per_wg, const char *kernel,
                   hipStream_t st, const Args &...args) const
     {
-        h->ray_offset = off;
-        int rc = s.group > 0 ? launch_race(h, s.poses, s.cars, 11, s.n / s.group, s.group, *s.outline, s.fov, s.num_rays,
+        const LaunchArgs a = at(off);
+        int rc = s.group > 0 ? launch_race(h, a, s.poses, s.cars, 11, s.n / s.group, s.group, *s.outline, s.fov, s.num_rays,
                                            s.ranges, nullptr, nullptr, st)
-                             : launch_fan(h, s.poses, s.n, s.fov, s.num_rays, s.ranges, nullptr, nullptr, nullptr, st);
+                             : launch_fan(h, FanCall{a, s.poses, s.n, s.fov, s.num_rays, s.ranges, nullptr, nullptr, nullptr, st});
         if (rc == RL_OK && p) rc = policy_launch(p, s.ranges, s.n, s.num_rays, s.mlp, st);
         if (rc) return rc;
         table[(s.num_rays + 63) / 64 - 1]<<<dim3((s.n + per_wg - 1) / per_wg), dim3(64 * per_wg), 0, st>>>(args...);
@@ -752,7 +739,7 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
     // (a race reads every car's outline from its f64 state after this tick's step: all cars step, then all scan)
     const LoopScan scan{b.pose, R, a.fov, num_rays, (float *)c->ranges.p, (float *)c->mlp.p, race ? group : 0, b.state, &op};
     for (int t = 0; t < n_ticks && rc == RL_OK; ++t)
-        rc = lp.scan_then(scan, lp.ov.ray_offset + (uint64_t)t * n_rays, g ? fg_tick_table : policy_tick_table, DRIVE_CARS,
+        rc = lp.scan_then(scan, lp.base + (uint64_t)t * n_rays, g ? fg_tick_table : policy_tick_table, DRIVE_CARS,
                           "drive_tick_kernel", st, dp, b, t);
     if (rc) {
         (void)hipStreamSynchronize(st);           // nothing of this call is left in flight on the handles' buffers
@@ -942,7 +929,7 @@ static int env_reset_locked(rl_env *e, const Loop &lp, uint64_t seed, const int 
 {
     e->ready = false;
     e->ep.key = noise_key(seed);
-    e->base = lp.ov.ray_offset;
+    e->base = lp.base;
     const int rc = env_launch(e, lp, true, 0, nullptr, d_start_index, d_obs, nullptr, d_done, d_aux, st);
     if (rc) return rc;
     e->k = 0;
@@ -1437,7 +1424,7 @@ extern "C" int rl_mcts_reset(rl_mcts *m, const double *root_states, const double
     m->ready = false;
     std::vector<uint32_t> keys(K);
     for (int k = 0; k < K; ++k) keys[k] = noise_key(seeds[k]);
-    const uint64_t base = lp.ov.ray_offset;
+    const uint64_t base = lp.base;
     rc = mcts_start(m, mcts_bufs(m), m->keys, keys, root_states, root_actions, st);
     if (!rc) rc = mcts_act(m, lp, mcts_bufs(m), base, 1, st);
     const hipError_t e = hipStreamSynchronize(st);            // (the host's root arrays are the caller's)
@@ -1468,11 +1455,9 @@ static int mcts_iterations(rl_mcts *m, const Loop &lp, const MctsBufs &b, uint64
                                (double *)nullptr, (double *)m->vel);
             if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "rollout_kernel launch failed");
         }
-        if (!rc) {
-            m->h->ray_offset = off + KB;
-            rc = crash_groups_device(m->h, m->rposes, K, L, m->prm.fov, B, m->edge, m->prm.crash_thresh, m->first,
-                                     m->rranges, st);
-        }
+        if (!rc)
+            rc = crash_groups_device(m->h, lp.at(off + KB), m->rposes, K, L, m->prm.fov, B, m->edge, m->prm.crash_thresh,
+                                     m->first, m->rranges, st);
         if (!rc) {
             hipLaunchKernelGGL(mcts_backup_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b);
             if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_backup_kernel launch failed");
@@ -1555,9 +1540,9 @@ extern "C" int rl_mcts_drive(rl_mcts *m, const double *states_in, const double *
                        trace_states_or_null ? (double *)m->dr_trace : nullptr, D, steps_per_decision, steer_clip};
     const uint64_t stride = (uint64_t)K * B * (1 + (uint64_t)I * (1 + L));
     rc = mcts_start(m, b, m->dr_keys, keys, states_in, recent_in, st);
-    uint64_t base = lp.ov.ray_offset;
+    uint64_t base = lp.base;
     for (int d = 0; d < D && rc == RL_OK; ++d) {
-        base = lp.ov.ray_offset + (uint64_t)d * stride;
+        base = lp.base + (uint64_t)d * stride;
         b.keys = m->dr_keys + (size_t)d * K;
         rc = mcts_act(m, lp, b, base, 1, st);
         if (!rc) rc = mcts_iterations(m, lp, b, base, 0, I, st);

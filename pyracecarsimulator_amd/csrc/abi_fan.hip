@@ -253,7 +253,7 @@ extern "C" int rl_method_get_info(rl_method *h, const char *name, int64_t *value
 // ------------------------------------------------------------------------------
 // launches
 // ------------------------------------------------------------------------------
-FanParams make_fan(const rl_method *h, int n_poses, float fov, int num_rays)
+FanParams make_fan(const rl_method *h, int n_poses, float fov, int num_rays, uint64_t ray_offset)
 {
     FanParams f{};
     f.n_poses = n_poses;
@@ -264,7 +264,7 @@ FanParams make_fan(const rl_method *h, int n_poses, float fov, int num_rays)
     f.step_coeff = h->step_coeff;
     f.noise_std = h->noise_std;
     f.noise_seed = h->noise_seed;
-    f.ray_offset = h->ray_offset;
+    f.ray_offset = ray_offset;
     return f;
 }
 
@@ -841,22 +841,13 @@ LiteralParams make_literal(const rl_map *m)
 }
 
 
-// what a method family's launch function needs: the call's arguments, the plan, the launch context
-struct FanLaunch {
+// what a method family's launch function needs: the call, the plan, the launch context
+struct FanLaunch : FanCall {
     rl_method *h;
     const rl_map *m;
     const rl_launch_plan &pl;
     LaunchCtx *cx;
     FanParams f;
-    const float *d_poses;
-    int n_poses;
-    float fov;
-    int num_rays;
-    float *d_out;
-    int32_t *d_hits;
-    uint16_t *d_steps;
-    const CrashParams *crash;
-    hipStream_t stream;
     bool aux;
     dim3 grid, block;            // (the plan's)
     size_t lds;
@@ -879,7 +870,7 @@ static int launch_lut(const FanLaunch &L)
     if (!kernel) return fail(RL_ERR_INVALID, "internal: plan names an uninstantiated kernel (%s)", pl.name);
     int rc;
     if ((rc = ensure_lut(L.h, L.stream))) return rc;
-    if (L.h->timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
+    if (L.timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
     kernel<<<L.grid, L.block, L.lds, L.stream>>>(L.m->mp, L.f, L.h->lp, L.d_poses, L.d_out);
     return RL_OK;
 }
@@ -896,7 +887,7 @@ static int launch_cddt_bins(const FanLaunch &L)
         if ((rc = bin_poses(h, *L.cx, L.d_poses, L.n_poses, 0, L.stream, L.pl.binning))) return rc;
         d_order = (const uint32_t *)L.cx->order.p;
     }
-    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
+    if (L.timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
     hipLaunchKernelGGL(cddt_fan_bins_kernel, L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, h->cdp, L.d_poses, L.d_out,
                        d_order, L.pl.bands, L.pl.nl, L.pl.ch);
     return RL_OK;
@@ -917,7 +908,7 @@ static int launch_cddt_theta(const FanLaunch &L)
         return rc;
     float4 *d_prep = (float4 *)L.cx->cddt_r.p;
     float *d_r = (float *)((char *)L.cx->cddt_r.p + prep_bytes);
-    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
+    if (L.timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
     hipLaunchKernelGGL(cddt_theta_prep_kernel, dim3((unsigned)std::max(1, std::min((L.n_poses + 255) / 256, L.m->n_cu * 8))),
                        dim3(256), 0, L.stream, L.m->mp, L.f, h->cdp, L.d_poses, d_prep);
     if (fused) {
@@ -942,7 +933,7 @@ static int launch_cddt_rays(const FanLaunch &L)
 {
     int rc;
     if ((rc = ensure_cddt(L.h, L.stream))) return rc;
-    if (L.h->timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
+    if (L.timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
     hipLaunchKernelGGL(cddt_fan_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f, L.h->cdp, L.d_poses, L.d_out);
     return RL_OK;
 }
@@ -961,8 +952,8 @@ static int launch_bl_stream(const FanLaunch &L)
     sp.div_B = make_fastdiv((uint32_t)L.num_rays);
     sp.low_water = h->opt.low_water >= 0 ? h->opt.low_water : 12;
     sp.n_bands = L.pl.bands;
-    sp.plain_store = !h->nt_store;
-    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
+    sp.plain_store = L.plain_store;
+    if (L.timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
     if (L.aux)
         hipLaunchKernelGGL((bl_fan_stream_kernel<true, 1024>), L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, sp, h->blp,
                            L.d_out, L.d_hits, L.d_steps);
@@ -986,7 +977,7 @@ static int launch_bl_lds(const FanLaunch &L)
         HIPCHK(hipFuncSetAttribute(fa, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bl));
         HIPCHK(hipFuncSetAttribute(fb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bl));
     }
-    if (L.h->timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
+    if (L.timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
 #define LAUNCH_BL(K) hipLaunchKernelGGL((K), L.grid, L.block, lds_bl, L.stream, L.m->mp, L.f, bp, L.d_poses, L.d_out, L.d_hits, L.d_steps)
     // (occ_fan_lds: unit-step march on an LDS-resident occupancy window — A/B partner, approximate)
     if (bl) { if (L.aux) LAUNCH_BL(bl_fan_kernel<true>); else LAUNCH_BL(bl_fan_kernel<false>); }
@@ -1000,7 +991,7 @@ static int launch_rm_literal(const FanLaunch &L)
 {
     const LiteralParams lt = make_literal(L.m);
     const long n_rays = (long)L.n_poses * L.num_rays;
-    if (L.h->timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
+    if (L.timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
     if (L.aux)
         hipLaunchKernelGGL((rm_literal_kernel<true, false>), L.grid, L.block, 0, L.stream, L.m->mp, L.f, lt, L.d_poses, n_rays,
                            L.d_out, L.d_hits, L.d_steps);
@@ -1015,7 +1006,7 @@ static int launch_rm_chunk(const FanLaunch &L)
 {
     CrashParams cp{nullptr, 0.0, nullptr, 1};
     if (L.crash) cp = *L.crash;
-    if (L.h->timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
+    if (L.timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
 #define LAUNCH_CHUNK(A, C) hipLaunchKernelGGL((rm_fan_kernel<A, C>), L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, L.d_poses, \
                                               L.d_out, L.d_hits, L.d_steps, cp)
     if (L.crash) { if (L.aux) LAUNCH_CHUNK(true, true); else LAUNCH_CHUNK(false, true); }
@@ -1080,7 +1071,7 @@ static int launch_rm_stream_family(const FanLaunch &L)
     sp.drain_stretch = h->drain_stretch;
     sp.group_drain = h->group_drain;
     if (pl.kernel == RL_K_RM_STREAM_LIT) sp.lit = make_literal(L.m);
-    sp.plain_store = !h->nt_store;
+    sp.plain_store = L.plain_store;
     sp.dbg = nullptr;
     const int waves_per_wg = pl.block / 64;
     if (h->opt.debug_stamps) {
@@ -1107,7 +1098,7 @@ static int launch_rm_stream_family(const FanLaunch &L)
         sp.left_cap_log2 = cap_log2;
         sp.drain_cap = std::min(sp.drain_cap, 1 << cap_log2);
     }
-    if (h->timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));   // march kernel(s) alone
+    if (L.timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));   // march kernel(s) alone
     if ((rc = dispatch_rm_stream(pl, L.stream, pm, L.f, sp, L.d_out, L.d_hits, L.d_steps, cp))) return rc;
     if (handoff) {
         const int lw = h->handoff_wg / 64;                              // leftover waves per workgroup
@@ -1123,52 +1114,52 @@ static int launch_rm_stream_family(const FanLaunch &L)
     return RL_OK;
 }
 
-// a batch cut into pose slices (plan: slices > 1), each its own launch sequence on the stream
-static int launch_fan_sliced(rl_method *h, const rl_launch_plan &pl, const float *d_poses, int n_poses, float fov,
-                             int num_rays, float *d_out, int32_t *d_hits, uint16_t *d_steps, const CrashParams *crash,
-                             hipStream_t stream)
+FanCall FanCall::slice(int p0, int np, CrashParams *marks) const
 {
-    int rc = RL_OK;
-    // pose slices below 2^slice_log2 rays, each its own launch sequence
-    if (crash && crash->group != 0)
-        return fail(RL_ERR_UNSUPPORTED, "a fused crash test over %d poses in the upstream-literal mode needs the per-pose "
-                                        "mark form (rl_check_collision_groups*), not one roll-out of that length", n_poses);
-    const int per = pl.slice_poses;
-    const uint64_t base_off = h->ray_offset;
-    // one event pair around the whole sliced sequence (the per-slice pairs would leave the
-    // last slice only)
-    const int timing = h->timing;
-    h->timing = 0;
-    if (timing) HIPCHK(hipEventRecord(h->ev0, stream));
-    rc = RL_OK;
-    for (int p0 = 0; p0 < n_poses && rc == RL_OK; p0 += per) {
-        const int np = std::min(per, n_poses - p0);
-        const size_t r0 = (size_t)p0 * num_rays;
-        h->ray_offset = base_off + r0;               // noise stays keyed by the global ray id
-        // (a fused crash test reaches a sliced launch only in per-pose-mark form — the upstream-literal mode's
-        //  slices: slice k marks poses p0 .. p0 + np - 1 through a shifted mark array)
-        CrashParams cps{nullptr, 0.0, nullptr, 1, 0};
-        if (crash) {
-            cps = *crash;
-            cps.first_crashed = crash->first_crashed + p0;
-        }
-        rc = launch_fan(h, d_poses + (size_t)p0 * 3, np, fov, num_rays, d_out ? d_out + r0 : nullptr,
-                        d_hits ? d_hits + 2 * r0 : nullptr, d_steps ? d_steps + r0 : nullptr,
-                        crash ? &cps : nullptr, stream);
+    const size_t r0 = (size_t)p0 * num_rays;
+    FanCall s = *this;
+    s.ray_offset += r0;                              // noise stays keyed by the global ray id
+    s.d_poses += (size_t)p0 * 3;
+    s.n_poses = np;
+    if (d_out) s.d_out += r0;
+    if (d_hits) s.d_hits += 2 * r0;
+    if (d_steps) s.d_steps += r0;
+    if (crash) {
+        *marks = *crash;
+        marks->first_crashed += p0;
+        s.crash = marks;
     }
-    h->ray_offset = base_off;
-    h->timing = timing;
-    if (timing && rc == RL_OK) { HIPCHK(hipEventRecord(h->ev1, stream)); h->timed = true; }
+    return s;
+}
+
+// a batch cut into pose slices below 2^slice_log2 rays (plan: slices > 1), each its own launch sequence on the stream
+static int launch_fan_sliced(rl_method *h, const rl_launch_plan &pl, const FanCall &c)
+{
+    // (a fused crash test reaches a sliced launch only in per-pose-mark form — the upstream-literal mode's slices)
+    if (c.crash && c.crash->group != 0)
+        return fail(RL_ERR_UNSUPPORTED, "a fused crash test over %d poses in the upstream-literal mode needs the per-pose "
+                                        "mark form (rl_check_collision_groups*), not one roll-out of that length", c.n_poses);
+    // one event pair around the whole sliced sequence (the per-slice pairs would leave the last slice only)
+    if (c.timing) HIPCHK(hipEventRecord(h->ev0, c.stream));
+    int rc = RL_OK;
+    for (int p0 = 0; p0 < c.n_poses && rc == RL_OK; p0 += pl.slice_poses) {
+        CrashParams marks;
+        FanCall s = c.slice(p0, std::min(pl.slice_poses, c.n_poses - p0), &marks);
+        s.timing = 0;
+        rc = launch_fan(h, s);
+    }
+    if (c.timing && rc == RL_OK) { HIPCHK(hipEventRecord(h->ev1, c.stream)); h->timed = true; }
     return rc;
 }
 
-int launch_fan(rl_method *h, const float *d_poses, int n_poses, float fov, int num_rays,
-               float *d_out, int32_t *d_hits, uint16_t *d_steps, const CrashParams *crash,
-               hipStream_t stream)
+int launch_fan(rl_method *h, const FanCall &c)
 {
-    if (n_poses == 0) return RL_OK;
+    if (c.n_poses == 0) return RL_OK;
     const rl_map *m = h->map;
-    const bool aux = d_hits || d_steps;
+    const int num_rays = c.num_rays;
+    const hipStream_t stream = c.stream;
+    const CrashParams *const crash = c.crash;
+    const bool aux = c.d_hits || c.d_steps;
     if (h->kind != RL_RM && h->kind != RL_RM_GPU) {
         if (crash) return fail(RL_ERR_UNSUPPORTED, "fused crash test needs a ray-marching method");
         if (aux && h->kind != RL_BRESENHAM)
@@ -1178,20 +1169,19 @@ int launch_fan(rl_method *h, const float *d_poses, int n_poses, float fov, int n
     int rc = RL_OK;
     // (a code-map handle plans with its palette size: the step map and the palette are built before the plan)
     if (h->opt.code_map && (h->kind == RL_RM || h->kind == RL_RM_GPU) && h->opt.variant >= 1 && (rc = ensure_step_map(h, stream))) return rc;
-    rc = plan_for(h, n_poses, num_rays, aux, crash != nullptr, &pl);
+    rc = plan_for(h, c.n_poses, num_rays, aux, crash != nullptr, &pl);
     if (rc == RL_ERR_UNSUPPORTED)
         return fail(rc, (h->opt.variant >= 2 && crash) ? "the fused crash test needs variant 0 or 1 (not the occupancy-window or the audit kernel)"
                         : h->opt.variant == 2 ? "occupancy window of max_range %g does not fit LDS (num_rays %d)"
                                           : "the beam tables of max_range %g, num_rays %d exceed a workgroup's LDS (160 KB)",
                     h->max_range, num_rays);
     if (rc) return fail(rc, "launch planning failed");
-    if (pl.slices > 1) return launch_fan_sliced(h, pl, d_poses, n_poses, fov, num_rays, d_out, d_hits, d_steps, crash, stream);
+    if (pl.slices > 1) return launch_fan_sliced(h, pl, c);
     LaunchCtx *cx = nullptr;
     if ((rc = acquire_ctx(h, stream, &cx))) return rc;
     h->last_plan = pl;
-    FanParams f = make_fan(h, n_poses, fov, num_rays);
-    if (h->timing == 1) HIPCHK(hipEventRecord(h->ev0, stream));
-    const FanLaunch L{h, m, pl, cx, f, d_poses, n_poses, fov, num_rays, d_out, d_hits, d_steps, crash, stream, aux,
+    if (c.timing == 1) HIPCHK(hipEventRecord(h->ev0, stream));
+    const FanLaunch L{c, h, m, pl, cx, make_fan(h, c.n_poses, c.fov, num_rays, c.ray_offset), aux,
                       dim3(pl.grid), dim3(pl.block), (size_t)pl.lds_bytes};
     switch (pl.kernel) {
     case RL_K_LUT_LDS:
@@ -1229,7 +1219,7 @@ int launch_fan(rl_method *h, const float *d_poses, int n_poses, float fov, int n
     }
     if (rc) return rc;
     HIPCHK(hipGetLastError());
-    if (h->timing) { HIPCHK(hipEventRecord(h->ev1, stream)); h->timed = true; }
+    if (c.timing) { HIPCHK(hipEventRecord(h->ev1, stream)); h->timed = true; }
     return RL_OK;
 }
 
@@ -1238,11 +1228,12 @@ static int launch_rays(rl_method *h, const float *d_ins, long n, float *d_out, i
 {
     if (n == 0) return RL_OK;
     const rl_map *m = h->map;
-    FanParams f = make_fan(h, 0, 0.0f, 1);
+    const LaunchArgs a = LaunchArgs::of(h);
+    FanParams f = make_fan(h, 0, 0.0f, 1, a.ray_offset);
     long want = (n + WG - 1) / WG;
     long cap = (long)m->n_cu * h->opt.grid_mult;
     int grid = (int)std::max(1L, std::min(want, cap));
-    if (h->timing) HIPCHK(hipEventRecord(h->ev0, stream));
+    if (a.timing) HIPCHK(hipEventRecord(h->ev0, stream));
     int rc;
     if (h->kind == RL_GIANT_LUT) {
         if ((rc = ensure_lut(h, stream))) return rc;
@@ -1265,13 +1256,13 @@ static int launch_rays(rl_method *h, const float *d_ins, long n, float *d_out, i
     } else if (h->opt.variant >= 1 && n <= INT_MAX) {
         // a ray is a pose with one beam at alpha = 0: fan(num_rays = 1, fov = 0) gives exactly
         // (cos, sin) of the heading as direction, and the stream kernel packs 64 rays per block
-        return launch_fan(h, d_ins, (int)n, 0.0f, 1, d_out, d_hits, d_steps, nullptr, stream);
+        return launch_fan(h, FanCall{a, d_ins, (int)n, 0.0f, 1, d_out, d_hits, d_steps, nullptr, stream});
     } else {
         hipLaunchKernelGGL(rm_rays_kernel, dim3(grid), dim3(WG), 0, stream, m->mp, f, d_ins, n,
                            d_out, d_hits, d_steps);
     }
     HIPCHK(hipGetLastError());
-    if (h->timing) { HIPCHK(hipEventRecord(h->ev1, stream)); h->timed = true; }
+    if (a.timing) { HIPCHK(hipEventRecord(h->ev1, stream)); h->timed = true; }
     return RL_OK;
 }
 
@@ -1358,8 +1349,8 @@ extern "C" int rl_calc_range_fan_device(rl_method *h, const float *d_poses, int 
     std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
     rc = set_device(h->map);
     if (rc) return rc;
-    return launch_fan(h, d_poses, n_poses, fov, num_rays, d_outs, d_hits, d_steps, nullptr,
-                      (hipStream_t)hip_stream);
+    return launch_fan(h, FanCall{LaunchArgs::of(h), d_poses, n_poses, fov, num_rays, d_outs, d_hits, d_steps, nullptr,
+                                 (hipStream_t)hip_stream});
 }
 
 extern "C" int rl_calc_range_many_device(rl_method *h, const float *d_ins, float *d_outs, int n,
@@ -1477,8 +1468,10 @@ int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_r
     float *d_out = (outs || !first_crashed)
                        ? (direct_out ? outs : zc ? (float *)(pin + off_out) : (float *)h->outs.p)
                        : nullptr;
+    const FanCall call{LaunchArgs::of(h), d_poses, n_poses, fov, num_rays, d_out, hits ? (int32_t *)h->hits.p : nullptr,
+                       steps ? (uint16_t *)h->steps.p : nullptr, first_crashed ? &cp : nullptr, h->stream};
     if (outs && !zc && !first_crashed && !hits && !steps && h->overlap_min_rays > 0 &&
-        n_rays >= (size_t)h->overlap_min_rays && n_poses >= 4 && !h->timing &&
+        n_rays >= (size_t)h->overlap_min_rays && n_poses >= 4 && !call.timing &&
         (h->kind == RL_RM || h->kind == RL_RM_GPU || h->kind == RL_BRESENHAM)) {
         // big plain scans are bound by the 4 B per ray going back over PCIe: four pose slices, the copy of slice k on
         // a second stream while slice k+1 marches (the march of a 65536-pose batch is ~10 % of the call).  The table
@@ -1487,13 +1480,11 @@ int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_r
         constexpr int S = 4;
         HIPCHK(h->copy_stream.create());
         const int per = (n_poses + S - 1) / S;
-        const uint64_t base_off = h->ray_offset;
         rc = RL_OK;
         for (int k = 0, p0 = 0; p0 < n_poses && rc == RL_OK; ++k, p0 += per) {
             const int np = std::min(per, n_poses - p0);
             const size_t r0 = (size_t)p0 * num_rays, nr = (size_t)np * num_rays;
-            h->ray_offset = base_off + r0;               // noise stays keyed by the global ray id
-            rc = launch_fan(h, d_poses + (size_t)p0 * 3, np, fov, num_rays, d_out + r0, nullptr, nullptr, nullptr, h->stream);
+            rc = launch_fan(h, call.slice(p0, np));
             if (rc) break;
             if (h->slice_ev[k].create(hipEventDisableTiming) != hipSuccess) {
                 rc = fail(RL_ERR_HIP, "hipEventCreate failed");
@@ -1504,7 +1495,6 @@ int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_r
                 hipMemcpyAsync(outs + r0, d_out + r0, nr * sizeof(float), hipMemcpyDeviceToHost, h->copy_stream) != hipSuccess)
                 rc = fail(RL_ERR_HIP, "sliced device-to-host copy failed");
         }
-        h->ray_offset = base_off;
         // (both streams are drained whatever happened; a kernel fault or a copy error that only surfaces here
         //  must not come back as RL_OK with garbage in `outs`)
         const hipError_t e_launch = hipGetLastError();
@@ -1515,10 +1505,7 @@ int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_r
                       hipGetErrorString(e_launch), hipGetErrorString(e_march), hipGetErrorString(e_copy));
         return rc;
     }
-    rc = launch_fan(h, d_poses, n_poses, fov, num_rays, d_out,
-                    hits ? (int32_t *)h->hits.p : nullptr, steps ? (uint16_t *)h->steps.p : nullptr,
-                    first_crashed ? &cp : nullptr, h->stream);
-    if (rc) return rc;
+    if ((rc = launch_fan(h, call))) return rc;
     if (outs && !zc)
         HIPCHK(hipMemcpyAsync(outs, h->outs.p, n_rays * sizeof(float), hipMemcpyDeviceToHost,
                               h->stream));
@@ -1620,7 +1607,7 @@ static PfParams make_pf(const rl_method *h, int n_particles, int n_angles)
 
 #define PF_ANGLES(K, A) hipLaunchKernelGGL((pf_angles_kernel<K, A>), dim3(grid), dim3(PF_WG), 0, stream, m->mp, f, lt, h->cdp, \
                                            h->lp, d_poses, d_angles, n, d_out, d_hits, d_steps)
-static int launch_pf_angles(rl_method *h, int kind, const float *d_poses, int n_particles, const float *d_angles,
+static int launch_pf_angles(rl_method *h, const LaunchArgs &a, int kind, const float *d_poses, int n_particles, const float *d_angles,
                             int n_angles, float *d_out, int32_t *d_hits, uint16_t *d_steps, hipStream_t stream)
 {
     const rl_map *m = h->map;
@@ -1630,7 +1617,7 @@ static int launch_pf_angles(rl_method *h, int kind, const float *d_poses, int n_
     int rc;
     if (kind == PF_LUT && (rc = ensure_lut(h, stream))) return rc;
     if (kind == PF_CDDT && (rc = ensure_cddt(h, stream))) return rc;
-    const FanParams f = make_fan(h, n_particles, 0.0f, n_angles);
+    const FanParams f = make_fan(h, n_particles, 0.0f, n_angles, a.ray_offset);
     const LiteralParams lt = make_literal(m);
     const long n = (long)n_particles * n_angles;
     const int grid = (int)std::max(1L, std::min((n + PF_WG - 1) / PF_WG, (long)m->n_cu * 16));
@@ -1667,7 +1654,7 @@ static int launch_pf_eval(rl_method *h, const float *d_obs, const float *d_range
 
 // the fused call.  RM / RMGPU: pf_weight_kernel, nothing but the weights leaves the kernel.  CDDT / GiantLUT:
 // pf_angles_kernel into the launch context's scratch, then pf_eval_kernel — the same contract, 4 B per ray through HBM
-static int launch_pf_weights(rl_method *h, int kind, const float *d_poses, int n_particles, const float *d_angles,
+static int launch_pf_weights(rl_method *h, const LaunchArgs &a, int kind, const float *d_poses, int n_particles, const float *d_angles,
                              const float *d_obs, int n_angles, double *d_weights, hipStream_t stream)
 {
     int rc;
@@ -1675,13 +1662,13 @@ static int launch_pf_weights(rl_method *h, int kind, const float *d_poses, int n
         LaunchCtx *cx = nullptr;
         if ((rc = acquire_ctx(h, stream, &cx))) return rc;
         if ((rc = cx->pf_r.ensure((size_t)n_particles * n_angles * sizeof(float)))) return rc;
-        if ((rc = launch_pf_angles(h, kind, d_poses, n_particles, d_angles, n_angles, (float *)cx->pf_r.p, nullptr, nullptr, stream)))
+        if ((rc = launch_pf_angles(h, a, kind, d_poses, n_particles, d_angles, n_angles, (float *)cx->pf_r.p, nullptr, nullptr, stream)))
             return rc;
         return launch_pf_eval(h, d_obs, (const float *)cx->pf_r.p, n_angles, n_particles, d_weights, stream);
     }
     const rl_map *m = h->map;
     const PfParams pp = make_pf(h, n_particles, n_angles);
-    const FanParams f = make_fan(h, n_particles, 0.0f, n_angles);
+    const FanParams f = make_fan(h, n_particles, 0.0f, n_angles, a.ray_offset);
     const LiteralParams lt = make_literal(m);
     const int tiles = (n_particles + pp.block - 1) / pp.block;
     const dim3 grid(std::max(1, std::min(tiles, m->n_cu * 8)));
@@ -1725,7 +1712,7 @@ extern "C" int rl_calc_range_repeat_angles_device(rl_method *h, const float *d_i
     std::lock_guard<std::mutex> lk(h->mu);
     std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
     if ((rc = pf_kind_of(h, &kind)) || n_particles == 0 || (rc = set_device(h->map))) return rc;
-    return launch_pf_angles(h, kind, d_ins_p3, n_particles, d_angles, n_angles, d_outs, d_hit_cells_or_null,
+    return launch_pf_angles(h, LaunchArgs::of(h), kind, d_ins_p3, n_particles, d_angles, n_angles, d_outs, d_hit_cells_or_null,
                             d_steps_or_null, (hipStream_t)hip_stream);
 }
 
@@ -1754,7 +1741,7 @@ extern "C" int rl_calc_range_repeat_angles_eval_sensor_model_device(rl_method *h
     if ((rc = pf_kind_of(h, &kind))) return rc;
     if (!h->sensor_w) return fail(RL_ERR_INVALID, "rl_calc_range_repeat_angles_eval_sensor_model_device: no sensor model set (rl_set_sensor_model)");
     if (n_particles == 0 || (rc = set_device(h->map))) return rc;
-    return launch_pf_weights(h, kind, d_ins_p3, n_particles, d_angles, d_obs, n_angles, d_weights, (hipStream_t)hip_stream);
+    return launch_pf_weights(h, LaunchArgs::of(h), kind, d_ins_p3, n_particles, d_angles, d_obs, n_angles, d_weights, (hipStream_t)hip_stream);
 }
 
 // host-pointer forms: staged through the handle's device buffers on its own stream, synchronous
@@ -1793,12 +1780,12 @@ static int pf_host(rl_method *h, const char *fn, const PfHost &a, int n_particle
     if (a.hits && (rc = h->hits.ensure(n * 2 * sizeof(int32_t)))) return rc;
     if (a.steps && (rc = h->steps.ensure(n * sizeof(uint16_t)))) return rc;
     if (a.outs)
-        rc = launch_pf_angles(h, kind, (const float *)h->poses.p, n_particles, (const float *)h->pf_ang.p, n_angles, (float *)h->outs.p,
+        rc = launch_pf_angles(h, LaunchArgs::of(h), kind, (const float *)h->poses.p, n_particles, (const float *)h->pf_ang.p, n_angles, (float *)h->outs.p,
                               a.hits ? (int32_t *)h->hits.p : nullptr, a.steps ? (uint16_t *)h->steps.p : nullptr, s);
     else if (a.ranges)
         rc = launch_pf_eval(h, (const float *)h->pf_obs.p, (const float *)h->outs.p, n_angles, n_particles, (double *)h->pf_w.p, s);
     else
-        rc = launch_pf_weights(h, kind, (const float *)h->poses.p, n_particles, (const float *)h->pf_ang.p,
+        rc = launch_pf_weights(h, LaunchArgs::of(h), kind, (const float *)h->poses.p, n_particles, (const float *)h->pf_ang.p,
                                (const float *)h->pf_obs.p, n_angles, (double *)h->pf_w.p, s);
     if (rc) return rc;
     if (a.outs) HIPCHK(hipMemcpyAsync(a.outs, h->outs.p, n * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -1918,7 +1905,7 @@ extern "C" int rl_pf_reset(rl_pf *f, const double *particles_p3, const double *w
 }
 
 // one update, enqueued on `s`: step `k` of this call (its odometry and observation rows), step f->t + k since the reset
-static int launch_mcl_step(rl_pf *f, int kind, const MclParams &mp, int k, hipStream_t s)
+static int launch_mcl_step(rl_pf *f, const LaunchArgs &a, int kind, const MclParams &mp, int k, hipStream_t s)
 {
     rl_method *h = f->h;
     const uint32_t t = (uint32_t)(f->t + k);
@@ -1926,7 +1913,7 @@ static int launch_mcl_step(rl_pf *f, int kind, const MclParams &mp, int k, hipSt
     double *tot = (double *)f->tot.p, *tot6 = tot + f->NB;
     hipLaunchKernelGGL(mcl_motion_kernel, dim3(grid), dim3(MCL_WG), 0, s, mp, (const double *)f->odom.p + 3 * (size_t)k, t,
                        (const double *)f->cur.p, (double *)f->prop.p, (float *)f->q.p);
-    int rc = launch_pf_weights(h, kind, (const float *)f->q.p, f->P, (const float *)f->ang.p,
+    int rc = launch_pf_weights(h, a, kind, (const float *)f->q.p, f->P, (const float *)f->ang.p,
                                (const float *)f->obs.p + (size_t)k * f->A, f->A, (double *)f->lik.p, s);
     if (rc) return rc;
     hipLaunchKernelGGL(mcl_weight_kernel, dim3((f->NB + MCL_GROUP - 1) / MCL_GROUP), dim3(MCL_WG), 0, s, mp,
@@ -1965,12 +1952,12 @@ extern "C" int rl_pf_run(rl_pf *f, int n_steps, const double *odom_t3, const flo
     HIPCHK(hipMemcpyAsync(f->odom.p, odom_t3, T * 24, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(f->obs.p, obs_tA, T * f->A * 4, hipMemcpyHostToDevice, s));
     MclParams mp{f->P, f->NB, 1.0 / (double)f->P, {f->std[0], f->std[1], f->std[2]}, f->ratio * (double)f->P, f->key};
-    const uint64_t off = h->ray_offset;          // the scans' noise: step t's rays are off + t P A + p A + j
+    LaunchArgs a = LaunchArgs::of(h);            // the scans' noise: step t's rays are off + t P A + p A + j
+    const uint64_t off = a.ray_offset;
     for (int k = 0; k < n_steps && !rc; ++k) {
-        h->ray_offset = off + (uint64_t)(f->t + k) * (uint64_t)f->P * (uint64_t)f->A;
-        rc = launch_mcl_step(f, kind, mp, k, s);
+        a.ray_offset = off + (uint64_t)(f->t + k) * (uint64_t)f->P * (uint64_t)f->A;
+        rc = launch_mcl_step(f, a, kind, mp, k, s);
     }
-    h->ray_offset = off;
     if (rc) {
         (void)hipStreamSynchronize(s);
         f->ready = false;                         // part of the steps may have run: the state is no step's; reset again
@@ -2049,9 +2036,8 @@ int check_groups_args(int n_groups, int group)
 
 // d_first[g] <- first crashed pose of group g, or -(group+1) when none.  Ray-marching methods fuse the
 // test into the march kernel; the others scan into d_ranges (required then) and run one pass over the ranges.
-int crash_groups_device(rl_method *h, const float *d_poses, int n_groups, int group, float fov,
-                               int num_rays, const double *d_edge, double thresh, int *d_first,
-                               float *d_ranges, hipStream_t stream)
+int crash_groups_device(rl_method *h, const LaunchArgs &a, const float *d_poses, int n_groups, int group, float fov,
+                        int num_rays, const double *d_edge, double thresh, int *d_first, float *d_ranges, hipStream_t stream)
 {
     const int n_poses = n_groups * group;
     // the kernels mark crashed POSES (one word each, no contended atomics); groups are reduced after
@@ -2059,14 +2045,12 @@ int crash_groups_device(rl_method *h, const float *d_poses, int n_groups, int gr
     int mark;
     int *d_pose_first = nullptr;
     if ((rc = pose_marks(h, n_poses, stream, mark, &d_pose_first))) return rc;
-    if (h->kind == RL_RM || h->kind == RL_RM_GPU) {
-        CrashParams cp{d_edge, thresh, d_pose_first, 0, mark};
-        if ((rc = launch_fan(h, d_poses, n_poses, fov, num_rays, d_ranges, nullptr, nullptr, &cp, stream)))
-            return rc;
-    } else {
-        if (!d_ranges) return fail(RL_ERR_INVALID, "this range method needs a ranges buffer for the crash test");
-        if ((rc = launch_fan(h, d_poses, n_poses, fov, num_rays, d_ranges, nullptr, nullptr, nullptr, stream)))
-            return rc;
+    const CrashParams cp{d_edge, thresh, d_pose_first, 0, mark};
+    const bool fused = h->kind == RL_RM || h->kind == RL_RM_GPU;
+    if (!fused && !d_ranges) return fail(RL_ERR_INVALID, "this range method needs a ranges buffer for the crash test");
+    if ((rc = launch_fan(h, FanCall{a, d_poses, n_poses, fov, num_rays, d_ranges, nullptr, nullptr, fused ? &cp : nullptr, stream})))
+        return rc;
+    if (!fused) {
         const int grid = (int)std::max(1L, std::min(((long)n_poses + 3) / 4, (long)h->map->n_cu * 8));
         hipLaunchKernelGGL(crash_groups_kernel, dim3(grid), dim3(256), 0, stream, d_ranges, d_edge,
                            thresh, n_poses, num_rays, 0, mark, d_pose_first);
@@ -2093,7 +2077,7 @@ extern "C" int rl_check_collision_groups_device(rl_method *h, const float *d_pos
     std::lock_guard<std::mutex> lk(h->mu);
     std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
     if ((rc = set_device(h->map))) return rc;
-    return crash_groups_device(h, d_poses, n_groups, group, fov, num_rays, d_edge, crash_thresh,
+    return crash_groups_device(h, LaunchArgs::of(h), d_poses, n_groups, group, fov, num_rays, d_edge, crash_thresh,
                                d_first_crashed, d_ranges_or_null, (hipStream_t)hip_stream);
 }
 

@@ -2,12 +2,13 @@
 // DevPtr, Pinned, Stream, Event), the handles behind include/scanlib.h's opaque pointers, the error slot, and the few
 // internal entry points one unit calls in another.
 //   abi_map.hip    errors, check_device, the caller's pinned host blocks, rl_map_* (EDT, bit map, edge list, stamps)
-//   abi_fan.hip    rl_method_*: options, derived tables, the launch planner's C ABI, every fan / ray launch, the
+//   abi_fan.hip    rl_method_*: options, derived tables, the launch planner's C ABI, every fan / ray launch (told its
+//                  noise offset, store mode and timing by LaunchArgs / FanCall below, not by the handle), the
 //                  device-pointer entry points, the single-device host-pointer paths, the fused crash test; the
 //                  particle-filter weights (repeat-angle scans, sensor model) and localisation (rl_pf_*)
 //   abi_multi.hip  the host-pointer entry points and their multi-device forms (run_blocks below: one block per device)
 //   abi_car.hip    roll-out generator, FollowGap, the policy network, batched races and the race scan; the closed-loop
-//                  session (loop_args, Loop: the checks, locks, handle override and scan-then-consume step of every
+//                  session (loop_args, Loop: the checks, locks, launch arguments and scan-then-consume step of every
 //                  closed loop) and its three users: FollowGap / policy / race roll-outs (drive_loop), the driving
 //                  environment (rl_env_*), the MCTS planner and its closed-loop drive (rl_mcts_*); 16-bit ranges,
 //                  probes, the car-outline table and cells
@@ -519,17 +520,44 @@ void host_sincosf(float x, float &s, float &c);      // host twin of scan::det_s
 // abi_fan.hip, called from abi_multi.hip / abi_car.hip
 // ------------------------------------------------------------------------------
 int check_fan_args(const rl_method *h, int n_poses, float fov, int num_rays);
-FanParams make_fan(const rl_method *h, int n_poses, float fov, int num_rays);   // the handle's range, coefficient, noise
+FanParams make_fan(const rl_method *h, int n_poses, float fov, int num_rays, uint64_t ray_offset);   // + the handle's range, coefficient, noise
 LiteralParams make_literal(const rl_map *m);                                     // variant 3's per-map constants
 namespace scan { struct CrashParams; }
-// one fan launch sequence on `stream` as the planner picks it (noise keyed by h->ray_offset; the caller holds h->mu and
-// the map's tables_mu and has checked the arguments)
-int launch_fan(rl_method *h, const float *d_poses, int n_poses, float fov, int num_rays, float *d_out, int32_t *d_hits,
-               uint16_t *d_steps, const CrashParams *crash, hipStream_t stream);
+
+// What a launch is told instead of reading it off the handle.  rl_set_noise and rl_method_set_option are the only writers
+// of h->ray_offset, h->nt_store and h->timing; a path that needs another value for one launch (a pose slice, a closed
+// loop's tick, a filter step) says so here.  The events and h->timed, last_plan, last_grid, last_dbg stay on the handle:
+// they are results.
+struct LaunchArgs {
+    uint64_t ray_offset;         // global id of the launch's first ray (keys its noise)
+    bool plain_store;            // ranges leave the stream kernels with plain stores: a consumer kernel reads them next
+    int timing;                  // as the option: 1 events around the launch sequence, 2 around the march kernel only
+    static LaunchArgs of(const rl_method *h) { return {h->ray_offset, !h->nt_store, h->timing}; }   // the caller's settings
+};
+
+// one fan launch: launch_fan's arguments
+struct FanCall : LaunchArgs {
+    const float *d_poses;
+    int n_poses;
+    float fov;
+    int num_rays;
+    float *d_out;
+    int32_t *d_hits;
+    uint16_t *d_steps;
+    const CrashParams *crash;
+    hipStream_t stream;
+    // the call for poses [p0, p0 + np): every pointer and the noise offset move on by the poses (rays) before p0.  A
+    // per-pose-mark crash test marks through *marks, the slice's own copy with the mark array shifted by p0 (it has to
+    // live as long as the slice; not needed without a crash test)
+    FanCall slice(int p0, int np, CrashParams *marks = nullptr) const;
+};
+// one fan launch sequence as the planner picks it (the caller holds h->mu and the map's tables_mu and has checked the
+// arguments)
+int launch_fan(rl_method *h, const FanCall &c);
 int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_rays, float *outs, int32_t *hits,
              uint16_t *steps, const double *edge, double crash_thresh, int *first_crashed);
-int crash_groups_device(rl_method *h, const float *d_poses, int n_groups, int group, float fov, int num_rays,
-                        const double *d_edge, double thresh, int *d_first, float *d_ranges, hipStream_t stream);
+int crash_groups_device(rl_method *h, const LaunchArgs &a, const float *d_poses, int n_groups, int group, float fov,
+                        int num_rays, const double *d_edge, double thresh, int *d_first, float *d_ranges, hipStream_t stream);
 int upload_edge(rl_method *h, const double *edge, int num_rays);
 int rays_host(rl_method *h, const float *ins, float *outs, int n);
 int check_groups_args(int n_groups, int group);     // the grouped crash tests' first two checks

@@ -313,7 +313,7 @@ extern "C" int rl_check_collision_groups(rl_method *h, const float *poses, int n
         (rc = upload_edge(h, edge, num_rays)) || (rc = h->flag.ensure((size_t)n_groups * 4)))
         return rc;
     HIPCHK(hipMemcpyAsync(h->poses.p, poses, (size_t)n_poses * 12, hipMemcpyHostToDevice, h->stream));
-    rc = crash_groups_device(h, (const float *)h->poses.p, n_groups, group, fov, num_rays,
+    rc = crash_groups_device(h, LaunchArgs::of(h), (const float *)h->poses.p, n_groups, group, fov, num_rays,
                              (const double *)h->edge.p, crash_thresh, (int *)h->flag.p,
                              (float *)h->outs.p, h->stream);
     if (rc) return rc;

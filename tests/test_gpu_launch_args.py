@@ -1,0 +1,241 @@
+"""What a launch is told instead of reading it off the method handle (csrc/abi_internal.h LaunchArgs / FanCall): the noise
+offset of a pose slice, plain stores of a closed loop, the timing events of a sliced launch.  The handle's ``ray_offset``,
+``nt_store`` and ``timing`` are written by ``set_noise`` and ``set_option`` only, so every looped path leaves a plain fan at
+the caller's offset, and the options, as it found them.
+
+The suite's smallest maze (56^2 cells, range 60), 65 beams (the smallest fan that spans two 64-lane rows), RMGPU with noise
+std 1, a seed whose high word matters and an offset whose ids straddle 2^32."""
+import numpy as np
+import pytest
+
+from oracle import np_statement as N
+from test_gpu_drive import _edge, _same_bits, _starts
+from test_gpu_noise import SEED_HI
+from pyracecarsimulator_amd import DriveEnv, ParticleFilter, maps, range_libc
+from pyracecarsimulator_amd import racecar as RC
+from pyracecarsimulator_amd.followgap import PyFollowGap
+from pyracecarsimulator_amd.mcts import MCTSPlanner
+
+import mcl_statement as MS
+
+pytestmark = pytest.mark.gpu
+
+FOV, B, MRX, THRESH = 4.71, 65, 60, 0.001
+OFFSET = 2 ** 32 - 300
+SLICE_LOG2 = 8                                   # 256 rays: 3 poses of 65 beams per slice
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _gpu(need_gpu):
+    yield
+
+
+@pytest.fixture(scope="module")
+def world(oracle_mod):
+    g = maps.make_maze(56, cell=14, wall=2, p=0.5, seed=3, origin=(2.0, -1.5, -0.3))
+    om = oracle_mod.OracleMap.from_gridmap(g, MRX)
+    return g, om, range_libc.PyOMap(g)
+
+
+@pytest.fixture()
+def method(world):
+    m = range_libc.PyRayMarchingGPU(world[2], MRX)
+    m.set_noise(1.0, SEED_HI, OFFSET)
+    yield m
+    m.close()
+
+
+def _host_fan(m, poses):
+    out = np.full(len(poses) * B, -7.0, np.float32)
+    m.calc_range_fan(poses, out, FOV, B)
+    return out
+
+
+def test_partial_last_slice_on_a_callers_stream(world, method):
+    """11 poses in slices of 3 (the last one short) on a non-default stream: ranges, and with the diagnostics asked for
+    hit cells and step counts too, carry the bits of the unsliced launch — every output pointer and the noise offset
+    move on by the rays before the slice."""
+    import torch
+    g, om, _ = world
+    m = method
+    poses = maps.sample_free_poses(g, 11, 4, 2.0, om.dt)
+    n = len(poses) * B
+    d_poses = torch.from_numpy(np.ascontiguousarray(poses)).cuda()
+    stream = torch.cuda.Stream()
+
+    def scan(aux):
+        d_out = torch.full((n,), -7.0, dtype=torch.float32, device="cuda")
+        d_hits = torch.full((n, 2), -7, dtype=torch.int32, device="cuda")
+        d_steps = torch.full((n,), 7, dtype=torch.int16, device="cuda")
+        torch.cuda.synchronize()
+        m.calc_range_fan_device(d_poses.data_ptr(), len(poses), FOV, B, d_out.data_ptr(),
+                                d_hits.data_ptr() if aux else 0, d_steps.data_ptr() if aux else 0, stream=stream.cuda_stream)
+        stream.synchronize()
+        return d_out.cpu().numpy(), d_hits.cpu().numpy(), d_steps.cpu().numpy()
+
+    for aux in (False, True):
+        m.set_option("slice_log2", 30)
+        assert m.plan_fan(len(poses), B, aux=aux)["slices"] <= 1
+        whole = scan(aux)
+        m.set_option("slice_log2", SLICE_LOG2)
+        pl = m.plan_fan(len(poses), B, aux=aux)
+        assert pl["slices"] == 4 and pl["slice_poses"] == 3, pl
+        sliced = scan(aux)
+        for w, s, what in zip(whole, sliced, ("ranges", "hit cells", "steps")):
+            assert _same_bits(w, s), (aux, what, np.flatnonzero((w != s).reshape(len(w), -1).any(1))[:8])
+        assert not (whole[0] == -7.0).any()
+        if aux:
+            assert (whole[2] != 7).any() and (whole[1] != -7).any()
+    # the noise is on, and keyed by the global ray id: the clean scan differs nearly everywhere
+    m.set_noise(0.0, SEED_HI, OFFSET)
+    assert float(np.mean(scan(False)[0] != whole[0])) > 0.9
+
+
+def _crash_case(oracle_mod, g, om, std):
+    """12 poses in groups of 3 (two from the middle of a corridor, one from anywhere free) and the first-crash index of
+    every group as the CPU states it: the oracle's clean ranges plus std times the reference normal of the ray's global
+    id.  No pose of the case is within 7 mm of the crash threshold; the device's noise is within 1e-6 of the reference."""
+    far = maps.sample_free_poses(g, 8, 12, 5.0, om.dt)
+    near = maps.sample_free_poses(g, 4, 13, 0.0, om.dt)
+    poses = np.ascontiguousarray(np.concatenate([np.concatenate([far[2 * q:2 * q + 2], near[q:q + 1]]) for q in range(4)]))
+    edge = RC.edge_distances(B, -FOV / 2, FOV / B, 0.275, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
+    clean = om.rm_fan(poses, FOV, B, step_coeff=1.0)[0]
+    noisy = (clean.astype(np.float64) + std * N.gauss_noise_ref(SEED_HI, N.fan_ray_ids(OFFSET, clean.size, 1))).astype(np.float32)
+    want = [oracle_mod.is_crashed(noisy[q * 3 * B:(q + 1) * 3 * B], B, 3, edge, THRESH) for q in range(4)]
+    return poses, edge, want
+
+
+@pytest.mark.parametrize("std", [1.0, 0.01])
+def test_grouped_crash_test_under_slicing(oracle_mod, world, method, std):
+    """check_collision_groups, 12 poses in groups of 3, with the handle cut into 3-pose slices: first-crash indices and
+    ranges are the unsliced call's, and the indices the oracle's isCrashed over those ranges.  At std 1 every group
+    crashes at once; at std 0.01 the poses decide (the CPU's statement of the case: groups of the later slices crash, and
+    not at their first pose).  (A fused crash test is planned whole whatever slice_log2 says — only the upstream-literal
+    mode cuts one, test_gpu_noise / test_gpu_parity's three-slice cases — so this pins the equality, not the cut.)"""
+    g, om, _ = world
+    m = method
+    poses, edge, want = _crash_case(oracle_mod, g, om, std)
+    print("std", std, "CPU first-crash per group", want)
+    assert any(w >= 0 for w in want[2:]), want
+    if std < 1.0:
+        assert any(w > 0 for w in want[2:]), want
+    m.set_noise(std, SEED_HI, OFFSET)
+    got = {}
+    for sl in (30, SLICE_LOG2):
+        m.set_option("slice_log2", sl)
+        assert (m.plan_fan(len(poses), B)["slices"] == 4) == (sl == SLICE_LOG2)
+        r = np.full(len(poses) * B, -7.0, np.float32)
+        first = m.check_collision_groups(poses, 3, FOV, B, edge, THRESH, ranges=r)
+        fan = _host_fan(m, poses)
+        assert _same_bits(r, fan), sl
+        assert first.tolist() == [oracle_mod.is_crashed(r[q * 3 * B:(q + 1) * 3 * B], B, 3, edge, THRESH) for q in range(4)], sl
+        got[sl] = (first, r)
+    assert got[30][0].tolist() == got[SLICE_LOG2][0].tolist() and _same_bits(got[30][1], got[SLICE_LOG2][1])
+    assert got[30][0].tolist() == want
+    print("std", std, "device first-crash per group", got[30][0].tolist())
+
+
+@pytest.mark.parametrize("timing", [1, 2])
+def test_timing_is_an_argument_of_the_launch(world, method, timing):
+    """A sliced launch records one event pair around its slices and leaves the option alone; the unsliced launch after
+    it is timed as well."""
+    g, om, _ = world
+    m = method
+    poses = maps.sample_free_poses(g, 11, 4, 2.0, om.dt)
+    m.set_option("slice_log2", 30)
+    whole = _host_fan(m, poses)
+    m.set_option("timing", timing)
+    m.set_option("slice_log2", SLICE_LOG2)
+    assert m.plan_fan(len(poses), B)["slices"] == 4
+    sliced = _host_fan(m, poses)
+    assert m.get_info("timing") == timing
+    ms_sliced = m.last_kernel_ms()
+    assert ms_sliced > 0.0
+    assert _same_bits(sliced, whole)
+    m.set_option("slice_log2", 30)
+    again = _host_fan(m, poses)
+    assert m.get_info("timing") == timing and m.get_info("slice_log2") == 30
+    ms_whole = m.last_kernel_ms()
+    assert ms_whole > 0.0
+    assert _same_bits(again, whole)
+    print("timing", timing, "sliced %.4f ms, whole %.4f ms" % (ms_sliced, ms_whole))
+
+
+def test_handle_reads_the_same_after_every_looped_path(world, method):
+    """One method, noise set once.  After a sliced scan, the four-slice copy / march overlap, two filter steps, a
+    FollowGap roll-out, an env reset + step and a planner reset + run(1), a plain 5-pose fan still has the bits it had
+    before them and nt_store, timing and slice_log2 read as set; each path's own outputs repeat on a second round."""
+    g, om, _ = world
+    m = method
+    poses = maps.sample_free_poses(g, 5, 6, 2.0, om.dt)
+    fan0 = _host_fan(m, poses)
+    options = {k: m.get_info(k) for k in ("nt_store", "timing", "slice_log2")}
+    assert options == {"nt_store": 1, "timing": 0, "slice_log2": 30}
+    edge = _edge(B)
+    cars = RC.CarBatch()
+    states, speeds = _starts(g, om.dt, 2, 21, 4.0, speed_hi=3.0)
+    fg = PyFollowGap(10, 15.0, RC.DEFAULT_CAR["max_steer_ang"], 0.004)
+    parts, angles, odom, obs, table = MS.localisation_case(g, om.dt, MRX, FOV, 8, 5, 2)
+    m.set_sensor_model(table)
+    actions = np.array([[2.0, 0.1], [1.0, -0.2]], np.float32)
+    seeds = np.array([SEED_HI, 12345], np.uint64)
+
+    def sliced():
+        m.set_option("slice_log2", SLICE_LOG2)
+        assert m.plan_fan(len(poses), B)["slices"] == 2
+        out = _host_fan(m, poses)
+        m.set_option("slice_log2", 30)
+        return [out]
+
+    def overlap():
+        saved = {k: m.get_info(k) for k in ("overlap_min_rays", "direct_max_rays", "pinned_max_rays")}
+        for k, v in (("overlap_min_rays", 1), ("direct_max_rays", 0), ("pinned_max_rays", 0)):
+            m.set_option(k, v)
+        out = _host_fan(m, poses)
+        for k, v in saved.items():
+            m.set_option(k, v)
+        return [out]
+
+    def pf_run():
+        pf = ParticleFilter(m, angles, 8, motion_std=(0.02, 0.02, 0.01), resample_ratio=2.0)
+        pf.reset(parts, seed=3)
+        out = list(pf.run_raw(odom, obs))
+        rd = pf.read()
+        return out + [rd[k] for k in sorted(rd)]
+
+    def rollout():
+        return list(cars.drive_followgap(m, fg, states, 3, speeds, FOV, B, edge, THRESH, trace=True))
+
+    def env():
+        e = DriveEnv(m, states, 2, B, FOV, edge, THRESH, auto_reset=False, car=cars)
+        o0 = e.reset(seed=3, start_index=np.arange(2))
+        o1, rew, done = e.step(actions)
+        return [o0.copy(), o1.copy(), rew.copy(), done.copy(), e.read()["states"]]
+
+    def planner():
+        pl = MCTSPlanner(cars, m, 2, 2, FOV, B, edge, THRESH, source="fg", followgap=fg, rollout_steps=3, action_every=1)
+        pl.reset(states, np.array([0.1, -0.1]), seeds)
+        pl.run(1)
+        out = list(pl.best())
+        for k in range(2):
+            t = pl.read_tree(k)
+            out += [t[f] for f in sorted(t)]
+        return out
+
+    rounds = []
+    for _ in range(2):
+        outs = {}
+        for path in (sliced, overlap, pf_run, rollout, env, planner):
+            outs[path.__name__] = [np.array(x) for x in path()]
+            assert {k: m.get_info(k) for k in options} == options, path.__name__
+            assert _same_bits(_host_fan(m, poses), fan0), path.__name__
+        rounds.append(outs)
+    r0 = rounds[0]
+    print("roll-out first crash", r0["rollout"][0].tolist(), "| env done", r0["env"][3].tolist(), "| planner best", r0["planner"][0].tolist(),
+          "visits", r0["planner"][1].tolist(), "| filter neff", r0["pf_run"][1].tolist())
+    assert np.isfinite(r0["env"][0]).all() and np.isfinite(r0["pf_run"][0]).all() and (r0["planner"][2] == 2).all()
+    for name, first in rounds[0].items():
+        for i, (a, b) in enumerate(zip(first, rounds[1][name])):
+            assert a.shape == b.shape and _same_bits(a, b), (name, i)
+    # the sliced and the overlapped scans are the plain fan itself
+    assert _same_bits(rounds[0]["sliced"][0], fan0) and _same_bits(rounds[0]["overlap"][0], fan0)
