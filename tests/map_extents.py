@@ -1,0 +1,201 @@
+"""The maps tests/test_gpu_map_extents.py runs the map and range kernels on, at rl_map_create's limit of 16384 cells per
+side, as plain data and NumPy: no library call.  tests/test_map_extents_host.py checks with the oracle alone that these
+inputs do what the GPU tests take them to do."""
+import math
+
+import numpy as np
+
+RES = 0.05
+ORIGIN = (-3.0, 2.0, 0.3)                     # a non-zero origin with a yaw
+FOV, BEAMS = 4.71, 1081
+MRX_NEAR, MRX_FAR = 300, 17000                # nothing reaches past 300 cells / rays run the length of the corridor
+# The ray-marching methods pad their step map by the range window on every side and address it in 32 bits: a window
+# of 17000 cells on a 16384-cell map is RL_ERR_UNSUPPORTED (abi_fan.hip ensure_step_map; step_map_cells below).  They
+# run at the largest round window that fits; rays of 11 468 cells still cross 2^13.
+MRX_RM_FAR = 12000
+N_POSES = 600
+MAP_SIDE_MAX = 16384                          # rl_map_create: rows, cols in [1, 16384]
+
+# name: (rows, cols, kind).  "corridor": border wall, about 40 partial cross-walls and a free lane down the long axis;
+# "sparse": random cells (the maps one cell wide have no room for walls)
+SHAPES = {
+    "wide": (24, 16384, "corridor"),          # edt_rows at 64 KiB, CDDT wmax 16385 (the opt-in branch), tiles_x 2048, bit-map stride 512
+    "tall": (16384, 24, "corridor"),          # edt_cols seg_len 1024, gridDim.y 16384, edge rows up to 16383 << 16
+    "row": (1, 16384, "sparse"),              # edt_cols with 15 empty segments
+    "column": (16384, 1, "sparse"),
+    "lds48k": (20, 12288, "corridor"),        # edt_rows_kernel's dynamic LDS: 48 KiB exactly ...
+    "lds48k+": (20, 12289, "corridor"),       # ... and four bytes more
+    "cddt6100": (8, 6100, "corridor"),        # cddt_project_kernel's lds_fill at theta_disc 112: 48 808 B ...
+    "cddt6200": (8, 6200, "corridor"),        # ... and 49 608 B
+    "odd": (40, 8193, "corridor"),            # one column past 8192; no multiple of the 8-cell tile or the 32-cell word
+    "lut_wide": (12, 16384, "corridor"),      # GiantLUT, theta_disc 30
+    "lut_tall": (16384, 12, "corridor"),
+}
+EDT_MAPS = ("wide", "tall", "row", "column", "lds48k", "lds48k+", "cddt6100", "cddt6200", "odd", "lut_wide", "lut_tall")
+RAY_MAPS = ("wide", "tall", "odd")
+THIN_MAPS = ("row", "column")                 # one tile row / one tile column: the stripe binning's smallest map
+CDDT_LONG = ("wide", "tall")
+CDDT_PAIR = ("cddt6100", "cddt6200")
+LUT_MAPS = ("lut_wide", "lut_tall")
+CDDT_THETA = (112, 113)
+LUT_THETA = 30
+N_CROSS_WALLS = 40
+SPARSE_DENSE, SPARSE_LONE = 4096, (9000, 16000)
+
+# the map the CDDT build must refuse (wmax > 19200): every 32nd column occupied keeps the row pass of the EDT short
+REFUSED = (10400, 16384)
+
+CDDT_EPS = 1e-5                               # cddt_kernels.h
+LDS_DEFAULT = 48 * 1024                       # dynamic LDS a launch gets without hipFuncSetAttribute
+CDDT_LDS_MAX = 150 * 1024                     # abi_fan.hip ensure_cddt: above it RL_ERR_UNSUPPORTED
+
+
+def long_axis(name):
+    """1 when the long axis runs along the columns (x in the grid), 0 along the rows."""
+    rows, cols, _ = SHAPES[name]
+    return 1 if cols >= rows else 0
+
+
+def lane(short):
+    """(first, last) short-axis index of the free lane of a corridor `short` cells across."""
+    half = 2 if short >= 16 else 1
+    return short // 2 - half, short // 2 + half - 1
+
+
+def _corridor(short, length, rng):
+    occ = np.zeros((short, length), np.uint8)
+    occ[0, :] = occ[-1, :] = 1
+    occ[:, 0] = occ[:, -1] = 1
+    lo, hi = lane(short)
+    for c in np.sort(rng.choice(np.arange(8, length - 8), N_CROSS_WALLS, replace=False)):
+        thick = int(rng.integers(1, 3))
+        if rng.random() < 0.5:
+            occ[1:int(rng.integers(2, lo + 1)), c:c + thick] = 1          # from the first side, short of the lane
+        else:
+            occ[int(rng.integers(hi + 1, short - 1)):short - 1, c:c + thick] = 1
+    return occ
+
+
+def occupancy(name):
+    """The seeded occupancy (rows, cols) uint8 of SHAPES[name]."""
+    rows, cols, kind = SHAPES[name]
+    rng = np.random.default_rng(sorted(SHAPES).index(name) + 100)
+    if kind == "sparse":
+        # random cells in the first quarter, then two lone cells: the cells between them have their nearest occupied
+        # cell up to six of edt_cols_kernel's 16 row segments away, on either side, the last segment included
+        line = np.zeros(max(rows, cols), np.uint8)
+        line[:SPARSE_DENSE] = rng.random(SPARSE_DENSE) < 0.004
+        line[list(SPARSE_LONE)] = 1
+        return np.ascontiguousarray(line.reshape(rows, cols))
+    occ = _corridor(min(rows, cols), max(rows, cols), rng)
+    return np.ascontiguousarray(occ if cols >= rows else occ.T)
+
+
+def refused_occupancy():
+    occ = np.zeros(REFUSED, np.uint8)
+    occ[:, ::32] = 1
+    return occ
+
+
+def far_block(occ):
+    """A copy of occ with a block of cells at the far end of the long axis flipped (the input of PyOMap.update)."""
+    out = occ.copy()
+    rows, cols = occ.shape
+    if cols >= rows:
+        out[:, cols - 40:cols - 3] ^= 1
+    else:
+        out[rows - 40:rows - 3, :] ^= 1
+    return out
+
+
+def far_stamp(occ):
+    """Flat cell indices within 100 of rows * cols - 1 (the input of PyOMap.stamp_cells), two of them past the end."""
+    n = occ.size
+    idx = n - 1 - np.array([0, 1, 2, 7, 31, 32, 33, 64, 99], np.int64)
+    return np.concatenate([idx[idx >= 0], [n, n + 5]]).astype(np.int64)
+
+
+def long_wall(occ):
+    """A copy of occ with a new wall along most of the long axis, on the lane's first line."""
+    out = occ.copy()
+    rows, cols = occ.shape
+    k = lane(min(rows, cols))[0]
+    if cols >= rows:
+        out[k, 50:cols - 50] = 1
+    else:
+        out[50:rows - 50, k] = 1
+    return out
+
+
+def step_map_cells(rows, cols, mrx):
+    """abi_fan.hip ensure_step_map restated: cells of the row-major step map of a ray-marching handle, the EDT padded by
+    ceil(max_range) + 2 cells on every side, rows of a multiple of 32 cells.  The march's 32-bit byte address needs it
+    below 2^30 (and the row pitch below 2^23)."""
+    pad = int(math.ceil(mrx)) + 2
+    return (rows + 2 * pad) * ((cols + 2 * pad + 31) & ~31)
+
+
+def to_world(gx, gy, heading=0.0, resolution=RES, origin=ORIGIN):
+    """World poses float32 (n, 3) of grid points (gx, gy) with grid headings `heading` (maps.sample_free_poses' map)."""
+    gx, gy = np.atleast_1d(np.asarray(gx, np.float64)), np.atleast_1d(np.asarray(gy, np.float64))
+    c, s = math.cos(origin[2]), math.sin(origin[2])
+    xw = origin[0] + (c * gx - s * gy) * resolution
+    yw = origin[1] + (s * gx + c * gy) * resolution
+    th = np.broadcast_to(np.asarray(heading, np.float64) + origin[2], gx.shape)
+    return np.stack([xw, yw, th], -1).astype(np.float32)
+
+
+def special_poses(name):
+    """Hand-made poses: NaN, far outside, -1 < gx < 0, the last cell of the long axis (inside the border wall), the last
+    free cell before it, and seven poses in the lane whose beam 540 looks straight down the long axis (from both ends,
+    from the middle both ways, and 0.7 of the length from either end), so that rays run the whole length."""
+    rows, cols, _ = SHAPES[name]
+    along = long_axis(name)
+    short, length = (rows, cols) if along else (cols, rows)
+    lo, hi = lane(short)
+    lo = max(lo, 0)
+    mid = 0.5 * (lo + hi + 1)
+
+    def at(u, v, heading):                      # u along the long axis, v across it
+        return to_world(u, v, heading) if along else to_world(v, u, heading)
+
+    ahead = 0.0 if along else math.pi / 2.0     # grid heading of "towards the far end"
+    beam540 = FOV / 2.0 - 540.0 * FOV / BEAMS   # heading - this = direction of beam 540
+    out = [np.array([[np.nan, 0.0, 0.0]], np.float32), np.array([[1e6, 1e6, 1.0]], np.float32),
+           to_world(-0.3, 0.5 * rows, 0.2),
+           at(length - 0.5, mid, 1.0), at(length - 1.5, mid, ahead + math.pi + beam540),
+           at(1.5, mid, ahead + beam540), at(length - 1.5, mid + 0.25, ahead + math.pi + beam540),
+           at(0.5 * length, mid, ahead + beam540), at(0.5 * length, mid - 0.25, ahead + math.pi + beam540),
+           at(2.25, lo + 0.5, ahead + beam540),
+           at(0.3 * length, mid, ahead + beam540), at(0.7 * length, mid + 0.25, ahead + math.pi + beam540)]
+    return np.concatenate(out).astype(np.float32)
+
+
+def poses(gmap, dt, name, n=N_POSES, seed=7):
+    """n seeded free poses of the map and the special poses after them."""
+    from pyracecarsimulator_amd import maps
+    return np.ascontiguousarray(np.concatenate([maps.sample_free_poses(gmap, n, seed, dt=dt), special_poses(name)]))
+
+
+def ray_rows(p, n_rays, seed):
+    """(x, y, theta) rows of the 2-argument form: poses drawn from p with headings in (-10, 10)."""
+    rng = np.random.default_rng(seed)
+    ins = p[rng.integers(0, len(p), n_rays)].copy()
+    ins[:, 2] = rng.uniform(-10.0, 10.0, n_rays).astype(np.float32)
+    return np.ascontiguousarray(ins)
+
+
+def cddt_wmax(rows, cols, theta_disc, sincosf):
+    """abi_fan.hip ensure_cddt restated: the widest bin's bucket count, max_a ceil(|W sin a| + |H cos a| - 1e-5) + 1 in
+    float32 over the (theta_disc + 1) / 2 table bins; `sincosf` the oracle's det_sincosf."""
+    nb = (theta_disc + 1) // 2
+    ang = (np.arange(nb, dtype=np.float32) * (np.float32(6.283185307179586) / np.float32(theta_disc))).astype(np.float32)
+    s, c = sincosf(ang)
+    W, H = np.float32(cols), np.float32(rows)
+    span = (np.abs(W * s.astype(np.float32)) + np.abs(H * c.astype(np.float32))).astype(np.float32)
+    return int(np.ceil((span - np.float32(CDDT_EPS)).astype(np.float32)).max()) + 1
+
+
+def cddt_lds_fill(rows, cols, theta_disc, sincosf):
+    """Bytes of dynamic LDS of cddt_project_kernel<true>: two uint32 per bucket of the widest bin."""
+    return cddt_wmax(rows, cols, theta_disc, sincosf) * 2 * 4
