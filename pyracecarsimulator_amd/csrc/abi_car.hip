@@ -20,10 +20,16 @@ struct rl_car {
     int device = 0;
     CarParams P{};
     Stream stream;
-    DevBuf states, actions, poses, states_out, vel, ranges, edge, first;
-    DevBuf speeds, steer0, tr_steers, tr_poses, tr_states;     // rl_car_drive_followgap, rl_car_drive_policy
-    DevBuf mlp;                                                // rl_car_drive_policy: the network's steers of a tick
-    DevBuf o_cars, o_cells, o_counts;                          // rl_car_outline_cells
+    // per-call staging, counted in scalars: 11 doubles a car state, 2 an action, 3 floats a pose
+    DevPtr<double> states, actions, states_out, vel, edge;
+    DevPtr<float> poses, ranges;
+    DevPtr<int> first;
+    DevPtr<double> speeds, tr_states;                          // rl_car_drive_followgap, rl_car_drive_policy
+    DevPtr<float> steer0, tr_steers, tr_poses;
+    DevPtr<float> mlp;                                         // rl_car_drive_policy: the network's steers of a tick
+    DevPtr<double> o_cars;                                     // rl_car_outline_cells
+    DevPtr<int32_t> o_cells;
+    DevPtr<int> o_counts;
     std::mutex mu;
 };
 
@@ -89,25 +95,24 @@ static int check_rollout_args(int R, int n_steps, int every)
     return RL_OK;
 }
 
-static int car_rollout_device(rl_car *c, const double *states_in, const double *actions, int R,
-                              int n_steps, int every, double dt, bool want_states, bool want_vel)
+// the roll-outs of hc's call (on c's stream): states and actions up, rollout_kernel into c->poses (and, when wanted,
+// c->states_out and c->vel)
+static int car_rollout_device(rl_car *c, HostCall &hc, const double *states_in, const double *actions, int R, int n_steps,
+                              int every, double dt, bool want_states, bool want_vel)
 {
     int rc = check_rollout_args(R, n_steps, every);
     if (rc) return rc;
     if ((long)R * n_steps > INT_MAX / 4) return fail(RL_ERR_INVALID, "too many roll-out poses");
     HIPCHK(hipSetDevice(c->device));
     if (R == 0) return RL_OK;
-    const int n_act = (n_steps + every - 1) / every;
-    if ((rc = c->states.ensure((size_t)R * 11 * 8)) || (rc = c->actions.ensure((size_t)R * n_act * 16)) ||
-        (rc = c->poses.ensure((size_t)R * n_steps * 12)) || (rc = c->states_out.ensure((size_t)R * 11 * 8)) ||
-        (rc = c->vel.ensure((size_t)R * n_steps * 8)))
+    const size_t n_act = (size_t)(n_steps + every - 1) / every, n_poses = (size_t)R * n_steps;
+    if ((rc = hc.up(c->states, states_in, (size_t)R * 11)) || (rc = hc.up(c->actions, actions, R * n_act * 2)) ||
+        (rc = hc.room(c->poses, n_poses * 3)) || (rc = hc.room(c->states_out, (size_t)R * 11)) ||
+        (rc = hc.room(c->vel, n_poses)))
         return rc;
-    HIPCHK(hipMemcpyAsync(c->states.p, states_in, (size_t)R * 11 * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->actions.p, actions, (size_t)R * n_act * 16, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(rollout_kernel, dim3((R + 63) / 64), dim3(64), 0, c->stream, c->P,
-                       (const double *)c->states.p, (const double *)c->actions.p, R, n_steps, every, dt,
-                       (float *)c->poses.p, want_states ? (double *)c->states_out.p : nullptr,
-                       want_vel ? (double *)c->vel.p : nullptr);
+    hipLaunchKernelGGL(rollout_kernel, dim3((R + 63) / 64), dim3(64), 0, hc.st, c->P, (const double *)c->states,
+                       (const double *)c->actions, R, n_steps, every, dt, (float *)c->poses,
+                       want_states ? (double *)c->states_out : nullptr, want_vel ? (double *)c->vel : nullptr);
     HIPCHK(hipGetLastError());
     return RL_OK;
 }
@@ -132,13 +137,14 @@ extern "C" int rl_car_rollout(rl_car *c, const double *states_in, const double *
         });
     }
     std::lock_guard<std::mutex> lk(c->mu);
-    int rc = car_rollout_device(c, states_in, actions, R, n_steps, every, dt, states_out != nullptr, vel_out != nullptr);
+    HostCall hc(c->stream);
+    int rc = car_rollout_device(c, hc, states_in, actions, R, n_steps, every, dt, states_out != nullptr, vel_out != nullptr);
     if (rc || R == 0) return rc;
-    HIPCHK(hipMemcpyAsync(poses_out, c->poses.p, (size_t)R * n_steps * 12, hipMemcpyDeviceToHost, c->stream));
-    if (states_out) HIPCHK(hipMemcpyAsync(states_out, c->states_out.p, (size_t)R * 11 * 8, hipMemcpyDeviceToHost, c->stream));
-    if (vel_out) HIPCHK(hipMemcpyAsync(vel_out, c->vel.p, (size_t)R * n_steps * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return RL_OK;
+    const size_t n_poses = (size_t)R * n_steps;
+    if ((rc = hc.down(poses_out, c->poses, n_poses * 3)) || (rc = hc.down(states_out, c->states_out, (size_t)R * 11)) ||
+        (rc = hc.down(vel_out, c->vel, n_poses)))
+        return rc;
+    return hc.finish();
 }
 
 extern "C" int rl_car_rollout_check(rl_car *c, rl_method *h, const double *states_in, const double *actions,
@@ -172,23 +178,18 @@ extern "C" int rl_car_rollout_check(rl_car *c, rl_method *h, const double *state
     if (c->device != h->map->device) return fail(RL_ERR_INVALID, "car and range method live on different devices");
     std::scoped_lock lk(c->mu, h->mu);
     std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
-    int rc = car_rollout_device(c, states_in, actions, R, n_steps, every, dt, states_out != nullptr, vel_out != nullptr);
+    HostCall hc(c->stream);
+    int rc = car_rollout_device(c, hc, states_in, actions, R, n_steps, every, dt, states_out != nullptr, vel_out != nullptr);
     if (rc || R == 0) return rc;
     if ((rc = check_fan_args(h, R * n_steps, fov, num_rays))) return rc;
-    const size_t n_rays = (size_t)R * n_steps * num_rays;
-    if ((rc = c->ranges.ensure(n_rays * 4)) || (rc = c->edge.ensure((size_t)num_rays * 8)) ||
-        (rc = c->first.ensure((size_t)R * 4)))
+    const size_t n_poses = (size_t)R * n_steps;
+    if ((rc = hc.room(c->ranges, n_poses * num_rays)) || (rc = hc.up(c->edge, edge, num_rays)) || (rc = hc.room(c->first, R)) ||
+        (rc = crash_groups_device(h, LaunchArgs::of(h), c->poses, R, n_steps, fov, num_rays, c->edge, crash_thresh, c->first,
+                                  c->ranges, hc.st)) ||
+        (rc = hc.down(first_crashed, c->first, R)) || (rc = hc.down(states_out, c->states_out, (size_t)R * 11)) ||
+        (rc = hc.down(vel_out, c->vel, n_poses)))
         return rc;
-    HIPCHK(hipMemcpyAsync(c->edge.p, edge, (size_t)num_rays * 8, hipMemcpyHostToDevice, c->stream));
-    rc = crash_groups_device(h, LaunchArgs::of(h), (const float *)c->poses.p, R, n_steps, fov, num_rays,
-                             (const double *)c->edge.p, crash_thresh, (int *)c->first.p,
-                             (float *)c->ranges.p, c->stream);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(first_crashed, c->first.p, (size_t)R * 4, hipMemcpyDeviceToHost, c->stream));
-    if (states_out) HIPCHK(hipMemcpyAsync(states_out, c->states_out.p, (size_t)R * 11 * 8, hipMemcpyDeviceToHost, c->stream));
-    if (vel_out) HIPCHK(hipMemcpyAsync(vel_out, c->vel.p, (size_t)R * n_steps * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return RL_OK;
+    return hc.finish();
 }
 
 
@@ -200,7 +201,7 @@ struct rl_followgap {
     int n_cu = 256;                // (queried once: hipGetDeviceProperties costs the host tens of microseconds per call)
     bool walk_kernel = false;      // diagnostics (environment RL_FOLLOWGAP_WALK=1 at create): followgap_kernel at every size
     Stream stream;
-    DevBuf scans, angles;
+    DevPtr<float> scans, angles;
     std::mutex mu;
 };
 
@@ -279,15 +280,12 @@ extern "C" int rl_followgap_eval(rl_followgap *g, const float *scans, int n_scan
     if (n_scans < 0 || size < 10)
         return followgap_launch(g, nullptr, n_scans, size, nullptr, g->stream);   // (argument errors)
     if (n_scans == 0) return RL_OK;
-    const size_t bytes = (size_t)n_scans * size * sizeof(float);
+    HostCall hc(g->stream);
     int rc;
-    if ((rc = g->scans.ensure(bytes)) || (rc = g->angles.ensure((size_t)n_scans * sizeof(float)))) return rc;
-    HIPCHK(hipMemcpyAsync(g->scans.p, scans, bytes, hipMemcpyHostToDevice, g->stream));
-    if ((rc = followgap_launch(g, (const float *)g->scans.p, n_scans, size, (float *)g->angles.p, g->stream)))
+    if ((rc = hc.up(g->scans, scans, (size_t)n_scans * size)) || (rc = hc.room(g->angles, n_scans)) ||
+        (rc = followgap_launch(g, g->scans, n_scans, size, g->angles, hc.st)) || (rc = hc.down(angles, g->angles, n_scans)))
         return rc;
-    HIPCHK(hipMemcpyAsync(angles, g->angles.p, (size_t)n_scans * sizeof(float), hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipStreamSynchronize(g->stream));
-    return RL_OK;
+    return hc.finish();
 }
 
 extern "C" int rl_followgap_eval_device(rl_followgap *g, const float *d_scans, int n_scans, int size,
@@ -407,24 +405,15 @@ extern "C" int rl_calc_range_fan_cars(rl_method *h, const float *poses, const do
     std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
     if ((rc = set_device(h->map))) return rc;
     const size_t n = (size_t)n_groups * group, n_rays = n * num_rays;
-    if ((rc = h->poses.ensure(n * 12)) || (rc = h->cars.ensure(n * 24)) || (rc = h->outs.ensure(n_rays * 4)) ||
-        (hits_or_null && (rc = h->hits.ensure(n_rays * 8))) || (steps_or_null && (rc = h->steps.ensure(n_rays * 2))))
+    HostCall hc(h->stream);
+    if ((rc = hc.up(h->poses, poses, n * 3)) || (rc = hc.up(h->cars, cars, n * 3)) || (rc = hc.room(h->outs, n_rays)) ||
+        (hits_or_null && (rc = hc.room(h->hits, n_rays * 2))) || (steps_or_null && (rc = hc.room(h->steps, n_rays))) ||
+        (rc = launch_race(h, LaunchArgs::of(h), h->poses, h->cars, 3, n_groups, group, o, fov, num_rays, h->outs,
+                          hits_or_null ? (int32_t *)h->hits : nullptr, steps_or_null ? (uint16_t *)h->steps : nullptr, hc.st)) ||
+        (rc = hc.down(outs, h->outs, n_rays)) || (rc = hc.down(hits_or_null, h->hits, n_rays * 2)) ||
+        (rc = hc.down(steps_or_null, h->steps, n_rays)))
         return rc;
-    hipStream_t st = h->stream;
-    HIPCHK(hipMemcpyAsync(h->poses.p, poses, n * 12, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(h->cars.p, cars, n * 24, hipMemcpyHostToDevice, st));
-    rc = launch_race(h, LaunchArgs::of(h), (const float *)h->poses.p, (const double *)h->cars.p, 3, n_groups, group, o, fov, num_rays,
-                     (float *)h->outs.p, hits_or_null ? (int32_t *)h->hits.p : nullptr,
-                     steps_or_null ? (uint16_t *)h->steps.p : nullptr, st);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
-        return rc;
-    }
-    HIPCHK(hipMemcpyAsync(outs, h->outs.p, n_rays * 4, hipMemcpyDeviceToHost, st));
-    if (hits_or_null) HIPCHK(hipMemcpyAsync(hits_or_null, h->hits.p, n_rays * 8, hipMemcpyDeviceToHost, st));
-    if (steps_or_null) HIPCHK(hipMemcpyAsync(steps_or_null, h->steps.p, n_rays * 2, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return RL_OK;
+    return hc.finish();
 }
 
 extern "C" int rl_car_outline_cells(rl_car *c, rl_map *m, const double *cars_p3, int n, int max_cells, int32_t *cells,
@@ -444,18 +433,14 @@ extern "C" int rl_car_outline_cells(rl_car *c, rl_map *m, const double *cars_p3,
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCHK(hipSetDevice(c->device));
     const size_t n_cells = (size_t)n * max_cells;
-    if ((rc = c->o_cars.ensure((size_t)n * 24)) || (rc = c->o_cells.ensure(n_cells * 4)) ||
-        (rc = c->o_counts.ensure((size_t)n * 4)))
+    HostCall hc(c->stream);
+    if ((rc = hc.up(c->o_cars, cars_p3, (size_t)n * 3)) || (rc = hc.room(c->o_cells, n_cells)) || (rc = hc.room(c->o_counts, n)))
         return rc;
-    hipStream_t st = c->stream;
-    HIPCHK(hipMemcpyAsync(c->o_cars.p, cars_p3, (size_t)n * 24, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(outline_cells_kernel, dim3((n + 3) / 4), dim3(256), 0, st, o, (const double *)c->o_cars.p, n,
-                       max_cells, (int32_t *)c->o_cells.p, (int *)c->o_counts.p);
+    hipLaunchKernelGGL(outline_cells_kernel, dim3((n + 3) / 4), dim3(256), 0, hc.st, o, (const double *)c->o_cars, n,
+                       max_cells, (int32_t *)c->o_cells, (int *)c->o_counts);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(cells, c->o_cells.p, n_cells * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(counts, c->o_counts.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return RL_OK;
+    if ((rc = hc.down(cells, c->o_cells, n_cells)) || (rc = hc.down(counts, c->o_counts, n))) return rc;
+    return hc.finish();
 }
 
 // ---------------------------------------------------------------- the steering policy network (policy_kernels.h)
@@ -463,7 +448,7 @@ struct rl_policy {
     int device = 0;
     PolicyParams P{};                  // device pointers into `weights`
     Stream stream;
-    DevBuf weights, scans, steers;
+    DevPtr<float> weights, scans, steers;
     std::mutex mu;
 };
 
@@ -505,15 +490,15 @@ extern "C" int rl_policy_create(int device, int n_layers, const int *dims, const
     if (!p) return fail(RL_ERR_NOMEM, "out of host memory");
     p->device = device;
     if (hipSetDevice(device) != hipSuccess || p->stream.create() != hipSuccess) return fail(RL_ERR_HIP, "stream creation failed");
-    if ((rc = p->weights.ensure(host.size() * sizeof(float)))) return rc;
-    if (hipMemcpy(p->weights.p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+    if ((rc = p->weights.ensure(host.size()))) return rc;
+    if (hipMemcpy(p->weights, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
         return fail(RL_ERR_HIP, "rl_policy_create: weight upload failed");
     p->P.n_layers = n_layers;
     p->P.relu = 0;
     for (int l = 0; l <= n_layers; ++l) p->P.dims[l] = dims[l];
     for (int l = 0; l < n_layers; ++l) {
-        p->P.W[l] = (const float *)p->weights.p + offW[l];
-        p->P.b[l] = (const float *)p->weights.p + offB[l];
+        p->P.W[l] = p->weights + offW[l];
+        p->P.b[l] = p->weights + offB[l];
         if (relu[l]) p->P.relu |= 1u << l;
     }
     p->P.in_start = in_start;
@@ -556,16 +541,11 @@ extern "C" int rl_policy_eval(rl_policy *p, const float *scans, int n_scans, int
     if (rc || n_scans == 0) return rc;
     std::lock_guard<std::mutex> lk(p->mu);
     HIPCHK(hipSetDevice(p->device));
-    const size_t bytes = (size_t)n_scans * size * sizeof(float);
-    if ((rc = p->scans.ensure(bytes)) || (rc = p->steers.ensure((size_t)n_scans * sizeof(float)))) return rc;
-    HIPCHK(hipMemcpyAsync(p->scans.p, scans, bytes, hipMemcpyHostToDevice, p->stream));
-    if ((rc = policy_launch(p, (const float *)p->scans.p, n_scans, size, (float *)p->steers.p, p->stream))) {
-        (void)hipStreamSynchronize(p->stream);
+    HostCall hc(p->stream);
+    if ((rc = hc.up(p->scans, scans, (size_t)n_scans * size)) || (rc = hc.room(p->steers, n_scans)) ||
+        (rc = policy_launch(p, p->scans, n_scans, size, p->steers, hc.st)) || (rc = hc.down(steers, p->steers, n_scans)))
         return rc;
-    }
-    HIPCHK(hipMemcpyAsync(steers, p->steers.p, (size_t)n_scans * sizeof(float), hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(hipStreamSynchronize(p->stream));
-    return RL_OK;
+    return hc.finish();
 }
 
 extern "C" int rl_policy_eval_device(rl_policy *p, const float *d_scans, int n_scans, int size, float *d_steers,
@@ -699,24 +679,16 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
     const Loop lp(nullptr, c, h, g, p);
     HIPCHK(hipSetDevice(c->device));
     const size_t rows = (size_t)R * n_ticks, n_rays = (size_t)R * num_rays;
-    if ((rc = c->states.ensure((size_t)R * 11 * 8)) || (rc = c->speeds.ensure((size_t)R * 8)) ||
-        (rc = c->steer0.ensure((size_t)R * 4)) || (rc = c->first.ensure((size_t)R * 4)) ||
-        (rc = c->poses.ensure((size_t)R * 12)) || (rc = c->ranges.ensure(n_rays * 4)) ||
-        (rc = c->edge.ensure((size_t)num_rays * 8)) || (p && (rc = c->mlp.ensure((size_t)R * 4))) ||
-        (a.velocities && (rc = c->vel.ensure(rows * 8))) || (a.steers && (rc = c->tr_steers.ensure(rows * 4))) ||
-        (a.scan_poses && (rc = c->tr_poses.ensure(rows * 12))) || (a.states_trace && (rc = c->tr_states.ensure(rows * 88))))
-        return rc;
-    hipStream_t st = c->stream;
-    HIPCHK(hipMemcpyAsync(c->states.p, a.states_in, (size_t)R * 11 * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(c->speeds.p, a.speeds, (size_t)R * 8, hipMemcpyHostToDevice, st));
-    if (a.steer0) HIPCHK(hipMemcpyAsync(c->steer0.p, a.steer0, (size_t)R * 4, hipMemcpyHostToDevice, st));
-    else HIPCHK(hipMemsetAsync(c->steer0.p, 0, (size_t)R * 4, st));
-    HIPCHK(hipMemcpyAsync(c->edge.p, a.edge, (size_t)num_rays * 8, hipMemcpyHostToDevice, st));
+    HostCall hc(c->stream);
+    hipStream_t st = hc.st;
     // trace rows a car never reaches (after its crash tick; the steer of the crash tick) read NaN: all-ones bytes
-    if (a.velocities) HIPCHK(hipMemsetAsync(c->vel.p, 0xff, rows * 8, st));
-    if (a.steers) HIPCHK(hipMemsetAsync(c->tr_steers.p, 0xff, rows * 4, st));
-    if (a.scan_poses) HIPCHK(hipMemsetAsync(c->tr_poses.p, 0xff, rows * 12, st));
-    if (a.states_trace) HIPCHK(hipMemsetAsync(c->tr_states.p, 0xff, rows * 88, st));
+    if ((rc = hc.up(c->states, a.states_in, (size_t)R * 11)) || (rc = hc.up(c->speeds, a.speeds, R)) ||
+        (rc = a.steer0 ? hc.up(c->steer0, a.steer0, R) : hc.zero(c->steer0, R)) || (rc = hc.up(c->edge, a.edge, num_rays)) ||
+        (rc = hc.room(c->first, R)) || (rc = hc.room(c->poses, (size_t)R * 3)) || (rc = hc.room(c->ranges, n_rays)) ||
+        (p && (rc = hc.room(c->mlp, R))) || (a.velocities && (rc = hc.fill(c->vel, 0xff, rows))) ||
+        (a.steers && (rc = hc.fill(c->tr_steers, 0xff, rows))) || (a.scan_poses && (rc = hc.fill(c->tr_poses, 0xff, rows * 3))) ||
+        (a.states_trace && (rc = hc.fill(c->tr_states, 0xff, rows * 11))))
+        return rc;
 
     DriveParams dp{};
     dp.P = c->P;
@@ -728,31 +700,23 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
     dp.n_cars = R;
     dp.n_ticks = n_ticks;
     dp.steer_clip = steer_clip;
-    DriveBufs b{(double *)c->states.p, (const double *)c->speeds.p, (const float *)c->steer0.p, (const double *)c->edge.p,
-                (int *)c->first.p, (float *)c->poses.p, (const float *)c->ranges.p,
-                a.velocities ? (double *)c->vel.p : nullptr, a.steers ? (float *)c->tr_steers.p : nullptr,
-                a.scan_poses ? (float *)c->tr_poses.p : nullptr, a.states_trace ? (double *)c->tr_states.p : nullptr,
-                p ? (const float *)c->mlp.p : nullptr};
+    DriveBufs b{c->states, c->speeds, c->steer0, c->edge, c->first, c->poses, c->ranges,
+                a.velocities ? (double *)c->vel : nullptr, a.steers ? (float *)c->tr_steers : nullptr,
+                a.scan_poses ? (float *)c->tr_poses : nullptr, a.states_trace ? (double *)c->tr_states : nullptr,
+                p ? (const float *)c->mlp : nullptr};
     hipLaunchKernelGGL(drive_start_kernel, dim3((R + 63) / 64), dim3(64), 0, st, dp, b);
     HIPCHK(hipGetLastError());
     // the noise offset walks the global ray id t R num_rays + r num_rays of every tick
     // (a race reads every car's outline from its f64 state after this tick's step: all cars step, then all scan)
-    const LoopScan scan{b.pose, R, a.fov, num_rays, (float *)c->ranges.p, (float *)c->mlp.p, race ? group : 0, b.state, &op};
+    const LoopScan scan{b.pose, R, a.fov, num_rays, c->ranges, c->mlp, race ? group : 0, b.state, &op};
     for (int t = 0; t < n_ticks && rc == RL_OK; ++t)
         rc = lp.scan_then(scan, lp.base + (uint64_t)t * n_rays, g ? fg_tick_table : policy_tick_table, DRIVE_CARS,
                           "drive_tick_kernel", st, dp, b, t);
-    if (rc) {
-        (void)hipStreamSynchronize(st);           // nothing of this call is left in flight on the handles' buffers
+    if (rc || (rc = hc.down(a.first_crashed, c->first, R)) || (rc = hc.down(a.states_out, c->states, (size_t)R * 11)) ||
+        (rc = hc.down(a.velocities, c->vel, rows)) || (rc = hc.down(a.steers, c->tr_steers, rows)) ||
+        (rc = hc.down(a.scan_poses, c->tr_poses, rows * 3)) || (rc = hc.down(a.states_trace, c->tr_states, rows * 11)))
         return rc;
-    }
-    HIPCHK(hipMemcpyAsync(a.first_crashed, c->first.p, (size_t)R * 4, hipMemcpyDeviceToHost, st));
-    if (a.states_out) HIPCHK(hipMemcpyAsync(a.states_out, c->states.p, (size_t)R * 88, hipMemcpyDeviceToHost, st));
-    if (a.velocities) HIPCHK(hipMemcpyAsync(a.velocities, c->vel.p, rows * 8, hipMemcpyDeviceToHost, st));
-    if (a.steers) HIPCHK(hipMemcpyAsync(a.steers, c->tr_steers.p, rows * 4, hipMemcpyDeviceToHost, st));
-    if (a.scan_poses) HIPCHK(hipMemcpyAsync(a.scan_poses, c->tr_poses.p, rows * 12, hipMemcpyDeviceToHost, st));
-    if (a.states_trace) HIPCHK(hipMemcpyAsync(a.states_trace, c->tr_states.p, rows * 88, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return RL_OK;
+    return hc.finish();
 }
 
 extern "C" int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in,
@@ -885,16 +849,14 @@ extern "C" int rl_env_create(rl_car *c, rl_method *h, const rl_env_params *param
     ep.n_starts = n_starts;
     if (hipSetDevice(e->device) != hipSuccess) return fail(RL_ERR_HIP, "rl_env_create: hipSetDevice failed");
     const size_t N = q.n_envs, B = q.num_rays, M = n_starts;
-    struct { DevBuf *b; size_t bytes; } need[] = {
-        {&e->state.buf, N * 88}, {&e->starts.buf, M * 88}, {&e->edge.buf, B * 8}, {&e->tick.buf, N * 4},
-        {&e->episode.buf, N * 4}, {&e->start_index.buf, N * 4}, {&e->done.buf, N * 4}, {&e->phase.buf, N * 4},
-        {&e->moved.buf, N * 8}, {&e->pose.buf, N * 12}, {&e->ranges.buf, N * B * 4}, {&e->h_actions.buf, N * 8},
-        {&e->h_sidx.buf, N * 4}, {&e->h_obs.buf, N * q.obs_count * 4}, {&e->h_reward.buf, N * 4}, {&e->h_done.buf, N * 4},
-        {&e->h_aux.buf, N * 16}};
-    for (auto &n : need)
-        if ((rc = n.b->ensure(n.bytes))) return rc;
-    if (hipMemcpy(e->starts, starts_m11, M * 88, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(e->edge, edge, B * 8, hipMemcpyHostToDevice) != hipSuccess)
+    if ((rc = e->state.ensure(N * 11)) || (rc = e->starts.ensure(M * 11)) || (rc = e->edge.ensure(B)) || (rc = e->tick.ensure(N)) ||
+        (rc = e->episode.ensure(N)) || (rc = e->start_index.ensure(N)) || (rc = e->done.ensure(N)) || (rc = e->phase.ensure(N)) ||
+        (rc = e->moved.ensure(N)) || (rc = e->pose.ensure(N * 3)) || (rc = e->ranges.ensure(N * B)) ||
+        (rc = e->h_actions.ensure(N * 2)) || (rc = e->h_sidx.ensure(N)) || (rc = e->h_obs.ensure(N * q.obs_count)) ||
+        (rc = e->h_reward.ensure(N)) || (rc = e->h_done.ensure(N)) || (rc = e->h_aux.ensure(N * 4)))
+        return rc;
+    if (hipMemcpy(e->starts, starts_m11, M * 11 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(e->edge, edge, B * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
         return fail(RL_ERR_HIP, "rl_env_create: upload failed");
     *out = e.release();
     return RL_OK;
@@ -976,16 +938,15 @@ extern "C" int rl_env_step_device(rl_env *e, const float *d_actions_n2, float *d
     return env_step_locked(e, lp, d_actions_n2, d_obs, d_reward, d_done, d_aux_or_null, st);
 }
 
-// the host forms' way back: the staged results to the caller, then the wait
-static int env_download(rl_env *e, float *obs, float *reward, int *done, float *aux, hipStream_t st)
+// the host forms' way back: the staged results to the caller, then the wait (a failure leaves the env to be reset)
+static int env_download(rl_env *e, HostCall &hc, float *obs, float *reward, int *done, float *aux)
 {
     const size_t N = e->prm.n_envs;
-    HIPCHK(hipMemcpyAsync(obs, e->h_obs, N * e->prm.obs_count * 4, hipMemcpyDeviceToHost, st));
-    if (reward) HIPCHK(hipMemcpyAsync(reward, e->h_reward, N * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(done, e->h_done, N * 4, hipMemcpyDeviceToHost, st));
-    if (aux) HIPCHK(hipMemcpyAsync(aux, e->h_aux, N * 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return RL_OK;
+    int rc;
+    if ((rc = hc.down(obs, e->h_obs, N * e->prm.obs_count)) || (rc = hc.down(reward, e->h_reward, N)) ||
+        (rc = hc.down(done, e->h_done, N)) || (rc = hc.down(aux, e->h_aux, N * 4)) || (rc = hc.finish()))
+        e->ready = false;
+    return rc;
 }
 
 extern "C" int rl_env_reset(rl_env *e, uint64_t seed, const int *start_index_or_null, float *obs, float *aux_or_null,
@@ -1003,16 +964,12 @@ extern "C" int rl_env_reset(rl_env *e, uint64_t seed, const int *start_index_or_
     const Loop lp(&e->mu, e->c, e->h, nullptr, nullptr);
     HIPCHK(hipSetDevice(e->device));
     if ((rc = env_settle(e))) return rc;
-    hipStream_t st = e->c->stream;
-    if (start_index_or_null) HIPCHK(hipMemcpyAsync(e->h_sidx, start_index_or_null, (size_t)N * 4, hipMemcpyHostToDevice, st));
-    rc = env_reset_locked(e, lp, seed, start_index_or_null ? (int *)e->h_sidx : nullptr, e->h_obs,
-                          aux_or_null ? (float *)e->h_aux : nullptr, e->h_done, st);
-    if (rc) {
-        (void)hipStreamSynchronize(st);           // nothing of this call is left in flight
+    HostCall hc(e->c->stream);
+    if ((start_index_or_null && (rc = hc.up(e->h_sidx, start_index_or_null, N))) ||
+        (rc = env_reset_locked(e, lp, seed, start_index_or_null ? (int *)e->h_sidx : nullptr, e->h_obs,
+                               aux_or_null ? (float *)e->h_aux : nullptr, e->h_done, hc.st)))
         return rc;
-    }
-    if ((rc = env_download(e, obs, nullptr, done, aux_or_null, st))) e->ready = false;
-    return rc;
+    return env_download(e, hc, obs, nullptr, done, aux_or_null);
 }
 
 extern "C" int rl_env_step(rl_env *e, const float *actions_n2, float *obs, float *reward, int *done, float *aux_or_null)
@@ -1025,16 +982,12 @@ extern "C" int rl_env_step(rl_env *e, const float *actions_n2, float *obs, float
     if (rc) return rc;
     HIPCHK(hipSetDevice(e->device));
     if ((rc = env_settle(e))) return rc;
-    hipStream_t st = e->c->stream;
-    HIPCHK(hipMemcpyAsync(e->h_actions, actions_n2, (size_t)N * 8, hipMemcpyHostToDevice, st));
-    rc = env_step_locked(e, lp, e->h_actions, e->h_obs, e->h_reward, e->h_done, aux_or_null ? (float *)e->h_aux : nullptr,
-                         st);
-    if (rc) {
-        (void)hipStreamSynchronize(st);
+    HostCall hc(e->c->stream);
+    if ((rc = hc.up(e->h_actions, actions_n2, (size_t)N * 2)) ||
+        (rc = env_step_locked(e, lp, e->h_actions, e->h_obs, e->h_reward, e->h_done, aux_or_null ? (float *)e->h_aux : nullptr,
+                              hc.st)))
         return rc;
-    }
-    if ((rc = env_download(e, obs, reward, done, aux_or_null, st))) e->ready = false;
-    return rc;
+    return env_download(e, hc, obs, reward, done, aux_or_null);
 }
 
 extern "C" int rl_env_read(rl_env *e, double *states_n11, int *ticks, int *episodes, int *start_index, int *done)
@@ -1045,15 +998,13 @@ extern "C" int rl_env_read(rl_env *e, double *states_n11, int *ticks, int *episo
     HIPCHK(hipSetDevice(e->device));
     int rc = env_settle(e);
     if (rc) return rc;
-    hipStream_t st = e->c->stream;
+    HostCall hc(e->c->stream);
     const size_t N = e->prm.n_envs;
-    if (states_n11) HIPCHK(hipMemcpyAsync(states_n11, e->state, N * 88, hipMemcpyDeviceToHost, st));
-    if (ticks) HIPCHK(hipMemcpyAsync(ticks, e->tick, N * 4, hipMemcpyDeviceToHost, st));
-    if (episodes) HIPCHK(hipMemcpyAsync(episodes, e->episode, N * 4, hipMemcpyDeviceToHost, st));
-    if (start_index) HIPCHK(hipMemcpyAsync(start_index, e->start_index, N * 4, hipMemcpyDeviceToHost, st));
-    if (done) HIPCHK(hipMemcpyAsync(done, e->done, N * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return RL_OK;
+    if ((rc = hc.down(states_n11, e->state, N * 11)) || (rc = hc.down(ticks, e->tick, N)) ||
+        (rc = hc.down(episodes, e->episode, N)) || (rc = hc.down(start_index, e->start_index, N)) ||
+        (rc = hc.down(done, e->done, N)))
+        return rc;
+    return hc.finish();
 }
 
 // ---------------------------------------------------------------- diagnostics: HBM stream probe
@@ -1370,20 +1321,21 @@ extern "C" int rl_mcts_create(rl_car *c, rl_method *h, rl_followgap *g, rl_polic
     const size_t K = q.n_trees, N = (size_t)q.n_trees * q.max_nodes, B = q.num_rays;
     if (hipSetDevice(m->device) != hipSuccess) return fail(RL_ERR_HIP, "rl_mcts_create: hipSetDevice failed");
     const size_t L = q.rollout_steps;
-    struct { DevBuf *b; size_t bytes; } need[] = {
-        {&m->parent.buf, N * 4}, {&m->first_child.buf, N * 4}, {&m->next_sibling.buf, N * 4}, {&m->last_child.buf, N * 4},
-        {&m->n_children.buf, N * 4}, {&m->visits.buf, N * 4}, {&m->child_visits.buf, N * 4}, {&m->terminal.buf, N * 4}, {&m->crash.buf, N * 4},
-        {&m->reward.buf, N * 8}, {&m->action.buf, N * 8}, {&m->state.buf, N * 88}, {&m->pose.buf, N * 12}, {&m->answer.buf, N * 4},
-        {&m->n_nodes.buf, K * 4}, {&m->child.buf, K * 4}, {&m->exp_term.buf, K * 4}, {&m->keys.buf, K * 4}, {&m->first.buf, K * 4},
-        {&m->mlp.buf, K * 4}, {&m->best_v.buf, K * 4}, {&m->best_n.buf, K * 4}, {&m->best_a.buf, K * 8},
-        {&m->logtab.buf, ((size_t)q.max_nodes + 1) * 8}, {&m->cstate.buf, K * 88}, {&m->roots.buf, K * 96}, {&m->cpose.buf, K * 12},
-        {&m->actions.buf, K * mp.n_act * 16}, {&m->ranges.buf, K * B * 4}, {&m->edge.buf, B * 8}, {&m->rposes.buf, K * L * 12},
-        {&m->vel.buf, K * L * 8}};
-    for (auto &n : need)
-        if ((rc = n.b->ensure(n.bytes))) return rc;
+    for (DevPtr<int> *b : {&m->parent, &m->first_child, &m->next_sibling, &m->last_child, &m->n_children, &m->visits,
+                           &m->child_visits, &m->terminal, &m->crash})
+        if ((rc = b->ensure(N))) return rc;
+    for (DevPtr<int> *b : {&m->n_nodes, &m->child, &m->exp_term, &m->first, &m->best_v, &m->best_n})
+        if ((rc = b->ensure(K))) return rc;
+    // (roots: 11 doubles of state, then one action, a tree)
+    if ((rc = m->reward.ensure(N)) || (rc = m->action.ensure(N)) || (rc = m->state.ensure(N * 11)) || (rc = m->pose.ensure(N * 3)) ||
+        (rc = m->answer.ensure(N)) || (rc = m->keys.ensure(K)) || (rc = m->mlp.ensure(K)) || (rc = m->best_a.ensure(K)) ||
+        (rc = m->logtab.ensure((size_t)q.max_nodes + 1)) || (rc = m->cstate.ensure(K * 11)) || (rc = m->roots.ensure(K * 12)) ||
+        (rc = m->cpose.ensure(K * 3)) || (rc = m->actions.ensure(K * mp.n_act * 2)) || (rc = m->ranges.ensure(K * B)) ||
+        (rc = m->edge.ensure(B)) || (rc = m->rposes.ensure(K * L * 3)) || (rc = m->vel.ensure(K * L)))
+        return rc;
     const std::vector<double> lt = mcts_log_table(q.max_nodes);
-    if (hipMemcpy(m->logtab, lt.data(), lt.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(m->edge, edge, B * 8, hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(m->logtab, lt.data(), lt.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(m->edge, edge, B * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
         return fail(RL_ERR_HIP, "rl_mcts_create: upload failed");
     *out = m.release();
     return RL_OK;
@@ -1398,15 +1350,16 @@ static int mcts_act(rl_mcts *m, const Loop &lp, const MctsBufs &b, uint64_t off,
 
 // how rl_mcts_reset and rl_mcts_drive begin: the keys go up to d_keys, the K root states and root (recent) actions into
 // m->roots, then mcts_start_kernel makes the root nodes
-static int mcts_start(rl_mcts *m, const MctsBufs &b, uint32_t *d_keys, const std::vector<uint32_t> &keys, const double *states,
-                      const double *actions, hipStream_t st)
+static int mcts_start(rl_mcts *m, HostCall &hc, const MctsBufs &b, DevPtr<uint32_t> &d_keys, const std::vector<uint32_t> &keys,
+                      const double *states, const double *actions)
 {
     const size_t K = m->prm.n_trees;
     double *d_states = m->roots, *d_actions = d_states + K * 11;
-    HIPCHK(hipMemcpyAsync(d_keys, keys.data(), keys.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_states, states, K * 88, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_actions, actions, K * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(mcts_start_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, (const double *)d_states,
+    int rc;
+    if ((rc = hc.up(d_keys, keys.data(), keys.size())) || (rc = hc.up(d_states, states, K * 11)) ||
+        (rc = hc.up(d_actions, actions, K)))
+        return rc;
+    hipLaunchKernelGGL(mcts_start_kernel, dim3((K + 63) / 64), dim3(64), 0, hc.st, m->mp, b, (const double *)d_states,
                        (const double *)d_actions);
     if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "mcts_start_kernel launch failed");
     return RL_OK;
@@ -1420,16 +1373,14 @@ extern "C" int rl_mcts_reset(rl_mcts *m, const double *root_states, const double
     if (rc) return rc;
     const Loop lp(&m->mu, m->c, m->h, m->g, m->p);
     HIPCHK(hipSetDevice(m->device));
-    hipStream_t st = m->c->stream;
     m->ready = false;
     std::vector<uint32_t> keys(K);
     for (int k = 0; k < K; ++k) keys[k] = noise_key(seeds[k]);
     const uint64_t base = lp.base;
-    rc = mcts_start(m, mcts_bufs(m), m->keys, keys, root_states, root_actions, st);
-    if (!rc) rc = mcts_act(m, lp, mcts_bufs(m), base, 1, st);
-    const hipError_t e = hipStreamSynchronize(st);            // (the host's root arrays are the caller's)
-    if (!rc && e != hipSuccess) rc = fail(RL_ERR_HIP, "rl_mcts_reset: %s", hipGetErrorString(e));
-    if (rc) return rc;
+    HostCall hc(m->c->stream);                                // (after `keys`: they stay until the call has drained)
+    if ((rc = mcts_start(m, hc, mcts_bufs(m), m->keys, keys, root_states, root_actions)) ||
+        (rc = mcts_act(m, lp, mcts_bufs(m), base, 1, hc.st)) || (rc = hc.finish()))
+        return rc;
     m->base = base;
     m->iters = 0;
     m->ready = true;
@@ -1480,7 +1431,7 @@ extern "C" int rl_mcts_run(rl_mcts *m, int n_iterations)
     if ((rc = check_fan_args(m->h, K, m->prm.fov, B)) || (rc = check_fan_args(m->h, K * L, m->prm.fov, B))) return rc;
     if (n_iterations == 0) return RL_OK;
     HIPCHK(hipSetDevice(m->device));
-    if ((rc = m->rranges.ensure((size_t)K * L * B * 4))) return rc;
+    if ((rc = m->rranges.ensure((size_t)K * L * B))) return rc;
     hipStream_t st = m->c->stream;
     rc = mcts_iterations(m, lp, mcts_bufs(m), m->base, m->iters, n_iterations, st);
     const hipError_t e = hipStreamSynchronize(st);
@@ -1516,30 +1467,30 @@ extern "C" int rl_mcts_drive(rl_mcts *m, const double *states_in, const double *
     if ((rc = check_fan_args(m->h, K, m->prm.fov, B)) || (rc = check_fan_args(m->h, K * L, m->prm.fov, B))) return rc;
     if (D == 0) {
         for (int k = 0; k < K; ++k) first[k] = -1;
-        if (states_out != states_in) memmove(states_out, states_in, (size_t)K * 88);
-        if (recent_out != recent_in) memmove(recent_out, recent_in, (size_t)K * 8);
+        if (states_out != states_in) memmove(states_out, states_in, (size_t)K * 11 * sizeof(double));
+        if (recent_out != recent_in) memmove(recent_out, recent_in, (size_t)K * sizeof(double));
         return RL_OK;
     }
     const size_t rows = (size_t)K * D;
     const Loop lp(&m->mu, m->c, m->h, m->g, m->p);
     HIPCHK(hipSetDevice(m->device));
-    if ((rc = m->rranges.ensure((size_t)K * L * B * 4)) || (rc = m->root_crash.ensure((size_t)K * 4)) ||
-        (rc = m->dr_keys.ensure(rows * 4)) || (rc = m->dr_first.ensure((size_t)K * 4)) ||
-        (rc = m->dr_actions.ensure(rows * 8)) || (rc = m->dr_visits.ensure(rows * 4)) ||
-        (trace_states_or_null && (rc = m->dr_trace.ensure(rows * 88))))
-        return rc;
-    hipStream_t st = m->c->stream;
-    m->ready = false;
     std::vector<uint32_t> keys(rows);                  // [D][K]: decision d's seed is seeds[k] + d mod 2^64
     for (int d = 0; d < D; ++d)
         for (int k = 0; k < K; ++k) keys[(size_t)d * K + k] = noise_key(seeds[k] + (uint64_t)d);
+    HostCall hc(m->c->stream);                         // (after `keys`: they stay until the call has drained)
+    hipStream_t st = hc.st;
+    if ((rc = hc.room(m->rranges, (size_t)K * L * B)) || (rc = hc.room(m->root_crash, K)) || (rc = hc.room(m->dr_first, K)) ||
+        (rc = hc.room(m->dr_actions, rows)) || (rc = hc.room(m->dr_visits, rows)) ||
+        (trace_states_or_null && (rc = hc.room(m->dr_trace, rows * 11))))
+        return rc;
+    m->ready = false;
     double *d_states = m->roots, *d_recent = d_states + (size_t)K * 11;
     MctsBufs b = mcts_bufs(m);
     b.root_crash = m->root_crash;
     const MctsDrive dv{d_states, d_recent, m->dr_first, m->dr_actions, m->dr_visits,
                        trace_states_or_null ? (double *)m->dr_trace : nullptr, D, steps_per_decision, steer_clip};
     const uint64_t stride = (uint64_t)K * B * (1 + (uint64_t)I * (1 + L));
-    rc = mcts_start(m, b, m->dr_keys, keys, states_in, recent_in, st);
+    rc = mcts_start(m, hc, b, m->dr_keys, keys, states_in, recent_in);
     uint64_t base = lp.base;
     for (int d = 0; d < D && rc == RL_OK; ++d) {
         base = lp.base + (uint64_t)d * stride;
@@ -1551,20 +1502,14 @@ extern "C" int rl_mcts_drive(rl_mcts *m, const double *states_in, const double *
             if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_advance_kernel launch failed");
         }
     }
-    if (rc) {
-        (void)hipStreamSynchronize(st);                // nothing of this call is left in flight; the trees need a reset
-        return rc;
-    }
+    if (rc) return rc;                                 // (the trees need a reset)
     // the planner keeps the last decision's trees: its keys, ray offset and iteration count are that decision's
-    HIPCHK(hipMemcpyAsync(m->keys, b.keys, (size_t)K * 4, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(first, m->dr_first, (size_t)K * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(states_out, d_states, (size_t)K * 88, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(recent_out, d_recent, (size_t)K * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(actions, m->dr_actions, rows * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(visits, m->dr_visits, rows * 4, hipMemcpyDeviceToHost, st));
-    if (trace_states_or_null)
-        HIPCHK(hipMemcpyAsync(trace_states_or_null, m->dr_trace, rows * 88, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(m->keys, b.keys, (size_t)K * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    if ((rc = hc.down(first, m->dr_first, K)) || (rc = hc.down(states_out, (const double *)d_states, (size_t)K * 11)) ||
+        (rc = hc.down(recent_out, (const double *)d_recent, K)) || (rc = hc.down(actions, m->dr_actions, rows)) ||
+        (rc = hc.down(visits, m->dr_visits, rows)) || (rc = hc.down(trace_states_or_null, m->dr_trace, rows * 11)) ||
+        (rc = hc.finish()))
+        return rc;
     m->base = base;
     m->iters = I;
     m->ready = true;
@@ -1577,16 +1522,15 @@ extern "C" int rl_mcts_best(rl_mcts *m, double *actions, int *visits, int *n_nod
     std::scoped_lock lk(m->mu, m->c->mu);
     if (!m->ready) return fail(RL_ERR_INVALID, "rl_mcts_best: reset the planner first (rl_mcts_reset)");
     HIPCHK(hipSetDevice(m->device));
-    hipStream_t st = m->c->stream;
+    HostCall hc(m->c->stream);
     const int K = m->prm.n_trees;
-    hipLaunchKernelGGL(mcts_best_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, mcts_bufs(m),
+    hipLaunchKernelGGL(mcts_best_kernel, dim3((K + 63) / 64), dim3(64), 0, hc.st, m->mp, mcts_bufs(m),
                        (double *)m->best_a, (int *)m->best_v, (int *)m->best_n);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(actions, m->best_a, (size_t)K * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(visits, m->best_v, (size_t)K * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(n_nodes, m->best_n, (size_t)K * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return RL_OK;
+    int rc;
+    if ((rc = hc.down(actions, m->best_a, K)) || (rc = hc.down(visits, m->best_v, K)) || (rc = hc.down(n_nodes, m->best_n, K)))
+        return rc;
+    return hc.finish();
 }
 
 extern "C" int rl_mcts_read_tree(rl_mcts *m, int tree, int *parent, int *first_child, int *next_sibling,
@@ -1600,22 +1544,23 @@ extern "C" int rl_mcts_read_tree(rl_mcts *m, int tree, int *parent, int *first_c
     std::scoped_lock lk(m->mu, m->c->mu);
     if (!m->ready) return fail(RL_ERR_INVALID, "rl_mcts_read_tree: reset the planner first (rl_mcts_reset)");
     HIPCHK(hipSetDevice(m->device));
-    hipStream_t st = m->c->stream;
-    int n = 0;
-    HIPCHK(hipMemcpyAsync(&n, m->n_nodes + tree, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HostCall hc(m->c->stream);
+    int n = 0, rc;
+    if ((rc = hc.down(&n, m->n_nodes + tree, 1))) return rc;
+    HIPCHK(hipStreamSynchronize(hc.st));
     n = std::min(std::max(n, 0), m->prm.max_nodes);
+    // the tree's first n nodes of an array of `per` scalars a node, when the caller wants it
     const size_t t0 = (size_t)tree * m->prm.max_nodes;
-    struct Out { void *dst; const DevBuf *src; size_t w; };
-    const Out outs[] = {{parent, &m->parent.buf, 4}, {first_child, &m->first_child.buf, 4}, {next_sibling, &m->next_sibling.buf, 4},
-                        {n_children, &m->n_children.buf, 4}, {visits, &m->visits.buf, 4}, {child_visits, &m->child_visits.buf, 4},
-                        {reward, &m->reward.buf, 8}, {action, &m->action.buf, 8}, {terminal, &m->terminal.buf, 4},
-                        {state, &m->state.buf, 88}, {scan_pose, &m->pose.buf, 12}, {answer, &m->answer.buf, 4},
-                        {crash, &m->crash.buf, 4}};
-    for (const Out &o : outs)
-        if (o.dst && n > 0)
-            HIPCHK(hipMemcpyAsync(o.dst, (const char *)o.src->p + t0 * o.w, (size_t)n * o.w, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    const auto rows = [&](auto *dst, const auto &src, size_t per) {
+        return n > 0 ? hc.down(dst, src + t0 * per, (size_t)n * per) : (int)RL_OK;
+    };
+    if ((rc = rows(parent, m->parent, 1)) || (rc = rows(first_child, m->first_child, 1)) ||
+        (rc = rows(next_sibling, m->next_sibling, 1)) || (rc = rows(n_children, m->n_children, 1)) ||
+        (rc = rows(visits, m->visits, 1)) || (rc = rows(child_visits, m->child_visits, 1)) || (rc = rows(reward, m->reward, 1)) ||
+        (rc = rows(action, m->action, 1)) || (rc = rows(terminal, m->terminal, 1)) || (rc = rows(state, m->state, 11)) ||
+        (rc = rows(scan_pose, m->pose, 3)) || (rc = rows(answer, m->answer, 1)) || (rc = rows(crash, m->crash, 1)) ||
+        (rc = hc.finish()))
+        return rc;
     *n_nodes_out = n;
     return RL_OK;
 }

@@ -1401,13 +1401,12 @@ static int pin_ensure(rl_method *h, size_t bytes)
 // car-outline table -> h->edge, re-sent only when its contents changed since the last call
 int upload_edge(rl_method *h, const double *edge, int num_rays)
 {
-    const size_t cap_before = h->edge.cap;
-    int rc = h->edge.ensure((size_t)num_rays * sizeof(double));
+    const size_t cap_before = h->edge.buf.cap;
+    int rc = h->edge.ensure(num_rays);
     if (rc) return rc;
-    if (h->edge.cap != cap_before || h->edge_host.size() != (size_t)num_rays ||
+    if (h->edge.buf.cap != cap_before || h->edge_host.size() != (size_t)num_rays ||
         memcmp(h->edge_host.data(), edge, (size_t)num_rays * sizeof(double)) != 0) {
-        HIPCHK(hipMemcpyAsync(h->edge.p, edge, (size_t)num_rays * sizeof(double), hipMemcpyHostToDevice,
-                              h->stream));
+        HIPCHK(hipMemcpyAsync(h->edge, edge, (size_t)num_rays * sizeof(double), hipMemcpyHostToDevice, h->stream));
         h->edge_host.assign(edge, edge + num_rays);
     }
     return RL_OK;
@@ -1424,6 +1423,7 @@ int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_r
         if (first_crashed) *first_crashed = -1;
         return RL_OK;
     }
+    HostCall hc(h->stream);
     // small calls: zero-copy through pinned host memory (scan() 45 -> ~25 us host-visible)
     // output buffer inside a pinned block of rl_host_alloc: the kernel writes the ranges straight into it
     const bool direct_out = outs && !hits && !steps && n_rays <= (size_t)h->direct_max_rays &&
@@ -1434,29 +1434,24 @@ int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_r
     if (zc) {
         if ((rc = pin_ensure(h, off_end))) return rc;
         memcpy(h->pin, poses, (size_t)n_poses * 3 * sizeof(float));
-    } else {
-        if ((rc = h->poses.ensure((size_t)n_poses * 3 * sizeof(float)))) return rc;
-        if (outs || !first_crashed)
-            if ((rc = h->outs.ensure(n_rays * sizeof(float)))) return rc;
-        if (hits && (rc = h->hits.ensure(n_rays * 2 * sizeof(int32_t)))) return rc;
-        if (steps && (rc = h->steps.ensure(n_rays * sizeof(uint16_t)))) return rc;
-        HIPCHK(hipMemcpyAsync(h->poses.p, poses, (size_t)n_poses * 3 * sizeof(float),
-                              hipMemcpyHostToDevice, h->stream));
-    }
+    } else if ((rc = hc.up(h->poses, poses, (size_t)n_poses * 3)) ||
+               ((outs || !first_crashed) && (rc = hc.room(h->outs, n_rays))) || (hits && (rc = hc.room(h->hits, n_rays * 2))) ||
+               (steps && (rc = hc.room(h->steps, n_rays))))
+        return rc;
     char *const pin = h->pin;
-    const float *d_poses = zc ? (const float *)pin : (const float *)h->poses.p;
+    const float *d_poses = zc ? (const float *)pin : (const float *)h->poses;
     CrashParams cp{nullptr, 0.0, nullptr, 1, 0};
     const bool crash_direct = first_crashed && n_poses <= 512;
     if (first_crashed) {
         if ((rc = upload_edge(h, edge, num_rays))) return rc;
-        if ((rc = h->flag.ensure(sizeof(int)))) return rc;
+        if ((rc = hc.room(h->flag, 1))) return rc;
         if (!h->pin_flag && h->pin_flag.alloc(64) != hipSuccess) return fail(RL_ERR_NOMEM, "pinned allocation of 64 bytes failed");
-        cp.edge = (const double *)h->edge.p;
+        cp.edge = h->edge;
         cp.thresh = crash_thresh;
         if (crash_direct) {
             // one roll-out: atomicMin straight into the result word (few poses, little contention)
-            hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64), 0, h->stream, (int *)h->flag.p, 1, INT_MAX);
-            cp.first_crashed = (int *)h->flag.p;
+            hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64), 0, h->stream, (int *)h->flag, 1, INT_MAX);
+            cp.first_crashed = h->flag;
             cp.group = n_poses;
         } else {
             // big batches: the kernel marks crashed poses (a word per pose), the first one is reduced
@@ -1466,10 +1461,10 @@ int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_r
         }
     }
     float *d_out = (outs || !first_crashed)
-                       ? (direct_out ? outs : zc ? (float *)(pin + off_out) : (float *)h->outs.p)
+                       ? (direct_out ? outs : zc ? (float *)(pin + off_out) : (float *)h->outs)
                        : nullptr;
-    const FanCall call{LaunchArgs::of(h), d_poses, n_poses, fov, num_rays, d_out, hits ? (int32_t *)h->hits.p : nullptr,
-                       steps ? (uint16_t *)h->steps.p : nullptr, first_crashed ? &cp : nullptr, h->stream};
+    const FanCall call{LaunchArgs::of(h), d_poses, n_poses, fov, num_rays, d_out, hits ? (int32_t *)h->hits : nullptr,
+                       steps ? (uint16_t *)h->steps : nullptr, first_crashed ? &cp : nullptr, h->stream};
     if (outs && !zc && !first_crashed && !hits && !steps && h->overlap_min_rays > 0 &&
         n_rays >= (size_t)h->overlap_min_rays && n_poses >= 4 && !call.timing &&
         (h->kind == RL_RM || h->kind == RL_RM_GPU || h->kind == RL_BRESENHAM)) {
@@ -1506,22 +1501,16 @@ int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_r
         return rc;
     }
     if ((rc = launch_fan(h, call))) return rc;
-    if (outs && !zc)
-        HIPCHK(hipMemcpyAsync(outs, h->outs.p, n_rays * sizeof(float), hipMemcpyDeviceToHost,
-                              h->stream));
-    if (hits)
-        HIPCHK(hipMemcpyAsync(hits, h->hits.p, n_rays * 2 * sizeof(int32_t), hipMemcpyDeviceToHost,
-                              h->stream));
-    if (steps)
-        HIPCHK(hipMemcpyAsync(steps, h->steps.p, n_rays * sizeof(uint16_t), hipMemcpyDeviceToHost,
-                              h->stream));
+    if (!zc && ((rc = hc.down(outs, h->outs, n_rays)) || (rc = hc.down(hits, h->hits, n_rays * 2)) ||
+                (rc = hc.down(steps, h->steps, n_rays))))
+        return rc;
     if (first_crashed) {
         if (!crash_direct)
             hipLaunchKernelGGL(crash_reduce_kernel, dim3(1), dim3(64), 0, h->stream,
-                               (const int *)cp.first_crashed, cp.mark, 1, n_poses, (int *)h->flag.p);
-        HIPCHK(hipMemcpyAsync(h->pin_flag, h->flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+                               (const int *)cp.first_crashed, cp.mark, 1, n_poses, (int *)h->flag);
+        HIPCHK(hipMemcpyAsync(h->pin_flag, h->flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     }
-    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((rc = hc.finish())) return rc;
     int flag = first_crashed ? *h->pin_flag : 0;
     if (crash_direct && flag == INT_MAX) flag = -(n_poses + 1);
     if (zc && !direct_out) {
@@ -1539,28 +1528,21 @@ int rays_host(rl_method *h, const float *ins, float *outs, int n)
     std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
     int rc = set_device(h->map);
     if (rc) return rc;
+    HostCall hc(h->stream);
     if (n <= h->pinned_max_rays) {                       // one scan's worth of rows: zero-copy
         const size_t off_out = ((size_t)n * 3 * sizeof(float) + 255) & ~(size_t)255;
         if ((rc = pin_ensure(h, off_out + (size_t)n * sizeof(float)))) return rc;
         memcpy(h->pin, ins, (size_t)n * 3 * sizeof(float));
         char *const pin = h->pin;
         float *p_out = (float *)(pin + off_out);
-        if ((rc = launch_rays(h, (const float *)pin, n, p_out, nullptr, nullptr, h->stream))) return rc;
-        HIPCHK(hipStreamSynchronize(h->stream));
+        if ((rc = launch_rays(h, (const float *)pin, n, p_out, nullptr, nullptr, h->stream)) || (rc = hc.finish())) return rc;
         memcpy(outs, p_out, (size_t)n * sizeof(float));
         return RL_OK;
     }
-    if ((rc = h->poses.ensure((size_t)n * 3 * sizeof(float)))) return rc;
-    if ((rc = h->outs.ensure((size_t)n * sizeof(float)))) return rc;
-    HIPCHK(hipMemcpyAsync(h->poses.p, ins, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice,
-                          h->stream));
-    rc = launch_rays(h, (const float *)h->poses.p, n, (float *)h->outs.p, nullptr, nullptr,
-                     h->stream);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(outs, h->outs.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost,
-                          h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return RL_OK;
+    if ((rc = hc.up(h->poses, ins, (size_t)n * 3)) || (rc = hc.room(h->outs, n)) ||
+        (rc = launch_rays(h, h->poses, n, h->outs, nullptr, nullptr, hc.st)) || (rc = hc.down(outs, h->outs, n)))
+        return rc;
+    return hc.finish();
 }
 
 // ------------------------------------------------------------------------------
@@ -1762,38 +1744,25 @@ static int pf_host(rl_method *h, const char *fn, const PfHost &a, int n_particle
     if (a.ins && (rc = pf_kind_of(h, &kind))) return rc;
     if (a.weights && !h->sensor_w) return fail(RL_ERR_INVALID, "%s: no sensor model set (rl_set_sensor_model)", fn);
     if (n_particles == 0 || (rc = set_device(h->map))) return rc;
-    const size_t n = (size_t)n_particles * n_angles, fa = (size_t)n_angles * sizeof(float);
-    hipStream_t s = h->stream;
-    if (a.ins) {
-        if ((rc = h->poses.ensure((size_t)n_particles * 3 * sizeof(float))) || (rc = h->pf_ang.ensure(fa))) return rc;
-        HIPCHK(hipMemcpyAsync(h->poses.p, a.ins, (size_t)n_particles * 3 * sizeof(float), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(h->pf_ang.p, a.angles, fa, hipMemcpyHostToDevice, s));
-    }
-    if (a.obs) {
-        if ((rc = h->pf_obs.ensure(fa)) || (rc = h->pf_w.ensure((size_t)n_particles * sizeof(double)))) return rc;
-        HIPCHK(hipMemcpyAsync(h->pf_obs.p, a.obs, fa, hipMemcpyHostToDevice, s));
-    }
-    if (a.outs || a.ranges) {
-        if ((rc = h->outs.ensure(n * sizeof(float)))) return rc;
-        if (a.ranges) HIPCHK(hipMemcpyAsync(h->outs.p, a.ranges, n * sizeof(float), hipMemcpyHostToDevice, s));
-    }
-    if (a.hits && (rc = h->hits.ensure(n * 2 * sizeof(int32_t)))) return rc;
-    if (a.steps && (rc = h->steps.ensure(n * sizeof(uint16_t)))) return rc;
+    const size_t n = (size_t)n_particles * n_angles;
+    HostCall hc(h->stream);
+    hipStream_t s = hc.st;
+    if ((a.ins && ((rc = hc.up(h->poses, a.ins, (size_t)n_particles * 3)) || (rc = hc.up(h->pf_ang, a.angles, n_angles)))) ||
+        (a.obs && ((rc = hc.up(h->pf_obs, a.obs, n_angles)) || (rc = hc.room(h->pf_w, n_particles)))) ||
+        (a.ranges && (rc = hc.up(h->outs, a.ranges, n))) || (a.outs && (rc = hc.room(h->outs, n))) ||
+        (a.hits && (rc = hc.room(h->hits, n * 2))) || (a.steps && (rc = hc.room(h->steps, n))))
+        return rc;
     if (a.outs)
-        rc = launch_pf_angles(h, LaunchArgs::of(h), kind, (const float *)h->poses.p, n_particles, (const float *)h->pf_ang.p, n_angles, (float *)h->outs.p,
-                              a.hits ? (int32_t *)h->hits.p : nullptr, a.steps ? (uint16_t *)h->steps.p : nullptr, s);
+        rc = launch_pf_angles(h, LaunchArgs::of(h), kind, h->poses, n_particles, h->pf_ang, n_angles, h->outs,
+                              a.hits ? (int32_t *)h->hits : nullptr, a.steps ? (uint16_t *)h->steps : nullptr, s);
     else if (a.ranges)
-        rc = launch_pf_eval(h, (const float *)h->pf_obs.p, (const float *)h->outs.p, n_angles, n_particles, (double *)h->pf_w.p, s);
+        rc = launch_pf_eval(h, h->pf_obs, h->outs, n_angles, n_particles, h->pf_w, s);
     else
-        rc = launch_pf_weights(h, LaunchArgs::of(h), kind, (const float *)h->poses.p, n_particles, (const float *)h->pf_ang.p,
-                               (const float *)h->pf_obs.p, n_angles, (double *)h->pf_w.p, s);
-    if (rc) return rc;
-    if (a.outs) HIPCHK(hipMemcpyAsync(a.outs, h->outs.p, n * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (a.hits) HIPCHK(hipMemcpyAsync(a.hits, h->hits.p, n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (a.steps) HIPCHK(hipMemcpyAsync(a.steps, h->steps.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
-    if (a.weights) HIPCHK(hipMemcpyAsync(a.weights, h->pf_w.p, (size_t)n_particles * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return RL_OK;
+        rc = launch_pf_weights(h, LaunchArgs::of(h), kind, h->poses, n_particles, h->pf_ang, h->pf_obs, n_angles, h->pf_w, s);
+    if (rc || (rc = hc.down(a.outs, h->outs, n)) || (rc = hc.down(a.hits, h->hits, n * 2)) ||
+        (rc = hc.down(a.steps, h->steps, n)) || (rc = hc.down(a.weights, h->pf_w, n_particles)))
+        return rc;
+    return hc.finish();
 }
 
 extern "C" int rl_calc_range_repeat_angles(rl_method *h, const float *ins_p3, int n_particles, const float *angles,
@@ -1835,7 +1804,11 @@ struct rl_pf {
     bool ready = false;            // a reset has been made
     // state: X (cur), X' (prop), the float32 poses of the scan, w, L, omega, the in-chunk sums, cum, ancestors; the chunk
     // totals ([1 + MCL_SUMS][NB]: omega's, then the six of the estimate), the chunk bases, W; a call's inputs and outputs
-    DevBuf ang, cur, prop, q, w, lik, omega, part, cum, anc, tot, base, scal, odom, obs, est, neff, flags;
+    // (counted in scalars: 3 a pose or an odometry row, 4 an estimate)
+    DevPtr<float> ang, q, obs;
+    DevPtr<double> cur, prop, w, lik, omega, part, cum, tot, base, scal, odom, est, neff;
+    DevPtr<int32_t> anc;
+    DevPtr<int> flags;
     std::mutex mu;
 };
 
@@ -1865,13 +1838,12 @@ extern "C" int rl_pf_create(rl_method *h, const rl_pf_params *p, const float *an
     for (int a = 0; a < 3; ++a) f->std[a] = p->motion_std[a];
     f->ratio = p->resample_ratio;
     const size_t P = (size_t)f->P, NB = (size_t)f->NB;
-    struct { DevBuf *b; size_t bytes; } need[] = {
-        {&f->ang, (size_t)f->A * 4}, {&f->cur, P * 24}, {&f->prop, P * 24}, {&f->q, P * 12}, {&f->w, P * 8}, {&f->lik, P * 8},
-        {&f->omega, P * 8}, {&f->part, P * 8}, {&f->cum, P * 8}, {&f->anc, P * 4}, {&f->tot, (1 + MCL_SUMS) * NB * 8},
-        {&f->base, NB * 8}, {&f->scal, 8}};
-    for (auto &n : need)
-        if ((rc = n.b->ensure(n.bytes))) return rc;
-    if (hipMemcpy(f->ang.p, angles, (size_t)f->A * 4, hipMemcpyHostToDevice) != hipSuccess)
+    if ((rc = f->ang.ensure(f->A)) || (rc = f->cur.ensure(P * 3)) || (rc = f->prop.ensure(P * 3)) || (rc = f->q.ensure(P * 3)) ||
+        (rc = f->w.ensure(P)) || (rc = f->lik.ensure(P)) || (rc = f->omega.ensure(P)) || (rc = f->part.ensure(P)) ||
+        (rc = f->cum.ensure(P)) || (rc = f->anc.ensure(P)) || (rc = f->tot.ensure((1 + MCL_SUMS) * NB)) ||
+        (rc = f->base.ensure(NB)) || (rc = f->scal.ensure(1)))
+        return rc;
+    if (hipMemcpy(f->ang, angles, (size_t)f->A * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
         return fail(RL_ERR_HIP, "rl_pf_create: the copy of the angles failed");
     *out = f.release();
     return RL_OK;
@@ -1890,14 +1862,14 @@ extern "C" int rl_pf_reset(rl_pf *f, const double *particles_p3, const double *w
     std::scoped_lock lk(f->mu, f->h->mu);
     int rc = set_device(f->h->map);
     if (rc) return rc;
-    hipStream_t s = f->h->stream;
     const size_t P = (size_t)f->P;
     std::vector<double> uniform;
     if (!weights_or_null) uniform.assign(P, 1.0 / (double)f->P);
-    HIPCHK(hipMemcpyAsync(f->cur.p, particles_p3, P * 24, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(f->w.p, weights_or_null ? weights_or_null : uniform.data(), P * 8, hipMemcpyHostToDevice, s));
-    for (DevBuf *b : {&f->prop, &f->lik, &f->omega, &f->part, &f->cum, &f->anc}) HIPCHK(hipMemsetAsync(b->p, 0, b->cap, s));
-    HIPCHK(hipStreamSynchronize(s));
+    HostCall hc(f->h->stream);                   // (after `uniform`: it stays until the call has drained)
+    if ((rc = hc.up(f->cur, particles_p3, P * 3)) || (rc = hc.up(f->w, weights_or_null ? weights_or_null : uniform.data(), P)) ||
+        (rc = hc.zero(f->prop, P * 3)) || (rc = hc.zero(f->lik, P)) || (rc = hc.zero(f->omega, P)) ||
+        (rc = hc.zero(f->part, P)) || (rc = hc.zero(f->cum, P)) || (rc = hc.zero(f->anc, P)) || (rc = hc.finish()))
+        return rc;
     f->key = noise_key(seed);
     f->t = 0;
     f->ready = true;
@@ -1910,22 +1882,18 @@ static int launch_mcl_step(rl_pf *f, const LaunchArgs &a, int kind, const MclPar
     rl_method *h = f->h;
     const uint32_t t = (uint32_t)(f->t + k);
     const int grid = (f->P + MCL_WG - 1) / MCL_WG;
-    double *tot = (double *)f->tot.p, *tot6 = tot + f->NB;
-    hipLaunchKernelGGL(mcl_motion_kernel, dim3(grid), dim3(MCL_WG), 0, s, mp, (const double *)f->odom.p + 3 * (size_t)k, t,
-                       (const double *)f->cur.p, (double *)f->prop.p, (float *)f->q.p);
-    int rc = launch_pf_weights(h, a, kind, (const float *)f->q.p, f->P, (const float *)f->ang.p,
-                               (const float *)f->obs.p + (size_t)k * f->A, f->A, (double *)f->lik.p, s);
+    double *tot = f->tot, *tot6 = tot + f->NB;
+    hipLaunchKernelGGL(mcl_motion_kernel, dim3(grid), dim3(MCL_WG), 0, s, mp, f->odom + 3 * (size_t)k, t, f->cur, f->prop, f->q);
+    int rc = launch_pf_weights(h, a, kind, f->q, f->P, f->ang, f->obs + (size_t)k * f->A, f->A, f->lik, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(mcl_weight_kernel, dim3((f->NB + MCL_GROUP - 1) / MCL_GROUP), dim3(MCL_WG), 0, s, mp,
-                       (const double *)f->w.p, (const double *)f->lik.p, (double *)f->omega.p, tot);
-    hipLaunchKernelGGL(mcl_norm_kernel, dim3((f->NB + MCL_NGROUP - 1) / MCL_NGROUP), dim3(MCL_WG), 0, s, mp, (const double *)tot,
-                       (const double *)f->omega.p, (const double *)f->prop.p, (double *)f->w.p, (double *)f->part.p, tot6,
-                       (double *)f->scal.p);
-    hipLaunchKernelGGL(mcl_base_kernel, dim3(1), dim3(64 * MCL_SUMS), 0, s, mp, (const double *)tot6, (const double *)f->scal.p,
-                       (double *)f->base.p, (double *)f->est.p + 4 * (size_t)k, (double *)f->neff.p + k, (int *)f->flags.p + k);
-    hipLaunchKernelGGL(mcl_resample_kernel, dim3(grid), dim3(MCL_WG), 0, s, mp, t, (const int *)f->flags.p + k,
-                       (const double *)f->base.p, (const double *)f->part.p, (const double *)f->prop.p, (double *)f->cur.p,
-                       (double *)f->w.p, (int32_t *)f->anc.p, (double *)f->cum.p);
+    hipLaunchKernelGGL(mcl_weight_kernel, dim3((f->NB + MCL_GROUP - 1) / MCL_GROUP), dim3(MCL_WG), 0, s, mp, f->w, f->lik,
+                       f->omega, tot);
+    hipLaunchKernelGGL(mcl_norm_kernel, dim3((f->NB + MCL_NGROUP - 1) / MCL_NGROUP), dim3(MCL_WG), 0, s, mp, tot, f->omega,
+                       f->prop, f->w, f->part, tot6, f->scal);
+    hipLaunchKernelGGL(mcl_base_kernel, dim3(1), dim3(64 * MCL_SUMS), 0, s, mp, tot6, f->scal, f->base, f->est + 4 * (size_t)k,
+                       f->neff + k, f->flags + k);
+    hipLaunchKernelGGL(mcl_resample_kernel, dim3(grid), dim3(MCL_WG), 0, s, mp, t, f->flags + k, f->base, f->part, f->prop,
+                       f->cur, f->w, f->anc, f->cum);
     HIPCHK(hipGetLastError());
     return RL_OK;
 }
@@ -1945,12 +1913,11 @@ extern "C" int rl_pf_run(rl_pf *f, int n_steps, const double *odom_t3, const flo
     int rc, kind = 0;
     if ((rc = pf_kind_of(h, &kind)) || (rc = set_device(h->map))) return rc;
     const size_t T = (size_t)n_steps;
-    if ((rc = f->odom.ensure(T * 24)) || (rc = f->obs.ensure(T * f->A * 4)) || (rc = f->est.ensure(T * 32)) ||
-        (rc = f->neff.ensure(T * 8)) || (rc = f->flags.ensure(T * 4)))
+    HostCall hc(h->stream);
+    hipStream_t s = hc.st;
+    if ((rc = hc.up(f->odom, odom_t3, T * 3)) || (rc = hc.up(f->obs, obs_tA, T * f->A)) || (rc = hc.room(f->est, T * 4)) ||
+        (rc = hc.room(f->neff, T)) || (rc = hc.room(f->flags, T)))
         return rc;
-    hipStream_t s = h->stream;
-    HIPCHK(hipMemcpyAsync(f->odom.p, odom_t3, T * 24, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(f->obs.p, obs_tA, T * f->A * 4, hipMemcpyHostToDevice, s));
     MclParams mp{f->P, f->NB, 1.0 / (double)f->P, {f->std[0], f->std[1], f->std[2]}, f->ratio * (double)f->P, f->key};
     LaunchArgs a = LaunchArgs::of(h);            // the scans' noise: step t's rays are off + t P A + p A + j
     const uint64_t off = a.ray_offset;
@@ -1959,14 +1926,12 @@ extern "C" int rl_pf_run(rl_pf *f, int n_steps, const double *odom_t3, const flo
         rc = launch_mcl_step(f, a, kind, mp, k, s);
     }
     if (rc) {
-        (void)hipStreamSynchronize(s);
         f->ready = false;                         // part of the steps may have run: the state is no step's; reset again
         return rc;
     }
-    HIPCHK(hipMemcpyAsync(est_t4, f->est.p, T * 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(neff_t, f->neff.p, T * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(flags_t, f->flags.p, T * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    if ((rc = hc.down(est_t4, f->est, T * 4)) || (rc = hc.down(neff_t, f->neff, T)) || (rc = hc.down(flags_t, f->flags, T)) ||
+        (rc = hc.finish()))
+        return rc;
     f->t += n_steps;
     return RL_OK;
 }
@@ -1978,15 +1943,12 @@ extern "C" int rl_pf_read(rl_pf *f, double *particles_p3, double *weights, int32
     if (!f->ready) return fail(RL_ERR_INVALID, "rl_pf_read: the filter has not been reset (rl_pf_reset)");
     int rc = set_device(f->h->map);
     if (rc) return rc;
-    hipStream_t s = f->h->stream;
+    HostCall hc(f->h->stream);
     const size_t P = (size_t)f->P;
-    if (particles_p3) HIPCHK(hipMemcpyAsync(particles_p3, f->cur.p, P * 24, hipMemcpyDeviceToHost, s));
-    if (weights) HIPCHK(hipMemcpyAsync(weights, f->w.p, P * 8, hipMemcpyDeviceToHost, s));
-    if (ancestors) HIPCHK(hipMemcpyAsync(ancestors, f->anc.p, P * 4, hipMemcpyDeviceToHost, s));
-    if (cum) HIPCHK(hipMemcpyAsync(cum, f->cum.p, P * 8, hipMemcpyDeviceToHost, s));
-    if (likelihood) HIPCHK(hipMemcpyAsync(likelihood, f->lik.p, P * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return RL_OK;
+    if ((rc = hc.down(particles_p3, f->cur, P * 3)) || (rc = hc.down(weights, f->w, P)) || (rc = hc.down(ancestors, f->anc, P)) ||
+        (rc = hc.down(cum, f->cum, P)) || (rc = hc.down(likelihood, f->lik, P)))
+        return rc;
+    return hc.finish();
 }
 
 extern "C" int rl_method_read_lut(rl_method *h, int row0, int row1, uint16_t *out)
@@ -2002,11 +1964,9 @@ extern "C" int rl_method_read_lut(rl_method *h, int row0, int row1, uint16_t *ou
         return fail(RL_ERR_INVALID, "row range [%d,%d) outside the map", row0, row1);
     if ((rc = ensure_lut(h, h->stream))) return rc;
     const size_t per_row = (size_t)h->map->cols * h->theta_disc;
-    HIPCHK(hipMemcpyAsync(out, (const uint16_t *)h->lut.p + (size_t)row0 * per_row,
-                          (size_t)(row1 - row0) * per_row * sizeof(uint16_t), hipMemcpyDeviceToHost,
-                          h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return RL_OK;
+    HostCall hc(h->stream);
+    if ((rc = hc.down(out, (const uint16_t *)h->lut.p + (size_t)row0 * per_row, (size_t)(row1 - row0) * per_row))) return rc;
+    return hc.finish();
 }
 
 extern "C" int rl_debug_read_stamps(rl_method *h, uint64_t *out, int max_words)

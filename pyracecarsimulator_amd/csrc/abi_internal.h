@@ -1,6 +1,7 @@
 // abi_internal.h — what the translation units of libscan_amd.so share: the owners of every device resource (DevBuf,
-// DevPtr, Pinned, Stream, Event), the handles behind include/scanlib.h's opaque pointers, the error slot, and the few
-// internal entry points one unit calls in another.
+// DevPtr, Pinned, Stream, Event), HostCall (one synchronous host-pointer call: staging up, results down, the wait, and
+// the drain of a call that is refused on the way), the handles behind include/scanlib.h's opaque pointers, the error
+// slot, and the few internal entry points one unit calls in another.
 //   abi_map.hip    errors, check_device, the caller's pinned host blocks, rl_map_* (EDT, bit map, edge list, stamps)
 //   abi_fan.hip    rl_method_*: options, derived tables, the launch planner's C ABI, every fan / ray launch (told its
 //                  noise offset, store mode and timing by LaunchArgs / FanCall below, not by the handle), the
@@ -107,12 +108,14 @@ struct DevBuf {
     }
 };
 
-// a device array of T, sized in bytes as DevBuf sizes it; reads as the T* the launches take
+// a device array of T; reads as the T* the launches take.  A table is allocated by its bytes, per-call staging is sized
+// by its ELEMENT count (a flattened record by its scalars: R * 11 doubles of car state, n * 3 floats of poses) and grows
+// as DevBuf::ensure grows count * sizeof(T) bytes
 template <class T>
 struct DevPtr {
     DevBuf buf;
     int alloc(size_t bytes) { return buf.alloc(bytes); }
-    int ensure(size_t bytes) { return buf.ensure(bytes); }
+    int ensure(size_t count) { return buf.ensure(count * sizeof(T)); }
     void release() { buf.release(); }
     operator T *() const { return (T *)buf.p; }
 };
@@ -170,6 +173,70 @@ static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_constr
                   !std::is_copy_constructible<Pinned<int>>::value && !std::is_copy_constructible<Stream>::value &&
                   !std::is_copy_constructible<Event>::value,
               "an owner frees what it holds exactly once");
+
+// One synchronous host-pointer call on stream `st`: the caller's arrays go up through a handle's staging, the launches
+// follow on st, the results come down, finish() waits.  Every method is the HIP call it names, enqueued where it stands;
+// counts are elements of T, and T has to agree between the host pointer and the buffer.  A call that returns before
+// finish() — an argument a launch refuses, a failed HIP call — is drained by the destructor: nothing of it is left in
+// flight, neither on the handle's staging nor into the caller's arrays.
+struct HostCall {
+    const hipStream_t st;
+    bool finished = false;
+    explicit HostCall(hipStream_t s) : st(s) {}
+    HostCall(const HostCall &) = delete;
+    HostCall &operator=(const HostCall &) = delete;
+    ~HostCall()
+    {
+        if (!finished) (void)hipStreamSynchronize(st);
+    }
+    template <class T>
+    int room(DevPtr<T> &b, size_t n)             // outputs and scratch: at least n elements
+    {
+        return b.ensure(n);
+    }
+    template <class T>
+    int up(T *dev, const T *host, size_t n)      // into room made before (a buffer's second half)
+    {
+        HIPCHK(hipMemcpyAsync(dev, host, n * sizeof(T), hipMemcpyHostToDevice, st));
+        return RL_OK;
+    }
+    template <class T>
+    int up(DevPtr<T> &b, const T *host, size_t n)
+    {
+        const int rc = b.ensure(n);
+        return rc ? rc : up((T *)b, host, n);
+    }
+    template <class T>
+    int fill(DevPtr<T> &b, int byte, size_t n)   // every byte of n elements (0xff: NaN)
+    {
+        const int rc = b.ensure(n);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync((T *)b, byte, n * sizeof(T), st));
+        return RL_OK;
+    }
+    template <class T>
+    int zero(DevPtr<T> &b, size_t n)
+    {
+        return fill(b, 0, n);
+    }
+    template <class T>
+    int down(T *host_or_null, const T *dev, size_t n)
+    {
+        if (host_or_null) HIPCHK(hipMemcpyAsync(host_or_null, dev, n * sizeof(T), hipMemcpyDeviceToHost, st));
+        return RL_OK;
+    }
+    template <class T>
+    int down(T *host_or_null, const DevPtr<T> &dev, size_t n)
+    {
+        return down(host_or_null, (const T *)dev, n);
+    }
+    int finish()
+    {
+        finished = true;
+        HIPCHK(hipStreamSynchronize(st));
+        return RL_OK;
+    }
+};
 
 // ------------------------------------------------------------------------------
 // handles
@@ -427,13 +494,20 @@ struct rl_method {
     int overlap_min_rays = 1 << 24;      // ... from this many rays per call (0 = never); below ~16 k poses the slices cost more than they hide
     Event ev0, ev1;
     bool timed = false;
-    DevBuf poses, outs, hits, steps, edge, flag;
-    DevBuf cars;                 // rl_calc_range_fan_cars: the cars' (x, y, theta) rows
+    // the host-pointer forms' staging: (x, y, theta) rows, ranges, hit cells (2 per ray), step counts, the car-outline
+    // table, crash indices
+    DevPtr<float> poses, outs;
+    DevPtr<int32_t> hits;
+    DevPtr<uint16_t> steps;
+    DevPtr<double> edge;
+    DevPtr<int> flag;
+    DevPtr<double> cars;         // rl_calc_range_fan_cars: the cars' (x, y, theta) rows
     // particle-filter weights (pf_kernels.h): the sensor-model table (rl_set_sensor_model; width 0 = none set) and the
     // host-pointer forms' staging of angles, observation and weights
     DevPtr<double> sensor;
     int sensor_w = 0;
-    DevBuf pf_ang, pf_obs, pf_w;
+    DevPtr<float> pf_ang, pf_obs;
+    DevPtr<double> pf_w;
     int pf_block = 0;            // particles per tile of the weight kernels (0: sized from the shape, make_pf)
     LaunchCtx ctx[N_LAUNCH_CTX];
     uint64_t use_clock = 0;

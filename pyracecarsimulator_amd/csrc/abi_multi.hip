@@ -109,14 +109,14 @@ static int replica_fan_to_consumer(rl_method *r, const float *poses_blk, int np,
     float *d_poses = nullptr, *d_local = nullptr;
     {
         std::lock_guard<std::mutex> lk(r->mu);
-        if ((rc = r->poses.ensure((size_t)np * 12))) return rc;
-        if (!is_consumer && (rc = r->outs.ensure(n_rays * sizeof(float)))) return rc;
+        if ((rc = r->poses.ensure((size_t)np * 3))) return rc;
+        if (!is_consumer && (rc = r->outs.ensure(n_rays))) return rc;
         if ((rc = ensure_copy_stream(r))) return rc;
-        d_poses = (float *)r->poses.p;
-        d_local = is_consumer ? d_dst : (float *)r->outs.p;
+        d_poses = r->poses;
+        d_local = is_consumer ? d_dst : (float *)r->outs;
     }
     if (!is_consumer) try_peer(dev, consumer_dev);
-    HIPCHK(hipMemcpyAsync(d_poses, poses_blk, (size_t)np * 12, hipMemcpyHostToDevice, r->stream));
+    HIPCHK(hipMemcpyAsync(d_poses, poses_blk, (size_t)np * 3 * sizeof(float), hipMemcpyHostToDevice, r->stream));
     const int k = std::max(1, std::min(chunks, np));
     for (int c = 0; c < k; ++c) {
         long lo, hi;
@@ -150,15 +150,15 @@ static int replica_crash_to_consumer(rl_method *r, const float *poses_blk, int n
     const double *d_edge = nullptr;
     {
         std::lock_guard<std::mutex> lk(r->mu);
-        if ((rc = r->poses.ensure(np * 12)) || (rc = upload_edge(r, edge, num_rays))) return rc;
-        if (!is_consumer && (rc = r->flag.ensure((size_t)n_groups * sizeof(int)))) return rc;
+        if ((rc = r->poses.ensure(np * 3)) || (rc = upload_edge(r, edge, num_rays))) return rc;
+        if (!is_consumer && (rc = r->flag.ensure(n_groups))) return rc;
         if ((rc = ensure_copy_stream(r))) return rc;
-        d_poses = (float *)r->poses.p;
-        d_edge = (const double *)r->edge.p;
-        d_local = is_consumer ? d_dst : (int *)r->flag.p;
+        d_poses = r->poses;
+        d_edge = r->edge;
+        d_local = is_consumer ? d_dst : (int *)r->flag;
     }
     if (!is_consumer) try_peer(dev, consumer_dev);
-    HIPCHK(hipMemcpyAsync(d_poses, poses_blk, np * 12, hipMemcpyHostToDevice, r->stream));
+    HIPCHK(hipMemcpyAsync(d_poses, poses_blk, np * 3 * sizeof(float), hipMemcpyHostToDevice, r->stream));
     if ((rc = rl_check_collision_groups_device(r, d_poses, n_groups, group, fov, num_rays, d_edge, thresh, d_local, nullptr,
                                                (void *)r->stream)))
         return rc;
@@ -309,18 +309,13 @@ extern "C" int rl_check_collision_groups(rl_method *h, const float *poses, int n
     std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
     if ((rc = set_device(h->map))) return rc;
     const size_t n_rays = (size_t)n_poses * num_rays;
-    if ((rc = h->poses.ensure((size_t)n_poses * 12)) || (rc = h->outs.ensure(n_rays * 4)) ||
-        (rc = upload_edge(h, edge, num_rays)) || (rc = h->flag.ensure((size_t)n_groups * 4)))
+    HostCall hc(h->stream);
+    if ((rc = hc.up(h->poses, poses, (size_t)n_poses * 3)) || (rc = hc.room(h->outs, n_rays)) ||
+        (rc = upload_edge(h, edge, num_rays)) || (rc = hc.room(h->flag, n_groups)) ||
+        (rc = crash_groups_device(h, LaunchArgs::of(h), h->poses, n_groups, group, fov, num_rays, h->edge, crash_thresh, h->flag,
+                                  h->outs, hc.st)) ||
+        (rc = hc.down(first_crashed, h->flag, n_groups)) || (rc = hc.down(ranges_or_null, h->outs, n_rays)))
         return rc;
-    HIPCHK(hipMemcpyAsync(h->poses.p, poses, (size_t)n_poses * 12, hipMemcpyHostToDevice, h->stream));
-    rc = crash_groups_device(h, LaunchArgs::of(h), (const float *)h->poses.p, n_groups, group, fov, num_rays,
-                             (const double *)h->edge.p, crash_thresh, (int *)h->flag.p,
-                             (float *)h->outs.p, h->stream);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(first_crashed, h->flag.p, (size_t)n_groups * 4, hipMemcpyDeviceToHost, h->stream));
-    if (ranges_or_null)
-        HIPCHK(hipMemcpyAsync(ranges_or_null, h->outs.p, n_rays * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return RL_OK;
+    return hc.finish();
 }
 

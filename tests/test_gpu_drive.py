@@ -74,29 +74,20 @@ def _ref_libs():
     return L, F
 
 
-def test_drive_teacher_forced_vs_reference(oracle_mod):
-    """Colombia, RMGPU, 32 cars x 150 ticks: at every live tick each link of the loop, fed the GPU's own state of
-    the tick before, agrees with the reference's compiled Car / FollowGap and the oracle scan."""
-    L, F = _ref_libs()
-    g = maps.load_colombia()
-    mrx = 300
-    om = oracle_mod.OracleMap.from_gridmap(g, mrx)
-    m = range_libc.PyRayMarchingGPU(range_libc.PyOMap(g), mrx)
-    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
-    R, T = 32, 150
-    states, speeds = _starts(g, om.dt, R, 3, 6.0, speed_hi=4.0)
-    edge = _edge()
-    cars = RC.CarBatch()
-    first, final, vel, steers, sp, st = cars.drive_followgap(m, fg, states, T, speeds, FOV, B, edge, THRESH, trace=True)
+def _assert_teacher_forced(L, F, om, states, speeds, drive, T, num_rays):
+    """Every link of a traced drive_followgap result, fed the GPU's own state of the tick before, against the reference's
+    compiled Car / FollowGap (libraries L, F of _ref_libs) and the oracle map's scan; returns the crashes seen."""
+    first, final, vel, steers, sp, st = drive
+    R = len(states)
     assert first.shape == (R,) and vel.shape == (R, T) and steers.shape == (R, T) and sp.shape == (R, T, 3)
     assert st.shape == (R, T, 11)
     last = np.where(first >= 0, first, T - 1)
     live = [(r, t) for r in range(R) for t in range(last[r] + 1)]
-    want_r, _, _ = om.rm_fan(np.ascontiguousarray(np.array([sp[r, t] for r, t in live], np.float32)), FOV, B,
+    want_r, _, _ = om.rm_fan(np.ascontiguousarray(np.array([sp[r, t] for r, t in live], np.float32)), FOV, num_rays,
                              step_coeff=1.0, nthreads=8)
-    want_r = want_r.reshape(len(live), B)
+    want_r = want_r.reshape(len(live), num_rays)
     ref = L.ref_car_create((C.c_double * 17)(*[RC.DEFAULT_CAR[k] for k in RC.CAR_PARAM_ORDER]))
-    L.ref_car_set_edge_distances(ref, B, -FOV / 2, FOV / B, D_BASE)
+    L.ref_car_set_edge_distances(ref, num_rays, -FOV / 2, FOV / num_rays, D_BASE)
     buf, pose = (C.c_double * 11)(), (C.c_double * 3)()
     n_crash = 0
     try:
@@ -113,19 +104,35 @@ def test_drive_teacher_forced_vs_reference(oracle_mod):
             L.ref_car_get_scan_pose(ref, D_BASE, pose)
             assert _within_one_ulp(np.array(pose, np.float64).astype(np.float32), sp[r, t]), (r, t)
             rays = np.ascontiguousarray(want_r[k])
-            crashed = L.ref_car_is_crashed(ref, rays.ctypes.data_as(C.POINTER(C.c_float)), B, 1) >= 0
+            crashed = L.ref_car_is_crashed(ref, rays.ctypes.data_as(C.POINTER(C.c_float)), num_rays, 1) >= 0
             assert crashed == (first[r] == t), (r, t)
             if crashed:
                 n_crash += 1
                 assert np.isnan(steers[r, t])
                 continue
-            a = F.ref_followgap_eval(rays.ctypes.data_as(C.POINTER(C.c_float)), B, 10, 15.0, MAX_STEER, 0.004)
+            a = F.ref_followgap_eval(rays.ctypes.data_as(C.POINTER(C.c_float)), num_rays, 10, 15.0, MAX_STEER, 0.004)
             assert np.float32(a).tobytes() == steers[r, t].tobytes(), (r, t)
     finally:
         L.ref_car_destroy(ref)
     # the states out are the last trace rows
     assert _same_bits(final, st[np.arange(R), last])
     assert n_crash == int((first >= 0).sum())
+    return n_crash
+
+
+def test_drive_teacher_forced_vs_reference(oracle_mod):
+    """Colombia, RMGPU, 32 cars x 150 ticks: at every live tick each link of the loop, fed the GPU's own state of
+    the tick before, agrees with the reference's compiled Car / FollowGap and the oracle scan."""
+    L, F = _ref_libs()
+    g = maps.load_colombia()
+    mrx = 300
+    om = oracle_mod.OracleMap.from_gridmap(g, mrx)
+    m = range_libc.PyRayMarchingGPU(range_libc.PyOMap(g), mrx)
+    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    R, T = 32, 150
+    states, speeds = _starts(g, om.dt, R, 3, 6.0, speed_hi=4.0)
+    drive = RC.CarBatch().drive_followgap(m, fg, states, T, speeds, FOV, B, _edge(), THRESH, trace=True)
+    _assert_teacher_forced(L, F, om, states, speeds, drive, T, B)
 
 
 def _maze_methods(omap, mrx):
