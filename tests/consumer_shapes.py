@@ -1,12 +1,13 @@
 """The shapes tests/test_gpu_consumer_shapes.py runs the closed-loop kernels at (drive_tick_kernel<ROWS, *>,
 mcts_act_kernel<ROWS>, the one-lane-per-tree planner kernels, the roll-out reward sum, the fused crash test), as plain
-data and NumPy: no library call.  tests/test_consumer_shapes_host.py checks with the references alone that these inputs
-do what the GPU tests take them to do."""
+data and NumPy (the fixed values are tests/support.py's): no library call.  tests/test_consumer_shapes_host.py checks
+with the references alone that these inputs do what the GPU tests take them to do."""
 import math
 
 import numpy as np
 
-FOV, THRESH, D_BASE = 4.71, 0.001, 0.275
+from support import D_BASE, FOV, THRESH  # noqa: F401  (the cases' fixed values, read as CS.FOV ...)
+
 FG_ROWS = 20                                  # consumer_kernels.h: one instantiation per ROWS = 1 ... FG_ROWS
 MIN_RAYS, MAX_RAYS = 10, 64 * FG_ROWS         # loop_args (every closed loop): num_rays in [10, 1280]
 DRIVE_CARS = 8                                # drive_kernels.h: cars (waves) per workgroup of drive_tick_kernel
@@ -46,12 +47,6 @@ def one_hot_edge(n, j):
     if j is not None:
         edge[j] = 100.0
     return edge
-
-
-def lidar_poses(states):
-    """The f64 lidar pose formula of Car::getScanPose on (R, 11) states, rounded to f32."""
-    x, y, th = states[..., 0], states[..., 1], states[..., 2]
-    return np.stack([x + D_BASE * np.cos(th), y + D_BASE * np.sin(th), th], -1).astype(np.float32)
 
 
 # ---------------------------------------------------------------- part A / B: 19 cars in an empty 10 m room

@@ -13,6 +13,7 @@ Callbacks:
 import numpy as np
 
 from mcts_statement import uniform01
+from support import lidar_poses
 
 RUNNING, CRASHED, TRUNCATED, BAD_ACTION = 0, 1, 2, 3
 
@@ -21,13 +22,6 @@ def spawn_index(seed, e, q, n_starts):
     """Env e's start of episode q: min(M-1, (int)(U(e, q) * (double)M)), U the planner's 53-bit uniform."""
     u = float(uniform01(seed, np.uint64(e), np.uint64(q)))
     return min(int(n_starts) - 1, int(u * float(n_starts)))
-
-
-def lidar_pose(states, scan_dist_to_base):
-    """Car::getScanPose in f64, cast to the f32 lidar pose: (x + d cos th, y + d sin th, th)."""
-    s = np.asarray(states, np.float64).reshape(-1, 11)
-    d = np.float64(scan_dist_to_base)
-    return np.stack([s[:, 0] + d * np.cos(s[:, 2]), s[:, 1] + d * np.sin(s[:, 2]), s[:, 2]], -1).astype(np.float32)
 
 
 def observation(ranges, window, obs_clip, obs_scale):
@@ -63,7 +57,7 @@ class EnvStatement:
     def _observe(self, stepped, fresh, invalid, moved):
         """The scan of slot k and phase B; returns (obs, reward)."""
         N = self.N
-        ranges = np.asarray(self.scan(lidar_pose(self.states, self.d_base), self.k), np.float32).reshape(N, self.B)
+        ranges = np.asarray(self.scan(lidar_poses(self.states, self.d_base), self.k), np.float32).reshape(N, self.B)
         self.ranges = ranges
         reward = np.zeros(N, np.float32)
         for e in range(N):

@@ -8,7 +8,7 @@ sys.path.insert(0, ROOT)
 from pyracecarsimulator_amd import maps, range_libc
 from oracle import oracle as O
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from test_gpu_noise import check_noise
+from noise_checks import check_noise
 
 
 def noisy_launch(r, m, poses, fov, B, want, what):

@@ -5,9 +5,11 @@ import math
 
 import numpy as np
 
+from support import FOV  # noqa: F401  (read as X.FOV)
+
 RES = 0.05
 ORIGIN = (-3.0, 2.0, 0.3)                     # a non-zero origin with a yaw
-FOV, BEAMS = 4.71, 1081
+BEAMS = 1081
 MRX_NEAR, MRX_FAR = 300, 17000                # nothing reaches past 300 cells / rays run the length of the corridor
 # The ray-marching methods pad their step map by the range window on every side and address it in 32 bits: a window
 # of 17000 cells on a 16384-cell map is RL_ERR_UNSUPPORTED (abi_fan.hip ensure_step_map; step_map_cells below).  They

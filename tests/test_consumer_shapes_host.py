@@ -4,10 +4,9 @@ and do steer differently, the roll-out lengths reach the regime of the reward su
 batches hold groups whose first crash is past their first pose, and the generalised helpers of the closed-loop test files still default to the
 shapes their own tests run.
 
-The roll-out velocities of part D come from the reference's compiled Car (oracle/_ref/libracecar_ref.so) driving the
+The roll-out velocities of part D come from the reference's compiled Car (oracle/reference.py) driving the
 statement's trees in an empty room where nothing crashes; the GPU test asserts the same condition again on its own
 replay before it compares."""
-import ctypes as C
 import inspect
 import math
 
@@ -15,7 +14,10 @@ import numpy as np
 import pytest
 
 import consumer_shapes as CS
+import mcts_checks as MC
 import mcts_statement as S
+import support
+from oracle import reference
 from pyracecarsimulator_amd import maps
 from pyracecarsimulator_amd import racecar as RC
 
@@ -66,14 +68,13 @@ def test_whole_loop_cars_crash_and_steer_differently(oracle_mod):
         states, speeds, steer0 = CS.room_starts(n)
         assert states.shape == (CS.R_CARS, 11) and steer0.dtype == np.float32 and len(set(CS.WALL_CARS)) == 6
         assert {r // CS.DRIVE_CARS for r in CS.WALL_CARS} == {0, 1, 2}
-        poses = CS.lidar_poses(states)
+        poses = support.lidar_poses(states)
         if kind == "RMGPU":
             scans = om.rm_fan(poses, CS.FOV, n, step_coeff=1.0)[0]
         else:
             scans = om.rm_fan_libm(poses, CS.FOV, n, step_coeff=0.999)[0]
         scans = scans.reshape(CS.R_CARS, n)
-        edge = oracle_mod.edge_distances(n, -CS.FOV / 2, CS.FOV / n, CS.D_BASE, RC.DEFAULT_CAR["width"],
-                                         RC.DEFAULT_CAR["wb"])
+        edge = support.oracle_edge(oracle_mod, n)
         crashed = np.array([oracle_mod.is_crashed(scans[r], n, 1, edge, CS.THRESH) >= 0 for r in range(CS.R_CARS)])
         assert crashed[list(CS.WALL_CARS)].all(), (n, crashed)
         assert (~crashed).sum() >= 8, (n, crashed)
@@ -86,29 +87,20 @@ def test_whole_loop_cars_crash_and_steer_differently(oracle_mod):
 def _reference_rollouts(L, every):
     """The statement's trees of part D driven by the reference's compiled Car (nothing crashes): every roll-out the
     statement asks for, as (crash index, velocities)."""
-    from test_gpu_drive import _ref_libs
-    lib, _ = _ref_libs()
-    ref = lib.ref_car_create((C.c_double * 17)(*[RC.DEFAULT_CAR[k] for k in RC.CAR_PARAM_ORDER]))
-    buf = (C.c_double * 11)()
+    reference.require()
+    ref = reference.RefCar()
     n_act = (L + every - 1) // every
     states, actions, seeds = CS.big_room_roots()
     K = len(states)
-    trees = [S.Tree(states[k].copy(), CS.lidar_poses(states[k]), math.nan, float(actions[k]), int(seeds[k]),
+    trees = [S.Tree(states[k].copy(), support.lidar_poses(states[k]), math.nan, float(actions[k]), int(seeds[k]),
                     source="random") for k in range(K)]
     rollouts = []
-
-    def step(speed, steer):
-        lib.ref_car_control(ref, float(speed), float(steer))
-        lib.ref_car_update_position(ref, 0.01)
-        lib.ref_car_get_state(ref, buf)
-        return np.array(buf)
 
     def act_many(i, reqs):
         out = []
         for _, node, a in reqs:
-            lib.ref_car_set_state(ref, (C.c_double * 11)(*node.state))
-            st = step(2.0, a)
-            out.append((st, CS.lidar_poses(st), math.nan, False))
+            st = ref.step(node.state, 2.0, a)
+            out.append((st, support.lidar_poses(st), math.nan, False))
         return out
 
     def rollout_many(i, reqs, acts):
@@ -116,8 +108,8 @@ def _reference_rollouts(L, every):
         for k, child in reqs:
             acts_ro = S.rollout_actions(int(seeds[k]), i, n_act, MAX_STEER, MAX_SPEED)
             assert acts_ro.shape == (n_act, 2)
-            lib.ref_car_set_state(ref, (C.c_double * 11)(*child.state))
-            vel = np.array([step(*acts_ro[s // every])[3] for s in range(L)])
+            ref.set_state(child.state)
+            vel = np.array([ref.step(None, *acts_ro[s // every])[3] for s in range(L)])
             out.append((-(L + 1), vel))
         rollouts.extend(out)
         return out
@@ -126,7 +118,7 @@ def _reference_rollouts(L, every):
         S.run_lockstep(trees, CS.ROLLOUT_ITERS, act_many, rollout_many)
         far = max(np.abs(nd.state[:2] - CS.BIG_ROOM * 0.05 / 2).max() for t in trees for nd in t.nodes)
     finally:
-        lib.ref_car_destroy(ref)
+        ref.close()
     assert all(len(t.nodes) == CS.ROLLOUT_ITERS + 1 for t in trees)
     return rollouts, far
 
@@ -165,7 +157,7 @@ def test_crash_batches_hold_groups_crashed_past_their_first_pose(oracle_mod):
     poses = maps.sample_free_poses(g, max(CS.CRASH_POSES), 31, dt=om.dt)
     assert CS.CRASH_POSES == (200, 513) and set(CS.CRASH_CDDT_BEAMS) <= set(CS.CRASH_BEAMS)
     for nb in CS.CRASH_BEAMS:
-        edge = oracle_mod.edge_distances(nb, -CS.FOV / 2, CS.FOV / nb, 0.275, 0.2032, 0.3302) + 0.25
+        edge = support.oracle_edge(oracle_mod, nb) + 0.25
         for n in CS.CRASH_POSES:
             r0 = om.rm_fan(poses[:n], CS.FOV, nb, step_coeff=1.0, nthreads=8, want_hits=False, want_steps=False)[0]
             grp = 40 if n % 40 == 0 else 27
@@ -177,25 +169,23 @@ def test_crash_batches_hold_groups_crashed_past_their_first_pose(oracle_mod):
 
 
 def test_generalised_helpers_default_to_their_files_shapes():
-    """The keyword arguments added to the closed-loop helpers default to the constants their own tests run with."""
-    import test_gpu_drive as TG
-    import test_gpu_mcts as TM
-    import test_gpu_mcts_drive as TD
+    """The keyword arguments of the closed-loop helpers (tests/mcts_checks.py) default to the constants tests/test_gpu_mcts.py
+    and tests/test_gpu_mcts_drive.py run with; the edge table (tests/support.py) takes its beam count from the caller."""
 
     def defaults(fn):
         return {k: p.default for k, p in inspect.signature(fn).parameters.items() if p.default is not inspect.Parameter.empty}
 
-    assert (TG.B, TM.B, TM.L, TM.EVERY, TD.B, TD.L, TD.EVERY) == (1081, 1081, 200, 10, 1081, 40, 10)
-    assert defaults(TG._edge) == {"num_rays": 1081}
-    for fn in (TM._answers, TM._scan):
+    assert (MC.B, MC.L, MC.DRIVE_L, MC.EVERY) == (1081, 200, 40, 10)
+    assert defaults(support.edge) == {"fov": 4.71}
+    for fn in (MC.answers, MC.scan):
         assert defaults(fn) == {"num_rays": 1081}
-    for fn in (TM._replay, TM._device):
+    for fn in (MC.replay, MC.device):
         d = defaults(fn)
         assert (d["num_rays"], d["rollout_steps"], d["action_every"], d["edge"]) == (1081, 200, 10, None), fn
-    assert defaults(TM._replay)["is_crashed"] is RC.is_crashed
-    for fn in (TD._planner, TD._loop_case):
+    assert defaults(MC.replay)["is_crashed"] is RC.is_crashed
+    for fn in (MC.planner, MC.loop_case):
         d = defaults(fn)
         assert (d["num_rays"], d["rollout_steps"], d["action_every"], d["edge"]) == (1081, 40, 10, None), fn
-    d = defaults(TD._host_loop)
+    d = defaults(MC.host_loop)
     assert (d["num_rays"], d["rollout_steps"], d["edge"], d["is_crashed"]) == (1081, 40, None, RC.is_crashed)
-    assert defaults(TD._scan_keep) == {"num_rays": 1081} and defaults(TD._loop_case)["starts"] is None
+    assert defaults(MC.scan_keep) == {"num_rays": 1081} and defaults(MC.loop_case)["starts"] is None

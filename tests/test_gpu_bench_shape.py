@@ -15,12 +15,7 @@ from conftest import ROOT
 from pyracecarsimulator_amd import _lib, range_libc, workloads
 from pyracecarsimulator_amd.pipeline import concurrent_streams
 
-pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
 
 def test_cfg2_bench_shape_four_batches_in_flight_bit_equal_to_oracle(oracle_mod):

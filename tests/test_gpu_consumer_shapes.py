@@ -18,30 +18,23 @@ import numpy as np
 import pytest
 
 import consumer_shapes as CS
+import drive_cases as DC
+import mcts_checks as MC
 import policy_statement as PS
 import race_statement as RS
-import test_gpu_mcts as TM
-import test_gpu_mcts_drive as TD
-import test_gpu_race as TR
+import support
 from conftest import GOLD
-from test_gpu_drive import _edge, _same_bits, _within_one_ulp
+from support import D_BASE, FOV, MAX_STEER, THRESH, same_bits, within_one_ulp
 from pyracecarsimulator_amd import Policy, _lib, maps, range_libc
 from pyracecarsimulator_amd import racecar as RC
-from pyracecarsimulator_amd.followgap import PyFollowGap
 from pyracecarsimulator_amd.mcts import MCTSPlanner
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
-FOV, THRESH, D_BASE = CS.FOV, CS.THRESH, CS.D_BASE
-MAX_STEER = RC.DEFAULT_CAR["max_steer_ang"]
 MRX = 300
 R = CS.R_CARS
-CLIP = 0.4189
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
+CLIP = MC.CLIP
+RL_ERR_UNSUPPORTED = -4                               # include/scanlib.h rl_status
 
 
 class Room:
@@ -54,7 +47,7 @@ class Room:
         self.omap = range_libc.PyOMap(self.g)
         self.m = {"RMGPU": range_libc.PyRayMarchingGPU(self.omap, MRX), "RM": range_libc.PyRayMarching(self.omap, MRX)}
         self.cars = RC.CarBatch()
-        self.fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+        self.fg = support.followgap()
 
     def oracle_scan(self, poses, n):
         return self.om.rm_fan(np.ascontiguousarray(poses, np.float32), FOV, n, step_coeff=1.0)[0].reshape(-1, n)
@@ -93,13 +86,13 @@ def _ballot(room, n, run, answer):
         assert first.shape == (R,) and steers.shape == (R, 1) and st.shape == (R, 1, 11)
         if scans is None:
             poses0, scans = sp[:, 0].copy(), room.oracle_scan(sp[:, 0], n)
-        assert _same_bits(sp[:, 0], poses0), (n, j)
+        assert same_bits(sp[:, 0], poses0), (n, j)
         want = [0 if room.O.is_crashed(scans[r], n, 1, edge, THRESH) >= 0 else -2 for r in range(R)]
         assert want == [0 if j is not None else -2] * R, (n, j)          # what the table was built to decide
         assert first.tolist() == want, (n, j, rows)
-        assert np.isfinite(st).all() and _same_bits(final, st[:, 0]) and _same_bits(vel[:, 0], st[:, 0, 3]), (n, j)
+        assert np.isfinite(st).all() and same_bits(final, st[:, 0]) and same_bits(vel[:, 0], st[:, 0, 3]), (n, j)
         if j is None:
-            assert _same_bits(steers[:, 0], np.array([answer(scans[r]) for r in range(R)], np.float32)), (n, j)
+            assert same_bits(steers[:, 0], np.array([answer(scans[r]) for r in range(R)], np.float32)), (n, j)
         else:
             assert np.isnan(steers).all(), (n, j)
 
@@ -145,9 +138,9 @@ def _ballot_mcts(room, n, source, h):
     shape = dict(num_rays=n, rollout_steps=MCTS_L, action_every=MCTS_EVERY)
     for j in CS.one_hot_beams(n) + (None,):
         edge = CS.one_hot_edge(n, j)
-        pl, trees, best = TM._device(room.cars, m, 0.0, 0, source, h, states, actions, seeds, MCTS_IT, edge=edge, **shape)
+        pl, trees, best = MC.device(room.cars, m, 0.0, 0, source, h, states, actions, seeds, MCTS_IT, edge=edge, **shape)
         pl.close()
-        stmt, snaps = TM._replay(room.cars, m, 0.0, 0, source, h, states, actions, seeds, MCTS_IT, trees, (MCTS_IT,),
+        stmt, snaps = MC.replay(room.cars, m, 0.0, 0, source, h, states, actions, seeds, MCTS_IT, trees, (MCTS_IT,),
                                  edge=edge, is_crashed=room.O.is_crashed, **shape)
         for k in range(MCTS_K):
             t = snaps[MCTS_IT][k]
@@ -156,9 +149,9 @@ def _ballot_mcts(room, n, source, h):
             else:
                 assert t["terminal"].tolist() == [0] + [1] * MCTS_IT, (n, j, k)
                 assert (t["parent"] > 0).any(), "no expansion under a terminal node"
-            TM._assert_tree(trees[k], t, (source, n, j, k))
+            MC.assert_tree(trees[k], t, (source, n, j, k))
             a, v = stmt[k].best()
-            assert best[1][k] == v and _same_bits(best[0][k:k + 1], np.array([a])), (n, j, k)
+            assert best[1][k] == v and same_bits(best[0][k:k + 1], np.array([a])), (n, j, k)
 
 
 @pytest.mark.parametrize("n", CS.SIZES)
@@ -189,9 +182,9 @@ def _host_drive(room, m, std, base, n, states, speeds, steer0, T, edge, got, ans
             assert np.isnan(arr[dead, t]).all(), (n, t)                # rows after a crash stay NaN
         _, out, v1 = room.cars.rollout(cur[idx], np.stack([speeds[idx], steer[idx]], -1)[:, None, :], n_steps=1,
                                        action_every=1)
-        assert _same_bits(out, st[idx, t]) and _same_bits(v1[:, 0], vel[idx, t]), (n, t)
+        assert same_bits(out, st[idx, t]) and same_bits(v1[:, 0], vel[idx, t]), (n, t)
         cur[idx] = out
-        assert _within_one_ulp(CS.lidar_poses(out), sp[idx, t]), (n, t)
+        assert within_one_ulp(support.lidar_poses(out), sp[idx, t]), (n, t)
         last_pose[idx] = sp[idx, t]                                    # frozen cars keep their last pose
         m.set_noise(std, 99, base + t * N * n)
         if scan is None:
@@ -207,12 +200,12 @@ def _host_drive(room, m, std, base, n, states, speeds, steer0, T, edge, got, ans
         go = idx[~crashed]
         if go.size:
             a = answer(ranges[go])
-            assert _same_bits(a, steers[go, t]), (n, t, np.nonzero(a != steers[go, t]))
+            assert same_bits(a, steers[go, t]), (n, t, np.nonzero(a != steers[go, t]))
             steer[go] = steer_of(a)
         alive[idx[crashed]] = False
     m.set_noise(0.0, 0, 0)
     assert first.tolist() == want_first.tolist(), n
-    assert _same_bits(final, cur), n
+    assert same_bits(final, cur), n
     return want_first
 
 
@@ -226,7 +219,7 @@ def test_loop_drive_followgap(room, n):
     assert (kind == "RMGPU") == bool(rows % 2) and (std > 0) == (kind == "RMGPU")
     m = room.m[kind]
     states, speeds, steer0 = CS.room_starts(n)
-    edge, base = _edge(n), 5 * R * n + 3
+    edge, base = support.edge(n), 5 * R * n + 3
     assert n == 1081 or base + R * n != base + R * 1081                # the noise walk depends on the beam count
     m.set_noise(std, 99, base)
     got = room.cars.drive_followgap(m, room.fg, states, T_LOOP, speeds, FOV, n, edge, THRESH, steer0=steer0, trace=True)
@@ -245,7 +238,7 @@ def test_loop_drive_policy(room, nets, n, in_start):
     kind, std = CS.room_method(n)
     m = room.m[kind]
     states, speeds, steer0 = CS.room_starts(n)
-    edge, base = _edge(n), 2 * R * n + 1
+    edge, base = support.edge(n), 2 * R * n + 1
     m.set_noise(std, 99, base)
     got = room.cars.drive_policy(m, pol, states, T_LOOP, speeds, FOV, n, edge, THRESH, steer0=steer0, steer_clip=clip,
                                  trace=True)
@@ -279,7 +272,7 @@ def test_loop_race_followgap(room, n):
     kind, std = ("RM", 0.0) if n == 720 else ("RMGPU", 0.05)           # (noise on: the offset walks by t R n here too)
     assert n <= CS.MAX_RAYS and CS.rows_of(n) in (2, 12, 20)
     m = room.m[kind]
-    edge = _edge(n)
+    edge = support.edge(n)
     firsts = []
     for n_races, group, seed in ((2, 3, 7 + n), (1, 8, 8 + n)):
         states, speeds, steer0, N = _race_states(n_races, group, seed)
@@ -300,20 +293,21 @@ def test_loop_race_followgap(room, n):
 def test_fan_cars_equal_the_oracle_on_the_stamped_grid(oracle_mod, kind, variant, nb):
     """calc_range_fan_cars (the race loop's reference above) against stamp-and-scan at 65 and 1280 beams, group 4."""
     assert nb not in (360, 1081) and CS.MIN_RAYS <= nb <= CS.MAX_RAYS        # (the sizes test_gpu_race.py pins it at)
-    g = TR._maze()
+    g = DC.race_maze()
     dt = oracle_mod.edt(g.occ)
     m = (range_libc.PyRayMarching if kind == "RM" else range_libc.PyRayMarchingGPU)(range_libc.PyOMap(g), MRX)
     m.set_option("variant", variant)
     group = 4
-    cars = TR._clusters(g, dt, 3, group, 13)
-    poses = TR._lidar(cars)
+    cars = DC.race_clusters(g, dt, 3, group, 13)
+    poses = support.lidar_poses(cars)
     N = poses.shape[0]
     hits, steps = np.empty((N * nb, 2), np.int32), np.empty(N * nb, np.uint16)
     outs = m.calc_range_fan_cars(poses, cars, group, FOV, nb, hit_cells=hits, steps=steps)
-    cells = RS.outline_cells(cars, TR.L, TR.W, g.resolution, g.origin, g.rows, g.cols, oracle_mod.sincosf)
-    want_r, want_h, want_s = TR._oracle_fan(oracle_mod, g, cells, group, poses, nb, variant == 3,
+    cells = RS.outline_cells(cars, RC.DEFAULT_CAR["length"], RC.DEFAULT_CAR["width"], g.resolution, g.origin, g.rows,
+                            g.cols, oracle_mod.sincosf)
+    want_r, want_h, want_s = DC.race_oracle_fan(oracle_mod, g, cells, group, poses, nb, variant == 3,
                                             0.999 if kind == "RM" else 1.0)
-    assert _same_bits(outs, want_r) and _same_bits(hits, want_h.reshape(-1, 2)) and _same_bits(steps, want_s)
+    assert same_bits(outs, want_r) and same_bits(hits, want_h.reshape(-1, 2)) and same_bits(steps, want_s)
     plain = np.empty(N * nb, np.float32)
     m.calc_range_fan(poses, plain, FOV, nb)
     assert (outs != plain).sum() > 10                                  # the other cars are seen
@@ -325,7 +319,7 @@ def maze():
     g = maps.make_maze(256, cell=40, wall=3, p=0.45, seed=11)
     omap = range_libc.PyOMap(g)
     return {"g": g, "omap": omap, "dt": omap.distance_transform(), "m": range_libc.PyRayMarchingGPU(omap, MRX),
-            "cars": RC.CarBatch(), "fg": PyFollowGap(10, 15.0, MAX_STEER, 0.004)}
+            "cars": RC.CarBatch(), "fg": support.followgap()}
 
 
 @pytest.mark.parametrize("source", ["fg", "random"])
@@ -336,24 +330,24 @@ def test_trees_beyond_one_workgroup(maze, K, source):
     cars, m, h = maze["cars"], maze["m"], maze["fg"] if source == "fg" else None
     n_it, nb, std, base = 10, 65, 0.05, 4242
     shape = dict(num_rays=nb, rollout_steps=20, action_every=10)
-    states, actions, seeds = TM._roots(maze["g"], maze["dt"], K, 200 + K)
-    pl, trees, best = TM._device(cars, m, std, base, source, h, states, actions, seeds, n_it, **shape)
+    states, actions, seeds = MC.roots(maze["g"], maze["dt"], K, 200 + K)
+    pl, trees, best = MC.device(cars, m, std, base, source, h, states, actions, seeds, n_it, **shape)
     pl.close()
-    stmt, snaps = TM._replay(cars, m, std, base, source, h, states, actions, seeds, n_it, trees, (n_it,), **shape)
+    stmt, snaps = MC.replay(cars, m, std, base, source, h, states, actions, seeds, n_it, trees, (n_it,), **shape)
     for k in range(K):
-        TM._assert_tree(trees[k], snaps[n_it][k], (source, K, k))
+        MC.assert_tree(trees[k], snaps[n_it][k], (source, K, k))
         a, v = stmt[k].best()
-        assert best[1][k] == v and _same_bits(best[0][k:k + 1], np.array([a])) and best[2][k] == n_it + 1, (K, k)
+        assert best[1][k] == v and same_bits(best[0][k:k + 1], np.array([a])) and best[2][k] == n_it + 1, (K, k)
     # a tree alone with its seed equals its copy in the batch (noise off: the ray ids depend on K)
     alone = [k for k in CS.ALONE_TREES if k < K]
     assert alone and min(alone) >= 64
-    pl, batch, _ = TM._device(cars, m, 0.0, 0, source, h, states, actions, seeds, n_it, **shape)
+    pl, batch, _ = MC.device(cars, m, 0.0, 0, source, h, states, actions, seeds, n_it, **shape)
     pl.close()
     for k in alone:
-        pl, one, _ = TM._device(cars, m, 0.0, 0, source, h, states[k:k + 1], actions[k:k + 1], seeds[k:k + 1], n_it,
+        pl, one, _ = MC.device(cars, m, 0.0, 0, source, h, states[k:k + 1], actions[k:k + 1], seeds[k:k + 1], n_it,
                                 **shape)
         pl.close()
-        TM._assert_tree(one[0], batch[k], ("alone", K, k))
+        MC.assert_tree(one[0], batch[k], ("alone", K, k))
     m.set_noise(0.0, 0, 0)
 
 
@@ -371,32 +365,32 @@ def test_drive_cars_beyond_one_workgroup(room):
     recent = rng.uniform(-0.3, 0.3, K)
     seeds = rng.integers(0, 2 ** 63, K, dtype=np.uint64)
     world = {"cars": room.cars, "g": room.g, "dt": None}
-    first, out, rec, actions, visits, trace = TD._loop_case(
-        world, room.m["RMGPU"], 0.05, "fg", room.fg, K, S_, D, I, num_rays=nb, rollout_steps=TD.L,
+    first, out, rec, actions, visits, trace = MC.loop_case(
+        world, room.m["RMGPU"], 0.05, "fg", room.fg, K, S_, D, I, num_rays=nb, rollout_steps=MC.DRIVE_L,
         starts=(states, recent, seeds), is_crashed=room.O.is_crashed)
     assert first[66] == 0 and 1 <= first[68] < D and (first[:64] < 0).any(), first
     for k in (66, 68):
         d = int(first[k])
         assert np.isnan(actions[k, d:]).all() and (visits[k, d:] == -1).all() and np.isnan(trace[k, d:]).all()
         assert np.isfinite(actions[k, :d]).all() and (visits[k, :d] >= 1).all()
-    assert _same_bits(out[66], states[66]) and _same_bits(rec[66], recent[66])
+    assert same_bits(out[66], states[66]) and same_bits(rec[66], recent[66])
     d = int(first[68]) - 1                                             # frozen in the state its last live decision stepped to
-    _, want, _ = room.cars.rollout(trace[68, d][None, :], np.array([[[TD.SPEED, actions[68, d]]]]), n_steps=S_,
+    _, want, _ = room.cars.rollout(trace[68, d][None, :], np.array([[[MC.SPEED, actions[68, d]]]]), n_steps=S_,
                                    action_every=S_)
-    assert _same_bits(out[68], want[0]) and rec[68] == np.clip(actions[68, d], -TD.CLIP, TD.CLIP)
+    assert same_bits(out[68], want[0]) and rec[68] == np.clip(actions[68, d], -MC.CLIP, MC.CLIP)
     # the one-hot table of part A on the cars beyond the first workgroup alone: the table is per call, so this is a second
     # call with the same seeds, and every car is crashed at decision 0
     tail = slice(64, K)
     n_tail = K - 64
     edge = CS.one_hot_edge(nb, nb - 1)
-    pl = TD._planner(room.cars, room.m["RMGPU"], n_tail, I, "fg", room.fg, num_rays=nb, edge=edge)
+    pl = MC.planner(room.cars, room.m["RMGPU"], n_tail, I, "fg", room.fg, num_rays=nb, edge=edge)
     try:
         f2, out2, rec2, act2, vis2 = pl.drive(states[tail], recent[tail], seeds[tail], D, I, steps_per_decision=S_,
-                                              steer_clip=TD.CLIP)
+                                              steer_clip=MC.CLIP)
     finally:
         pl.close()
     assert (f2 == 0).all() and np.isnan(act2).all() and (vis2 == -1).all()
-    assert _same_bits(out2, states[tail]) and _same_bits(rec2, recent[tail])
+    assert same_bits(out2, states[tail]) and same_bits(rec2, recent[tail])
 
 
 # ---------------------------------------------------------------- D. roll-out lengths
@@ -419,16 +413,16 @@ def test_rollout_lengths(big_room, L, every):
     assert (n_act * every != L) == ((L, every) in ((7, 3), (128, 10), (129, 10), (257, 16), (300, 7)))
     states, actions, seeds = CS.big_room_roots()
     shape = dict(num_rays=nb, rollout_steps=L, action_every=every)
-    pl, trees, best = TM._device(cars, m, 0.0, 0, "random", None, states, actions, seeds, n_it, **shape)
+    pl, trees, best = MC.device(cars, m, 0.0, 0, "random", None, states, actions, seeds, n_it, **shape)
     pl.close()
     rollouts = []
-    stmt, snaps = TM._replay(cars, m, 0.0, 0, "random", None, states, actions, seeds, n_it, trees, (n_it,),
+    stmt, snaps = MC.replay(cars, m, 0.0, 0, "random", None, states, actions, seeds, n_it, trees, (n_it,),
                              rollouts=rollouts, **shape)
     CS.assert_rollout_regime(L, every, rollouts)
     for k in range(K):
-        TM._assert_tree(trees[k], snaps[n_it][k], (L, every, k))
+        MC.assert_tree(trees[k], snaps[n_it][k], (L, every, k))
         a, v = stmt[k].best()
-        assert best[1][k] == v and _same_bits(best[0][k:k + 1], np.array([a])), (L, every, k)
+        assert best[1][k] == v and same_bits(best[0][k:k + 1], np.array([a])), (L, every, k)
     m.set_noise(0.0, 0, 0)
 
 
@@ -437,9 +431,9 @@ def test_rollout_length_limits(big_room):
     cars, m = big_room["cars"], big_room["m"]
     for L in (0, 513):
         with pytest.raises(_lib.ScanLibError, match="rollout_steps"):
-            MCTSPlanner(cars, m, 2, 4, FOV, 65, _edge(65), THRESH, source="random", rollout_steps=L)
+            MCTSPlanner(cars, m, 2, 4, FOV, 65, support.edge(65), THRESH, source="random", rollout_steps=L)
     for L in (1, 512):
-        MCTSPlanner(cars, m, 2, 4, FOV, 65, _edge(65), THRESH, source="random", rollout_steps=L).close()
+        MCTSPlanner(cars, m, 2, 4, FOV, 65, support.edge(65), THRESH, source="random", rollout_steps=L).close()
 
 
 # ---------------------------------------------------------------- E. the crash test at other beam counts
@@ -470,7 +464,7 @@ def crash(oracle_mod):
 
 
 def _wide_edge(nb):
-    return RC.edge_distances(nb, -FOV / 2, FOV / nb, 0.275, 0.2032, 0.3302) + 0.25       # wide car: many crashes
+    return support.edge(nb) + 0.25       # wide car: many crashes
 
 
 def _crash_cases():
@@ -493,7 +487,7 @@ def test_crash_test_at_other_beam_counts(crash, kind, nb):
         want = crash.O.is_crashed(r0, nb, n, edge, THRESH)
         assert m.check_collision_many(poses, FOV, nb, edge, THRESH) == want, (kind, nb, n)
         kept = np.empty(n * nb, np.float32)
-        assert m.check_collision_many(poses, FOV, nb, edge, THRESH, ranges=kept) == want and _same_bits(kept, r0)
+        assert m.check_collision_many(poses, FOV, nb, edge, THRESH, ranges=kept) == want and same_bits(kept, r0)
         assert m.check_collision_many(poses, FOV, nb, np.full(nb, -100.0), THRESH) == -(n + 1)
         grp = 40 if n % 40 == 0 else 27
         assert n % grp == 0
@@ -514,7 +508,7 @@ def test_literal_handle_refuses_the_crash_test_below_64_beams(crash, maze, nb):
     g, dt, cars, fg = maze["g"], maze["dt"], maze["cars"], maze["fg"]
     m = range_libc.PyRayMarching(maze["omap"], MRX)
     K, n_it = 4, 3
-    states, actions, seeds = TM._roots(g, dt, K, 9)
+    states, actions, seeds = MC.roots(g, dt, K, 9)
     probe = maps.sample_free_poses(g, 8, 3, 4.0, dt)
 
     def probes():
@@ -525,14 +519,15 @@ def test_literal_handle_refuses_the_crash_test_below_64_beams(crash, maze, nb):
 
     before = probes()
     with pytest.raises(_lib.ScanLibError) as e:
-        m.check_collision_many(probe, FOV, nb, _edge(nb), THRESH)
-    assert e.value.code == TR.RL_ERR_UNSUPPORTED
-    pl = MCTSPlanner(cars, m, K, n_it + 1, FOV, nb, _edge(nb), THRESH, source="fg", followgap=fg, rollout_steps=20)
+        m.check_collision_many(probe, FOV, nb, support.edge(nb), THRESH)
+    assert e.value.code == RL_ERR_UNSUPPORTED
+    pl = MCTSPlanner(cars, m, K, n_it + 1, FOV, nb, support.edge(nb), THRESH, source="fg", followgap=fg,
+                     rollout_steps=20)
     try:
         pl.reset(states, actions, seeds)
         with pytest.raises(_lib.ScanLibError) as e:
             pl.run(1)
-        assert e.value.code == TR.RL_ERR_UNSUPPORTED
+        assert e.value.code == RL_ERR_UNSUPPORTED
         with pytest.raises(_lib.ScanLibError, match="reset"):          # rl_mcts_run cleared `ready`
             pl.run(1)
         with pytest.raises(_lib.ScanLibError, match="reset"):
@@ -542,10 +537,10 @@ def test_literal_handle_refuses_the_crash_test_below_64_beams(crash, maze, nb):
     finally:
         pl.close()
     for a, b in zip(probes(), before):
-        assert _same_bits(a, b)
+        assert same_bits(a, b)
     shape = dict(num_rays=64, rollout_steps=20, action_every=10)
-    pl, trees, best = TM._device(cars, m, 0.0, 0, "fg", fg, states, actions, seeds, n_it, **shape)
+    pl, trees, best = MC.device(cars, m, 0.0, 0, "fg", fg, states, actions, seeds, n_it, **shape)
     pl.close()
-    _, snaps = TM._replay(cars, m, 0.0, 0, "fg", fg, states, actions, seeds, n_it, trees, (n_it,), **shape)
+    _, snaps = MC.replay(cars, m, 0.0, 0, "fg", fg, states, actions, seeds, n_it, trees, (n_it,), **shape)
     for k in range(K):
-        TM._assert_tree(trees[k], snaps[n_it][k], ("RM at 64 beams", k))
+        MC.assert_tree(trees[k], snaps[n_it][k], ("RM at 64 beams", k))

@@ -13,15 +13,11 @@ import sys
 import numpy as np
 import pytest
 
+import support
 from conftest import ROOT
 from pyracecarsimulator_amd import maps
 
-pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
 
 def _free_port():
@@ -106,7 +102,6 @@ def test_reduced_exchanges_equal_the_unsharded_result(oracle_mod, tmp_path, worl
     order (crash: also the reference-pinned host isCrashed over the oracle-equal ranges; steer: also the CPU
     restatement of FollowGap::eval)."""
     from pyracecarsimulator_amd import racecar as RC, range_libc
-    from pyracecarsimulator_amd.followgap import PyFollowGap
     n_total, B, GROUP = 640, 1081, 20
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
@@ -118,7 +113,7 @@ def test_reduced_exchanges_equal_the_unsharded_result(oracle_mod, tmp_path, worl
     om = oracle_mod.OracleMap.from_gridmap(g, 300)
     omap = range_libc.PyOMap(g)
     m = range_libc.PyRayMarchingGPU(omap, 300)
-    edge = RC.edge_distances(B, -4.71 / 2.0, 4.71 / B, 0.275, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
+    edge = support.edge(B)
     want = []
     for k in range(2):
         poses_all = maps.sample_free_poses(g, n_total, 5 + k)
@@ -130,7 +125,7 @@ def test_reduced_exchanges_equal_the_unsharded_result(oracle_mod, tmp_path, worl
             assert np.array_equal(first, host)
             want.append(first)
         else:
-            fg = PyFollowGap(10, 15.0, RC.DEFAULT_CAR["max_steer_ang"], 0.004)
+            fg = support.followgap()
             ang = fg.eval_many(ranges, B)
             ref = np.array([oracle_mod.followgap_eval(ranges[i * B:(i + 1) * B], 15.0, RC.DEFAULT_CAR["max_steer_ang"], 0.004)
                             for i in range(n_total)], np.float32)

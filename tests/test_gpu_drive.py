@@ -4,143 +4,35 @@ steering — pinned against the reference's compiled Car and FollowGap and again
 the existing public calls."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import support
+from drive_cases import assert_teacher_forced
+from oracle import reference
+from support import D_BASE, FOV, THRESH, same_bits, within_one_ulp
 from pyracecarsimulator_amd import RacecarSimulator, _lib, maps, range_libc
 from pyracecarsimulator_amd import racecar as RC
-from pyracecarsimulator_amd.followgap import PyFollowGap
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
-FOV, B, THRESH, D_BASE = 4.71, 1081, 0.001, 0.275
-MAX_STEER = RC.DEFAULT_CAR["max_steer_ang"]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
-
-
-def _edge(num_rays=B):
-    return RC.edge_distances(num_rays, -FOV / 2, FOV / num_rays, D_BASE, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
-
-
-def _starts(g, dt, n, seed, clear_px, speed_hi=7.0):
-    rng = np.random.default_rng(seed)
-    states = np.zeros((n, 11))
-    states[:, :3] = maps.sample_free_poses(g, n, seed, clear_px, dt)
-    speeds = rng.uniform(1.0, speed_hi, n)
-    states[:, 3] = rng.uniform(0.0, 1.0, n) * speeds
-    return states, speeds
-
-
-def _within_one_ulp(a, b):
-    a = np.asarray(a, np.float32)
-    b = np.asarray(b, np.float32)
-    d = np.abs(a.astype(np.float64) - b.astype(np.float64))
-    return bool((d <= np.spacing(np.maximum(np.abs(a), np.abs(b)))).all())
-
-
-def _same_bits(a, b):
-    return np.asarray(a).tobytes() == np.asarray(b).tobytes()
-
-
-def _ref_libs():
-    car_so = os.path.join(ROOT, "oracle/_ref/libracecar_ref.so")
-    fg_so = os.path.join(ROOT, "oracle/_ref/libfollowgap_ref.so")
-    missing = [p for p in (car_so, fg_so) if not os.path.exists(p)]
-    if missing:
-        pytest.fail("reference builds missing (build() makes them): %s" % missing)
-    L = C.CDLL(car_so)
-    d, vp, dp = C.c_double, C.c_void_p, C.POINTER(C.c_double)
-    L.ref_car_create.restype = vp
-    L.ref_car_create.argtypes = [dp]
-    L.ref_car_destroy.argtypes = [vp]
-    L.ref_car_control.argtypes = [vp, d, d]
-    L.ref_car_update_position.argtypes = [vp, d]
-    L.ref_car_get_state.argtypes = [vp, dp]
-    L.ref_car_set_state.argtypes = [vp, dp]
-    L.ref_car_get_scan_pose.argtypes = [vp, d, dp]
-    L.ref_car_set_edge_distances.argtypes = [vp, C.c_int, d, d, d]
-    L.ref_car_is_crashed.restype = C.c_int
-    L.ref_car_is_crashed.argtypes = [vp, C.POINTER(C.c_float), C.c_int, C.c_int]
-    F = C.CDLL(fg_so)
-    F.ref_followgap_eval.restype = C.c_float
-    F.ref_followgap_eval.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]
-    return L, F
-
-
-def _assert_teacher_forced(L, F, om, states, speeds, drive, T, num_rays):
-    """Every link of a traced drive_followgap result, fed the GPU's own state of the tick before, against the reference's
-    compiled Car / FollowGap (libraries L, F of _ref_libs) and the oracle map's scan; returns the crashes seen."""
-    first, final, vel, steers, sp, st = drive
-    R = len(states)
-    assert first.shape == (R,) and vel.shape == (R, T) and steers.shape == (R, T) and sp.shape == (R, T, 3)
-    assert st.shape == (R, T, 11)
-    last = np.where(first >= 0, first, T - 1)
-    live = [(r, t) for r in range(R) for t in range(last[r] + 1)]
-    want_r, _, _ = om.rm_fan(np.ascontiguousarray(np.array([sp[r, t] for r, t in live], np.float32)), FOV, num_rays,
-                             step_coeff=1.0, nthreads=8)
-    want_r = want_r.reshape(len(live), num_rays)
-    ref = L.ref_car_create((C.c_double * 17)(*[RC.DEFAULT_CAR[k] for k in RC.CAR_PARAM_ORDER]))
-    L.ref_car_set_edge_distances(ref, num_rays, -FOV / 2, FOV / num_rays, D_BASE)
-    buf, pose = (C.c_double * 11)(), (C.c_double * 3)()
-    n_crash = 0
-    try:
-        for k, (r, t) in enumerate(live):
-            prev = states[r] if t == 0 else st[r, t - 1]
-            steer_in = 0.0 if t == 0 else float(steers[r, t - 1])
-            L.ref_car_set_state(ref, (C.c_double * 11)(*prev))
-            L.ref_car_control(ref, float(speeds[r]), steer_in)
-            L.ref_car_update_position(ref, 0.01)
-            L.ref_car_get_state(ref, buf)
-            assert np.allclose(st[r, t], np.array(buf), rtol=1e-9, atol=1e-9), (r, t)
-            assert vel[r, t] == st[r, t, 3]
-            L.ref_car_set_state(ref, (C.c_double * 11)(*st[r, t]))
-            L.ref_car_get_scan_pose(ref, D_BASE, pose)
-            assert _within_one_ulp(np.array(pose, np.float64).astype(np.float32), sp[r, t]), (r, t)
-            rays = np.ascontiguousarray(want_r[k])
-            crashed = L.ref_car_is_crashed(ref, rays.ctypes.data_as(C.POINTER(C.c_float)), num_rays, 1) >= 0
-            assert crashed == (first[r] == t), (r, t)
-            if crashed:
-                n_crash += 1
-                assert np.isnan(steers[r, t])
-                continue
-            a = F.ref_followgap_eval(rays.ctypes.data_as(C.POINTER(C.c_float)), num_rays, 10, 15.0, MAX_STEER, 0.004)
-            assert np.float32(a).tobytes() == steers[r, t].tobytes(), (r, t)
-    finally:
-        L.ref_car_destroy(ref)
-    # the states out are the last trace rows
-    assert _same_bits(final, st[np.arange(R), last])
-    assert n_crash == int((first >= 0).sum())
-    return n_crash
+B = 1081
 
 
 def test_drive_teacher_forced_vs_reference(oracle_mod):
     """Colombia, RMGPU, 32 cars x 150 ticks: at every live tick each link of the loop, fed the GPU's own state of
     the tick before, agrees with the reference's compiled Car / FollowGap and the oracle scan."""
-    L, F = _ref_libs()
+    reference.require()
     g = maps.load_colombia()
     mrx = 300
     om = oracle_mod.OracleMap.from_gridmap(g, mrx)
     m = range_libc.PyRayMarchingGPU(range_libc.PyOMap(g), mrx)
-    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    fg = support.followgap()
     R, T = 32, 150
-    states, speeds = _starts(g, om.dt, R, 3, 6.0, speed_hi=4.0)
-    drive = RC.CarBatch().drive_followgap(m, fg, states, T, speeds, FOV, B, _edge(), THRESH, trace=True)
-    _assert_teacher_forced(L, F, om, states, speeds, drive, T, B)
-
-
-def _maze_methods(omap, mrx):
-    return [("RM", range_libc.PyRayMarching(omap, mrx), 0.0),
-            ("RMGPU", range_libc.PyRayMarchingGPU(omap, mrx), 0.05),
-            ("CDDT", range_libc.PyCDDTCast(omap, mrx, 112), 0.0),
-            ("GiantLUT", range_libc.PyGiantLUTCast(omap, mrx, 112), 0.0),
-            ("Bresenham", range_libc.PyBresenhamsLine(omap, mrx), 0.0)]
+    states, speeds = support.starts(g, om.dt, R, 3, 6.0, speed_hi=4.0)
+    drive = RC.CarBatch().drive_followgap(m, fg, states, T, speeds, FOV, B, support.edge(B), THRESH, trace=True)
+    assert_teacher_forced(om, states, speeds, drive, T, B)
 
 
 def test_drive_equals_composed_public_calls(oracle_mod):
@@ -150,15 +42,15 @@ def test_drive_equals_composed_public_calls(oracle_mod):
     mrx = 300
     om = oracle_mod.OracleMap.from_gridmap(g, mrx)
     omap = range_libc.PyOMap(g)
-    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    fg = support.followgap()
     R, T = 256, 40
-    far, sp_far = _starts(g, om.dt, R - 32, 21, 8.0)
-    near, sp_near = _starts(g, om.dt, 32, 22, 1.0)         # next to walls: some crash at once
+    far, sp_far = support.starts(g, om.dt, R - 32, 21, 8.0)
+    near, sp_near = support.starts(g, om.dt, 32, 22, 1.0)         # next to walls: some crash at once
     states, speeds = np.concatenate([far, near]), np.concatenate([sp_far, sp_near])
     steer0 = np.random.default_rng(5).uniform(-0.3, 0.3, R).astype(np.float32)
-    edge = _edge()
+    edge = support.edge(B)
     cars = RC.CarBatch()
-    for name, m, std in _maze_methods(omap, mrx):
+    for name, m, std in support.five_methods(omap, mrx):
         base = 7 * R * B
         m.set_noise(std, 99, base)
         first, final, vel, steers, sp, st = cars.drive_followgap(m, fg, states, T, speeds, FOV, B, edge, THRESH,
@@ -167,9 +59,7 @@ def test_drive_equals_composed_public_calls(oracle_mod):
         assert ((first >= 0) | (first == -(T + 1))).all(), name
         # lidar poses: numpy's f64 formula within one f32 ulp
         alive_t = np.arange(T)[None, :] <= np.where(first >= 0, first, T)[:, None]
-        x, y, th = st[..., 0][alive_t], st[..., 1][alive_t], st[..., 2][alive_t]
-        want_p = np.stack([x + D_BASE * np.cos(th), y + D_BASE * np.sin(th), th], -1).astype(np.float32)
-        assert _within_one_ulp(want_p, sp[alive_t]), name
+        assert within_one_ulp(support.lidar_poses(st[alive_t]), sp[alive_t]), name
         cur = states.copy()
         steer = steer0.astype(np.float64)
         alive = np.ones(R, bool)
@@ -179,7 +69,7 @@ def test_drive_equals_composed_public_calls(oracle_mod):
             idx = np.nonzero(alive)[0]
             _, out, v1 = cars.rollout(cur[idx], np.stack([speeds[idx], steer[idx]], -1)[:, None, :], n_steps=1,
                                       action_every=1)
-            assert _same_bits(out, st[idx, t]) and _same_bits(v1[:, 0], vel[idx, t]), (name, t)
+            assert same_bits(out, st[idx, t]) and same_bits(v1[:, 0], vel[idx, t]), (name, t)
             cur[idx] = out
             last_pose[idx] = sp[idx, t]
             # scan: every car, the frozen ones at their last pose, noise at this tick's ray offset
@@ -191,12 +81,12 @@ def test_drive_equals_composed_public_calls(oracle_mod):
             assert (first[idx] == t).tolist() == crashed.tolist(), (name, t)
             go = idx[~crashed]
             a = fg.eval_many(np.ascontiguousarray(ranges[go]))
-            assert _same_bits(a, steers[go, t]), (name, t)
+            assert same_bits(a, steers[go, t]), (name, t)
             assert np.isnan(steers[idx[crashed], t]).all()
             steer[go] = a
             alive[idx[crashed]] = False
         m.set_noise(0.0, 0, 0)
-        assert _same_bits(final, cur), name
+        assert same_bits(final, cur), name
 
 
 def test_drive_chunking_is_invariant():
@@ -205,10 +95,10 @@ def test_drive_chunking_is_invariant():
     dt = range_libc.PyOMap(g).distance_transform()
     omap = range_libc.PyOMap(g)
     m = range_libc.PyRayMarchingGPU(omap, 300)
-    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    fg = support.followgap()
     R, T, H = 64, 60, 30
-    states, speeds = _starts(g, dt, R, 8, 3.0)
-    edge = _edge()
+    states, speeds = support.starts(g, dt, R, 8, 3.0)
+    edge = support.edge(B)
     cars = RC.CarBatch()
     base = 12345
     m.set_noise(0.05, 4, base)
@@ -222,12 +112,12 @@ def test_drive_chunking_is_invariant():
     assert ok.any()
     # first half: identical for every car
     for k in range(2, 6):
-        assert _same_bits(whole[k][:, :H], a[k]), k
+        assert same_bits(whole[k][:, :H], a[k]), k
     assert (np.where(a[0] >= 0, a[0], -(T + 1)) == np.where(whole[0] < H, whole[0], -(T + 1))).all()
     # second half: identical for the cars alive at its start
-    assert _same_bits(whole[1][ok], b[1][ok])
+    assert same_bits(whole[1][ok], b[1][ok])
     for k in range(2, 6):
-        assert _same_bits(whole[k][ok, H:], b[k][ok]), k
+        assert same_bits(whole[k][ok, H:], b[k][ok]), k
     want_first = np.where(b[0][ok] >= 0, b[0][ok] + H, -(T + 1))
     assert (whole[0][ok] == want_first).all()
 
@@ -238,14 +128,14 @@ def test_drive_crash_and_freeze(oracle_mod):
     mrx = 300
     om = oracle_mod.OracleMap.from_gridmap(g, mrx)
     m = range_libc.PyRayMarchingGPU(range_libc.PyOMap(g), mrx)
-    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    fg = support.followgap()
     T = 60
     states = np.zeros((3, 11))
     states[0, :4] = (9.1, 5.0, 0.0, 7.0)                         # 0.6 m from the east wall, heading at it
     states[1, :3] = (0.09, 5.0, math.pi / 2)                     # 4 cm from the west wall: inside the outline
     states[2, :3] = (5.0, 5.0, 0.3)                              # the middle of the room
     speeds = np.array([7.0, 1.0, 1.0])
-    edge = _edge()
+    edge = support.edge(B)
     first, final, vel, steers, sp, st = RC.CarBatch().drive_followgap(m, fg, states, T, speeds, FOV, B, edge,
                                                                       THRESH, trace=True)
     assert first[1] == 0 and first[2] == -(T + 1) and 0 < first[0] < T, first
@@ -259,8 +149,8 @@ def test_drive_crash_and_freeze(oracle_mod):
         assert np.isfinite(steers[r, :t]).all()
         for arr in (vel, steers, sp, st):
             assert np.isnan(arr[r, t + 1:]).all()
-        assert _same_bits(final[r], st[r, t])
-    assert np.isfinite(steers[2]).all() and np.isfinite(st[2]).all() and _same_bits(final[2], st[2, -1])
+        assert same_bits(final[r], st[r, t])
+    assert np.isfinite(steers[2]).all() and np.isfinite(st[2]).all() and same_bits(final[2], st[2, -1])
     assert st[0, first[0], 0] > 9.1                              # it did drive into the wall
 
 
@@ -269,11 +159,11 @@ def test_drive_errors_leave_handles_usable():
     omap = range_libc.PyOMap(g)
     dt = omap.distance_transform()
     m = range_libc.PyRayMarchingGPU(omap, 300)
-    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    fg = support.followgap()
     cars = RC.CarBatch()
     R, T = 8, 10
-    states, speeds = _starts(g, dt, R, 2, 8.0)
-    edge = _edge()
+    states, speeds = support.starts(g, dt, R, 2, 8.0)
+    edge = support.edge(B)
     poses = maps.sample_free_poses(g, 16, 3, 4.0, dt)
     m.set_noise(0.05, 7, 321)
     m.set_option("nt_store", 1)
@@ -285,8 +175,8 @@ def test_drive_errors_leave_handles_usable():
     def still_usable():
         again = np.empty_like(scan0)
         m.calc_range_fan(poses, again, FOV, B)
-        assert _same_bits(again, scan0)                          # same noise offset, same ranges
-        assert _same_bits(fg.eval_many(scan0, B), steer0)
+        assert same_bits(again, scan0)                          # same noise offset, same ranges
+        assert same_bits(fg.eval_many(scan0, B), steer0)
         assert m.get_info("nt_store") == 1
 
     Lb = _lib.lib()
@@ -316,11 +206,11 @@ def test_drive_errors_leave_handles_usable():
         still_usable()
     for nr in (9, 1281):
         with pytest.raises(_lib.ScanLibError):
-            cars.drive_followgap(m, fg, states, T, speeds, FOV, nr, _edge(nr), THRESH)
+            cars.drive_followgap(m, fg, states, T, speeds, FOV, nr, support.edge(nr), THRESH)
         still_usable()
     # R num_rays >= 2^31 (refused before anything is read or launched)
     big = (1 << 31) // 1000 + 1
-    expect_error(raw(big, 1, 1000, st_=np.zeros((big, 11)), sp_=np.ones(big), ed=_edge(1000)))
+    expect_error(raw(big, 1, 1000, st_=np.zeros((big, 11)), sp_=np.ones(big), ed=support.edge(1000)))
     # multi-device handles: refused (single-device only)
     multi = RC.CarBatch(device=[0])
     with pytest.raises(_lib.ScanLibError, match="single-device"):
@@ -328,7 +218,7 @@ def test_drive_errors_leave_handles_usable():
     still_usable()
     # handles on different devices (where a second device exists)
     if _lib.lib().rl_device_count() >= 2:
-        fg1 = PyFollowGap(10, 15.0, MAX_STEER, 0.004, device=1)
+        fg1 = support.followgap(device=1)
         with pytest.raises(_lib.ScanLibError, match="device"):
             cars.drive_followgap(m, fg1, states, T, speeds, FOV, B, edge, THRESH)
         still_usable()
@@ -344,7 +234,7 @@ def test_drive_errors_leave_handles_usable():
     assert f0[0].shape == (0,)
     again = cars.drive_followgap(m, fg, states, T, speeds, FOV, B, edge, THRESH)
     for x, y in zip(drive0, again):
-        assert _same_bits(x, y)
+        assert same_bits(x, y)
     still_usable()
 
 
@@ -365,7 +255,7 @@ def test_drive_facade_matches_manual_ticks():
         st0 = np.zeros(11)
         st0[:3] = maps.sample_free_poses(g, 1, seed, 10.0, dt)[0]
         first, final, vel, steers = sim.driveFollowGapMany(st0[None, :], T, speed=2.0)
-        fg = PyFollowGap(10, 15.0, cfg["max_steer_ang"], 0.004)
+        fg = support.followgap()
         sim.setState(st0)
         s, crash = 0.0, -(T + 1)
         for t in range(T):

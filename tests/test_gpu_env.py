@@ -2,115 +2,46 @@
 tick composed from the public calls (CarBatch.rollout, calc_range_fan, is_crashed), against the closed loops it opens
 (drive_followgap, drive_policy), against the statement (tests/env_statement.py) and the reference's compiled Car."""
 import ctypes as C
-import math
 import os
 
 import numpy as np
 import pytest
 
+import drive_cases as DC
 import env_statement as ES
 import policy_statement as PS
-from conftest import GOLD, ROOT
+import support
+from conftest import GOLD
+from oracle import reference
+from support import D_BASE, FOV, THRESH, same_bits
 from pyracecarsimulator_amd import DriveEnv, Policy, RacecarSimulator, _lib, maps, range_libc
 from pyracecarsimulator_amd import racecar as RC
-from pyracecarsimulator_amd.followgap import PyFollowGap
 
-pytestmark = pytest.mark.gpu
-
-FOV, THRESH, D_BASE = 4.71, 0.001, 0.275
-MAX_STEER = RC.DEFAULT_CAR["max_steer_ang"]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
-
-
-def _edge(num_rays):
-    return RC.edge_distances(num_rays, -FOV / 2, FOV / num_rays, D_BASE, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
-
-
-def _same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _starts(g, dt, n, seed, clear_px, speed_hi=7.0):
-    rng = np.random.default_rng(seed)
-    states = np.zeros((n, 11))
-    states[:, :3] = maps.sample_free_poses(g, n, seed, clear_px, dt)
-    speeds = rng.uniform(1.0, speed_hi, n)
-    states[:, 3] = rng.uniform(0.0, 1.0, n) * speeds
-    return states, speeds
-
-
-def _actions(seed, steps, n):
-    """Seeded (steps, n, 2) float32: speed U(0, 7), steer U(-0.5, 0.5)."""
-    rng = np.random.default_rng(seed)
-    return np.stack([rng.uniform(0.0, 7.0, (steps, n)), rng.uniform(-0.5, 0.5, (steps, n))], -1).astype(np.float32)
-
-
-class Composed:
-    """The statement's three callbacks built from the public calls: the parent commit's only way to run this tick."""
-
-    def __init__(self, m, cars, n, num_rays, edge, substeps, std=0.0, seed=0, base=0, dt=0.01):
-        self.m, self.cars, self.N, self.B, self.edge = m, cars, n, num_rays, edge
-        self.S, self.std, self.seed, self.base, self.dt = substeps, std, seed, base, dt
-
-    def step_cars(self, states, speed, steer):
-        _, out, _ = self.cars.rollout(states, np.stack([speed, steer], -1)[:, None, :], n_steps=self.S,
-                                      action_every=self.S, dt=self.dt)
-        return out
-
-    def scan(self, poses, k):
-        ranges = np.empty(self.N * self.B, np.float32)
-        self.m.set_noise(self.std, self.seed, self.base + k * self.N * self.B)
-        self.m.calc_range_fan(np.ascontiguousarray(poses, np.float32), ranges, FOV, self.B)
-        self.m.set_noise(self.std, self.seed, self.base)
-        return ranges.reshape(self.N, self.B)
-
-    def is_crashed(self, r):
-        return RC.is_crashed(np.ascontiguousarray(r), self.B, 1, self.edge, THRESH) >= 0
-
-
-def _maze_methods(omap, mrx):
-    return [("RM", range_libc.PyRayMarching(omap, mrx), 0.0),
-            ("RMGPU", range_libc.PyRayMarchingGPU(omap, mrx), 0.05),
-            ("CDDT", range_libc.PyCDDTCast(omap, mrx, 112), 0.0),
-            ("GiantLUT", range_libc.PyGiantLUTCast(omap, mrx, 112), 0.0),
-            ("Bresenham", range_libc.PyBresenhamsLine(omap, mrx), 0.0)]
-
-
-def maze_case(dt):
-    """Test 1's cars: 46 in the open and 24 a few cells from a wall, so that some crash and some survive."""
-    g = maps.make_maze(256, cell=40, wall=3, p=0.45, seed=11)
-    far, _ = _starts(g, dt(g), 46, 21, 8.0)
-    near, _ = _starts(g, dt(g), 24, 22, 4.0)
-    return g, np.concatenate([far, near]), _actions(5, 12, 70)
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
 
 def test_env_equals_composed_public_calls(oracle_mod):
     """A 256^2 maze, 70 envs x 12 steps of 3 substeps, five range methods (noise on for RMGPU at a non-zero base),
     window (7, 40, 2): states, observations, done and rewards equal the same tick built from rollout(n_steps=3),
     calc_range_fan at the slot's ray offset and is_crashed, bit for bit; frozen envs are scanned at their last pose."""
-    g, states, actions = maze_case(lambda g_: oracle_mod.OracleMap.from_gridmap(g_, 300).dt)
+    g, states, actions = DC.maze_case(lambda g_: oracle_mod.OracleMap.from_gridmap(g_, 300).dt)
     N, B, S, T, win = 70, 100, 3, 12, (7, 40, 2)
     omap = range_libc.PyOMap(g)
-    edge = _edge(B)
+    edge = support.edge(B)
     cars = RC.CarBatch()
-    for name, m, std in _maze_methods(omap, 300):
+    for name, m, std in support.five_methods(omap, 300):
         base = 7 * N * B + 13
         m.set_noise(std, 99, base)
-        pub = Composed(m, cars, N, B, edge, S, std, 99, base)
+        pub = DC.Composed(m, cars, N, B, edge, S, std, 99, base)
         env = DriveEnv(m, states, N, B, FOV, edge, THRESH, substeps=S, obs_window=win, auto_reset=False, car=cars)
         assert env.n_envs == N and env.obs_shape == (N, 40)
         obs = env.reset(seed=3, start_index=np.arange(N))
         cur = states.copy()
-        ranges = pub.scan(ES.lidar_pose(cur, D_BASE), 0)
-        assert _same_bits(obs, ES.observation(ranges, win, 0, 0)), name
+        ranges = pub.scan(support.lidar_poses(cur), 0)
+        assert same_bits(obs, ES.observation(ranges, win, 0, 0)), name
         done = np.array([int(pub.is_crashed(r)) for r in ranges], np.int32)
         rd = env.read()
-        assert _same_bits(rd["states"], cur) and _same_bits(rd["done"], done), name
+        assert same_bits(rd["states"], cur) and same_bits(rd["done"], done), name
         assert (rd["ticks"] == 0).all() and (rd["start_index"] == np.arange(N)).all()
         for k in range(1, T + 1):
             a = actions[k - 1]
@@ -120,28 +51,20 @@ def test_env_equals_composed_public_calls(oracle_mod):
             _, out, _ = cars.rollout(cur[live], a[live].astype(np.float64)[:, None, :], n_steps=S, action_every=S)
             cur[live] = out
             rd = env.read()
-            assert _same_bits(rd["states"], cur), (name, k)
-            ranges = pub.scan(ES.lidar_pose(cur, D_BASE), k)                # every env, the frozen ones where they stand
-            assert _same_bits(obs, ES.observation(ranges, win, 0, 0)), (name, k)
+            assert same_bits(rd["states"], cur), (name, k)
+            ranges = pub.scan(support.lidar_poses(cur), k)                # every env, the frozen ones where they stand
+            assert same_bits(obs, ES.observation(ranges, win, 0, 0)), (name, k)
             crashed = np.array([pub.is_crashed(ranges[e]) for e in live], bool)
             want_rew = np.zeros(N, np.float32)
             want_rew[live[~crashed]] = (cur[live, 8] - before).astype(np.float32)[~crashed]
             done[live[crashed]] = 1
-            assert _same_bits(dn, done) and _same_bits(rd["done"], done), (name, k)
-            assert _same_bits(rew, want_rew), (name, k)
+            assert same_bits(dn, done) and same_bits(rd["done"], done), (name, k)
+            assert same_bits(rew, want_rew), (name, k)
             assert (rd["ticks"][live] == k).all(), (name, k)
         assert (done == 1).any() and (done == 0).any(), name
         assert (done[rd["ticks"] > 0] == 1).any(), name                     # ... and not only at the reset
         m.set_noise(0.0, 0, 0)
         env.close()
-
-
-def colombia_case(dt):
-    g = maps.load_colombia()
-    # (seed and clearance picked on the CPU with the statement and the CPU scan: every start clears the crash margin by
-    #  0.35 m, seven noise sigmas, and four of the cars reach a wall within the 30 ticks)
-    states, speeds = _starts(g, dt(g), 24, 12, 8.0)
-    return g, states, speeds.astype(np.float32)
 
 
 def test_env_fed_followgap_equals_drive_followgap():
@@ -150,11 +73,11 @@ def test_env_fed_followgap_equals_drive_followgap():
     the scans of the drive's traced lidar poses, the observations — bit for bit, frozen cars included.  The drive's
     noise base lies N B above the env's (the reset is slot 0)."""
     omap0 = range_libc.PyOMap(maps.load_colombia())
-    g, states, speeds = colombia_case(lambda g_: omap0.distance_transform())
+    g, states, speeds = DC.colombia_case(lambda g_: omap0.distance_transform())
     N, B, T = 24, 130, 30
     m = range_libc.PyRayMarchingGPU(omap0, 300)
-    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
-    edge = _edge(B)
+    fg = support.followgap()
+    edge = support.edge(B)
     cars = RC.CarBatch()
     base = 4321
     m.set_noise(0.05, 17, base)
@@ -167,7 +90,7 @@ def test_env_fed_followgap_equals_drive_followgap():
                                                              THRESH, steer0=steer0, trace=True)
     m.set_noise(0.05, 17, base)
     assert (first >= 0).any() and (first < 0).any()
-    pub = Composed(m, cars, N, B, edge, 1, 0.05, 17, base)
+    pub = DC.Composed(m, cars, N, B, edge, 1, 0.05, 17, base)
     steer = steer0
     want_first = np.full(N, -(T + 1), np.int32)
     last_pose = np.zeros((N, 3), np.float32)
@@ -176,16 +99,16 @@ def test_env_fed_followgap_equals_drive_followgap():
         obs, rew, dn = env.step(np.stack([speeds, steer], -1).astype(np.float32))
         rd = env.read()
         want_first[alive & (dn == 1)] = t
-        assert _same_bits(rd["states"][alive], st[alive, t]), t
+        assert same_bits(rd["states"][alive], st[alive, t]), t
         # the drive's traced lidar poses (frozen cars: the last one) scanned at this slot are the env's observation
         last_pose[alive] = sp[alive, t]
-        assert _same_bits(obs, pub.scan(last_pose, t + 1)), t
+        assert same_bits(obs, pub.scan(last_pose, t + 1)), t
         go = want_first < 0
         steer = fg.eval_many(np.ascontiguousarray(obs))
-        assert _same_bits(steer[go], steers[go, t]), t
+        assert same_bits(steer[go], steers[go, t]), t
         assert np.isnan(steers[alive & ~go, t]).all()
-    assert _same_bits(want_first, first)
-    assert _same_bits(env.read()["states"], final)
+    assert same_bits(want_first, first)
+    assert same_bits(env.read()["states"], final)
     m.set_noise(0.0, 0, 0)
 
 
@@ -198,10 +121,10 @@ def test_env_fed_the_network_equals_drive_policy():
     g = maps.load_colombia()
     omap = range_libc.PyOMap(g)
     N, B, T = 9, 900, 8
-    states, speeds = _starts(g, omap.distance_transform(), N, 5, 10.0, speed_hi=4.0)     # (0.4 m clear of the margin)
+    states, speeds = support.starts(g, omap.distance_transform(), N, 5, 10.0, speed_hi=4.0)     # (0.4 m clear of the margin)
     speeds = speeds.astype(np.float32)
     m = range_libc.PyRayMarchingGPU(omap, 300)
-    edge = _edge(B)
+    edge = support.edge(B)
     cars = RC.CarBatch()
     base = 999
     for clip in (None, 0.2):
@@ -216,7 +139,7 @@ def test_env_fed_the_network_equals_drive_policy():
             return np.where(r <= 15, r / np.float32(15), np.float32(1)).astype(np.float32)
 
         obs = env.reset(start_index=np.arange(N))
-        assert _same_bits(twin.reset(start_index=np.arange(N)), input_form(obs))
+        assert same_bits(twin.reset(start_index=np.arange(N)), input_form(obs))
         assert (env.read()["done"] == 0).all()
         # (the drive takes steer0 unclamped; the starts have steer_angle 0, so the env's clamped first steer and the
         #  drive's raw one, of one sign, turn the wheel alike: tick 0 agrees bit for bit as well)
@@ -234,32 +157,18 @@ def test_env_fed_the_network_equals_drive_policy():
             n_clipped += int((np.abs(steer[alive]) > 0.2).sum())
             obs, rew, dn = env.step(a)
             obs2, rew2, dn2 = twin.step(a)
-            assert _same_bits(obs2, input_form(obs)) and _same_bits(rew, rew2) and _same_bits(dn, dn2), (clip, t)
+            assert same_bits(obs2, input_form(obs)) and same_bits(rew, rew2) and same_bits(dn, dn2), (clip, t)
             want_first[alive & (dn == 1)] = t
-            assert _same_bits(env.read()["states"][alive], st[alive, t]), (clip, t)
+            assert same_bits(env.read()["states"][alive], st[alive, t]), (clip, t)
             go = want_first < 0
             steer = pol.predict_many(obs)
-            assert _same_bits(steer[go], steers[go, t]), (clip, t)
-        assert _same_bits(want_first, first), clip
-        assert _same_bits(env.read()["states"], final) and _same_bits(twin.read()["states"], final), clip
+            assert same_bits(steer[go], steers[go, t]), (clip, t)
+        assert same_bits(want_first, first), clip
+        assert same_bits(env.read()["states"], final) and same_bits(twin.read()["states"], final), clip
         assert n_clipped > 0                                       # the network asked for more than the clip somewhere
         env.close()
         twin.close()
     m.set_noise(0.0, 0, 0)
-
-
-def room_case():
-    """Test 4's pool: into the east wall at 7 m/s, inside the west wall's margin, three in the open."""
-    g = maps.make_room(200)
-    starts = np.zeros((5, 11))
-    starts[0, :4] = (9.1, 5.0, 0.0, 7.0)
-    starts[1, :3] = (0.09, 5.0, math.pi / 2)
-    starts[2, :4] = (5.0, 5.0, 0.3, 2.0)
-    starts[3, :4] = (3.0, 7.0, -2.0, 4.0)
-    starts[4, :4] = (6.0, 2.5, 1.2, 0.0)
-    rng = np.random.default_rng(12)
-    actions = np.stack([np.full((25, 12), 7.0), rng.uniform(-0.3, 0.3, (25, 12))], -1).astype(np.float32)
-    return g, starts, actions
 
 
 def _against_statement(env, stmt, actions, seed, start_index=None, aux=False):
@@ -270,21 +179,21 @@ def _against_statement(env, stmt, actions, seed, start_index=None, aux=False):
 
     def counters(k):
         rd = env.read()
-        assert _same_bits(rd["states"], stmt.states), k
+        assert same_bits(rd["states"], stmt.states), k
         for key, want in (("ticks", stmt.tick), ("episodes", stmt.episode), ("start_index", stmt.start_index),
                           ("done", stmt.done)):
-            assert _same_bits(rd[key], want), (k, key)
+            assert same_bits(rd[key], want), (k, key)
         return rd
 
-    assert _same_bits(obs, want_obs)
+    assert same_bits(obs, want_obs)
     counters(0)
     for k, a in enumerate(actions, 1):
         prev_done = stmt.done.copy()
         obs, rew, dn = env.step(a)
         want_obs, want_rew, want_done = stmt.step(a)
-        assert _same_bits(obs, want_obs), k
-        assert _same_bits(rew, want_rew), k
-        assert _same_bits(dn, want_done), k
+        assert same_bits(obs, want_obs), k
+        assert same_bits(rew, want_rew), k
+        assert same_bits(dn, want_done), k
         rd = counters(k)
         log.append((prev_done, dn.copy(), rew.copy(), rd))
     return log
@@ -294,16 +203,16 @@ def test_env_auto_reset_and_truncation_against_the_statement():
     """A 10 m room, a pool of five hand-built starts, 12 envs, max_ticks 6, 25 steps of 3 substeps with auto_reset: done
     codes, ticks, episodes, start indices, states, rewards and observations equal the statement driven by the composed
     public calls; codes 1 and 2 both occur; the step after a done returns reward 0, tick 0 and the drawn start."""
-    g, starts, actions = room_case()
+    g, starts, actions = DC.room_case()
     N, B, S = 12, 100, 3
     m = range_libc.PyRayMarchingGPU(range_libc.PyOMap(g), 300)
-    edge = _edge(B)
+    edge = support.edge(B)
     cars = RC.CarBatch()
     base, seed = 555, 6
     m.set_noise(0.02, 3, base)
     kw = dict(max_ticks=6, auto_reset=True, crash_reward=-2.5)
     env = DriveEnv(m, starts, N, B, FOV, edge, THRESH, substeps=S, car=cars, **kw)
-    pub = Composed(m, cars, N, B, edge, S, 0.02, 3, base)
+    pub = DC.Composed(m, cars, N, B, edge, S, 0.02, 3, base)
     stmt = ES.EnvStatement(starts, N, B, pub.step_cars, pub.scan, pub.is_crashed, scan_dist_to_base=D_BASE, **kw)
     log = _against_statement(env, stmt, actions, seed)
     codes = np.concatenate([dn for _, dn, _, _ in log])
@@ -314,7 +223,7 @@ def test_env_auto_reset_and_truncation_against_the_statement():
             n_fresh += 1
             assert rew[e] == 0.0 and rd["ticks"][e] == 0
             assert rd["start_index"][e] == ES.spawn_index(seed, e, rd["episodes"][e], 5)
-            assert _same_bits(rd["states"][e], starts[rd["start_index"][e]])
+            assert same_bits(rd["states"][e], starts[rd["start_index"][e]])
     assert n_fresh >= N                                            # every env ended an episode at least once
     assert len(set(np.concatenate([rd["start_index"] for _, _, _, rd in log]).tolist())) == 5
     m.set_noise(0.0, 0, 0)
@@ -324,22 +233,22 @@ def test_env_device_form_equals_host_form():
     """Two twin envs, 70 x 100 beams, 6 steps: torch tensors on the current stream give the bits of the NumPy form;
     the method's ray offset and options read the same after every call."""
     import torch
-    g, states, actions = maze_case(lambda g_: range_libc.PyOMap(g_).distance_transform())
+    g, states, actions = DC.maze_case(lambda g_: range_libc.PyOMap(g_).distance_transform())
     N, B = 70, 100
     omap = range_libc.PyOMap(g)
     m = range_libc.PyRayMarchingGPU(omap, 300)
-    edge = _edge(B)
+    edge = support.edge(B)
     cars = RC.CarBatch()
     m.set_noise(0.05, 8, 777)
     m.set_option("nt_store", 1)
-    probe = np.ascontiguousarray(ES.lidar_pose(states[:16], D_BASE))
+    probe = np.ascontiguousarray(support.lidar_poses(states[:16]))
     scan0 = np.empty(16 * B, np.float32)
     m.calc_range_fan(probe, scan0, FOV, B)
 
     def handle_unchanged():
         again = np.empty_like(scan0)
         m.calc_range_fan(probe, again, FOV, B)
-        assert _same_bits(again, scan0) and m.get_info("nt_store") == 1
+        assert same_bits(again, scan0) and m.get_info("nt_store") == 1
 
     kw = dict(substeps=2, obs_window=(3, 45, 2), max_ticks=4, auto_reset=True, crash_reward=-1.0, car=cars)
     host = DriveEnv(m, states, N, B, FOV, edge, THRESH, **kw)
@@ -348,7 +257,7 @@ def test_env_device_form_equals_host_form():
     handle_unchanged()
     o_d, x_d = dev.reset(seed=9, aux=True, on_device=True)
     assert o_d.is_cuda and o_d.dtype == torch.float32 and tuple(o_d.shape) == (N, 45)
-    assert _same_bits(o_d.cpu().numpy(), o_h) and _same_bits(x_d.cpu().numpy(), x_h)
+    assert same_bits(o_d.cpu().numpy(), o_h) and same_bits(x_d.cpu().numpy(), x_h)
     handle_unchanged()
     stream = torch.cuda.Stream()
     seen = set()
@@ -365,17 +274,17 @@ def test_env_device_form_equals_host_form():
             out = dev.step(a, aux=True)
         o_d, r_d, d_d, x_d = (t.cpu().numpy() for t in out)
         assert out[0].data_ptr() == dev._torch["obs"].data_ptr()    # the env's own tensors, every call
-        assert _same_bits(o_d, o_h) and _same_bits(r_d, r_h) and _same_bits(d_d, d_h) and _same_bits(x_d, x_h), k
+        assert same_bits(o_d, o_h) and same_bits(r_d, r_h) and same_bits(d_d, d_h) and same_bits(x_d, x_h), k
         handle_unchanged()
         seen |= set(d_h.tolist())
     assert {0, 2} <= seen
     rd_h, rd_d = host.read(), dev.read()
     for key in rd_h:
-        assert _same_bits(rd_h[key], rd_d[key]), key
+        assert same_bits(rd_h[key], rd_d[key]), key
     # a NumPy step on the env that has been stepping on the device, and the other way round
     o1, r1, d1 = dev.step(actions[6])
     o2, r2, d2 = (t.cpu().numpy() for t in host.step(torch.from_numpy(actions[6]).cuda()))
-    assert _same_bits(o1, o2) and _same_bits(r1, r2) and _same_bits(d1, d2)
+    assert same_bits(o1, o2) and same_bits(r1, r2) and same_bits(d1, d2)
     with pytest.raises(ValueError):
         dev.step(torch.from_numpy(actions[0].astype(np.float64)).cuda())
     with pytest.raises(ValueError):
@@ -390,65 +299,41 @@ def test_env_beam_count_limits(B, N):
     g = maps.make_maze(256, cell=40, wall=3, p=0.45, seed=11)
     omap = range_libc.PyOMap(g)
     m = range_libc.PyRayMarchingGPU(omap, 300)
-    states, _ = _starts(g, omap.distance_transform(), N, 40 + N, 4.0)
-    edge = _edge(B)
+    states, _ = support.starts(g, omap.distance_transform(), N, 40 + N, 4.0)
+    edge = support.edge(B)
     cars = RC.CarBatch()
     m.set_noise(0.03, 2, 10 * B)
     win = (1, B // 2, 2)
     env = DriveEnv(m, states, N, B, FOV, edge, THRESH, substeps=2, obs_window=win, car=cars, obs_clip=6.0, obs_scale=3.0)
-    pub = Composed(m, cars, N, B, edge, 2, 0.03, 2, 10 * B)
+    pub = DC.Composed(m, cars, N, B, edge, 2, 0.03, 2, 10 * B)
     stmt = ES.EnvStatement(states, N, B, pub.step_cars, pub.scan, pub.is_crashed, obs_window=win, obs_clip=6.0,
                            obs_scale=3.0, scan_dist_to_base=D_BASE)
-    _against_statement(env, stmt, _actions(B + N, 3, N), seed=1)
+    _against_statement(env, stmt, DC.actions(B + N, 3, N), seed=1)
     m.set_noise(0.0, 0, 0)
-
-
-def _ref_car():
-    car_so = os.path.join(ROOT, "oracle/_ref/libracecar_ref.so")
-    if not os.path.exists(car_so):
-        pytest.fail("reference build missing (build() makes it): %s" % car_so)
-    L = C.CDLL(car_so)
-    d, vp, dp = C.c_double, C.c_void_p, C.POINTER(C.c_double)
-    L.ref_car_create.restype = vp
-    L.ref_car_create.argtypes = [dp]
-    L.ref_car_destroy.argtypes = [vp]
-    L.ref_car_control.argtypes = [vp, d, d]
-    L.ref_car_update_position.argtypes = [vp, d]
-    L.ref_car_get_state.argtypes = [vp, dp]
-    L.ref_car_set_state.argtypes = [vp, dp]
-    return L
 
 
 def test_env_teacher_forced_vs_reference_car():
     """8 envs x 10 steps of 3 substeps: every step, fed the env's own state of the step before, agrees with the
     reference's compiled Car to the rtol = atol = 1e-9 of test_drive_teacher_forced_vs_reference."""
-    L = _ref_car()
+    reference.require()
     g = maps.load_colombia()
     omap = range_libc.PyOMap(g)
     N, B, S, T = 8, 100, 3, 10
-    states, _ = _starts(g, omap.distance_transform(), N, 3, 6.0, speed_hi=4.0)
+    states, _ = support.starts(g, omap.distance_transform(), N, 3, 6.0, speed_hi=4.0)
     m = range_libc.PyRayMarchingGPU(omap, 300)
-    env = DriveEnv(m, states, N, B, FOV, _edge(B), THRESH, substeps=S, auto_reset=False)
+    env = DriveEnv(m, states, N, B, FOV, support.edge(B), THRESH, substeps=S, auto_reset=False)
     env.reset(start_index=np.arange(N))
-    actions = _actions(77, T, N)
-    ref = L.ref_car_create((C.c_double * 17)(*[RC.DEFAULT_CAR[k] for k in RC.CAR_PARAM_ORDER]))
-    buf = (C.c_double * 11)()
+    actions = DC.actions(77, T, N)
     n_checked = 0
-    try:
+    with reference.RefCar() as ref:
         for k in range(T):
             before = env.read()
             env.step(actions[k])
             after = env.read()
             for e in np.nonzero(before["done"] == 0)[0]:
-                L.ref_car_set_state(ref, (C.c_double * 11)(*before["states"][e]))
-                for _ in range(S):
-                    L.ref_car_control(ref, float(actions[k, e, 0]), float(actions[k, e, 1]))
-                    L.ref_car_update_position(ref, 0.01)
-                L.ref_car_get_state(ref, buf)
-                assert np.allclose(after["states"][e], np.array(buf), rtol=1e-9, atol=1e-9), (k, e)
+                want = ref.step(before["states"][e], actions[k, e, 0], actions[k, e, 1], n=S)
+                assert np.allclose(after["states"][e], want, rtol=1e-9, atol=1e-9), (k, e)
                 n_checked += 1
-    finally:
-        L.ref_car_destroy(ref)
     assert n_checked >= N * T // 2
 
 
@@ -457,9 +342,9 @@ def test_env_errors_leave_everything_usable():
     omap = range_libc.PyOMap(g)
     dt = omap.distance_transform()
     N, B, M = 9, 100, 4
-    states, _ = _starts(g, dt, M, 2, 8.0)
-    edge = _edge(B)
-    actions = _actions(3, 8, N)
+    states, _ = support.starts(g, dt, M, 2, 8.0)
+    edge = support.edge(B)
+    actions = DC.actions(3, 8, N)
     # the env that sees the errors and a twin that never does, each on handles of its own
     mA, mB = range_libc.PyRayMarchingGPU(omap, 300), range_libc.PyRayMarchingGPU(omap, 300)
     carsA, carsB = RC.CarBatch(), RC.CarBatch()
@@ -515,11 +400,11 @@ def test_env_errors_leave_everything_usable():
     def same(xs, ys):
         for x, y in zip(xs, ys):
             for a, b in zip(x, y):
-                assert _same_bits(a, b)
+                assert same_bits(a, b)
 
     assert create() == 0                                            # the helper itself creates a valid env
     o_a, o_b = A.reset(seed=5), Bt.reset(seed=5)
-    assert _same_bits(o_a, o_b)
+    assert same_bits(o_a, o_b)
     same(run(A, (0, 1)), run(Bt, (0, 1)))
 
     # every refusal of rl_env_create
@@ -543,7 +428,7 @@ def test_env_errors_leave_everything_usable():
     bad[2, 5] = nan
     refused(create(starts=bad))
     big = (1 << 31) // 1000 + 1
-    refused(create(n_envs=big, num_rays=1000, obs_count=1, ed=_edge(1000)))
+    refused(create(n_envs=big, num_rays=1000, obs_count=1, ed=support.edge(1000)))
     multi = RC.CarBatch(device=[0])
     refused(create(car=multi._h))
     with pytest.raises(_lib.ScanLibError, match="single-device"):
@@ -576,13 +461,13 @@ def test_env_errors_leave_everything_usable():
     same(run(A, (2, 3)), run(Bt, (2, 3)))
     rd_a, rd_b = A.read(), Bt.read()
     for key in rd_a:
-        assert _same_bits(rd_a[key], rd_b[key]), key
+        assert same_bits(rd_a[key], rd_b[key]), key
     # the handles scan as a twin's: same noise offset, same options
     poses = maps.sample_free_poses(g, 16, 3, 4.0, dt)
     sa, sb = np.empty(16 * B, np.float32), np.empty(16 * B, np.float32)
     mA.calc_range_fan(poses, sa, FOV, B)
     mB.calc_range_fan(poses, sb, FOV, B)
-    assert _same_bits(sa, sb) and mA.get_info("nt_store") == 1
+    assert same_bits(sa, sb) and mA.get_info("nt_store") == 1
 
     # NaN and inf actions: done = 3, the state unchanged, crash_reward; no other env is affected
     A.reset(seed=11, start_index=np.arange(N) % M)
@@ -598,10 +483,10 @@ def test_env_errors_leave_everything_usable():
     hit[[1, 4, 6]] = True
     after = A.read()
     assert (d_a[hit] == 3).all() and (r_a[hit] == np.float32(-4.0)).all()
-    assert _same_bits(after["states"][hit], before["states"][hit]) and _same_bits(after["ticks"][hit], before["ticks"][hit])
+    assert same_bits(after["states"][hit], before["states"][hit]) and same_bits(after["ticks"][hit], before["ticks"][hit])
     assert np.isfinite(o_a).all() and np.isfinite(x_a).all() and np.isfinite(after["states"]).all()
     for x, y in ((o_a, o_b), (r_a, r_b), (d_a, d_b), (x_a, x_b), (after["states"], Bt.read()["states"])):
-        assert _same_bits(x[~hit], y[~hit])
+        assert same_bits(x[~hit], y[~hit])
     # with auto_reset (the default) the three re-spawn on the next step
     o_a, r_a, d_a = A.step(actions[2])
     rd = A.read()
@@ -622,18 +507,18 @@ def test_env_facade_matches_hand_built():
     sim.setMap(omap, g.resolution, g.origin)
     sim.setRaytracingMethod("RMGPU")
     N = 9
-    starts, _ = _starts(g, omap.distance_transform(), 4, 6, 6.0)
+    starts, _ = support.starts(g, omap.distance_transform(), 4, 6, 6.0)
     kw = dict(substeps=2, obs_window=(180, 720, 1), obs_clip=15, obs_scale=15, max_ticks=3, crash_reward=-1.0)
     env = sim.driveEnv(N, starts, **kw)
     assert isinstance(env, DriveEnv) and env.obs_shape == (N, 720)
     hand = DriveEnv(sim.scan_simulator.scan_method, starts, N, 1080, 4.71, sim.edge_distances, cfg["ttc_thresh"],
                     car=sim.car, scan_dist_to_base=0.275, **kw)
-    actions = _actions(21, 5, N)
-    assert _same_bits(env.reset(seed=2), hand.reset(seed=2))
+    actions = DC.actions(21, 5, N)
+    assert same_bits(env.reset(seed=2), hand.reset(seed=2))
     for a in actions:
         for x, y in zip(env.step(a, aux=True), hand.step(a, aux=True)):
-            assert _same_bits(x, y)
+            assert same_bits(x, y)
     rd_a, rd_b = env.read(), hand.read()
     for key in rd_a:
-        assert _same_bits(rd_a[key], rd_b[key]), key
+        assert same_bits(rd_a[key], rd_b[key]), key
     assert (rd_a["episodes"] > 0).any()

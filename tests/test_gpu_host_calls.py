@@ -12,29 +12,24 @@ The suite's smallest maze (56^2 cells, range 60), 65 beams, RMGPU unless said ot
 No case refuses rl_pf_run in the middle of a call: once it has staged its rows, launch_mcl_step / launch_pf_weights can
 only fail on a HIP error or an allocation (pf_kind_of and the shape are checked before the uploads), and this file
 provokes neither."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import mcl_statement as MS
 import race_statement as RS
-from test_gpu_drive import _assert_teacher_forced, _edge, _ref_libs, _same_bits, _starts, _within_one_ulp
-from test_gpu_mcl import _assert_equal_to_statement
+import support
+from drive_cases import assert_teacher_forced
+from oracle import reference
+from pf_cases import assert_equal_to_statement
+from support import FOV, THRESH, same_bits, within_one_ulp
 from pyracecarsimulator_amd import ParticleFilter, _lib, maps, range_libc
 from pyracecarsimulator_amd import racecar as RC
-from pyracecarsimulator_amd.followgap import PyFollowGap
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
-FOV, B, MRX, THRESH = 4.71, 65, 60, 0.001
+B, MRX = 65, 60
 RL_ERR_INVALID, RL_ERR_UNSUPPORTED = -1, -4           # include/scanlib.h rl_status
 R, STEPS, EVERY, DT = 3, 4, 2, 0.01                   # the roll-outs: 3 x 4 steps, an action every 2
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
 
 
 @pytest.fixture(scope="module")
@@ -52,7 +47,7 @@ def method(world):
 
 
 def _rollout_case(g, om):
-    states, _ = _starts(g, om.dt, R, 21, 4.0, speed_hi=3.0)
+    states, _ = support.starts(g, om.dt, R, 21, 4.0, speed_hi=3.0)
     rng = np.random.default_rng(4)
     actions = np.stack([rng.uniform(0.5, 4.0, (R, 2)), rng.uniform(-0.4, 0.4, (R, 2))], -1)
     return states, actions
@@ -72,7 +67,7 @@ def test_rollout_check_refused_after_the_rollout_kernel(world, method):
     g, om, _ = world
     cars = RC.CarBatch()
     states, actions = _rollout_case(g, om)
-    edge = _edge(B)
+    edge = support.edge(B)
 
     def valid():
         return cars.rollout_check(method, states, actions, FOV, B, edge, THRESH, n_steps=STEPS, action_every=EVERY, dt=DT)
@@ -84,9 +79,9 @@ def test_rollout_check_refused_after_the_rollout_kernel(world, method):
                        n_steps=STEPS, action_every=EVERY, dt=DT)
         print("refused:", msg)
         for a, b in zip(valid(), want):
-            assert _same_bits(a, b), (fov, num_rays)
+            assert same_bits(a, b), (fov, num_rays)
     _, final, vel = cars.rollout(states, actions, STEPS, EVERY, DT)
-    assert _same_bits(final, want[1]) and _same_bits(vel, want[2])
+    assert same_bits(final, want[1]) and same_bits(vel, want[2])
     cars.close()
 
 
@@ -110,12 +105,12 @@ def test_staged_fan_refused_after_its_poses_were_queued(world):
         return out
 
     before = fans()
-    assert not (before[0] == -7.0).any() and _same_bits(before[0], before[1])
+    assert not (before[0] == -7.0).any() and same_bits(before[0], before[1])
     hits = np.full((len(poses) * B, 2), -7, np.int32)
     ranges = np.full(len(poses) * B, -7.0, np.float32)
     print("refused:", _refused(RL_ERR_UNSUPPORTED, m.calc_range_fan, poses, ranges, FOV, B, hit_cells=hits))
     for a, b in zip(fans(), before):
-        assert _same_bits(a, b)
+        assert same_bits(a, b)
     m.close()
 
 
@@ -123,27 +118,20 @@ def test_rollout_returns_states_and_velocities(world):
     """rl_car_rollout with states_out and vel_out, 3 roll-outs x 4 steps: every step against the reference's compiled
     Car (f64 state to 1e-9 as test_gpu_drive holds it, the f32 pose within one ulp, the velocity the state's)."""
     g, om, _ = world
-    L, _ = _ref_libs()
+    reference.require()
     states, actions = _rollout_case(g, om)
     cars = RC.CarBatch()
     poses, final, vel = cars.rollout(states, actions, STEPS, EVERY, DT)
     assert poses.shape == (R, STEPS, 3) and final.shape == (R, 11) and vel.shape == (R, STEPS)
-    ref = L.ref_car_create((C.c_double * 17)(*[RC.DEFAULT_CAR[k] for k in RC.CAR_PARAM_ORDER]))
-    buf = (C.c_double * 11)()
-    try:
+    with reference.RefCar() as ref:
         for r in range(R):
-            L.ref_car_set_state(ref, (C.c_double * 11)(*states[r]))
+            ref.set_state(states[r])
             for t in range(STEPS):
-                L.ref_car_control(ref, float(actions[r, t // EVERY, 0]), float(actions[r, t // EVERY, 1]))
-                L.ref_car_update_position(ref, DT)
-                L.ref_car_get_state(ref, buf)
-                now = np.array(buf)
-                assert _within_one_ulp(now[:3].astype(np.float32), poses[r, t]), (r, t)
+                now = ref.step(None, actions[r, t // EVERY, 0], actions[r, t // EVERY, 1], dt=DT)
+                assert within_one_ulp(now[:3].astype(np.float32), poses[r, t]), (r, t)
                 assert np.allclose(vel[r, t], now[3], rtol=1e-9, atol=1e-9), (r, t)
             assert np.allclose(final[r], now, rtol=1e-9, atol=1e-9), r
             assert vel[r, -1] == final[r, 3]
-    finally:
-        L.ref_car_destroy(ref)
     cars.close()
 
 
@@ -151,13 +139,13 @@ def test_followgap_drive_returns_all_four_traces(world, method):
     """2 cars x 3 ticks with velocities, steers, lidar poses and states traced: every link against the reference's Car
     and FollowGap and the oracle's scan, as test_gpu_drive's teacher-forced case holds the 32-car drive."""
     g, om, _ = world
-    L, F = _ref_libs()
-    states, speeds = _starts(g, om.dt, 2, 21, 4.0, speed_hi=3.0)
-    fg = PyFollowGap(10, 15.0, RC.DEFAULT_CAR["max_steer_ang"], 0.004)
+    reference.require()
+    states, speeds = support.starts(g, om.dt, 2, 21, 4.0, speed_hi=3.0)
+    fg = support.followgap()
     cars = RC.CarBatch()
-    drive = cars.drive_followgap(method, fg, states, 3, speeds, FOV, B, _edge(B), THRESH, trace=True)
+    drive = cars.drive_followgap(method, fg, states, 3, speeds, FOV, B, support.edge(B), THRESH, trace=True)
     assert len(drive) == 6
-    _assert_teacher_forced(L, F, om, states, speeds, drive, 3, B)
+    assert_teacher_forced(om, states, speeds, drive, 3, B)
     cars.close()
 
 
@@ -192,5 +180,5 @@ def test_filter_read_returns_all_five_arrays(world, method):
     st.reset(parts, seed=3)
     want = st.run(odom, obs)
     assert sorted(pf.read()) == ["ancestors", "cum", "likelihood", "particles", "weights"]
-    _assert_equal_to_statement(pf, out, st, want, "8 x 5")
+    assert_equal_to_statement(pf, out, st, want, "8 x 5")
     pf.close()

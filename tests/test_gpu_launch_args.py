@@ -8,26 +8,20 @@ std 1, a seed whose high word matters and an offset whose ids straddle 2^32."""
 import numpy as np
 import pytest
 
+import mcl_statement as MS
+import support
+from noise_checks import SEED_HI
 from oracle import np_statement as N
-from test_gpu_drive import _edge, _same_bits, _starts
-from test_gpu_noise import SEED_HI
+from support import FOV, THRESH, same_bits
 from pyracecarsimulator_amd import DriveEnv, ParticleFilter, maps, range_libc
 from pyracecarsimulator_amd import racecar as RC
-from pyracecarsimulator_amd.followgap import PyFollowGap
 from pyracecarsimulator_amd.mcts import MCTSPlanner
 
-import mcl_statement as MS
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
-pytestmark = pytest.mark.gpu
-
-FOV, B, MRX, THRESH = 4.71, 65, 60, 0.001
+B, MRX = 65, 60
 OFFSET = 2 ** 32 - 300
 SLICE_LOG2 = 8                                   # 256 rays: 3 poses of 65 beams per slice
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
 
 
 @pytest.fixture(scope="module")
@@ -82,7 +76,7 @@ def test_partial_last_slice_on_a_callers_stream(world, method):
         assert pl["slices"] == 4 and pl["slice_poses"] == 3, pl
         sliced = scan(aux)
         for w, s, what in zip(whole, sliced, ("ranges", "hit cells", "steps")):
-            assert _same_bits(w, s), (aux, what, np.flatnonzero((w != s).reshape(len(w), -1).any(1))[:8])
+            assert same_bits(w, s), (aux, what, np.flatnonzero((w != s).reshape(len(w), -1).any(1))[:8])
         assert not (whole[0] == -7.0).any()
         if aux:
             assert (whole[2] != 7).any() and (whole[1] != -7).any()
@@ -98,7 +92,7 @@ def _crash_case(oracle_mod, g, om, std):
     far = maps.sample_free_poses(g, 8, 12, 5.0, om.dt)
     near = maps.sample_free_poses(g, 4, 13, 0.0, om.dt)
     poses = np.ascontiguousarray(np.concatenate([np.concatenate([far[2 * q:2 * q + 2], near[q:q + 1]]) for q in range(4)]))
-    edge = RC.edge_distances(B, -FOV / 2, FOV / B, 0.275, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
+    edge = support.edge(B)
     clean = om.rm_fan(poses, FOV, B, step_coeff=1.0)[0]
     noisy = (clean.astype(np.float64) + std * N.gauss_noise_ref(SEED_HI, N.fan_ray_ids(OFFSET, clean.size, 1))).astype(np.float32)
     want = [oracle_mod.is_crashed(noisy[q * 3 * B:(q + 1) * 3 * B], B, 3, edge, THRESH) for q in range(4)]
@@ -127,10 +121,10 @@ def test_grouped_crash_test_under_slicing(oracle_mod, world, method, std):
         r = np.full(len(poses) * B, -7.0, np.float32)
         first = m.check_collision_groups(poses, 3, FOV, B, edge, THRESH, ranges=r)
         fan = _host_fan(m, poses)
-        assert _same_bits(r, fan), sl
+        assert same_bits(r, fan), sl
         assert first.tolist() == [oracle_mod.is_crashed(r[q * 3 * B:(q + 1) * 3 * B], B, 3, edge, THRESH) for q in range(4)], sl
         got[sl] = (first, r)
-    assert got[30][0].tolist() == got[SLICE_LOG2][0].tolist() and _same_bits(got[30][1], got[SLICE_LOG2][1])
+    assert got[30][0].tolist() == got[SLICE_LOG2][0].tolist() and same_bits(got[30][1], got[SLICE_LOG2][1])
     assert got[30][0].tolist() == want
     print("std", std, "device first-crash per group", got[30][0].tolist())
 
@@ -151,13 +145,13 @@ def test_timing_is_an_argument_of_the_launch(world, method, timing):
     assert m.get_info("timing") == timing
     ms_sliced = m.last_kernel_ms()
     assert ms_sliced > 0.0
-    assert _same_bits(sliced, whole)
+    assert same_bits(sliced, whole)
     m.set_option("slice_log2", 30)
     again = _host_fan(m, poses)
     assert m.get_info("timing") == timing and m.get_info("slice_log2") == 30
     ms_whole = m.last_kernel_ms()
     assert ms_whole > 0.0
-    assert _same_bits(again, whole)
+    assert same_bits(again, whole)
     print("timing", timing, "sliced %.4f ms, whole %.4f ms" % (ms_sliced, ms_whole))
 
 
@@ -171,10 +165,10 @@ def test_handle_reads_the_same_after_every_looped_path(world, method):
     fan0 = _host_fan(m, poses)
     options = {k: m.get_info(k) for k in ("nt_store", "timing", "slice_log2")}
     assert options == {"nt_store": 1, "timing": 0, "slice_log2": 30}
-    edge = _edge(B)
+    edge = support.edge(B)
     cars = RC.CarBatch()
-    states, speeds = _starts(g, om.dt, 2, 21, 4.0, speed_hi=3.0)
-    fg = PyFollowGap(10, 15.0, RC.DEFAULT_CAR["max_steer_ang"], 0.004)
+    states, speeds = support.starts(g, om.dt, 2, 21, 4.0, speed_hi=3.0)
+    fg = support.followgap()
     parts, angles, odom, obs, table = MS.localisation_case(g, om.dt, MRX, FOV, 8, 5, 2)
     m.set_sensor_model(table)
     actions = np.array([[2.0, 0.1], [1.0, -0.2]], np.float32)
@@ -228,7 +222,7 @@ def test_handle_reads_the_same_after_every_looped_path(world, method):
         for path in (sliced, overlap, pf_run, rollout, env, planner):
             outs[path.__name__] = [np.array(x) for x in path()]
             assert {k: m.get_info(k) for k in options} == options, path.__name__
-            assert _same_bits(_host_fan(m, poses), fan0), path.__name__
+            assert same_bits(_host_fan(m, poses), fan0), path.__name__
         rounds.append(outs)
     r0 = rounds[0]
     print("roll-out first crash", r0["rollout"][0].tolist(), "| env done", r0["env"][3].tolist(), "| planner best", r0["planner"][0].tolist(),
@@ -236,6 +230,6 @@ def test_handle_reads_the_same_after_every_looped_path(world, method):
     assert np.isfinite(r0["env"][0]).all() and np.isfinite(r0["pf_run"][0]).all() and (r0["planner"][2] == 2).all()
     for name, first in rounds[0].items():
         for i, (a, b) in enumerate(zip(first, rounds[1][name])):
-            assert a.shape == b.shape and _same_bits(a, b), (name, i)
+            assert a.shape == b.shape and same_bits(a, b), (name, i)
     # the sliced and the overlapped scans are the plain fan itself
-    assert _same_bits(rounds[0]["sliced"][0], fan0) and _same_bits(rounds[0]["overlap"][0], fan0)
+    assert same_bits(rounds[0]["sliced"][0], fan0) and same_bits(rounds[0]["overlap"][0], fan0)

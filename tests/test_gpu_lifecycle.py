@@ -7,21 +7,15 @@ import gc
 import numpy as np
 import pytest
 
+import support
 from pyracecarsimulator_amd import _lib, maps, range_libc
-from pyracecarsimulator_amd import racecar as RC
-from pyracecarsimulator_amd.followgap import PyFollowGap
 from pyracecarsimulator_amd.mcts import MCTSPlanner
 from pyracecarsimulator_amd.particle_filter import ParticleFilter
 from pyracecarsimulator_amd.policy import Policy
 from pyracecarsimulator_amd.racecar import CarBatch
 from pyracecarsimulator_amd.scan_simulator import ScanSimulator2D
 
-pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
 
 def _free_bytes(torch):
@@ -57,7 +51,7 @@ def _one_life(g, poses, B, fov, with_big_tables):
     sim.setMap(omap, 120, g.resolution, g.origin)
     sim.setRaytracingMethod("RMGPU")
     sim.scanMany(poses.astype(np.float64))
-    fg = PyFollowGap(10, 15.0, 0.4189, fov / B)
+    fg = support.followgap(inc=fov / B)
     fg.eval(out[:B].copy(), B)
     car = CarBatch(device=0)
     pin = _lib.pinned_zeros((len(poses) * B,), np.float32)
@@ -151,13 +145,13 @@ def _every_handle_life(g, poses, B, fov):
     outline cells, the MCTS planner and its drive, sensor model + repeat-angle calls + particle filter, and multi-device
     handles — each created, used once and dropped.  Returns (16 ranges of one scan, the planner's chosen actions)."""
     rng = np.random.default_rng(3)
-    edge = RC.edge_distances(B, -fov / 2, fov / B, 0.275, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
+    edge = support.edge(B, fov)
     states = np.zeros((4, 11))
     states[:, :3] = poses[:4]
     omap = range_libc.PyOMap(g)
     m = range_libc.PyRayMarchingGPU(omap, 120)
     cars = CarBatch()
-    fg = PyFollowGap(10, 15.0, 0.4189, fov / B)
+    fg = support.followgap(inc=fov / B)
     # the smallest network of tests/test_gpu_policy.py: 3 -> 1, window [7, 10)
     pol = Policy.from_arrays([(rng.standard_normal((3, 1)).astype(np.float32), np.zeros(1, np.float32))], (False,),
                              in_start=7, clip=12.5, scale=7.0)

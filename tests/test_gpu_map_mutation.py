@@ -7,37 +7,19 @@ bit for bit, and first asserts that the oracle's answer on the new grid differs 
 a handle that served a stale table would fail.  Each probe is called twice after a mutation (the first call rebuilds,
 the second takes the cached tables).
 
-TABLE_CACHES names the case that covers each ``*_epoch == m->epoch`` guard under csrc/; tests/test_host.py keeps it in
+tests/coverage_tables.py TABLE_CACHES names the case that covers each ``*_epoch == m->epoch`` guard under csrc/; tests/test_host.py keeps it in
 step with the sources."""
 import threading
 
 import numpy as np
 import pytest
 
+import support
 from pyracecarsimulator_amd import _lib, maps, range_libc
 
-pytestmark = pytest.mark.gpu
-
-#: (source file, epoch field of the guard, the table it guards, the case that fails when the guard goes stale)
-TABLE_CACHES = [
-    ("abi_fan.hip", "lut_epoch", "ensure_lut: GiantLUT table", "test_warm_handles_follow_a_mutation_script (LUT)"),
-    ("abi_fan.hip", "cddt_epoch", "ensure_cddt: CDDT blocked table",
-     "test_warm_handles_follow_a_mutation_script (CDDT pose-major, theta-major, lds_sort 128); test_multi_device_map_mutations"),
-    ("abi_fan.hip", "blpad_epoch", "ensure_blpad: Bresenham padded bit maps",
-     "test_warm_handles_follow_a_mutation_script (BL variant 1)"),
-    ("abi_fan.hip", "pdt_epoch", "opts_of: code_entries the planner sees",
-     "test_code_map_palette_follows_updates"),
-    ("abi_fan.hip", "pdt_epoch", "ensure_step_map: step map, code map and palette",
-     "test_warm_handles_follow_a_mutation_script (RM, RMGPU code map / row-major); test_entry_points_after_a_stamp"),
-]
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
 MRX, B, FOV, TD = 120, 256, 6.2, 112
-EDGE_ARGS = (0.275, 0.2032, 0.3302)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
 
 
 def _dev_occ(omap):
@@ -143,7 +125,7 @@ def _fan(m, poses, aux=False):
     return out, hits, steps
 
 
-def _same(a, b):
+def _all_equal(a, b):
     return all(np.array_equal(x, y) for x, y in zip(a, b))
 
 
@@ -169,15 +151,15 @@ def _run_script(oracle_mod, omap, g, base0, steps, probes):
     prev = {}
     for name, dev, ora in probes:
         prev[name] = ora(om)
-        assert _same(dev(), prev[name]), (name, "epoch 0")
+        assert _all_equal(dev(), prev[name]), (name, "epoch 0")
     for label, action, grid in steps:
         _apply(omap, action)
         om = _check_map(oracle_mod, omap, grid, g, label)
         for name, dev, ora in probes:
             want = ora(om)
-            assert not _same(want, prev[name]), (name, label, "the probe does not see this mutation")
+            assert not _all_equal(want, prev[name]), (name, label, "the probe does not see this mutation")
             for call in (1, 2):
-                assert _same(dev(), want), (name, label, call)
+                assert _all_equal(dev(), want), (name, label, call)
             prev[name] = want
 
 
@@ -190,7 +172,7 @@ def test_warm_handles_follow_a_mutation_script(oracle_mod):
     g = maps.GridMap(base0, 0.05, (-1.3, 0.7, 0.25), "mut")
     poses = _poses(g, [base0], focus, 40, 3)
     omap = range_libc.PyOMap(g)
-    edge = oracle_mod.edge_distances(B, -FOV / 2, FOV / B, *EDGE_ARGS)
+    edge = support.oracle_edge(oracle_mod, B, FOV)
     grp = len(poses) // 2
     probes = []
 
@@ -317,7 +299,7 @@ def test_entry_points_after_a_stamp(oracle_mod):
     sparse[::B] = poses
     rm = range_libc.PyRayMarching(omap, MRX)                    # upstream-literal arithmetic in both arities
     dev = range_libc.PyRayMarchingGPU(omap, MRX)
-    edge = oracle_mod.edge_distances(B, -FOV / 2, FOV / B, *EDGE_ARGS)
+    edge = support.oracle_edge(oracle_mod, B, FOV)
     group = len(poses) // 4
     d_poses = torch.from_numpy(poses).cuda()
     d_edge = torch.from_numpy(edge).cuda()
@@ -357,7 +339,7 @@ def test_entry_points_after_a_stamp(oracle_mod):
     w0, w1 = ref(om0), ref(om1)
     for k in (0, 1, 2, 5):                     # ranges of every form (and of the roll-out poses) see the stamp
         assert not np.array_equal(w0[k], w1[k]), k
-    assert _same(run(), w0[:5])
+    assert _all_equal(run(), w0[:5])
     omap.stamp_cells(stamp)
     assert np.array_equal(omap.distance_transform(), om1.dt)
     for call in (1, 2):

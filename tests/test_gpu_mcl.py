@@ -9,72 +9,16 @@ import numpy as np
 import pytest
 
 import mcl_statement as MS
-import pf_statement as PS
-from conftest import load_golden
+from pf_cases import MAPS, MCL_KINDS as KINDS, STD, T, MclWorld as World, assert_equal_to_statement, both, mcl_fused
+from support import same_bits
 from pyracecarsimulator_amd import ParticleFilter, _lib, range_libc
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
 f32 = np.float32
 RL_ERR_INVALID, RL_ERR_UNSUPPORTED = -1, -4           # include/scanlib.h rl_status
-THETA = 112
-#: name -> (class, extra constructor arguments, variant or None, arithmetic)
-KINDS = {
-    "RM-3": (range_libc.PyRayMarching, (), 3, "literal"),
-    "RMGPU-1": (range_libc.PyRayMarchingGPU, (), 1, "canonical"),
-    "CDDT": (range_libc.PyCDDTCast, (THETA,), None, "cddt"),
-    "GLT": (range_libc.PyGiantLUTCast, (THETA,), None, "lut"),
-}
-MAPS = ("rm_maze256", "rm_maze192_yaw")
-T = 3
-STD = (0.02, 0.02, 0.01)
 #: (P, A, resample ratio): every P of {1, 256, 600} and A of {1, 7, 54}; ratio 2 always resamples, 0 never, 0.5 as neff says
 RUNS = [(600, 54, 2.0), (256, 7, 2.0), (1, 1, 2.0), (600, 7, 0.0), (256, 1, 0.5), (1, 54, 0.5)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
-
-
-class World:
-    """One fixture map: the device map, the oracle map, the handles made on it and the cases drawn on it."""
-
-    def __init__(self, oracle_mod, name):
-        self.name = name
-        self.g, z = load_golden(name)
-        self.fov, self.mrx = float(z["fov"]), int(z["max_range_px"])
-        self.om = oracle_mod.OracleMap.from_gridmap(self.g, self.mrx)
-        self.omap = range_libc.PyOMap(self.g)
-        self.inv_res = PS.inv_res_of(self.g.resolution)
-        self.methods, self.cases = {}, {}
-
-    def method(self, kind):
-        if kind not in self.methods:
-            cls, extra, variant, _ = KINDS[kind]
-            m = cls(self.omap, self.mrx, *extra)
-            if variant is not None:
-                m.set_option("variant", variant)
-            self.methods[kind] = m
-        return self.methods[kind]
-
-    def case(self, P, A, n_steps=T):
-        key = (P, A, n_steps)
-        if key not in self.cases:
-            self.cases[key] = MS.localisation_case(self.g, self.om.dt, self.mrx, self.fov, P, A, n_steps)
-        return self.cases[key]
-
-    def likelihood(self, kind, angles, table):
-        """The statement's L: the kind's ranges by the oracle / tests/pf_statement.py and the ascending product.  The
-        oracle's table kinds are stated for a yaw-0 origin; on the yawed map theirs is the public fused call itself,
-        which is what the contract says L is."""
-        form = KINDS[kind][3]
-        m = self.method(kind)
-
-        if form in ("cddt", "lut") and float(self.g.origin[2]) != 0.0:
-            return lambda q, obs, t: _fused(m, q, angles, obs)
-        return MS.statement_likelihood(self.g, self.om, self.mrx, form, angles, table, THETA,
-                                       m.table() if form == "lut" else None)
 
 
 @pytest.fixture(scope="module")
@@ -88,47 +32,6 @@ def worlds(oracle_mod):
     return get
 
 
-def _fused(m, q, angles, obs):
-    wts = np.full(q.shape[0], -1.0)
-    m.calc_range_repeat_angles_eval_sensor_model(np.ascontiguousarray(q, f32), angles, np.ascontiguousarray(obs, f32), wts)
-    return wts
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def _assert_equal_to_statement(pf, out, st, want, what):
-    est, neff, flags = out
-    w_est, w_neff, w_flags = want
-    print(what, "neff", neff, "flags", flags)
-    assert _same(flags, w_flags), (what, flags, w_flags)
-    assert _same(neff, w_neff), (what, neff, w_neff)
-    assert _same(est, w_est), (what, est - w_est)
-    rd = pf.read()
-    assert _same(rd["likelihood"], st.L), (what, int((rd["likelihood"] != st.L).sum()))
-    assert _same(rd["cum"], st.cum), (what, int((rd["cum"] != st.cum).sum()))
-    assert _same(rd["ancestors"], st.anc), (what, int((rd["ancestors"] != st.anc).sum()))
-    assert _same(rd["weights"], st.w), (what, int((rd["weights"] != st.w).sum()))
-    assert _same(rd["particles"], st.X), (what, int((rd["particles"] != st.X).sum()))
-
-
-def _both(w, kind, P, A, ratio, std=STD, seed=3, weights=None, n_steps=T, table=None):
-    """The device filter and the statement after the same n_steps steps of case (P, A); ``table`` replaces the case's."""
-    parts, angles, odom, obs, case_table = w.case(P, A, n_steps)
-    table = case_table if table is None else table
-    m = w.method(kind)
-    m.set_sensor_model(table)
-    pf = ParticleFilter(m, angles, P, motion_std=std, resample_ratio=ratio)
-    pf.reset(parts, weights=weights, seed=seed)
-    out = pf.run_raw(odom, obs)
-    st = MS.Filter(w.likelihood(kind, angles, table), P, std, ratio)
-    st.reset(parts, weights=weights, seed=seed)
-    want = st.run(odom, obs)
-    return pf, out, st, want
-
-
 # ---------------------------------------------------------------- 1. the statement, bit for bit
 @pytest.mark.parametrize("name", MAPS)
 @pytest.mark.parametrize("kind", sorted(KINDS))
@@ -136,8 +39,8 @@ def test_runs_equal_the_statement(worlds, kind, name):
     w = worlds(name)
     seen = 0
     for P, A, ratio in RUNS:
-        pf, out, st, want = _both(w, kind, P, A, ratio)
-        _assert_equal_to_statement(pf, out, st, want, (kind, name, P, A, ratio))
+        pf, out, st, want = both(w, kind, P, A, ratio)
+        assert_equal_to_statement(pf, out, st, want, (kind, name, P, A, ratio))
         seen |= 1 << int(out[2][-1])
         if ratio == 2.0:
             assert (out[2] & MS.RESAMPLED).all()
@@ -145,7 +48,7 @@ def test_runs_equal_the_statement(worlds, kind, name):
                 n = np.bincount(pf.read()["ancestors"], minlength=P)
                 assert (n == 0).mean() >= 0.25 and n.max() >= 3
         if ratio == 0.0:
-            assert not out[2].any() and _same(pf.read()["ancestors"], np.arange(P, dtype=np.int32))
+            assert not out[2].any() and same_bits(pf.read()["ancestors"], np.arange(P, dtype=np.int32))
         pf.close()
     assert seen & 0b11 == 0b11                            # runs ended both on a resampled and on a kept step
 
@@ -159,8 +62,8 @@ def test_multi_pass_tiles_and_given_weights(worlds):
     m.set_option("pf_block", 2)
     try:
         given = np.random.default_rng(8).uniform(0.5, 1.5, 256) * 1e-29
-        pf, out, st, want = _both(w, "RMGPU-1", 256, 7, 0.5, weights=given)
-        _assert_equal_to_statement(pf, out, st, want, "pf_block 2")
+        pf, out, st, want = both(w, "RMGPU-1", 256, 7, 0.5, weights=given)
+        assert_equal_to_statement(pf, out, st, want, "pf_block 2")
         assert m.get_info("pf_block") == 2
     finally:
         m.set_option("pf_block", 0)
@@ -170,12 +73,12 @@ def test_motion_noise_off_and_per_axis(worlds):
     w = worlds(MAPS[1])
     got = {}
     for std in ((0.0, 0.0, 0.0), (0.03, 0.0, 0.0), (0.0, 0.0, 0.02)):
-        pf, out, st, want = _both(w, "RM-3", 600, 7, 0.0, std=std)
-        _assert_equal_to_statement(pf, out, st, want, std)
+        pf, out, st, want = both(w, "RM-3", 600, 7, 0.0, std=std)
+        assert_equal_to_statement(pf, out, st, want, std)
         got[std] = pf.read()["particles"]
     # an axis with std 0 draws nothing and adds nothing: with noise on x alone, y and theta are the quiet run's
     quiet, x_only, th_only = (got[k] for k in ((0.0, 0.0, 0.0), (0.03, 0.0, 0.0), (0.0, 0.0, 0.02)))
-    assert _same(x_only[:, 1:], quiet[:, 1:]) and (x_only[:, 0] != quiet[:, 0]).mean() > 0.9
+    assert same_bits(x_only[:, 1:], quiet[:, 1:]) and (x_only[:, 0] != quiet[:, 0]).mean() > 0.9
     assert (th_only[:, 2] != quiet[:, 2]).mean() > 0.9
 
 
@@ -197,17 +100,17 @@ def test_run_three_equals_run_one_then_two(worlds, kind):
         first = b.run_raw(odom[:1], obs[:1])
         rest = b.run_raw(odom[1:], obs[1:])
         for x, y, z in zip(whole, first, rest):
-            assert _same(x, np.concatenate([y, z]))
+            assert same_bits(x, np.concatenate([y, z]))
         ra, rb = a.read(), b.read()
-        assert all(_same(ra[k], rb[k]) for k in ra)
+        assert all(same_bits(ra[k], rb[k]) for k in ra)
         # the poses of run() are the raw sums' (x, y, atan2(sin, cos))
         a.reset(parts, seed=5)
         poses, neff, flags = a.run(odom, obs)
-        assert _same(poses, MS.pose_of(whole[0])) and _same(neff, whole[1]) and _same(flags, whole[2])
+        assert same_bits(poses, MS.pose_of(whole[0])) and same_bits(neff, whole[1]) and same_bits(flags, whole[2])
         # step() is run() of one row
         b.reset(parts, seed=5)
         pose, ne, fl = b.step(odom[0], obs[0])
-        assert _same(pose, poses[0]) and ne == neff[0] and fl == flags[0]
+        assert same_bits(pose, poses[0]) and ne == neff[0] and fl == flags[0]
     finally:
         m.set_noise(0.0)
 
@@ -235,17 +138,17 @@ def test_likelihood_is_the_public_fused_call_scan_noise_included(worlds, kind):
                 rd = pf.read()
                 q = rd["particles"].astype(f32)
                 # the handle's offset is back at R0: the public call at the handle's own offset ...
-                at_entry = _fused(m, q, angles, obs[n_steps - 1])
+                at_entry = mcl_fused(m, q, angles, obs[n_steps - 1])
                 m.set_noise(noise, seed=77, ray_offset=R0)
-                assert _same(at_entry, _fused(m, q, angles, obs[n_steps - 1]))
+                assert same_bits(at_entry, mcl_fused(m, q, angles, obs[n_steps - 1]))
                 # ... and L at the step's
                 m.set_noise(noise, seed=77, ray_offset=R0 + (n_steps - 1) * P * A)
-                L = _fused(m, q, angles, obs[n_steps - 1])
+                L = mcl_fused(m, q, angles, obs[n_steps - 1])
                 m.set_noise(noise, seed=77, ray_offset=R0)
-                assert _same(rd["likelihood"], L), (kind, noise, n_steps)
+                assert same_bits(rd["likelihood"], L), (kind, noise, n_steps)
                 if n_steps == 1:
                     omega = np.full(P, 1.0 / P) * L
-                    assert _same(rd["weights"], omega / np.float64(MS.bs(omega)))
+                    assert same_bits(rd["weights"], omega / np.float64(MS.bs(omega)))
                     if noise:
                         assert (at_entry == L).all()          # (step 0's offset is the entry offset)
                 elif noise:
@@ -270,9 +173,9 @@ def test_all_zero_table_is_degenerate(worlds):
         est, neff, flags = pf.run_raw(odom, obs)
         st = MS.Filter(lambda q, o, t: np.zeros(P), P, STD, ratio)
         st.reset(parts, seed=1)
-        _assert_equal_to_statement(pf, (est, neff, flags), st, st.run(odom, obs), ("zero table", ratio))
+        assert_equal_to_statement(pf, (est, neff, flags), st, st.run(odom, obs), ("zero table", ratio))
         assert (flags == flag).all()
-        assert _same(pf.read()["weights"], np.full(P, 1.0 / P)) and not pf.read()["likelihood"].any()
+        assert same_bits(pf.read()["weights"], np.full(P, 1.0 / P)) and not pf.read()["likelihood"].any()
         assert np.isfinite(est).all()
 
 
@@ -285,14 +188,14 @@ def test_reset_is_idempotent(worlds):
     pf = ParticleFilter(m, angles, P, motion_std=STD, resample_ratio=0.5)
     pf.reset(parts, seed=4)
     rd = pf.read()
-    assert _same(rd["particles"], parts) and _same(rd["weights"], np.full(P, 1.0 / P))
+    assert same_bits(rd["particles"], parts) and same_bits(rd["weights"], np.full(P, 1.0 / P))
     one = pf.run_raw(odom, obs), pf.read()
     pf.reset(parts, seed=4)
     pf.reset(parts, seed=4)
     two = pf.run_raw(odom, obs), pf.read()
-    assert all(_same(x, y) for x, y in zip(one[0], two[0])) and all(_same(one[1][k], two[1][k]) for k in one[1])
+    assert all(same_bits(x, y) for x, y in zip(one[0], two[0])) and all(same_bits(one[1][k], two[1][k]) for k in one[1])
     pf.reset(parts, seed=5)                                   # (another seed: other draws)
-    assert not _same(pf.run_raw(odom, obs)[0], one[0][0])
+    assert not same_bits(pf.run_raw(odom, obs)[0], one[0][0])
 
 
 # ---------------------------------------------------------------- 4. errors
@@ -359,4 +262,4 @@ def test_every_error_of_the_contract_and_a_correct_run_afterwards(worlds):
     assert run() == 0
     st = MS.Filter(w.likelihood("RMGPU-1", angles, table), P, STD, 0.5)
     st.reset(parts, seed=3)
-    _assert_equal_to_statement(pf, (est, neff, flags), st, st.run(odom, obs), "after the errors")
+    assert_equal_to_statement(pf, (est, neff, flags), st, st.run(odom, obs), "after the errors")

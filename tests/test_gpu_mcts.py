@@ -11,118 +11,28 @@ import numpy as np
 import pytest
 
 from conftest import GOLD
-import mcts_statement as S
 import policy_statement as PS
-from test_gpu_drive import _edge, _ref_libs, _same_bits, _starts, _within_one_ulp
+import support
+from mcts_checks import B, EVERY, L, MAX_SPEED, SPEED, answers, assert_tree, device, replay, roots, scan
+from oracle import reference
+from support import D_BASE, FOV, MAX_STEER, THRESH, same_bits, within_one_ulp
 from pyracecarsimulator_amd import MCTS, Policy, RacecarSimulator, _lib, maps, range_libc
 from pyracecarsimulator_amd import racecar as RC
-from pyracecarsimulator_amd.followgap import PyFollowGap
-from pyracecarsimulator_amd.mcts import MCTSPlanner, TREE_FIELDS
+from pyracecarsimulator_amd.mcts import MCTSPlanner
 
-pytestmark = pytest.mark.gpu
-
-FOV, B, THRESH, D_BASE = 4.71, 1081, 0.001, 0.275
-MAX_STEER, MAX_SPEED = RC.DEFAULT_CAR["max_steer_ang"], RC.DEFAULT_CAR["max_speed"]
-L, EVERY, SPEED = 200, 10, 2.0
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
 
 @pytest.fixture(scope="module")
 def handles():
     layers, relu = PS.load_fixture(os.path.join(GOLD, "policy_mlp720.npz"))
-    return {"fg": PyFollowGap(10, 15.0, MAX_STEER, 0.004), "nn": Policy.from_arrays(layers, relu), "random": None}
-
-
-def _roots(g, dt, K, seed):
-    states, _ = _starts(g, dt, K - K // 3, seed, 6.0, speed_hi=3.0)
-    if K // 3:
-        near, _ = _starts(g, dt, K // 3, seed + 1, 1.2, speed_hi=3.0)        # close to walls: terminal children
-        states = np.concatenate([states, near])
-    rng = np.random.default_rng(seed)
-    return states, rng.uniform(-0.3, 0.3, K), rng.integers(0, 2 ** 63, K, dtype=np.uint64) * np.uint64(2) + np.uint64(1)
-
-
-def _answers(source, h, ranges, num_rays=B):
-    if source == "fg":
-        return h.eval_many(np.ascontiguousarray(ranges), num_rays).astype(np.float32)
-    if source == "nn":
-        return h.predict_many(np.ascontiguousarray(ranges)).astype(np.float32)
-    return np.full(len(ranges), np.nan, np.float32)
-
-
-def _scan(m, std, base, poses, num_rays=B):
-    m.set_noise(std, 99, base)
-    out = np.empty(len(poses) * num_rays, np.float32)
-    m.calc_range_fan(np.ascontiguousarray(poses, np.float32), out, FOV, num_rays)
-    return out.reshape(len(poses), num_rays)
-
-
-def _replay(cars, m, std, base, source, h, states, actions, seeds, n_it, dev_trees, snapshots, *, num_rays=B,
-            rollout_steps=L, action_every=EVERY, edge=None, is_crashed=RC.is_crashed, rollouts=None):
-    """The statement of K trees replayed with the public calls; scan poses from the device dump (dev_trees: the
-    read_tree dicts of a run of >= n_it iterations).  edge: the planner's outline table (the car's by default);
-    is_crashed: the crash test of the act scans; rollouts: a list that receives every roll-out the statement asks
-    for, (crash index, velocities)."""
-    K, nb, L_ = len(states), num_rays, rollout_steps
-    edge = _edge(nb) if edge is None else edge
-    n_act = (L_ + action_every - 1) // action_every
-    pose0 = np.stack([dev_trees[k]["scan_pose"][0] for k in range(K)])
-    ans0 = _answers(source, h, _scan(m, std, base, pose0, nb), nb)
-    trees = [S.Tree(states[k].copy(), pose0[k], float(ans0[k]) if source != "random" else math.nan, float(actions[k]),
-                    int(seeds[k]), source=source) for k in range(K)]
-    last = {}
-
-    def act_many(i, reqs):
-        st = np.stack([node.state for _, node, _ in reqs])
-        ac = np.array([[SPEED, a] for _, _, a in reqs])[:, None, :]
-        _, out, _ = cars.rollout(st, ac, n_steps=1, action_every=1)
-        poses = np.stack([dev_trees[k]["scan_pose"][i + 1] for k in range(K)])
-        ranges = _scan(m, std, base + (K + i * K * (1 + L_)) * nb, poses, nb)
-        ans = _answers(source, h, ranges, nb)
-        last["states"] = out
-        return [(out[k], poses[k], float(ans[k]) if source != "random" else math.nan,
-                 is_crashed(ranges[k], nb, 1, edge, THRESH) >= 0) for k in range(K)]
-
-    def rollout_many(i, reqs, acts):
-        acts_ro = np.stack([S.rollout_actions(int(seeds[k]), i, n_act, MAX_STEER, MAX_SPEED) for k in range(K)])
-        m.set_noise(std, 99, base + (K + i * K * (1 + L_) + K) * nb)
-        first, _, vel = cars.rollout_check(m, last["states"], acts_ro, FOV, nb, edge, THRESH, n_steps=L_,
-                                           action_every=action_every)
-        if rollouts is not None:
-            rollouts.extend((int(first[k]), vel[k].copy()) for k, _ in reqs)
-        return [(int(first[k]), vel[k]) for k, _ in reqs]
-
-    snaps = S.run_lockstep(trees, n_it, act_many, rollout_many, snapshots=snapshots)
-    m.set_noise(std, 99, base)
-    return trees, snaps
-
-
-def _device(cars, m, std, base, source, h, states, actions, seeds, n_it, max_nodes=None, *, num_rays=B,
-            rollout_steps=L, action_every=EVERY, edge=None):
-    m.set_noise(std, 99, base)
-    pl = MCTSPlanner(cars, m, len(states), max_nodes or n_it + 1, FOV, num_rays,
-                     _edge(num_rays) if edge is None else edge, THRESH, source=source,
-                     followgap=h if source == "fg" else None, policy=h if source == "nn" else None,
-                     rollout_steps=rollout_steps, action_every=action_every)
-    pl.reset(states, actions, seeds)
-    pl.run(n_it)
-    return pl, [pl.read_tree(k) for k in range(len(states))], pl.best()
-
-
-def _assert_tree(got, want, what):
-    for f in TREE_FIELDS:
-        assert got[f].shape == want[f].shape, (what, f)
-        assert _same_bits(got[f], want[f]), (what, f, np.nonzero(got[f] != want[f]))
+    return {"fg": support.followgap(), "nn": Policy.from_arrays(layers, relu), "random": None}
 
 
 # ---------------------------------------------------------------- 1. the act links
 @pytest.mark.parametrize("source", ["fg", "nn"])
 def test_act_links_against_public_calls_and_reference(handles, source):
-    L_, F = _ref_libs()
+    reference.require()
     g = maps.load_colombia()
     omap = range_libc.PyOMap(g)
     dt = omap.distance_transform()
@@ -130,24 +40,22 @@ def test_act_links_against_public_calls_and_reference(handles, source):
     h = handles[source]
     cars = RC.CarBatch()
     K, n_it, std, base = 6, 24, 0.05, 777
-    states, actions, seeds = _roots(g, dt, K, 31)
-    pl, trees, _ = _device(cars, m, std, base, source, h, states, actions, seeds, n_it)
+    states, actions, seeds = roots(g, dt, K, 31)
+    pl, trees, _ = device(cars, m, std, base, source, h, states, actions, seeds, n_it)
     assert m.get_info("nt_store") == 1
-    edge = _edge()
-    ref = L_.ref_car_create((C.c_double * 17)(*[RC.DEFAULT_CAR[k] for k in RC.CAR_PARAM_ORDER]))
-    buf = (C.c_double * 11)()
+    edge = support.edge(B)
+    ref = reference.RefCar()
     n_term = 0
     try:
         for k in range(K):
             t = trees[k]
-            assert len(t["parent"]) == n_it + 1 and _same_bits(t["state"][0], states[k])
+            assert len(t["parent"]) == n_it + 1 and same_bits(t["state"][0], states[k])
             for c in range(n_it + 1):
                 st = t["state"][c]
-                want_p = np.array([st[0] + D_BASE * np.cos(st[2]), st[1] + D_BASE * np.sin(st[2]), st[2]])
-                assert _within_one_ulp(want_p.astype(np.float32), t["scan_pose"][c]), (k, c)
+                assert within_one_ulp(support.lidar_poses(st), t["scan_pose"][c]), (k, c)
                 off = base + (k * B if c == 0 else (K + (c - 1) * K * (1 + L) + k) * B)
-                ranges = _scan(m, std, off, t["scan_pose"][c][None, :])
-                assert _same_bits(_answers(source, h, ranges), t["answer"][c:c + 1]), (k, c)
+                ranges = scan(m, std, off, t["scan_pose"][c][None, :])
+                assert same_bits(answers(source, h, ranges), t["answer"][c:c + 1]), (k, c)
                 crashed = RC.is_crashed(ranges[0], B, 1, edge, THRESH) >= 0
                 assert t["terminal"][c] == (int(crashed) if c > 0 else 0), (k, c)
                 n_term += int(t["terminal"][c])
@@ -156,20 +64,16 @@ def test_act_links_against_public_calls_and_reference(handles, source):
                 par = t["parent"][c]
                 _, out, _ = cars.rollout(t["state"][par][None, :], np.array([[[SPEED, t["action"][c]]]]), n_steps=1,
                                          action_every=1)
-                assert _same_bits(out[0], st), (k, c)
-                L_.ref_car_set_state(ref, (C.c_double * 11)(*t["state"][par]))
-                L_.ref_car_control(ref, SPEED, float(t["action"][c]))
-                L_.ref_car_update_position(ref, 0.01)
-                L_.ref_car_get_state(ref, buf)
-                assert np.allclose(st, np.array(buf), rtol=1e-9, atol=1e-9), (k, c)
+                assert same_bits(out[0], st), (k, c)
+                assert np.allclose(st, ref.step(t["state"][par], SPEED, t["action"][c]), rtol=1e-9, atol=1e-9), (k, c)
     finally:
-        L_.ref_car_destroy(ref)
+        ref.close()
         m.set_noise(0.0, 0, 0)
     assert n_term >= 0
 
 
 # ---------------------------------------------------------------- 2. whole trees against the statement
-def _maze_methods(omap, mrx):
+def _method_factories(omap, mrx):
     return [("RM", lambda: range_libc.PyRayMarching(omap, mrx), 0.0),
             ("RMGPU", lambda: range_libc.PyRayMarchingGPU(omap, mrx), 0.05),
             ("CDDT", lambda: range_libc.PyCDDTCast(omap, mrx, 112), 0.0),
@@ -188,27 +92,27 @@ def maze():
 @pytest.mark.parametrize("source", ["fg", "nn", "random"])
 def test_whole_trees_equal_statement(handles, maze, method, source):
     g, omap, dt = maze
-    name, make, std = [x for x in _maze_methods(omap, 300) if x[0] == method][0]
+    name, make, std = [x for x in _method_factories(omap, 300) if x[0] == method][0]
     m = make()
     h = handles[source]
     cars = RC.CarBatch()
     base = 4242
     n_term = 0
     for K in (1, 7, 64):
-        states, actions, seeds = _roots(g, dt, K, 100 + K)
-        _, trees37, best37 = _device(cars, m, std, base, source, h, states, actions, seeds, 37)
-        stmt, snaps = _replay(cars, m, std, base, source, h, states, actions, seeds, 37, trees37, (1, 2, 37))
+        states, actions, seeds = roots(g, dt, K, 100 + K)
+        _, trees37, best37 = device(cars, m, std, base, source, h, states, actions, seeds, 37)
+        stmt, snaps = replay(cars, m, std, base, source, h, states, actions, seeds, 37, trees37, (1, 2, 37))
         for n in (1, 2, 37):
             if n == 37:
                 trees, best = trees37, best37
             else:
-                _, trees, best = _device(cars, m, std, base, source, h, states, actions, seeds, n)
+                _, trees, best = device(cars, m, std, base, source, h, states, actions, seeds, n)
             for k in range(K):
-                _assert_tree(trees[k], snaps[n][k], (name, source, K, n, k))
+                assert_tree(trees[k], snaps[n][k], (name, source, K, n, k))
             if n == 37:
                 for k in range(K):
                     a, v = stmt[k].best()
-                    assert best[1][k] == v and _same_bits(best[0][k:k + 1], np.array([a])), (K, k)
+                    assert best[1][k] == v and same_bits(best[0][k:k + 1], np.array([a])), (K, k)
                     assert best[2][k] == 38
         for k in range(K):
             t = snaps[37][k]
@@ -225,9 +129,9 @@ def test_chunking_and_batching_invariance(handles, maze):
     m = range_libc.PyRayMarchingGPU(omap, 300)
     h = handles["fg"]
     K, n = 16, 30
-    states, actions, seeds = _roots(g, dt, K, 7)
+    states, actions, seeds = roots(g, dt, K, 7)
     m.set_noise(0.05, 99, 555)
-    pl = MCTSPlanner(cars, m, K, n + 1, FOV, B, _edge(), THRESH, source="fg", followgap=h)
+    pl = MCTSPlanner(cars, m, K, n + 1, FOV, B, support.edge(B), THRESH, source="fg", followgap=h)
     pl.reset(states, actions, seeds)
     pl.run(n)
     whole = [pl.read_tree(k) for k in range(K)]
@@ -236,13 +140,13 @@ def test_chunking_and_batching_invariance(handles, maze):
     pl.run(0)
     pl.run(n - n // 2)
     for k in range(K):
-        _assert_tree(pl.read_tree(k), whole[k], ("chunked", k))
+        assert_tree(pl.read_tree(k), whole[k], ("chunked", k))
     # tree k alone with seeds[k] == tree k in the batch (noise off: the ray ids depend on K)
     m.set_noise(0.0, 0, 0)
-    _, batch, _ = _device(cars, m, 0.0, 0, "fg", h, states, actions, seeds, n)
+    _, batch, _ = device(cars, m, 0.0, 0, "fg", h, states, actions, seeds, n)
     for k in (0, 5, 15):
-        _, alone, _ = _device(cars, m, 0.0, 0, "fg", h, states[k:k + 1], actions[k:k + 1], seeds[k:k + 1], n)
-        _assert_tree(alone[0], batch[k], ("alone", k))
+        _, alone, _ = device(cars, m, 0.0, 0, "fg", h, states[k:k + 1], actions[k:k + 1], seeds[k:k + 1], n)
+        assert_tree(alone[0], batch[k], ("alone", k))
 
 
 # ---------------------------------------------------------------- 4. errors
@@ -252,26 +156,26 @@ def test_errors_leave_handles_usable(handles, maze):
     m = range_libc.PyRayMarchingGPU(omap, 300)
     fg, pol = handles["fg"], handles["nn"]
     K = 4
-    states, actions, seeds = _roots(g, dt, K, 9)
+    states, actions, seeds = roots(g, dt, K, 9)
     m.set_noise(0.05, 7, 321)
     poses = maps.sample_free_poses(g, 8, 3, 4.0, dt)
     scan0 = np.empty(8 * B, np.float32)
     m.calc_range_fan(poses, scan0, FOV, B)
-    _, want, _ = _device(cars, m, 0.05, 321, "fg", fg, states, actions, seeds, 3)
+    _, want, _ = device(cars, m, 0.05, 321, "fg", fg, states, actions, seeds, 3)
     m.set_noise(0.05, 7, 321)
 
     def still_usable():
         again = np.empty_like(scan0)
         m.calc_range_fan(poses, again, FOV, B)
-        assert _same_bits(again, scan0)
+        assert same_bits(again, scan0)
         assert m.get_info("nt_store") == 1
-        _, got, _ = _device(cars, m, 0.05, 321, "fg", fg, states, actions, seeds, 3)
+        _, got, _ = device(cars, m, 0.05, 321, "fg", fg, states, actions, seeds, 3)
         for k in range(K):
-            _assert_tree(got[k], want[k], k)
+            assert_tree(got[k], want[k], k)
         m.set_noise(0.05, 7, 321)
 
     Lb = _lib.lib()
-    edge = _edge()
+    edge = support.edge(B)
 
     def params(**kw):
         p = _lib.MctsParams()
@@ -300,8 +204,8 @@ def test_errors_leave_handles_usable(handles, maze):
     expect_error(create(params(source=_lib.RL_MCTS_NN))[0])                       # NN without its handle
     expect_error(create(params(source=7))[0])
     for nr in (9, 1281):
-        expect_error(create(params(num_rays=nr), ed=_edge(nr))[0])
-    expect_error(create(params(source=_lib.RL_MCTS_NN, num_rays=899), pol_=pol._h, ed=_edge(899))[0])  # window [180, 900)
+        expect_error(create(params(num_rays=nr), ed=support.edge(nr))[0])
+    expect_error(create(params(source=_lib.RL_MCTS_NN, num_rays=899), pol_=pol._h, ed=support.edge(899))[0])  # window [180, 900)
     for bad in (dict(n_trees=0), dict(max_nodes=0), dict(rollout_steps=0), dict(rollout_steps=513),
                 dict(action_every=0)):
         expect_error(create(params(**bad))[0])
@@ -315,7 +219,7 @@ def test_errors_leave_handles_usable(handles, maze):
     with pytest.raises(_lib.ScanLibError, match="max_nodes"):
         pl.run(2)
     for k in range(K):
-        _assert_tree(pl.read_tree(k), before[k], k)
+        assert_tree(pl.read_tree(k), before[k], k)
     pl.run(1)
     assert (pl.best()[2] == 4).all()
     assert Lb.rl_mcts_run(None, 1) == -1 and Lb.rl_mcts_reset(pl._h, None, None, None) == -1
@@ -340,7 +244,7 @@ def test_errors_leave_handles_usable(handles, maze):
         MCTSPlanner(multi, m, K, 8, FOV, B, edge, THRESH, source="fg", followgap=fg)
     still_usable()
     if Lb.rl_device_count() >= 2:
-        fg1 = PyFollowGap(10, 15.0, MAX_STEER, 0.004, device=1)
+        fg1 = support.followgap(device=1)
         with pytest.raises(_lib.ScanLibError, match="device"):
             MCTSPlanner(cars, m, K, 8, FOV, B, edge, THRESH, source="fg", followgap=fg1)
         still_usable()
@@ -389,14 +293,14 @@ def test_facade_matches_planner():
     for nd in nodes:
         i = nd.index
         assert nd.visits == arr["visits"][i] and nd.terminal == bool(arr["terminal"][i])
-        assert _same_bits(np.float64(nd.reward), arr["reward"][i]) and _same_bits(np.float64(nd.action), arr["action"][i])
-        assert _same_bits(nd.state, arr["state"][i])
+        assert same_bits(np.float64(nd.reward), arr["reward"][i]) and same_bits(np.float64(nd.action), arr["action"][i])
+        assert same_bits(nd.state, arr["state"][i])
         assert [c.index for c in nd.children] == ([] if arr["first_child"][i] < 0 else
                                                   _siblings(arr, arr["first_child"][i]))
     assert max(agent.root.children, key=lambda c: c.visits).action == a       # (first of equals: max keeps the first)
     # the many-trees façade: the same tree from the same state and seed
     acts, vis, nn = sim.planMCTSMany(sim.getState()[None, :], n, seeds=[3], root_actions=0.05)
-    assert _same_bits(acts, best_a) and (vis == best_v).all() and (nn == n_nodes).all()
+    assert same_bits(acts, best_a) and (vis == best_v).all() and (nn == n_nodes).all()
 
 
 def _siblings(arr, c):
@@ -441,7 +345,7 @@ def test_ucb_probe_equals_python():
     want = np.array([r / int(v) + Cc * math.sqrt(math.log(int(s)) / int(v)) for r, v, s in zip(reward, visits, sums)])
     nan = np.isnan(want)
     assert (np.isnan(out) == nan).all()
-    assert _same_bits(out[~nan], want[~nan])
+    assert same_bits(out[~nan], want[~nan])
     bad = np.zeros(1, np.int32)
     assert _lib.lib().rl_mcts_probe_ucb(0, reward.ctypes.data_as(_lib.f64p), bad.ctypes.data_as(_lib.i32p),
                                         sums.ctypes.data_as(_lib.i32p), 1, Cc, out.ctypes.data_as(_lib.f64p)) == -1

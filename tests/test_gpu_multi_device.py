@@ -11,12 +11,14 @@ single-device call — ranges, noise (global ray ids), crash indices — and to 
 import numpy as np
 import pytest
 
+import support
+from support import FOV
 from pyracecarsimulator_amd import _lib, maps, range_libc
 from pyracecarsimulator_amd import racecar as RC
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
-FOV, B, MRX = 4.71, 1081, 300
+B, MRX = 1081, 300
 
 
 def _devs(k=3):
@@ -30,11 +32,6 @@ def _devs(k=3):
 
 def _distinct():
     return _lib.lib().rl_device_count() >= 2
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
 
 
 @pytest.fixture(scope="module")
@@ -51,10 +48,6 @@ def _split(m, per_device=64):
     """A multi-device method that really cuts these (small) test batches: the default brings a device in per 512 poses."""
     m.set_option("multi_min_poses", per_device)
     return m
-
-
-def _edge():
-    return RC.edge_distances(B, -FOV / 2.0, FOV / B, 0.275, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
 
 
 def test_multi_map_shape_and_replicas(world):
@@ -189,7 +182,7 @@ def test_crash_indices_are_global(world, cls):
     g, one, multi = world
     args = (MRX, 108) if cls is range_libc.PyCDDTCast else (MRX,)
     m1, mm = cls(one, *args), _split(cls(multi, *args))
-    edge = _edge()
+    edge = support.edge(B)
     rng = np.random.default_rng(5)
     n = 900
     poses = maps.sample_free_poses(g, n, 21)
@@ -238,7 +231,7 @@ def test_rollout_chain_over_device_blocks(world):
     pm, sm, vm = cm.rollout(states, actions)
     assert np.array_equal(p1, pm) and np.array_equal(s1, sm) and np.array_equal(v1, vm)
     m1, mm = range_libc.PyRayMarchingGPU(one, MRX), _split(range_libc.PyRayMarchingGPU(multi, MRX))
-    edge = _edge()
+    edge = support.edge(B)
     f1, o1, w1 = c1.rollout_check(m1, states, actions, FOV, B, edge, 0.001)
     fm, om_, wm = cm.rollout_check(mm, states, actions, FOV, B, edge, 0.001)
     assert np.array_equal(f1, fm) and np.array_equal(o1, om_) and np.array_equal(w1, wm)
@@ -348,7 +341,7 @@ def test_device_resident_exchange_lands_in_the_consumer_gpu(world, oracle_mod, c
         m1.calc_range_fan_multi_device(poses, 8, FOV, B, consumer=0)          # not a multi-device handle
     if cls is not range_libc.PyCDDTCast:
         # the fused crash test: one int32 per roll-out lands in the consumer's memory
-        edge = _edge()
+        edge = support.edge(B)
         for n_groups, grp, consumer in ((20, 50, 0), (7, 100, nd - 1), (1, 64, 1 % nd)):
             poses = maps.sample_free_poses(g, n_groups * grp, 900 + grp)
             want = m1.check_collision_groups(poses, grp, FOV, B, edge, 0.001)

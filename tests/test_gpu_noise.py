@@ -2,119 +2,24 @@
 
 Every kernel that adds noise computes ``gauss_noise(seed, ray_id)`` (csrc/scan_device.h) with its own
 global ray id.  The contract: a fan's ray ``j`` of the caller's pose ``p`` is ``ray_offset + p * num_rays + j``,
-the many-rays calls' row ``i`` is ``ray_offset + i`` (mod 2^64).  ``check_noise`` scans clean (bit-equal to
-the CPU oracle), then with std 1 and 0.01, and requires every noisy range to be the clean range plus
+the many-rays calls' row ``i`` is ``ray_offset + i`` (mod 2^64).  ``check_noise`` (tests/noise_checks.py) scans clean
+(bit-equal to the CPU oracle), then with std 1 and 0.01, and requires every noisy range to be the clean range plus
 ``std * g`` for the oracle's Philox-2x32-10 / Box-Muller normal ``g`` of that id (oracle/np_statement.py
 ``gauss_noise_ref``), up to the rounding of the sum and ``EPS_G`` for the device's log / cos estimates.
-A ray keyed by any other id is off by ~1 at std 1.  NOISE_SITES names the case that reaches each call site;
-tests/test_host.py keeps it in step with the sources."""
+A ray keyed by any other id is off by ~1 at std 1.  tests/coverage_tables.py NOISE_SITES names the case that reaches
+each call site; tests/test_host.py keeps it in step with the sources."""
 import numpy as np
 import pytest
 
-from oracle import np_statement as N
+import support
+from noise_checks import EPS_G, SEED_HI, check_noise, max_dg
 from pyracecarsimulator_amd import _lib, maps, range_libc, workloads
 
-#: bound on |g_device - g_ref| (the hardware log2 / cos estimates in Box-Muller): the MI355X was observed at
-#: 2.0e-6 over this module, the schedules and the fuzz (``max_dg``); a ray keyed by a wrong id is off by ~1
-EPS_G = 2e-5
-
-#: every ``gauss_noise(`` call under csrc/: (file, kernel, the case here that asserts it ran that kernel)
-NOISE_SITES = [
-    ("rm_kernels.h", "rm_fan_kernel", "test_noise_rm_chunk_and_rays_kernels; test_gpu_parity schedules variant 0"),
-    ("rm_kernels.h", "rm_rays_kernel", "test_noise_many_rays_entry_points (RMGPU variant 0)"),
-    ("rm_kernels.h", "rm_fan_stream_kernel (2-3 slots)", "test_gpu_parity::test_every_kernel_schedule_is_bit_identical slots 2/3"),
-    ("rm_kernels.h", "rm_fan_stream_kernel (1 slot)", "test_gpu_parity schedules variant 1; test_noise_literal_kernels"),
-    ("rm_kernels.h", "rm_leftover_kernel", "test_gpu_parity schedules handoff; test_noise_consumers_of_noisy_ranges"),
-    ("bl_kernels.h", "bl_fan_kernel", "test_noise_bresenham_kernels (bl_lds, mrx 300 / 700)"),
-    ("bl_kernels.h", "occ_fan_lds_kernel", "test_noise_bresenham_kernels (occ_lds)"),
-    ("bl_kernels.h", "bl_fan_stream_kernel", "test_noise_bresenham_kernels (bl_stream)"),
-    ("bl_kernels.h", "bl_rays_kernel", "test_noise_many_rays_entry_points (Bresenham)"),
-    ("lut_kernels.h", "lut_fan_kernel", "test_noise_giant_lut_kernels (lut_fan)"),
-    ("lut_kernels.h", "lut_fan_lds_kernel (general statement)", "test_noise_giant_lut_kernels (lut_lds)"),
-    ("lut_kernels.h", "lut_rays_kernel", "test_noise_many_rays_entry_points (GiantLUT)"),
-    ("cddt_kernels.h", "cddt_fan_bins_kernel", "test_noise_cddt_kernels (cddt_bins, cddt_sort 0 / 1)"),
-    ("cddt_kernels.h", "cddt_theta_fan_group", "test_noise_cddt_kernels (cddt_theta, aligned / +4 B output)"),
-    ("cddt_kernels.h", "cddt_fan_kernel", "test_noise_cddt_kernels (cddt_rays)"),
-    ("cddt_kernels.h", "cddt_rays_kernel", "test_noise_many_rays_entry_points (CDDT)"),
-    ("literal_kernels.h", "rm_literal_kernel", "test_noise_literal_kernels; test_noise_many_rays_entry_points (variant 3)"),
-]
-
-pytestmark = pytest.mark.gpu
-
-SEED_HI = 0x9E3779B97F4A7C15           # a seed whose high word matters (the fold)
-_MAX_DG = [0.0]
-
-
-def max_dg():
-    """The largest |g_device - g_ref| seen so far (beyond the rounding of range + std g), over every check_noise."""
-    return _MAX_DG[0]
-
-
-def noise_mismatch(noisy, clean, std, g_ref, eps_g=EPS_G):
-    """Indices of rays whose noise is not std * g_ref (NaN positions must match, finite ones agree to
-    ulp(noisy) + std * eps_g); records the observed excess in units of g."""
-    noisy = np.asarray(noisy, np.float32)
-    clean = np.asarray(clean, np.float32)
-    nan = np.isnan(noisy)
-    bad = np.flatnonzero(nan != np.isnan(clean))
-    if bad.size:
-        return bad
-    ok = ~nan
-    d = np.abs(noisy[ok].astype(np.float64) - clean[ok].astype(np.float64) - std * g_ref[ok])
-    ulp = np.spacing(np.abs(noisy[ok])).astype(np.float64)
-    if d.size:
-        _MAX_DG[0] = max(_MAX_DG[0], float(np.max(np.maximum(d - ulp, 0.0)) / std))
-    return np.flatnonzero(ok)[d > ulp + std * eps_g]
-
-
-def check_noise(m, poses, fov, num_rays, want, seed, offset, stds=(1.0, 0.01), scan=None, ids=None,
-                kernel=None, name=None, what=""):
-    """Noise of handle ``m`` on one launch shape against the reference.
-
-    ``scan()`` launches with the handle's current noise and returns the float32 ranges (default: calc_range_fan of
-    ``poses``); ``want`` the oracle's clean ranges (None: only for the approximate occ_lds kernel); ``ids`` the global
-    ray id of every output (default ``offset + arange``); ``kernel`` / ``name`` what last_plan() must report after
-    each launch.  Returns the clean ranges."""
-    if scan is None:
-        P = len(poses)
-
-        def scan():
-            out = np.full(P * num_rays, -7.0, np.float32)
-            m.calc_range_fan(poses, out, fov, num_rays)
-            return out
-
-    def ran(tag):
-        if kernel is None and name is None:
-            return
-        pl = m.last_plan()
-        assert kernel is None or pl["kernel"] == kernel, (what, tag, pl["kernel"], pl["name"])
-        assert name is None or name in pl["name"], (what, tag, pl["name"])
-
-    m.set_noise(0.0, seed, offset)
-    clean = scan()
-    ran("clean")
-    if want is not None:
-        assert np.array_equal(clean.view(np.uint32), np.asarray(want, np.float32).view(np.uint32)), \
-            (what, "clean ranges differ from the oracle", int((clean != want).sum()))
-    if ids is None:
-        ids = N.fan_ray_ids(offset, clean.size, 1)
-    g = N.gauss_noise_ref(seed, ids)
-    try:
-        for std in stds:
-            m.set_noise(std, seed, offset)
-            noisy = scan()
-            ran("std %g" % std)
-            bad = noise_mismatch(noisy, clean, std, g)
-            assert bad.size == 0, (what, "std %g seed %#x offset %#x: %d rays off, first %s: got %r clean %r ref %r"
-                                   % (std, seed, offset, bad.size, bad[:4].tolist(), noisy[bad[:4]].tolist(),
-                                      clean[bad[:4]].tolist(), (std * g[bad[:4]]).tolist()))
-    finally:
-        m.set_noise(0.0, 0, 0)
-    return clean
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
 
 @pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
+def _report_max_dg():
     yield
     print("\nnoise: max |g_device - g_ref| beyond rounding over this module: %.3g (EPS_G %.3g)" % (max_dg(), EPS_G))
 
@@ -395,7 +300,7 @@ def test_noise_consumers_of_noisy_ranges(oracle_mod):
     g, om, omap, _ = _maze(oracle_mod)
     B, fov, grp = 1081, 4.71, 20
     poses = np.concatenate([maps.sample_free_poses(g, 150, 12, 6.0, om.dt), maps.sample_free_poses(g, 150, 13, 0.5, om.dt)])
-    edge = RC.edge_distances(B, -fov / 2, fov / B, 0.275, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
+    edge = support.edge(B, fov)
     thr = 0.001
     for cls, opts, sc in ((range_libc.PyRayMarchingGPU, {"slots": 1}, 1.0), (range_libc.PyRayMarchingGPU, {"slots": 2}, 1.0),
                           (range_libc.PyRayMarchingGPU, {"slots": 2, "handoff": 1, "handoff_cap": 8}, 1.0),

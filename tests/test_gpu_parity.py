@@ -9,17 +9,14 @@ import numpy as np
 import pytest
 
 from conftest import GOLD, load_golden
-from test_gpu_noise import SEED_HI, check_noise
+import support
+from noise_checks import SEED_HI, check_noise
+from oracle import reference
 from pyracecarsimulator_amd import ScanSimulator2D, _lib, maps, range_libc, workloads
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
 SCAN_FOV_720 = 4.71 * 720.0 / 1080.0
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
 
 
 def _fan(method, poses, fov, B):
@@ -397,7 +394,7 @@ def test_audit_mode_reproduces_the_upstream_literal_form_bit_for_bit(oracle_mod)
     rb, hb, sb = om.rm_fan_libm(poses, w.fov, B, step_coeff=1.0)
     assert np.array_equal(r, rb) and np.array_equal(h, hb) and np.array_equal(s_, sb)
     # the fused crash test in the literal arithmetic: Car::isCrashed (oracle._ref-pinned restatement) over the LITERAL ranges
-    edge = oracle_mod.edge_distances(B, -w.fov / 2, w.fov / B, 0.275, 0.2032, 0.3302)
+    edge = support.oracle_edge(oracle_mod, B, w.fov)
     assert m.check_collision_many(poses, w.fov, B, edge, 0.001) == oracle_mod.is_crashed(rb, B, len(poses), edge, 0.001)
     assert m.last_plan()["kernel"] == "rm_stream_literal" and m.last_plan()["crash"] == 1
 
@@ -410,7 +407,7 @@ def test_code_map_is_engaged_and_bit_identical(oracle_mod):
     past max_range only); a map whose palette does not fit falls back to the float32 map."""
     from pyracecarsimulator_amd import racecar as RC
     B, fov = 1081, 4.71
-    edge = RC.edge_distances(B, -fov / 2.0, fov / B, 0.275, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
+    edge = support.edge(B, fov)
     cases = [("maze400", maps.make_maze(400, cell=40, wall=3, p=0.45, seed=21, origin=(-7.0, 3.0, -0.4)), 300),
              ("colombia", maps.load_colombia(), 300),
              ("maze700_r120", maps.make_maze(700, cell=64, wall=2, p=0.5, seed=4), 120)]
@@ -511,7 +508,7 @@ def test_upstream_literal_mode_in_production_shape(oracle_mod):
     omap = range_libc.PyOMap(g)
     om = oracle_mod.OracleMap.from_gridmap(g, mrx)
     all_poses = workloads.make_poses(w, dt=om.dt)
-    edge = RC.edge_distances(B, -w.fov / 2.0, w.fov / B, 0.275, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
+    edge = support.edge(B, w.fov)
     for cls, sc in ((range_libc.PyRayMarchingGPU, 1.0), (range_libc.PyRayMarching, 0.999)):
         m = cls(omap, mrx)
         m.set_option("variant", 3)
@@ -776,7 +773,7 @@ def test_fused_crash_test_matches_is_crashed(oracle_mod):
     om = oracle_mod.OracleMap.from_gridmap(g, mrx)
     omap = range_libc.PyOMap(g)
     m = range_libc.PyRayMarchingGPU(omap, mrx)
-    edge = oracle_mod.edge_distances(B, -fov / 2, fov / B, 0.275, 0.2032, 0.3302)
+    edge = support.oracle_edge(oracle_mod, B, fov)
     rng = np.random.default_rng(8)
     seen = set()
     for trial in range(12):
@@ -1305,7 +1302,7 @@ def test_cfg4_colombia_rollout_shard_properties(oracle_mod):
     m.calc_range_fan(poses[half:], b, w.fov, B)
     assert np.array_equal(out[:half * B], a) and np.array_equal(out[half * B:], b)
     # fused crash test: whole block == isCrashed over the ranges, and per 200-pose roll-out
-    edge = oracle_mod.edge_distances(B, -w.fov / 2, w.fov / B, 0.275, 0.2032, 0.3302)
+    edge = support.oracle_edge(oracle_mod, B, w.fov)
     code = m.check_collision_many(poses, w.fov, B, edge, 0.001)
     assert code == oracle_mod.is_crashed(out, B, len(poses), edge, 0.001)
     n_ro = 640
@@ -1398,7 +1395,7 @@ def test_rollout_check_chain_equals_staged_oracle(oracle_mod):
     states[:, 3] = rng.uniform(0, 3, R)
     actions = np.stack([rng.uniform(0, 7, (R, 20)), rng.uniform(-0.4189, 0.4189, (R, 20))], -1)
     cars = RC.CarBatch()
-    edge = RC.edge_distances(B, -fov / 2, fov / B, 0.275, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
+    edge = support.edge(B, fov)
     first, final, vel = cars.rollout_check(m, states, actions, fov, B, edge, 0.001)
     poses, final2, vel2 = cars.rollout(states, actions)
     assert np.array_equal(final, final2) and np.array_equal(vel, vel2)
@@ -1429,7 +1426,7 @@ def test_grouped_crash_device_api_fused_and_generic(oracle_mod):
     omap = range_libc.PyOMap(g)
     poses = np.concatenate([maps.sample_free_poses(g, 200, 12, 9.0, om.dt),      # far from walls
                             maps.sample_free_poses(g, 200, 13, 2.0, om.dt)])     # some too close
-    edge = RC.edge_distances(B, -fov / 2, fov / B, 0.275, 0.2032, 0.3302)
+    edge = support.edge(B, fov)
     want_r, _, _ = om.rm_fan(poses, fov, B, step_coeff=1.0, nthreads=8)
     want = [oracle_mod.is_crashed(want_r[k * group * B:(k + 1) * group * B], B, group, edge, 0.001)
             for k in range(8)]
@@ -1506,9 +1503,6 @@ def test_racecar_simulator_facade_drives_like_the_reference(oracle_mod):
     """RacecarSimulator (scripts/racecar_simulator_v2.py) end to end: drive/updatePose against the
     reference's compiled Car (oracle/_ref, when present) and runScan/checkCollision[Many] against the
     oracle scan + isCrashed."""
-    import ctypes as C
-    import os
-    from conftest import ROOT
     from pyracecarsimulator_amd import RacecarSimulator, racecar as RC
     g = maps.load_colombia()
     cfg = _ref_config()
@@ -1523,32 +1517,23 @@ def test_racecar_simulator_facade_drives_like_the_reference(oracle_mod):
     st[:3] = start
     sim.setState(st)
     ref = None
-    so = os.path.join(ROOT, "oracle/_ref/libracecar_ref.so")
-    if os.path.exists(so):
-        L = C.CDLL(so)
-        L.ref_car_create.restype = C.c_void_p
-        L.ref_car_create.argtypes = [C.POINTER(C.c_double)]
-        L.ref_car_control.argtypes = [C.c_void_p, C.c_double, C.c_double]
-        L.ref_car_update_position.argtypes = [C.c_void_p, C.c_double]
-        L.ref_car_get_state.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-        L.ref_car_set_state.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-        ref = L.ref_car_create((C.c_double * 17)(*[cfg[k] for k in RC.CAR_PARAM_ORDER]))
-        L.ref_car_set_state(ref, (C.c_double * 11)(*st))
-    edge = oracle_mod.edge_distances(1080, -4.71 / 2, 4.71 / 1080, 0.275, cfg["width"], cfg["wb"])
+    if reference.available():
+        ref = reference.RefCar([cfg[k] for k in RC.CAR_PARAM_ORDER])
+        ref.set_state(st)
+    edge = support.oracle_edge(oracle_mod, 1080)
     for i in range(30):
         sim.drive(2.0 + 0.1 * i, 0.3 * math.sin(i / 3.0))
         sim.updatePose()
         if ref is not None:
-            L.ref_car_control(ref, 2.0 + 0.1 * i, 0.3 * math.sin(i / 3.0))
-            L.ref_car_update_position(ref, 0.01)
-            buf = (C.c_double * 11)()
-            L.ref_car_get_state(ref, buf)
-            assert np.allclose(sim.getState(), np.array(buf), rtol=1e-9, atol=1e-9)
+            want_state = ref.step(None, 2.0 + 0.1 * i, 0.3 * math.sin(i / 3.0))
+            assert np.allclose(sim.getState(), want_state, rtol=1e-9, atol=1e-9)
         sim.runScan()
         pose = np.array([sim.getScanPose()], np.float32)
         want, _, _ = om.rm_fan(pose, 4.71, 1080, step_coeff=1.0)
         assert np.array_equal(sim.getScan(), want)
         assert sim.checkCollision() == oracle_mod.is_crashed(want, 1080, 1, edge, cfg["ttc_thresh"])
+    if ref is not None:
+        ref.close()
     assert sim.getTravelDistance() > 0 and sim.getMeanVelocity() > 0
     poses = maps.sample_free_poses(g, 45, 5, 2.0, om.dt)
     want, _, _ = om.rm_fan(poses[:40], 4.71, 1080, step_coeff=1.0)
@@ -1598,7 +1583,7 @@ def test_followgap_batches_equal_the_oracle(oracle_mod, size):
     scans[5, 3:9] = np.nan
     scans[6, :] = 0.0
     scans[8, -1], scans[8, :-1] = 5.0, 1.0                       # gap = the single last beam
-    fg = PyFollowGap(10, 15.0, 0.4189, 0.004)
+    fg = support.followgap()
     got = fg.eval_many(scans)
     want = np.array([oracle_mod.followgap_eval(scans[i], 15.0, 0.4189, 0.004) for i in range(n)], np.float32)
     same = (got.view(np.uint32) == want.view(np.uint32)) | (np.isnan(got) & np.isnan(want))
@@ -1628,7 +1613,7 @@ def test_followgap_batches_equal_the_oracle(oracle_mod, size):
         s2[k] = v
     # (a steering limit nothing reaches: every `best` beam gives its own angle)
     for blk in (s2, scans):
-        got2 = PyFollowGap(10, 15.0, 1.0e6, 0.004).eval_many(blk)
+        got2 = support.followgap(max_angle=1.0e6).eval_many(blk)
         want2 = np.array([oracle_mod.followgap_eval(blk[i], 15.0, 1.0e6, 0.004) for i in range(len(blk))], np.float32)
         same2 = (got2.view(np.uint32) == want2.view(np.uint32)) | (np.isnan(got2) & np.isnan(want2))
         assert same2.all(), np.where(~same2)[0][:10]
@@ -1649,7 +1634,7 @@ def test_followgap_consumes_a_scanned_batch_on_the_device(oracle_mod):
     om = oracle_mod.OracleMap.from_gridmap(g, 300)
     poses = maps.sample_free_poses(g, 300, 11, dt=om.dt)
     m = range_libc.PyRayMarchingGPU(omap, 300)
-    fg = PyFollowGap(10, 15.0, 0.4189, 0.004)
+    fg = support.followgap()
     d_poses = torch.from_numpy(poses).cuda()
     d_out = torch.empty(len(poses) * 1081, dtype=torch.float32, device="cuda")
     d_ang = torch.empty(len(poses), dtype=torch.float32, device="cuda")
@@ -1672,7 +1657,7 @@ def test_small_host_calls_zero_copy_equals_staged_path(oracle_mod):
     omap = range_libc.PyOMap(g)
     om = oracle_mod.OracleMap.from_gridmap(g, 300)
     poses = maps.sample_free_poses(g, 50, 21, dt=om.dt)
-    edge = RC.edge_distances(1081, -4.71 / 2, 4.71 / 1081, 0.275, 0.2032, 0.3302)
+    edge = support.edge(1081)
     for cls, args in ((range_libc.PyRayMarchingGPU, ()), (range_libc.PyRayMarching, ()),
                       (range_libc.PyBresenhamsLine, ()), (range_libc.PyCDDTCast, (108,))):
         m = cls(omap, 300, *args)
@@ -1732,7 +1717,7 @@ def test_pinned_result_vectors_are_written_directly(oracle_mod):
     w2 = om.rm_fan(p2, 4.71, 1081, step_coeff=1.0, nthreads=oracle_mod.max_threads())[0]
     sim.scan_method.calc_range_fan(p2, big, 4.71, 1081)
     assert np.array_equal(big, w2)
-    edge = oracle_mod.edge_distances(1081, -4.71 / 2, 4.71 / 1081, 0.275, 0.2032, 0.3302)
+    edge = support.oracle_edge(oracle_mod, 1081)
     big[:] = 0
     code = sim.scan_method.check_collision_many(p2, 4.71, 1081, edge, 0.001, ranges=big)
     assert code == oracle_mod.is_crashed(w2, 1081, 2000, edge, 0.001) and np.array_equal(big, w2)
@@ -1885,7 +1870,7 @@ def test_fused_crash_marks_poses_then_reduces(oracle_mod, n, slots):
     omap = range_libc.PyOMap(g)
     poses = maps.sample_free_poses(g, n, 31, dt=om.dt)
     B, fov = 360, 4.71
-    edge = RC.edge_distances(B, -fov / 2, fov / B, 0.275, 0.2032, 0.3302) + 0.25      # wide car: many crashes
+    edge = support.edge(B, fov) + 0.25      # wide car: many crashes
     r0, _, _ = om.rm_fan(poses, fov, B, step_coeff=1.0, nthreads=4)
     m = range_libc.PyRayMarchingGPU(omap, 300)
     m.set_option("slots", slots)
@@ -1979,7 +1964,7 @@ def test_speculating_drain_loop_on_long_chains_bit_equal_to_oracle(oracle_mod, c
     m.set_option("drain_cap", 64)
     m.set_option("drain_stretch", 8)
     # ... and with the fused crash test riding along (two rays per lane keeps it)
-    edge = oracle_mod.edge_distances(B, -fov / 2, fov / B, 0.275, 0.2032, 0.3302)
+    edge = support.oracle_edge(oracle_mod, B, fov)
     m.set_option("slots", 2)
     m.set_option("spec_drain", 8)
     m.set_option("grid_mult", 8)

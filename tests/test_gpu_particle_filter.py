@@ -4,76 +4,20 @@ fan (the pin to the oracle) and against the oracle / tests/pf_statement.py on ar
 the statement's ascending product bit for bit, fused against unfused, noise keyed by the global ray id, the
 device-pointer forms, and every error of the contract."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 
 import pf_statement as PS
-from conftest import load_golden
-from pyracecarsimulator_amd import _lib, maps, range_libc
+import pf_cases as PF
+from pf_cases import MAPS, WEIGHT_KINDS as KINDS, WeightWorld as World
+from support import same_bits
+from pyracecarsimulator_amd import _lib, range_libc
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
 f32 = np.float32
 RL_ERR_INVALID, RL_ERR_UNSUPPORTED = -1, -4           # include/scanlib.h rl_status
-THETA = 112
-#: name -> (class, extra constructor arguments, variant or None, step coefficient, arithmetic)
-KINDS = {
-    "RM-3": (range_libc.PyRayMarching, (), 3, 0.999, "literal"),
-    "RM-1": (range_libc.PyRayMarching, (), 1, 0.999, "canonical"),
-    "RMGPU-1": (range_libc.PyRayMarchingGPU, (), 1, 1.0, "canonical"),
-    "RMGPU-3": (range_libc.PyRayMarchingGPU, (), 3, 1.0, "literal"),
-    "CDDT": (range_libc.PyCDDTCast, (THETA,), None, None, "cddt"),
-    "GLT": (range_libc.PyGiantLUTCast, (THETA,), None, None, "lut"),
-}
-MAPS = ("rm_maze256", "rm_maze192_yaw")              # yaw 0 / yawed origin
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
-
-
-class World:
-    """One fixture map: the device map, the oracle map, 257 free poses, and the handles made on it."""
-
-    def __init__(self, oracle_mod, name):
-        self.name = name
-        self.g, z = load_golden(name)
-        self.fov, self.mrx = float(z["fov"]), int(z["max_range_px"])
-        self.om = oracle_mod.OracleMap.from_gridmap(self.g, self.mrx)
-        self.omap = range_libc.PyOMap(self.g)
-        self.poses = np.ascontiguousarray(maps.sample_free_poses(self.g, 257, 31, 2.0, self.om.dt), f32)
-        self.inv_res = PS.inv_res_of(self.g.resolution)
-        self.methods, self.expected = {}, {}
-
-    def method(self, kind):
-        if kind not in self.methods:
-            cls, extra, variant, _, _ = KINDS[kind]
-            m = cls(self.omap, self.mrx, *extra)
-            if variant is not None:
-                m.set_option("variant", variant)
-            self.methods[kind] = m
-        return self.methods[kind]
-
-    def expect(self, kind, poses, angles, key):
-        """Ranges of the repeat-angle scan by the oracle / the statement; computed once per (arithmetic, shape)."""
-        _, _, _, coeff, form = KINDS[kind]
-        key = (form, coeff, key)
-        if key not in self.expected:
-            rows = PS.expand_rows(poses, angles)
-            if form == "literal":
-                want = self.om.rm_rays_libm(rows, step_coeff=coeff)
-            elif form == "canonical":
-                want = PS.repeat_angles(self.g.occ, self.g.resolution, self.g.origin, self.mrx, poses, angles,
-                                        step_coeff=coeff, dt=self.om.dt)[0]
-            elif form == "cddt":
-                want = self.om.cddt_rays(THETA, rows)
-            else:
-                want = self.om.lut_rays(self.method(kind).table(), rows)
-            self.expected[key] = want
-        return self.expected[key]
 
 
 @pytest.fixture(scope="module")
@@ -87,44 +31,8 @@ def worlds(oracle_mod):
     return get
 
 
-def _same_bits(a, b):
-    return np.asarray(a).tobytes() == np.asarray(b).tobytes()
-
-
 def _fan_equivalent(kind, fov, B):
     return PS.fan_angles_literal(fov, B) if KINDS[kind][4] == "literal" else PS.fan_angles(fov, B)
-
-
-def _wild_angles(A, seed):
-    """Non-monotone, with duplicates, with values beyond +-pi."""
-    rng = np.random.default_rng(seed)
-    a = rng.uniform(-4.0 * math.pi, 4.0 * math.pi, A).astype(f32)
-    if A >= 8:
-        a[A // 2] = a[1]
-        a[A - 1] = a[0]
-        a[2], a[3] = f32(7.5), f32(-9.25)
-        a[5] = f32(0.0)
-    return a
-
-
-def _scan(m, poses, angles, aux=False):
-    n = poses.shape[0] * angles.size
-    outs = np.full(n, -7.0, f32)
-    if not aux:
-        m.calc_range_repeat_angles(poses, angles, outs)
-        return outs
-    hits, steps = np.full((n, 2), -9, np.int32), np.full(n, 9, np.uint16)
-    m.calc_range_repeat_angles(poses, angles, outs, hits, steps)
-    return outs, hits, steps
-
-
-def _obs_of(w, A, seed):
-    """An observed scan: plausible ranges with a few values off the table's ends."""
-    rng = np.random.default_rng(seed)
-    obs = rng.uniform(0.0, w.mrx * w.g.resolution, A).astype(f32)
-    if A >= 8:
-        obs[0], obs[3], obs[6] = f32(-1.0), f32(1e6), f32(np.nan)
-    return obs
 
 
 # ---------------------------------------------------------------- 1. fan equivalence
@@ -143,13 +51,13 @@ def test_repeat_angles_of_the_fans_own_angles_equal_the_fan(worlds, kind, name):
             if aux:
                 want_h, want_s = np.empty((P * B, 2), np.int32), np.empty(P * B, np.uint16)
                 m.calc_range_fan(poses, want, w.fov, B, want_h, want_s)
-                got, got_h, got_s = _scan(m, poses, angles, aux=True)
+                got, got_h, got_s = PF.scan(m, poses, angles, aux=True)
                 assert np.array_equal(got_h, want_h) and np.array_equal(got_s, want_s), (kind, name, B, P)
                 some_hit |= bool((got_h[:, 0] >= 0).any())
             else:
                 m.calc_range_fan(poses, want, w.fov, B)
-                got = _scan(m, poses, angles)
-            assert _same_bits(got, want), (kind, name, B, P, np.abs(got - want).max())
+                got = PF.scan(m, poses, angles)
+            assert same_bits(got, want), (kind, name, B, P, np.abs(got - want).max())
     assert some_hit or not aux
 
 
@@ -164,11 +72,11 @@ def test_arbitrary_angles_equal_the_oracle(worlds, kind):
         w = worlds(name)
         m = w.method(kind)
         for A, P in SHAPES:
-            angles = _wild_angles(A, 100 + A)
+            angles = PF.wild_angles(A, 100 + A)
             poses = np.ascontiguousarray(w.poses[:P])
             want = w.expect(kind, poses, angles, (A, P))
-            got = _scan(m, poses, angles)
-            assert _same_bits(got, want), (kind, name, A, P, int((got != want).sum()))
+            got = PF.scan(m, poses, angles)
+            assert same_bits(got, want), (kind, name, A, P, int((got != want).sum()))
             assert np.unique(got).size > min(A * P, 4) // 2
 
 
@@ -180,31 +88,13 @@ def test_out_of_map_and_huge_heading_particles(worlds):
     poses[1, :2] += f32(3.0 * span)
     poses[4, 2] = f32(1234.5)
     poses[6, 0] -= f32(2.0 * span)
-    angles = _wild_angles(65, 5)
+    angles = PF.wild_angles(65, 5)
     for kind in ("RM-3", "RMGPU-1"):
-        got = _scan(w.method(kind), poses, angles)
-        assert _same_bits(got, w.expect(kind, poses, angles, "outside")), kind
+        got = PF.scan(w.method(kind), poses, angles)
+        assert same_bits(got, w.expect(kind, poses, angles, "outside")), kind
 
 
 # ---------------------------------------------------------------- 3. eval_sensor_model
-def _planted_ranges(w, m, A, P, seed, poses=None):
-    """Ranges of a real scan (of ``poses``, else the world's first P) with planted values: negative, NaN, above the
-    table, on and next to bin edges."""
-    angles = _wild_angles(A, seed)
-    r = _scan(m, np.ascontiguousarray(w.poses[:P] if poses is None else poses[:P]), angles).copy()
-    rng = np.random.default_rng(seed)
-    res = f32(w.g.resolution)
-    for v in (f32(-0.3), f32(np.nan), f32(1e5), f32(np.inf), f32(-np.inf), f32(-0.0)):
-        r[rng.integers(0, r.size, 5)] = v
-    k = rng.integers(1, 60, 40).astype(f32)
-    edges = (k * res).astype(f32)
-    idx = rng.choice(r.size, 120, replace=False)
-    r[idx[:40]] = edges
-    r[idx[40:80]] = np.nextafter(edges, f32(0), dtype=f32)
-    r[idx[80:]] = np.nextafter(edges, f32(1e9), dtype=f32)
-    return r
-
-
 def test_eval_sensor_model_equals_the_statement(worlds):
     w = worlds(MAPS[0])
     m = w.method("RMGPU-1")
@@ -216,13 +106,13 @@ def test_eval_sensor_model_equals_the_statement(worlds):
             for (A, P), block in [((54, 257), 0), ((54, 257), 38), ((54, 257), 5), ((65, 7), 0), ((130, 257), 0),
                                   ((1, 257), 0), ((2048, 2), 0), ((2048, 2), 2)]:
                 m.set_option("pf_block", block)
-                ranges = _planted_ranges(w, m, A, P, 7 * A + P)
-                obs = _obs_of(w, A, A)
+                ranges = PF.planted_ranges(w, m, A, P, 7 * A + P)
+                obs = PF.obs_of(w, A, A)
                 got = np.full(P, -1.0)
                 m.eval_sensor_model(obs, ranges, got, A, P)
                 fac = PS.factors(table, obs, ranges, w.inv_res)
                 want = PS.product_ascending(fac)
-                assert _same_bits(got, want), (width, A, P, block, int((got != want).sum()))
+                assert same_bits(got, want), (width, A, P, block, int((got != want).sum()))
                 assert np.isfinite(got).all() and (got > 0).all()
                 if (A, P) == (54, 257):
                     differs = max(differs, int((want != PS.product_tree(fac)).sum()))
@@ -232,19 +122,6 @@ def test_eval_sensor_model_equals_the_statement(worlds):
 
 
 # ---------------------------------------------------------------- 4. the fused call
-def _fused(m, poses, angles, obs):
-    wts = np.full(poses.shape[0], -1.0)
-    m.calc_range_repeat_angles_eval_sensor_model(poses, angles, obs, wts)
-    return wts
-
-
-def _unfused(m, poses, angles, obs):
-    ranges = _scan(m, poses, angles)
-    wts = np.full(poses.shape[0], -1.0)
-    m.eval_sensor_model(obs, ranges, wts, angles.size, poses.shape[0])
-    return ranges, wts
-
-
 @pytest.mark.parametrize("name", MAPS)
 @pytest.mark.parametrize("kind", sorted(KINDS))
 def test_fused_equals_unfused_equals_the_statement(worlds, kind, name):
@@ -259,25 +136,25 @@ def test_fused_equals_unfused_equals_the_statement(worlds, kind, name):
             for (A, P), block in [((54, 257), 0), ((54, 257), 38), ((54, 257), 5), ((65, 7), 0), ((130, 40), 0),
                                   ((1, 257), 0), ((2048, 2), 0)]:
                 m.set_option("pf_block", block)
-                angles = _wild_angles(A, 300 + A)
+                angles = PF.wild_angles(A, 300 + A)
                 poses = np.ascontiguousarray(w.poses[:P])
-                obs = _obs_of(w, A, 3 * A)
-                ranges, unfused = _unfused(m, poses, angles, obs)
-                fused = _fused(m, poses, angles, obs)
-                assert _same_bits(fused, unfused), (kind, name, noise, A, P, block, int((fused != unfused).sum()))
-                assert _same_bits(fused, PS.weights(table, obs, ranges, w.inv_res)), (kind, name, noise, A, P, block)
+                obs = PF.obs_of(w, A, 3 * A)
+                ranges, unfused = PF.unfused(m, poses, angles, obs)
+                fused = PF.fused(m, poses, angles, obs)
+                assert same_bits(fused, unfused), (kind, name, noise, A, P, block, int((fused != unfused).sum()))
+                assert same_bits(fused, PS.weights(table, obs, ranges, w.inv_res)), (kind, name, noise, A, P, block)
                 if not noise and (name == MAPS[0] or KINDS[kind][4] in ("literal", "canonical")):
-                    assert _same_bits(ranges, w.expect(kind, poses, angles, ("fused", A, P)))
+                    assert same_bits(ranges, w.expect(kind, poses, angles, ("fused", A, P)))
             if noise:
                 # the ray ids: with the fan's own angles the noisy ranges are the noisy fan's
                 B, P = 65, 7
                 poses = np.ascontiguousarray(w.poses[:P])
                 want = np.empty(P * B, f32)
                 m.calc_range_fan(poses, want, w.fov, B)
-                got = _scan(m, poses, _fan_equivalent(kind, w.fov, B))
-                assert _same_bits(got, want), (kind, name)
+                got = PF.scan(m, poses, _fan_equivalent(kind, w.fov, B))
+                assert same_bits(got, want), (kind, name)
                 m.set_noise(0.0)
-                clean = _scan(m, poses, _fan_equivalent(kind, w.fov, B))
+                clean = PF.scan(m, poses, _fan_equivalent(kind, w.fov, B))
                 assert (clean != got).mean() > 0.9
     finally:
         m.set_noise(0.0)
@@ -295,10 +172,10 @@ def test_device_pointer_forms_equal_the_host_forms(worlds, kind):
     m.set_sensor_model(table)
     m.set_noise(0.01, seed=5, ray_offset=999)
     try:
-        angles, obs = _wild_angles(A, 41), _obs_of(w, A, 42)
+        angles, obs = PF.wild_angles(A, 41), PF.obs_of(w, A, 42)
         poses = np.ascontiguousarray(w.poses[:P])
-        ranges, unfused = _unfused(m, poses, angles, obs)
-        fused = _fused(m, poses, angles, obs)
+        ranges, unfused = PF.unfused(m, poses, angles, obs)
+        fused = PF.fused(m, poses, angles, obs)
         before = {k: m.get_info(k) for k in ("variant", "pf_block", "slots", "timing", "grid_mult")}
         plan_before = m.last_plan()
         dev = torch.device("cuda:0")
@@ -315,15 +192,15 @@ def test_device_pointer_forms_equal_the_host_forms(worlds, kind):
                 m.calc_range_repeat_angles_eval_sensor_model_device(d_poses.data_ptr(), P, d_ang.data_ptr(), d_obs.data_ptr(),
                                                                     A, d_w[k].data_ptr(), stream=s.cuda_stream)
         s.synchronize()
-        assert _same_bits(d_r.cpu().numpy(), ranges)
-        assert _same_bits(d_w[0].cpu().numpy(), unfused)
-        assert _same_bits(d_w[1].cpu().numpy(), fused) and _same_bits(d_w[2].cpu().numpy(), fused)
-        assert _same_bits(fused, unfused)
+        assert same_bits(d_r.cpu().numpy(), ranges)
+        assert same_bits(d_w[0].cpu().numpy(), unfused)
+        assert same_bits(d_w[1].cpu().numpy(), fused) and same_bits(d_w[2].cpu().numpy(), fused)
+        assert same_bits(fused, unfused)
         # options and the noise offset read the same afterwards: the host forms give the same bits again
         assert {k: m.get_info(k) for k in before} == before
         assert m.last_plan() == plan_before
-        assert _same_bits(_fused(m, poses, angles, obs), fused)
-        assert _same_bits(_scan(m, poses, angles), ranges)
+        assert same_bits(PF.fused(m, poses, angles, obs), fused)
+        assert same_bits(PF.scan(m, poses, angles), ranges)
     finally:
         m.set_noise(0.0)
 
@@ -335,7 +212,7 @@ def test_every_error_of_the_contract_and_a_correct_call_afterwards(worlds):
     m = range_libc.PyRayMarchingGPU(w.omap, w.mrx)          # a fresh handle: no table set yet
     A, P = 54, 7
     poses = np.ascontiguousarray(w.poses[:P])
-    angles, obs = _wild_angles(A, 1), _obs_of(w, A, 2)
+    angles, obs = PF.wild_angles(A, 1), PF.obs_of(w, A, 2)
     outs, wts = np.zeros(P * A, f32), np.zeros(P)
     table = PS.witness_table(64)
     p_ins, p_ang, p_obs = poses.ctypes.data_as(_lib.f32p), angles.ctypes.data_as(_lib.f32p), obs.ctypes.data_as(_lib.f32p)
@@ -398,10 +275,10 @@ def test_every_error_of_the_contract_and_a_correct_call_afterwards(worlds):
     rep = mm.replica(1)                                       # ... whose replicas are ordinary handles
     rep.set_sensor_model(table)
     # a correct call on the same handle afterwards succeeds, with the right answer
-    good = _fused(m, poses, angles, obs)
-    ranges = _scan(m, poses, angles)
-    assert _same_bits(good, PS.weights(table, obs, ranges, w.inv_res))
-    assert _same_bits(_fused(rep, poses, angles, obs), good)
+    good = PF.fused(m, poses, angles, obs)
+    ranges = PF.scan(m, poses, angles)
+    assert same_bits(good, PS.weights(table, obs, ranges, w.inv_res))
+    assert same_bits(PF.fused(rep, poses, angles, obs), good)
     with pytest.raises(_lib.ScanLibError) as e:
         m.calc_range_repeat_angles(poses, np.zeros(2049, f32), np.zeros(P * 2049, f32))
     assert e.value.code == RL_ERR_INVALID

@@ -10,27 +10,22 @@ import pytest
 
 import mcl_statement as MS
 import pf_statement as PS
-import test_gpu_mcl as TM
-import test_gpu_particle_filter as TP
+import pf_cases as PF
+from support import same_bits
 from pyracecarsimulator_amd import ParticleFilter, maps
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
 f32 = np.float32
-KINDS = sorted(TM.KINDS)                     # RM-3 literal, RMGPU-1 canonical, CDDT, GLT
+KINDS = sorted(PF.MCL_KINDS)                     # RM-3 literal, RMGPU-1 canonical, CDDT, GLT
 MARCH = ("RM-3", "RMGPU-1")
-MAPS = TM.MAPS
-STD = TM.STD
+MAPS = PF.MAPS
+STD = PF.STD
 WG, TILE_RAYS, CHUNK = 256, 2048, MS.CHUNK   # pf_kernels.h PF_WG, PF_TILE_RAYS; the contract's chunk
 NOISE = dict(seed=77, ray_offset=123457)
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
-
-
-class Weights(TP.World):
+class Weights(PF.WeightWorld):
     """The weight tests' world: as many free poses as a shape asks for, drawn once per P."""
 
     def poses_of(self, P):
@@ -49,7 +44,7 @@ def pf_worlds(oracle_mod):
 @pytest.fixture(scope="module")
 def mcl_worlds(oracle_mod):
     cache = {}
-    return lambda name: cache[name] if name in cache else cache.setdefault(name, TM.World(oracle_mod, name))
+    return lambda name: cache[name] if name in cache else cache.setdefault(name, PF.MclWorld(oracle_mod, name))
 
 
 def _lds_bytes(block, A):
@@ -103,20 +98,20 @@ def test_later_tiles_of_the_fused_call(pf_worlds, kind):
                 _assert_later_tiles(n_cu, block, P)
                 m.set_option("pf_block", block)
                 assert m.get_info("pf_block") == block == _tile_block(n_cu, P, A, block)
-                angles, obs, poses = TP._wild_angles(A, 300 + A), TP._obs_of(w, A, 3 * A), w.poses_of(P)
-                fused = TP._fused(m, poses, angles, obs)
+                angles, obs, poses = PF.wild_angles(A, 300 + A), PF.obs_of(w, A, 3 * A), w.poses_of(P)
+                fused = PF.fused(m, poses, angles, obs)
                 want = PS.weights(table, obs, w.expect(kind, poses, angles, ("scale", A, P)), w.inv_res)
                 bad = np.nonzero(fused != want)[0]
-                assert TP._same_bits(fused, want), (kind, name, block, P, bad.size, bad[:4], bad[:4] // block)
+                assert same_bits(fused, want), (kind, name, block, P, bad.size, bad[:4], bad[:4] // block)
                 assert np.unique(fused).size > P // 4
                 # scan noise is keyed by the global ray id: (p0 + p) A + j of a later tile is the plain scan's p A + j
                 m.set_noise(0.02, **NOISE)
-                ranges, unfused = TP._unfused(m, poses, angles, obs)
-                fused = TP._fused(m, poses, angles, obs)
+                ranges, unfused = PF.unfused(m, poses, angles, obs)
+                fused = PF.fused(m, poses, angles, obs)
                 m.set_noise(0.0)
                 bad = np.nonzero(fused != unfused)[0]
-                assert TP._same_bits(fused, unfused), (kind, name, block, P, "noise", bad.size, bad[:4], bad[:4] // block)
-                assert TP._same_bits(fused, PS.weights(table, obs, ranges, w.inv_res)), (kind, name, block, P, "noise")
+                assert same_bits(fused, unfused), (kind, name, block, P, "noise", bad.size, bad[:4], bad[:4] // block)
+                assert same_bits(fused, PS.weights(table, obs, ranges, w.inv_res)), (kind, name, block, P, "noise")
                 assert (ranges != w.expect(kind, poses, angles, ("scale", A, P))).mean() > 0.9
         finally:
             m.set_noise(0.0)
@@ -133,14 +128,14 @@ def test_later_tiles_of_eval_sensor_model(pf_worlds):
         for block, A, P in _later_tile_shapes(n_cu):
             _assert_later_tiles(n_cu, block, P)
             m.set_option("pf_block", block)
-            ranges = TP._planted_ranges(w, m, A, P, 7 * A + P, poses=w.poses_of(P))
+            ranges = PF.planted_ranges(w, m, A, P, 7 * A + P, poses=w.poses_of(P))
             assert ranges.size == P * A
-            obs = TP._obs_of(w, A, A)
+            obs = PF.obs_of(w, A, A)
             got = np.full(P, -1.0)
             m.eval_sensor_model(obs, ranges, got, A, P)
             want = PS.weights(table, obs, ranges, w.inv_res)
             bad = np.nonzero(got != want)[0]
-            assert TP._same_bits(got, want), (block, P, bad.size, bad[:4], bad[:4] // block)
+            assert same_bits(got, want), (block, P, bad.size, bad[:4], bad[:4] // block)
             assert np.isfinite(got).all() and (got > 0).all()
     finally:
         m.set_option("pf_block", 0)
@@ -162,11 +157,11 @@ def test_production_tile_sizes(pf_worlds, kind):
         assert P > 4 * n_cu and -(-P // (4 * n_cu)) > WG // A            # the spread, not the floor, sizes the tile
         assert _tile_block(n_cu, P, A) == block
         assert P % block != 0                                            # (a short last tile)
-        angles, obs, poses = TP._wild_angles(A, 300 + A), TP._obs_of(w, A, 3 * A), w.poses_of(P)
-        fused = TP._fused(m, poses, angles, obs)
+        angles, obs, poses = PF.wild_angles(A, 300 + A), PF.obs_of(w, A, 3 * A), w.poses_of(P)
+        fused = PF.fused(m, poses, angles, obs)
         want = PS.weights(table, obs, w.expect(kind, poses, angles, ("scale", A, P)), w.inv_res)
         bad = np.nonzero(fused != want)[0]
-        assert TP._same_bits(fused, want), (kind, P, block, bad.size, bad[:4], bad[:4] // block)
+        assert same_bits(fused, want), (kind, P, block, bad.size, bad[:4], bad[:4] // block)
 
 
 # ---------------------------------------------------------------- A3. the scan's second grid-stride round
@@ -177,20 +172,20 @@ def test_second_round_of_the_repeat_angle_scan(pf_worlds, kind):
     n_cu = m.get_info("n_cu")
     A, P = 2048, 2 * n_cu + 9
     assert P * A > 16 * n_cu * WG, "the scan's grid covers every ray in one round on this part"
-    angles, poses = TP._wild_angles(A, 100 + A), w.poses_of(P)
+    angles, poses = PF.wild_angles(A, 100 + A), w.poses_of(P)
     if kind == "RMGPU-1":                                   # the AUX instantiation: hit cells and step counts too
         want, want_h, want_s = PS.repeat_angles(w.g.occ, w.g.resolution, w.g.origin, w.mrx, poses, angles,
                                                 step_coeff=1.0, dt=w.om.dt)
-        got, got_h, got_s = TP._scan(m, poses, angles, aux=True)
+        got, got_h, got_s = PF.scan(m, poses, angles, aux=True)
         assert np.array_equal(got_h, want_h), int((got_h != want_h).any(1).sum())
         assert np.array_equal(got_s, want_s), int((got_s != want_s).sum())
         assert (got_h[16 * n_cu * WG:, 0] >= 0).any()
-        assert TP._same_bits(got, want)
+        assert same_bits(got, want)
     else:
         want = w.expect(kind, poses, angles, ("scale", A, P))
-    got = TP._scan(m, poses, angles)
+    got = PF.scan(m, poses, angles)
     bad = np.nonzero(got != want)[0]
-    assert TP._same_bits(got, want), (kind, bad.size, bad[:4])
+    assert same_bits(got, want), (kind, bad.size, bad[:4])
     assert np.unique(got[16 * n_cu * WG:]).size > 100
 
 
@@ -201,7 +196,7 @@ def test_tile_shrinks_to_the_lds_cap(pf_worlds):
     w = pf_worlds(MAPS[0])
     A, P = 2048, 5
     table = PS.witness_table(301, seed=5)
-    angles, obs, poses = TP._wild_angles(A, 300 + A), TP._obs_of(w, A, 3 * A), w.poses_of(P)
+    angles, obs, poses = PF.wild_angles(A, 300 + A), PF.obs_of(w, A, 3 * A), w.poses_of(P)
     for kind in MARCH:
         m = w.method(kind)
         n_cu = m.get_info("n_cu")
@@ -210,14 +205,14 @@ def test_tile_shrinks_to_the_lds_cap(pf_worlds):
             for forced in (4, 256):
                 assert _lds_bytes(3, A) > 65536 >= _lds_bytes(2, A) and _tile_block(n_cu, P, A, forced) == 2
                 m.set_option("pf_block", forced)
-                fused = TP._fused(m, poses, angles, obs)
+                fused = PF.fused(m, poses, angles, obs)
                 want = PS.weights(table, obs, w.expect(kind, poses, angles, ("scale", A, P)), w.inv_res)
-                assert TP._same_bits(fused, want), (kind, forced, np.nonzero(fused != want)[0])
-                ranges = TP._planted_ranges(w, m, A, P, 7 * A + P, poses=poses)
+                assert same_bits(fused, want), (kind, forced, np.nonzero(fused != want)[0])
+                ranges = PF.planted_ranges(w, m, A, P, 7 * A + P, poses=poses)
                 got = np.full(P, -1.0)
                 m.eval_sensor_model(obs, ranges, got, A, P)
                 want = PS.weights(table, obs, ranges, w.inv_res)
-                assert TP._same_bits(got, want), (kind, forced, "eval", np.nonzero(got != want)[0])
+                assert same_bits(got, want), (kind, forced, "eval", np.nonzero(got != want)[0])
         finally:
             m.set_option("pf_block", 0)
 
@@ -262,11 +257,11 @@ def test_localisation_rows_equal_the_statement(mcl_worlds, P, A, T, kind, ratios
     for name in (_maps_of(kind) if P == 2500 else MAPS[:1]):
         w = mcl_worlds(name)
         for ratio in ratios:
-            pf, out, st, want = TM._both(w, kind, P, A, ratio, n_steps=T)
+            pf, out, st, want = PF.both(w, kind, P, A, ratio, n_steps=T)
             what = (kind, name, P, A, ratio)
-            if not TM._same(pf.read()["cum"], st.cum) or not TM._same(out[1], want[1]):
+            if not same_bits(pf.read()["cum"], st.cum) or not same_bits(out[1], want[1]):
                 print(what, _first_difference(pf, st))
-            TM._assert_equal_to_statement(pf, out, st, want, what)
+            PF.assert_equal_to_statement(pf, out, st, want, what)
             if name == MAPS[0]:
                 assert out[2].tolist() == MS.scale_flags(A, T, ratio), (what, out[1])
             if ratio == 2.0:
@@ -274,7 +269,7 @@ def test_localisation_rows_equal_the_statement(mcl_worlds, P, A, T, kind, ratios
                 n = np.bincount(pf.read()["ancestors"], minlength=P)
                 assert (n == 0).mean() >= dead and n.max() >= most, (what, (n == 0).mean(), n.max())
             if ratio == 0.0:
-                assert not out[2].any() and TM._same(pf.read()["ancestors"], np.arange(P, dtype=np.int32))
+                assert not out[2].any() and same_bits(pf.read()["ancestors"], np.arange(P, dtype=np.int32))
             pf.close()
 
 
@@ -296,10 +291,10 @@ def test_run_two_equals_run_one_twice_at_scale(mcl_worlds):
     assert (n == 0).mean() >= 0.25 and n.max() >= 3
     rest = b.run_raw(odom[1:], obs[1:])
     for x, y, z in zip(whole, first, rest):
-        assert TM._same(x, np.concatenate([y, z]))
+        assert same_bits(x, np.concatenate([y, z]))
     assert whole[2].tolist() == MS.scale_flags(A, 2, 0.5)
     ra, rb = a.read(), b.read()
-    assert all(TM._same(ra[k], rb[k]) for k in ra)
+    assert all(same_bits(ra[k], rb[k]) for k in ra)
     a.close()
     b.close()
 
@@ -310,20 +305,20 @@ def _small(w, ratio, table, weights=None):
     P, A = 600, 7
     tb = table(w.case(P, A)[4])
     with np.errstate(over="ignore", invalid="ignore"):
-        return TM._both(w, "RMGPU-1", P, A, ratio, weights=weights, table=tb)
+        return PF.both(w, "RMGPU-1", P, A, ratio, weights=weights, table=tb)
 
 
 def test_infinite_total_is_degenerate(mcl_worlds):
     w = mcl_worlds(MAPS[0])
     P = 600
     pf, out, st, want = _small(w, 0.0, MS.overflow_table, weights=np.full(P, 1e308))
-    TM._assert_equal_to_statement(pf, out, st, want, "W = +inf")
+    PF.assert_equal_to_statement(pf, out, st, want, "W = +inf")
     assert out[2].tolist() == [MS.DEGENERATE, 0, 0]
     # step 0 alone: omega overflows, the weights are reset to 1 / P
     pf.reset(w.case(P, 7)[0], weights=np.full(P, 1e308), seed=3)
     _, neff, flags = pf.run_raw(w.case(P, 7)[2][:1], w.case(P, 7)[3][:1])
     rd = pf.read()
-    assert flags[0] == MS.DEGENERATE and TM._same(rd["weights"], np.full(P, 1.0 / P))
+    assert flags[0] == MS.DEGENERATE and same_bits(rd["weights"], np.full(P, 1.0 / P))
     with np.errstate(over="ignore"):
         assert np.isinf(1e308 * rd["likelihood"]).any() and abs(neff[0] - P) < 1e-6
     pf.close()
@@ -334,18 +329,18 @@ def test_nan_total_is_degenerate(mcl_worlds):
     P = 600
     for ratio, flag in ((0.0, MS.DEGENERATE), (2.0, MS.DEGENERATE | MS.RESAMPLED)):
         pf, out, st, want = _small(w, ratio, MS.nan_table)
-        TM._assert_equal_to_statement(pf, out, st, want, ("W = NaN", ratio))
+        PF.assert_equal_to_statement(pf, out, st, want, ("W = NaN", ratio))
         assert (out[2] == flag).all()
         assert np.isfinite(out[0]).all() and np.isfinite(out[1]).all()
         rd = pf.read()
-        assert 0.05 < np.isnan(rd["likelihood"]).mean() < 0.5 and TM._same(rd["weights"], np.full(P, 1.0 / P))
+        assert 0.05 < np.isnan(rd["likelihood"]).mean() < 0.5 and same_bits(rd["weights"], np.full(P, 1.0 / P))
         pf.close()
 
 
 def test_zero_weight_plateaus(mcl_worlds):
     w = mcl_worlds(MAPS[0])
     pf, out, st, want = _small(w, 2.0, MS.plateau_table)
-    TM._assert_equal_to_statement(pf, out, st, want, "plateaus")
+    PF.assert_equal_to_statement(pf, out, st, want, "plateaus")
     rd = pf.read()
     assert (rd["likelihood"] == 0).mean() >= 0.5 and (np.diff(rd["cum"]) == 0).mean() >= 0.5
     assert (out[2] == MS.RESAMPLED).all()

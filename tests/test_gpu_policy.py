@@ -10,19 +10,16 @@ import pytest
 
 from conftest import GOLD
 import policy_statement as S
-from test_gpu_drive import _edge, _ref_libs, _same_bits, _starts
+import support
+from oracle import reference
+from support import D_BASE, FOV, THRESH, same_bits
 from pyracecarsimulator_amd import Policy, RacecarSimulator, _lib, maps, range_libc
 from pyracecarsimulator_amd import racecar as RC
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
-FOV, B, THRESH, D_BASE = 4.71, 1081, 0.001, 0.275
+B = 1081
 CLIP = 0.4189                                            # scripts/policy_driver.py:33
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
 
 
 @pytest.fixture(scope="module")
@@ -47,7 +44,7 @@ def _same_or_nan(a, b):
     """bit-equal where finite, NaN at the same places (the trace rows a car never reaches are all-ones NaNs)."""
     a, b = np.asarray(a), np.asarray(b)
     na, nb = np.isnan(a), np.isnan(b)
-    return a.shape == b.shape and (na == nb).all() and _same_bits(a[~na], b[~nb])
+    return a.shape == b.shape and (na == nb).all() and same_bits(a[~na], b[~nb])
 
 
 def _rows_to_check(R, rng):
@@ -64,7 +61,7 @@ def test_predict_many_equals_statement_fixture(net, R):
     got = pol.predict_many(scans)
     rows = _rows_to_check(R, np.random.default_rng(R))
     want = S.forward(scans[rows], layers, relu)
-    assert _same_bits(got[rows], want)
+    assert same_bits(got[rows], want)
     assert np.isfinite(got).all()
 
 
@@ -85,7 +82,7 @@ def test_predict_many_equals_statement_random_chains(dims, in_start, size, relu)
         scans = _hard_scans(R, size, R + size)
         got = pol.predict_many(scans)
         want = S.forward(scans, layers, relu, in_start=in_start, clip=12.5, scale=7.0)
-        assert _same_bits(got, want), (dims, R)
+        assert same_bits(got, want), (dims, R)
 
 
 def test_device_and_single_forms(net):
@@ -98,11 +95,11 @@ def test_device_and_single_forms(net):
     d_out = torch.full((R,), float("nan"), dtype=torch.float32, device="cuda:0")
     pol.predict_device(d_in.data_ptr(), R, B, d_out.data_ptr())
     torch.cuda.synchronize()
-    assert _same_bits(d_out.cpu().numpy(), host)
+    assert same_bits(d_out.cpu().numpy(), host)
     one = pol.predict_action(scans[123])
     assert isinstance(one, np.float32) and one.tobytes() == host[123].tobytes()
     # a flat (n * size,) batch as scanMany returns it
-    assert _same_bits(pol.predict_many(scans.reshape(-1), B), host)
+    assert same_bits(pol.predict_many(scans.reshape(-1), B), host)
 
 
 def test_create_caps_and_errors(net):
@@ -125,7 +122,7 @@ def test_create_caps_and_errors(net):
             pol.predict_many(np.ascontiguousarray(scans[:, :size]))
     assert L.rl_policy_eval(pol._h, None, 4, B, None) != 0
     assert pol.predict_many(scans[:0]).shape == (0,)
-    assert _same_bits(pol.predict_many(scans), want)
+    assert same_bits(pol.predict_many(scans), want)
 
 
 # ---------------------------------------------------------------- closed loop
@@ -153,8 +150,7 @@ def _composed(cars, m, std, base, layers, relu, states, speeds, steer0, T, edge,
                                  action_every=1)
         cur[idx] = out
         st[idx, t] = out
-        x, y, th = out[:, 0], out[:, 1], out[:, 2]
-        last_pose[idx] = np.stack([x + D_BASE * np.cos(th), y + D_BASE * np.sin(th), th], -1).astype(np.float32)
+        last_pose[idx] = support.lidar_poses(out)
         ranges = np.empty(R * B, np.float32)
         m.set_noise(std, 99, base + t * R * B)
         m.calc_range_fan(last_pose, ranges, FOV, B)
@@ -181,11 +177,11 @@ def test_drive_policy_equals_composed_public_calls(net):
     omap = range_libc.PyOMap(g)
     dt = omap.distance_transform()
     R, T = 48, 25
-    far, sp_far = _starts(g, dt, R - 8, 31, 8.0)
-    near, sp_near = _starts(g, dt, 8, 32, 1.0)
+    far, sp_far = support.starts(g, dt, R - 8, 31, 8.0)
+    near, sp_near = support.starts(g, dt, 8, 32, 1.0)
     states, speeds = np.concatenate([far, near]), np.concatenate([sp_far, sp_near])
     steer0 = np.random.default_rng(7).uniform(-0.3, 0.3, R).astype(np.float32)
-    edge = _edge()
+    edge = support.edge(B)
     cars = RC.CarBatch()
     n_clipped = 0
     for name, m, std in _methods(omap, mrx):
@@ -198,7 +194,7 @@ def test_drive_policy_equals_composed_public_calls(net):
             m.set_noise(0.0, 0, 0)
             assert (first >= 0).any() and (first < 0).any(), name
             assert (first == want[0]).all(), (name, clip)
-            assert _same_bits(final, want[1]), (name, clip)
+            assert same_bits(final, want[1]), (name, clip)
             assert _same_or_nan(steers, want[2]), (name, clip)
             assert _same_or_nan(st, want[3]), (name, clip)
             assert _same_or_nan(vel, st[..., 3]), (name, clip)
@@ -210,31 +206,23 @@ def test_drive_policy_steps_match_reference_car(net):
     """Colombia, RMGPU, 16 cars x 60 ticks, clipped: every step, fed the GPU's own state of the tick before and the
     clamped network output, agrees with the reference's compiled Car (as test_gpu_drive pins FollowGap's loop)."""
     layers, relu, pol = net
-    L, _ = _ref_libs()
+    reference.require()
     g = maps.load_colombia()
     omap = range_libc.PyOMap(g)
     dt = omap.distance_transform()
     m = range_libc.PyRayMarchingGPU(omap, 300)
     R, T = 16, 60
-    states, speeds = _starts(g, dt, R, 4, 6.0, speed_hi=4.0)
-    edge = _edge()
+    states, speeds = support.starts(g, dt, R, 4, 6.0, speed_hi=4.0)
+    edge = support.edge(B)
     first, final, vel, steers, sp, st = RC.CarBatch().drive_policy(m, pol, states, T, speeds, FOV, B, edge, THRESH,
                                                                     steer_clip=CLIP, trace=True)
-    ref = L.ref_car_create((C.c_double * 17)(*[RC.DEFAULT_CAR[k] for k in RC.CAR_PARAM_ORDER]))
-    buf = (C.c_double * 11)()
-    try:
+    with reference.RefCar() as ref:
         for r in range(R):
             last = first[r] if first[r] >= 0 else T - 1
             for t in range(last + 1):
                 prev = states[r] if t == 0 else st[r, t - 1]
                 s_in = 0.0 if t == 0 else float(np.clip(np.float64(steers[r, t - 1]), -CLIP, CLIP))
-                L.ref_car_set_state(ref, (C.c_double * 11)(*prev))
-                L.ref_car_control(ref, float(speeds[r]), s_in)
-                L.ref_car_update_position(ref, 0.01)
-                L.ref_car_get_state(ref, buf)
-                assert np.allclose(st[r, t], np.array(buf), rtol=1e-9, atol=1e-9), (r, t)
-    finally:
-        L.ref_car_destroy(ref)
+                assert np.allclose(st[r, t], ref.step(prev, speeds[r], s_in), rtol=1e-9, atol=1e-9), (r, t)
 
 
 def test_drive_policy_chunking_is_invariant(net):
@@ -245,8 +233,8 @@ def test_drive_policy_chunking_is_invariant(net):
     dt = omap.distance_transform()
     m = range_libc.PyRayMarchingGPU(omap, 300)
     R, T, H = 64, 60, 30
-    states, speeds = _starts(g, dt, R, 8, 3.0)
-    edge = _edge()
+    states, speeds = support.starts(g, dt, R, 8, 3.0)
+    edge = support.edge(B)
     cars = RC.CarBatch()
     base = 12345
     for clip in (None, CLIP):
@@ -261,15 +249,15 @@ def test_drive_policy_chunking_is_invariant(net):
         m.set_noise(0.0, 0, 0)
         assert ok.any()
         for k in range(2, 6):
-            assert _same_bits(whole[k][:, :H], a[k]), (clip, k)
+            assert same_bits(whole[k][:, :H], a[k]), (clip, k)
         # steer0 is f32: with the clip on, the chained call equals the whole one for the cars whose last output
         # the clamp leaves alone (a clamped one would get the f32 bound, not the f64 one)
         raw = a[3][:, -1].astype(np.float64)
         exact = ok if not clip else ok & (np.abs(raw) <= clip)
         assert exact.any()
-        assert _same_bits(whole[1][exact], b[1][exact]), clip
+        assert same_bits(whole[1][exact], b[1][exact]), clip
         for k in range(2, 6):
-            assert _same_bits(whole[k][exact, H:], b[k][exact]), (clip, k)
+            assert same_bits(whole[k][exact, H:], b[k][exact]), (clip, k)
         want_first = np.where(b[0][exact] >= 0, b[0][exact] + H, -(T + 1))
         assert (whole[0][exact] == want_first).all(), clip
 
@@ -282,19 +270,19 @@ def test_drive_policy_facade_and_errors(net):
     m = range_libc.PyRayMarchingGPU(omap, 300)
     cars = RC.CarBatch()
     R, T = 8, 10
-    states, speeds = _starts(g, dt, R, 2, 8.0)
-    edge = _edge()
+    states, speeds = support.starts(g, dt, R, 2, 8.0)
+    edge = support.edge(B)
     m.set_option("nt_store", 1)
     drive0 = cars.drive_policy(m, pol, states, T, speeds, FOV, B, edge, THRESH)
     scans = _hard_scans(4, B, 1)
     p0 = pol.predict_many(scans)
 
     def still_usable():
-        assert _same_bits(pol.predict_many(scans), p0)
+        assert same_bits(pol.predict_many(scans), p0)
         assert m.get_info("nt_store") == 1
         again = cars.drive_policy(m, pol, states, T, speeds, FOV, B, edge, THRESH)
         for x, y in zip(drive0, again):
-            assert _same_bits(x, y)
+            assert same_bits(x, y)
 
     Lb = _lib.lib()
     f64p = _lib.f64p
@@ -316,7 +304,7 @@ def test_drive_policy_facade_and_errors(net):
     # scans too short for the window [180, 900): 720 beams (cfg5's fans need in_start 0), 899
     for nr in (720, 899):
         with pytest.raises(_lib.ScanLibError, match="window"):
-            cars.drive_policy(m, pol, states, T, speeds, FOV, nr, _edge(nr), THRESH)
+            cars.drive_policy(m, pol, states, T, speeds, FOV, nr, support.edge(nr), THRESH)
         still_usable()
     multi = RC.CarBatch(device=[0])
     with pytest.raises(_lib.ScanLibError, match="single-device"):
@@ -334,7 +322,7 @@ def test_drive_policy_facade_and_errors(net):
     still_usable()
     # in_start 0 on cfg5-sized 720-beam fans drives
     pol720 = Policy.from_arrays(layers, relu, in_start=0)
-    f720 = cars.drive_policy(m, pol720, states, 3, speeds, FOV, 720, _edge(720), THRESH)
+    f720 = cars.drive_policy(m, pol720, states, 3, speeds, FOV, 720, support.edge(720), THRESH)
     assert f720[3].shape == (R, 3)
     # the façade: RacecarSimulator.drivePolicyMany is CarBatch.drive_policy on the simulator's method and edge table
     cfg = dict(RC.DEFAULT_CAR)
@@ -348,4 +336,4 @@ def test_drive_policy_facade_and_errors(net):
                                 sim.edge_distances, sim.ttc_thresh, scan_dist_to_base=sim.scan_dist_to_base,
                                 steer_clip=CLIP)
     for x, y in zip(got, want):
-        assert _same_bits(x, y)
+        assert same_bits(x, y)

@@ -8,65 +8,17 @@ import numpy as np
 import pytest
 
 import race_statement as RS
+import support
+from drive_cases import RACE_MRX as MRX, race_clusters, race_maze, race_oracle_fan
+from support import D_BASE, FOV, MAX_STEER, THRESH, same_bits
 from pyracecarsimulator_amd import RacecarSimulator, _lib, maps, range_libc
 from pyracecarsimulator_amd import racecar as RC
-from pyracecarsimulator_amd.followgap import PyFollowGap
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
-FOV, B, THRESH, D_BASE = 4.71, 1081, 0.001, 0.275
+B = 1081
 L, W = RC.DEFAULT_CAR["length"], RC.DEFAULT_CAR["width"]
-MAX_STEER = RC.DEFAULT_CAR["max_steer_ang"]
-MRX = 300
 RL_ERR_INVALID, RL_ERR_UNSUPPORTED = -1, -4           # include/scanlib.h rl_status
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _gpu(need_gpu):
-    yield
-
-
-def _same_bits(a, b):
-    return np.asarray(a).tobytes() == np.asarray(b).tobytes()
-
-
-def _edge(num_rays=B):
-    return RC.edge_distances(num_rays, -FOV / 2, FOV / num_rays, D_BASE, W, RC.DEFAULT_CAR["wb"])
-
-
-def _lidar(cars):
-    cars = np.asarray(cars, np.float64).reshape(-1, 3)
-    return np.stack([cars[:, 0] + D_BASE * np.cos(cars[:, 2]), cars[:, 1] + D_BASE * np.sin(cars[:, 2]),
-                     cars[:, 2]], -1).astype(np.float32)
-
-
-def _clusters(g, dt, n_groups, group, seed, spread=1.2):
-    """n_groups races of `group` cars each within `spread` m of a free race centre (they occlude each other)."""
-    rng = np.random.default_rng(seed)
-    centres = maps.sample_free_poses(g, n_groups, seed, 12.0, dt).astype(np.float64)
-    cars = np.repeat(centres, group, 0)
-    cars[:, :2] += rng.uniform(-spread, spread, (n_groups * group, 2))
-    cars[:, 2] = rng.uniform(-math.pi, math.pi, n_groups * group)
-    return cars
-
-
-def _maze():
-    return maps.make_maze(256, cell=40, wall=3, p=0.45, seed=5)
-
-
-def _oracle_fan(oracle_mod, g, cells, group, poses, num_rays, literal, step_coeff):
-    """Per pose: the oracle scan on the grid with the other cars of its group stamped."""
-    n = poses.shape[0]
-    r_all, h_all, s_all = [], [], []
-    for p in range(n):
-        occ = RS.stamped(g.occ, RS.others(cells, group, p))
-        om = oracle_mod.OracleMap(occ, g.resolution, g.origin, MRX)
-        if literal:
-            r, h, s = om.rm_fan_libm(poses[p:p + 1], FOV, num_rays, step_coeff=step_coeff)
-        else:
-            r, h, s = om.rm_fan(poses[p:p + 1], FOV, num_rays, step_coeff=step_coeff)
-        r_all.append(r); h_all.append(h); s_all.append(s)
-    return np.concatenate(r_all), np.concatenate(h_all), np.concatenate(s_all)
 
 
 def test_outline_cells_equal_the_statement(oracle_mod):
@@ -74,7 +26,7 @@ def test_outline_cells_equal_the_statement(oracle_mod):
     cars_h = RC.CarBatch()
     rng = np.random.default_rng(1)
     col = maps.load_colombia()
-    yawed = _maze()
+    yawed = race_maze()
     yawed = maps.GridMap(yawed.occ, yawed.resolution, (3.1, -2.7, 0.61), "yawed")
     for g, n in ((col, 6000), (yawed, 4000)):
         omap = range_libc.PyOMap(g)
@@ -95,7 +47,7 @@ def test_outline_cells_equal_the_statement(oracle_mod):
 
 @pytest.mark.parametrize("kind,variant", [("RM", 3), ("RM", 1), ("RMGPU", 1)])
 def test_fan_cars_equal_the_oracle_on_the_stamped_grid(oracle_mod, kind, variant):
-    g = _maze()
+    g = race_maze()
     dt = oracle_mod.edt(g.occ)
     omap = range_libc.PyOMap(g)
     m = (range_libc.PyRayMarching if kind == "RM" else range_libc.PyRayMarchingGPU)(omap, MRX)
@@ -104,21 +56,21 @@ def test_fan_cars_equal_the_oracle_on_the_stamped_grid(oracle_mod, kind, variant
     nb = 360
     n_changed = 0
     for group, n_groups, seed in ((1, 3, 11), (2, 4, 12), (4, 3, 13), (8, 2, 14)):
-        cars = _clusters(g, dt, n_groups, group, seed)
-        poses = _lidar(cars)
+        cars = race_clusters(g, dt, n_groups, group, seed)
+        poses = support.lidar_poses(cars)
         N = poses.shape[0]
         hits = np.empty((N * nb, 2), np.int32)
         steps = np.empty(N * nb, np.uint16)
         outs = m.calc_range_fan_cars(poses, cars, group, FOV, nb, hit_cells=hits, steps=steps)
         cells = RS.outline_cells(cars, L, W, g.resolution, g.origin, g.rows, g.cols, oracle_mod.sincosf)
-        want_r, want_h, want_s = _oracle_fan(oracle_mod, g, cells, group, poses, nb, variant == 3, coeff)
-        assert _same_bits(outs, want_r), (group, kind, variant)
-        assert _same_bits(hits, want_h.reshape(-1, 2)), (group, kind, variant)
-        assert _same_bits(steps, want_s), (group, kind, variant)
+        want_r, want_h, want_s = race_oracle_fan(oracle_mod, g, cells, group, poses, nb, variant == 3, coeff)
+        assert same_bits(outs, want_r), (group, kind, variant)
+        assert same_bits(hits, want_h.reshape(-1, 2)), (group, kind, variant)
+        assert same_bits(steps, want_s), (group, kind, variant)
         plain = np.empty(N * nb, np.float32)
         m.calc_range_fan(poses, plain, FOV, nb)
         if group == 1:
-            assert _same_bits(outs, plain)
+            assert same_bits(outs, plain)
         else:
             n_changed += int((outs != plain).sum())
     assert n_changed > 100
@@ -128,7 +80,7 @@ def test_fan_cars_equal_the_oracle_on_the_stamped_grid(oracle_mod, kind, variant
 def test_fan_cars_with_noise_equal_a_stamped_map(oracle_mod, kind):
     """Noise on: each pose's race scan equals the same handle's ordinary scan of a second map with the other cars laid
     by PyOMap.stamp_cells (the noise at the same global ray id); group 1 equals calc_range_fan."""
-    g = _maze()
+    g = race_maze()
     dt = oracle_mod.edt(g.occ)
     cls = range_libc.PyRayMarching if kind == "RM" else range_libc.PyRayMarchingGPU
     m = cls(range_libc.PyOMap(g), MRX)
@@ -137,8 +89,8 @@ def test_fan_cars_with_noise_equal_a_stamped_map(oracle_mod, kind):
     base = 777 * B
     m.set_noise(0.05, 9, base)
     group, n_groups = 4, 3
-    cars = _clusters(g, dt, n_groups, group, 31)
-    poses = _lidar(cars)
+    cars = race_clusters(g, dt, n_groups, group, 31)
+    poses = support.lidar_poses(cars)
     outs = m.calc_range_fan_cars(poses, cars, group, FOV, B)
     cells = RS.outline_cells(cars, L, W, g.resolution, g.origin, g.rows, g.cols, oracle_mod.sincosf)
     for p in range(poses.shape[0]):
@@ -146,15 +98,15 @@ def test_fan_cars_with_noise_equal_a_stamped_map(oracle_mod, kind):
         m2.set_noise(0.05, 9, base + p * B)
         one = np.empty(B, np.float32)
         m2.calc_range_fan(poses[p:p + 1], one, FOV, B)
-        assert _same_bits(outs[p * B:(p + 1) * B], one), p
+        assert same_bits(outs[p * B:(p + 1) * B], one), p
     outs1 = m.calc_range_fan_cars(poses, cars, 1, FOV, B)
     plain = np.empty(poses.shape[0] * B, np.float32)
     m.calc_range_fan(poses, plain, FOV, B)
-    assert _same_bits(outs1, plain)
+    assert same_bits(outs1, plain)
 
 
 def _race_starts(g, dt, n_races, group, seed, spread=0.9):
-    cars = _clusters(g, dt, n_races, group, seed, spread)
+    cars = race_clusters(g, dt, n_races, group, seed, spread)
     rng = np.random.default_rng(seed)
     states = np.zeros((n_races * group, 11))
     states[:, :3] = cars
@@ -167,17 +119,17 @@ def test_race_of_one_equals_drive_followgap(oracle_mod):
     g = maps.load_colombia()
     dt = oracle_mod.edt(g.occ)
     m = range_libc.PyRayMarchingGPU(range_libc.PyOMap(g), MRX)
-    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    fg = support.followgap()
     states, speeds = _race_starts(g, dt, 48, 1, 41)
     steer0 = np.random.default_rng(2).uniform(-0.2, 0.2, (48, 1)).astype(np.float32)
     cars = RC.CarBatch()
     m.set_noise(0.03, 5, 1000)
-    race = cars.race_followgap(m, fg, states, 80, speeds, FOV, B, _edge(), THRESH, steer0=steer0, trace=True)
-    drive = cars.drive_followgap(m, fg, states[:, 0], 80, speeds[:, 0], FOV, B, _edge(), THRESH,
+    race = cars.race_followgap(m, fg, states, 80, speeds, FOV, B, support.edge(B), THRESH, steer0=steer0, trace=True)
+    drive = cars.drive_followgap(m, fg, states[:, 0], 80, speeds[:, 0], FOV, B, support.edge(B), THRESH,
                                  steer0=steer0[:, 0], trace=True)
     m.set_noise(0.0, 0, 0)
     for a, b in zip(race, drive):
-        assert _same_bits(a.reshape(b.shape), b)
+        assert same_bits(a.reshape(b.shape), b)
 
 
 @pytest.mark.parametrize("kind,group", [("RMGPU", 2), ("RM", 4)])
@@ -185,15 +137,15 @@ def test_race_teacher_forced_replay(oracle_mod, kind, group):
     """Every link of every tick of a race: the step (rollout of one step), the outline statement of the other cars at
     their states after that tick's step (wrecks at their crash-tick state), the oracle scan of the stamped grid, the
     crash test and FollowGap."""
-    g = _maze()
+    g = race_maze()
     dt = oracle_mod.edt(g.occ)
     m = (range_libc.PyRayMarching if kind == "RM" else range_libc.PyRayMarchingGPU)(range_libc.PyOMap(g), MRX)
     literal = kind == "RM"
     coeff = 0.999 if literal else 1.0
-    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    fg = support.followgap()
     n_races, T = 4, 50
     states, speeds = _race_starts(g, dt, n_races, group, 50 + group)
-    edge = _edge()
+    edge = support.edge(B)
     cars = RC.CarBatch()
     first, final, vel, steers, sp, st = cars.race_followgap(m, fg, states, T, speeds, FOV, B, edge, THRESH, trace=True)
     N = n_races * group
@@ -212,7 +164,7 @@ def test_race_teacher_forced_replay(oracle_mod, kind, group):
             prev = flat_states[n] if t == 0 else st[n, t - 1]
             steer_in = 0.0 if t == 0 else float(steers[n, t - 1])
             _, one, _ = cars.rollout(prev[None], np.array([[[flat_speeds[n], steer_in]]]), n_steps=1, action_every=1)
-            assert _same_bits(one[0], st[n, t]), (n, t)
+            assert same_bits(one[0], st[n, t]), (n, t)
             occ = RS.stamped(g.occ, RS.others(cells, group, n))
             om = oracle_mod.OracleMap(occ, g.resolution, g.origin, MRX)
             pose = sp[n, t:t + 1]
@@ -224,11 +176,11 @@ def test_race_teacher_forced_replay(oracle_mod, kind, group):
                 continue
             a = oracle_mod.followgap_eval(r, 15.0, MAX_STEER, 0.004)
             assert np.float32(a).tobytes() == steers[n, t].tobytes(), (n, t)
-    assert _same_bits(final, st[np.arange(N), last])
+    assert same_bits(final, st[np.arange(N), last])
 
 
 def _room_race(m, fg, states, speeds, T):
-    return RC.CarBatch().race_followgap(m, fg, states, T, speeds, FOV, B, _edge(), THRESH, trace=True)
+    return RC.CarBatch().race_followgap(m, fg, states, T, speeds, FOV, B, support.edge(B), THRESH, trace=True)
 
 
 def test_head_on_and_wreck():
@@ -236,7 +188,7 @@ def test_head_on_and_wreck():
     neither crashes alone.  A car driven into a wall stays a wreck that the car following it crashes into."""
     g = maps.make_room(200)
     m = range_libc.PyRayMarchingGPU(range_libc.PyOMap(g), MRX)
-    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    fg = support.followgap()
     T = 40
     s = np.zeros((1, 2, 11))
     s[0, 0, :4] = (4.4, 5.0, 0.0, 3.0)
@@ -256,19 +208,19 @@ def test_head_on_and_wreck():
     alone_b = _room_race(m, fg, s[:, 1:], sp[:, 1:], 60)[0]
     assert alone_b[0, 0] < 0 or alone_b[0, 0] > b, (alone_b, b)
     assert final[0, 1, 0] < final[0, 0, 0]             # B stopped behind A's wreck
-    assert _same_bits(final[0, 0], st[0, 0, a])        # the wreck stayed at its crash-tick state
+    assert same_bits(final[0, 0], st[0, 0, a])        # the wreck stayed at its crash-tick state
 
 
 def test_race_chunking_is_invariant(oracle_mod):
     """T ticks in one call == T/2 + T/2 with states, steers and the noise offset chained, for every race whose cars
     are all alive after the first half (a wreck would be stepped again by a second call)."""
-    g = _maze()
+    g = race_maze()
     dt = oracle_mod.edt(g.occ)
     m = range_libc.PyRayMarchingGPU(range_libc.PyOMap(g), MRX)
-    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    fg = support.followgap()
     n_races, P, T, H = 32, 2, 60, 30
     states, speeds = _race_starts(g, dt, n_races, P, 71, spread=1.5)
-    edge = _edge()
+    edge = support.edge(B)
     cars = RC.CarBatch()
     base = 4242
     m.set_noise(0.05, 3, base)
@@ -281,20 +233,20 @@ def test_race_chunking_is_invariant(oracle_mod):
     m.set_noise(0.0, 0, 0)
     assert ok.sum() >= 4
     for k in range(2, 6):
-        assert _same_bits(whole[k][:, :, :H], a[k]), k
-    assert _same_bits(whole[1][ok], b[1][ok])
+        assert same_bits(whole[k][:, :, :H], a[k]), k
+    assert same_bits(whole[1][ok], b[1][ok])
     for k in range(2, 6):
-        assert _same_bits(whole[k][ok][:, :, H:], b[k][ok]), k
+        assert same_bits(whole[k][ok][:, :, H:], b[k][ok]), k
     want_first = np.where(b[0][ok] >= 0, b[0][ok] + H, -(T + 1))
     assert (whole[0][ok] == want_first).all()
 
 
 def test_errors_leave_handles_usable(oracle_mod):
-    g = _maze()
+    g = race_maze()
     dt = oracle_mod.edt(g.occ)
     omap = range_libc.PyOMap(g)
-    cars = _clusters(g, dt, 2, 2, 3)
-    poses = _lidar(cars)
+    cars = race_clusters(g, dt, 2, 2, 3)
+    poses = support.lidar_poses(cars)
     for cls, args in ((range_libc.PyCDDTCast, (112,)), (range_libc.PyGiantLUTCast, (112,)),
                       (range_libc.PyBresenhamsLine, ())):
         h = cls(omap, MRX, *args)
@@ -317,21 +269,21 @@ def test_errors_leave_handles_usable(oracle_mod):
     assert e.value.code == RL_ERR_UNSUPPORTED
     # null pointers through the C ABI
     assert _lib.lib().rl_calc_range_fan_cars(m._h, None, None, 2, 2, L, W, FOV, 90, None, None, None) == RL_ERR_INVALID
-    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
+    fg = support.followgap()
     cb = RC.CarBatch()
     assert _lib.lib().rl_car_race_followgap(cb._h, m._h, fg._h, None, None, None, 2, 2, 10, 0.01, D_BASE, FOV, B,
                                             None, THRESH, None, None, None, None, None, None) == RL_ERR_INVALID
     st = np.zeros((2, 9, 11))
     with pytest.raises(_lib.ScanLibError):
-        cb.race_followgap(m, fg, st, 5, 1.0, FOV, B, _edge(), THRESH)
-    assert _same_bits(m.calc_range_fan_cars(poses, cars, 2, FOV, 90), want)
+        cb.race_followgap(m, fg, st, 5, 1.0, FOV, B, support.edge(B), THRESH)
+    assert same_bits(m.calc_range_fan_cars(poses, cars, 2, FOV, 90), want)
     assert cb.outline_cells(omap, cars)[1].shape == (4,)
 
 
 def test_facade_race_many(oracle_mod):
     """RacecarSimulator.raceFollowGapMany equals CarBatch.race_followgap on the façade's method, edge table and
-    FollowGap (PyFollowGap(10, 15.0, max_steer_ang, 0.004), as simple_driver.py builds it)."""
-    g = _maze()
+    FollowGap (support.followgap(), as simple_driver.py builds it)."""
+    g = race_maze()
     cfg = dict(RC.DEFAULT_CAR)
     cfg.update(scan_dist_to_base=D_BASE, batch_size=40, scan_beams=1080, scan_fov=FOV, scan_std=0.0,
                scan_max_range=15.0, free_thresh=0.8)
@@ -341,10 +293,10 @@ def test_facade_race_many(oracle_mod):
     sim.setRaytracingMethod("RMGPU")
     states, _ = _race_starts(g, oracle_mod.edt(g.occ), 6, 3, 91)
     got = sim.raceFollowGapMany(states, 30, speed=2.0)
-    fg = PyFollowGap(10, 15.0, cfg["max_steer_ang"], 0.004)
+    fg = support.followgap()
     want = RC.CarBatch().race_followgap(sim.scan_simulator.scan_method, fg, states, 30, 2.0, sim.scan_fov,
                                         sim.num_rays, sim.edge_distances, sim.ttc_thresh,
                                         scan_dist_to_base=sim.scan_dist_to_base)
     assert len(got) == 4
     for a, b in zip(got, want):
-        assert _same_bits(a, b)
+        assert same_bits(a, b)

@@ -540,9 +540,9 @@ def test_kernel_register_budgets_are_a_build_gate(tmp_path):
 
 
 def test_every_noise_call_site_has_a_gpu_case():
-    """tests/test_gpu_noise.py NOISE_SITES names the case that checks each gauss_noise( call against the reference
+    """tests/coverage_tables.py NOISE_SITES names the case that checks each gauss_noise( call against the reference
     generator: a kernel that adds noise anywhere else must add a row (and a case) there."""
-    from test_gpu_noise import NOISE_SITES
+    from coverage_tables import NOISE_SITES
     csrc = os.path.join(ROOT, "pyracecarsimulator_amd", "csrc")
     found = {}
     for name in sorted(os.listdir(csrc)):
@@ -562,9 +562,9 @@ def test_every_noise_call_site_has_a_gpu_case():
 
 
 def test_every_table_cache_guard_has_a_gpu_case():
-    """tests/test_gpu_map_mutation.py TABLE_CACHES names the case that checks each lazily rebuilt per-handle table
+    """tests/coverage_tables.py TABLE_CACHES names the case that checks each lazily rebuilt per-handle table
     (a ``*_epoch == <map>->epoch`` guard under csrc/) after a map mutation: a new cache must add a row (and a case)."""
-    from test_gpu_map_mutation import TABLE_CACHES
+    from coverage_tables import TABLE_CACHES
     csrc = os.path.join(ROOT, "pyracecarsimulator_amd", "csrc")
     guard = re.compile(r"\b(\w+_epoch)\s*==\s*(?:\w+->)?(?:m|map)->epoch\b")
     found = {}

@@ -1,16 +1,16 @@
 """CPU tests of the oracle itself: known answers, the independent NumPy statement, and the
 committed golden vectors.  PARITY UNPINNED upstream (range_libc absent) — these
 pins are the build's own."""
-import ctypes as C
 import math
 import os
 
 import numpy as np
 import pytest
 
-from conftest import GOLD, ROOT, load_golden
+from conftest import GOLD, load_golden
 from oracle import np_statement as N
 from oracle import oracle as O
+from oracle import reference
 from pyracecarsimulator_amd import maps
 
 
@@ -387,27 +387,22 @@ def test_edge_distances_and_is_crashed_vs_reference_build(oracle_mod):
     assert oracle_mod.is_crashed(far, 8, 3, edge, 0.001) == 1
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle/_ref/libracecar_ref.so")),
-                    reason="oracle/_ref not built")
+@pytest.mark.skipif(not os.path.exists(reference.CAR_SO), reason="oracle/_ref not built")
 def test_oracle_edge_table_equals_live_reference_build(oracle_mod):
-    L = C.CDLL(os.path.join(ROOT, "oracle/_ref/libracecar_ref.so"))
-    L.ref_car_create.restype = C.c_void_p
-    L.ref_car_create.argtypes = [C.POINTER(C.c_double)]
-    L.ref_car_set_edge_distances.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double]
-    L.ref_car_is_crashed.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int]
     z = np.load(os.path.join(GOLD, "car_ref.npz"))
-    car = L.ref_car_create((C.c_double * 17)(*z["car"]))
+    car = reference.RefCar(z["car"])
     B, fov = 1081, 4.71
-    L.ref_car_set_edge_distances(car, B, -fov / 2, fov / B, 0.275)
+    car.set_edge(B, fov, 0.275)
     edge = oracle_mod.edge_distances(B, -fov / 2, fov / B, 0.275, float(z["car"][10]), float(z["car"][0]))
     # probe the private table through isCrashed: a ray just under / over edge+thresh per beam
     thresh = float(z["car"][9])
     for j in range(0, B, 37):
         rays = np.full(B, 100.0, np.float32)
         rays[j] = np.float32(edge[j] + thresh) - np.float32(1e-3)
-        assert L.ref_car_is_crashed(car, rays.ctypes.data_as(C.POINTER(C.c_float)), B, 1) == 0
+        assert car.is_crashed(rays, B, 1) == 0
         rays[j] = np.float32(edge[j] + thresh) + np.float32(1e-3)
-        assert L.ref_car_is_crashed(car, rays.ctypes.data_as(C.POINTER(C.c_float)), B, 1) == -2
+        assert car.is_crashed(rays, B, 1) == -2
+    car.close()
 
 
 def test_random_maps_c_oracle_vs_numpy_statement(oracle_mod):
@@ -454,12 +449,8 @@ def test_followgap_restatement_equals_reference_build_vectors(oracle_mod):
     assert np.isnan(oracle_mod.followgap_eval(np.ones(9, np.float32), 15.0, 0.4, 0.004))   # size < 10
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle/_ref/libfollowgap_ref.so")),
-                    reason="oracle/_ref not built")
+@pytest.mark.skipif(not os.path.exists(reference.FOLLOWGAP_SO), reason="oracle/_ref not built")
 def test_followgap_restatement_equals_live_reference_build(oracle_mod):
-    L = C.CDLL(os.path.join(ROOT, "oracle/_ref/libfollowgap_ref.so"))
-    L.ref_followgap_eval.restype = C.c_float
-    L.ref_followgap_eval.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]
     rng = np.random.default_rng(5)
     n = 0
     for trial in range(300):
@@ -468,7 +459,7 @@ def test_followgap_restatement_equals_live_reference_build(oracle_mod):
         v[rng.random(size) < 0.1] = 0.0
         v[-1] = 0.5                       # keeps the chosen gap off the last beam (reference reads past the end there)
         md, ma, inc = 15.0, float(rng.choice([0.4189, 0.2])), float(rng.choice([0.004, 0.00436]))
-        ref = L.ref_followgap_eval(v.ctypes.data_as(C.POINTER(C.c_float)), size, 10, md, ma, inc)
+        ref = reference.followgap_eval(v, 10, md, ma, inc)
         got = oracle_mod.followgap_eval(v, md, ma, inc)
         assert np.float32(got).tobytes() == np.float32(ref).tobytes() or (np.isnan(got) and np.isnan(ref))
         n += 1

@@ -169,7 +169,7 @@ def _rand_layers(dims, seed=0):
              rng.standard_normal(dims[i + 1]).astype(np.float32)) for i in range(len(dims) - 1)]
 
 
-def _same(a, b):
+def _same_layers(a, b):
     return len(a) == len(b) and all(x[0].tobytes() == y[0].tobytes() and x[1].tobytes() == y[1].tobytes()
                                     and x[0].shape == y[0].shape for x, y in zip(a, b))
 
@@ -179,18 +179,18 @@ def test_reader_tensor_forms():
     layers[2] = (layers[2][0], np.full(1, 0.25, np.float32))
     forms = ["content", "packed", "unpacked", "content", "packed", "scalar"]
     got = read_frozen_graph(_graph(layers, forms))
-    assert _same(got, layers)
+    assert _same_layers(got, layers)
     assert got.relu == (True, True, False)
     # a single float_val broadcast over a whole weight matrix
     layers2 = [(np.full((4, 3), -1.5, np.float32), np.zeros(3, np.float32)), (np.ones((3, 1), np.float32), np.ones(1, np.float32))]
     got2 = read_frozen_graph(_graph(layers2, ["scalar", "scalar", "scalar", "scalar"]))
-    assert _same(got2, layers2)
+    assert _same_layers(got2, layers2)
 
 
 def test_reader_identity_chains_and_relu_pattern():
     layers = _rand_layers([9, 4, 6, 1], 4)
     got = read_frozen_graph(_graph(layers, identity=True, relu=[False, True, False]))
-    assert _same(got, layers) and got.relu == (False, True, False)
+    assert _same_layers(got, layers) and got.relu == (False, True, False)
 
 
 @pytest.mark.parametrize("case", ["tanh", "transpose_b", "half", "shape"])
@@ -223,7 +223,7 @@ def test_reader_reference_graphs_equal_fixture():
         path = os.path.join(REF_MODEL, fname)
         assert hashlib.sha256(open(path, "rb").read()).hexdigest() == str(z[key])
         got = read_frozen_graph(path)
-        assert _same(got, layers) and got.relu == relu
+        assert _same_layers(got, layers) and got.relu == relu
 
 
 def test_fixture_shape():

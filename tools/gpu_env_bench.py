@@ -18,7 +18,6 @@ of a K2-step and a K1-step run of one leg, differenced, so that set-up launches 
 import argparse
 import csv
 import glob
-import json
 import os
 import statistics
 import subprocess
@@ -28,22 +27,17 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bench_common import B, FOV, THRESH, free_starts, lidar_poses, world, write_rows  # noqa: E402
 
-FOV, B, THRESH, D_BASE, SPEED, GAIN, CLIP = 4.71, 1081, 0.001, 0.275, 2.0, 0.1, 0.4189
+SPEED, GAIN, CLIP = 2.0, 0.1, 0.4189
 MAX_TICKS, POOL = 200, 512
 
 
 def setup(N):
-    from pyracecarsimulator_amd import DriveEnv, maps, range_libc, racecar as RC
-    g = maps.load_colombia()
-    omap = range_libc.PyOMap(g)
-    m = range_libc.PyRayMarchingGPU(omap, 300)
-    cars = RC.CarBatch()
-    edge = RC.edge_distances(B, -FOV / 2, FOV / B, D_BASE, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
-    starts = np.zeros((POOL, 11))
-    starts[:, :3] = maps.sample_free_poses(g, POOL, 17, 6.0, omap.distance_transform())
+    from pyracecarsimulator_amd import DriveEnv
+    g, _, dt, m, _, cars, edge = world("colombia")
+    starts = free_starts(g, dt, POOL)
     env = DriveEnv(m, starts, N, B, FOV, edge, THRESH, max_ticks=MAX_TICKS, auto_reset=True, car=cars)
     return env, m, cars, edge, starts
 
@@ -77,9 +71,7 @@ class ComposedLeg:
         self.scan()
 
     def scan(self):
-        th = self.cur[:, 2]
-        poses = np.stack([self.cur[:, 0] + D_BASE * np.cos(th), self.cur[:, 1] + D_BASE * np.sin(th), th], -1)
-        self.m.calc_range_fan(poses.astype(np.float32), self.ranges, FOV, B)
+        self.m.calc_range_fan(lidar_poses(self.cur), self.ranges, FOV, B)
         return self.ranges.reshape(self.N, B)
 
     def run(self, steps):
@@ -181,8 +173,7 @@ def main():
         os.makedirs(a.out_dir, exist_ok=True)
         with open(os.path.join(a.out_dir, "gpu_env_bench.txt"), "w") as f:
             f.write("\n".join(lines) + "\n")
-        with open(os.path.join(a.out_dir, "gpu_env_bench.json"), "w") as f:
-            json.dump(dict(tool="tools/gpu_env_bench.py", rows=rows), f, indent=1)
+        write_rows(os.path.join(a.out_dir, "gpu_env_bench.json"), "tools/gpu_env_bench.py", rows)
 
 
 if __name__ == "__main__":

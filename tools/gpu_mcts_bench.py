@@ -10,22 +10,19 @@ L = 200 roll-out steps (mcts.py's roll_out_itr), n iterations after a reset:
             eval_many, is_crashed, rollout_check): two synchronous round trips per iteration (K = 1 and 64 only)
 Prints us per iteration and the ratios; --out writes the rows as JSON."""
 import argparse
-import json
 import os
 import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-from pyracecarsimulator_amd import maps, range_libc, workloads, racecar as RC  # noqa: E402
-from pyracecarsimulator_amd.followgap import PyFollowGap  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bench_common import B, FOV, THRESH, free_starts, lidar_poses, world, write_rows  # noqa: E402
+from pyracecarsimulator_amd import racecar as RC  # noqa: E402
 from pyracecarsimulator_amd.mcts import MCTSPlanner  # noqa: E402
 import mcts_statement as S  # noqa: E402
 
-FOV, B, THRESH, D_BASE, SPEED, L, EVERY = workloads.SCAN_FOV, 1081, 0.001, 0.275, 2.0, 200, 10
+SPEED, L, EVERY = 2.0, 200, 10
 MAX_STEER, MAX_SPEED = RC.DEFAULT_CAR["max_steer_ang"], RC.DEFAULT_CAR["max_speed"]
 
 
@@ -33,8 +30,7 @@ def composed(cars, m, fg, states, n_it, edge, seeds):
     """The search on the host: the statement's recursion, each act and roll-out one synchronous batched call."""
     K = len(states)
     n_act = (L + EVERY - 1) // EVERY
-    th = states[:, 2]
-    p0 = np.stack([states[:, 0] + D_BASE * np.cos(th), states[:, 1] + D_BASE * np.sin(th), th], -1).astype(np.float32)
+    p0 = lidar_poses(states)
     r0 = np.empty(K * B, np.float32)
     m.calc_range_fan(p0, r0, FOV, B)
     ans0 = fg.eval_many(r0, B)
@@ -44,8 +40,7 @@ def composed(cars, m, fg, states, n_it, edge, seeds):
     def act_many(i, reqs):
         st = np.stack([node.state for _, node, _ in reqs])
         _, out, _ = cars.rollout(st, np.array([[SPEED, a] for _, _, a in reqs])[:, None, :], n_steps=1, action_every=1)
-        t = out[:, 2]
-        poses = np.stack([out[:, 0] + D_BASE * np.cos(t), out[:, 1] + D_BASE * np.sin(t), t], -1).astype(np.float32)
+        poses = lidar_poses(out)
         ranges = np.empty(K * B, np.float32)
         m.calc_range_fan(poses, ranges, FOV, B)
         ranges = ranges.reshape(K, B)
@@ -73,17 +68,10 @@ def main():
     a = ap.parse_args()
     rows = []
     for mname in a.maps.split(","):
-        g = workloads.cfg2().gmap if mname == "cfg2" else maps.load_colombia()
-        omap = range_libc.PyOMap(g)
-        dt = omap.distance_transform()
-        m = range_libc.PyRayMarchingGPU(omap, workloads.MAX_RANGE_PX)
-        fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
-        cars = RC.CarBatch()
-        edge = RC.edge_distances(B, -FOV / 2, FOV / B, D_BASE, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
+        g, _, dt, m, fg, cars, edge = world(mname)
         for K in (int(s) for s in a.sizes.split(",")):
             n = a.iterations or (200 if K <= 64 else 20)
-            states = np.zeros((K, 11))
-            states[:, :3] = maps.sample_free_poses(g, K, 17, 6.0, dt)
+            states = free_starts(g, dt, K)
             seeds = np.arange(K, dtype=np.uint64)
             pl = MCTSPlanner(cars, m, K, 2 * n + 2, FOV, B, edge, THRESH, source="fg", followgap=fg)
             pl.reset(states, 0.0, seeds)
@@ -121,9 +109,7 @@ def main():
                                    if "composed_us_per_iteration" in row else "skipped"), flush=True)
             pl.close()
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(dict(tool="tools/gpu_mcts_bench.py", rows=rows), f, indent=1)
+        write_rows(a.out, "tools/gpu_mcts_bench.py", rows)
 
 
 if __name__ == "__main__":

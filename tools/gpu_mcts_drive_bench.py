@@ -10,21 +10,17 @@ colombia, RMGPU, 1081 beams, FG source, L = 200 roll-out steps, one car step per
   run       MCTSPlanner.run(I) alone after one reset: what a decision's search costs without its reset and step
 Prints ms per decision and the ratios; --out writes the rows as JSON."""
 import argparse
-import json
 import os
 import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from pyracecarsimulator_amd import maps, range_libc, workloads, racecar as RC  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bench_common import B, FOV, THRESH, free_starts, world, write_rows  # noqa: E402
 from pyracecarsimulator_amd import mcts as M  # noqa: E402
-from pyracecarsimulator_amd.followgap import PyFollowGap  # noqa: E402
 
-FOV, B, THRESH, D_BASE, SPEED, L, EVERY, CLIP = workloads.SCAN_FOV, 1081, 0.001, 0.275, 2.0, 200, 10, 0.4189
-MAX_STEER = RC.DEFAULT_CAR["max_steer_ang"]
+SPEED, L, EVERY, CLIP = 2.0, 200, 10, 0.4189
 
 
 def composed(cars, m, pl, states, recent, seeds, D, I, base):
@@ -51,17 +47,10 @@ def main():
     ap.add_argument("--decisions", type=int, default=0, help="decisions per timed run (0: 20 for K <= 64, 3 above)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    g = maps.load_colombia()
-    omap = range_libc.PyOMap(g)
-    dt = omap.distance_transform()
-    m = range_libc.PyRayMarchingGPU(omap, workloads.MAX_RANGE_PX)
-    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
-    cars = RC.CarBatch()
-    edge = RC.edge_distances(B, -FOV / 2, FOV / B, D_BASE, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
+    g, _, dt, m, fg, cars, edge = world("colombia")
     rows = []
     for K in (int(s) for s in a.sizes.split(",")):
-        states = np.zeros((K, 11))
-        states[:, :3] = maps.sample_free_poses(g, K, 17, 6.0, dt)
+        states = free_starts(g, dt, K)
         recent, seeds = np.zeros(K), np.arange(K, dtype=np.uint64)
         for I in (int(s) for s in a.iterations.split(",")):
             D = a.decisions or (20 if K <= 64 else 3)
@@ -90,9 +79,7 @@ def main():
                   % (K, I, D, row["drive_ms_per_decision"], row["composed_ms_per_decision"], row["composed_over_drive"],
                      row["run_ms"], row["drive_over_run"], row["crashed"], same), flush=True)
     if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(dict(tool="tools/gpu_mcts_drive_bench.py", rows=rows), f, indent=1)
+        write_rows(a.out, "tools/gpu_mcts_drive_bench.py", rows)
 
 
 if __name__ == "__main__":

@@ -10,7 +10,6 @@
       car's outline, then an ordinary scan, per car), R = 64 races of P = 2: microseconds per race-tick.
 Prints one line per row; --out writes the rows as JSON."""
 import argparse
-import json
 import os
 import sys
 import time
@@ -18,13 +17,9 @@ import time
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from pyracecarsimulator_amd import maps, range_libc, workloads, racecar as RC  # noqa: E402
-from pyracecarsimulator_amd.followgap import PyFollowGap  # noqa: E402
-
-FOV, B, THRESH, D_BASE = workloads.SCAN_FOV, 1081, 0.001, 0.275
-MAX_STEER = RC.DEFAULT_CAR["max_steer_ang"]
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bench_common import B, FOV, THRESH, lidar_poses, world, write_rows  # noqa: E402
+from pyracecarsimulator_amd import maps, range_libc  # noqa: E402
 
 
 def race_states(g, dt, n_races, group, seed, spread=1.0):
@@ -36,11 +31,6 @@ def race_states(g, dt, n_races, group, seed, spread=1.0):
     s[:, 2] = rng.uniform(-np.pi, np.pi, n_races * group)
     s[:, 3] = 2.0
     return s.reshape(n_races, group, 11)
-
-
-def lidar(cars):
-    return np.stack([cars[:, 0] + D_BASE * np.cos(cars[:, 2]), cars[:, 1] + D_BASE * np.sin(cars[:, 2]),
-                     cars[:, 2]], -1).astype(np.float32)
 
 
 def device_ms(fn, reps):
@@ -62,10 +52,7 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     rows = []
-    g = maps.load_colombia()
-    omap = range_libc.PyOMap(g)
-    dt = omap.distance_transform()
-    m = range_libc.PyRayMarchingGPU(omap, 300)
+    g, omap, dt, m, fg, cb, edge = world("colombia")
     stream = torch.cuda.current_stream().cuda_stream
     N = 4096
 
@@ -73,7 +60,7 @@ def main():
     for P in (2, 4):
         st = race_states(g, dt, N // P, P, 5 + P).reshape(N, 11)
         cars = torch.from_numpy(np.ascontiguousarray(st[:, :3])).cuda()
-        poses = torch.from_numpy(lidar(st)).cuda()
+        poses = torch.from_numpy(lidar_poses(st)).cuda()
         out = torch.empty(N * B, dtype=torch.float32, device="cuda")
         for _ in range(3):
             m.calc_range_fan_cars_device(poses.data_ptr(), cars.data_ptr(), N // P, P, FOV, B, out.data_ptr(), stream=stream)
@@ -92,9 +79,6 @@ def main():
               % (P, race * 1e3, alone * 1e3, plan * 1e3, race / alone, race / plan), flush=True)
 
     # (b) the tick
-    fg = PyFollowGap(10, 15.0, MAX_STEER, 0.004)
-    cb = RC.CarBatch()
-    edge = RC.edge_distances(B, -FOV / 2, FOV / B, D_BASE, RC.DEFAULT_CAR["width"], RC.DEFAULT_CAR["wb"])
     T = args.ticks
     for P in (2, 4):
         st = race_states(g, dt, N // P, P, 5 + P)
@@ -117,7 +101,7 @@ def main():
     st = race_states(g, dt, R, P, 77)
     flat = st.reshape(-1, 11)
     cells, counts = cb.outline_cells(omap, flat[:, :3])
-    poses = lidar(flat)
+    poses = lidar_poses(flat)
     omap2 = range_libc.PyOMap(g)
     m2 = range_libc.PyRayMarchingGPU(omap2, 300)
     one = np.empty(B, np.float32)
@@ -141,8 +125,7 @@ def main():
     print("(c) R=64 P=2  race %.2f us per race-tick  stamp-and-scan loop %.1f us per race-tick (scans only)  %.0fx"
           % (race * 1e6, loop * 1e6, loop / race), flush=True)
     if args.out:
-        with open(args.out, "w") as f:
-            json.dump(dict(device=torch.cuda.get_device_name(0), rows=rows), f, indent=1)
+        write_rows(args.out, None, rows, device=torch.cuda.get_device_name(0))
 
 
 if __name__ == "__main__":

@@ -9,7 +9,7 @@ a = torch.empty(n, dtype=torch.float32, device="cuda").normal_()
 b = torch.empty_like(a)
 
 
-def timed(fn, reps=10):
+def event_seconds(fn, reps=10):
     for _ in range(2):
         fn()
     torch.cuda.synchronize()
@@ -23,11 +23,11 @@ def timed(fn, reps=10):
 
 
 gb = n * 4 / 1e9
-t = timed(lambda: b.copy_(a))
+t = event_seconds(lambda: b.copy_(a))
 print("copy  (read %.1f GB + write %.1f GB): %.0f GB/s" % (gb, gb, 2 * gb / t))
-t = timed(lambda: b.fill_(1.0))
+t = event_seconds(lambda: b.fill_(1.0))
 print("fill  (write only)              : %.0f GB/s" % (gb / t))
-t = timed(lambda: a.sum())
+t = event_seconds(lambda: a.sum())
 print("sum   (read only)               : %.0f GB/s" % (gb / t))
 
 
