@@ -598,8 +598,8 @@ int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const double *sta
  * < 0, n_starts < 1, a non-finite start state, n_envs num_rays >= 2^31, a start_index outside [0, M) (host form),
  * handles on different devices or multi-device handles, a step or read before a reset; the range method's own
  * refusals come back with their code.  After a failed launch the env needs a reset.
- * Out of scope: races inside the environment (a car re-spawned alone into a running race has no obvious rule),
- * multi-device handles, graph capture (a step advances host-side counters).
+ * Races inside the environment: the next section, "the race environment".  Out of scope: multi-device handles,
+ * graph capture (a step advances host-side counters).
  * Per call: env_step_kernel, the fan launch sequence of h's planner, env_observe_kernel (env_kernels.h).       */
 typedef struct rl_env rl_env;
 typedef struct rl_env_params {
@@ -622,6 +622,58 @@ int  rl_env_reset_device(rl_env *e, uint64_t seed, const int *d_start_index_or_n
 int  rl_env_step_device(rl_env *e, const float *d_actions_n2, float *d_obs, float *d_reward, int *d_done,
                         float *d_aux_or_null, void *hip_stream);
 int  rl_env_read(rl_env *e, double *states_n11, int *ticks, int *episodes, int *start_index, int *done);
+
+/* ---- the race environment ----------------------------------------------------------------------
+ * The driving environment with the race as the episode: R races of `group` = P cars (1 <= P <= 8) that see each other
+ * in every scan, as in rl_car_race_followgap, driven by the caller's actions.  A race spawns and re-spawns as a
+ * whole; in between a finished car stays in the map as a wreck.  An rl_env made by rl_env_create_race is served by
+ * rl_env_reset / _step (+ _device), rl_env_read and rl_env_destroy; fed FollowGap's answers it reproduces
+ * rl_car_race_followgap bit for bit, and with P = 1 it is rl_env_create's environment.  tests/race_env_statement.py
+ * restates this section.  Everything is as written for the driving environment except:
+ *
+ * Layout.  R = n_envs / P races; car k of race r is env e = r P + k.  Actions, obs, reward, done and aux stay one row
+ *   per car.  starts_mp11: a pool of M = n_starts line-ups of P rows in getState layout; car k of a race spawned from
+ *   line-up idx gets row idx P + k.  The cars' outline is c's LENGTH x WIDTH.
+ * Per-race counters: race_tick[r], race_episode[r], race_start_index[r] and race_over[r] in {0 running, 1 over because
+ *   fewer than min_running cars run (none running included), 2 truncated at max_ticks}.  Per car, episode[e] and
+ *   start_index[e] mirror the race's; tick[e] counts the steps that car took in this episode (a wreck stops counting).
+ * Spawn of race r at episode q: idx = start_index[r] when the caller gave start indices and q = 0 (the index arrays
+ *   of rl_env_reset* hold n_races entries), otherwise idx = min(M-1, (int)(U(r, q) * (double)M)) with the env's
+ *   uniform and key.  All P cars spawn together.
+ * Step k, phase A (race_env_step_kernel, one lane per car):
+ *   race_over[r] != 0 and auto_reset: the whole race spawns with q = race_episode[r] + 1 and race_tick = 0; every car
+ *     is "fresh", its action is ignored;
+ *   race_over[r] != 0 without auto_reset: every car of the race is frozen;
+ *   otherwise race_tick[r] += 1, and a car with done[e] != 0 is a frozen wreck: its state stays, its action is
+ *     ignored, it is scanned again where it stands with this slot's noise, and the others see it.  Every other car
+ *     goes through the env's action check (done = 3 makes it a wreck), clamp and `substeps` steps.
+ * Scan: the race scan of rl_calc_range_fan_cars over all n_envs lidar poses, the other cars of the race read from the
+ *   f64 states as they stand after phase A; ray offset base + (k n_envs + e) num_rays.  Kinds RL_RM and RL_RM_GPU,
+ *   variants 0, 1 and 3.
+ * Phase B (race_env_observe_kernel, one workgroup per race, one wave per car), per car: the env's rule with
+ *   race_tick[r] for the truncation test: a hit sets done = 1 for a stepped or fresh car, otherwise a stepped car with
+ *   max_ticks > 0 and race_tick[r] == max_ticks gets done = 2; the reward is the env's, 0 for a wreck.
+ *   Then per race, once every car has its code: running = the number of cars with done == 0.  If a car was truncated
+ *   race_over = 2; else if running < min_running race_over = 1 and every car still running reads done = 2 and keeps
+ *   its (float)moved reward (it survived; at a reset or re-spawn such a fresh car reads 2 with reward 0); else
+ *   race_over = 0.  Cars that hit each other in the same step both read 1.  A finished race that stands (no
+ *   auto_reset) keeps its codes and reads reward 0.
+ *
+ * Errors (RL_ERR_INVALID, nothing launched, the handles usable as before): group outside [1, 8], n_envs not a multiple
+ * of group, min_running outside [1, group], everything rl_env_create refuses, a race start_index outside [0, M) (host
+ * form), rl_env_read_races on an env that is not a race env or before a reset.  The refusals of rl_calc_range_fan_cars
+ * come back with their codes at create and at every reset and step: RL_ERR_UNSUPPORTED for RL_CDDT, RL_GIANT_LUT,
+ * RL_BRESENHAM, variant 2, outlines of more than 512 points and maps of 32768 or more cells a side.
+ * rl_env_read_races: the races' counters [n_races] each, every pointer optional; it waits like rl_env_read.
+ * Per call: race_env_step_kernel, race_fan_kernel, race_env_observe_kernel (env_kernels.h, race_kernels.h).        */
+typedef struct rl_race_env_params {
+    rl_env_params env;   /* n_envs = n_races * group cars, race-major; every other field as rl_env_create reads it */
+    int group;           /* P cars per race, 1 .. 8 */
+    int min_running;     /* the race is over once fewer than this many cars run: 1 .. group */
+} rl_race_env_params;
+int  rl_env_create_race(rl_car *c, rl_method *h, const rl_race_env_params *p, const double *edge,
+                        const double *starts_mp11, int n_starts, rl_env **out);
+int  rl_env_read_races(rl_env *e, int *race_ticks, int *race_episodes, int *race_start_index, int *race_over);
 
 /* ---- the MCTS planner ----------------------------------------------------------------------------
  * scripts/mcts.py's tree search (MCTS.mcts / mctsIteration / act / rollout, :109-245) for K independent trees in

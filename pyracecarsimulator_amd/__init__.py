@@ -10,7 +10,7 @@ from .racecar_simulator import RacecarSimulator      # noqa: F401
 from .policy import Policy                           # noqa: F401
 from .mcts import MCTS                               # noqa: F401
 from .particle_filter import ParticleFilter          # noqa: F401
-from .env import DriveEnv                            # noqa: F401
+from .env import DriveEnv, RaceEnv                   # noqa: F401
 
 __all__ = ["maps", "racecar", "range_libc", "ScanSimulator2D", "RacecarSimulator", "Policy", "MCTS",
-           "ParticleFilter", "DriveEnv"]
+           "ParticleFilter", "DriveEnv", "RaceEnv"]

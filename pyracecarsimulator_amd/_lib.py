@@ -71,6 +71,11 @@ class EnvParams(C.Structure):
         ("fov", C.c_float)]
 
 
+class RaceEnvParams(C.Structure):
+    """rl_race_env_params (include/scanlib.h)."""
+    _fields_ = [("env", EnvParams), ("group", C.c_int), ("min_running", C.c_int)]
+
+
 RL_MCTS_FG, RL_MCTS_NN, RL_MCTS_RANDOM = 0, 1, 2
 
 KERNEL_IDS = {0: "none", 1: "rm_chunk", 2: "rm_stream", 3: "occ_lds", 4: "bl_stream", 5: "bl_lds", 6: "lut_lds",
@@ -177,6 +182,9 @@ SYMBOLS = {
     "rl_env_reset_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rl_env_step_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rl_env_read": (C.c_int, [C.c_void_p, f64p, i32p, i32p, i32p, i32p]),
+    "rl_env_create_race": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RaceEnvParams), f64p, f64p, C.c_int,
+                                     C.POINTER(C.c_void_p)]),
+    "rl_env_read_races": (C.c_int, [C.c_void_p, i32p, i32p, i32p, i32p]),
     "rl_mcts_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MctsParams), f64p,
                                  C.POINTER(C.c_void_p)]),
     "rl_mcts_destroy": (None, [C.c_void_p]),

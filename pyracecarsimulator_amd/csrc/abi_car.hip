@@ -762,6 +762,9 @@ extern "C" int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const 
 typedef void (*env_observe_fn)(EnvParams, EnvBufs, float *, float *, int *, float *);
 static const std::array<env_observe_fn, FG_ROWS> env_observe_table =
     rows_table<env_observe_fn>([](auto rows) { return env_observe_kernel<rows>; });
+typedef void (*race_env_observe_fn)(EnvParams, EnvBufs, RaceEnvBufs, float *, float *, int *, float *);
+static const std::array<race_env_observe_fn, FG_ROWS> race_env_observe_table =
+    rows_table<race_env_observe_fn>([](auto rows) { return race_env_observe_kernel<rows>; });
 
 struct rl_env {
     rl_car *c = nullptr;
@@ -772,6 +775,10 @@ struct rl_env {
     DevPtr<double> state, starts, edge, moved;
     DevPtr<int> tick, episode, start_index, done, phase;
     DevPtr<float> pose, ranges;
+    // a race env (rl_env_create_race): group > 0, the races' counters [n_envs / group] and the cars' outline
+    int group = 0, min_running = 0;
+    DevPtr<int> race_tick, race_episode, race_start_index, race_over;
+    OutlineParams outline{};
     // the host forms' staging: actions and start indices in, observation, reward, done and aux out
     DevPtr<float> h_actions, h_obs, h_reward, h_aux;
     DevPtr<int> h_sidx, h_done;
@@ -788,6 +795,19 @@ static EnvBufs env_bufs(rl_env *e)
                    e->ranges};
 }
 
+static RaceEnvBufs race_env_bufs(rl_env *e)
+{
+    return RaceEnvBufs{e->group, e->min_running, e->race_tick, e->race_episode, e->race_start_index, e->race_over};
+}
+
+// the scan's own refusals, checked before every launching call: a race env adds those of rl_calc_range_fan_cars
+static int env_scan_args(rl_env *e)
+{
+    int rc = check_fan_args(e->h, e->prm.n_envs, e->prm.fov, e->prm.num_rays);
+    if (rc == RL_OK && e->group > 0) rc = race_args(e->h, e->prm.n_envs / e->group, e->group, e->prm.num_rays);
+    return rc;
+}
+
 extern "C" void rl_env_destroy(rl_env *e)
 {
     if (!e) return;
@@ -797,11 +817,13 @@ extern "C" void rl_env_destroy(rl_env *e)
     delete e;
 }
 
-extern "C" int rl_env_create(rl_car *c, rl_method *h, const rl_env_params *params, const double *edge,
-                             const double *starts_m11, int n_starts, rl_env **out)
+// rl_env_create (group = 0) and rl_env_create_race (group = P >= 1: the pool holds n_starts line-ups of P rows)
+static int env_create(rl_car *c, rl_method *h, const rl_env_params *params, const double *edge, const double *starts_m11,
+                      int n_starts, int group, int min_running, rl_env **out)
 {
     if (!c || !h || !params || !edge || !starts_m11 || !out) return fail(RL_ERR_INVALID, "rl_env_create: null pointer");
     const rl_env_params q = *params;
+    const int per = group > 0 ? group : 1;      // pool rows per start
     int rc = loop_args("rl_env_create", c, h, nullptr, nullptr, q.n_envs, q.num_rays);
     if (rc) return rc;
     if (q.n_envs < 1) return fail(RL_ERR_INVALID, "rl_env_create: n_envs must be >= 1 (got %d)", q.n_envs);
@@ -817,11 +839,15 @@ extern "C" int rl_env_create(rl_car *c, rl_method *h, const rl_env_params *param
         return fail(RL_ERR_INVALID, "rl_env_create: crash_reward must not be NaN and dt must be finite");
     if (q.max_ticks < 0) return fail(RL_ERR_INVALID, "rl_env_create: max_ticks must be >= 0 (got %d)", q.max_ticks);
     if (n_starts < 1) return fail(RL_ERR_INVALID, "rl_env_create: n_starts must be >= 1 (got %d)", n_starts);
-    if (n_starts > INT_MAX / 11) return fail(RL_ERR_INVALID, "rl_env_create: too many start states (%d)", n_starts);
-    for (size_t i = 0; i < (size_t)n_starts * 11; ++i)
+    if (n_starts > INT_MAX / (11 * per)) return fail(RL_ERR_INVALID, "rl_env_create: too many start states (%d)", n_starts);
+    for (size_t i = 0; i < (size_t)n_starts * per * 11; ++i)
         if (!std::isfinite(starts_m11[i]))
             return fail(RL_ERR_INVALID, "rl_env_create: start state %zu holds a non-finite value", i / 11);
     if ((rc = check_fan_args(h, q.n_envs, q.fov, q.num_rays))) return rc;
+    OutlineParams outline{};
+    if (group > 0 && ((rc = race_args(h, q.n_envs / group, group, q.num_rays)) ||
+                      (rc = race_outline(h->map, c->P.LENGTH, c->P.WIDTH, outline))))
+        return rc;
     std::unique_ptr<rl_env, decltype(&rl_env_destroy)> e(new (std::nothrow) rl_env(), rl_env_destroy);
     if (!e) return fail(RL_ERR_NOMEM, "out of host memory");
     e->c = c;
@@ -829,6 +855,9 @@ extern "C" int rl_env_create(rl_car *c, rl_method *h, const rl_env_params *param
     e->prm = q;
     e->device = c->device;
     e->n_starts = n_starts;
+    e->group = group;
+    e->min_running = min_running;
+    e->outline = outline;
     EnvParams &ep = e->ep;
     ep.P = c->P;
     ep.dt = q.dt;
@@ -848,8 +877,10 @@ extern "C" int rl_env_create(rl_car *c, rl_method *h, const rl_env_params *param
     ep.auto_reset = q.auto_reset != 0;
     ep.n_starts = n_starts;
     if (hipSetDevice(e->device) != hipSuccess) return fail(RL_ERR_HIP, "rl_env_create: hipSetDevice failed");
-    const size_t N = q.n_envs, B = q.num_rays, M = n_starts;
-    if ((rc = e->state.ensure(N * 11)) || (rc = e->starts.ensure(M * 11)) || (rc = e->edge.ensure(B)) || (rc = e->tick.ensure(N)) ||
+    const size_t N = q.n_envs, B = q.num_rays, M = (size_t)n_starts * per, R = N / per;
+    if ((group > 0 && ((rc = e->race_tick.ensure(R)) || (rc = e->race_episode.ensure(R)) ||
+                       (rc = e->race_start_index.ensure(R)) || (rc = e->race_over.ensure(R)))) ||
+        (rc = e->state.ensure(N * 11)) || (rc = e->starts.ensure(M * 11)) || (rc = e->edge.ensure(B)) || (rc = e->tick.ensure(N)) ||
         (rc = e->episode.ensure(N)) || (rc = e->start_index.ensure(N)) || (rc = e->done.ensure(N)) || (rc = e->phase.ensure(N)) ||
         (rc = e->moved.ensure(N)) || (rc = e->pose.ensure(N * 3)) || (rc = e->ranges.ensure(N * B)) ||
         (rc = e->h_actions.ensure(N * 2)) || (rc = e->h_sidx.ensure(N)) || (rc = e->h_obs.ensure(N * q.obs_count)) ||
@@ -862,17 +893,47 @@ extern "C" int rl_env_create(rl_car *c, rl_method *h, const rl_env_params *param
     return RL_OK;
 }
 
+extern "C" int rl_env_create(rl_car *c, rl_method *h, const rl_env_params *params, const double *edge,
+                             const double *starts_m11, int n_starts, rl_env **out)
+{
+    return env_create(c, h, params, edge, starts_m11, n_starts, 0, 0, out);
+}
+
+extern "C" int rl_env_create_race(rl_car *c, rl_method *h, const rl_race_env_params *params, const double *edge,
+                                  const double *starts_mp11, int n_starts, rl_env **out)
+{
+    if (!params) return fail(RL_ERR_INVALID, "rl_env_create_race: null pointer");
+    const int P = params->group;
+    if (P < 1 || P > RACE_MAX_GROUP)
+        return fail(RL_ERR_INVALID, "rl_env_create_race: group must lie in [1, %d] cars (got %d)", RACE_MAX_GROUP, P);
+    if (params->env.n_envs % P != 0)
+        return fail(RL_ERR_INVALID, "rl_env_create_race: n_envs (%d) must be a multiple of group (%d)", params->env.n_envs, P);
+    if (params->min_running < 1 || params->min_running > P)
+        return fail(RL_ERR_INVALID, "rl_env_create_race: min_running must lie in [1, %d] (got %d)", P, params->min_running);
+    return env_create(c, h, &params->env, edge, starts_mp11, n_starts, P, params->min_running, out);
+}
+
 // one call's launches on st: phase A (reset: the spawn), the scan at slot k, phase B.  lp: the call's Loop, owner e.
 static int env_launch(rl_env *e, const Loop &lp, bool reset, uint64_t k, const float *d_actions, const int *d_start_index,
                       float *d_obs, float *d_reward, int *d_done, float *d_aux, hipStream_t st)
 {
     const int N = e->prm.n_envs, B = e->prm.num_rays;
     const EnvBufs b = env_bufs(e);
+    const uint64_t off = e->base + k * (uint64_t)N * (uint64_t)B;
+    if (e->group > 0) {          // a race env: whole races spawn and end, and the cars see each other in the scan
+        const RaceEnvBufs rb = race_env_bufs(e);
+        hipLaunchKernelGGL(race_env_step_kernel, dim3((N + 63) / 64), dim3(64), 0, st, e->ep, b, rb, d_actions,
+                           d_start_index, reset ? 1 : 0);
+        if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "race_env_step_kernel launch failed");
+        const LoopScan scan{e->pose, N, e->prm.fov, B, e->ranges, nullptr, e->group, e->state, &e->outline};
+        return lp.scan_then(scan, off, race_env_observe_table, e->group, "race_env_observe_kernel", st, e->ep, b, rb, d_obs,
+                            d_reward, d_done, d_aux);
+    }
     hipLaunchKernelGGL(env_step_kernel, dim3((N + 63) / 64), dim3(64), 0, st, e->ep, b, d_actions, d_start_index,
                        reset ? 1 : 0);
     if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "env_step_kernel launch failed");
     const LoopScan scan{e->pose, N, e->prm.fov, B, e->ranges, nullptr, 0, nullptr, nullptr};
-    return lp.scan_then(scan, e->base + k * (uint64_t)N * (uint64_t)B, env_observe_table, DRIVE_CARS, "env_observe_kernel",
+    return lp.scan_then(scan, off, env_observe_table, DRIVE_CARS, "env_observe_kernel",
                         st, e->ep, b, d_obs, d_reward, d_done, d_aux);
 }
 
@@ -915,7 +976,7 @@ extern "C" int rl_env_reset_device(rl_env *e, uint64_t seed, const int *d_start_
                                    float *d_aux_or_null, int *d_done, void *hip_stream)
 {
     if (!e || !d_obs || !d_done) return fail(RL_ERR_INVALID, "rl_env_reset_device: null pointer");
-    int rc = check_fan_args(e->h, e->prm.n_envs, e->prm.fov, e->prm.num_rays);
+    int rc = env_scan_args(e);
     if (rc) return rc;
     const Loop lp(&e->mu, e->c, e->h, nullptr, nullptr);
     HIPCHK(hipSetDevice(e->device));
@@ -930,7 +991,7 @@ extern "C" int rl_env_step_device(rl_env *e, const float *d_actions_n2, float *d
     if (!e || !d_actions_n2 || !d_obs || !d_reward || !d_done) return fail(RL_ERR_INVALID, "rl_env_step_device: null pointer");
     const Loop lp(&e->mu, e->c, e->h, nullptr, nullptr);
     if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_step_device: reset the environment first (rl_env_reset)");
-    int rc = check_fan_args(e->h, e->prm.n_envs, e->prm.fov, e->prm.num_rays);
+    int rc = env_scan_args(e);
     if (rc) return rc;
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)hip_stream;
@@ -953,19 +1014,19 @@ extern "C" int rl_env_reset(rl_env *e, uint64_t seed, const int *start_index_or_
                             int *done)
 {
     if (!e || !obs || !done) return fail(RL_ERR_INVALID, "rl_env_reset: null pointer");
-    const int N = e->prm.n_envs;
+    const int N = e->prm.n_envs, n_idx = e->group > 0 ? N / e->group : N;     // (a race env: one index per race)
     if (start_index_or_null)
-        for (int i = 0; i < N; ++i)
+        for (int i = 0; i < n_idx; ++i)
             if (start_index_or_null[i] < 0 || start_index_or_null[i] >= e->n_starts)
                 return fail(RL_ERR_INVALID, "rl_env_reset: start_index[%d] = %d lies outside [0, %d)", i,
                             start_index_or_null[i], e->n_starts);
-    int rc = check_fan_args(e->h, N, e->prm.fov, e->prm.num_rays);
+    int rc = env_scan_args(e);
     if (rc) return rc;
     const Loop lp(&e->mu, e->c, e->h, nullptr, nullptr);
     HIPCHK(hipSetDevice(e->device));
     if ((rc = env_settle(e))) return rc;
     HostCall hc(e->c->stream);
-    if ((start_index_or_null && (rc = hc.up(e->h_sidx, start_index_or_null, N))) ||
+    if ((start_index_or_null && (rc = hc.up(e->h_sidx, start_index_or_null, n_idx))) ||
         (rc = env_reset_locked(e, lp, seed, start_index_or_null ? (int *)e->h_sidx : nullptr, e->h_obs,
                                aux_or_null ? (float *)e->h_aux : nullptr, e->h_done, hc.st)))
         return rc;
@@ -978,7 +1039,7 @@ extern "C" int rl_env_step(rl_env *e, const float *actions_n2, float *obs, float
     const Loop lp(&e->mu, e->c, e->h, nullptr, nullptr);
     if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_step: reset the environment first (rl_env_reset)");
     const int N = e->prm.n_envs;
-    int rc = check_fan_args(e->h, N, e->prm.fov, e->prm.num_rays);
+    int rc = env_scan_args(e);
     if (rc) return rc;
     HIPCHK(hipSetDevice(e->device));
     if ((rc = env_settle(e))) return rc;
@@ -1003,6 +1064,23 @@ extern "C" int rl_env_read(rl_env *e, double *states_n11, int *ticks, int *episo
     if ((rc = hc.down(states_n11, e->state, N * 11)) || (rc = hc.down(ticks, e->tick, N)) ||
         (rc = hc.down(episodes, e->episode, N)) || (rc = hc.down(start_index, e->start_index, N)) ||
         (rc = hc.down(done, e->done, N)))
+        return rc;
+    return hc.finish();
+}
+
+extern "C" int rl_env_read_races(rl_env *e, int *race_ticks, int *race_episodes, int *race_start_index, int *race_over)
+{
+    if (!e) return fail(RL_ERR_INVALID, "rl_env_read_races: null pointer");
+    std::scoped_lock lk(e->mu, e->c->mu);
+    if (e->group < 1) return fail(RL_ERR_INVALID, "rl_env_read_races: not a race environment (rl_env_create_race)");
+    if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_read_races: reset the environment first (rl_env_reset)");
+    HIPCHK(hipSetDevice(e->device));
+    int rc = env_settle(e);
+    if (rc) return rc;
+    HostCall hc(e->c->stream);
+    const size_t R = e->prm.n_envs / e->group;
+    if ((rc = hc.down(race_ticks, e->race_tick, R)) || (rc = hc.down(race_episodes, e->race_episode, R)) ||
+        (rc = hc.down(race_start_index, e->race_start_index, R)) || (rc = hc.down(race_over, e->race_over, R)))
         return rc;
     return hc.finish();
 }

@@ -30,6 +30,9 @@ BOUNDS = [
     # the driving environment: the spawn / step lane and the observe wave keep nothing in scratch
     ("scan::env_step_kernel", {"scratch": 0}),
     ("scan::env_observe_kernel<", {"scratch": 0}),
+    # the race environment: the same lane and wave with the race's rule around them
+    ("scan::race_env_step_kernel", {"scratch": 0}),
+    ("scan::race_env_observe_kernel<", {"scratch": 0}),
     # the policy network: the micro-tile accumulators stay in registers
     ("scan::policy_mlp_kernel", {"scratch": 0}),
     # the MCTS planner: the descent, the act wave, the backup's pairwise sum and the walks keep nothing in scratch

@@ -8,6 +8,9 @@
 //   B. env_observe_kernel<ROWS>, one wave per env: Car::isCrashed as a ballot (drive_crashed), truncation, the reward,
 //      the observation window (lane-contiguous stores), the optional aux row.
 // A reset is the same sequence with env_step_kernel in spawn mode.
+// A race environment (rl_env_create_race) makes the race of P cars the episode: race_env_step_kernel spawns, freezes
+// and steps whole races, the scan is race_fan_kernel over the cars' f64 states (race_kernels.h), and
+// race_env_observe_kernel<ROWS>, one workgroup per race, decides after every car's code when the race is over.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,6 +18,7 @@
 #include "car_kernels.h"
 #include "drive_kernels.h"
 #include "policy_kernels.h"
+#include "race_kernels.h"
 #include "scan_device.h"
 
 namespace scan {
@@ -145,6 +149,143 @@ __global__ __launch_bounds__(64 * DRIVE_CARS) void env_observe_kernel(EnvParams 
     }
     float *o = obs + (size_t)e * p.obs_count;
     for (int i = lane; i < p.obs_count; i += 64) {              // lane i of a round stores word i: whole lines
+        const float v = row[p.obs_start + i * p.obs_stride];
+        o[i] = p.obs_scale > 0.0f ? policy_input(v, p.obs_clip, p.obs_scale) : v;
+    }
+    if (aux && lane < 4) aux[4 * (size_t)e + lane] = (float)b.state[(size_t)e * 11 + 3 + lane];
+}
+
+// ---- the race environment: the episode is a race of p.n_envs / R.group cars; car k of race r is env r P + k
+// why a race is over (RaceEnvBufs::over; include/scanlib.h)
+enum : int { RACE_RUNNING = 0, RACE_ATTRITION = 1, RACE_TRUNCATED = 2 };
+
+struct RaceEnvBufs {
+    int group, min_running;      // P cars a race; the race is over below min_running running cars
+    int *tick, *episode, *start_index, *over;     // [R] each; starts: [M, P, 11]
+};
+
+// car k of race r joins the race's spawn at episode q (every lane of the race draws the same idx)
+__device__ inline void race_env_spawn(const EnvParams &p, const EnvBufs &b, const RaceEnvBufs &R, int e, int q,
+                                      const int *given, CarState &cs)
+{
+    const int r = e / R.group, k = e - r * R.group;
+    const int idx = env_spawn_index(p, r, q, given);
+    const double *s = b.starts + ((size_t)idx * R.group + k) * 11;
+    double *o = b.state + (size_t)e * 11;
+#pragma unroll
+    for (int i = 0; i < 11; ++i) o[i] = s[i];
+    cs = drive_load_state(s);
+    b.tick[e] = 0;
+    b.episode[e] = q;
+    b.start_index[e] = idx;
+    b.done[e] = ENV_RUNNING;
+    b.phase[e] = ENV_FRESH;
+    b.moved[e] = 0.0;
+    if (k == 0) {
+        R.tick[r] = 0;
+        R.episode[r] = q;
+        R.start_index[r] = idx;
+    }
+}
+
+// phase A of a race env, one lane per car.  Races straddle blocks, so no word is written by one lane and read by
+// another in here: R.over is read only, R.tick / R.episode / R.start_index are written by car 0's lane and read in
+// phase B, and every lane takes the race's episode from its own car's mirror.
+__global__ __launch_bounds__(64) void race_env_step_kernel(EnvParams p, EnvBufs b, RaceEnvBufs R,
+                                                           const float *__restrict__ actions,
+                                                           const int *__restrict__ start_index, int reset)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= p.n_envs) return;
+    const int r = e / R.group;
+    double *s = b.state + (size_t)e * 11;
+    CarState cs;
+    if (reset) {
+        race_env_spawn(p, b, R, e, 0, start_index, cs);
+    } else if (R.over[r] != RACE_RUNNING) {
+        if (p.auto_reset) {
+            race_env_spawn(p, b, R, e, b.episode[e] + 1, nullptr, cs);
+        } else {
+            cs = drive_load_state(s);            // a finished race stands
+            b.phase[e] = ENV_FROZEN;
+            b.moved[e] = 0.0;
+        }
+    } else {
+        if (e == r * R.group) R.tick[r] += 1;
+        cs = drive_load_state(s);
+        if (b.done[e] != ENV_RUNNING) {          // a wreck: scanned again where it stands, and the others see it
+            b.phase[e] = ENV_FROZEN;
+            b.moved[e] = 0.0;
+        } else {
+            const double speed = (double)actions[2 * e + 0];
+            double steer = (double)actions[2 * e + 1];
+            if (!(isfinite(speed) && isfinite(steer))) {
+                b.done[e] = ENV_BAD_ACTION;
+                b.phase[e] = ENV_INVALID;
+                b.moved[e] = 0.0;
+            } else {
+                if (p.steer_clip > 0.0) steer = fmin(fmax(steer, -p.steer_clip), p.steer_clip);
+                const double before = cs.travel_dist;
+                for (int i = 0; i < p.substeps; ++i) car_step(p.P, cs, speed, steer, p.dt);
+                drive_store_state(cs, s);
+                b.tick[e] += 1;
+                b.phase[e] = ENV_STEPPED;
+                b.moved[e] = cs.travel_dist - before;
+            }
+        }
+    }
+    float pose[3];
+    car_scan_pose(cs, p.scan_dist_to_base, pose);
+    b.pose[3 * e + 0] = pose[0];
+    b.pose[3 * e + 1] = pose[1];
+    b.pose[3 * e + 2] = pose[2];
+}
+
+// phase B of a race env: one workgroup per race, one wave per car (blockDim = 64 P, always P live waves).  Each wave
+// does env_observe_kernel's work for its car, parks the code in LDS, and after the barrier applies the race's rule.
+template <int ROWS>
+__global__ __launch_bounds__(64 * RACE_MAX_GROUP) void race_env_observe_kernel(EnvParams p, EnvBufs b, RaceEnvBufs R,
+                                                                               float *__restrict__ obs,
+                                                                               float *__restrict__ reward,
+                                                                               int *__restrict__ done_out,
+                                                                               float *__restrict__ aux)
+{
+    __shared__ int codes[RACE_MAX_GROUP];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x, e = r * R.group + w;
+    const float *row = b.ranges + (size_t)e * p.num_rays;
+    float raw[ROWS];
+    const bool hit = drive_crashed<ROWS>(row, b.edge, p.num_rays, p.crash_thresh, lane, raw);
+    const int phase = b.phase[e];
+    int done = b.done[e];
+    // a race spawns as a whole: a fresh car means a fresh race, whatever R.over still holds from the last episode
+    const int over0 = phase == ENV_FRESH ? RACE_RUNNING : R.over[r];
+    const bool stepped = phase == ENV_STEPPED;
+    if ((stepped || phase == ENV_FRESH) && hit) done = ENV_CRASHED;
+    else if (stepped && p.max_ticks > 0 && R.tick[r] == p.max_ticks) done = ENV_TRUNCATED;
+    float rw = 0.0f;
+    if (stepped) rw = done == ENV_CRASHED ? (float)p.crash_reward : (float)b.moved[e];
+    else if (phase == ENV_INVALID) rw = (float)p.crash_reward;
+    if (lane == 0) codes[w] = done;
+    __syncthreads();
+    if (over0 == RACE_RUNNING) {                                // (a finished race that stands: nothing changes)
+        int running = 0;
+        bool truncated = false;                                 // (a running race held no 2 before this call)
+        for (int k = 0; k < R.group; ++k) {
+            running += codes[k] == ENV_RUNNING;
+            truncated |= codes[k] == ENV_TRUNCATED;
+        }
+        const int over = truncated ? RACE_TRUNCATED : running < R.min_running ? RACE_ATTRITION : RACE_RUNNING;
+        if (over == RACE_ATTRITION && done == ENV_RUNNING) done = ENV_TRUNCATED;    // it survived: its reward stays
+        if (threadIdx.x == 0) R.over[r] = over;
+    }
+    if (lane == 0) {
+        b.done[e] = done;
+        done_out[e] = done;
+        if (reward) reward[e] = rw;
+    }
+    float *o = obs + (size_t)e * p.obs_count;
+    for (int i = lane; i < p.obs_count; i += 64) {
         const float v = row[p.obs_start + i * p.obs_stride];
         o[i] = p.obs_scale > 0.0f ? policy_input(v, p.obs_clip, p.obs_scale) : v;
     }

@@ -17,6 +17,10 @@ The interface follows the usual vectorised-environment shape (``reset`` -> obs, 
 depends on no environment toolkit.  ``done`` codes: 0 running, 1 crashed, 2 truncated, 3 invalid (non-finite) action.
 The reward of a step is the distance travelled (float32), ``crash_reward`` for a step that crashes or an invalid
 action, 0 for an env that was re-spawned by this call or that stands frozen.
+
+``RaceEnv`` is the same environment with a race of P cars as the episode (``rl_env_create_race``): the cars of a race
+see each other in every scan, a finished car stays in the map as a wreck, and the race spawns and re-spawns as a whole
+once fewer than ``min_running`` of its cars run or ``max_ticks`` is reached.
 """
 from __future__ import annotations
 
@@ -69,6 +73,26 @@ def env_args(n_envs, num_rays, starts, edge, substeps=1, obs_window=None, obs_cl
     return np.ascontiguousarray(st), np.ascontiguousarray(ed), (start, count, stride)
 
 
+def race_env_args(n_races, num_rays, starts, edge, min_running=1, **kw):
+    """``RaceEnv``'s arguments checked and laid out for ``rl_env_create_race`` (no library call): returns (starts
+    float64 (M, P, 11), edge, the observation window, P).  ``kw``: what ``env_args`` takes after ``edge``."""
+    R = int(n_races)
+    if R != n_races or int(min_running) != min_running:
+        raise ValueError("n_races and min_running must be integers")
+    if R < 1:
+        raise ValueError("n_races must be >= 1")
+    st = np.asarray(starts)
+    if st.dtype != np.float64 or st.ndim != 3 or st.shape[2] != 11 or st.shape[0] < 1:
+        raise ValueError("starts must be float64 (M, P, 11) with M >= 1")
+    P = st.shape[1]
+    if not 1 <= P <= 8:
+        raise ValueError("a race holds 1 to 8 cars (starts is (M, P, 11))")
+    if not 1 <= int(min_running) <= P:
+        raise ValueError("min_running must lie in [1, P]")
+    flat, ed, win = env_args(R * P, num_rays, st.reshape(-1, 11), edge, **kw)
+    return flat.reshape(-1, P, 11), ed, win, P
+
+
 class DriveEnv(_lib.Handle):
     """``n_envs`` cars on one device, driven by the caller's actions.  ``method`` scans (any kind, with its options and
     noise), ``starts`` float64 (M, 11) is the pool of start states (getState layout), ``edge`` the car-outline table
@@ -97,11 +121,15 @@ class DriveEnv(_lib.Handle):
         self.n_starts = st.shape[0]
         self._keep = (car, method)
         self._n, self._count = int(n_envs), win[1]
+        self._n_idx = self._n         # start indices a reset takes
         self._torch = None            # the device form's tensors, made at its first call
         self._h = C.c_void_p()
+        self._create(car, method, p, ed, st)
+        self.device = self._method_device(method)
+
+    def _create(self, car, method, p, ed, st):
         _lib.check(_lib.lib().rl_env_create(car._h, method._h, C.byref(p), ed.ctypes.data_as(f64p),
                                             st.ctypes.data_as(f64p), st.shape[0], C.byref(self._h)))
-        self.device = self._method_device(method)
 
     @staticmethod
     def _method_device(method):
@@ -158,7 +186,7 @@ class DriveEnv(_lib.Handle):
             if start_index is not None:
                 if not self._is_tensor(start_index):
                     raise ValueError("on_device=True takes start_index as a torch tensor (or None)")
-                self._check_tensor(start_index, (self._n,), "int32", "start_index")
+                self._check_tensor(start_index, (self._n_idx,), "int32", "start_index")
                 sidx = start_index.data_ptr()
             _lib.check(_lib.lib().rl_env_reset_device(
                 self._h, seed, C.c_void_p(sidx), C.c_void_p(t["obs"].data_ptr()),
@@ -168,8 +196,8 @@ class DriveEnv(_lib.Handle):
         sidx = None
         if start_index is not None:
             sidx = np.asarray(start_index)
-            if sidx.dtype.kind not in "iu" or sidx.shape != (self._n,):
-                raise ValueError("start_index must be integers (n_envs,)")
+            if sidx.dtype.kind not in "iu" or sidx.shape != (self._n_idx,):
+                raise ValueError("start_index must be integers (%d,)" % self._n_idx)
             if ((sidx < 0) | (sidx >= self.n_starts)).any():
                 raise ValueError("start_index must lie in [0, %d)" % self.n_starts)
             sidx = np.ascontiguousarray(sidx, dtype=np.int32)
@@ -217,4 +245,63 @@ class DriveEnv(_lib.Handle):
         _lib.check(_lib.lib().rl_env_read(self._h, out["states"].ctypes.data_as(f64p), out["ticks"].ctypes.data_as(i32p),
                                           out["episodes"].ctypes.data_as(i32p),
                                           out["start_index"].ctypes.data_as(i32p), out["done"].ctypes.data_as(i32p)))
+        return out
+
+
+class RaceEnv(DriveEnv):
+    """``n_races`` races of P cars on one device, every car driven by the caller's actions.  ``starts`` float64
+    (M, P, 11) is the pool of line-ups: a race spawns all its cars from one of them.  ``method``: RM or RMGPU.  The race
+    is over once fewer than ``min_running`` of its cars run (``race_over`` 1; the cars still running read done = 2) or
+    at ``max_ticks`` steps (``race_over`` 2); until then a finished car stays where it is and the others see it.  The
+    other arguments are ``DriveEnv``'s.  ``reset`` takes one start index per race; ``reset``, ``step`` and ``read`` give
+    the per-car rows as (n_races, P, ...) views, car k of race r at [r, k]; ``step`` takes (n_races, P, 2) actions."""
+
+    def __init__(self, method, starts, n_races, num_rays, fov, edge, crash_thresh, *, min_running=1, **kw):
+        checks = {k: kw[k] for k in ("substeps", "obs_window", "obs_clip", "obs_scale", "max_ticks", "steer_clip",
+                                     "crash_reward", "dt") if k in kw}
+        st, _, _, P = race_env_args(n_races, num_rays, starts, edge, min_running, **checks)
+        self._group, self._min_running, self._races = P, int(min_running), int(n_races)
+        super().__init__(method, st.reshape(-1, 11), self._races * P, num_rays, fov, edge, crash_thresh, **kw)
+        self.n_starts = st.shape[0]
+        self._n_idx = self._races
+
+    def _create(self, car, method, p, ed, st):
+        rp = _lib.RaceEnvParams()
+        rp.env, rp.group, rp.min_running = p, self._group, self._min_running
+        _lib.check(_lib.lib().rl_env_create_race(car._h, method._h, C.byref(rp), ed.ctypes.data_as(f64p),
+                                                 st.ctypes.data_as(f64p), st.shape[0] // self._group, C.byref(self._h)))
+
+    @property
+    def n_races(self):
+        return self._races
+
+    @property
+    def group(self):
+        return self._group
+
+    def _rows(self, x):
+        """Per-car rows (n_envs, ...) as (n_races, P, ...), a view in both forms."""
+        return x.reshape((self._races, self._group) + tuple(x.shape[1:]))
+
+    def reset(self, seed=0, start_index=None, *, aux=False, on_device=False):
+        """``DriveEnv.reset`` with ``start_index`` (n_races,): the line-up of every race.  Returns the observation
+        (n_races, P, obs_count), plus aux (n_races, P, 4) with ``aux=True``."""
+        out = super().reset(seed, start_index, aux=aux, on_device=on_device)
+        return tuple(self._rows(x) for x in out) if aux else self._rows(out)
+
+    def step(self, actions, aux=False):
+        """``DriveEnv.step`` with ``actions`` (n_races, P, 2) (or the per-car rows (n_envs, 2)): returns obs
+        (n_races, P, obs_count), reward and done (n_races, P), and aux (n_races, P, 4) with ``aux=True``."""
+        if tuple(actions.shape) == (self._races, self._group, 2):
+            actions = actions.reshape(self._n, 2)
+        return tuple(self._rows(x) for x in super().step(actions, aux))
+
+    def read(self):
+        """``DriveEnv.read``'s per-car arrays as (n_races, P, ...), and the races' counters ``race_ticks``,
+        ``race_episodes``, ``race_start_index`` and ``race_over`` (0 running, 1 too few cars run, 2 truncated), int32
+        (n_races,)."""
+        out = {k: self._rows(v) for k, v in super().read().items()}
+        names = ("race_ticks", "race_episodes", "race_start_index", "race_over")
+        out.update((k, np.empty(self._races, np.int32)) for k in names)
+        _lib.check(_lib.lib().rl_env_read_races(self._h, *(out[k].ctypes.data_as(i32p) for k in names)))
         return out

@@ -16,7 +16,8 @@ it unchanged.  The two native pieces behind it are on the GPU:
 loop of the simulator tick and simple_driver.py's FollowGap answer to every scan; ``drivePolicyMany`` the same loop
 steered by the policy network (scripts/policy_driver.py); ``planMCTSMany`` scripts/mcts.py's tree search from many
 start states at once; ``raceFollowGapMany`` many races of up to 8 cars that see each other (scripts/two_player/);
-``driveEnv`` the same tick with the steering left to the caller (``env.DriveEnv``).
+``driveEnv`` the same tick with the steering left to the caller (``env.DriveEnv``), ``raceEnv`` the race's
+(``env.RaceEnv``).
 """
 from __future__ import annotations
 
@@ -256,6 +257,17 @@ class RacecarSimulator:
         kw.setdefault("scan_dist_to_base", self.scan_dist_to_base)
         return DriveEnv(self.scan_simulator.scan_method, np.asarray(starts, dtype=np.float64).reshape(-1, 11), n_envs,
                         self.num_rays, self.scan_fov, self.edge_distances, self.ttc_thresh, **kw)
+
+    def raceEnv(self, n_races, starts, **kw):
+        """A ``RaceEnv`` of ``n_races`` races on this simulator's range method (RM or RMGPU), car, fan, edge table,
+        ttc_thresh and scan_dist_to_base, spawning from the line-ups ``starts`` float64 (M, P, 11): the tick of
+        ``raceFollowGapMany`` with the (speed, steer) of every car supplied by the caller.  ``kw``: ``RaceEnv``'s keyword
+        arguments (min_running and ``DriveEnv``'s)."""
+        from .env import RaceEnv
+        kw.setdefault("car", self.car)
+        kw.setdefault("scan_dist_to_base", self.scan_dist_to_base)
+        return RaceEnv(self.scan_simulator.scan_method, starts, n_races, self.num_rays, self.scan_fov,
+                       self.edge_distances, self.ttc_thresh, **kw)
 
     def stop(self):
         state = self.getState()
