@@ -11,6 +11,14 @@
 // A race environment (rl_env_create_race) makes the race of P cars the episode: race_env_step_kernel spawns, freezes
 // and steps whole races, the scan is race_fan_kernel over the cars' f64 states (race_kernels.h), and
 // race_env_observe_kernel<ROWS>, one workgroup per race, decides after every car's code when the race is over.
+// What happens to one car is stated once, for both environments:
+//   env_spawn_index, env_spawn   the draw and the start of an episode
+//   env_act, env_stand           a running env's action; an env that stays where it is
+//   car_scan_pose                the lidar pose, straight into EnvBufs::pose (car_kernels.h)
+//   env_done, env_reward         the verdict after the scan
+//   env_emit                     what the caller sees: done, reward, the observation window, the aux row
+// The race kernels add only the race's rule: the pool row and the race's counters at a spawn, the race's tick, the
+// wreck, and when the race is over.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,18 +58,19 @@ struct EnvBufs {
     const float *ranges;         // [N, num_rays] this call's scans
 };
 
-// env e's start of episode q: the caller's index (clamped to the pool) or the planner's uniform at counter (e, q)
-__device__ inline int env_spawn_index(const EnvParams &p, int e, int q, const int *given)
+// the start of episode q for whatever draws at counter `id` (an env, or a race for all its cars): the caller's index
+// (clamped to the pool) or the planner's uniform at counter (id, q)
+__device__ inline int env_spawn_index(const EnvParams &p, int id, int q, const int *given)
 {
-    if (given) return min(max(given[e], 0), p.n_starts - 1);
-    const double u = mcts_uniform01(p.key, (uint32_t)e, (uint32_t)q);
+    if (given) return min(max(given[id], 0), p.n_starts - 1);
+    const double u = mcts_uniform01(p.key, (uint32_t)id, (uint32_t)q);
     return min(p.n_starts - 1, (int)(u * (double)p.n_starts));
 }
 
-__device__ inline void env_spawn(const EnvParams &p, const EnvBufs &b, int e, int q, const int *given, CarState &cs)
+// env e starts episode q, drawn as start idx, from row `row` of the pool
+__device__ inline void env_spawn(const EnvBufs &b, int e, int q, int idx, size_t row, CarState &cs)
 {
-    const int idx = env_spawn_index(p, e, q, given);
-    const double *s = b.starts + (size_t)idx * 11;
+    const double *s = b.starts + row * 11;
     double *o = b.state + (size_t)e * 11;
 #pragma unroll
     for (int i = 0; i < 11; ++i) o[i] = s[i];
@@ -74,6 +83,32 @@ __device__ inline void env_spawn(const EnvParams &p, const EnvBufs &b, int e, in
     b.moved[e] = 0.0;
 }
 
+// env e stands where it is (frozen, a wreck, or after a refused action): scanned again from the same state
+__device__ inline void env_stand(const EnvBufs &b, int e, int phase)
+{
+    b.phase[e] = phase;
+    b.moved[e] = 0.0;
+}
+
+// a running env e takes its pair of actions [N, 2] f32 (speed, steer): `substeps` car steps from cs, or ENV_BAD_ACTION
+__device__ inline void env_act(const EnvParams &p, const EnvBufs &b, int e, const float *actions, CarState &cs)
+{
+    const double speed = (double)actions[2 * e + 0];
+    double steer = (double)actions[2 * e + 1];
+    if (!(isfinite(speed) && isfinite(steer))) {
+        b.done[e] = ENV_BAD_ACTION;              // the state stays as it is: nothing non-finite reaches car_step
+        env_stand(b, e, ENV_INVALID);
+        return;
+    }
+    if (p.steer_clip > 0.0) steer = fmin(fmax(steer, -p.steer_clip), p.steer_clip);   // PolicySteer::steer
+    const double before = cs.travel_dist;
+    for (int i = 0; i < p.substeps; ++i) car_step(p.P, cs, speed, steer, p.dt);
+    drive_store_state(cs, b.state + (size_t)e * 11);
+    b.tick[e] += 1;
+    b.phase[e] = ENV_STEPPED;
+    b.moved[e] = cs.travel_dist - before;
+}
+
 // phase A.  reset != 0: every env spawns with q = 0 (start_index: the caller's indices or null); otherwise one step
 // of the state machine with actions [N, 2] f32 (speed, steer).
 __global__ __launch_bounds__(64) void env_step_kernel(EnvParams p, EnvBufs b, const float *__restrict__ actions,
@@ -81,45 +116,67 @@ __global__ __launch_bounds__(64) void env_step_kernel(EnvParams p, EnvBufs b, co
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= p.n_envs) return;
-    double *s = b.state + (size_t)e * 11;
     CarState cs;
     if (reset) {
-        env_spawn(p, b, e, 0, start_index, cs);
+        const int idx = env_spawn_index(p, e, 0, start_index);
+        env_spawn(b, e, 0, idx, idx, cs);
     } else if (b.done[e] != ENV_RUNNING) {
         if (p.auto_reset) {
-            env_spawn(p, b, e, b.episode[e] + 1, nullptr, cs);
+            const int q = b.episode[e] + 1, idx = env_spawn_index(p, e, q, nullptr);
+            env_spawn(b, e, q, idx, idx, cs);
         } else {
-            cs = drive_load_state(s);            // frozen: scanned again where it stands
-            b.phase[e] = ENV_FROZEN;
-            b.moved[e] = 0.0;
+            cs = drive_load_state(b.state + (size_t)e * 11);
+            env_stand(b, e, ENV_FROZEN);         // frozen: scanned again where it stands
         }
     } else {
-        cs = drive_load_state(s);
-        const double speed = (double)actions[2 * e + 0];
-        double steer = (double)actions[2 * e + 1];
-        if (!(isfinite(speed) && isfinite(steer))) {
-            b.done[e] = ENV_BAD_ACTION;          // the state stays as it is: nothing non-finite reaches car_step
-            b.phase[e] = ENV_INVALID;
-            b.moved[e] = 0.0;
-        } else {
-            if (p.steer_clip > 0.0) steer = fmin(fmax(steer, -p.steer_clip), p.steer_clip);   // PolicySteer::steer
-            const double before = cs.travel_dist;
-            for (int i = 0; i < p.substeps; ++i) car_step(p.P, cs, speed, steer, p.dt);
-            drive_store_state(cs, s);
-            b.tick[e] += 1;
-            b.phase[e] = ENV_STEPPED;
-            b.moved[e] = cs.travel_dist - before;
-        }
+        cs = drive_load_state(b.state + (size_t)e * 11);
+        env_act(p, b, e, actions, cs);
     }
-    float pose[3];
-    car_scan_pose(cs, p.scan_dist_to_base, pose);
-    b.pose[3 * e + 0] = pose[0];
-    b.pose[3 * e + 1] = pose[1];
-    b.pose[3 * e + 2] = pose[2];
+    car_scan_pose(cs, p.scan_dist_to_base, b.pose + 3 * e);
 }
 
-// phase B: DRIVE_CARS envs per workgroup, one wave each (ROWS = ceil(num_rays / 64)).  reward may be null (a reset
-// has none), aux too.
+// The verdict on env e after this call's scan, in two scalars (a pair in one struct cost race_env_observe_kernel
+// registers across its barrier).  env_done: the done code; `hit` is Car::isCrashed's ballot, `tick` the count that
+// max_ticks bounds (the env's own, or its race's).  A crash outranks a truncation at the same tick.
+__device__ inline int env_done(const EnvParams &p, const EnvBufs &b, int e, bool hit, int tick)
+{
+    const int phase = b.phase[e];
+    int done = b.done[e];
+    const bool stepped = phase == ENV_STEPPED;
+    if (stepped && p.max_ticks > 0 && tick == p.max_ticks) done = ENV_TRUNCATED;
+    if ((stepped || phase == ENV_FRESH) && hit) done = ENV_CRASHED;
+    return done;
+}
+
+// env_reward: the distance of a step that did not crash; crash_reward where this call's action ended the episode with
+// 1 or 3; 0 for fresh envs (their action was ignored, even where the start lies inside the crash margin) and frozen
+// ones.  done: env_done's answer.
+__device__ inline float env_reward(const EnvParams &p, const EnvBufs &b, int e, int done)
+{
+    const int phase = b.phase[e];
+    if (phase == ENV_STEPPED) return done == ENV_CRASHED ? (float)p.crash_reward : (float)b.moved[e];
+    return phase == ENV_INVALID ? (float)p.crash_reward : 0.0f;
+}
+
+// env e's wave writes what the caller sees: the verdict (lane 0), the observation window of its scan `row`, the aux
+// row.  reward may be null (a reset has none), aux too.
+__device__ inline void env_emit(const EnvParams &p, const EnvBufs &b, int e, int lane, const float *row, int done,
+                                float r, float *obs, float *reward, int *done_out, float *aux)
+{
+    if (lane == 0) {
+        b.done[e] = done;
+        done_out[e] = done;
+        if (reward) reward[e] = r;
+    }
+    float *o = obs + (size_t)e * p.obs_count;
+    for (int i = lane; i < p.obs_count; i += 64) {              // lane i of a round stores word i: whole lines
+        const float v = row[p.obs_start + i * p.obs_stride];
+        o[i] = p.obs_scale > 0.0f ? policy_input(v, p.obs_clip, p.obs_scale) : v;
+    }
+    if (aux && lane < 4) aux[4 * (size_t)e + lane] = (float)b.state[(size_t)e * 11 + 3 + lane];
+}
+
+// phase B: DRIVE_CARS envs per workgroup, one wave each (ROWS = ceil(num_rays / 64)).
 template <int ROWS>
 __global__ __launch_bounds__(64 * DRIVE_CARS) void env_observe_kernel(EnvParams p, EnvBufs b, float *__restrict__ obs,
                                                                       float *__restrict__ reward,
@@ -132,27 +189,8 @@ __global__ __launch_bounds__(64 * DRIVE_CARS) void env_observe_kernel(EnvParams 
     const float *row = b.ranges + (size_t)e * p.num_rays;
     float raw[ROWS];
     const bool hit = drive_crashed<ROWS>(row, b.edge, p.num_rays, p.crash_thresh, lane, raw);
-    const int phase = b.phase[e];
-    int done = b.done[e];
-    const bool stepped = phase == ENV_STEPPED;
-    if ((stepped || phase == ENV_FRESH) && hit) done = ENV_CRASHED;
-    else if (stepped && p.max_ticks > 0 && b.tick[e] == p.max_ticks) done = ENV_TRUNCATED;
-    // the distance of a step that did not crash; crash_reward where this call's action ended the episode with 1 or 3;
-    // 0 for fresh envs (their action was ignored, even where the start lies inside the crash margin) and frozen ones
-    float r = 0.0f;
-    if (stepped) r = done == ENV_CRASHED ? (float)p.crash_reward : (float)b.moved[e];
-    else if (phase == ENV_INVALID) r = (float)p.crash_reward;
-    if (lane == 0) {
-        b.done[e] = done;
-        done_out[e] = done;
-        if (reward) reward[e] = r;
-    }
-    float *o = obs + (size_t)e * p.obs_count;
-    for (int i = lane; i < p.obs_count; i += 64) {              // lane i of a round stores word i: whole lines
-        const float v = row[p.obs_start + i * p.obs_stride];
-        o[i] = p.obs_scale > 0.0f ? policy_input(v, p.obs_clip, p.obs_scale) : v;
-    }
-    if (aux && lane < 4) aux[4 * (size_t)e + lane] = (float)b.state[(size_t)e * 11 + 3 + lane];
+    const int done = env_done(p, b, e, hit, b.tick[e]);
+    env_emit(p, b, e, lane, row, done, env_reward(p, b, e, done), obs, reward, done_out, aux);
 }
 
 // ---- the race environment: the episode is a race of p.n_envs / R.group cars; car k of race r is env r P + k
@@ -170,17 +208,7 @@ __device__ inline void race_env_spawn(const EnvParams &p, const EnvBufs &b, cons
 {
     const int r = e / R.group, k = e - r * R.group;
     const int idx = env_spawn_index(p, r, q, given);
-    const double *s = b.starts + ((size_t)idx * R.group + k) * 11;
-    double *o = b.state + (size_t)e * 11;
-#pragma unroll
-    for (int i = 0; i < 11; ++i) o[i] = s[i];
-    cs = drive_load_state(s);
-    b.tick[e] = 0;
-    b.episode[e] = q;
-    b.start_index[e] = idx;
-    b.done[e] = ENV_RUNNING;
-    b.phase[e] = ENV_FRESH;
-    b.moved[e] = 0.0;
+    env_spawn(b, e, q, idx, (size_t)idx * R.group + k, cs);
     if (k == 0) {
         R.tick[r] = 0;
         R.episode[r] = q;
@@ -198,7 +226,6 @@ __global__ __launch_bounds__(64) void race_env_step_kernel(EnvParams p, EnvBufs 
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= p.n_envs) return;
     const int r = e / R.group;
-    double *s = b.state + (size_t)e * 11;
     CarState cs;
     if (reset) {
         race_env_spawn(p, b, R, e, 0, start_index, cs);
@@ -206,43 +233,21 @@ __global__ __launch_bounds__(64) void race_env_step_kernel(EnvParams p, EnvBufs 
         if (p.auto_reset) {
             race_env_spawn(p, b, R, e, b.episode[e] + 1, nullptr, cs);
         } else {
-            cs = drive_load_state(s);            // a finished race stands
-            b.phase[e] = ENV_FROZEN;
-            b.moved[e] = 0.0;
+            cs = drive_load_state(b.state + (size_t)e * 11);
+            env_stand(b, e, ENV_FROZEN);         // a finished race stands
         }
     } else {
         if (e == r * R.group) R.tick[r] += 1;
-        cs = drive_load_state(s);
-        if (b.done[e] != ENV_RUNNING) {          // a wreck: scanned again where it stands, and the others see it
-            b.phase[e] = ENV_FROZEN;
-            b.moved[e] = 0.0;
-        } else {
-            const double speed = (double)actions[2 * e + 0];
-            double steer = (double)actions[2 * e + 1];
-            if (!(isfinite(speed) && isfinite(steer))) {
-                b.done[e] = ENV_BAD_ACTION;
-                b.phase[e] = ENV_INVALID;
-                b.moved[e] = 0.0;
-            } else {
-                if (p.steer_clip > 0.0) steer = fmin(fmax(steer, -p.steer_clip), p.steer_clip);
-                const double before = cs.travel_dist;
-                for (int i = 0; i < p.substeps; ++i) car_step(p.P, cs, speed, steer, p.dt);
-                drive_store_state(cs, s);
-                b.tick[e] += 1;
-                b.phase[e] = ENV_STEPPED;
-                b.moved[e] = cs.travel_dist - before;
-            }
-        }
+        cs = drive_load_state(b.state + (size_t)e * 11);
+        if (b.done[e] != ENV_RUNNING) env_stand(b, e, ENV_FROZEN);     // a wreck: scanned again, and the others see it
+        else env_act(p, b, e, actions, cs);
     }
-    float pose[3];
-    car_scan_pose(cs, p.scan_dist_to_base, pose);
-    b.pose[3 * e + 0] = pose[0];
-    b.pose[3 * e + 1] = pose[1];
-    b.pose[3 * e + 2] = pose[2];
+    car_scan_pose(cs, p.scan_dist_to_base, b.pose + 3 * e);
 }
 
 // phase B of a race env: one workgroup per race, one wave per car (blockDim = 64 P, always P live waves).  Each wave
-// does env_observe_kernel's work for its car, parks the code in LDS, and after the barrier applies the race's rule.
+// reaches its car's verdict as env_observe_kernel does, with the race's tick, parks the code in LDS, and after the
+// barrier applies the race's rule before the emit.
 template <int ROWS>
 __global__ __launch_bounds__(64 * RACE_MAX_GROUP) void race_env_observe_kernel(EnvParams p, EnvBufs b, RaceEnvBufs R,
                                                                                float *__restrict__ obs,
@@ -256,16 +261,10 @@ __global__ __launch_bounds__(64 * RACE_MAX_GROUP) void race_env_observe_kernel(E
     const float *row = b.ranges + (size_t)e * p.num_rays;
     float raw[ROWS];
     const bool hit = drive_crashed<ROWS>(row, b.edge, p.num_rays, p.crash_thresh, lane, raw);
-    const int phase = b.phase[e];
-    int done = b.done[e];
+    int done = env_done(p, b, e, hit, R.tick[r]);
+    const float rw = env_reward(p, b, e, done);                 // (before the race's rule: a survivor's reward stays)
     // a race spawns as a whole: a fresh car means a fresh race, whatever R.over still holds from the last episode
-    const int over0 = phase == ENV_FRESH ? RACE_RUNNING : R.over[r];
-    const bool stepped = phase == ENV_STEPPED;
-    if ((stepped || phase == ENV_FRESH) && hit) done = ENV_CRASHED;
-    else if (stepped && p.max_ticks > 0 && R.tick[r] == p.max_ticks) done = ENV_TRUNCATED;
-    float rw = 0.0f;
-    if (stepped) rw = done == ENV_CRASHED ? (float)p.crash_reward : (float)b.moved[e];
-    else if (phase == ENV_INVALID) rw = (float)p.crash_reward;
+    const int over0 = b.phase[e] == ENV_FRESH ? RACE_RUNNING : R.over[r];
     if (lane == 0) codes[w] = done;
     __syncthreads();
     if (over0 == RACE_RUNNING) {                                // (a finished race that stands: nothing changes)
@@ -279,17 +278,7 @@ __global__ __launch_bounds__(64 * RACE_MAX_GROUP) void race_env_observe_kernel(E
         if (over == RACE_ATTRITION && done == ENV_RUNNING) done = ENV_TRUNCATED;    // it survived: its reward stays
         if (threadIdx.x == 0) R.over[r] = over;
     }
-    if (lane == 0) {
-        b.done[e] = done;
-        done_out[e] = done;
-        if (reward) reward[e] = rw;
-    }
-    float *o = obs + (size_t)e * p.obs_count;
-    for (int i = lane; i < p.obs_count; i += 64) {
-        const float v = row[p.obs_start + i * p.obs_stride];
-        o[i] = p.obs_scale > 0.0f ? policy_input(v, p.obs_clip, p.obs_scale) : v;
-    }
-    if (aux && lane < 4) aux[4 * (size_t)e + lane] = (float)b.state[(size_t)e * 11 + 3 + lane];
+    env_emit(p, b, e, lane, row, done, rw, obs, reward, done_out, aux);
 }
 
 }  // namespace scan
