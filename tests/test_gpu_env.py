@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import consumer_shapes as CS
 import drive_cases as DC
 import env_statement as ES
 import policy_statement as PS
@@ -309,6 +310,36 @@ def test_env_beam_count_limits(B, N):
     stmt = ES.EnvStatement(states, N, B, pub.step_cars, pub.scan, pub.is_crashed, obs_window=win, obs_clip=6.0,
                            obs_scale=3.0, scan_dist_to_base=D_BASE)
     _against_statement(env, stmt, DC.actions(B + N, 3, N), seed=1)
+    m.set_noise(0.0, 0, 0)
+
+
+@pytest.mark.parametrize("B", CS.SIZES)
+def test_env_observe_ballot_at_every_row_count(B):
+    """env_observe_kernel<ROWS> at every ROWS = 1 ... 20 (consumer_shapes.SIZES: 27 beam counts): nine envs — one past
+    a workgroup's eight waves —, a reset and two steps against the statement over the composed public calls, once per
+    beam that decides the crash alone (both ends of the first row, the last beam of the last full row, both ends of the
+    last row) and once with an outline no beam reaches.  The window's last element is beam B - 1; clip, scale and
+    noise on at odd ROWS, the raw window at even ROWS."""
+    rows, N, S = CS.rows_of(B), CS.DRIVE_CARS + 1, 2
+    odd = rows % 2 == 1
+    g = maps.make_maze(256, cell=40, wall=3, p=0.45, seed=11)
+    omap = range_libc.PyOMap(g)
+    m = range_libc.PyRayMarchingGPU(omap, 300)
+    states, _ = support.starts(g, omap.distance_transform(), N, 40 + N, 4.0)
+    cars = RC.CarBatch()
+    std, nseed, base = (0.03, 2, 10 * B) if odd else (0.0, 0, 0)
+    win = (B - 2 * (B // 2) + 1, B // 2, 2)
+    assert win[0] + win[2] * (win[1] - 1) == B - 1
+    kw = dict(obs_window=win, **(dict(obs_clip=6.0, obs_scale=3.0) if odd else {}))
+    for j in CS.one_hot_beams(B) + (None,):
+        edge = CS.one_hot_edge(B, j)
+        m.set_noise(std, nseed, base)
+        env = DriveEnv(m, states, N, B, FOV, edge, THRESH, substeps=S, car=cars, **kw)
+        pub = DC.Composed(m, cars, N, B, edge, S, std, nseed, base)
+        stmt = ES.EnvStatement(states, N, B, pub.step_cars, pub.scan, pub.is_crashed, scan_dist_to_base=D_BASE, **kw)
+        log = _against_statement(env, stmt, DC.actions(B + N, 2, N), seed=1)
+        for _, dn, _, _ in log:                 # beam j alone decides: every env crashes, or none does
+            assert (dn == (ES.RUNNING if j is None else ES.CRASHED)).all(), (B, j, dn)
     m.set_noise(0.0, 0, 0)
 
 

@@ -169,7 +169,8 @@ def test_noise_bresenham_kernels(oracle_mod):
     g, z = load_golden("rm_maze256")
     m = range_libc.PyRayMarchingGPU(range_libc.PyOMap(g), 300)
     m.set_option("variant", 2)
-    check_noise(m, z["poses"], 4.71, 1081, None, SEED_HI, 2 ** 64 - 1000, kernel="occ_lds", what="occ_lds")
+    check_noise(m, z["poses"], 4.71, 1081, None, SEED_HI, 2 ** 64 - 1000, kernel="occ_lds",
+                name="scan::occ_fan_lds_kernel<false>", what="occ_lds")
     m.close()
 
 

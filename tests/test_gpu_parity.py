@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLD, load_golden
+import consumer_shapes as CS
 import support
 from noise_checks import SEED_HI, check_noise
 from oracle import reference
@@ -17,6 +18,7 @@ from pyracecarsimulator_amd import ScanSimulator2D, _lib, maps, range_libc, work
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
 
 SCAN_FOV_720 = 4.71 * 720.0 / 1080.0
+FOLLOWGAP_SIZES = [10, 11, 63, 64, 65, 128, 129, 720, 1081, 1088, 1089, 1217, 1280, 1281, 4097]
 
 
 def _fan(method, poses, fov, B):
@@ -961,6 +963,7 @@ def test_occ_fan_lds_north_star_shape_within_one_cell_of_ray_marching(oracle_mod
         m.set_option("variant", 2)
         poses = z["poses"]
         r, h, s = _fan(m, poses, 4.71, 1081)
+        assert m.last_plan()["name"] == "scan::occ_fan_lds_kernel<true>"
         r0, h0, _ = om.rm_fan(poses, 4.71, 1081, step_coeff=1.0)
         err = np.abs(r - r0) / g.resolution
         within = float((err <= 1.0001).mean())
@@ -1568,7 +1571,7 @@ def test_followgap_kernel_reproduces_reference_build_vectors():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("size", [10, 11, 63, 64, 65, 128, 129, 720, 1081, 1088, 1089, 1217, 1280, 1281, 4097])
+@pytest.mark.parametrize("size", FOLLOWGAP_SIZES + sorted(set(CS.SIZES) - set(FOLLOWGAP_SIZES)))   # ... and every ROWS = 1 ... 20
 def test_followgap_batches_equal_the_oracle(oracle_mod, size):
     from pyracecarsimulator_amd.followgap import PyFollowGap
     rng = np.random.default_rng(size)

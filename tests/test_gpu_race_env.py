@@ -8,6 +8,7 @@ import math
 import numpy as np
 import pytest
 
+import consumer_shapes as CS
 import drive_cases as DC
 import race_env_statement as RES
 import support
@@ -346,6 +347,84 @@ def test_race_env_extents(P, B, R):
     assert env.obs_shape == (R * P, B // 2)
     stmt = _statement(pool, R, B, pub, **kw)
     against_statement(env, stmt, actions, seed=2)
+    m.set_noise(0.0, 0, 0)
+
+
+@pytest.mark.parametrize("B", CS.SIZES)
+def test_race_env_observe_ballot_at_every_row_count(B):
+    """race_env_observe_kernel<ROWS> at every ROWS = 1 ... 20 (consumer_shapes.SIZES): three races of three cars — a
+    workgroup per race, waves 0 ... 2 —, a reset and two steps against the statement over the public calls, once per
+    beam that decides the crash alone and once with an outline no beam reaches; window, clip, scale and noise as in
+    test_gpu_env.py's test of the same name."""
+    rows, R, P, S = CS.rows_of(B), 3, 3, CASE3["S"]
+    odd = rows % 2 == 1
+    g = DC.race_maze()
+    omap = range_libc.PyOMap(g)
+    m = range_libc.PyRayMarchingGPU(omap, MRX)
+    pool = lineups(g, omap.distance_transform(), 3, P, 11 + P)
+    cars = RC.CarBatch()
+    std, nseed, base = (CASE3["std"], CASE3["noise_seed"], CASE3["base"]) if odd else (0.0, 0, 0)
+    win = (B - 2 * (B // 2) + 1, B // 2, 2)
+    kw = dict(min_running=1, auto_reset=True, crash_reward=-1.0, obs_window=win,
+              **(dict(obs_clip=6.0, obs_scale=3.0) if odd else {}))
+    actions = DC.actions(31 + P, 2, R * P)
+    for j in CS.one_hot_beams(B) + (None,):
+        edge = CS.one_hot_edge(B, j)
+        m.set_noise(std, nseed, base)
+        env = RaceEnv(m, pool, R, B, FOV, edge, THRESH, substeps=S, car=cars, **kw)
+        pub = RaceComposed(m, cars, R * P, P, B, edge, S, std, nseed, base)
+        log = against_statement(env, _statement(pool, R, B, pub, **kw), actions, seed=2)
+        for _, dn, _, _ in log:                 # beam j alone decides: every car crashes, or none does
+            assert (dn == (RES.RUNNING if j is None else RES.CRASHED)).all(), (B, j, dn)
+    m.set_noise(0.0, 0, 0)
+
+
+def test_race_env_steer_clip_clamps_the_action():
+    """steer_clip 0.25 and steers of +-0.4 (beyond it) and +-0.2 (within), two races of three cars clear of every crash
+    margin, four steps: the race env equals the statement, whose clamp is np.minimum / np.maximum in f64; the same six
+    cars as races of one equal a DriveEnv twin.  The cars start with 0.2 rad of steer towards their action, so the
+    first step already turns past the clamp: the statement without the clamp ends somewhere else."""
+    R, P, B, T = 2, 3, 100, 4
+    g = DC.race_maze()
+    omap = range_libc.PyOMap(g)
+    m = range_libc.PyRayMarchingGPU(omap, MRX)
+    pool, _ = _race_starts(g, omap.distance_transform(), R, P, 54)
+    steer = np.float32([0.4, -0.4, 0.2, -0.2, -0.4, 0.4])
+    pool[..., 4] = 0.2 * np.sign(steer).reshape(R, P)
+    actions = np.tile(np.stack([np.full(R * P, 3.0, np.float32), steer], -1), (T, 1, 1))
+    cars = RC.CarBatch()
+    edge = support.edge(B)
+    m.set_noise(CASE3["std"], CASE3["noise_seed"], CASE3["base"])
+    kw = dict(min_running=1, auto_reset=False, crash_reward=-1.0, obs_window=(3, 45, 2), steer_clip=0.25)
+    pub = RaceComposed(m, cars, R * P, P, B, edge, CASE3["S"], CASE3["std"], CASE3["noise_seed"], CASE3["base"])
+    env = RaceEnv(m, pool, R, B, FOV, edge, THRESH, substeps=CASE3["S"], car=cars, **kw)
+    stmt = _statement(pool, R, B, pub, **kw)
+    log = against_statement(env, stmt, actions, seed=1, start_index=np.arange(R))
+    assert (log[-1][1] == RES.RUNNING).all()                       # every car drove all four steps
+    # (the car turns at max_steer_vel towards its target and overshoots it by less than one substep's turn)
+    clamped = stmt.states.reshape(R * P, 11)[:, 4]
+    turn = RC.DEFAULT_CAR["max_steer_vel"] * 0.01
+    assert (np.abs(clamped) < 0.25 + turn).all()
+    free = _statement(pool, R, B, pub, **dict(kw, steer_clip=0.0))
+    free.reset(1, np.arange(R))
+    for a in actions:
+        free.step(a)
+    beyond = np.abs(steer) > 0.25
+    assert (np.abs(free.states.reshape(R * P, 11)[beyond, 4]) > 0.4 - turn).all()
+    assert same_bits(free.states.reshape(R * P, 11)[~beyond], stmt.states.reshape(R * P, 11)[~beyond])
+    # P = 1: the race env of one car per race and the DriveEnv, the same clamp
+    flat = pool.reshape(R * P, 11)
+    m.set_noise(CASE3["std"], CASE3["noise_seed"], CASE3["base"])
+    race = RaceEnv(m, flat[:, None, :], R * P, B, FOV, edge, THRESH, substeps=CASE3["S"], car=cars, **kw)
+    kw1 = {k: v for k, v in kw.items() if k != "min_running"}
+    one = DriveEnv(m, flat, R * P, B, FOV, edge, THRESH, substeps=CASE3["S"], car=cars, **kw1)
+    idx = np.arange(R * P)
+    assert same_bits(race.reset(seed=1, start_index=idx)[:, 0], one.reset(seed=1, start_index=idx))
+    for k, a in enumerate(actions):
+        for x, y in zip(race.step(a[:, None, :]), one.step(a)):
+            assert same_bits(x[:, 0], y), k
+        assert same_bits(race.read()["states"][:, 0], one.read()["states"]), k
+    assert np.array_equal(one.read()["states"][:, 4], clamped)       # (alone, a car turns the same way)
     m.set_noise(0.0, 0, 0)
 
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLD, ROOT
+from kernel_instances import _stream_instance   # csrc/launch_plan.h stream_instance, restated once for the tests
 from pyracecarsimulator_amd import _lib, maps, range_libc, workloads
 from pyracecarsimulator_amd.scan_simulator import ScanSimulator2D
 
@@ -379,17 +380,6 @@ def test_launch_plan_survives_zeroed_and_out_of_range_options():
     assert L.rl_plan_fan(_lib.RL_RM_GPU, 256, 2049, 2049, 300.0, 0, C.byref(o), 4096, 1081, 0, 1, C.byref(pl2)) == 0
     assert pl2.as_dict()["kernel"] == "rm_stream_literal" and pl2.crash == 1
     assert L.rl_plan_fan(_lib.RL_RM_GPU, 256, 2049, 2049, 300.0, 0, C.byref(o), 4096, 32, 0, 1, C.byref(pl2)) == -4       # RL_ERR_UNSUPPORTED
-
-
-def _stream_instance(a, c, n, inl, t, s, lit, code):
-    """csrc/launch_plan.h stream_instance, restated: the rm_fan_stream_kernel<AUX, CRASH, NT, INLINE, TILED, SLOTS, LIT,
-    CODE> instances the library compiles."""
-    return (n in (256, 512, 1024) and 1 <= s <= 3 and code in (0, 2)
-            and (not lit or (not a and n == 1024 and inl and t and s <= 2))
-            and (code == 0 or (s == 2 and not a and t and n == 1024))
-            and (s == 1 or (not a and t))
-            and (s != 3 or (not c and n == 1024 and code == 0))
-            and (not inl or n == 1024 or (n == 512 and not c and t and s == 2 and not lit and code == 0)))
 
 
 def test_every_stream_plan_names_a_compiled_instance_and_every_instance_is_reached():
