@@ -952,6 +952,7 @@ static int launch_bl_stream(const FanLaunch &L)
     sp.div_B = make_fastdiv((uint32_t)L.num_rays);
     sp.low_water = h->opt.low_water >= 0 ? h->opt.low_water : 12;
     sp.n_bands = L.pl.bands;
+    sp.div_bands = make_fastdiv((uint32_t)L.pl.bands);
     sp.plain_store = L.plain_store;
     if (L.timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
     if (L.aux)
@@ -1059,8 +1060,9 @@ static int launch_rm_stream_family(const FanLaunch &L)
     sp.div_B = make_fastdiv((uint32_t)L.num_rays);
     sp.low_water = h->opt.low_water >= 0 ? h->opt.low_water : ((pl.record_source != 0 && pl.slots >= 2) ? 20 : 12);
     sp.n_bands = pl.bands;
+    sp.div_bands = make_fastdiv((uint32_t)pl.bands);
     sp.raw_poses = L.d_poses;
-    sp.map = L.m->d_mp;
+    sp.map = L.m->mp;
     sp.k_max = pl.k_max;
     sp.cpp = (uint32_t)((L.num_rays + 63) / 64);
     sp.div_cpp = make_fastdiv(sp.cpp);

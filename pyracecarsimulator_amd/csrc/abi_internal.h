@@ -260,8 +260,7 @@ struct rl_map {
     int bits_stride = 0;
     Stream stream;
     std::atomic<uint64_t> epoch{0};   // bumped by rl_map_update; derived tables rebuild lazily
-    MapParams mp{};
-    DevPtr<MapParams> d_mp;      // device copy (kernels that take the map by pointer)
+    MapParams mp{};              // (kernels take it by value)
     // edge cells (occupied with a free 4-neighbour), the input of every CDDT table of this map: built
     // with the other map tables once a CDDT method exists, so that a table rebuild knows the count on
     // the host without a read-back of its own (rl_map_update synchronises anyway)

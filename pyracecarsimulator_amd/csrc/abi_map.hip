@@ -231,8 +231,6 @@ extern "C" int rl_map_create(const uint8_t *occ, int rows, int cols, float res, 
     p.oy = oy;
     p.wa = -oyaw;                                   // PyOMap: world_angle = -yaw
     host_sincosf(p.wa, p.wa_sin, p.wa_cos);
-    if (m->d_mp.alloc(sizeof(MapParams)) || hipMemcpy(m->d_mp, &m->mp, sizeof(MapParams), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(RL_ERR_NOMEM, "map parameter upload failed");
     *out = own.release();
     return RL_OK;
 }

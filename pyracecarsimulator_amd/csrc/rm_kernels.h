@@ -337,6 +337,14 @@ __device__ __forceinline__ float pose_first_step(const MapParams &m, float gx, f
     const float v = m.dt[(size_t)(int)gy * m.cols + (int)gx];
     return v <= 0.0f ? 0.0f : __builtin_fmaxf(v * coeff, 1.0f);
 }
+// ... with the cell named ahead of the verdict on the pose (pose_record_of's cell0: the pose's own cell, or cell 0 for
+// an origin outside the map): the load goes out as soon as the grid position is known, not behind the heading's sin / cos
+__device__ __forceinline__ float pose_first_step_at(const MapParams &m, size_t cell0, uint32_t flags, float coeff)
+{
+    const float v = m.dt[cell0];
+    if (flags & POSE_INVALID) return PDT_NO_RAY;
+    return v <= 0.0f ? 0.0f : __builtin_fmaxf(v * coeff, 1.0f);
+}
 
 // Tile (ty, tx) -> its rank in the binning order.  `tiles_xs` = tiles_x | stripe << 16.  stripe == 0: row-major.  Else the
 // tile rows are grouped in stripes of `stripe` rows and a stripe is walked COLUMN by column: a band of the sorted pose
@@ -352,16 +360,18 @@ __device__ __forceinline__ uint32_t tile_key(int ty, int tx, int tiles_xs, int n
     return (uint32_t)(y0 * tiles_x + tx * h + (ty - y0));
 }
 
-__device__ __forceinline__ uint32_t pose_record(const MapParams &m, const float *__restrict__ poses,
-                                                int p, int tile_shift, int tiles_x, int n_tiles,
-                                                PoseRec &r, bool walk_outside = false)
+// (the world pose by value: a caller that loads the triple itself — the stream kernel's prologue, which keeps other
+//  loads in flight behind it — and pose_record below state the same record)
+__device__ __forceinline__ uint32_t pose_record_of(const MapParams &m, float xw, float yw, float thw,
+                                                   int tile_shift, int tiles_x, int n_tiles,
+                                                   PoseRec &r, size_t &cell0, bool walk_outside = false)
 {
     float thg;
-    world_to_grid(m, poses[3 * (size_t)p], poses[3 * (size_t)p + 1], poses[3 * (size_t)p + 2], r.gx,
-                  r.gy, thg);
+    world_to_grid(m, xw, yw, thw, r.gx, r.gy, thg);
+    const bool inb = r.gx > -1.0f && r.gx < m.fcols && r.gy > -1.0f && r.gy < m.frows;
+    cell0 = inb ? (size_t)(int)r.gy * m.cols + (int)r.gx : 0;
     det_sincosf(thg, r.st, r.ct);
     const bool fin = (r.ct - r.ct) + (r.st - r.st) == 0.0f;
-    const bool inb = r.gx > -1.0f && r.gx < m.fcols && r.gy > -1.0f && r.gy < m.frows;
     if (walk_outside) {
         // Bresenham keeps walking from an origin outside the map (cells out there are free); only
         // poses that cannot index the grid at all are dropped
@@ -378,6 +388,15 @@ __device__ __forceinline__ uint32_t pose_record(const MapParams &m, const float 
     return tile_key((int)r.gy >> tile_shift, (int)r.gx >> tile_shift, tiles_x, n_tiles);
 }
 
+__device__ __forceinline__ uint32_t pose_record(const MapParams &m, const float *__restrict__ poses,
+                                                int p, int tile_shift, int tiles_x, int n_tiles,
+                                                PoseRec &r, bool walk_outside = false)
+{
+    size_t cell0;
+    return pose_record_of(m, poses[3 * (size_t)p], poses[3 * (size_t)p + 1], poses[3 * (size_t)p + 2], tile_shift,
+                          tiles_x, n_tiles, r, cell0, walk_outside);
+}
+
 // The record of a pose in the UPSTREAM-LITERAL arithmetic (variant 3, stream kernel template argument LIT):
 // RangeMethod::numpy_calc_range's world -> grid with un-fused products and the double-precision sin / cos of the world
 // angle rounded once (the checker's rm_cast_libm; literal_kernels.h::literal_cast).  calc_range(y, x, theta') marches
@@ -385,10 +404,9 @@ __device__ __forceinline__ uint32_t pose_record(const MapParams &m, const float 
 // and the pose's world heading in ct — the direction is computed per RAY at claim time (libm sinf / cosf of
 // theta_p + alpha_j).  A pose the literal march would leave before its first sample (outside the map, non-finite) is
 // flagged like the canonical one: every beam a miss.
-__device__ __forceinline__ uint32_t pose_record_lit(const MapParams &m, const LiteralParams &lp, const float *__restrict__ poses,
-                                                    int p, PoseRec &r)
+__device__ __forceinline__ uint32_t pose_record_lit(const MapParams &m, const LiteralParams &lp, float xw, float yw,
+                                                    float thw, PoseRec &r, size_t &cell0)
 {
-    const float xw = poses[3 * (size_t)p], yw = poses[3 * (size_t)p + 1], thw = poses[3 * (size_t)p + 2];
     float x = (xw - m.ox) * m.inv_res;
     float y = (yw - m.oy) * m.inv_res;
     const float temp = x;
@@ -400,6 +418,7 @@ __device__ __forceinline__ uint32_t pose_record_lit(const MapParams &m, const Li
     r.st = 0.0f;
     const bool fin = (thw - thw) == 0.0f;
     const bool inb = x > -1.0f && x < m.fcols && y > -1.0f && y < m.frows;       // (int) truncation: (-1, 0) is cell 0
+    cell0 = inb ? (size_t)(int)y * m.cols + (int)x : 0;
     if (!(fin && inb)) {
         r.gx = 0.0f; r.gy = 0.0f; r.ct = 0.0f;
         return POSE_INVALID;
@@ -472,8 +491,7 @@ __global__ __launch_bounds__(1024) void pose_bin_kernel(MapParams m, const float
 }
 
 // Up to 8192 poses: the same binning with every lane keeping its (up to 8) pose records in
-// registers between the histogram and the scatter pass — no scratch round trip through memory,
-// and the 8 pose loads of a lane are in flight together.
+// registers between the histogram and the scatter pass — no scratch round trip through memory.
 // KEYS_ONLY: only the tile order is produced (order[slot] = pose id) — no sincos, no records: the
 // march kernel derives the records of the blocks it owns itself (INLINE prologue, pose ids from
 // `order`), so the ~100 instructions per pose of the record leave this one-workgroup critical path.
@@ -487,6 +505,21 @@ __global__ __launch_bounds__(1024) void pose_bin_small_kernel(MapParams m, const
     extern __shared__ uint32_t hist[];          // n_tiles counters, then 1024 scan partials
     uint32_t *part = hist + n_tiles;
     const int tid = threadIdx.x;
+    // KEYS_ONLY: the positions of the lane's poses, requested before anything else — every launch of the march waits
+    // for this one workgroup, and a load guarded per lane is a load hipcc waits for on the spot (eight round trips one
+    // after the other): the index is clamped instead, the rounds past n skipped as a whole
+    float px[8], py[8];
+    if (KEYS_ONLY) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            px[u] = py[u] = 0.0f;
+            if (u * 1024 < n) {
+                const size_t pc = (size_t)min(tid + u * 1024, n - 1);
+                px[u] = poses[3 * pc];
+                py[u] = poses[3 * pc + 1];
+            }
+        }
+    }
     for (int i = tid; i < n_tiles; i += 1024) hist[i] = 0;
     __syncthreads();
     PoseRec r[8];
@@ -498,7 +531,7 @@ __global__ __launch_bounds__(1024) void pose_bin_small_kernel(MapParams m, const
         if (p < n) {
             if (KEYS_ONLY) {
                 float gx, gy, thg;
-                world_to_grid(m, poses[3 * (size_t)p], poses[3 * (size_t)p + 1], 0.0f, gx, gy, thg);
+                world_to_grid(m, px[u], py[u], 0.0f, gx, gy, thg);
                 const bool inb = gx > -1.0f && gx < m.fcols && gy > -1.0f && gy < m.frows;   // (NaN -> false)
                 kf[u] = inb ? tile_key((int)gy >> tile_shift, (int)gx >> tile_shift, tiles_x, n_tiles) : (uint32_t)n_tiles - 1;
             } else {
@@ -1456,8 +1489,10 @@ struct StreamParams {
     FastDiv div_B;           // division by num_rays
     int low_water;           // refill when <= low_water lanes are still marching
     int n_bands;
+    FastDiv div_bands;       // division by n_bands
     const float *raw_poses;  // INLINE only: world poses (x, y, theta); every workgroup derives the
-    const MapParams *map;    //   records of the chunks it owns itself (device copy of the map params)
+    MapParams map;           //   records of the chunks it owns itself (the map params by value: kernel arguments, no
+                             //   round trip to memory in front of the prologue's first load)
     int k_max;               // INLINE only: LDS capacity in block records (BlockRec)
     uint32_t cpp;            // INLINE only: 64-ray blocks per pose, ceil(num_rays / 64) — blocks never straddle a pose
     FastDiv div_cpp;
@@ -1644,6 +1679,10 @@ void rm_fan_stream_kernel(PadMap pm, FanParams f, StreamParams sp, float *__rest
     // naming: bit-identical to the checker's orc_rm_fan_libm.  Records come from the INLINE prologue only.
     static_assert(!LIT || (INLINE && TILED && !AUX), "literal stream form: INLINE records, tiled step map, no diagnostics");
     extern __shared__ __attribute__((aligned(32))) float lds_f[];
+    // (the kernel arguments span seven 64-byte lines; hipcc loads each field where it is first used, one scalar round
+    //  trip after the other in front of the first pose load.  Naming one field of the two lines the first batch of
+    //  loads would not touch — the map's parameters, the grid size — puts their misses under that batch's wait.)
+    asm volatile("" ::"s"(sp.cpp), "s"(gridDim.x));
     const unsigned long long t_entry = sp.dbg ? wall_clock64() : 0ull;   // diagnostics
     uint32_t *q_next = reinterpret_cast<uint32_t *>(lds_f);     // shared slot counter
     // [2 .. STREAM_HDR): CRASH only — poses this workgroup has already reported as crashed
@@ -1666,27 +1705,40 @@ void rm_fan_stream_kernel(PadMap pm, FanParams f, StreamParams sp, float *__rest
     BlockRec *lrec = reinterpret_cast<BlockRec *>(lds_f + ((tables + 7) & ~(size_t)7) + DRAIN_WORDS);   // 32-B aligned
     if (threadIdx.x == 0) *q_next = 0;
     if (CRASH && threadIdx.x < STREAM_HDR - 2) crash_seen[threadIdx.x] = 0xffffffffu;
-    // (the beam directions are the same for every workgroup of every launch with this fan: a table
-    //  of the handle, fan_table_kernel — 1081 sincos per workgroup were 3 % of a cfg2 launch's VALU
-    //  work and the first microsecond of every workgroup's life)
-    for (int j = threadIdx.x; j < f.num_rays; j += NT) {
-        fan_cs[j] = sp.fan_tab[j];
-        if (CRASH) edge_l[j] = cp.edge[j];
+    // ---- prologue: the tables and (INLINE) the block records of this workgroup, into LDS.  Every lane requests what it
+    // needs as early as its address is known and writes LDS only once everything has been requested: the tables' round
+    // trip runs under the band arithmetic and the record chain (order word -> pose triple -> distance-map cell) instead
+    // of in front of them, and the map's parameters are kernel arguments (sp.map), not a fourth trip ahead of the chain.
+    const uint32_t tid = threadIdx.x;
+    // (1) the lane's first PRO_TAB entries of the fan table (and of the car outline), its first of the palette: they
+    // need nothing but kernel arguments.  Loads only, indices clamped instead of guarded.  (The beam directions are the
+    // same for every workgroup of every launch with this fan: a table of the handle, fan_table_kernel — 1081 sincos per
+    // workgroup were 3 % of a cfg2 launch's VALU work and the first microsecond of every workgroup's life.)
+    constexpr int PRO_TAB = 2;
+    float2 t_cs[PRO_TAB];
+    double t_edge[PRO_TAB];
+#pragma unroll
+    for (int u = 0; u < PRO_TAB; ++u) {
+        const uint32_t j = min(tid + (uint32_t)(u * NT), (uint32_t)f.num_rays - 1u);
+        t_cs[u] = sp.fan_tab[j];
+        if (CRASH) t_edge[u] = cp.edge[j];
     }
-    if (CODE) {
-        // (RM_DECODE names the table's LDS address as an immediate: the dynamic LDS block starts at 0 — this kernel has
-        //  no static LDS —, anything else would be a build that silently reads the wrong table)
-        if ((uint32_t)(uintptr_t)lds_f != 0u) __builtin_trap();
-        for (int j = threadIdx.x; j < sp.code_n; j += NT) lds_f[STREAM_HDR + j] = sp.code_tab[j];
-    }
-
+    float t_pal = 0.0f;
+    if (CODE) t_pal = sp.code_tab[min(tid, (uint32_t)sp.code_n - 1u)];
     // ---- which band of the sorted pose list, and which workgroups share it
-    const int nb = sp.n_bands;
-    const int band = (int)(blockIdx.x % (unsigned)nb);
-    const uint32_t g = blockIdx.x / (unsigned)nb;
-    const uint32_t G = ((uint32_t)gridDim.x - (uint32_t)band + (uint32_t)nb - 1) / (uint32_t)nb;
-    const uint32_t seg_lo = (uint32_t)(((long)f.n_poses * band) / nb);
-    const uint32_t seg_hi = (uint32_t)(((long)f.n_poses * (band + 1)) / nb);
+    // (every lane's first load of a pose waits for this arithmetic: the divisions by the band count go through the
+    //  host's reciprocal, sp.div_bands — four of hipcc's 32-bit divisions were a third of the instructions in front of it)
+    const uint32_t nb = (uint32_t)sp.n_bands;
+    const uint32_t g = fast_div(blockIdx.x, sp.div_bands);
+    const uint32_t band = blockIdx.x - g * nb;
+    const uint32_t G = fast_div((uint32_t)gridDim.x - band + nb - 1u, sp.div_bands);
+    // n_poses * b / n_bands: the band's first pose (a product beyond 32 bits takes the long division)
+    auto band_cut = [&](uint32_t b) -> uint32_t {
+        const unsigned long long pb = (unsigned long long)(uint32_t)f.n_poses * b;
+        return (pb >> 32) ? (uint32_t)(pb / nb) : fast_div((uint32_t)pb, sp.div_bands);
+    };
+    const uint32_t seg_lo = band_cut(band);
+    const uint32_t seg_hi = band_cut(band + 1u);
     // the band's rays in blocks of 64: this workgroup owns blocks g, g+G, ... (in runs) — K blocks, 64*K ray
     // slots.  Binned records: the band's rays pose-major, beam-minor, cut every 64 (any num_rays, no
     // padding lanes).  INLINE: cpp blocks per pose, the last one partly filled.
@@ -1712,34 +1764,95 @@ void rm_fan_stream_kernel(PadMap pm, FanParams f, StreamParams sp, float *__rest
     auto blkidx_of = [&](uint32_t i) { return ((own_first + (i >> rl) * own_stride) << rl) + (i & rmask); };
     auto blk_of = [&](uint32_t i) { return blkidx_of(i) << 6; };
     const unsigned lane = threadIdx.x & 63;
+    const MapParams &mp = sp.map;
+    // INLINE, stripe mode: this band's poses (a row stripe of the map) compacted here, in LDS
+    uint32_t *list = reinterpret_cast<uint32_t *>(lrec + sp.k_max);
+    if (INLINE && sp.stripe == 1 && seg_hi > seg_lo)
+        stripe_band_list<NT>(mp, sp.raw_poses, f.n_poses, seg_lo, seg_hi, list,
+                             reinterpret_cast<int *>(list + (seg_hi - seg_lo) + 1));
+    // INLINE: no binning launch (or a keys-only one) in front of the march — each workgroup turns the poses of its own
+    // blocks into records (a few hundred, one per lane) and keeps them in LDS.
+    // block i of the stream -> the band's pose slot and the block's first beam; false: no such block (past K, or the
+    // padding of the band's last run).  Such a lane still walks the chain with pose 0 — every load below is
+    // unconditional, in bounds, and none sits behind a divergent branch — and only its record stays empty.
+    auto blk_pose = [&](uint32_t i, uint32_t &p0, uint32_t &j0) -> bool {
+        const uint32_t b = blkidx_of(i);
+        const bool own = i < K && b < seg_chunks;
+        p0 = own ? fast_div(b, sp.div_cpp) : 0u;
+        j0 = own ? (b - p0 * sp.cpp) << 6 : 0u;
+        return own;
+    };
+    auto blk_pid = [&](bool own, uint32_t p0) -> uint32_t {
+        if (sp.stripe == 1) return own ? list[p0] : 0u;
+        if (sp.stripe == 2) return sp.order[own ? seg_lo + p0 : 0u] & ~POSE_INVALID;
+        return own ? seg_lo + p0 : 0u;
+    };
+    auto blk_rec = [&](bool own, uint32_t j0, uint32_t pid, float xw, float yw, float thw) -> BlockRec {
+        BlockRec br{0.0f, 0.0f, 1.0f, 0.0f, PDT_NO_RAY, 0u, 0u, 0u};
+        PoseRec r;
+        size_t cell0;
+        const uint32_t kf = LIT ? pose_record_lit(mp, sp.lit, xw, yw, thw, r, cell0)
+                                : pose_record_of(mp, xw, yw, thw, 0, 1, 1, r, cell0);
+        const float d0 = pose_first_step_at(mp, cell0, kf, f.step_coeff);
+        if (own) {
+            const uint32_t nvalid = min(64u, (uint32_t)f.num_rays - j0);
+            br.gx = r.gx; br.gy = r.gy; br.ct = r.ct; br.st = r.st;
+            br.d0 = d0;
+            br.obase = (pid * (uint32_t)f.num_rays + j0) << 2;
+            br.j0nv = j0 | (nvalid << 16);
+            br.pose = pid;
+        }
+        return br;
+    };
+    // (wave-uniform: the waves past the workgroup's K blocks hold no record and only copy tables)
+    const bool wave_recs = INLINE && (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid & ~63u)) < K;
+    // (2) the chain's head: the lane's pose id
+    bool own = false;
+    uint32_t p0 = 0u, j0 = 0u, pid = 0u;
+    if (wave_recs) {
+        own = blk_pose(tid, p0, j0);
+        pid = blk_pid(own, p0);
+    }
+    // (3) the pose triple, as soon as the id is back
+    float xw = 0.0f, yw = 0.0f, thw = 0.0f;
+    if (wave_recs) {
+        const float *pp = sp.raw_poses + 3 * (size_t)pid;
+        xw = pp[0]; yw = pp[1]; thw = pp[2];
+    }
+    // (4) the tables to LDS, behind the pose loads; what a fan beyond PRO_TAB * NT beams or a palette beyond NT entries
+    // has left follows in rounds of load and write
+#pragma unroll
+    for (int u = 0; u < PRO_TAB; ++u) {
+        const uint32_t j = tid + (uint32_t)(u * NT);
+        if (j < (uint32_t)f.num_rays) {
+            fan_cs[j] = t_cs[u];
+            if (CRASH) edge_l[j] = t_edge[u];
+        }
+    }
+#pragma unroll 1
+    for (int j = (int)tid + PRO_TAB * NT; j < f.num_rays; j += NT) {
+        fan_cs[j] = sp.fan_tab[j];
+        if (CRASH) edge_l[j] = cp.edge[j];
+    }
+    if (CODE) {
+        // (RM_DECODE names the table's LDS address as an immediate: the dynamic LDS block starts at 0 — this kernel has
+        //  no static LDS —, anything else would be a build that silently reads the wrong table)
+        if ((uint32_t)(uintptr_t)lds_f != 0u) __builtin_trap();
+        if (tid < (uint32_t)sp.code_n) lds_f[STREAM_HDR + tid] = t_pal;
+#pragma unroll 1
+        for (int j = (int)tid + NT; j < sp.code_n; j += NT) lds_f[STREAM_HDR + j] = sp.code_tab[j];
+    }
+    // (5) the record: world -> grid, the heading's sin / cos, the pose's own cell of the distance map
+    if (wave_recs) {
+        const BlockRec br = blk_rec(own, j0, pid, xw, yw, thw);
+        if (tid < K) lrec[tid] = br;
+    }
     if (INLINE) {
-        // no binning launch (or a keys-only one) in front of the march — each workgroup turns the poses
-        // of its own blocks into records (a few hundred, one per lane) and keeps them in LDS
-        const MapParams mp = *sp.map;
-        // stripe mode: this band's poses (a row stripe of the map) compacted here, in LDS
-        uint32_t *list = reinterpret_cast<uint32_t *>(lrec + sp.k_max);
-        if (sp.stripe == 1 && seg_hi > seg_lo)
-            stripe_band_list<NT>(mp, sp.raw_poses, f.n_poses, seg_lo, seg_hi, list,
-                                 reinterpret_cast<int *>(list + (seg_hi - seg_lo) + 1));
-        for (uint32_t i = threadIdx.x; i < K; i += NT) {
-            const uint32_t b = blkidx_of(i);
-            BlockRec br{0.0f, 0.0f, 1.0f, 0.0f, PDT_NO_RAY, 0u, 0u, 0u};
-            if (b < seg_chunks) {
-                const uint32_t p0 = fast_div(b, sp.div_cpp);
-                const uint32_t j0 = (b - p0 * sp.cpp) << 6;
-                const uint32_t nvalid = min(64u, (uint32_t)f.num_rays - j0);
-                const uint32_t pid = sp.stripe == 1 ? list[p0]
-                                   : sp.stripe == 2 ? (sp.order[seg_lo + p0] & ~POSE_INVALID) : seg_lo + p0;
-                PoseRec r;
-                const uint32_t kf = LIT ? pose_record_lit(mp, sp.lit, sp.raw_poses, (int)pid, r)
-                                        : pose_record(mp, sp.raw_poses, (int)pid, 0, 1, 1, r);
-                br.gx = r.gx; br.gy = r.gy; br.ct = r.ct; br.st = r.st;
-                br.d0 = pose_first_step(mp, r.gx, r.gy, kf, f.step_coeff);
-                br.obase = (pid * (uint32_t)f.num_rays + j0) << 2;
-                br.j0nv = j0 | (nvalid << 16);
-                br.pose = pid;
-            }
-            lrec[i] = br;
+        for (uint32_t i = tid + NT; i < K; i += NT) {       // (workgroups with more blocks than lanes: the rest in rounds)
+            own = blk_pose(i, p0, j0);
+            pid = blk_pid(own, p0);
+            const float *pp = sp.raw_poses + 3 * (size_t)pid;
+            lrec[i] = blk_rec(own, j0, pid, pp[0], pp[1], pp[2]);
         }
     }
     __syncthreads();

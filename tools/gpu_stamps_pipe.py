@@ -62,6 +62,10 @@ print("workgroups %d: lifetime p50 %.1f p90 %.1f us; stream dry -> workgroup end
       "first wave done -> last wave done p50 %.1f p90 %.1f us" % (
           len(wg_end), *np.percentile((wg_end - wg_ent) / 100.0, [50, 90]),
           *np.percentile((wg_end - wg_dry) / 100.0, [50, 90, 100]), *np.percentile((wg_end - wg_first_done) / 100.0, [50, 90])))
+wg_pro = (pro.reshape(-1, 16).max(axis=1) - wg_ent) / 100.0
+print("per workgroup: prologue (first entry -> last wave past the barrier) p10 %.2f p50 %.2f p90 %.2f max %.2f us; "
+      "residency (first entry -> last wave end) p10 %.1f p50 %.1f p90 %.1f max %.1f us" % (
+          *np.percentile(wg_pro, [10, 50, 90, 100]), *np.percentile((wg_end - wg_ent) / 100.0, [10, 50, 90, 100])))
 tot_slot_time = (wg_end - wg_ent).sum() / 100.0
 idle = ((wg_end[:, None] - end.reshape(-1, 16))).sum() / 100.0 / 16
 print("wave-slot time held after the wave itself ended (waiting for the workgroup's last wave): %.1f %% of the workgroups' lifetime"
