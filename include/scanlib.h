@@ -675,6 +675,69 @@ int  rl_env_create_race(rl_car *c, rl_method *h, const rl_race_env_params *p, co
                         const double *starts_mp11, int n_starts, rl_env **out);
 int  rl_env_read_races(rl_env *e, int *race_ticks, int *race_episodes, int *race_start_index, int *race_over);
 
+/* ---- track progress ----------------------------------------------------------------------------
+ * Where every car of an environment is on a track, how far it came along it, its laps, a lookahead waypoint in the
+ * car's frame and, in a race, its position: the global path of the reference's driver (paths/wp-u.csv,
+ * scripts/mcts_driver.py:139-169) for every env on the device at every reset and step.  Opt-in: an env without a track
+ * runs exactly the launches of the two sections above; with one, a single kernel (track_kernel, track_kernels.h) is
+ * enqueued behind phase B on the same stream.  tests/track_statement.py restates this section line by line.
+ * Every f64 operation below is separately rounded (the library is built with -ffp-contract=off).
+ *
+ * Track.  W points (x_i, y_i) f64, closed or open.  S segments: S = W when closed, segment i running from point i to
+ *   point (i+1) mod W; S = W - 1 when open.  Per segment: dx_i = x_(i+1) - x_i, dy_i = y_(i+1) - y_i,
+ *   q_i = dx_i*dx_i + dy_i*dy_i, len_i = sqrt(q_i); cum_0 = 0, cum_(i+1) = cum_i + len_i summed in ascending order;
+ *   L = cum_S.  Refused (RL_ERR_INVALID): W < 2, W < 3 when closed, W > 65536, a non-finite coordinate, a segment
+ *   with q_i == 0 (or not finite).
+ * Projection of a car at (cx, cy, th) = state[0..2] onto segment i:
+ *   ax = cx - x_i, ay = cy - y_i;  u = ax*dx_i + ay*dy_i;  t = fmin(fmax(u / q_i, 0), 1);
+ *   ex = ax - t*dx_i, ey = ay - t*dy_i;  d2 = ex*ex + ey*ey.
+ * Nearest segment: the candidate with the smallest d2, the lowest index i among equals.  Candidates: every segment
+ *   for a fresh (just spawned) env or when window == 0; otherwise the segments within `window` of the previous
+ *   nearest segment p: (p - window + m) mod S for m <= 2 window on a closed track, max(p - window, 0) ..
+ *   min(p + window, S - 1) on an open one; all segments once 2*window + 1 >= S.
+ * From the nearest segment i and its t:
+ *   s = cum_i + t*len_i;
+ *   lateral = (dx_i*ay - dy_i*ax) / len_i, left of the direction of travel positive;
+ *   with hx = cos th, hy = sin th: heading_err = atan2(dx_i*hy - dy_i*hx, dx_i*hx + dy_i*hy).
+ * Progress.  Fresh env: D = 0, progress = 0, laps = 0, s_prev = s.  Stepped env: D = s - s_prev; on a closed track
+ *   with half = 0.5*L: D < -half gives D += L and laps += 1; D > half gives D -= L and laps -= 1; then
+ *   progress += D and s_prev = s.  Frozen envs, wrecks and refused actions: D = 0, nothing else changes (their rank
+ *   is still counted anew).  laps is the signed count of start-line (s = 0) crossings since the spawn.
+ * Goal waypoint, lookahead l > 0 (findBestPoint's rule).  Over the candidate waypoints j in order:
+ *   dist_j = sqrt((x_j-cx)*(x_j-cx) + (y_j-cy)*(y_j-cy)), g_j = fabs(l - dist_j); the best starts at 2l and j wins on
+ *   g_j < best, strictly: the first candidate among equals.  No winner: goal = -1, goal point (0, 0).  Candidates:
+ *   goal_span == 0: all W waypoints in index order (the reference's rule); goal_span > 0: the waypoints
+ *   (i + 1 + m) mod W for m < goal_span, forward of the nearest segment i, in order of m (m < W: a second visit cannot
+ *   win); an open track stops at W - 1.  In the car's frame, with rx = x_g - cx, ry = y_g - cy:
+ *   gx = hx*rx + hy*ry, gy = hx*ry - hy*rx.
+ * Race order.  An env of rl_env_create reads offset = 0 and rank = 0.  At a race's spawn offset[e] = s_e - s_(car 0 of
+ *   the race), wrapped on a closed track by the same +-L rule as D (no lap is counted).  race_dist[e] = offset[e] +
+ *   progress[e].  rank[e] = the number of cars k' of the race with a larger race_dist, or an equal one and k' < k.
+ *   Wrecks keep their race_dist and are ranked with the rest.
+ * What the caller sees, per env: an f32 row [8] = (D, s, lateral, heading_err, gx, gy, progress, race_dist), each cast
+ *   from f64, and an int row [4] = (segment, goal, laps, rank).
+ * Reward.  reward_mode 0 leaves the env's reward alone; reward_mode 1 writes (float)D exactly where the env's rule
+ *   writes (float)moved: a stepped env that did not crash (a survivor of a race that ended included).  Crash, refused,
+ *   fresh and frozen rewards stay.
+ *
+ * rl_track_create copies the points and builds the table on `device`; rl_track_read gives cum [S + 1] and L back.
+ * rl_env_attach_track: t is borrowed (keep it alive as long as it is attached); a null t detaches (p is not read); the
+ * env needs a reset afterwards.  rl_env_read_track: host pointers, each optional; it waits like rl_env_read.
+ * rl_env_read_track_device: device pointers, each optional; it only enqueues the copies on the given stream (the one
+ * of the step before it, or one ordered behind it).
+ * Errors (RL_ERR_INVALID, nothing launched, the env usable as before): null params with a track, window or goal_span
+ * < 0 or > 65536, reward_mode outside {0, 1}, lookahead not finite or <= 0, a track on another device than the env, a
+ * track read on an env with no track attached or before a reset.  Out of scope: off-track termination, multi-device
+ * handles, graph capture.                                                                                         */
+typedef struct rl_track rl_track;
+int  rl_track_create(int device, const double *xy_w2, int n_points, int closed, rl_track **out);
+void rl_track_destroy(rl_track *t);
+int  rl_track_read(rl_track *t, double *cum_s_plus_1_or_null, double *length_or_null);
+typedef struct rl_track_params { int window, goal_span, reward_mode; double lookahead; } rl_track_params;
+int  rl_env_attach_track(rl_env *e, rl_track *t, const rl_track_params *p);
+int  rl_env_read_track(rl_env *e, float *rows_n8, int *ints_n4);
+int  rl_env_read_track_device(rl_env *e, float *d_rows_n8, int *d_ints_n4, void *hip_stream);
+
 /* ---- the MCTS planner ----------------------------------------------------------------------------
  * scripts/mcts.py's tree search (MCTS.mcts / mctsIteration / act / rollout, :109-245) for K independent trees in
  * lock step on one device: every iteration adds exactly one node to every tree, so each iteration is one batched

@@ -11,6 +11,7 @@ from .policy import Policy                           # noqa: F401
 from .mcts import MCTS                               # noqa: F401
 from .particle_filter import ParticleFilter          # noqa: F401
 from .env import DriveEnv, RaceEnv                   # noqa: F401
+from .track import Track                             # noqa: F401
 
 __all__ = ["maps", "racecar", "range_libc", "ScanSimulator2D", "RacecarSimulator", "Policy", "MCTS",
-           "ParticleFilter", "DriveEnv", "RaceEnv"]
+           "ParticleFilter", "DriveEnv", "RaceEnv", "Track"]

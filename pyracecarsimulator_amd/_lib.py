@@ -76,6 +76,11 @@ class RaceEnvParams(C.Structure):
     _fields_ = [("env", EnvParams), ("group", C.c_int), ("min_running", C.c_int)]
 
 
+class TrackParams(C.Structure):
+    """rl_track_params (include/scanlib.h)."""
+    _fields_ = [("window", C.c_int), ("goal_span", C.c_int), ("reward_mode", C.c_int), ("lookahead", C.c_double)]
+
+
 RL_MCTS_FG, RL_MCTS_NN, RL_MCTS_RANDOM = 0, 1, 2
 
 KERNEL_IDS = {0: "none", 1: "rm_chunk", 2: "rm_stream", 3: "occ_lds", 4: "bl_stream", 5: "bl_lds", 6: "lut_lds",
@@ -185,6 +190,12 @@ SYMBOLS = {
     "rl_env_create_race": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RaceEnvParams), f64p, f64p, C.c_int,
                                      C.POINTER(C.c_void_p)]),
     "rl_env_read_races": (C.c_int, [C.c_void_p, i32p, i32p, i32p, i32p]),
+    "rl_track_create": (C.c_int, [C.c_int, f64p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "rl_track_destroy": (None, [C.c_void_p]),
+    "rl_track_read": (C.c_int, [C.c_void_p, f64p, f64p]),
+    "rl_env_attach_track": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(TrackParams)]),
+    "rl_env_read_track": (C.c_int, [C.c_void_p, f32p, i32p]),
+    "rl_env_read_track_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rl_mcts_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MctsParams), f64p,
                                  C.POINTER(C.c_void_p)]),
     "rl_mcts_destroy": (None, [C.c_void_p]),

@@ -9,6 +9,7 @@
 #include "consumer_kernels.h"
 #include "drive_kernels.h"
 #include "env_kernels.h"
+#include "track_kernels.h"
 #include "mcts_kernels.h"
 #include "policy_kernels.h"
 #include "probe_kernels.h"
@@ -766,6 +767,13 @@ typedef void (*race_env_observe_fn)(EnvParams, EnvBufs, RaceEnvBufs, float *, fl
 static const std::array<race_env_observe_fn, FG_ROWS> race_env_observe_table =
     rows_table<race_env_observe_fn>([](auto rows) { return race_env_observe_kernel<rows>; });
 
+// a track (rl_track_create): the table of track_kernels.h in one device block, and the host's copy of cum
+struct rl_track {
+    int device = 0, W = 0, S = 0, closed = 0;
+    DevPtr<double> table;          // x, y [W]; dx, dy, q, len [S]; cum [S + 1]
+    std::vector<double> cum;       // [S + 1]; L = cum[S]
+};
+
 struct rl_env {
     rl_car *c = nullptr;
     rl_method *h = nullptr;
@@ -782,6 +790,12 @@ struct rl_env {
     // the host forms' staging: actions and start indices in, observation, reward, done and aux out
     DevPtr<float> h_actions, h_obs, h_reward, h_aux;
     DevPtr<int> h_sidx, h_done;
+    // track progress (rl_env_attach_track): the borrowed track, its options and the per-env rows
+    rl_track *track = nullptr;
+    TrackParams tp{};
+    DevPtr<double> track_st;
+    DevPtr<float> track_rows;
+    DevPtr<int> track_ints;
     bool ready = false;            // reset done and no launch failed since (read and written under mu only)
     bool foreign = false;          // the last launches went to a caller's stream: a host form waits for the device first
     uint64_t k = 0;                // calls since the last reset (the reset is slot 0)
@@ -913,7 +927,33 @@ extern "C" int rl_env_create_race(rl_car *c, rl_method *h, const rl_race_env_par
     return env_create(c, h, &params->env, edge, starts_mp11, n_starts, P, params->min_running, out);
 }
 
-// one call's launches on st: phase A (reset: the spawn), the scan at slot k, phase B.  lp: the call's Loop, owner e.
+static TrackTable track_table(const rl_track *t)
+{
+    const double *p = t->table;
+    const size_t W = t->W, S = t->S;
+    return TrackTable{p, p + W, p + 2 * W, p + 2 * W + S, p + 2 * W + 2 * S, p + 2 * W + 3 * S, p + 2 * W + 4 * S,
+                      t->W, t->S, t->closed, t->cum[S]};
+}
+
+// the track kernel of an env with a track, behind phase B on st: it reads this call's phase, done and states
+static int track_launch(rl_env *e, float *d_reward, hipStream_t st)
+{
+    if (!e->track) return RL_OK;
+    const int N = e->prm.n_envs;
+    const TrackTable T = track_table(e->track);
+    const TrackBufs tb{e->track_st, e->track_rows, e->track_ints};
+    if (e->group > 0)
+        hipLaunchKernelGGL(track_kernel<true>, dim3(N / e->group), dim3(64 * e->group), 0, st, N, T, e->tp, tb, e->state,
+                           e->phase, e->done, d_reward);
+    else
+        hipLaunchKernelGGL(track_kernel<false>, dim3((N + DRIVE_CARS - 1) / DRIVE_CARS), dim3(64 * DRIVE_CARS), 0, st, N, T,
+                           e->tp, tb, e->state, e->phase, e->done, d_reward);
+    if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "track_kernel launch failed");
+    return RL_OK;
+}
+
+// one call's launches on st: phase A (reset: the spawn), the scan at slot k, phase B, then the track kernel where a
+// track is attached.  lp: the call's Loop, owner e.
 static int env_launch(rl_env *e, const Loop &lp, bool reset, uint64_t k, const float *d_actions, const int *d_start_index,
                       float *d_obs, float *d_reward, int *d_done, float *d_aux, hipStream_t st)
 {
@@ -926,15 +966,17 @@ static int env_launch(rl_env *e, const Loop &lp, bool reset, uint64_t k, const f
                            d_start_index, reset ? 1 : 0);
         if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "race_env_step_kernel launch failed");
         const LoopScan scan{e->pose, N, e->prm.fov, B, e->ranges, nullptr, e->group, e->state, &e->outline};
-        return lp.scan_then(scan, off, race_env_observe_table, e->group, "race_env_observe_kernel", st, e->ep, b, rb, d_obs,
-                            d_reward, d_done, d_aux);
+        const int rc = lp.scan_then(scan, off, race_env_observe_table, e->group, "race_env_observe_kernel", st, e->ep, b, rb,
+                                    d_obs, d_reward, d_done, d_aux);
+        return rc ? rc : track_launch(e, d_reward, st);
     }
     hipLaunchKernelGGL(env_step_kernel, dim3((N + 63) / 64), dim3(64), 0, st, e->ep, b, d_actions, d_start_index,
                        reset ? 1 : 0);
     if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "env_step_kernel launch failed");
     const LoopScan scan{e->pose, N, e->prm.fov, B, e->ranges, nullptr, 0, nullptr, nullptr};
-    return lp.scan_then(scan, off, env_observe_table, DRIVE_CARS, "env_observe_kernel",
-                        st, e->ep, b, d_obs, d_reward, d_done, d_aux);
+    const int rc = lp.scan_then(scan, off, env_observe_table, DRIVE_CARS, "env_observe_kernel",
+                                st, e->ep, b, d_obs, d_reward, d_done, d_aux);
+    return rc ? rc : track_launch(e, d_reward, st);
 }
 
 // a host form after launches on a caller's stream: c's stream is not ordered behind that one
@@ -1083,6 +1125,121 @@ extern "C" int rl_env_read_races(rl_env *e, int *race_ticks, int *race_episodes,
         (rc = hc.down(race_start_index, e->race_start_index, R)) || (rc = hc.down(race_over, e->race_over, R)))
         return rc;
     return hc.finish();
+}
+
+// ---------------------------------------------------------------- track progress (track_kernels.h)
+extern "C" void rl_track_destroy(rl_track *t)
+{
+    if (!t) return;
+    (void)hipSetDevice(t->device);
+    (void)hipDeviceSynchronize();       // (an env's last track kernel may still read the table)
+    delete t;
+}
+
+extern "C" int rl_track_create(int device, const double *xy_w2, int n_points, int closed, rl_track **out)
+{
+    if (!xy_w2 || !out) return fail(RL_ERR_INVALID, "rl_track_create: null pointer");
+    const int W = n_points, S = closed ? W : W - 1;
+    if (W < (closed ? 3 : 2) || W > 65536)
+        return fail(RL_ERR_INVALID, "rl_track_create: n_points must lie in [%d, 65536] (got %d)", closed ? 3 : 2, W);
+    for (int i = 0; i < 2 * W; ++i)
+        if (!std::isfinite(xy_w2[i])) return fail(RL_ERR_INVALID, "rl_track_create: point %d holds a non-finite value", i / 2);
+    int rc = check_device(device);
+    if (rc) return rc;
+    // x, y [W]; dx, dy, q, len [S]; cum [S + 1]
+    std::vector<double> tab(2 * (size_t)W + 4 * (size_t)S + S + 1);
+    double *x = tab.data(), *y = x + W, *dx = y + W, *dy = dx + S, *q = dy + S, *len = q + S, *cum = len + S;
+    for (int i = 0; i < W; ++i) x[i] = xy_w2[2 * i], y[i] = xy_w2[2 * i + 1];
+    cum[0] = 0.0;
+    for (int i = 0; i < S; ++i) {
+        const int j = i + 1 == W ? 0 : i + 1;
+        dx[i] = x[j] - x[i];
+        dy[i] = y[j] - y[i];
+        const double a = dx[i] * dx[i], b = dy[i] * dy[i];
+        q[i] = a + b;
+        if (q[i] == 0.0) return fail(RL_ERR_INVALID, "rl_track_create: segment %d has no length", i);
+        if (!std::isfinite(q[i])) return fail(RL_ERR_INVALID, "rl_track_create: segment %d is too long for f64", i);
+        len[i] = std::sqrt(q[i]);
+        cum[i + 1] = cum[i] + len[i];
+    }
+    std::unique_ptr<rl_track, decltype(&rl_track_destroy)> t(new (std::nothrow) rl_track(), rl_track_destroy);
+    if (!t) return fail(RL_ERR_NOMEM, "out of host memory");
+    t->device = device;
+    t->W = W;
+    t->S = S;
+    t->closed = closed != 0;
+    t->cum.assign(cum, cum + S + 1);
+    HIPCHK(hipSetDevice(device));
+    if ((rc = t->table.alloc(tab.size() * sizeof(double)))) return rc;
+    HIPCHK(hipMemcpy(t->table, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    *out = t.release();
+    return RL_OK;
+}
+
+extern "C" int rl_track_read(rl_track *t, double *cum_s_plus_1_or_null, double *length_or_null)
+{
+    if (!t) return fail(RL_ERR_INVALID, "rl_track_read: null pointer");
+    if (cum_s_plus_1_or_null) std::copy(t->cum.begin(), t->cum.end(), cum_s_plus_1_or_null);
+    if (length_or_null) *length_or_null = t->cum.back();
+    return RL_OK;
+}
+
+extern "C" int rl_env_attach_track(rl_env *e, rl_track *t, const rl_track_params *p)
+{
+    if (!e) return fail(RL_ERR_INVALID, "rl_env_attach_track: null pointer");
+    std::scoped_lock lk(e->mu, e->c->mu);
+    if (t) {
+        if (!p) return fail(RL_ERR_INVALID, "rl_env_attach_track: null params");
+        if (p->window < 0 || p->window > 65536 || p->goal_span < 0 || p->goal_span > 65536)
+            return fail(RL_ERR_INVALID, "rl_env_attach_track: window and goal_span must lie in [0, 65536] (got %d, %d)",
+                        p->window, p->goal_span);
+        if (p->reward_mode != 0 && p->reward_mode != 1)
+            return fail(RL_ERR_INVALID, "rl_env_attach_track: reward_mode must be 0 or 1 (got %d)", p->reward_mode);
+        if (!std::isfinite(p->lookahead) || !(p->lookahead > 0.0))
+            return fail(RL_ERR_INVALID, "rl_env_attach_track: lookahead must be finite and > 0");
+        if (t->device != e->device)
+            return fail(RL_ERR_INVALID, "rl_env_attach_track: track (device %d) and env (device %d) must share one device",
+                        t->device, e->device);
+        HIPCHK(hipSetDevice(e->device));
+        const size_t N = e->prm.n_envs;
+        int rc;
+        if ((rc = e->track_st.ensure(N * 3)) || (rc = e->track_rows.ensure(N * 8)) || (rc = e->track_ints.ensure(N * 4)))
+            return rc;
+        e->tp = TrackParams{p->window, p->goal_span, p->reward_mode, e->group, p->lookahead};
+    }
+    e->track = t;
+    e->ready = false;                   // the rows of the new track start at the next reset
+    return RL_OK;
+}
+
+extern "C" int rl_env_read_track(rl_env *e, float *rows_n8, int *ints_n4)
+{
+    if (!e) return fail(RL_ERR_INVALID, "rl_env_read_track: null pointer");
+    std::scoped_lock lk(e->mu, e->c->mu);
+    if (!e->track) return fail(RL_ERR_INVALID, "rl_env_read_track: no track attached (rl_env_attach_track)");
+    if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_read_track: reset the environment first (rl_env_reset)");
+    HIPCHK(hipSetDevice(e->device));
+    int rc = env_settle(e);
+    if (rc) return rc;
+    HostCall hc(e->c->stream);
+    const size_t N = e->prm.n_envs;
+    if ((rc = hc.down(rows_n8, e->track_rows, N * 8)) || (rc = hc.down(ints_n4, e->track_ints, N * 4))) return rc;
+    return hc.finish();
+}
+
+extern "C" int rl_env_read_track_device(rl_env *e, float *d_rows_n8, int *d_ints_n4, void *hip_stream)
+{
+    if (!e) return fail(RL_ERR_INVALID, "rl_env_read_track_device: null pointer");
+    std::scoped_lock lk(e->mu, e->c->mu);
+    if (!e->track) return fail(RL_ERR_INVALID, "rl_env_read_track_device: no track attached (rl_env_attach_track)");
+    if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_read_track_device: reset the environment first (rl_env_reset)");
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (st != (hipStream_t)e->c->stream) e->foreign = true;
+    const size_t N = e->prm.n_envs;
+    if (d_rows_n8) HIPCHK(hipMemcpyAsync(d_rows_n8, e->track_rows, N * 8 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (d_ints_n4) HIPCHK(hipMemcpyAsync(d_ints_n4, e->track_ints, N * 4 * sizeof(int), hipMemcpyDeviceToDevice, st));
+    return RL_OK;
 }
 
 // ---------------------------------------------------------------- diagnostics: HBM stream probe

@@ -33,6 +33,8 @@ BOUNDS = [
     # the race environment: the same lane and wave with the race's rule around them
     ("scan::race_env_step_kernel", {"scratch": 0}),
     ("scan::race_env_observe_kernel<", {"scratch": 0}),
+    # track progress: the f64 search, the wave's (value, index) minimum and lane 0's trigonometry spill nothing
+    ("scan::track_kernel<", {"scratch": 0}),
     # the policy network: the micro-tile accumulators stay in registers
     ("scan::policy_mlp_kernel", {"scratch": 0}),
     # the MCTS planner: the descent, the act wave, the backup's pairwise sum and the walks keep nothing in scratch

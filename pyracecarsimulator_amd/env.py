@@ -21,6 +21,10 @@ action, 0 for an env that was re-spawned by this call or that stands frozen.
 ``RaceEnv`` is the same environment with a race of P cars as the episode (``rl_env_create_race``): the cars of a race
 see each other in every scan, a finished car stays in the map as a wreck, and the race spawns and re-spawns as a whole
 once fewer than ``min_running`` of its cars run or ``max_ticks`` is reached.
+
+Both take a ``track`` (``track.Track``): every reset and step then also places each car on the track, on the device,
+and ``track_state()`` reads the result; ``progress_reward=True`` pays the progress along the track instead of the
+distance travelled.
 """
 from __future__ import annotations
 
@@ -30,6 +34,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import f32p, f64p, i32p
+from .track import Track, track_env_args
 
 
 def env_args(n_envs, num_rays, starts, edge, substeps=1, obs_window=None, obs_clip=0, obs_scale=0, max_ticks=0,
@@ -99,14 +104,23 @@ class DriveEnv(_lib.Handle):
     (``racecar.edge_distances``).  ``obs_window`` (start, count, stride) picks the beams of the observation (None:
     all); ``obs_scale`` > 0 gives them in the policy network's input form, (r <= obs_clip) ? r / obs_scale : 1.
     ``car``: a ``CarBatch`` on the method's device (None: one with the default parameters).  The handles are
-    borrowed: the env keeps them alive."""
+    borrowed: the env keeps them alive.
+
+    ``track``: a ``Track`` on the method's device (None: no track work at all).  ``track_window`` > 0 searches the
+    nearest segment only within that many segments of the last one (0: all, every step), ``lookahead`` (m) and
+    ``goal_span`` pick the goal waypoint (0: among all waypoints, the reference's rule; > 0: among that many forward of
+    the car), ``progress_reward`` pays the step's progress along the track where the env pays the distance travelled."""
     _destroy = "rl_env_destroy"
 
     def __init__(self, method, starts, n_envs, num_rays, fov, edge, crash_thresh, *, substeps=1, obs_window=None,
                  obs_clip=0, obs_scale=0, max_ticks=0, auto_reset=True, steer_clip=0, crash_reward=0, car=None,
-                 dt=0.01, scan_dist_to_base=0.275):
+                 dt=0.01, scan_dist_to_base=0.275, track=None, track_window=0, lookahead=1.5, goal_span=0,
+                 progress_reward=False):
         st, ed, win = env_args(n_envs, num_rays, starts, edge, substeps, obs_window, obs_clip, obs_scale, max_ticks,
                                steer_clip, crash_reward, dt)
+        tp = track_env_args(track_window, lookahead, goal_span, progress_reward)
+        if track is not None and not isinstance(track, Track):
+            raise ValueError("track must be a Track (or None)")
         if car is None:
             from .racecar import CarBatch
             car = CarBatch(device=self._method_device(method))
@@ -126,6 +140,9 @@ class DriveEnv(_lib.Handle):
         self._h = C.c_void_p()
         self._create(car, method, p, ed, st)
         self.device = self._method_device(method)
+        self.track = None
+        if track is not None:
+            self.attach_track(track, tp)
 
     def _create(self, car, method, p, ed, st):
         _lib.check(_lib.lib().rl_env_create(car._h, method._h, C.byref(p), ed.ctypes.data_as(f64p),
@@ -144,6 +161,38 @@ class DriveEnv(_lib.Handle):
     @property
     def obs_shape(self):
         return (self._n, self._count)
+
+    # -- track progress -----------------------------------------------------------------
+    def attach_track(self, track, params=None, **kw):
+        """Attach ``track`` (None: detach) with ``params`` (``track_env_args``'s result) or its keywords.  The env needs
+        a ``reset`` afterwards."""
+        tp = params if params is not None else track_env_args(**kw)
+        _lib.check(_lib.lib().rl_env_attach_track(self._h, track._h if track is not None else None, C.byref(tp)))
+        self.track = track            # (borrowed by the library: kept alive here)
+        self._track_torch = None
+
+    def track_state(self, on_device=False):
+        """Where every env is on its track after the last reset or step: a dict of ``rows`` (n_envs, 8) float32 =
+        (delta, s, lateral, heading_err, gx, gy, progress, race_dist) and ``segment``, ``goal``, ``laps``, ``rank`` int32
+        (n_envs,).  NumPy by default (waits for the device); ``on_device=True``: the env's own torch tensors, filled on
+        the current stream and overwritten by the next call."""
+        if on_device:
+            import torch
+            if getattr(self, "_track_torch", None) is None:
+                dev = torch.device("cuda", self.device)
+                self._track_torch = (torch.empty((self._n, 8), dtype=torch.float32, device=dev),
+                                     torch.empty((self._n, 4), dtype=torch.int32, device=dev))
+            rows, ints = self._track_torch
+            _lib.check(_lib.lib().rl_env_read_track_device(self._h, C.c_void_p(rows.data_ptr()),
+                                                           C.c_void_p(ints.data_ptr()), C.c_void_p(self._stream())))
+        else:
+            rows, ints = np.empty((self._n, 8), np.float32), np.empty((self._n, 4), np.int32)
+            _lib.check(_lib.lib().rl_env_read_track(self._h, rows.ctypes.data_as(f32p), ints.ctypes.data_as(i32p)))
+        return self._track_dict(rows, ints)
+
+    @staticmethod
+    def _track_dict(rows, ints):
+        return dict(rows=rows, segment=ints[:, 0], goal=ints[:, 1], laps=ints[:, 2], rank=ints[:, 3])
 
     # -- the device form's buffers ----------------------------------------------------
     def _tensors(self):
@@ -295,6 +344,10 @@ class RaceEnv(DriveEnv):
         if tuple(actions.shape) == (self._races, self._group, 2):
             actions = actions.reshape(self._n, 2)
         return tuple(self._rows(x) for x in super().step(actions, aux))
+
+    def track_state(self, on_device=False):
+        """``DriveEnv.track_state`` as (n_races, P, ...); ``rank`` 0 leads its race."""
+        return {k: self._rows(v) for k, v in super().track_state(on_device).items()}
 
     def read(self):
         """``DriveEnv.read``'s per-car arrays as (n_races, P, ...), and the races' counters ``race_ticks``,

@@ -251,7 +251,8 @@ class RacecarSimulator:
         """A ``DriveEnv`` of ``n_envs`` cars on this simulator's range method, car, fan, edge table, ttc_thresh and
         scan_dist_to_base, spawning from ``starts`` float64 (M, 11): the tick of ``driveFollowGapMany`` with the (speed,
         steer) of every step supplied by the caller.  ``kw``: ``DriveEnv``'s keyword arguments (substeps, obs_window,
-        obs_clip, obs_scale, max_ticks, auto_reset, steer_clip, crash_reward, dt)."""
+        obs_clip, obs_scale, max_ticks, auto_reset, steer_clip, crash_reward, dt, and the track keywords track,
+        track_window, lookahead, goal_span, progress_reward)."""
         from .env import DriveEnv
         kw.setdefault("car", self.car)
         kw.setdefault("scan_dist_to_base", self.scan_dist_to_base)
@@ -262,7 +263,7 @@ class RacecarSimulator:
         """A ``RaceEnv`` of ``n_races`` races on this simulator's range method (RM or RMGPU), car, fan, edge table,
         ttc_thresh and scan_dist_to_base, spawning from the line-ups ``starts`` float64 (M, P, 11): the tick of
         ``raceFollowGapMany`` with the (speed, steer) of every car supplied by the caller.  ``kw``: ``RaceEnv``'s keyword
-        arguments (min_running and ``DriveEnv``'s)."""
+        arguments (min_running and ``DriveEnv``'s, the track keywords included)."""
         from .env import RaceEnv
         kw.setdefault("car", self.car)
         kw.setdefault("scan_dist_to_base", self.scan_dist_to_base)
