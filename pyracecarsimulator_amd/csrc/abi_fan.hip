@@ -133,68 +133,72 @@ extern "C" int rl_set_noise(rl_method *h, float std, uint64_t seed, uint64_t ray
 }
 
 // Every option of a handle: where its value lives — a planner option (rl_plan_opts field) or a tunable of the handle
-// itself — and how rl_method_set_option brings a value into range (nullptr: stored as given).  get_info reads the same
-// field back.
+// itself —, how rl_method_set_option brings a value into range (nullptr: stored as given), and what else has to follow
+// once the value is stored (nullptr: nothing).  get_info reads the same field back.
 struct OptionRow {
     const char *name;
-    int rl_plan_opts::*plan;
-    int rl_method::*own;
+    int &(*at)(rl_method *);
     int (*clamp)(int);
+    void (*stored)(rl_method *, int);
 };
+#define PLAN(field) [](rl_method *h) -> int & { return h->opt.field; }
+#define OWN(field) [](rl_method *h) -> int & { return h->field; }
 static int clamp_int(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 static int as_bool(int v) { return v != 0; }
 static const OptionRow OPTIONS[] = {
-    {"variant", &rl_plan_opts::variant, nullptr, nullptr},            // (< 0: the kind's default, rl_method_set_option)
-    {"grid_mult", &rl_plan_opts::grid_mult, nullptr, [](int v) { return std::max(v, 1); }},
-    {"wg_threads", &rl_plan_opts::wg_threads, nullptr, [](int v) { return v >= 1024 ? 1024 : (v >= 512 ? 512 : 256); }},
-    {"low_water", &rl_plan_opts::low_water, nullptr, [](int v) { return v < 0 ? -1 : std::min(v, 63); }},
-    {"sort_poses", &rl_plan_opts::sort_poses, nullptr, as_bool},
-    {"xcd_bands", &rl_plan_opts::xcd_bands, nullptr, [](int v) { return std::max(v, 1); }},
-    {"slots", &rl_plan_opts::slots, nullptr, [](int v) { return v >= 3 ? 3 : std::max(v, 0); }},
-    {"tiled", &rl_plan_opts::tiled, nullptr, as_bool},
-    {"inline_prep", &rl_plan_opts::inline_prep, nullptr, as_bool},
-    {"inline_max", &rl_plan_opts::inline_max, nullptr, nullptr},
-    {"inline_map_kb", &rl_plan_opts::inline_map_kb, nullptr, [](int v) { return std::max(v, 0); }},
-    {"stripe_max", &rl_plan_opts::stripe_max, nullptr, [](int v) { return std::max(v, 0); }},
-    {"order_inline", &rl_plan_opts::order_inline, nullptr, as_bool},
-    {"bin_multi_min", &rl_plan_opts::bin_multi_min, nullptr, nullptr},
-    {"bin_generic", &rl_plan_opts::bin_generic, nullptr, as_bool},
-    {"run_log2", &rl_plan_opts::run_log2, nullptr, [](int v) { return v < 0 ? -1 : std::min(v, 8); }},
-    {"cddt_bins", &rl_plan_opts::cddt_bins, nullptr, as_bool},
-    {"cddt_sort", &rl_plan_opts::cddt_sort, nullptr, as_bool},
-    {"lut_debug", &rl_plan_opts::lut_debug, nullptr, nullptr},        // (also LutParams / CddtParams debug)
-    {"debug_stamps", &rl_plan_opts::debug_stamps, nullptr, as_bool},
-    {"slice_log2", &rl_plan_opts::slice_log2, nullptr, [](int v) { return clamp_int(v, 8, 30); }},
-    {"cddt_theta_min", &rl_plan_opts::cddt_theta_min, nullptr, [](int v) { return std::max(v, 0); }},
-    {"cddt_search", &rl_plan_opts::cddt_search, nullptr, [](int v) { return clamp_int(v, 0, 2); }},
-    {"code_map", &rl_plan_opts::code_map, nullptr, [](int v) { return v == 2 ? 2 : 0; }},
-    {"code_min_rays", &rl_plan_opts::code_min_rays, nullptr, [](int v) { return std::max(v, 0); }},
-    {"tail_pct", &rl_plan_opts::tail_pct, nullptr, [](int v) { return clamp_int(v, 0, 75); }},
-    {"tail_wg_pct", &rl_plan_opts::tail_wg_pct, nullptr, [](int v) { return clamp_int(v, 10, 400); }},
-    {"timing", nullptr, &rl_method::timing, [](int v) { return clamp_int(v, 0, 2); }},
-    {"drain_prio", nullptr, &rl_method::drain_prio, as_bool},
-    {"spec_drain", nullptr, &rl_method::spec_drain, [](int v) { return clamp_int(v, 0, 64); }},
-    {"spec_stretch", nullptr, &rl_method::spec_stretch, [](int v) { return clamp_int(v, 1, 4096); }},
-    {"drain_cap", nullptr, &rl_method::drain_cap, [](int v) { return clamp_int(v, 1, 64); }},
-    {"drain_stretch", nullptr, &rl_method::drain_stretch, [](int v) { return clamp_int(v, 1, 4096); }},
-    {"group_drain", nullptr, &rl_method::group_drain, [](int v) { return clamp_int(v, 0, 16); }},
-    {"handoff", nullptr, &rl_method::handoff, as_bool},
-    {"handoff_cap", nullptr, &rl_method::handoff_cap, [](int v) { return v >= 64 ? 64 : (v >= 32 ? 32 : (v >= 16 ? 16 : 8)); }},
-    {"handoff_wg", nullptr, &rl_method::handoff_wg, [](int v) { return v >= 256 ? 256 : (v >= 128 ? 128 : 64); }},
-    {"nt_store", nullptr, &rl_method::nt_store, as_bool},
-    {"bin_ppw", nullptr, &rl_method::bin_ppw, [](int v) { return clamp_int(v, 256, 8192); }},
-    {"tile_stripe", nullptr, &rl_method::tile_stripe, [](int v) { return v < 0 ? -1 : std::min(v, 4096); }},
-    {"pinned_max_rays", nullptr, &rl_method::pinned_max_rays, [](int v) { return std::max(v, 0); }},
-    {"direct_max_rays", nullptr, &rl_method::direct_max_rays, [](int v) { return std::max(v, 0); }},
-    {"overlap_min_rays", nullptr, &rl_method::overlap_min_rays, [](int v) { return std::max(v, 0); }},
-    {"pf_block", nullptr, &rl_method::pf_block, [](int v) { return clamp_int(v, 0, PF_WG); }},
+    {"variant", PLAN(variant), nullptr},            // (< 0: the kind's default, rl_method_set_option)
+    {"grid_mult", PLAN(grid_mult), [](int v) { return std::max(v, 1); }},
+    {"wg_threads", PLAN(wg_threads), [](int v) { return v >= 1024 ? 1024 : (v >= 512 ? 512 : 256); }},
+    {"low_water", PLAN(low_water), [](int v) { return v < 0 ? -1 : std::min(v, 63); }},
+    {"sort_poses", PLAN(sort_poses), as_bool},
+    {"xcd_bands", PLAN(xcd_bands), [](int v) { return std::max(v, 1); }},
+    {"slots", PLAN(slots), [](int v) { return v >= 3 ? 3 : std::max(v, 0); }},
+    {"tiled", PLAN(tiled), as_bool},
+    {"inline_prep", PLAN(inline_prep), as_bool},
+    {"inline_max", PLAN(inline_max), nullptr},
+    {"inline_map_kb", PLAN(inline_map_kb), [](int v) { return std::max(v, 0); }},
+    {"stripe_max", PLAN(stripe_max), [](int v) { return std::max(v, 0); }},
+    {"order_inline", PLAN(order_inline), as_bool},
+    {"bin_multi_min", PLAN(bin_multi_min), nullptr},
+    {"bin_generic", PLAN(bin_generic), as_bool},
+    {"run_log2", PLAN(run_log2), [](int v) { return v < 0 ? -1 : std::min(v, 8); }},
+    {"cddt_bins", PLAN(cddt_bins), as_bool},
+    {"cddt_sort", PLAN(cddt_sort), as_bool},
+    {"lut_debug", PLAN(lut_debug), nullptr, [](rl_method *h, int v) { h->lut.lp.debug = h->cddt.cdp.debug = v; }},
+    {"debug_stamps", PLAN(debug_stamps), as_bool},
+    {"slice_log2", PLAN(slice_log2), [](int v) { return clamp_int(v, 8, 30); }},
+    {"cddt_theta_min", PLAN(cddt_theta_min), [](int v) { return std::max(v, 0); }},
+    {"cddt_search", PLAN(cddt_search), [](int v) { return clamp_int(v, 0, 2); }},
+    {"code_map", PLAN(code_map), [](int v) { return v == 2 ? 2 : 0; }},
+    {"code_min_rays", PLAN(code_min_rays), [](int v) { return std::max(v, 0); }},
+    {"tail_pct", PLAN(tail_pct), [](int v) { return clamp_int(v, 0, 75); }},
+    {"tail_wg_pct", PLAN(tail_wg_pct), [](int v) { return clamp_int(v, 10, 400); }},
+    {"timing", OWN(timing), [](int v) { return clamp_int(v, 0, 2); }},
+    {"drain_prio", OWN(drain_prio), as_bool},
+    {"spec_drain", OWN(spec_drain), [](int v) { return clamp_int(v, 0, 64); }},
+    {"spec_stretch", OWN(spec_stretch), [](int v) { return clamp_int(v, 1, 4096); }},
+    {"drain_cap", OWN(drain_cap), [](int v) { return clamp_int(v, 1, 64); }},
+    {"drain_stretch", OWN(drain_stretch), [](int v) { return clamp_int(v, 1, 4096); }},
+    {"group_drain", OWN(group_drain), [](int v) { return clamp_int(v, 0, 16); }},
+    {"handoff", OWN(handoff), as_bool},
+    {"handoff_cap", OWN(handoff_cap), [](int v) { return v >= 64 ? 64 : (v >= 32 ? 32 : (v >= 16 ? 16 : 8)); }},
+    {"handoff_wg", OWN(handoff_wg), [](int v) { return v >= 256 ? 256 : (v >= 128 ? 128 : 64); }},
+    {"nt_store", OWN(nt_store), as_bool},
+    {"bin_ppw", OWN(bin_ppw), [](int v) { return clamp_int(v, 256, 8192); }},
+    {"tile_stripe", OWN(tile_stripe), [](int v) { return v < 0 ? -1 : std::min(v, 4096); }},
+    {"pinned_max_rays", OWN(pinned_max_rays), [](int v) { return std::max(v, 0); }},
+    {"direct_max_rays", OWN(direct_max_rays), [](int v) { return std::max(v, 0); }},
+    {"overlap_min_rays", OWN(overlap_min_rays), [](int v) { return std::max(v, 0); }},
+    {"pf_block", OWN(pf_block), [](int v) { return clamp_int(v, 0, PF_WG); }},
     // (a power of two in [128, CDDT_LDS_SORT]: the bitonic network pads to one)
-    {"cddt_lds_sort", nullptr, &rl_method::cddt_lds_sort, [](int v) {
+    {"cddt_lds_sort", OWN(cddt.lds_sort), [](int v) {
          int p = 128;
          while (p * 2 <= v && p * 2 <= (int)CDDT_LDS_SORT) p *= 2;
          return p;
-     }},
+     }, [](rl_method *h, int) { h->cddt.cache.invalidate(); }},      // (the table is rebuilt with the new bound)
 };
+#undef PLAN
+#undef OWN
 
 static const OptionRow *find_option(const char *name)
 {
@@ -202,7 +206,6 @@ static const OptionRow *find_option(const char *name)
         if (!strcmp(name, r.name)) return &r;
     return nullptr;
 }
-static int &option_value(rl_method *h, const OptionRow &r) { return r.plan ? h->opt.*r.plan : h->*r.own; }
 
 extern "C" int rl_method_set_option(rl_method *h, const char *name, int value)
 {
@@ -223,9 +226,8 @@ extern "C" int rl_method_set_option(rl_method *h, const char *name, int value)
     const OptionRow *row = find_option(name);
     if (!row) return fail(RL_ERR_INVALID, "unknown option '%s'", name);
     if (!strcmp(name, "variant") && value < 0) value = plan::default_variant(h->kind);
-    if (!strcmp(name, "lut_debug")) h->lp.debug = h->cdp.debug = value;
-    if (!strcmp(name, "cddt_lds_sort")) h->cddt_epoch = ~0ull;       // (the table is rebuilt with the new bound)
-    option_value(h, *row) = row->clamp ? row->clamp(value) : value;
+    const int stored = row->at(h) = row->clamp ? row->clamp(value) : value;
+    if (row->stored) row->stored(h, stored);
     return RL_OK;
 }
 
@@ -242,10 +244,10 @@ extern "C" int rl_method_get_info(rl_method *h, const char *name, int64_t *value
     // (read-only)
     if (!strcmp(name, "n_cu")) *value_out = h->map->n_cu;
     else if (!strcmp(name, "clock_khz")) *value_out = h->map->clock_khz;
-    else if (!strcmp(name, "code_entries")) *value_out = h->code_n;
+    else if (!strcmp(name, "code_entries")) *value_out = h->step.code_n;
     else if (!strcmp(name, "last_grid")) *value_out = h->last_grid;
     else if (!strcmp(name, "map_epoch")) *value_out = (int64_t)h->map->epoch;
-    else if (const OptionRow *row = find_option(name)) *value_out = option_value(h, *row);
+    else if (const OptionRow *row = find_option(name)) *value_out = row->at(h);
     else return fail(RL_ERR_INVALID, "unknown info '%s'", name);
     return RL_OK;
 }
@@ -281,7 +283,7 @@ int check_fan_args(const rl_method *h, int n_poses, float fov, int num_rays)
 
 
 // ------------------------------------------------------------------------------
-// launch contexts and table dependencies (see LaunchCtx / TableDep)
+// launch contexts (see LaunchCtx)
 // ------------------------------------------------------------------------------
 static int acquire_ctx(rl_method *h, hipStream_t stream, LaunchCtx **out)
 {
@@ -307,51 +309,40 @@ static int acquire_ctx(rl_method *h, hipStream_t stream, LaunchCtx **out)
     return RL_OK;
 }
 
-// after (re)building a table on `stream`
-static int table_built(TableDep &d, hipStream_t stream)
+// ------------------------------------------------------------------------------
+// derived tables (built lazily on the launch stream, rebuilt when the map changed).  A build_* function sizes and
+// enqueues one table from the inputs it names; ensure_table runs the cache protocol around it (TableCache)
+// ------------------------------------------------------------------------------
+template <class Build>
+static int ensure_table(TableCache &cache, bool fresh, const rl_map *m, hipStream_t stream, const Build &build)
 {
-    HIPCHK(d.ev.create(hipEventDisableTiming));
-    HIPCHK(hipEventRecord(d.ev, stream));
-    d.built_on = stream;
-    d.pending = true;
-    return RL_OK;
+    if (fresh) return cache.wait(stream);
+    int rc = cache.begin_rebuild();              // launches of other streams may still read the old copy
+    if (rc || (rc = build())) return rc;
+    HIPCHK(hipGetLastError());
+    return cache.built(m, stream);
 }
 
-// before a launch on `stream` reads the table
-static int table_wait(TableDep &d, hipStream_t stream)
-{
-    if (!d.pending || stream == d.built_on) return RL_OK;      // (same stream: stream order)
-    if (hipEventQuery(d.ev) == hipSuccess) {
-        d.pending = false;
-        return RL_OK;
-    }
-    HIPCHK(hipStreamWaitEvent(stream, d.ev, 0));
-    return RL_OK;
-}
-
-// ------------------------------------------------------------------------------
-// derived tables (built lazily on the launch stream, rebuilt when the map changed)
-// ------------------------------------------------------------------------------
 // (cos, sin) of the beam angles of fan f: one small table per (fov, num_rays) the handle is called
 // with — four are kept, the least recently used one is rebuilt (after a device synchronisation:
 // launches of other streams may still read it) when a fifth fan shows up
-static int ensure_fan_table(rl_method *h, const FanParams &f, float fov, hipStream_t stream, const float2 **out)
+static int ensure_fan_table(FanTabs &t, const FanParams &f, float fov, hipStream_t stream, const float2 **out)
 {
     uint32_t bits;
     memcpy(&bits, &fov, sizeof bits);
-    rl_method::FanTab *slot = nullptr;
-    for (auto &ft : h->fan_tabs)
+    FanTabs::Tab *slot = nullptr;
+    for (auto &ft : t.tabs)
         if (ft.tab.p && ft.fov_bits == bits && ft.num_rays == f.num_rays) slot = &ft;
     if (slot) {
-        slot->last_use = ++h->fan_clock;
+        slot->last_use = ++t.clock;
         *out = (const float2 *)slot->tab.p;
-        return table_wait(slot->dep, stream);
+        return slot->dep.wait(stream);
     }
-    for (auto &ft : h->fan_tabs)
+    for (auto &ft : t.tabs)
         if (!ft.tab.p) { slot = &ft; break; }
     if (!slot) {
-        slot = &h->fan_tabs[0];
-        for (auto &ft : h->fan_tabs)
+        slot = &t.tabs[0];
+        for (auto &ft : t.tabs)
             if (ft.last_use < slot->last_use) slot = &ft;
         HIPCHK(hipDeviceSynchronize());
     }
@@ -360,34 +351,36 @@ static int ensure_fan_table(rl_method *h, const FanParams &f, float fov, hipStre
     hipLaunchKernelGGL(fan_table_kernel, dim3((f.num_rays + 255) / 256), dim3(256), 0, stream, f, (float2 *)slot->tab.p);
     slot->fov_bits = bits;
     slot->num_rays = f.num_rays;
-    slot->last_use = ++h->fan_clock;
+    slot->last_use = ++t.clock;
     *out = (const float2 *)slot->tab.p;
-    return table_built(slot->dep, stream);
+    return slot->dep.built(stream);
+}
+
+static int build_lut(LutTable &t, const rl_map *m, float max_range, float step_coeff, int theta_disc, int debug,
+                     hipStream_t stream)
+{
+    const size_t n = (size_t)m->rows * m->cols * theta_disc;
+    int rc = t.buf.ensure(n * sizeof(uint16_t) + 64);      // + slack: rows are read in 16-B pieces
+    if (rc) return rc;
+    LutParams &lp = t.lp;
+    lp.lut = (uint16_t *)t.buf.p;
+    lp.theta_disc = theta_disc;
+    lp.bins_per_rad = (float)theta_disc * 0.15915494309189535f;
+    lp.bin_width = 6.283185307179586f / (float)theta_disc;
+    lp.quant = 65535.0f / max_range;
+    lp.dequant = max_range / 65535.0f;
+    lp.debug = debug;
+    const long cells = (long)m->rows * m->cols;
+    const int grid = (int)std::min(cells, (long)m->n_cu * 16);
+    hipLaunchKernelGGL(lut_build_kernel, dim3(grid), dim3(256), 0, stream, m->mp, lp, max_range, step_coeff, 0, m->rows);
+    return RL_OK;
 }
 
 static int ensure_lut(rl_method *h, hipStream_t stream)
 {
-    rl_map *m = h->map;
-    if (h->lut_epoch == m->epoch && h->lut.p) return table_wait(h->lut_dep, stream);
-    HIPCHK(hipDeviceSynchronize());     // launches of other streams may still read the old table
-    const size_t n = (size_t)m->rows * m->cols * h->theta_disc;
-    int rc = h->lut.ensure(n * sizeof(uint16_t) + 64);      // + slack: rows are read in 16-B pieces
-    if (rc) return rc;
-    LutParams &lp = h->lp;
-    lp.lut = (uint16_t *)h->lut.p;
-    lp.theta_disc = h->theta_disc;
-    lp.bins_per_rad = (float)h->theta_disc * 0.15915494309189535f;
-    lp.bin_width = 6.283185307179586f / (float)h->theta_disc;
-    lp.quant = 65535.0f / h->max_range;
-    lp.dequant = h->max_range / 65535.0f;
-    lp.debug = h->opt.lut_debug;
-    const long cells = (long)m->rows * m->cols;
-    const int grid = (int)std::min(cells, (long)m->n_cu * 16);
-    hipLaunchKernelGGL(lut_build_kernel, dim3(grid), dim3(256), 0, stream, m->mp, lp, h->max_range,
-                       h->step_coeff, 0, m->rows);
-    HIPCHK(hipGetLastError());
-    h->lut_epoch = m->epoch;
-    return table_built(h->lut_dep, stream);
+    return ensure_table(h->lut.cache, h->lut.cache.fresh_for(h->map), h->map, stream, [&]() {
+        return build_lut(h->lut, h->map, h->max_range, h->step_coeff, h->theta_disc, h->opt.lut_debug, stream);
+    });
 }
 
 // CDDT table of the current map, ENQUEUED on `stream` with no host synchronisation and no read-back:
@@ -395,86 +388,82 @@ static int ensure_lut(rl_method *h, hipStream_t stream)
 // Sizes the host needs are known without asking the device: bucket counts follow from the map shape,
 // and the number of stored values is bounded by 3 per (edge cell, theta bin) — a cell's footprint
 // (half-width <= sqrt(2)/2) covers at most 3 buckets — with the edge count kept by the map.
-static int ensure_cddt(rl_method *h, hipStream_t stream)
+static int build_cddt(CddtTable &t, const rl_map *m, int theta_disc, int debug, hipStream_t stream)
 {
-    rl_map *m = h->map;
-    if (h->cddt_epoch == m->epoch && h->cd_tab.p) return table_wait(h->cddt_dep, stream);
-    if (h->cd_tab.p) HIPCHK(hipDeviceSynchronize());     // launches of other streams may still read the old table
-    const int td = h->theta_disc, nb = (td + 1) / 2;
+    const int td = theta_disc, nb = (td + 1) / 2;
     int rc;
-    if (h->cd_geom_rows != m->rows || h->cd_geom_cols != m->cols) {
+    if (t.geom_rows != m->rows || t.geom_cols != m->cols) {
         // per-bin geometry: depends on the map SHAPE only, uploaded once
-        h->cd_h_cos.resize(nb); h->cd_h_sin.resize(nb); h->cd_h_trans.resize(nb);
-        h->cd_h_width.resize(nb); h->cd_h_boff.resize(nb + 1);
+        t.h_cos.resize(nb); t.h_sin.resize(nb); t.h_trans.resize(nb);
+        t.h_width.resize(nb); t.h_boff.resize(nb + 1);
         uint32_t nbk = 0;
         const float W = (float)m->cols, H = (float)m->rows;
         for (int a = 0; a < nb; ++a) {
             float s, c;
             host_sincosf((float)a * (6.283185307179586f / (float)td), s, c);
-            h->cd_h_cos[a] = c;
-            h->cd_h_sin[a] = s;
+            t.h_cos[a] = c;
+            t.h_sin[a] = s;
             // buckets = height of the rotated map's bounding box; translation lifts the lowest
             // rotated corner to bucket 0
-            h->cd_h_width[a] = (int)ceilf((fabsf(W * s) + fabsf(H * c)) - CDDT_EPS) + 1;
+            t.h_width[a] = (int)ceilf((fabsf(W * s) + fabsf(H * c)) - CDDT_EPS) + 1;
             const float lt = H * c, rt = fmaf(W, s, H * c), rb = W * s;
-            h->cd_h_trans[a] = fmaxf(0.0f, -fminf(lt, fminf(rt, rb)) - CDDT_EPS);
-            h->cd_h_boff[a] = nbk;
-            nbk += (uint32_t)h->cd_h_width[a];
+            t.h_trans[a] = fmaxf(0.0f, -fminf(lt, fminf(rt, rb)) - CDDT_EPS);
+            t.h_boff[a] = nbk;
+            nbk += (uint32_t)t.h_width[a];
         }
-        h->cd_h_boff[nb] = nbk;
-        h->cd_buckets = nbk;
-        if ((rc = h->cd_cos.ensure(nb * 4)) || (rc = h->cd_sin.ensure(nb * 4)) ||
-            (rc = h->cd_trans.ensure(nb * 4)) || (rc = h->cd_width.ensure(nb * 4)) ||
-            (rc = h->cd_boff.ensure((nb + 1) * 4)) || (rc = h->cd_offsets.ensure(((size_t)nbk + 1) * 4)) ||
-            (rc = h->cd_cursor.ensure(((size_t)nbk + 1) * 4)))
+        t.h_boff[nb] = nbk;
+        t.buckets = nbk;
+        if ((rc = t.cos.ensure(nb * 4)) || (rc = t.sin.ensure(nb * 4)) || (rc = t.trans.ensure(nb * 4)) ||
+            (rc = t.width.ensure(nb * 4)) || (rc = t.boff.ensure((nb + 1) * 4)) ||
+            (rc = t.offsets.ensure(((size_t)nbk + 1) * 4)) || (rc = t.cursor.ensure(((size_t)nbk + 1) * 4)))
             return rc;
-        HIPCHK(hipMemcpyAsync(h->cd_cos.p, h->cd_h_cos.data(), nb * 4, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(h->cd_sin.p, h->cd_h_sin.data(), nb * 4, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(h->cd_trans.p, h->cd_h_trans.data(), nb * 4, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(h->cd_width.p, h->cd_h_width.data(), nb * 4, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(h->cd_boff.p, h->cd_h_boff.data(), (nb + 1) * 4, hipMemcpyHostToDevice, stream));
-        h->cd_geom_rows = m->rows;
-        h->cd_geom_cols = m->cols;
-        h->cd_counts_clean = false;
+        HIPCHK(hipMemcpyAsync(t.cos.p, t.h_cos.data(), nb * 4, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(t.sin.p, t.h_sin.data(), nb * 4, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(t.trans.p, t.h_trans.data(), nb * 4, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(t.width.p, t.h_width.data(), nb * 4, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(t.boff.p, t.h_boff.data(), (nb + 1) * 4, hipMemcpyHostToDevice, stream));
+        t.geom_rows = m->rows;
+        t.geom_cols = m->cols;
+        t.counts_clean = false;
     }
-    const uint32_t nbk = h->cd_buckets;
+    const uint32_t nbk = t.buckets;
     const size_t cap = std::max<size_t>((size_t)m->n_edges * nb * 3, 1);    // stored values, upper bound
     if (cap > (size_t)INT_MAX) return fail(RL_ERR_UNSUPPORTED, "CDDT table too large (%zu values)", cap);
-    if ((rc = h->cd_xs2.ensure(cap * 4))) return rc;
+    if ((rc = t.xs2.ensure(cap * 4))) return rc;
     // the blocked table the queries read (cddt_kernels.h, CddtParams): leaves of 32 values + separator lines;
     // upper bound: every bucket pads its last leaf and, with more than one leaf, its last separator line
     const size_t tab_lines = cap / 32 + cap / 1024 + 2 * (size_t)nbk + 2;
     if (tab_lines > (size_t)UINT32_MAX) return fail(RL_ERR_UNSUPPORTED, "CDDT table too large (%zu lines)", tab_lines);
-    if ((rc = h->cd_hdr.ensure((size_t)nbk * 8)) || (rc = h->cd_tab.ensure(tab_lines * 128))) return rc;
-    CddtParams &cp = h->cdp;
+    if ((rc = t.hdr.ensure((size_t)nbk * 8)) || (rc = t.tab.ensure(tab_lines * 128))) return rc;
+    CddtParams &cp = t.cdp;
     cp.theta_disc = td;
     cp.n_bins = nb;
-    cp.cosv = (const float *)h->cd_cos.p;
-    cp.sinv = (const float *)h->cd_sin.p;
-    cp.trans = (const float *)h->cd_trans.p;
-    cp.width = (const int *)h->cd_width.p;
-    cp.bucket_off = (const uint32_t *)h->cd_boff.p;
-    cp.offsets = (uint32_t *)h->cd_offsets.p;
-    cp.xs = (float *)h->cd_xs2.p;
-    cp.hdr = (uint2 *)h->cd_hdr.p;
-    cp.tab = (float *)h->cd_tab.p;
+    cp.cosv = (const float *)t.cos.p;
+    cp.sinv = (const float *)t.sin.p;
+    cp.trans = (const float *)t.trans.p;
+    cp.width = (const int *)t.width.p;
+    cp.bucket_off = (const uint32_t *)t.boff.p;
+    cp.offsets = (uint32_t *)t.offsets.p;
+    cp.xs = (float *)t.xs2.p;
+    cp.hdr = (uint2 *)t.hdr.p;
+    cp.tab = (float *)t.tab.p;
     cp.bins_per_rad = (float)td * 0.15915494309189535f;
-    cp.debug = h->opt.lut_debug;
-    if ((rc = h->cd_tmp.ensure(((size_t)nbk + 2 * nb + 64) * 4))) return rc;   // big-bucket count, bin totals (values, lines), list
-    if (!h->cd_sort_attr) {
+    cp.debug = debug;
+    if ((rc = t.tmp.ensure(((size_t)nbk + 2 * nb + 64) * 4))) return rc;   // big-bucket count, bin totals (values, lines), list
+    if (!t.sort_attr) {
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&cddt_sort_kernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CDDT_LDS_SORT * sizeof(float))));
-        h->cd_sort_attr = true;
+        t.sort_attr = true;
     }
     // bucket counters: zeroed once; every complete build returns them to zero (FILL subtracts what
     // COUNT added), so a rebuild starts without a memset
-    if (!h->cd_counts_clean) {
-        HIPCHK(hipMemsetAsync(h->cd_cursor.p, 0, ((size_t)nbk + 1) * 4, stream));
-        h->cd_counts_clean = true;
+    if (!t.counts_clean) {
+        HIPCHK(hipMemsetAsync(t.cursor.p, 0, ((size_t)nbk + 1) * 4, stream));
+        t.counts_clean = true;
     }
     // one workgroup per (chunk of edge cells, theta bin), bucket histogram of the bin in LDS
     int wmax = 0;
-    for (int a = 0; a < nb; ++a) wmax = std::max(wmax, h->cd_h_width[a]);
+    for (int a = 0; a < nb; ++a) wmax = std::max(wmax, t.h_width[a]);
     const size_t lds_fill = (size_t)wmax * 2 * sizeof(uint32_t);
     if (lds_fill > 150 * 1024) return fail(RL_ERR_UNSUPPORTED, "CDDT: map too large for the LDS bucket histogram");
     if (lds_fill > 48 * 1024) {
@@ -485,33 +474,34 @@ static int ensure_cddt(rl_method *h, hipStream_t stream)
     }
     const dim3 pgrid((unsigned)std::max<uint32_t>(1u, (m->n_edges + CDDT_CHUNK - 1) / CDDT_CHUNK), (unsigned)nb);
     // count -> exclusive scan (CSR offsets) -> fill -> sort every bucket
-    hipLaunchKernelGGL(cddt_project_kernel<false>, pgrid, dim3(256), lds_fill / 2, stream, cp,
-                       (const uint32_t *)m->d_edges, (const uint32_t *)m->d_n_edges, (uint32_t *)h->cd_cursor.p);
+    hipLaunchKernelGGL(cddt_project_kernel<false>, pgrid, dim3(256), lds_fill / 2, stream, cp, (const uint32_t *)m->d_edges,
+                       (const uint32_t *)m->d_n_edges, (uint32_t *)t.cursor.p);
     // [0] big-bucket count (zeroed by the sort's last reader), [1..64) spare, [64..64+nb) bin totals, then the list
-    uint32_t *big_count = (uint32_t *)h->cd_tmp.p, *bin_total = (uint32_t *)h->cd_tmp.p + 64;
+    uint32_t *big_count = (uint32_t *)t.tmp.p, *bin_total = (uint32_t *)t.tmp.p + 64;
     uint32_t *bin_lines = bin_total + nb, *big_list = bin_lines + nb;
     HIPCHK(hipMemsetAsync(big_count, 0, 4, stream));
-    hipLaunchKernelGGL(cddt_scan_bins_kernel, dim3(nb), dim3(256), 0, stream, cp, (const uint32_t *)h->cd_cursor.p,
-                       bin_total, bin_lines);
-    hipLaunchKernelGGL(cddt_scan_add_kernel, dim3(nb), dim3(256), 0, stream, cp, (const uint32_t *)h->cd_cursor.p,
+    hipLaunchKernelGGL(cddt_scan_bins_kernel, dim3(nb), dim3(256), 0, stream, cp, (const uint32_t *)t.cursor.p, bin_total, bin_lines);
+    hipLaunchKernelGGL(cddt_scan_add_kernel, dim3(nb), dim3(256), 0, stream, cp, (const uint32_t *)t.cursor.p,
                        (const uint32_t *)bin_total, (const uint32_t *)bin_lines, big_list, big_count);
-    hipLaunchKernelGGL(cddt_project_kernel<true>, pgrid, dim3(256), lds_fill, stream, cp,
-                       (const uint32_t *)m->d_edges, (const uint32_t *)m->d_n_edges, (uint32_t *)h->cd_cursor.p);
+    hipLaunchKernelGGL(cddt_project_kernel<true>, pgrid, dim3(256), lds_fill, stream, cp, (const uint32_t *)m->d_edges,
+                       (const uint32_t *)m->d_n_edges, (uint32_t *)t.cursor.p);
     // two launches of the sort kernel: the large buckets (workgroup each, 64 KB of LDS) and the small ones
     // (wave each, no LDS — in one launch the LDS size of the large path would cap everybody's occupancy)
     const uint32_t n_big_wg = (uint32_t)m->n_cu;
-    hipLaunchKernelGGL(cddt_sort_kernel, dim3(n_big_wg), dim3(256), (size_t)h->cddt_lds_sort * sizeof(float), stream,
-                       (const uint32_t *)h->cd_offsets.p, nbk, (const float *)h->cd_xs2.p, (const uint2 *)h->cd_hdr.p,
-                       (float *)h->cd_tab.p, (const uint32_t *)big_list, (const uint32_t *)big_count, n_big_wg,
-                       (uint32_t)h->cddt_lds_sort);
+    hipLaunchKernelGGL(cddt_sort_kernel, dim3(n_big_wg), dim3(256), (size_t)t.lds_sort * sizeof(float), stream,
+                       (const uint32_t *)t.offsets.p, nbk, (const float *)t.xs2.p, (const uint2 *)t.hdr.p, (float *)t.tab.p,
+                       (const uint32_t *)big_list, (const uint32_t *)big_count, n_big_wg, (uint32_t)t.lds_sort);
     const int sgrid = (int)std::max(1L, std::min(((long)nbk + 3) / 4, (long)m->n_cu * 32));
-    hipLaunchKernelGGL(cddt_sort_kernel, dim3(sgrid), dim3(256), 0, stream,
-                       (const uint32_t *)h->cd_offsets.p, nbk, (const float *)h->cd_xs2.p, (const uint2 *)h->cd_hdr.p,
-                       (float *)h->cd_tab.p, (const uint32_t *)big_list, (const uint32_t *)big_count, 0u,
-                       (uint32_t)h->cddt_lds_sort);
-    HIPCHK(hipGetLastError());
-    h->cddt_epoch = m->epoch;
-    return table_built(h->cddt_dep, stream);
+    hipLaunchKernelGGL(cddt_sort_kernel, dim3(sgrid), dim3(256), 0, stream, (const uint32_t *)t.offsets.p, nbk,
+                       (const float *)t.xs2.p, (const uint2 *)t.hdr.p, (float *)t.tab.p, (const uint32_t *)big_list,
+                       (const uint32_t *)big_count, 0u, (uint32_t)t.lds_sort);
+    return RL_OK;
+}
+
+static int ensure_cddt(rl_method *h, hipStream_t stream)
+{
+    return ensure_table(h->cddt.cache, h->cddt.cache.fresh_for(h->map), h->map, stream,
+                        [&]() { return build_cddt(h->cddt, h->map, h->theta_disc, h->opt.lut_debug, stream); });
 }
 
 // diagnostics (bench.py's algorithmic bytes of a CDDT ray): stored values, buckets and non-empty buckets of the
@@ -525,23 +515,21 @@ static int cddt_table_stats(rl_method *h, const char *name, int64_t *value_out)
     if (rc) return rc;
     if ((rc = ensure_cddt(h, h->stream))) return rc;
     HIPCHK(hipDeviceSynchronize());
-    std::vector<uint32_t> off((size_t)h->cd_buckets + 1);
-    HIPCHK(hipMemcpy(off.data(), h->cd_offsets.p, off.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const CddtTable &t = h->cddt;
+    std::vector<uint32_t> off((size_t)t.buckets + 1);
+    HIPCHK(hipMemcpy(off.data(), t.offsets.p, off.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     int64_t nonempty = 0;
-    for (size_t b = 0; b < (size_t)h->cd_buckets; ++b) nonempty += off[b + 1] > off[b];
-    if (!strcmp(name, "cddt_values")) *value_out = (int64_t)off[h->cd_buckets];
-    else if (!strcmp(name, "cddt_buckets")) *value_out = (int64_t)h->cd_buckets;
+    for (size_t b = 0; b < (size_t)t.buckets; ++b) nonempty += off[b + 1] > off[b];
+    if (!strcmp(name, "cddt_values")) *value_out = (int64_t)off[t.buckets];
+    else if (!strcmp(name, "cddt_buckets")) *value_out = (int64_t)t.buckets;
     else *value_out = nonempty;
     return RL_OK;
 }
 
 // K2b's padded bit maps (normal + transposed), rebuilt when the map changed
-static int ensure_blpad(rl_method *h, hipStream_t stream)
+static int build_blpad(BlPadMaps &t, const rl_map *m, float max_range, hipStream_t stream)
 {
-    rl_map *m = h->map;
-    if (h->blpad_epoch == m->epoch && h->blpad.p) return table_wait(h->blpad_dep, stream);
-    if (h->blpad.p) HIPCHK(hipDeviceSynchronize());     // launches of other streams may still read the old copy
-    const int reach = (int)h->max_range + 3 + 2;        // cells a walk can get away from its origin (cap + margin)
+    const int reach = (int)max_range + 3 + 2;           // cells a walk can get away from its origin (cap + margin)
     const int near = reach;                             // origins up to here outside the map are still covered
     const int pad = near + reach + 2;
     const int pad32 = (pad + 31) / 32;                  // major-axis padding in words
@@ -549,23 +537,27 @@ static int ensure_blpad(rl_method *h, hipStream_t stream)
     const int stride_t = (m->rows + 31) / 32 + 2 * pad32, prow_t = m->cols + 2 * pad;
     const size_t words_n = (size_t)stride_n * prow_n, words_t = (size_t)stride_t * prow_t;
     if ((words_n + words_t) * 4 > (size_t)1 << 31) return fail(RL_ERR_UNSUPPORTED, "map too large for the padded bit maps");
-    int rc = h->blpad.ensure((words_n + words_t) * 4);
+    int rc = t.buf.ensure((words_n + words_t) * 4);
     if (rc) return rc;
-    uint32_t *out_n = (uint32_t *)h->blpad.p, *out_t = out_n + words_n;
+    uint32_t *out_n = (uint32_t *)t.buf.p, *out_t = out_n + words_n;
     hipLaunchKernelGGL(bl_pad_bits_kernel, dim3((stride_n + 255) / 256, prow_n), dim3(256), 0, stream, m->d_occ,
                        m->rows, m->cols, 0, pad, pad32, stride_n, prow_n, out_n);
     hipLaunchKernelGGL(bl_pad_bits_kernel, dim3((stride_t + 255) / 256, prow_t), dim3(256), 0, stream, m->d_occ,
                        m->rows, m->cols, 1, pad, pad32, stride_t, prow_t, out_t);
-    HIPCHK(hipGetLastError());
-    BlPad &bp = h->blp;
+    BlPad &bp = t.blp;
     bp.bits = out_n;
     bp.stride_n = stride_n;
     bp.stride_t = stride_t;
     bp.k_n = (uint32_t)(((size_t)pad * stride_n + pad32) * 4);
     bp.k_t = (uint32_t)((words_n + (size_t)pad * stride_t + pad32) * 4);
     bp.near = (float)near;
-    h->blpad_epoch = m->epoch;
-    return table_built(h->blpad_dep, stream);
+    return RL_OK;
+}
+
+static int ensure_blpad(rl_method *h, hipStream_t stream)
+{
+    return ensure_table(h->blpad.cache, h->blpad.cache.fresh_for(h->map), h->map, stream,
+                        [&]() { return build_blpad(h->blpad, h->map, h->max_range, stream); });
 }
 
 static BlParams make_bl(const rl_method *h, int num_rays, size_t &lds_bytes)
@@ -683,7 +675,7 @@ static FastDiv make_fastdiv(uint32_t d)
 static rl_plan_opts opts_of(const rl_method *h)
 {
     rl_plan_opts o = h->opt;
-    o.code_entries = (o.code_map && h->code_built == o.code_map && h->pdt_epoch == h->map->epoch) ? h->code_n : 0;
+    o.code_entries = h->step.code_entries_for(h->map, h->max_range, h->opt);
     return o;
 }
 
@@ -704,93 +696,109 @@ static int plan_for(const rl_method *h, int n_poses, int num_rays, bool aux, boo
     return plan::plan_fan(in, out);
 }
 
-// step map of a ray-marching method (the EDT padded, holding the march's step), rebuilt when the map
-// or the layout option changed
-static int ensure_step_map(rl_method *h, hipStream_t stream)
+// the layout of the step map under the `tiled` option (the planner marches on the row-major copy when the tiled geometry
+// does not fit the address arithmetic: plan::tiled_fit — elongated maps whose pitch would need K > 24, tables beyond 4 GiB)
+static int step_map_layout(const rl_map *m, float max_range, int opt_tiled)
 {
-    const rl_map *m = h->map;
+    return (opt_tiled && plan::tiled_fit(m->rows, m->cols, max_range).ok) ? 1 : 0;
+}
+
+bool StepMap::fresh_for(const rl_map *m, float max_range, const rl_plan_opts &o) const
+{
+    // (a copy in the layout the option names is the layout wanted — tiled, so it fits — without a look at the geometry;
+    //  only a row-major copy under tiled = 1 asks: the fallback of a map that does not fit)
+    return cache.fresh_for(m) && code_built == o.code_map &&
+           (tiled == (o.tiled != 0) || tiled == step_map_layout(m, max_range, o.tiled));
+}
+
+int StepMap::code_entries_for(const rl_map *m, float max_range, const rl_plan_opts &o) const
+{
+    return (o.code_map && fresh_for(m, max_range, o)) ? code_n : 0;
+}
+
+PadMap StepMap::pad_map(bool code, float res) const
+{
+    const Addr &a = code ? code_at : at;
+    PadMap pm{};
+    pm.pdt = (const float *)((const char *)(code ? cmap : pdt).p + a.base_off);
+    pm.stride = a.stride;
+    pm.nstride = (int)a.mask;
+    pm.k4 = a.k4;
+    pm.pad = pad;                                            // (the border and the divisor are the float32 map's in both)
+    pm.div_stride = make_fastdiv((uint32_t)at.stride);
+    pm.res = res;
+    return pm;
+}
+
+// step map of a ray-marching method (the EDT padded, holding the march's step) in the layout the `tiled` option asks
+// for, and the code map next to it when `code_map` asks for one
+static int build_step_map(StepMap &t, const rl_map *m, float max_range, float step_coeff, int opt_tiled, int code_map,
+                          hipStream_t stream)
+{
     int rc;
-    // (the planner marches on the row-major copy when the tiled geometry does not fit the address arithmetic:
-    //  plan::tiled_fit — elongated maps whose pitch would need K > 24, tables beyond 4 GiB)
-    const plan::TiledFit fit = plan::tiled_fit(m->rows, m->cols, h->max_range);
-    const int want_tiled = (h->opt.tiled && fit.ok) ? 1 : 0;
-    if (h->pdt_epoch == m->epoch && h->pdt.p && h->pdt_tiled == want_tiled && h->code_built == h->opt.code_map)
-        return table_wait(h->pdt_dep, stream);
-    if (h->pdt.p) HIPCHK(hipDeviceSynchronize());   // launches of other streams may still read the old copy
-    h->pad = (int)std::ceil(h->max_range) + 2;
+    const int want_tiled = step_map_layout(m, max_range, opt_tiled);
+    t.pad = (int)std::ceil(max_range) + 2;
     if (want_tiled) {
-        TiledGeom tg{};
-        tg.pad = h->pad = fit.pad;
-        tg.padr = fit.padr;
-        tg.pcols = fit.pcols;
-        tg.prows = fit.prows;
-        tg.K = fit.K;
-        const size_t bytes = fit.bytes;
+        const plan::TiledFit fit = plan::tiled_fit(m->rows, m->cols, max_range);
+        const TiledGeom tg{fit.K, fit.pad, fit.padr, fit.pcols, fit.prows};
         const uint32_t M = 4u + (1u << (tg.K - 2));
-        h->pstride = (int)M;
-        h->pdt_mask = 0xCu | (~0u << tg.K);
-        h->pdt_k4 = (uint32_t)tg.padr * M;
-        h->pdt_base_off = (size_t)h->pad << 4;
-        if ((rc = h->pdt.ensure(bytes))) return rc;
+        t.pad = fit.pad;
+        t.at = {(size_t)t.pad << 4, (int)M, (uint32_t)tg.padr * M, 0xCu | (~0u << tg.K)};
+        if ((rc = t.pdt.ensure(fit.bytes))) return rc;
         hipLaunchKernelGGL(pad_dt_tiled_kernel, dim3((tg.pcols + 255) / 256, tg.prows), dim3(256), 0, stream,
-                           m->d_dt, m->rows, m->cols, (float *)h->pdt.p, tg, h->step_coeff);
+                           m->d_dt, m->rows, m->cols, (float *)t.pdt.p, tg, step_coeff);
     } else {
-        h->pstride = (m->cols + 2 * h->pad + 31) & ~31;
-        const int prow = m->rows + 2 * h->pad;
+        const int stride = (m->cols + 2 * t.pad + 31) & ~31, prow = m->rows + 2 * t.pad;
         // (row-major address: v_mad_i32_i24 r * stride + c, then << 2 in 32 bits)
-        if (h->pstride >= (1 << 23) || (size_t)prow * h->pstride >= ((size_t)1 << 30))
+        if (stride >= (1 << 23) || (size_t)prow * stride >= ((size_t)1 << 30))
             return fail(RL_ERR_UNSUPPORTED, "map %dx%d with max_range %g is too large for the step map", m->rows, m->cols,
-                        h->max_range);
-        if ((rc = h->pdt.ensure((size_t)prow * h->pstride * sizeof(float)))) return rc;
-        hipLaunchKernelGGL(pad_dt_kernel, dim3((h->pstride + 255) / 256, prow), dim3(256), 0,
-                           stream, m->d_dt, m->rows, m->cols, (float *)h->pdt.p, h->pad,
-                           h->pstride, h->step_coeff);
-        h->pdt_k4 = (uint32_t)(((size_t)h->pad * h->pstride + h->pad) * 4);
-        h->pdt_mask = 0;
-        h->pdt_base_off = 0;
+                        max_range);
+        t.at = {0, stride, (uint32_t)(((size_t)t.pad * stride + t.pad) * 4), 0u};
+        if ((rc = t.pdt.ensure((size_t)prow * stride * sizeof(float)))) return rc;
+        hipLaunchKernelGGL(pad_dt_kernel, dim3((stride + 255) / 256, prow), dim3(256), 0, stream, m->d_dt, m->rows, m->cols,
+                           (float *)t.pdt.p, t.pad, stride, step_coeff);
     }
     // the CODE map next to it: palette of the map's distinct steps (mark -> scan), then the tiled map of their codes.
     // The palette size decides the launches' LDS, so the host reads it back here (a map build, not a scan).
-    h->code_n = 0;
-    const plan::CodeFit cf = plan::code_fit(m->rows, m->cols, h->max_range, 1);
-    if (h->opt.code_map == 2 && want_tiled && cf.ok) {
+    t.code_n = 0;
+    const plan::CodeFit cf = plan::code_fit(m->rows, m->cols, max_range, 1);
+    if (code_map == 2 && want_tiled && cf.ok) {
         const uint32_t cap = (uint32_t)plan::CODE_MAX_ENTRIES;
-        if ((rc = h->cval.ensure((size_t)cf.nb * sizeof(float)))) return rc;
-        if ((rc = h->cidx.ensure((size_t)cf.nb * sizeof(uint32_t)))) return rc;
-        if ((rc = h->ctab.ensure((size_t)cap * sizeof(float)))) return rc;
-        if ((rc = h->cnum.ensure(2 * sizeof(uint32_t)))) return rc;
-        if (!h->pin_cnum) HIPCHK(h->pin_cnum.alloc(2 * sizeof(uint32_t)));
-        HIPCHK(hipMemsetAsync(h->cval.p, 0, (size_t)cf.nb * sizeof(float), stream));
+        if ((rc = t.cval.ensure((size_t)cf.nb * sizeof(float)))) return rc;
+        if ((rc = t.cidx.ensure((size_t)cf.nb * sizeof(uint32_t)))) return rc;
+        if ((rc = t.ctab.ensure((size_t)cap * sizeof(float)))) return rc;
+        if ((rc = t.cnum.ensure(2 * sizeof(uint32_t)))) return rc;
+        if (!t.pin_cnum) HIPCHK(t.pin_cnum.alloc(2 * sizeof(uint32_t)));
+        HIPCHK(hipMemsetAsync(t.cval.p, 0, (size_t)cf.nb * sizeof(float), stream));
         const size_t n_cells = (size_t)m->rows * m->cols;
         hipLaunchKernelGGL(code_mark_kernel, dim3((unsigned)std::min<size_t>((n_cells + 255) / 256, (size_t)m->n_cu * 8)), dim3(256),
-                           0, stream, m->d_dt, n_cells, (float *)h->cval.p, cf.nb, h->step_coeff, h->max_range);
-        hipLaunchKernelGGL(code_scan_kernel, dim3(1), dim3(1024), 0, stream, (const float *)h->cval.p, cf.nb, h->step_coeff,
-                           (uint32_t *)h->cidx.p, (float *)h->ctab.p, cap, (uint32_t *)h->cnum.p);
-        HIPCHK(hipMemcpyAsync(h->pin_cnum, h->cnum.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+                           0, stream, m->d_dt, n_cells, (float *)t.cval.p, cf.nb, step_coeff, max_range);
+        hipLaunchKernelGGL(code_scan_kernel, dim3(1), dim3(1024), 0, stream, (const float *)t.cval.p, cf.nb, step_coeff,
+                           (uint32_t *)t.cidx.p, (float *)t.ctab.p, cap, (uint32_t *)t.cnum.p);
+        HIPCHK(hipMemcpyAsync(t.pin_cnum, t.cnum.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
-        if (h->pin_cnum[1] == 0u && h->pin_cnum[0] <= cap) {
-            TiledGeom tg{};
-            tg.pad = cf.pad;
-            tg.padr = cf.padr;
-            tg.pcols = cf.pcols;
-            tg.prows = cf.prows;
-            tg.K = cf.K;
-            if ((rc = h->cmap.ensure(cf.bytes))) return rc;
+        if (t.pin_cnum[1] == 0u && t.pin_cnum[0] <= cap) {
+            const TiledGeom tg{cf.K, cf.pad, cf.padr, cf.pcols, cf.prows};
+            if ((rc = t.cmap.ensure(cf.bytes))) return rc;
             hipLaunchKernelGGL((pad_code_tiled_kernel<1>), dim3((tg.pcols + 255) / 256, tg.prows), dim3(256), 0, stream,
-                               m->d_dt, m->rows, m->cols, h->cmap.p, tg, h->step_coeff, h->max_range,
-                               (const uint32_t *)h->cidx.p, cf.nb, (const uint32_t *)h->cnum.p);
+                               m->d_dt, m->rows, m->cols, t.cmap.p, tg, step_coeff, max_range,
+                               (const uint32_t *)t.cidx.p, cf.nb, (const uint32_t *)t.cnum.p);
             const uint32_t M = (1u << cf.es) + (1u << (cf.K - 3));
-            h->cstride = (int)M;
-            h->cmask = (7u << cf.es) | (~0u << cf.K);
-            h->ck4 = (uint32_t)cf.padr * M;
-            h->cbase_off = (size_t)cf.pad << (3 + cf.es);
-            h->code_n = (int)h->pin_cnum[0];
+            t.code_at = {(size_t)cf.pad << (3 + cf.es), (int)M, (uint32_t)cf.padr * M, (7u << cf.es) | (~0u << cf.K)};
+            t.code_n = (int)t.pin_cnum[0];
         }
     }
-    h->code_built = h->opt.code_map;
-    h->pdt_epoch = m->epoch;
-    h->pdt_tiled = want_tiled;
-    return table_built(h->pdt_dep, stream);
+    t.code_built = code_map;
+    t.tiled = want_tiled;
+    return RL_OK;
+}
+
+// ... rebuilt when the map, the layout option or the code-map option changed
+static int ensure_step_map(rl_method *h, hipStream_t stream)
+{
+    return ensure_table(h->step.cache, h->step.fresh_for(h->map, h->max_range, h->opt), h->map, stream, [&]() {
+        return build_step_map(h->step, h->map, h->max_range, h->step_coeff, h->opt.tiled, h->opt.code_map, stream);
+    });
 }
 
 // rm_fan_stream_kernel by plan::stream_index: every instance of plan::stream_instance, nullptr in the other slots
@@ -871,7 +879,7 @@ static int launch_lut(const FanLaunch &L)
     int rc;
     if ((rc = ensure_lut(L.h, L.stream))) return rc;
     if (L.timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
-    kernel<<<L.grid, L.block, L.lds, L.stream>>>(L.m->mp, L.f, L.h->lp, L.d_poses, L.d_out);
+    kernel<<<L.grid, L.block, L.lds, L.stream>>>(L.m->mp, L.f, L.h->lut.lp, L.d_poses, L.d_out);
     return RL_OK;
 }
 
@@ -888,7 +896,7 @@ static int launch_cddt_bins(const FanLaunch &L)
         d_order = (const uint32_t *)L.cx->order.p;
     }
     if (L.timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
-    hipLaunchKernelGGL(cddt_fan_bins_kernel, L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, h->cdp, L.d_poses, L.d_out,
+    hipLaunchKernelGGL(cddt_fan_bins_kernel, L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, h->cddt.cdp, L.d_poses, L.d_out,
                        d_order, L.pl.bands, L.pl.nl, L.pl.ch);
     return RL_OK;
 }
@@ -904,27 +912,27 @@ static int launch_cddt_theta(const FanLaunch &L)
     if ((rc = ensure_cddt(h, L.stream))) return rc;
     // scratch of the launch context: R[raw bin][pose] behind the per-pose records {gx, gy, first bin, bins}
     const size_t prep_bytes = (((size_t)L.n_poses * 16) + 255) & ~(size_t)255;
-    if ((rc = L.cx->cddt_r.ensure(prep_bytes + (fused ? 0 : (size_t)h->cdp.theta_disc * (size_t)L.n_poses * sizeof(float)))))
+    if ((rc = L.cx->cddt_r.ensure(prep_bytes + (fused ? 0 : (size_t)h->cddt.cdp.theta_disc * (size_t)L.n_poses * sizeof(float)))))
         return rc;
     float4 *d_prep = (float4 *)L.cx->cddt_r.p;
     float *d_r = (float *)((char *)L.cx->cddt_r.p + prep_bytes);
     if (L.timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
     hipLaunchKernelGGL(cddt_theta_prep_kernel, dim3((unsigned)std::max(1, std::min((L.n_poses + 255) / 256, L.m->n_cu * 8))),
-                       dim3(256), 0, L.stream, L.m->mp, L.f, h->cdp, L.d_poses, d_prep);
+                       dim3(256), 0, L.stream, L.m->mp, L.f, h->cddt.cdp, L.d_poses, d_prep);
     if (fused) {
-        hipLaunchKernelGGL(cddt_theta_fused_kernel, L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, h->cdp, L.d_poses,
+        hipLaunchKernelGGL(cddt_theta_fused_kernel, L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, h->cddt.cdp, L.d_poses,
                            (const float4 *)d_prep, L.d_out, L.pl.nl);
         return RL_OK;
     }
     if (form == plan::CDDT_THETA_SEARCH2)
-        hipLaunchKernelGGL(cddt_theta_search2_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f, h->cdp, L.d_poses,
+        hipLaunchKernelGGL(cddt_theta_search2_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f, h->cddt.cdp, L.d_poses,
                            (const float4 *)d_prep, d_r, L.pl.bands);
     else
-        hipLaunchKernelGGL(cddt_theta_search_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f, h->cdp, L.d_poses,
+        hipLaunchKernelGGL(cddt_theta_search_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f, h->cddt.cdp, L.d_poses,
                            (const float4 *)d_prep, d_r, L.pl.bands);
     const int n_grp = (L.n_poses + (1 << L.pl.ch) - 1) >> L.pl.ch;
     hipLaunchKernelGGL(cddt_theta_fan_kernel, dim3((unsigned)std::max(1, std::min(n_grp, L.m->n_cu * 8))), L.block, L.lds,
-                       L.stream, L.m->mp, L.f, h->cdp, L.d_poses, (const float *)d_r, L.d_out, L.pl.ch, L.pl.nl);
+                       L.stream, L.m->mp, L.f, h->cddt.cdp, L.d_poses, (const float *)d_r, L.d_out, L.pl.ch, L.pl.nl);
     return RL_OK;
 }
 
@@ -934,7 +942,7 @@ static int launch_cddt_rays(const FanLaunch &L)
     int rc;
     if ((rc = ensure_cddt(L.h, L.stream))) return rc;
     if (L.timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
-    hipLaunchKernelGGL(cddt_fan_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f, L.h->cdp, L.d_poses, L.d_out);
+    hipLaunchKernelGGL(cddt_fan_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f, L.h->cddt.cdp, L.d_poses, L.d_out);
     return RL_OK;
 }
 
@@ -956,10 +964,10 @@ static int launch_bl_stream(const FanLaunch &L)
     sp.plain_store = L.plain_store;
     if (L.timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
     if (L.aux)
-        hipLaunchKernelGGL((bl_fan_stream_kernel<true, 1024>), L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, sp, h->blp,
+        hipLaunchKernelGGL((bl_fan_stream_kernel<true, 1024>), L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, sp, h->blpad.blp,
                            L.d_out, L.d_hits, L.d_steps);
     else
-        hipLaunchKernelGGL((bl_fan_stream_kernel<false, 1024>), L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, sp, h->blp,
+        hipLaunchKernelGGL((bl_fan_stream_kernel<false, 1024>), L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, sp, h->blpad.blp,
                            L.d_out, L.d_hits, L.d_steps);
     return RL_OK;
 }
@@ -1032,31 +1040,19 @@ static int launch_rm_stream_family(const FanLaunch &L)
     if (pl.binning != RL_BIN_NONE &&
         (rc = bin_poses(h, *L.cx, L.d_poses, L.n_poses, 0, L.stream, pl.binning)))
         return rc;
-    PadMap pm{};
-    pm.pdt = (const float *)((const char *)h->pdt.p + h->pdt_base_off);
-    pm.stride = h->pstride;
-    pm.nstride = (int)h->pdt_mask;
-    pm.pad = h->pad;
-    pm.k4 = h->pdt_k4;
-    pm.div_stride = make_fastdiv((uint32_t)h->pstride);
-    pm.res = L.m->res;
-    if (pl.code) {                               // the march reads the map of palette codes: its base and address constants
-        if (h->code_n <= 0 || pl.code_entries != h->code_n)
-            return fail(RL_ERR_INVALID, "internal: code-map plan (%d entries) without a matching palette (%d)", pl.code_entries, h->code_n);
-        pm.pdt = (const float *)((const char *)h->cmap.p + h->cbase_off);
-        pm.stride = h->cstride;
-        pm.nstride = (int)h->cmask;
-        pm.k4 = h->ck4;
-    }
+    const StepMap &sm = h->step;
+    if (pl.code && (sm.code_n <= 0 || pl.code_entries != sm.code_n))
+        return fail(RL_ERR_INVALID, "internal: code-map plan (%d entries) without a matching palette (%d)", pl.code_entries, sm.code_n);
+    const PadMap pm = sm.pad_map(pl.code != 0, L.m->res);
     StreamParams sp{};
-    sp.code_tab = (const float *)h->ctab.p;
-    sp.code_n = pl.code ? h->code_n : 0;
+    sp.code_tab = (const float *)sm.ctab.p;
+    sp.code_n = pl.code ? sm.code_n : 0;
     sp.tail_g1 = pl.gen1 > 0 ? pl.gen1 / std::max(pl.bands, 1) : 0;
     sp.tail_pct = std::min(h->opt.tail_pct, h->opt.tail_wg_pct);
     sp.rec = (const PoseRec *)L.cx->rec_sorted.p;
     sp.order = (const uint32_t *)L.cx->order.p;
     sp.d0 = (const float *)L.cx->d0.p;
-    if ((rc = ensure_fan_table(h, L.f, L.fov, L.stream, &sp.fan_tab))) return rc;
+    if ((rc = ensure_fan_table(h->fans, L.f, L.fov, L.stream, &sp.fan_tab))) return rc;
     sp.div_B = make_fastdiv((uint32_t)L.num_rays);
     sp.low_water = h->opt.low_water >= 0 ? h->opt.low_water : ((pl.record_source != 0 && pl.slots >= 2) ? 20 : 12);
     sp.n_bands = pl.bands;
@@ -1239,11 +1235,11 @@ static int launch_rays(rl_method *h, const float *d_ins, long n, float *d_out, i
     int rc;
     if (h->kind == RL_GIANT_LUT) {
         if ((rc = ensure_lut(h, stream))) return rc;
-        hipLaunchKernelGGL(lut_rays_kernel, dim3(grid), dim3(256), 0, stream, m->mp, f, h->lp, d_ins,
+        hipLaunchKernelGGL(lut_rays_kernel, dim3(grid), dim3(256), 0, stream, m->mp, f, h->lut.lp, d_ins,
                            n, d_out);
     } else if (h->kind == RL_CDDT) {
         if ((rc = ensure_cddt(h, stream))) return rc;
-        hipLaunchKernelGGL(cddt_rays_kernel, dim3(grid), dim3(256), 0, stream, m->mp, f, h->cdp,
+        hipLaunchKernelGGL(cddt_rays_kernel, dim3(grid), dim3(256), 0, stream, m->mp, f, h->cddt.cdp,
                            d_ins, n, d_out);
     } else if (h->kind == RL_BRESENHAM) {
         hipLaunchKernelGGL(bl_rays_kernel, dim3(grid), dim3(256), 0, stream, m->mp, f, d_ins, n,
@@ -1589,8 +1585,8 @@ static PfParams make_pf(const rl_method *h, int n_particles, int n_angles)
     return PfParams{n_particles, n_angles, block, h->sensor, h->sensor_w, (float)(h->sensor_w - 1)};
 }
 
-#define PF_ANGLES(K, A) hipLaunchKernelGGL((pf_angles_kernel<K, A>), dim3(grid), dim3(PF_WG), 0, stream, m->mp, f, lt, h->cdp, \
-                                           h->lp, d_poses, d_angles, n, d_out, d_hits, d_steps)
+#define PF_ANGLES(K, A) hipLaunchKernelGGL((pf_angles_kernel<K, A>), dim3(grid), dim3(PF_WG), 0, stream, m->mp, f, lt, h->cddt.cdp, \
+                                           h->lut.lp, d_poses, d_angles, n, d_out, d_hits, d_steps)
 static int launch_pf_angles(rl_method *h, const LaunchArgs &a, int kind, const float *d_poses, int n_particles, const float *d_angles,
                             int n_angles, float *d_out, int32_t *d_hits, uint16_t *d_steps, hipStream_t stream)
 {
@@ -1967,7 +1963,7 @@ extern "C" int rl_method_read_lut(rl_method *h, int row0, int row1, uint16_t *ou
     if ((rc = ensure_lut(h, h->stream))) return rc;
     const size_t per_row = (size_t)h->map->cols * h->theta_disc;
     HostCall hc(h->stream);
-    if ((rc = hc.down(out, (const uint16_t *)h->lut.p + (size_t)row0 * per_row, (size_t)(row1 - row0) * per_row))) return rc;
+    if ((rc = hc.down(out, (const uint16_t *)h->lut.buf.p + (size_t)row0 * per_row, (size_t)(row1 - row0) * per_row))) return rc;
     return hc.finish();
 }
 

@@ -1,9 +1,11 @@
 // abi_internal.h — what the translation units of libscan_amd.so share: the owners of every device resource (DevBuf,
 // DevPtr, Pinned, Stream, Event), HostCall (one synchronous host-pointer call: staging up, results down, the wait, and
-// the drain of a call that is refused on the way), the handles behind include/scanlib.h's opaque pointers, the error
-// slot, and the few internal entry points one unit calls in another.
+// the drain of a call that is refused on the way), the derived tables of a method (StepMap, LutTable, CddtTable,
+// BlPadMaps, FanTabs: one struct each, owning its buffers, parameter block and cache) with their one cache protocol
+// (TableCache), the handles behind include/scanlib.h's opaque pointers (rl_method: options, streams, staging, launch
+// contexts and the five tables), the error slot, and the few internal entry points one unit calls in another.
 //   abi_map.hip    errors, check_device, the caller's pinned host blocks, rl_map_* (EDT, bit map, edge list, stamps)
-//   abi_fan.hip    rl_method_*: options, derived tables, the launch planner's C ABI, every fan / ray launch (told its
+//   abi_fan.hip    rl_method_*: options, the tables' builds, the launch planner's C ABI, every fan / ray launch (told its
 //                  noise offset, store mode and timing by LaunchArgs / FanCall below, not by the handle), the
 //                  device-pointer entry points, the single-device host-pointer paths, the fused crash test; the
 //                  particle-filter weights (repeat-angle scans, sensor model) and localisation (rl_pf_*)
@@ -302,12 +304,130 @@ struct LaunchCtx {
 };
 constexpr int N_LAUNCH_CTX = 8;      // (HIP's default 4 hardware queues carry 4 concurrent streams; GPU_MAX_HW_QUEUES=8 carries 8)
 
-// A derived table (step map, GiantLUT, CDDT) is built lazily on the stream of the call that needs
-// it first; launches on OTHER streams must not start before the build has finished.
+// ------------------------------------------------------------------------------
+// derived tables: what a method builds from its map, lazily, on the stream of the call that needs it first.  One struct
+// per table holds everything that belongs to it — device buffers, the parameter block the kernels take, host copies, its
+// cache —, and one protocol (TableCache) says when a table is still good and what a reader or a rebuild has to wait for.
+// The builds are in abi_fan.hip (build_* / ensure_*).
+// ------------------------------------------------------------------------------
+// launches on OTHER streams than the one a table was built on must not start before the build has finished
 struct TableDep {
     Event ev;                    // (made by the first build)
     hipStream_t built_on = nullptr;
     bool pending = false;
+    int built(hipStream_t stream)                // after (re)building the table on `stream`
+    {
+        HIPCHK(ev.create(hipEventDisableTiming));
+        HIPCHK(hipEventRecord(ev, stream));
+        built_on = stream;
+        pending = true;
+        return RL_OK;
+    }
+    int wait(hipStream_t stream)                 // before a launch on `stream` reads the table
+    {
+        if (!pending || stream == built_on) return RL_OK;      // (same stream: stream order)
+        if (hipEventQuery(ev) == hipSuccess) {
+            pending = false;
+            return RL_OK;
+        }
+        HIPCHK(hipStreamWaitEvent(stream, ev, 0));
+        return RL_OK;
+    }
+};
+
+// The cache protocol of a table that follows the map: fresh_for(map) ? wait(stream) : begin_rebuild(), the build
+// enqueued on `stream`, built(map, stream).  A table is good for exactly the map epoch it was stamped with, and it is
+// stamped only once its build is enqueued and its event recorded: a build that fails on the way leaves it stale.
+struct TableCache {
+    static constexpr uint64_t NEVER = ~0ull;
+    uint64_t epoch = NEVER;      // map epoch the table was built from
+    bool begun = false;          // a build has been started before: launches of other streams may still read that copy
+    TableDep dep;
+    bool fresh_for(const rl_map *m) const { return epoch == m->epoch; }
+    int wait(hipStream_t stream) { return dep.wait(stream); }
+    int begin_rebuild()
+    {
+        epoch = NEVER;
+        if (begun) HIPCHK(hipDeviceSynchronize());
+        begun = true;
+        return RL_OK;
+    }
+    int built(const rl_map *m, hipStream_t stream)
+    {
+        const int rc = dep.built(stream);
+        if (rc == RL_OK) epoch = m->epoch;
+        return rc;
+    }
+    void invalidate() { epoch = NEVER; }         // (an option the table was built with changed)
+};
+
+namespace scan { struct PadMap; }
+
+// Ray marching: the step map — the EDT with a border of `pad` cells of -1, holding the march's step — and, built next
+// to it, the CODE map (option code_map = 2): the step map as u16 palette codes + the palette (rm_kernels.h).
+struct StepMap {
+    struct Addr {                // the march's address constants of one copy
+        size_t base_off;         // tiled: the column bias (pad << 4 bytes) folded into the base address
+        int stride;              // elements per row (row-major) | M (tiled, see pdt_tiled_byte)
+        uint32_t k4, mask;
+    };
+    DevBuf pdt;
+    Addr at{};
+    int pad = 0;
+    int tiled = -1;              // layout the copy was built with
+    // code_n = palette entries with the two stop codes, 0 = none (option off, geometry does not fit, or more distinct
+    // steps than plan::CODE_MAX_ENTRIES)
+    DevBuf cmap, cval, cidx, ctab, cnum;
+    Pinned<uint32_t> pin_cnum;   // (made with the first code map)
+    int code_n = 0;
+    int code_built = -1;         // code_map value the tables were built for
+    Addr code_at{};
+    TableCache cache;
+    // THE freshness test: built from this map, in the layout these options ask for, for this code_map option
+    bool fresh_for(const rl_map *m, float max_range, const rl_plan_opts &o) const;
+    // palette size a plan for this map and these options may count on (0: no code map, or not the one built)
+    int code_entries_for(const rl_map *m, float max_range, const rl_plan_opts &o) const;
+    // the march's address constants of the float32 map, or of the code map
+    scan::PadMap pad_map(bool code, float res) const;
+};
+
+struct LutTable {                // GiantLUT (K3)
+    DevBuf buf;
+    LutParams lp{};
+    TableCache cache;
+};
+
+struct CddtTable {               // CDDT (K3b)
+    DevBuf cos, sin, trans, width, boff, offsets, xs2, cursor, tmp, hdr, tab;
+    CddtParams cdp{};
+    uint32_t buckets = 0;
+    std::vector<float> h_cos, h_sin, h_trans;              // per-bin constants (host copies stay alive:
+    std::vector<int> h_width;                              //  their uploads are asynchronous)
+    std::vector<uint32_t> h_boff;
+    int geom_rows = -1, geom_cols = -1;                    // map shape the constants were made for
+    bool sort_attr = false;
+    bool counts_clean = false;                             // bucket counters are all zero (see build_cddt)
+    int lds_sort = (int)CDDT_LDS_SORT;                     // buckets up to this size are sorted in LDS (diagnostics: lower it)
+    TableCache cache;
+};
+
+struct BlPadMaps {               // K2b: padded normal + transposed bit maps (bl_pad_bits_kernel)
+    DevBuf buf;
+    BlPad blp{};
+    TableCache cache;
+};
+
+// beam-direction tables (cos, sin per beam) of the fans a handle has been called with: they depend on the fan, not on
+// the map, so each has the dependency half of the protocol only
+struct FanTabs {
+    struct Tab {
+        uint32_t fov_bits = 0;
+        int num_rays = 0;
+        uint64_t last_use = 0;
+        DevBuf tab;
+        TableDep dep;
+    } tabs[4];
+    uint64_t clock = 0;
 };
 
 
@@ -464,29 +584,12 @@ struct rl_method {
     int handoff_cap = 16;        //   ... rays per wave handed over (8, 16, 32 or 64)
     int handoff_wg = 256;        //   ... workgroup size of the leftover launch (64, 128 or 256)
     int nt_store = 1;            // ranges leave the stream kernels with non-temporal stores (0: plain — a consumer kernel reads them next)
-    // GiantLUT (K3)
-    DevBuf lut;
-    uint64_t lut_epoch = ~0ull;
-    LutParams lp{};
-    // CDDT (K3b)
-    DevBuf cd_cos, cd_sin, cd_trans, cd_width, cd_boff, cd_offsets, cd_xs2, cd_cursor, cd_tmp, cd_hdr, cd_tab;
-    uint64_t cddt_epoch = ~0ull;
-    CddtParams cdp{};
-    uint32_t cd_buckets = 0;
-    std::vector<float> cd_h_cos, cd_h_sin, cd_h_trans;     // per-bin constants (host copies stay alive:
-    std::vector<int> cd_h_width;                           //  their uploads are asynchronous)
-    std::vector<uint32_t> cd_h_boff;
-    int cd_geom_rows = -1, cd_geom_cols = -1;              // map shape the constants were made for
-    bool cd_sort_attr = false;
-    bool cd_counts_clean = false;                          // bucket counters are all zero (see ensure_cddt)
-    int cddt_lds_sort = (int)CDDT_LDS_SORT;                // buckets up to this size are sorted in LDS (diagnostics: lower it)
-    DevBuf blpad;                // K2b: padded normal + transposed bit maps (bl_pad_bits_kernel)
-    BlPad blp{};
-    uint64_t blpad_epoch = ~0ull;
-    TableDep blpad_dep;
-    DevBuf pdt;                  // EDT with a border of `pad` cells of -1 (stream kernel)
-    int pad = 0, pstride = 0;    // pstride: elements per row (row-major) | M (tiled, see pdt_tiled_byte)
-    uint64_t pdt_epoch = ~0ull;  // map epoch the padded copy was built from
+    // the derived tables (above): which of them a handle ever builds follows from its kind
+    StepMap step;
+    LutTable lut;
+    CddtTable cddt;
+    BlPadMaps blpad;
+    FanTabs fans;
     Stream stream;
     Stream copy_stream;                  // big host-pointer calls (made by the first one): the D2H copy of pose slice k overlaps the march of slice k+1
     Event slice_ev[4];
@@ -510,16 +613,6 @@ struct rl_method {
     int pf_block = 0;            // particles per tile of the weight kernels (0: sized from the shape, make_pf)
     LaunchCtx ctx[N_LAUNCH_CTX];
     uint64_t use_clock = 0;
-    TableDep pdt_dep, lut_dep, cddt_dep;
-    // beam-direction tables (cos, sin per beam) of the fans this handle has been called with
-    struct FanTab {
-        uint32_t fov_bits = 0;
-        int num_rays = 0;
-        uint64_t last_use = 0;
-        DevBuf tab;
-        TableDep dep;
-    } fan_tabs[4];
-    uint64_t fan_clock = 0;
     // small host calls (scan(): one pose, scanMany(): a roll-out): poses and ranges go through ONE
     // pinned, device-mapped host buffer the kernels read / write directly — no staging copies
     Pinned<char> pin;
@@ -534,19 +627,6 @@ struct rl_method {
     Pinned<int> pin_flag;          // pinned landing slot for the crash index
     int tile_stripe = -1;        // binning order: tile rows per stripe walked column-major (rm_kernels.h tile_key); 0: row-major, -1: by xcd_bands
     int bin_ppw = POSES_PER_WG;  // ... poses per workgroup of those kernels
-    int pdt_tiled = -1;          // layout the padded copy was built with
-    uint32_t pdt_k4 = 0, pdt_mask = 0;
-    size_t pdt_base_off = 0;     // tiled: the column bias (pad << 4 bytes) folded into the base address
-    // the CODE map (option code_map = 2): the step map as u16 palette codes + the palette (rm_kernels.h), built next to
-    // the float32 step map by ensure_step_map; code_n = palette entries with the two stop codes, 0 = none (option off,
-    // geometry does not fit, or more distinct steps than plan::CODE_MAX_ENTRIES)
-    DevBuf cmap, cval, cidx, ctab, cnum;
-    Pinned<uint32_t> pin_cnum;   // (made with the first code map)
-    int code_n = 0;
-    int code_built = -1;         // code_map value the tables were built for
-    int cstride = 0;             // M of the code map's address
-    uint32_t ck4 = 0, cmask = 0;
-    size_t cbase_off = 0;
     int last_grid = 0;
     void *last_dbg = nullptr;    // stamps buffer of the last launch (in its context)
     rl_launch_plan last_plan{};  // what the last fan launch of this handle was planned as (plan::plan_fan)

@@ -21,15 +21,17 @@ NOISE_SITES = [
     ("literal_kernels.h", "rm_literal_kernel", "test_noise_literal_kernels; test_noise_many_rays_entry_points (variant 3)"),
 ]
 
-#: (source file, epoch field of the guard, the table it guards, the case that fails when the guard goes stale)
+#: (source file, the freshness test asked, the table it guards, the case that fails when the answer goes stale)
 TABLE_CACHES = [
-    ("abi_fan.hip", "lut_epoch", "ensure_lut: GiantLUT table", "test_warm_handles_follow_a_mutation_script (LUT)"),
-    ("abi_fan.hip", "cddt_epoch", "ensure_cddt: CDDT blocked table",
+    ("abi_fan.hip", "lut.cache.fresh_for", "ensure_lut: GiantLUT table", "test_warm_handles_follow_a_mutation_script (LUT)"),
+    ("abi_fan.hip", "cddt.cache.fresh_for", "ensure_cddt: CDDT blocked table",
      "test_warm_handles_follow_a_mutation_script (CDDT pose-major, theta-major, lds_sort 128); test_multi_device_map_mutations"),
-    ("abi_fan.hip", "blpad_epoch", "ensure_blpad: Bresenham padded bit maps",
+    ("abi_fan.hip", "blpad.cache.fresh_for", "ensure_blpad: Bresenham padded bit maps",
      "test_warm_handles_follow_a_mutation_script (BL variant 1)"),
-    ("abi_fan.hip", "pdt_epoch", "opts_of: code_entries the planner sees",
+    ("abi_fan.hip", "step.code_entries_for", "opts_of: code_entries the planner sees",
      "test_code_map_palette_follows_updates"),
-    ("abi_fan.hip", "pdt_epoch", "ensure_step_map: step map, code map and palette",
+    ("abi_fan.hip", "step.fresh_for", "ensure_step_map: step map, code map and palette",
      "test_warm_handles_follow_a_mutation_script (RM, RMGPU code map / row-major); test_entry_points_after_a_stamp"),
+    ("abi_fan.hip", "cache.fresh_for", "StepMap::fresh_for: the epoch third of the step map's one test, behind the two rows above",
+     "test_warm_handles_follow_a_mutation_script (RM, RMGPU code map / row-major); test_code_map_palette_follows_updates"),
 ]

@@ -7,14 +7,15 @@ bit for bit, and first asserts that the oracle's answer on the new grid differs 
 a handle that served a stale table would fail.  Each probe is called twice after a mutation (the first call rebuilds,
 the second takes the cached tables).
 
-tests/coverage_tables.py TABLE_CACHES names the case that covers each ``*_epoch == m->epoch`` guard under csrc/; tests/test_host.py keeps it in
-step with the sources."""
+tests/coverage_tables.py TABLE_CACHES names the case that covers each site under csrc/ that asks a table's cache whether
+it is still good for the map (``fresh_for``); tests/test_host.py keeps it in step with the sources."""
 import threading
 
 import numpy as np
 import pytest
 
 import support
+from table_cases import all_equal as _all_equal, cddt_ranges, rm_ranges
 from pyracecarsimulator_amd import _lib, maps, range_libc
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("need_gpu")]
@@ -125,10 +126,6 @@ def _fan(m, poses, aux=False):
     return out, hits, steps
 
 
-def _all_equal(a, b):
-    return all(np.array_equal(x, y) for x, y in zip(a, b))
-
-
 def _apply(omap, action):
     if action[0] == "stamp":
         omap.stamp_cells(action[1], value=action[2])
@@ -201,7 +198,7 @@ def test_warm_handles_follow_a_mutation_script(oracle_mod):
         return r[0], np.array([first_many]), groups
 
     def code_ref(o):
-        r = o.rm_fan(poses, FOV, B, step_coeff=1.0, nthreads=8, want_hits=False, want_steps=False)[0]
+        r = rm_ranges(o, poses, FOV, B)
         return r, np.array([oracle_mod.is_crashed(r, B, len(poses), edge, 0.001)]), \
             np.array([oracle_mod.is_crashed(r[k * grp * B:(k + 1) * grp * B], B, grp, edge, 0.001) for k in range(2)])
     probes.append(("RMGPU code map + crash", code_fan, lambda o: code_ref(o)))
@@ -211,7 +208,7 @@ def test_warm_handles_follow_a_mutation_script(oracle_mod):
     probes.append(("RMGPU tiled 0", lambda: _fan(rowmajor, poses, aux=True),
                    lambda o: o.rm_fan(poses, FOV, B, step_coeff=1.0, nthreads=8)))
     probes.append(("RMGPU tiled 0 ranges", lambda: _fan(rowmajor, poses),
-                   lambda o: o.rm_fan(poses, FOV, B, step_coeff=1.0, nthreads=8, want_hits=False, want_steps=False)[:1]))
+                   lambda o: (rm_ranges(o, poses, FOV, B),)))
     for variant in (0, 1):
         m = range_libc.PyBresenhamsLine(omap, MRX)
         m.set_option("variant", variant)
@@ -222,7 +219,7 @@ def test_warm_handles_follow_a_mutation_script(oracle_mod):
         m = range_libc.PyCDDTCast(omap, MRX, TD)
         for k, v in opts.items():
             m.set_option(k, v)
-        probes.append(("CDDT " + label, lambda m=m: _fan(m, poses), lambda o: (o.cddt_fan(TD, poses, FOV, B, nthreads=8),)))
+        probes.append(("CDDT " + label, lambda m=m: _fan(m, poses), lambda o: (cddt_ranges(o, TD, poses, FOV, B),)))
     _run_script(oracle_mod, omap, g, base0, steps, probes)
     omap.close()
 
@@ -328,8 +325,8 @@ def test_entry_points_after_a_stamp(oracle_mod):
         return outs, fan4, d_out.cpu().numpy(), d_first.cpu().numpy(), first
 
     def ref(o):
-        fan = o.rm_fan(poses, FOV, B, step_coeff=1.0, nthreads=8, want_hits=False, want_steps=False)[0]
-        rr = o.rm_fan(roll_poses, FOV, B, step_coeff=1.0, nthreads=8, want_hits=False, want_steps=False)[0]
+        fan = rm_ranges(o, poses, FOV, B)
+        rr = rm_ranges(o, roll_poses, FOV, B)
         return (o.rm_rays_libm(ins, step_coeff=0.999), o.rm_fan_libm(poses, FOV, B, step_coeff=0.999)[0], fan,
                 np.array([oracle_mod.is_crashed(fan[k * group * B:(k + 1) * group * B], B, group, edge, 0.001)
                           for k in range(4)], np.int32),
@@ -363,8 +360,8 @@ def test_multi_device_map_mutations(oracle_mod):
     cd.set_option("multi_min_poses", 1)
     assert rm.n_devices == 2 and cd.n_devices == 2
     probes = [("multi RMGPU", lambda: _fan(rm, poses),
-               lambda o: (o.rm_fan(poses, FOV, B, step_coeff=1.0, nthreads=8, want_hits=False, want_steps=False)[0],)),
-              ("multi CDDT", lambda: _fan(cd, poses), lambda o: (o.cddt_fan(TD, poses, FOV, B, nthreads=8),))]
+               lambda o: (rm_ranges(o, poses, FOV, B),)),
+              ("multi CDDT", lambda: _fan(cd, poses), lambda o: (cddt_ranges(o, TD, poses, FOV, B),))]
     # outline A, the growth path, the update, a stamp on the new base
     _run_script(oracle_mod, omap, g, base0, [steps[0], steps[2], steps[6], steps[7]], probes)
     omap.close()

@@ -552,25 +552,34 @@ def test_every_noise_call_site_has_a_gpu_case():
 
 
 def test_every_table_cache_guard_has_a_gpu_case():
-    """tests/coverage_tables.py TABLE_CACHES names the case that checks each lazily rebuilt per-handle table
-    (a ``*_epoch == <map>->epoch`` guard under csrc/) after a map mutation: a new cache must add a row (and a case)."""
+    """tests/coverage_tables.py TABLE_CACHES names the case that checks each lazily rebuilt per-handle table after a map
+    mutation.  A table is still good when its TableCache says so (csrc/abi_internal.h): the one comparison with the
+    map's epoch is TableCache::fresh_for, and every site that asks it — ``<table>.cache.fresh_for(``, the step map's own
+    ``fresh_for(`` and ``code_entries_for(`` — has a row, per file and per count: a new cache, or a new place that
+    decides for an old one, must add a row (and a case)."""
     from coverage_tables import TABLE_CACHES
     csrc = os.path.join(ROOT, "pyracecarsimulator_amd", "csrc")
-    guard = re.compile(r"\b(\w+_epoch)\s*==\s*(?:\w+->)?(?:m|map)->epoch\b")
-    found = {}
+    site = re.compile(r"((?:\w+\.)*\w+)\.(fresh_for|code_entries_for)\s*\(")
+    compare = re.compile(r"epoch\s*[!=]=|[!=]=\s*[\w.>-]*epoch\b")
+    found, compares = {}, []
     for name in sorted(os.listdir(csrc)):
         if not name.endswith((".h", ".hip", ".cpp")):
             continue
         with open(os.path.join(csrc, name), errors="replace") as f:
             for line in f:
-                for field in guard.findall(line.split("//")[0]):
-                    found[(name, field)] = found.get((name, field), 0) + 1
+                code = line.split("//")[0]
+                for recv, call in site.findall(code):
+                    found[(name, recv + "." + call)] = found.get((name, recv + "." + call), 0) + 1
+                if compare.search(code):
+                    compares.append((name, code.strip()))
     table = {}
     for fname, field, what, case in TABLE_CACHES:
         table[(fname, field)] = table.get((fname, field), 0) + 1
         assert what.strip() and case.strip()
-    assert found, "no epoch guard found under csrc/"
+    assert found, "no freshness test found under csrc/"
     assert found == table
+    # no table is compared with the map's epoch behind the protocol's back
+    assert compares == [("abi_internal.h", "bool fresh_for(const rl_map *m) const { return epoch == m->epoch; }")], compares
 
 
 def test_stamp_indices_filter_on_the_integer_value():
