@@ -1,12 +1,31 @@
-"""ctypes loader for libscan_amd.so (C ABI: include/scanlib.h).
+"""ctypes loader for libscan_amd.so (C ABI: include/scanlib.h) and the one call layer of the package.
 
 The library is the product: hand-written HIP kernels for gfx950 behind a C ABI.
 There is no Python/NumPy fallback — if the shared object is missing or no HIP
 device is usable, the calls raise.
+
+``SYMBOLS`` restates every prototype of the header (tests/test_py_calls_host.py pins it to the header, argument by
+argument, with the structures and enums below).  ``call(name, *args)`` is how the package's wrappers enter the library:
+every argument is converted by the type ``SYMBOLS`` declares for it, and a symbol that returns ``rl_status`` is checked
+(``ScanLibError``) and gives None.  What a declared type takes:
+
+* pointer to a scalar (``float *``, ``int *``, ``uint64_t *`` ...): an ``ndarray`` of exactly that dtype, C-contiguous
+  (anything else is a ``TypeError`` naming symbol and position — never a silent copy, an output would be lost); None
+  (NULL); a ctypes scalar of the pointee type, passed by reference (an out-parameter);
+* ``void **`` (a handle out) and pointer to a ``Structure``: the instance, by reference; None (NULL);
+* ``void *`` (handles, device pointers, streams): a ``Handle`` or its ``_h``; None or 0 (NULL); an int (an address).
+  An ``ndarray`` is refused: a host array where a handle or device pointer is wanted;
+* ``const char *``: a ``str`` (encoded) or ``bytes``;
+* scalars: ``int()`` / ``float()`` of the argument (NumPy scalars and bools pass);
+* ``const float *const *`` (rl_policy_create): a sequence of float32 arrays, each checked as above.
+
+``lib()`` is the typed CDLL for direct use (tests, tools, bench.py); ``raw(name)`` the all-``void *`` form for callers
+that keep the addresses of long-lived buffers.
 """
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import os
 import subprocess
 
@@ -15,7 +34,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("SCANLIB_SO") or os.path.join(_HERE, "libscan_amd.so")
 _LIB = None
 
-RL_OK = 0
+RL_OK, RL_ERR_INVALID, RL_ERR_NO_DEVICE, RL_ERR_HIP, RL_ERR_UNSUPPORTED, RL_ERR_NOMEM = 0, -1, -2, -3, -4, -5
 RL_BRESENHAM, RL_RM, RL_RM_GPU, RL_CDDT, RL_GIANT_LUT = 0, 1, 2, 3, 4
 
 f32p = C.POINTER(C.c_float)
@@ -23,7 +42,6 @@ f64p = C.POINTER(C.c_double)
 i32p = C.POINTER(C.c_int32)
 u16p = C.POINTER(C.c_uint16)
 u8p = C.POINTER(C.c_uint8)
-
 
 
 class PlanOpts(C.Structure):
@@ -231,20 +249,24 @@ SYMBOLS = {
     "rl_ranges_from_u16_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
 }
 
+#: the symbols whose ``int`` is a value; every other ``int`` function returns rl_status (``call`` checks it)
+INT_VALUED = frozenset(("rl_device_count", "rl_launch_contexts", "rl_map_rows", "rl_map_cols", "rl_map_device",
+                        "rl_map_n_devices", "rl_method_kind", "rl_method_n_devices", "rl_debug_read_stamps"))
+
 
 def plan_fan(kind, rows, cols, n_poses, num_rays, max_range_px=300.0, theta_disc=0, n_cu=256, aux=False,
              crash=False, **opts):
     """The launch plan of a fan call (rl_plan_fan: pure host arithmetic, no device needed) as a dict.
     ``opts`` override fields of the default rl_plan_opts."""
     o = PlanOpts()
-    check(lib().rl_plan_default_opts(C.byref(o)))
+    call("rl_plan_default_opts", o)
     for k, v in opts.items():
         if not hasattr(o, k):
             raise KeyError("unknown plan option %r" % k)
         setattr(o, k, int(v))
     pl = LaunchPlan()
-    check(lib().rl_plan_fan(int(kind), int(n_cu), int(rows), int(cols), float(max_range_px), int(theta_disc),
-                            C.byref(o), int(n_poses), int(num_rays), int(bool(aux)), int(bool(crash)), C.byref(pl)))
+    call("rl_plan_fan", kind, n_cu, rows, cols, max_range_px, theta_disc, o, n_poses, num_rays, bool(aux), bool(crash),
+         pl)
     return pl.as_dict()
 
 
@@ -336,6 +358,85 @@ def raw(name):
 def check(code: int) -> None:
     if code != RL_OK:
         raise ScanLibError(code, lib().rl_last_error().decode("utf-8", "replace"))
+
+
+def _refuse(name, i, what, a):
+    return TypeError("%s argument %d: %s, got %s" % (name, i, what, getattr(a, "dtype", type(a).__name__)))
+
+
+def _converter(name, i, t):
+    """What ``call`` does to argument ``i`` (declared type ``t``) of ``name``: see the module text."""
+    import numpy as np
+    if t is C.c_void_p:
+        def conv(a):
+            if type(a) is int:                             # (first: the device forms pass addresses, call after call)
+                return a or None
+            if isinstance(a, Handle):
+                return a._h
+            if a is None or isinstance(a, C.c_void_p):
+                return a
+            if isinstance(a, np.ndarray):
+                raise _refuse(name, i, "a handle or device address, not a host array", a)
+            return operator.index(a) or None
+    elif t is C.c_char_p:
+        def conv(a):
+            return a.encode() if isinstance(a, str) else a
+    elif not issubclass(t, C._Pointer):
+        conv = float if t in (C.c_float, C.c_double) else int
+    elif issubclass(t._type_, C._Pointer):                 # const float *const *
+        inner = _converter(name, i, t._type_)
+
+        def conv(a):
+            return (C.c_void_p * len(a))(*[inner(x) for x in a])
+    elif issubclass(t._type_, (C.Structure, C.c_void_p)):
+        cls = t._type_
+
+        def conv(a):
+            if a is None:
+                return None
+            if not isinstance(a, cls):
+                raise _refuse(name, i, "a %s" % cls.__name__, a)
+            return C.addressof(a)
+    else:
+        cls, dt = t._type_, np.dtype(t._type_)
+
+        def conv(a):
+            if isinstance(a, np.ndarray):
+                if a.dtype != dt or not a.flags.c_contiguous:
+                    raise _refuse(name, i, "a C-contiguous %s array" % dt, a)
+                return a.ctypes.data
+            if a is None:
+                return None
+            if not isinstance(a, cls):
+                raise _refuse(name, i, "a %s array, a %s or None" % (dt, cls.__name__), a)
+            return C.addressof(a)
+    return conv
+
+
+_CALLS = {}
+
+
+def converters(name):
+    """(the all-``void *`` entry point, one converter per argument, returns rl_status?) of ``name``, built once."""
+    ent = _CALLS.get(name)
+    if ent is None:
+        res, args = SYMBOLS[name]
+        ent = _CALLS[name] = (raw(name), tuple(_converter(name, i, t) for i, t in enumerate(args)),
+                              res is C.c_int and name not in INT_VALUED)
+    return ent
+
+
+def call(name, *args):
+    """Enter the library at ``name`` with ``args`` converted by their declared types (the module text says how).  A
+    symbol that returns rl_status gives None or raises ``ScanLibError``; any other gives its value."""
+    fn, convs, status = converters(name)
+    if len(args) != len(convs):
+        raise TypeError("%s takes %d arguments, got %d" % (name, len(convs), len(args)))
+    rc = fn(*[cv(a) for cv, a in zip(convs, args)])
+    if not status:
+        return rc
+    if rc:
+        check(rc)
 
 
 class Handle:

@@ -394,8 +394,8 @@ class ShardedScan:
         from . import _lib
         vq = sl.views_q[ci]
         if self._dev_index >= 0:
-            _lib.check(_lib.lib().rl_ranges_to_u16_device(self._dev_index, view.data_ptr(), view.numel(),
-                                                          self.max_range_m, vq.data_ptr(), sl.sptr or None))
+            _lib.call("rl_ranges_to_u16_device", self._dev_index, view.data_ptr(), view.numel(), self.max_range_m,
+                      vq.data_ptr(), sl.sptr)
         else:                                   # CPU tests (gloo): the same arithmetic in torch
             q = self.torch.round(view.clamp(0.0, self.max_range_m) * (65535.0 / self.max_range_m))
             vq.copy_((q.to(self.torch.int32) - ((q >= 32768).to(self.torch.int32) << 16)).to(self.torch.int16))
@@ -410,9 +410,8 @@ class ShardedScan:
             return
         if self._dev_index >= 0:
             from . import _lib
-            _lib.check(_lib.lib().rl_ranges_from_u16_device(self._dev_index, sl.gathered_q.data_ptr(),
-                                                            sl.gathered_q.numel(), self.max_range_m,
-                                                            sl.gathered.data_ptr(), sl.sptr or None))
+            _lib.call("rl_ranges_from_u16_device", self._dev_index, sl.gathered_q.data_ptr(), sl.gathered_q.numel(),
+                      self.max_range_m, sl.gathered.data_ptr(), sl.sptr)
         else:
             q = sl.gathered_q.to(self.torch.int32) & 0xffff
             sl.gathered.copy_(q.to(self.torch.float32) * (self.max_range_m / 65535.0))

@@ -33,7 +33,6 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import f32p, f64p, i32p
 from .track import Track, track_env_args
 
 
@@ -145,8 +144,7 @@ class DriveEnv(_lib.Handle):
             self.attach_track(track, tp)
 
     def _create(self, car, method, p, ed, st):
-        _lib.check(_lib.lib().rl_env_create(car._h, method._h, C.byref(p), ed.ctypes.data_as(f64p),
-                                            st.ctypes.data_as(f64p), st.shape[0], C.byref(self._h)))
+        _lib.call("rl_env_create", car, method, p, ed, st, st.shape[0], self._h)
 
     @staticmethod
     def _method_device(method):
@@ -167,7 +165,7 @@ class DriveEnv(_lib.Handle):
         """Attach ``track`` (None: detach) with ``params`` (``track_env_args``'s result) or its keywords.  The env needs
         a ``reset`` afterwards."""
         tp = params if params is not None else track_env_args(**kw)
-        _lib.check(_lib.lib().rl_env_attach_track(self._h, track._h if track is not None else None, C.byref(tp)))
+        _lib.call("rl_env_attach_track", self, track, tp)
         self.track = track            # (borrowed by the library: kept alive here)
         self._track_torch = None
 
@@ -183,11 +181,10 @@ class DriveEnv(_lib.Handle):
                 self._track_torch = (torch.empty((self._n, 8), dtype=torch.float32, device=dev),
                                      torch.empty((self._n, 4), dtype=torch.int32, device=dev))
             rows, ints = self._track_torch
-            _lib.check(_lib.lib().rl_env_read_track_device(self._h, C.c_void_p(rows.data_ptr()),
-                                                           C.c_void_p(ints.data_ptr()), C.c_void_p(self._stream())))
+            _lib.call("rl_env_read_track_device", self, rows.data_ptr(), ints.data_ptr(), self._stream())
         else:
             rows, ints = np.empty((self._n, 8), np.float32), np.empty((self._n, 4), np.int32)
-            _lib.check(_lib.lib().rl_env_read_track(self._h, rows.ctypes.data_as(f32p), ints.ctypes.data_as(i32p)))
+            _lib.call("rl_env_read_track", self, rows, ints)
         return self._track_dict(rows, ints)
 
     @staticmethod
@@ -237,10 +234,8 @@ class DriveEnv(_lib.Handle):
                     raise ValueError("on_device=True takes start_index as a torch tensor (or None)")
                 self._check_tensor(start_index, (self._n_idx,), "int32", "start_index")
                 sidx = start_index.data_ptr()
-            _lib.check(_lib.lib().rl_env_reset_device(
-                self._h, seed, C.c_void_p(sidx), C.c_void_p(t["obs"].data_ptr()),
-                C.c_void_p(t["aux"].data_ptr()) if aux else None, C.c_void_p(t["done"].data_ptr()),
-                C.c_void_p(self._stream())))
+            _lib.call("rl_env_reset_device", self, seed, sidx, t["obs"].data_ptr(),
+                      t["aux"].data_ptr() if aux else None, t["done"].data_ptr(), self._stream())
             return (t["obs"], t["aux"]) if aux else t["obs"]
         sidx = None
         if start_index is not None:
@@ -253,9 +248,7 @@ class DriveEnv(_lib.Handle):
         obs = np.empty(self.obs_shape, np.float32)
         done = np.empty(self._n, np.int32)
         ax = np.empty((self._n, 4), np.float32) if aux else None
-        _lib.check(_lib.lib().rl_env_reset(self._h, seed, sidx.ctypes.data_as(i32p) if sidx is not None else None,
-                                           obs.ctypes.data_as(f32p), ax.ctypes.data_as(f32p) if aux else None,
-                                           done.ctypes.data_as(i32p)))
+        _lib.call("rl_env_reset", self, seed, sidx, obs, ax, done)
         return (obs, ax) if aux else obs
 
     def step(self, actions, aux=False):
@@ -267,10 +260,8 @@ class DriveEnv(_lib.Handle):
         if self._is_tensor(actions):
             self._check_tensor(actions, (self._n, 2), "float32", "actions")
             t = self._tensors()
-            _lib.check(_lib.lib().rl_env_step_device(
-                self._h, C.c_void_p(actions.data_ptr()), C.c_void_p(t["obs"].data_ptr()),
-                C.c_void_p(t["reward"].data_ptr()), C.c_void_p(t["done"].data_ptr()),
-                C.c_void_p(t["aux"].data_ptr()) if aux else None, C.c_void_p(self._stream())))
+            _lib.call("rl_env_step_device", self, actions.data_ptr(), t["obs"].data_ptr(), t["reward"].data_ptr(),
+                      t["done"].data_ptr(), t["aux"].data_ptr() if aux else None, self._stream())
             return (t["obs"], t["reward"], t["done"]) + ((t["aux"],) if aux else ())
         a = np.asarray(actions)
         if a.dtype != np.float32 or a.shape != (self._n, 2):
@@ -280,9 +271,7 @@ class DriveEnv(_lib.Handle):
         reward = np.empty(self._n, np.float32)
         done = np.empty(self._n, np.int32)
         ax = np.empty((self._n, 4), np.float32) if aux else None
-        _lib.check(_lib.lib().rl_env_step(self._h, a.ctypes.data_as(f32p), obs.ctypes.data_as(f32p),
-                                          reward.ctypes.data_as(f32p), done.ctypes.data_as(i32p),
-                                          ax.ctypes.data_as(f32p) if aux else None))
+        _lib.call("rl_env_step", self, a, obs, reward, done, ax)
         return (obs, reward, done) + ((ax,) if aux else ())
 
     def read(self):
@@ -291,9 +280,7 @@ class DriveEnv(_lib.Handle):
         out = dict(states=np.empty((self._n, 11)), ticks=np.empty(self._n, np.int32),
                    episodes=np.empty(self._n, np.int32), start_index=np.empty(self._n, np.int32),
                    done=np.empty(self._n, np.int32))
-        _lib.check(_lib.lib().rl_env_read(self._h, out["states"].ctypes.data_as(f64p), out["ticks"].ctypes.data_as(i32p),
-                                          out["episodes"].ctypes.data_as(i32p),
-                                          out["start_index"].ctypes.data_as(i32p), out["done"].ctypes.data_as(i32p)))
+        _lib.call("rl_env_read", self, *out.values())
         return out
 
 
@@ -317,8 +304,7 @@ class RaceEnv(DriveEnv):
     def _create(self, car, method, p, ed, st):
         rp = _lib.RaceEnvParams()
         rp.env, rp.group, rp.min_running = p, self._group, self._min_running
-        _lib.check(_lib.lib().rl_env_create_race(car._h, method._h, C.byref(rp), ed.ctypes.data_as(f64p),
-                                                 st.ctypes.data_as(f64p), st.shape[0] // self._group, C.byref(self._h)))
+        _lib.call("rl_env_create_race", car, method, rp, ed, st, st.shape[0] // self._group, self._h)
 
     @property
     def n_races(self):
@@ -356,5 +342,5 @@ class RaceEnv(DriveEnv):
         out = {k: self._rows(v) for k, v in super().read().items()}
         names = ("race_ticks", "race_episodes", "race_start_index", "race_over")
         out.update((k, np.empty(self._races, np.int32)) for k in names)
-        _lib.check(_lib.lib().rl_env_read_races(self._h, *(out[k].ctypes.data_as(i32p) for k in names)))
+        _lib.call("rl_env_read_races", self, *(out[k] for k in names))
         return out

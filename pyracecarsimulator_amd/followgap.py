@@ -17,7 +17,6 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import f32p
 
 
 class PyFollowGap(_lib.Handle):
@@ -30,8 +29,8 @@ class PyFollowGap(_lib.Handle):
         self.window_size, self.max_distance = int(ws), float(md)
         self.max_angle, self.angle_inc = float(ma), float(angle_inc)
         self._h = C.c_void_p()
-        _lib.check(_lib.lib().rl_followgap_create(int(device), self.window_size, self.max_distance,
-                                                  self.max_angle, self.angle_inc, C.byref(self._h)))
+        _lib.call("rl_followgap_create", device, self.window_size, self.max_distance, self.max_angle, self.angle_inc,
+                  self._h)
 
     @staticmethod
     def _f32c(a, what):
@@ -49,8 +48,7 @@ class PyFollowGap(_lib.Handle):
         if size > lidar.shape[0]:
             raise ValueError("size exceeds the scan length")
         out = np.empty(1, dtype=np.float32)
-        _lib.check(_lib.lib().rl_followgap_eval(self._h, lidar.ctypes.data_as(f32p), 1, size,
-                                                out.ctypes.data_as(f32p)))
+        _lib.call("rl_followgap_eval", self, lidar, 1, size, out)
         return float(out[0])
 
     def eval_many(self, scans, size=None):
@@ -65,13 +63,10 @@ class PyFollowGap(_lib.Handle):
             size = int(size)
             n = scans.size // size
         out = np.empty(n, dtype=np.float32)
-        _lib.check(_lib.lib().rl_followgap_eval(self._h, scans.ctypes.data_as(f32p), int(n), int(size),
-                                                out.ctypes.data_as(f32p)))
+        _lib.call("rl_followgap_eval", self, scans, n, size, out)
         return out
 
     def eval_many_device(self, d_scans_ptr, n_scans, size, d_angles_ptr, stream=0):
         """Device-resident form: ``d_scans_ptr`` -> float32[n_scans*size] (e.g. the output of
         ``calc_range_fan_device``), ``d_angles_ptr`` -> float32[n_scans]; asynchronous on ``stream``."""
-        _lib.check(_lib.lib().rl_followgap_eval_device(self._h, C.c_void_p(int(d_scans_ptr)), int(n_scans),
-                                                       int(size), C.c_void_p(int(d_angles_ptr)),
-                                                       C.c_void_p(int(stream))))
+        _lib.call("rl_followgap_eval_device", self, int(d_scans_ptr), n_scans, size, int(d_angles_ptr), int(stream))

@@ -20,7 +20,6 @@ import time
 import numpy as np
 
 from . import _lib
-from ._lib import f32p, f64p, i32p
 
 SOURCES = {"fg": _lib.RL_MCTS_FG, "nn": _lib.RL_MCTS_NN, "random": _lib.RL_MCTS_RANDOM}
 TREE_FIELDS = ("parent", "first_child", "next_sibling", "n_children", "visits", "child_visits", "reward", "action",
@@ -109,9 +108,7 @@ class MCTSPlanner(_lib.Handle):
         self.n_trees, self.max_nodes, self.source = int(n_trees), int(max_nodes), source
         self._keep = (car, method, followgap, policy)
         self._h = C.c_void_p()
-        _lib.check(_lib.lib().rl_mcts_create(car._h, method._h, followgap._h if followgap is not None else None,
-                                             policy._h if policy is not None else None, C.byref(p),
-                                             self._edge.ctypes.data_as(f64p), C.byref(self._h)))
+        _lib.call("rl_mcts_create", car, method, followgap, policy, p, self._edge, self._h)
 
     def reset(self, root_states, root_actions, seeds):
         """The K roots: states float64 (K, 11) in getState layout, recent actions (K,), one 64-bit seed per tree."""
@@ -119,18 +116,16 @@ class MCTSPlanner(_lib.Handle):
         st = np.ascontiguousarray(np.asarray(root_states, np.float64).reshape(K, 11))
         ac = np.ascontiguousarray(np.broadcast_to(np.asarray(root_actions, np.float64), (K,)))
         sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, np.uint64), (K,)))
-        _lib.check(_lib.lib().rl_mcts_reset(self._h, st.ctypes.data_as(f64p), ac.ctypes.data_as(f64p),
-                                            sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+        _lib.call("rl_mcts_reset", self, st, ac, sd)
 
     def run(self, n_iterations):
-        _lib.check(_lib.lib().rl_mcts_run(self._h, int(n_iterations)))
+        _lib.call("rl_mcts_run", self, n_iterations)
 
     def best(self):
         """(best root action float64 (K,), its visits int32 (K,), nodes per tree int32 (K,))."""
         K = self.n_trees
         a, v, n = np.empty(K), np.empty(K, np.int32), np.empty(K, np.int32)
-        _lib.check(_lib.lib().rl_mcts_best(self._h, a.ctypes.data_as(f64p), v.ctypes.data_as(i32p),
-                                           n.ctypes.data_as(i32p)))
+        _lib.call("rl_mcts_best", self, a, v, n)
         return a, v, n
 
     def read_tree(self, tree):
@@ -141,12 +136,7 @@ class MCTSPlanner(_lib.Handle):
         out.update(reward=np.empty(N), action=np.empty(N), state=np.empty((N, 11)),
                    scan_pose=np.empty((N, 3), np.float32), answer=np.empty(N, np.float32))
         n = C.c_int(0)
-        ptr = lambda f, t: out[f].ctypes.data_as(t)
-        _lib.check(_lib.lib().rl_mcts_read_tree(
-            self._h, int(tree), ptr("parent", i32p), ptr("first_child", i32p), ptr("next_sibling", i32p),
-            ptr("n_children", i32p), ptr("visits", i32p), ptr("child_visits", i32p), ptr("reward", f64p),
-            ptr("action", f64p), ptr("terminal", i32p), ptr("state", f64p), ptr("scan_pose", f32p),
-            ptr("answer", f32p), ptr("crash", i32p), C.byref(n)))
+        _lib.call("rl_mcts_read_tree", self, tree, *(out[f] for f in TREE_FIELDS), n)
         return {f: a[:n.value] for f, a in out.items()}
 
     def drive(self, states, recent_actions, seeds, n_decisions, n_iterations, steps_per_decision=1, steer_clip=None,
@@ -165,10 +155,7 @@ class MCTSPlanner(_lib.Handle):
         first, out, recent = np.empty(K, np.int32), np.empty((K, 11)), np.empty(K)
         actions, visits = np.empty((K, D)), np.empty((K, D), np.int32)
         tr = np.empty((K, D, 11)) if trace else None
-        _lib.check(_lib.lib().rl_mcts_drive(
-            self._h, st.ctypes.data_as(f64p), ac.ctypes.data_as(f64p), sd.ctypes.data_as(C.POINTER(C.c_uint64)), D, I,
-            S, clip, first.ctypes.data_as(i32p), out.ctypes.data_as(f64p), recent.ctypes.data_as(f64p),
-            actions.ctypes.data_as(f64p), visits.ctypes.data_as(i32p), tr.ctypes.data_as(f64p) if trace else None))
+        _lib.call("rl_mcts_drive", self, st, ac, sd, D, I, S, clip, first, out, recent, actions, visits, tr)
         return (first, out, recent, actions, visits) + ((tr,) if trace else ())
 
 

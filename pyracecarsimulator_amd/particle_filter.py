@@ -13,8 +13,6 @@ import numpy as np
 
 from . import _lib
 
-f32p, f64p, i32p = _lib.f32p, _lib.f64p, _lib.i32p
-
 RESAMPLED, DEGENERATE = 1, 2        # bits of a step's flags
 
 
@@ -42,7 +40,7 @@ class ParticleFilter(_lib.Handle):
         if std.size != 3:
             raise ValueError("motion_std needs three values (x, y, theta)")
         par = _lib.PfParams(self.n_particles, int(self.angles.size), (C.c_double * 3)(*std), float(resample_ratio))
-        _lib.check(_lib.lib().rl_pf_create(method._h, C.byref(par), self.angles.ctypes.data_as(f32p), C.byref(self._h)))
+        _lib.call("rl_pf_create", method, par, self.angles, self._h)
 
     def reset(self, particles, weights=None, seed=0):
         """Start from ``particles`` (P, 3) float64 (x, y, theta) with uniform weights, or ``weights`` taken as given;
@@ -50,13 +48,11 @@ class ParticleFilter(_lib.Handle):
         particles = np.ascontiguousarray(particles, dtype=np.float64)
         if particles.shape != (self.n_particles, 3):
             raise ValueError("particles must be (%d, 3)" % self.n_particles)
-        wp = None
         if weights is not None:
             weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
             if weights.size != self.n_particles:
                 raise ValueError("weights must have %d values" % self.n_particles)
-            wp = weights.ctypes.data_as(f64p)
-        _lib.check(_lib.lib().rl_pf_reset(self._h, particles.ctypes.data_as(f64p), wp, int(seed)))
+        _lib.call("rl_pf_reset", self, particles, weights, seed)
 
     def run_raw(self, odom, obs):
         """T updates: ``odom`` (T, 3) float64 (dx, dy, dtheta) in the car frame, ``obs`` (T, A) float32 observed ranges
@@ -67,8 +63,7 @@ class ParticleFilter(_lib.Handle):
         if obs.shape[0] != T:
             raise ValueError("odom has %d rows, obs %d" % (T, obs.shape[0]))
         est, neff, flags = np.zeros((T, 4)), np.zeros(T), np.zeros(T, np.int32)
-        _lib.check(_lib.lib().rl_pf_run(self._h, T, odom.ctypes.data_as(f64p), obs.ctypes.data_as(f32p),
-                                        est.ctypes.data_as(f64p), neff.ctypes.data_as(f64p), flags.ctypes.data_as(i32p)))
+        _lib.call("rl_pf_run", self, T, odom, obs, est, neff, flags)
         return est, neff, flags
 
     def run(self, odom, obs):
@@ -90,7 +85,5 @@ class ParticleFilter(_lib.Handle):
         P = self.n_particles
         out = dict(particles=np.zeros((P, 3)), weights=np.zeros(P), ancestors=np.zeros(P, np.int32), cum=np.zeros(P),
                    likelihood=np.zeros(P))
-        _lib.check(_lib.lib().rl_pf_read(self._h, out["particles"].ctypes.data_as(f64p), out["weights"].ctypes.data_as(f64p),
-                                         out["ancestors"].ctypes.data_as(i32p), out["cum"].ctypes.data_as(f64p),
-                                         out["likelihood"].ctypes.data_as(f64p)))
+        _lib.call("rl_pf_read", self, *out.values())
         return out

@@ -17,7 +17,6 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._lib import f32p
 
 #: the reference's tensor names (scripts/policy.py:25-26)
 INPUT_NAME = "input_layer"
@@ -256,12 +255,9 @@ class Policy(_lib.Handle):
         self.dims = tuple(int(d) for d in dims)
         self.in_start, self.clip, self.scale = int(in_start), float(clip), float(scale)
         self.device = int(device)
-        L = len(Ws)
         self._h = C.c_void_p()
-        _lib.check(_lib.lib().rl_policy_create(
-            self.device, L, (C.c_int32 * (L + 1))(*self.dims),
-            (f32p * L)(*[W.ctypes.data_as(f32p) for W in Ws]), (f32p * L)(*[b.ctypes.data_as(f32p) for b in bs]),
-            (C.c_uint8 * L)(*[int(r) for r in self.relu]), self.in_start, self.clip, self.scale, C.byref(self._h)))
+        _lib.call("rl_policy_create", self.device, len(Ws), np.array(self.dims, np.int32), Ws, bs,
+                  np.array(self.relu, np.uint8), self.in_start, self.clip, self.scale, self._h)
 
     @classmethod
     def from_arrays(cls, layers, relu=None, device=0, in_start=180, clip=15.0, scale=15.0):
@@ -293,12 +289,10 @@ class Policy(_lib.Handle):
             size = int(size)
             n = scans.size // size
         out = np.empty(n, dtype=np.float32)
-        _lib.check(_lib.lib().rl_policy_eval(self._h, scans.ctypes.data_as(f32p), int(n), int(size),
-                                             out.ctypes.data_as(f32p)))
+        _lib.call("rl_policy_eval", self, scans, n, size, out)
         return out
 
     def predict_device(self, d_scans_ptr, n_scans, size, d_steers_ptr, stream=0):
         """Device-resident form: ``d_scans_ptr`` -> float32[n_scans*size] (e.g. ``calc_range_fan_device``'s output),
         ``d_steers_ptr`` -> float32[n_scans]; asynchronous on ``stream``."""
-        _lib.check(_lib.lib().rl_policy_eval_device(self._h, C.c_void_p(int(d_scans_ptr)), int(n_scans), int(size),
-                                                    C.c_void_p(int(d_steers_ptr)), C.c_void_p(int(stream))))
+        _lib.call("rl_policy_eval_device", self, int(d_scans_ptr), n_scans, size, int(d_steers_ptr), int(stream))

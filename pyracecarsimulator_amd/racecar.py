@@ -27,7 +27,6 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import f32p, f64p
 
 #: constructor order of Car (racecar/include/racecar.hpp:32-36) with the reference's values
 #: (params.yaml:3-21,47)
@@ -47,9 +46,7 @@ def edge_distances(num_rays, min_ang, scan_ang_inc, scan_dist_to_base, width, wh
     use (table shifted by one beam, :256), ``PI = 3.145`` (racecar.hpp:117), and a beam at exactly
     0 rad gets ``side / sin(-0.0001)`` (a large negative number, :277-283)."""
     out = np.empty(int(num_rays), dtype=np.float64)
-    _lib.check(_lib.lib().rl_car_edge_distances(int(num_rays), float(min_ang), float(scan_ang_inc),
-                                                float(scan_dist_to_base), float(width), float(wheelbase),
-                                                out.ctypes.data_as(f64p)))
+    _lib.call("rl_car_edge_distances", num_rays, min_ang, scan_ang_inc, scan_dist_to_base, width, wheelbase, out)
     return out
 
 
@@ -61,8 +58,7 @@ def is_crashed(rays, num_rays, poses, edge, crash_thresh):
     if rays.size < num_rays * poses or edge.size < num_rays:
         raise ValueError("is_crashed: rays needs poses*num_rays values, edge num_rays")
     first = C.c_int(0)
-    _lib.check(_lib.lib().rl_car_is_crashed(rays.ctypes.data_as(f32p), int(num_rays), int(poses),
-                                            edge.ctypes.data_as(f64p), float(crash_thresh), C.byref(first)))
+    _lib.call("rl_car_is_crashed", rays, num_rays, poses, edge, crash_thresh, first)
     return int(first.value)
 
 
@@ -79,10 +75,10 @@ class CarBatch(_lib.Handle):
         if isinstance(device, (list, tuple)):
             # several devices (pair with a method of PyOMap(device=[...]) on the same list): roll-outs are cut
             # into contiguous blocks, one per device, inside this one process
-            devs = (C.c_int * len(device))(*[int(d) for d in device])
-            _lib.check(_lib.lib().rl_car_create_multi(devs, len(device), arr.ctypes.data_as(f64p), C.byref(self._h)))
+            devs = np.array([int(d) for d in device], dtype=np.intc)
+            _lib.call("rl_car_create_multi", devs, len(devs), arr, self._h)
         else:
-            _lib.check(_lib.lib().rl_car_create(int(device), arr.ctypes.data_as(f64p), C.byref(self._h)))
+            _lib.call("rl_car_create", device, arr, self._h)
 
     @staticmethod
     def _prep(states, actions, n_steps, action_every):
@@ -100,10 +96,7 @@ class CarBatch(_lib.Handle):
         poses = np.empty((R, n_steps, 3), dtype=np.float32)
         out = np.empty((R, 11), dtype=np.float64)
         vel = np.empty((R, n_steps), dtype=np.float64)
-        _lib.check(_lib.lib().rl_car_rollout(
-            self._h, states.ctypes.data_as(f64p), actions.ctypes.data_as(f64p), R, int(n_steps),
-            int(action_every), float(dt), poses.ctypes.data_as(f32p), out.ctypes.data_as(f64p),
-            vel.ctypes.data_as(f64p)))
+        _lib.call("rl_car_rollout", self, states, actions, R, n_steps, action_every, dt, poses, out, vel)
         return poses, out, vel
 
     def rollout_check(self, method, states, actions, fov, num_rays, edge, crash_thresh, n_steps=200,
@@ -116,11 +109,8 @@ class CarBatch(_lib.Handle):
         first = np.zeros(R, dtype=np.int32)
         out = np.empty((R, 11), dtype=np.float64)
         vel = np.empty((R, n_steps), dtype=np.float64)
-        _lib.check(_lib.lib().rl_car_rollout_check(
-            self._h, method._h, states.ctypes.data_as(f64p), actions.ctypes.data_as(f64p), R,
-            int(n_steps), int(action_every), float(dt), float(fov), int(num_rays),
-            edge.ctypes.data_as(f64p), float(crash_thresh), first.ctypes.data_as(C.POINTER(C.c_int)),
-            out.ctypes.data_as(f64p), vel.ctypes.data_as(f64p)))
+        _lib.call("rl_car_rollout_check", self, method, states, actions, R, n_steps, action_every, dt, fov, num_rays,
+                  edge, crash_thresh, first, out, vel)
         return first, out, vel
 
     def drive_followgap(self, method, followgap, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
@@ -135,7 +125,7 @@ class CarBatch(_lib.Handle):
         final states (R, 11), velocities float64 (R, n_ticks), steers float32 (R, n_ticks)) and with
         ``trace=True`` also (lidar poses float32 (R, n_ticks, 3), states float64 (R, n_ticks, 11)).  Trace
         rows after a car's crash tick, and its steer at that tick, are NaN."""
-        return self._drive(_lib.lib().rl_car_drive_followgap, method, followgap, None, (), states, n_ticks, speed, fov,
+        return self._drive("rl_car_drive_followgap", method, followgap, None, (), states, n_ticks, speed, fov,
                            num_rays, edge, crash_thresh, scan_dist_to_base, dt, steer0, trace)
 
     def outline_cells(self, omap, car_poses):
@@ -146,9 +136,7 @@ class CarBatch(_lib.Handle):
         n = cars.shape[0]
         cells = np.empty((n, 512), dtype=np.int32)
         counts = np.zeros(n, dtype=np.int32)
-        _lib.check(_lib.lib().rl_car_outline_cells(self._h, omap._h, cars.ctypes.data_as(f64p), n, 512,
-                                                    cells.ctypes.data_as(_lib.i32p),
-                                                    counts.ctypes.data_as(C.POINTER(C.c_int))))
+        _lib.call("rl_car_outline_cells", self, omap, cars, n, 512, cells, counts)
         width = int(counts.max()) if n else 0
         return np.ascontiguousarray(cells[:, :width]), counts
 
@@ -167,7 +155,7 @@ class CarBatch(_lib.Handle):
         spd = np.asarray(speed, dtype=np.float64)
         spd = float(spd) if spd.ndim == 0 else spd.reshape(-1)
         st0 = None if steer0 is None else np.asarray(steer0).reshape(-1)
-        res = self._drive(_lib.lib().rl_car_race_followgap, method, followgap, (n_races, group), (), st.reshape(-1, 11),
+        res = self._drive("rl_car_race_followgap", method, followgap, (n_races, group), (), st.reshape(-1, 11),
                           n_ticks, spd, fov, num_rays, edge, crash_thresh, scan_dist_to_base, dt, st0, trace)
         # every array's leading R P becomes (R, P)
         return tuple(a.reshape((n_races, group) + a.shape[1:]) for a in res)
@@ -182,7 +170,7 @@ class CarBatch(_lib.Handle):
         clip = 0.0 if steer_clip is None else float(steer_clip)
         if steer_clip is not None and not clip > 0:
             raise ValueError("steer_clip must be None or > 0")
-        return self._drive(_lib.lib().rl_car_drive_policy, method, policy, None, (clip,), states, n_ticks, speed, fov,
+        return self._drive("rl_car_drive_policy", method, policy, None, (clip,), states, n_ticks, speed, fov,
                            num_rays, edge, crash_thresh, scan_dist_to_base, dt, steer0, trace)
 
     def plan_mcts(self, method, followgap_or_policy, root_states, n_iterations, seeds, fov, num_rays, edge,
@@ -195,19 +183,12 @@ class CarBatch(_lib.Handle):
         (K, 11), root_actions scalar or (K,), seeds uint64 (K,).  Returns (best root action float64 (K,), its visits
         int32 (K,), nodes per tree int32 (K,)) and with ``trees=True`` also the K node-array dicts of
         ``MCTSPlanner.read_tree``."""
-        from .mcts import MCTSPlanner
-        from .policy import Policy
-        if source is None:
-            source = "random" if followgap_or_policy is None else ("nn" if isinstance(followgap_or_policy, Policy)
-                                                                   else "fg")
         root_states = np.asarray(root_states, np.float64).reshape(-1, 11)
         K = root_states.shape[0]
         n_iterations = int(n_iterations)
-        pl = MCTSPlanner(self, method, K, max_nodes or n_iterations + 1, fov, num_rays, edge, crash_thresh,
-                         source=source, followgap=followgap_or_policy if source == "fg" else None,
-                         policy=followgap_or_policy if source == "nn" else None, rollout_steps=rollout_steps,
-                         action_every=action_every, speed=speed, dt=dt, scan_dist_to_base=scan_dist_to_base,
-                         C_ucb=C_ucb, crash_pen=crash_pen, uni_dev=uni_dev)
+        pl = self._planner(method, followgap_or_policy, source, K, max_nodes or n_iterations + 1, fov, num_rays, edge,
+                           crash_thresh, rollout_steps=rollout_steps, action_every=action_every, speed=speed, dt=dt,
+                           scan_dist_to_base=scan_dist_to_base, C_ucb=C_ucb, crash_pen=crash_pen, uni_dev=uni_dev)
         try:
             pl.reset(root_states, root_actions, seeds)
             pl.run(n_iterations)
@@ -226,39 +207,39 @@ class CarBatch(_lib.Handle):
         ``n_decisions`` decisions (a fresh tree of ``n_iterations`` iterations from its state) and takes
         ``steps_per_decision`` steps with the most visited root action.  Source and handles as ``plan_mcts``; states
         float64 (K, 11), recent_actions scalar or (K,), seeds integers (K,).  Returns ``MCTSPlanner.drive``'s tuple."""
-        from .mcts import MCTSPlanner
-        from .policy import Policy
-        if source is None:
-            source = "random" if followgap_or_policy is None else ("nn" if isinstance(followgap_or_policy, Policy)
-                                                                   else "fg")
         states = np.asarray(states)
         if states.dtype != np.float64 or states.ndim != 2 or states.shape[1] != 11:
             raise ValueError("states must be float64 (K, 11)")
-        pl = MCTSPlanner(self, method, states.shape[0], int(n_iterations) + 1, fov, num_rays, edge, crash_thresh,
-                         source=source, followgap=followgap_or_policy if source == "fg" else None,
-                         policy=followgap_or_policy if source == "nn" else None, rollout_steps=rollout_steps,
-                         action_every=action_every, speed=speed, dt=dt, scan_dist_to_base=scan_dist_to_base,
-                         C_ucb=C_ucb, crash_pen=crash_pen, uni_dev=uni_dev)
+        pl = self._planner(method, followgap_or_policy, source, states.shape[0], int(n_iterations) + 1, fov, num_rays,
+                           edge, crash_thresh, rollout_steps=rollout_steps, action_every=action_every, speed=speed,
+                           dt=dt, scan_dist_to_base=scan_dist_to_base, C_ucb=C_ucb, crash_pen=crash_pen, uni_dev=uni_dev)
         try:
             return pl.drive(states, recent_actions, seeds, n_decisions, n_iterations,
                             steps_per_decision=steps_per_decision, steer_clip=steer_clip, trace=trace)
         finally:
             pl.close()
 
+    def _planner(self, method, followgap_or_policy, source, n_trees, max_nodes, *args, **kw):
+        """The ``MCTSPlanner`` of ``plan_mcts`` and ``drive_mcts``: ``source`` None picks "random" for no handle, "nn"
+        for a ``Policy``, "fg" otherwise; the handle goes to the planner as the source's."""
+        from .mcts import MCTSPlanner
+        from .policy import Policy
+        if source is None:
+            source = "random" if followgap_or_policy is None else ("nn" if isinstance(followgap_or_policy, Policy)
+                                                                   else "fg")
+        return MCTSPlanner(self, method, n_trees, max_nodes, *args, source=source,
+                           followgap=followgap_or_policy if source == "fg" else None,
+                           policy=followgap_or_policy if source == "nn" else None, **kw)
+
     def _drive(self, fn, method, source, counts, after_thresh, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
                scan_dist_to_base, dt, steer0, trace):
-        """The one ctypes call of the closed loops: ``fn`` is rl_car_drive_followgap, rl_car_race_followgap or
+        """The one library call of the closed loops: ``fn`` names rl_car_drive_followgap, rl_car_race_followgap or
         rl_car_drive_policy, ``source`` the steering source's wrapper.  ``counts`` replaces (R,) as the car-count
         arguments (races: (n_races, group)); ``after_thresh`` goes after crash_thresh (the policy's steer_clip)."""
         R, n_ticks, states, speeds, st0, edge, first, out, vel, steers, poses, trace_st = self._drive_args(
             states, n_ticks, speed, num_rays, edge, steer0, trace)
-        ptr = lambda a, t: a.ctypes.data_as(t) if a is not None else None
-        _lib.check(fn(
-            self._h, method._h, source._h, states.ctypes.data_as(f64p), speeds.ctypes.data_as(f64p), ptr(st0, f32p),
-            *(counts or (R,)), n_ticks, float(dt), float(scan_dist_to_base), float(fov), int(num_rays),
-            edge.ctypes.data_as(f64p), float(crash_thresh), *after_thresh, first.ctypes.data_as(C.POINTER(C.c_int)),
-            out.ctypes.data_as(f64p), vel.ctypes.data_as(f64p), steers.ctypes.data_as(f32p), ptr(poses, f32p),
-            ptr(trace_st, f64p)))
+        _lib.call(fn, self, method, source, states, speeds, st0, *(counts or (R,)), n_ticks, dt, scan_dist_to_base, fov,
+                  num_rays, edge, crash_thresh, *after_thresh, first, out, vel, steers, poses, trace_st)
         if trace:
             return first, out, vel, steers, poses, trace_st
         return first, out, vel, steers

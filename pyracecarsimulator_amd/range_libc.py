@@ -30,7 +30,6 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import f32p, f64p, i32p, u16p, u8p
 
 __all__ = ["PyOMap", "PyRayMarching", "PyRayMarchingGPU", "PyCDDTCast", "PyBresenhamsLine",
            "PyGiantLUTCast", "USE_CUDA", "SHOULD_USE_CUDA"]
@@ -90,16 +89,13 @@ class PyOMap(_lib.Handle):
             if not self.devices:
                 raise ValueError("PyOMap: empty device list")
             self.device = self.devices[0]
-            arr = (C.c_int * len(self.devices))(*self.devices)
-            _lib.check(_lib.lib().rl_map_create_multi(
-                self.occ.ctypes.data_as(u8p), self.height, self.width, self.resolution,
-                self.origin[0], self.origin[1], self.origin[2], arr, len(self.devices), C.byref(self._h)))
+            _lib.call("rl_map_create_multi", self.occ, self.height, self.width, self.resolution, *self.origin[:3],
+                      np.array(self.devices, dtype=np.intc), len(self.devices), self._h)
             return
         self.device = int(device)
         self.devices = [self.device]
-        _lib.check(_lib.lib().rl_map_create(
-            self.occ.ctypes.data_as(u8p), self.height, self.width, self.resolution,
-            self.origin[0], self.origin[1], self.origin[2], self.device, C.byref(self._h)))
+        _lib.call("rl_map_create", self.occ, self.height, self.width, self.resolution, *self.origin[:3], self.device,
+                  self._h)
 
     @staticmethod
     def _ingest(arg1, arg2, resolution, origin):
@@ -131,7 +127,7 @@ class PyOMap(_lib.Handle):
             raise ValueError("PyOMap.update: shape mismatch")
         self.occ = occ
         self._base_occ = None
-        _lib.check(_lib.lib().rl_map_update(self._h, occ.ctypes.data_as(u8p)))
+        _lib.call("rl_map_update", self, occ)
 
     def stamp_cells(self, flat_idx, value=255):
         """The two-player tick without re-uploading the grid (rl_map_stamp_cells): the occupancy becomes the BASE map
@@ -146,7 +142,7 @@ class PyOMap(_lib.Handle):
         idx = stamp_indices(flat_idx, self.occ.size)
         if getattr(self, "_base_occ", None) is None:
             self._base_occ = self.occ.copy()
-        _lib.check(_lib.lib().rl_map_stamp_cells(self._h, idx.ctypes.data_as(_lib.i32p), int(idx.size), int(value) & 0xff))
+        _lib.call("rl_map_stamp_cells", self, idx, idx.size, int(value) & 0xff)
         occ = self._base_occ.copy()
         occ.reshape(-1)[idx] = 1 if (int(value) & 0xff) else 0
         self.occ = occ
@@ -154,7 +150,7 @@ class PyOMap(_lib.Handle):
     def distance_transform(self):
         """float32 (H, W) exact EDT in cells as built on the device (test hook)."""
         out = np.empty((self.height, self.width), dtype=np.float32)
-        _lib.check(_lib.lib().rl_map_get_dt(self._h, out.ctypes.data_as(f32p)))
+        _lib.call("rl_map_get_dt", self, out)
         return out
 
 
@@ -180,6 +176,30 @@ def _check_ranges_out(ranges, n):
     if not isinstance(ranges, np.ndarray) or ranges.dtype != np.float32 or not ranges.flags.c_contiguous \
             or ranges.size < n:
         raise ValueError("ranges must be a C-contiguous float32 array with n_poses*num_rays elements")
+
+
+def _check_aux_outs(hit_cells, steps, n, shape, exact=False):
+    """The optional diagnostics of an n-ray scan: ``hit_cells`` int32 with 2 n elements, ``steps`` uint16 with n, both
+    C-contiguous arrays.  ``exact``: the sizes must match; otherwise a larger buffer passes.  ``shape`` names n in the
+    message."""
+    for name, a, dtype, size in (("hit_cells", hit_cells, np.int32, 2 * n), ("steps", steps, np.uint16, n)):
+        if a is None:
+            continue
+        if not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous \
+                or (a.size != size if exact else a.size < size):
+            raise ValueError("%s must be C-contiguous %s (%s%s)" % (name, np.dtype(dtype).name, shape,
+                                                                    ", 2" if name == "hit_cells" else ","))
+
+
+def _prep_crash(poses, edge_distances, num_rays, group=None):
+    """The crash-test wrappers' inputs: (poses float32 (n, 3), edge float64) as C-contiguous arrays, checked."""
+    poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
+    if group is not None and poses.shape[0] % group:
+        raise ValueError("number of poses is not a multiple of the group size")
+    edge = np.ascontiguousarray(edge_distances, dtype=np.float64)
+    if edge.size < num_rays:
+        raise ValueError("edge_distances needs num_rays entries")
+    return poses, edge
 
 
 def _check_f32_vector(name, a, n=None):
@@ -229,8 +249,7 @@ class _RangeMethod(_lib.Handle):
         self.max_range_px = float(max_range_px)
         self.theta_disc = int(theta_disc)
         self._h = C.c_void_p()
-        _lib.check(_lib.lib().rl_method_create(omap._h, self.KIND, self.max_range_px,
-                                               self.theta_disc, C.byref(self._h)))
+        _lib.call("rl_method_create", omap, self.KIND, self.max_range_px, self.theta_disc, self._h)
         self._fan_raw = _lib.raw("rl_calc_range_many_fan")
         self._fan_dense_raw = _lib.raw("rl_calc_range_fan")
 
@@ -241,16 +260,12 @@ class _RangeMethod(_lib.Handle):
         ``p*num_rays``, result ``outs[p*num_rays + j]`` (scripts/scan_simulator.py:103-106,
         130-133)."""
         _check_ins_outs(ins, outs)
-        L = _lib.lib()
         if fov is None and num_rays is None:
-            _lib.check(L.rl_calc_range_many(self._h, ins.ctypes.data_as(f32p),
-                                            outs.ctypes.data_as(f32p), ins.shape[0]))
+            _lib.call("rl_calc_range_many", self, ins, outs, ins.shape[0])
         elif fov is None or num_rays is None:
             raise TypeError("calc_range_many takes (ins, outs) or (ins, outs, fov, num_rays)")
         else:
-            _lib.check(L.rl_calc_range_many_fan(self._h, ins.ctypes.data_as(f32p),
-                                                outs.ctypes.data_as(f32p), ins.shape[0],
-                                                float(fov), int(num_rays)))
+            _lib.call("rl_calc_range_many_fan", self, ins, outs, ins.shape[0], fov, num_rays)
         return None
 
     def _fan_rows_ptr(self, ins_addr, outs_addr, n_rows, fov, num_rays):
@@ -275,17 +290,8 @@ class _RangeMethod(_lib.Handle):
         n = poses.shape[0] * int(num_rays)
         if outs.dtype != np.float32 or not outs.flags.c_contiguous or outs.size < n:
             raise ValueError("outs must be C-contiguous float32 with P*num_rays elements")
-        if hit_cells is not None and (hit_cells.dtype != np.int32 or hit_cells.size < 2 * n
-                                      or not hit_cells.flags.c_contiguous):
-            raise ValueError("hit_cells must be C-contiguous int32 (P*num_rays, 2)")
-        if steps is not None and (steps.dtype != np.uint16 or steps.size < n
-                                  or not steps.flags.c_contiguous):
-            raise ValueError("steps must be C-contiguous uint16 (P*num_rays,)")
-        _lib.check(_lib.lib().rl_calc_range_fan(
-            self._h, poses.ctypes.data_as(f32p), poses.shape[0], float(fov), int(num_rays),
-            outs.ctypes.data_as(f32p),
-            hit_cells.ctypes.data_as(i32p) if hit_cells is not None else None,
-            steps.ctypes.data_as(u16p) if steps is not None else None))
+        _check_aux_outs(hit_cells, steps, n, "P*num_rays")
+        _lib.call("rl_calc_range_fan", self, poses, poses.shape[0], fov, num_rays, outs, hit_cells, steps)
         return None
 
     def calc_range_fan_cars(self, poses, car_poses, group, fov, num_rays, outs=None, length=0.4064, width=0.2032,
@@ -306,38 +312,25 @@ class _RangeMethod(_lib.Handle):
             outs = np.empty(n, dtype=np.float32)
         if outs.dtype != np.float32 or not outs.flags.c_contiguous or outs.size < n:
             raise ValueError("outs must be C-contiguous float32 with N*num_rays elements")
-        if hit_cells is not None and (hit_cells.dtype != np.int32 or hit_cells.size < 2 * n
-                                      or not hit_cells.flags.c_contiguous):
-            raise ValueError("hit_cells must be C-contiguous int32 (N*num_rays, 2)")
-        if steps is not None and (steps.dtype != np.uint16 or steps.size < n or not steps.flags.c_contiguous):
-            raise ValueError("steps must be C-contiguous uint16 (N*num_rays,)")
-        _lib.check(_lib.lib().rl_calc_range_fan_cars(
-            self._h, poses.ctypes.data_as(f32p), cars.ctypes.data_as(f64p), poses.shape[0] // group, group,
-            float(length), float(width), float(fov), int(num_rays), outs.ctypes.data_as(f32p),
-            hit_cells.ctypes.data_as(i32p) if hit_cells is not None else None,
-            steps.ctypes.data_as(u16p) if steps is not None else None))
+        _check_aux_outs(hit_cells, steps, n, "N*num_rays")
+        _lib.call("rl_calc_range_fan_cars", self, poses, cars, poses.shape[0] // group, group, length, width, fov,
+                  num_rays, outs, hit_cells, steps)
         return outs
 
     def calc_range_fan_cars_device(self, d_poses_ptr, d_cars_ptr, n_groups, group, fov, num_rays, d_outs_ptr,
                                    length=0.4064, width=0.2032, d_hits_ptr=0, d_steps_ptr=0, stream=0):
         """``calc_range_fan_cars`` on device pointers (ints, e.g. torch ``tensor.data_ptr()``): asynchronous."""
-        _lib.check(_lib.lib().rl_calc_range_fan_cars_device(
-            self._h, C.c_void_p(d_poses_ptr), C.c_void_p(d_cars_ptr), int(n_groups), int(group), float(length),
-            float(width), float(fov), int(num_rays), C.c_void_p(d_outs_ptr), C.c_void_p(d_hits_ptr or None),
-            C.c_void_p(d_steps_ptr or None), C.c_void_p(stream or None)))
+        _lib.call("rl_calc_range_fan_cars_device", self, d_poses_ptr, d_cars_ptr, n_groups, group, length, width, fov,
+                  num_rays, d_outs_ptr, d_hits_ptr, d_steps_ptr, stream)
 
     def calc_range_fan_device(self, d_poses_ptr, n_poses, fov, num_rays, d_outs_ptr,
                               d_hits_ptr=0, d_steps_ptr=0, stream=0):
         """Asynchronous launch on device pointers (ints), e.g. torch ``tensor.data_ptr()``."""
-        _lib.check(_lib.lib().rl_calc_range_fan_device(
-            self._h, C.c_void_p(d_poses_ptr), int(n_poses), float(fov), int(num_rays),
-            C.c_void_p(d_outs_ptr), C.c_void_p(d_hits_ptr or None),
-            C.c_void_p(d_steps_ptr or None), C.c_void_p(stream or None)))
+        _lib.call("rl_calc_range_fan_device", self, d_poses_ptr, n_poses, fov, num_rays, d_outs_ptr, d_hits_ptr,
+                  d_steps_ptr, stream)
 
     def calc_range_many_device(self, d_ins_ptr, d_outs_ptr, n, stream=0):
-        _lib.check(_lib.lib().rl_calc_range_many_device(
-            self._h, C.c_void_p(d_ins_ptr), C.c_void_p(d_outs_ptr), int(n),
-            C.c_void_p(stream or None)))
+        _lib.call("rl_calc_range_many_device", self, d_ins_ptr, d_outs_ptr, n, stream)
 
     # -- particle-filter weights (range_libc's Monte-Carlo localisation calls) -------
     def calc_range_repeat_angles(self, ins, angles, outs, hit_cells=None, steps=None):
@@ -347,16 +340,9 @@ class _RangeMethod(_lib.Handle):
         _check_f32_vector("angles", angles)
         n = ins.shape[0] * angles.shape[0]
         _check_f32_vector("outs", outs, n)
-        if hit_cells is not None and (not isinstance(hit_cells, np.ndarray) or hit_cells.dtype != np.int32
-                                      or hit_cells.size != 2 * n or not hit_cells.flags.c_contiguous):
-            raise ValueError("hit_cells must be C-contiguous int32 (P*A, 2)")
-        if steps is not None and (not isinstance(steps, np.ndarray) or steps.dtype != np.uint16 or steps.size != n
-                                  or not steps.flags.c_contiguous):
-            raise ValueError("steps must be C-contiguous uint16 (P*A,)")
-        _lib.check(_lib.lib().rl_calc_range_repeat_angles(
-            self._h, ins.ctypes.data_as(f32p), ins.shape[0], angles.ctypes.data_as(f32p), angles.shape[0],
-            outs.ctypes.data_as(f32p), hit_cells.ctypes.data_as(i32p) if hit_cells is not None else None,
-            steps.ctypes.data_as(u16p) if steps is not None else None))
+        _check_aux_outs(hit_cells, steps, n, "P*A", exact=True)
+        _lib.call("rl_calc_range_repeat_angles", self, ins, ins.shape[0], angles, angles.shape[0], outs, hit_cells,
+                  steps)
         return None
 
     def set_sensor_model(self, table):
@@ -366,8 +352,7 @@ class _RangeMethod(_lib.Handle):
             raise TypeError("table must be a numpy array")
         if table.dtype != np.float64 or table.ndim != 2 or table.shape[0] != table.shape[1]:
             raise ValueError("the sensor model must be a square 2-D float64 array")
-        table = np.ascontiguousarray(table)
-        _lib.check(_lib.lib().rl_set_sensor_model(self._h, table.ctypes.data_as(f64p), table.shape[0]))
+        _lib.call("rl_set_sensor_model", self, np.ascontiguousarray(table), table.shape[0])
         return None
 
     def eval_sensor_model(self, obs, ranges, outs, num_rays, num_particles):
@@ -377,8 +362,7 @@ class _RangeMethod(_lib.Handle):
         _check_f32_vector("obs", obs, num_rays)
         _check_f32_vector("ranges", ranges, num_rays * num_particles)
         _check_weights(outs, num_particles)
-        _lib.check(_lib.lib().rl_eval_sensor_model(self._h, obs.ctypes.data_as(f32p), ranges.ctypes.data_as(f32p),
-                                                   num_rays, num_particles, outs.ctypes.data_as(f64p)))
+        _lib.call("rl_eval_sensor_model", self, obs, ranges, num_rays, num_particles, outs)
         return None
 
     def calc_range_repeat_angles_eval_sensor_model(self, ins, angles, obs, weights):
@@ -388,75 +372,55 @@ class _RangeMethod(_lib.Handle):
         _check_f32_vector("angles", angles)
         _check_f32_vector("obs", obs, angles.shape[0])
         _check_weights(weights, ins.shape[0])
-        _lib.check(_lib.lib().rl_calc_range_repeat_angles_eval_sensor_model(
-            self._h, ins.ctypes.data_as(f32p), ins.shape[0], angles.ctypes.data_as(f32p), obs.ctypes.data_as(f32p),
-            angles.shape[0], weights.ctypes.data_as(f64p)))
+        _lib.call("rl_calc_range_repeat_angles_eval_sensor_model", self, ins, ins.shape[0], angles, obs,
+                  angles.shape[0], weights)
         return None
 
     def calc_range_repeat_angles_device(self, d_ins_ptr, n_particles, d_angles_ptr, n_angles, d_outs_ptr,
                                         d_hits_ptr=0, d_steps_ptr=0, stream=0):
         """``calc_range_repeat_angles`` on device pointers (ints, e.g. torch ``tensor.data_ptr()``): asynchronous."""
-        _lib.check(_lib.lib().rl_calc_range_repeat_angles_device(
-            self._h, C.c_void_p(d_ins_ptr), int(n_particles), C.c_void_p(d_angles_ptr), int(n_angles),
-            C.c_void_p(d_outs_ptr), C.c_void_p(d_hits_ptr or None), C.c_void_p(d_steps_ptr or None),
-            C.c_void_p(stream or None)))
+        _lib.call("rl_calc_range_repeat_angles_device", self, d_ins_ptr, n_particles, d_angles_ptr, n_angles,
+                  d_outs_ptr, d_hits_ptr, d_steps_ptr, stream)
 
     def eval_sensor_model_device(self, d_obs_ptr, d_ranges_ptr, d_outs_ptr, num_rays, num_particles, stream=0):
         """``eval_sensor_model`` on device pointers: asynchronous."""
-        _lib.check(_lib.lib().rl_eval_sensor_model_device(
-            self._h, C.c_void_p(d_obs_ptr), C.c_void_p(d_ranges_ptr), int(num_rays), int(num_particles),
-            C.c_void_p(d_outs_ptr), C.c_void_p(stream or None)))
+        _lib.call("rl_eval_sensor_model_device", self, d_obs_ptr, d_ranges_ptr, num_rays, num_particles, d_outs_ptr,
+                  stream)
 
     def calc_range_repeat_angles_eval_sensor_model_device(self, d_ins_ptr, n_particles, d_angles_ptr, d_obs_ptr,
                                                           n_angles, d_weights_ptr, stream=0):
         """``calc_range_repeat_angles_eval_sensor_model`` on device pointers: asynchronous."""
-        _lib.check(_lib.lib().rl_calc_range_repeat_angles_eval_sensor_model_device(
-            self._h, C.c_void_p(d_ins_ptr), int(n_particles), C.c_void_p(d_angles_ptr), C.c_void_p(d_obs_ptr),
-            int(n_angles), C.c_void_p(d_weights_ptr), C.c_void_p(stream or None)))
+        _lib.call("rl_calc_range_repeat_angles_eval_sensor_model_device", self, d_ins_ptr, n_particles, d_angles_ptr,
+                  d_obs_ptr, n_angles, d_weights_ptr, stream)
 
     def check_collision_many(self, poses, fov, num_rays, edge_distances, crash_thresh,
                              ranges=None):
         """Scan + Car::isCrashed fused (racecar/src/racecar.cpp:305-328): index of the first
         crashed pose, else ``-(n_poses+1)``."""
-        poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
-        edge = np.ascontiguousarray(edge_distances, dtype=np.float64)
-        if edge.size < num_rays:
-            raise ValueError("edge_distances needs num_rays entries")
+        poses, edge = _prep_crash(poses, edge_distances, num_rays)
         _check_ranges_out(ranges, poses.shape[0] * int(num_rays))
         first = C.c_int(0)
-        _lib.check(_lib.lib().rl_check_collision_many(
-            self._h, poses.ctypes.data_as(f32p), poses.shape[0], float(fov), int(num_rays),
-            edge.ctypes.data_as(f64p), float(crash_thresh), C.byref(first),
-            ranges.ctypes.data_as(f32p) if ranges is not None else None))
+        _lib.call("rl_check_collision_many", self, poses, poses.shape[0], fov, num_rays, edge, crash_thresh, first,
+                  ranges)
         return int(first.value)
 
     def check_collision_groups(self, poses, group, fov, num_rays, edge_distances, crash_thresh,
                                ranges=None):
         """isCrashed per roll-out of a batch: ``poses`` holds consecutive roll-outs of ``group``
         poses; returns int32[n_groups] (first crashed pose inside each roll-out, else -(group+1))."""
-        poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
-        if poses.shape[0] % group:
-            raise ValueError("number of poses is not a multiple of the group size")
+        poses, edge = _prep_crash(poses, edge_distances, num_rays, group)
         n_groups = poses.shape[0] // group
-        edge = np.ascontiguousarray(edge_distances, dtype=np.float64)
-        if edge.size < num_rays:
-            raise ValueError("edge_distances needs num_rays entries")
         _check_ranges_out(ranges, poses.shape[0] * int(num_rays))
         first = np.zeros(n_groups, dtype=np.int32)
-        _lib.check(_lib.lib().rl_check_collision_groups(
-            self._h, poses.ctypes.data_as(f32p), n_groups, int(group), float(fov), int(num_rays),
-            edge.ctypes.data_as(f64p), float(crash_thresh),
-            first.ctypes.data_as(C.POINTER(C.c_int)),
-            ranges.ctypes.data_as(f32p) if ranges is not None else None))
+        _lib.call("rl_check_collision_groups", self, poses, n_groups, group, fov, num_rays, edge, crash_thresh, first,
+                  ranges)
         return first
 
     def check_collision_groups_device(self, d_poses_ptr, n_groups, group, fov, num_rays, d_edge_ptr,
                                       crash_thresh, d_first_ptr, d_ranges_ptr=0, stream=0):
         """Asynchronous grouped scan + crash test on device pointers (ints)."""
-        _lib.check(_lib.lib().rl_check_collision_groups_device(
-            self._h, C.c_void_p(d_poses_ptr), int(n_groups), int(group), float(fov), int(num_rays),
-            C.c_void_p(d_edge_ptr), float(crash_thresh), C.c_void_p(d_first_ptr),
-            C.c_void_p(d_ranges_ptr or None), C.c_void_p(stream or None)))
+        _lib.call("rl_check_collision_groups_device", self, d_poses_ptr, n_groups, group, fov, num_rays, d_edge_ptr,
+                  crash_thresh, d_first_ptr, d_ranges_ptr, stream)
 
     def calc_range_fan_multi_device(self, poses, d_outs_ptr, fov, num_rays, consumer=0, chunks=0):
         """Multi-device handle, results in DEVICE memory of replica ``consumer``'s GPU (rl_calc_range_fan_multi_device):
@@ -464,72 +428,65 @@ class _RangeMethod(_lib.Handle):
         (hipMemcpyPeerAsync: xGMI between peers) under the next chunk's march.  ``poses``: host array (n, 3);
         ``d_outs_ptr``: device address (int) of n * num_rays float32 on the consumer's device.  Synchronous."""
         poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
-        _lib.check(_lib.lib().rl_calc_range_fan_multi_device(
-            self._h, poses.ctypes.data_as(f32p), poses.shape[0], float(fov), int(num_rays), int(consumer),
-            C.c_void_p(d_outs_ptr), int(chunks)))
+        _lib.call("rl_calc_range_fan_multi_device", self, poses, poses.shape[0], fov, num_rays, consumer, d_outs_ptr,
+                  chunks)
 
     def check_collision_groups_multi_device(self, poses, group, fov, num_rays, edge_distances, crash_thresh, d_first_ptr,
                                             consumer=0):
         """... the fused crash indices (int32 per roll-out of ``group`` poses) of every device's block, gathered in the
         consumer device's memory at ``d_first_ptr`` (rl_check_collision_groups_multi_device)."""
-        poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
-        if poses.shape[0] % group:
-            raise ValueError("number of poses is not a multiple of the group size")
-        edge = np.ascontiguousarray(edge_distances, dtype=np.float64)
-        if edge.size < num_rays:
-            raise ValueError("edge_distances needs num_rays entries")
-        _lib.check(_lib.lib().rl_check_collision_groups_multi_device(
-            self._h, poses.ctypes.data_as(f32p), poses.shape[0] // int(group), int(group), float(fov), int(num_rays),
-            edge.ctypes.data_as(f64p), float(crash_thresh), int(consumer), C.c_void_p(d_first_ptr)))
+        poses, edge = _prep_crash(poses, edge_distances, num_rays, group)
+        _lib.call("rl_check_collision_groups_multi_device", self, poses, poses.shape[0] // int(group), group, fov,
+                  num_rays, edge, crash_thresh, consumer, d_first_ptr)
 
     @property
     def n_devices(self):
         """Devices behind this handle (> 1 for a method of a multi-device ``PyOMap``)."""
-        return int(_lib.lib().rl_method_n_devices(self._h))
+        return _lib.call("rl_method_n_devices", self)
 
     def replica(self, i):
         """The per-device method ``i`` of a multi-device handle as a borrowed object for the ``*_device``
         calls (device pointers belong to one device); the handle itself for a single-device method."""
-        p = _lib.lib().rl_method_replica(self._h, int(i))
+        p = _lib.call("rl_method_replica", self, i)
         if not p:
             raise IndexError("replica %d out of range (%d devices)" % (i, self.n_devices))
         if p == self._h.value:
             return self
         r = object.__new__(type(self))
         r.__dict__.update(omap=self.omap, max_range_px=self.max_range_px, theta_disc=self.theta_disc,
-                          _h=C.c_void_p(p), _fan_raw=self._fan_raw, _fan_dense_raw=self._fan_dense_raw, _parent=self, _borrowed=True)   # (_parent keeps the owner alive)
+                          _h=C.c_void_p(p), _fan_raw=self._fan_raw, _fan_dense_raw=self._fan_dense_raw,
+                          _parent=self, _borrowed=True)          # (_parent keeps the owner alive)
         return r
 
     def set_noise(self, std, seed=0, ray_offset=0):
-        _lib.check(_lib.lib().rl_set_noise(self._h, float(std), int(seed), int(ray_offset)))
+        _lib.call("rl_set_noise", self, std, seed, ray_offset)
 
     def set_option(self, name, value):
-        _lib.check(_lib.lib().rl_method_set_option(self._h, name.encode(), int(value)))
+        _lib.call("rl_method_set_option", self, name, value)
 
     def get_info(self, name):
         v = C.c_int64(0)
-        _lib.check(_lib.lib().rl_method_get_info(self._h, name.encode(), C.byref(v)))
+        _lib.call("rl_method_get_info", self, name, v)
         return int(v.value)
 
     def plan_fan(self, n_poses, num_rays, aux=False, crash=False):
         """What a fan call of this shape would launch with the handle's current options
         (kernel with template arguments, grid, LDS, binning pass): rl_method_plan_fan."""
         pl = _lib.LaunchPlan()
-        _lib.check(_lib.lib().rl_method_plan_fan(self._h, int(n_poses), int(num_rays), int(bool(aux)),
-                                                 int(bool(crash)), C.byref(pl)))
+        _lib.call("rl_method_plan_fan", self, n_poses, num_rays, bool(aux), bool(crash), pl)
         return pl.as_dict()
 
     def last_plan(self):
         """The plan the last fan launch of this handle executed (rl_method_last_plan)."""
         pl = _lib.LaunchPlan()
-        _lib.check(_lib.lib().rl_method_last_plan(self._h, C.byref(pl)))
+        _lib.call("rl_method_last_plan", self, pl)
         return pl.as_dict()
 
     def debug_stamps(self):
         """(n_waves, 4) uint64 diagnostics of the last stream-kernel launch (option debug_stamps)."""
         n = self.get_info("last_grid") * 4 * 4
         buf = np.zeros(max(n, 4), dtype=np.uint64)
-        got = _lib.lib().rl_debug_read_stamps(self._h, buf.ctypes.data_as(C.POINTER(C.c_uint64)), n)
+        got = _lib.call("rl_debug_read_stamps", self, buf, n)
         if got < 0:
             _lib.check(got)
         return buf[:got].reshape(-1, 4)
@@ -537,7 +494,7 @@ class _RangeMethod(_lib.Handle):
     def last_kernel_ms(self):
         """Device time of the last launch; needs ``set_option("timing", 1)`` before that launch."""
         ms = C.c_float(0)
-        _lib.check(_lib.lib().rl_last_kernel_ms(self._h, C.byref(ms)))
+        _lib.call("rl_last_kernel_ms", self, ms)
         return float(ms.value)
 
 
@@ -579,5 +536,5 @@ class PyGiantLUTCast(_RangeMethod):
         """(row1-row0, cols, theta_disc) uint16 slab of the device table (test hook)."""
         row1 = self.omap.height if row1 is None else row1
         out = np.empty((row1 - row0, self.omap.width, self.theta_disc), dtype=np.uint16)
-        _lib.check(_lib.lib().rl_method_read_lut(self._h, row0, row1, out.ctypes.data_as(u16p)))
+        _lib.call("rl_method_read_lut", self, row0, row1, out)
         return out

@@ -10,7 +10,6 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import f64p
 
 MAX_POINTS = 65536
 
@@ -65,8 +64,7 @@ class Track(_lib.Handle):
         self.n_points = p.shape[0]
         self.n_segments = self.n_points if self.closed else self.n_points - 1
         self._h = C.c_void_p()
-        _lib.check(_lib.lib().rl_track_create(self.device, p.ctypes.data_as(f64p), self.n_points, int(self.closed),
-                                              C.byref(self._h)))
+        _lib.call("rl_track_create", self.device, p, self.n_points, self.closed, self._h)
 
     @staticmethod
     def read_csv(path):
@@ -87,11 +85,11 @@ class Track(_lib.Handle):
     def cum(self):
         """Arc length at every point, float64 (S + 1,): cum[0] = 0, cum[S] = length."""
         out = np.empty(self.n_segments + 1)
-        _lib.check(_lib.lib().rl_track_read(self._h, out.ctypes.data_as(f64p), None))
+        _lib.call("rl_track_read", self, out, None)
         return out
 
     @property
     def length(self):
         L = C.c_double()
-        _lib.check(_lib.lib().rl_track_read(self._h, None, C.byref(L)))
+        _lib.call("rl_track_read", self, None, L)
         return L.value

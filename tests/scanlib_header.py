@@ -1,0 +1,128 @@
+"""include/scanlib.h read with regular expressions, as ctypes: its prototypes, structures and enums, for the tests that
+pin ``_lib``'s restatement to it.  Anything the mapping does not know raises ``HeaderError``.  No tests live here."""
+import ctypes as C
+import os
+import re
+
+from pyracecarsimulator_amd import _lib
+
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "scanlib.h")
+
+SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "uint8_t": C.c_uint8,
+           "unsigned char": C.c_uint8, "uint16_t": C.c_uint16, "int32_t": C.c_int32, "uint64_t": C.c_uint64,
+           "int64_t": C.c_int64}
+#: the header's structures and the classes that restate them
+STRUCTS = {"rl_plan_opts": _lib.PlanOpts, "rl_launch_plan": _lib.LaunchPlan, "rl_mcts_params": _lib.MctsParams,
+           "rl_pf_params": _lib.PfParams, "rl_env_params": _lib.EnvParams, "rl_race_env_params": _lib.RaceEnvParams,
+           "rl_track_params": _lib.TrackParams}
+
+
+class HeaderError(AssertionError):
+    """A construct of the header the mapping to ctypes does not know."""
+
+
+def text():
+    """The header without comments and preprocessor lines."""
+    s = open(HEADER).read()
+    s = re.sub(r"/\*.*?\*/", " ", s, flags=re.S)
+    s = re.sub(r"//[^\n]*", " ", s)
+    return re.sub(r"^[ \t]*#.*$", "", s, flags=re.M)
+
+
+def handles(s=None):
+    """The opaque handle types: ``typedef struct rl_x rl_x;``."""
+    return set(re.findall(r"typedef\s+struct\s+(rl_\w+)\s+\1\s*;", s or text()))
+
+
+def ctype(decl, name="", opaque=()):
+    """The ctypes type of a declaration's type text (``const float *``) for the parameter or field ``name``: a handle
+    pointer and ``void *`` are ``c_void_p``, and so is a pointer parameter named ``d_*`` (a device pointer); None for
+    ``void``."""
+    toks = [t for t in decl.replace("*", " * ").split() if t != "const"]
+    stars = toks.count("*")
+    if not toks or "*" in toks[:len(toks) - stars]:
+        raise HeaderError("cannot read the type %r" % decl)
+    base = " ".join(toks[:len(toks) - stars])
+    if base in opaque or base == "void":
+        if stars == 0 and base == "void":
+            return None
+        if 1 <= stars <= 2:
+            return C.c_void_p if stars == 1 else C.POINTER(C.c_void_p)
+    elif base == "char" and stars == 1:
+        return C.c_char_p
+    elif base == "char" and stars == 0:
+        return C.c_char
+    elif base in STRUCTS and stars <= 1:
+        return C.POINTER(STRUCTS[base]) if stars else STRUCTS[base]
+    elif base in SCALARS and stars <= 2:
+        t = SCALARS[base]
+        if stars and name.startswith("d_"):
+            return C.c_void_p
+        for _ in range(stars):
+            t = C.POINTER(t)
+        return t
+    raise HeaderError("no ctypes mapping for %r" % decl)
+
+
+def _split(declarator):
+    """(type text, name, array length or None) of ``const float *d_poses`` / ``double motion_std[3]``."""
+    m = re.fullmatch(r"(.*?)(\w+)\s*(?:\[(\d+)\])?", declarator.strip(), flags=re.S)
+    if not m or not m.group(1).strip():
+        raise HeaderError("cannot read the declarator %r" % declarator)
+    return m.group(1), m.group(2), (int(m.group(3)) if m.group(3) else None)
+
+
+def prototypes():
+    """{name: (restype, [argtypes], [parameter names])} of every ``rl_*`` function the header declares."""
+    s = text()
+    opaque = handles(s)
+    out = {}
+    for ret, name, params in re.findall(r"([\w\s\*]+?)\b(rl_\w+)\s*\(([^(){};]*)\)\s*;", s):
+        args, names = [], []
+        if params.strip() != "void":
+            for p in params.split(","):
+                decl, pname, n = _split(p)
+                if n is not None:
+                    raise HeaderError("array parameter %r of %s" % (p, name))
+                args.append(ctype(decl, pname, opaque))
+                names.append(pname)
+        if name in out:
+            raise HeaderError("%s is declared twice" % name)
+        out[name] = (ctype(ret, "", opaque), args, names)
+    declared = set(re.findall(r"\b(rl_[a-z_0-9]+)\s*\(", s))
+    if declared != set(out):
+        raise HeaderError("prototypes the parser did not read: %s" % sorted(declared ^ set(out)))
+    return out
+
+
+def structs():
+    """{struct name: [(field, ctype), ...]} in declaration order (``int a, b;`` gives two fields, ``x[3]`` an array)."""
+    out = {}
+    for name, body in re.findall(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;", text()):
+        fields = []
+        for stmt in body.split(";"):
+            if not stmt.strip():
+                continue
+            first, *rest = stmt.split(",")
+            if "*" in "".join(rest):
+                raise HeaderError("pointer in a joined declarator: %r" % stmt)
+            decl, fname, n = _split(first)
+            t = ctype(decl)
+            for fname, n in [(fname, n)] + [_split("int " + r)[1:] for r in rest]:    # (the type text is the first one's)
+                fields.append((fname, t * n if n else t))
+        out[name] = fields
+    return out
+
+
+def enums():
+    """{enum name: {constant: value}}; every constant carries its value in the header."""
+    out = {}
+    for name, body in re.findall(r"typedef\s+enum\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;", text()):
+        vals = {}
+        for item in body.split(","):
+            m = re.fullmatch(r"\s*(\w+)\s*=\s*(-?\d+)\s*", item)
+            if not m:
+                raise HeaderError("enum %s: cannot read %r" % (name, item))
+            vals[m.group(1)] = int(m.group(2))
+        out[name] = vals
+    return out

@@ -608,12 +608,11 @@ def test_stamp_cells_host_mirror_and_c_arguments(monkeypatch):
     import ctypes as C
     calls = []
 
-    class Stub:
-        def rl_map_stamp_cells(self, h, p, n, value):
-            calls.append((np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.int32), n, value))
-            return 0
+    def stub(name, h, idx, n, value):
+        assert name == "rl_map_stamp_cells" and idx.dtype == np.int32 and idx.flags.c_contiguous and idx.size == n
+        calls.append((idx.copy(), n, value))
 
-    monkeypatch.setattr(range_libc._lib, "lib", lambda: Stub())
+    monkeypatch.setattr(range_libc._lib, "call", stub)
     rows, cols = 50, 61
     size = rows * cols
     base = np.zeros((rows, cols), np.uint8)
