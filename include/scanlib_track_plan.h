@@ -1,0 +1,76 @@
+/* scanlib_track_plan.h — the track in the MCTS planner and in the roll-outs: an extension of scanlib.h (which it
+ * includes and whose conventions it keeps: every function returns RL_OK or a negative rl_status, rl_last_error names
+ * the reason).  pyracecarsimulator_amd/_lib.py restates it in EXT_SYMBOLS; tests/mcts_track_statement.py restates the
+ * rules below line by line.
+ *
+ * ---- track-guided planning ------------------------------------------------------------------------
+ * The reference's global planner (scripts/mcts_driver.py:40-51, 139-169, 216-227: readGlobalPath, findBestPoint and
+ * MCTS(..., track_point=closest_point, with_global=True)) and its waypoint reward (scripts/mcts.py:233-234, 247-250,
+ * commented out upstream), for rl_mcts_reset / rl_mcts_run, rl_mcts_drive and the plain roll-outs.  Every step of a
+ * roll-out gets a reward TERM; the value of a roll-out stays mcts.py:240-245, numpy.sum(terms[:index] or all L) /
+ * |action| in the pinned pairwise order of scanlib.h: mcts_backup_kernel reads the terms where it read the velocities.
+ * Draws, ray ids, trees, rl_mcts_best, rl_mcts_read_tree and rl_mcts_drive's outputs are unchanged in form.  Nothing
+ * new crosses to the host between iterations or decisions.
+ *
+ * The state behind every term.  (x_i, y_i, v_i) is the float64 state after roll-out step i, i = 0 ... L-1, from the
+ *   same car_step sequence as rl_car_rollout.  All arithmetic below is float64, every operation rounded separately,
+ *   no contraction (the library is built with -ffp-contract=off).  "The section" is scanlib.h's "track progress".
+ * reward_mode 0 (velocity): term_i = v_i, the planner of scanlib.h.  A planner with no track, or with mode 0
+ *   attached, is bit-identical to it in every output.
+ * reward_mode 1 (waypoint, mcts.py:234): term_i = v_i / sqrt((px-x_i)*(px-x_i) + (py-y_i)*(py-y_i)), IEEE inf / NaN
+ *   kept.  (px, py) is the tree's track point: the explicit point of rl_mcts_set_points when one is set, as the
+ *   reference's constructor takes it; otherwise findBestPoint of the root position: the section's goal rule with the
+ *   attached lookahead and goal_span (goal_span == 0 is the reference's loop over all waypoints; goal_span > 0 looks
+ *   forward of the root's nearest segment over all segments), chosen at rl_mcts_reset and again for every decision of
+ *   rl_mcts_drive from the car's current state (mcts_driver.py:220).  A tree with no winner (goal -1) and no explicit
+ *   point uses term_i = v_i (the reference would raise there).  rl_car_rollout_track takes the points from
+ *   points_or_null; with null the point is the goal rule applied at each roll-out's start position.
+ * reward_mode 2 (progress): the anchor segment r is the nearest segment to the tree's root position over ALL segments
+ *   (the section's projection, its d2 tie rule, lowest index, and its rule for degenerate segments: rl_track_create
+ *   refuses them), found at reset and at every decision of the drive.  Candidates: all segments when window == 0,
+ *   otherwise the segments within `window` of r by the section's closed / open rule with p = r; the same for every
+ *   step of every roll-out of that tree.  s_start = s of the roll-out's start state (the new child) over the
+ *   candidates, s_i the same for step i; term_i = wrap(s_i - s_(i-1)) with s_(-1) = s_start and the section's +-L
+ *   rule (no laps are kept).  rl_car_rollout_track takes the anchors from anchor_segment_or_null (each in [0, S));
+ *   with null the anchor is a full search at the roll-out's start.
+ *
+ * rl_car_rollout_track: rl_car_rollout's R roll-outs with the terms [R x n_steps] of *p's reward_mode on track t.
+ *   n_steps <= 512.  anchor_segment_or_null is read in mode 2, points_or_null in mode 1; s, segment [R x n_steps] and
+ *   start_s [R] (each optional) are written in mode 2 only.  t may be null in mode 0, and in mode 1 with points.
+ * rl_mcts_attach_track: t is borrowed (keep it alive while attached); a null t detaches (p is not read).  The planner
+ *   needs a reset after attaching or detaching, and after rl_mcts_set_points.
+ * rl_mcts_set_points: one explicit point per tree (K x 2, copied), null removes them.  They are the track points of
+ *   mode 1; a planner with points and no track attached runs mode 1 with them.
+ * rl_mcts_read_track: per tree the current roots' segment, s, goal index and track point (K, K, K, K x 2; each
+ *   pointer optional); after rl_mcts_drive those of the last decision.  Without a track: segment -1, s NaN, goal -1.
+ *   With an explicit point the point reads back as given; without a goal or point it reads (0, 0).
+ * Errors (RL_ERR_INVALID, nothing launched, the handles usable as before): null params with a track; reward_mode
+ *   outside {0, 1, 2}; window or goal_span < 0 or > 65536; lookahead not finite or <= 0 in mode 1 without explicit
+ *   points; a track on another device; mode 2 without a track (mode 1 without a track or points likewise);
+ *   rl_mcts_drive on a planner with explicit points (the drive needs a track to re-choose the point);
+ *   rl_mcts_read_track before a reset or without a track or points; an anchor outside [0, S); n_steps > 512 and what
+ *   rl_car_rollout refuses; multi-device handles.
+ * Kernels: plan_root_kernel, plan_term_kernel (plan_track_kernels.h).  Cost: without a window every roll-out step
+ *   searches all S segments; long tracks want a window.                                                          */
+#ifndef SCANLIB_TRACK_PLAN_H
+#define SCANLIB_TRACK_PLAN_H
+
+#include "scanlib.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct rl_plan_track_params { int reward_mode, window, goal_span; double lookahead; } rl_plan_track_params;
+int rl_car_rollout_track(rl_car *c, rl_track *t, const rl_plan_track_params *p, const double *states,
+                        const double *actions, int n_rollouts, int n_steps, int action_every, double dt,
+                        const int *anchor_segment_or_null, const double *points_or_null, double *terms,
+                        double *s_or_null, int *segment_or_null, double *start_s_or_null);
+int rl_mcts_attach_track(rl_mcts *m, rl_track *t, const rl_plan_track_params *p);
+int rl_mcts_set_points(rl_mcts *m, const double *xy_k2_or_null);
+int rl_mcts_read_track(rl_mcts *m, int *segment, double *s, int *goal, double *point_k2);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

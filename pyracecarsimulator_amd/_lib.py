@@ -5,9 +5,10 @@ There is no Python/NumPy fallback — if the shared object is missing or no HIP
 device is usable, the calls raise.
 
 ``SYMBOLS`` restates every prototype of the header (tests/test_py_calls_host.py pins it to the header, argument by
-argument, with the structures and enums below).  ``call(name, *args)`` is how the package's wrappers enter the library:
-every argument is converted by the type ``SYMBOLS`` declares for it, and a symbol that returns ``rl_status`` is checked
-(``ScanLibError``) and gives None.  What a declared type takes:
+argument, with the structures and enums below); ``EXT_SYMBOLS`` does the same for include/scanlib_track_plan.h.
+``call(name, *args)`` is how the package's wrappers enter the library: every argument is converted by the type the
+tables declare for it, and a symbol that returns ``rl_status`` is checked (``ScanLibError``) and gives None.  What a
+declared type takes:
 
 * pointer to a scalar (``float *``, ``int *``, ``uint64_t *`` ...): an ``ndarray`` of exactly that dtype, C-contiguous
   (anything else is a ``TypeError`` naming symbol and position — never a silent copy, an output would be lost); None
@@ -97,6 +98,11 @@ class RaceEnvParams(C.Structure):
 class TrackParams(C.Structure):
     """rl_track_params (include/scanlib.h)."""
     _fields_ = [("window", C.c_int), ("goal_span", C.c_int), ("reward_mode", C.c_int), ("lookahead", C.c_double)]
+
+
+class PlanTrackParams(C.Structure):
+    """rl_plan_track_params (include/scanlib_track_plan.h)."""
+    _fields_ = [("reward_mode", C.c_int), ("window", C.c_int), ("goal_span", C.c_int), ("lookahead", C.c_double)]
 
 
 RL_MCTS_FG, RL_MCTS_NN, RL_MCTS_RANDOM = 0, 1, 2
@@ -249,6 +255,24 @@ SYMBOLS = {
     "rl_ranges_from_u16_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
 }
 
+#: every symbol include/scanlib_track_plan.h declares, in the shape of ``SYMBOLS`` (tests/test_mcts_track_host.py pins it
+#: to that header); ``raw``, ``converters`` and so ``call`` look here after ``SYMBOLS``
+EXT_SYMBOLS = {
+    "rl_car_rollout_track": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PlanTrackParams), f64p, f64p, C.c_int, C.c_int,
+                                       C.c_int, C.c_double, C.POINTER(C.c_int), f64p, f64p, f64p, C.POINTER(C.c_int),
+                                       f64p]),
+    "rl_mcts_attach_track": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PlanTrackParams)]),
+    "rl_mcts_set_points": (C.c_int, [C.c_void_p, f64p]),
+    "rl_mcts_read_track": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), f64p, C.POINTER(C.c_int), f64p]),
+}
+
+
+def declared(name):
+    """(restype, argtypes) of ``name`` from ``SYMBOLS``, then ``EXT_SYMBOLS``."""
+    ent = SYMBOLS.get(name)
+    return EXT_SYMBOLS[name] if ent is None else ent
+
+
 #: the symbols whose ``int`` is a value; every other ``int`` function returns rl_status (``call`` checks it)
 INT_VALUED = frozenset(("rl_device_count", "rl_launch_contexts", "rl_map_rows", "rl_map_cols", "rl_map_device",
                         "rl_map_n_devices", "rl_method_kind", "rl_method_n_devices", "rl_debug_read_stamps"))
@@ -282,7 +306,7 @@ def build(force: bool = False) -> str:
     """Compile libscan_amd.so for gfx950 with hipcc (in-tree; cross-compiles without a GPU)."""
     srcs = [os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc"))
             if f.endswith((".hip", ".h"))]
-    srcs.append(os.path.join(_HERE, "..", "include", "scanlib.h"))
+    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("scanlib.h", "scanlib_track_plan.h")]
     stale = (not os.path.exists(_SO)) or any(os.path.getmtime(s) > os.path.getmtime(_SO)
                                              for s in srcs)
     if force or stale:
@@ -326,7 +350,7 @@ def lib():
                 "g.build()'` (or make -C pyracecarsimulator_amd/csrc). There is no CPU fallback.")
         _share_torch_hip_runtime()
         L = C.CDLL(_SO)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()):
             try:
                 fn = getattr(L, name)
             except AttributeError:
@@ -348,7 +372,7 @@ def raw(name):
     a few microseconds on the 25-us scan() path."""
     fn = _RAW.get(name)
     if fn is None:
-        res, args = SYMBOLS[name]
+        res, args = declared(name)
         args = [C.c_void_p if (isinstance(a, type) and issubclass(a, C._Pointer)) else a for a in args]
         fn = C.CFUNCTYPE(res, *args)((name, lib()))
         _RAW[name] = fn
@@ -420,7 +444,7 @@ def converters(name):
     """(the all-``void *`` entry point, one converter per argument, returns rl_status?) of ``name``, built once."""
     ent = _CALLS.get(name)
     if ent is None:
-        res, args = SYMBOLS[name]
+        res, args = declared(name)
         ent = _CALLS[name] = (raw(name), tuple(_converter(name, i, t) for i, t in enumerate(args)),
                               res is C.c_int and name not in INT_VALUED)
     return ent

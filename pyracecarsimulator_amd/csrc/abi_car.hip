@@ -1,8 +1,12 @@
 // abi_car.hip — what sits in front of and behind the scan path in libscan_amd.so (C ABI: include/scanlib.h; SURVEY.md
 // section 8f): the MCTS roll-out generator, FollowGap, the policy network, the race scan; the closed-loop session (loop_args
 // and Loop: handle checks, locks, launch arguments, scan-then-consume) with its users drive_loop, rl_env_* and rl_mcts_*;
+// track-guided planning (include/scanlib_track_plan.h: the planner's track, rl_car_rollout_track);
 // 16-bit ranges for the xGMI exchange, diagnostics probes, the car-outline table and Car::isCrashed on the host.
 #include "abi_internal.h"
+#pragma GCC visibility push(default)
+#include "../../include/scanlib_track_plan.h"
+#pragma GCC visibility pop
 #include <array>
 #include <utility>
 #include "car_kernels.h"
@@ -11,6 +15,7 @@
 #include "env_kernels.h"
 #include "track_kernels.h"
 #include "mcts_kernels.h"
+#include "plan_track_kernels.h"
 #include "policy_kernels.h"
 #include "probe_kernels.h"
 #include "race_kernels.h"
@@ -31,6 +36,9 @@ struct rl_car {
     DevPtr<double> o_cars;                                     // rl_car_outline_cells
     DevPtr<int32_t> o_cells;
     DevPtr<int> o_counts;
+    // rl_car_rollout_track: the roll-outs' f64 positions, their terms and s, and the per-roll-out roots (PlanRoots)
+    DevPtr<double> tk_xy, tk_terms, tk_s, tk_start_s, tk_root_s, tk_point, tk_points_in;
+    DevPtr<int> tk_seg, tk_root_seg, tk_goal, tk_has;
     std::mutex mu;
 };
 
@@ -97,9 +105,9 @@ static int check_rollout_args(int R, int n_steps, int every)
 }
 
 // the roll-outs of hc's call (on c's stream): states and actions up, rollout_kernel into c->poses (and, when wanted,
-// c->states_out and c->vel)
+// c->states_out and c->vel; d_xy: the f64 positions [R][n_steps][2] where the caller wants them)
 static int car_rollout_device(rl_car *c, HostCall &hc, const double *states_in, const double *actions, int R, int n_steps,
-                              int every, double dt, bool want_states, bool want_vel)
+                              int every, double dt, bool want_states, bool want_vel, double *d_xy = nullptr)
 {
     int rc = check_rollout_args(R, n_steps, every);
     if (rc) return rc;
@@ -111,9 +119,13 @@ static int car_rollout_device(rl_car *c, HostCall &hc, const double *states_in, 
         (rc = hc.room(c->poses, n_poses * 3)) || (rc = hc.room(c->states_out, (size_t)R * 11)) ||
         (rc = hc.room(c->vel, n_poses)))
         return rc;
-    hipLaunchKernelGGL(rollout_kernel, dim3((R + 63) / 64), dim3(64), 0, hc.st, c->P, (const double *)c->states,
-                       (const double *)c->actions, R, n_steps, every, dt, (float *)c->poses,
-                       want_states ? (double *)c->states_out : nullptr, want_vel ? (double *)c->vel : nullptr);
+    if (d_xy)           // (rl_car_rollout_track: poses, velocities and positions, no final states)
+        hipLaunchKernelGGL(rollout_xy_kernel, dim3((R + 63) / 64), dim3(64), 0, hc.st, c->P, (const double *)c->states,
+                           (const double *)c->actions, R, n_steps, every, dt, (float *)c->poses, (double *)c->vel, d_xy);
+    else
+        hipLaunchKernelGGL(rollout_kernel, dim3((R + 63) / 64), dim3(64), 0, hc.st, c->P, (const double *)c->states,
+                           (const double *)c->actions, R, n_steps, every, dt, (float *)c->poses,
+                           want_states ? (double *)c->states_out : nullptr, want_vel ? (double *)c->vel : nullptr);
     HIPCHK(hipGetLastError());
     return RL_OK;
 }
@@ -1477,6 +1489,13 @@ struct rl_mcts {
     DevPtr<int> root_crash, dr_first, dr_visits;
     DevPtr<uint32_t> dr_keys;
     DevPtr<double> dr_actions, dr_trace;
+    // track-guided planning (rl_mcts_attach_track, rl_mcts_set_points): the borrowed track, its options, the explicit
+    // points, the roots' rows (PlanRoots) and the roll-outs' f64 positions and terms
+    rl_track *track = nullptr;
+    PlanTrackParams tp{};
+    bool has_points = false;
+    DevPtr<double> tk_points, tk_s, tk_point, rxy, terms;
+    DevPtr<int> tk_seg, tk_goal, tk_has;
     bool ready = false;            // reset done and no launch failed since (read and written under mu only)
     long iters = 0;                // iterations since reset
     uint64_t base = 0;             // h's ray offset at reset
@@ -1583,6 +1602,38 @@ static int mcts_act(rl_mcts *m, const Loop &lp, const MctsBufs &b, uint64_t off,
     return lp.scan_then(scan, off, mcts_act_table, MCTS_TREES, "mcts_act_kernel", st, m->mp, b, root);
 }
 
+// the reward mode the planner runs: the attached track's, the waypoint reward for explicit points alone, else velocity
+static int plan_mode(const rl_mcts *m)
+{
+    return m->track ? m->tp.mode : m->has_points ? PLAN_WAYPOINT : PLAN_VELOCITY;
+}
+
+static PlanRoots plan_roots_of(rl_mcts *m)
+{
+    return PlanRoots{m->tk_seg, m->tk_s, m->tk_goal, m->tk_point, m->tk_has};
+}
+
+// what a reset and a drive refuse of the track options before anything is launched
+static int plan_args(const rl_mcts *m, const char *name)
+{
+    if (plan_mode(m) == PLAN_WAYPOINT && !m->has_points && (!std::isfinite(m->tp.lookahead) || !(m->tp.lookahead > 0.0)))
+        return fail(RL_ERR_INVALID, "%s: the waypoint reward without explicit points needs a finite lookahead > 0", name);
+    return RL_OK;
+}
+
+// plan_root_kernel over the K root states in m->roots, on st: at a reset, and behind every mcts_advance_kernel that
+// wrote new roots.  A planner with neither track nor points launches nothing.
+static int plan_roots(rl_mcts *m, hipStream_t st)
+{
+    if (!m->track && !m->has_points) return RL_OK;
+    const int K = m->prm.n_trees;
+    const TrackTable T = m->track ? track_table(m->track) : TrackTable{};
+    hipLaunchKernelGGL(plan_root_kernel, dim3((K + MCTS_TREES - 1) / MCTS_TREES), dim3(64 * MCTS_TREES), 0, st, K, T, m->tp,
+                       (const double *)m->roots, m->has_points ? (const double *)m->tk_points : nullptr, plan_roots_of(m));
+    if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "plan_root_kernel launch failed");
+    return RL_OK;
+}
+
 // how rl_mcts_reset and rl_mcts_drive begin: the keys go up to d_keys, the K root states and root (recent) actions into
 // m->roots, then mcts_start_kernel makes the root nodes
 static int mcts_start(rl_mcts *m, HostCall &hc, const MctsBufs &b, DevPtr<uint32_t> &d_keys, const std::vector<uint32_t> &keys,
@@ -1597,7 +1648,7 @@ static int mcts_start(rl_mcts *m, HostCall &hc, const MctsBufs &b, DevPtr<uint32
     hipLaunchKernelGGL(mcts_start_kernel, dim3((K + 63) / 64), dim3(64), 0, hc.st, m->mp, b, (const double *)d_states,
                        (const double *)d_actions);
     if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "mcts_start_kernel launch failed");
-    return RL_OK;
+    return plan_roots(m, hc.st);
 }
 
 extern "C" int rl_mcts_reset(rl_mcts *m, const double *root_states, const double *root_actions, const uint64_t *seeds)
@@ -1607,6 +1658,7 @@ extern "C" int rl_mcts_reset(rl_mcts *m, const double *root_states, const double
     int rc = check_fan_args(m->h, K, m->prm.fov, m->prm.num_rays);
     if (rc) return rc;
     const Loop lp(&m->mu, m->c, m->h, m->g, m->p);
+    if ((rc = plan_args(m, "rl_mcts_reset"))) return rc;
     HIPCHK(hipSetDevice(m->device));
     m->ready = false;
     std::vector<uint32_t> keys(K);
@@ -1624,9 +1676,17 @@ extern "C" int rl_mcts_reset(rl_mcts *m, const double *root_states, const double
 
 // iterations it0 ... it0 + n - 1 of every tree, enqueued on st: select, the act, the roll-outs and their crash
 // test, the backup.  base: the ray offset of the trees' reset.  lp: the call's Loop; the caller has sized m->rranges.
-static int mcts_iterations(rl_mcts *m, const Loop &lp, const MctsBufs &b, uint64_t base, long it0, int n, hipStream_t st)
+// With a reward mode other than velocity the roll-outs also give their f64 positions, plan_term_kernel turns them into
+// the terms, and the backup sums those.
+static int mcts_iterations(rl_mcts *m, const Loop &lp, const MctsBufs &bufs, uint64_t base, long it0, int n, hipStream_t st)
 {
     const int K = m->prm.n_trees, L = m->prm.rollout_steps, B = m->prm.num_rays;
+    const bool terms = plan_mode(m) != PLAN_VELOCITY;
+    const TrackTable T = m->track ? track_table(m->track) : TrackTable{};
+    PlanTrackParams tp = m->tp;
+    tp.mode = plan_mode(m);
+    MctsBufs b = bufs;
+    if (terms) b.vel = m->terms;
     const uint64_t KB = (uint64_t)K * B, per_it = (uint64_t)K * (1 + L) * B;
     int rc = RL_OK;
     for (int t = 0; t < n && rc == RL_OK; ++t) {
@@ -1636,10 +1696,21 @@ static int mcts_iterations(rl_mcts *m, const Loop &lp, const MctsBufs &b, uint64
         if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_select_kernel launch failed");
         if (!rc) rc = mcts_act(m, lp, b, off, 0, st);
         if (!rc) {
-            hipLaunchKernelGGL(rollout_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, (const double *)m->cstate,
-                               (const double *)m->actions, K, L, m->prm.action_every, m->prm.dt, (float *)m->rposes,
-                               (double *)nullptr, (double *)m->vel);
+            if (terms)
+                hipLaunchKernelGGL(rollout_xy_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, (const double *)m->cstate,
+                                   (const double *)m->actions, K, L, m->prm.action_every, m->prm.dt, (float *)m->rposes,
+                                   (double *)m->vel, (double *)m->rxy);
+            else
+                hipLaunchKernelGGL(rollout_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, (const double *)m->cstate,
+                                   (const double *)m->actions, K, L, m->prm.action_every, m->prm.dt, (float *)m->rposes,
+                                   (double *)nullptr, (double *)m->vel);
             if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "rollout_kernel launch failed");
+        }
+        if (!rc && terms) {
+            hipLaunchKernelGGL(plan_term_kernel, dim3(K), dim3(64 * PLAN_TERM_WAVES), 0, st, T, tp, L, (const double *)m->cstate,
+                               (const double *)m->rxy, (const double *)m->vel, plan_roots_of(m), (double *)m->terms,
+                               (double *)nullptr, (int *)nullptr, (double *)nullptr);
+            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "plan_term_kernel launch failed");
         }
         if (!rc)
             rc = crash_groups_device(m->h, lp.at(off + KB), m->rposes, K, L, m->prm.fov, B, m->edge, m->prm.crash_thresh,
@@ -1700,6 +1771,13 @@ extern "C" int rl_mcts_drive(rl_mcts *m, const double *states_in, const double *
     const int K = m->prm.n_trees, L = m->prm.rollout_steps, B = m->prm.num_rays, D = n_decisions, I = n_iterations;
     int rc;
     if ((rc = check_fan_args(m->h, K, m->prm.fov, B)) || (rc = check_fan_args(m->h, K * L, m->prm.fov, B))) return rc;
+    {
+        std::lock_guard<std::mutex> lk(m->mu);
+        if (m->has_points)
+            return fail(RL_ERR_INVALID, "rl_mcts_drive: explicit points (rl_mcts_set_points) cannot be driven: attach a track, "
+                        "which re-chooses the point at every decision");
+        if ((rc = plan_args(m, "rl_mcts_drive"))) return rc;
+    }
     if (D == 0) {
         for (int k = 0; k < K; ++k) first[k] = -1;
         if (states_out != states_in) memmove(states_out, states_in, (size_t)K * 11 * sizeof(double));
@@ -1736,6 +1814,7 @@ extern "C" int rl_mcts_drive(rl_mcts *m, const double *states_in, const double *
             hipLaunchKernelGGL(mcts_advance_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, dv, d);
             if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_advance_kernel launch failed");
         }
+        if (!rc && d + 1 < D) rc = plan_roots(m, st);          // the next decision's roots: their segment, goal and point
     }
     if (rc) return rc;                                 // (the trees need a reset)
     // the planner keeps the last decision's trees: its keys, ray offset and iteration count are that decision's
@@ -1829,4 +1908,135 @@ extern "C" int rl_mcts_probe_ucb(int device, const double *reward, const int *vi
     if (hipMemcpy(out, dout.p, n * 8, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(RL_ERR_HIP, "rl_mcts_probe_ucb: kernel or download failed");
     return RL_OK;
+}
+
+// ---------------------------------------------------------------- track-guided planning (plan_track_kernels.h)
+// what rl_mcts_attach_track and rl_car_rollout_track refuse of *p (contract: include/scanlib_track_plan.h); `points`:
+// explicit points stand in for the goal rule
+static int plan_track_args(const char *name, const rl_plan_track_params *p, bool points)
+{
+    if (!p) return fail(RL_ERR_INVALID, "%s: null params", name);
+    if (p->reward_mode < PLAN_VELOCITY || p->reward_mode > PLAN_PROGRESS)
+        return fail(RL_ERR_INVALID, "%s: reward_mode must be 0, 1 or 2 (got %d)", name, p->reward_mode);
+    if (p->window < 0 || p->window > 65536 || p->goal_span < 0 || p->goal_span > 65536)
+        return fail(RL_ERR_INVALID, "%s: window and goal_span must lie in [0, 65536] (got %d, %d)", name, p->window,
+                    p->goal_span);
+    if (p->reward_mode == PLAN_WAYPOINT && !points && (!std::isfinite(p->lookahead) || !(p->lookahead > 0.0)))
+        return fail(RL_ERR_INVALID, "%s: the waypoint reward without explicit points needs a finite lookahead > 0", name);
+    return RL_OK;
+}
+
+extern "C" int rl_mcts_attach_track(rl_mcts *m, rl_track *t, const rl_plan_track_params *p)
+{
+    if (!m) return fail(RL_ERR_INVALID, "rl_mcts_attach_track: null pointer");
+    std::scoped_lock lk(m->mu, m->c->mu);
+    if (t) {
+        int rc = plan_track_args("rl_mcts_attach_track", p, m->has_points);
+        if (rc) return rc;
+        if (t->device != m->device)
+            return fail(RL_ERR_INVALID, "rl_mcts_attach_track: track (device %d) and planner (device %d) must share one device",
+                        t->device, m->device);
+        HIPCHK(hipSetDevice(m->device));
+        const size_t K = m->prm.n_trees, L = m->prm.rollout_steps;
+        if ((rc = m->tk_seg.ensure(K)) || (rc = m->tk_s.ensure(K)) || (rc = m->tk_goal.ensure(K)) ||
+            (rc = m->tk_point.ensure(K * 2)) || (rc = m->tk_has.ensure(K)) || (rc = m->rxy.ensure(K * L * 2)) ||
+            (rc = m->terms.ensure(K * L)))
+            return rc;
+        m->tp = PlanTrackParams{p->reward_mode, p->window, p->goal_span, p->lookahead};
+    }
+    m->track = t;
+    m->ready = false;                   // the roots of the new track are found at the next reset
+    return RL_OK;
+}
+
+extern "C" int rl_mcts_set_points(rl_mcts *m, const double *xy_k2_or_null)
+{
+    if (!m) return fail(RL_ERR_INVALID, "rl_mcts_set_points: null pointer");
+    std::scoped_lock lk(m->mu, m->c->mu);
+    if (xy_k2_or_null) {
+        HIPCHK(hipSetDevice(m->device));
+        const size_t K = m->prm.n_trees, L = m->prm.rollout_steps;
+        int rc;
+        if ((rc = m->tk_points.ensure(K * 2)) || (rc = m->tk_seg.ensure(K)) || (rc = m->tk_s.ensure(K)) ||
+            (rc = m->tk_goal.ensure(K)) || (rc = m->tk_point.ensure(K * 2)) || (rc = m->tk_has.ensure(K)) ||
+            (rc = m->rxy.ensure(K * L * 2)) || (rc = m->terms.ensure(K * L)))
+            return rc;
+        HostCall hc(m->c->stream);      // (the planner's launches read the points on this stream)
+        if ((rc = hc.up((double *)m->tk_points, xy_k2_or_null, K * 2)) || (rc = hc.finish())) return rc;
+    }
+    m->has_points = xy_k2_or_null != nullptr;
+    m->ready = false;
+    return RL_OK;
+}
+
+extern "C" int rl_mcts_read_track(rl_mcts *m, int *segment, double *s, int *goal, double *point_k2)
+{
+    if (!m) return fail(RL_ERR_INVALID, "rl_mcts_read_track: null pointer");
+    std::scoped_lock lk(m->mu, m->c->mu);
+    if (!m->track && !m->has_points)
+        return fail(RL_ERR_INVALID, "rl_mcts_read_track: no track attached and no points set (rl_mcts_attach_track)");
+    if (!m->ready) return fail(RL_ERR_INVALID, "rl_mcts_read_track: reset the planner first (rl_mcts_reset)");
+    HIPCHK(hipSetDevice(m->device));
+    HostCall hc(m->c->stream);
+    const size_t K = m->prm.n_trees;
+    int rc;
+    if ((rc = hc.down(segment, m->tk_seg, K)) || (rc = hc.down(s, m->tk_s, K)) || (rc = hc.down(goal, m->tk_goal, K)) ||
+        (rc = hc.down(point_k2, m->tk_point, K * 2)))
+        return rc;
+    return hc.finish();
+}
+
+extern "C" int rl_car_rollout_track(rl_car *c, rl_track *t, const rl_plan_track_params *p, const double *states,
+                                    const double *actions, int R, int n_steps, int every, double dt,
+                                    const int *anchor_segment_or_null, const double *points_or_null, double *terms,
+                                    double *s_or_null, int *segment_or_null, double *start_s_or_null)
+{
+    if (!c || (R > 0 && (!states || !actions || !terms))) return fail(RL_ERR_INVALID, "rl_car_rollout_track: null pointer");
+    if (!c->reps.empty()) return fail(RL_ERR_INVALID, "rl_car_rollout_track is single-device only: pass an ordinary car handle");
+    int rc = plan_track_args("rl_car_rollout_track", p, points_or_null != nullptr);
+    if (rc || (rc = check_rollout_args(R, n_steps, every))) return rc;
+    if (n_steps > MCTS_MAX_STEPS)
+        return fail(RL_ERR_INVALID, "rl_car_rollout_track: n_steps must not exceed %d (got %d)", MCTS_MAX_STEPS, n_steps);
+    const int mode = p->reward_mode;
+    if (!t && (mode == PLAN_PROGRESS || (mode == PLAN_WAYPOINT && !points_or_null)))
+        return fail(RL_ERR_INVALID, "rl_car_rollout_track: reward_mode %d needs a track%s", mode,
+                    mode == PLAN_WAYPOINT ? " or explicit points" : "");
+    if (t && t->device != c->device)
+        return fail(RL_ERR_INVALID, "rl_car_rollout_track: track (device %d) and car (device %d) must share one device",
+                    t->device, c->device);
+    const bool anchors = mode == PLAN_PROGRESS && anchor_segment_or_null, points = mode == PLAN_WAYPOINT && points_or_null;
+    if (anchors)
+        for (int r = 0; r < R; ++r)
+            if (anchor_segment_or_null[r] < 0 || anchor_segment_or_null[r] >= t->S)
+                return fail(RL_ERR_INVALID, "rl_car_rollout_track: anchor segment %d of roll-out %d lies outside [0, %d)",
+                            anchor_segment_or_null[r], r, t->S);
+    std::lock_guard<std::mutex> lk(c->mu);
+    HostCall hc(c->stream);
+    const size_t n = (size_t)std::max(R, 0), rows = n * n_steps;
+    HIPCHK(hipSetDevice(c->device));
+    if (R == 0) return RL_OK;
+    if ((rc = hc.room(c->tk_xy, rows * 2)) || (rc = hc.room(c->tk_terms, rows)) || (rc = hc.room(c->tk_s, rows)) ||
+        (rc = hc.room(c->tk_seg, rows)) || (rc = hc.room(c->tk_start_s, n)) || (rc = hc.room(c->tk_root_seg, n)) ||
+        (rc = hc.room(c->tk_root_s, n)) || (rc = hc.room(c->tk_goal, n)) || (rc = hc.room(c->tk_point, n * 2)) ||
+        (rc = hc.room(c->tk_has, n)) || (points && (rc = hc.up(c->tk_points_in, points_or_null, n * 2))) ||
+        (rc = car_rollout_device(c, hc, states, actions, R, n_steps, every, dt, false, true, c->tk_xy)))
+        return rc;
+    // the roots of the roll-outs: their start states (c->states, uploaded above); the caller's anchors replace the search's
+    const TrackTable T = t ? track_table(t) : TrackTable{};
+    const PlanTrackParams tp{mode, p->window, p->goal_span, p->lookahead};
+    const PlanRoots roots{c->tk_root_seg, c->tk_root_s, c->tk_goal, c->tk_point, c->tk_has};
+    hipLaunchKernelGGL(plan_root_kernel, dim3((R + MCTS_TREES - 1) / MCTS_TREES), dim3(64 * MCTS_TREES), 0, hc.st, R, T, tp,
+                       (const double *)c->states, points ? (const double *)c->tk_points_in : nullptr, roots);
+    HIPCHK(hipGetLastError());
+    if (anchors && (rc = hc.up((int *)c->tk_root_seg, anchor_segment_or_null, n))) return rc;
+    hipLaunchKernelGGL(plan_term_kernel, dim3(R), dim3(64 * PLAN_TERM_WAVES), 0, hc.st, T, tp, n_steps, (const double *)c->states,
+                       (const double *)c->tk_xy, (const double *)c->vel, roots, (double *)c->tk_terms, (double *)c->tk_s,
+                       (int *)c->tk_seg, (double *)c->tk_start_s);
+    HIPCHK(hipGetLastError());
+    const bool progress = mode == PLAN_PROGRESS;
+    if ((rc = hc.down(terms, c->tk_terms, rows)) || (rc = hc.down(progress ? s_or_null : nullptr, c->tk_s, rows)) ||
+        (rc = hc.down(progress ? segment_or_null : nullptr, c->tk_seg, rows)) ||
+        (rc = hc.down(progress ? start_s_or_null : nullptr, c->tk_start_s, n)))
+        return rc;
+    return hc.finish();
 }

@@ -45,6 +45,9 @@ BOUNDS = [
     ("scan::mcts_best_kernel", {"scratch": 0}),
     ("scan::mcts_advance_kernel", {"scratch": 0}),
     ("scan::mcts_ucb_probe_kernel", {"scratch": 0}),
+    # track-guided planning: the roots' wave and the term workgroup spill nothing, and eight waves share a SIMD
+    ("scan::plan_root_kernel", {"scratch": 0, "occupancy": 8}),
+    ("scan::plan_term_kernel", {"scratch": 0, "occupancy": 8}),
     # batched races: the outline raster, and the race scan's march with the other cars' cells folded into each sample
     ("scan::outline_cells_kernel", {"scratch": 0}),
     ("scan::race_fan_kernel<", {"scratch": 0}),

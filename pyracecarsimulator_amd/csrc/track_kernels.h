@@ -88,6 +88,62 @@ __device__ inline int track_wrap(const TrackTable &T, double &d)
     return 0;
 }
 
+// the candidate segments of a search around segment p: `count` of them from `first`, wrapping on a closed track; all
+// of them when window == 0 or once 2 window + 1 >= S
+__device__ inline void track_window(const TrackTable &T, int window, int p, int &first, int &count)
+{
+    first = 0;
+    count = T.S;
+    if (window <= 0 || 2 * window + 1 >= T.S) return;
+    if (T.closed) {
+        first = p - window;
+        if (first < 0) first += T.S;
+        count = 2 * window + 1;
+    } else {
+        first = max(p - window, 0);
+        count = min(p + window, T.S - 1) - first + 1;
+    }
+}
+
+// the nearest of the candidate segments to (cx, cy), the lowest index among equal d2, in every lane of the wave
+__device__ inline int track_nearest(const TrackTable &T, int first, int count, double cx, double cy, int lane)
+{
+    double bv = INFINITY;
+    int bi = INT_MAX;
+    for (int m = lane; m < count; m += 64) {
+        int i = first + m;
+        if (i >= T.S) i -= T.S;
+        const double d2 = track_project(T, i, cx, cy, nullptr);
+        if (track_less(d2, i, bv, bi)) bv = d2, bi = i;
+    }
+    track_wave_min(bv, bi);
+    return bi == INT_MAX ? first : bi;                          // (every d2 a NaN: coordinates beyond 1e154)
+}
+
+// the goal waypoint seen from (cx, cy) with nearest segment seg (-1: none), in every lane of the wave: candidates in
+// order of m, the first among equals, and only inside 2 lookahead
+__device__ inline int track_goal(const TrackTable &T, double lookahead, int goal_span, int seg, double cx, double cy, int lane)
+{
+    int gfirst = 0, gcount = T.W;
+    if (goal_span > 0) {
+        gfirst = seg + 1;
+        gcount = T.closed ? min(goal_span, T.W) : min(goal_span, T.W - 1 - seg);
+    }
+    double gv = INFINITY;
+    int gm = INT_MAX;
+    for (int m = lane; m < gcount; m += 64) {
+        int j = gfirst + m;
+        if (j >= T.W) j -= T.W;
+        const double rx = T.x[j] - cx, ry = T.y[j] - cy;
+        const double g = fabs(lookahead - sqrt(rx * rx + ry * ry));
+        if (track_less(g, m, gv, gm)) gv = g, gm = m;
+    }
+    track_wave_min(gv, gm);
+    if (gm == INT_MAX || !(gv < 2.0 * lookahead)) return -1;
+    const int goal = gfirst + gm;
+    return goal >= T.W ? goal - T.W : goal;
+}
+
 template <bool RACE>
 __global__ __launch_bounds__(64 * (RACE ? RACE_MAX_GROUP : DRIVE_CARS)) void track_kernel(
     int n_envs, TrackTable T, TrackParams tp, TrackBufs tb, const double *__restrict__ state,
@@ -109,51 +165,13 @@ __global__ __launch_bounds__(64 * (RACE ? RACE_MAX_GROUP : DRIVE_CARS)) void tra
     if (live) {                                                 // (wave-uniform)
         cx = state[(size_t)e * 11 + 0];
         cy = state[(size_t)e * 11 + 1];
-        // the candidate segments: `count` of them from `first`, wrapping on a closed track
+        // the candidate segments: all for a fresh env, otherwise those within the window of the previous nearest one
         int first = 0, count = T.S;
-        if (!fresh && tp.window > 0 && 2 * tp.window + 1 < T.S) {
-            const int prev = ints[TRACK_SEGMENT];
-            if (T.closed) {
-                first = prev - tp.window;
-                if (first < 0) first += T.S;
-                count = 2 * tp.window + 1;
-            } else {
-                first = max(prev - tp.window, 0);
-                count = min(prev + tp.window, T.S - 1) - first + 1;
-            }
-        }
-        double bv = INFINITY;
-        int bi = INT_MAX;
-        for (int m = lane; m < count; m += 64) {
-            int i = first + m;
-            if (i >= T.S) i -= T.S;
-            const double d2 = track_project(T, i, cx, cy, nullptr);
-            if (track_less(d2, i, bv, bi)) bv = d2, bi = i;
-        }
-        track_wave_min(bv, bi);
-        seg = bi == INT_MAX ? first : bi;                       // (every d2 a NaN: coordinates beyond 1e154)
+        if (!fresh) track_window(T, tp.window, ints[TRACK_SEGMENT], first, count);
+        seg = track_nearest(T, first, count, cx, cy, lane);
         track_project(T, seg, cx, cy, &t);
         s = T.cum[seg] + t * T.len[seg];
-        // the goal waypoint: candidates in order of m, the first among equals, and only inside 2 lookahead
-        int gfirst = 0, gcount = T.W;
-        if (tp.goal_span > 0) {
-            gfirst = seg + 1;
-            gcount = T.closed ? min(tp.goal_span, T.W) : min(tp.goal_span, T.W - 1 - seg);
-        }
-        double gv = INFINITY;
-        int gm = INT_MAX;
-        for (int m = lane; m < gcount; m += 64) {
-            int j = gfirst + m;
-            if (j >= T.W) j -= T.W;
-            const double rx = T.x[j] - cx, ry = T.y[j] - cy;
-            const double g = fabs(tp.lookahead - sqrt(rx * rx + ry * ry));
-            if (track_less(g, m, gv, gm)) gv = g, gm = m;
-        }
-        track_wave_min(gv, gm);
-        if (gm != INT_MAX && gv < 2.0 * tp.lookahead) {
-            goal = gfirst + gm;
-            if (goal >= T.W) goal -= T.W;
-        }
+        goal = track_goal(T, tp.lookahead, tp.goal_span, seg, cx, cy, lane);
     }
 
     // the spawn offset against car 0 of the race (a race spawns as a whole: car 0 is fresh with the others)

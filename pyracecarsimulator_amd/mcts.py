@@ -8,6 +8,10 @@ nothing leaving the device between iterations.  The trees are the reference's bi
 decision a fresh tree from the car's state, the search, the most visited root action, the car's steps with it — all
 decisions enqueued at once, nothing leaving the device in between.
 
+``MCTSPlanner.attach_track`` gives the planner a ``Track`` (include/scanlib_track_plan.h; kernels
+csrc/plan_track_kernels.h): every roll-out step's reward term becomes the reference's waypoint reward (mcts.py:233-234)
+or the track progress of the step, for ``run`` and for ``drive`` alike, with nothing new crossing to the host.
+
 ``MCTS`` is a drop-in for the reference class (scripts/mcts.py:83-148) on a ``RacecarSimulator``: ``mcts()`` plans
 from the simulator's state and returns the most visited root action; ``root`` holds the tree read back from the
 device as ``Node`` objects.
@@ -22,6 +26,9 @@ import numpy as np
 from . import _lib
 
 SOURCES = {"fg": _lib.RL_MCTS_FG, "nn": _lib.RL_MCTS_NN, "random": _lib.RL_MCTS_RANDOM}
+#: the reward term of a roll-out step (rl_plan_track_params.reward_mode)
+REWARDS = {"velocity": 0, "waypoint": 1, "progress": 2}
+MAX_TRACK_POINTS = 65536
 TREE_FIELDS = ("parent", "first_child", "next_sibling", "n_children", "visits", "child_visits", "reward", "action",
                "terminal", "state", "scan_pose", "answer", "crash")
 
@@ -81,11 +88,41 @@ def drive_args(n_trees, states, recent_actions, seeds, n_decisions, n_iterations
             np.ascontiguousarray(np.broadcast_to(sd.astype(np.uint64), (K,))), D, I, S, clip)
 
 
+def plan_track_args(reward="progress", lookahead=1.5, window=0, goal_span=0, points=False):
+    """The track keywords of the planner and of ``CarBatch.rollout_track`` checked and laid out as
+    ``rl_plan_track_params`` (no library call).  ``points``: explicit points stand in for the goal rule, so the
+    lookahead is not read."""
+    if reward not in REWARDS:
+        raise ValueError("reward must be one of %s" % sorted(REWARDS))
+    for name, v in (("window", window), ("goal_span", goal_span)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("%s must be an integer" % name)
+        if not 0 <= int(v) <= MAX_TRACK_POINTS:
+            raise ValueError("%s must lie in [0, %d]" % (name, MAX_TRACK_POINTS))
+    la = float(lookahead)
+    if reward == "waypoint" and not points and (not np.isfinite(la) or la <= 0):
+        raise ValueError("lookahead must be finite and > 0")
+    p = _lib.PlanTrackParams()
+    p.reward_mode, p.window, p.goal_span, p.lookahead = REWARDS[reward], int(window), int(goal_span), la
+    return p
+
+
+def points_args(xy, n):
+    """Explicit track points checked and laid out (no library call): float64 (n, 2), or one point for all."""
+    p = np.asarray(xy, np.float64)
+    if p.shape == (2,):
+        p = np.broadcast_to(p, (int(n), 2))
+    if p.shape != (int(n), 2):
+        raise ValueError("points must be (2,) or (%d, 2)" % int(n))
+    return np.ascontiguousarray(p)
+
+
 class MCTSPlanner(_lib.Handle):
     """K trees of at most ``max_nodes`` nodes on one device.  ``method`` scans, ``source`` ("fg", "nn" or "random")
     picks the expansion answer: ``followgap`` (a ``PyFollowGap``) for "fg", ``policy`` (a ``Policy``) for "nn".
     The handles are borrowed: keep them alive as long as the planner."""
     _destroy = "rl_mcts_destroy"
+    _track, _points = None, False       # (the attached Track, kept alive here; are explicit points set)
 
     def __init__(self, car, method, n_trees, max_nodes, fov, num_rays, edge, crash_thresh, source="fg",
                  followgap=None, policy=None, rollout_steps=200, action_every=10, speed=2.0, dt=0.01,
@@ -109,6 +146,37 @@ class MCTSPlanner(_lib.Handle):
         self._keep = (car, method, followgap, policy)
         self._h = C.c_void_p()
         _lib.call("rl_mcts_create", car, method, followgap, policy, p, self._edge, self._h)
+
+    def attach_track(self, track, reward="progress", lookahead=1.5, window=0, goal_span=0):
+        """Give the planner ``track`` (a ``Track``, borrowed: kept alive here while attached).  ``reward``: "progress"
+        (per step the arc length gained, searched within ``window`` segments of the root's nearest segment; 0: all),
+        "waypoint" (velocity over the distance to the tree's track point: the waypoint ``lookahead`` away from the
+        root, findBestPoint's rule, looking ``goal_span`` waypoints ahead; 0: all) or "velocity" (today's reward).
+        Takes effect at the next ``reset`` or ``drive``."""
+        p = plan_track_args(reward, lookahead, window, goal_span, points=self._points)
+        if track is None:
+            raise ValueError("track must be a Track (detach_track() removes it)")
+        _lib.call("rl_mcts_attach_track", self, track, p)
+        self._track = track
+
+    def detach_track(self):
+        _lib.call("rl_mcts_attach_track", self, None, None)
+        self._track = None
+
+    def set_points(self, xy):
+        """One explicit track point per tree, float64 (K, 2) or (2,) for all (None removes them): the waypoint reward's
+        point, as the reference's constructor takes it.  Without a track the planner then runs the waypoint reward."""
+        p = None if xy is None else points_args(xy, self.n_trees)
+        _lib.call("rl_mcts_set_points", self, p)
+        self._points = p is not None
+
+    def read_track(self):
+        """The current roots on the track, a dict: segment int32 (K,), s float64 (K,), goal int32 (K,) (-1: none), point
+        float64 (K, 2).  After ``drive``: those of the last decision."""
+        K = self.n_trees
+        out = dict(segment=np.empty(K, np.int32), s=np.empty(K), goal=np.empty(K, np.int32), point=np.empty((K, 2)))
+        _lib.call("rl_mcts_read_track", self, out["segment"], out["s"], out["goal"], out["point"])
+        return out
 
     def reset(self, root_states, root_actions, seeds):
         """The K roots: states float64 (K, 11) in getState layout, recent actions (K,), one 64-bit seed per tree."""
@@ -150,6 +218,8 @@ class MCTSPlanner(_lib.Handle):
         int32 (K, D) — -1 from the crash on) and with ``trace=True`` also the states every decision was planned
         from, (K, D, 11).  The planner keeps the last decision's trees (``read_tree``, ``best``)."""
         K = self.n_trees
+        if self._points:
+            raise ValueError("a planner with explicit points cannot drive: attach a track instead")
         st, ac, sd, D, I, S, clip = drive_args(K, states, recent_actions, seeds, n_decisions, n_iterations,
                                                steps_per_decision, steer_clip)
         first, out, recent = np.empty(K, np.int32), np.empty((K, 11)), np.empty(K)
@@ -203,11 +273,15 @@ class MCTS:
     ``budget`` seconds of wall clock run chunks of iterations until the time is spent or ``max_nodes`` is reached,
     at least one iteration; ``n_iterations`` runs exactly that many instead (deterministic).  ``seed`` keys the
     draws.  ``source``: "fg" (the reference's live generateActionFromFG, PyFollowGap(10, 15.0, max_steer, 0.004)),
-    "nn" (``policy_session``, a ``Policy``) or "random".  ``track_point`` and ``with_global`` are accepted and have
-    no effect: their only use, the waypoint reward, is commented out in the reference (mcts.py:233-234)."""
+    "nn" (``policy_session``, a ``Policy``) or "random".  ``with_global=True`` with a ``track_point`` (x, y) is the
+    reference's global-planner call (mcts_driver.py:224-227): every roll-out step is rewarded with its velocity over the
+    distance to that point (mcts.py:233-234, 247-250, commented out upstream).  ``with_global=False``, the default,
+    is the velocity reward, whatever ``track_point`` holds."""
 
     def __init__(self, simulator, policy_session, recent_action, roll_out_itr, budget=1.0, track_point=None,
                  with_global=False, *, seed=0, n_iterations=None, source="fg", max_nodes=4097):
+        if with_global and track_point is None:
+            raise ValueError("with_global=True needs a track_point")
         self.point_to_follow = track_point
         self.with_global = with_global
         self.simulator = simulator
@@ -242,6 +316,8 @@ class MCTS:
     def mcts(self):
         if self._planner is None:
             self._planner = self._make_planner()
+            if self.with_global:
+                self._planner.set_points(self.point_to_follow)
         pl = self._planner
         pl.reset(self.simulator.getState()[None, :], [self.action], [self.seed])
         cap = self.max_nodes - 1

@@ -113,6 +113,40 @@ class CarBatch(_lib.Handle):
                   edge, crash_thresh, first, out, vel)
         return first, out, vel
 
+    def rollout_track(self, track, states, actions, reward="progress", lookahead=1.5, window=0, goal_span=0,
+                      anchors=None, points=None, n_steps=200, action_every=10, dt=0.01):
+        """``rollout``'s roll-outs with the per-step reward terms of the track-guided planner
+        (``rl_car_rollout_track``, include/scanlib_track_plan.h) on ``track`` (a ``Track``; None for "velocity", and
+        for "waypoint" with ``points``).  ``reward`` and the keywords as ``MCTSPlanner.attach_track``; ``anchors``
+        int32 (R,): the segments the "progress" windows are centred on (None: the nearest segment of each start);
+        ``points`` float64 (R, 2) or (2,): the "waypoint" points (None: the goal rule at each start).  Returns a dict:
+        terms float64 (R, n_steps) and, for "progress", s (R, n_steps), segment int32 (R, n_steps), start_s (R,)."""
+        from .mcts import plan_track_args, points_args
+        states, actions = self._prep(states, actions, n_steps, action_every)
+        R = states.shape[0]
+        p = plan_track_args(reward, lookahead, window, goal_span, points=points is not None)
+        if track is None and (reward == "progress" or (reward == "waypoint" and points is None)):
+            raise ValueError("reward %r needs a track" % reward)
+        if not 1 <= int(n_steps) <= 512:
+            raise ValueError("n_steps must lie in [1, 512]")
+        anc = pts = None
+        if anchors is not None:
+            anc = np.asarray(anchors)
+            if anc.dtype.kind not in "iu" or anc.shape != (R,):
+                raise ValueError("anchors must be integers (%d,)" % R)
+            if track is not None and ((anc < 0) | (anc >= track.n_segments)).any():
+                raise ValueError("anchors must lie in [0, %d)" % track.n_segments)
+            anc = np.ascontiguousarray(anc, np.int32)
+        if points is not None:
+            pts = points_args(points, R)
+        progress = reward == "progress"
+        out = dict(terms=np.empty((R, n_steps)))
+        if progress:
+            out.update(s=np.empty((R, n_steps)), segment=np.empty((R, n_steps), np.int32), start_s=np.empty(R))
+        _lib.call("rl_car_rollout_track", self, track, p, states, actions, R, n_steps, action_every, dt, anc, pts,
+                  out["terms"], out.get("s"), out.get("segment"), out.get("start_s"))
+        return out
+
     def drive_followgap(self, method, followgap, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
                         scan_dist_to_base=0.275, dt=0.01, steer0=None, trace=False):
         """Closed-loop Follow-the-Gap roll-outs (``rl_car_drive_followgap``): every tick steps each live car,
@@ -176,13 +210,14 @@ class CarBatch(_lib.Handle):
     def plan_mcts(self, method, followgap_or_policy, root_states, n_iterations, seeds, fov, num_rays, edge,
                   crash_thresh, root_actions=0.0, source=None, rollout_steps=200, action_every=10, speed=2.0,
                   dt=0.01, scan_dist_to_base=0.275, C_ucb=0.5, crash_pen=-10.0, uni_dev=0.05, max_nodes=None,
-                  trees=False):
+                  trees=False, track=None, track_reward="progress", lookahead=1.5, track_window=0, goal_span=0):
         """scripts/mcts.py's search for K trees at once (``rl_mcts_*``, one tree per root state): ``n_iterations``
         iterations each, every tree adding one node per iteration.  ``followgap_or_policy``: a ``PyFollowGap``
         (source "fg"), a ``Policy`` ("nn") or None ("random"); ``source`` overrides the choice.  root_states float64
         (K, 11), root_actions scalar or (K,), seeds uint64 (K,).  Returns (best root action float64 (K,), its visits
         int32 (K,), nodes per tree int32 (K,)) and with ``trees=True`` also the K node-array dicts of
-        ``MCTSPlanner.read_tree``."""
+        ``MCTSPlanner.read_tree``.  ``track`` (a ``Track``): the roll-outs are rewarded along it, ``track_reward``,
+        ``lookahead``, ``track_window`` and ``goal_span`` as ``MCTSPlanner.attach_track`` takes them."""
         root_states = np.asarray(root_states, np.float64).reshape(-1, 11)
         K = root_states.shape[0]
         n_iterations = int(n_iterations)
@@ -190,6 +225,8 @@ class CarBatch(_lib.Handle):
                            crash_thresh, rollout_steps=rollout_steps, action_every=action_every, speed=speed, dt=dt,
                            scan_dist_to_base=scan_dist_to_base, C_ucb=C_ucb, crash_pen=crash_pen, uni_dev=uni_dev)
         try:
+            if track is not None:
+                pl.attach_track(track, track_reward, lookahead, track_window, goal_span)
             pl.reset(root_states, root_actions, seeds)
             pl.run(n_iterations)
             res = pl.best()
@@ -202,11 +239,13 @@ class CarBatch(_lib.Handle):
     def drive_mcts(self, method, followgap_or_policy, states, n_decisions, n_iterations, seeds, fov, num_rays, edge,
                    crash_thresh, recent_actions=0.0, source=None, steps_per_decision=1, steer_clip=None,
                    rollout_steps=200, action_every=10, speed=2.0, dt=0.01, scan_dist_to_base=0.275, C_ucb=0.5,
-                   crash_pen=-10.0, uni_dev=0.05, trace=False):
+                   crash_pen=-10.0, uni_dev=0.05, trace=False, track=None, track_reward="progress", lookahead=1.5,
+                   track_window=0, goal_span=0):
         """scripts/mcts_driver.py's closed loop for K cars at once (``rl_mcts_drive``): every car replans at each of
         ``n_decisions`` decisions (a fresh tree of ``n_iterations`` iterations from its state) and takes
         ``steps_per_decision`` steps with the most visited root action.  Source and handles as ``plan_mcts``; states
-        float64 (K, 11), recent_actions scalar or (K,), seeds integers (K,).  Returns ``MCTSPlanner.drive``'s tuple."""
+        float64 (K, 11), recent_actions scalar or (K,), seeds integers (K,).  Returns ``MCTSPlanner.drive``'s tuple.
+        ``track`` and its keywords as ``plan_mcts``: the roots are placed on it anew at every decision, on the device."""
         states = np.asarray(states)
         if states.dtype != np.float64 or states.ndim != 2 or states.shape[1] != 11:
             raise ValueError("states must be float64 (K, 11)")
@@ -214,6 +253,8 @@ class CarBatch(_lib.Handle):
                            edge, crash_thresh, rollout_steps=rollout_steps, action_every=action_every, speed=speed,
                            dt=dt, scan_dist_to_base=scan_dist_to_base, C_ucb=C_ucb, crash_pen=crash_pen, uni_dev=uni_dev)
         try:
+            if track is not None:
+                pl.attach_track(track, track_reward, lookahead, track_window, goal_span)
             return pl.drive(states, recent_actions, seeds, n_decisions, n_iterations,
                             steps_per_decision=steps_per_decision, steer_clip=steer_clip, trace=trace)
         finally:

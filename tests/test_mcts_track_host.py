@@ -1,0 +1,230 @@
+"""Track-guided MCTS without a GPU: the statement (tests/mcts_track_statement.py) against literal transcriptions of the
+reference's findBestPoint and waypoint reward, known answers of the progress terms, include/scanlib_track_plan.h pinned
+to ``_lib.EXT_SYMBOLS`` and its structure prototype by prototype, and every Python-side argument check."""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+import mcts_statement as MS
+import mcts_track_statement as S
+import scanlib_header as H
+import track_statement as TS
+from conftest import GOLD, ROOT
+from test_track_host import SQUARE, wp_u
+from pyracecarsimulator_amd import Track, _lib
+from pyracecarsimulator_amd import racecar as RC
+from pyracecarsimulator_amd.mcts import MCTS, REWARDS, MCTSPlanner, plan_track_args, points_args
+
+EXT_HEADER = os.path.join(ROOT, "include", "scanlib_track_plan.h")
+
+
+# ---------------------------------------------------------------- the reference's lines, literally
+def find_best_point(global_path, current_pose, lookahead_distance=1.5):
+    """scripts/mcts_driver.py:151-169, as written (``closest_point`` is unbound when no waypoint wins)."""
+    closest_distance = lookahead_distance*2
+
+    for track_point in global_path:
+        distance = math.sqrt(
+        (track_point[0] - current_pose[0])**2 +
+        (track_point[1] - current_pose[1])**2)
+
+        diff_distance = abs(lookahead_distance - distance)
+
+        if diff_distance < closest_distance :
+            closest_distance = diff_distance
+            closest_point = track_point
+
+    return closest_point
+
+
+def calculate_distance(point_to_follow, current_pose):
+    """scripts/mcts.py:247-250."""
+    return math.sqrt(
+    (point_to_follow[0] - current_pose[0])**2 +
+    (point_to_follow[1] - current_pose[1])**2)
+
+
+def test_root_point_is_find_best_point_on_the_waypoint_file():
+    """A grid of positions over and around wp_u.csv, the driver's lookahead and two others: the statement's root point
+    is findBestPoint's, and where the reference would raise (no waypoint within twice the lookahead of the lookahead)
+    the goal reads -1."""
+    xy = wp_u()
+    T = TS.build(xy, True)
+    path = [(float(x), float(y)) for x, y in xy]
+    none = 0
+    for la in (1.5, 0.4, 3.0):
+        for cx in np.linspace(-9.0, 14.0, 24):
+            for cy in np.linspace(-7.0, 16.0, 24):
+                rt = S.root(T, cx, cy, la, 0)
+                try:
+                    want = find_best_point(path, (float(cx), float(cy)), la)
+                except UnboundLocalError:
+                    none += 1
+                    assert rt["goal"] == -1 and not rt["has"] and rt["point"] == (0.0, 0.0), (la, cx, cy)
+                    continue
+                assert rt["goal"] >= 0 and rt["has"] and (float(rt["point"][0]), float(rt["point"][1])) == want, (la, cx, cy)
+                assert path[rt["goal"]] == want
+    assert 100 < none < 3 * 24 * 24 - 100, none
+    # an explicit point replaces the rule's, as the reference's constructor takes it
+    rt = S.root(T, 0.0, 0.0, 1.5, 0, point=(7.0, -2.0))
+    assert rt["point"] == (7.0, -2.0) and rt["has"] and rt["goal"] >= 0 and rt["segment"] == TS.nearest(T, 0.0, 0.0)
+    rt = S.root(None, 0.0, 0.0, point=(7.0, -2.0))
+    assert (rt["segment"], rt["goal"], rt["has"]) == (-1, -1, True) and math.isnan(rt["s"])
+
+
+def test_waypoint_term_is_the_reference_line():
+    """rewards[i] = new_state[3] / self.calculateDistance((new_state[0], new_state[1])) (mcts.py:234), on random
+    states, a state on the point (inf) and a standing car on the point (NaN)."""
+    rng = np.random.default_rng(3)
+    xy = rng.uniform(-20.0, 20.0, (500, 2))
+    vel = rng.uniform(-7.0, 7.0, 500)
+    point = (3.25, -1.7)
+    xy[7], xy[8], vel[8] = point, point, 0.0
+    got = S.waypoint_terms(vel, xy, point)
+    for i in range(500):
+        new_state = [float(xy[i, 0]), float(xy[i, 1]), 0.0, float(vel[i])]
+        try:
+            want = new_state[3] / calculate_distance(point, (new_state[0], new_state[1]))
+        except ZeroDivisionError:
+            want = math.nan if new_state[3] == 0 else math.copysign(math.inf, new_state[3])
+        assert (got[i] == want) or (math.isnan(got[i]) and math.isnan(want)), (i, got[i], want)
+    assert math.isinf(got[7]) and math.isnan(got[8])
+    # the value of a roll-out is the reference's: numpy.sum of the terms up to the crash over |action|
+    assert S.value(3, got[:20], -0.25) == float(np.sum(got[:3]) / 0.25) and S.value(-21, got[20:40], 0.5) == float(np.sum(got[20:40]) / 0.5)
+    assert S.value(-201, got[100:300], 0.1) == MS.pairwise_sum(got[100:300]) / 0.1 == float(np.sum(got[100:300]) / 0.1)
+
+
+def test_progress_terms_on_the_square():
+    """Known answers: a lap of the unit square in quarter steps from just short of the start line; a window that
+    leaves the true segment out; an open line does not wrap."""
+    T = TS.build(SQUARE, True)
+    xy = [(0.25, -0.1), (0.75, -0.1), (1.1, 0.5), (0.5, 1.1), (-0.1, 0.75), (0.1, -0.1)]
+    terms, s, seg, s0 = S.progress_terms(T, 3, 0, (-0.1, 0.25), xy)
+    assert s0 == 3.75 and seg.tolist() == [0, 0, 1, 2, 3, 0] and s.tolist() == [0.25, 0.75, 1.5, 2.5, 3.25, 0.1]
+    assert terms.tolist() == [0.5, 0.5, 0.75, 1.0, 0.75, 0.1 - 3.25 + 4.0]
+    # window 1 around segment 0 on a 12-point ring leaves the far side out: a position there projects onto a candidate
+    ring = [(math.cos(a), math.sin(a)) for a in np.arange(12) * math.pi / 6]
+    R = TS.build(ring, True)
+    far = (-1.0, 0.05)
+    assert TS.nearest(R, *far) == 5 and TS.nearest(R, far[0], far[1], 0, 1, False) in (11, 0, 1)
+    t_all = S.progress_terms(R, 0, 0, (1.0, 0.05), [far])
+    t_win = S.progress_terms(R, 0, 1, (1.0, 0.05), [far])
+    assert t_all[2][0] == 5 and t_win[2][0] in (11, 0, 1) and t_all[0][0] != t_win[0][0]
+    # terms(): velocity mode and a waypoint tree without a point give the velocities back
+    vel = np.array([1.0, 2.0])
+    for mode, rt in ((S.VELOCITY, S.root(T, 0.5, 0.5)), (S.WAYPOINT, S.root(T, 0.5, 0.5, lookahead=1e-3))):
+        assert S.terms(T, mode, 0, rt, (0.5, 0.5), xy[:2], vel).tolist() == [1.0, 2.0]
+    line = TS.build([(0.0, 0.0), (10.0, 0.0)], False)
+    assert S.progress_terms(line, 0, 3, (9.5, 1.0), [(0.5, 1.0)])[0].tolist() == [-9.0]
+
+
+# ---------------------------------------------------------------- the header against the tables
+@pytest.fixture
+def ext(monkeypatch):
+    """tests/scanlib_header.py reading the extension header: its handle types come from scanlib.h."""
+    opaque = H.handles()
+    structs = dict(H.STRUCTS, rl_plan_track_params=_lib.PlanTrackParams)
+    monkeypatch.setattr(H, "HEADER", EXT_HEADER)
+    monkeypatch.setattr(H, "STRUCTS", structs)
+    monkeypatch.setattr(H, "handles", lambda s=None: opaque)
+    return H
+
+
+def test_extension_header_is_pinned_to_ext_symbols(ext):
+    protos = ext.prototypes()
+    assert set(protos) == set(_lib.EXT_SYMBOLS) and len(protos) == 4
+    for name, (res, args, names) in protos.items():
+        bound_res, bound_args = _lib.EXT_SYMBOLS[name]
+        assert bound_res is res is C.c_int, name
+        assert len(bound_args) == len(args), (name, names)
+        for i, (got, want) in enumerate(zip(bound_args, args)):
+            assert got is want, "%s argument %d (%s): the table has %s, the header %s" % (name, i, names[i], got, want)
+    declared = ext.structs()
+    assert set(declared) == {"rl_plan_track_params"} and ext.enums() == {}
+    fields = [(n, t) for n, t in _lib.PlanTrackParams._fields_]
+    assert [n for n, _ in fields] == [n for n, _ in declared["rl_plan_track_params"]] == \
+        ["reward_mode", "window", "goal_span", "lookahead"]
+    for (n, got), (_, want) in zip(fields, declared["rl_plan_track_params"]):
+        assert got is want, n
+    # the header carries its contract and builds on scanlib.h
+    raw = open(EXT_HEADER).read()
+    assert '#include "scanlib.h"' in raw and "reward_mode 2 (progress)" in raw and "Errors (RL_ERR_INVALID" in raw
+    assert set(re.findall(r"\b(rl_[a-z_0-9]+)\s*\(", ext.text())) == set(_lib.EXT_SYMBOLS)
+
+
+def test_tables_are_disjoint_and_the_library_exports_the_extension():
+    assert not set(_lib.SYMBOLS) & set(_lib.EXT_SYMBOLS)
+    L = _lib.lib()
+    for name, (res, args) in _lib.EXT_SYMBOLS.items():
+        fn = getattr(L, name)
+        assert fn.restype is res and list(fn.argtypes) == list(args), name
+        assert _lib.declared(name) == (res, args) and _lib.converters(name)[2], name      # (rl_status: call checks it)
+        assert len(_lib.converters(name)[1]) == len(args)
+    assert _lib.declared("rl_mcts_run") is _lib.SYMBOLS["rl_mcts_run"]
+    with pytest.raises(KeyError):
+        _lib.declared("rl_no_such_symbol")
+    assert REWARDS == {"velocity": 0, "waypoint": 1, "progress": 2}
+    assert not [n for n in vars(_lib) if n.startswith("RL_") and ("TRACK" in n or "PLAN" in n)]
+
+
+# ---------------------------------------------------------------- the wrappers' refusals
+@pytest.fixture
+def no_calls(monkeypatch):
+    def refuse(name, *a):
+        raise AssertionError("the library was entered at %s" % name)
+    monkeypatch.setattr(_lib, "call", refuse)
+
+
+def test_plan_track_args(no_calls):
+    p = plan_track_args()
+    assert (p.reward_mode, p.window, p.goal_span, p.lookahead) == (2, 0, 0, 1.5)
+    p = plan_track_args("waypoint", 2.5, 64, 10)
+    assert (p.reward_mode, p.window, p.goal_span, p.lookahead) == (1, 64, 10, 2.5)
+    assert plan_track_args("progress", lookahead=math.nan).reward_mode == 2       # (the lookahead is the waypoint rule's)
+    assert plan_track_args("waypoint", lookahead=0.0, points=True).lookahead == 0.0
+    for kw in (dict(reward="speed"), dict(reward=1), dict(window=-1), dict(window=65537), dict(window=1.5), dict(window=True),
+               dict(goal_span=-1), dict(goal_span=65537), dict(goal_span=0.5), dict(reward="waypoint", lookahead=0.0),
+               dict(reward="waypoint", lookahead=-1.0), dict(reward="waypoint", lookahead=math.nan),
+               dict(reward="waypoint", lookahead=math.inf)):
+        with pytest.raises(ValueError):
+            plan_track_args(**kw)
+    assert points_args((1.0, 2.0), 3).tolist() == [[1.0, 2.0]] * 3 and points_args(np.zeros((3, 2)), 3).flags.c_contiguous
+    for bad, n in ((np.zeros((2, 2)), 3), (np.zeros(3), 3), (np.zeros((3, 3)), 3)):
+        with pytest.raises(ValueError):
+            points_args(bad, n)
+
+
+def test_wrappers_refuse_before_the_library(no_calls):
+    pl = MCTSPlanner.__new__(MCTSPlanner)
+    pl.n_trees, pl._points, pl._track = 3, False, None
+    with pytest.raises(ValueError):
+        pl.attach_track(None)
+    with pytest.raises(ValueError):
+        pl.attach_track(object(), reward="laps")
+    with pytest.raises(ValueError):
+        pl.attach_track(object(), reward="waypoint", lookahead=0.0)
+    with pytest.raises(ValueError):
+        pl.set_points(np.zeros((2, 2)))
+    pl._points = True
+    with pytest.raises(ValueError):
+        pl.drive(np.zeros((3, 11)), 0.0, [1, 2, 3], 1, 2)
+    cars = RC.CarBatch.__new__(RC.CarBatch)
+    st, act = np.zeros((2, 11)), np.zeros((2, 1, 2))
+    for kw in (dict(reward="progress"), dict(reward="waypoint"), dict(reward="laps")):
+        with pytest.raises(ValueError):
+            cars.rollout_track(None, st, act, n_steps=5, **kw)
+
+    class Stub:
+        n_segments = 4
+    for kw in (dict(n_steps=513), dict(n_steps=0), dict(anchors=[0, 4]), dict(anchors=[0, -1]), dict(anchors=[0]),
+               dict(anchors=[0.5, 1.0]), dict(reward="waypoint", points=np.zeros((3, 2))), dict(window=-1),
+               dict(reward="waypoint", lookahead=0.0)):
+        with pytest.raises(ValueError):
+            cars.rollout_track(Stub(), st, np.zeros((2, 52, 2)) if kw.get("n_steps") == 513 else act,
+                               **dict(dict(n_steps=5), **kw))
+    with pytest.raises(ValueError):
+        MCTS.__new__(MCTS).__init__(None, None, 0.0, 10, with_global=True)
