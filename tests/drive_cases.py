@@ -1,5 +1,6 @@
 """Cases and checks of the closed-loop tests that more than one module runs: the teacher-forced check of a traced
-drive_followgap result, the environment's cases and its tick composed from the public calls, and the race clusters."""
+drive_followgap result, the environment's cases and its tick composed from the public calls, the race clusters and
+the teacher-forced replay of a race."""
 import math
 
 import numpy as np
@@ -7,7 +8,7 @@ import numpy as np
 import race_statement as RS
 import support
 from oracle import reference
-from support import D_BASE, FOV, FOLLOWGAP_ARGS, THRESH, same_bits, within_one_ulp
+from support import D_BASE, FOV, FOLLOWGAP_ARGS, MAX_STEER, THRESH, same_bits, within_one_ulp
 from pyracecarsimulator_amd import maps
 from pyracecarsimulator_amd import racecar as RC
 
@@ -139,3 +140,48 @@ def race_oracle_fan(oracle_mod, g, cells, group, poses, num_rays, literal, step_
             r, h, s = om.rm_fan(poses[p:p + 1], FOV, num_rays, step_coeff=step_coeff)
         r_all.append(r); h_all.append(h); s_all.append(s)
     return np.concatenate(r_all), np.concatenate(h_all), np.concatenate(s_all)
+
+
+def race_teacher_forced_replay(oracle_mod, g, m, literal, cars, fg, states, speeds, T, num_rays, edge, length, width):
+    """``cars.race_followgap`` on ``m`` (RM: ``literal``) traced over T ticks, and every link of every tick of it: the
+    step (rollout of one step), the outline statement (length x width) of the other cars at their states after that
+    tick's step (wrecks at their crash-tick state), the oracle scan of the stamped grid, the crash test and
+    FollowGap.  states (R, P, 11), speeds (R, P).  Returns (first crash ticks (N,), rays the other cars changed)."""
+    coeff = 0.999 if literal else 1.0
+    n_races, group = states.shape[:2]
+    first, final, vel, steers, sp, st = cars.race_followgap(m, fg, states, T, speeds, FOV, num_rays, edge, THRESH,
+                                                            trace=True)
+    N = n_races * group
+    first, final, vel, steers, sp, st = (first.reshape(N), final.reshape(N, 11), vel.reshape(N, T),
+                                         steers.reshape(N, T), sp.reshape(N, T, 3), st.reshape(N, T, 11))
+    flat_states, flat_speeds = states.reshape(N, 11), speeds.reshape(N)
+    last = np.where(first >= 0, first, T - 1)
+    plain = oracle_mod.OracleMap(g.occ, g.resolution, g.origin, RACE_MRX)
+    n_seen = 0
+    for t in range(T):
+        # every car's state after tick t's step: a wreck keeps its crash-tick row
+        now = st[np.arange(N), np.minimum(t, last)]
+        cells = RS.outline_cells(now[:, :3], length, width, g.resolution, g.origin, g.rows, g.cols, oracle_mod.sincosf)
+        for n in range(N):
+            if t > last[n]:
+                assert np.isnan(st[n, t]).all() and np.isnan(steers[n, t])
+                continue
+            prev = flat_states[n] if t == 0 else st[n, t - 1]
+            steer_in = 0.0 if t == 0 else float(steers[n, t - 1])
+            _, one, _ = cars.rollout(prev[None], np.array([[[flat_speeds[n], steer_in]]]), n_steps=1, action_every=1)
+            assert same_bits(one[0], st[n, t]), (n, t)
+            occ = RS.stamped(g.occ, RS.others(cells, group, n))
+            om = oracle_mod.OracleMap(occ, g.resolution, g.origin, RACE_MRX)
+            pose = sp[n, t:t + 1]
+            r = (om.rm_fan_libm if literal else om.rm_fan)(pose, FOV, num_rays, step_coeff=coeff)[0]
+            alone = (plain.rm_fan_libm if literal else plain.rm_fan)(pose, FOV, num_rays, step_coeff=coeff)[0]
+            n_seen += int((r != alone).sum())
+            crashed = oracle_mod.is_crashed(r, num_rays, 1, edge, THRESH) >= 0
+            assert crashed == (first[n] == t), (n, t)
+            if crashed:
+                assert np.isnan(steers[n, t])
+                continue
+            a = oracle_mod.followgap_eval(r, 15.0, MAX_STEER, 0.004)
+            assert np.float32(a).tobytes() == steers[n, t].tobytes(), (n, t)
+    assert same_bits(final, st[np.arange(N), last])
+    return first, n_seen

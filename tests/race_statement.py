@@ -57,6 +57,32 @@ def outline_cells(cars, length, width, resolution, origin, rows, cols, sincosf):
     return out
 
 
+def point_cells(cars, length, width, resolution, origin, rows, cols, sincosf):
+    """int64 (n, points): the flat cell of every outline point, -1 where the point is off the grid or not finite."""
+    gx, gy = grid_points(cars, length, width, resolution, origin, sincosf)
+    with np.errstate(invalid="ignore"):
+        inside = np.isfinite(gx) & np.isfinite(gy) & (gx >= 0) & (gx < cols) & (gy >= 0) & (gy < rows)
+    col = np.floor(np.where(inside, gx, 0.0)).astype(np.int64)
+    row = np.floor(np.where(inside, gy, 0.0)).astype(np.int64)
+    return np.where(inside, row * cols + col, -1)
+
+
+def kept_points(cell):
+    """bool, the shape of ``cell`` (point_cells): the points rl_car_outline_cells emits.  A point is kept when it has
+    a cell and that cell differs from the cell of the point immediately before it in the full point list; a point
+    without a cell is no cell to repeat, point 0 has no predecessor, and the last point is not compared with the first."""
+    before = np.concatenate([np.full(cell.shape[:-1] + (1,), -1, cell.dtype), cell[..., :-1]], -1)
+    return (cell >= 0) & (cell != before)
+
+
+def outline_sequence(cars, length, width, resolution, origin, rows, cols, sincosf):
+    """Per car the cells rl_car_outline_cells emits, in its order (include/scanlib.h: "points whose cell repeats the
+    point before dropped"): a list of int64 arrays, point_cells at kept_points."""
+    cell = point_cells(cars, length, width, resolution, origin, rows, cols, sincosf)
+    keep = kept_points(cell)
+    return [cell[i][keep[i]] for i in range(cell.shape[0])]
+
+
 def stamped(occ, cells):
     """occ with the flat cells set (a copy)."""
     o = np.array(occ, dtype=np.uint8, copy=True)

@@ -9,8 +9,8 @@ import pytest
 
 import race_statement as RS
 import support
-from drive_cases import RACE_MRX as MRX, race_clusters, race_maze, race_oracle_fan
-from support import D_BASE, FOV, MAX_STEER, THRESH, same_bits
+from drive_cases import RACE_MRX as MRX, race_clusters, race_maze, race_oracle_fan, race_teacher_forced_replay
+from support import D_BASE, FOV, THRESH, same_bits
 from pyracecarsimulator_amd import RacecarSimulator, _lib, maps, range_libc
 from pyracecarsimulator_amd import racecar as RC
 
@@ -22,7 +22,8 @@ RL_ERR_INVALID, RL_ERR_UNSUPPORTED = -1, -4           # include/scanlib.h rl_sta
 
 
 def test_outline_cells_equal_the_statement(oracle_mod):
-    """About 10 000 random cars on colombia and on a yawed maze: the device's cells equal the statement's, as sets."""
+    """About 10 000 random cars on colombia and on a yawed maze: the device's counts and cells equal the statement's
+    sequence (RS.outline_sequence) element for element."""
     cars_h = RC.CarBatch()
     rng = np.random.default_rng(1)
     col = maps.load_colombia()
@@ -35,12 +36,12 @@ def test_outline_cells_equal_the_statement(oracle_mod):
         cars = np.stack([lo[0] + rng.uniform(-span, span, n), lo[1] + rng.uniform(-span, span, n),
                          rng.uniform(-7.0, 7.0, n)], -1)
         cells, counts = cars_h.outline_cells(omap, cars)
-        want = RS.outline_cells(cars, L, W, g.resolution, g.origin, g.rows, g.cols, oracle_mod.sincosf)
+        want = RS.outline_sequence(cars, L, W, g.resolution, g.origin, g.rows, g.cols, oracle_mod.sincosf)
         n_some = 0
         for i in range(n):
-            got = cells[i, :counts[i]]
+            assert counts[i] == len(want[i]), (g.name, i)
             assert (cells[i, counts[i]:] == -1).all()
-            assert set(got.tolist()) == set(want[i].tolist()), (g.name, i)
+            assert np.array_equal(cells[i, :counts[i]], want[i]), (g.name, i)
             n_some += counts[i] > 0
         assert n_some > n // 10, g.name
 
@@ -140,43 +141,10 @@ def test_race_teacher_forced_replay(oracle_mod, kind, group):
     g = race_maze()
     dt = oracle_mod.edt(g.occ)
     m = (range_libc.PyRayMarching if kind == "RM" else range_libc.PyRayMarchingGPU)(range_libc.PyOMap(g), MRX)
-    literal = kind == "RM"
-    coeff = 0.999 if literal else 1.0
-    fg = support.followgap()
     n_races, T = 4, 50
     states, speeds = _race_starts(g, dt, n_races, group, 50 + group)
-    edge = support.edge(B)
-    cars = RC.CarBatch()
-    first, final, vel, steers, sp, st = cars.race_followgap(m, fg, states, T, speeds, FOV, B, edge, THRESH, trace=True)
-    N = n_races * group
-    first, final, vel, steers, sp, st = (first.reshape(N), final.reshape(N, 11), vel.reshape(N, T),
-                                         steers.reshape(N, T), sp.reshape(N, T, 3), st.reshape(N, T, 11))
-    flat_states, flat_speeds = states.reshape(N, 11), speeds.reshape(N)
-    last = np.where(first >= 0, first, T - 1)
-    for t in range(T):
-        # every car's state after tick t's step: a wreck keeps its crash-tick row
-        now = st[np.arange(N), np.minimum(t, last)]
-        cells = RS.outline_cells(now[:, :3], L, W, g.resolution, g.origin, g.rows, g.cols, oracle_mod.sincosf)
-        for n in range(N):
-            if t > last[n]:
-                assert np.isnan(st[n, t]).all() and np.isnan(steers[n, t])
-                continue
-            prev = flat_states[n] if t == 0 else st[n, t - 1]
-            steer_in = 0.0 if t == 0 else float(steers[n, t - 1])
-            _, one, _ = cars.rollout(prev[None], np.array([[[flat_speeds[n], steer_in]]]), n_steps=1, action_every=1)
-            assert same_bits(one[0], st[n, t]), (n, t)
-            occ = RS.stamped(g.occ, RS.others(cells, group, n))
-            om = oracle_mod.OracleMap(occ, g.resolution, g.origin, MRX)
-            pose = sp[n, t:t + 1]
-            r = (om.rm_fan_libm if literal else om.rm_fan)(pose, FOV, B, step_coeff=coeff)[0]
-            crashed = oracle_mod.is_crashed(r, B, 1, edge, THRESH) >= 0
-            assert crashed == (first[n] == t), (n, t)
-            if crashed:
-                assert np.isnan(steers[n, t])
-                continue
-            a = oracle_mod.followgap_eval(r, 15.0, MAX_STEER, 0.004)
-            assert np.float32(a).tobytes() == steers[n, t].tobytes(), (n, t)
-    assert same_bits(final, st[np.arange(N), last])
+    race_teacher_forced_replay(oracle_mod, g, m, kind == "RM", RC.CarBatch(), support.followgap(), states, speeds, T, B,
+                               support.edge(B), L, W)
 
 
 def _room_race(m, fg, states, speeds, T):
