@@ -190,6 +190,8 @@ static const OptionRow OPTIONS[] = {
     {"direct_max_rays", OWN(direct_max_rays), [](int v) { return std::max(v, 0); }},
     {"overlap_min_rays", OWN(overlap_min_rays), [](int v) { return std::max(v, 0); }},
     {"pf_block", OWN(pf_block), [](int v) { return clamp_int(v, 0, PF_WG); }},
+    // (the origin-corrected GiantLUT query; stored and ignored by the other kinds, as lut_debug is)
+    {"lut_refine", OWN(lut_refine), as_bool},
     // (a power of two in [128, CDDT_LDS_SORT]: the bitonic network pads to one)
     {"cddt_lds_sort", OWN(cddt.lds_sort), [](int v) {
          int p = 128;
@@ -867,18 +869,32 @@ static const lut_fn lut_lds_table[3][2] = {{lut_fan_lds_kernel<1, 12>, lut_fan_l
                                            {lut_fan_lds_kernel<2, 12>, lut_fan_lds_kernel<2, 17>},
                                            {lut_fan_lds_kernel<3, 12>, lut_fan_lds_kernel<3, 17>}};
 static const lut_fn lut_fan_table[2] = {lut_fan_kernel<12>, lut_fan_kernel<17>};
+// ... and their origin-corrected twins (handle option lut_refine): the plan stays the default's, the launch takes the twin
+static const lut_fn lut_lds_refine_table[3][2] = {{lut_fan_lds_refine_kernel<1, 12>, lut_fan_lds_refine_kernel<1, 17>},
+                                                  {lut_fan_lds_refine_kernel<2, 12>, lut_fan_lds_refine_kernel<2, 17>},
+                                                  {lut_fan_lds_refine_kernel<3, 12>, lut_fan_lds_refine_kernel<3, 17>}};
+static const lut_fn lut_fan_refine_table[2] = {lut_fan_refine_kernel<12>, lut_fan_refine_kernel<17>};
 
 static int launch_lut(const FanLaunch &L)
 {
     const rl_launch_plan &pl = L.pl;
     const int ch = pl.ch == 12 ? 0 : (pl.ch == 17 ? 1 : -1);
     lut_fn kernel = nullptr;
-    if (ch >= 0 && pl.kernel == RL_K_LUT_FAN) kernel = lut_fan_table[ch];
-    if (ch >= 0 && pl.kernel == RL_K_LUT_LDS && pl.nl >= 1 && pl.nl <= 3) kernel = lut_lds_table[pl.nl - 1][ch];
+    const bool refine = L.h->lut_refine != 0;
+    if (ch >= 0 && pl.kernel == RL_K_LUT_FAN) kernel = (refine ? lut_fan_refine_table : lut_fan_table)[ch];
+    if (ch >= 0 && pl.kernel == RL_K_LUT_LDS && pl.nl >= 1 && pl.nl <= 3)
+        kernel = (refine ? lut_lds_refine_table : lut_lds_table)[pl.nl - 1][ch];
     if (!kernel) return fail(RL_ERR_INVALID, "internal: plan names an uninstantiated kernel (%s)", pl.name);
     int rc;
     if ((rc = ensure_lut(L.h, L.stream))) return rc;
     if (L.timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
+    if (refine && pl.kernel == RL_K_LUT_LDS) {
+        // the planned waves in workgroups of LUT_REFINE_WG lanes, each with the beam table in front of its waves' rows
+        const unsigned per = LUT_REFINE_WG / L.block.x;
+        const size_t lds = L.lds * per + (size_t)lut_dir_dwords(L.f.num_rays) * sizeof(uint32_t);
+        kernel<<<dim3((L.grid.x + per - 1) / per), dim3(LUT_REFINE_WG), lds, L.stream>>>(L.m->mp, L.f, L.h->lut.lp, L.d_poses, L.d_out);
+        return RL_OK;
+    }
     kernel<<<L.grid, L.block, L.lds, L.stream>>>(L.m->mp, L.f, L.h->lut.lp, L.d_poses, L.d_out);
     return RL_OK;
 }
@@ -1235,8 +1251,8 @@ static int launch_rays(rl_method *h, const float *d_ins, long n, float *d_out, i
     int rc;
     if (h->kind == RL_GIANT_LUT) {
         if ((rc = ensure_lut(h, stream))) return rc;
-        hipLaunchKernelGGL(lut_rays_kernel, dim3(grid), dim3(256), 0, stream, m->mp, f, h->lut.lp, d_ins,
-                           n, d_out);
+        hipLaunchKernelGGL(h->lut_refine ? lut_rays_refine_kernel : lut_rays_kernel, dim3(grid), dim3(256), 0, stream, m->mp, f,
+                           h->lut.lp, d_ins, n, d_out);
     } else if (h->kind == RL_CDDT) {
         if ((rc = ensure_cddt(h, stream))) return rc;
         hipLaunchKernelGGL(cddt_rays_kernel, dim3(grid), dim3(256), 0, stream, m->mp, f, h->cddt.cdp,
@@ -1562,7 +1578,7 @@ static int check_pf_shape(const rl_method *h, const char *fn, int n_particles, i
 static int pf_kind_of(const rl_method *h, int *kind)
 {
     if (h->kind == RL_CDDT || h->kind == RL_GIANT_LUT) {
-        *kind = h->kind == RL_CDDT ? PF_CDDT : PF_LUT;
+        *kind = h->kind == RL_CDDT ? PF_CDDT : (h->lut_refine ? PF_LUT_REFINE : PF_LUT);
         return RL_OK;
     }
     if (h->kind != RL_RM && h->kind != RL_RM_GPU)
@@ -1592,10 +1608,10 @@ static int launch_pf_angles(rl_method *h, const LaunchArgs &a, int kind, const f
 {
     const rl_map *m = h->map;
     const bool aux = d_hits || d_steps;
-    if (aux && (kind == PF_CDDT || kind == PF_LUT))
+    if (aux && pf_table_kind(kind))
         return fail(RL_ERR_UNSUPPORTED, "hit cells / step counts exist only for the ray-marching methods");
     int rc;
-    if (kind == PF_LUT && (rc = ensure_lut(h, stream))) return rc;
+    if ((kind == PF_LUT || kind == PF_LUT_REFINE) && (rc = ensure_lut(h, stream))) return rc;
     if (kind == PF_CDDT && (rc = ensure_cddt(h, stream))) return rc;
     const FanParams f = make_fan(h, n_particles, 0.0f, n_angles, a.ray_offset);
     const LiteralParams lt = make_literal(m);
@@ -1610,6 +1626,9 @@ static int launch_pf_angles(rl_method *h, const LaunchArgs &a, int kind, const f
         break;
     case PF_CDDT:
         PF_ANGLES(PF_CDDT, false);
+        break;
+    case PF_LUT_REFINE:
+        PF_ANGLES(PF_LUT_REFINE, false);
         break;
     default:
         PF_ANGLES(PF_LUT, false);
@@ -1638,7 +1657,7 @@ static int launch_pf_weights(rl_method *h, const LaunchArgs &a, int kind, const 
                              const float *d_obs, int n_angles, double *d_weights, hipStream_t stream)
 {
     int rc;
-    if (kind == PF_CDDT || kind == PF_LUT) {
+    if (pf_table_kind(kind)) {
         LaunchCtx *cx = nullptr;
         if ((rc = acquire_ctx(h, stream, &cx))) return rc;
         if ((rc = cx->pf_r.ensure((size_t)n_particles * n_angles * sizeof(float)))) return rc;

@@ -611,6 +611,7 @@ struct rl_method {
     DevPtr<float> pf_ang, pf_obs;
     DevPtr<double> pf_w;
     int pf_block = 0;            // particles per tile of the weight kernels (0: sized from the shape, make_pf)
+    int lut_refine = 0;          // GiantLUT: the origin-corrected query (lut_kernels.h) in every query path; other kinds ignore it
     LaunchCtx ctx[N_LAUNCH_CTX];
     uint64_t use_clock = 0;
     // small host calls (scan(): one pose, scanMany(): a roll-out): poses and ranges go through ONE

@@ -18,6 +18,8 @@ BOUNDS = [
     ("scan::rm_fan_stream_kernel<false, false, 1024, true, true, 2, false,", {"scratch": 0}),
     ("scan::rm_fan_stream_kernel<false, false, 1024, false, true, 2, false,", {"scratch": 0}),
     ("scan::lut_fan_lds_kernel<", {"vgpr": 56, "sgpr": 96, "occupancy": 8, "scratch": 0}),
+    # its origin-corrected twin (option lut_refine): the beam table in LDS and the per-pose offsets fit the same eight waves
+    ("scan::lut_fan_lds_refine_kernel<", {"vgpr": 64, "sgpr": 96, "occupancy": 8, "scratch": 0}),
     ("scan::cddt_theta_search2_kernel", {"vgpr": 64, "sgpr": 80, "occupancy": 8, "scratch": 0}),
     ("scan::cddt_theta_fan_kernel", {"vgpr": 32, "sgpr": 96, "occupancy": 8, "scratch": 0}),
     ("scan::cddt_fan_bins_kernel", {"vgpr": 64, "sgpr": 80, "occupancy": 8, "scratch": 0}),

@@ -24,7 +24,8 @@ constexpr int PF_MAX_ANGLES = 2048;        // beams per particle: tables + one p
 constexpr int PF_MAX_WIDTH = 2048;         // sensor-model table side
 constexpr int PF_TILE_RAYS = 2048;         // rays a workgroup marches between two barriers (8 per lane)
 
-enum { PF_RM = 0, PF_RM_LITERAL = 1, PF_CDDT = 2, PF_LUT = 3 };
+enum { PF_RM = 0, PF_RM_LITERAL = 1, PF_CDDT = 2, PF_LUT = 3, PF_LUT_REFINE = 4 };      // (4: handle option lut_refine)
+static inline bool pf_table_kind(int kind) { return kind == PF_CDDT || kind == PF_LUT || kind == PF_LUT_REFINE; }
 
 struct PfParams {
     int n_particles, n_angles;
@@ -80,12 +81,26 @@ __device__ __forceinline__ RayResult pf_cast(const MapParams &m, const FanParams
     } else if (KIND == PF_CDDT) {
         rr.range_px = cddt_query(m, cp, f.max_range, px, py, pth + a);
         return rr;
-    } else {
+    } else if (KIND == PF_LUT) {
         const float td_f = (float)lp.theta_disc, inv_td = 1.0f / (float)lp.theta_disc;
         rr.range_px = f.max_range * m.res;
         if (px >= 0.0f && px < m.fcols && py >= 0.0f && py < m.frows)
             rr.range_px = (float)lp.lut[((size_t)(int)py * m.cols + (int)px) * lp.theta_disc +
                                         lut_bin_fast(pth + a, lp, td_f, inv_td)] * lp.dequant * m.res;
+        return rr;
+    } else {
+        // the origin-corrected query (lut_kernels.h): the refined fan's arithmetic with angles[j] for fan_alpha(f, j)
+        const float td_f = (float)lp.theta_disc, inv_td = 1.0f / (float)lp.theta_disc;
+        rr.range_px = f.max_range * m.res;
+        if (px >= 0.0f && px < m.fcols && py >= 0.0f && py < m.frows) {
+            LutOrigin o;
+            float sa, ca;
+            const int cell = lut_origin_cell(m, px, py, m.dt[lut_nearest_cell(m, px, py)], o.fx, o.fy);
+            det_sincosf(pth, o.st, o.ct);
+            det_sincosf(a, sa, ca);
+            rr.range_px = lut_refined_px(lp.lut[(size_t)cell * lp.theta_disc + lut_bin_fast(pth + a, lp, td_f, inv_td)],
+                                         lp.dequant, f.max_range, o, sa, ca) * m.res;
+        }
         return rr;
     }
 }

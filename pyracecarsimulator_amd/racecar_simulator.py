@@ -288,5 +288,5 @@ class RacecarSimulator:
         max_range_px = int(self.scan_max_range / resolution)        # :196
         self.scan_simulator.setMap(ros_map, max_range_px, resolution, origin)
 
-    def setRaytracingMethod(self, method="RMGPU"):
-        self.scan_simulator.setRaytracingMethod(method)
+    def setRaytracingMethod(self, method="RMGPU", **kw):
+        self.scan_simulator.setRaytracingMethod(method, **kw)      # (theta_disc=, lut_refine= for "GLT")

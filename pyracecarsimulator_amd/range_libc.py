@@ -526,11 +526,17 @@ class PyCDDTCast(_RangeMethod):
 
 class PyGiantLUTCast(_RangeMethod):
     """range_libc.PyGiantLUTCast(omap, mrx, theta_disc): uint16 table [row][col][theta_bin] built
-    on the device at first use (rows*cols*theta_disc*2 bytes of HBM)."""
+    on the device at first use (rows*cols*theta_disc*2 bytes of HBM).
+
+    ``refine=True`` turns on the origin-corrected query (option ``lut_refine``, include/scanlib.h): every query reads the
+    row of the pose's nearest cell corner and takes the pose's offset from it, projected on the beam, off the entry —
+    the same table and table bytes, ranges within one cell of exact ray marching for ~97 % of the rays instead of ~78 %."""
     KIND = _lib.RL_GIANT_LUT
 
-    def __init__(self, omap, max_range_px, theta_disc):
+    def __init__(self, omap, max_range_px, theta_disc, refine=False):
         super().__init__(omap, max_range_px, theta_disc)
+        if refine:
+            self.set_option("lut_refine", 1)
 
     def table(self, row0=0, row1=None):
         """(row1-row0, cols, theta_disc) uint16 slab of the device table (test hook)."""

@@ -60,7 +60,10 @@ class ScanSimulator2D:
         self.res = resolution
         self.hasMap = True
 
-    def setRaytracingMethod(self, method="RM"):
+    def setRaytracingMethod(self, method="RM", theta_disc=None, lut_refine=False):
+        """"RM" / "RMGPU" as in the reference; "GLT": range_libc's GiantLUTCast with ``theta_disc`` bins (default: one
+        bin per beam spacing, 2 pi num_rays / fov rounded to an even number) and, with ``lut_refine``, its
+        origin-corrected query."""
         if not self.hasMap:
             print("for set RaytracingMethod use setMap first")
             return
@@ -68,6 +71,10 @@ class ScanSimulator2D:
             self.scan_method = range_libc.PyRayMarching(self.omap, self.mrx)
         elif method == "RMGPU":
             self.scan_method = range_libc.PyRayMarchingGPU(self.omap, self.mrx)
+        elif method == "GLT":
+            if theta_disc is None:
+                theta_disc = 2 * int(round(math.pi * self.num_rays / self.fov))
+            self.scan_method = range_libc.PyGiantLUTCast(self.omap, self.mrx, theta_disc, refine=lut_refine)
         else:
             print("Only ray marching is supported")
             sys.exit()
