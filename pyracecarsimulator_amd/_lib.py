@@ -5,7 +5,8 @@ There is no Python/NumPy fallback — if the shared object is missing or no HIP
 device is usable, the calls raise.
 
 ``SYMBOLS`` restates every prototype of the header (tests/test_py_calls_host.py pins it to the header, argument by
-argument, with the structures and enums below); ``EXT_SYMBOLS`` does the same for include/scanlib_track_plan.h.
+argument, with the structures and enums below); ``EXT_SYMBOLS`` does the same for include/scanlib_track_plan.h and
+``SEAT_SYMBOLS`` for include/scanlib_seats.h.
 ``call(name, *args)`` is how the package's wrappers enter the library: every argument is converted by the type the
 tables declare for it, and a symbol that returns ``rl_status`` is checked (``ScanLibError``) and gives None.  What a
 declared type takes:
@@ -105,7 +106,14 @@ class PlanTrackParams(C.Structure):
     _fields_ = [("reward_mode", C.c_int), ("window", C.c_int), ("goal_span", C.c_int), ("lookahead", C.c_double)]
 
 
+class SeatParams(C.Structure):
+    """rl_seat_params (include/scanlib_seats.h)."""
+    _fields_ = [("driver", C.c_int * 8), ("speed", C.c_float * 8)]
+
+
 RL_MCTS_FG, RL_MCTS_NN, RL_MCTS_RANDOM = 0, 1, 2
+#: enum rl_seat_driver (include/scanlib_seats.h)
+SEAT_DRIVERS = {"caller": 0, "followgap": 1, "policy": 2}
 
 KERNEL_IDS = {0: "none", 1: "rm_chunk", 2: "rm_stream", 3: "occ_lds", 4: "bl_stream", 5: "bl_lds", 6: "lut_lds",
               7: "lut_fan", 8: "cddt_bins", 9: "cddt_rays", 10: "cddt_theta", 11: "rm_literal", 12: "rm_stream_literal"}
@@ -267,10 +275,25 @@ EXT_SYMBOLS = {
 }
 
 
+#: every symbol include/scanlib_seats.h declares, in the shape of ``SYMBOLS`` (tests/test_seats_host.py pins it to that
+#: header); looked up after ``EXT_SYMBOLS``
+SEAT_SYMBOLS = {
+    "rl_car_race_seats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_double, f64p,
+                                    f64p, f32p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_float, C.c_int,
+                                    f64p, C.c_double, C.POINTER(C.c_int), f64p, f64p, f32p, f32p, f64p]),
+    "rl_env_attach_seats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SeatParams)]),
+    "rl_env_read_seats": (C.c_int, [C.c_void_p, f32p]),
+    "rl_env_read_seats_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
 def declared(name):
-    """(restype, argtypes) of ``name`` from ``SYMBOLS``, then ``EXT_SYMBOLS``."""
-    ent = SYMBOLS.get(name)
-    return EXT_SYMBOLS[name] if ent is None else ent
+    """(restype, argtypes) of ``name`` from ``SYMBOLS``, then ``EXT_SYMBOLS``, then ``SEAT_SYMBOLS``."""
+    for table in (SYMBOLS, EXT_SYMBOLS):
+        ent = table.get(name)
+        if ent is not None:
+            return ent
+    return SEAT_SYMBOLS[name]
 
 
 #: the symbols whose ``int`` is a value; every other ``int`` function returns rl_status (``call`` checks it)
@@ -306,7 +329,7 @@ def build(force: bool = False) -> str:
     """Compile libscan_amd.so for gfx950 with hipcc (in-tree; cross-compiles without a GPU)."""
     srcs = [os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc"))
             if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("scanlib.h", "scanlib_track_plan.h")]
+    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("scanlib.h", "scanlib_track_plan.h", "scanlib_seats.h")]
     stale = (not os.path.exists(_SO)) or any(os.path.getmtime(s) > os.path.getmtime(_SO)
                                              for s in srcs)
     if force or stale:
@@ -350,7 +373,7 @@ def lib():
                 "g.build()'` (or make -C pyracecarsimulator_amd/csrc). There is no CPU fallback.")
         _share_torch_hip_runtime()
         L = C.CDLL(_SO)
-        for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(SEAT_SYMBOLS.items()):
             try:
                 fn = getattr(L, name)
             except AttributeError:

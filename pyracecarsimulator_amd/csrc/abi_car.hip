@@ -1,11 +1,13 @@
 // abi_car.hip — what sits in front of and behind the scan path in libscan_amd.so (C ABI: include/scanlib.h; SURVEY.md
 // section 8f): the MCTS roll-out generator, FollowGap, the policy network, the race scan; the closed-loop session (loop_args
 // and Loop: handle checks, locks, launch arguments, scan-then-consume) with its users drive_loop, rl_env_* and rl_mcts_*;
-// track-guided planning (include/scanlib_track_plan.h: the planner's track, rl_car_rollout_track);
+// track-guided planning (include/scanlib_track_plan.h: the planner's track, rl_car_rollout_track); per-seat drivers
+// (include/scanlib_seats.h: rl_car_race_seats, rl_env_attach_seats);
 // 16-bit ranges for the xGMI exchange, diagnostics probes, the car-outline table and Car::isCrashed on the host.
 #include "abi_internal.h"
 #pragma GCC visibility push(default)
 #include "../../include/scanlib_track_plan.h"
+#include "../../include/scanlib_seats.h"
 #pragma GCC visibility pop
 #include <array>
 #include <utility>
@@ -33,6 +35,7 @@ struct rl_car {
     DevPtr<double> speeds, tr_states;                          // rl_car_drive_followgap, rl_car_drive_policy
     DevPtr<float> steer0, tr_steers, tr_poses;
     DevPtr<float> mlp;                                         // rl_car_drive_policy: the network's steers of a tick
+    DevPtr<int> seat_rows;                                     // rl_car_race_seats: the cars in policy seats
     DevPtr<double> o_cars;                                     // rl_car_outline_cells
     DevPtr<int32_t> o_cells;
     DevPtr<int> o_counts;
@@ -547,6 +550,17 @@ static int policy_launch(rl_policy *p, const float *d_scans, int n_scans, int si
     return RL_OK;
 }
 
+// the row-indexed form: the network for the n_rows scans d_rows names, answers to d_steers[row]
+static int policy_rows_launch(const PolicyParams &P, const float *d_scans, const int *d_rows, int n_rows, int size,
+                              float *d_steers, hipStream_t st)
+{
+    if (n_rows == 0) return RL_OK;
+    hipLaunchKernelGGL(policy_mlp_rows_kernel, dim3((n_rows + PM_CARS - 1) / PM_CARS), dim3(64), 0, st, P, d_scans, d_rows,
+                       n_rows, size, d_steers);
+    HIPCHK(hipGetLastError());
+    return RL_OK;
+}
+
 extern "C" int rl_policy_eval(rl_policy *p, const float *scans, int n_scans, int size, float *steers)
 {
     if (!p || (n_scans > 0 && (!scans || !steers))) return fail(RL_ERR_INVALID, "rl_policy_eval: null pointer");
@@ -600,7 +614,8 @@ static int loop_args(const char *name, const rl_car *c, const rl_method *h, cons
 }
 
 // one scan of a closed loop: n poses (a race: n / group races over the cars' f64 states, 11 doubles a car) into `ranges`,
-// and into `mlp` the policy's answers when the loop's source is one
+// and into `mlp` the policy's answers when the loop's source is one; with seats, `net` answers the n_rows scans `rows`
+// names and no others
 struct LoopScan {
     const float *poses;
     int n;
@@ -610,23 +625,27 @@ struct LoopScan {
     int group;                      // 0: every pose scans alone with the method's planner
     const double *cars;
     const OutlineParams *outline;
+    const PolicyParams *net = nullptr;
+    const int *rows = nullptr;
+    int n_rows = 0;
 };
 
 // One launching call of a closed loop.  Locks in ONE order: the owner's mutex (rl_env::mu, rl_mcts::mu; none for the
-// roll-outs), the car's, the method's, the steering source's (if any), then the map's tables_mu shared.  The method's
+// roll-outs), the car's, the method's, the steering sources' (FollowGap's, then the policy's: rl_car_race_seats holds
+// both), then the map's tables_mu shared.  The method's
 // settings are read under its mutex and never written: `base` is the noise offset the loop walks from, and every launch
 // is told its own offset and plain stores (the consumer kernels read the ranges right after the scan).  `ready` of an
 // owner is read and written inside only.
 struct Loop {
     rl_method *const h;
     rl_policy *const p;
-    std::unique_lock<std::mutex> lo, lc, lh, ls;
+    std::unique_lock<std::mutex> lo, lc, lh, ls, ln;
     std::shared_lock<std::shared_mutex> ml;
     const uint64_t base;
     static std::unique_lock<std::mutex> held(std::mutex *m) { return m ? std::unique_lock(*m) : std::unique_lock<std::mutex>(); }
     Loop(std::mutex *owner, rl_car *c, rl_method *h_, rl_followgap *g, rl_policy *p_)
-        : h(h_), p(p_), lo(held(owner)), lc(c->mu), lh(h_->mu), ls(held(g ? &g->mu : p_ ? &p_->mu : nullptr)),
-          ml(h_->map->tables_mu), base(h_->ray_offset)
+        : h(h_), p(p_), lo(held(owner)), lc(c->mu), lh(h_->mu), ls(held(g ? &g->mu : nullptr)),
+          ln(held(p_ ? &p_->mu : nullptr)), ml(h_->map->tables_mu), base(h_->ray_offset)
     {
     }
     LaunchArgs at(uint64_t off) const { return {off, true, h->timing}; }
@@ -641,7 +660,8 @@ struct Loop {
         int rc = s.group > 0 ? launch_race(h, a, s.poses, s.cars, 11, s.n / s.group, s.group, *s.outline, s.fov, s.num_rays,
                                            s.ranges, nullptr, nullptr, st)
                              : launch_fan(h, FanCall{a, s.poses, s.n, s.fov, s.num_rays, s.ranges, nullptr, nullptr, nullptr, st});
-        if (rc == RL_OK && p) rc = policy_launch(p, s.ranges, s.n, s.num_rays, s.mlp, st);
+        if (rc == RL_OK && s.net) rc = policy_rows_launch(*s.net, s.ranges, s.rows, s.n_rows, s.num_rays, s.mlp, st);
+        else if (rc == RL_OK && p) rc = policy_launch(p, s.ranges, s.n, s.num_rays, s.mlp, st);
         if (rc) return rc;
         table[(s.num_rays + 63) / 64 - 1]<<<dim3((s.n + per_wg - 1) / per_wg), dim3(64 * per_wg), 0, st>>>(args...);
         if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "%s launch failed", kernel);
@@ -655,6 +675,8 @@ static const std::array<drive_tick_fn, FG_ROWS> fg_tick_table =
     rows_table<drive_tick_fn>([](auto rows) { return drive_tick_kernel<rows, FollowGapSteer>; });
 static const std::array<drive_tick_fn, FG_ROWS> policy_tick_table =
     rows_table<drive_tick_fn>([](auto rows) { return drive_tick_kernel<rows, PolicySteer>; });
+static const std::array<drive_tick_fn, FG_ROWS> seat_tick_table =
+    rows_table<drive_tick_fn>([](auto rows) { return drive_tick_kernel<rows, SeatSteer>; });
 
 // what the three roll-out entry points share of their arguments (include/scanlib.h names them)
 struct DriveCall {
@@ -673,9 +695,10 @@ struct DriveCall {
 };
 
 // n cars for n_ticks ticks, steered by FollowGap (g) or the policy network (p, steer_clip), each scanning alone with h's
-// planner; race: n races of `group` cars, which see each other in every scan (race_fan_kernel)
+// planner; race: n races of `group` cars, which see each other in every scan (race_fan_kernel); seats (a race only):
+// the checked driver code of each seat, g and p the handles of the drivers that occur
 static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g, rl_policy *p, double steer_clip, int n,
-                      bool race, int group, const DriveCall &a)
+                      bool race, int group, const DriveCall &a, const int *seats = nullptr)
 {
     if (!c || !h || !(g || p) || (n > 0 && (!a.states_in || !a.speeds || !a.edge || !a.first_crashed)))
         return fail(RL_ERR_INVALID, "%s: null pointer", name);
@@ -684,7 +707,9 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
     if (race && n < 0) return fail(RL_ERR_INVALID, "n_races must be >= 0 (got %d)", n);
     if (race && (rc = race_args(h, n, group, num_rays))) return rc;
     const int R = race ? n * group : n;          // (a race: < 2^31 / num_rays, race_args)
-    if ((rc = loop_args(name, c, h, g, p, R, num_rays))) return rc;
+    if ((rc = loop_args(name, c, h, g, g ? nullptr : p, R, num_rays)) ||
+        (g && p && (rc = loop_args(name, c, h, nullptr, p, R, num_rays))))
+        return rc;
     if (R < 0 || n_ticks <= 0) return fail(RL_ERR_INVALID, "n_rollouts >= 0 and n_ticks > 0 required (got %d, %d)", R, n_ticks);
     if ((p && (rc = policy_args(p, R, num_rays))) || (rc = check_fan_args(h, R, a.fov, num_rays)) || R == 0) return rc;
     OutlineParams op{};
@@ -692,8 +717,19 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
     const Loop lp(nullptr, c, h, g, p);
     HIPCHK(hipSetDevice(c->device));
     const size_t rows = (size_t)R * n_ticks, n_rays = (size_t)R * num_rays;
+    // seats: the cars the network drives, race by race (declared before hc: the list outlives the call's copies)
+    uint32_t policy_seats = 0;
+    std::vector<int> seat_rows;
+    if (seats) {
+        for (int k = 0; k < group; ++k)
+            if (seats[k] == RL_SEAT_POLICY) policy_seats |= 1u << k;
+        for (int r = 0; r < n && policy_seats; ++r)
+            for (int k = 0; k < group; ++k)
+                if ((policy_seats >> k) & 1u) seat_rows.push_back(r * group + k);
+    }
     HostCall hc(c->stream);
     hipStream_t st = hc.st;
+    if (!seat_rows.empty() && (rc = hc.up(c->seat_rows, (const int *)seat_rows.data(), seat_rows.size()))) return rc;
     // trace rows a car never reaches (after its crash tick; the steer of the crash tick) read NaN: all-ones bytes
     if ((rc = hc.up(c->states, a.states_in, (size_t)R * 11)) || (rc = hc.up(c->speeds, a.speeds, R)) ||
         (rc = a.steer0 ? hc.up(c->steer0, a.steer0, R) : hc.zero(c->steer0, R)) || (rc = hc.up(c->edge, a.edge, num_rays)) ||
@@ -713,6 +749,8 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
     dp.n_cars = R;
     dp.n_ticks = n_ticks;
     dp.steer_clip = steer_clip;
+    dp.group = seats ? group : 0;
+    dp.policy_seats = policy_seats;
     DriveBufs b{c->states, c->speeds, c->steer0, c->edge, c->first, c->poses, c->ranges,
                 a.velocities ? (double *)c->vel : nullptr, a.steers ? (float *)c->tr_steers : nullptr,
                 a.scan_poses ? (float *)c->tr_poses : nullptr, a.states_trace ? (double *)c->tr_states : nullptr,
@@ -721,10 +759,15 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
     HIPCHK(hipGetLastError());
     // the noise offset walks the global ray id t R num_rays + r num_rays of every tick
     // (a race reads every car's outline from its f64 state after this tick's step: all cars step, then all scan)
-    const LoopScan scan{b.pose, R, a.fov, num_rays, c->ranges, c->mlp, race ? group : 0, b.state, &op};
+    LoopScan scan{b.pose, R, a.fov, num_rays, c->ranges, c->mlp, race ? group : 0, b.state, &op};
+    if (seats && p) {
+        scan.net = &p->P;
+        scan.rows = c->seat_rows;
+        scan.n_rows = (int)seat_rows.size();
+    }
+    const auto &table = seats ? seat_tick_table : g ? fg_tick_table : policy_tick_table;
     for (int t = 0; t < n_ticks && rc == RL_OK; ++t)
-        rc = lp.scan_then(scan, lp.base + (uint64_t)t * n_rays, g ? fg_tick_table : policy_tick_table, DRIVE_CARS,
-                          "drive_tick_kernel", st, dp, b, t);
+        rc = lp.scan_then(scan, lp.base + (uint64_t)t * n_rays, table, DRIVE_CARS, "drive_tick_kernel", st, dp, b, t);
     if (rc || (rc = hc.down(a.first_crashed, c->first, R)) || (rc = hc.down(a.states_out, c->states, (size_t)R * 11)) ||
         (rc = hc.down(a.velocities, c->vel, rows)) || (rc = hc.down(a.steers, c->tr_steers, rows)) ||
         (rc = hc.down(a.scan_poses, c->tr_poses, rows * 3)) || (rc = hc.down(a.states_trace, c->tr_states, rows * 11)))
@@ -771,6 +814,36 @@ extern "C" int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const 
     return drive_loop("rl_car_drive_policy", c, h, nullptr, p, steer_clip, R, false, 0, a);
 }
 
+extern "C" int rl_car_race_seats(rl_car *c, rl_method *h, rl_followgap *g_or_null, rl_policy *p_or_null,
+                                 const int *seat_driver, double steer_clip, const double *states_in, const double *speeds,
+                                 const float *steer0_or_null, int n_races, int group, int n_ticks, double dt,
+                                 double scan_dist_to_base, float fov, int num_rays, const double *edge, double crash_thresh,
+                                 int *first_crashed, double *states_out_or_null, double *velocities_or_null,
+                                 float *steers_or_null, float *scan_poses_or_null, double *states_trace_or_null)
+{
+    if (!c || !h || !seat_driver) return fail(RL_ERR_INVALID, "rl_car_race_seats: null pointer");
+    if (group < 1 || group > RACE_MAX_GROUP)
+        return fail(RL_ERR_INVALID, "group must lie in [1, %d] cars (got %d)", RACE_MAX_GROUP, group);
+    bool fg = false, net = false;
+    for (int k = 0; k < group; ++k) {
+        const int d = seat_driver[k];
+        if (d == RL_SEAT_CALLER)
+            return fail(RL_ERR_INVALID, "rl_car_race_seats: seat %d is the caller's: a roll-out has no caller to ask", k);
+        if (d != RL_SEAT_FOLLOWGAP && d != RL_SEAT_POLICY)
+            return fail(RL_ERR_INVALID, "rl_car_race_seats: seat %d: unknown driver code %d", k, d);
+        if (!(d == RL_SEAT_FOLLOWGAP ? (void *)g_or_null : (void *)p_or_null))
+            return fail(RL_ERR_INVALID, "rl_car_race_seats: seat %d is driven by %s, whose handle is null", k,
+                        d == RL_SEAT_FOLLOWGAP ? "FollowGap" : "the policy");
+        (d == RL_SEAT_FOLLOWGAP ? fg : net) = true;
+    }
+    const DriveCall a{states_in, speeds, steer0_or_null, n_ticks, dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh,
+                      first_crashed, states_out_or_null, velocities_or_null, steers_or_null, scan_poses_or_null,
+                      states_trace_or_null};
+    // (a handle no seat uses is not looked at)
+    return drive_loop("rl_car_race_seats", c, h, fg ? g_or_null : nullptr, net ? p_or_null : nullptr, steer_clip, n_races,
+                      true, group, a, seat_driver);
+}
+
 // ---------------------------------------------------------------- the driving environment (env_kernels.h)
 typedef void (*env_observe_fn)(EnvParams, EnvBufs, float *, float *, int *, float *);
 static const std::array<env_observe_fn, FG_ROWS> env_observe_table =
@@ -778,6 +851,9 @@ static const std::array<env_observe_fn, FG_ROWS> env_observe_table =
 typedef void (*race_env_observe_fn)(EnvParams, EnvBufs, RaceEnvBufs, float *, float *, int *, float *);
 static const std::array<race_env_observe_fn, FG_ROWS> race_env_observe_table =
     rows_table<race_env_observe_fn>([](auto rows) { return race_env_observe_kernel<rows>; });
+typedef void (*race_env_seat_observe_fn)(EnvParams, EnvBufs, RaceEnvBufs, SeatBufs, float *, float *, int *, float *);
+static const std::array<race_env_seat_observe_fn, FG_ROWS> race_env_seat_observe_table =
+    rows_table<race_env_seat_observe_fn>([](auto rows) { return race_env_seat_observe_kernel<rows>; });
 
 // a track (rl_track_create): the table of track_kernels.h in one device block, and the host's copy of cum
 struct rl_track {
@@ -808,6 +884,15 @@ struct rl_env {
     DevPtr<double> track_st;
     DevPtr<float> track_rows;
     DevPtr<int> track_ints;
+    // per-seat drivers (rl_env_attach_seats): the borrowed handles, the kernels' table (its pointers into the buffers
+    // below) and the cars in policy seats
+    bool seated = false;
+    rl_followgap *seat_g = nullptr;
+    rl_policy *seat_p = nullptr;
+    SeatBufs seats{};
+    DevPtr<float> seat_mlp, seat_answer;
+    DevPtr<int> seat_rows;
+    int n_seat_rows = 0;
     bool ready = false;            // reset done and no launch failed since (read and written under mu only)
     bool foreign = false;          // the last launches went to a caller's stream: a host form waits for the device first
     uint64_t k = 0;                // calls since the last reset (the reset is slot 0)
@@ -972,6 +1057,21 @@ static int env_launch(rl_env *e, const Loop &lp, bool reset, uint64_t k, const f
     const int N = e->prm.n_envs, B = e->prm.num_rays;
     const EnvBufs b = env_bufs(e);
     const uint64_t off = e->base + k * (uint64_t)N * (uint64_t)B;
+    if (e->group > 0 && e->seated) {     // ... with drivers in its seats: the SEATS instances, and the network between
+        const RaceEnvBufs rb = race_env_bufs(e);
+        hipLaunchKernelGGL(race_env_seat_step_kernel, dim3((N + 63) / 64), dim3(64), 0, st, e->ep, b, rb, e->seats, d_actions,
+                           d_start_index, reset ? 1 : 0);
+        if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "race_env_seat_step_kernel launch failed");
+        LoopScan scan{e->pose, N, e->prm.fov, B, e->ranges, e->seat_mlp, e->group, e->state, &e->outline};
+        if (e->n_seat_rows > 0) {
+            scan.net = &e->seat_p->P;
+            scan.rows = e->seat_rows;
+            scan.n_rows = e->n_seat_rows;
+        }
+        const int rc = lp.scan_then(scan, off, race_env_seat_observe_table, e->group, "race_env_seat_observe_kernel", st,
+                                    e->ep, b, rb, e->seats, d_obs, d_reward, d_done, d_aux);
+        return rc ? rc : track_launch(e, d_reward, st);
+    }
     if (e->group > 0) {          // a race env: whole races spawn and end, and the cars see each other in the scan
         const RaceEnvBufs rb = race_env_bufs(e);
         hipLaunchKernelGGL(race_env_step_kernel, dim3((N + 63) / 64), dim3(64), 0, st, e->ep, b, rb, d_actions,
@@ -1251,6 +1351,100 @@ extern "C" int rl_env_read_track_device(rl_env *e, float *d_rows_n8, int *d_ints
     const size_t N = e->prm.n_envs;
     if (d_rows_n8) HIPCHK(hipMemcpyAsync(d_rows_n8, e->track_rows, N * 8 * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (d_ints_n4) HIPCHK(hipMemcpyAsync(d_ints_n4, e->track_ints, N * 4 * sizeof(int), hipMemcpyDeviceToDevice, st));
+    return RL_OK;
+}
+
+// ---------------------------------------------------------------- per-seat drivers (include/scanlib_seats.h)
+extern "C" int rl_env_attach_seats(rl_env *e, rl_followgap *g_or_null, rl_policy *p_or_null, const rl_seat_params *sp_or_null)
+{
+    if (!e) return fail(RL_ERR_INVALID, "rl_env_attach_seats: null pointer");
+    std::scoped_lock lk(e->mu, e->c->mu);
+    if (e->group < 1) return fail(RL_ERR_INVALID, "rl_env_attach_seats: not a race environment (rl_env_create_race)");
+    const int N = e->prm.n_envs, P = e->group, B = e->prm.num_rays;
+    SeatBufs S{};
+    if (sp_or_null) {
+        for (int k = 0; k < P; ++k) {
+            const int d = sp_or_null->driver[k];
+            if (d == RL_SEAT_CALLER) continue;
+            if (d != RL_SEAT_FOLLOWGAP && d != RL_SEAT_POLICY)
+                return fail(RL_ERR_INVALID, "rl_env_attach_seats: seat %d: unknown driver code %d", k, d);
+            const bool net = d == RL_SEAT_POLICY;
+            if (!(net ? (void *)p_or_null : (void *)g_or_null))
+                return fail(RL_ERR_INVALID, "rl_env_attach_seats: seat %d is driven by %s, whose handle is null", k,
+                            net ? "the policy" : "FollowGap");
+            const int dev = net ? p_or_null->device : g_or_null->device;
+            if (dev != e->device)
+                return fail(RL_ERR_INVALID, "rl_env_attach_seats: %s (device %d) and env (device %d) must share one device",
+                            net ? "policy" : "FollowGap", dev, e->device);
+            if (!std::isfinite(sp_or_null->speed[k]))
+                return fail(RL_ERR_INVALID, "rl_env_attach_seats: the speed of seat %d must be finite", k);
+            S.scripted |= 1u << k;
+            if (net) S.policy |= 1u << k;
+            S.speed[k] = sp_or_null->speed[k];
+        }
+        int rc;
+        if (S.policy && (rc = policy_args(p_or_null, N, B))) return rc;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipDeviceSynchronize());     // (launches in flight may still read the tables replaced below)
+    e->foreign = false;
+    e->seated = false;
+    e->ready = false;                   // the answers of the new seats start at the next reset
+    e->n_seat_rows = 0;
+    if (!sp_or_null) return RL_OK;
+    int rc;
+    if ((rc = e->seat_answer.ensure(N))) return rc;
+    if (S.policy) {
+        std::vector<int> rows;
+        for (int r = 0; r < N / P; ++r)
+            for (int k = 0; k < P; ++k)
+                if ((S.policy >> k) & 1u) rows.push_back(r * P + k);
+        if ((rc = e->seat_mlp.ensure(N)) || (rc = e->seat_rows.ensure(rows.size()))) return rc;
+        HIPCHK(hipMemcpy(e->seat_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
+        e->n_seat_rows = (int)rows.size();
+    }
+    if (S.scripted & ~S.policy) S.fg = g_or_null->P;
+    S.fg.size = B;
+    S.mlp = e->seat_mlp;
+    S.answer = e->seat_answer;
+    e->seats = S;
+    e->seat_g = g_or_null;
+    e->seat_p = p_or_null;
+    e->seated = true;
+    return RL_OK;
+}
+
+static int env_seats_ready(rl_env *e, const char *name)
+{
+    if (!e->seated) return fail(RL_ERR_INVALID, "%s: no seats attached (rl_env_attach_seats)", name);
+    if (!e->ready) return fail(RL_ERR_INVALID, "%s: reset the environment first (rl_env_reset)", name);
+    return RL_OK;
+}
+
+extern "C" int rl_env_read_seats(rl_env *e, float *steer_n)
+{
+    if (!e) return fail(RL_ERR_INVALID, "rl_env_read_seats: null pointer");
+    std::scoped_lock lk(e->mu, e->c->mu);
+    int rc = env_seats_ready(e, "rl_env_read_seats");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    if ((rc = env_settle(e))) return rc;
+    HostCall hc(e->c->stream);
+    if ((rc = hc.down(steer_n, e->seat_answer, (size_t)e->prm.n_envs))) return rc;
+    return hc.finish();
+}
+
+extern "C" int rl_env_read_seats_device(rl_env *e, float *d_steer_n, void *hip_stream)
+{
+    if (!e) return fail(RL_ERR_INVALID, "rl_env_read_seats_device: null pointer");
+    std::scoped_lock lk(e->mu, e->c->mu);
+    const int rc = env_seats_ready(e, "rl_env_read_seats_device");
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (st != (hipStream_t)e->c->stream) e->foreign = true;
+    if (d_steer_n)
+        HIPCHK(hipMemcpyAsync(d_steer_n, e->seat_answer, (size_t)e->prm.n_envs * sizeof(float), hipMemcpyDeviceToDevice, st));
     return RL_OK;
 }
 

@@ -25,7 +25,7 @@ BOUNDS = [
     ("scan::cddt_fan_bins_kernel", {"vgpr": 64, "sgpr": 80, "occupancy": 8, "scratch": 0}),
     ("scan::bl_fan_stream_kernel<false, 1024>", {"vgpr": 56, "sgpr": 96, "occupancy": 8, "scratch": 0}),
     ("scan::rm_leftover_kernel<", {"vgpr": 48, "occupancy": 8, "scratch": 0}),
-    # closed-loop roll-outs, both steering sources: scan, crash compare, FollowGap or the network's answer and the f64
+    # closed-loop roll-outs, every steering source (FollowGap, the network, the seat table): scan, crash compare, FollowGap or the network's answer and the f64
     # car step in one wave per car, no spills
     ("scan::drive_tick_kernel<", {"scratch": 0}),
     ("scan::drive_start_kernel", {"scratch": 0}),
@@ -35,10 +35,14 @@ BOUNDS = [
     # the race environment: the same lane and wave with the race's rule around them
     ("scan::race_env_step_kernel", {"scratch": 0}),
     ("scan::race_env_observe_kernel<", {"scratch": 0}),
+    # ... with drivers in its seats: the scripted pair's select chain and FollowGap's passes behind the ballot spill nothing
+    ("scan::race_env_seat_step_kernel", {"scratch": 0}),
+    ("scan::race_env_seat_observe_kernel<", {"scratch": 0}),
     # track progress: the f64 search, the wave's (value, index) minimum and lane 0's trigonometry spill nothing
     ("scan::track_kernel<", {"scratch": 0}),
     # the policy network: the micro-tile accumulators stay in registers
     ("scan::policy_mlp_kernel", {"scratch": 0}),
+    ("scan::policy_mlp_rows_kernel", {"scratch": 0}),
     # the MCTS planner: the descent, the act wave, the backup's pairwise sum and the walks keep nothing in scratch
     ("scan::mcts_start_kernel", {"scratch": 0}),
     ("scan::mcts_select_kernel", {"scratch": 0}),

@@ -1,5 +1,5 @@
 // drive_kernels.h — closed-loop roll-outs (rl_car_drive_followgap, rl_car_race_followgap, rl_car_drive_policy;
-// include/scanlib.h): the reference's simulator tick (scripts/ros_interface.py:119-148: updatePose, runScan,
+// include/scanlib.h; rl_car_race_seats, include/scanlib_seats.h): the reference's simulator tick (scripts/ros_interface.py:119-148: updatePose, runScan,
 // checkCollision >= 0) driven by a steering source's answer to every scan — FollowGap (scripts/two_player/
 // simple_driver.py:31,48-53) or the policy network (scripts/policy_driver.py) — for many cars at once with nothing
 // crossing PCIe between ticks.  Per tick the host enqueues on one stream:
@@ -7,8 +7,9 @@
 //      race_fan_kernel (race_kernels.h); for the policy, then policy_mlp_kernel over every scan (policy_kernels.h);
 //   2. drive_tick_kernel<ROWS, Steer>: one wave per car — the scan into registers, Car::isCrashed's f64 compare
 //      (racecar.cpp:305-328) as a ballot, the source's answer (FollowGapSteer: followgap_bits_eval's four passes,
-//      consumer_kernels.h; PolicySteer: the network's output) —, then one lane per car: the car step of the NEXT
-//      tick with the new steering angle and that tick's lidar pose.
+//      consumer_kernels.h; PolicySteer: the network's output; SeatSteer: whichever of the two drives the car's seat
+//      of its race) —, then one lane per car: the car step of the NEXT tick with the new steering angle and that
+//      tick's lidar pose.
 // drive_start_kernel (one lane per car) is the prologue: tick 0's step with the initial steer.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,6 +26,8 @@ struct DriveParams {
     double dt, scan_dist_to_base, crash_thresh;
     int n_cars, n_ticks;
     double steer_clip;           // policy source: > 0 clamps the network's steer to +-steer_clip
+    int group;                   // seat source: cars per race (car r sits in seat r % group); 0 otherwise
+    uint32_t policy_seats;       // seat source: bit k set: the network drives seat k; clear: FollowGap
 };
 
 struct DriveBufs {
@@ -39,7 +42,8 @@ struct DriveBufs {
     float *steers;
     float *scan_poses;           // [R, T, 3]
     double *states_trace;        // [R, T, 11]
-    const float *mlp;            // policy source: [R] the network's answers to this tick's scans
+    const float *mlp;            // policy source: [R] the network's answers to this tick's scans (seat source: the rows
+                                 // of the cars in policy seats; the others are never read)
 };
 
 __device__ inline CarState drive_load_state(const double *s)
@@ -112,14 +116,14 @@ __global__ __launch_bounds__(64) void drive_start_kernel(DriveParams dp, DriveBu
 }
 
 // The steering sources of drive_tick_kernel.  answer(): car r's f32 answer to its scan of this tick (the steers trace),
-// in every lane of the car's wave; steer(): the f64 steer the car gets from it, in the lane of wave 0 that steps it.
+// in every lane of the car's wave; steer(): the f64 steer car r gets from it, in the lane of wave 0 that steps it.
 struct FollowGapSteer {
     template <int ROWS>
     __device__ static float answer(const DriveParams &dp, const DriveBufs &, int, const float (&raw)[ROWS], uint32_t *bits)
     {
         return followgap_bits_eval<ROWS>(raw, dp.fg, bits);
     }
-    __device__ static double steer(const DriveParams &, float a) { return (double)a; }
+    __device__ static double steer(const DriveParams &, int, float a) { return (double)a; }
 };
 
 // policy_mlp_kernel's output (every car's scan, frozen ones included).  steer_clip > 0: the car gets
@@ -131,10 +135,27 @@ struct PolicySteer {
     {
         return b.mlp[r];
     }
-    __device__ static double steer(const DriveParams &dp, float a)
+    __device__ static double steer(const DriveParams &dp, int, float a)
     {
         const double s = (double)a;
         return dp.steer_clip > 0.0 ? fmin(fmax(s, -dp.steer_clip), dp.steer_clip) : s;
+    }
+};
+
+// Per-seat drivers (rl_car_race_seats): car r of a race of dp.group cars sits in seat r % dp.group, and that seat's
+// driver, FollowGap or the network (dp.policy_seats), answers and steers exactly as its own source above does: the
+// clip never touches a FollowGap seat.  One wave is one car, so answer()'s branch is wave-uniform.
+struct SeatSteer {
+    __device__ static bool policy(const DriveParams &dp, int r) { return (dp.policy_seats >> (r % dp.group)) & 1u; }
+    template <int ROWS>
+    __device__ static float answer(const DriveParams &dp, const DriveBufs &b, int r, const float (&raw)[ROWS], uint32_t *bits)
+    {
+        if (policy(dp, r)) return PolicySteer::answer<ROWS>(dp, b, r, raw, bits);
+        return FollowGapSteer::answer<ROWS>(dp, b, r, raw, bits);
+    }
+    __device__ static double steer(const DriveParams &dp, int r, float a)
+    {
+        return policy(dp, r) ? PolicySteer::steer(dp, r, a) : FollowGapSteer::steer(dp, r, a);
     }
 };
 
@@ -170,8 +191,10 @@ __global__ __launch_bounds__(64 * DRIVE_CARS) void drive_tick_kernel(DriveParams
         step_next[w] = go;
     }
     __syncthreads();
-    if (threadIdx.x < DRIVE_CARS && step_next[threadIdx.x])
-        drive_step(dp, b, blockIdx.x * DRIVE_CARS + threadIdx.x, t + 1, Steer::steer(dp, answer_next[threadIdx.x]));
+    if (threadIdx.x < DRIVE_CARS && step_next[threadIdx.x]) {
+        const int rs = blockIdx.x * DRIVE_CARS + threadIdx.x;
+        drive_step(dp, b, rs, t + 1, Steer::steer(dp, rs, answer_next[threadIdx.x]));
+    }
 }
 
 }  // namespace scan

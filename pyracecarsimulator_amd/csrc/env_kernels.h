@@ -19,6 +19,11 @@
 //   env_emit                     what the caller sees: done, reward, the observation window, the aux row
 // The race kernels add only the race's rule: the pool row and the race's counters at a spawn, the race's tick, the
 // wreck, and when the race is over.
+// Seats (rl_env_attach_seats, include/scanlib_seats.h): a race env whose seats have drivers runs the SEATS instances of
+// the two race kernels.  Phase B's wave answers its car's scan with the seat's driver (FollowGap from the registers
+// the crash ballot filled; the network from policy_mlp_rows_kernel, enqueued between the scan and phase B) into
+// SeatBufs::answer, and the next call's phase A takes a scripted car's pair from there instead of `actions`.  An env
+// without seats launches the plain instances, which hold none of this.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -90,11 +95,9 @@ __device__ inline void env_stand(const EnvBufs &b, int e, int phase)
     b.moved[e] = 0.0;
 }
 
-// a running env e takes its pair of actions [N, 2] f32 (speed, steer): `substeps` car steps from cs, or ENV_BAD_ACTION
-__device__ inline void env_act(const EnvParams &p, const EnvBufs &b, int e, const float *actions, CarState &cs)
+// a running env e takes the pair (speed, steer), two f32 widened: `substeps` car steps from cs, or ENV_BAD_ACTION
+__device__ inline void env_act_pair(const EnvParams &p, const EnvBufs &b, int e, double speed, double steer, CarState &cs)
 {
-    const double speed = (double)actions[2 * e + 0];
-    double steer = (double)actions[2 * e + 1];
     if (!(isfinite(speed) && isfinite(steer))) {
         b.done[e] = ENV_BAD_ACTION;              // the state stays as it is: nothing non-finite reaches car_step
         env_stand(b, e, ENV_INVALID);
@@ -107,6 +110,12 @@ __device__ inline void env_act(const EnvParams &p, const EnvBufs &b, int e, cons
     b.tick[e] += 1;
     b.phase[e] = ENV_STEPPED;
     b.moved[e] = cs.travel_dist - before;
+}
+
+// ... its pair of actions [N, 2] f32 (speed, steer)
+__device__ inline void env_act(const EnvParams &p, const EnvBufs &b, int e, const float *actions, CarState &cs)
+{
+    env_act_pair(p, b, e, (double)actions[2 * e + 0], (double)actions[2 * e + 1], cs);
 }
 
 // phase A.  reset != 0: every env spawns with q = 0 (start_index: the caller's indices or null); otherwise one step
@@ -216,12 +225,25 @@ __device__ inline void race_env_spawn(const EnvParams &p, const EnvBufs &b, cons
     }
 }
 
+// the seats of a race env: who drives seat k = e % group, and the scripted cars' answers
+struct SeatBufs {
+    uint32_t scripted, policy;   // bit k: seat k has a driver (else the caller's); ... and it is the network
+    float speed[RACE_MAX_GROUP]; // the commanded speed of a scripted seat
+    FollowGapParams fg;          // fg.size = num_rays
+    const float *mlp;            // [N] the network's answers to this call's scans: the rows of the cars in policy seats
+    float *answer;               // [N] the seat driver's f32 answer to the car's latest scan; NaN: a caller's seat, or a
+                                 // car that was not running after that scan's phase B
+};
+
 // phase A of a race env, one lane per car.  Races straddle blocks, so no word is written by one lane and read by
 // another in here: R.over is read only, R.tick / R.episode / R.start_index are written by car 0's lane and read in
-// phase B, and every lane takes the race's episode from its own car's mirror.
-__global__ __launch_bounds__(64) void race_env_step_kernel(EnvParams p, EnvBufs b, RaceEnvBufs R,
-                                                           const float *__restrict__ actions,
-                                                           const int *__restrict__ start_index, int reset)
+// phase B, and every lane takes the race's episode from its own car's mirror.  SEATS: a car in a scripted seat that
+// reaches the action check takes (S.speed[k], S.answer[e]), the answer phase B of the call before left for it, and its
+// row of `actions` is not read.
+template <bool SEATS>
+__device__ __forceinline__ void race_env_step_body(const EnvParams &p, const EnvBufs &b, const RaceEnvBufs &R,
+                                                   const SeatBufs *S, const float *__restrict__ actions,
+                                                   const int *__restrict__ start_index, int reset)
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= p.n_envs) return;
@@ -239,21 +261,44 @@ __global__ __launch_bounds__(64) void race_env_step_kernel(EnvParams p, EnvBufs 
     } else {
         if (e == r * R.group) R.tick[r] += 1;
         cs = drive_load_state(b.state + (size_t)e * 11);
-        if (b.done[e] != ENV_RUNNING) env_stand(b, e, ENV_FROZEN);     // a wreck: scanned again, and the others see it
-        else env_act(p, b, e, actions, cs);
+        const int k = e - r * R.group;
+        if (b.done[e] != ENV_RUNNING) {
+            env_stand(b, e, ENV_FROZEN);         // a wreck: scanned again, and the others see it
+        } else if (SEATS && ((S->scripted >> k) & 1u)) {
+            float speed = 0.0f;                  // (a select chain: a lane-indexed kernel argument would go to scratch)
+#pragma unroll
+            for (int i = 0; i < RACE_MAX_GROUP; ++i) speed = i == k ? S->speed[i] : speed;
+            env_act_pair(p, b, e, (double)speed, (double)S->answer[e], cs);
+        } else {
+            env_act(p, b, e, actions, cs);
+        }
     }
     car_scan_pose(cs, p.scan_dist_to_base, b.pose + 3 * e);
 }
 
+__global__ __launch_bounds__(64) void race_env_step_kernel(EnvParams p, EnvBufs b, RaceEnvBufs R,
+                                                           const float *__restrict__ actions,
+                                                           const int *__restrict__ start_index, int reset)
+{
+    race_env_step_body<false>(p, b, R, nullptr, actions, start_index, reset);
+}
+
+__global__ __launch_bounds__(64) void race_env_seat_step_kernel(EnvParams p, EnvBufs b, RaceEnvBufs R, SeatBufs S,
+                                                                const float *__restrict__ actions,
+                                                                const int *__restrict__ start_index, int reset)
+{
+    race_env_step_body<true>(p, b, R, &S, actions, start_index, reset);
+}
+
 // phase B of a race env: one workgroup per race, one wave per car (blockDim = 64 P, always P live waves).  Each wave
 // reaches its car's verdict as env_observe_kernel does, with the race's tick, parks the code in LDS, and after the
-// barrier applies the race's rule before the emit.
-template <int ROWS>
-__global__ __launch_bounds__(64 * RACE_MAX_GROUP) void race_env_observe_kernel(EnvParams p, EnvBufs b, RaceEnvBufs R,
-                                                                               float *__restrict__ obs,
-                                                                               float *__restrict__ reward,
-                                                                               int *__restrict__ done_out,
-                                                                               float *__restrict__ aux)
+// barrier applies the race's rule before the emit.  SEATS: a scripted seat's wave (w is the seat: wave-uniform) also
+// answers the scan with its driver, and S.answer[e] keeps the answer where the car runs on after the race's rule.
+template <int ROWS, bool SEATS>
+__device__ __forceinline__ void race_env_observe_body(const EnvParams &p, const EnvBufs &b, const RaceEnvBufs &R,
+                                                      const SeatBufs *S, uint32_t *bits, float *__restrict__ obs,
+                                                      float *__restrict__ reward, int *__restrict__ done_out,
+                                                      float *__restrict__ aux)
 {
     __shared__ int codes[RACE_MAX_GROUP];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -263,6 +308,9 @@ __global__ __launch_bounds__(64 * RACE_MAX_GROUP) void race_env_observe_kernel(E
     const bool hit = drive_crashed<ROWS>(row, b.edge, p.num_rays, p.crash_thresh, lane, raw);
     int done = env_done(p, b, e, hit, R.tick[r]);
     const float rw = env_reward(p, b, e, done);                 // (before the race's rule: a survivor's reward stays)
+    float answer = __builtin_nanf("");
+    if (SEATS && ((S->scripted >> w) & 1u))
+        answer = ((S->policy >> w) & 1u) ? S->mlp[e] : followgap_bits_eval<ROWS>(raw, S->fg, bits);
     // a race spawns as a whole: a fresh car means a fresh race, whatever R.over still holds from the last episode
     const int over0 = b.phase[e] == ENV_FRESH ? RACE_RUNNING : R.over[r];
     if (lane == 0) codes[w] = done;
@@ -278,7 +326,29 @@ __global__ __launch_bounds__(64 * RACE_MAX_GROUP) void race_env_observe_kernel(E
         if (over == RACE_ATTRITION && done == ENV_RUNNING) done = ENV_TRUNCATED;    // it survived: its reward stays
         if (threadIdx.x == 0) R.over[r] = over;
     }
+    if (SEATS && lane == 0) S->answer[e] = done == ENV_RUNNING ? answer : __builtin_nanf("");
     env_emit(p, b, e, lane, row, done, rw, obs, reward, done_out, aux);
+}
+
+template <int ROWS>
+__global__ __launch_bounds__(64 * RACE_MAX_GROUP) void race_env_observe_kernel(EnvParams p, EnvBufs b, RaceEnvBufs R,
+                                                                               float *__restrict__ obs,
+                                                                               float *__restrict__ reward,
+                                                                               int *__restrict__ done_out,
+                                                                               float *__restrict__ aux)
+{
+    race_env_observe_body<ROWS, false>(p, b, R, nullptr, nullptr, obs, reward, done_out, aux);
+}
+
+template <int ROWS>
+__global__ __launch_bounds__(64 * RACE_MAX_GROUP) void race_env_seat_observe_kernel(EnvParams p, EnvBufs b, RaceEnvBufs R,
+                                                                                    SeatBufs S, float *__restrict__ obs,
+                                                                                    float *__restrict__ reward,
+                                                                                    int *__restrict__ done_out,
+                                                                                    float *__restrict__ aux)
+{
+    __shared__ uint32_t bits[RACE_MAX_GROUP][2 * ROWS + 4];     // FollowGap's bit rows, one set per wave
+    race_env_observe_body<ROWS, true>(p, b, R, &S, bits[threadIdx.x >> 6], obs, reward, done_out, aux);
 }
 
 }  // namespace scan

@@ -17,6 +17,8 @@
 // measured ~230 us per launch at any R; staging with a load-wait-store loop ~180 us: latency-bound both.)  Layer 1's inputs come in the same k-blocks straight from the range
 // buffer, the input transform fused in.  Zero padding (neurons to a multiple
 // of 4, cars to PM_CARS) never enters a kept output's chain.
+// policy_mlp_rows_kernel is the same body over a list of scan rows (per-seat drivers, include/scanlib_seats.h: the
+// network for the cars it drives); policy_mlp_kernel is the dense form, every row.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -46,9 +48,12 @@ __device__ inline float policy_input(float r, float clip, float scale)
     return (r <= clip) ? r / scale : 1.0f;      // NaN and +inf: 1.0 (scripts/policy.py's `x if x <= 15.0 else 15.0`)
 }
 
-// scans [n][size] (row stride `size`) -> out [n]
-__global__ __launch_bounds__(64) void policy_mlp_kernel(PolicyParams p, const float *__restrict__ scans, int n, int size,
-                                                        float *__restrict__ out)
+// The chain for the n cars of a launch.  ROWS_FORM false: car i is scan row i.  ROWS_FORM true: car i is scan row
+// rows[i] (any order, each row once) and its answer goes to out[rows[i]]: the network for the cars it drives and no
+// others.  A car's chain reads its own scan row and the weights only, so both forms give a row the same bits.
+template <bool ROWS_FORM>
+__device__ __forceinline__ void policy_mlp_body(const PolicyParams &p, const float *__restrict__ scans,
+                                                const int *__restrict__ rows, int n, int size, float *__restrict__ out)
 {
     __shared__ float xin[PM_KB * PM_CARS];
     __shared__ float act[PM_MAX_W * PM_CARS];
@@ -56,6 +61,12 @@ __global__ __launch_bounds__(64) void policy_mlp_kernel(PolicyParams p, const fl
     const int lane = threadIdx.x;
     const int car0 = blockIdx.x * PM_CARS;
     constexpr int CG = PM_CARS / PM_MC;
+    int srow[PM_CARS];                         // the scan row of each of the workgroup's cars (padding: the last car's)
+#pragma unroll
+    for (int c = 0; c < PM_CARS; ++c) {
+        const int i = min(car0 + c, n - 1);
+        srow[c] = ROWS_FORM ? rows[i] : i;
+    }
     for (int l = 0; l < p.n_layers; ++l) {
         const int K = p.dims[l], N = p.dims[l + 1], ng = (N + 3) >> 2, n_mt = CG * ng;
         const float4 *__restrict__ W4 = reinterpret_cast<const float4 *>(p.W[l]);
@@ -84,7 +95,7 @@ __global__ __launch_bounds__(64) void policy_mlp_kernel(PolicyParams p, const fl
             if (l == 0) {
                 const int kk = p.in_start + kb + min(lane, kn - 1);
 #pragma unroll
-                for (int c = 0; c < PM_CARS; ++c) xv[c] = scans[(size_t)min(car0 + c, n - 1) * size + kk];
+                for (int c = 0; c < PM_CARS; ++c) xv[c] = scans[(size_t)srow[c] * size + kk];
             }
 #pragma unroll
             for (int u = 0; u < PM_KB; ++u) wl[lane + 64 * u] = wv[u];    // (entries past ne: never read)
@@ -129,7 +140,7 @@ __global__ __launch_bounds__(64) void policy_mlp_kernel(PolicyParams p, const fl
                     float y = acc[m][i][j] + bb[j];
                     if (relu) y = y > 0.0f ? y : 0.0f;
                     if (last) {
-                        if (jg[m] == 0 && j == 0 && car0 + c < n) out[car0 + c] = y;
+                        if (jg[m] == 0 && j == 0 && car0 + c < n) out[ROWS_FORM ? srow[c] : car0 + c] = y;
                     } else {
                         act[(4 * jg[m] + j) * PM_CARS + c] = y;
                     }
@@ -138,6 +149,22 @@ __global__ __launch_bounds__(64) void policy_mlp_kernel(PolicyParams p, const fl
         }
         if (!last) __syncthreads();
     }
+}
+
+// scans [n][size] (row stride `size`) -> out [n]
+__global__ __launch_bounds__(64) void policy_mlp_kernel(PolicyParams p, const float *__restrict__ scans, int n, int size,
+                                                        float *__restrict__ out)
+{
+    policy_mlp_body<false>(p, scans, nullptr, n, size, out);
+}
+
+// the row-indexed form: rows [n] names the scan rows (of stride `size`) the network answers -> out [rows[i]]; the
+// other rows of out are left alone
+__global__ __launch_bounds__(64) void policy_mlp_rows_kernel(PolicyParams p, const float *__restrict__ scans,
+                                                             const int *__restrict__ rows, int n, int size,
+                                                             float *__restrict__ out)
+{
+    policy_mlp_body<true>(p, scans, rows, n, size, out);
 }
 
 }  // namespace scan

@@ -25,6 +25,10 @@ once fewer than ``min_running`` of its cars run or ``max_ticks`` is reached.
 Both take a ``track`` (``track.Track``): every reset and step then also places each car on the track, on the device,
 and ``track_state()`` reads the result; ``progress_reward=True`` pays the progress along the track instead of the
 distance travelled.
+
+``RaceEnv`` also takes ``seats``: a driver per seat of the race (``seats.py``, include/scanlib_seats.h).  A car in a seat
+with a ``PyFollowGap`` or a ``Policy`` is steered on the device by that driver's answer to its own full scan of the call
+before, at ``seat_speed``; only the seats left None read the caller's actions.
 """
 from __future__ import annotations
 
@@ -290,9 +294,16 @@ class RaceEnv(DriveEnv):
     is over once fewer than ``min_running`` of its cars run (``race_over`` 1; the cars still running read done = 2) or
     at ``max_ticks`` steps (``race_over`` 2); until then a finished car stays where it is and the others see it.  The
     other arguments are ``DriveEnv``'s.  ``reset`` takes one start index per race; ``reset``, ``step`` and ``read`` give
-    the per-car rows as (n_races, P, ...) views, car k of race r at [r, k]; ``step`` takes (n_races, P, 2) actions."""
+    the per-car rows as (n_races, P, ...) views, car k of race r at [r, k]; ``step`` takes (n_races, P, 2) actions.
 
-    def __init__(self, method, starts, n_races, num_rays, fov, edge, crash_thresh, *, min_running=1, **kw):
+    ``seats``: one driver per seat, ``[None, fg, pol, ...]`` — None is the caller's seat, a ``PyFollowGap`` or a
+    ``Policy`` (at most one object of each kind) drives car k of every race itself: at each step such a car takes
+    (``seat_speed``, its driver's answer to the car's own scan of the call before: all ``num_rays`` beams, whatever
+    ``obs_window`` shows the caller) in place of its row of ``actions``, which is not read.  ``seat_speed``: a scalar or
+    one value per seat.  ``seat_steers()`` reads the answers."""
+
+    def __init__(self, method, starts, n_races, num_rays, fov, edge, crash_thresh, *, min_running=1, seats=None,
+                 seat_speed=2.0, **kw):
         checks = {k: kw[k] for k in ("substeps", "obs_window", "obs_clip", "obs_scale", "max_ticks", "steer_clip",
                                      "crash_reward", "dt") if k in kw}
         st, _, _, P = race_env_args(n_races, num_rays, starts, edge, min_running, **checks)
@@ -300,6 +311,9 @@ class RaceEnv(DriveEnv):
         super().__init__(method, st.reshape(-1, 11), self._races * P, num_rays, fov, edge, crash_thresh, **kw)
         self.n_starts = st.shape[0]
         self._n_idx = self._races
+        self.seats = None
+        if seats is not None:
+            self.attach_seats(seats, seat_speed)
 
     def _create(self, car, method, p, ed, st):
         rp = _lib.RaceEnvParams()
@@ -330,6 +344,37 @@ class RaceEnv(DriveEnv):
         if tuple(actions.shape) == (self._races, self._group, 2):
             actions = actions.reshape(self._n, 2)
         return tuple(self._rows(x) for x in super().step(actions, aux))
+
+    # -- per-seat drivers ---------------------------------------------------------------
+    def attach_seats(self, seats, seat_speed=2.0):
+        """Give the seats their drivers (``seats`` and ``seat_speed`` as the constructor takes them; None: detach, every
+        seat is the caller's again).  The env needs a ``reset`` afterwards."""
+        from .seats import seat_env_args
+        if seats is None:
+            _lib.call("rl_env_attach_seats", self, None, None, None)
+            self.seats = None
+            return
+        sp, fg, pol = seat_env_args(seats, seat_speed, self._group, self.params.num_rays)
+        _lib.call("rl_env_attach_seats", self, fg, pol, sp)
+        self.seats = (tuple(seats), fg, pol)      # (borrowed by the library: kept alive here)
+
+    def seat_steers(self, on_device=False):
+        """Each car's seat driver's answer to its latest scan, float32 (n_races, P): the steer it takes at the next
+        step.  NaN for a car in the caller's seat and for one that is not running after that scan.  NumPy by default
+        (waits for the device); ``on_device=True``: the env's own torch tensor, filled on the current stream and
+        overwritten by the next call."""
+        if self.seats is None:
+            raise ValueError("no seats attached (attach_seats)")
+        if on_device:
+            import torch
+            if getattr(self, "_seat_torch", None) is None:
+                self._seat_torch = torch.empty(self._n, dtype=torch.float32, device=torch.device("cuda", self.device))
+            out = self._seat_torch
+            _lib.call("rl_env_read_seats_device", self, out.data_ptr(), self._stream())
+        else:
+            out = np.empty(self._n, np.float32)
+            _lib.call("rl_env_read_seats", self, out)
+        return self._rows(out)
 
     def track_state(self, on_device=False):
         """``DriveEnv.track_state`` as (n_races, P, ...); ``rank`` 0 leads its race."""

@@ -194,6 +194,33 @@ class CarBatch(_lib.Handle):
         # every array's leading R P becomes (R, P)
         return tuple(a.reshape((n_races, group) + a.shape[1:]) for a in res)
 
+    def race_seats(self, method, drivers, states, n_ticks, speed, fov, num_rays, edge, crash_thresh, steer_clip=None,
+                   steer0=None, dt=0.01, trace=False, scan_dist_to_base=0.275):
+        """``race_followgap`` with a driver per seat (``rl_car_race_seats``, include/scanlib_seats.h): ``drivers`` holds
+        one ``PyFollowGap`` or ``Policy`` per car of a race (at most one distinct object of each kind), and car k of
+        every race is steered by ``drivers[k]``'s answer to its scan — scripts/two_player/ with simple_driver.py in some
+        seats and policy_driver.py in others.  ``steer_clip`` as ``drive_policy`` takes it: it clamps the network's
+        seats only.  The steers returned are each driver's raw answers.  Arguments and results as ``race_followgap``;
+        with FollowGap in every seat it returns that call's bits."""
+        from .seats import seat_args
+        st = np.asarray(states)
+        if st.dtype != np.float64 or st.ndim != 3 or st.shape[2] != 11:
+            raise ValueError("states must be float64 (R, P, 11)")
+        n_races, group = st.shape[0], st.shape[1]
+        codes, fg, pol = seat_args(drivers, group, num_rays, caller_ok=False)
+        clip = 0.0 if steer_clip is None else float(steer_clip)
+        if steer_clip is not None and not clip > 0:
+            raise ValueError("steer_clip must be None or > 0")
+        spd = np.asarray(speed, dtype=np.float64)
+        spd = float(spd) if spd.ndim == 0 else spd.reshape(-1)
+        st0 = None if steer0 is None else np.asarray(steer0).reshape(-1)
+        R, n_ticks, states, speeds, st0, edge, first, out, vel, steers, poses, trace_st = self._drive_args(
+            st.reshape(-1, 11), n_ticks, spd, num_rays, edge, st0, trace)
+        _lib.call("rl_car_race_seats", self, method, fg, pol, codes, clip, states, speeds, st0, n_races, group, n_ticks,
+                  dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh, first, out, vel, steers, poses, trace_st)
+        res = (first, out, vel, steers) + ((poses, trace_st) if trace else ())
+        return tuple(a.reshape((n_races, group) + a.shape[1:]) for a in res)
+
     def drive_policy(self, method, policy, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
                      scan_dist_to_base=0.275, dt=0.01, steer0=None, steer_clip=None, trace=False):
         """Closed-loop policy roll-outs (``rl_car_drive_policy``): ``drive_followgap``'s loop with the steer of

@@ -178,6 +178,17 @@ class RacecarSimulator:
                                        self.num_rays, self.edge_distances, self.ttc_thresh,
                                        scan_dist_to_base=self.scan_dist_to_base)
 
+    def raceSeatsMany(self, states, n_ticks, drivers, speed=2.0, steer_clip=None):
+        """``raceFollowGapMany`` with a driver per seat: ``drivers`` holds, for each of the P cars of a race, a
+        ``policy.Policy``, a ``PyFollowGap`` or the string "fg" (this simulator's own FollowGap driver, as
+        ``raceFollowGapMany`` builds it) — scripts/two_player/ with the network in some seats and simple_driver.py in
+        the others.  ``steer_clip`` clamps the network's seats only (scripts/policy_driver.py uses 0.4189).  Returns
+        ``CarBatch.race_seats``'s tuple."""
+        drivers = [self._mcts_source("fg", None) if isinstance(d, str) and d == "fg" else d for d in drivers]
+        return self.car.race_seats(self.scan_simulator.scan_method, drivers, np.asarray(states, dtype=np.float64),
+                                   n_ticks, speed, self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
+                                   steer_clip=steer_clip, scan_dist_to_base=self.scan_dist_to_base)
+
     def drivePolicyMany(self, states, n_ticks, policy, speed=2.0, steer_clip=None):
         """``driveFollowGapMany`` with the steer of every tick from ``policy`` (a ``policy.Policy``, e.g.
         ``Policy('model/frozen_model.pb')``): scripts/policy_driver.py's driver with ``steer_clip=0.4189``, MCTS's
@@ -269,8 +280,11 @@ class RacecarSimulator:
         """A ``RaceEnv`` of ``n_races`` races on this simulator's range method (RM or RMGPU), car, fan, edge table,
         ttc_thresh and scan_dist_to_base, spawning from the line-ups ``starts`` float64 (M, P, 11): the tick of
         ``raceFollowGapMany`` with the (speed, steer) of every car supplied by the caller.  ``kw``: ``RaceEnv``'s keyword
-        arguments (min_running and ``DriveEnv``'s, the track keywords included)."""
+        arguments (min_running and ``DriveEnv``'s, the track keywords included; ``seats`` and ``seat_speed`` put a
+        driver into a seat, "fg" standing for this simulator's own FollowGap driver)."""
         from .env import RaceEnv
+        if kw.get("seats") is not None:
+            kw["seats"] = [self._mcts_source("fg", None) if isinstance(d, str) and d == "fg" else d for d in kw["seats"]]
         kw.setdefault("car", self.car)
         kw.setdefault("scan_dist_to_base", self.scan_dist_to_base)
         return RaceEnv(self.scan_simulator.scan_method, starts, n_races, self.num_rays, self.scan_fov,
