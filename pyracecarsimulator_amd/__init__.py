@@ -8,10 +8,11 @@ from . import maps, racecar, range_libc             # noqa: F401
 from .scan_simulator import ScanSimulator2D          # noqa: F401
 from .racecar_simulator import RacecarSimulator      # noqa: F401
 from .policy import Policy                           # noqa: F401
+from .population import PolicyPopulation             # noqa: F401
 from .mcts import MCTS                               # noqa: F401
 from .particle_filter import ParticleFilter          # noqa: F401
 from .env import DriveEnv, RaceEnv                   # noqa: F401
 from .track import Track                             # noqa: F401
 
-__all__ = ["maps", "racecar", "range_libc", "ScanSimulator2D", "RacecarSimulator", "Policy", "MCTS",
+__all__ = ["maps", "racecar", "range_libc", "ScanSimulator2D", "RacecarSimulator", "Policy", "PolicyPopulation", "MCTS",
            "ParticleFilter", "DriveEnv", "RaceEnv", "Track"]

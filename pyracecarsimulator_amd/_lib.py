@@ -6,7 +6,7 @@ device is usable, the calls raise.
 
 ``SYMBOLS`` restates every prototype of the header (tests/test_py_calls_host.py pins it to the header, argument by
 argument, with the structures and enums below); ``EXT_SYMBOLS`` does the same for include/scanlib_track_plan.h and
-``SEAT_SYMBOLS`` for include/scanlib_seats.h.
+``SEAT_SYMBOLS`` for include/scanlib_seats.h, ``POP_SYMBOLS`` for include/scanlib_population.h.
 ``call(name, *args)`` is how the package's wrappers enter the library: every argument is converted by the type the
 tables declare for it, and a symbol that returns ``rl_status`` is checked (``ScanLibError``) and gives None.  What a
 declared type takes:
@@ -287,13 +287,32 @@ SEAT_SYMBOLS = {
 }
 
 
+#: every symbol include/scanlib_population.h declares, in the shape of ``SYMBOLS`` (tests/test_population_host.py pins it
+#: to that header); looked up after ``SEAT_SYMBOLS``.  Every ``int`` is an rl_status: sizes come back through pointers
+POP_SYMBOLS = {
+    "rl_policy_pop_create": (C.c_int, [C.c_int, C.c_int, C.c_int, i32p, u8p, C.c_int, C.c_float, C.c_float,
+                                       C.POINTER(C.c_void_p)]),
+    "rl_policy_pop_destroy": (None, [C.c_void_p]),
+    "rl_policy_pop_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rl_policy_pop_set": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f32p]),
+    "rl_policy_pop_set_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rl_policy_pop_get": (C.c_int, [C.c_void_p, C.c_int, f32p]),
+    "rl_policy_pop_eval": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f32p]),
+    "rl_policy_pop_eval_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                            C.c_void_p]),
+    "rl_car_drive_population": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, f64p,
+                                          f64p, f32p, C.c_int, C.c_double, C.c_double, C.c_float, C.c_int, f64p,
+                                          C.c_double, C.POINTER(C.c_int), f64p, f64p, f32p, f32p, f64p, f64p]),
+}
+
+
 def declared(name):
-    """(restype, argtypes) of ``name`` from ``SYMBOLS``, then ``EXT_SYMBOLS``, then ``SEAT_SYMBOLS``."""
-    for table in (SYMBOLS, EXT_SYMBOLS):
+    """(restype, argtypes) of ``name`` from ``SYMBOLS``, then ``EXT_SYMBOLS``, ``SEAT_SYMBOLS`` and ``POP_SYMBOLS``."""
+    for table in (SYMBOLS, EXT_SYMBOLS, SEAT_SYMBOLS):
         ent = table.get(name)
         if ent is not None:
             return ent
-    return SEAT_SYMBOLS[name]
+    return POP_SYMBOLS[name]
 
 
 #: the symbols whose ``int`` is a value; every other ``int`` function returns rl_status (``call`` checks it)
@@ -329,7 +348,7 @@ def build(force: bool = False) -> str:
     """Compile libscan_amd.so for gfx950 with hipcc (in-tree; cross-compiles without a GPU)."""
     srcs = [os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc"))
             if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("scanlib.h", "scanlib_track_plan.h", "scanlib_seats.h")]
+    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("scanlib.h", "scanlib_track_plan.h", "scanlib_seats.h", "scanlib_population.h")]
     stale = (not os.path.exists(_SO)) or any(os.path.getmtime(s) > os.path.getmtime(_SO)
                                              for s in srcs)
     if force or stale:
@@ -373,7 +392,8 @@ def lib():
                 "g.build()'` (or make -C pyracecarsimulator_amd/csrc). There is no CPU fallback.")
         _share_torch_hip_runtime()
         L = C.CDLL(_SO)
-        for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(SEAT_SYMBOLS.items()):
+        for name, (res, args) in (list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(SEAT_SYMBOLS.items())
+                                  + list(POP_SYMBOLS.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

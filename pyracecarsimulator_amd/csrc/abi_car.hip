@@ -2,12 +2,14 @@
 // section 8f): the MCTS roll-out generator, FollowGap, the policy network, the race scan; the closed-loop session (loop_args
 // and Loop: handle checks, locks, launch arguments, scan-then-consume) with its users drive_loop, rl_env_* and rl_mcts_*;
 // track-guided planning (include/scanlib_track_plan.h: the planner's track, rl_car_rollout_track); per-seat drivers
-// (include/scanlib_seats.h: rl_car_race_seats, rl_env_attach_seats);
+// (include/scanlib_seats.h: rl_car_race_seats, rl_env_attach_seats); policy populations (include/scanlib_population.h:
+// rl_policy_pop_*, rl_car_drive_population);
 // 16-bit ranges for the xGMI exchange, diagnostics probes, the car-outline table and Car::isCrashed on the host.
 #include "abi_internal.h"
 #pragma GCC visibility push(default)
 #include "../../include/scanlib_track_plan.h"
 #include "../../include/scanlib_seats.h"
+#include "../../include/scanlib_population.h"
 #pragma GCC visibility pop
 #include <array>
 #include <utility>
@@ -36,6 +38,7 @@ struct rl_car {
     DevPtr<float> steer0, tr_steers, tr_poses;
     DevPtr<float> mlp;                                         // rl_car_drive_policy: the network's steers of a tick
     DevPtr<int> seat_rows;                                     // rl_car_race_seats: the cars in policy seats
+    DevPtr<double> pop_states0, pop_fitness;                   // rl_car_drive_population: the starts, fitness [n][2]
     DevPtr<double> o_cars;                                     // rl_car_outline_cells
     DevPtr<int32_t> o_cells;
     DevPtr<int> o_counts;
@@ -587,6 +590,228 @@ extern "C" int rl_policy_eval_device(rl_policy *p, const float *d_scans, int n_s
     return policy_launch(p, d_scans, n_scans, size, d_steers, (hipStream_t)hip_stream);
 }
 
+// ---------------------------------------------------------------- policy populations (include/scanlib_population.h)
+// n_members networks of one architecture in one device block: member m's padded block (rl_policy_create's layout) at
+// m * stride floats; P.W / P.b point into member 0's.
+struct rl_policy_pop {
+    int device = 0, n_members = 0, n_params = 0;
+    size_t stride = 0;                 // floats of a member's padded block: a multiple of 4
+    PolicyParams P{};
+    PopLayout L{};
+    Stream stream;
+    DevPtr<float> weights, theta, scans, steers;
+    // a caller's stream has work of this handle on it (rl_policy_pop_set_device, rl_policy_pop_eval_device): a call that
+    // launches on another stream waits for the device first
+    bool foreign = false;
+    hipStream_t foreign_st = nullptr;
+    std::mutex mu;
+};
+
+extern "C" int rl_policy_pop_create(int device, int n_members, int n_layers, const int *dims, const unsigned char *relu,
+                                    int in_start, float clip, float scale, rl_policy_pop **out)
+{
+    if (!dims || !relu || !out) return fail(RL_ERR_INVALID, "rl_policy_pop_create: null pointer");
+    if (n_members < 1) return fail(RL_ERR_INVALID, "rl_policy_pop_create: n_members must be >= 1 (got %d)", n_members);
+    // (rl_policy_create's checks and codes)
+    if (n_layers < 1) return fail(RL_ERR_INVALID, "rl_policy_pop_create: n_layers must be >= 1 (got %d)", n_layers);
+    if (n_layers > PM_MAX_LAYERS)
+        return fail(RL_ERR_UNSUPPORTED, "rl_policy_pop_create: at most %d layers (got %d)", PM_MAX_LAYERS, n_layers);
+    for (int l = 0; l <= n_layers; ++l)
+        if (dims[l] < 1) return fail(RL_ERR_INVALID, "rl_policy_pop_create: dims[%d] = %d must be >= 1", l, dims[l]);
+    if (dims[0] > PM_MAX_IN)
+        return fail(RL_ERR_UNSUPPORTED, "rl_policy_pop_create: input width %d > %d", dims[0], PM_MAX_IN);
+    for (int l = 1; l < n_layers; ++l)
+        if (dims[l] > PM_MAX_W)
+            return fail(RL_ERR_UNSUPPORTED, "rl_policy_pop_create: width %d of layer %d > %d", dims[l], l, PM_MAX_W);
+    if (dims[n_layers] != 1)
+        return fail(RL_ERR_UNSUPPORTED, "rl_policy_pop_create: one output only (got %d)", dims[n_layers]);
+    if (in_start < 0) return fail(RL_ERR_INVALID, "rl_policy_pop_create: in_start must be >= 0 (got %d)", in_start);
+    int rc = check_device(device);
+    if (rc) return rc;
+    std::unique_ptr<rl_policy_pop, decltype(&rl_policy_pop_destroy)> p(new (std::nothrow) rl_policy_pop(), rl_policy_pop_destroy);
+    if (!p) return fail(RL_ERR_NOMEM, "out of host memory");
+    p->device = device;
+    p->n_members = n_members;
+    // per layer W [K][ceil4(N)] then b [ceil4(N)], as rl_policy_create lays one network out
+    size_t off = 0;
+    int theta = 0;
+    p->L.n_layers = p->P.n_layers = n_layers;
+    for (int l = 0; l <= n_layers; ++l) p->L.dims[l] = p->P.dims[l] = dims[l];
+    for (int l = 0; l < n_layers; ++l) {
+        const int K = dims[l], N = dims[l + 1], Np = (N + 3) & ~3;
+        p->L.theta_off[l] = theta;
+        theta += (K + 1) * N;
+        p->L.w_off[l] = (int)off;
+        off += (size_t)K * Np;
+        p->L.b_off[l] = (int)off;
+        off += Np;
+        if (relu[l]) p->P.relu |= 1u << l;
+    }
+    p->L.theta_off[n_layers] = p->n_params = theta;
+    p->stride = off;
+    p->P.in_start = in_start;
+    p->P.clip = clip;
+    p->P.scale = scale;
+    if (hipSetDevice(device) != hipSuccess || p->stream.create() != hipSuccess) return fail(RL_ERR_HIP, "stream creation failed");
+    const size_t bytes = (size_t)n_members * p->stride * sizeof(float);
+    if ((rc = p->weights.alloc(bytes))) return rc;
+    if (hipMemset(p->weights, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return fail(RL_ERR_HIP, "rl_policy_pop_create: zeroing the members failed");
+    for (int l = 0; l < n_layers; ++l) {
+        p->P.W[l] = p->weights + p->L.w_off[l];
+        p->P.b[l] = p->weights + p->L.b_off[l];
+    }
+    *out = p.release();
+    return RL_OK;
+}
+
+extern "C" void rl_policy_pop_destroy(rl_policy_pop *p)
+{
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    if (p->foreign) (void)hipDeviceSynchronize();
+    if (p->stream) (void)hipStreamSynchronize(p->stream);
+    delete p;
+}
+
+extern "C" int rl_policy_pop_layout(rl_policy_pop *p, int *n_members, int *n_params)
+{
+    if (!p) return fail(RL_ERR_INVALID, "rl_policy_pop_layout: null pointer");
+    if (n_members) *n_members = p->n_members;
+    if (n_params) *n_params = p->n_params;
+    return RL_OK;
+}
+
+// members [first, first + n) of the population, E cars each over scans of `size` beams
+static int pop_range(const char *fn, const rl_policy_pop *p, int first, int n)
+{
+    if (first < 0 || n < 0 || first > p->n_members - n)
+        return fail(RL_ERR_INVALID, "%s: members [%d, %d + %d) do not lie in the population's [0, %d)", fn, first, first, n,
+                    p->n_members);
+    return RL_OK;
+}
+
+static int pop_args(const char *fn, const rl_policy_pop *p, int first, int n, int E, int size)
+{
+    const int rc = pop_range(fn, p, first, n);
+    if (rc) return rc;
+    if (E < 1) return fail(RL_ERR_INVALID, "%s: cars_per_member must be >= 1 (got %d)", fn, E);
+    if (size < p->P.in_start + p->P.dims[0])
+        return fail(RL_ERR_INVALID, "scans of %d beams do not hold the policy's window [%d, %d)", size, p->P.in_start,
+                    p->P.in_start + p->P.dims[0]);
+    const long cars = (long)n * E;     // (n, E < 2^31: no overflow; then cars < 2^31 before the second product)
+    if (cars >= (1L << 31) || cars * std::max(size, 1) >= (1L << 31))
+        return fail(RL_ERR_INVALID, "%s: %d members of %d cars, scans of %d beams: their product must stay below 2^31", fn, n,
+                    E, size);
+    return RL_OK;
+}
+
+// before a launch of the handle on st (under its mutex): work a caller left on another stream is waited for
+static int pop_enter(rl_policy_pop *p, hipStream_t st)
+{
+    HIPCHK(hipSetDevice(p->device));
+    if (p->foreign && st != p->foreign_st) {
+        HIPCHK(hipDeviceSynchronize());
+        p->foreign = false;
+    }
+    if (st != (hipStream_t)p->stream) p->foreign = true, p->foreign_st = st;
+    return RL_OK;
+}
+
+static int pop_pack_launch(rl_policy_pop *p, int first, int n, const float *d_theta, hipStream_t st)
+{
+    const size_t total = (size_t)n * p->n_params;
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 65536);
+    hipLaunchKernelGGL(policy_pop_pack_kernel, dim3(grid), dim3(256), 0, st, p->L, d_theta, first, n, p->stride,
+                       (float *)p->weights);
+    HIPCHK(hipGetLastError());
+    return RL_OK;
+}
+
+extern "C" int rl_policy_pop_set(rl_policy_pop *p, int first, int n, const float *theta_nP)
+{
+    if (!p || (n > 0 && !theta_nP)) return fail(RL_ERR_INVALID, "rl_policy_pop_set: null pointer");
+    int rc = pop_range("rl_policy_pop_set", p, first, n);
+    if (rc || n == 0) return rc;
+    std::lock_guard<std::mutex> lk(p->mu);
+    if ((rc = pop_enter(p, p->stream))) return rc;
+    HostCall hc(p->stream);
+    if ((rc = hc.up(p->theta, theta_nP, (size_t)n * p->n_params)) || (rc = pop_pack_launch(p, first, n, p->theta, hc.st)))
+        return rc;
+    return hc.finish();
+}
+
+extern "C" int rl_policy_pop_set_device(rl_policy_pop *p, int first, int n, const float *d_theta_nP, void *hip_stream)
+{
+    if (!p || (n > 0 && !d_theta_nP)) return fail(RL_ERR_INVALID, "rl_policy_pop_set_device: null pointer");
+    int rc = pop_range("rl_policy_pop_set_device", p, first, n);
+    if (rc || n == 0) return rc;
+    std::lock_guard<std::mutex> lk(p->mu);
+    if ((rc = pop_enter(p, (hipStream_t)hip_stream))) return rc;
+    return pop_pack_launch(p, first, n, d_theta_nP, (hipStream_t)hip_stream);
+}
+
+extern "C" int rl_policy_pop_get(rl_policy_pop *p, int member, float *theta_P)
+{
+    if (!p || !theta_P) return fail(RL_ERR_INVALID, "rl_policy_pop_get: null pointer");
+    int rc = pop_range("rl_policy_pop_get", p, member, 1);
+    if (rc) return rc;
+    std::vector<float> block(p->stride);
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if ((rc = pop_enter(p, p->stream))) return rc;
+        HostCall hc(p->stream);
+        if ((rc = hc.down(block.data(), (const float *)p->weights + (size_t)member * p->stride, p->stride)) || (rc = hc.finish()))
+            return rc;
+    }
+    // the padded block back into theta's order: W[l] row by row without its padding columns, then b[l]
+    for (int l = 0; l < p->L.n_layers; ++l) {
+        const int K = p->L.dims[l], N = p->L.dims[l + 1], Np = (N + 3) & ~3;
+        float *t = theta_P + p->L.theta_off[l];
+        for (int k = 0; k < K; ++k) std::memcpy(t + (size_t)k * N, &block[p->L.w_off[l] + (size_t)k * Np], (size_t)N * sizeof(float));
+        std::memcpy(t + (size_t)K * N, &block[p->L.b_off[l]], (size_t)N * sizeof(float));
+    }
+    return RL_OK;
+}
+
+// the population's network launch: scans [n E][size] -> steers [n E], member first + i / E answers row i
+static int pop_launch(rl_policy_pop *p, int first, int n, int E, const float *d_scans, int size, float *d_steers, hipStream_t st)
+{
+    if (n == 0) return RL_OK;
+    const int wg = (E + PM_CARS - 1) / PM_CARS;
+    hipLaunchKernelGGL(policy_mlp_pop_kernel, dim3((unsigned)n * wg), dim3(64), 0, st, p->P, p->stride, first, wg, E, d_scans,
+                       size, d_steers);
+    HIPCHK(hipGetLastError());
+    return RL_OK;
+}
+
+extern "C" int rl_policy_pop_eval(rl_policy_pop *p, int first, int n, int cars_per_member, const float *scans, int size,
+                                  float *steers)
+{
+    if (!p || (n > 0 && (!scans || !steers))) return fail(RL_ERR_INVALID, "rl_policy_pop_eval: null pointer");
+    int rc = pop_args("rl_policy_pop_eval", p, first, n, cars_per_member, size);
+    if (rc || n == 0) return rc;
+    const size_t R = (size_t)n * cars_per_member;
+    std::lock_guard<std::mutex> lk(p->mu);
+    if ((rc = pop_enter(p, p->stream))) return rc;
+    HostCall hc(p->stream);
+    if ((rc = hc.up(p->scans, scans, R * size)) || (rc = hc.room(p->steers, R)) ||
+        (rc = pop_launch(p, first, n, cars_per_member, p->scans, size, p->steers, hc.st)) || (rc = hc.down(steers, p->steers, R)))
+        return rc;
+    return hc.finish();
+}
+
+extern "C" int rl_policy_pop_eval_device(rl_policy_pop *p, int first, int n, int cars_per_member, const float *d_scans,
+                                         int size, float *d_steers, void *hip_stream)
+{
+    if (!p || (n > 0 && (!d_scans || !d_steers))) return fail(RL_ERR_INVALID, "rl_policy_pop_eval_device: null pointer");
+    int rc = pop_args("rl_policy_pop_eval_device", p, first, n, cars_per_member, size);
+    if (rc || n == 0) return rc;
+    std::lock_guard<std::mutex> lk(p->mu);
+    if ((rc = pop_enter(p, (hipStream_t)hip_stream))) return rc;
+    return pop_launch(p, first, n, cars_per_member, d_scans, size, d_steers, (hipStream_t)hip_stream);
+}
+
 // ---------------------------------------------------------------- the closed-loop session
 // What the closed loops share on the host.  The roll-outs (drive_loop), the driving environment (rl_env_*) and the MCTS
 // planner (rl_mcts_*) check their handles with loop_args, and each of their launching calls lives inside one Loop: its
@@ -628,29 +853,32 @@ struct LoopScan {
     const PolicyParams *net = nullptr;
     const int *rows = nullptr;
     int n_rows = 0;
+    int pop_first = 0, pop_n = 0, pop_E = 0;    // a population as the source: members [pop_first, pop_first + pop_n), n = pop_n pop_E
 };
 
 // One launching call of a closed loop.  Locks in ONE order: the owner's mutex (rl_env::mu, rl_mcts::mu; none for the
 // roll-outs), the car's, the method's, the steering sources' (FollowGap's, then the policy's: rl_car_race_seats holds
-// both), then the map's tables_mu shared.  The method's
+// both; a population's mutex takes the policy's place), then the map's tables_mu shared.  The method's
 // settings are read under its mutex and never written: `base` is the noise offset the loop walks from, and every launch
 // is told its own offset and plain stores (the consumer kernels read the ranges right after the scan).  `ready` of an
 // owner is read and written inside only.
 struct Loop {
     rl_method *const h;
     rl_policy *const p;
+    rl_policy_pop *const pop;
     std::unique_lock<std::mutex> lo, lc, lh, ls, ln;
     std::shared_lock<std::shared_mutex> ml;
     const uint64_t base;
     static std::unique_lock<std::mutex> held(std::mutex *m) { return m ? std::unique_lock(*m) : std::unique_lock<std::mutex>(); }
-    Loop(std::mutex *owner, rl_car *c, rl_method *h_, rl_followgap *g, rl_policy *p_)
-        : h(h_), p(p_), lo(held(owner)), lc(c->mu), lh(h_->mu), ls(held(g ? &g->mu : nullptr)),
-          ln(held(p_ ? &p_->mu : nullptr)), ml(h_->map->tables_mu), base(h_->ray_offset)
+    Loop(std::mutex *owner, rl_car *c, rl_method *h_, rl_followgap *g, rl_policy *p_, rl_policy_pop *pop_ = nullptr)
+        : h(h_), p(p_), pop(pop_), lo(held(owner)), lc(c->mu), lh(h_->mu), ls(held(g ? &g->mu : nullptr)),
+          ln(held(p_ ? &p_->mu : pop_ ? &pop_->mu : nullptr)), ml(h_->map->tables_mu), base(h_->ray_offset)
     {
     }
     LaunchArgs at(uint64_t off) const { return {off, true, h->timing}; }
 
-    // scan-then-consume on st: the scan at noise offset `off`, the network when the source is a policy, then the ROWS
+    // scan-then-consume on st: the scan at noise offset `off`, the network when the source is a policy (a population:
+    // every member's network in its one launch), then the ROWS
     // instantiation of `table` for num_rays, one wave per unit and per_wg units per workgroup
     template <class Fn, class... Args>
     int scan_then(const LoopScan &s, uint64_t off, const std::array<Fn, FG_ROWS> &table, int per_wg, const char *kernel,
@@ -662,6 +890,7 @@ struct Loop {
                              : launch_fan(h, FanCall{a, s.poses, s.n, s.fov, s.num_rays, s.ranges, nullptr, nullptr, nullptr, st});
         if (rc == RL_OK && s.net) rc = policy_rows_launch(*s.net, s.ranges, s.rows, s.n_rows, s.num_rays, s.mlp, st);
         else if (rc == RL_OK && p) rc = policy_launch(p, s.ranges, s.n, s.num_rays, s.mlp, st);
+        else if (rc == RL_OK && pop) rc = pop_launch(pop, s.pop_first, s.pop_n, s.pop_E, s.ranges, s.num_rays, s.mlp, st);
         if (rc) return rc;
         table[(s.num_rays + 63) / 64 - 1]<<<dim3((s.n + per_wg - 1) / per_wg), dim3(64 * per_wg), 0, st>>>(args...);
         if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "%s launch failed", kernel);
@@ -696,11 +925,18 @@ struct DriveCall {
 
 // n cars for n_ticks ticks, steered by FollowGap (g) or the policy network (p, steer_clip), each scanning alone with h's
 // planner; race: n races of `group` cars, which see each other in every scan (race_fan_kernel); seats (a race only):
-// the checked driver code of each seat, g and p the handles of the drivers that occur
+// the checked driver code of each seat, g and p the handles of the drivers that occur; ps: a population as the source
+// (n = ps->n ps->E cars, car r steered by member ps->first + r / ps->E through PolicySteer), checked with pop_args
+struct PopSource {
+    rl_policy_pop *pop;
+    int first, n, E;
+    double *fitness;                   // [n][2] or null
+};
 static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g, rl_policy *p, double steer_clip, int n,
-                      bool race, int group, const DriveCall &a, const int *seats = nullptr)
+                      bool race, int group, const DriveCall &a, const int *seats = nullptr, const PopSource *ps = nullptr)
 {
-    if (!c || !h || !(g || p) || (n > 0 && (!a.states_in || !a.speeds || !a.edge || !a.first_crashed)))
+    const bool net = p || ps;          // the tick reads the network's answers
+    if (!c || !h || !(g || net) || (n > 0 && (!a.states_in || !a.speeds || !a.edge || !a.first_crashed)))
         return fail(RL_ERR_INVALID, "%s: null pointer", name);
     const int n_ticks = a.n_ticks, num_rays = a.num_rays;
     int rc;
@@ -711,11 +947,15 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
         (g && p && (rc = loop_args(name, c, h, nullptr, p, R, num_rays))))
         return rc;
     if (R < 0 || n_ticks <= 0) return fail(RL_ERR_INVALID, "n_rollouts >= 0 and n_ticks > 0 required (got %d, %d)", R, n_ticks);
+    if (ps && ps->pop->device != c->device)
+        return fail(RL_ERR_INVALID, "%s: car (device %d) and population (device %d) must share one device", name, c->device,
+                    ps->pop->device);
     if ((p && (rc = policy_args(p, R, num_rays))) || (rc = check_fan_args(h, R, a.fov, num_rays)) || R == 0) return rc;
     OutlineParams op{};
     if (race && (rc = race_outline(h->map, c->P.LENGTH, c->P.WIDTH, op))) return rc;
-    const Loop lp(nullptr, c, h, g, p);
+    const Loop lp(nullptr, c, h, g, p, ps ? ps->pop : nullptr);
     HIPCHK(hipSetDevice(c->device));
+    if (ps && (rc = pop_enter(ps->pop, c->stream))) return rc;
     const size_t rows = (size_t)R * n_ticks, n_rays = (size_t)R * num_rays;
     // seats: the cars the network drives, race by race (declared before hc: the list outlives the call's copies)
     uint32_t policy_seats = 0;
@@ -734,9 +974,13 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
     if ((rc = hc.up(c->states, a.states_in, (size_t)R * 11)) || (rc = hc.up(c->speeds, a.speeds, R)) ||
         (rc = a.steer0 ? hc.up(c->steer0, a.steer0, R) : hc.zero(c->steer0, R)) || (rc = hc.up(c->edge, a.edge, num_rays)) ||
         (rc = hc.room(c->first, R)) || (rc = hc.room(c->poses, (size_t)R * 3)) || (rc = hc.room(c->ranges, n_rays)) ||
-        (p && (rc = hc.room(c->mlp, R))) || (a.velocities && (rc = hc.fill(c->vel, 0xff, rows))) ||
+        (net && (rc = hc.room(c->mlp, R))) || (a.velocities && (rc = hc.fill(c->vel, 0xff, rows))) ||
         (a.steers && (rc = hc.fill(c->tr_steers, 0xff, rows))) || (a.scan_poses && (rc = hc.fill(c->tr_poses, 0xff, rows * 3))) ||
         (a.states_trace && (rc = hc.fill(c->tr_states, 0xff, rows * 11))))
+        return rc;
+    // the fitness reads the starts again after the last tick: c->states is stepped in place
+    const bool fit = ps && ps->fitness;
+    if (fit && ((rc = hc.up(c->pop_states0, a.states_in, (size_t)R * 11)) || (rc = hc.room(c->pop_fitness, 2 * (size_t)ps->n))))
         return rc;
 
     DriveParams dp{};
@@ -754,7 +998,7 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
     DriveBufs b{c->states, c->speeds, c->steer0, c->edge, c->first, c->poses, c->ranges,
                 a.velocities ? (double *)c->vel : nullptr, a.steers ? (float *)c->tr_steers : nullptr,
                 a.scan_poses ? (float *)c->tr_poses : nullptr, a.states_trace ? (double *)c->tr_states : nullptr,
-                p ? (const float *)c->mlp : nullptr};
+                net ? (const float *)c->mlp : nullptr};
     hipLaunchKernelGGL(drive_start_kernel, dim3((R + 63) / 64), dim3(64), 0, st, dp, b);
     HIPCHK(hipGetLastError());
     // the noise offset walks the global ray id t R num_rays + r num_rays of every tick
@@ -765,9 +1009,16 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
         scan.rows = c->seat_rows;
         scan.n_rows = (int)seat_rows.size();
     }
+    if (ps) scan.pop_first = ps->first, scan.pop_n = ps->n, scan.pop_E = ps->E;
     const auto &table = seats ? seat_tick_table : g ? fg_tick_table : policy_tick_table;
     for (int t = 0; t < n_ticks && rc == RL_OK; ++t)
         rc = lp.scan_then(scan, lp.base + (uint64_t)t * n_rays, table, DRIVE_CARS, "drive_tick_kernel", st, dp, b, t);
+    if (rc == RL_OK && fit) {
+        hipLaunchKernelGGL(policy_pop_fitness_kernel, dim3((ps->n + 63) / 64), dim3(64), 0, st, (const double *)c->states,
+                           (const double *)c->pop_states0, (const int *)c->first, ps->n, ps->E, (double *)c->pop_fitness);
+        HIPCHK(hipGetLastError());
+        rc = hc.down(ps->fitness, c->pop_fitness, 2 * (size_t)ps->n);
+    }
     if (rc || (rc = hc.down(a.first_crashed, c->first, R)) || (rc = hc.down(a.states_out, c->states, (size_t)R * 11)) ||
         (rc = hc.down(a.velocities, c->vel, rows)) || (rc = hc.down(a.steers, c->tr_steers, rows)) ||
         (rc = hc.down(a.scan_poses, c->tr_poses, rows * 3)) || (rc = hc.down(a.states_trace, c->tr_states, rows * 11)))
@@ -812,6 +1063,25 @@ extern "C" int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const 
                       first_crashed, states_out_or_null, velocities_or_null, steers_or_null, scan_poses_or_null,
                       states_trace_or_null};
     return drive_loop("rl_car_drive_policy", c, h, nullptr, p, steer_clip, R, false, 0, a);
+}
+
+extern "C" int rl_car_drive_population(rl_car *c, rl_method *h, rl_policy_pop *pop, int first, int n, int cars_per_member,
+                                       double steer_clip, const double *states_in, const double *speeds,
+                                       const float *steer0_or_null, int n_ticks, double dt, double scan_dist_to_base,
+                                       float fov, int num_rays, const double *edge, double crash_thresh, int *first_crashed,
+                                       double *states_out_or_null, double *velocities_or_null, float *steers_or_null,
+                                       float *scan_poses_or_null, double *states_trace_or_null, double *fitness_n2_or_null)
+{
+    if (!c || !h || !pop) return fail(RL_ERR_INVALID, "rl_car_drive_population: null pointer");
+    // (R = n E must be a number of cars before the loop's checks read it)
+    const int rc = pop_args("rl_car_drive_population", pop, first, n, cars_per_member, num_rays);
+    if (rc) return rc;
+    const DriveCall a{states_in, speeds, steer0_or_null, n_ticks, dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh,
+                      first_crashed, states_out_or_null, velocities_or_null, steers_or_null, scan_poses_or_null,
+                      states_trace_or_null};
+    const PopSource ps{pop, first, n, cars_per_member, fitness_n2_or_null};
+    return drive_loop("rl_car_drive_population", c, h, nullptr, nullptr, steer_clip, n * cars_per_member, false, 0, a, nullptr,
+                      &ps);
 }
 
 extern "C" int rl_car_race_seats(rl_car *c, rl_method *h, rl_followgap *g_or_null, rl_policy *p_or_null,

@@ -43,6 +43,10 @@ BOUNDS = [
     # the policy network: the micro-tile accumulators stay in registers
     ("scan::policy_mlp_kernel", {"scratch": 0}),
     ("scan::policy_mlp_rows_kernel", {"scratch": 0}),
+    # policy populations: the same body a member at a time, the re-layout of theta and the one-lane-per-member fitness sum
+    ("scan::policy_mlp_pop_kernel", {"scratch": 0}),
+    ("scan::policy_pop_pack_kernel", {"scratch": 0}),
+    ("scan::policy_pop_fitness_kernel", {"scratch": 0}),
     # the MCTS planner: the descent, the act wave, the backup's pairwise sum and the walks keep nothing in scratch
     ("scan::mcts_start_kernel", {"scratch": 0}),
     ("scan::mcts_select_kernel", {"scratch": 0}),

@@ -234,6 +234,35 @@ class CarBatch(_lib.Handle):
         return self._drive("rl_car_drive_policy", method, policy, None, (clip,), states, n_ticks, speed, fov,
                            num_rays, edge, crash_thresh, scan_dist_to_base, dt, steer0, trace)
 
+    def drive_population(self, method, pop, states, n_ticks, speed, fov, num_rays, edge, crash_thresh, cars_per_member,
+                         first=0, steer_clip=None, scan_dist_to_base=0.275, dt=0.01, steer0=None, trace=False):
+        """``drive_policy`` for a population (``rl_car_drive_population``, include/scanlib_population.h): ``pop`` a
+        ``population.PolicyPopulation``, states float64 (n E, 11) with E = ``cars_per_member``; car r is steered by
+        member ``first + r // E`` at every tick, every member's network in one launch.  Returns ``drive_policy``'s
+        tuple plus ``fitness`` float64 (n, 2): per member the sum over its cars (ascending, each addition rounded) of
+        travel_dist gained (state index 8), and the number of its cars that crashed."""
+        clip = 0.0 if steer_clip is None else float(steer_clip)
+        if steer_clip is not None and not clip > 0:
+            raise ValueError("steer_clip must be None or > 0")
+        E, first = int(cars_per_member), int(first)
+        if E < 1:
+            raise ValueError("cars_per_member must be >= 1")
+        R, n_ticks, states, speeds, st0, edge, first_crashed, out, vel, steers, poses, trace_st = self._drive_args(
+            states, n_ticks, speed, num_rays, edge, steer0, trace)
+        if R % E:
+            raise ValueError("states must hold a whole number of members: %d cars, %d per member" % (R, E))
+        n = R // E
+        if first < 0 or first + n > pop.n_members:
+            raise ValueError("members [%d, %d) do not lie in [0, %d)" % (first, first + n, pop.n_members))
+        if int(num_rays) < pop.in_start + pop.dims[0]:
+            raise ValueError("scans of %d beams do not hold the policy's window [%d, %d)"
+                             % (num_rays, pop.in_start, pop.in_start + pop.dims[0]))
+        fitness = np.zeros((n, 2), dtype=np.float64)
+        _lib.call("rl_car_drive_population", self, method, pop, first, n, E, clip, states, speeds, st0, n_ticks, dt,
+                  scan_dist_to_base, fov, num_rays, edge, crash_thresh, first_crashed, out, vel, steers, poses, trace_st,
+                  fitness)
+        return (first_crashed, out, vel, steers) + ((poses, trace_st) if trace else ()) + (fitness,)
+
     def plan_mcts(self, method, followgap_or_policy, root_states, n_iterations, seeds, fov, num_rays, edge,
                   crash_thresh, root_actions=0.0, source=None, rollout_steps=200, action_every=10, speed=2.0,
                   dt=0.01, scan_dist_to_base=0.275, C_ucb=0.5, crash_pen=-10.0, uni_dev=0.05, max_nodes=None,

@@ -199,6 +199,16 @@ class RacecarSimulator:
                                      self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
                                      scan_dist_to_base=self.scan_dist_to_base, steer_clip=steer_clip)
 
+    def drivePopulationMany(self, states, n_ticks, pop, cars_per_member, speed=2.0, first=0, steer_clip=None):
+        """``drivePolicyMany`` for a ``population.PolicyPopulation``: states (n E, 11), car r steered by member
+        ``first + r // E`` (E = ``cars_per_member``), every member's network in one launch per tick.  Returns
+        ``CarBatch.drive_population``'s tuple, the (n, 2) ``fitness`` last."""
+        return self.car.drive_population(self.scan_simulator.scan_method, pop,
+                                         np.asarray(states, dtype=np.float64).reshape(-1, 11), n_ticks, speed,
+                                         self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
+                                         cars_per_member, first=first, steer_clip=steer_clip,
+                                         scan_dist_to_base=self.scan_dist_to_base)
+
     def _mcts_source(self, source, policy):
         if source == "fg":
             if self._followgap is None:
