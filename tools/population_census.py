@@ -3,7 +3,9 @@
 tests/population_statement.py over the oracle's scan (noise off), the compiled reference Car and the network's host
 statement.  Prints, per roll-out case, what the reference alone meets of the censuses the GPU tests assert on the
 device's own run: the members' steer traces differ pairwise, a car crashes, a car finishes, an answer passes the clip.
-docs/history/population.md records the output.
+docs/history/population.md records the output.  The last lines are the shapes past one block of work
+(tests/network_scale.py: 67 members x 3 cars, 130 x 1) with the censuses tests/test_gpu_network_scale.py asserts;
+docs/history/network_scale.md records those.
 
 usage: python tools/population_census.py"""
 import os
@@ -70,6 +72,17 @@ def main():
     for B in (64, 65):
         rollout_case(g, dt, "small", TG.ROLLOUT, B, 3, 5, 25, TG.CLIP)
     rollout_case(g, dt, "fixture", TG.ROLLOUT_FIXTURE, 1081, 3, 5, 25, TG.CLIP)
+    # the shapes past one block (tests/network_scale.py, tests/test_gpu_network_scale.py)
+    import network_scale as NS
+    for n, E in sorted(NS.ROLLOUTS):
+        first, final, steers, trace, fit = NS.rollout_cpu(O, reference, g, dt, n, E)
+        ok = np.isfinite(steers)
+        print("roll-out past one block, %d members x %d cars, B %d, %d ticks, seeds %s: %s; %d of %d cars crash, %d of "
+              "them of members >= 64, crash counts %s, %d answers beyond %.1f, %d distinct fitness sums"
+              % (n, E, NS.ROLLOUT_B, NS.ROLLOUT_T, {k: v for k, v in NS.ROLLOUTS[(n, E)].items() if "seed" in k},
+                 NS.rollout_census(first, steers, fit, n, E, TG.CLIP), (first >= 0).sum(), n * E,
+                 (first[64 * E:] >= 0).sum(), sorted(set(fit[:, 1].astype(int).tolist())),
+                 (np.abs(steers[ok]) > TG.CLIP).sum(), TG.CLIP, len(set(fit[:, 0].tolist()))))
 
 
 if __name__ == "__main__":

@@ -3,7 +3,9 @@
 oracle's stamped-grid scan (drive_cases.race_oracle_fan, noise off), the compiled reference Car, the oracle's FollowGap
 and the network's host statement.  Prints, per case, what the reference alone meets of the censuses the GPU tests
 assert: crashes, clamped policy answers, rays the other cars changed, attrition and re-spawn, a wreck seen by a
-scripted car.  docs/history/seats.md records the output.
+scripted car.  docs/history/seats.md records the output.  The last lines are the seated envs across the step kernel's
+64-lane blocks (tests/network_scale.py: 69 and 72 cars) with the censuses tests/test_gpu_network_scale.py asserts;
+docs/history/network_scale.md records those.
 
 usage: python tools/seats_census.py"""
 import os
@@ -109,6 +111,14 @@ def main():
                                   (3, 65, "fpf", 52, 5, 30), (8, 64, "pfpppfpf", 58, 2, 24)):
         rollout_case(g, dt, P, B, mix, seed, R, T)
     env_case(g, dt)
+    # the seated envs across the step kernel's blocks (tests/network_scale.py, tests/test_gpu_network_scale.py)
+    import network_scale as NS
+    for name, case in sorted(NS.SEAT_ENVS.items()):
+        census = NS.seat_env_cpu(O, reference, g, dt, case, TG.small_net())
+        print("env across blocks %s: %d races x %d cars, B %d, pool seed %d (%d line-ups, clear %.0f px), seat speeds %s, "
+              "%d steps: %s -> %s" % (name, case["R"], case["P"], case["B"], case["pool_seed"], case["M"],
+                                      NS.SEAT_CLEAR_PX, case["speed"], case["steps"], census.seen,
+                                      "ok" if census.ok() else "MISSING"))
 
 
 if __name__ == "__main__":
