@@ -306,13 +306,26 @@ POP_SYMBOLS = {
 }
 
 
+#: every symbol include/scanlib_league.h declares, in the shape of ``SYMBOLS`` (tests/test_league_host.py pins it to that
+#: header); looked up after ``POP_SYMBOLS``.  Every ``int`` is an rl_status
+LEAGUE_SYMBOLS = {
+    "rl_policy_pop_eval_rows": (C.c_int, [C.c_void_p, C.c_int, i32p, f32p, C.c_int, f32p]),
+    "rl_policy_pop_eval_rows_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                 C.c_void_p]),
+    "rl_car_race_league": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i32p, C.c_double, f64p, f64p, f32p,
+                                     C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_float, C.c_int, f64p,
+                                     C.c_double, C.POINTER(C.c_int), f64p, f64p, f32p, f32p, f64p, f64p]),
+}
+
+
 def declared(name):
-    """(restype, argtypes) of ``name`` from ``SYMBOLS``, then ``EXT_SYMBOLS``, ``SEAT_SYMBOLS`` and ``POP_SYMBOLS``."""
-    for table in (SYMBOLS, EXT_SYMBOLS, SEAT_SYMBOLS):
+    """(restype, argtypes) of ``name`` from ``SYMBOLS``, then ``EXT_SYMBOLS``, ``SEAT_SYMBOLS``, ``POP_SYMBOLS`` and
+    ``LEAGUE_SYMBOLS``."""
+    for table in (SYMBOLS, EXT_SYMBOLS, SEAT_SYMBOLS, POP_SYMBOLS):
         ent = table.get(name)
         if ent is not None:
             return ent
-    return POP_SYMBOLS[name]
+    return LEAGUE_SYMBOLS[name]
 
 
 #: the symbols whose ``int`` is a value; every other ``int`` function returns rl_status (``call`` checks it)
@@ -348,7 +361,7 @@ def build(force: bool = False) -> str:
     """Compile libscan_amd.so for gfx950 with hipcc (in-tree; cross-compiles without a GPU)."""
     srcs = [os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc"))
             if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("scanlib.h", "scanlib_track_plan.h", "scanlib_seats.h", "scanlib_population.h")]
+    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("scanlib.h", "scanlib_track_plan.h", "scanlib_seats.h", "scanlib_population.h", "scanlib_league.h")]
     stale = (not os.path.exists(_SO)) or any(os.path.getmtime(s) > os.path.getmtime(_SO)
                                              for s in srcs)
     if force or stale:
@@ -393,7 +406,7 @@ def lib():
         _share_torch_hip_runtime()
         L = C.CDLL(_SO)
         for name, (res, args) in (list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(SEAT_SYMBOLS.items())
-                                  + list(POP_SYMBOLS.items())):
+                                  + list(POP_SYMBOLS.items()) + list(LEAGUE_SYMBOLS.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -3,13 +3,15 @@
 // and Loop: handle checks, locks, launch arguments, scan-then-consume) with its users drive_loop, rl_env_* and rl_mcts_*;
 // track-guided planning (include/scanlib_track_plan.h: the planner's track, rl_car_rollout_track); per-seat drivers
 // (include/scanlib_seats.h: rl_car_race_seats, rl_env_attach_seats); policy populations (include/scanlib_population.h:
-// rl_policy_pop_*, rl_car_drive_population);
+// rl_policy_pop_*, rl_car_drive_population); league races (include/scanlib_league.h: rl_policy_pop_eval_rows,
+// rl_car_race_league);
 // 16-bit ranges for the xGMI exchange, diagnostics probes, the car-outline table and Car::isCrashed on the host.
 #include "abi_internal.h"
 #pragma GCC visibility push(default)
 #include "../../include/scanlib_track_plan.h"
 #include "../../include/scanlib_seats.h"
 #include "../../include/scanlib_population.h"
+#include "../../include/scanlib_league.h"
 #pragma GCC visibility pop
 #include <array>
 #include <utility>
@@ -23,6 +25,7 @@
 #include "policy_kernels.h"
 #include "probe_kernels.h"
 #include "race_kernels.h"
+#include "league_kernels.h"
 
 struct rl_car {
     std::vector<rl_car *> reps;          // multi-device (rl_car_create_multi): one ordinary handle per device
@@ -39,6 +42,7 @@ struct rl_car {
     DevPtr<float> mlp;                                         // rl_car_drive_policy: the network's steers of a tick
     DevPtr<int> seat_rows;                                     // rl_car_race_seats: the cars in policy seats
     DevPtr<double> pop_states0, pop_fitness;                   // rl_car_drive_population: the starts, fitness [n][2]
+                                                               // (rl_car_race_league: the starts, standings [N][4])
     DevPtr<double> o_cars;                                     // rl_car_outline_cells
     DevPtr<int32_t> o_cells;
     DevPtr<int> o_counts;
@@ -600,6 +604,10 @@ struct rl_policy_pop {
     PopLayout L{};
     Stream stream;
     DevPtr<float> weights, theta, scans, steers;
+    // league calls (include/scanlib_league.h): the call's member per row, and what the grouping makes of it: per member
+    // the count, the segment start in lg_rows and the start in the workgroup table; the table's length in lg_total
+    DevPtr<int> lg_member, lg_count, lg_start, lg_wg_start, lg_rows, lg_total;
+    DevPtr<int2> lg_table;
     // a caller's stream has work of this handle on it (rl_policy_pop_set_device, rl_policy_pop_eval_device): a call that
     // launches on another stream waits for the device first
     bool foreign = false;
@@ -812,6 +820,92 @@ extern "C" int rl_policy_pop_eval_device(rl_policy_pop *p, int first, int n, int
     return pop_launch(p, first, n, cars_per_member, d_scans, size, d_steers, (hipStream_t)hip_stream);
 }
 
+// ---------------------------------------------------------------- league calls (include/scanlib_league.h)
+// the workgroups of the league network launch over n rows: the host's upper bound of sum_m ceil(count[m] / PM_CARS)
+static size_t league_wg_bound(const rl_policy_pop *p, int n)
+{
+    return (size_t)(n + PM_CARS - 1) / PM_CARS + (size_t)std::min(n, p->n_members);
+}
+
+// the grouping of d_member [n] (n > 0) by member into the handle's buffers: three launches, once per call
+static int league_group(rl_policy_pop *p, const int *d_member, int n, hipStream_t st)
+{
+    const int N = p->n_members;
+    int rc;
+    if ((rc = p->lg_count.ensure(N)) || (rc = p->lg_start.ensure(N)) || (rc = p->lg_wg_start.ensure(N)) ||
+        (rc = p->lg_rows.ensure(n)) || (rc = p->lg_table.ensure(league_wg_bound(p, n))) || (rc = p->lg_total.ensure(1)))
+        return rc;
+    const dim3 per_member((N + LG_WAVES - 1) / LG_WAVES), waves(64 * LG_WAVES);
+    hipLaunchKernelGGL(league_count_kernel, per_member, waves, 0, st, d_member, n, N, (int *)p->lg_count);
+    hipLaunchKernelGGL(league_offsets_kernel, dim3(1), dim3(LG_SCAN), 0, st, (const int *)p->lg_count, N, (int *)p->lg_start,
+                       (int *)p->lg_wg_start, (int *)p->lg_total);
+    hipLaunchKernelGGL(league_fill_kernel, per_member, waves, 0, st, d_member, n, N, (const int *)p->lg_count,
+                       (const int *)p->lg_start, (const int *)p->lg_wg_start, (int *)p->lg_rows, (int2 *)p->lg_table);
+    HIPCHK(hipGetLastError());
+    return RL_OK;
+}
+
+// the league's network launch over the grouping of n rows: scans [.][size] -> steers [row] for every grouped row
+static int league_launch(rl_policy_pop *p, int n, const float *d_scans, int size, float *d_steers, hipStream_t st)
+{
+    if (n == 0) return RL_OK;
+    hipLaunchKernelGGL(policy_mlp_league_kernel, dim3((unsigned)league_wg_bound(p, n)), dim3(64), 0, st, p->P, p->stride,
+                       (const int2 *)p->lg_table, (const int *)p->lg_total, (const int *)p->lg_start, (const int *)p->lg_count,
+                       (const int *)p->lg_rows, d_scans, size, d_steers);
+    HIPCHK(hipGetLastError());
+    return RL_OK;
+}
+
+static int league_rows_args(const char *fn, const rl_policy_pop *p, int n, int size)
+{
+    if (n < 0) return fail(RL_ERR_INVALID, "%s: n must be >= 0 (got %d)", fn, n);
+    if (size < p->P.in_start + p->P.dims[0])
+        return fail(RL_ERR_INVALID, "scans of %d beams do not hold the policy's window [%d, %d)", size, p->P.in_start,
+                    p->P.in_start + p->P.dims[0]);
+    if ((long)n * std::max(size, 1) >= (1L << 31))
+        return fail(RL_ERR_INVALID, "%s: %d scans of %d beams: their product must stay below 2^31", fn, n, size);
+    return RL_OK;
+}
+
+// every entry a member of the population or -1
+static int league_entries(const char *fn, const rl_policy_pop *p, const int *entry, size_t n)
+{
+    for (size_t i = 0; i < n; ++i)
+        if (entry[i] < -1 || entry[i] >= p->n_members)
+            return fail(RL_ERR_INVALID, "%s: entry %zu names member %d: not -1 and not in the population's [0, %d)", fn, i,
+                        entry[i], p->n_members);
+    return RL_OK;
+}
+
+extern "C" int rl_policy_pop_eval_rows(rl_policy_pop *p, int n, const int *member_n, const float *scans, int size,
+                                       float *steers)
+{
+    if (!p || (n > 0 && (!member_n || !scans || !steers))) return fail(RL_ERR_INVALID, "rl_policy_pop_eval_rows: null pointer");
+    int rc = league_rows_args("rl_policy_pop_eval_rows", p, n, size);
+    if (rc || n == 0 || (rc = league_entries("rl_policy_pop_eval_rows", p, member_n, n))) return rc;
+    std::lock_guard<std::mutex> lk(p->mu);
+    if ((rc = pop_enter(p, p->stream))) return rc;
+    HostCall hc(p->stream);
+    // (the caller's steers go up first: a -1 row comes back with the bits it had)
+    if ((rc = hc.up(p->steers, (const float *)steers, n)) || (rc = hc.up(p->lg_member, member_n, n)) ||
+        (rc = hc.up(p->scans, scans, (size_t)n * size)) || (rc = league_group(p, p->lg_member, n, hc.st)) ||
+        (rc = league_launch(p, n, p->scans, size, p->steers, hc.st)) || (rc = hc.down(steers, p->steers, n)))
+        return rc;
+    return hc.finish();
+}
+
+extern "C" int rl_policy_pop_eval_rows_device(rl_policy_pop *p, int n, const int *d_member_n, const float *d_scans, int size,
+                                              float *d_steers, void *hip_stream)
+{
+    if (!p || (n > 0 && (!d_member_n || !d_scans || !d_steers)))
+        return fail(RL_ERR_INVALID, "rl_policy_pop_eval_rows_device: null pointer");
+    int rc = league_rows_args("rl_policy_pop_eval_rows_device", p, n, size);
+    if (rc || n == 0) return rc;
+    std::lock_guard<std::mutex> lk(p->mu);
+    if ((rc = pop_enter(p, (hipStream_t)hip_stream)) || (rc = league_group(p, d_member_n, n, (hipStream_t)hip_stream))) return rc;
+    return league_launch(p, n, d_scans, size, d_steers, (hipStream_t)hip_stream);
+}
+
 // ---------------------------------------------------------------- the closed-loop session
 // What the closed loops share on the host.  The roll-outs (drive_loop), the driving environment (rl_env_*) and the MCTS
 // planner (rl_mcts_*) check their handles with loop_args, and each of their launching calls lives inside one Loop: its
@@ -854,6 +948,8 @@ struct LoopScan {
     const int *rows = nullptr;
     int n_rows = 0;
     int pop_first = 0, pop_n = 0, pop_E = 0;    // a population as the source: members [pop_first, pop_first + pop_n), n = pop_n pop_E
+    bool league = false;                        // a league: the population's members over the grouping of the call's entries
+    int league_net = 0;                         // ... of which this many name a member (0: no network launch)
 };
 
 // One launching call of a closed loop.  Locks in ONE order: the owner's mutex (rl_env::mu, rl_mcts::mu; none for the
@@ -890,6 +986,7 @@ struct Loop {
                              : launch_fan(h, FanCall{a, s.poses, s.n, s.fov, s.num_rays, s.ranges, nullptr, nullptr, nullptr, st});
         if (rc == RL_OK && s.net) rc = policy_rows_launch(*s.net, s.ranges, s.rows, s.n_rows, s.num_rays, s.mlp, st);
         else if (rc == RL_OK && p) rc = policy_launch(p, s.ranges, s.n, s.num_rays, s.mlp, st);
+        else if (rc == RL_OK && pop && s.league) rc = league_launch(pop, s.league_net ? s.n : 0, s.ranges, s.num_rays, s.mlp, st);
         else if (rc == RL_OK && pop) rc = pop_launch(pop, s.pop_first, s.pop_n, s.pop_E, s.ranges, s.num_rays, s.mlp, st);
         if (rc) return rc;
         table[(s.num_rays + 63) / 64 - 1]<<<dim3((s.n + per_wg - 1) / per_wg), dim3(64 * per_wg), 0, st>>>(args...);
@@ -906,6 +1003,8 @@ static const std::array<drive_tick_fn, FG_ROWS> policy_tick_table =
     rows_table<drive_tick_fn>([](auto rows) { return drive_tick_kernel<rows, PolicySteer>; });
 static const std::array<drive_tick_fn, FG_ROWS> seat_tick_table =
     rows_table<drive_tick_fn>([](auto rows) { return drive_tick_kernel<rows, SeatSteer>; });
+static const std::array<drive_tick_fn, FG_ROWS> league_tick_table =
+    rows_table<drive_tick_fn>([](auto rows) { return drive_tick_kernel<rows, LeagueSteer>; });
 
 // what the three roll-out entry points share of their arguments (include/scanlib.h names them)
 struct DriveCall {
@@ -932,10 +1031,19 @@ struct PopSource {
     int first, n, E;
     double *fitness;                   // [n][2] or null
 };
+// lg: a league as the source (a race only): car r steered by member lg->entry[r] of lg->pop, or by g when that is -1;
+// the entries checked with league_entries, n_net of them >= 0
+struct LeagueSource {
+    rl_policy_pop *pop;
+    const int *entry;                  // [n group], host
+    int n_net;
+    double *standings;                 // [n_members][4] or null
+};
 static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g, rl_policy *p, double steer_clip, int n,
-                      bool race, int group, const DriveCall &a, const int *seats = nullptr, const PopSource *ps = nullptr)
+                      bool race, int group, const DriveCall &a, const int *seats = nullptr, const PopSource *ps = nullptr,
+                      const LeagueSource *lg = nullptr)
 {
-    const bool net = p || ps;          // the tick reads the network's answers
+    const bool net = p || ps || lg;    // the tick reads the network's answers
     if (!c || !h || !(g || net) || (n > 0 && (!a.states_in || !a.speeds || !a.edge || !a.first_crashed)))
         return fail(RL_ERR_INVALID, "%s: null pointer", name);
     const int n_ticks = a.n_ticks, num_rays = a.num_rays;
@@ -947,15 +1055,16 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
         (g && p && (rc = loop_args(name, c, h, nullptr, p, R, num_rays))))
         return rc;
     if (R < 0 || n_ticks <= 0) return fail(RL_ERR_INVALID, "n_rollouts >= 0 and n_ticks > 0 required (got %d, %d)", R, n_ticks);
-    if (ps && ps->pop->device != c->device)
+    rl_policy_pop *const pop = ps ? ps->pop : lg ? lg->pop : nullptr;
+    if (pop && pop->device != c->device)
         return fail(RL_ERR_INVALID, "%s: car (device %d) and population (device %d) must share one device", name, c->device,
-                    ps->pop->device);
+                    pop->device);
     if ((p && (rc = policy_args(p, R, num_rays))) || (rc = check_fan_args(h, R, a.fov, num_rays)) || R == 0) return rc;
     OutlineParams op{};
     if (race && (rc = race_outline(h->map, c->P.LENGTH, c->P.WIDTH, op))) return rc;
-    const Loop lp(nullptr, c, h, g, p, ps ? ps->pop : nullptr);
+    const Loop lp(nullptr, c, h, g, p, pop);
     HIPCHK(hipSetDevice(c->device));
-    if (ps && (rc = pop_enter(ps->pop, c->stream))) return rc;
+    if (pop && (rc = pop_enter(pop, c->stream))) return rc;
     const size_t rows = (size_t)R * n_ticks, n_rays = (size_t)R * num_rays;
     // seats: the cars the network drives, race by race (declared before hc: the list outlives the call's copies)
     uint32_t policy_seats = 0;
@@ -982,6 +1091,11 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
     const bool fit = ps && ps->fitness;
     if (fit && ((rc = hc.up(c->pop_states0, a.states_in, (size_t)R * 11)) || (rc = hc.room(c->pop_fitness, 2 * (size_t)ps->n))))
         return rc;
+    // a league: the entries go up and are grouped by member once, before the first tick; the standings read the starts
+    const bool stand = lg && lg->standings;
+    if (lg && ((rc = hc.up(pop->lg_member, lg->entry, R)) || (rc = league_group(pop, pop->lg_member, R, st)))) return rc;
+    if (stand && ((rc = hc.up(c->pop_states0, a.states_in, (size_t)R * 11)) || (rc = hc.room(c->pop_fitness, 4 * (size_t)pop->n_members))))
+        return rc;
 
     DriveParams dp{};
     dp.P = c->P;
@@ -993,12 +1107,12 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
     dp.n_cars = R;
     dp.n_ticks = n_ticks;
     dp.steer_clip = steer_clip;
-    dp.group = seats ? group : 0;
+    dp.group = seats ? group : 0;                 // (a league asks the car's entry, not its seat)
     dp.policy_seats = policy_seats;
     DriveBufs b{c->states, c->speeds, c->steer0, c->edge, c->first, c->poses, c->ranges,
                 a.velocities ? (double *)c->vel : nullptr, a.steers ? (float *)c->tr_steers : nullptr,
                 a.scan_poses ? (float *)c->tr_poses : nullptr, a.states_trace ? (double *)c->tr_states : nullptr,
-                net ? (const float *)c->mlp : nullptr};
+                net ? (const float *)c->mlp : nullptr, lg ? (const int *)pop->lg_member : nullptr};
     hipLaunchKernelGGL(drive_start_kernel, dim3((R + 63) / 64), dim3(64), 0, st, dp, b);
     HIPCHK(hipGetLastError());
     // the noise offset walks the global ray id t R num_rays + r num_rays of every tick
@@ -1010,7 +1124,8 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
         scan.n_rows = (int)seat_rows.size();
     }
     if (ps) scan.pop_first = ps->first, scan.pop_n = ps->n, scan.pop_E = ps->E;
-    const auto &table = seats ? seat_tick_table : g ? fg_tick_table : policy_tick_table;
+    if (lg) scan.league = true, scan.league_net = lg->n_net;
+    const auto &table = lg ? league_tick_table : seats ? seat_tick_table : g ? fg_tick_table : policy_tick_table;
     for (int t = 0; t < n_ticks && rc == RL_OK; ++t)
         rc = lp.scan_then(scan, lp.base + (uint64_t)t * n_rays, table, DRIVE_CARS, "drive_tick_kernel", st, dp, b, t);
     if (rc == RL_OK && fit) {
@@ -1018,6 +1133,14 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
                            (const double *)c->pop_states0, (const int *)c->first, ps->n, ps->E, (double *)c->pop_fitness);
         HIPCHK(hipGetLastError());
         rc = hc.down(ps->fitness, c->pop_fitness, 2 * (size_t)ps->n);
+    }
+    if (rc == RL_OK && stand) {
+        hipLaunchKernelGGL(league_standings_kernel, dim3((pop->n_members + 63) / 64), dim3(64), 0, st, (const double *)c->states,
+                           (const double *)c->pop_states0, (const int *)c->first, (const int *)pop->lg_start,
+                           (const int *)pop->lg_count, (const int *)pop->lg_rows, pop->n_members, group, n_ticks,
+                           (double *)c->pop_fitness);
+        HIPCHK(hipGetLastError());
+        rc = hc.down(lg->standings, c->pop_fitness, 4 * (size_t)pop->n_members);
     }
     if (rc || (rc = hc.down(a.first_crashed, c->first, R)) || (rc = hc.down(a.states_out, c->states, (size_t)R * 11)) ||
         (rc = hc.down(a.velocities, c->vel, rows)) || (rc = hc.down(a.steers, c->tr_steers, rows)) ||
@@ -1112,6 +1235,41 @@ extern "C" int rl_car_race_seats(rl_car *c, rl_method *h, rl_followgap *g_or_nul
     // (a handle no seat uses is not looked at)
     return drive_loop("rl_car_race_seats", c, h, fg ? g_or_null : nullptr, net ? p_or_null : nullptr, steer_clip, n_races,
                       true, group, a, seat_driver);
+}
+
+extern "C" int rl_car_race_league(rl_car *c, rl_method *h, rl_followgap *g_or_null, rl_policy_pop *pop, const int *entry_RP,
+                                  double steer_clip, const double *states_in, const double *speeds,
+                                  const float *steer0_or_null, int n_races, int group, int n_ticks, double dt,
+                                  double scan_dist_to_base, float fov, int num_rays, const double *edge, double crash_thresh,
+                                  int *first_crashed, double *states_out_or_null, double *velocities_or_null,
+                                  float *steers_or_null, float *scan_poses_or_null, double *states_trace_or_null,
+                                  double *standings_N4_or_null)
+{
+    if (!c || !h || !pop || (n_races > 0 && !entry_RP)) return fail(RL_ERR_INVALID, "rl_car_race_league: null pointer");
+    if (group < 1 || group > RACE_MAX_GROUP)
+        return fail(RL_ERR_INVALID, "group must lie in [1, %d] cars (got %d)", RACE_MAX_GROUP, group);
+    if (n_races < 0) return fail(RL_ERR_INVALID, "n_races must be >= 0 (got %d)", n_races);
+    // (n_races group must be a number of cars before the entries are walked: the race scan's own bound, here first)
+    if ((long)n_races * group * std::max(num_rays, 1) >= (1L << 31))
+        return fail(RL_ERR_INVALID, "rl_car_race_league: %d races of %d cars, scans of %d beams: their product must stay below 2^31",
+                    n_races, group, num_rays);
+    const size_t R = (size_t)n_races * group;
+    int rc = league_entries("rl_car_race_league", pop, entry_RP, R);
+    if (rc) return rc;
+    int n_net = 0;
+    for (size_t r = 0; r < R; ++r) n_net += entry_RP[r] >= 0;
+    if ((size_t)n_net < R && !g_or_null)
+        return fail(RL_ERR_INVALID, "rl_car_race_league: an entry is -1 (FollowGap), whose handle is null");
+    if (n_net && num_rays < pop->P.in_start + pop->P.dims[0])
+        return fail(RL_ERR_INVALID, "scans of %d beams do not hold the policy's window [%d, %d)", num_rays, pop->P.in_start,
+                    pop->P.in_start + pop->P.dims[0]);
+    const DriveCall a{states_in, speeds, steer0_or_null, n_ticks, dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh,
+                      first_crashed, states_out_or_null, velocities_or_null, steers_or_null, scan_poses_or_null,
+                      states_trace_or_null};
+    // (a FollowGap handle no entry uses is not looked at)
+    const LeagueSource lg{pop, entry_RP, n_net, standings_N4_or_null};
+    return drive_loop("rl_car_race_league", c, h, (size_t)n_net < R ? g_or_null : nullptr, nullptr, steer_clip, n_races, true,
+                      group, a, nullptr, nullptr, &lg);
 }
 
 // ---------------------------------------------------------------- the driving environment (env_kernels.h)

@@ -47,6 +47,14 @@ BOUNDS = [
     ("scan::policy_mlp_pop_kernel", {"scratch": 0}),
     ("scan::policy_pop_pack_kernel", {"scratch": 0}),
     ("scan::policy_pop_fitness_kernel", {"scratch": 0}),
+    # league races: the grouping's ballot walks and offsets scan, the network over the device's workgroup table, and the
+    # one-lane-per-member standings (the LeagueSteer tick is one of the drive_tick_kernel< rows above)
+    ("scan::league_count_kernel", {"scratch": 0}),
+    ("scan::league_offsets_kernel", {"scratch": 0}),
+    ("scan::league_fill_kernel", {"scratch": 0}),
+    ("scan::policy_mlp_league_kernel", {"scratch": 0}),
+    ("scan::league_standings_kernel", {"scratch": 0}),
+    ("scan::drive_tick_kernel<20, scan::LeagueSteer>", {"scratch": 0}),
     # the MCTS planner: the descent, the act wave, the backup's pairwise sum and the walks keep nothing in scratch
     ("scan::mcts_start_kernel", {"scratch": 0}),
     ("scan::mcts_select_kernel", {"scratch": 0}),

@@ -8,7 +8,7 @@
 //   2. drive_tick_kernel<ROWS, Steer>: one wave per car — the scan into registers, Car::isCrashed's f64 compare
 //      (racecar.cpp:305-328) as a ballot, the source's answer (FollowGapSteer: followgap_bits_eval's four passes,
 //      consumer_kernels.h; PolicySteer: the network's output; SeatSteer: whichever of the two drives the car's seat
-//      of its race) —, then one lane per car: the car step of the NEXT tick with the new steering angle and that
+//      of its race; LeagueSteer, league_kernels.h: the population member or FollowGap its entry names) —, then one lane per car: the car step of the NEXT tick with the new steering angle and that
 //      tick's lidar pose.
 // drive_start_kernel (one lane per car) is the prologue: tick 0's step with the initial steer.
 #pragma once
@@ -44,6 +44,8 @@ struct DriveBufs {
     double *states_trace;        // [R, T, 11]
     const float *mlp;            // policy source: [R] the network's answers to this tick's scans (seat source: the rows
                                  // of the cars in policy seats; the others are never read)
+    const int *entry;            // league source (league_kernels.h): [R] the car's driver, a member of the population or
+                                 // -1 for FollowGap; null otherwise
 };
 
 __device__ inline CarState drive_load_state(const double *s)
@@ -123,7 +125,7 @@ struct FollowGapSteer {
     {
         return followgap_bits_eval<ROWS>(raw, dp.fg, bits);
     }
-    __device__ static double steer(const DriveParams &, int, float a) { return (double)a; }
+    __device__ static double steer(const DriveParams &, const DriveBufs &, int, float a) { return (double)a; }
 };
 
 // policy_mlp_kernel's output (every car's scan, frozen ones included).  steer_clip > 0: the car gets
@@ -135,7 +137,7 @@ struct PolicySteer {
     {
         return b.mlp[r];
     }
-    __device__ static double steer(const DriveParams &dp, int, float a)
+    __device__ static double steer(const DriveParams &dp, const DriveBufs &, int, float a)
     {
         const double s = (double)a;
         return dp.steer_clip > 0.0 ? fmin(fmax(s, -dp.steer_clip), dp.steer_clip) : s;
@@ -153,9 +155,9 @@ struct SeatSteer {
         if (policy(dp, r)) return PolicySteer::answer<ROWS>(dp, b, r, raw, bits);
         return FollowGapSteer::answer<ROWS>(dp, b, r, raw, bits);
     }
-    __device__ static double steer(const DriveParams &dp, int r, float a)
+    __device__ static double steer(const DriveParams &dp, const DriveBufs &b, int r, float a)
     {
-        return policy(dp, r) ? PolicySteer::steer(dp, r, a) : FollowGapSteer::steer(dp, r, a);
+        return policy(dp, r) ? PolicySteer::steer(dp, b, r, a) : FollowGapSteer::steer(dp, b, r, a);
     }
 };
 
@@ -193,7 +195,7 @@ __global__ __launch_bounds__(64 * DRIVE_CARS) void drive_tick_kernel(DriveParams
     __syncthreads();
     if (threadIdx.x < DRIVE_CARS && step_next[threadIdx.x]) {
         const int rs = blockIdx.x * DRIVE_CARS + threadIdx.x;
-        drive_step(dp, b, rs, t + 1, Steer::steer(dp, rs, answer_next[threadIdx.x]));
+        drive_step(dp, b, rs, t + 1, Steer::steer(dp, b, rs, answer_next[threadIdx.x]));
     }
 }
 

@@ -161,6 +161,42 @@ class PolicyPopulation(_lib.Handle):
         _lib.call("rl_policy_pop_eval", self, first, n, E, np.ascontiguousarray(scans), scans.shape[1], out)
         return out
 
+    def predict_rows(self, scans, members, out=None):
+        """Row-indexed evaluation (``rl_policy_pop_eval_rows``, include/scanlib_league.h): steers float32 (n,) of scans
+        float32 (n, size), row i by member ``members[i]``, in any order.  A row with ``members[i] == -1`` is not
+        answered: it keeps the value ``out`` (float32 (n,), written in place when C-contiguous) holds there, NaN
+        without ``out``."""
+        from .league import member_args
+        scans = np.asarray(scans)
+        if scans.dtype != np.float32 or scans.ndim != 2:
+            raise ValueError("scans must be float32 (n, size)")
+        n = scans.shape[0]
+        members = member_args(members, n, self.n_members)
+        if scans.shape[1] < self.in_start + self.dims[0]:
+            raise ValueError("scans of %d beams do not hold the policy's window [%d, %d)"
+                             % (scans.shape[1], self.in_start, self.in_start + self.dims[0]))
+        if out is None:
+            out = np.full(n, np.nan, np.float32)
+        else:
+            out = np.asarray(out)
+            if out.dtype != np.float32 or out.shape != (n,):
+                raise ValueError("out must be float32 (%d,)" % n)
+            out = np.ascontiguousarray(out)
+        _lib.call("rl_policy_pop_eval_rows", self, n, members, np.ascontiguousarray(scans), scans.shape[1], out)
+        return out
+
+    def predict_rows_device(self, d_scans_ptr, d_members_ptr, n, size, d_steers_ptr, stream=0):
+        """Device-resident form of ``predict_rows``: ``d_scans_ptr`` -> float32[n size], ``d_members_ptr`` -> int32[n],
+        ``d_steers_ptr`` -> float32[n]; asynchronous on ``stream``.  An entry outside [0, n_members) is treated as -1."""
+        n, size = int(n), int(size)
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        if size < self.in_start + self.dims[0]:
+            raise ValueError("scans of %d beams do not hold the policy's window [%d, %d)"
+                             % (size, self.in_start, self.in_start + self.dims[0]))
+        _lib.call("rl_policy_pop_eval_rows_device", self, n, int(d_members_ptr), int(d_scans_ptr), size,
+                  int(d_steers_ptr), int(stream))
+
     def predict_device(self, d_scans_ptr, cars_per_member, size, d_steers_ptr, first=0, n=None, stream=0):
         """Device-resident form: ``d_scans_ptr`` -> float32[n E size], ``d_steers_ptr`` -> float32[n E];
         asynchronous on ``stream``."""

@@ -263,6 +263,35 @@ class CarBatch(_lib.Handle):
                   fitness)
         return (first_crashed, out, vel, steers) + ((poses, trace_st) if trace else ()) + (fitness,)
 
+    def race_league(self, method, pop, entries, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
+                    followgap=None, steer_clip=None, steer0=None, dt=0.01, trace=False, scan_dist_to_base=0.275):
+        """``race_seats`` with a line-up per race drawn from a population (``rl_car_race_league``,
+        include/scanlib_league.h): ``entries`` int (R, P) names the driver of every car, member m >= 0 of ``pop`` (a
+        ``population.PolicyPopulation``) or -1 for ``followgap``; states float64 (R, P, 11).  ``steer_clip`` clamps the
+        members' cars only.  Returns ``race_seats``'s tuple plus ``standings`` float64 (n_members, 4): per member the
+        cars it entered, the sum of their travel_dist gains (ascending car index, each addition rounded), how many
+        crashed, and how many cars of their own races they beat (alive longer, or as long with the larger gain)."""
+        from .league import league_args
+        st = np.asarray(states)
+        if st.dtype != np.float64 or st.ndim != 3 or st.shape[2] != 11:
+            raise ValueError("states must be float64 (R, P, 11)")
+        n_races, group = st.shape[0], st.shape[1]
+        entry = league_args(entries, n_races, group, pop, followgap, num_rays)
+        clip = 0.0 if steer_clip is None else float(steer_clip)
+        if steer_clip is not None and not clip > 0:
+            raise ValueError("steer_clip must be None or > 0")
+        spd = np.asarray(speed, dtype=np.float64)
+        spd = float(spd) if spd.ndim == 0 else spd.reshape(-1)
+        st0 = None if steer0 is None else np.asarray(steer0).reshape(-1)
+        R, n_ticks, states, speeds, st0, edge, first, out, vel, steers, poses, trace_st = self._drive_args(
+            st.reshape(-1, 11), n_ticks, spd, num_rays, edge, st0, trace)
+        standings = np.zeros((pop.n_members, 4), dtype=np.float64)
+        _lib.call("rl_car_race_league", self, method, followgap, pop, entry, clip, states, speeds, st0, n_races, group,
+                  n_ticks, dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh, first, out, vel, steers, poses,
+                  trace_st, standings)
+        res = (first, out, vel, steers) + ((poses, trace_st) if trace else ())
+        return tuple(a.reshape((n_races, group) + a.shape[1:]) for a in res) + (standings,)
+
     def plan_mcts(self, method, followgap_or_policy, root_states, n_iterations, seeds, fov, num_rays, edge,
                   crash_thresh, root_actions=0.0, source=None, rollout_steps=200, action_every=10, speed=2.0,
                   dt=0.01, scan_dist_to_base=0.275, C_ucb=0.5, crash_pen=-10.0, uni_dev=0.05, max_nodes=None,

@@ -209,6 +209,16 @@ class RacecarSimulator:
                                          cars_per_member, first=first, steer_clip=steer_clip,
                                          scan_dist_to_base=self.scan_dist_to_base)
 
+    def raceLeagueMany(self, states, n_ticks, pop, entries, speed=2.0, steer_clip=None):
+        """``raceSeatsMany`` with a line-up per race drawn from a ``population.PolicyPopulation``: ``entries`` int
+        (R, P) names every car's driver, member m >= 0 of ``pop`` or -1 for this simulator's own FollowGap driver (as
+        ``raceFollowGapMany`` builds it).  ``steer_clip`` clamps the members' cars only.  Returns
+        ``CarBatch.race_league``'s tuple, the (n_members, 4) ``standings`` last."""
+        fg = self._mcts_source("fg", None) if (np.asarray(entries) < 0).any() else None
+        return self.car.race_league(self.scan_simulator.scan_method, pop, entries, np.asarray(states, dtype=np.float64),
+                                    n_ticks, speed, self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
+                                    followgap=fg, steer_clip=steer_clip, scan_dist_to_base=self.scan_dist_to_base)
+
     def _mcts_source(self, source, policy):
         if source == "fg":
             if self._followgap is None:
