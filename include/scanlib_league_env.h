@@ -1,0 +1,119 @@
+/* scanlib_league_env.h — league line-ups in the race environment, with per-driver results.  An extension of
+ * scanlib_league.h (which it includes, and with it scanlib_population.h, scanlib_seats.h and scanlib.h, whose
+ * conventions it keeps: every function returns RL_OK or a negative rl_status, rl_last_error names the reason).
+ * pyracecarsimulator_amd/_lib.py restates it in LEAGUE_ENV_SYMBOLS; tests/league_env_statement.py restates the rules.
+ *
+ * ---- what it covers ----------------------------------------------------------------------------------------
+ * Seats (scanlib_seats.h) script the opponents of a race environment, but every race shares one seat table with at most
+ * one network.  Leagues (scanlib_league.h) give every race its own line-up from a population, but only inside the closed
+ * roll-out rl_car_race_league, where nobody acts from outside.  Here a race environment (rl_env_create_race) takes a
+ * league: every car has its own ENTRY, so that a learner can sit in one seat of each of R races, each race against
+ * different members of a population; line-ups can be replaced while races run; and the env keeps, per driver, a running
+ * tally of who beat whom.  An env without a league launches exactly the kernels it launched before.
+ *
+ * ---- entries -------------------------------------------------------------------------------------------------
+ * One int per car of the env: car k of race r (P = group cars a race) is entry[r P + k].
+ *     -2      the caller's actions;
+ *     -1      FollowGap g;
+ *     m >= 0  member m of pop.
+ * A car with an entry >= -1 is SCRIPTED and follows the seats' rule (scanlib_seats.h, "The rule"): in phase A of a step
+ * a scripted car that would otherwise go through the env's action check takes ((double)speed[k], (double)answer) in
+ * place of its row of `actions`, which is not read (NaN there is no refused action).  answer is its driver's f32 answer
+ * to the car's own full scan of the call before (all num_rays beams, that slot's noise).  The pair goes through the same
+ * finiteness check (a non-finite answer reads done = 3), the env's steer_clip clamp and `substeps` steps as a caller's
+ * pair.  A member's answer is bit for bit rl_policy_eval of an rl_policy made from that member's theta as it stands in
+ * stream order at that call's launch: rl_policy_pop_set* between two steps takes effect from the next call's scan.
+ * Equivalently: the env behaves bit for bit like the same env without a league whose caller writes (speed[k], answer)
+ * into the scripted cars' rows.
+ *
+ * ---- pending and live line-ups -------------------------------------------------------------------------------
+ * The env holds two tables of n_envs entries.  The setters replace the PENDING one.  Every race runs with its LIVE
+ * line-up and adopts the pending entries of its cars only when it spawns: at a reset, and at an auto-reset re-spawn.
+ * Phase A copies pending -> live car by car, in the lane that spawns the car.  A running race is never re-seated, and a
+ * finished race that stands (auto_reset = 0) keeps its line-up: a trainer hands over a new table at any time, with no
+ * masking, and each race picks it up at its next episode.
+ *
+ * ---- entry points --------------------------------------------------------------------------------------------
+ * rl_env_attach_league(e, g_or_null, pop, entry_N, speed_P): race envs only (group = 1 included).  g and pop are
+ *   borrowed: keep them alive while they are attached.  entry_N (host, n_envs ints, checked) becomes the pending table;
+ *   speed_P[k], k < group, is the commanded speed of a scripted car in seat k (finite wherever entry_N scripts a car of
+ *   that seat; a seat with caller's cars only is not looked at).  A null entry_N detaches the league (g, pop and speed_P
+ *   are not read).  The env needs a reset afterwards.  The results start at zero.  Refused while seats are attached; a
+ *   non-null rl_env_attach_seats is refused while a league is attached.
+ * rl_env_set_league_entries(e, entry_N): host pointer, synchronous, entries checked as at the attach (the speeds are
+ *   the attach's).
+ * rl_env_set_league_entries_device(e, d_entry_N, hip_stream): device pointer, only enqueued (a copy on hip_stream).  It
+ *   cannot look at the entries: an entry outside [-2, n_members) behaves as -2, by construction (the kernels script a
+ *   car only when its entry lies in [-1, n_members), and the grouping matches no member); so does -1 in an env attached
+ *   with a null g, and so does every m >= 0 in an env whose num_rays is below the population's window (no network is
+ *   ever launched there).  A seat speed that is not finite makes a scripted car of that seat read done = 3.  It sets the
+ *   env's foreign-stream flag as the other device forms do.
+ * rl_env_read_league_steers(e, steer_n) / rl_env_read_league_steers_device(e, d_steer_n, hip_stream): the answer kept
+ *   per car after phase B: the driver's answer to this call's scan when the car is scripted and reads done = 0 after
+ *   phase B (the race's rule included); NaN otherwise (a caller's car; a car that is not running after that scan) —
+ *   rl_env_read_seats' rule.
+ * rl_env_read_league_entries(e, live_N, pending_N): host pointers, either may be null.  The live table holds the bits the
+ *   cars adopted (an out-of-range device entry reads back as it was set).
+ * rl_env_read_league_results(e, results, clear): int64 [n_members + 2][8]; row m < n_members is member m, row n_members
+ *   FollowGap, row n_members + 1 the caller's cars.  clear != 0 zeroes the counters after the copy, in stream order.  A
+ *   reset does not clear them.
+ *
+ * ---- results -------------------------------------------------------------------------------------------------
+ * Added once per race, in phase B of the call in which the race's `over` leaves RACE_RUNNING, for the line-up the race
+ * ran with (the live entries).  For car a of that race: ticks(a) = tick[a], the steps it took this episode, as
+ * rl_env_read shows them; gain(a) = state[a][8] - the [8] of its row of the start pool; done(a) the code after the race's
+ * rule.  Car a BEATS car b of the same race when, tested in order:
+ *     ticks(a) > ticks(b);
+ *     the ticks are equal, a reads done 2 and b reads 1 or 3;
+ *     the ticks are equal, both are in the same of those two classes, and gain(a) > gain(b) in plain f64.
+ * Ties and NaN beat nobody.  Columns of a driver's row:
+ *     0 cars entered in finished races      4 cars beaten
+ *     1 of them, done 1 or 3                5 caller cars faced
+ *     2 the sum of their ticks              6 caller cars beaten
+ *     3 cars faced (P - 1 each)             7 caller cars that beat it
+ * A race cut off by a reset adds nothing; a finished race that stands adds nothing more.  Every column is an integer,
+ * so the tally does not depend on the order in which races finish: the wave of each car adds its eight columns with
+ * 64-bit vector atomics (one global_atomic_add_x2 per non-zero column, lanes 0-7), which needs no pass over the
+ * population and costs nothing in the calls in which no race ends.
+ *
+ * ---- per call ------------------------------------------------------------------------------------------------
+ * race_env_league_step_kernel (phase A, with the adoption), league_count / offsets / fill over the LIVE entries (every
+ * call, reset and step: the adoption happens on the device and the host cannot know when; it also makes the env immune
+ * to other league calls that reuse the population's grouping buffers between two steps), race_fan_kernel,
+ * policy_mlp_league_kernel over this call's ranges (-2 and -1 match no member and are in no segment; the launch is
+ * skipped only while the host knows that no pending or live entry can be >= 0: every host-set table since the attach
+ * had none and no device setter ran), race_env_league_observe_kernel.  Locks: the env's, the car's, the method's,
+ * FollowGap's, then the population's.  A track, the observation window, aux, auto-reset and both device forms of reset
+ * and step work unchanged with a league attached.
+ *
+ * Errors (RL_ERR_INVALID, nothing launched or changed, the handles usable as before): a null e or pop; an env that is
+ *   not a race env; g or pop on another device than the env (none of these handles has a multi-device form); a -1 entry
+ *   with a null g (host forms); a host entry outside [-2, n_members); a non-finite speed of a seat that holds a scripted
+ *   entry; num_rays below the population's window when an entry >= 0 exists; the attach while seats are attached (and
+ *   rl_env_attach_seats while a league is); setters or reads with no league attached; steers or results read before a
+ *   reset; a null entry table in a setter, a null results pointer.
+ *
+ * Out of scope: leagues in the single-car environment (rl_env_create); a placing by track progress; members of
+ *   different architectures; multi-device handles; graph capture; a device-pointer form of the results read.         */
+#ifndef SCANLIB_LEAGUE_ENV_H
+#define SCANLIB_LEAGUE_ENV_H
+
+#include "scanlib_league.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+int rl_env_attach_league(rl_env *e, rl_followgap *g_or_null, rl_policy_pop *pop, const int *entry_N_or_null,
+                         const float *speed_P);
+int rl_env_set_league_entries(rl_env *e, const int *entry_N);
+int rl_env_set_league_entries_device(rl_env *e, const int *d_entry_N, void *hip_stream);
+int rl_env_read_league_steers(rl_env *e, float *steer_n);
+int rl_env_read_league_steers_device(rl_env *e, float *d_steer_n, void *hip_stream);
+int rl_env_read_league_entries(rl_env *e, int *live_N_or_null, int *pending_N_or_null);
+int rl_env_read_league_results(rl_env *e, int64_t *results, int clear);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

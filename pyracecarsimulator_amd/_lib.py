@@ -6,7 +6,8 @@ device is usable, the calls raise.
 
 ``SYMBOLS`` restates every prototype of the header (tests/test_py_calls_host.py pins it to the header, argument by
 argument, with the structures and enums below); ``EXT_SYMBOLS`` does the same for include/scanlib_track_plan.h and
-``SEAT_SYMBOLS`` for include/scanlib_seats.h, ``POP_SYMBOLS`` for include/scanlib_population.h.
+``SEAT_SYMBOLS`` for include/scanlib_seats.h, ``POP_SYMBOLS`` for include/scanlib_population.h, ``LEAGUE_SYMBOLS`` for
+include/scanlib_league.h and ``LEAGUE_ENV_SYMBOLS`` for include/scanlib_league_env.h.
 ``call(name, *args)`` is how the package's wrappers enter the library: every argument is converted by the type the
 tables declare for it, and a symbol that returns ``rl_status`` is checked (``ScanLibError``) and gives None.  What a
 declared type takes:
@@ -318,14 +319,27 @@ LEAGUE_SYMBOLS = {
 }
 
 
+#: every symbol include/scanlib_league_env.h declares, in the shape of ``SYMBOLS`` (tests/test_league_env_host.py pins it
+#: to that header); looked up after ``LEAGUE_SYMBOLS``.  Every ``int`` is an rl_status
+LEAGUE_ENV_SYMBOLS = {
+    "rl_env_attach_league": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, i32p, f32p]),
+    "rl_env_set_league_entries": (C.c_int, [C.c_void_p, i32p]),
+    "rl_env_set_league_entries_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rl_env_read_league_steers": (C.c_int, [C.c_void_p, f32p]),
+    "rl_env_read_league_steers_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rl_env_read_league_entries": (C.c_int, [C.c_void_p, i32p, i32p]),
+    "rl_env_read_league_results": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+}
+
+
 def declared(name):
-    """(restype, argtypes) of ``name`` from ``SYMBOLS``, then ``EXT_SYMBOLS``, ``SEAT_SYMBOLS``, ``POP_SYMBOLS`` and
-    ``LEAGUE_SYMBOLS``."""
-    for table in (SYMBOLS, EXT_SYMBOLS, SEAT_SYMBOLS, POP_SYMBOLS):
+    """(restype, argtypes) of ``name`` from ``SYMBOLS``, then ``EXT_SYMBOLS``, ``SEAT_SYMBOLS``, ``POP_SYMBOLS``,
+    ``LEAGUE_SYMBOLS`` and ``LEAGUE_ENV_SYMBOLS``."""
+    for table in (SYMBOLS, EXT_SYMBOLS, SEAT_SYMBOLS, POP_SYMBOLS, LEAGUE_SYMBOLS):
         ent = table.get(name)
         if ent is not None:
             return ent
-    return LEAGUE_SYMBOLS[name]
+    return LEAGUE_ENV_SYMBOLS[name]
 
 
 #: the symbols whose ``int`` is a value; every other ``int`` function returns rl_status (``call`` checks it)
@@ -361,7 +375,8 @@ def build(force: bool = False) -> str:
     """Compile libscan_amd.so for gfx950 with hipcc (in-tree; cross-compiles without a GPU)."""
     srcs = [os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc"))
             if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("scanlib.h", "scanlib_track_plan.h", "scanlib_seats.h", "scanlib_population.h", "scanlib_league.h")]
+    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("scanlib.h", "scanlib_track_plan.h", "scanlib_seats.h", "scanlib_population.h", "scanlib_league.h",
+                                                                       "scanlib_league_env.h")]
     stale = (not os.path.exists(_SO)) or any(os.path.getmtime(s) > os.path.getmtime(_SO)
                                              for s in srcs)
     if force or stale:
@@ -406,7 +421,8 @@ def lib():
         _share_torch_hip_runtime()
         L = C.CDLL(_SO)
         for name, (res, args) in (list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(SEAT_SYMBOLS.items())
-                                  + list(POP_SYMBOLS.items()) + list(LEAGUE_SYMBOLS.items())):
+                                  + list(POP_SYMBOLS.items()) + list(LEAGUE_SYMBOLS.items())
+                                  + list(LEAGUE_ENV_SYMBOLS.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

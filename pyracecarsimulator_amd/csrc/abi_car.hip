@@ -4,7 +4,8 @@
 // track-guided planning (include/scanlib_track_plan.h: the planner's track, rl_car_rollout_track); per-seat drivers
 // (include/scanlib_seats.h: rl_car_race_seats, rl_env_attach_seats); policy populations (include/scanlib_population.h:
 // rl_policy_pop_*, rl_car_drive_population); league races (include/scanlib_league.h: rl_policy_pop_eval_rows,
-// rl_car_race_league);
+// rl_car_race_league); league line-ups in the race environment (include/scanlib_league_env.h: rl_env_attach_league,
+// rl_env_set_league_entries*, rl_env_read_league_*);
 // 16-bit ranges for the xGMI exchange, diagnostics probes, the car-outline table and Car::isCrashed on the host.
 #include "abi_internal.h"
 #pragma GCC visibility push(default)
@@ -12,6 +13,7 @@
 #include "../../include/scanlib_seats.h"
 #include "../../include/scanlib_population.h"
 #include "../../include/scanlib_league.h"
+#include "../../include/scanlib_league_env.h"
 #pragma GCC visibility pop
 #include <array>
 #include <utility>
@@ -1282,6 +1284,9 @@ static const std::array<race_env_observe_fn, FG_ROWS> race_env_observe_table =
 typedef void (*race_env_seat_observe_fn)(EnvParams, EnvBufs, RaceEnvBufs, SeatBufs, float *, float *, int *, float *);
 static const std::array<race_env_seat_observe_fn, FG_ROWS> race_env_seat_observe_table =
     rows_table<race_env_seat_observe_fn>([](auto rows) { return race_env_seat_observe_kernel<rows>; });
+typedef void (*race_env_league_observe_fn)(EnvParams, EnvBufs, RaceEnvBufs, LeagueEnvBufs, float *, float *, int *, float *);
+static const std::array<race_env_league_observe_fn, FG_ROWS> race_env_league_observe_table =
+    rows_table<race_env_league_observe_fn>([](auto rows) { return race_env_league_observe_kernel<rows>; });
 
 // a track (rl_track_create): the table of track_kernels.h in one device block, and the host's copy of cum
 struct rl_track {
@@ -1321,6 +1326,17 @@ struct rl_env {
     DevPtr<float> seat_mlp, seat_answer;
     DevPtr<int> seat_rows;
     int n_seat_rows = 0;
+    // league line-ups (rl_env_attach_league): the borrowed handles, the kernels' table (its pointers into the buffers
+    // below: the pending and live entries, the members' answers, the kept answers, the results) and the host's copy of
+    // the seat speeds.  lg_may_net: a pending or live entry may name a member (a host-set table since the attach held
+    // one, or a device setter ran): the network launch is made
+    bool league = false, lg_may_net = false;
+    rl_followgap *lg_g = nullptr;
+    rl_policy_pop *lg_pop = nullptr;
+    LeagueEnvBufs lg{};
+    DevPtr<int> lg_pending, lg_live;
+    DevPtr<float> lg_mlp, lg_answer;
+    DevPtr<unsigned long long> lg_results;
     bool ready = false;            // reset done and no launch failed since (read and written under mu only)
     bool foreign = false;          // the last launches went to a caller's stream: a host form waits for the device first
     uint64_t k = 0;                // calls since the last reset (the reset is slot 0)
@@ -1338,6 +1354,17 @@ static RaceEnvBufs race_env_bufs(rl_env *e)
 {
     return RaceEnvBufs{e->group, e->min_running, e->race_tick, e->race_episode, e->race_start_index, e->race_over};
 }
+
+// The Loop of a launching call of env e: the env's mutex first (its league is read under it), then Loop's order with
+// the league's FollowGap and population as the steering sources.
+struct EnvLoop {
+    std::unique_lock<std::mutex> own;
+    const Loop lp;
+    explicit EnvLoop(rl_env *e)
+        : own(e->mu), lp(nullptr, e->c, e->h, e->league ? e->lg_g : nullptr, nullptr, e->league ? e->lg_pop : nullptr)
+    {
+    }
+};
 
 // the scan's own refusals, checked before every launching call: a race env adds those of rl_calc_range_fan_cars
 static int env_scan_args(rl_env *e)
@@ -1500,6 +1527,21 @@ static int env_launch(rl_env *e, const Loop &lp, bool reset, uint64_t k, const f
                                     e->ep, b, rb, e->seats, d_obs, d_reward, d_done, d_aux);
         return rc ? rc : track_launch(e, d_reward, st);
     }
+    if (e->group > 0 && e->league) {     // ... with a league: the LEAGUE instances; the live entries are grouped by member
+        const RaceEnvBufs rb = race_env_bufs(e);     // behind phase A (which adopts them), the members' network behind the scan
+        int rc = pop_enter(e->lg_pop, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(race_env_league_step_kernel, dim3((N + 63) / 64), dim3(64), 0, st, e->ep, b, rb, e->lg, d_actions,
+                           d_start_index, reset ? 1 : 0);
+        if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "race_env_league_step_kernel launch failed");
+        if ((rc = league_group(e->lg_pop, e->lg_live, N, st))) return rc;
+        LoopScan scan{e->pose, N, e->prm.fov, B, e->ranges, e->lg_mlp, e->group, e->state, &e->outline};
+        scan.league = true;
+        scan.league_net = e->lg_may_net && e->lg.hi > 0 ? N : 0;
+        rc = lp.scan_then(scan, off, race_env_league_observe_table, e->group, "race_env_league_observe_kernel", st, e->ep, b,
+                          rb, e->lg, d_obs, d_reward, d_done, d_aux);
+        return rc ? rc : track_launch(e, d_reward, st);
+    }
     if (e->group > 0) {          // a race env: whole races spawn and end, and the cars see each other in the scan
         const RaceEnvBufs rb = race_env_bufs(e);
         hipLaunchKernelGGL(race_env_step_kernel, dim3((N + 63) / 64), dim3(64), 0, st, e->ep, b, rb, d_actions,
@@ -1560,7 +1602,8 @@ extern "C" int rl_env_reset_device(rl_env *e, uint64_t seed, const int *d_start_
     if (!e || !d_obs || !d_done) return fail(RL_ERR_INVALID, "rl_env_reset_device: null pointer");
     int rc = env_scan_args(e);
     if (rc) return rc;
-    const Loop lp(&e->mu, e->c, e->h, nullptr, nullptr);
+    const EnvLoop el(e);
+    const Loop &lp = el.lp;
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)hip_stream;
     if (st != (hipStream_t)e->c->stream) e->foreign = true;
@@ -1571,7 +1614,8 @@ extern "C" int rl_env_step_device(rl_env *e, const float *d_actions_n2, float *d
                                   float *d_aux_or_null, void *hip_stream)
 {
     if (!e || !d_actions_n2 || !d_obs || !d_reward || !d_done) return fail(RL_ERR_INVALID, "rl_env_step_device: null pointer");
-    const Loop lp(&e->mu, e->c, e->h, nullptr, nullptr);
+    const EnvLoop el(e);
+    const Loop &lp = el.lp;
     if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_step_device: reset the environment first (rl_env_reset)");
     int rc = env_scan_args(e);
     if (rc) return rc;
@@ -1604,7 +1648,8 @@ extern "C" int rl_env_reset(rl_env *e, uint64_t seed, const int *start_index_or_
                             start_index_or_null[i], e->n_starts);
     int rc = env_scan_args(e);
     if (rc) return rc;
-    const Loop lp(&e->mu, e->c, e->h, nullptr, nullptr);
+    const EnvLoop el(e);
+    const Loop &lp = el.lp;
     HIPCHK(hipSetDevice(e->device));
     if ((rc = env_settle(e))) return rc;
     HostCall hc(e->c->stream);
@@ -1618,7 +1663,8 @@ extern "C" int rl_env_reset(rl_env *e, uint64_t seed, const int *start_index_or_
 extern "C" int rl_env_step(rl_env *e, const float *actions_n2, float *obs, float *reward, int *done, float *aux_or_null)
 {
     if (!e || !actions_n2 || !obs || !reward || !done) return fail(RL_ERR_INVALID, "rl_env_step: null pointer");
-    const Loop lp(&e->mu, e->c, e->h, nullptr, nullptr);
+    const EnvLoop el(e);
+    const Loop &lp = el.lp;
     if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_step: reset the environment first (rl_env_reset)");
     const int N = e->prm.n_envs;
     int rc = env_scan_args(e);
@@ -1788,6 +1834,8 @@ extern "C" int rl_env_attach_seats(rl_env *e, rl_followgap *g_or_null, rl_policy
     if (!e) return fail(RL_ERR_INVALID, "rl_env_attach_seats: null pointer");
     std::scoped_lock lk(e->mu, e->c->mu);
     if (e->group < 1) return fail(RL_ERR_INVALID, "rl_env_attach_seats: not a race environment (rl_env_create_race)");
+    if (sp_or_null && e->league)
+        return fail(RL_ERR_INVALID, "rl_env_attach_seats: a league is attached (rl_env_attach_league): detach it first");
     const int N = e->prm.n_envs, P = e->group, B = e->prm.num_rays;
     SeatBufs S{};
     if (sp_or_null) {
@@ -1874,6 +1922,177 @@ extern "C" int rl_env_read_seats_device(rl_env *e, float *d_steer_n, void *hip_s
     if (d_steer_n)
         HIPCHK(hipMemcpyAsync(d_steer_n, e->seat_answer, (size_t)e->prm.n_envs * sizeof(float), hipMemcpyDeviceToDevice, st));
     return RL_OK;
+}
+
+// ---------------------------------------------------------------- league line-ups in the race env (include/scanlib_league_env.h)
+// the host forms' look at an entry table of env e with population pop, FollowGap g and the seat speeds `speed`
+static int league_env_entries(const char *fn, const rl_env *e, const rl_policy_pop *pop, const rl_followgap *g,
+                              const int *entry, const float *speed, bool *any_net)
+{
+    const int N = e->prm.n_envs, P = e->group;
+    *any_net = false;
+    for (int i = 0; i < N; ++i) {
+        const int m = entry[i];
+        if (m < -2 || m >= pop->n_members)
+            return fail(RL_ERR_INVALID, "%s: entry %d names member %d: not -2, -1 and not in the population's [0, %d)", fn, i, m,
+                        pop->n_members);
+        if (m == -1 && !g) return fail(RL_ERR_INVALID, "%s: entry %d is -1 (FollowGap), whose handle is null", fn, i);
+        if (m >= -1 && !std::isfinite(speed[i % P]))
+            return fail(RL_ERR_INVALID, "%s: the speed of seat %d must be finite (entry %d scripts a car of it)", fn, i % P, i);
+        *any_net |= m >= 0;
+    }
+    if (*any_net && e->prm.num_rays < pop->P.in_start + pop->P.dims[0])
+        return fail(RL_ERR_INVALID, "%s: scans of %d beams do not hold the policy's window [%d, %d)", fn, e->prm.num_rays,
+                    pop->P.in_start, pop->P.in_start + pop->P.dims[0]);
+    return RL_OK;
+}
+
+extern "C" int rl_env_attach_league(rl_env *e, rl_followgap *g_or_null, rl_policy_pop *pop, const int *entry_N_or_null,
+                                    const float *speed_P)
+{
+    if (!e) return fail(RL_ERR_INVALID, "rl_env_attach_league: null pointer");
+    std::scoped_lock lk(e->mu, e->c->mu);
+    if (e->group < 1) return fail(RL_ERR_INVALID, "rl_env_attach_league: not a race environment (rl_env_create_race)");
+    const size_t N = e->prm.n_envs;
+    LeagueEnvBufs L{};
+    bool any_net = false;
+    if (entry_N_or_null) {
+        if (!pop || !speed_P) return fail(RL_ERR_INVALID, "rl_env_attach_league: null pointer");
+        if (e->seated)
+            return fail(RL_ERR_INVALID, "rl_env_attach_league: seats are attached (rl_env_attach_seats): detach them first");
+        if (pop->device != e->device || (g_or_null && g_or_null->device != e->device))
+            return fail(RL_ERR_INVALID, "rl_env_attach_league: %s (device %d) and env (device %d) must share one device",
+                        pop->device != e->device ? "population" : "FollowGap",
+                        pop->device != e->device ? pop->device : g_or_null->device, e->device);
+        const int rc = league_env_entries("rl_env_attach_league", e, pop, g_or_null, entry_N_or_null, speed_P, &any_net);
+        if (rc) return rc;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipDeviceSynchronize());     // (launches in flight may still read the tables replaced below)
+    e->foreign = false;
+    e->league = false;
+    e->ready = false;                   // the line-ups and answers of the new league start at the next reset
+    e->lg_g = nullptr;
+    e->lg_pop = nullptr;
+    if (!entry_N_or_null) return RL_OK;
+    const size_t rows = (size_t)pop->n_members + 2;
+    int rc;
+    if ((rc = e->lg_pending.ensure(N)) || (rc = e->lg_live.ensure(N)) || (rc = e->lg_mlp.ensure(N)) ||
+        (rc = e->lg_answer.ensure(N)) || (rc = e->lg_results.ensure(rows * 8)))
+        return rc;
+    HIPCHK(hipMemcpy(e->lg_pending, entry_N_or_null, N * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(e->lg_results, 0, rows * 8 * sizeof(unsigned long long)));
+    const bool window = e->prm.num_rays >= pop->P.in_start + pop->P.dims[0];
+    L.lo = g_or_null ? -1 : 0;
+    L.hi = window ? pop->n_members : 0;
+    L.n_members = pop->n_members;
+    for (int k = 0; k < e->group; ++k) L.speed[k] = speed_P[k];
+    if (g_or_null) L.fg = g_or_null->P;
+    L.fg.size = e->prm.num_rays;
+    L.pending = e->lg_pending;
+    L.live = e->lg_live;
+    L.mlp = e->lg_mlp;
+    L.answer = e->lg_answer;
+    L.results = e->lg_results;
+    e->lg = L;
+    e->lg_g = g_or_null;
+    e->lg_pop = pop;
+    e->lg_may_net = any_net;
+    e->league = true;
+    return RL_OK;
+}
+
+static int env_league_attached(const rl_env *e, const char *name, bool need_reset)
+{
+    if (!e->league) return fail(RL_ERR_INVALID, "%s: no league attached (rl_env_attach_league)", name);
+    if (need_reset && !e->ready) return fail(RL_ERR_INVALID, "%s: reset the environment first (rl_env_reset)", name);
+    return RL_OK;
+}
+
+extern "C" int rl_env_set_league_entries(rl_env *e, const int *entry_N)
+{
+    if (!e || !entry_N) return fail(RL_ERR_INVALID, "rl_env_set_league_entries: null pointer");
+    std::scoped_lock lk(e->mu, e->c->mu);
+    int rc = env_league_attached(e, "rl_env_set_league_entries", false);
+    bool any_net = false;
+    if (rc || (rc = league_env_entries("rl_env_set_league_entries", e, e->lg_pop, e->lg_g, entry_N, e->lg.speed, &any_net)))
+        return rc;
+    HIPCHK(hipSetDevice(e->device));
+    if ((rc = env_settle(e))) return rc;
+    HostCall hc(e->c->stream);
+    if ((rc = hc.up((int *)e->lg_pending, entry_N, (size_t)e->prm.n_envs))) return rc;
+    e->lg_may_net |= any_net;
+    return hc.finish();
+}
+
+extern "C" int rl_env_set_league_entries_device(rl_env *e, const int *d_entry_N, void *hip_stream)
+{
+    if (!e || !d_entry_N) return fail(RL_ERR_INVALID, "rl_env_set_league_entries_device: null pointer");
+    std::scoped_lock lk(e->mu, e->c->mu);
+    const int rc = env_league_attached(e, "rl_env_set_league_entries_device", false);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (st != (hipStream_t)e->c->stream) e->foreign = true;
+    HIPCHK(hipMemcpyAsync(e->lg_pending, d_entry_N, (size_t)e->prm.n_envs * sizeof(int), hipMemcpyDeviceToDevice, st));
+    e->lg_may_net = true;               // (the host cannot look at these entries)
+    return RL_OK;
+}
+
+extern "C" int rl_env_read_league_steers(rl_env *e, float *steer_n)
+{
+    if (!e) return fail(RL_ERR_INVALID, "rl_env_read_league_steers: null pointer");
+    std::scoped_lock lk(e->mu, e->c->mu);
+    int rc = env_league_attached(e, "rl_env_read_league_steers", true);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    if ((rc = env_settle(e))) return rc;
+    HostCall hc(e->c->stream);
+    if ((rc = hc.down(steer_n, e->lg_answer, (size_t)e->prm.n_envs))) return rc;
+    return hc.finish();
+}
+
+extern "C" int rl_env_read_league_steers_device(rl_env *e, float *d_steer_n, void *hip_stream)
+{
+    if (!e) return fail(RL_ERR_INVALID, "rl_env_read_league_steers_device: null pointer");
+    std::scoped_lock lk(e->mu, e->c->mu);
+    const int rc = env_league_attached(e, "rl_env_read_league_steers_device", true);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (st != (hipStream_t)e->c->stream) e->foreign = true;
+    if (d_steer_n)
+        HIPCHK(hipMemcpyAsync(d_steer_n, e->lg_answer, (size_t)e->prm.n_envs * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return RL_OK;
+}
+
+extern "C" int rl_env_read_league_entries(rl_env *e, int *live_N_or_null, int *pending_N_or_null)
+{
+    if (!e) return fail(RL_ERR_INVALID, "rl_env_read_league_entries: null pointer");
+    std::scoped_lock lk(e->mu, e->c->mu);
+    int rc = env_league_attached(e, "rl_env_read_league_entries", live_N_or_null != nullptr);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    if ((rc = env_settle(e))) return rc;
+    HostCall hc(e->c->stream);
+    const size_t N = e->prm.n_envs;
+    if ((rc = hc.down(live_N_or_null, e->lg_live, N)) || (rc = hc.down(pending_N_or_null, e->lg_pending, N))) return rc;
+    return hc.finish();
+}
+
+extern "C" int rl_env_read_league_results(rl_env *e, int64_t *results, int clear)
+{
+    if (!e || !results) return fail(RL_ERR_INVALID, "rl_env_read_league_results: null pointer");
+    std::scoped_lock lk(e->mu, e->c->mu);
+    int rc = env_league_attached(e, "rl_env_read_league_results", true);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    if ((rc = env_settle(e))) return rc;
+    HostCall hc(e->c->stream);
+    const size_t n = ((size_t)e->lg.n_members + 2) * 8;
+    if ((rc = hc.down((unsigned long long *)results, e->lg_results, n))) return rc;
+    if (clear) HIPCHK(hipMemsetAsync(e->lg_results, 0, n * sizeof(unsigned long long), hc.st));
+    return hc.finish();
 }
 
 // ---------------------------------------------------------------- diagnostics: HBM stream probe

@@ -38,6 +38,9 @@ BOUNDS = [
     # ... with drivers in its seats: the scripted pair's select chain and FollowGap's passes behind the ballot spill nothing
     ("scan::race_env_seat_step_kernel", {"scratch": 0}),
     ("scan::race_env_seat_observe_kernel<", {"scratch": 0}),
+    # ... with a league: the per-car entry, the adoption at a spawn and the results' columns behind the barrier spill nothing
+    ("scan::race_env_league_step_kernel", {"scratch": 0}),
+    ("scan::race_env_league_observe_kernel<", {"scratch": 0}),
     # track progress: the f64 search, the wave's (value, index) minimum and lane 0's trigonometry spill nothing
     ("scan::track_kernel<", {"scratch": 0}),
     # the policy network: the micro-tile accumulators stay in registers

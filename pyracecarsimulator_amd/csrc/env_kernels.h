@@ -24,6 +24,11 @@
 // the crash ballot filled; the network from policy_mlp_rows_kernel, enqueued between the scan and phase B) into
 // SeatBufs::answer, and the next call's phase A takes a scripted car's pair from there instead of `actions`.  An env
 // without seats launches the plain instances, which hold none of this.
+// League line-ups (rl_env_attach_league, include/scanlib_league_env.h): the LEAGUE instances ask a per-car ENTRY where
+// the SEATS ones ask a per-seat bit.  Phase A copies a car's pending entry to its live one in the lane that spawns the
+// car; phase B's wave answers the scan with the live entry's driver (FollowGap as above; a member's answer from
+// policy_mlp_league_kernel over this call's grouping of the live entries) and, in the call that ends the race, adds
+// the race's results to the drivers' rows of LeagueEnvBufs::results with 64-bit vector atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -235,15 +240,45 @@ struct SeatBufs {
                                  // car that was not running after that scan's phase B
 };
 
+// the league of a race env: who drives car e (an entry per car, pending and live), the scripted cars' answers and the
+// drivers' results.  An entry in [lo, hi) is SCRIPTED: -1 FollowGap (lo = -1 only with a FollowGap handle), m >= 0
+// member m (hi = n_members only where the scans hold the network's window, else 0); every other value is the caller's.
+struct LeagueEnvBufs {
+    int lo, hi, n_members;
+    float speed[RACE_MAX_GROUP]; // the commanded speed of a scripted car in seat k
+    FollowGapParams fg;          // fg.size = num_rays
+    const int *pending;          // [N] the line-up a car adopts at its next spawn
+    int *live;                   // [N] the line-up the race runs with
+    const float *mlp;            // [N] the members' answers to this call's scans: the rows of the cars with a live entry >= 0
+    float *answer;               // [N] as SeatBufs::answer
+    unsigned long long *results; // [n_members + 2][8]: the members, FollowGap, the caller's cars
+};
+
+__device__ inline bool league_scripted(const LeagueEnvBufs &L, int entry) { return entry >= L.lo && entry < L.hi; }
+
+// car a beats car b of its race (include/scanlib_league_env.h): more ticks; as many and a survivor (done 2) against a
+// car that is out (1 or 3); as many, the same of the two classes and the larger gain.  Ties and NaN beat nobody.
+__device__ inline bool league_beats(int ticks_a, int done_a, double gain_a, int ticks_b, int done_b, double gain_b)
+{
+    if (ticks_a != ticks_b) return ticks_a > ticks_b;
+    const bool up_a = done_a == ENV_TRUNCATED, up_b = done_b == ENV_TRUNCATED;
+    const bool out_a = done_a == ENV_CRASHED || done_a == ENV_BAD_ACTION;
+    const bool out_b = done_b == ENV_CRASHED || done_b == ENV_BAD_ACTION;
+    if (up_a && out_b) return true;
+    return ((up_a && up_b) || (out_a && out_b)) && gain_a > gain_b;
+}
+
 // phase A of a race env, one lane per car.  Races straddle blocks, so no word is written by one lane and read by
 // another in here: R.over is read only, R.tick / R.episode / R.start_index are written by car 0's lane and read in
 // phase B, and every lane takes the race's episode from its own car's mirror.  SEATS: a car in a scripted seat that
 // reaches the action check takes (S.speed[k], S.answer[e]), the answer phase B of the call before left for it, and its
-// row of `actions` is not read.
-template <bool SEATS>
+// row of `actions` is not read.  LEAGUE: the lane that spawns a car copies the car's pending entry to its live one (a
+// running race is never re-seated), and a car whose live entry is scripted takes (L.speed[k], L.answer[e]).
+template <bool SEATS, bool LEAGUE = false>
 __device__ __forceinline__ void race_env_step_body(const EnvParams &p, const EnvBufs &b, const RaceEnvBufs &R,
                                                    const SeatBufs *S, const float *__restrict__ actions,
-                                                   const int *__restrict__ start_index, int reset)
+                                                   const int *__restrict__ start_index, int reset,
+                                                   const LeagueEnvBufs *L = nullptr)
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= p.n_envs) return;
@@ -251,9 +286,11 @@ __device__ __forceinline__ void race_env_step_body(const EnvParams &p, const Env
     CarState cs;
     if (reset) {
         race_env_spawn(p, b, R, e, 0, start_index, cs);
+        if (LEAGUE) L->live[e] = L->pending[e];
     } else if (R.over[r] != RACE_RUNNING) {
         if (p.auto_reset) {
             race_env_spawn(p, b, R, e, b.episode[e] + 1, nullptr, cs);
+            if (LEAGUE) L->live[e] = L->pending[e];
         } else {
             cs = drive_load_state(b.state + (size_t)e * 11);
             env_stand(b, e, ENV_FROZEN);         // a finished race stands
@@ -269,6 +306,11 @@ __device__ __forceinline__ void race_env_step_body(const EnvParams &p, const Env
 #pragma unroll
             for (int i = 0; i < RACE_MAX_GROUP; ++i) speed = i == k ? S->speed[i] : speed;
             env_act_pair(p, b, e, (double)speed, (double)S->answer[e], cs);
+        } else if (LEAGUE && league_scripted(*L, L->live[e])) {
+            float speed = 0.0f;
+#pragma unroll
+            for (int i = 0; i < RACE_MAX_GROUP; ++i) speed = i == k ? L->speed[i] : speed;
+            env_act_pair(p, b, e, (double)speed, (double)L->answer[e], cs);
         } else {
             env_act(p, b, e, actions, cs);
         }
@@ -290,17 +332,29 @@ __global__ __launch_bounds__(64) void race_env_seat_step_kernel(EnvParams p, Env
     race_env_step_body<true>(p, b, R, &S, actions, start_index, reset);
 }
 
+__global__ __launch_bounds__(64) void race_env_league_step_kernel(EnvParams p, EnvBufs b, RaceEnvBufs R, LeagueEnvBufs L,
+                                                                  const float *__restrict__ actions,
+                                                                  const int *__restrict__ start_index, int reset)
+{
+    race_env_step_body<false, true>(p, b, R, nullptr, actions, start_index, reset, &L);
+}
+
 // phase B of a race env: one workgroup per race, one wave per car (blockDim = 64 P, always P live waves).  Each wave
 // reaches its car's verdict as env_observe_kernel does, with the race's tick, parks the code in LDS, and after the
 // barrier applies the race's rule before the emit.  SEATS: a scripted seat's wave (w is the seat: wave-uniform) also
 // answers the scan with its driver, and S.answer[e] keeps the answer where the car runs on after the race's rule.
-template <int ROWS, bool SEATS>
+// LEAGUE: the wave asks its car's live entry (one car a wave: wave-uniform) instead; every wave parks its car's entry,
+// ticks and gain beside the code, and in the call that ends the race (over leaves RACE_RUNNING) adds its car's eight
+// columns to its driver's row.  The other cars' codes after the race's rule follow from codes[] and `over`.
+template <int ROWS, bool SEATS, bool LEAGUE = false>
 __device__ __forceinline__ void race_env_observe_body(const EnvParams &p, const EnvBufs &b, const RaceEnvBufs &R,
                                                       const SeatBufs *S, uint32_t *bits, float *__restrict__ obs,
                                                       float *__restrict__ reward, int *__restrict__ done_out,
-                                                      float *__restrict__ aux)
+                                                      float *__restrict__ aux, const LeagueEnvBufs *L = nullptr)
 {
     __shared__ int codes[RACE_MAX_GROUP];
+    __shared__ int lg_entry[LEAGUE ? RACE_MAX_GROUP : 1], lg_ticks[LEAGUE ? RACE_MAX_GROUP : 1];
+    __shared__ double lg_gain[LEAGUE ? RACE_MAX_GROUP : 1];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x, e = r * R.group + w;
     const float *row = b.ranges + (size_t)e * p.num_rays;
@@ -311,6 +365,16 @@ __device__ __forceinline__ void race_env_observe_body(const EnvParams &p, const 
     float answer = __builtin_nanf("");
     if (SEATS && ((S->scripted >> w) & 1u))
         answer = ((S->policy >> w) & 1u) ? S->mlp[e] : followgap_bits_eval<ROWS>(raw, S->fg, bits);
+    int entry = -2;
+    if (LEAGUE) {
+        entry = L->live[e];
+        if (league_scripted(*L, entry)) answer = entry >= 0 ? L->mlp[e] : followgap_bits_eval<ROWS>(raw, L->fg, bits);
+        if (lane == 0) {
+            lg_entry[w] = entry;
+            lg_ticks[w] = b.tick[e];
+            lg_gain[w] = b.state[(size_t)e * 11 + 8] - b.starts[((size_t)b.start_index[e] * R.group + w) * 11 + 8];
+        }
+    }
     // a race spawns as a whole: a fresh car means a fresh race, whatever R.over still holds from the last episode
     const int over0 = b.phase[e] == ENV_FRESH ? RACE_RUNNING : R.over[r];
     if (lane == 0) codes[w] = done;
@@ -325,8 +389,30 @@ __device__ __forceinline__ void race_env_observe_body(const EnvParams &p, const 
         const int over = truncated ? RACE_TRUNCATED : running < R.min_running ? RACE_ATTRITION : RACE_RUNNING;
         if (over == RACE_ATTRITION && done == ENV_RUNNING) done = ENV_TRUNCATED;    // it survived: its reward stays
         if (threadIdx.x == 0) R.over[r] = over;
+        if (LEAGUE && over != RACE_RUNNING && lane < 8) {       // the race ends in this call: lane c adds column c
+            const bool callers_car = !league_scripted(*L, entry);
+            int beaten = 0, callers = 0, callers_beaten = 0, callers_won = 0;
+            for (int k = 0; k < R.group; ++k) {
+                if (k == w) continue;
+                const int dk = over == RACE_ATTRITION && codes[k] == ENV_RUNNING ? ENV_TRUNCATED : codes[k];
+                const bool win = league_beats(lg_ticks[w], done, lg_gain[w], lg_ticks[k], dk, lg_gain[k]);
+                const bool caller = !league_scripted(*L, lg_entry[k]);
+                beaten += win;
+                callers += caller;
+                callers_beaten += caller && win;
+                callers_won += caller && league_beats(lg_ticks[k], dk, lg_gain[k], lg_ticks[w], done, lg_gain[w]);
+            }
+            const int col[8] = {1, done == ENV_CRASHED || done == ENV_BAD_ACTION, lg_ticks[w], R.group - 1, beaten, callers,
+                                callers_beaten, callers_won};
+            int v = 0;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) v = c == lane ? col[c] : v;
+            const int row = callers_car ? L->n_members + 1 : entry < 0 ? L->n_members : entry;
+            if (v) atomicAdd(L->results + 8 * (size_t)row + lane, (unsigned long long)v);
+        }
     }
     if (SEATS && lane == 0) S->answer[e] = done == ENV_RUNNING ? answer : __builtin_nanf("");
+    if (LEAGUE && lane == 0) L->answer[e] = done == ENV_RUNNING ? answer : __builtin_nanf("");
     env_emit(p, b, e, lane, row, done, rw, obs, reward, done_out, aux);
 }
 
@@ -349,6 +435,17 @@ __global__ __launch_bounds__(64 * RACE_MAX_GROUP) void race_env_seat_observe_ker
 {
     __shared__ uint32_t bits[RACE_MAX_GROUP][2 * ROWS + 4];     // FollowGap's bit rows, one set per wave
     race_env_observe_body<ROWS, true>(p, b, R, &S, bits[threadIdx.x >> 6], obs, reward, done_out, aux);
+}
+
+template <int ROWS>
+__global__ __launch_bounds__(64 * RACE_MAX_GROUP) void race_env_league_observe_kernel(EnvParams p, EnvBufs b, RaceEnvBufs R,
+                                                                                      LeagueEnvBufs L, float *__restrict__ obs,
+                                                                                      float *__restrict__ reward,
+                                                                                      int *__restrict__ done_out,
+                                                                                      float *__restrict__ aux)
+{
+    __shared__ uint32_t bits[RACE_MAX_GROUP][2 * ROWS + 4];     // FollowGap's bit rows, one set per wave
+    race_env_observe_body<ROWS, false, true>(p, b, R, nullptr, bits[threadIdx.x >> 6], obs, reward, done_out, aux, &L);
 }
 
 }  // namespace scan

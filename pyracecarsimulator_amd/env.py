@@ -29,6 +29,11 @@ distance travelled.
 ``RaceEnv`` also takes ``seats``: a driver per seat of the race (``seats.py``, include/scanlib_seats.h).  A car in a seat
 with a ``PyFollowGap`` or a ``Policy`` is steered on the device by that driver's answer to its own full scan of the call
 before, at ``seat_speed``; only the seats left None read the caller's actions.
+
+``RaceEnv`` takes ``league`` instead: a ``PolicyPopulation`` and one entry per car (``league.py``,
+include/scanlib_league_env.h), so that every race has its own line-up of members, FollowGap and caller's cars.
+``set_entries`` hands over new line-ups at any time (a race adopts them when it spawns), and ``league_results`` reads
+the running tally of who beat whom.
 """
 from __future__ import annotations
 
@@ -300,12 +305,20 @@ class RaceEnv(DriveEnv):
     ``Policy`` (at most one object of each kind) drives car k of every race itself: at each step such a car takes
     (``seat_speed``, its driver's answer to the car's own scan of the call before: all ``num_rays`` beams, whatever
     ``obs_window`` shows the caller) in place of its row of ``actions``, which is not read.  ``seat_speed``: a scalar or
-    one value per seat.  ``seat_steers()`` reads the answers."""
+    one value per seat.  ``seat_steers()`` reads the answers.
+
+    ``league``: ``(pop, entries)`` instead of ``seats`` — a ``PolicyPopulation`` and one entry per car, int
+    (n_races, P): ``league.CALLER`` (-2), ``league.FOLLOWGAP`` (-1: ``followgap``) or member m >= 0 of ``pop``;
+    ``seat_speed`` is the speed of the scripted cars of a seat.  See ``attach_league``, ``set_entries``, ``entries``,
+    ``league_steers`` and ``league_results``."""
+    league = None                 # (pop, followgap, seat speeds) while a league is attached
 
     def __init__(self, method, starts, n_races, num_rays, fov, edge, crash_thresh, *, min_running=1, seats=None,
-                 seat_speed=2.0, **kw):
+                 seat_speed=2.0, league=None, followgap=None, **kw):
         checks = {k: kw[k] for k in ("substeps", "obs_window", "obs_clip", "obs_scale", "max_ticks", "steer_clip",
                                      "crash_reward", "dt") if k in kw}
+        if seats is not None and league is not None:
+            raise ValueError("seats and league exclude each other: a league names every car's driver")
         st, _, _, P = race_env_args(n_races, num_rays, starts, edge, min_running, **checks)
         self._group, self._min_running, self._races = P, int(min_running), int(n_races)
         super().__init__(method, st.reshape(-1, 11), self._races * P, num_rays, fov, edge, crash_thresh, **kw)
@@ -314,6 +327,8 @@ class RaceEnv(DriveEnv):
         self.seats = None
         if seats is not None:
             self.attach_seats(seats, seat_speed)
+        if league is not None:
+            self.attach_league(league[0], league[1], followgap, seat_speed)
 
     def _create(self, car, method, p, ed, st):
         rp = _lib.RaceEnvParams()
@@ -350,6 +365,8 @@ class RaceEnv(DriveEnv):
         """Give the seats their drivers (``seats`` and ``seat_speed`` as the constructor takes them; None: detach, every
         seat is the caller's again).  The env needs a ``reset`` afterwards."""
         from .seats import seat_env_args
+        if seats is not None and self.league is not None:
+            raise ValueError("a league is attached (attach_league(None) first)")
         if seats is None:
             _lib.call("rl_env_attach_seats", self, None, None, None)
             self.seats = None
@@ -375,6 +392,83 @@ class RaceEnv(DriveEnv):
             out = np.empty(self._n, np.float32)
             _lib.call("rl_env_read_seats", self, out)
         return self._rows(out)
+
+    # -- league line-ups ----------------------------------------------------------------
+    def attach_league(self, pop, entries=None, followgap=None, seat_speed=2.0):
+        """Give every car its driver: ``entries`` int (n_races, P) with ``league.CALLER`` (-2, the caller's actions),
+        ``league.FOLLOWGAP`` (-1, ``followgap``) or m >= 0, member m of ``pop`` (a ``PolicyPopulation``).  A scripted
+        car (an entry >= -1) takes (``seat_speed`` of its seat, its driver's answer to the car's own full scan of the
+        call before) in place of its row of ``actions``.  ``pop`` None (or ``entries`` None) detaches the league.  The
+        env needs a ``reset`` afterwards; the results start at zero."""
+        from . import league as LG
+        if pop is None or entries is None:
+            _lib.call("rl_env_attach_league", self, None, None, None, None)
+            self.league = None
+            return
+        if self.seats is not None:
+            raise ValueError("seats are attached (attach_seats(None) first)")
+        spd = LG.seat_speeds(seat_speed, self._group)
+        ent = LG.league_env_args(entries, self._races, self._group, pop, followgap, self.params.num_rays, spd)
+        _lib.call("rl_env_attach_league", self, followgap, pop, ent, np.where(np.isfinite(spd), spd, np.float32(0)))
+        self.league = (pop, followgap, spd)       # (borrowed by the library: kept alive here)
+        self._league_torch = None
+
+    def _need_league(self):
+        if self.league is None:
+            raise ValueError("no league attached (attach_league)")
+        return self.league
+
+    def set_entries(self, entries):
+        """Replace the pending line-ups: every race adopts its cars' entries when it next spawns (a reset or an
+        auto-reset re-spawn), and a running race keeps the line-up it has.  A NumPy array (n_races, P) takes the host
+        form (checked, synchronous); a torch int32 tensor (n_races, P) or (n_envs,) on the env's device takes the
+        enqueued form on the current stream, where an entry the checks would refuse behaves as ``league.CALLER``."""
+        from . import league as LG
+        pop, fg, spd = self._need_league()
+        if self._is_tensor(entries):
+            if tuple(entries.shape) == (self._races, self._group):
+                entries = entries.reshape(self._n)
+            self._check_tensor(entries, (self._n,), "int32", "entries")
+            _lib.call("rl_env_set_league_entries_device", self, entries.data_ptr(), self._stream())
+            return
+        ent = LG.league_env_args(entries, self._races, self._group, pop, fg, self.params.num_rays, spd)
+        _lib.call("rl_env_set_league_entries", self, ent)
+
+    def entries(self):
+        """The line-ups as a dict of ``live`` (what every race runs with) and ``pending`` (what it adopts at its next
+        spawn), int32 (n_races, P).  Waits for the device."""
+        self._need_league()
+        live, pending = np.empty(self._n, np.int32), np.empty(self._n, np.int32)
+        _lib.call("rl_env_read_league_entries", self, live, pending)
+        return dict(live=self._rows(live), pending=self._rows(pending))
+
+    def league_steers(self, on_device=False):
+        """``seat_steers`` for a league: each scripted car's driver's answer to its latest scan, float32 (n_races, P); NaN
+        for a caller's car and for one that is not running after that scan."""
+        self._need_league()
+        if on_device:
+            import torch
+            if getattr(self, "_league_torch", None) is None:
+                self._league_torch = torch.empty(self._n, dtype=torch.float32, device=torch.device("cuda", self.device))
+            out = self._league_torch
+            _lib.call("rl_env_read_league_steers_device", self, out.data_ptr(), self._stream())
+        else:
+            out = np.empty(self._n, np.float32)
+            _lib.call("rl_env_read_league_steers", self, out)
+        return self._rows(out)
+
+    def league_results(self, clear=False):
+        """The tally of the races that finished since the attach (or the last ``clear=True``): a dict with one int64
+        (n_members,) array per column of ``league.RESULT_COLUMNS`` — ``entered`` (cars in finished races), ``out`` (of
+        them, done 1 or 3), ``ticks`` (their summed ticks), ``faced`` / ``beaten`` (cars of their own races),
+        ``callers_faced`` / ``callers_beaten`` / ``callers_won`` (the caller's cars among them, and those that beat the
+        driver's car) — and the same columns for FollowGap's cars (``followgap``) and the caller's (``caller``) as dicts
+        of ints.  A reset does not clear it."""
+        from . import league as LG
+        pop = self._need_league()[0]
+        raw = np.zeros((pop.n_members + 2, 8), np.int64)
+        _lib.call("rl_env_read_league_results", self, raw, 1 if clear else 0)
+        return LG.results_dict(raw, pop.n_members)
 
     def track_state(self, on_device=False):
         """``DriveEnv.track_state`` as (n_races, P, ...); ``rank`` 0 leads its race."""

@@ -301,8 +301,11 @@ class RacecarSimulator:
         ttc_thresh and scan_dist_to_base, spawning from the line-ups ``starts`` float64 (M, P, 11): the tick of
         ``raceFollowGapMany`` with the (speed, steer) of every car supplied by the caller.  ``kw``: ``RaceEnv``'s keyword
         arguments (min_running and ``DriveEnv``'s, the track keywords included; ``seats`` and ``seat_speed`` put a
-        driver into a seat, "fg" standing for this simulator's own FollowGap driver)."""
+        driver into a seat, "fg" standing for this simulator's own FollowGap driver; ``league=(pop, entries)`` gives
+        every car its own driver, -1 entries going to ``followgap`` or, without one, to the simulator's own)."""
         from .env import RaceEnv
+        if kw.get("league") is not None and kw.get("followgap") is None and (np.asarray(kw["league"][1]) == -1).any():
+            kw["followgap"] = self._mcts_source("fg", None)
         if kw.get("seats") is not None:
             kw["seats"] = [self._mcts_source("fg", None) if isinstance(d, str) and d == "fg" else d for d in kw["seats"]]
         kw.setdefault("car", self.car)
