@@ -1,6 +1,6 @@
 // abi_car.hip — what sits in front of and behind the scan path in libscan_amd.so (C ABI: include/scanlib.h; SURVEY.md
-// section 8f): the MCTS roll-out generator, FollowGap, the policy network, the race scan; the closed-loop session (loop_args
-// and Loop: handle checks, locks, launch arguments, scan-then-consume) with its users drive_loop, rl_env_* and rl_mcts_*;
+// section 8f): the MCTS roll-out generator, FollowGap, the policy network, the race scan; the closed-loop session (loop_args,
+// SteerSource and Loop: handle checks, who steers, locks, scan-then-consume) with its users drive_loop, rl_env_*, rl_mcts_*;
 // track-guided planning (include/scanlib_track_plan.h: the planner's track, rl_car_rollout_track); per-seat drivers
 // (include/scanlib_seats.h: rl_car_race_seats, rl_env_attach_seats); policy populations (include/scanlib_population.h:
 // rl_policy_pop_*, rl_car_drive_population); league races (include/scanlib_league.h: rl_policy_pop_eval_rows,
@@ -350,11 +350,18 @@ static int race_outline(const rl_map *m, double length, double width, OutlinePar
     return RL_OK;
 }
 
+static int race_group(int group)
+{
+    if (group < 1 || group > RACE_MAX_GROUP)
+        return fail(RL_ERR_INVALID, "group must lie in [1, %d] cars (got %d)", RACE_MAX_GROUP, group);
+    return RL_OK;
+}
+
 static int race_args(rl_method *h, long n_groups, int group, int num_rays)
 {
     if (!h->reps.empty()) return fail(RL_ERR_INVALID, "races are single-device only: pass an ordinary (not multi-device) method");
-    if (group < 1 || group > RACE_MAX_GROUP)
-        return fail(RL_ERR_INVALID, "group must lie in [1, %d] cars (got %d)", RACE_MAX_GROUP, group);
+    int rc = race_group(group);
+    if (rc) return rc;
     if (n_groups < 0) return fail(RL_ERR_INVALID, "n_groups must be >= 0 (got %ld)", n_groups);
     if (num_rays < 10 || num_rays > RACE_MAX_RAYS)
         return fail(RL_ERR_INVALID, "num_rays must lie in [10, %d] (got %d)", RACE_MAX_RAYS, num_rays);
@@ -541,13 +548,19 @@ extern "C" void rl_policy_destroy(rl_policy *p)
     delete p;
 }
 
+// scans of `size` beams hold the network's input window (fn: the callers that name themselves in this message)
+static int policy_window(const PolicyParams &P, int size, const char *fn = nullptr)
+{
+    if (size < P.in_start + P.dims[0])
+        return fail(RL_ERR_INVALID, "%s%sscans of %d beams do not hold the policy's window [%d, %d)", fn ? fn : "", fn ? ": " : "",
+                    size, P.in_start, P.in_start + P.dims[0]);
+    return RL_OK;
+}
+
 static int policy_args(const rl_policy *p, int n_scans, int size)
 {
     if (n_scans < 0) return fail(RL_ERR_INVALID, "n_scans must be >= 0 (got %d)", n_scans);
-    if (size < p->P.in_start + p->P.dims[0])
-        return fail(RL_ERR_INVALID, "scans of %d beams do not hold the policy's window [%d, %d)", size, p->P.in_start,
-                    p->P.in_start + p->P.dims[0]);
-    return RL_OK;
+    return policy_window(p->P, size);
 }
 
 static int policy_launch(rl_policy *p, const float *d_scans, int n_scans, int size, float *d_steers, hipStream_t st)
@@ -703,12 +716,10 @@ static int pop_range(const char *fn, const rl_policy_pop *p, int first, int n)
 
 static int pop_args(const char *fn, const rl_policy_pop *p, int first, int n, int E, int size)
 {
-    const int rc = pop_range(fn, p, first, n);
+    int rc = pop_range(fn, p, first, n);
     if (rc) return rc;
     if (E < 1) return fail(RL_ERR_INVALID, "%s: cars_per_member must be >= 1 (got %d)", fn, E);
-    if (size < p->P.in_start + p->P.dims[0])
-        return fail(RL_ERR_INVALID, "scans of %d beams do not hold the policy's window [%d, %d)", size, p->P.in_start,
-                    p->P.in_start + p->P.dims[0]);
+    if ((rc = policy_window(p->P, size))) return rc;
     const long cars = (long)n * E;     // (n, E < 2^31: no overflow; then cars < 2^31 before the second product)
     if (cars >= (1L << 31) || cars * std::max(size, 1) >= (1L << 31))
         return fail(RL_ERR_INVALID, "%s: %d members of %d cars, scans of %d beams: their product must stay below 2^31", fn, n,
@@ -861,21 +872,32 @@ static int league_launch(rl_policy_pop *p, int n, const float *d_scans, int size
 static int league_rows_args(const char *fn, const rl_policy_pop *p, int n, int size)
 {
     if (n < 0) return fail(RL_ERR_INVALID, "%s: n must be >= 0 (got %d)", fn, n);
-    if (size < p->P.in_start + p->P.dims[0])
-        return fail(RL_ERR_INVALID, "scans of %d beams do not hold the policy's window [%d, %d)", size, p->P.in_start,
-                    p->P.in_start + p->P.dims[0]);
+    const int rc = policy_window(p->P, size);
+    if (rc) return rc;
     if ((long)n * std::max(size, 1) >= (1L << 31))
         return fail(RL_ERR_INVALID, "%s: %d scans of %d beams: their product must stay below 2^31", fn, n, size);
     return RL_OK;
 }
 
-// every entry a member of the population or -1
-static int league_entries(const char *fn, const rl_policy_pop *p, const int *entry, size_t n)
+// the entry walk of every league call: each of the n entries names a member of the population or a code from `lowest`
+// up (-1: FollowGap, or a row left alone; -2, the env: the caller's car).  fg: a -1 entry has a FollowGap handle to ask
+// (callers that word this refusal themselves pass true).  speed (the env, else null): the speed of seat i % group, which
+// a scripted car of it needs finite.  *n_net: the entries that name a member.
+static int league_entries(const char *fn, const int *entry, size_t n, int n_members, int lowest, bool fg,
+                          const float *speed = nullptr, int group = 1, size_t *n_net = nullptr)
 {
-    for (size_t i = 0; i < n; ++i)
-        if (entry[i] < -1 || entry[i] >= p->n_members)
-            return fail(RL_ERR_INVALID, "%s: entry %zu names member %d: not -1 and not in the population's [0, %d)", fn, i,
-                        entry[i], p->n_members);
+    size_t net = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const int m = entry[i];
+        if (m < lowest || m >= n_members)
+            return fail(RL_ERR_INVALID, "%s: entry %zu names member %d: not %s and not in the population's [0, %d)", fn, i, m,
+                        lowest < -1 ? "-2, -1" : "-1", n_members);
+        if (m == -1 && !fg) return fail(RL_ERR_INVALID, "%s: entry %zu is -1 (FollowGap), whose handle is null", fn, i);
+        if (speed && m >= -1 && !std::isfinite(speed[i % group]))
+            return fail(RL_ERR_INVALID, "%s: the speed of seat %zu must be finite (entry %zu scripts a car of it)", fn, i % group, i);
+        net += m >= 0;
+    }
+    if (n_net) *n_net = net;
     return RL_OK;
 }
 
@@ -884,7 +906,8 @@ extern "C" int rl_policy_pop_eval_rows(rl_policy_pop *p, int n, const int *membe
 {
     if (!p || (n > 0 && (!member_n || !scans || !steers))) return fail(RL_ERR_INVALID, "rl_policy_pop_eval_rows: null pointer");
     int rc = league_rows_args("rl_policy_pop_eval_rows", p, n, size);
-    if (rc || n == 0 || (rc = league_entries("rl_policy_pop_eval_rows", p, member_n, n))) return rc;
+    if (rc || n == 0 || (rc = league_entries("rl_policy_pop_eval_rows", member_n, n, p->n_members, -1, true)))
+        return rc;
     std::lock_guard<std::mutex> lk(p->mu);
     if ((rc = pop_enter(p, p->stream))) return rc;
     HostCall hc(p->stream);
@@ -934,9 +957,87 @@ static int loop_args(const char *name, const rl_car *c, const rl_method *h, cons
     return RL_OK;
 }
 
-// one scan of a closed loop: n poses (a race: n / group races over the cars' f64 states, 11 doubles a car) into `ranges`,
-// and into `mlp` the policy's answers when the loop's source is one; with seats, `net` answers the n_rows scans `rows`
-// names and no others
+// Who answers the scans of a closed loop, the handles it borrows and the one launch it puts between a scan and its
+// consumer.  Loop locks the handles a source NAMES: g in FollowGap's slot, then p or pop in the network's.  Per kind:
+//   NOBODY      the plain and the race env, the planner's random source: no handle, no lock, no launch
+//   FOLLOWGAP   g, locked; no launch (the consumer kernel holds FollowGap)
+//   POLICY      p, locked; its network over every scan
+//   SEATS       `net` over the rows of the cars in the `policy_seats` of every race of `group` (the list: *rows).  A
+//               roll-out (rl_car_race_seats) names g and p, each only where a seat uses it, and both are locked.  A race
+//               env (rl_env_attach_seats) names NEITHER and so takes neither mutex: it copied FollowGap's parameters at
+//               the attach and borrows the policy's weights through `net` alone
+//   POPULATION  pop, locked; members [first, first + n) over E scans each
+//   LEAGUE      pop over the grouping of the call's entries (league_group has run on it), locked, and g where an entry
+//               may be -1, locked: the roll-out (rl_car_race_league; `entry`: its host table) and the race env
+//               (rl_env_attach_league) both take both.  n_net: the scans to give the network, 0 for no launch
+struct SteerSource {
+    enum Kind { NOBODY, FOLLOWGAP, POLICY, SEATS, POPULATION, LEAGUE };
+    Kind kind = NOBODY;
+    rl_followgap *g = nullptr;
+    rl_policy *p = nullptr;
+    rl_policy_pop *pop = nullptr;
+    const PolicyParams *net = nullptr;
+    uint32_t policy_seats = 0;
+    int group = 0;
+    const DevPtr<int> *rows = nullptr;
+    int first = 0, n = 0, E = 0;
+    const int *entry = nullptr;
+    int n_net = 0;
+
+    static SteerSource followgap(rl_followgap *g) { return {FOLLOWGAP, g}; }
+    static SteerSource policy(rl_policy *p) { return {POLICY, nullptr, p}; }
+    static SteerSource seats(rl_followgap *g, rl_policy *p, const PolicyParams *net, uint32_t policy_seats, int group,
+                             const DevPtr<int> *rows)
+    {
+        return {SEATS, g, p, nullptr, policy_seats ? net : nullptr, policy_seats, group, rows};
+    }
+    static SteerSource population(rl_policy_pop *pop, int first, int n, int E)
+    {
+        SteerSource s{POPULATION, nullptr, nullptr, pop};
+        s.first = first, s.n = n, s.E = E;
+        return s;
+    }
+    static SteerSource league(rl_followgap *g, rl_policy_pop *pop, const int *entry, int n_net)
+    {
+        SteerSource s{LEAGUE, g, nullptr, pop};
+        s.entry = entry, s.n_net = n_net;
+        return s;
+    }
+    bool empty() const { return !g && !p && !pop; }
+
+    // loop_args for the handles named: FollowGap's device first, then the policy's
+    int check(const char *name, const rl_car *c, const rl_method *h, long units, int num_rays) const
+    {
+        int rc = loop_args(name, c, h, g, g ? nullptr : p, units, num_rays);
+        if (rc == RL_OK && g && p) rc = loop_args(name, c, h, nullptr, p, units, num_rays);
+        return rc;
+    }
+    // the population's device, and the policy's window in n_scans scans of num_rays beams (a population's window is its
+    // entry point's to check: pop_args, rl_car_race_league)
+    int fits(const char *name, const rl_car *c, int n_scans, int num_rays) const
+    {
+        if (pop && pop->device != c->device)
+            return fail(RL_ERR_INVALID, "%s: car (device %d) and population (device %d) must share one device", name, c->device,
+                        pop->device);
+        return p ? policy_args(p, n_scans, num_rays) : (int)RL_OK;
+    }
+    // the network's answers to the n scans in `ranges`, into mlp [n] (SEATS, LEAGUE: the rows it drives and no others)
+    int answer(const float *ranges, int n_scans, int num_rays, float *mlp, hipStream_t st) const
+    {
+        switch (kind) {
+        case POLICY: return policy_launch(p, ranges, n_scans, num_rays, mlp, st);
+        case SEATS:
+            if (!net) return RL_OK;
+            return policy_rows_launch(*net, ranges, *rows, n_scans / group * __builtin_popcount(policy_seats), num_rays, mlp, st);
+        case POPULATION: return pop_launch(pop, first, n, E, ranges, num_rays, mlp, st);
+        case LEAGUE: return league_launch(pop, n_net ? n_scans : 0, ranges, num_rays, mlp, st);
+        default: return RL_OK;
+        }
+    }
+};
+
+// one scan of a closed loop: n poses (a race: n / group races over the cars' f64 states, 11 doubles a car) into `ranges`;
+// mlp: where the loop's source puts its answers
 struct LoopScan {
     const float *poses;
     int n;
@@ -946,38 +1047,30 @@ struct LoopScan {
     int group;                      // 0: every pose scans alone with the method's planner
     const double *cars;
     const OutlineParams *outline;
-    const PolicyParams *net = nullptr;
-    const int *rows = nullptr;
-    int n_rows = 0;
-    int pop_first = 0, pop_n = 0, pop_E = 0;    // a population as the source: members [pop_first, pop_first + pop_n), n = pop_n pop_E
-    bool league = false;                        // a league: the population's members over the grouping of the call's entries
-    int league_net = 0;                         // ... of which this many name a member (0: no network launch)
 };
 
 // One launching call of a closed loop.  Locks in ONE order: the owner's mutex (rl_env::mu, rl_mcts::mu; none for the
-// roll-outs), the car's, the method's, the steering sources' (FollowGap's, then the policy's: rl_car_race_seats holds
-// both; a population's mutex takes the policy's place), then the map's tables_mu shared.  The method's
+// roll-outs), the car's, the method's, the source's (FollowGap's, then the policy's or the population's: SteerSource
+// says which a kind names), then the map's tables_mu shared.  The method's
 // settings are read under its mutex and never written: `base` is the noise offset the loop walks from, and every launch
 // is told its own offset and plain stores (the consumer kernels read the ranges right after the scan).  `ready` of an
 // owner is read and written inside only.
 struct Loop {
     rl_method *const h;
-    rl_policy *const p;
-    rl_policy_pop *const pop;
+    const SteerSource src;
     std::unique_lock<std::mutex> lo, lc, lh, ls, ln;
     std::shared_lock<std::shared_mutex> ml;
     const uint64_t base;
     static std::unique_lock<std::mutex> held(std::mutex *m) { return m ? std::unique_lock(*m) : std::unique_lock<std::mutex>(); }
-    Loop(std::mutex *owner, rl_car *c, rl_method *h_, rl_followgap *g, rl_policy *p_, rl_policy_pop *pop_ = nullptr)
-        : h(h_), p(p_), pop(pop_), lo(held(owner)), lc(c->mu), lh(h_->mu), ls(held(g ? &g->mu : nullptr)),
-          ln(held(p_ ? &p_->mu : pop_ ? &pop_->mu : nullptr)), ml(h_->map->tables_mu), base(h_->ray_offset)
+    Loop(std::mutex *owner, rl_car *c, rl_method *h_, const SteerSource &s)
+        : h(h_), src(s), lo(held(owner)), lc(c->mu), lh(h_->mu), ls(held(s.g ? &s.g->mu : nullptr)),
+          ln(held(s.p ? &s.p->mu : s.pop ? &s.pop->mu : nullptr)), ml(h_->map->tables_mu), base(h_->ray_offset)
     {
     }
     LaunchArgs at(uint64_t off) const { return {off, true, h->timing}; }
 
-    // scan-then-consume on st: the scan at noise offset `off`, the network when the source is a policy (a population:
-    // every member's network in its one launch), then the ROWS
-    // instantiation of `table` for num_rays, one wave per unit and per_wg units per workgroup
+    // scan-then-consume on st: the scan at noise offset `off`, the source's answers, then the ROWS instantiation of
+    // `table` for num_rays, one wave per unit and per_wg units per workgroup
     template <class Fn, class... Args>
     int scan_then(const LoopScan &s, uint64_t off, const std::array<Fn, FG_ROWS> &table, int per_wg, const char *kernel,
                   hipStream_t st, const Args &...args) const
@@ -986,16 +1079,32 @@ struct Loop {
         int rc = s.group > 0 ? launch_race(h, a, s.poses, s.cars, 11, s.n / s.group, s.group, *s.outline, s.fov, s.num_rays,
                                            s.ranges, nullptr, nullptr, st)
                              : launch_fan(h, FanCall{a, s.poses, s.n, s.fov, s.num_rays, s.ranges, nullptr, nullptr, nullptr, st});
-        if (rc == RL_OK && s.net) rc = policy_rows_launch(*s.net, s.ranges, s.rows, s.n_rows, s.num_rays, s.mlp, st);
-        else if (rc == RL_OK && p) rc = policy_launch(p, s.ranges, s.n, s.num_rays, s.mlp, st);
-        else if (rc == RL_OK && pop && s.league) rc = league_launch(pop, s.league_net ? s.n : 0, s.ranges, s.num_rays, s.mlp, st);
-        else if (rc == RL_OK && pop) rc = pop_launch(pop, s.pop_first, s.pop_n, s.pop_E, s.ranges, s.num_rays, s.mlp, st);
-        if (rc) return rc;
+        if (rc || (rc = src.answer(s.ranges, s.n, s.num_rays, s.mlp, st))) return rc;
         table[(s.num_rays + 63) / 64 - 1]<<<dim3((s.n + per_wg - 1) / per_wg), dim3(64 * per_wg), 0, st>>>(args...);
         if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "%s launch failed", kernel);
         return RL_OK;
     }
 };
+
+// one seat's driver code: FollowGap or the policy, whose handle must be there (the caller's code is the caller's to sort out)
+static int seat_code(const char *fn, int k, int d, const rl_followgap *g, const rl_policy *p)
+{
+    if (d != RL_SEAT_FOLLOWGAP && d != RL_SEAT_POLICY) return fail(RL_ERR_INVALID, "%s: seat %d: unknown driver code %d", fn, k, d);
+    const bool net = d == RL_SEAT_POLICY;
+    if (!(net ? (const void *)p : (const void *)g))
+        return fail(RL_ERR_INVALID, "%s: seat %d is driven by %s, whose handle is null", fn, k, net ? "the policy" : "FollowGap");
+    return RL_OK;
+}
+
+// the cars in the seats of `mask`, race by race: what SteerSource::rows holds on the device
+static std::vector<int> seat_row_list(uint32_t mask, int n_races, int group)
+{
+    std::vector<int> rows;
+    for (int r = 0; r < n_races && mask; ++r)
+        for (int k = 0; k < group; ++k)
+            if ((mask >> k) & 1u) rows.push_back(r * group + k);
+    return rows;
+}
 
 // ---------------------------------------------------------------- closed-loop roll-outs (drive_kernels.h)
 typedef void (*drive_tick_fn)(DriveParams, DriveBufs, int);
@@ -1008,7 +1117,7 @@ static const std::array<drive_tick_fn, FG_ROWS> seat_tick_table =
 static const std::array<drive_tick_fn, FG_ROWS> league_tick_table =
     rows_table<drive_tick_fn>([](auto rows) { return drive_tick_kernel<rows, LeagueSteer>; });
 
-// what the three roll-out entry points share of their arguments (include/scanlib.h names them)
+// what the roll-out entry points share of their arguments (include/scanlib.h names them)
 struct DriveCall {
     const double *states_in, *speeds;
     const float *steer0;
@@ -1024,63 +1133,39 @@ struct DriveCall {
     double *states_trace;
 };
 
-// n cars for n_ticks ticks, steered by FollowGap (g) or the policy network (p, steer_clip), each scanning alone with h's
-// planner; race: n races of `group` cars, which see each other in every scan (race_fan_kernel); seats (a race only):
-// the checked driver code of each seat, g and p the handles of the drivers that occur; ps: a population as the source
-// (n = ps->n ps->E cars, car r steered by member ps->first + r / ps->E through PolicySteer), checked with pop_args
-struct PopSource {
-    rl_policy_pop *pop;
-    int first, n, E;
-    double *fitness;                   // [n][2] or null
-};
-// lg: a league as the source (a race only): car r steered by member lg->entry[r] of lg->pop, or by g when that is -1;
-// the entries checked with league_entries, n_net of them >= 0
-struct LeagueSource {
-    rl_policy_pop *pop;
-    const int *entry;                  // [n group], host
-    int n_net;
-    double *standings;                 // [n_members][4] or null
-};
-static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g, rl_policy *p, double steer_clip, int n,
-                      bool race, int group, const DriveCall &a, const int *seats = nullptr, const PopSource *ps = nullptr,
-                      const LeagueSource *lg = nullptr)
+// n cars for n_ticks ticks, steered by src (steer_clip: the networks'), each scanning alone with h's planner; race: n
+// races of `group` cars, which see each other in every scan (race_fan_kernel).  The tick kernel, what it is told of seats
+// and entries, and the uploads a source needs before the first tick all follow from src.kind.  A POPULATION has
+// n = src.n src.E cars, car r steered by member src.first + r / src.E; a LEAGUE (a race only) steers car r by member
+// src.entry[r] of src.pop, or by src.g when that is -1.  scores: after the last tick a population's fitness [src.n][2] or
+// a league's standings [n_members][4], or null
+static int drive_loop(const char *name, rl_car *c, rl_method *h, const SteerSource &src, double steer_clip, int n, bool race,
+                      int group, const DriveCall &a, double *scores = nullptr)
 {
-    const bool net = p || ps || lg;    // the tick reads the network's answers
-    if (!c || !h || !(g || net) || (n > 0 && (!a.states_in || !a.speeds || !a.edge || !a.first_crashed)))
+    if (!c || !h || src.empty() || (n > 0 && (!a.states_in || !a.speeds || !a.edge || !a.first_crashed)))
         return fail(RL_ERR_INVALID, "%s: null pointer", name);
     const int n_ticks = a.n_ticks, num_rays = a.num_rays;
     int rc;
     if (race && n < 0) return fail(RL_ERR_INVALID, "n_races must be >= 0 (got %d)", n);
     if (race && (rc = race_args(h, n, group, num_rays))) return rc;
     const int R = race ? n * group : n;          // (a race: < 2^31 / num_rays, race_args)
-    if ((rc = loop_args(name, c, h, g, g ? nullptr : p, R, num_rays)) ||
-        (g && p && (rc = loop_args(name, c, h, nullptr, p, R, num_rays))))
-        return rc;
+    if ((rc = src.check(name, c, h, R, num_rays))) return rc;
     if (R < 0 || n_ticks <= 0) return fail(RL_ERR_INVALID, "n_rollouts >= 0 and n_ticks > 0 required (got %d, %d)", R, n_ticks);
-    rl_policy_pop *const pop = ps ? ps->pop : lg ? lg->pop : nullptr;
-    if (pop && pop->device != c->device)
-        return fail(RL_ERR_INVALID, "%s: car (device %d) and population (device %d) must share one device", name, c->device,
-                    pop->device);
-    if ((p && (rc = policy_args(p, R, num_rays))) || (rc = check_fan_args(h, R, a.fov, num_rays)) || R == 0) return rc;
+    if ((rc = src.fits(name, c, R, num_rays)) || (rc = check_fan_args(h, R, a.fov, num_rays)) || R == 0) return rc;
     OutlineParams op{};
     if (race && (rc = race_outline(h->map, c->P.LENGTH, c->P.WIDTH, op))) return rc;
-    const Loop lp(nullptr, c, h, g, p, pop);
+    const Loop lp(nullptr, c, h, src);
     HIPCHK(hipSetDevice(c->device));
+    rl_policy_pop *const pop = src.pop;
     if (pop && (rc = pop_enter(pop, c->stream))) return rc;
+    const bool net = src.p || pop;     // the tick reads the network's answers
+    const bool seats = src.kind == SteerSource::SEATS, league = src.kind == SteerSource::LEAGUE;
     const size_t rows = (size_t)R * n_ticks, n_rays = (size_t)R * num_rays;
-    // seats: the cars the network drives, race by race (declared before hc: the list outlives the call's copies)
-    uint32_t policy_seats = 0;
-    std::vector<int> seat_rows;
-    if (seats) {
-        for (int k = 0; k < group; ++k)
-            if (seats[k] == RL_SEAT_POLICY) policy_seats |= 1u << k;
-        for (int r = 0; r < n && policy_seats; ++r)
-            for (int k = 0; k < group; ++k)
-                if ((policy_seats >> k) & 1u) seat_rows.push_back(r * group + k);
-    }
+    // seats: the cars the network drives (declared before hc: the list outlives the call's copies)
+    const std::vector<int> seat_rows = seat_row_list(src.policy_seats, n, group);
     HostCall hc(c->stream);
     hipStream_t st = hc.st;
-    if (!seat_rows.empty() && (rc = hc.up(c->seat_rows, (const int *)seat_rows.data(), seat_rows.size()))) return rc;
+    if (!seat_rows.empty() && (rc = hc.up(c->seat_rows, seat_rows.data(), seat_rows.size()))) return rc;
     // trace rows a car never reaches (after its crash tick; the steer of the crash tick) read NaN: all-ones bytes
     if ((rc = hc.up(c->states, a.states_in, (size_t)R * 11)) || (rc = hc.up(c->speeds, a.speeds, R)) ||
         (rc = a.steer0 ? hc.up(c->steer0, a.steer0, R) : hc.zero(c->steer0, R)) || (rc = hc.up(c->edge, a.edge, num_rays)) ||
@@ -1089,19 +1174,16 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
         (a.steers && (rc = hc.fill(c->tr_steers, 0xff, rows))) || (a.scan_poses && (rc = hc.fill(c->tr_poses, 0xff, rows * 3))) ||
         (a.states_trace && (rc = hc.fill(c->tr_states, 0xff, rows * 11))))
         return rc;
-    // the fitness reads the starts again after the last tick: c->states is stepped in place
-    const bool fit = ps && ps->fitness;
-    if (fit && ((rc = hc.up(c->pop_states0, a.states_in, (size_t)R * 11)) || (rc = hc.room(c->pop_fitness, 2 * (size_t)ps->n))))
-        return rc;
-    // a league: the entries go up and are grouped by member once, before the first tick; the standings read the starts
-    const bool stand = lg && lg->standings;
-    if (lg && ((rc = hc.up(pop->lg_member, lg->entry, R)) || (rc = league_group(pop, pop->lg_member, R, st)))) return rc;
-    if (stand && ((rc = hc.up(c->pop_states0, a.states_in, (size_t)R * 11)) || (rc = hc.room(c->pop_fitness, 4 * (size_t)pop->n_members))))
+    // a league: the entries go up and are grouped by member once, before the first tick
+    if (league && ((rc = hc.up(pop->lg_member, src.entry, R)) || (rc = league_group(pop, pop->lg_member, R, st)))) return rc;
+    // the scores read the starts again after the last tick: c->states is stepped in place
+    const size_t n_scores = !scores ? 0 : league ? 4 * (size_t)pop->n_members : 2 * (size_t)src.n;
+    if (n_scores && ((rc = hc.up(c->pop_states0, a.states_in, (size_t)R * 11)) || (rc = hc.room(c->pop_fitness, n_scores))))
         return rc;
 
     DriveParams dp{};
     dp.P = c->P;
-    if (g) dp.fg = g->P;
+    if (src.g) dp.fg = src.g->P;
     dp.fg.size = num_rays;                        // (for the policy only the crash ballot's beam count)
     dp.dt = a.dt;
     dp.scan_dist_to_base = a.scan_dist_to_base;
@@ -1110,39 +1192,30 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, rl_followgap *g
     dp.n_ticks = n_ticks;
     dp.steer_clip = steer_clip;
     dp.group = seats ? group : 0;                 // (a league asks the car's entry, not its seat)
-    dp.policy_seats = policy_seats;
+    dp.policy_seats = src.policy_seats;
     DriveBufs b{c->states, c->speeds, c->steer0, c->edge, c->first, c->poses, c->ranges,
                 a.velocities ? (double *)c->vel : nullptr, a.steers ? (float *)c->tr_steers : nullptr,
                 a.scan_poses ? (float *)c->tr_poses : nullptr, a.states_trace ? (double *)c->tr_states : nullptr,
-                net ? (const float *)c->mlp : nullptr, lg ? (const int *)pop->lg_member : nullptr};
+                net ? (const float *)c->mlp : nullptr, league ? (const int *)pop->lg_member : nullptr};
     hipLaunchKernelGGL(drive_start_kernel, dim3((R + 63) / 64), dim3(64), 0, st, dp, b);
     HIPCHK(hipGetLastError());
     // the noise offset walks the global ray id t R num_rays + r num_rays of every tick
     // (a race reads every car's outline from its f64 state after this tick's step: all cars step, then all scan)
-    LoopScan scan{b.pose, R, a.fov, num_rays, c->ranges, c->mlp, race ? group : 0, b.state, &op};
-    if (seats && p) {
-        scan.net = &p->P;
-        scan.rows = c->seat_rows;
-        scan.n_rows = (int)seat_rows.size();
-    }
-    if (ps) scan.pop_first = ps->first, scan.pop_n = ps->n, scan.pop_E = ps->E;
-    if (lg) scan.league = true, scan.league_net = lg->n_net;
-    const auto &table = lg ? league_tick_table : seats ? seat_tick_table : g ? fg_tick_table : policy_tick_table;
+    const LoopScan scan{b.pose, R, a.fov, num_rays, c->ranges, c->mlp, race ? group : 0, b.state, &op};
+    const auto &table = league ? league_tick_table : seats ? seat_tick_table : src.g ? fg_tick_table : policy_tick_table;
     for (int t = 0; t < n_ticks && rc == RL_OK; ++t)
         rc = lp.scan_then(scan, lp.base + (uint64_t)t * n_rays, table, DRIVE_CARS, "drive_tick_kernel", st, dp, b, t);
-    if (rc == RL_OK && fit) {
-        hipLaunchKernelGGL(policy_pop_fitness_kernel, dim3((ps->n + 63) / 64), dim3(64), 0, st, (const double *)c->states,
-                           (const double *)c->pop_states0, (const int *)c->first, ps->n, ps->E, (double *)c->pop_fitness);
+    if (rc == RL_OK && n_scores) {
+        if (league)
+            hipLaunchKernelGGL(league_standings_kernel, dim3((pop->n_members + 63) / 64), dim3(64), 0, st,
+                               (const double *)c->states, (const double *)c->pop_states0, (const int *)c->first,
+                               (const int *)pop->lg_start, (const int *)pop->lg_count, (const int *)pop->lg_rows, pop->n_members,
+                               group, n_ticks, (double *)c->pop_fitness);
+        else
+            hipLaunchKernelGGL(policy_pop_fitness_kernel, dim3((src.n + 63) / 64), dim3(64), 0, st, (const double *)c->states,
+                               (const double *)c->pop_states0, (const int *)c->first, src.n, src.E, (double *)c->pop_fitness);
         HIPCHK(hipGetLastError());
-        rc = hc.down(ps->fitness, c->pop_fitness, 2 * (size_t)ps->n);
-    }
-    if (rc == RL_OK && stand) {
-        hipLaunchKernelGGL(league_standings_kernel, dim3((pop->n_members + 63) / 64), dim3(64), 0, st, (const double *)c->states,
-                           (const double *)c->pop_states0, (const int *)c->first, (const int *)pop->lg_start,
-                           (const int *)pop->lg_count, (const int *)pop->lg_rows, pop->n_members, group, n_ticks,
-                           (double *)c->pop_fitness);
-        HIPCHK(hipGetLastError());
-        rc = hc.down(lg->standings, c->pop_fitness, 4 * (size_t)pop->n_members);
+        rc = hc.down(scores, c->pop_fitness, n_scores);
     }
     if (rc || (rc = hc.down(a.first_crashed, c->first, R)) || (rc = hc.down(a.states_out, c->states, (size_t)R * 11)) ||
         (rc = hc.down(a.velocities, c->vel, rows)) || (rc = hc.down(a.steers, c->tr_steers, rows)) ||
@@ -1161,7 +1234,7 @@ extern "C" int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, 
     const DriveCall a{states_in, speeds, steer0_or_null, n_ticks, dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh,
                       first_crashed, states_out_or_null, velocities_or_null, steers_or_null, scan_poses_or_null,
                       states_trace_or_null};
-    return drive_loop("rl_car_drive_followgap", c, h, g, nullptr, 0.0, R, false, 0, a);
+    return drive_loop("rl_car_drive_followgap", c, h, SteerSource::followgap(g), 0.0, R, false, 0, a);
 }
 
 extern "C" int rl_car_race_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in,
@@ -1174,7 +1247,7 @@ extern "C" int rl_car_race_followgap(rl_car *c, rl_method *h, rl_followgap *g, c
     const DriveCall a{states_in, speeds, steer0_or_null, n_ticks, dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh,
                       first_crashed, states_out_or_null, velocities_or_null, steers_or_null, scan_poses_or_null,
                       states_trace_or_null};
-    return drive_loop("rl_car_race_followgap", c, h, g, nullptr, 0.0, n_races, true, group, a);
+    return drive_loop("rl_car_race_followgap", c, h, SteerSource::followgap(g), 0.0, n_races, true, group, a);
 }
 
 extern "C" int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const double *states_in,
@@ -1187,7 +1260,7 @@ extern "C" int rl_car_drive_policy(rl_car *c, rl_method *h, rl_policy *p, const 
     const DriveCall a{states_in, speeds, steer0_or_null, n_ticks, dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh,
                       first_crashed, states_out_or_null, velocities_or_null, steers_or_null, scan_poses_or_null,
                       states_trace_or_null};
-    return drive_loop("rl_car_drive_policy", c, h, nullptr, p, steer_clip, R, false, 0, a);
+    return drive_loop("rl_car_drive_policy", c, h, SteerSource::policy(p), steer_clip, R, false, 0, a);
 }
 
 extern "C" int rl_car_drive_population(rl_car *c, rl_method *h, rl_policy_pop *pop, int first, int n, int cars_per_member,
@@ -1204,9 +1277,8 @@ extern "C" int rl_car_drive_population(rl_car *c, rl_method *h, rl_policy_pop *p
     const DriveCall a{states_in, speeds, steer0_or_null, n_ticks, dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh,
                       first_crashed, states_out_or_null, velocities_or_null, steers_or_null, scan_poses_or_null,
                       states_trace_or_null};
-    const PopSource ps{pop, first, n, cars_per_member, fitness_n2_or_null};
-    return drive_loop("rl_car_drive_population", c, h, nullptr, nullptr, steer_clip, n * cars_per_member, false, 0, a, nullptr,
-                      &ps);
+    return drive_loop("rl_car_drive_population", c, h, SteerSource::population(pop, first, n, cars_per_member), steer_clip,
+                      n * cars_per_member, false, 0, a, fitness_n2_or_null);
 }
 
 extern "C" int rl_car_race_seats(rl_car *c, rl_method *h, rl_followgap *g_or_null, rl_policy *p_or_null,
@@ -1217,26 +1289,25 @@ extern "C" int rl_car_race_seats(rl_car *c, rl_method *h, rl_followgap *g_or_nul
                                  float *steers_or_null, float *scan_poses_or_null, double *states_trace_or_null)
 {
     if (!c || !h || !seat_driver) return fail(RL_ERR_INVALID, "rl_car_race_seats: null pointer");
-    if (group < 1 || group > RACE_MAX_GROUP)
-        return fail(RL_ERR_INVALID, "group must lie in [1, %d] cars (got %d)", RACE_MAX_GROUP, group);
-    bool fg = false, net = false;
+    int rc = race_group(group);
+    if (rc) return rc;
+    bool fg = false;
+    uint32_t policy_seats = 0;
     for (int k = 0; k < group; ++k) {
         const int d = seat_driver[k];
         if (d == RL_SEAT_CALLER)
             return fail(RL_ERR_INVALID, "rl_car_race_seats: seat %d is the caller's: a roll-out has no caller to ask", k);
-        if (d != RL_SEAT_FOLLOWGAP && d != RL_SEAT_POLICY)
-            return fail(RL_ERR_INVALID, "rl_car_race_seats: seat %d: unknown driver code %d", k, d);
-        if (!(d == RL_SEAT_FOLLOWGAP ? (void *)g_or_null : (void *)p_or_null))
-            return fail(RL_ERR_INVALID, "rl_car_race_seats: seat %d is driven by %s, whose handle is null", k,
-                        d == RL_SEAT_FOLLOWGAP ? "FollowGap" : "the policy");
-        (d == RL_SEAT_FOLLOWGAP ? fg : net) = true;
+        if ((rc = seat_code("rl_car_race_seats", k, d, g_or_null, p_or_null))) return rc;
+        if (d == RL_SEAT_POLICY) policy_seats |= 1u << k;
+        else fg = true;
     }
     const DriveCall a{states_in, speeds, steer0_or_null, n_ticks, dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh,
                       first_crashed, states_out_or_null, velocities_or_null, steers_or_null, scan_poses_or_null,
                       states_trace_or_null};
     // (a handle no seat uses is not looked at)
-    return drive_loop("rl_car_race_seats", c, h, fg ? g_or_null : nullptr, net ? p_or_null : nullptr, steer_clip, n_races,
-                      true, group, a, seat_driver);
+    rl_policy *const p = policy_seats ? p_or_null : nullptr;
+    const SteerSource src = SteerSource::seats(fg ? g_or_null : nullptr, p, p ? &p->P : nullptr, policy_seats, group, &c->seat_rows);
+    return drive_loop("rl_car_race_seats", c, h, src, steer_clip, n_races, true, group, a);
 }
 
 extern "C" int rl_car_race_league(rl_car *c, rl_method *h, rl_followgap *g_or_null, rl_policy_pop *pop, const int *entry_RP,
@@ -1248,30 +1319,25 @@ extern "C" int rl_car_race_league(rl_car *c, rl_method *h, rl_followgap *g_or_nu
                                   double *standings_N4_or_null)
 {
     if (!c || !h || !pop || (n_races > 0 && !entry_RP)) return fail(RL_ERR_INVALID, "rl_car_race_league: null pointer");
-    if (group < 1 || group > RACE_MAX_GROUP)
-        return fail(RL_ERR_INVALID, "group must lie in [1, %d] cars (got %d)", RACE_MAX_GROUP, group);
+    int rc = race_group(group);
+    if (rc) return rc;
     if (n_races < 0) return fail(RL_ERR_INVALID, "n_races must be >= 0 (got %d)", n_races);
     // (n_races group must be a number of cars before the entries are walked: the race scan's own bound, here first)
     if ((long)n_races * group * std::max(num_rays, 1) >= (1L << 31))
         return fail(RL_ERR_INVALID, "rl_car_race_league: %d races of %d cars, scans of %d beams: their product must stay below 2^31",
                     n_races, group, num_rays);
     const size_t R = (size_t)n_races * group;
-    int rc = league_entries("rl_car_race_league", pop, entry_RP, R);
-    if (rc) return rc;
-    int n_net = 0;
-    for (size_t r = 0; r < R; ++r) n_net += entry_RP[r] >= 0;
-    if ((size_t)n_net < R && !g_or_null)
+    size_t n_net = 0;
+    if ((rc = league_entries("rl_car_race_league", entry_RP, R, pop->n_members, -1, true, nullptr, 1, &n_net))) return rc;
+    if (n_net < R && !g_or_null)
         return fail(RL_ERR_INVALID, "rl_car_race_league: an entry is -1 (FollowGap), whose handle is null");
-    if (n_net && num_rays < pop->P.in_start + pop->P.dims[0])
-        return fail(RL_ERR_INVALID, "scans of %d beams do not hold the policy's window [%d, %d)", num_rays, pop->P.in_start,
-                    pop->P.in_start + pop->P.dims[0]);
+    if (n_net && (rc = policy_window(pop->P, num_rays))) return rc;
     const DriveCall a{states_in, speeds, steer0_or_null, n_ticks, dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh,
                       first_crashed, states_out_or_null, velocities_or_null, steers_or_null, scan_poses_or_null,
                       states_trace_or_null};
     // (a FollowGap handle no entry uses is not looked at)
-    const LeagueSource lg{pop, entry_RP, n_net, standings_N4_or_null};
-    return drive_loop("rl_car_race_league", c, h, (size_t)n_net < R ? g_or_null : nullptr, nullptr, steer_clip, n_races, true,
-                      group, a, nullptr, nullptr, &lg);
+    const SteerSource src = SteerSource::league(n_net < R ? g_or_null : nullptr, pop, entry_RP, (int)n_net);
+    return drive_loop("rl_car_race_league", c, h, src, steer_clip, n_races, true, group, a, standings_N4_or_null);
 }
 
 // ---------------------------------------------------------------- the driving environment (env_kernels.h)
@@ -1317,25 +1383,19 @@ struct rl_env {
     DevPtr<double> track_st;
     DevPtr<float> track_rows;
     DevPtr<int> track_ints;
-    // per-seat drivers (rl_env_attach_seats): the borrowed handles, the kernels' table (its pointers into the buffers
-    // below) and the cars in policy seats
-    bool seated = false;
-    rl_followgap *seat_g = nullptr;
-    rl_policy *seat_p = nullptr;
+    // who drives the cars: src.kind is the env's driver mode.  NOBODY: the caller drives every car.  SEATS
+    // (rl_env_attach_seats) or LEAGUE (rl_env_attach_league): the source with its borrowed handles, and the network's
+    // answers of a call and the kept answers, N floats each, which the mode's kernel table points into
+    SteerSource src;
+    DevPtr<float> mlp, answer;
+    // per-seat drivers: the kernels' table and the cars in policy seats
     SeatBufs seats{};
-    DevPtr<float> seat_mlp, seat_answer;
     DevPtr<int> seat_rows;
-    int n_seat_rows = 0;
-    // league line-ups (rl_env_attach_league): the borrowed handles, the kernels' table (its pointers into the buffers
-    // below: the pending and live entries, the members' answers, the kept answers, the results) and the host's copy of
-    // the seat speeds.  lg_may_net: a pending or live entry may name a member (a host-set table since the attach held
-    // one, or a device setter ran): the network launch is made
-    bool league = false, lg_may_net = false;
-    rl_followgap *lg_g = nullptr;
-    rl_policy_pop *lg_pop = nullptr;
+    // league line-ups: the kernels' table (the pending and live entries, the results, the host's copy of the seat
+    // speeds).  src.n_net > 0: a pending or live entry may name a member (a host-set table since the attach held one, or
+    // a device setter ran) and the scans hold the network's window: the network launch is made
     LeagueEnvBufs lg{};
     DevPtr<int> lg_pending, lg_live;
-    DevPtr<float> lg_mlp, lg_answer;
     DevPtr<unsigned long long> lg_results;
     bool ready = false;            // reset done and no launch failed since (read and written under mu only)
     bool foreign = false;          // the last launches went to a caller's stream: a host form waits for the device first
@@ -1355,15 +1415,11 @@ static RaceEnvBufs race_env_bufs(rl_env *e)
     return RaceEnvBufs{e->group, e->min_running, e->race_tick, e->race_episode, e->race_start_index, e->race_over};
 }
 
-// The Loop of a launching call of env e: the env's mutex first (its league is read under it), then Loop's order with
-// the league's FollowGap and population as the steering sources.
+// The Loop of a launching call of env e: the env's mutex first (its source is read under it), then Loop's order.
 struct EnvLoop {
     std::unique_lock<std::mutex> own;
     const Loop lp;
-    explicit EnvLoop(rl_env *e)
-        : own(e->mu), lp(nullptr, e->c, e->h, e->league ? e->lg_g : nullptr, nullptr, e->league ? e->lg_pop : nullptr)
-    {
-    }
+    explicit EnvLoop(rl_env *e) : own(e->mu), lp(nullptr, e->c, e->h, e->src) {}
 };
 
 // the scan's own refusals, checked before every launching call: a race env adds those of rl_calc_range_fan_cars
@@ -1504,60 +1560,40 @@ static int track_launch(rl_env *e, float *d_reward, hipStream_t st)
     return RL_OK;
 }
 
-// one call's launches on st: phase A (reset: the spawn), the scan at slot k, phase B, then the track kernel where a
-// track is attached.  lp: the call's Loop, owner e.
+// one call's launches on st: phase A (reset: the spawn), the scan at slot k, the source's answers, phase B, then the
+// track kernel where a track is attached.  lp: the call's Loop, owner e.  The env's kind picks phase A and B: a plain
+// env; a race env (whole races spawn and end, and the cars see each other in the scan); one with drivers in its seats
+// (the SEATS instances); one with a league (the LEAGUE instances: phase A adopts the pending entries, so the live ones
+// are grouped by member behind it, for the members' network behind the scan)
 static int env_launch(rl_env *e, const Loop &lp, bool reset, uint64_t k, const float *d_actions, const int *d_start_index,
                       float *d_obs, float *d_reward, int *d_done, float *d_aux, hipStream_t st)
 {
     const int N = e->prm.n_envs, B = e->prm.num_rays;
     const EnvBufs b = env_bufs(e);
+    const RaceEnvBufs rb = race_env_bufs(e);
     const uint64_t off = e->base + k * (uint64_t)N * (uint64_t)B;
-    if (e->group > 0 && e->seated) {     // ... with drivers in its seats: the SEATS instances, and the network between
-        const RaceEnvBufs rb = race_env_bufs(e);
-        hipLaunchKernelGGL(race_env_seat_step_kernel, dim3((N + 63) / 64), dim3(64), 0, st, e->ep, b, rb, e->seats, d_actions,
-                           d_start_index, reset ? 1 : 0);
-        if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "race_env_seat_step_kernel launch failed");
-        LoopScan scan{e->pose, N, e->prm.fov, B, e->ranges, e->seat_mlp, e->group, e->state, &e->outline};
-        if (e->n_seat_rows > 0) {
-            scan.net = &e->seat_p->P;
-            scan.rows = e->seat_rows;
-            scan.n_rows = e->n_seat_rows;
-        }
-        const int rc = lp.scan_then(scan, off, race_env_seat_observe_table, e->group, "race_env_seat_observe_kernel", st,
-                                    e->ep, b, rb, e->seats, d_obs, d_reward, d_done, d_aux);
-        return rc ? rc : track_launch(e, d_reward, st);
-    }
-    if (e->group > 0 && e->league) {     // ... with a league: the LEAGUE instances; the live entries are grouped by member
-        const RaceEnvBufs rb = race_env_bufs(e);     // behind phase A (which adopts them), the members' network behind the scan
-        int rc = pop_enter(e->lg_pop, st);
-        if (rc) return rc;
-        hipLaunchKernelGGL(race_env_league_step_kernel, dim3((N + 63) / 64), dim3(64), 0, st, e->ep, b, rb, e->lg, d_actions,
-                           d_start_index, reset ? 1 : 0);
-        if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "race_env_league_step_kernel launch failed");
-        if ((rc = league_group(e->lg_pop, e->lg_live, N, st))) return rc;
-        LoopScan scan{e->pose, N, e->prm.fov, B, e->ranges, e->lg_mlp, e->group, e->state, &e->outline};
-        scan.league = true;
-        scan.league_net = e->lg_may_net && e->lg.hi > 0 ? N : 0;
-        rc = lp.scan_then(scan, off, race_env_league_observe_table, e->group, "race_env_league_observe_kernel", st, e->ep, b,
-                          rb, e->lg, d_obs, d_reward, d_done, d_aux);
-        return rc ? rc : track_launch(e, d_reward, st);
-    }
-    if (e->group > 0) {          // a race env: whole races spawn and end, and the cars see each other in the scan
-        const RaceEnvBufs rb = race_env_bufs(e);
-        hipLaunchKernelGGL(race_env_step_kernel, dim3((N + 63) / 64), dim3(64), 0, st, e->ep, b, rb, d_actions,
-                           d_start_index, reset ? 1 : 0);
-        if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "race_env_step_kernel launch failed");
-        const LoopScan scan{e->pose, N, e->prm.fov, B, e->ranges, nullptr, e->group, e->state, &e->outline};
-        const int rc = lp.scan_then(scan, off, race_env_observe_table, e->group, "race_env_observe_kernel", st, e->ep, b, rb,
-                                    d_obs, d_reward, d_done, d_aux);
-        return rc ? rc : track_launch(e, d_reward, st);
-    }
-    hipLaunchKernelGGL(env_step_kernel, dim3((N + 63) / 64), dim3(64), 0, st, e->ep, b, d_actions, d_start_index,
-                       reset ? 1 : 0);
-    if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "env_step_kernel launch failed");
-    const LoopScan scan{e->pose, N, e->prm.fov, B, e->ranges, nullptr, 0, nullptr, nullptr};
-    const int rc = lp.scan_then(scan, off, env_observe_table, DRIVE_CARS, "env_observe_kernel",
-                                st, e->ep, b, d_obs, d_reward, d_done, d_aux);
+    const bool race = e->group > 0, seats = lp.src.kind == SteerSource::SEATS, league = lp.src.kind == SteerSource::LEAGUE;
+    const LoopScan scan{e->pose, N, e->prm.fov, B, e->ranges, e->mlp, e->group, e->state, &e->outline};
+    // phase A and phase B of a kind: `mode` is what its kernels take between the env's buffers and the call's
+    const auto step = [&](auto kernel, const char *name, const auto &...mode) {
+        kernel<<<dim3((N + 63) / 64), dim3(64), 0, st>>>(e->ep, b, mode..., d_actions, d_start_index, reset ? 1 : 0);
+        return hipGetLastError() != hipSuccess ? fail(RL_ERR_HIP, "%s launch failed", name) : (int)RL_OK;
+    };
+    const auto observe = [&](const auto &table, int per_wg, const char *name, const auto &...mode) {
+        return lp.scan_then(scan, off, table, per_wg, name, st, e->ep, b, mode..., d_obs, d_reward, d_done, d_aux);
+    };
+    int rc = league ? pop_enter(lp.src.pop, st) : (int)RL_OK;
+    if (rc == RL_OK)
+        rc = seats    ? step(race_env_seat_step_kernel, "race_env_seat_step_kernel", rb, e->seats)
+             : league ? step(race_env_league_step_kernel, "race_env_league_step_kernel", rb, e->lg)
+             : race   ? step(race_env_step_kernel, "race_env_step_kernel", rb)
+                      : step(env_step_kernel, "env_step_kernel");
+    if (rc == RL_OK && league) rc = league_group(lp.src.pop, e->lg_live, N, st);
+    if (rc == RL_OK)
+        rc = seats    ? observe(race_env_seat_observe_table, e->group, "race_env_seat_observe_kernel", rb, e->seats)
+             : league ? observe(race_env_league_observe_table, e->group, "race_env_league_observe_kernel", rb, e->lg)
+             : race   ? observe(race_env_observe_table, e->group, "race_env_observe_kernel", rb)
+                      : observe(env_observe_table, DRIVE_CARS, "env_observe_kernel");
     return rc ? rc : track_launch(e, d_reward, st);
 }
 
@@ -1569,6 +1605,41 @@ static int env_settle(rl_env *e)
         e->foreign = false;
     }
     return RL_OK;
+}
+
+// a device form: this call enqueues on the caller's stream st
+static int env_on_stream(rl_env *e, void *hip_stream, hipStream_t &st)
+{
+    HIPCHK(hipSetDevice(e->device));
+    st = (hipStream_t)hip_stream;
+    if (st != (hipStream_t)e->c->stream) e->foreign = true;
+    return RL_OK;
+}
+
+// what a call asks of env e under its mutex: the driver mode the call is about (NOBODY: any), and a reset
+static int env_ready(const rl_env *e, const char *name, SteerSource::Kind mode = SteerSource::NOBODY, bool need_reset = true)
+{
+    if (mode == SteerSource::SEATS && e->src.kind != mode)
+        return fail(RL_ERR_INVALID, "%s: no seats attached (rl_env_attach_seats)", name);
+    if (mode == SteerSource::LEAGUE && e->src.kind != mode)
+        return fail(RL_ERR_INVALID, "%s: no league attached (rl_env_attach_league)", name);
+    if (need_reset && !e->ready) return fail(RL_ERR_INVALID, "%s: reset the environment first (rl_env_reset)", name);
+    return RL_OK;
+}
+
+// a host form that launches nothing: the env's and the car's mutex, the call's own refusals, the device, the wait for a
+// caller's stream, then body's copies on one HostCall and its wait
+template <class Refusals, class Body>
+static int env_host_call(rl_env *e, Refusals refusals, Body body)
+{
+    std::scoped_lock lk(e->mu, e->c->mu);
+    int rc = refusals();
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    if ((rc = env_settle(e))) return rc;
+    HostCall hc(e->c->stream);
+    if ((rc = body(hc))) return rc;
+    return hc.finish();
 }
 
 static int env_reset_locked(rl_env *e, const Loop &lp, uint64_t seed, const int *d_start_index, float *d_obs,
@@ -1603,11 +1674,9 @@ extern "C" int rl_env_reset_device(rl_env *e, uint64_t seed, const int *d_start_
     int rc = env_scan_args(e);
     if (rc) return rc;
     const EnvLoop el(e);
-    const Loop &lp = el.lp;
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (st != (hipStream_t)e->c->stream) e->foreign = true;
-    return env_reset_locked(e, lp, seed, d_start_index_or_null, d_obs, d_aux_or_null, d_done, st);
+    hipStream_t st;
+    if ((rc = env_on_stream(e, hip_stream, st))) return rc;
+    return env_reset_locked(e, el.lp, seed, d_start_index_or_null, d_obs, d_aux_or_null, d_done, st);
 }
 
 extern "C" int rl_env_step_device(rl_env *e, const float *d_actions_n2, float *d_obs, float *d_reward, int *d_done,
@@ -1615,14 +1684,10 @@ extern "C" int rl_env_step_device(rl_env *e, const float *d_actions_n2, float *d
 {
     if (!e || !d_actions_n2 || !d_obs || !d_reward || !d_done) return fail(RL_ERR_INVALID, "rl_env_step_device: null pointer");
     const EnvLoop el(e);
-    const Loop &lp = el.lp;
-    if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_step_device: reset the environment first (rl_env_reset)");
-    int rc = env_scan_args(e);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (st != (hipStream_t)e->c->stream) e->foreign = true;
-    return env_step_locked(e, lp, d_actions_n2, d_obs, d_reward, d_done, d_aux_or_null, st);
+    hipStream_t st;
+    int rc;
+    if ((rc = env_ready(e, "rl_env_step_device")) || (rc = env_scan_args(e)) || (rc = env_on_stream(e, hip_stream, st))) return rc;
+    return env_step_locked(e, el.lp, d_actions_n2, d_obs, d_reward, d_done, d_aux_or_null, st);
 }
 
 // the host forms' way back: the staged results to the caller, then the wait (a failure leaves the env to be reset)
@@ -1665,10 +1730,9 @@ extern "C" int rl_env_step(rl_env *e, const float *actions_n2, float *obs, float
     if (!e || !actions_n2 || !obs || !reward || !done) return fail(RL_ERR_INVALID, "rl_env_step: null pointer");
     const EnvLoop el(e);
     const Loop &lp = el.lp;
-    if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_step: reset the environment first (rl_env_reset)");
     const int N = e->prm.n_envs;
-    int rc = env_scan_args(e);
-    if (rc) return rc;
+    int rc;
+    if ((rc = env_ready(e, "rl_env_step")) || (rc = env_scan_args(e))) return rc;
     HIPCHK(hipSetDevice(e->device));
     if ((rc = env_settle(e))) return rc;
     HostCall hc(e->c->stream);
@@ -1682,35 +1746,31 @@ extern "C" int rl_env_step(rl_env *e, const float *actions_n2, float *obs, float
 extern "C" int rl_env_read(rl_env *e, double *states_n11, int *ticks, int *episodes, int *start_index, int *done)
 {
     if (!e) return fail(RL_ERR_INVALID, "rl_env_read: null pointer");
-    std::scoped_lock lk(e->mu, e->c->mu);
-    if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_read: reset the environment first (rl_env_reset)");
-    HIPCHK(hipSetDevice(e->device));
-    int rc = env_settle(e);
-    if (rc) return rc;
-    HostCall hc(e->c->stream);
     const size_t N = e->prm.n_envs;
-    if ((rc = hc.down(states_n11, e->state, N * 11)) || (rc = hc.down(ticks, e->tick, N)) ||
-        (rc = hc.down(episodes, e->episode, N)) || (rc = hc.down(start_index, e->start_index, N)) ||
-        (rc = hc.down(done, e->done, N)))
-        return rc;
-    return hc.finish();
+    return env_host_call(e, [&] { return env_ready(e, "rl_env_read"); }, [&](HostCall &hc) {
+        int rc;
+        if ((rc = hc.down(states_n11, e->state, N * 11)) || (rc = hc.down(ticks, e->tick, N)) ||
+            (rc = hc.down(episodes, e->episode, N)) || (rc = hc.down(start_index, e->start_index, N)))
+            return rc;
+        return hc.down(done, e->done, N);
+    });
 }
 
 extern "C" int rl_env_read_races(rl_env *e, int *race_ticks, int *race_episodes, int *race_start_index, int *race_over)
 {
     if (!e) return fail(RL_ERR_INVALID, "rl_env_read_races: null pointer");
-    std::scoped_lock lk(e->mu, e->c->mu);
-    if (e->group < 1) return fail(RL_ERR_INVALID, "rl_env_read_races: not a race environment (rl_env_create_race)");
-    if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_read_races: reset the environment first (rl_env_reset)");
-    HIPCHK(hipSetDevice(e->device));
-    int rc = env_settle(e);
-    if (rc) return rc;
-    HostCall hc(e->c->stream);
-    const size_t R = e->prm.n_envs / e->group;
-    if ((rc = hc.down(race_ticks, e->race_tick, R)) || (rc = hc.down(race_episodes, e->race_episode, R)) ||
-        (rc = hc.down(race_start_index, e->race_start_index, R)) || (rc = hc.down(race_over, e->race_over, R)))
-        return rc;
-    return hc.finish();
+    const auto refusals = [&] {
+        if (e->group < 1) return fail(RL_ERR_INVALID, "rl_env_read_races: not a race environment (rl_env_create_race)");
+        return env_ready(e, "rl_env_read_races");
+    };
+    return env_host_call(e, refusals, [&](HostCall &hc) {
+        const size_t R = e->prm.n_envs / e->group;
+        int rc;
+        if ((rc = hc.down(race_ticks, e->race_tick, R)) || (rc = hc.down(race_episodes, e->race_episode, R)) ||
+            (rc = hc.down(race_start_index, e->race_start_index, R)))
+            return rc;
+        return hc.down(race_over, e->race_over, R);
+    });
 }
 
 // ---------------------------------------------------------------- track progress (track_kernels.h)
@@ -1801,16 +1861,15 @@ extern "C" int rl_env_attach_track(rl_env *e, rl_track *t, const rl_track_params
 extern "C" int rl_env_read_track(rl_env *e, float *rows_n8, int *ints_n4)
 {
     if (!e) return fail(RL_ERR_INVALID, "rl_env_read_track: null pointer");
-    std::scoped_lock lk(e->mu, e->c->mu);
-    if (!e->track) return fail(RL_ERR_INVALID, "rl_env_read_track: no track attached (rl_env_attach_track)");
-    if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_read_track: reset the environment first (rl_env_reset)");
-    HIPCHK(hipSetDevice(e->device));
-    int rc = env_settle(e);
-    if (rc) return rc;
-    HostCall hc(e->c->stream);
-    const size_t N = e->prm.n_envs;
-    if ((rc = hc.down(rows_n8, e->track_rows, N * 8)) || (rc = hc.down(ints_n4, e->track_ints, N * 4))) return rc;
-    return hc.finish();
+    const auto refusals = [&] {
+        if (!e->track) return fail(RL_ERR_INVALID, "rl_env_read_track: no track attached (rl_env_attach_track)");
+        return env_ready(e, "rl_env_read_track");
+    };
+    return env_host_call(e, refusals, [&](HostCall &hc) {
+        const size_t N = e->prm.n_envs;
+        const int rc = hc.down(rows_n8, e->track_rows, N * 8);
+        return rc ? rc : hc.down(ints_n4, e->track_ints, N * 4);
+    });
 }
 
 extern "C" int rl_env_read_track_device(rl_env *e, float *d_rows_n8, int *d_ints_n4, void *hip_stream)
@@ -1818,36 +1877,45 @@ extern "C" int rl_env_read_track_device(rl_env *e, float *d_rows_n8, int *d_ints
     if (!e) return fail(RL_ERR_INVALID, "rl_env_read_track_device: null pointer");
     std::scoped_lock lk(e->mu, e->c->mu);
     if (!e->track) return fail(RL_ERR_INVALID, "rl_env_read_track_device: no track attached (rl_env_attach_track)");
-    if (!e->ready) return fail(RL_ERR_INVALID, "rl_env_read_track_device: reset the environment first (rl_env_reset)");
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (st != (hipStream_t)e->c->stream) e->foreign = true;
+    hipStream_t st;
+    int rc;
+    if ((rc = env_ready(e, "rl_env_read_track_device")) || (rc = env_on_stream(e, hip_stream, st))) return rc;
     const size_t N = e->prm.n_envs;
     if (d_rows_n8) HIPCHK(hipMemcpyAsync(d_rows_n8, e->track_rows, N * 8 * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (d_ints_n4) HIPCHK(hipMemcpyAsync(d_ints_n4, e->track_ints, N * 4 * sizeof(int), hipMemcpyDeviceToDevice, st));
     return RL_OK;
 }
 
-// ---------------------------------------------------------------- per-seat drivers (include/scanlib_seats.h)
+// ---------------------------------------------------------------- the env's drivers: seats and leagues
+// (include/scanlib_seats.h, include/scanlib_league_env.h)
+// how both attach calls begin once they have refused what they refuse: launches in flight may still read the tables
+// replaced below, the attached drivers of `mode` go, and the answers of new ones start at the next reset
+static int env_detach(rl_env *e, SteerSource::Kind mode)
+{
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipDeviceSynchronize());
+    e->foreign = false;
+    if (e->src.kind == mode) e->src = SteerSource();
+    e->ready = false;
+    return RL_OK;
+}
+
 extern "C" int rl_env_attach_seats(rl_env *e, rl_followgap *g_or_null, rl_policy *p_or_null, const rl_seat_params *sp_or_null)
 {
     if (!e) return fail(RL_ERR_INVALID, "rl_env_attach_seats: null pointer");
     std::scoped_lock lk(e->mu, e->c->mu);
     if (e->group < 1) return fail(RL_ERR_INVALID, "rl_env_attach_seats: not a race environment (rl_env_create_race)");
-    if (sp_or_null && e->league)
+    if (sp_or_null && e->src.kind == SteerSource::LEAGUE)
         return fail(RL_ERR_INVALID, "rl_env_attach_seats: a league is attached (rl_env_attach_league): detach it first");
     const int N = e->prm.n_envs, P = e->group, B = e->prm.num_rays;
     SeatBufs S{};
+    int rc;
     if (sp_or_null) {
         for (int k = 0; k < P; ++k) {
             const int d = sp_or_null->driver[k];
             if (d == RL_SEAT_CALLER) continue;
-            if (d != RL_SEAT_FOLLOWGAP && d != RL_SEAT_POLICY)
-                return fail(RL_ERR_INVALID, "rl_env_attach_seats: seat %d: unknown driver code %d", k, d);
+            if ((rc = seat_code("rl_env_attach_seats", k, d, g_or_null, p_or_null))) return rc;
             const bool net = d == RL_SEAT_POLICY;
-            if (!(net ? (void *)p_or_null : (void *)g_or_null))
-                return fail(RL_ERR_INVALID, "rl_env_attach_seats: seat %d is driven by %s, whose handle is null", k,
-                            net ? "the policy" : "FollowGap");
             const int dev = net ? p_or_null->device : g_or_null->device;
             if (dev != e->device)
                 return fail(RL_ERR_INVALID, "rl_env_attach_seats: %s (device %d) and env (device %d) must share one device",
@@ -1858,93 +1926,60 @@ extern "C" int rl_env_attach_seats(rl_env *e, rl_followgap *g_or_null, rl_policy
             if (net) S.policy |= 1u << k;
             S.speed[k] = sp_or_null->speed[k];
         }
-        int rc;
         if (S.policy && (rc = policy_args(p_or_null, N, B))) return rc;
     }
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipDeviceSynchronize());     // (launches in flight may still read the tables replaced below)
-    e->foreign = false;
-    e->seated = false;
-    e->ready = false;                   // the answers of the new seats start at the next reset
-    e->n_seat_rows = 0;
-    if (!sp_or_null) return RL_OK;
-    int rc;
-    if ((rc = e->seat_answer.ensure(N))) return rc;
+    if ((rc = env_detach(e, SteerSource::SEATS)) || !sp_or_null) return rc;
+    if ((rc = e->answer.ensure(N))) return rc;
     if (S.policy) {
-        std::vector<int> rows;
-        for (int r = 0; r < N / P; ++r)
-            for (int k = 0; k < P; ++k)
-                if ((S.policy >> k) & 1u) rows.push_back(r * P + k);
-        if ((rc = e->seat_mlp.ensure(N)) || (rc = e->seat_rows.ensure(rows.size()))) return rc;
+        const std::vector<int> rows = seat_row_list(S.policy, N / P, P);
+        if ((rc = e->mlp.ensure(N)) || (rc = e->seat_rows.ensure(rows.size()))) return rc;
         HIPCHK(hipMemcpy(e->seat_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
-        e->n_seat_rows = (int)rows.size();
     }
     if (S.scripted & ~S.policy) S.fg = g_or_null->P;
     S.fg.size = B;
-    S.mlp = e->seat_mlp;
-    S.answer = e->seat_answer;
+    S.mlp = e->mlp;
+    S.answer = e->answer;
     e->seats = S;
-    e->seat_g = g_or_null;
-    e->seat_p = p_or_null;
-    e->seated = true;
+    // (neither handle is named: SteerSource says why)
+    e->src = SteerSource::seats(nullptr, nullptr, S.policy ? &p_or_null->P : nullptr, S.policy, P, &e->seat_rows);
     return RL_OK;
 }
 
-static int env_seats_ready(rl_env *e, const char *name)
+// the seat drivers' or the league's kept answers, to the host (dev = false) or on the caller's stream
+static int env_read_answers(rl_env *e, const char *name, SteerSource::Kind mode, float *steer_n, bool dev, void *hip_stream)
 {
-    if (!e->seated) return fail(RL_ERR_INVALID, "%s: no seats attached (rl_env_attach_seats)", name);
-    if (!e->ready) return fail(RL_ERR_INVALID, "%s: reset the environment first (rl_env_reset)", name);
+    if (!e) return fail(RL_ERR_INVALID, "%s: null pointer", name);
+    const size_t N = e->prm.n_envs;
+    if (!dev)
+        return env_host_call(e, [&] { return env_ready(e, name, mode); },
+                             [&](HostCall &hc) { return hc.down(steer_n, e->answer, N); });
+    std::scoped_lock lk(e->mu, e->c->mu);
+    hipStream_t st;
+    int rc;
+    if ((rc = env_ready(e, name, mode)) || (rc = env_on_stream(e, hip_stream, st))) return rc;
+    if (steer_n) HIPCHK(hipMemcpyAsync(steer_n, e->answer, N * sizeof(float), hipMemcpyDeviceToDevice, st));
     return RL_OK;
 }
 
 extern "C" int rl_env_read_seats(rl_env *e, float *steer_n)
 {
-    if (!e) return fail(RL_ERR_INVALID, "rl_env_read_seats: null pointer");
-    std::scoped_lock lk(e->mu, e->c->mu);
-    int rc = env_seats_ready(e, "rl_env_read_seats");
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    if ((rc = env_settle(e))) return rc;
-    HostCall hc(e->c->stream);
-    if ((rc = hc.down(steer_n, e->seat_answer, (size_t)e->prm.n_envs))) return rc;
-    return hc.finish();
+    return env_read_answers(e, "rl_env_read_seats", SteerSource::SEATS, steer_n, false, nullptr);
 }
 
 extern "C" int rl_env_read_seats_device(rl_env *e, float *d_steer_n, void *hip_stream)
 {
-    if (!e) return fail(RL_ERR_INVALID, "rl_env_read_seats_device: null pointer");
-    std::scoped_lock lk(e->mu, e->c->mu);
-    const int rc = env_seats_ready(e, "rl_env_read_seats_device");
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (st != (hipStream_t)e->c->stream) e->foreign = true;
-    if (d_steer_n)
-        HIPCHK(hipMemcpyAsync(d_steer_n, e->seat_answer, (size_t)e->prm.n_envs * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return RL_OK;
+    return env_read_answers(e, "rl_env_read_seats_device", SteerSource::SEATS, d_steer_n, true, hip_stream);
 }
 
-// ---------------------------------------------------------------- league line-ups in the race env (include/scanlib_league_env.h)
 // the host forms' look at an entry table of env e with population pop, FollowGap g and the seat speeds `speed`
 static int league_env_entries(const char *fn, const rl_env *e, const rl_policy_pop *pop, const rl_followgap *g,
                               const int *entry, const float *speed, bool *any_net)
 {
-    const int N = e->prm.n_envs, P = e->group;
-    *any_net = false;
-    for (int i = 0; i < N; ++i) {
-        const int m = entry[i];
-        if (m < -2 || m >= pop->n_members)
-            return fail(RL_ERR_INVALID, "%s: entry %d names member %d: not -2, -1 and not in the population's [0, %d)", fn, i, m,
-                        pop->n_members);
-        if (m == -1 && !g) return fail(RL_ERR_INVALID, "%s: entry %d is -1 (FollowGap), whose handle is null", fn, i);
-        if (m >= -1 && !std::isfinite(speed[i % P]))
-            return fail(RL_ERR_INVALID, "%s: the speed of seat %d must be finite (entry %d scripts a car of it)", fn, i % P, i);
-        *any_net |= m >= 0;
-    }
-    if (*any_net && e->prm.num_rays < pop->P.in_start + pop->P.dims[0])
-        return fail(RL_ERR_INVALID, "%s: scans of %d beams do not hold the policy's window [%d, %d)", fn, e->prm.num_rays,
-                    pop->P.in_start, pop->P.in_start + pop->P.dims[0]);
-    return RL_OK;
+    size_t n_net = 0;
+    int rc = league_entries(fn, entry, (size_t)e->prm.n_envs, pop->n_members, -2, g != nullptr, speed, e->group, &n_net);
+    if (rc == RL_OK && n_net) rc = policy_window(pop->P, e->prm.num_rays, fn);
+    *any_net = n_net > 0;
+    return rc;
 }
 
 extern "C" int rl_env_attach_league(rl_env *e, rl_followgap *g_or_null, rl_policy_pop *pop, const int *entry_N_or_null,
@@ -1956,29 +1991,21 @@ extern "C" int rl_env_attach_league(rl_env *e, rl_followgap *g_or_null, rl_polic
     const size_t N = e->prm.n_envs;
     LeagueEnvBufs L{};
     bool any_net = false;
+    int rc;
     if (entry_N_or_null) {
         if (!pop || !speed_P) return fail(RL_ERR_INVALID, "rl_env_attach_league: null pointer");
-        if (e->seated)
+        if (e->src.kind == SteerSource::SEATS)
             return fail(RL_ERR_INVALID, "rl_env_attach_league: seats are attached (rl_env_attach_seats): detach them first");
         if (pop->device != e->device || (g_or_null && g_or_null->device != e->device))
             return fail(RL_ERR_INVALID, "rl_env_attach_league: %s (device %d) and env (device %d) must share one device",
                         pop->device != e->device ? "population" : "FollowGap",
                         pop->device != e->device ? pop->device : g_or_null->device, e->device);
-        const int rc = league_env_entries("rl_env_attach_league", e, pop, g_or_null, entry_N_or_null, speed_P, &any_net);
-        if (rc) return rc;
+        if ((rc = league_env_entries("rl_env_attach_league", e, pop, g_or_null, entry_N_or_null, speed_P, &any_net))) return rc;
     }
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipDeviceSynchronize());     // (launches in flight may still read the tables replaced below)
-    e->foreign = false;
-    e->league = false;
-    e->ready = false;                   // the line-ups and answers of the new league start at the next reset
-    e->lg_g = nullptr;
-    e->lg_pop = nullptr;
-    if (!entry_N_or_null) return RL_OK;
+    if ((rc = env_detach(e, SteerSource::LEAGUE)) || !entry_N_or_null) return rc;
     const size_t rows = (size_t)pop->n_members + 2;
-    int rc;
-    if ((rc = e->lg_pending.ensure(N)) || (rc = e->lg_live.ensure(N)) || (rc = e->lg_mlp.ensure(N)) ||
-        (rc = e->lg_answer.ensure(N)) || (rc = e->lg_results.ensure(rows * 8)))
+    if ((rc = e->lg_pending.ensure(N)) || (rc = e->lg_live.ensure(N)) || (rc = e->mlp.ensure(N)) ||
+        (rc = e->answer.ensure(N)) || (rc = e->lg_results.ensure(rows * 8)))
         return rc;
     HIPCHK(hipMemcpy(e->lg_pending, entry_N_or_null, N * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(hipMemset(e->lg_results, 0, rows * 8 * sizeof(unsigned long long)));
@@ -1991,108 +2018,78 @@ extern "C" int rl_env_attach_league(rl_env *e, rl_followgap *g_or_null, rl_polic
     L.fg.size = e->prm.num_rays;
     L.pending = e->lg_pending;
     L.live = e->lg_live;
-    L.mlp = e->lg_mlp;
-    L.answer = e->lg_answer;
+    L.mlp = e->mlp;
+    L.answer = e->answer;
     L.results = e->lg_results;
     e->lg = L;
-    e->lg_g = g_or_null;
-    e->lg_pop = pop;
-    e->lg_may_net = any_net;
-    e->league = true;
-    return RL_OK;
-}
-
-static int env_league_attached(const rl_env *e, const char *name, bool need_reset)
-{
-    if (!e->league) return fail(RL_ERR_INVALID, "%s: no league attached (rl_env_attach_league)", name);
-    if (need_reset && !e->ready) return fail(RL_ERR_INVALID, "%s: reset the environment first (rl_env_reset)", name);
+    // (the entries live on the device: the grouping is env_launch's; an entry that names a member has a window, so L.hi > 0)
+    e->src = SteerSource::league(g_or_null, pop, nullptr, any_net ? (int)N : 0);
     return RL_OK;
 }
 
 extern "C" int rl_env_set_league_entries(rl_env *e, const int *entry_N)
 {
     if (!e || !entry_N) return fail(RL_ERR_INVALID, "rl_env_set_league_entries: null pointer");
-    std::scoped_lock lk(e->mu, e->c->mu);
-    int rc = env_league_attached(e, "rl_env_set_league_entries", false);
     bool any_net = false;
-    if (rc || (rc = league_env_entries("rl_env_set_league_entries", e, e->lg_pop, e->lg_g, entry_N, e->lg.speed, &any_net)))
+    const auto refusals = [&] {
+        const int rc = env_ready(e, "rl_env_set_league_entries", SteerSource::LEAGUE, false);
+        return rc ? rc : league_env_entries("rl_env_set_league_entries", e, e->src.pop, e->src.g, entry_N, e->lg.speed, &any_net);
+    };
+    return env_host_call(e, refusals, [&](HostCall &hc) {
+        const int rc = hc.up((int *)e->lg_pending, entry_N, (size_t)e->prm.n_envs);
+        if (rc == RL_OK && any_net) e->src.n_net = e->prm.n_envs;
         return rc;
-    HIPCHK(hipSetDevice(e->device));
-    if ((rc = env_settle(e))) return rc;
-    HostCall hc(e->c->stream);
-    if ((rc = hc.up((int *)e->lg_pending, entry_N, (size_t)e->prm.n_envs))) return rc;
-    e->lg_may_net |= any_net;
-    return hc.finish();
+    });
 }
 
 extern "C" int rl_env_set_league_entries_device(rl_env *e, const int *d_entry_N, void *hip_stream)
 {
     if (!e || !d_entry_N) return fail(RL_ERR_INVALID, "rl_env_set_league_entries_device: null pointer");
     std::scoped_lock lk(e->mu, e->c->mu);
-    const int rc = env_league_attached(e, "rl_env_set_league_entries_device", false);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (st != (hipStream_t)e->c->stream) e->foreign = true;
+    hipStream_t st;
+    int rc;
+    if ((rc = env_ready(e, "rl_env_set_league_entries_device", SteerSource::LEAGUE, false)) ||
+        (rc = env_on_stream(e, hip_stream, st)))
+        return rc;
     HIPCHK(hipMemcpyAsync(e->lg_pending, d_entry_N, (size_t)e->prm.n_envs * sizeof(int), hipMemcpyDeviceToDevice, st));
-    e->lg_may_net = true;               // (the host cannot look at these entries)
+    if (e->lg.hi > 0) e->src.n_net = e->prm.n_envs;     // (the host cannot look at these entries: one may name a member)
     return RL_OK;
 }
 
 extern "C" int rl_env_read_league_steers(rl_env *e, float *steer_n)
 {
-    if (!e) return fail(RL_ERR_INVALID, "rl_env_read_league_steers: null pointer");
-    std::scoped_lock lk(e->mu, e->c->mu);
-    int rc = env_league_attached(e, "rl_env_read_league_steers", true);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    if ((rc = env_settle(e))) return rc;
-    HostCall hc(e->c->stream);
-    if ((rc = hc.down(steer_n, e->lg_answer, (size_t)e->prm.n_envs))) return rc;
-    return hc.finish();
+    return env_read_answers(e, "rl_env_read_league_steers", SteerSource::LEAGUE, steer_n, false, nullptr);
 }
 
 extern "C" int rl_env_read_league_steers_device(rl_env *e, float *d_steer_n, void *hip_stream)
 {
-    if (!e) return fail(RL_ERR_INVALID, "rl_env_read_league_steers_device: null pointer");
-    std::scoped_lock lk(e->mu, e->c->mu);
-    const int rc = env_league_attached(e, "rl_env_read_league_steers_device", true);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (st != (hipStream_t)e->c->stream) e->foreign = true;
-    if (d_steer_n)
-        HIPCHK(hipMemcpyAsync(d_steer_n, e->lg_answer, (size_t)e->prm.n_envs * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return RL_OK;
+    return env_read_answers(e, "rl_env_read_league_steers_device", SteerSource::LEAGUE, d_steer_n, true, hip_stream);
 }
 
 extern "C" int rl_env_read_league_entries(rl_env *e, int *live_N_or_null, int *pending_N_or_null)
 {
     if (!e) return fail(RL_ERR_INVALID, "rl_env_read_league_entries: null pointer");
-    std::scoped_lock lk(e->mu, e->c->mu);
-    int rc = env_league_attached(e, "rl_env_read_league_entries", live_N_or_null != nullptr);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    if ((rc = env_settle(e))) return rc;
-    HostCall hc(e->c->stream);
-    const size_t N = e->prm.n_envs;
-    if ((rc = hc.down(live_N_or_null, e->lg_live, N)) || (rc = hc.down(pending_N_or_null, e->lg_pending, N))) return rc;
-    return hc.finish();
+    const auto refusals = [&] {
+        return env_ready(e, "rl_env_read_league_entries", SteerSource::LEAGUE, live_N_or_null != nullptr);
+    };
+    return env_host_call(e, refusals, [&](HostCall &hc) {
+        const size_t N = e->prm.n_envs;
+        const int rc = hc.down(live_N_or_null, e->lg_live, N);
+        return rc ? rc : hc.down(pending_N_or_null, e->lg_pending, N);
+    });
 }
 
 extern "C" int rl_env_read_league_results(rl_env *e, int64_t *results, int clear)
 {
     if (!e || !results) return fail(RL_ERR_INVALID, "rl_env_read_league_results: null pointer");
-    std::scoped_lock lk(e->mu, e->c->mu);
-    int rc = env_league_attached(e, "rl_env_read_league_results", true);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(e->device));
-    if ((rc = env_settle(e))) return rc;
-    HostCall hc(e->c->stream);
-    const size_t n = ((size_t)e->lg.n_members + 2) * 8;
-    if ((rc = hc.down((unsigned long long *)results, e->lg_results, n))) return rc;
-    if (clear) HIPCHK(hipMemsetAsync(e->lg_results, 0, n * sizeof(unsigned long long), hc.st));
-    return hc.finish();
+    const auto refusals = [&] { return env_ready(e, "rl_env_read_league_results", SteerSource::LEAGUE); };
+    return env_host_call(e, refusals, [&](HostCall &hc) {
+        const size_t n = ((size_t)e->lg.n_members + 2) * 8;
+        const int rc = hc.down((unsigned long long *)results, e->lg_results, n);
+        if (rc) return rc;
+        if (clear) HIPCHK(hipMemsetAsync(e->lg_results, 0, n * sizeof(unsigned long long), hc.st));
+        return (int)RL_OK;
+    });
 }
 
 // ---------------------------------------------------------------- diagnostics: HBM stream probe
@@ -2315,8 +2312,7 @@ static const std::array<mcts_act_fn, FG_ROWS> mcts_act_table =
 struct rl_mcts {
     rl_car *c = nullptr;
     rl_method *h = nullptr;
-    rl_followgap *g = nullptr;
-    rl_policy *p = nullptr;
+    SteerSource src;               // FollowGap, the policy or nobody (the random source)
     rl_mcts_params prm{};
     MctsParams mp{};
     int device = 0;
@@ -2377,21 +2373,20 @@ extern "C" int rl_mcts_create(rl_car *c, rl_method *h, rl_followgap *g, rl_polic
     if (q.source != RL_MCTS_FG && q.source != RL_MCTS_NN && q.source != RL_MCTS_RANDOM)
         return fail(RL_ERR_INVALID, "rl_mcts_create: unknown source %d", q.source);
     g = q.source == RL_MCTS_FG ? g : nullptr;
-    p = q.source == RL_MCTS_NN ? p : nullptr;
+    const SteerSource src = g ? SteerSource::followgap(g) : q.source == RL_MCTS_NN ? SteerSource::policy(p) : SteerSource();
     if (q.n_trees < 1 || q.max_nodes < 1 || q.action_every < 1 || q.rollout_steps < 1 || q.rollout_steps > MCTS_MAX_STEPS)
         return fail(RL_ERR_INVALID, "rl_mcts_create: n_trees >= 1, max_nodes >= 1, action_every >= 1 and 1 <= "
                     "rollout_steps <= %d required (got %d, %d, %d, %d)", MCTS_MAX_STEPS, q.n_trees, q.max_nodes,
                     q.action_every, q.rollout_steps);
-    int rc = loop_args("rl_mcts_create", c, h, g, p, (long)q.n_trees * q.rollout_steps, q.num_rays);      // (the roll-out scans)
-    if (rc || (p && (rc = policy_args(p, q.n_trees, q.num_rays)))) return rc;
+    int rc = src.check("rl_mcts_create", c, h, (long)q.n_trees * q.rollout_steps, q.num_rays);      // (the roll-out scans)
+    if (rc || (rc = src.fits("rl_mcts_create", c, q.n_trees, q.num_rays))) return rc;
     if ((long)q.n_trees * q.max_nodes >= (1L << 31) / 11)
         return fail(RL_ERR_INVALID, "rl_mcts_create: the node arrays (n_trees * max_nodes * 11) must stay below 2^31");
     std::unique_ptr<rl_mcts, decltype(&rl_mcts_destroy)> m(new (std::nothrow) rl_mcts(), rl_mcts_destroy);
     if (!m) return fail(RL_ERR_NOMEM, "out of host memory");
     m->c = c;
     m->h = h;
-    m->g = g;
-    m->p = p;
+    m->src = src;
     m->prm = q;
     m->device = c->device;
     MctsParams &mp = m->mp;
@@ -2498,7 +2493,7 @@ extern "C" int rl_mcts_reset(rl_mcts *m, const double *root_states, const double
     const int K = m->prm.n_trees;
     int rc = check_fan_args(m->h, K, m->prm.fov, m->prm.num_rays);
     if (rc) return rc;
-    const Loop lp(&m->mu, m->c, m->h, m->g, m->p);
+    const Loop lp(&m->mu, m->c, m->h, m->src);
     if ((rc = plan_args(m, "rl_mcts_reset"))) return rc;
     HIPCHK(hipSetDevice(m->device));
     m->ready = false;
@@ -2568,7 +2563,7 @@ extern "C" int rl_mcts_run(rl_mcts *m, int n_iterations)
 {
     if (!m) return fail(RL_ERR_INVALID, "rl_mcts_run: null pointer");
     if (n_iterations < 0) return fail(RL_ERR_INVALID, "rl_mcts_run: n_iterations must be >= 0 (got %d)", n_iterations);
-    const Loop lp(&m->mu, m->c, m->h, m->g, m->p);
+    const Loop lp(&m->mu, m->c, m->h, m->src);
     if (!m->ready) return fail(RL_ERR_INVALID, "rl_mcts_run: reset the planner first (rl_mcts_reset)");
     if (1 + m->iters + (long)n_iterations > m->prm.max_nodes)
         return fail(RL_ERR_INVALID, "rl_mcts_run: %d more iterations exceed max_nodes = %d (%ld done since reset)",
@@ -2626,7 +2621,7 @@ extern "C" int rl_mcts_drive(rl_mcts *m, const double *states_in, const double *
         return RL_OK;
     }
     const size_t rows = (size_t)K * D;
-    const Loop lp(&m->mu, m->c, m->h, m->g, m->p);
+    const Loop lp(&m->mu, m->c, m->h, m->src);
     HIPCHK(hipSetDevice(m->device));
     std::vector<uint32_t> keys(rows);                  // [D][K]: decision d's seed is seeds[k] + d mod 2^64
     for (int d = 0; d < D; ++d)

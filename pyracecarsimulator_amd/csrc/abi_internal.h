@@ -11,8 +11,8 @@
 //                  particle-filter weights (repeat-angle scans, sensor model) and localisation (rl_pf_*)
 //   abi_multi.hip  the host-pointer entry points and their multi-device forms (run_blocks below: one block per device)
 //   abi_car.hip    roll-out generator, FollowGap, the policy network, batched races and the race scan; the closed-loop
-//                  session (loop_args, Loop: the checks, locks, launch arguments and scan-then-consume step of every
-//                  closed loop) and its three users: FollowGap / policy / race roll-outs (drive_loop), the driving
+//                  session (loop_args, SteerSource, Loop: the checks, who answers the scans, the locks and the
+//                  scan-then-consume step of every closed loop) and its three users: the roll-outs (drive_loop), the driving
 //                  environment (rl_env_*), the MCTS planner and its closed-loop drive (rl_mcts_*); 16-bit ranges,
 //                  probes, the car-outline table and cells
 #pragma once

@@ -279,3 +279,97 @@ def test_closed_loops_share_their_handles_across_threads():
     pl.close()
     env.close()
     m.set_noise(0.0, 0, 0)
+
+
+def test_league_and_seat_loops_share_their_handles_across_threads():
+    """The sibling of the case above for the steering sources it leaves out, each of which takes its own set of
+    mutexes: a league race env (the env's, the car's, the method's, FollowGap's and the population's), a league roll-out
+    followed by the population's row-indexed evaluation (the same handles without an env's; then the population's
+    alone) and a race env with drivers in its seats (neither seat handle's).  One CarBatch, one RMGPU method with noise
+    on, one PyFollowGap and one 3-member population of the seat tests' 40 -> 16 -> 8 -> 1 network on 65 beams (two beam
+    rows, the second holding one beam); 2 races of 3 cars.  Serially first, then in three threads at once: every output
+    equals its serial twin bit for bit and the method is left as it was.  A thread still alive after 30 s fails the
+    case (the work takes milliseconds), so a lock-order mistake shows as a failure, not as a run that hangs."""
+    import drive_cases as DC
+    import test_gpu_population as TP
+    from test_gpu_race_env import _race_starts
+    from pyracecarsimulator_amd import RaceEnv, league
+    R, P, B, T, base = 2, 3, 65, 4, 4242
+    g = DC.race_maze()
+    omap = range_libc.PyOMap(g)
+    m = range_libc.PyRayMarchingGPU(omap, DC.RACE_MRX)
+    m.set_noise(0.01, 77, base)
+    cars, fg, edge = RC.CarBatch(), support.followgap(), support.edge(B)
+    pop, _, _ = TP.make_pop("small", 3)
+    pol = pop.member(0)
+    pool, _ = _race_starts(g, omap.distance_transform(), 3, P, 52)
+    pool[:, :, 3] = 3.0
+    entries = np.array([[-2, -1, 0], [2, -2, -1]], np.int32)           # the caller's, FollowGap's, members 0 and 2
+    kw = dict(car=cars, seat_speed=(3.0, 3.5, 4.0), min_running=2, max_ticks=8, auto_reset=True, steer_clip=0.2,
+              substeps=4, obs_window=(5, 40, 1), obs_clip=15.0, obs_scale=15.0)
+    league_env = RaceEnv(m, pool, R, B, FOV, edge, THRESH, league=(pop, entries), followgap=fg, **kw)
+    seat_env = RaceEnv(m, pool, R, B, FOV, edge, THRESH, seats=[None, fg, pol], **kw)
+    acts = DC.actions(31, T, R * P).reshape(T, R, P, 2)
+    league_acts, seat_acts = acts.copy(), acts.copy()
+    league_acts[:, entries != -2] = np.nan                                # (a scripted car's action is not read)
+    seat_acts[:, :, 1:] = np.nan
+    roll_entries = np.array([[-1, 0, 2], [2, -1, 0]], np.int32)
+    states = np.ascontiguousarray(pool[:R])
+    rows = np.random.default_rng(9).uniform(0.2, 12.0, (R * P, B)).astype(np.float32)
+    row_members = np.array([0, -1, 2, 1, -1, 0], np.int32)
+    poses = np.ascontiguousarray(states.reshape(-1, 11)[:, :3], np.float32)
+
+    def fan():
+        out = np.empty(R * P * B, np.float32)
+        m.calc_range_fan(poses, out, FOV, B)
+        return out
+
+    def run_league_env():
+        out = [league_env.reset(seed=5, start_index=np.arange(R, dtype=np.int32))]
+        for k in range(T):
+            out.extend(league_env.step(league_acts[k]))
+        steers, res = league_env.league_steers(), league_env.league_results()
+        out.extend(res[k] for k in league.RESULT_COLUMNS)
+        out.append(np.array([[res[who][k] for k in league.RESULT_COLUMNS] for who in ("followgap", "caller")]))
+        return out + [steers]
+
+    def run_league_rollout():
+        out = list(cars.race_league(m, pop, roll_entries, states, 3, (3.0, 3.5, 4.0) * R, FOV, B, edge, THRESH,
+                                    followgap=fg, steer_clip=0.2, trace=True))
+        return out + [pop.predict_rows(rows, row_members)]
+
+    def run_seat_env():
+        out = [seat_env.reset(seed=5, start_index=np.arange(R, dtype=np.int32))]
+        for k in range(T):
+            out.extend(seat_env.step(seat_acts[k]))
+        return out + [seat_env.seat_steers()]
+
+    work = [run_league_env, run_league_rollout, run_seat_env]
+    before = fan()
+    serial = [[np.array(a) for a in w()] for w in work]
+    got, errors = [None] * len(work), []
+
+    def runner(i):
+        try:
+            got[i] = [np.array(a) for a in work[i]()]
+        except Exception as e:                                  # noqa: BLE001
+            errors.append((i, repr(e)))
+
+    threads = [threading.Thread(target=runner, args=(i,), daemon=True) for i in range(len(work))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(30)
+    assert not any(t.is_alive() for t in threads), "a closed loop did not return within 30 s"
+    assert not errors, errors
+    for i, w in enumerate(work):
+        assert len(got[i]) == len(serial[i]), w.__name__
+        for j, (a, b) in enumerate(zip(got[i], serial[i])):
+            assert same_bits(a, b), (w.__name__, j)
+    # (the case is about the locks, not the drivers: still, a line-up that scripted nothing would test nothing)
+    assert np.isfinite(serial[0][-1]).any() and np.isfinite(serial[2][-1]).any()
+    assert m.get_info("nt_store") == 1
+    assert same_bits(fan(), before)
+    league_env.close()
+    seat_env.close()
+    m.set_noise(0.0, 0, 0)

@@ -57,7 +57,7 @@ def test_population_shapes_reach_a_third_workgroup_a_member_and_a_second_block()
     assert "const int m = blockIdx.x / wg_per_member, chunk = blockIdx.x - m * wg_per_member;" in kern
     assert "const int m = blockIdx.x * 64 + threadIdx.x;" in kern
     abi = _src("abi_car.hip")
-    assert "policy_pop_fitness_kernel, dim3((ps->n + 63) / 64), dim3(64)" in abi
+    assert "policy_pop_fitness_kernel, dim3((src.n + 63) / 64), dim3(64)" in abi     # (src.n: the members of the call)
     assert "const int wg = (E + PM_CARS - 1) / PM_CARS;" in abi
     seen = set()
     for name, n, E in NS.EVAL:
