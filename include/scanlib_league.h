@@ -62,8 +62,9 @@
  *   outside [1, 8]; handles on different devices or multi-device handles; everything rl_car_race_seats and
  *   rl_car_drive_population refuse, with their codes.  n == 0 and n_races == 0 are RL_OK and launch nothing.
  *
- * Out of scope: leagues in rl_env_*; a placing by track progress; a device-pointer form of the roll-out; members of
- *   different architectures; multi-device handles.                                                                   */
+ * Out of scope: leagues in rl_env_*; a placing by track progress in standings_N4 itself (with a track attached to the
+ *   car handle the roll-out has it: scanlib_track_drive.h, rl_car_read_track_scores); a device-pointer form of the
+ *   roll-out; members of different architectures; multi-device handles.                                              */
 #ifndef SCANLIB_LEAGUE_H
 #define SCANLIB_LEAGUE_H
 

@@ -93,8 +93,9 @@
  *   rl_env_attach_seats while a league is); setters or reads with no league attached; steers or results read before a
  *   reset; a null entry table in a setter, a null results pointer.
  *
- * Out of scope: leagues in the single-car environment (rl_env_create); a placing by track progress; members of
- *   different architectures; multi-device handles; graph capture; a device-pointer form of the results read.         */
+ * Out of scope: leagues in the single-car environment (rl_env_create); a tally of the env's results by track progress
+ *   (the league ROLL-OUT has that placing: scanlib_track_drive.h); members of different architectures; multi-device
+ *   handles; graph capture; a device-pointer form of the results read.                                               */
 #ifndef SCANLIB_LEAGUE_ENV_H
 #define SCANLIB_LEAGUE_ENV_H
 

@@ -7,7 +7,8 @@ device is usable, the calls raise.
 ``SYMBOLS`` restates every prototype of the header (tests/test_py_calls_host.py pins it to the header, argument by
 argument, with the structures and enums below); ``EXT_SYMBOLS`` does the same for include/scanlib_track_plan.h and
 ``SEAT_SYMBOLS`` for include/scanlib_seats.h, ``POP_SYMBOLS`` for include/scanlib_population.h, ``LEAGUE_SYMBOLS`` for
-include/scanlib_league.h and ``LEAGUE_ENV_SYMBOLS`` for include/scanlib_league_env.h.
+include/scanlib_league.h, ``LEAGUE_ENV_SYMBOLS`` for include/scanlib_league_env.h and ``TRACK_DRIVE_SYMBOLS`` for
+include/scanlib_track_drive.h.
 ``call(name, *args)`` is how the package's wrappers enter the library: every argument is converted by the type the
 tables declare for it, and a symbol that returns ``rl_status`` is checked (``ScanLibError``) and gives None.  What a
 declared type takes:
@@ -105,6 +106,11 @@ class TrackParams(C.Structure):
 class PlanTrackParams(C.Structure):
     """rl_plan_track_params (include/scanlib_track_plan.h)."""
     _fields_ = [("reward_mode", C.c_int), ("window", C.c_int), ("goal_span", C.c_int), ("lookahead", C.c_double)]
+
+
+class DriveTrackParams(C.Structure):
+    """rl_drive_track_params (include/scanlib_track_drive.h)."""
+    _fields_ = [("window", C.c_int), ("goal_dist", C.c_double)]
 
 
 class SeatParams(C.Structure):
@@ -332,14 +338,23 @@ LEAGUE_ENV_SYMBOLS = {
 }
 
 
+#: every symbol include/scanlib_track_drive.h declares, in the shape of ``SYMBOLS`` (tests/test_track_drive_host.py pins
+#: it to that header); looked up after ``LEAGUE_ENV_SYMBOLS``.  Every ``int`` is an rl_status
+TRACK_DRIVE_SYMBOLS = {
+    "rl_car_attach_track": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DriveTrackParams)]),
+    "rl_car_read_track": (C.c_int, [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_int)]),
+    "rl_car_read_track_scores": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f64p]),
+}
+
+
 def declared(name):
     """(restype, argtypes) of ``name`` from ``SYMBOLS``, then ``EXT_SYMBOLS``, ``SEAT_SYMBOLS``, ``POP_SYMBOLS``,
-    ``LEAGUE_SYMBOLS`` and ``LEAGUE_ENV_SYMBOLS``."""
-    for table in (SYMBOLS, EXT_SYMBOLS, SEAT_SYMBOLS, POP_SYMBOLS, LEAGUE_SYMBOLS):
+    ``LEAGUE_SYMBOLS``, ``LEAGUE_ENV_SYMBOLS`` and ``TRACK_DRIVE_SYMBOLS``."""
+    for table in (SYMBOLS, EXT_SYMBOLS, SEAT_SYMBOLS, POP_SYMBOLS, LEAGUE_SYMBOLS, LEAGUE_ENV_SYMBOLS):
         ent = table.get(name)
         if ent is not None:
             return ent
-    return LEAGUE_ENV_SYMBOLS[name]
+    return TRACK_DRIVE_SYMBOLS[name]
 
 
 #: the symbols whose ``int`` is a value; every other ``int`` function returns rl_status (``call`` checks it)
@@ -376,7 +391,7 @@ def build(force: bool = False) -> str:
     srcs = [os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc"))
             if f.endswith((".hip", ".h"))]
     srcs += [os.path.join(_HERE, "..", "include", h) for h in ("scanlib.h", "scanlib_track_plan.h", "scanlib_seats.h", "scanlib_population.h", "scanlib_league.h",
-                                                                       "scanlib_league_env.h")]
+                                                                       "scanlib_league_env.h", "scanlib_track_drive.h")]
     stale = (not os.path.exists(_SO)) or any(os.path.getmtime(s) > os.path.getmtime(_SO)
                                              for s in srcs)
     if force or stale:
@@ -422,7 +437,7 @@ def lib():
         L = C.CDLL(_SO)
         for name, (res, args) in (list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(SEAT_SYMBOLS.items())
                                   + list(POP_SYMBOLS.items()) + list(LEAGUE_SYMBOLS.items())
-                                  + list(LEAGUE_ENV_SYMBOLS.items())):
+                                  + list(LEAGUE_ENV_SYMBOLS.items()) + list(TRACK_DRIVE_SYMBOLS.items())):
             try:
                 fn = getattr(L, name)
             except AttributeError:

@@ -5,7 +5,8 @@
 // (include/scanlib_seats.h: rl_car_race_seats, rl_env_attach_seats); policy populations (include/scanlib_population.h:
 // rl_policy_pop_*, rl_car_drive_population); league races (include/scanlib_league.h: rl_policy_pop_eval_rows,
 // rl_car_race_league); league line-ups in the race environment (include/scanlib_league_env.h: rl_env_attach_league,
-// rl_env_set_league_entries*, rl_env_read_league_*);
+// rl_env_set_league_entries*, rl_env_read_league_*); track progress of the roll-outs (include/scanlib_track_drive.h:
+// rl_car_attach_track, rl_car_read_track*);
 // 16-bit ranges for the xGMI exchange, diagnostics probes, the car-outline table and Car::isCrashed on the host.
 #include "abi_internal.h"
 #pragma GCC visibility push(default)
@@ -14,6 +15,7 @@
 #include "../../include/scanlib_population.h"
 #include "../../include/scanlib_league.h"
 #include "../../include/scanlib_league_env.h"
+#include "../../include/scanlib_track_drive.h"
 #pragma GCC visibility pop
 #include <array>
 #include <utility>
@@ -22,6 +24,7 @@
 #include "drive_kernels.h"
 #include "env_kernels.h"
 #include "track_kernels.h"
+#include "drive_track_kernels.h"
 #include "mcts_kernels.h"
 #include "plan_track_kernels.h"
 #include "policy_kernels.h"
@@ -51,6 +54,14 @@ struct rl_car {
     // rl_car_rollout_track: the roll-outs' f64 positions, their terms and s, and the per-roll-out roots (PlanRoots)
     DevPtr<double> tk_xy, tk_terms, tk_s, tk_start_s, tk_root_s, tk_point, tk_points_in;
     DevPtr<int> tk_seg, tk_root_seg, tk_goal, tk_has;
+    // track progress of the roll-outs (rl_car_attach_track): the borrowed track, its options (goal: L where the caller
+    // gave 0), the rows of the last tracked call, its R (0: none yet) and the shape of the scores it left (0: none)
+    rl_track *track = nullptr;
+    int dt_window = 0;
+    double dt_goal = 0.0;
+    DevPtr<double> dt_rows, dt_scores;
+    DevPtr<int> dt_ints;
+    int dt_cars = 0, dt_score_rows = 0, dt_score_cols = 0;
     std::mutex mu;
 };
 
@@ -1117,6 +1128,8 @@ static const std::array<drive_tick_fn, FG_ROWS> seat_tick_table =
 static const std::array<drive_tick_fn, FG_ROWS> league_tick_table =
     rows_table<drive_tick_fn>([](auto rows) { return drive_tick_kernel<rows, LeagueSteer>; });
 
+static TrackTable track_table(const rl_track *t);
+
 // what the roll-out entry points share of their arguments (include/scanlib.h names them)
 struct DriveCall {
     const double *states_in, *speeds;
@@ -1138,7 +1151,9 @@ struct DriveCall {
 // and entries, and the uploads a source needs before the first tick all follow from src.kind.  A POPULATION has
 // n = src.n src.E cars, car r steered by member src.first + r / src.E; a LEAGUE (a race only) steers car r by member
 // src.entry[r] of src.pop, or by src.g when that is -1.  scores: after the last tick a population's fitness [src.n][2] or
-// a league's standings [n_members][4], or null
+// a league's standings [n_members][4], or null.  With a track attached to c (include/scanlib_track_drive.h) the cars are
+// placed on it: once on the start states, ahead of every tick's scan, and ranked and scored after the last tick; the
+// launches of a handle without a track are the ones below and no others
 static int drive_loop(const char *name, rl_car *c, rl_method *h, const SteerSource &src, double steer_clip, int n, bool race,
                       int group, const DriveCall &a, double *scores = nullptr)
 {
@@ -1180,6 +1195,18 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, const SteerSour
     const size_t n_scores = !scores ? 0 : league ? 4 * (size_t)pop->n_members : 2 * (size_t)src.n;
     if (n_scores && ((rc = hc.up(c->pop_states0, a.states_in, (size_t)R * 11)) || (rc = hc.room(c->pop_fitness, n_scores))))
         return rc;
+    // a track: the fresh placement reads the start states before drive_start_kernel steps them in place
+    const rl_track *const trk = c->track;
+    const TrackTable tt = trk ? track_table(trk) : TrackTable{};
+    const dim3 track_grid((R + DRIVE_CARS - 1) / DRIVE_CARS), track_block(64 * DRIVE_CARS);
+    if (trk) {
+        c->dt_cars = c->dt_score_rows = c->dt_score_cols = 0;      // (a call that fails leaves nothing to read)
+        if ((rc = hc.room(c->dt_rows, (size_t)R * 4)) || (rc = hc.room(c->dt_ints, (size_t)R * 4))) return rc;
+        hipLaunchKernelGGL(drive_track_kernel<true>, track_grid, track_block, 0, st, R, tt, c->dt_window, c->dt_goal,
+                           DriveTrackBufs{c->dt_rows, c->dt_ints}, (const double *)c->states, (const int *)nullptr, 0);
+        HIPCHK(hipGetLastError());
+    }
+    const DriveTrackBufs tb{c->dt_rows, c->dt_ints};
 
     DriveParams dp{};
     dp.P = c->P;
@@ -1203,8 +1230,14 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, const SteerSour
     // (a race reads every car's outline from its f64 state after this tick's step: all cars step, then all scan)
     const LoopScan scan{b.pose, R, a.fov, num_rays, c->ranges, c->mlp, race ? group : 0, b.state, &op};
     const auto &table = league ? league_tick_table : seats ? seat_tick_table : src.g ? fg_tick_table : policy_tick_table;
-    for (int t = 0; t < n_ticks && rc == RL_OK; ++t)
+    for (int t = 0; t < n_ticks && rc == RL_OK; ++t) {
+        if (trk) {      // the cars still running hold the state after tick t's step
+            hipLaunchKernelGGL(drive_track_kernel<false>, track_grid, track_block, 0, st, R, tt, c->dt_window, c->dt_goal, tb,
+                               (const double *)c->states, (const int *)c->first, t);
+            HIPCHK(hipGetLastError());
+        }
         rc = lp.scan_then(scan, lp.base + (uint64_t)t * n_rays, table, DRIVE_CARS, "drive_tick_kernel", st, dp, b, t);
+    }
     if (rc == RL_OK && n_scores) {
         if (league)
             hipLaunchKernelGGL(league_standings_kernel, dim3((pop->n_members + 63) / 64), dim3(64), 0, st,
@@ -1217,11 +1250,30 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, const SteerSour
         HIPCHK(hipGetLastError());
         rc = hc.down(scores, c->pop_fitness, n_scores);
     }
+    // a track: ranks per race, then the population's or the league's track scores (whether or not `scores` was asked for)
+    int score_rows = 0, score_cols = 0;
+    if (rc == RL_OK && trk) {
+        hipLaunchKernelGGL(drive_track_rank_kernel, dim3((R + 63) / 64), dim3(64), 0, st, R, race ? group : 0, tt, tb);
+        HIPCHK(hipGetLastError());
+        if (league) score_rows = pop->n_members, score_cols = 4;
+        else if (src.kind == SteerSource::POPULATION) score_rows = src.n, score_cols = 3;
+        if (score_rows && (rc = hc.room(c->dt_scores, (size_t)score_rows * score_cols))) return rc;
+        if (league)
+            hipLaunchKernelGGL(drive_track_standings_kernel, dim3((score_rows + 63) / 64), dim3(64), 0, st, tb,
+                               (const int *)pop->lg_start, (const int *)pop->lg_count, (const int *)pop->lg_rows, score_rows,
+                               group, (double *)c->dt_scores);
+        else if (score_rows)
+            hipLaunchKernelGGL(drive_track_fitness_kernel, dim3((score_rows + 63) / 64), dim3(64), 0, st, tb, src.n, src.E,
+                               (double *)c->dt_scores);
+        HIPCHK(hipGetLastError());
+    }
     if (rc || (rc = hc.down(a.first_crashed, c->first, R)) || (rc = hc.down(a.states_out, c->states, (size_t)R * 11)) ||
         (rc = hc.down(a.velocities, c->vel, rows)) || (rc = hc.down(a.steers, c->tr_steers, rows)) ||
         (rc = hc.down(a.scan_poses, c->tr_poses, rows * 3)) || (rc = hc.down(a.states_trace, c->tr_states, rows * 11)))
         return rc;
-    return hc.finish();
+    if ((rc = hc.finish())) return rc;
+    if (trk) c->dt_cars = R, c->dt_score_rows = score_rows, c->dt_score_cols = score_cols;
+    return RL_OK;
 }
 
 extern "C" int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, const double *states_in,
@@ -1884,6 +1936,61 @@ extern "C" int rl_env_read_track_device(rl_env *e, float *d_rows_n8, int *d_ints
     if (d_rows_n8) HIPCHK(hipMemcpyAsync(d_rows_n8, e->track_rows, N * 8 * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (d_ints_n4) HIPCHK(hipMemcpyAsync(d_ints_n4, e->track_ints, N * 4 * sizeof(int), hipMemcpyDeviceToDevice, st));
     return RL_OK;
+}
+
+// ---------------------------------------------------------------- track progress of the roll-outs
+// (include/scanlib_track_drive.h; the launches are drive_loop's)
+extern "C" int rl_car_attach_track(rl_car *c, rl_track *t, const rl_drive_track_params *p)
+{
+    if (!c) return fail(RL_ERR_INVALID, "rl_car_attach_track: null pointer");
+    std::scoped_lock lk(c->mu);
+    if (t) {
+        if (!p) return fail(RL_ERR_INVALID, "rl_car_attach_track: null params");
+        if (!c->reps.empty()) return fail(RL_ERR_INVALID, "rl_car_attach_track is single-device only: pass an ordinary car handle");
+        if (p->window < 0 || p->window > 65536)
+            return fail(RL_ERR_INVALID, "rl_car_attach_track: window must lie in [0, 65536] (got %d)", p->window);
+        if (!std::isfinite(p->goal_dist) || p->goal_dist < 0.0)
+            return fail(RL_ERR_INVALID, "rl_car_attach_track: goal_dist must be finite and >= 0");
+        if (t->device != c->device)
+            return fail(RL_ERR_INVALID, "rl_car_attach_track: track (device %d) and car (device %d) must share one device",
+                        t->device, c->device);
+        c->dt_window = p->window;
+        c->dt_goal = p->goal_dist == 0.0 ? t->cum.back() : p->goal_dist;
+    }
+    c->track = t;
+    c->dt_cars = c->dt_score_rows = c->dt_score_cols = 0;      // the rows of the new track start at the next roll-out
+    return RL_OK;
+}
+
+extern "C" int rl_car_read_track(rl_car *c, int n_cars, double *rows_n4, int *ints_n4)
+{
+    if (!c) return fail(RL_ERR_INVALID, "rl_car_read_track: null pointer");
+    std::scoped_lock lk(c->mu);
+    if (!c->track) return fail(RL_ERR_INVALID, "rl_car_read_track: no track attached (rl_car_attach_track)");
+    if (!c->dt_cars) return fail(RL_ERR_INVALID, "rl_car_read_track: no roll-out has run with the track yet");
+    if (n_cars != c->dt_cars)
+        return fail(RL_ERR_INVALID, "rl_car_read_track: the last tracked roll-out had %d cars (got n_cars %d)", c->dt_cars, n_cars);
+    HIPCHK(hipSetDevice(c->device));
+    HostCall hc(c->stream);
+    int rc;
+    if ((rc = hc.down(rows_n4, c->dt_rows, (size_t)n_cars * 4)) || (rc = hc.down(ints_n4, c->dt_ints, (size_t)n_cars * 4))) return rc;
+    return hc.finish();
+}
+
+extern "C" int rl_car_read_track_scores(rl_car *c, int n_rows, int n_cols, double *scores)
+{
+    if (!c || !scores) return fail(RL_ERR_INVALID, "rl_car_read_track_scores: null pointer");
+    std::scoped_lock lk(c->mu);
+    if (!c->track) return fail(RL_ERR_INVALID, "rl_car_read_track_scores: no track attached (rl_car_attach_track)");
+    if (!c->dt_score_rows)
+        return fail(RL_ERR_INVALID, "rl_car_read_track_scores: the last tracked roll-out was no population's and no league's");
+    if (n_rows != c->dt_score_rows || n_cols != c->dt_score_cols)
+        return fail(RL_ERR_INVALID, "rl_car_read_track_scores: the last tracked roll-out left scores [%d][%d] (got [%d][%d])",
+                    c->dt_score_rows, c->dt_score_cols, n_rows, n_cols);
+    HIPCHK(hipSetDevice(c->device));
+    HostCall hc(c->stream);
+    const int rc = hc.down(scores, c->dt_scores, (size_t)n_rows * n_cols);
+    return rc ? rc : hc.finish();
 }
 
 // ---------------------------------------------------------------- the env's drivers: seats and leagues

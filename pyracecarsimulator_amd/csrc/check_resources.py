@@ -43,6 +43,12 @@ BOUNDS = [
     ("scan::race_env_league_observe_kernel<", {"scratch": 0}),
     # track progress: the f64 search, the wave's (value, index) minimum and lane 0's trigonometry spill nothing
     ("scan::track_kernel<", {"scratch": 0}),
+    # track progress of the roll-outs: the same search per car and tick, the per-race rank and the one-lane-per-member
+    # track scores spill nothing
+    ("scan::drive_track_kernel<", {"scratch": 0}),
+    ("scan::drive_track_rank_kernel", {"scratch": 0}),
+    ("scan::drive_track_fitness_kernel", {"scratch": 0}),
+    ("scan::drive_track_standings_kernel", {"scratch": 0}),
     # the policy network: the micro-tile accumulators stay in registers
     ("scan::policy_mlp_kernel", {"scratch": 0}),
     ("scan::policy_mlp_rows_kernel", {"scratch": 0}),

@@ -19,6 +19,9 @@ scripts/mcts.py's tree search for many trees at once on the device (``mcts.MCTSP
 scripts/mcts_driver.py's closed loop of it: every car replans at every decision.
 ``CarBatch.race_followgap`` runs many races of up to 8 cars at once, each car's scan seeing the other cars of its
 race (scripts/two_player/); ``CarBatch.outline_cells`` gives the canonical outline cells of the cars.
+``CarBatch.attach_track`` places the cars of every closed-loop roll-out on a ``Track`` after each step they take
+(include/scanlib_track_drive.h): ``track_state`` and ``track_scores`` read progress, laps, goal ticks, places and the
+population's and league's scores built on them.
 """
 from __future__ import annotations
 
@@ -218,6 +221,7 @@ class CarBatch(_lib.Handle):
             st.reshape(-1, 11), n_ticks, spd, num_rays, edge, st0, trace)
         _lib.call("rl_car_race_seats", self, method, fg, pol, codes, clip, states, speeds, st0, n_races, group, n_ticks,
                   dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh, first, out, vel, steers, poses, trace_st)
+        self._tracked((n_races, group))
         res = (first, out, vel, steers) + ((poses, trace_st) if trace else ())
         return tuple(a.reshape((n_races, group) + a.shape[1:]) for a in res)
 
@@ -261,6 +265,7 @@ class CarBatch(_lib.Handle):
         _lib.call("rl_car_drive_population", self, method, pop, first, n, E, clip, states, speeds, st0, n_ticks, dt,
                   scan_dist_to_base, fov, num_rays, edge, crash_thresh, first_crashed, out, vel, steers, poses, trace_st,
                   fitness)
+        self._tracked((R,), (n, 3))
         return (first_crashed, out, vel, steers) + ((poses, trace_st) if trace else ()) + (fitness,)
 
     def race_league(self, method, pop, entries, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
@@ -289,8 +294,68 @@ class CarBatch(_lib.Handle):
         _lib.call("rl_car_race_league", self, method, followgap, pop, entry, clip, states, speeds, st0, n_races, group,
                   n_ticks, dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh, first, out, vel, steers, poses,
                   trace_st, standings)
+        self._tracked((n_races, group), (pop.n_members, 4))
         res = (first, out, vel, steers) + ((poses, trace_st) if trace else ())
         return tuple(a.reshape((n_races, group) + a.shape[1:]) for a in res) + (standings,)
+
+    # -- track progress of the roll-outs (include/scanlib_track_drive.h) -----------------------------------
+    _track = None             # the attached ``Track``, kept referenced: the library only borrows it
+    _track_shape = None       # the car shape of the last roll-out made with it: (R,) or (n_races, P)
+    _score_shape = None       # the shape of the track scores that roll-out left, if any
+
+    def attach_track(self, track, window=0, goal_dist=None):
+        """Place the cars of every later roll-out (``drive_*``, ``race_*``) on ``track`` (a ``Track``) after each step
+        they take (``rl_car_attach_track``): read the result with ``track_state`` and ``track_scores``.  ``window``: 0
+        searches every segment at every tick, w > 0 the segments within w of the previous one; ``goal_dist`` metres of
+        progress for ``goal_tick`` (None: one track length).  The roll-outs' own results keep their bits."""
+        from .track import Track
+        if not isinstance(track, Track):
+            raise ValueError("track must be a Track")
+        if isinstance(window, (bool, np.bool_)) or not isinstance(window, (int, np.integer)) or not 0 <= window <= 65536:
+            raise ValueError("window must be an integer in [0, 65536]")
+        if goal_dist is not None and not (isinstance(goal_dist, (int, float, np.integer, np.floating))
+                                          and np.isfinite(goal_dist) and goal_dist > 0):
+            raise ValueError("goal_dist must be None or finite and > 0")
+        goal = 0.0 if goal_dist is None else float(goal_dist)
+        _lib.call("rl_car_attach_track", self, track, _lib.DriveTrackParams(int(window), goal))
+        self._track, self._track_shape, self._score_shape = track, None, None
+
+    def detach_track(self):
+        """Later roll-outs run without a track again (``rl_car_attach_track`` with no track)."""
+        _lib.call("rl_car_attach_track", self, None, None)
+        self._track = self._track_shape = self._score_shape = None
+
+    def _tracked(self, shape, scores=None):
+        """After a roll-out's library call: what ``track_state`` and ``track_scores`` may ask for."""
+        if self._track is not None:
+            self._track_shape, self._score_shape = tuple(int(v) for v in shape), scores
+
+    def track_state(self):
+        """Where the last roll-out's cars are on the attached track (``rl_car_read_track``): a dict of s0, s, progress
+        and race_dist (float64), segment, laps, goal_tick and rank (int32), each shaped (R,) or, after a race,
+        (n_races, P)."""
+        if self._track is None or self._track_shape is None:
+            raise ValueError("track_state needs an attached track and a roll-out made with it")
+        shape = self._track_shape
+        R = int(np.prod(shape))
+        rows, ints = np.empty((R, 4), dtype=np.float64), np.empty((R, 4), dtype=np.intc)
+        _lib.call("rl_car_read_track", self, R, rows, ints)
+        out = {k: np.ascontiguousarray(rows[:, i]).reshape(shape) for i, k in enumerate(("s0", "s", "progress", "race_dist"))}
+        out.update({k: np.ascontiguousarray(ints[:, i]).astype(np.int32).reshape(shape)
+                    for i, k in enumerate(("segment", "laps", "goal_tick", "rank"))})
+        return out
+
+    def track_scores(self):
+        """The track scores the last roll-out left (``rl_car_read_track_scores``): float64 (n, 3) after
+        ``drive_population`` — per member the sum of its cars' progress (ascending, each addition rounded), how many
+        reached ``goal_dist`` and the sum of their goal ticks —, (n_members, 4) after ``race_league`` — cars entered,
+        the sum of their progress, how many reached the goal, and how many cars of their own races they are ahead of."""
+        shape = self._score_shape
+        if self._track is None or self._track_shape is None or shape is None:
+            raise ValueError("track_scores needs an attached track and a drive_population or race_league made with it")
+        out = np.empty(shape, dtype=np.float64)
+        _lib.call("rl_car_read_track_scores", self, shape[0], shape[1], out)
+        return out
 
     def plan_mcts(self, method, followgap_or_policy, root_states, n_iterations, seeds, fov, num_rays, edge,
                   crash_thresh, root_actions=0.0, source=None, rollout_steps=200, action_every=10, speed=2.0,
@@ -366,6 +431,7 @@ class CarBatch(_lib.Handle):
             states, n_ticks, speed, num_rays, edge, steer0, trace)
         _lib.call(fn, self, method, source, states, speeds, st0, *(counts or (R,)), n_ticks, dt, scan_dist_to_base, fov,
                   num_rays, edge, crash_thresh, *after_thresh, first, out, vel, steers, poses, trace_st)
+        self._tracked(counts or (R,))
         if trace:
             return first, out, vel, steers, poses, trace_st
         return first, out, vel, steers

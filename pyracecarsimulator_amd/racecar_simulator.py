@@ -151,73 +151,109 @@ class RacecarSimulator:
                                       self.num_rays, self.edge_distances, self.ttc_thresh,
                                       n_steps=n_steps, action_every=action_every, dt=dt)
 
-    def driveFollowGapMany(self, states, n_ticks, speed=2.0):
+    def driveFollowGapMany(self, states, n_ticks, speed=2.0, track=None, track_window=0, goal_dist=None):
         """R closed-loop roll-outs of the reference's tick (scripts/ros_interface.py:119-148: updatePose, runScan,
         checkCollision() >= 0) steered by ``PyFollowGap(10, 15.0, max_steer_ang, 0.004)`` as
         scripts/two_player/simple_driver.py:31 builds it, on this simulator's range method, edge table and
         ttc_thresh.  Returns ``CarBatch.drive_followgap``'s (first crash tick or -(n_ticks+1), final states,
-        velocities, steers); ranges never leave the GPU."""
+        velocities, steers); ranges never leave the GPU.  ``track`` (a ``Track``): the cars are placed on it
+        (``CarBatch.attach_track`` for the call, ``track_window`` and ``goal_dist`` as it takes them) and
+        ``CarBatch.track_state``'s dict is appended to the tuple."""
         if self._followgap is None:
             from .followgap import PyFollowGap
             self._followgap = PyFollowGap(10, 15.0, self.max_steer_ang, 0.004, device=self._device)
-        return self.car.drive_followgap(self.scan_simulator.scan_method, self._followgap,
+        return self._tracked(track, track_window, goal_dist, False, self.car.drive_followgap,
+                             self.scan_simulator.scan_method, self._followgap,
                                         np.asarray(states, dtype=np.float64).reshape(-1, 11), n_ticks, speed,
                                         self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
                                         scan_dist_to_base=self.scan_dist_to_base)
 
-    def raceFollowGapMany(self, states, n_ticks, speed=2.0):
+    def raceFollowGapMany(self, states, n_ticks, speed=2.0, track=None, track_window=0, goal_dist=None):
         """R batched races of P cars (states float64 (R, P, 11)) under ``driveFollowGapMany``'s driver, method, edge
         table and ttc_thresh: scripts/two_player/'s tick (every car steps, then every car scans with the others in the
         map) for many races at once.  Returns ``CarBatch.race_followgap``'s (first crash tick or -(n_ticks+1) (R, P),
-        final states, velocities, steers); ranges never leave the GPU."""
+        final states, velocities, steers); ranges never leave the GPU.  ``track`` (a ``Track``): the cars are placed
+        on it (``CarBatch.attach_track`` for the call, ``track_window`` and ``goal_dist`` as it takes them) and
+        ``CarBatch.track_state``'s dict is appended to the tuple."""
         if self._followgap is None:
             from .followgap import PyFollowGap
             self._followgap = PyFollowGap(10, 15.0, self.max_steer_ang, 0.004, device=self._device)
-        return self.car.race_followgap(self.scan_simulator.scan_method, self._followgap,
+        return self._tracked(track, track_window, goal_dist, False, self.car.race_followgap,
+                             self.scan_simulator.scan_method, self._followgap,
                                        np.asarray(states, dtype=np.float64), n_ticks, speed, self.scan_fov,
                                        self.num_rays, self.edge_distances, self.ttc_thresh,
                                        scan_dist_to_base=self.scan_dist_to_base)
 
-    def raceSeatsMany(self, states, n_ticks, drivers, speed=2.0, steer_clip=None):
+    def raceSeatsMany(self, states, n_ticks, drivers, speed=2.0, steer_clip=None, track=None, track_window=0,
+                      goal_dist=None):
         """``raceFollowGapMany`` with a driver per seat: ``drivers`` holds, for each of the P cars of a race, a
         ``policy.Policy``, a ``PyFollowGap`` or the string "fg" (this simulator's own FollowGap driver, as
         ``raceFollowGapMany`` builds it) — scripts/two_player/ with the network in some seats and simple_driver.py in
         the others.  ``steer_clip`` clamps the network's seats only (scripts/policy_driver.py uses 0.4189).  Returns
-        ``CarBatch.race_seats``'s tuple."""
+        ``CarBatch.race_seats``'s tuple.  ``track`` (a ``Track``): the cars are placed on it
+        (``CarBatch.attach_track`` for the call, ``track_window`` and ``goal_dist`` as it takes them) and
+        ``CarBatch.track_state``'s dict is appended to the tuple."""
         drivers = [self._mcts_source("fg", None) if isinstance(d, str) and d == "fg" else d for d in drivers]
-        return self.car.race_seats(self.scan_simulator.scan_method, drivers, np.asarray(states, dtype=np.float64),
+        return self._tracked(track, track_window, goal_dist, False, self.car.race_seats,
+                             self.scan_simulator.scan_method, drivers, np.asarray(states, dtype=np.float64),
                                    n_ticks, speed, self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
                                    steer_clip=steer_clip, scan_dist_to_base=self.scan_dist_to_base)
 
-    def drivePolicyMany(self, states, n_ticks, policy, speed=2.0, steer_clip=None):
+    def drivePolicyMany(self, states, n_ticks, policy, speed=2.0, steer_clip=None, track=None, track_window=0,
+                        goal_dist=None):
         """``driveFollowGapMany`` with the steer of every tick from ``policy`` (a ``policy.Policy``, e.g.
         ``Policy('model/frozen_model.pb')``): scripts/policy_driver.py's driver with ``steer_clip=0.4189``, MCTS's
         roll-out policy (scripts/mcts.py:252-256, the raw output) with None.  Returns
-        ``CarBatch.drive_policy``'s tuple."""
-        return self.car.drive_policy(self.scan_simulator.scan_method, policy,
+        ``CarBatch.drive_policy``'s tuple.  ``track`` (a ``Track``): the cars are placed on it
+        (``CarBatch.attach_track`` for the call, ``track_window`` and ``goal_dist`` as it takes them) and
+        ``CarBatch.track_state``'s dict is appended to the tuple."""
+        return self._tracked(track, track_window, goal_dist, False, self.car.drive_policy,
+                             self.scan_simulator.scan_method, policy,
                                      np.asarray(states, dtype=np.float64).reshape(-1, 11), n_ticks, speed,
                                      self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
                                      scan_dist_to_base=self.scan_dist_to_base, steer_clip=steer_clip)
 
-    def drivePopulationMany(self, states, n_ticks, pop, cars_per_member, speed=2.0, first=0, steer_clip=None):
+    def drivePopulationMany(self, states, n_ticks, pop, cars_per_member, speed=2.0, first=0, steer_clip=None, track=None,
+                            track_window=0, goal_dist=None):
         """``drivePolicyMany`` for a ``population.PolicyPopulation``: states (n E, 11), car r steered by member
         ``first + r // E`` (E = ``cars_per_member``), every member's network in one launch per tick.  Returns
-        ``CarBatch.drive_population``'s tuple, the (n, 2) ``fitness`` last."""
-        return self.car.drive_population(self.scan_simulator.scan_method, pop,
+        ``CarBatch.drive_population``'s tuple, the (n, 2) ``fitness`` last.  ``track`` (a ``Track``): the cars are placed
+        on it (``CarBatch.attach_track`` for the call, ``track_window`` and ``goal_dist`` as it takes them) and
+        ``CarBatch.track_state``'s dict is appended to the tuple, then ``CarBatch.track_scores``'s (n, 3)."""
+        return self._tracked(track, track_window, goal_dist, True, self.car.drive_population,
+                             self.scan_simulator.scan_method, pop,
                                          np.asarray(states, dtype=np.float64).reshape(-1, 11), n_ticks, speed,
                                          self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
                                          cars_per_member, first=first, steer_clip=steer_clip,
                                          scan_dist_to_base=self.scan_dist_to_base)
 
-    def raceLeagueMany(self, states, n_ticks, pop, entries, speed=2.0, steer_clip=None):
+    def raceLeagueMany(self, states, n_ticks, pop, entries, speed=2.0, steer_clip=None, track=None, track_window=0,
+                       goal_dist=None):
         """``raceSeatsMany`` with a line-up per race drawn from a ``population.PolicyPopulation``: ``entries`` int
         (R, P) names every car's driver, member m >= 0 of ``pop`` or -1 for this simulator's own FollowGap driver (as
         ``raceFollowGapMany`` builds it).  ``steer_clip`` clamps the members' cars only.  Returns
-        ``CarBatch.race_league``'s tuple, the (n_members, 4) ``standings`` last."""
+        ``CarBatch.race_league``'s tuple, the (n_members, 4) ``standings`` last.  ``track`` (a ``Track``): the cars are
+        placed on it (``CarBatch.attach_track`` for the call, ``track_window`` and ``goal_dist`` as it takes them) and
+        ``CarBatch.track_state``'s dict is appended to the tuple, then ``CarBatch.track_scores``'s
+        (n_members, 4)."""
         fg = self._mcts_source("fg", None) if (np.asarray(entries) < 0).any() else None
-        return self.car.race_league(self.scan_simulator.scan_method, pop, entries, np.asarray(states, dtype=np.float64),
+        return self._tracked(track, track_window, goal_dist, True, self.car.race_league,
+                             self.scan_simulator.scan_method, pop, entries, np.asarray(states, dtype=np.float64),
                                     n_ticks, speed, self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
                                     followgap=fg, steer_clip=steer_clip, scan_dist_to_base=self.scan_dist_to_base)
+
+    def _tracked(self, track, track_window, goal_dist, scores, rollout, *args, **kw):
+        """``rollout(*args, **kw)`` of ``self.car``; with a ``track`` it is attached for the call and detached
+        afterwards, and ``track_state`` (``scores``: then ``track_scores``) is appended to the result."""
+        if track is None:
+            return rollout(*args, **kw)
+        self.car.attach_track(track, track_window, goal_dist)
+        try:
+            res = rollout(*args, **kw)
+            extra = (self.car.track_state(),) + ((self.car.track_scores(),) if scores else ())
+        finally:
+            self.car.detach_track()
+        return tuple(res) + extra
 
     def _mcts_source(self, source, policy):
         if source == "fg":
