@@ -4,11 +4,11 @@ The library is the product: hand-written HIP kernels for gfx950 behind a C ABI.
 There is no Python/NumPy fallback — if the shared object is missing or no HIP
 device is usable, the calls raise.
 
-``SYMBOLS`` restates every prototype of the header (tests/test_py_calls_host.py pins it to the header, argument by
-argument, with the structures and enums below); ``EXT_SYMBOLS`` does the same for include/scanlib_track_plan.h and
-``SEAT_SYMBOLS`` for include/scanlib_seats.h, ``POP_SYMBOLS`` for include/scanlib_population.h, ``LEAGUE_SYMBOLS`` for
-include/scanlib_league.h, ``LEAGUE_ENV_SYMBOLS`` for include/scanlib_league_env.h and ``TRACK_DRIVE_SYMBOLS`` for
-include/scanlib_track_drive.h.
+``SYMBOLS`` restates every prototype of the header, and one table more does the same for each feature header next to
+it.  ``HEADERS`` is the one list of them: per public header its file, its table, the structures it declares with the
+classes that restate them, and its handle types (the list closes this text).  tests/test_py_calls_host.py pins every
+entry to its header, argument by argument, with the structures and enums below; ``declared``, ``lib`` and ``build``
+read the tables through ``HEADERS`` only.
 ``call(name, *args)`` is how the package's wrappers enter the library: every argument is converted by the type the
 tables declare for it, and a symbol that returns ``rl_status`` is checked (``ScanLibError``) and gives None.  What a
 declared type takes:
@@ -28,6 +28,7 @@ that keep the addresses of long-lived buffers.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import operator
 import os
@@ -270,8 +271,7 @@ SYMBOLS = {
     "rl_ranges_from_u16_device": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
 }
 
-#: every symbol include/scanlib_track_plan.h declares, in the shape of ``SYMBOLS`` (tests/test_mcts_track_host.py pins it
-#: to that header); ``raw``, ``converters`` and so ``call`` look here after ``SYMBOLS``
+#: every symbol include/scanlib_track_plan.h declares, in the shape of ``SYMBOLS``
 EXT_SYMBOLS = {
     "rl_car_rollout_track": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PlanTrackParams), f64p, f64p, C.c_int, C.c_int,
                                        C.c_int, C.c_double, C.POINTER(C.c_int), f64p, f64p, f64p, C.POINTER(C.c_int),
@@ -282,8 +282,7 @@ EXT_SYMBOLS = {
 }
 
 
-#: every symbol include/scanlib_seats.h declares, in the shape of ``SYMBOLS`` (tests/test_seats_host.py pins it to that
-#: header); looked up after ``EXT_SYMBOLS``
+#: every symbol include/scanlib_seats.h declares, in the shape of ``SYMBOLS``
 SEAT_SYMBOLS = {
     "rl_car_race_seats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_double, f64p,
                                     f64p, f32p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_float, C.c_int,
@@ -294,8 +293,8 @@ SEAT_SYMBOLS = {
 }
 
 
-#: every symbol include/scanlib_population.h declares, in the shape of ``SYMBOLS`` (tests/test_population_host.py pins it
-#: to that header); looked up after ``SEAT_SYMBOLS``.  Every ``int`` is an rl_status: sizes come back through pointers
+#: every symbol include/scanlib_population.h declares, in the shape of ``SYMBOLS``.  Every ``int`` is an rl_status:
+#: sizes come back through pointers
 POP_SYMBOLS = {
     "rl_policy_pop_create": (C.c_int, [C.c_int, C.c_int, C.c_int, i32p, u8p, C.c_int, C.c_float, C.c_float,
                                        C.POINTER(C.c_void_p)]),
@@ -313,8 +312,7 @@ POP_SYMBOLS = {
 }
 
 
-#: every symbol include/scanlib_league.h declares, in the shape of ``SYMBOLS`` (tests/test_league_host.py pins it to that
-#: header); looked up after ``POP_SYMBOLS``.  Every ``int`` is an rl_status
+#: every symbol include/scanlib_league.h declares, in the shape of ``SYMBOLS``.  Every ``int`` is an rl_status
 LEAGUE_SYMBOLS = {
     "rl_policy_pop_eval_rows": (C.c_int, [C.c_void_p, C.c_int, i32p, f32p, C.c_int, f32p]),
     "rl_policy_pop_eval_rows_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
@@ -325,8 +323,7 @@ LEAGUE_SYMBOLS = {
 }
 
 
-#: every symbol include/scanlib_league_env.h declares, in the shape of ``SYMBOLS`` (tests/test_league_env_host.py pins it
-#: to that header); looked up after ``LEAGUE_SYMBOLS``.  Every ``int`` is an rl_status
+#: every symbol include/scanlib_league_env.h declares, in the shape of ``SYMBOLS``.  Every ``int`` is an rl_status
 LEAGUE_ENV_SYMBOLS = {
     "rl_env_attach_league": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, i32p, f32p]),
     "rl_env_set_league_entries": (C.c_int, [C.c_void_p, i32p]),
@@ -338,8 +335,7 @@ LEAGUE_ENV_SYMBOLS = {
 }
 
 
-#: every symbol include/scanlib_track_drive.h declares, in the shape of ``SYMBOLS`` (tests/test_track_drive_host.py pins
-#: it to that header); looked up after ``LEAGUE_ENV_SYMBOLS``.  Every ``int`` is an rl_status
+#: every symbol include/scanlib_track_drive.h declares, in the shape of ``SYMBOLS``.  Every ``int`` is an rl_status
 TRACK_DRIVE_SYMBOLS = {
     "rl_car_attach_track": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DriveTrackParams)]),
     "rl_car_read_track": (C.c_int, [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_int)]),
@@ -347,14 +343,36 @@ TRACK_DRIVE_SYMBOLS = {
 }
 
 
-def declared(name):
-    """(restype, argtypes) of ``name`` from ``SYMBOLS``, then ``EXT_SYMBOLS``, ``SEAT_SYMBOLS``, ``POP_SYMBOLS``,
-    ``LEAGUE_SYMBOLS``, ``LEAGUE_ENV_SYMBOLS`` and ``TRACK_DRIVE_SYMBOLS``."""
-    for table in (SYMBOLS, EXT_SYMBOLS, SEAT_SYMBOLS, POP_SYMBOLS, LEAGUE_SYMBOLS, LEAGUE_ENV_SYMBOLS):
-        ent = table.get(name)
-        if ent is not None:
-            return ent
-    return TRACK_DRIVE_SYMBOLS[name]
+#: every public header, in the order the features came: its file under include/, the table of its symbols, {structure it
+#: declares: the class that restates it}, and the handle types it declares beyond those of scanlib.h
+Header = collections.namedtuple("Header", "file symbols structs handles")
+HEADERS = (
+    Header("scanlib.h", SYMBOLS, {"rl_plan_opts": PlanOpts, "rl_launch_plan": LaunchPlan, "rl_mcts_params": MctsParams,
+                                  "rl_pf_params": PfParams, "rl_env_params": EnvParams,
+                                  "rl_race_env_params": RaceEnvParams, "rl_track_params": TrackParams}, ()),
+    Header("scanlib_track_plan.h", EXT_SYMBOLS, {"rl_plan_track_params": PlanTrackParams}, ()),
+    Header("scanlib_seats.h", SEAT_SYMBOLS, {"rl_seat_params": SeatParams}, ()),
+    Header("scanlib_population.h", POP_SYMBOLS, {}, ("rl_policy_pop",)),
+    Header("scanlib_league.h", LEAGUE_SYMBOLS, {}, ()),
+    Header("scanlib_league_env.h", LEAGUE_ENV_SYMBOLS, {}, ()),
+    Header("scanlib_track_drive.h", TRACK_DRIVE_SYMBOLS, {"rl_drive_track_params": DriveTrackParams}, ()),
+)
+__doc__ += "\nThe public headers: %s.\n" % ", ".join("include/%s (%d symbols)" % (h.file, len(h.symbols)) for h in HEADERS)
+
+
+def _merge(headers):
+    """One dictionary of every header's symbols; a name two headers declare is an error."""
+    merged = {}
+    for h in headers:
+        if set(merged) & set(h.symbols):
+            raise ValueError("include/%s declares %s again" % (h.file, ", ".join(sorted(set(merged) & set(h.symbols)))))
+        merged.update(h.symbols)
+    return merged
+
+
+_DECLARED = _merge(HEADERS)
+#: (restype, argtypes) of a name, whichever header of ``HEADERS`` declares it; KeyError for any other
+declared = _DECLARED.__getitem__
 
 
 #: the symbols whose ``int`` is a value; every other ``int`` function returns rl_status (``call`` checks it)
@@ -386,14 +404,16 @@ class ScanLibError(RuntimeError):
         self.code = code
 
 
+def build_sources():
+    """The files ``build`` compares with the library: csrc's units and kernel headers, and every header of ``HEADERS``."""
+    return [os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc")) if f.endswith((".hip", ".h"))
+            ] + [os.path.join(_HERE, "..", "include", h.file) for h in HEADERS]
+
+
 def build(force: bool = False) -> str:
     """Compile libscan_amd.so for gfx950 with hipcc (in-tree; cross-compiles without a GPU)."""
-    srcs = [os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc"))
-            if f.endswith((".hip", ".h"))]
-    srcs += [os.path.join(_HERE, "..", "include", h) for h in ("scanlib.h", "scanlib_track_plan.h", "scanlib_seats.h", "scanlib_population.h", "scanlib_league.h",
-                                                                       "scanlib_league_env.h", "scanlib_track_drive.h")]
     stale = (not os.path.exists(_SO)) or any(os.path.getmtime(s) > os.path.getmtime(_SO)
-                                             for s in srcs)
+                                             for s in build_sources())
     if force or stale:
         subprocess.check_call(["make", "-j4", "-C", os.path.join(_HERE, "csrc"), "../libscan_amd.so"]
                               + (["-B"] if force else []))
@@ -435,9 +455,7 @@ def lib():
                 "g.build()'` (or make -C pyracecarsimulator_amd/csrc). There is no CPU fallback.")
         _share_torch_hip_runtime()
         L = C.CDLL(_SO)
-        for name, (res, args) in (list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()) + list(SEAT_SYMBOLS.items())
-                                  + list(POP_SYMBOLS.items()) + list(LEAGUE_SYMBOLS.items())
-                                  + list(LEAGUE_ENV_SYMBOLS.items()) + list(TRACK_DRIVE_SYMBOLS.items())):
+        for name, (res, args) in _DECLARED.items():
             try:
                 fn = getattr(L, name)
             except AttributeError:

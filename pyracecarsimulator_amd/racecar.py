@@ -162,7 +162,7 @@ class CarBatch(_lib.Handle):
         final states (R, 11), velocities float64 (R, n_ticks), steers float32 (R, n_ticks)) and with
         ``trace=True`` also (lidar poses float32 (R, n_ticks, 3), states float64 (R, n_ticks, 11)).  Trace
         rows after a car's crash tick, and its steer at that tick, are NaN."""
-        return self._drive("rl_car_drive_followgap", method, followgap, None, (), states, n_ticks, speed, fov,
+        return self._drive("rl_car_drive_followgap", (method, followgap), None, (), (), states, n_ticks, speed, fov,
                            num_rays, edge, crash_thresh, scan_dist_to_base, dt, steer0, trace)
 
     def outline_cells(self, omap, car_poses):
@@ -185,17 +185,9 @@ class CarBatch(_lib.Handle):
         None (0) or float32 (R, P).  Returns ``drive_followgap``'s tuple with R P reshaped to (R, P): first crash tick
         (R, P), final states (R, P, 11), velocities and steers (R, P, n_ticks), with ``trace=True`` also lidar poses
         (R, P, n_ticks, 3) and states (R, P, n_ticks, 11).  A crashed car stays in its race as a wreck."""
-        st = np.asarray(states)
-        if st.dtype != np.float64 or st.ndim != 3 or st.shape[2] != 11:
-            raise ValueError("states must be float64 (R, P, 11)")
-        n_races, group = st.shape[0], st.shape[1]
-        spd = np.asarray(speed, dtype=np.float64)
-        spd = float(spd) if spd.ndim == 0 else spd.reshape(-1)
-        st0 = None if steer0 is None else np.asarray(steer0).reshape(-1)
-        res = self._drive("rl_car_race_followgap", method, followgap, (n_races, group), (), st.reshape(-1, 11),
-                          n_ticks, spd, fov, num_rays, edge, crash_thresh, scan_dist_to_base, dt, st0, trace)
-        # every array's leading R P becomes (R, P)
-        return tuple(a.reshape((n_races, group) + a.shape[1:]) for a in res)
+        st, counts = self._race_states(states)
+        return self._drive("rl_car_race_followgap", (method, followgap), counts, (), (), st, n_ticks, speed, fov,
+                           num_rays, edge, crash_thresh, scan_dist_to_base, dt, steer0, trace)
 
     def race_seats(self, method, drivers, states, n_ticks, speed, fov, num_rays, edge, crash_thresh, steer_clip=None,
                    steer0=None, dt=0.01, trace=False, scan_dist_to_base=0.275):
@@ -206,24 +198,11 @@ class CarBatch(_lib.Handle):
         seats only.  The steers returned are each driver's raw answers.  Arguments and results as ``race_followgap``;
         with FollowGap in every seat it returns that call's bits."""
         from .seats import seat_args
-        st = np.asarray(states)
-        if st.dtype != np.float64 or st.ndim != 3 or st.shape[2] != 11:
-            raise ValueError("states must be float64 (R, P, 11)")
-        n_races, group = st.shape[0], st.shape[1]
-        codes, fg, pol = seat_args(drivers, group, num_rays, caller_ok=False)
-        clip = 0.0 if steer_clip is None else float(steer_clip)
-        if steer_clip is not None and not clip > 0:
-            raise ValueError("steer_clip must be None or > 0")
-        spd = np.asarray(speed, dtype=np.float64)
-        spd = float(spd) if spd.ndim == 0 else spd.reshape(-1)
-        st0 = None if steer0 is None else np.asarray(steer0).reshape(-1)
-        R, n_ticks, states, speeds, st0, edge, first, out, vel, steers, poses, trace_st = self._drive_args(
-            st.reshape(-1, 11), n_ticks, spd, num_rays, edge, st0, trace)
-        _lib.call("rl_car_race_seats", self, method, fg, pol, codes, clip, states, speeds, st0, n_races, group, n_ticks,
-                  dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh, first, out, vel, steers, poses, trace_st)
-        self._tracked((n_races, group))
-        res = (first, out, vel, steers) + ((poses, trace_st) if trace else ())
-        return tuple(a.reshape((n_races, group) + a.shape[1:]) for a in res)
+        st, counts = self._race_states(states)
+        codes, fg, pol = seat_args(drivers, counts[1], num_rays, caller_ok=False)
+        front = (method, fg, pol, codes, self._clip(steer_clip))
+        return self._drive("rl_car_race_seats", front, counts, (), (), st, n_ticks, speed, fov, num_rays, edge,
+                           crash_thresh, scan_dist_to_base, dt, steer0, trace)
 
     def drive_policy(self, method, policy, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
                      scan_dist_to_base=0.275, dt=0.01, steer0=None, steer_clip=None, trace=False):
@@ -232,11 +211,8 @@ class CarBatch(_lib.Handle):
         ``steer_clip`` None: the car gets the raw output (as scripts/mcts.py passes it to drive()); a value: the
         output clamped to +-steer_clip (policy_driver.py uses 0.4189).  The steers returned are the raw network
         outputs.  Arguments and results as ``drive_followgap``."""
-        clip = 0.0 if steer_clip is None else float(steer_clip)
-        if steer_clip is not None and not clip > 0:
-            raise ValueError("steer_clip must be None or > 0")
-        return self._drive("rl_car_drive_policy", method, policy, None, (clip,), states, n_ticks, speed, fov,
-                           num_rays, edge, crash_thresh, scan_dist_to_base, dt, steer0, trace)
+        return self._drive("rl_car_drive_policy", (method, policy), None, (self._clip(steer_clip),), (), states,
+                           n_ticks, speed, fov, num_rays, edge, crash_thresh, scan_dist_to_base, dt, steer0, trace)
 
     def drive_population(self, method, pop, states, n_ticks, speed, fov, num_rays, edge, crash_thresh, cars_per_member,
                          first=0, steer_clip=None, scan_dist_to_base=0.275, dt=0.01, steer0=None, trace=False):
@@ -245,28 +221,23 @@ class CarBatch(_lib.Handle):
         member ``first + r // E`` at every tick, every member's network in one launch.  Returns ``drive_policy``'s
         tuple plus ``fitness`` float64 (n, 2): per member the sum over its cars (ascending, each addition rounded) of
         travel_dist gained (state index 8), and the number of its cars that crashed."""
-        clip = 0.0 if steer_clip is None else float(steer_clip)
-        if steer_clip is not None and not clip > 0:
-            raise ValueError("steer_clip must be None or > 0")
+        clip = self._clip(steer_clip)
         E, first = int(cars_per_member), int(first)
         if E < 1:
             raise ValueError("cars_per_member must be >= 1")
-        R, n_ticks, states, speeds, st0, edge, first_crashed, out, vel, steers, poses, trace_st = self._drive_args(
-            states, n_ticks, speed, num_rays, edge, steer0, trace)
-        if R % E:
-            raise ValueError("states must hold a whole number of members: %d cars, %d per member" % (R, E))
-        n = R // E
-        if first < 0 or first + n > pop.n_members:
-            raise ValueError("members [%d, %d) do not lie in [0, %d)" % (first, first + n, pop.n_members))
-        if int(num_rays) < pop.in_start + pop.dims[0]:
-            raise ValueError("scans of %d beams do not hold the policy's window [%d, %d)"
-                             % (num_rays, pop.in_start, pop.in_start + pop.dims[0]))
-        fitness = np.zeros((n, 2), dtype=np.float64)
-        _lib.call("rl_car_drive_population", self, method, pop, first, n, E, clip, states, speeds, st0, n_ticks, dt,
-                  scan_dist_to_base, fov, num_rays, edge, crash_thresh, first_crashed, out, vel, steers, poses, trace_st,
-                  fitness)
-        self._tracked((R,), (n, 3))
-        return (first_crashed, out, vel, steers) + ((poses, trace_st) if trace else ()) + (fitness,)
+
+        def members(R):                                    # (the members are known once the cars are counted)
+            if R % E:
+                raise ValueError("states must hold a whole number of members: %d cars, %d per member" % (R, E))
+            n = R // E
+            if first < 0 or first + n > pop.n_members:
+                raise ValueError("members [%d, %d) do not lie in [0, %d)" % (first, first + n, pop.n_members))
+            if int(num_rays) < pop.in_start + pop.dims[0]:
+                raise ValueError("scans of %d beams do not hold the policy's window [%d, %d)"
+                                 % (num_rays, pop.in_start, pop.in_start + pop.dims[0]))
+            return (method, pop, first, n, E, clip), (np.zeros((n, 2), dtype=np.float64), (n, 3))
+        return self._drive("rl_car_drive_population", members, (), (), (), states, n_ticks, speed, fov, num_rays, edge,
+                           crash_thresh, scan_dist_to_base, dt, steer0, trace)
 
     def race_league(self, method, pop, entries, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
                     followgap=None, steer_clip=None, steer0=None, dt=0.01, trace=False, scan_dist_to_base=0.275):
@@ -277,26 +248,12 @@ class CarBatch(_lib.Handle):
         cars it entered, the sum of their travel_dist gains (ascending car index, each addition rounded), how many
         crashed, and how many cars of their own races they beat (alive longer, or as long with the larger gain)."""
         from .league import league_args
-        st = np.asarray(states)
-        if st.dtype != np.float64 or st.ndim != 3 or st.shape[2] != 11:
-            raise ValueError("states must be float64 (R, P, 11)")
-        n_races, group = st.shape[0], st.shape[1]
-        entry = league_args(entries, n_races, group, pop, followgap, num_rays)
-        clip = 0.0 if steer_clip is None else float(steer_clip)
-        if steer_clip is not None and not clip > 0:
-            raise ValueError("steer_clip must be None or > 0")
-        spd = np.asarray(speed, dtype=np.float64)
-        spd = float(spd) if spd.ndim == 0 else spd.reshape(-1)
-        st0 = None if steer0 is None else np.asarray(steer0).reshape(-1)
-        R, n_ticks, states, speeds, st0, edge, first, out, vel, steers, poses, trace_st = self._drive_args(
-            st.reshape(-1, 11), n_ticks, spd, num_rays, edge, st0, trace)
-        standings = np.zeros((pop.n_members, 4), dtype=np.float64)
-        _lib.call("rl_car_race_league", self, method, followgap, pop, entry, clip, states, speeds, st0, n_races, group,
-                  n_ticks, dt, scan_dist_to_base, fov, num_rays, edge, crash_thresh, first, out, vel, steers, poses,
-                  trace_st, standings)
-        self._tracked((n_races, group), (pop.n_members, 4))
-        res = (first, out, vel, steers) + ((poses, trace_st) if trace else ())
-        return tuple(a.reshape((n_races, group) + a.shape[1:]) for a in res) + (standings,)
+        st, counts = self._race_states(states)
+        entry = league_args(entries, counts[0], counts[1], pop, followgap, num_rays)
+        front = (method, followgap, pop, entry, self._clip(steer_clip))
+        scores = (np.zeros((pop.n_members, 4), dtype=np.float64), (pop.n_members, 4))
+        return self._drive("rl_car_race_league", front, counts, (), scores, st, n_ticks, speed, fov, num_rays, edge,
+                           crash_thresh, scan_dist_to_base, dt, steer0, trace)
 
     # -- track progress of the roll-outs (include/scanlib_track_drive.h) -----------------------------------
     _track = None             # the attached ``Track``, kept referenced: the library only borrows it
@@ -422,19 +379,47 @@ class CarBatch(_lib.Handle):
                            followgap=followgap_or_policy if source == "fg" else None,
                            policy=followgap_or_policy if source == "nn" else None, **kw)
 
-    def _drive(self, fn, method, source, counts, after_thresh, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
+    @staticmethod
+    def _clip(steer_clip):
+        """``steer_clip`` as the library takes it: 0 for None (the raw output), else a value > 0."""
+        if steer_clip is not None and not float(steer_clip) > 0:
+            raise ValueError("steer_clip must be None or > 0")
+        return 0.0 if steer_clip is None else float(steer_clip)
+
+    @staticmethod
+    def _race_states(states):
+        """A race's states float64 (R, P, 11) as an array, and (R, P): the car-count arguments of its roll-out."""
+        st = np.asarray(states)
+        if st.dtype != np.float64 or st.ndim != 3 or st.shape[2] != 11:
+            raise ValueError("states must be float64 (R, P, 11)")
+        return st, (st.shape[0], st.shape[1])
+
+    def _drive(self, fn, front, counts, after_thresh, scores, states, n_ticks, speed, fov, num_rays, edge, crash_thresh,
                scan_dist_to_base, dt, steer0, trace):
-        """The one library call of the closed loops: ``fn`` names rl_car_drive_followgap, rl_car_race_followgap or
-        rl_car_drive_policy, ``source`` the steering source's wrapper.  ``counts`` replaces (R,) as the car-count
-        arguments (races: (n_races, group)); ``after_thresh`` goes after crash_thresh (the policy's steer_clip)."""
+        """The one library call of the closed-loop roll-outs, ``fn``.  ``front``: what stands between the cars and
+        ``states_in`` (the method, the steering source's handles and arguments).  ``counts``: the car-count arguments,
+        None for (R,), () for none (a population), (n_races, group) for a race, whose states, speed and steer0 come
+        shaped (R, P, ...) and whose results go back that way.  ``after_thresh`` goes after crash_thresh (the policy's
+        steer_clip).  ``scores``: (), or the score array that goes last and the shape of the track scores of such a
+        roll-out.  Where these depend on the number of cars, ``front`` is a function of it that gives (front, scores)."""
+        race = counts is not None and len(counts) == 2
+        if race:
+            states = states.reshape(-1, 11)
+            speed = np.asarray(speed, dtype=np.float64)
+            speed = float(speed) if speed.ndim == 0 else speed.reshape(-1)
+            steer0 = None if steer0 is None else np.asarray(steer0).reshape(-1)
         R, n_ticks, states, speeds, st0, edge, first, out, vel, steers, poses, trace_st = self._drive_args(
             states, n_ticks, speed, num_rays, edge, steer0, trace)
-        _lib.call(fn, self, method, source, states, speeds, st0, *(counts or (R,)), n_ticks, dt, scan_dist_to_base, fov,
-                  num_rays, edge, crash_thresh, *after_thresh, first, out, vel, steers, poses, trace_st)
-        self._tracked(counts or (R,))
-        if trace:
-            return first, out, vel, steers, poses, trace_st
-        return first, out, vel, steers
+        if callable(front):
+            front, scores = front(R)
+        _lib.call(fn, self, *front, states, speeds, st0, *((R,) if counts is None else counts), n_ticks, dt,
+                  scan_dist_to_base, fov, num_rays, edge, crash_thresh, *after_thresh, first, out, vel, steers, poses,
+                  trace_st, *scores[:1])
+        self._tracked(counts if race else (R,), *scores[1:])
+        res = (first, out, vel, steers) + ((poses, trace_st) if trace else ())
+        if race:                                           # every array's leading R P becomes (R, P)
+            res = tuple(a.reshape(counts + a.shape[1:]) for a in res)
+        return res + scores[:1]
 
     @staticmethod
     def _drive_args(states, n_ticks, speed, num_rays, edge, steer0, trace):

@@ -1,37 +1,23 @@
-"""include/scanlib.h read with regular expressions, as ctypes: its prototypes, structures and enums, for the tests that
-pin ``_lib``'s restatement to it.  Anything the mapping does not know raises ``HeaderError``.  No tests live here."""
+"""A public header of ``_lib.HEADERS`` read with regular expressions, as ctypes: its prototypes, structures and enums,
+for the tests that pin ``_lib``'s restatement to it.  Anything the mapping does not know raises ``HeaderError``.  No
+tests live here."""
 import ctypes as C
 import os
 import re
 
 from pyracecarsimulator_amd import _lib
 
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "scanlib.h")
+INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 
 SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "uint8_t": C.c_uint8,
            "unsigned char": C.c_uint8, "uint16_t": C.c_uint16, "int32_t": C.c_int32, "uint64_t": C.c_uint64,
            "int64_t": C.c_int64}
-#: the header's structures and the classes that restate them
-STRUCTS = {"rl_plan_opts": _lib.PlanOpts, "rl_launch_plan": _lib.LaunchPlan, "rl_mcts_params": _lib.MctsParams,
-           "rl_pf_params": _lib.PfParams, "rl_env_params": _lib.EnvParams, "rl_race_env_params": _lib.RaceEnvParams,
-           "rl_track_params": _lib.TrackParams}
+#: the headers' structures and the classes that restate them: every header may name every one
+STRUCTS = {name: cls for h in _lib.HEADERS for name, cls in h.structs.items()}
 
 
 class HeaderError(AssertionError):
     """A construct of the header the mapping to ctypes does not know."""
-
-
-def text():
-    """The header without comments and preprocessor lines."""
-    s = open(HEADER).read()
-    s = re.sub(r"/\*.*?\*/", " ", s, flags=re.S)
-    s = re.sub(r"//[^\n]*", " ", s)
-    return re.sub(r"^[ \t]*#.*$", "", s, flags=re.M)
-
-
-def handles(s=None):
-    """The opaque handle types: ``typedef struct rl_x rl_x;``."""
-    return set(re.findall(r"typedef\s+struct\s+(rl_\w+)\s+\1\s*;", s or text()))
 
 
 def ctype(decl, name="", opaque=()):
@@ -72,57 +58,79 @@ def _split(declarator):
     return m.group(1), m.group(2), (int(m.group(3)) if m.group(3) else None)
 
 
-def prototypes():
-    """{name: (restype, [argtypes], [parameter names])} of every ``rl_*`` function the header declares."""
-    s = text()
-    opaque = handles(s)
-    out = {}
-    for ret, name, params in re.findall(r"([\w\s\*]+?)\b(rl_\w+)\s*\(([^(){};]*)\)\s*;", s):
-        args, names = [], []
-        if params.strip() != "void":
-            for p in params.split(","):
-                decl, pname, n = _split(p)
-                if n is not None:
-                    raise HeaderError("array parameter %r of %s" % (p, name))
-                args.append(ctype(decl, pname, opaque))
-                names.append(pname)
-        if name in out:
-            raise HeaderError("%s is declared twice" % name)
-        out[name] = (ctype(ret, "", opaque), args, names)
-    declared = set(re.findall(r"\b(rl_[a-z_0-9]+)\s*\(", s))
-    if declared != set(out):
-        raise HeaderError("prototypes the parser did not read: %s" % sorted(declared ^ set(out)))
-    return out
+class Header:
+    """One entry of ``_lib.HEADERS`` read from its file."""
+
+    def __init__(self, entry):
+        self.entry = entry
+        self.path = os.path.join(INCLUDE, entry.file)
+
+    def text(self):
+        """The header without comments and preprocessor lines."""
+        s = open(self.path).read()
+        s = re.sub(r"/\*.*?\*/", " ", s, flags=re.S)
+        s = re.sub(r"//[^\n]*", " ", s)
+        return re.sub(r"^[ \t]*#.*$", "", s, flags=re.M)
+
+    def handles(self):
+        """The opaque handle types it declares: ``typedef struct rl_x rl_x;``."""
+        return set(re.findall(r"typedef\s+struct\s+(rl_\w+)\s+\1\s*;", self.text()))
+
+    def prototypes(self):
+        """{name: (restype, [argtypes], [parameter names])} of every ``rl_*`` function the header declares."""
+        s = self.text()
+        # the handle types it may name: scanlib.h's, and what the registry says the others declare
+        opaque = Header(_lib.HEADERS[0]).handles() | {t for h in _lib.HEADERS for t in h.handles}
+        out = {}
+        for ret, name, params in re.findall(r"([\w\s\*]+?)\b(rl_\w+)\s*\(([^(){};]*)\)\s*;", s):
+            args, names = [], []
+            if params.strip() != "void":
+                for p in params.split(","):
+                    decl, pname, n = _split(p)
+                    if n is not None:
+                        raise HeaderError("array parameter %r of %s" % (p, name))
+                    args.append(ctype(decl, pname, opaque))
+                    names.append(pname)
+            if name in out:
+                raise HeaderError("%s is declared twice" % name)
+            out[name] = (ctype(ret, "", opaque), args, names)
+        declared = set(re.findall(r"\b(rl_[a-z_0-9]+)\s*\(", s))
+        if declared != set(out):
+            raise HeaderError("prototypes the parser did not read: %s" % sorted(declared ^ set(out)))
+        return out
+
+    def structs(self):
+        """{struct name: [(field, ctype), ...]} in declaration order (``int a, b;`` gives two fields, ``x[3]`` an array)."""
+        out = {}
+        for name, body in re.findall(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;", self.text()):
+            fields = []
+            for stmt in body.split(";"):
+                if not stmt.strip():
+                    continue
+                first, *rest = stmt.split(",")
+                if "*" in "".join(rest):
+                    raise HeaderError("pointer in a joined declarator: %r" % stmt)
+                decl, fname, n = _split(first)
+                t = ctype(decl)
+                for fname, n in [(fname, n)] + [_split("int " + r)[1:] for r in rest]:    # (the type text is the first one's)
+                    fields.append((fname, t * n if n else t))
+            out[name] = fields
+        return out
+
+    def enums(self):
+        """{enum name: {constant: value}}; every constant carries its value in the header."""
+        out = {}
+        for name, body in re.findall(r"typedef\s+enum\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;", self.text()):
+            vals = {}
+            for item in body.split(","):
+                m = re.fullmatch(r"\s*(\w+)\s*=\s*(-?\d+)\s*", item)
+                if not m:
+                    raise HeaderError("enum %s: cannot read %r" % (name, item))
+                vals[m.group(1)] = int(m.group(2))
+            out[name] = vals
+        return out
 
 
-def structs():
-    """{struct name: [(field, ctype), ...]} in declaration order (``int a, b;`` gives two fields, ``x[3]`` an array)."""
-    out = {}
-    for name, body in re.findall(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;", text()):
-        fields = []
-        for stmt in body.split(";"):
-            if not stmt.strip():
-                continue
-            first, *rest = stmt.split(",")
-            if "*" in "".join(rest):
-                raise HeaderError("pointer in a joined declarator: %r" % stmt)
-            decl, fname, n = _split(first)
-            t = ctype(decl)
-            for fname, n in [(fname, n)] + [_split("int " + r)[1:] for r in rest]:    # (the type text is the first one's)
-                fields.append((fname, t * n if n else t))
-        out[name] = fields
-    return out
-
-
-def enums():
-    """{enum name: {constant: value}}; every constant carries its value in the header."""
-    out = {}
-    for name, body in re.findall(r"typedef\s+enum\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;", text()):
-        vals = {}
-        for item in body.split(","):
-            m = re.fullmatch(r"\s*(\w+)\s*=\s*(-?\d+)\s*", item)
-            if not m:
-                raise HeaderError("enum %s: cannot read %r" % (name, item))
-            vals[m.group(1)] = int(m.group(2))
-        out[name] = vals
-    return out
+def read(file):
+    """The ``Header`` of the registry's entry for include/``file``."""
+    return Header(next(h for h in _lib.HEADERS if h.file == file))

@@ -1,11 +1,10 @@
 """League line-ups in the race environment without a GPU: the statement (tests/league_env_statement.py) on the fake
 one-dimensional world of test_race_env_host.py — adoption only at a spawn, every clause of "beats", the results'
-columns — include/scanlib_league_env.h pinned to ``_lib.LEAGUE_ENV_SYMBOLS`` prototype by prototype, the six symbol
-tables disjoint and every Python-side refusal."""
+columns — what include/scanlib_league_env.h says beyond its prototypes (tests/test_py_calls_host.py pins those to
+``_lib.LEAGUE_ENV_SYMBOLS``) and every Python-side refusal."""
 import ctypes as C
 import inspect
 import math
-import os
 import re
 
 import numpy as np
@@ -14,12 +13,11 @@ import pytest
 import env_statement as E
 import league_env_statement as LE
 import scanlib_header as H
-from conftest import ROOT
 from test_population_host import _pop, no_calls  # noqa: F401  (no_calls: a fixture)
 from test_race_env_host import B, World1D, _acts, _lineup
 from pyracecarsimulator_amd import RaceEnv, _lib, league
 
-HEADER = os.path.join(ROOT, "include", "scanlib_league_env.h")
+HEADER = H.read("scanlib_league_env.h")
 N_MEMBERS = 3
 
 
@@ -212,59 +210,25 @@ def test_the_spawn_draw_is_the_race_envs():
     assert env.race_start_index.tolist() == [E.spawn_index(4, r, 1, 3) for r in range(2)]
 
 
-# ---------------------------------------------------------------- the header against the table
-@pytest.fixture
-def league_env_header(monkeypatch):
-    opaque = H.handles() | {"rl_policy_pop"}
-    monkeypatch.setattr(H, "HEADER", HEADER)
-    monkeypatch.setattr(H, "handles", lambda s=None: opaque)
-    return H
-
-
-def test_header_is_pinned_to_league_env_symbols(league_env_header):
-    protos = league_env_header.prototypes()
-    assert set(protos) == set(_lib.LEAGUE_ENV_SYMBOLS) and len(protos) == 7
-    for name, (res, args, names) in protos.items():
-        bound_res, bound_args = _lib.LEAGUE_ENV_SYMBOLS[name]
-        assert bound_res is res is C.c_int, name
-        assert len(bound_args) == len(args), (name, names)
-        for i, (got, want) in enumerate(zip(bound_args, args)):
-            assert got is want, "%s argument %d (%s): the table has %s, the header %s" % (name, i, names[i], got, want)
+# ---------------------------------------------------------------- the header
+def test_header_is_pinned_to_league_env_symbols():
+    protos = HEADER.prototypes()
     assert protos["rl_env_attach_league"][2] == ["e", "g_or_null", "pop", "entry_N_or_null", "speed_P"]
     assert protos["rl_env_read_league_results"][2] == ["e", "results", "clear"]
     assert protos["rl_env_read_league_results"][1][1] is C.POINTER(C.c_int64)
     for name in ("rl_env_set_league_entries_device", "rl_env_read_league_steers_device"):
         assert protos[name][2][-1] == "hip_stream"
         assert protos[name][1] == list(_lib.SEAT_SYMBOLS["rl_env_read_seats_device"][1])
-    assert not league_env_header.structs() and not league_env_header.handles(league_env_header.text()) - H.handles()
-    assert not set(_lib.LEAGUE_ENV_SYMBOLS) & _lib.INT_VALUED
-    raw = open(HEADER).read()
+    assert not HEADER.structs() and not HEADER.handles()
+    raw = open(HEADER.path).read()
     assert '#include "scanlib_league.h"' in raw and raw.count("#include") == 1
     assert "Out of scope" in raw and "Errors (RL_ERR_INVALID" in raw
     for phrase in ("Ties and NaN beat nobody", "never re-seated", "behaves as -2, by construction", "reset does not clear them",
                    "64-bit vector atomics", "FollowGap's, then the population's", "graph capture",
                    "A race cut off by a reset adds nothing"):
         assert phrase in raw, phrase
-    assert set(re.findall(r"\b(rl_[a-z_0-9]+)\s*\(", league_env_header.text())) == set(_lib.LEAGUE_ENV_SYMBOLS)
     assert (league.CALLER, league.FOLLOWGAP) == (LE.CALLER, LE.FOLLOWGAP) == (-2, -1)
     assert league.RESULT_COLUMNS == LE.COLUMNS and len(LE.COLUMNS) == 8
-
-
-def test_six_tables_are_disjoint_and_the_library_exports_the_league_env():
-    tables = (_lib.SYMBOLS, _lib.EXT_SYMBOLS, _lib.SEAT_SYMBOLS, _lib.POP_SYMBOLS, _lib.LEAGUE_SYMBOLS,
-              _lib.LEAGUE_ENV_SYMBOLS)
-    assert len(set().union(*tables)) == sum(len(t) for t in tables)
-    assert [len(t) for t in tables] == [105, 4, 4, 9, 3, 7]
-    L = _lib.lib()
-    for name, (res, args) in _lib.LEAGUE_ENV_SYMBOLS.items():
-        fn = getattr(L, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-        assert _lib.declared(name) == (res, args), name
-        assert _lib.converters(name)[2] is True, name               # (rl_status: call checks it)
-    assert _lib.declared("rl_car_race_league") is _lib.LEAGUE_SYMBOLS["rl_car_race_league"]
-    with pytest.raises(KeyError):
-        _lib.declared("rl_no_such_symbol")
-    assert "scanlib_league_env.h" in inspect.getsource(_lib.build)
     import pyracecarsimulator_amd as P
     for name in ("attach_league", "set_entries", "entries", "league_steers", "league_results"):
         assert callable(getattr(P.RaceEnv, name)), name

@@ -1,12 +1,10 @@
 """League races without a GPU: the grouping, the roll-out and the standings (tests/league_statement.py) in plain Python
-and on a fake one-dimensional world, include/scanlib_league.h pinned to ``_lib.LEAGUE_SYMBOLS`` prototype by prototype,
-the five symbol tables disjoint, ``round_robin``'s balance and every Python-side refusal."""
+and on a fake one-dimensional world, what include/scanlib_league.h says beyond its prototypes
+(tests/test_py_calls_host.py pins those to ``_lib.LEAGUE_SYMBOLS``), ``round_robin``'s balance and every Python-side
+refusal."""
 import ctypes as C
-import inspect
 import itertools
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -14,13 +12,12 @@ import pytest
 import league_statement as LS
 import policy_statement as S
 import scanlib_header as H
-from conftest import ROOT
 from test_population_host import DIMS, _layers, _pop, no_calls  # noqa: F401  (no_calls: a fixture)
 from test_race_env_host import B, World1D, _lineup
 from pyracecarsimulator_amd import _lib, league, population
 from pyracecarsimulator_amd import racecar as RC
 
-LEAGUE_HEADER = os.path.join(ROOT, "include", "scanlib_league.h")
+LEAGUE_HEADER = H.read("scanlib_league.h")
 
 
 # ---------------------------------------------------------------- the grouping
@@ -137,25 +134,9 @@ def test_standings_order_ties_and_nan():
     assert edge[:, 3].tolist() == [0.0, 1.0]
 
 
-# ---------------------------------------------------------------- the header against the table
-@pytest.fixture
-def league_header(monkeypatch):
-    """tests/scanlib_header.py reading the league header: its handle types are scanlib.h's and the population's."""
-    opaque = H.handles() | {"rl_policy_pop"}
-    monkeypatch.setattr(H, "HEADER", LEAGUE_HEADER)
-    monkeypatch.setattr(H, "handles", lambda s=None: opaque)
-    return H
-
-
-def test_league_header_is_pinned_to_league_symbols(league_header):
-    protos = league_header.prototypes()
-    assert set(protos) == set(_lib.LEAGUE_SYMBOLS) and len(protos) == 3
-    for name, (res, args, names) in protos.items():
-        bound_res, bound_args = _lib.LEAGUE_SYMBOLS[name]
-        assert bound_res is res is C.c_int, name
-        assert len(bound_args) == len(args), (name, names)
-        for i, (got, want) in enumerate(zip(bound_args, args)):
-            assert got is want, "%s argument %d (%s): the table has %s, the header %s" % (name, i, names[i], got, want)
+# ---------------------------------------------------------------- the header
+def test_league_header_is_pinned_to_league_symbols():
+    protos = LEAGUE_HEADER.prototypes()
     # rl_car_race_league: rl_car_race_seats' arguments from states_in on, behind its own six, the standings last
     names = protos["rl_car_race_league"][2]
     assert names[:6] == ["c", "h", "g_or_null", "pop", "entry_RP", "steer_clip"]
@@ -167,33 +148,13 @@ def test_league_header_is_pinned_to_league_symbols(league_header):
     ev = list(_lib.POP_SYMBOLS["rl_policy_pop_eval"][1])
     assert protos["rl_policy_pop_eval_rows"][1] == [ev[0], C.c_int, _lib.i32p] + ev[4:]
     assert protos["rl_policy_pop_eval_rows_device"][2][-1] == "hip_stream"
-    assert not league_header.structs() and not league_header.handles(league_header.text()) - H.handles()
-    assert not set(_lib.LEAGUE_SYMBOLS) & _lib.INT_VALUED
-    raw = open(LEAGUE_HEADER).read()
+    assert not LEAGUE_HEADER.structs() and not LEAGUE_HEADER.handles()
+    raw = open(LEAGUE_HEADER.path).read()
     assert '#include "scanlib_population.h"' in raw and '#include "scanlib_seats.h"' in raw
     assert "Out of scope" in raw and "Errors (RL_ERR_INVALID" in raw
     for phrase in ("ascending car index", "keeps its bits", "never clipped", "ties and\n *            NaN beat nobody",
                    "ceil(n / 8) + min(n, n_members)", "rl_car_race_followgap bit for bit", "rl_car_drive_population"):
         assert phrase in raw, phrase
-    assert set(re.findall(r"\b(rl_[a-z_0-9]+)\s*\(", league_header.text())) == set(_lib.LEAGUE_SYMBOLS)
-
-
-def test_five_tables_are_disjoint_and_the_library_exports_the_league():
-    tables = (_lib.SYMBOLS, _lib.EXT_SYMBOLS, _lib.SEAT_SYMBOLS, _lib.POP_SYMBOLS, _lib.LEAGUE_SYMBOLS)
-    assert len(set().union(*tables)) == sum(len(t) for t in tables)
-    assert [len(t) for t in tables] == [105, 4, 4, 9, 3]
-    L = _lib.lib()
-    for name, (res, args) in _lib.LEAGUE_SYMBOLS.items():
-        fn = getattr(L, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-        assert _lib.declared(name) == (res, args), name
-        assert _lib.converters(name)[2] is True, name                              # (rl_status: call checks it)
-        assert len(_lib.converters(name)[1]) == len(args)
-    assert _lib.declared("rl_car_race_league") is _lib.LEAGUE_SYMBOLS["rl_car_race_league"]
-    assert _lib.declared("rl_policy_pop_eval") is _lib.POP_SYMBOLS["rl_policy_pop_eval"]
-    with pytest.raises(KeyError):
-        _lib.declared("rl_no_such_symbol")
-    assert "scanlib_league.h" in inspect.getsource(_lib.build)
     import pyracecarsimulator_amd as P
     assert P.league is league and P.round_robin is league.round_robin and {"league", "round_robin"} <= set(P.__all__)
     assert hasattr(P.RacecarSimulator, "raceLeagueMany") and hasattr(P.PolicyPopulation, "predict_rows_device")

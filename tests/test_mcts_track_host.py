@@ -1,10 +1,8 @@
 """Track-guided MCTS without a GPU: the statement (tests/mcts_track_statement.py) against literal transcriptions of the
-reference's findBestPoint and waypoint reward, known answers of the progress terms, include/scanlib_track_plan.h pinned
-to ``_lib.EXT_SYMBOLS`` and its structure prototype by prototype, and every Python-side argument check."""
-import ctypes as C
+reference's findBestPoint and waypoint reward, known answers of the progress terms, what include/scanlib_track_plan.h
+says beyond its prototypes (tests/test_py_calls_host.py pins those to ``_lib.EXT_SYMBOLS``), and every Python-side
+argument check."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,13 +11,14 @@ import mcts_statement as MS
 import mcts_track_statement as S
 import scanlib_header as H
 import track_statement as TS
-from conftest import GOLD, ROOT
+from conftest import GOLD
+from test_population_host import no_calls  # noqa: F401  (a fixture)
 from test_track_host import SQUARE, wp_u
 from pyracecarsimulator_amd import Track, _lib
 from pyracecarsimulator_amd import racecar as RC
 from pyracecarsimulator_amd.mcts import MCTS, REWARDS, MCTSPlanner, plan_track_args, points_args
 
-EXT_HEADER = os.path.join(ROOT, "include", "scanlib_track_plan.h")
+EXT = H.read("scanlib_track_plan.h")
 
 
 # ---------------------------------------------------------------- the reference's lines, literally
@@ -122,63 +121,20 @@ def test_progress_terms_on_the_square():
     assert S.progress_terms(line, 0, 3, (9.5, 1.0), [(0.5, 1.0)])[0].tolist() == [-9.0]
 
 
-# ---------------------------------------------------------------- the header against the tables
-@pytest.fixture
-def ext(monkeypatch):
-    """tests/scanlib_header.py reading the extension header: its handle types come from scanlib.h."""
-    opaque = H.handles()
-    structs = dict(H.STRUCTS, rl_plan_track_params=_lib.PlanTrackParams)
-    monkeypatch.setattr(H, "HEADER", EXT_HEADER)
-    monkeypatch.setattr(H, "STRUCTS", structs)
-    monkeypatch.setattr(H, "handles", lambda s=None: opaque)
-    return H
-
-
-def test_extension_header_is_pinned_to_ext_symbols(ext):
-    protos = ext.prototypes()
-    assert set(protos) == set(_lib.EXT_SYMBOLS) and len(protos) == 4
-    for name, (res, args, names) in protos.items():
-        bound_res, bound_args = _lib.EXT_SYMBOLS[name]
-        assert bound_res is res is C.c_int, name
-        assert len(bound_args) == len(args), (name, names)
-        for i, (got, want) in enumerate(zip(bound_args, args)):
-            assert got is want, "%s argument %d (%s): the table has %s, the header %s" % (name, i, names[i], got, want)
-    declared = ext.structs()
-    assert set(declared) == {"rl_plan_track_params"} and ext.enums() == {}
-    fields = [(n, t) for n, t in _lib.PlanTrackParams._fields_]
-    assert [n for n, _ in fields] == [n for n, _ in declared["rl_plan_track_params"]] == \
+# ---------------------------------------------------------------- the header
+def test_extension_header_is_pinned_to_ext_symbols():
+    declared = EXT.structs()
+    assert set(declared) == {"rl_plan_track_params"} and EXT.enums() == {}
+    assert [n for n, _ in _lib.PlanTrackParams._fields_] == [n for n, _ in declared["rl_plan_track_params"]] == \
         ["reward_mode", "window", "goal_span", "lookahead"]
-    for (n, got), (_, want) in zip(fields, declared["rl_plan_track_params"]):
-        assert got is want, n
     # the header carries its contract and builds on scanlib.h
-    raw = open(EXT_HEADER).read()
+    raw = open(EXT.path).read()
     assert '#include "scanlib.h"' in raw and "reward_mode 2 (progress)" in raw and "Errors (RL_ERR_INVALID" in raw
-    assert set(re.findall(r"\b(rl_[a-z_0-9]+)\s*\(", ext.text())) == set(_lib.EXT_SYMBOLS)
-
-
-def test_tables_are_disjoint_and_the_library_exports_the_extension():
-    assert not set(_lib.SYMBOLS) & set(_lib.EXT_SYMBOLS)
-    L = _lib.lib()
-    for name, (res, args) in _lib.EXT_SYMBOLS.items():
-        fn = getattr(L, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-        assert _lib.declared(name) == (res, args) and _lib.converters(name)[2], name      # (rl_status: call checks it)
-        assert len(_lib.converters(name)[1]) == len(args)
-    assert _lib.declared("rl_mcts_run") is _lib.SYMBOLS["rl_mcts_run"]
-    with pytest.raises(KeyError):
-        _lib.declared("rl_no_such_symbol")
     assert REWARDS == {"velocity": 0, "waypoint": 1, "progress": 2}
     assert not [n for n in vars(_lib) if n.startswith("RL_") and ("TRACK" in n or "PLAN" in n)]
 
 
 # ---------------------------------------------------------------- the wrappers' refusals
-@pytest.fixture
-def no_calls(monkeypatch):
-    def refuse(name, *a):
-        raise AssertionError("the library was entered at %s" % name)
-    monkeypatch.setattr(_lib, "call", refuse)
-
-
 def test_plan_track_args(no_calls):
     p = plan_track_args()
     assert (p.reward_mode, p.window, p.goal_span, p.lookahead) == (2, 0, 0, 1.5)

@@ -1,8 +1,7 @@
 """Policy populations without a GPU: θ's order and the statements (tests/population_statement.py) on a fake
-one-dimensional world, include/scanlib_population.h pinned to ``_lib.POP_SYMBOLS`` prototype by prototype, the four
-symbol tables disjoint, and every Python-side refusal."""
+one-dimensional world, what include/scanlib_population.h says beyond its prototypes (tests/test_py_calls_host.py pins
+those to ``_lib.POP_SYMBOLS``), and every Python-side refusal."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -11,13 +10,12 @@ import pytest
 import policy_statement as S
 import population_statement as PS
 import scanlib_header as H
-from conftest import ROOT
 from test_race_env_host import B, World1D, _lineup
 from pyracecarsimulator_amd import PolicyPopulation, _lib, population
 from pyracecarsimulator_amd import racecar as RC
 from pyracecarsimulator_amd.policy import Policy
 
-POP_HEADER = os.path.join(ROOT, "include", "scanlib_population.h")
+POP_HEADER = H.read("scanlib_population.h")
 DIMS = (13, 7, 5, 1)
 
 
@@ -106,26 +104,10 @@ def test_population_rollout_statement():
     assert up == 1e16 and up != ((1.0 + 1.0) + 1.0) + 1e16
 
 
-# ---------------------------------------------------------------- the header against the table
-@pytest.fixture
-def pop_header(monkeypatch):
-    """tests/scanlib_header.py reading the population header: its own handle type on top of scanlib.h's."""
-    opaque = H.handles() | {"rl_policy_pop"}
-    monkeypatch.setattr(H, "HEADER", POP_HEADER)
-    monkeypatch.setattr(H, "handles", lambda s=None: opaque)
-    return H
-
-
-def test_population_header_is_pinned_to_pop_symbols(pop_header):
-    protos = pop_header.prototypes()
-    assert set(protos) == set(_lib.POP_SYMBOLS) and len(protos) == 9
-    for name, (res, args, names) in protos.items():
-        bound_res, bound_args = _lib.POP_SYMBOLS[name]
-        assert bound_res is res, name
-        assert res is C.c_int or name == "rl_policy_pop_destroy", name
-        assert len(bound_args) == len(args), (name, names)
-        for i, (got, want) in enumerate(zip(bound_args, args)):
-            assert got is want, "%s argument %d (%s): the table has %s, the header %s" % (name, i, names[i], got, want)
+# ---------------------------------------------------------------- the header
+def test_population_header_is_pinned_to_pop_symbols():
+    protos = POP_HEADER.prototypes()
+    assert all(res is C.c_int or name == "rl_policy_pop_destroy" for name, (res, _, _) in protos.items())
     # rl_car_drive_population: rl_car_drive_policy's arguments behind its own seven, steer_clip moved up, fitness last
     names = protos["rl_car_drive_population"][2]
     assert names[:7] == ["c", "h", "pop", "first", "n", "cars_per_member", "steer_clip"]
@@ -135,35 +117,11 @@ def test_population_header_is_pinned_to_pop_symbols(pop_header):
     # rl_policy_pop_create: rl_policy_create's without the weights, n_members second
     create = list(_lib.SYMBOLS["rl_policy_create"][1])
     assert protos["rl_policy_pop_create"][1] == create[:1] + [C.c_int] + create[1:3] + create[5:]
-    assert not pop_header.structs()
-    assert re.search(r"typedef\s+struct\s+rl_policy_pop\s+rl_policy_pop\s*;", pop_header.text())
-    # every int is an rl_status: nothing of the table is int-valued
-    assert not set(_lib.POP_SYMBOLS) & _lib.INT_VALUED
-    raw = open(POP_HEADER).read()
+    assert not POP_HEADER.structs()
+    assert re.search(r"typedef\s+struct\s+rl_policy_pop\s+rl_policy_pop\s*;", POP_HEADER.text())
+    raw = open(POP_HEADER.path).read()
     assert '#include "scanlib.h"' in raw and "Out of scope" in raw and "Errors (RL_ERR_INVALID" in raw
     assert "first + i / E" in raw and "first + r / E" in raw and "ascending car order" in raw
-    assert set(re.findall(r"\b(rl_[a-z_0-9]+)\s*\(", pop_header.text())) == set(_lib.POP_SYMBOLS)
-
-
-def test_four_tables_are_disjoint_and_the_library_exports_the_population():
-    tables = (_lib.SYMBOLS, _lib.EXT_SYMBOLS, _lib.SEAT_SYMBOLS, _lib.POP_SYMBOLS)
-    assert len(set().union(*tables)) == sum(len(t) for t in tables)
-    assert (len(_lib.SYMBOLS), len(_lib.EXT_SYMBOLS), len(_lib.SEAT_SYMBOLS)) == (105, 4, 4)
-    L = _lib.lib()
-    for name, (res, args) in _lib.POP_SYMBOLS.items():
-        fn = getattr(L, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-        assert _lib.declared(name) == (res, args), name
-        assert _lib.converters(name)[2] == (res is C.c_int), name                  # (rl_status: call checks it)
-        assert len(_lib.converters(name)[1]) == len(args)
-    assert _lib.declared("rl_policy_pop_eval") is _lib.POP_SYMBOLS["rl_policy_pop_eval"]
-    assert _lib.declared("rl_env_read_seats") is _lib.SEAT_SYMBOLS["rl_env_read_seats"]
-    assert _lib.declared("rl_policy_eval") is _lib.SYMBOLS["rl_policy_eval"]
-    with pytest.raises(KeyError):
-        _lib.declared("rl_no_such_symbol")
-    # the rebuild looks at the new header
-    import inspect
-    assert "scanlib_population.h" in inspect.getsource(_lib.build)
 
 
 # ---------------------------------------------------------------- the wrappers' refusals

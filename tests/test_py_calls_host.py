@@ -1,9 +1,11 @@
-"""``_lib``'s restatement of include/scanlib.h pinned to the header, prototype by prototype, structure by structure and
-enum by enum; and the contract of ``_lib.call``, the one way the package's wrappers enter the library.  No device."""
+"""``_lib``'s restatement of every public header of ``_lib.HEADERS`` pinned to the header, prototype by prototype,
+structure by structure and enum by enum; and the contract of ``_lib.call``, the one way the package's wrappers enter the
+library.  No device."""
 import ctypes as C
 import glob
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -16,19 +18,47 @@ PKG = os.path.dirname(os.path.abspath(_lib.__file__))
 EDGE_ARGS = (16, -2.355, 0.29, 0.275, 0.2032, 0.3302)        # rl_car_edge_distances without its output
 
 
-# ---------------------------------------------------------------- the table against the header
-PROTOTYPES = H.prototypes()
+# ---------------------------------------------------------------- the tables against the headers
+HEADERS = [H.Header(entry) for entry in _lib.HEADERS]
+SCANLIB = HEADERS[0]
+PROTOTYPES = {h.entry.file: h.prototypes() for h in HEADERS}
 
 
-def test_the_header_and_the_table_name_the_same_symbols():
-    assert set(PROTOTYPES) == set(_lib.SYMBOLS), set(PROTOTYPES) ^ set(_lib.SYMBOLS)
-    assert len(PROTOTYPES) == 105
+per_header = pytest.mark.parametrize("header", HEADERS, ids=[h.entry.file for h in HEADERS])
 
 
-@pytest.mark.parametrize("name", sorted(PROTOTYPES))
+def test_the_registry_is_the_headers_of_include():
+    assert sorted(e.file for e in _lib.HEADERS) == sorted(f for f in os.listdir(H.INCLUDE) if f.endswith(".h"))
+    assert [len(e.symbols) for e in _lib.HEADERS] == [105, 4, 4, 9, 3, 7, 3]
+    tables = [getattr(_lib, t) for t in ("SYMBOLS", "EXT_SYMBOLS", "SEAT_SYMBOLS", "POP_SYMBOLS", "LEAGUE_SYMBOLS",
+                                         "LEAGUE_ENV_SYMBOLS", "TRACK_DRIVE_SYMBOLS")]
+    assert all(e.symbols is t for e, t in zip(_lib.HEADERS, tables)) and len(_lib.HEADERS) == len(tables)
+    assert _lib.HEADERS[0].file == "scanlib.h" and not _lib.HEADERS[0].handles
+    # two headers that declare one name do not load
+    twice = _lib.Header("scanlib_extra.h", {"rl_env_step": _lib.SYMBOLS["rl_env_step"]}, {}, ())
+    with pytest.raises(ValueError, match="scanlib_extra.h declares rl_env_step again"):
+        _lib._merge(_lib.HEADERS + (twice,))
+    assert _lib._merge(_lib.HEADERS) == _lib._DECLARED and len(_lib._DECLARED) == 135
+    with pytest.raises(KeyError):
+        _lib.declared("rl_no_such_symbol")
+    # what build() watches: every unit and kernel header of csrc, and every file of include/
+    watched, csrc = {os.path.normpath(f) for f in _lib.build_sources()}, os.path.join(PKG, "csrc")
+    assert {os.path.join(H.INCLUDE, f) for f in os.listdir(H.INCLUDE)} <= watched
+    assert {os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))} <= watched
+
+
+@per_header
+def test_the_header_and_the_table_name_the_same_symbols(header):
+    protos, table = PROTOTYPES[header.entry.file], header.entry.symbols
+    assert set(protos) == set(table), set(protos) ^ set(table)
+    assert set(re.findall(r"\b(rl_[a-z_0-9]+)\s*\(", header.text())) == set(table)
+
+
+@pytest.mark.parametrize("name", [pytest.param((h, n), id=n) for h in HEADERS for n in sorted(h.entry.symbols)])
 def test_prototype_matches_the_table(name):
-    res, args, names = PROTOTYPES[name]
-    bound_res, bound_args = _lib.SYMBOLS[name]
+    header, name = name
+    res, args, names = PROTOTYPES[header.entry.file][name]
+    bound_res, bound_args = header.entry.symbols[name]
     assert bound_res is res, (name, bound_res, res)
     assert len(bound_args) == len(args), (name, names)
     for i, (got, want) in enumerate(zip(bound_args, args)):
@@ -36,33 +66,66 @@ def test_prototype_matches_the_table(name):
 
 
 def test_int_valued_symbols_return_int_and_are_declared():
-    assert _lib.INT_VALUED <= set(PROTOTYPES)
-    assert all(PROTOTYPES[n][0] is C.c_int for n in _lib.INT_VALUED)
+    protos = PROTOTYPES["scanlib.h"]
+    assert _lib.INT_VALUED <= set(protos)
+    assert all(protos[n][0] is C.c_int for n in _lib.INT_VALUED)
     # the header's rule, "every function returns RL_OK (0) or a negative rl_status", covers every other int function
-    status = [n for n, (res, _, _) in PROTOTYPES.items() if res is C.c_int and n not in _lib.INT_VALUED]
+    status = [n for n, (res, _, _) in protos.items() if res is C.c_int and n not in _lib.INT_VALUED]
     assert all(_lib.converters(n)[2] for n in status) and not any(_lib.converters(n)[2] for n in _lib.INT_VALUED)
     assert not _lib.converters("rl_version")[2] and not _lib.converters("rl_map_destroy")[2]
 
 
-@pytest.mark.parametrize("name", sorted(H.STRUCTS))
+@per_header
+def test_the_library_exports_the_table_and_the_call_layer_reads_it(header):
+    L = _lib.lib()
+    for name, (res, args) in header.entry.symbols.items():
+        fn = getattr(L, name)
+        assert fn.restype is res and list(fn.argtypes) == list(args), name
+        assert _lib.declared(name) is header.entry.symbols[name], name
+        raw, convs, status = _lib.converters(name)
+        assert status is (res is C.c_int and name not in _lib.INT_VALUED), name        # (rl_status: call checks it)
+        assert len(convs) == len(args), name
+    if header is not SCANLIB:
+        # a feature header's int is always an rl_status, and its handle types are the registry's
+        assert not set(header.entry.symbols) & _lib.INT_VALUED
+        assert all(res is C.c_int or (res is None and name.endswith("_destroy"))
+                   for name, (res, _) in header.entry.symbols.items())
+        assert header.handles() == set(header.entry.handles) and not header.handles() & SCANLIB.handles()
+
+
+@per_header
+def test_a_newer_header_rebuilds_the_unit_that_includes_it(header):
+    """make itself: with the header newer than everything (-W), a dry run of the library's rule compiles abi_car."""
+    _lib.build()
+    out = subprocess.run(["make", "-n", "-W", "../../include/" + header.entry.file, "../libscan_amd.so"],
+                         cwd=os.path.join(PKG, "csrc"), check=True, capture_output=True, text=True).stdout
+    assert re.search(r"-c -o \.obj/abi_car\.o abi_car\.hip", out), out
+
+
+@pytest.mark.parametrize("name", [pytest.param((h, n), id=n) for h in HEADERS for n in sorted(h.entry.structs)])
 def test_structure_matches_the_header(name):
-    declared = H.structs()[name]
-    fields = [(f[0], f[1]) for f in H.STRUCTS[name]._fields_]
+    header, name = name
+    declared = header.structs()[name]
+    fields = [(f[0], f[1]) for f in header.entry.structs[name]._fields_]
     assert [n for n, _ in fields] == [n for n, _ in declared]
     for (n, got), (_, want) in zip(fields, declared):
         assert got is want, "%s.%s: the class has %s, the header %s" % (name, n, got, want)
 
 
-def test_every_structure_of_the_header_is_restated():
-    assert set(H.structs()) == set(H.STRUCTS)
-    assert dict(_lib.RaceEnvParams._fields_)["env"] is _lib.EnvParams
-    assert dict(_lib.PfParams._fields_)["motion_std"] is C.c_double * 3
-    assert [n for n, _ in _lib.TrackParams._fields_] == ["window", "goal_span", "reward_mode", "lookahead"]
-    assert len(_lib.PlanOpts._fields_) == 28
+@per_header
+def test_every_structure_of_the_header_is_restated(header):
+    assert set(header.structs()) == set(header.entry.structs)
+    assert all(H.STRUCTS[name] is cls for name, cls in header.entry.structs.items())
+    if header is SCANLIB:
+        assert len(header.entry.structs) == 7
+        assert dict(_lib.RaceEnvParams._fields_)["env"] is _lib.EnvParams
+        assert dict(_lib.PfParams._fields_)["motion_std"] is C.c_double * 3
+        assert [n for n, _ in _lib.TrackParams._fields_] == ["window", "goal_span", "reward_mode", "lookahead"]
+        assert len(_lib.PlanOpts._fields_) == 28
 
 
 def test_enums_match_the_header():
-    E = H.enums()
+    E = SCANLIB.enums()
     assert set(E) == {"rl_status", "rl_kind", "rl_mcts_source", "rl_kernel_id", "rl_binning"}
     for enum in ("rl_status", "rl_kind", "rl_mcts_source"):
         for const, value in E[enum].items():
@@ -83,7 +146,7 @@ def test_enums_match_the_header():
 def test_the_parser_refuses_what_it_does_not_know():
     for decl in ("long", "unsigned int", "struct foo *", "float ***", "rl_plan_opts **", "char **"):
         with pytest.raises(H.HeaderError):
-            H.ctype(decl, "x", H.handles())
+            H.ctype(decl, "x", SCANLIB.handles())
     assert H.ctype("const float *", "d_poses") is C.c_void_p and H.ctype("const float *", "poses") is _lib.f32p
     assert H.ctype("rl_map **", "out", {"rl_map"}) == C.POINTER(C.c_void_p) and H.ctype("void ", "") is None
 
@@ -196,11 +259,7 @@ def test_a_value_symbol_returns_its_value():
 
 
 def test_lib_and_raw_are_what_they_were():
-    L = _lib.lib()
-    for name, (res, args) in _lib.SYMBOLS.items():
-        fn = getattr(L, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-    raw = _lib.raw("rl_calc_range_fan")
+    raw = _lib.raw("rl_calc_range_fan")                # (lib(): test_the_library_exports_the_table_and_the_call_layer_reads_it)
     assert raw is _lib.raw("rl_calc_range_fan") and raw.restype is C.c_int
     assert tuple(raw.argtypes) == (C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)
 

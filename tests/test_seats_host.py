@@ -1,9 +1,8 @@
 """Per-seat drivers without a GPU: the statement (tests/seat_statement.py) on a fake one-dimensional world,
-include/scanlib_seats.h pinned to ``_lib.SEAT_SYMBOLS`` and ``rl_seat_params`` prototype by prototype, the three symbol
-tables disjoint, and every Python-side refusal."""
+what include/scanlib_seats.h says beyond its prototypes (tests/test_py_calls_host.py pins those to
+``_lib.SEAT_SYMBOLS``), and every Python-side refusal."""
 import ctypes as C
 import math
-import os
 import re
 
 import numpy as np
@@ -12,7 +11,7 @@ import pytest
 import race_env_statement as RE
 import scanlib_header as H
 import seat_statement as SS
-from conftest import ROOT
+from test_population_host import no_calls  # noqa: F401  (a fixture)
 from test_race_env_host import B, World1D, _acts, _lineup
 from pyracecarsimulator_amd import _lib, seats
 from pyracecarsimulator_amd import racecar as RC
@@ -20,7 +19,7 @@ from pyracecarsimulator_amd.env import RaceEnv
 from pyracecarsimulator_amd.followgap import PyFollowGap
 from pyracecarsimulator_amd.policy import Policy
 
-SEAT_HEADER = os.path.join(ROOT, "include", "scanlib_seats.h")
+SEAT_HEADER = H.read("scanlib_seats.h")
 
 
 # ---------------------------------------------------------------- the statement on the fake world
@@ -146,74 +145,30 @@ def test_seated_rollout_statement():
     assert trace[0, 0, 4] == 0.0 and np.array_equal(final[[0, 1, 3, 4, 5]], trace[[0, 1, 3, 4, 5], 3])
 
 
-# ---------------------------------------------------------------- the header against the tables
-@pytest.fixture
-def seat_header(monkeypatch):
-    """tests/scanlib_header.py reading the seats header: its handle types come from scanlib.h."""
-    opaque = H.handles()
-    structs = dict(H.STRUCTS, rl_seat_params=_lib.SeatParams)
-    monkeypatch.setattr(H, "HEADER", SEAT_HEADER)
-    monkeypatch.setattr(H, "STRUCTS", structs)
-    monkeypatch.setattr(H, "handles", lambda s=None: opaque)
-    return H
-
-
-def test_seats_header_is_pinned_to_seat_symbols(seat_header):
-    protos = seat_header.prototypes()
-    assert set(protos) == set(_lib.SEAT_SYMBOLS) and len(protos) == 4
-    for name, (res, args, names) in protos.items():
-        bound_res, bound_args = _lib.SEAT_SYMBOLS[name]
-        assert bound_res is res is C.c_int, name
-        assert len(bound_args) == len(args), (name, names)
-        for i, (got, want) in enumerate(zip(bound_args, args)):
-            assert got is want, "%s argument %d (%s): the table has %s, the header %s" % (name, i, names[i], got, want)
+# ---------------------------------------------------------------- the header
+def test_seats_header_is_pinned_to_seat_symbols():
+    protos = SEAT_HEADER.prototypes()
     # rl_car_race_seats: rl_car_race_followgap's arguments from states_in on, behind its own six
     names = protos["rl_car_race_seats"][2]
     assert names[:6] == ["c", "h", "g_or_null", "p_or_null", "seat_driver", "steer_clip"]
     assert protos["rl_car_race_seats"][1][6:] == _lib.SYMBOLS["rl_car_race_followgap"][1][3:]
-    declared = seat_header.structs()
+    declared = SEAT_HEADER.structs()
     assert set(declared) == {"rl_seat_params"}
-    fields = [(n, t) for n, t in _lib.SeatParams._fields_]
-    assert [n for n, _ in fields] == [n for n, _ in declared["rl_seat_params"]] == ["driver", "speed"]
-    for (n, got), (_, want) in zip(fields, declared["rl_seat_params"]):
-        assert got is want, n
+    assert [n for n, _ in _lib.SeatParams._fields_] == [n for n, _ in declared["rl_seat_params"]] == ["driver", "speed"]
     assert C.sizeof(_lib.SeatParams) == 64
     # the driver codes: one plain enum, restated as a dictionary and in seats.py, never as RL_* names of _lib
-    m = re.search(r"enum\s+rl_seat_driver\s*\{([^{}]*)\}\s*;", seat_header.text())
+    m = re.search(r"enum\s+rl_seat_driver\s*\{([^{}]*)\}\s*;", SEAT_HEADER.text())
     codes = {k.strip(): int(v) for k, v in (item.split("=") for item in m.group(1).split(","))}
     assert codes == {"RL_SEAT_CALLER": 0, "RL_SEAT_FOLLOWGAP": 1, "RL_SEAT_POLICY": 2}
     assert _lib.SEAT_DRIVERS == {"caller": 0, "followgap": 1, "policy": 2}
     assert (seats.SEAT_CALLER, seats.SEAT_FOLLOWGAP, seats.SEAT_POLICY) == (0, 1, 2)
     assert not [n for n in vars(_lib) if n.startswith("RL_") and "SEAT" in n]
     # the header carries its contract and builds on scanlib.h
-    raw = open(SEAT_HEADER).read()
+    raw = open(SEAT_HEADER.path).read()
     assert '#include "scanlib.h"' in raw and "The rule." in raw and raw.count("Errors (RL_ERR_INVALID") == 2
-    assert set(re.findall(r"\b(rl_[a-z_0-9]+)\s*\(", seat_header.text())) == set(_lib.SEAT_SYMBOLS)
-
-
-def test_three_tables_are_disjoint_and_the_library_exports_the_seats():
-    tables = (_lib.SYMBOLS, _lib.EXT_SYMBOLS, _lib.SEAT_SYMBOLS)
-    assert len(set().union(*tables)) == sum(len(t) for t in tables)
-    L = _lib.lib()
-    for name, (res, args) in _lib.SEAT_SYMBOLS.items():
-        fn = getattr(L, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-        assert _lib.declared(name) == (res, args) and _lib.converters(name)[2], name      # (rl_status: call checks it)
-        assert len(_lib.converters(name)[1]) == len(args)
-    assert _lib.declared("rl_env_step") is _lib.SYMBOLS["rl_env_step"]
-    assert _lib.declared("rl_mcts_set_points") is _lib.EXT_SYMBOLS["rl_mcts_set_points"]
-    with pytest.raises(KeyError):
-        _lib.declared("rl_no_such_symbol")
 
 
 # ---------------------------------------------------------------- the wrappers' refusals
-@pytest.fixture
-def no_calls(monkeypatch):
-    def refuse(name, *a):
-        raise AssertionError("the library was entered at %s" % name)
-    monkeypatch.setattr(_lib, "call", refuse)
-
-
 def _drivers():
     """A FollowGap and a policy object (window [5, 45)) that never saw the library."""
     fg, pol = PyFollowGap.__new__(PyFollowGap), Policy.__new__(Policy)

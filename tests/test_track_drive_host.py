@@ -1,10 +1,10 @@
-"""Track progress of the roll-outs without a GPU: include/scanlib_track_drive.h pinned to ``_lib.TRACK_DRIVE_SYMBOLS``
-prototype by prototype, the seven symbol tables disjoint, the statement (tests/track_drive_statement.py) on hand-made
-trajectories with the expected numbers written out, and every Python-side refusal."""
+"""Track progress of the roll-outs without a GPU: what include/scanlib_track_drive.h says beyond its prototypes
+(tests/test_py_calls_host.py pins those to ``_lib.TRACK_DRIVE_SYMBOLS``), the statement
+(tests/track_drive_statement.py) on hand-made trajectories with the expected numbers written out, and every Python-side
+refusal."""
 import ctypes as C
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -18,7 +18,7 @@ from test_track_host import SQUARE
 from pyracecarsimulator_amd import RacecarSimulator, Track, _lib
 from pyracecarsimulator_amd import racecar as RC
 
-HEADER = os.path.join(ROOT, "include", "scanlib_track_drive.h")
+HEADER = H.read("scanlib_track_drive.h")
 CORNER = [(0.0, 0.0), (4.0, 0.0), (4.0, 3.0)]                  # 3 points: closed 4 + 3 + 5 = 12 m, open 4 + 3 = 7 m
 NAN = float("nan")
 
@@ -146,66 +146,35 @@ def test_track_fitness_sums_upwards():
     assert st[:, 3].tolist() == [3.0, 0.0]
 
 
-# ---------------------------------------------------------------- the header against the table
-@pytest.fixture
-def header(monkeypatch):
-    """tests/scanlib_header.py reading the new header: its handle types are scanlib.h's."""
-    opaque = H.handles()
-    monkeypatch.setattr(H, "HEADER", HEADER)
-    monkeypatch.setattr(H, "STRUCTS", dict(H.STRUCTS, rl_drive_track_params=_lib.DriveTrackParams))
-    monkeypatch.setattr(H, "handles", lambda s=None: opaque)
-    return H
-
-
-def test_header_is_pinned_to_track_drive_symbols(header):
-    protos = header.prototypes()
-    assert set(protos) == set(_lib.TRACK_DRIVE_SYMBOLS) and len(protos) == 3
-    for name, (res, args, names) in protos.items():
-        bound_res, bound_args = _lib.TRACK_DRIVE_SYMBOLS[name]
-        assert bound_res is res is C.c_int, name
-        assert len(bound_args) == len(args), (name, names)
-        for i, (got, want) in enumerate(zip(bound_args, args)):
-            assert got is want, "%s argument %d (%s): the table has %s, the header %s" % (name, i, names[i], got, want)
+# ---------------------------------------------------------------- the header
+def test_header_is_pinned_to_track_drive_symbols():
+    protos = HEADER.prototypes()
     assert protos["rl_car_attach_track"][2] == ["c", "t", "p"]
     assert protos["rl_car_read_track"][2] == ["c", "n_cars", "rows_n4", "ints_n4"]
     assert protos["rl_car_read_track_scores"][2] == ["c", "n_rows", "n_cols", "scores"]
-    structs = header.structs()
+    structs = HEADER.structs()
     assert list(structs) == ["rl_drive_track_params"]
     assert structs["rl_drive_track_params"] == [("window", C.c_int), ("goal_dist", C.c_double)] == _lib.DriveTrackParams._fields_
     P = _lib.DriveTrackParams
     assert C.sizeof(P) == 16 and (P.window.offset, P.goal_dist.offset) == (0, 8)
-    assert not header.handles(header.text()) - H.handles() and not set(_lib.TRACK_DRIVE_SYMBOLS) & _lib.INT_VALUED
-    raw = open(HEADER).read()
+    assert not HEADER.handles()
+    raw = open(HEADER.path).read()
     assert '#include "scanlib_league.h"' in raw and "Out of scope" in raw and "Refused (RL_ERR_INVALID" in raw
     for phrase in ("progress >= goal_dist", "goal_dist == 0 means the track length L", "The step of the crash tick counts",
                    "A frozen car", "with no lap counted", "an equal one and k' < k", "ties and NaN beat nobody",
                    "ascending car order from +0.0", "four zeros", "keeps its meaning and bits", "rl_mcts_drive",
                    "graph capture", "multi-device", "off-track", "device-pointer forms"):
         assert phrase in raw, phrase
-    assert set(re.findall(r"\b(rl_[a-z_0-9]+)\s*\(", header.text())) == set(_lib.TRACK_DRIVE_SYMBOLS)
     # the two headers that named the gap now name what is left of it
     for name in ("scanlib_league.h", "scanlib_league_env.h"):
         text = open(os.path.join(ROOT, "include", name)).read()
         assert "scanlib_track_drive.h" in text, name
 
 
-def test_seven_tables_are_disjoint_and_the_library_exports_the_new_one():
-    tables = (_lib.SYMBOLS, _lib.EXT_SYMBOLS, _lib.SEAT_SYMBOLS, _lib.POP_SYMBOLS, _lib.LEAGUE_SYMBOLS,
-              _lib.LEAGUE_ENV_SYMBOLS, _lib.TRACK_DRIVE_SYMBOLS)
-    assert len(set().union(*tables)) == sum(len(t) for t in tables)
-    L = _lib.lib()
-    for name, (res, args) in _lib.TRACK_DRIVE_SYMBOLS.items():
-        fn = getattr(L, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args), name
-        assert _lib.declared(name) == (res, args), name
-        assert _lib.converters(name)[2] is True, name             # (rl_status: call checks it)
-    assert _lib.declared("rl_env_read_league_steers") is _lib.LEAGUE_ENV_SYMBOLS["rl_env_read_league_steers"]
-    with pytest.raises(KeyError):
-        _lib.declared("rl_no_such_symbol")
-    assert "scanlib_track_drive.h" in inspect.getsource(_lib.build)
+def test_the_kernels_are_built_budgeted_and_shared_and_the_wrappers_take_a_track():
     csrc = os.path.join(ROOT, "pyracecarsimulator_amd", "csrc")
     make = open(os.path.join(csrc, "Makefile")).read()
-    assert "drive_track_kernels.h" in make and "scanlib_track_drive.h" in make
+    assert "drive_track_kernels.h" in make                        # (the public header: test_py_calls_host.py asks make)
     budgets = open(os.path.join(csrc, "check_resources.py")).read()
     for kernel in ("drive_track_kernel<", "drive_track_rank_kernel", "drive_track_fitness_kernel", "drive_track_standings_kernel"):
         assert '("scan::%s", {"scratch": 0})' % kernel in budgets, kernel
