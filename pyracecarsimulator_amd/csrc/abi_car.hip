@@ -143,14 +143,10 @@ static int car_rollout_device(rl_car *c, HostCall &hc, const double *states_in, 
         (rc = hc.room(c->vel, n_poses)))
         return rc;
     if (d_xy)           // (rl_car_rollout_track: poses, velocities and positions, no final states)
-        hipLaunchKernelGGL(rollout_xy_kernel, dim3((R + 63) / 64), dim3(64), 0, hc.st, c->P, (const double *)c->states,
-                           (const double *)c->actions, R, n_steps, every, dt, (float *)c->poses, (double *)c->vel, d_xy);
-    else
-        hipLaunchKernelGGL(rollout_kernel, dim3((R + 63) / 64), dim3(64), 0, hc.st, c->P, (const double *)c->states,
-                           (const double *)c->actions, R, n_steps, every, dt, (float *)c->poses,
-                           want_states ? (double *)c->states_out : nullptr, want_vel ? (double *)c->vel : nullptr);
-    HIPCHK(hipGetLastError());
-    return RL_OK;
+        return launch("rollout_xy_kernel", rollout_xy_kernel, dim3((R + 63) / 64), dim3(64), 0, hc.st, c->P, c->states, c->actions, R,
+                      n_steps, every, dt, c->poses, c->vel, d_xy);
+    return launch("rollout_kernel", rollout_kernel, dim3((R + 63) / 64), dim3(64), 0, hc.st, c->P, c->states, c->actions, R, n_steps,
+                  every, dt, c->poses, want_states ? (double *)c->states_out : nullptr, want_vel ? (double *)c->vel : nullptr);
 }
 
 extern "C" int rl_car_rollout(rl_car *c, const double *states_in, const double *actions, int R,
@@ -299,12 +295,10 @@ static int followgap_launch(rl_followgap *g, const float *d_scans, int n_scans, 
     p.size = size;
     const int grid = std::min(n_scans, g->n_cu * 32);
     if (size <= 64 * FG_ROWS && !g->walk_kernel)
-        fg_bits_table[(size + 63) / 64 - 1]<<<dim3(grid), dim3(64), 0, stream>>>(d_scans, n_scans, p, d_angles);
-    else
-        hipLaunchKernelGGL(followgap_kernel, dim3(grid), dim3(64), (size_t)size * sizeof(float), stream,
-                           d_scans, n_scans, p, d_angles);
-    HIPCHK(hipGetLastError());
-    return RL_OK;
+        return launch("followgap_bits_kernel", fg_bits_table[(size + 63) / 64 - 1], dim3(grid), dim3(64), 0, stream, d_scans, n_scans,
+                      p, d_angles);
+    return launch("followgap_kernel", followgap_kernel, dim3(grid), dim3(64), (size_t)size * sizeof(float), stream, d_scans, n_scans,
+                  p, d_angles);
 }
 
 extern "C" int rl_followgap_eval(rl_followgap *g, const float *scans, int n_scans, int size,
@@ -401,9 +395,9 @@ static int launch_race(rl_method *h, const LaunchArgs &a, const float *d_poses, 
     const LiteralParams lp = lit ? make_literal(h->map) : LiteralParams{};
     const RaceParams rp{o, d_cars, car_stride, group, n_groups};
     if (a.timing) HIPCHK(hipEventRecord(h->ev0, stream));
-    race_table[lit][aux]<<<dim3(n_groups), dim3(RACE_WG), 0, stream>>>(h->map->mp, f, lp, rp, d_poses, d_out, d_hits,
-                                                                       d_steps);
-    HIPCHK(hipGetLastError());
+    const int rc = launch("race_fan_kernel", race_table[lit][aux], dim3(n_groups), dim3(RACE_WG), 0, stream, h->map->mp, f, lp, rp,
+                          d_poses, d_out, d_hits, d_steps);
+    if (rc) return rc;
     if (a.timing) {
         HIPCHK(hipEventRecord(h->ev1, stream));
         h->timed = true;
@@ -479,10 +473,10 @@ extern "C" int rl_car_outline_cells(rl_car *c, rl_map *m, const double *cars_p3,
     HostCall hc(c->stream);
     if ((rc = hc.up(c->o_cars, cars_p3, (size_t)n * 3)) || (rc = hc.room(c->o_cells, n_cells)) || (rc = hc.room(c->o_counts, n)))
         return rc;
-    hipLaunchKernelGGL(outline_cells_kernel, dim3((n + 3) / 4), dim3(256), 0, hc.st, o, (const double *)c->o_cars, n,
-                       max_cells, (int32_t *)c->o_cells, (int *)c->o_counts);
-    HIPCHK(hipGetLastError());
-    if ((rc = hc.down(cells, c->o_cells, n_cells)) || (rc = hc.down(counts, c->o_counts, n))) return rc;
+    if ((rc = launch("outline_cells_kernel", outline_cells_kernel, dim3((n + 3) / 4), dim3(256), 0, hc.st, o, c->o_cars, n, max_cells,
+                     c->o_cells, c->o_counts)) ||
+        (rc = hc.down(cells, c->o_cells, n_cells)) || (rc = hc.down(counts, c->o_counts, n)))
+        return rc;
     return hc.finish();
 }
 
@@ -577,10 +571,8 @@ static int policy_args(const rl_policy *p, int n_scans, int size)
 static int policy_launch(rl_policy *p, const float *d_scans, int n_scans, int size, float *d_steers, hipStream_t st)
 {
     if (n_scans == 0) return RL_OK;
-    hipLaunchKernelGGL(policy_mlp_kernel, dim3((n_scans + PM_CARS - 1) / PM_CARS), dim3(64), 0, st, p->P, d_scans,
-                       n_scans, size, d_steers);
-    HIPCHK(hipGetLastError());
-    return RL_OK;
+    return launch("policy_mlp_kernel", policy_mlp_kernel, dim3((n_scans + PM_CARS - 1) / PM_CARS), dim3(64), 0, st, p->P, d_scans,
+                  n_scans, size, d_steers);
 }
 
 // the row-indexed form: the network for the n_rows scans d_rows names, answers to d_steers[row]
@@ -588,10 +580,8 @@ static int policy_rows_launch(const PolicyParams &P, const float *d_scans, const
                               float *d_steers, hipStream_t st)
 {
     if (n_rows == 0) return RL_OK;
-    hipLaunchKernelGGL(policy_mlp_rows_kernel, dim3((n_rows + PM_CARS - 1) / PM_CARS), dim3(64), 0, st, P, d_scans, d_rows,
-                       n_rows, size, d_steers);
-    HIPCHK(hipGetLastError());
-    return RL_OK;
+    return launch("policy_mlp_rows_kernel", policy_mlp_rows_kernel, dim3((n_rows + PM_CARS - 1) / PM_CARS), dim3(64), 0, st, P,
+                  d_scans, d_rows, n_rows, size, d_steers);
 }
 
 extern "C" int rl_policy_eval(rl_policy *p, const float *scans, int n_scans, int size, float *steers)
@@ -754,10 +744,8 @@ static int pop_pack_launch(rl_policy_pop *p, int first, int n, const float *d_th
 {
     const size_t total = (size_t)n * p->n_params;
     const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 65536);
-    hipLaunchKernelGGL(policy_pop_pack_kernel, dim3(grid), dim3(256), 0, st, p->L, d_theta, first, n, p->stride,
-                       (float *)p->weights);
-    HIPCHK(hipGetLastError());
-    return RL_OK;
+    return launch("policy_pop_pack_kernel", policy_pop_pack_kernel, dim3(grid), dim3(256), 0, st, p->L, d_theta, first, n, p->stride,
+                  p->weights);
 }
 
 extern "C" int rl_policy_pop_set(rl_policy_pop *p, int first, int n, const float *theta_nP)
@@ -811,10 +799,8 @@ static int pop_launch(rl_policy_pop *p, int first, int n, int E, const float *d_
 {
     if (n == 0) return RL_OK;
     const int wg = (E + PM_CARS - 1) / PM_CARS;
-    hipLaunchKernelGGL(policy_mlp_pop_kernel, dim3((unsigned)n * wg), dim3(64), 0, st, p->P, p->stride, first, wg, E, d_scans,
-                       size, d_steers);
-    HIPCHK(hipGetLastError());
-    return RL_OK;
+    return launch("policy_mlp_pop_kernel", policy_mlp_pop_kernel, dim3((unsigned)n * wg), dim3(64), 0, st, p->P, p->stride, first, wg,
+                  E, d_scans, size, d_steers);
 }
 
 extern "C" int rl_policy_pop_eval(rl_policy_pop *p, int first, int n, int cars_per_member, const float *scans, int size,
@@ -860,24 +846,20 @@ static int league_group(rl_policy_pop *p, const int *d_member, int n, hipStream_
         (rc = p->lg_rows.ensure(n)) || (rc = p->lg_table.ensure(league_wg_bound(p, n))) || (rc = p->lg_total.ensure(1)))
         return rc;
     const dim3 per_member((N + LG_WAVES - 1) / LG_WAVES), waves(64 * LG_WAVES);
-    hipLaunchKernelGGL(league_count_kernel, per_member, waves, 0, st, d_member, n, N, (int *)p->lg_count);
-    hipLaunchKernelGGL(league_offsets_kernel, dim3(1), dim3(LG_SCAN), 0, st, (const int *)p->lg_count, N, (int *)p->lg_start,
-                       (int *)p->lg_wg_start, (int *)p->lg_total);
-    hipLaunchKernelGGL(league_fill_kernel, per_member, waves, 0, st, d_member, n, N, (const int *)p->lg_count,
-                       (const int *)p->lg_start, (const int *)p->lg_wg_start, (int *)p->lg_rows, (int2 *)p->lg_table);
-    HIPCHK(hipGetLastError());
-    return RL_OK;
+    if ((rc = launch("league_count_kernel", league_count_kernel, per_member, waves, 0, st, d_member, n, N, p->lg_count)) ||
+        (rc = launch("league_offsets_kernel", league_offsets_kernel, dim3(1), dim3(LG_SCAN), 0, st, p->lg_count, N, p->lg_start,
+                     p->lg_wg_start, p->lg_total)))
+        return rc;
+    return launch("league_fill_kernel", league_fill_kernel, per_member, waves, 0, st, d_member, n, N, p->lg_count, p->lg_start,
+                  p->lg_wg_start, p->lg_rows, p->lg_table);
 }
 
 // the league's network launch over the grouping of n rows: scans [.][size] -> steers [row] for every grouped row
 static int league_launch(rl_policy_pop *p, int n, const float *d_scans, int size, float *d_steers, hipStream_t st)
 {
     if (n == 0) return RL_OK;
-    hipLaunchKernelGGL(policy_mlp_league_kernel, dim3((unsigned)league_wg_bound(p, n)), dim3(64), 0, st, p->P, p->stride,
-                       (const int2 *)p->lg_table, (const int *)p->lg_total, (const int *)p->lg_start, (const int *)p->lg_count,
-                       (const int *)p->lg_rows, d_scans, size, d_steers);
-    HIPCHK(hipGetLastError());
-    return RL_OK;
+    return launch("policy_mlp_league_kernel", policy_mlp_league_kernel, dim3((unsigned)league_wg_bound(p, n)), dim3(64), 0, st, p->P,
+                  p->stride, p->lg_table, p->lg_total, p->lg_start, p->lg_count, p->lg_rows, d_scans, size, d_steers);
 }
 
 static int league_rows_args(const char *fn, const rl_policy_pop *p, int n, int size)
@@ -1091,9 +1073,7 @@ struct Loop {
                                            s.ranges, nullptr, nullptr, st)
                              : launch_fan(h, FanCall{a, s.poses, s.n, s.fov, s.num_rays, s.ranges, nullptr, nullptr, nullptr, st});
         if (rc || (rc = src.answer(s.ranges, s.n, s.num_rays, s.mlp, st))) return rc;
-        table[(s.num_rays + 63) / 64 - 1]<<<dim3((s.n + per_wg - 1) / per_wg), dim3(64 * per_wg), 0, st>>>(args...);
-        if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "%s launch failed", kernel);
-        return RL_OK;
+        return launch(kernel, table[(s.num_rays + 63) / 64 - 1], dim3((s.n + per_wg - 1) / per_wg), dim3(64 * per_wg), 0, st, args...);
     }
 };
 
@@ -1202,9 +1182,9 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, const SteerSour
     if (trk) {
         c->dt_cars = c->dt_score_rows = c->dt_score_cols = 0;      // (a call that fails leaves nothing to read)
         if ((rc = hc.room(c->dt_rows, (size_t)R * 4)) || (rc = hc.room(c->dt_ints, (size_t)R * 4))) return rc;
-        hipLaunchKernelGGL(drive_track_kernel<true>, track_grid, track_block, 0, st, R, tt, c->dt_window, c->dt_goal,
-                           DriveTrackBufs{c->dt_rows, c->dt_ints}, (const double *)c->states, (const int *)nullptr, 0);
-        HIPCHK(hipGetLastError());
+        if ((rc = launch("drive_track_kernel", drive_track_kernel<true>, track_grid, track_block, 0, st, R, tt, c->dt_window,
+                         c->dt_goal, DriveTrackBufs{c->dt_rows, c->dt_ints}, c->states, nullptr, 0)))
+            return rc;
     }
     const DriveTrackBufs tb{c->dt_rows, c->dt_ints};
 
@@ -1224,48 +1204,41 @@ static int drive_loop(const char *name, rl_car *c, rl_method *h, const SteerSour
                 a.velocities ? (double *)c->vel : nullptr, a.steers ? (float *)c->tr_steers : nullptr,
                 a.scan_poses ? (float *)c->tr_poses : nullptr, a.states_trace ? (double *)c->tr_states : nullptr,
                 net ? (const float *)c->mlp : nullptr, league ? (const int *)pop->lg_member : nullptr};
-    hipLaunchKernelGGL(drive_start_kernel, dim3((R + 63) / 64), dim3(64), 0, st, dp, b);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch("drive_start_kernel", drive_start_kernel, dim3((R + 63) / 64), dim3(64), 0, st, dp, b))) return rc;
     // the noise offset walks the global ray id t R num_rays + r num_rays of every tick
     // (a race reads every car's outline from its f64 state after this tick's step: all cars step, then all scan)
     const LoopScan scan{b.pose, R, a.fov, num_rays, c->ranges, c->mlp, race ? group : 0, b.state, &op};
     const auto &table = league ? league_tick_table : seats ? seat_tick_table : src.g ? fg_tick_table : policy_tick_table;
     for (int t = 0; t < n_ticks && rc == RL_OK; ++t) {
-        if (trk) {      // the cars still running hold the state after tick t's step
-            hipLaunchKernelGGL(drive_track_kernel<false>, track_grid, track_block, 0, st, R, tt, c->dt_window, c->dt_goal, tb,
-                               (const double *)c->states, (const int *)c->first, t);
-            HIPCHK(hipGetLastError());
-        }
+        // (a track: the cars still running hold the state after tick t's step)
+        if (trk && (rc = launch("drive_track_kernel", drive_track_kernel<false>, track_grid, track_block, 0, st, R, tt, c->dt_window,
+                                c->dt_goal, tb, c->states, c->first, t)))
+            break;
         rc = lp.scan_then(scan, lp.base + (uint64_t)t * n_rays, table, DRIVE_CARS, "drive_tick_kernel", st, dp, b, t);
     }
     if (rc == RL_OK && n_scores) {
-        if (league)
-            hipLaunchKernelGGL(league_standings_kernel, dim3((pop->n_members + 63) / 64), dim3(64), 0, st,
-                               (const double *)c->states, (const double *)c->pop_states0, (const int *)c->first,
-                               (const int *)pop->lg_start, (const int *)pop->lg_count, (const int *)pop->lg_rows, pop->n_members,
-                               group, n_ticks, (double *)c->pop_fitness);
-        else
-            hipLaunchKernelGGL(policy_pop_fitness_kernel, dim3((src.n + 63) / 64), dim3(64), 0, st, (const double *)c->states,
-                               (const double *)c->pop_states0, (const int *)c->first, src.n, src.E, (double *)c->pop_fitness);
-        HIPCHK(hipGetLastError());
-        rc = hc.down(scores, c->pop_fitness, n_scores);
+        rc = league ? launch("league_standings_kernel", league_standings_kernel, dim3((pop->n_members + 63) / 64), dim3(64), 0, st,
+                             c->states, c->pop_states0, c->first, pop->lg_start, pop->lg_count, pop->lg_rows, pop->n_members, group,
+                             n_ticks, c->pop_fitness)
+                    : launch("policy_pop_fitness_kernel", policy_pop_fitness_kernel, dim3((src.n + 63) / 64), dim3(64), 0, st,
+                             c->states, c->pop_states0, c->first, src.n, src.E, c->pop_fitness);
+        if (rc == RL_OK) rc = hc.down(scores, c->pop_fitness, n_scores);
     }
     // a track: ranks per race, then the population's or the league's track scores (whether or not `scores` was asked for)
     int score_rows = 0, score_cols = 0;
     if (rc == RL_OK && trk) {
-        hipLaunchKernelGGL(drive_track_rank_kernel, dim3((R + 63) / 64), dim3(64), 0, st, R, race ? group : 0, tt, tb);
-        HIPCHK(hipGetLastError());
         if (league) score_rows = pop->n_members, score_cols = 4;
         else if (src.kind == SteerSource::POPULATION) score_rows = src.n, score_cols = 3;
-        if (score_rows && (rc = hc.room(c->dt_scores, (size_t)score_rows * score_cols))) return rc;
+        if ((rc = launch("drive_track_rank_kernel", drive_track_rank_kernel, dim3((R + 63) / 64), dim3(64), 0, st, R,
+                         race ? group : 0, tt, tb)) ||
+            (score_rows && (rc = hc.room(c->dt_scores, (size_t)score_rows * score_cols))))
+            return rc;
         if (league)
-            hipLaunchKernelGGL(drive_track_standings_kernel, dim3((score_rows + 63) / 64), dim3(64), 0, st, tb,
-                               (const int *)pop->lg_start, (const int *)pop->lg_count, (const int *)pop->lg_rows, score_rows,
-                               group, (double *)c->dt_scores);
+            rc = launch("drive_track_standings_kernel", drive_track_standings_kernel, dim3((score_rows + 63) / 64), dim3(64), 0, st,
+                        tb, pop->lg_start, pop->lg_count, pop->lg_rows, score_rows, group, c->dt_scores);
         else if (score_rows)
-            hipLaunchKernelGGL(drive_track_fitness_kernel, dim3((score_rows + 63) / 64), dim3(64), 0, st, tb, src.n, src.E,
-                               (double *)c->dt_scores);
-        HIPCHK(hipGetLastError());
+            rc = launch("drive_track_fitness_kernel", drive_track_fitness_kernel, dim3((score_rows + 63) / 64), dim3(64), 0, st, tb,
+                        src.n, src.E, c->dt_scores);
     }
     if (rc || (rc = hc.down(a.first_crashed, c->first, R)) || (rc = hc.down(a.states_out, c->states, (size_t)R * 11)) ||
         (rc = hc.down(a.velocities, c->vel, rows)) || (rc = hc.down(a.steers, c->tr_steers, rows)) ||
@@ -1603,13 +1576,10 @@ static int track_launch(rl_env *e, float *d_reward, hipStream_t st)
     const TrackTable T = track_table(e->track);
     const TrackBufs tb{e->track_st, e->track_rows, e->track_ints};
     if (e->group > 0)
-        hipLaunchKernelGGL(track_kernel<true>, dim3(N / e->group), dim3(64 * e->group), 0, st, N, T, e->tp, tb, e->state,
-                           e->phase, e->done, d_reward);
-    else
-        hipLaunchKernelGGL(track_kernel<false>, dim3((N + DRIVE_CARS - 1) / DRIVE_CARS), dim3(64 * DRIVE_CARS), 0, st, N, T,
-                           e->tp, tb, e->state, e->phase, e->done, d_reward);
-    if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "track_kernel launch failed");
-    return RL_OK;
+        return launch("track_kernel", track_kernel<true>, dim3(N / e->group), dim3(64 * e->group), 0, st, N, T, e->tp, tb, e->state,
+                      e->phase, e->done, d_reward);
+    return launch("track_kernel", track_kernel<false>, dim3((N + DRIVE_CARS - 1) / DRIVE_CARS), dim3(64 * DRIVE_CARS), 0, st, N, T,
+                  e->tp, tb, e->state, e->phase, e->done, d_reward);
 }
 
 // one call's launches on st: phase A (reset: the spawn), the scan at slot k, the source's answers, phase B, then the
@@ -1628,8 +1598,7 @@ static int env_launch(rl_env *e, const Loop &lp, bool reset, uint64_t k, const f
     const LoopScan scan{e->pose, N, e->prm.fov, B, e->ranges, e->mlp, e->group, e->state, &e->outline};
     // phase A and phase B of a kind: `mode` is what its kernels take between the env's buffers and the call's
     const auto step = [&](auto kernel, const char *name, const auto &...mode) {
-        kernel<<<dim3((N + 63) / 64), dim3(64), 0, st>>>(e->ep, b, mode..., d_actions, d_start_index, reset ? 1 : 0);
-        return hipGetLastError() != hipSuccess ? fail(RL_ERR_HIP, "%s launch failed", name) : (int)RL_OK;
+        return launch(name, kernel, dim3((N + 63) / 64), dim3(64), 0, st, e->ep, b, mode..., d_actions, d_start_index, reset ? 1 : 0);
     };
     const auto observe = [&](const auto &table, int per_wg, const char *name, const auto &...mode) {
         return lp.scan_then(scan, off, table, per_wg, name, st, e->ep, b, mode..., d_obs, d_reward, d_done, d_aux);
@@ -2215,7 +2184,7 @@ extern "C" int rl_probe_hbm_nt(int device, size_t bytes, double *gbs_out3)
 extern "C" int rl_probe_literal_sincosf(int device, const float *x, size_t n, float *sin_out, float *cos_out)
 {
     if (!x || !sin_out || !cos_out) return fail(RL_ERR_INVALID, "rl_probe_literal_sincosf: null pointer");
-    const int rc = check_device(device);
+    int rc = check_device(device);
     if (rc || n == 0) return rc;
     HIPCHK(hipSetDevice(device));
     DevPtr<float> buf;
@@ -2223,7 +2192,9 @@ extern "C" int rl_probe_literal_sincosf(int device, const float *x, size_t n, fl
     float *const d = buf;
     if (hipMemcpy(d, x, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(RL_ERR_HIP, "upload failed");
     const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(literal_sincosf_kernel, dim3(grid), dim3(256), 0, nullptr, d, (long)n, d + n, d + 2 * n);
+    if ((rc = launch("literal_sincosf_kernel", literal_sincosf_kernel, dim3(grid), dim3(256), 0, nullptr, d, (long)n, d + n,
+                     d + 2 * n)))
+        return rc;
     if (hipMemcpy(sin_out, d + n, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(cos_out, d + 2 * n, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
         return fail(RL_ERR_HIP, "rl_probe_literal_sincosf: kernel or download failed");
@@ -2234,7 +2205,7 @@ static int probe_hbm_modes(int device, size_t bytes, double *gbs_out5, int mode_
 {
     if (!gbs_out5) return fail(RL_ERR_INVALID, "rl_probe_hbm: null pointer");
     if (bytes < ((size_t)1 << 20)) return fail(RL_ERR_INVALID, "rl_probe_hbm: at least 1 MiB per buffer");
-    const int rc = check_device(device);
+    int rc = check_device(device);
     if (rc) return rc;
     HIPCHK(hipSetDevice(device));
     hipDeviceProp_t prop;
@@ -2250,10 +2221,11 @@ static int probe_hbm_modes(int device, size_t bytes, double *gbs_out5, int mode_
         return fail(RL_ERR_NOMEM, "rl_probe_hbm: setup failed (2 x %zu bytes)", n16 * 16);
     const int grid = prop.multiProcessorCount * 8, reps = 10;
     for (int mode = mode_lo; mode < mode_hi; ++mode) {
-        hipLaunchKernelGGL(hbm_probe_kernel, dim3(grid), dim3(256), 0, st, a, b, n16, mode, sink);     // warm
+        // (the first one warms)
+        if ((rc = launch("hbm_probe_kernel", hbm_probe_kernel, dim3(grid), dim3(256), 0, st, a, b, n16, mode, sink))) return rc;
         (void)hipEventRecord(e0, st);
         for (int r = 0; r < reps; ++r)
-            hipLaunchKernelGGL(hbm_probe_kernel, dim3(grid), dim3(256), 0, st, a, b, n16, mode, sink);
+            if ((rc = launch("hbm_probe_kernel", hbm_probe_kernel, dim3(grid), dim3(256), 0, st, a, b, n16, mode, sink))) return rc;
         (void)hipEventRecord(e1, st);
         float ms = 0.f;
         if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess || !(ms > 0.f))
@@ -2290,10 +2262,8 @@ extern "C" int rl_ranges_to_u16_device(int device, const float *d_ranges, size_t
     int vec;
     u16_split(d_ranges, d_out, n, head, vec);
     const int grid = (int)std::min<size_t>((n / 8 + 255) / 256 + 1, 256 * 16);
-    hipLaunchKernelGGL(ranges_to_u16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)hip_stream, d_ranges, n,
-                       max_range_m, 65535.0f / max_range_m, d_out, head, vec);
-    HIPCHK(hipGetLastError());
-    return RL_OK;
+    return launch("ranges_to_u16_kernel", ranges_to_u16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)hip_stream, d_ranges, n,
+                  max_range_m, 65535.0f / max_range_m, d_out, head, vec);
 }
 
 extern "C" int rl_ranges_from_u16_device(int device, const uint16_t *d_in, size_t n, float max_range_m,
@@ -2306,10 +2276,8 @@ extern "C" int rl_ranges_from_u16_device(int device, const uint16_t *d_in, size_
     int vec;
     u16_split(d_ranges, d_in, n, head, vec);
     const int grid = (int)std::min<size_t>((n / 8 + 255) / 256 + 1, 256 * 16);
-    hipLaunchKernelGGL(ranges_from_u16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)hip_stream, d_in, n,
-                       max_range_m / 65535.0f, d_ranges, head, vec);
-    HIPCHK(hipGetLastError());
-    return RL_OK;
+    return launch("ranges_from_u16_kernel", ranges_from_u16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)hip_stream, d_in, n,
+                  max_range_m / 65535.0f, d_ranges, head, vec);
 }
 
 // ---------------------------------------------------------------- diagnostics: gather-rate probe
@@ -2318,7 +2286,7 @@ extern "C" int rl_probe_gather_rate(int device, int active_lanes, double *lanes_
 {
     if (!lanes_per_clk_per_cu) return fail(RL_ERR_INVALID, "rl_probe_gather_rate: null pointer");
     if (active_lanes < 1 || active_lanes > 64) return fail(RL_ERR_INVALID, "active_lanes must be in [1,64]");
-    const int rc = check_device(device);
+    int rc = check_device(device);
     if (rc) return rc;
     HIPCHK(hipSetDevice(device));
     hipDeviceProp_t prop;
@@ -2346,9 +2314,11 @@ extern "C" int rl_probe_gather_rate(int device, int active_lanes, double *lanes_
         hipMemsetAsync(tab, 0, 4 * 2048 * sizeof(float), st) != hipSuccess ||
         hipMemcpyAsync(d_off, off, sizeof off, hipMemcpyHostToDevice, st) != hipSuccess)
         return fail(RL_ERR_HIP, "gather probe: setup failed");
-    hipLaunchKernelGGL(gather_probe_kernel, dim3(grid), dim3(1024), 0, st, tab, d_off, mask, 10, sink);
+    if ((rc = launch("gather_probe_kernel", gather_probe_kernel, dim3(grid), dim3(1024), 0, st, tab, d_off, mask, 10, sink)))
+        return rc;
     (void)hipEventRecord(e0, st);
-    hipLaunchKernelGGL(gather_probe_kernel, dim3(grid), dim3(1024), 0, st, tab, d_off, mask, iters, sink);
+    if ((rc = launch("gather_probe_kernel", gather_probe_kernel, dim3(grid), dim3(1024), 0, st, tab, d_off, mask, iters, sink)))
+        return rc;
     (void)hipEventRecord(e1, st);
     if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess || !(ms > 0.f))
         return fail(RL_ERR_HIP, "gather probe: launch failed");
@@ -2571,10 +2541,8 @@ static int plan_roots(rl_mcts *m, hipStream_t st)
     if (!m->track && !m->has_points) return RL_OK;
     const int K = m->prm.n_trees;
     const TrackTable T = m->track ? track_table(m->track) : TrackTable{};
-    hipLaunchKernelGGL(plan_root_kernel, dim3((K + MCTS_TREES - 1) / MCTS_TREES), dim3(64 * MCTS_TREES), 0, st, K, T, m->tp,
-                       (const double *)m->roots, m->has_points ? (const double *)m->tk_points : nullptr, plan_roots_of(m));
-    if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "plan_root_kernel launch failed");
-    return RL_OK;
+    return launch("plan_root_kernel", plan_root_kernel, dim3((K + MCTS_TREES - 1) / MCTS_TREES), dim3(64 * MCTS_TREES), 0, st, K, T,
+                  m->tp, m->roots, m->has_points ? (const double *)m->tk_points : nullptr, plan_roots_of(m));
 }
 
 // how rl_mcts_reset and rl_mcts_drive begin: the keys go up to d_keys, the K root states and root (recent) actions into
@@ -2586,11 +2554,9 @@ static int mcts_start(rl_mcts *m, HostCall &hc, const MctsBufs &b, DevPtr<uint32
     double *d_states = m->roots, *d_actions = d_states + K * 11;
     int rc;
     if ((rc = hc.up(d_keys, keys.data(), keys.size())) || (rc = hc.up(d_states, states, K * 11)) ||
-        (rc = hc.up(d_actions, actions, K)))
+        (rc = hc.up(d_actions, actions, K)) ||
+        (rc = launch("mcts_start_kernel", mcts_start_kernel, dim3((K + 63) / 64), dim3(64), 0, hc.st, m->mp, b, d_states, d_actions)))
         return rc;
-    hipLaunchKernelGGL(mcts_start_kernel, dim3((K + 63) / 64), dim3(64), 0, hc.st, m->mp, b, (const double *)d_states,
-                       (const double *)d_actions);
-    if (hipGetLastError() != hipSuccess) return fail(RL_ERR_HIP, "mcts_start_kernel launch failed");
     return plan_roots(m, hc.st);
 }
 
@@ -2631,39 +2597,24 @@ static int mcts_iterations(rl_mcts *m, const Loop &lp, const MctsBufs &bufs, uin
     MctsBufs b = bufs;
     if (terms) b.vel = m->terms;
     const uint64_t KB = (uint64_t)K * B, per_it = (uint64_t)K * (1 + L) * B;
-    int rc = RL_OK;
-    for (int t = 0; t < n && rc == RL_OK; ++t) {
+    for (int t = 0; t < n; ++t) {
         const long it = it0 + t;
         const uint64_t off = base + KB + (uint64_t)it * per_it;
-        hipLaunchKernelGGL(mcts_select_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, (int)it);
-        if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_select_kernel launch failed");
-        if (!rc) rc = mcts_act(m, lp, b, off, 0, st);
-        if (!rc) {
-            if (terms)
-                hipLaunchKernelGGL(rollout_xy_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, (const double *)m->cstate,
-                                   (const double *)m->actions, K, L, m->prm.action_every, m->prm.dt, (float *)m->rposes,
-                                   (double *)m->vel, (double *)m->rxy);
-            else
-                hipLaunchKernelGGL(rollout_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, (const double *)m->cstate,
-                                   (const double *)m->actions, K, L, m->prm.action_every, m->prm.dt, (float *)m->rposes,
-                                   (double *)nullptr, (double *)m->vel);
-            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "rollout_kernel launch failed");
-        }
-        if (!rc && terms) {
-            hipLaunchKernelGGL(plan_term_kernel, dim3(K), dim3(64 * PLAN_TERM_WAVES), 0, st, T, tp, L, (const double *)m->cstate,
-                               (const double *)m->rxy, (const double *)m->vel, plan_roots_of(m), (double *)m->terms,
-                               (double *)nullptr, (int *)nullptr, (double *)nullptr);
-            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "plan_term_kernel launch failed");
-        }
-        if (!rc)
-            rc = crash_groups_device(m->h, lp.at(off + KB), m->rposes, K, L, m->prm.fov, B, m->edge, m->prm.crash_thresh,
-                                     m->first, m->rranges, st);
-        if (!rc) {
-            hipLaunchKernelGGL(mcts_backup_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b);
-            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_backup_kernel launch failed");
-        }
+        int rc;
+        if ((rc = launch("mcts_select_kernel", mcts_select_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, (int)it)) ||
+            (rc = mcts_act(m, lp, b, off, 0, st)) ||
+            (rc = terms ? launch("rollout_xy_kernel", rollout_xy_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, m->cstate,
+                                 m->actions, K, L, m->prm.action_every, m->prm.dt, m->rposes, m->vel, m->rxy)
+                        : launch("rollout_kernel", rollout_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, m->cstate,
+                                 m->actions, K, L, m->prm.action_every, m->prm.dt, m->rposes, nullptr, m->vel)) ||
+            (terms && (rc = launch("plan_term_kernel", plan_term_kernel, dim3(K), dim3(64 * PLAN_TERM_WAVES), 0, st, T, tp, L,
+                                   m->cstate, m->rxy, m->vel, plan_roots_of(m), m->terms, nullptr, nullptr, nullptr))) ||
+            (rc = crash_groups_device(m->h, lp.at(off + KB), m->rposes, K, L, m->prm.fov, B, m->edge, m->prm.crash_thresh, m->first,
+                                      m->rranges, st)) ||
+            (rc = launch("mcts_backup_kernel", mcts_backup_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b)))
+            return rc;
     }
-    return rc;
+    return RL_OK;
 }
 
 extern "C" int rl_mcts_run(rl_mcts *m, int n_iterations)
@@ -2746,20 +2697,17 @@ extern "C" int rl_mcts_drive(rl_mcts *m, const double *states_in, const double *
     const MctsDrive dv{d_states, d_recent, m->dr_first, m->dr_actions, m->dr_visits,
                        trace_states_or_null ? (double *)m->dr_trace : nullptr, D, steps_per_decision, steer_clip};
     const uint64_t stride = (uint64_t)K * B * (1 + (uint64_t)I * (1 + L));
-    rc = mcts_start(m, hc, b, m->dr_keys, keys, states_in, recent_in);
+    if ((rc = mcts_start(m, hc, b, m->dr_keys, keys, states_in, recent_in))) return rc;
     uint64_t base = lp.base;
-    for (int d = 0; d < D && rc == RL_OK; ++d) {
+    for (int d = 0; d < D; ++d) {
         base = lp.base + (uint64_t)d * stride;
         b.keys = m->dr_keys + (size_t)d * K;
-        rc = mcts_act(m, lp, b, base, 1, st);
-        if (!rc) rc = mcts_iterations(m, lp, b, base, 0, I, st);
-        if (!rc) {
-            hipLaunchKernelGGL(mcts_advance_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, dv, d);
-            if (hipGetLastError() != hipSuccess) rc = fail(RL_ERR_HIP, "mcts_advance_kernel launch failed");
-        }
-        if (!rc && d + 1 < D) rc = plan_roots(m, st);          // the next decision's roots: their segment, goal and point
+        // (plan_roots: the next decision's roots, their segment, goal and point; a refused launch: the trees need a reset)
+        if ((rc = mcts_act(m, lp, b, base, 1, st)) || (rc = mcts_iterations(m, lp, b, base, 0, I, st)) ||
+            (rc = launch("mcts_advance_kernel", mcts_advance_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, dv, d)) ||
+            (d + 1 < D && (rc = plan_roots(m, st))))
+            return rc;
     }
-    if (rc) return rc;                                 // (the trees need a reset)
     // the planner keeps the last decision's trees: its keys, ray offset and iteration count are that decision's
     HIPCHK(hipMemcpyAsync(m->keys, b.keys, (size_t)K * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     if ((rc = hc.down(first, m->dr_first, K)) || (rc = hc.down(states_out, (const double *)d_states, (size_t)K * 11)) ||
@@ -2781,11 +2729,10 @@ extern "C" int rl_mcts_best(rl_mcts *m, double *actions, int *visits, int *n_nod
     HIPCHK(hipSetDevice(m->device));
     HostCall hc(m->c->stream);
     const int K = m->prm.n_trees;
-    hipLaunchKernelGGL(mcts_best_kernel, dim3((K + 63) / 64), dim3(64), 0, hc.st, m->mp, mcts_bufs(m),
-                       (double *)m->best_a, (int *)m->best_v, (int *)m->best_n);
-    HIPCHK(hipGetLastError());
     int rc;
-    if ((rc = hc.down(actions, m->best_a, K)) || (rc = hc.down(visits, m->best_v, K)) || (rc = hc.down(n_nodes, m->best_n, K)))
+    if ((rc = launch("mcts_best_kernel", mcts_best_kernel, dim3((K + 63) / 64), dim3(64), 0, hc.st, m->mp, mcts_bufs(m), m->best_a,
+                     m->best_v, m->best_n)) ||
+        (rc = hc.down(actions, m->best_a, K)) || (rc = hc.down(visits, m->best_v, K)) || (rc = hc.down(n_nodes, m->best_n, K)))
         return rc;
     return hc.finish();
 }
@@ -2846,8 +2793,9 @@ extern "C" int rl_mcts_probe_ucb(int device, const double *reward, const int *vi
         hipMemcpy(dl.p, lt.data(), lt.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
         return fail(RL_ERR_HIP, "rl_mcts_probe_ucb: upload failed");
     const int grid = (int)std::min<size_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(mcts_ucb_probe_kernel, dim3(grid), dim3(256), 0, nullptr, (const double *)dr.p,
-                       (const int *)dv.p, (const int *)ds.p, (const double *)dl.p, (long)n, C, (double *)dout.p);
+    if ((rc = launch("mcts_ucb_probe_kernel", mcts_ucb_probe_kernel, dim3(grid), dim3(256), 0, nullptr, (const double *)dr.p,
+                     (const int *)dv.p, (const int *)ds.p, (const double *)dl.p, (long)n, C, (double *)dout.p)))
+        return rc;
     if (hipMemcpy(out, dout.p, n * 8, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(RL_ERR_HIP, "rl_mcts_probe_ucb: kernel or download failed");
     return RL_OK;
@@ -2968,16 +2916,13 @@ extern "C" int rl_car_rollout_track(rl_car *c, rl_track *t, const rl_plan_track_
     const TrackTable T = t ? track_table(t) : TrackTable{};
     const PlanTrackParams tp{mode, p->window, p->goal_span, p->lookahead};
     const PlanRoots roots{c->tk_root_seg, c->tk_root_s, c->tk_goal, c->tk_point, c->tk_has};
-    hipLaunchKernelGGL(plan_root_kernel, dim3((R + MCTS_TREES - 1) / MCTS_TREES), dim3(64 * MCTS_TREES), 0, hc.st, R, T, tp,
-                       (const double *)c->states, points ? (const double *)c->tk_points_in : nullptr, roots);
-    HIPCHK(hipGetLastError());
-    if (anchors && (rc = hc.up((int *)c->tk_root_seg, anchor_segment_or_null, n))) return rc;
-    hipLaunchKernelGGL(plan_term_kernel, dim3(R), dim3(64 * PLAN_TERM_WAVES), 0, hc.st, T, tp, n_steps, (const double *)c->states,
-                       (const double *)c->tk_xy, (const double *)c->vel, roots, (double *)c->tk_terms, (double *)c->tk_s,
-                       (int *)c->tk_seg, (double *)c->tk_start_s);
-    HIPCHK(hipGetLastError());
     const bool progress = mode == PLAN_PROGRESS;
-    if ((rc = hc.down(terms, c->tk_terms, rows)) || (rc = hc.down(progress ? s_or_null : nullptr, c->tk_s, rows)) ||
+    if ((rc = launch("plan_root_kernel", plan_root_kernel, dim3((R + MCTS_TREES - 1) / MCTS_TREES), dim3(64 * MCTS_TREES), 0, hc.st, R,
+                     T, tp, c->states, points ? (const double *)c->tk_points_in : nullptr, roots)) ||
+        (anchors && (rc = hc.up((int *)c->tk_root_seg, anchor_segment_or_null, n))) ||
+        (rc = launch("plan_term_kernel", plan_term_kernel, dim3(R), dim3(64 * PLAN_TERM_WAVES), 0, hc.st, T, tp, n_steps, c->states,
+                     c->tk_xy, c->vel, roots, c->tk_terms, c->tk_s, c->tk_seg, c->tk_start_s)) ||
+        (rc = hc.down(terms, c->tk_terms, rows)) || (rc = hc.down(progress ? s_or_null : nullptr, c->tk_s, rows)) ||
         (rc = hc.down(progress ? segment_or_null : nullptr, c->tk_seg, rows)) ||
         (rc = hc.down(progress ? start_s_or_null : nullptr, c->tk_start_s, n)))
         return rc;

@@ -321,7 +321,6 @@ static int ensure_table(TableCache &cache, bool fresh, const rl_map *m, hipStrea
     if (fresh) return cache.wait(stream);
     int rc = cache.begin_rebuild();              // launches of other streams may still read the old copy
     if (rc || (rc = build())) return rc;
-    HIPCHK(hipGetLastError());
     return cache.built(m, stream);
 }
 
@@ -350,7 +349,9 @@ static int ensure_fan_table(FanTabs &t, const FanParams &f, float fov, hipStream
     }
     int rc = slot->tab.ensure((size_t)f.num_rays * sizeof(float2));
     if (rc) return rc;
-    hipLaunchKernelGGL(fan_table_kernel, dim3((f.num_rays + 255) / 256), dim3(256), 0, stream, f, (float2 *)slot->tab.p);
+    if ((rc = launch("fan_table_kernel", fan_table_kernel, dim3((f.num_rays + 255) / 256), dim3(256), 0, stream, f,
+                     (float2 *)slot->tab.p)))
+        return rc;
     slot->fov_bits = bits;
     slot->num_rays = f.num_rays;
     slot->last_use = ++t.clock;
@@ -374,8 +375,8 @@ static int build_lut(LutTable &t, const rl_map *m, float max_range, float step_c
     lp.debug = debug;
     const long cells = (long)m->rows * m->cols;
     const int grid = (int)std::min(cells, (long)m->n_cu * 16);
-    hipLaunchKernelGGL(lut_build_kernel, dim3(grid), dim3(256), 0, stream, m->mp, lp, max_range, step_coeff, 0, m->rows);
-    return RL_OK;
+    return launch("lut_build_kernel", lut_build_kernel, dim3(grid), dim3(256), 0, stream, m->mp, lp, max_range, step_coeff, 0,
+                  m->rows);
 }
 
 static int ensure_lut(rl_method *h, hipStream_t stream)
@@ -476,28 +477,30 @@ static int build_cddt(CddtTable &t, const rl_map *m, int theta_disc, int debug, 
     }
     const dim3 pgrid((unsigned)std::max<uint32_t>(1u, (m->n_edges + CDDT_CHUNK - 1) / CDDT_CHUNK), (unsigned)nb);
     // count -> exclusive scan (CSR offsets) -> fill -> sort every bucket
-    hipLaunchKernelGGL(cddt_project_kernel<false>, pgrid, dim3(256), lds_fill / 2, stream, cp, (const uint32_t *)m->d_edges,
-                       (const uint32_t *)m->d_n_edges, (uint32_t *)t.cursor.p);
+    if ((rc = launch("cddt_project_kernel", cddt_project_kernel<false>, pgrid, dim3(256), lds_fill / 2, stream, cp, m->d_edges,
+                     m->d_n_edges, (uint32_t *)t.cursor.p)))
+        return rc;
     // [0] big-bucket count (zeroed by the sort's last reader), [1..64) spare, [64..64+nb) bin totals, then the list
     uint32_t *big_count = (uint32_t *)t.tmp.p, *bin_total = (uint32_t *)t.tmp.p + 64;
     uint32_t *bin_lines = bin_total + nb, *big_list = bin_lines + nb;
     HIPCHK(hipMemsetAsync(big_count, 0, 4, stream));
-    hipLaunchKernelGGL(cddt_scan_bins_kernel, dim3(nb), dim3(256), 0, stream, cp, (const uint32_t *)t.cursor.p, bin_total, bin_lines);
-    hipLaunchKernelGGL(cddt_scan_add_kernel, dim3(nb), dim3(256), 0, stream, cp, (const uint32_t *)t.cursor.p,
-                       (const uint32_t *)bin_total, (const uint32_t *)bin_lines, big_list, big_count);
-    hipLaunchKernelGGL(cddt_project_kernel<true>, pgrid, dim3(256), lds_fill, stream, cp, (const uint32_t *)m->d_edges,
-                       (const uint32_t *)m->d_n_edges, (uint32_t *)t.cursor.p);
     // two launches of the sort kernel: the large buckets (workgroup each, 64 KB of LDS) and the small ones
     // (wave each, no LDS — in one launch the LDS size of the large path would cap everybody's occupancy)
     const uint32_t n_big_wg = (uint32_t)m->n_cu;
-    hipLaunchKernelGGL(cddt_sort_kernel, dim3(n_big_wg), dim3(256), (size_t)t.lds_sort * sizeof(float), stream,
-                       (const uint32_t *)t.offsets.p, nbk, (const float *)t.xs2.p, (const uint2 *)t.hdr.p, (float *)t.tab.p,
-                       (const uint32_t *)big_list, (const uint32_t *)big_count, n_big_wg, (uint32_t)t.lds_sort);
     const int sgrid = (int)std::max(1L, std::min(((long)nbk + 3) / 4, (long)m->n_cu * 32));
-    hipLaunchKernelGGL(cddt_sort_kernel, dim3(sgrid), dim3(256), 0, stream, (const uint32_t *)t.offsets.p, nbk,
-                       (const float *)t.xs2.p, (const uint2 *)t.hdr.p, (float *)t.tab.p, (const uint32_t *)big_list,
-                       (const uint32_t *)big_count, 0u, (uint32_t)t.lds_sort);
-    return RL_OK;
+    if ((rc = launch("cddt_scan_bins_kernel", cddt_scan_bins_kernel, dim3(nb), dim3(256), 0, stream, cp,
+                     (const uint32_t *)t.cursor.p, bin_total, bin_lines)) ||
+        (rc = launch("cddt_scan_add_kernel", cddt_scan_add_kernel, dim3(nb), dim3(256), 0, stream, cp,
+                     (const uint32_t *)t.cursor.p, bin_total, bin_lines, big_list, big_count)) ||
+        (rc = launch("cddt_project_kernel", cddt_project_kernel<true>, pgrid, dim3(256), lds_fill, stream, cp, m->d_edges,
+                     m->d_n_edges, (uint32_t *)t.cursor.p)) ||
+        (rc = launch("cddt_sort_kernel", cddt_sort_kernel, dim3(n_big_wg), dim3(256), (size_t)t.lds_sort * sizeof(float), stream,
+                     (const uint32_t *)t.offsets.p, nbk, (const float *)t.xs2.p, (const uint2 *)t.hdr.p, (float *)t.tab.p,
+                     big_list, big_count, n_big_wg, (uint32_t)t.lds_sort)))
+        return rc;
+    return launch("cddt_sort_kernel", cddt_sort_kernel, dim3(sgrid), dim3(256), 0, stream, (const uint32_t *)t.offsets.p, nbk,
+                  (const float *)t.xs2.p, (const uint2 *)t.hdr.p, (float *)t.tab.p, big_list, big_count, 0u,
+                  (uint32_t)t.lds_sort);
 }
 
 static int ensure_cddt(rl_method *h, hipStream_t stream)
@@ -542,10 +545,11 @@ static int build_blpad(BlPadMaps &t, const rl_map *m, float max_range, hipStream
     int rc = t.buf.ensure((words_n + words_t) * 4);
     if (rc) return rc;
     uint32_t *out_n = (uint32_t *)t.buf.p, *out_t = out_n + words_n;
-    hipLaunchKernelGGL(bl_pad_bits_kernel, dim3((stride_n + 255) / 256, prow_n), dim3(256), 0, stream, m->d_occ,
-                       m->rows, m->cols, 0, pad, pad32, stride_n, prow_n, out_n);
-    hipLaunchKernelGGL(bl_pad_bits_kernel, dim3((stride_t + 255) / 256, prow_t), dim3(256), 0, stream, m->d_occ,
-                       m->rows, m->cols, 1, pad, pad32, stride_t, prow_t, out_t);
+    if ((rc = launch("bl_pad_bits_kernel", bl_pad_bits_kernel, dim3((stride_n + 255) / 256, prow_n), dim3(256), 0, stream, m->d_occ,
+                     m->rows, m->cols, 0, pad, pad32, stride_n, prow_n, out_n)) ||
+        (rc = launch("bl_pad_bits_kernel", bl_pad_bits_kernel, dim3((stride_t + 255) / 256, prow_t), dim3(256), 0, stream, m->d_occ,
+                     m->rows, m->cols, 1, pad, pad32, stride_t, prow_t, out_t)))
+        return rc;
     BlPad &bp = t.blp;
     bp.bits = out_n;
     bp.stride_n = stride_n;
@@ -622,43 +626,34 @@ static int bin_poses(rl_method *h, LaunchCtx &cx, const float *d_poses, int n_po
             const int cnt = ((m->cols >> cshift) + 1) * ((m->rows >> cshift) + 1);
             const size_t n_ctr = (size_t)cnt * n_wg;
             if ((rc = cx.hist.ensure((n_ctr + cnt) * sizeof(uint32_t)))) return rc;     // counters, then tile totals
-            hipLaunchKernelGGL(pose_prep_kernel, dim3(n_wg), dim3(256), (size_t)cnt * 4, stream,
-                               m->mp, d_poses, n_poses, (PoseRec *)cx.rec.p,
-                               (uint32_t *)cx.keys.p, (uint32_t *)cx.hist.p, n_wg, cshift, ctx,
-                               cnt, (uint32_t *)nullptr, walk_outside, ppw, (float *)nullptr, coeff);
             uint32_t *tile_total = (uint32_t *)cx.hist.p + n_ctr;
-            hipLaunchKernelGGL(tile_scan_a_kernel, dim3(cnt), dim3(256), 0, stream, (uint32_t *)cx.hist.p, n_wg,
-                               tile_total);
-            hipLaunchKernelGGL(pose_scatter_kernel, dim3(n_wg), dim3(256), (size_t)cnt * 4, stream,
-                               n_poses, (const PoseRec *)cx.rec.p, (const uint32_t *)cx.keys.p,
-                               (const uint32_t *)cx.hist.p, (const uint32_t *)tile_total, n_wg, cnt, (PoseRec *)cx.rec_sorted.p,
-                               (uint32_t *)cx.order.p, ppw, m->mp, d0, coeff);
-        } else {
-            // caller's order kept: one fully parallel pass, records land in place
-            hipLaunchKernelGGL(pose_prep_kernel, dim3(n_wg), dim3(256), 0, stream, m->mp, d_poses,
-                               n_poses, (PoseRec *)cx.rec_sorted.p, (uint32_t *)nullptr,
-                               (uint32_t *)nullptr, n_wg, shift, tiles_x, n_tiles,
-                               (uint32_t *)cx.order.p, walk_outside, ppw, d0, coeff);
+            if ((rc = launch("pose_prep_kernel", pose_prep_kernel, dim3(n_wg), dim3(256), (size_t)cnt * 4, stream, m->mp, d_poses,
+                             n_poses, (PoseRec *)cx.rec.p, (uint32_t *)cx.keys.p, (uint32_t *)cx.hist.p, n_wg, cshift, ctx, cnt,
+                             nullptr, walk_outside, ppw, nullptr, coeff)) ||
+                (rc = launch("tile_scan_a_kernel", tile_scan_a_kernel, dim3(cnt), dim3(256), 0, stream, (uint32_t *)cx.hist.p,
+                             n_wg, tile_total)))
+                return rc;
+            return launch("pose_scatter_kernel", pose_scatter_kernel, dim3(n_wg), dim3(256), (size_t)cnt * 4, stream, n_poses,
+                          (const PoseRec *)cx.rec.p, (const uint32_t *)cx.keys.p, (const uint32_t *)cx.hist.p, tile_total, n_wg,
+                          cnt, (PoseRec *)cx.rec_sorted.p, (uint32_t *)cx.order.p, ppw, m->mp, d0, coeff);
         }
-    } else if (binning == RL_BIN_SMALL_KEYS || binning == RL_BIN_SMALL_RECORDS) {
-        if (keys_only)
-            hipLaunchKernelGGL(pose_bin_small_kernel<true>, dim3(1), dim3(1024),
-                               (size_t)(n_tiles + 1024) * sizeof(uint32_t), stream, m->mp, d_poses,
-                               n_poses, (PoseRec *)cx.rec_sorted.p, (uint32_t *)cx.order.p, shift,
-                               tiles_x, n_tiles, walk_outside, (float *)nullptr, coeff);
-        else
-            hipLaunchKernelGGL(pose_bin_small_kernel<false>, dim3(1), dim3(1024),
-                               (size_t)(n_tiles + 1024) * sizeof(uint32_t), stream, m->mp, d_poses,
-                               n_poses, (PoseRec *)cx.rec_sorted.p, (uint32_t *)cx.order.p, shift,
-                               tiles_x, n_tiles, walk_outside, d0, coeff);
-    } else {
-        hipLaunchKernelGGL(pose_bin_kernel, dim3(1), dim3(1024),
-                           (size_t)(n_tiles + 1024) * sizeof(uint32_t), stream, m->mp, d_poses,
-                           n_poses, (PoseRec *)cx.rec.p, (PoseRec *)cx.rec_sorted.p,
-                           (uint32_t *)cx.order.p, (uint32_t *)cx.keys.p, shift, tiles_x,
-                           n_tiles, do_sort, walk_outside, d0, coeff);
+        // caller's order kept: one fully parallel pass, records land in place
+        return launch("pose_prep_kernel", pose_prep_kernel, dim3(n_wg), dim3(256), 0, stream, m->mp, d_poses, n_poses,
+                      (PoseRec *)cx.rec_sorted.p, nullptr, nullptr, n_wg, shift, tiles_x, n_tiles, (uint32_t *)cx.order.p,
+                      walk_outside, ppw, d0, coeff);
     }
-    return RL_OK;
+    const size_t lds = (size_t)(n_tiles + 1024) * sizeof(uint32_t);
+    if (binning == RL_BIN_SMALL_KEYS)
+        return launch("pose_bin_small_kernel", pose_bin_small_kernel<true>, dim3(1), dim3(1024), lds, stream, m->mp, d_poses,
+                      n_poses, (PoseRec *)cx.rec_sorted.p, (uint32_t *)cx.order.p, shift, tiles_x, n_tiles, walk_outside,
+                      nullptr, coeff);
+    if (binning == RL_BIN_SMALL_RECORDS)
+        return launch("pose_bin_small_kernel", pose_bin_small_kernel<false>, dim3(1), dim3(1024), lds, stream, m->mp, d_poses,
+                      n_poses, (PoseRec *)cx.rec_sorted.p, (uint32_t *)cx.order.p, shift, tiles_x, n_tiles, walk_outside, d0,
+                      coeff);
+    return launch("pose_bin_kernel", pose_bin_kernel, dim3(1), dim3(1024), lds, stream, m->mp, d_poses, n_poses,
+                  (PoseRec *)cx.rec.p, (PoseRec *)cx.rec_sorted.p, (uint32_t *)cx.order.p, (uint32_t *)cx.keys.p, shift,
+                  tiles_x, n_tiles, do_sort, walk_outside, d0, coeff);
 }
 
 static FastDiv make_fastdiv(uint32_t d)
@@ -747,8 +742,9 @@ static int build_step_map(StepMap &t, const rl_map *m, float max_range, float st
         t.pad = fit.pad;
         t.at = {(size_t)t.pad << 4, (int)M, (uint32_t)tg.padr * M, 0xCu | (~0u << tg.K)};
         if ((rc = t.pdt.ensure(fit.bytes))) return rc;
-        hipLaunchKernelGGL(pad_dt_tiled_kernel, dim3((tg.pcols + 255) / 256, tg.prows), dim3(256), 0, stream,
-                           m->d_dt, m->rows, m->cols, (float *)t.pdt.p, tg, step_coeff);
+        if ((rc = launch("pad_dt_tiled_kernel", pad_dt_tiled_kernel, dim3((tg.pcols + 255) / 256, tg.prows), dim3(256), 0, stream,
+                         m->d_dt, m->rows, m->cols, (float *)t.pdt.p, tg, step_coeff)))
+            return rc;
     } else {
         const int stride = (m->cols + 2 * t.pad + 31) & ~31, prow = m->rows + 2 * t.pad;
         // (row-major address: v_mad_i32_i24 r * stride + c, then << 2 in 32 bits)
@@ -757,8 +753,9 @@ static int build_step_map(StepMap &t, const rl_map *m, float max_range, float st
                         max_range);
         t.at = {0, stride, (uint32_t)(((size_t)t.pad * stride + t.pad) * 4), 0u};
         if ((rc = t.pdt.ensure((size_t)prow * stride * sizeof(float)))) return rc;
-        hipLaunchKernelGGL(pad_dt_kernel, dim3((stride + 255) / 256, prow), dim3(256), 0, stream, m->d_dt, m->rows, m->cols,
-                           (float *)t.pdt.p, t.pad, stride, step_coeff);
+        if ((rc = launch("pad_dt_kernel", pad_dt_kernel, dim3((stride + 255) / 256, prow), dim3(256), 0, stream, m->d_dt, m->rows,
+                         m->cols, (float *)t.pdt.p, t.pad, stride, step_coeff)))
+            return rc;
     }
     // the CODE map next to it: palette of the map's distinct steps (mark -> scan), then the tiled map of their codes.
     // The palette size decides the launches' LDS, so the host reads it back here (a map build, not a scan).
@@ -773,18 +770,21 @@ static int build_step_map(StepMap &t, const rl_map *m, float max_range, float st
         if (!t.pin_cnum) HIPCHK(t.pin_cnum.alloc(2 * sizeof(uint32_t)));
         HIPCHK(hipMemsetAsync(t.cval.p, 0, (size_t)cf.nb * sizeof(float), stream));
         const size_t n_cells = (size_t)m->rows * m->cols;
-        hipLaunchKernelGGL(code_mark_kernel, dim3((unsigned)std::min<size_t>((n_cells + 255) / 256, (size_t)m->n_cu * 8)), dim3(256),
-                           0, stream, m->d_dt, n_cells, (float *)t.cval.p, cf.nb, step_coeff, max_range);
-        hipLaunchKernelGGL(code_scan_kernel, dim3(1), dim3(1024), 0, stream, (const float *)t.cval.p, cf.nb, step_coeff,
-                           (uint32_t *)t.cidx.p, (float *)t.ctab.p, cap, (uint32_t *)t.cnum.p);
+        if ((rc = launch("code_mark_kernel", code_mark_kernel,
+                         dim3((unsigned)std::min<size_t>((n_cells + 255) / 256, (size_t)m->n_cu * 8)), dim3(256), 0, stream, m->d_dt,
+                         n_cells, (float *)t.cval.p, cf.nb, step_coeff, max_range)) ||
+            (rc = launch("code_scan_kernel", code_scan_kernel, dim3(1), dim3(1024), 0, stream, (const float *)t.cval.p, cf.nb,
+                         step_coeff, (uint32_t *)t.cidx.p, (float *)t.ctab.p, cap, (uint32_t *)t.cnum.p)))
+            return rc;
         HIPCHK(hipMemcpyAsync(t.pin_cnum, t.cnum.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         if (t.pin_cnum[1] == 0u && t.pin_cnum[0] <= cap) {
             const TiledGeom tg{cf.K, cf.pad, cf.padr, cf.pcols, cf.prows};
             if ((rc = t.cmap.ensure(cf.bytes))) return rc;
-            hipLaunchKernelGGL((pad_code_tiled_kernel<1>), dim3((tg.pcols + 255) / 256, tg.prows), dim3(256), 0, stream,
-                               m->d_dt, m->rows, m->cols, t.cmap.p, tg, step_coeff, max_range,
-                               (const uint32_t *)t.cidx.p, cf.nb, (const uint32_t *)t.cnum.p);
+            if ((rc = launch("pad_code_tiled_kernel", pad_code_tiled_kernel<1>, dim3((tg.pcols + 255) / 256, tg.prows), dim3(256), 0,
+                             stream, m->d_dt, m->rows, m->cols, t.cmap.p, tg, step_coeff, max_range, (const uint32_t *)t.cidx.p,
+                             cf.nb, (const uint32_t *)t.cnum.p)))
+                return rc;
             const uint32_t M = (1u << cf.es) + (1u << (cf.K - 3));
             t.code_at = {(size_t)cf.pad << (3 + cf.es), (int)M, (uint32_t)cf.padr * M, (7u << cf.es) | (~0u << cf.K)};
             t.code_n = (int)t.pin_cnum[0];
@@ -832,8 +832,8 @@ static int dispatch_rm_stream(const rl_launch_plan &pl, hipStream_t stream, cons
     if (pl.lds_bytes > 48 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   pl.lds_bytes);
-    kernel<<<dim3(pl.grid), dim3(pl.block), (size_t)pl.lds_bytes, stream>>>(pm, f, sp, d_out, d_hits, d_steps, cp);
-    return RL_OK;
+    return launch("rm_fan_stream_kernel", kernel, dim3(pl.grid), dim3(pl.block), (size_t)pl.lds_bytes, stream, pm, f, sp, d_out,
+                  d_hits, d_steps, cp);
 }
 
 // enqueue the fan kernels on `stream`; all pointers are device pointers.  What is launched is decided by
@@ -892,11 +892,11 @@ static int launch_lut(const FanLaunch &L)
         // the planned waves in workgroups of LUT_REFINE_WG lanes, each with the beam table in front of its waves' rows
         const unsigned per = LUT_REFINE_WG / L.block.x;
         const size_t lds = L.lds * per + (size_t)lut_dir_dwords(L.f.num_rays) * sizeof(uint32_t);
-        kernel<<<dim3((L.grid.x + per - 1) / per), dim3(LUT_REFINE_WG), lds, L.stream>>>(L.m->mp, L.f, L.h->lut.lp, L.d_poses, L.d_out);
-        return RL_OK;
+        return launch("lut_fan_lds_refine_kernel", kernel, dim3((L.grid.x + per - 1) / per), dim3(LUT_REFINE_WG), lds, L.stream,
+                      L.m->mp, L.f, L.h->lut.lp, L.d_poses, L.d_out);
     }
-    kernel<<<L.grid, L.block, L.lds, L.stream>>>(L.m->mp, L.f, L.h->lut.lp, L.d_poses, L.d_out);
-    return RL_OK;
+    return launch(pl.kernel == RL_K_LUT_LDS ? "lut_fan_lds_kernel" : refine ? "lut_fan_refine_kernel" : "lut_fan_kernel", kernel,
+                  L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, L.h->lut.lp, L.d_poses, L.d_out);
 }
 
 // RL_K_CDDT_BINS
@@ -912,9 +912,8 @@ static int launch_cddt_bins(const FanLaunch &L)
         d_order = (const uint32_t *)L.cx->order.p;
     }
     if (L.timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
-    hipLaunchKernelGGL(cddt_fan_bins_kernel, L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, h->cddt.cdp, L.d_poses, L.d_out,
-                       d_order, L.pl.bands, L.pl.nl, L.pl.ch);
-    return RL_OK;
+    return launch("cddt_fan_bins_kernel", cddt_fan_bins_kernel, L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, h->cddt.cdp,
+                  L.d_poses, L.d_out, d_order, L.pl.bands, L.pl.nl, L.pl.ch);
 }
 
 // RL_K_CDDT_THETA
@@ -933,23 +932,21 @@ static int launch_cddt_theta(const FanLaunch &L)
     float4 *d_prep = (float4 *)L.cx->cddt_r.p;
     float *d_r = (float *)((char *)L.cx->cddt_r.p + prep_bytes);
     if (L.timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
-    hipLaunchKernelGGL(cddt_theta_prep_kernel, dim3((unsigned)std::max(1, std::min((L.n_poses + 255) / 256, L.m->n_cu * 8))),
-                       dim3(256), 0, L.stream, L.m->mp, L.f, h->cddt.cdp, L.d_poses, d_prep);
-    if (fused) {
-        hipLaunchKernelGGL(cddt_theta_fused_kernel, L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, h->cddt.cdp, L.d_poses,
-                           (const float4 *)d_prep, L.d_out, L.pl.nl);
-        return RL_OK;
-    }
-    if (form == plan::CDDT_THETA_SEARCH2)
-        hipLaunchKernelGGL(cddt_theta_search2_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f, h->cddt.cdp, L.d_poses,
-                           (const float4 *)d_prep, d_r, L.pl.bands);
-    else
-        hipLaunchKernelGGL(cddt_theta_search_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f, h->cddt.cdp, L.d_poses,
-                           (const float4 *)d_prep, d_r, L.pl.bands);
+    if ((rc = launch("cddt_theta_prep_kernel", cddt_theta_prep_kernel,
+                     dim3((unsigned)std::max(1, std::min((L.n_poses + 255) / 256, L.m->n_cu * 8))), dim3(256), 0, L.stream, L.m->mp,
+                     L.f, h->cddt.cdp, L.d_poses, d_prep)))
+        return rc;
+    if (fused)
+        return launch("cddt_theta_fused_kernel", cddt_theta_fused_kernel, L.grid, L.block, L.lds, L.stream, L.m->mp, L.f,
+                      h->cddt.cdp, L.d_poses, d_prep, L.d_out, L.pl.nl);
+    const bool search2 = form == plan::CDDT_THETA_SEARCH2;
+    if ((rc = launch(search2 ? "cddt_theta_search2_kernel" : "cddt_theta_search_kernel",
+                     search2 ? cddt_theta_search2_kernel : cddt_theta_search_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f,
+                     h->cddt.cdp, L.d_poses, d_prep, d_r, L.pl.bands)))
+        return rc;
     const int n_grp = (L.n_poses + (1 << L.pl.ch) - 1) >> L.pl.ch;
-    hipLaunchKernelGGL(cddt_theta_fan_kernel, dim3((unsigned)std::max(1, std::min(n_grp, L.m->n_cu * 8))), L.block, L.lds,
-                       L.stream, L.m->mp, L.f, h->cddt.cdp, L.d_poses, (const float *)d_r, L.d_out, L.pl.ch, L.pl.nl);
-    return RL_OK;
+    return launch("cddt_theta_fan_kernel", cddt_theta_fan_kernel, dim3((unsigned)std::max(1, std::min(n_grp, L.m->n_cu * 8))),
+                  L.block, L.lds, L.stream, L.m->mp, L.f, h->cddt.cdp, L.d_poses, d_r, L.d_out, L.pl.ch, L.pl.nl);
 }
 
 // RL_K_CDDT_RAYS
@@ -958,8 +955,8 @@ static int launch_cddt_rays(const FanLaunch &L)
     int rc;
     if ((rc = ensure_cddt(L.h, L.stream))) return rc;
     if (L.timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
-    hipLaunchKernelGGL(cddt_fan_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f, L.h->cddt.cdp, L.d_poses, L.d_out);
-    return RL_OK;
+    return launch("cddt_fan_kernel", cddt_fan_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f, L.h->cddt.cdp, L.d_poses,
+                  L.d_out);
 }
 
 // RL_K_BL_STREAM
@@ -979,13 +976,8 @@ static int launch_bl_stream(const FanLaunch &L)
     sp.div_bands = make_fastdiv((uint32_t)L.pl.bands);
     sp.plain_store = L.plain_store;
     if (L.timing == 2) HIPCHK(hipEventRecord(h->ev0, L.stream));
-    if (L.aux)
-        hipLaunchKernelGGL((bl_fan_stream_kernel<true, 1024>), L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, sp, h->blpad.blp,
-                           L.d_out, L.d_hits, L.d_steps);
-    else
-        hipLaunchKernelGGL((bl_fan_stream_kernel<false, 1024>), L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, sp, h->blpad.blp,
-                           L.d_out, L.d_hits, L.d_steps);
-    return RL_OK;
+    return launch("bl_fan_stream_kernel", L.aux ? bl_fan_stream_kernel<true, 1024> : bl_fan_stream_kernel<false, 1024>, L.grid,
+                  L.block, L.lds, L.stream, L.m->mp, L.f, sp, h->blpad.blp, L.d_out, L.d_hits, L.d_steps);
 }
 
 // RL_K_BL_LDS, RL_K_OCC_LDS
@@ -1003,12 +995,11 @@ static int launch_bl_lds(const FanLaunch &L)
         HIPCHK(hipFuncSetAttribute(fb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bl));
     }
     if (L.timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
-#define LAUNCH_BL(K) hipLaunchKernelGGL((K), L.grid, L.block, lds_bl, L.stream, L.m->mp, L.f, bp, L.d_poses, L.d_out, L.d_hits, L.d_steps)
     // (occ_fan_lds: unit-step march on an LDS-resident occupancy window — A/B partner, approximate)
-    if (bl) { if (L.aux) LAUNCH_BL(bl_fan_kernel<true>); else LAUNCH_BL(bl_fan_kernel<false>); }
-    else    { if (L.aux) LAUNCH_BL(occ_fan_lds_kernel<true>); else LAUNCH_BL(occ_fan_lds_kernel<false>); }
-#undef LAUNCH_BL
-    return RL_OK;
+    return launch(bl ? "bl_fan_kernel" : "occ_fan_lds_kernel",
+                  bl ? (L.aux ? bl_fan_kernel<true> : bl_fan_kernel<false>)
+                     : (L.aux ? occ_fan_lds_kernel<true> : occ_fan_lds_kernel<false>),
+                  L.grid, L.block, lds_bl, L.stream, L.m->mp, L.f, bp, L.d_poses, L.d_out, L.d_hits, L.d_steps);
 }
 
 // RL_K_RM_LITERAL
@@ -1017,13 +1008,8 @@ static int launch_rm_literal(const FanLaunch &L)
     const LiteralParams lt = make_literal(L.m);
     const long n_rays = (long)L.n_poses * L.num_rays;
     if (L.timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
-    if (L.aux)
-        hipLaunchKernelGGL((rm_literal_kernel<true, false>), L.grid, L.block, 0, L.stream, L.m->mp, L.f, lt, L.d_poses, n_rays,
-                           L.d_out, L.d_hits, L.d_steps);
-    else
-        hipLaunchKernelGGL((rm_literal_kernel<false, false>), L.grid, L.block, 0, L.stream, L.m->mp, L.f, lt, L.d_poses, n_rays,
-                           L.d_out, L.d_hits, L.d_steps);
-    return RL_OK;
+    return launch("rm_literal_kernel", L.aux ? rm_literal_kernel<true, false> : rm_literal_kernel<false, false>, L.grid, L.block,
+                  0, L.stream, L.m->mp, L.f, lt, L.d_poses, n_rays, L.d_out, L.d_hits, L.d_steps);
 }
 
 // RL_K_RM_CHUNK
@@ -1032,12 +1018,10 @@ static int launch_rm_chunk(const FanLaunch &L)
     CrashParams cp{nullptr, 0.0, nullptr, 1};
     if (L.crash) cp = *L.crash;
     if (L.timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
-#define LAUNCH_CHUNK(A, C) hipLaunchKernelGGL((rm_fan_kernel<A, C>), L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, L.d_poses, \
-                                              L.d_out, L.d_hits, L.d_steps, cp)
-    if (L.crash) { if (L.aux) LAUNCH_CHUNK(true, true); else LAUNCH_CHUNK(false, true); }
-    else         { if (L.aux) LAUNCH_CHUNK(true, false); else LAUNCH_CHUNK(false, false); }
-#undef LAUNCH_CHUNK
-    return RL_OK;
+    return launch("rm_fan_kernel",
+                  L.crash ? (L.aux ? rm_fan_kernel<true, true> : rm_fan_kernel<false, true>)
+                          : (L.aux ? rm_fan_kernel<true, false> : rm_fan_kernel<false, false>),
+                  L.grid, L.block, L.lds, L.stream, L.m->mp, L.f, L.d_poses, L.d_out, L.d_hits, L.d_steps, cp);
 }
 
 // RL_K_RM_STREAM_LIT, RL_K_RM_STREAM
@@ -1118,12 +1102,8 @@ static int launch_rm_stream_family(const FanLaunch &L)
         const int lw = h->handoff_wg / 64;                              // leftover waves per workgroup
         const int n_lw = (n_src + (64 >> cap_log2) - 1) / (64 >> cap_log2);
         const dim3 lgrid((unsigned)((n_lw + lw - 1) / lw)), lblock((unsigned)h->handoff_wg);
-        if (L.crash)
-            hipLaunchKernelGGL((rm_leftover_kernel<true>), lgrid, lblock, 0, L.stream, pm, L.f, (const LeftoverRec *)sp.left_rec,
-                               (const uint32_t *)sp.left_cnt, n_src, cap_log2, h->drain_stretch, sp.plain_store, L.d_out, cp);
-        else
-            hipLaunchKernelGGL((rm_leftover_kernel<false>), lgrid, lblock, 0, L.stream, pm, L.f, (const LeftoverRec *)sp.left_rec,
-                               (const uint32_t *)sp.left_cnt, n_src, cap_log2, h->drain_stretch, sp.plain_store, L.d_out, cp);
+        return launch("rm_leftover_kernel", L.crash ? rm_leftover_kernel<true> : rm_leftover_kernel<false>, lgrid, lblock, 0,
+                      L.stream, pm, L.f, sp.left_rec, sp.left_cnt, n_src, cap_log2, h->drain_stretch, sp.plain_store, L.d_out, cp);
     }
     return RL_OK;
 }
@@ -1232,7 +1212,6 @@ int launch_fan(rl_method *h, const FanCall &c)
         return fail(RL_ERR_INVALID, "launch plan names no kernel");
     }
     if (rc) return rc;
-    HIPCHK(hipGetLastError());
     if (c.timing) { HIPCHK(hipEventRecord(h->ev1, stream)); h->timed = true; }
     return RL_OK;
 }
@@ -1251,31 +1230,26 @@ static int launch_rays(rl_method *h, const float *d_ins, long n, float *d_out, i
     int rc;
     if (h->kind == RL_GIANT_LUT) {
         if ((rc = ensure_lut(h, stream))) return rc;
-        hipLaunchKernelGGL(h->lut_refine ? lut_rays_refine_kernel : lut_rays_kernel, dim3(grid), dim3(256), 0, stream, m->mp, f,
-                           h->lut.lp, d_ins, n, d_out);
+        rc = launch(h->lut_refine ? "lut_rays_refine_kernel" : "lut_rays_kernel",
+                    h->lut_refine ? lut_rays_refine_kernel : lut_rays_kernel, dim3(grid), dim3(256), 0, stream, m->mp, f, h->lut.lp,
+                    d_ins, n, d_out);
     } else if (h->kind == RL_CDDT) {
         if ((rc = ensure_cddt(h, stream))) return rc;
-        hipLaunchKernelGGL(cddt_rays_kernel, dim3(grid), dim3(256), 0, stream, m->mp, f, h->cddt.cdp,
-                           d_ins, n, d_out);
+        rc = launch("cddt_rays_kernel", cddt_rays_kernel, dim3(grid), dim3(256), 0, stream, m->mp, f, h->cddt.cdp, d_ins, n, d_out);
     } else if (h->kind == RL_BRESENHAM) {
-        hipLaunchKernelGGL(bl_rays_kernel, dim3(grid), dim3(256), 0, stream, m->mp, f, d_ins, n,
-                           d_out);
+        rc = launch("bl_rays_kernel", bl_rays_kernel, dim3(grid), dim3(256), 0, stream, m->mp, f, d_ins, n, d_out);
     } else if (h->opt.variant == 3) {
         // audit mode: the upstream 2-argument form stated literally, one lane per row
-        const LiteralParams lt = make_literal(m);
-        if (d_hits || d_steps)
-            hipLaunchKernelGGL((rm_literal_kernel<true, true>), dim3(grid), dim3(256), 0, stream, m->mp, f, lt, d_ins, n, d_out, d_hits, d_steps);
-        else
-            hipLaunchKernelGGL((rm_literal_kernel<false, true>), dim3(grid), dim3(256), 0, stream, m->mp, f, lt, d_ins, n, d_out, d_hits, d_steps);
+        rc = launch("rm_literal_kernel", (d_hits || d_steps) ? rm_literal_kernel<true, true> : rm_literal_kernel<false, true>,
+                    dim3(grid), dim3(256), 0, stream, m->mp, f, make_literal(m), d_ins, n, d_out, d_hits, d_steps);
     } else if (h->opt.variant >= 1 && n <= INT_MAX) {
         // a ray is a pose with one beam at alpha = 0: fan(num_rays = 1, fov = 0) gives exactly
         // (cos, sin) of the heading as direction, and the stream kernel packs 64 rays per block
         return launch_fan(h, FanCall{a, d_ins, (int)n, 0.0f, 1, d_out, d_hits, d_steps, nullptr, stream});
     } else {
-        hipLaunchKernelGGL(rm_rays_kernel, dim3(grid), dim3(WG), 0, stream, m->mp, f, d_ins, n,
-                           d_out, d_hits, d_steps);
+        rc = launch("rm_rays_kernel", rm_rays_kernel, dim3(grid), dim3(WG), 0, stream, m->mp, f, d_ins, n, d_out, d_hits, d_steps);
     }
-    HIPCHK(hipGetLastError());
+    if (rc) return rc;
     if (a.timing) { HIPCHK(hipEventRecord(h->ev1, stream)); h->timed = true; }
     return RL_OK;
 }
@@ -1464,7 +1438,7 @@ int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_r
         cp.thresh = crash_thresh;
         if (crash_direct) {
             // one roll-out: atomicMin straight into the result word (few poses, little contention)
-            hipLaunchKernelGGL(fill_int_kernel, dim3(1), dim3(64), 0, h->stream, (int *)h->flag, 1, INT_MAX);
+            if ((rc = launch("fill_int_kernel", fill_int_kernel, dim3(1), dim3(64), 0, h->stream, h->flag, 1, INT_MAX))) return rc;
             cp.first_crashed = h->flag;
             cp.group = n_poses;
         } else {
@@ -1519,9 +1493,9 @@ int fan_host(rl_method *h, const float *poses, int n_poses, float fov, int num_r
                 (rc = hc.down(steps, h->steps, n_rays))))
         return rc;
     if (first_crashed) {
-        if (!crash_direct)
-            hipLaunchKernelGGL(crash_reduce_kernel, dim3(1), dim3(64), 0, h->stream,
-                               (const int *)cp.first_crashed, cp.mark, 1, n_poses, (int *)h->flag);
+        if (!crash_direct && (rc = launch("crash_reduce_kernel", crash_reduce_kernel, dim3(1), dim3(64), 0, h->stream,
+                                          cp.first_crashed, cp.mark, 1, n_poses, h->flag)))
+            return rc;
         HIPCHK(hipMemcpyAsync(h->pin_flag, h->flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     }
     if ((rc = hc.finish())) return rc;
@@ -1601,8 +1575,6 @@ static PfParams make_pf(const rl_method *h, int n_particles, int n_angles)
     return PfParams{n_particles, n_angles, block, h->sensor, h->sensor_w, (float)(h->sensor_w - 1)};
 }
 
-#define PF_ANGLES(K, A) hipLaunchKernelGGL((pf_angles_kernel<K, A>), dim3(grid), dim3(PF_WG), 0, stream, m->mp, f, lt, h->cddt.cdp, \
-                                           h->lut.lp, d_poses, d_angles, n, d_out, d_hits, d_steps)
 static int launch_pf_angles(rl_method *h, const LaunchArgs &a, int kind, const float *d_poses, int n_particles, const float *d_angles,
                             int n_angles, float *d_out, int32_t *d_hits, uint16_t *d_steps, hipStream_t stream)
 {
@@ -1617,27 +1589,27 @@ static int launch_pf_angles(rl_method *h, const LaunchArgs &a, int kind, const f
     const LiteralParams lt = make_literal(m);
     const long n = (long)n_particles * n_angles;
     const int grid = (int)std::max(1L, std::min((n + PF_WG - 1) / PF_WG, (long)m->n_cu * 16));
+    decltype(&pf_angles_kernel<PF_RM, true>) kernel;
     switch (kind) {
     case PF_RM:
-        if (aux) PF_ANGLES(PF_RM, true); else PF_ANGLES(PF_RM, false);
+        kernel = aux ? pf_angles_kernel<PF_RM, true> : pf_angles_kernel<PF_RM, false>;
         break;
     case PF_RM_LITERAL:
-        if (aux) PF_ANGLES(PF_RM_LITERAL, true); else PF_ANGLES(PF_RM_LITERAL, false);
+        kernel = aux ? pf_angles_kernel<PF_RM_LITERAL, true> : pf_angles_kernel<PF_RM_LITERAL, false>;
         break;
     case PF_CDDT:
-        PF_ANGLES(PF_CDDT, false);
+        kernel = pf_angles_kernel<PF_CDDT, false>;
         break;
     case PF_LUT_REFINE:
-        PF_ANGLES(PF_LUT_REFINE, false);
+        kernel = pf_angles_kernel<PF_LUT_REFINE, false>;
         break;
     default:
-        PF_ANGLES(PF_LUT, false);
+        kernel = pf_angles_kernel<PF_LUT, false>;
         break;
     }
-    HIPCHK(hipGetLastError());
-    return RL_OK;
+    return launch("pf_angles_kernel", kernel, dim3(grid), dim3(PF_WG), 0, stream, m->mp, f, lt, h->cddt.cdp, h->lut.lp, d_poses,
+                  d_angles, n, d_out, d_hits, d_steps);
 }
-#undef PF_ANGLES
 
 static int launch_pf_eval(rl_method *h, const float *d_obs, const float *d_ranges, int n_angles, int n_particles,
                           double *d_weights, hipStream_t stream)
@@ -1645,10 +1617,8 @@ static int launch_pf_eval(rl_method *h, const float *d_obs, const float *d_range
     const PfParams pp = make_pf(h, n_particles, n_angles);
     const int tiles = (n_particles + pp.block - 1) / pp.block;
     const int grid = std::max(1, std::min(tiles, h->map->n_cu * 8));
-    hipLaunchKernelGGL(pf_eval_kernel, dim3(grid), dim3(PF_WG), pf_lds_bytes(pp.block, n_angles), stream, h->map->mp, pp,
-                       d_obs, d_ranges, d_weights);
-    HIPCHK(hipGetLastError());
-    return RL_OK;
+    return launch("pf_eval_kernel", pf_eval_kernel, dim3(grid), dim3(PF_WG), pf_lds_bytes(pp.block, n_angles), stream, h->map->mp,
+                  pp, d_obs, d_ranges, d_weights);
 }
 
 // the fused call.  RM / RMGPU: pf_weight_kernel, nothing but the weights leaves the kernel.  CDDT / GiantLUT:
@@ -1672,12 +1642,8 @@ static int launch_pf_weights(rl_method *h, const LaunchArgs &a, int kind, const 
     const int tiles = (n_particles + pp.block - 1) / pp.block;
     const dim3 grid(std::max(1, std::min(tiles, m->n_cu * 8)));
     const size_t lds = pf_lds_bytes(pp.block, n_angles);
-    if (kind == PF_RM_LITERAL)
-        hipLaunchKernelGGL((pf_weight_kernel<true>), grid, dim3(PF_WG), lds, stream, m->mp, f, lt, pp, d_poses, d_angles, d_obs, d_weights);
-    else
-        hipLaunchKernelGGL((pf_weight_kernel<false>), grid, dim3(PF_WG), lds, stream, m->mp, f, lt, pp, d_poses, d_angles, d_obs, d_weights);
-    HIPCHK(hipGetLastError());
-    return RL_OK;
+    return launch("pf_weight_kernel", kind == PF_RM_LITERAL ? pf_weight_kernel<true> : pf_weight_kernel<false>, grid, dim3(PF_WG),
+                  lds, stream, m->mp, f, lt, pp, d_poses, d_angles, d_obs, d_weights);
 }
 
 extern "C" int rl_set_sensor_model(rl_method *h, const double *table, int width)
@@ -1900,19 +1866,19 @@ static int launch_mcl_step(rl_pf *f, const LaunchArgs &a, int kind, const MclPar
     const uint32_t t = (uint32_t)(f->t + k);
     const int grid = (f->P + MCL_WG - 1) / MCL_WG;
     double *tot = f->tot, *tot6 = tot + f->NB;
-    hipLaunchKernelGGL(mcl_motion_kernel, dim3(grid), dim3(MCL_WG), 0, s, mp, f->odom + 3 * (size_t)k, t, f->cur, f->prop, f->q);
-    int rc = launch_pf_weights(h, a, kind, f->q, f->P, f->ang, f->obs + (size_t)k * f->A, f->A, f->lik, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(mcl_weight_kernel, dim3((f->NB + MCL_GROUP - 1) / MCL_GROUP), dim3(MCL_WG), 0, s, mp, f->w, f->lik,
-                       f->omega, tot);
-    hipLaunchKernelGGL(mcl_norm_kernel, dim3((f->NB + MCL_NGROUP - 1) / MCL_NGROUP), dim3(MCL_WG), 0, s, mp, tot, f->omega,
-                       f->prop, f->w, f->part, tot6, f->scal);
-    hipLaunchKernelGGL(mcl_base_kernel, dim3(1), dim3(64 * MCL_SUMS), 0, s, mp, tot6, f->scal, f->base, f->est + 4 * (size_t)k,
-                       f->neff + k, f->flags + k);
-    hipLaunchKernelGGL(mcl_resample_kernel, dim3(grid), dim3(MCL_WG), 0, s, mp, t, f->flags + k, f->base, f->part, f->prop,
-                       f->cur, f->w, f->anc, f->cum);
-    HIPCHK(hipGetLastError());
-    return RL_OK;
+    int rc;
+    if ((rc = launch("mcl_motion_kernel", mcl_motion_kernel, dim3(grid), dim3(MCL_WG), 0, s, mp, f->odom + 3 * (size_t)k, t, f->cur,
+                     f->prop, f->q)) ||
+        (rc = launch_pf_weights(h, a, kind, f->q, f->P, f->ang, f->obs + (size_t)k * f->A, f->A, f->lik, s)) ||
+        (rc = launch("mcl_weight_kernel", mcl_weight_kernel, dim3((f->NB + MCL_GROUP - 1) / MCL_GROUP), dim3(MCL_WG), 0, s, mp, f->w,
+                     f->lik, f->omega, tot)) ||
+        (rc = launch("mcl_norm_kernel", mcl_norm_kernel, dim3((f->NB + MCL_NGROUP - 1) / MCL_NGROUP), dim3(MCL_WG), 0, s, mp, tot,
+                     f->omega, f->prop, f->w, f->part, tot6, f->scal)) ||
+        (rc = launch("mcl_base_kernel", mcl_base_kernel, dim3(1), dim3(64 * MCL_SUMS), 0, s, mp, tot6, f->scal, f->base,
+                     f->est + 4 * (size_t)k, f->neff + k, f->flags + k)))
+        return rc;
+    return launch("mcl_resample_kernel", mcl_resample_kernel, dim3(grid), dim3(MCL_WG), 0, s, mp, t, f->flags + k, f->base, f->part,
+                  f->prop, f->cur, f->w, f->anc, f->cum);
 }
 
 extern "C" int rl_pf_run(rl_pf *f, int n_steps, const double *odom_t3, const float *obs_tA, double *est_t4, double *neff_t,
@@ -2027,16 +1993,13 @@ int crash_groups_device(rl_method *h, const LaunchArgs &a, const float *d_poses,
     if (!fused && !d_ranges) return fail(RL_ERR_INVALID, "this range method needs a ranges buffer for the crash test");
     if ((rc = launch_fan(h, FanCall{a, d_poses, n_poses, fov, num_rays, d_ranges, nullptr, nullptr, fused ? &cp : nullptr, stream})))
         return rc;
-    if (!fused) {
-        const int grid = (int)std::max(1L, std::min(((long)n_poses + 3) / 4, (long)h->map->n_cu * 8));
-        hipLaunchKernelGGL(crash_groups_kernel, dim3(grid), dim3(256), 0, stream, d_ranges, d_edge,
-                           thresh, n_poses, num_rays, 0, mark, d_pose_first);
-    }
+    const int grid = (int)std::max(1L, std::min(((long)n_poses + 3) / 4, (long)h->map->n_cu * 8));
+    if (!fused && (rc = launch("crash_groups_kernel", crash_groups_kernel, dim3(grid), dim3(256), 0, stream, d_ranges, d_edge, thresh,
+                               n_poses, num_rays, 0, mark, d_pose_first)))
+        return rc;
     const int rgrid = (int)std::max(1L, std::min(((long)n_groups + 3) / 4, (long)h->map->n_cu * 8));
-    hipLaunchKernelGGL(crash_reduce_kernel, dim3(rgrid), dim3(256), 0, stream, d_pose_first, mark,
-                       n_groups, group, d_first);
-    HIPCHK(hipGetLastError());
-    return RL_OK;
+    return launch("crash_reduce_kernel", crash_reduce_kernel, dim3(rgrid), dim3(256), 0, stream, d_pose_first, mark, n_groups, group,
+                  d_first);
 }
 
 extern "C" int rl_check_collision_groups_device(rl_method *h, const float *d_poses, int n_groups,

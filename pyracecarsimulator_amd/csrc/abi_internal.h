@@ -1,6 +1,7 @@
 // abi_internal.h — what the translation units of libscan_amd.so share: the owners of every device resource (DevBuf,
 // DevPtr, Pinned, Stream, Event), HostCall (one synchronous host-pointer call: staging up, results down, the wait, and
-// the drain of a call that is refused on the way), the derived tables of a method (StepMap, LutTable, CddtTable,
+// the drain of a call that is refused on the way), launch (THE kernel launch of every unit: typed by the kernel's own
+// parameter list, asked at once, reported by name), the derived tables of a method (StepMap, LutTable, CddtTable,
 // BlPadMaps, FanTabs: one struct each, owning its buffers, parameter block and cache) with their one cache protocol
 // (TableCache), the handles behind include/scanlib.h's opaque pointers (rl_method: options, streams, staging, launch
 // contexts and the five tables), the error slot, and the few internal entry points one unit calls in another.
@@ -239,6 +240,20 @@ struct HostCall {
         return RL_OK;
     }
 };
+
+// THE kernel launch of the library: `kernel` over grid x block with lds bytes on st, asked at once.  The kernel's own parameter
+// list is what the arguments are converted to — a DevPtr<T> goes where T * or const T * is taken, nullptr where any
+// pointer is, an int where a size_t is —, so a site writes no casts and an array of the wrong element type does not
+// compile.  A launch the runtime refuses answers RL_ERR_HIP with `name` (the kernel's; the family's for a table entry) and
+// HIP's reason; the caller enqueues nothing behind it.
+template <class... P, class... A>
+int launch(const char *name, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A &&...a)
+{
+    static_assert(sizeof...(P) == sizeof...(A), "one argument per kernel parameter");
+    kernel<<<grid, block, lds, st>>>(static_cast<P>(std::forward<A>(a))...);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? (int)RL_OK : fail(RL_ERR_HIP, "%s launch failed: %s", name, hipGetErrorString(e));
+}
 
 // ------------------------------------------------------------------------------
 // handles

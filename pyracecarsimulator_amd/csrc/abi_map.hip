@@ -158,12 +158,14 @@ int map_build_tables(rl_map *m)
 {
     // K0: exact EDT + bit-packed occupancy, all on the device
     const int rows = m->rows, cols = m->cols;
-    hipLaunchKernelGGL(edt_cols_kernel, dim3((cols + 63) / 64), dim3(1024), 0, m->stream,
-                       m->d_occ, rows, cols, m->d_g);
-    hipLaunchKernelGGL(edt_rows_kernel, dim3(rows), dim3(256), (size_t)cols * sizeof(int),
-                       m->stream, m->d_g, rows, cols, m->d_dt);
-    hipLaunchKernelGGL(pack_bits_kernel, dim3((m->bits_stride + 255) / 256, rows), dim3(256), 0,
-                       m->stream, m->d_occ, rows, cols, m->bits_stride, m->d_bits);
+    int rc;
+    if ((rc = launch("edt_cols_kernel", edt_cols_kernel, dim3((cols + 63) / 64), dim3(1024), 0, m->stream, m->d_occ, rows, cols,
+                     m->d_g)) ||
+        (rc = launch("edt_rows_kernel", edt_rows_kernel, dim3(rows), dim3(256), (size_t)cols * sizeof(int), m->stream, m->d_g,
+                     rows, cols, m->d_dt)) ||
+        (rc = launch("pack_bits_kernel", pack_bits_kernel, dim3((m->bits_stride + 255) / 256, rows), dim3(256), 0, m->stream,
+                     m->d_occ, rows, cols, m->bits_stride, m->d_bits)))
+        return rc;
     if (m->want_edges) {
         if (!m->pin_n_edges) {                       // (the last of the three: a failure before it starts over)
             if (m->d_edges.alloc((size_t)rows * cols * sizeof(uint32_t)) || m->d_n_edges.alloc(256))
@@ -171,12 +173,12 @@ int map_build_tables(rl_map *m)
             HIPCHK(m->pin_n_edges.alloc(64));
         }
         HIPCHK(hipMemsetAsync(m->d_n_edges, 0, 4, m->stream));
-        hipLaunchKernelGGL(cddt_edges_kernel, dim3((cols + 255) / 256, (rows + EDGE_ROWS_PER_WG - 1) / EDGE_ROWS_PER_WG),
-                           dim3(256), 0, m->stream,
-                           m->d_occ, rows, cols, m->d_n_edges, m->d_edges);
+        if ((rc = launch("cddt_edges_kernel", cddt_edges_kernel,
+                         dim3((cols + 255) / 256, (rows + EDGE_ROWS_PER_WG - 1) / EDGE_ROWS_PER_WG), dim3(256), 0, m->stream,
+                         m->d_occ, rows, cols, m->d_n_edges, m->d_edges)))
+            return rc;
         HIPCHK(hipMemcpyAsync(m->pin_n_edges, m->d_n_edges, 4, hipMemcpyDeviceToHost, m->stream));
     }
-    HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(m->stream));
     if (m->want_edges) m->n_edges = *m->pin_n_edges;
     return RL_OK;
@@ -368,9 +370,10 @@ extern "C" int rl_map_stamp_cells(rl_map *m, const int32_t *flat_idx, int n, uin
     // the indices land in pinned memory the kernel reads directly; ONE launch puts the previous outline's cells back
     // and sets the new ones (the stream was synchronised above: the pinned buffer is not in use)
     if (n > 0) memcpy(m->pin_stamp, flat_idx, (size_t)n * sizeof(int32_t));
-    if (n > 0 || m->n_stamped > 0)
-        hipLaunchKernelGGL(stamp_swap_kernel, dim3(1), dim3(1024), 0, m->stream, m->d_occ, (const uint8_t *)m->d_occ_base, cells,
-                           m->d_stamp, m->n_stamped, (const int32_t *)m->pin_stamp, n, value);
+    if ((n > 0 || m->n_stamped > 0) &&
+        (rc = launch("stamp_swap_kernel", stamp_swap_kernel, dim3(1), dim3(1024), 0, m->stream, m->d_occ, m->d_occ_base, cells,
+                     m->d_stamp, m->n_stamped, m->pin_stamp, n, value)))
+        return rc;
     m->n_stamped = n;
     rc = map_build_tables(m);
     if (rc) return rc;

@@ -495,6 +495,11 @@ def test_housekeeping_gates():
     hdr = open(os.path.join(csrc, "abi_internal.h")).read()
     for call in ("hipFree(", "hipHostFree(", "hipEventDestroy(", "hipStreamDestroy(", "hipMalloc(", "hipHostMalloc("):
         assert call in hdr, call
+    # every kernel launch goes through abi_internal.h's launch(): no unit launches by hand, the header does so once
+    for u, t in text.items():
+        for form in ("hipLaunchKernelGGL(", "<<<"):
+            assert form not in t, (u, form)
+    assert hdr.count("<<<") == 1
 
 
 def test_kernel_register_budgets_are_a_build_gate(tmp_path):

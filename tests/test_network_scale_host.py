@@ -33,7 +33,7 @@ def _const(text, name):
 # ---------------------------------------------------------------- the launch geometry the shapes are there for
 def test_pack_case_crosses_the_grid_cap_of_the_launch():
     abi = _src("abi_car.hip")
-    m = re.search(r"std::min<size_t>\(\(total \+ (\d+)\) / (\d+), (\d+)\);\s*hipLaunchKernelGGL\(policy_pop_pack_kernel, "
+    m = re.search(r"std::min<size_t>\(\(total \+ (\d+)\) / (\d+), (\d+)\);\s*return launch\(\"policy_pop_pack_kernel\", policy_pop_pack_kernel, "
                   r"dim3\(grid\), dim3\((\d+)\)", abi)
     assert m, "pop_pack_launch no longer reads as the case assumes"
     assert int(m.group(1)) + 1 == int(m.group(2)) == int(m.group(4)) == NS.PACK_THREADS
