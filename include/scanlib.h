@@ -368,8 +368,45 @@ int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, const doubl
  *     which would put its lidar inside an obstacle;
  *   - getBound's defects are not reproduced: bound[i] / bound[i+1] overwrite each other, the points are not
  *     translated to the car's position, and floatPosToPix adds +width / +height;
- *   - races run on ray marching only (RM, RMGPU);
+ *   - races run on ray marching (RM, RMGPU) and, with option race_cddt, on CDDT (below); not on the other tables;
  *   - a crashed car stays in the map as a wreck at its crash-tick state.
+ *
+ * Races on CDDT (option race_cddt; the kernel is cddt_kernels.h race_cddt_kernel, the host statement
+ * tests/race_cddt_statement.py).  rl_method_set_option(h, "race_cddt", v) — 0 = off, the default; any other value
+ * stores 1; readable through rl_method_get_info; a handle's own option, not part of rl_plan_opts; it goes to every
+ * replica of a multi-device handle; kinds other than RL_CDDT store and ignore it.  With 0 an RL_CDDT handle is refused
+ * by every race entry point, as before.  With 1 the race scan of an RL_CDDT handle is the following, and every call
+ * built on the race scan (rl_car_race_followgap, _seats, _league, the race environment with seats, league line-ups
+ * and a track, the track-progress roll-outs) takes it; ticks, noise offsets, crash ballot, wrecks, traces and
+ * chunking stay as they are.
+ *   Car i of a race scans against S_i, the set of outline cells of the OTHER cars of its race (rl_car_outline_cells'
+ *   set, taken from the f64 states or cars_p3 exactly as the ray-marching race scan takes it).  For table bin t, with
+ *   cs, sn, trans, width the static table's values of that bin, a cell (r, c) of S_i behaves as the table build
+ *   treats an edge cell:
+ *     px = (float)c + 0.5f, py = (float)r + 0.5f;
+ *     slx = fma(px, cs, -(py sn)), sly = fma(px, sn, py cs) + trans;  half = (|sn| + |cs|) 0.5f;
+ *     upper = (int)((sly + half) - 1e-5f), lower = (int)((sly - half) + 1e-5f), clamped to [0, width - 1];
+ *     the cell covers bucket b iff lower <= b <= upper.
+ *   A ray's bin is the CDDT query's, unchanged: the nearest bin of -heading, flipped by theta_disc / 2 into the
+ *   table's half turn (with the guard for odd theta_disc); lx, ly its origin's projection, and max_range at once when
+ *   ly lies outside [0, width).  With b = (int)ly let F be the static bucket's values plus slx of every cell of S_i
+ *   that covers b.  Forward: x* = min{x in F : x >= lx}, range_px = fminf(x* - lx, max_range); flipped:
+ *   x* = max{x in F : x <= lx}, range_px = fminf(lx - x*, max_range); max_range when no such x exists.  Then times
+ *   res, plus the handle's noise keyed by the global ray id as in the ray-marching race scan.  A group of 1 equals
+ *   rl_calc_range_fan of the same poses bit for bit.  No per-race table is built: the static bucket is searched once
+ *   per (car, table bin) and the others' cells are folded into its two extrema.
+ *   Relation to "stamp, rebuild, scan" — a deliberate divergence.  The statement equals stamping S_i
+ *   (rl_map_stamp_cells), rebuilding the table and scanning, bit for bit, when both hold:
+ *     (i)  every cell of S_i is an edge cell of grid u S_i (OMap::make_edge_map's 4-neighbour rule: occupied, and on
+ *          the border or with a free 4-neighbour);
+ *     (ii) every static edge cell is still an edge cell of grid u S_i.
+ *   Where they fail — a car overlapping a wall, a wreck flush against a wall, two interlocking outlines — the
+ *   rebuild drops entries the statement keeps.  On a 96-cell maze 352 of 400 line-ups with the others at least 7
+ *   cells off the walls meet both and no ray differs; with the others thrown anywhere, walls included, 8 of 58 200
+ *   rays differ, 0.014 % (docs/history/race_cddt.md; tests/test_race_cddt_host.py measures both).
+ *   Refused with RL_ERR_UNSUPPORTED: RL_GIANT_LUT and RL_BRESENHAM whatever the option says; hit cells or step counts
+ *   from an RL_CDDT handle, as the plain fan refuses them for the table kinds; group x theta_disc > 8192 (the kernel
+ *   keeps that many per-bin ranges, 32 KiB, in LDS next to the outlines' 16 KiB).  Multi-device handles: RL_ERR_INVALID.
  *
  * rl_car_outline_cells: n cars (x, y, theta rows in double) on m with c's LENGTH / WIDTH -> per car its cells
  * row * cols + col (points whose cell repeats the point before dropped), counts[i] of them, -1 past the count in a row
@@ -386,8 +423,9 @@ int rl_car_drive_followgap(rl_car *c, rl_method *h, rl_followgap *g, const doubl
  * do not apply and are ignored.  A group of 1 equals rl_calc_range_fan of the same poses bit for bit.
  * Errors (the handle stays usable): RL_ERR_INVALID for null pointers, group outside [1, 8], num_rays outside
  * [10, 1280], n_groups group num_rays >= 2^31, multi-device handles, a non-positive length or width;
- * RL_ERR_UNSUPPORTED for RL_CDDT, RL_GIANT_LUT and RL_BRESENHAM (their tables cover the whole map: the single-race
- * two_player.ScanSimulator2D with a stamp stays their path), variant 2, and outlines of more than 512 points.
+ * RL_ERR_UNSUPPORTED for RL_CDDT (unless option race_cddt is set: "Races on CDDT" above), RL_GIANT_LUT and RL_BRESENHAM
+ * (their tables cover the whole map: the single-race two_player.ScanSimulator2D with a stamp stays their path),
+ * variant 2, and outlines of more than 512 points.
  *
  * rl_car_race_followgap: rl_car_drive_followgap's loop (same arguments with n_rollouts = n_races group, same outputs,
  * traces, NaN rows, noise offsets per tick, chunking and option restore) in which every tick's scan is the race scan
@@ -946,6 +984,8 @@ int rl_last_kernel_ms(rl_method *h, float *ms_out);
  *              handle option, not part of rl_plan_opts: the plan — kernel name, grid, LDS — stays the default's and the
  *              launch takes the planned instance's refined twin; the LDS twin runs the planned waves in workgroups of
  *              512 lanes.  Stored and ignored by the other kinds)
+ *   CDDT       race_cddt (0, the default | 1: batched races on the table, "Races on CDDT" above; a handle option, not
+ *              part of rl_plan_opts.  Stored and ignored by the other kinds)
  *   multi-device handles: every option goes to every device's replica; multi_min_poses (poses per device
  *              from which another device is brought in, default 512) belongs to the handle itself.
  * rl_method_get_info additionally answers n_devices, n_cu, clock_khz, last_grid, map_epoch, code_entries (palette entries of

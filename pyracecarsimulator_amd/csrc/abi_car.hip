@@ -371,6 +371,13 @@ static int race_args(rl_method *h, long n_groups, int group, int num_rays)
     if (num_rays < 10 || num_rays > RACE_MAX_RAYS)
         return fail(RL_ERR_INVALID, "num_rays must lie in [10, %d] (got %d)", RACE_MAX_RAYS, num_rays);
     if (n_groups * group * num_rays >= (1L << 31)) return fail(RL_ERR_INVALID, "n_groups * group * num_rays must stay below 2^31");
+    if (h->kind == RL_CDDT && h->race_cddt) {
+        // race_cddt_kernel's per-bin ranges: group x theta_disc floats of LDS
+        if ((long)group * h->theta_disc > RACE_CDDT_MAX_BINS)
+            return fail(RL_ERR_UNSUPPORTED, "a CDDT race keeps group x theta_disc per-bin ranges in LDS: at most %d (got %d x %d)",
+                        RACE_CDDT_MAX_BINS, group, h->theta_disc);
+        return RL_OK;
+    }
     if (h->kind != RL_RM && h->kind != RL_RM_GPU)
         return fail(RL_ERR_UNSUPPORTED, "races run on ray marching only (RM, RMGPU): a CDDT, GiantLUT or Bresenham table "
                                         "covers the whole map and cannot see the other cars");
@@ -394,6 +401,10 @@ static int launch_race(rl_method *h, const LaunchArgs &a, const float *d_poses, 
     const FanParams f = make_fan(h, n_groups * group, fov, num_rays, a.ray_offset);
     const LiteralParams lp = lit ? make_literal(h->map) : LiteralParams{};
     const RaceParams rp{o, d_cars, car_stride, group, n_groups};
+    if (h->kind == RL_CDDT) {                    // (option race_cddt: race_args let the handle through)
+        if (aux) return fail(RL_ERR_UNSUPPORTED, "hit cells / step counts exist only for RM and Bresenham");
+        return launch_race_cddt(h, a, f, rp, d_poses, d_out, stream);
+    }
     if (a.timing) HIPCHK(hipEventRecord(h->ev0, stream));
     const int rc = launch("race_fan_kernel", race_table[lit][aux], dim3(n_groups), dim3(RACE_WG), 0, stream, h->map->mp, f, lp, rp,
                           d_poses, d_out, d_hits, d_steps);
@@ -406,10 +417,11 @@ static int launch_race(rl_method *h, const LaunchArgs &a, const float *d_poses, 
 }
 
 static int fan_cars_checks(rl_method *h, int n_groups, int group, float fov, int num_rays, double length, double width,
-                           OutlineParams &o)
+                           bool aux, OutlineParams &o)
 {
     int rc = race_args(h, n_groups, group, num_rays);
     if (rc) return rc;
+    if (aux && h->kind == RL_CDDT) return fail(RL_ERR_UNSUPPORTED, "hit cells / step counts exist only for RM and Bresenham");
     if ((rc = check_fan_args(h, n_groups * group, fov, num_rays))) return rc;
     return race_outline(h->map, length, width, o);
 }
@@ -421,7 +433,7 @@ extern "C" int rl_calc_range_fan_cars_device(rl_method *h, const float *d_poses,
     if (!h || (n_groups > 0 && (!d_poses || !d_cars || !d_outs)))
         return fail(RL_ERR_INVALID, "rl_calc_range_fan_cars_device: null pointer");
     OutlineParams o{};
-    int rc = fan_cars_checks(h, n_groups, group, fov, num_rays, length, width, o);
+    int rc = fan_cars_checks(h, n_groups, group, fov, num_rays, length, width, d_hits || d_steps, o);
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(h->mu);
     std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);
@@ -436,7 +448,7 @@ extern "C" int rl_calc_range_fan_cars(rl_method *h, const float *poses, const do
 {
     if (!h || (n_groups > 0 && (!poses || !cars || !outs))) return fail(RL_ERR_INVALID, "rl_calc_range_fan_cars: null pointer");
     OutlineParams o{};
-    int rc = fan_cars_checks(h, n_groups, group, fov, num_rays, length, width, o);
+    int rc = fan_cars_checks(h, n_groups, group, fov, num_rays, length, width, hits_or_null || steps_or_null, o);
     if (rc || n_groups == 0) return rc;
     std::lock_guard<std::mutex> lk(h->mu);
     std::shared_lock<std::shared_mutex> ml(h->map->tables_mu);

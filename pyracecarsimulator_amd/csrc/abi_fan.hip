@@ -192,6 +192,8 @@ static const OptionRow OPTIONS[] = {
     {"pf_block", OWN(pf_block), [](int v) { return clamp_int(v, 0, PF_WG); }},
     // (the origin-corrected GiantLUT query; stored and ignored by the other kinds, as lut_debug is)
     {"lut_refine", OWN(lut_refine), as_bool},
+    // (batched races on the CDDT table, race_args in abi_car.hip; stored and ignored by the other kinds)
+    {"race_cddt", OWN(race_cddt), as_bool},
     // (a power of two in [128, CDDT_LDS_SORT]: the bitonic network pads to one)
     {"cddt_lds_sort", OWN(cddt.lds_sort), [](int v) {
          int p = 128;
@@ -957,6 +959,24 @@ static int launch_cddt_rays(const FanLaunch &L)
     if (L.timing == 2) HIPCHK(hipEventRecord(L.h->ev0, L.stream));
     return launch("cddt_fan_kernel", cddt_fan_kernel, L.grid, L.block, 0, L.stream, L.m->mp, L.f, L.h->cddt.cdp, L.d_poses,
                   L.d_out);
+}
+
+// the race scan of a CDDT handle (option race_cddt; launch_race in abi_car.hip checked the shape): one workgroup per race
+int launch_race_cddt(rl_method *h, const LaunchArgs &a, const FanParams &f, const RaceParams &rp, const float *d_poses,
+                     float *d_out, hipStream_t stream)
+{
+    int rc;
+    if ((rc = ensure_cddt(h, stream))) return rc;
+    if (a.timing) HIPCHK(hipEventRecord(h->ev0, stream));
+    const size_t lds = (size_t)rp.group * h->cddt.cdp.theta_disc * sizeof(float);
+    if ((rc = launch("race_cddt_kernel", race_cddt_kernel, dim3(rp.n_groups), dim3(RACE_WG), lds, stream, h->map->mp, f,
+                     h->cddt.cdp, rp, d_poses, d_out)))
+        return rc;
+    if (a.timing) {
+        HIPCHK(hipEventRecord(h->ev1, stream));
+        h->timed = true;
+    }
+    return RL_OK;
 }
 
 // RL_K_BL_STREAM

@@ -627,6 +627,7 @@ struct rl_method {
     DevPtr<double> pf_w;
     int pf_block = 0;            // particles per tile of the weight kernels (0: sized from the shape, make_pf)
     int lut_refine = 0;          // GiantLUT: the origin-corrected query (lut_kernels.h) in every query path; other kinds ignore it
+    int race_cddt = 0;           // CDDT: batched races on the table (cddt_kernels.h race_cddt_kernel); other kinds ignore it
     LaunchCtx ctx[N_LAUNCH_CTX];
     uint64_t use_clock = 0;
     // small host calls (scan(): one pose, scanMany(): a roll-out): poses and ranges go through ONE
@@ -731,3 +732,7 @@ int upload_edge(rl_method *h, const double *edge, int num_rays);
 int rays_host(rl_method *h, const float *ins, float *outs, int n);
 int check_groups_args(int n_groups, int group);     // the grouped crash tests' first two checks
 int multi_parts(const rl_method *h, long n_poses);
+namespace scan { struct RaceParams; }
+// one race_cddt_kernel launch of a CDDT handle with option race_cddt (launch_race, abi_car.hip: same caller's duties)
+int launch_race_cddt(rl_method *h, const LaunchArgs &a, const FanParams &f, const RaceParams &rp, const float *d_poses,
+                     float *d_out, hipStream_t stream);

@@ -1,10 +1,12 @@
 // cddt_kernels.h — K3b: CDDTCast: device table build (blocked layout), the pose-major fan
-// kernel, the theta-major kernels for large batches, the per-ray kernels.  Part of scan_kernels.h.
+// kernel, the theta-major kernels for large batches, the per-ray kernels, the race kernel.  Part of scan_kernels.h.
 #pragma once
 #include "scan_device.h"
 #include "scan_params.h"
 #include "rm_kernels.h"
 #include "lut_kernels.h"
+#include "literal_kernels.h"     // fan_noise
+#include "outline_device.h"      // the race kernel's car outlines
 
 // ==============================================================================
 // K3b: CDDTCast (scripts/two_player/scan.py:46).
@@ -263,6 +265,60 @@ __global__ __launch_bounds__(256) void cddt_sort_kernel(const uint32_t *__restri
 // lx, the forward one — otherwise that is the next separator), then one pass of min / max over the leaf's 32
 // values.  No bisection, no sortedness needed inside a line; the padding (+inf) never wins.  out_f / out_b
 // are the two ranges in pixels (max_range when nothing is stored on that side).
+// The search itself, on a bucket of hd.y > 0 values: fwd = the first stored x >= lx (+inf: none), bwd = the last stored
+// x <= lx (-inf: none).  cddt_query_pair turns the two into ranges; race_cddt_kernel folds the other cars' cells in first.
+__device__ __forceinline__ void cddt_search_pair(const CddtParams &cp, const uint2 hd, float lx, float &fwd, float &bwd)
+{
+    const uint32_t n = hd.y;
+    const float INF = __builtin_inff();
+    const uint32_t nleaf = (n + 31u) >> 5;
+    const float4 *lines = reinterpret_cast<const float4 *>(cp.tab) + (size_t)hd.x * 8;
+    fwd = INF;
+    bwd = -INF;
+    uint32_t leaf = 0;
+    bool have_leaf = true;
+    if (nleaf > 1u) {
+        const uint32_t nsl = (nleaf + 31u) >> 5;
+        uint32_t L = 0;
+        if (nsl > 1u) {                        // > 1024 values: the separator line whose first value is the last <= lx
+            uint32_t a = 0, z = nsl;
+            while (z - a > 1u) {
+                const uint32_t mid = (a + z) >> 1;
+                if (lines[(size_t)mid * 8].x <= lx) a = mid; else z = mid;
+            }
+            L = a;
+            if (L + 1u < nsl) fwd = lines[(size_t)(L + 1u) * 8].x;      // (> lx: line z was probed)
+        }
+        uint32_t c = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float4 q = lines[(size_t)L * 8 + i];
+            c += (q.x <= lx ? 1u : 0u) + (q.y <= lx ? 1u : 0u) + (q.z <= lx ? 1u : 0u) + (q.w <= lx ? 1u : 0u);
+            fwd = __builtin_fminf(fwd, q.x > lx ? q.x : INF);
+            fwd = __builtin_fminf(fwd, q.y > lx ? q.y : INF);
+            fwd = __builtin_fminf(fwd, q.z > lx ? q.z : INF);
+            fwd = __builtin_fminf(fwd, q.w > lx ? q.w : INF);
+        }
+        have_leaf = L * 32u + c > 0u;
+        leaf = L * 32u + c - 1u;
+        lines += (size_t)nsl * 8;
+    }
+    if (have_leaf) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float4 q = lines[(size_t)leaf * 8 + i];
+            fwd = __builtin_fminf(fwd, q.x >= lx ? q.x : INF);
+            fwd = __builtin_fminf(fwd, q.y >= lx ? q.y : INF);
+            fwd = __builtin_fminf(fwd, q.z >= lx ? q.z : INF);
+            fwd = __builtin_fminf(fwd, q.w >= lx ? q.w : INF);
+            bwd = __builtin_fmaxf(bwd, q.x <= lx ? q.x : -INF);
+            bwd = __builtin_fmaxf(bwd, q.y <= lx ? q.y : -INF);
+            bwd = __builtin_fmaxf(bwd, q.z <= lx ? q.z : -INF);
+            bwd = __builtin_fmaxf(bwd, q.w <= lx ? q.w : -INF);
+        }
+    }
+}
+
 __device__ __forceinline__ void cddt_query_pair(const CddtParams &cp, float max_range, float gx, float gy, int t,
                                                 float &out_f, float &out_b)
 {
@@ -273,54 +329,9 @@ __device__ __forceinline__ void cddt_query_pair(const CddtParams &cp, float max_
     out_b = max_range;
     if (ly >= 0.0f && ly < (float)cp.width[t]) {
         const uint2 hd = cp.hdr[cp.bucket_off[t] + (uint32_t)(int)ly];
-        const uint32_t n = hd.y;
-        if (n) {
-            const float INF = __builtin_inff();
-            const uint32_t nleaf = (n + 31u) >> 5;
-            const float4 *lines = reinterpret_cast<const float4 *>(cp.tab) + (size_t)hd.x * 8;
-            float fwd = INF, bwd = -INF;
-            uint32_t leaf = 0;
-            bool have_leaf = true;
-            if (nleaf > 1u) {
-                const uint32_t nsl = (nleaf + 31u) >> 5;
-                uint32_t L = 0;
-                if (nsl > 1u) {                        // > 1024 values: the separator line whose first value is the last <= lx
-                    uint32_t a = 0, z = nsl;
-                    while (z - a > 1u) {
-                        const uint32_t mid = (a + z) >> 1;
-                        if (lines[(size_t)mid * 8].x <= lx) a = mid; else z = mid;
-                    }
-                    L = a;
-                    if (L + 1u < nsl) fwd = lines[(size_t)(L + 1u) * 8].x;      // (> lx: line z was probed)
-                }
-                uint32_t c = 0;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const float4 q = lines[(size_t)L * 8 + i];
-                    c += (q.x <= lx ? 1u : 0u) + (q.y <= lx ? 1u : 0u) + (q.z <= lx ? 1u : 0u) + (q.w <= lx ? 1u : 0u);
-                    fwd = __builtin_fminf(fwd, q.x > lx ? q.x : INF);
-                    fwd = __builtin_fminf(fwd, q.y > lx ? q.y : INF);
-                    fwd = __builtin_fminf(fwd, q.z > lx ? q.z : INF);
-                    fwd = __builtin_fminf(fwd, q.w > lx ? q.w : INF);
-                }
-                have_leaf = L * 32u + c > 0u;
-                leaf = L * 32u + c - 1u;
-                lines += (size_t)nsl * 8;
-            }
-            if (have_leaf) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const float4 q = lines[(size_t)leaf * 8 + i];
-                    fwd = __builtin_fminf(fwd, q.x >= lx ? q.x : INF);
-                    fwd = __builtin_fminf(fwd, q.y >= lx ? q.y : INF);
-                    fwd = __builtin_fminf(fwd, q.z >= lx ? q.z : INF);
-                    fwd = __builtin_fminf(fwd, q.w >= lx ? q.w : INF);
-                    bwd = __builtin_fmaxf(bwd, q.x <= lx ? q.x : -INF);
-                    bwd = __builtin_fmaxf(bwd, q.y <= lx ? q.y : -INF);
-                    bwd = __builtin_fmaxf(bwd, q.z <= lx ? q.z : -INF);
-                    bwd = __builtin_fmaxf(bwd, q.w <= lx ? q.w : -INF);
-                }
-            }
+        if (hd.y) {
+            float fwd, bwd;
+            cddt_search_pair(cp, hd, lx, fwd, bwd);
             out_f = __builtin_fminf(fwd - lx, max_range);
             out_b = __builtin_fminf(lx - bwd, max_range);
         }
@@ -974,6 +985,108 @@ __global__ __launch_bounds__(256) void cddt_rays_kernel(MapParams m, FanParams f
         float r = cddt_query(m, cp, f.max_range, gx, gy, thg);
         if (f.noise_std > 0.0f) r += f.noise_std * gauss_noise(f.noise_seed, f.ray_offset + i);
         out[i] = r;
+    }
+}
+
+// ---- batched races on the table (handle option race_cddt; include/scanlib.h "batched multi-car races") ----------
+// The reference's two-player tick stamps the other car into a copy of the grid and rebuilds this table.  A query is a
+// minimum (maximum) over ONE bucket, and every edge cell contributes its entries on its own, so the table of
+// "grid u other cars" is the static table plus what the other cars' outline cells add: car i of race g = blockIdx.x
+// takes, per table bin, the static bucket's two extrema (cddt_search_pair) and folds in the rotated x of every cell
+// of the other cars that covers the bucket, projected exactly as cddt_project_kernel projects an edge cell.  No
+// per-race table; one workgroup per race, as race_fan_kernel:
+//   1. the outlines of the race's cars -> LDS (outline_wave);
+//   2. one lane per (car, table bin): the bins the car's fan touches (cddt_fan_run), both raw bins of a table bin from
+//      one search, every lane of a wave reading the same cell of the same car (an LDS broadcast; a lane skips its own
+//      car by predicate).  min / max of finite values: the order of the cells does not matter;
+//   3. every beam looks its raw bin up, as cddt_fan_bins_kernel's store phase does.
+// A group of 1 folds nothing: cddt_fan_bins_kernel's arithmetic, bit for bit.  Dynamic LDS: group x theta_disc floats
+// (<= RACE_CDDT_MAX_BINS, checked on the host).
+__global__ __launch_bounds__(RACE_WG) void race_cddt_kernel(MapParams m, FanParams f, CddtParams cp, RaceParams rp,
+                                                            const float *__restrict__ poses, float *__restrict__ out)
+{
+    __shared__ uint32_t cells[RACE_MAX_GROUP][RACE_MAX_POINTS];
+    __shared__ int n_cells[RACE_MAX_GROUP];
+    extern __shared__ float bin_range[];                 // group x theta_disc floats
+    const int g = blockIdx.x, group = rp.group;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int k = wave; k < group; k += RACE_WG / 64) {
+        const double *s = rp.cars + (size_t)(g * group + k) * rp.car_stride;
+        CellBox b;
+        const int cnt = outline_wave(rp.o, s[0], s[1], s[2], lane, [&](int q, int cell) { cells[k][q] = (uint32_t)cell; }, b);
+        if (lane == 0) n_cells[k] = cnt;
+    }
+    __syncthreads();
+
+    const int td = cp.theta_disc, half = td / 2;
+    LutParams lp{};
+    lp.theta_disc = td;
+    lp.bins_per_rad = cp.bins_per_rad;
+    const float td_f = (float)td, inv_td = 1.0f / (float)td;
+    const float INF = __builtin_inff();
+    const int units = group * cp.n_bins;
+    for (int u = threadIdx.x; u < units; u += RACE_WG) {
+        const int i = u / cp.n_bins, t = u - i * cp.n_bins;
+        const size_t p = (size_t)g * group + i;
+        float gx, gy, thg;
+        world_to_grid(m, poses[3 * p], poses[3 * p + 1], poses[3 * p + 2], gx, gy, thg);
+        int first, cnt;
+        cddt_fan_run(f, cp, lp, thg, td_f, inv_td, first, cnt);
+        // raw bin t searches forward in table bin t; raw bin t + td/2 (if it maps here: >= n_bins) backward
+        const int rb = t + half;
+        const bool has_b = rb >= cp.n_bins && rb < td;
+        int df = t - first, db = rb - first;
+        df += df < 0 ? td : 0;
+        db += db < 0 ? td : 0;
+        const bool need_f = df < cnt, need_b = has_b && db < cnt;
+        if (!(need_f || need_b)) continue;
+        const float cs = cp.cosv[t], sn = cp.sinv[t], tr = cp.trans[t];
+        const int wdt = cp.width[t];
+        const float lx = __builtin_fmaf(gx, cs, -(gy * sn));
+        const float ly = __builtin_fmaf(gx, sn, gy * cs) + tr;
+        float rf = f.max_range, rbk = f.max_range;
+        if (ly >= 0.0f && ly < (float)wdt) {
+            const int b = (int)ly;
+            const uint2 hd = cp.hdr[cp.bucket_off[t] + (uint32_t)b];
+            float fwd = INF, bwd = -INF;
+            if (hd.y) cddt_search_pair(cp, hd, lx, fwd, bwd);
+            const float hw = (fabsf(sn) + fabsf(cs)) * 0.5f;
+            for (int k = 0; k < group; ++k) {
+                const int n = n_cells[k];
+                const bool other = k != i;
+                for (int q = 0; q < n; ++q) {
+                    const uint32_t cell = cells[k][q];
+                    const float px = (float)(cell & 0xffffu) + 0.5f, py = (float)(cell >> 16) + 0.5f;
+                    const float slx = __builtin_fmaf(px, cs, -(py * sn));
+                    const float sly = __builtin_fmaf(px, sn, py * cs) + tr;
+                    int upper = (int)((sly + hw) - CDDT_EPS);
+                    int lower = (int)((sly - hw) + CDDT_EPS);
+                    if (lower < 0) lower = 0;
+                    if (upper >= wdt) upper = wdt - 1;
+                    const bool covers = other && lower <= b && b <= upper;
+                    fwd = covers && slx >= lx ? __builtin_fminf(fwd, slx) : fwd;
+                    bwd = covers && slx <= lx ? __builtin_fmaxf(bwd, slx) : bwd;
+                }
+            }
+            rf = __builtin_fminf(fwd - lx, f.max_range);
+            rbk = __builtin_fminf(lx - bwd, f.max_range);
+        }
+        float *br = bin_range + (size_t)i * td;
+        if (need_f) br[t] = rf * m.res;
+        if (need_b) br[rb] = rbk * m.res;
+    }
+    __syncthreads();
+
+    // (bins a fan does not touch were never written: never looked up)
+    const int total = group * f.num_rays;
+    for (int r = threadIdx.x; r < total; r += RACE_WG) {
+        const int i = r / f.num_rays, j = r - i * f.num_rays;
+        const size_t p = (size_t)g * group + i;
+        const float thg = poses[3 * p + 2] + m.wa;
+        const size_t idx = p * f.num_rays + j;
+        float v = bin_range[(size_t)i * td + lut_bin_fast(-(thg + fan_alpha(f, j)), lp, td_f, inv_td)];
+        if (f.noise_std > 0.0f) v += fan_noise(f, idx);
+        out[idx] = v;
     }
 }
 

@@ -78,6 +78,8 @@ BOUNDS = [
     # batched races: the outline raster, and the race scan's march with the other cars' cells folded into each sample
     ("scan::outline_cells_kernel", {"scratch": 0}),
     ("scan::race_fan_kernel<", {"scratch": 0}),
+    # ... and its CDDT form (option race_cddt): the bucket search and the fold of the other cars' cells spill nothing
+    ("scan::race_cddt_kernel", {"scratch": 0}),
     # particle-filter weights: the fused march + sensor-model product spills nothing; eight waves per SIMD in the
     # canonical form, seven in the literal one (its libm-exact trig holds 106 SGPRs)
     ("scan::pf_weight_kernel<false>", {"scratch": 0, "occupancy": 8}),

@@ -295,7 +295,8 @@ class DriveEnv(_lib.Handle):
 
 class RaceEnv(DriveEnv):
     """``n_races`` races of P cars on one device, every car driven by the caller's actions.  ``starts`` float64
-    (M, P, 11) is the pool of line-ups: a race spawns all its cars from one of them.  ``method``: RM or RMGPU.  The race
+    (M, P, 11) is the pool of line-ups: a race spawns all its cars from one of them.  ``method``: RM, RMGPU, or
+    ``PyCDDTCast(..., races=True)`` (the two-player simulator's method; GiantLUT and Bresenham cannot race).  The race
     is over once fewer than ``min_running`` of its cars run (``race_over`` 1; the cars still running read done = 2) or
     at ``max_ticks`` steps (``race_over`` 2); until then a finished car stays where it is and the others see it.  The
     other arguments are ``DriveEnv``'s.  ``reset`` takes one start index per race; ``reset``, ``step`` and ``read`` give

@@ -184,7 +184,9 @@ class CarBatch(_lib.Handle):
         FollowGap).  states float64 (R, P, 11) — R races of P <= 8 cars —; speed a scalar or float64 (R, P); steer0
         None (0) or float32 (R, P).  Returns ``drive_followgap``'s tuple with R P reshaped to (R, P): first crash tick
         (R, P), final states (R, P, 11), velocities and steers (R, P, n_ticks), with ``trace=True`` also lidar poses
-        (R, P, n_ticks, 3) and states (R, P, n_ticks, 11).  A crashed car stays in its race as a wreck."""
+        (R, P, n_ticks, 3) and states (R, P, n_ticks, 11).  A crashed car stays in its race as a wreck.  ``method``: RM,
+        RMGPU, or ``PyCDDTCast(..., races=True)``; GiantLUT and Bresenham are refused (so in ``race_seats`` and
+        ``race_league``)."""
         st, counts = self._race_states(states)
         return self._drive("rl_car_race_followgap", (method, followgap), counts, (), (), st, n_ticks, speed, fov,
                            num_rays, edge, crash_thresh, scan_dist_to_base, dt, steer0, trace)
@@ -195,8 +197,8 @@ class CarBatch(_lib.Handle):
         one ``PyFollowGap`` or ``Policy`` per car of a race (at most one distinct object of each kind), and car k of
         every race is steered by ``drivers[k]``'s answer to its scan — scripts/two_player/ with simple_driver.py in some
         seats and policy_driver.py in others.  ``steer_clip`` as ``drive_policy`` takes it: it clamps the network's
-        seats only.  The steers returned are each driver's raw answers.  Arguments and results as ``race_followgap``;
-        with FollowGap in every seat it returns that call's bits."""
+        seats only.  The steers returned are each driver's raw answers.  Arguments (the kinds of ``method`` that race
+        included) and results as ``race_followgap``; with FollowGap in every seat it returns that call's bits."""
         from .seats import seat_args
         st, counts = self._race_states(states)
         codes, fg, pol = seat_args(drivers, counts[1], num_rays, caller_ok=False)
@@ -246,7 +248,8 @@ class CarBatch(_lib.Handle):
         ``population.PolicyPopulation``) or -1 for ``followgap``; states float64 (R, P, 11).  ``steer_clip`` clamps the
         members' cars only.  Returns ``race_seats``'s tuple plus ``standings`` float64 (n_members, 4): per member the
         cars it entered, the sum of their travel_dist gains (ascending car index, each addition rounded), how many
-        crashed, and how many cars of their own races they beat (alive longer, or as long with the larger gain)."""
+        crashed, and how many cars of their own races they beat (alive longer, or as long with the larger gain).
+        ``method`` as ``race_followgap``: RM, RMGPU or a CDDT handle made with ``races=True``."""
         from .league import league_args
         st, counts = self._race_states(states)
         entry = league_args(entries, counts[0], counts[1], pop, followgap, num_rays)

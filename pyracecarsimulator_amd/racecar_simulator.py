@@ -333,9 +333,9 @@ class RacecarSimulator:
                         self.num_rays, self.scan_fov, self.edge_distances, self.ttc_thresh, **kw)
 
     def raceEnv(self, n_races, starts, **kw):
-        """A ``RaceEnv`` of ``n_races`` races on this simulator's range method (RM or RMGPU), car, fan, edge table,
-        ttc_thresh and scan_dist_to_base, spawning from the line-ups ``starts`` float64 (M, P, 11): the tick of
-        ``raceFollowGapMany`` with the (speed, steer) of every car supplied by the caller.  ``kw``: ``RaceEnv``'s keyword
+        """A ``RaceEnv`` of ``n_races`` races on this simulator's range method (RM, RMGPU or "CDDT" set with
+        ``races=True``), car, fan, edge table, ttc_thresh and scan_dist_to_base, spawning from the line-ups ``starts``
+        float64 (M, P, 11): the tick of ``raceFollowGapMany`` with the (speed, steer) of every car supplied by the caller.  ``kw``: ``RaceEnv``'s keyword
         arguments (min_running and ``DriveEnv``'s, the track keywords included; ``seats`` and ``seat_speed`` put a
         driver into a seat, "fg" standing for this simulator's own FollowGap driver; ``league=(pop, entries)`` gives
         every car its own driver, -1 entries going to ``followgap`` or, without one, to the simulator's own)."""
@@ -362,4 +362,5 @@ class RacecarSimulator:
         self.scan_simulator.setMap(ros_map, max_range_px, resolution, origin)
 
     def setRaytracingMethod(self, method="RMGPU", **kw):
-        self.scan_simulator.setRaytracingMethod(method, **kw)      # (theta_disc=, lut_refine= for "GLT")
+        # (theta_disc=, lut_refine= for "GLT"; theta_disc=, races= for "CDDT")
+        self.scan_simulator.setRaytracingMethod(method, **kw)

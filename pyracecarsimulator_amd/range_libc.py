@@ -299,7 +299,9 @@ class _RangeMethod(_lib.Handle):
         """The scan of N = n_groups * group poses in races of ``group`` cars (``rl_calc_range_fan_cars``): pose i of
         group g is scanned on the grid with the outlines (length x width, the reference car by default) of the OTHER
         cars of group g stamped, car k at ``car_poses`` row g * group + k.  poses float32 (N, 3) lidar poses; car_poses
-        float64 (N, 3) car states (x, y, theta).  RM and RMGPU only.  Returns outs float32 (N * num_rays,)."""
+        float64 (N, 3) car states (x, y, theta).  RM and RMGPU, and CDDT with ``races=True`` (ranges only: the others'
+        cells join the static buckets at query time, include/scanlib.h); GiantLUT and Bresenham are refused.  Returns
+        outs float32 (N * num_rays,)."""
         poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 3)
         cars = np.ascontiguousarray(car_poses, dtype=np.float64).reshape(-1, 3)
         group = int(group)
@@ -514,11 +516,18 @@ class PyBresenhamsLine(_RangeMethod):
 
 
 class PyCDDTCast(_RangeMethod):
-    """range_libc.PyCDDTCast(omap, mrx, theta_disc) (scripts/two_player/scan.py:46)."""
+    """range_libc.PyCDDTCast(omap, mrx, theta_disc) (scripts/two_player/scan.py:46).
+
+    ``races=True`` lets the handle run batched races (option ``race_cddt``, include/scanlib.h "batched multi-car races"):
+    ``calc_range_fan_cars``, ``CarBatch.race_*`` and ``RaceEnv`` then query the static table with the other cars'
+    outline cells folded into each bucket, instead of refusing the kind.  It equals stamping the others, rebuilding and
+    scanning wherever every outline cell is an edge cell of the stamped grid and no static edge cell stops being one."""
     KIND = _lib.RL_CDDT
 
-    def __init__(self, omap, max_range_px, theta_disc):
+    def __init__(self, omap, max_range_px, theta_disc, races=False):
         super().__init__(omap, max_range_px, theta_disc)
+        if races:
+            self.set_option("race_cddt", 1)
 
     def prune(self, max_range=None):   # upstream API; pruning is a no-op for exactness
         return None

@@ -60,10 +60,12 @@ class ScanSimulator2D:
         self.res = resolution
         self.hasMap = True
 
-    def setRaytracingMethod(self, method="RM", theta_disc=None, lut_refine=False):
+    def setRaytracingMethod(self, method="RM", theta_disc=None, lut_refine=False, races=False):
         """"RM" / "RMGPU" as in the reference; "GLT": range_libc's GiantLUTCast with ``theta_disc`` bins (default: one
         bin per beam spacing, 2 pi num_rays / fov rounded to an even number) and, with ``lut_refine``, its
-        origin-corrected query."""
+        origin-corrected query; "CDDT" with ``theta_disc`` given (rcs_two_player.py builds with 112): range_libc's
+        CDDTCast, the two-player simulator's method, and, with ``races``, batched races on it (option ``race_cddt``).
+        Any other name, "CDDT" without its ``theta_disc`` included, prints and exits as the reference does."""
         if not self.hasMap:
             print("for set RaytracingMethod use setMap first")
             return
@@ -75,6 +77,8 @@ class ScanSimulator2D:
             if theta_disc is None:
                 theta_disc = 2 * int(round(math.pi * self.num_rays / self.fov))
             self.scan_method = range_libc.PyGiantLUTCast(self.omap, self.mrx, theta_disc, refine=lut_refine)
+        elif method == "CDDT" and theta_disc is not None:
+            self.scan_method = range_libc.PyCDDTCast(self.omap, self.mrx, theta_disc, races=races)
         else:
             print("Only ray marching is supported")
             sys.exit()
