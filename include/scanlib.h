@@ -858,7 +858,7 @@ int  rl_env_read_track_device(rl_env *e, float *d_rows_n8, int *d_ints_n4, void 
  * rl_mcts_create: c, h and the source's handle (g for FG, p for NN; borrowed, they must outlive the planner) on ONE
  * device, multi-device handles refused.  edge: num_rays doubles (rl_car_edge_distances).  Errors (RL_ERR_INVALID):
  * null pointers, K < 1, max_nodes < 1, L outside [1, 512], action_every < 1, an unknown source or one without its
- * handle, num_rays outside [10, 1280], num_rays < in_start + dims[0] for NN, K L num_rays >= 2^31, handles on
+ * handle (RL_MCTS_RANDOM and RL_MCTS_PURSUIT take none), num_rays outside [10, 1280], num_rays < in_start + dims[0] for NN, K L num_rays >= 2^31, handles on
  * different devices.
  * rl_mcts_reset: the K roots (states K x 11, recent actions K, one 64-bit seed per tree); takes the root scans.
  * rl_mcts_run: n_iterations iterations, synchronous; n iterations equal n/2 followed by n/2.  Refused before any
@@ -900,15 +900,44 @@ int  rl_env_read_track_device(rl_env *e, float *d_rows_n8, int *d_ints_n4, void 
  * states_out = states_in, recent_out = recent_in, the planner untouched.  Errors (RL_ERR_INVALID, nothing launched,
  * the handles usable as before): a null required pointer, n_decisions < 0, n_iterations < 1, n_iterations + 1 >
  * max_nodes, steps_per_decision < 1, steer_clip negative or NaN, and the range method's refusals as in rl_mcts_run.
- * Kernels: mcts_kernels.h.                                                                                    */
+ * Kernels: mcts_kernels.h.
+ *
+ * The track steering the search (kernels: plan_pursuit_kernels.h, pursuit_device.h; tests/mcts_pursuit_statement.py).
+ * The track, its options and the explicit points are those of scanlib_track_plan.h (rl_mcts_attach_track,
+ * rl_mcts_set_points); a zeroed rollout_source / rollout_dev and a source below 3 are the planner above, launch for launch.
+ *   - the pursuit steer of a car with state (x, y, th) = state[0..2] towards a world point (X, Y), all float64, every
+ *     operation rounded separately, WB the car's wheelbase:
+ *       rx = X - x; ry = Y - y; hx = cos th; hy = sin th; gx = hx rx + hy ry; gy = hx ry - hy rx  (the car frame of
+ *       "track progress"); d2 = gx gx + gy gy; if !(d2 > 0): 0.0f (the point is the car, or something is NaN);
+ *       else a = atan(((2.0 WB) gy) / d2), a = fmin(fmax(a, -max_steer), max_steer), the answer (float)a.
+ *     The answer is float32, as FollowGap's and the network's; whoever consumes it widens it with (double)answer;
+ *   - source RL_MCTS_PURSUIT (no handle): the stored expansion answer of every node, the root included, is the pursuit
+ *     steer from the node's own state towards the tree's track point: the (px, py) of scanlib_track_plan.h's reward
+ *     mode 1, chosen at rl_mcts_reset and at every decision of rl_mcts_drive whatever the reward mode (mode 0 with a
+ *     track attached is valid); 0.0f for a tree without a point (goal -1 and no explicit point).  Everything else is
+ *     the FG / NN rule: the first child takes (double)answer, later ones uniSample(children[0].action, uni_dev);
+ *   - rollout_source 1 (pursuit roll-outs, any source): roll-out action m's steer, chosen from the state before step
+ *     m action_every (m = 0: the child's state), is fmin(fmax(base + uniform(-rollout_dev, rollout_dev; u), -max_steer),
+ *     max_steer) with u the draw d = 1 + 2m of the uniform steer it replaces and base = (double)(the pursuit steer towards
+ *     the goal waypoint), 0.0 without a goal.  The goal: "track progress"'s nearest segment of the state among the
+ *     segments within `window` of the segment action m - 1 found (m = 0: of the root's segment, found over all segments;
+ *     window 0: all segments), then its goal rule from that segment with the attached lookahead and goal_span.  The
+ *     speed (d = 2 + 2m), the steps, the scans, the crash test, the reward terms and the backup are unchanged.
+ * Errors (RL_ERR_INVALID, nothing launched, the handles usable as before): rollout_source outside {0, 1}, or with 1 a
+ * rollout_dev negative or not finite, at create; reset, run or drive of an RL_MCTS_PURSUIT planner with neither a track nor
+ * explicit points, or of a pursuit roll-out planner without a track (explicit points do not help a roll-out); attach of
+ * a lookahead not finite or <= 0, in any reward mode, to a pursuit roll-out planner or to an RL_MCTS_PURSUIT planner
+ * without explicit points.                                                                                     */
 typedef struct rl_mcts rl_mcts;
-typedef enum rl_mcts_source { RL_MCTS_FG = 0, RL_MCTS_NN = 1, RL_MCTS_RANDOM = 2 } rl_mcts_source;
+typedef enum rl_mcts_source { RL_MCTS_FG = 0, RL_MCTS_NN = 1, RL_MCTS_RANDOM = 2, RL_MCTS_PURSUIT = 3 } rl_mcts_source;
 typedef struct rl_mcts_params {
     int n_trees, max_nodes, rollout_steps, action_every, source;
     double speed, dt, scan_dist_to_base, C, crash_pen, uni_dev, max_steer, max_speed;
     float fov;
     int num_rays;
     double crash_thresh;
+    int rollout_source;                 /* 0: the uniform steer (rollout_dev not read); 1: pursuit roll-outs */
+    double rollout_dev;
 } rl_mcts_params;
 int rl_mcts_create(rl_car *c, rl_method *h, rl_followgap *g_or_null, rl_policy *p_or_null,
                    const rl_mcts_params *params, const double *edge, rl_mcts **out);

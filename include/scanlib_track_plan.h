@@ -37,16 +37,19 @@
  * rl_car_rollout_track: rl_car_rollout's R roll-outs with the terms [R x n_steps] of *p's reward_mode on track t.
  *   n_steps <= 512.  anchor_segment_or_null is read in mode 2, points_or_null in mode 1; s, segment [R x n_steps] and
  *   start_s [R] (each optional) are written in mode 2 only.  t may be null in mode 0, and in mode 1 with points.
- * rl_mcts_attach_track: t is borrowed (keep it alive while attached); a null t detaches (p is not read).  The planner
- *   needs a reset after attaching or detaching, and after rl_mcts_set_points.
+ * rl_mcts_attach_track: t is borrowed (keep it alive while attached); a null t detaches, and of a non-null p only the
+ *   reward_mode is kept then (0 or 1): the mode a planner with explicit points and no track runs (null p: mode 1).  The
+ *   planner needs a reset after attaching or detaching, and after rl_mcts_set_points.  The attached window, goal_span,
+ *   lookahead and the tree's track point also steer the search where the planner asks for it (scanlib.h, "the track
+ *   steering the search": source RL_MCTS_PURSUIT pursues the point, rollout_source 1 the goal waypoint), in every mode.
  * rl_mcts_set_points: one explicit point per tree (K x 2, copied), null removes them.  They are the track points of
- *   mode 1; a planner with points and no track attached runs mode 1 with them.
+ *   mode 1; a planner with points and no track attached runs mode 1 with them unless an attach without a track said 0.
  * rl_mcts_read_track: per tree the current roots' segment, s, goal index and track point (K, K, K, K x 2; each
  *   pointer optional); after rl_mcts_drive those of the last decision.  Without a track: segment -1, s NaN, goal -1.
  *   With an explicit point the point reads back as given; without a goal or point it reads (0, 0).
  * Errors (RL_ERR_INVALID, nothing launched, the handles usable as before): null params with a track; reward_mode
  *   outside {0, 1, 2}; window or goal_span < 0 or > 65536; lookahead not finite or <= 0 in mode 1 without explicit
- *   points; a track on another device; mode 2 without a track (mode 1 without a track or points likewise);
+ *   points (and where scanlib.h's track steering reads it); a reward_mode other than 0 or 1 without a track; a track on another device; mode 2 without a track (mode 1 without a track or points likewise);
  *   rl_mcts_drive on a planner with explicit points (the drive needs a track to re-choose the point);
  *   rl_mcts_read_track before a reset or without a track or points; an anchor outside [0, S); n_steps > 512 and what
  *   rl_car_rollout refuses; multi-device handles.

@@ -77,7 +77,8 @@ class MctsParams(C.Structure):
     _fields_ = [("n_trees", C.c_int), ("max_nodes", C.c_int), ("rollout_steps", C.c_int), ("action_every", C.c_int),
                 ("source", C.c_int)] + [(n, C.c_double) for n in (
                     "speed", "dt", "scan_dist_to_base", "C", "crash_pen", "uni_dev", "max_steer", "max_speed")] + [
-                ("fov", C.c_float), ("num_rays", C.c_int), ("crash_thresh", C.c_double)]
+                ("fov", C.c_float), ("num_rays", C.c_int), ("crash_thresh", C.c_double), ("rollout_source", C.c_int),
+                ("rollout_dev", C.c_double)]
 
 
 class PfParams(C.Structure):
@@ -119,7 +120,7 @@ class SeatParams(C.Structure):
     _fields_ = [("driver", C.c_int * 8), ("speed", C.c_float * 8)]
 
 
-RL_MCTS_FG, RL_MCTS_NN, RL_MCTS_RANDOM = 0, 1, 2
+RL_MCTS_FG, RL_MCTS_NN, RL_MCTS_RANDOM, RL_MCTS_PURSUIT = 0, 1, 2, 3
 #: enum rl_seat_driver (include/scanlib_seats.h)
 SEAT_DRIVERS = {"caller": 0, "followgap": 1, "policy": 2}
 

@@ -27,6 +27,7 @@
 #include "drive_track_kernels.h"
 #include "mcts_kernels.h"
 #include "plan_track_kernels.h"
+#include "plan_pursuit_kernels.h"
 #include "policy_kernels.h"
 #include "probe_kernels.h"
 #include "race_kernels.h"
@@ -2401,7 +2402,7 @@ static const std::array<mcts_act_fn, FG_ROWS> mcts_act_table =
 struct rl_mcts {
     rl_car *c = nullptr;
     rl_method *h = nullptr;
-    SteerSource src;               // FollowGap, the policy or nobody (the random source)
+    SteerSource src;               // FollowGap, the policy or nobody (the random and the track source)
     rl_mcts_params prm{};
     MctsParams mp{};
     int device = 0;
@@ -2420,6 +2421,7 @@ struct rl_mcts {
     rl_track *track = nullptr;
     PlanTrackParams tp{};
     bool has_points = false;
+    int points_mode = PLAN_WAYPOINT;   // the reward mode of explicit points without a track (rl_mcts_attach_track(m, NULL, p))
     DevPtr<double> tk_points, tk_s, tk_point, rxy, terms;
     DevPtr<int> tk_seg, tk_goal, tk_has;
     bool ready = false;            // reset done and no launch failed since (read and written under mu only)
@@ -2459,8 +2461,12 @@ extern "C" int rl_mcts_create(rl_car *c, rl_method *h, rl_followgap *g, rl_polic
     const rl_mcts_params q = *params;
     if (q.source == RL_MCTS_FG && !g) return fail(RL_ERR_INVALID, "rl_mcts_create: the FG source needs a FollowGap handle");
     if (q.source == RL_MCTS_NN && !p) return fail(RL_ERR_INVALID, "rl_mcts_create: the NN source needs a policy handle");
-    if (q.source != RL_MCTS_FG && q.source != RL_MCTS_NN && q.source != RL_MCTS_RANDOM)
+    if (q.source != RL_MCTS_FG && q.source != RL_MCTS_NN && q.source != RL_MCTS_RANDOM && q.source != RL_MCTS_PURSUIT)
         return fail(RL_ERR_INVALID, "rl_mcts_create: unknown source %d", q.source);
+    if (q.rollout_source != 0 && q.rollout_source != 1)
+        return fail(RL_ERR_INVALID, "rl_mcts_create: rollout_source must be 0 (random) or 1 (pursuit) (got %d)", q.rollout_source);
+    if (q.rollout_source == 1 && (!std::isfinite(q.rollout_dev) || q.rollout_dev < 0.0))
+        return fail(RL_ERR_INVALID, "rl_mcts_create: rollout_dev must be finite and >= 0");
     g = q.source == RL_MCTS_FG ? g : nullptr;
     const SteerSource src = g ? SteerSource::followgap(g) : q.source == RL_MCTS_NN ? SteerSource::policy(p) : SteerSource();
     if (q.n_trees < 1 || q.max_nodes < 1 || q.action_every < 1 || q.rollout_steps < 1 || q.rollout_steps > MCTS_MAX_STEPS)
@@ -2520,17 +2526,26 @@ extern "C" int rl_mcts_create(rl_car *c, rl_method *h, rl_followgap *g, rl_polic
     return RL_OK;
 }
 
-// the act scans of the K nodes in m->cpose at ray offset `off`, the network for NN, then mcts_act_kernel on b
+static PlanRoots plan_roots_of(rl_mcts *m);
+
+// the act scans of the K nodes in m->cpose at ray offset `off`, the network for NN, then mcts_act_kernel on b and, for
+// the track source, mcts_pursuit_answer_kernel behind it
 static int mcts_act(rl_mcts *m, const Loop &lp, const MctsBufs &b, uint64_t off, int root, hipStream_t st)
 {
     const LoopScan scan{m->cpose, m->prm.n_trees, m->prm.fov, m->prm.num_rays, m->ranges, m->mlp, 0, nullptr, nullptr};
-    return lp.scan_then(scan, off, mcts_act_table, MCTS_TREES, "mcts_act_kernel", st, m->mp, b, root);
+    int rc = lp.scan_then(scan, off, mcts_act_table, MCTS_TREES, "mcts_act_kernel", st, m->mp, b, root);
+    if (rc || m->prm.source != RL_MCTS_PURSUIT) return rc;
+    // the track source: the node's answer is the pursuit of the tree's point from its own state
+    const int K = m->prm.n_trees;
+    return launch("mcts_pursuit_answer_kernel", mcts_pursuit_answer_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b,
+                  plan_roots_of(m));
 }
 
-// the reward mode the planner runs: the attached track's, the waypoint reward for explicit points alone, else velocity
+// the reward mode the planner runs: the attached track's; for explicit points alone the waypoint reward, or the mode
+// kept by an attach without a track; else velocity
 static int plan_mode(const rl_mcts *m)
 {
-    return m->track ? m->tp.mode : m->has_points ? PLAN_WAYPOINT : PLAN_VELOCITY;
+    return m->track ? m->tp.mode : m->has_points ? m->points_mode : PLAN_VELOCITY;
 }
 
 static PlanRoots plan_roots_of(rl_mcts *m)
@@ -2538,9 +2553,24 @@ static PlanRoots plan_roots_of(rl_mcts *m)
     return PlanRoots{m->tk_seg, m->tk_s, m->tk_goal, m->tk_point, m->tk_has};
 }
 
-// what a reset and a drive refuse of the track options before anything is launched
+// does the planner read the goal rule's lookahead: the waypoint reward and the track source without explicit points,
+// the pursuit roll-outs always
+static bool plan_needs_lookahead(const rl_mcts *m, int mode, bool points)
+{
+    return ((mode == PLAN_WAYPOINT || m->prm.source == RL_MCTS_PURSUIT) && !points) || m->prm.rollout_source == 1;
+}
+
+// what a reset, a run and a drive refuse of the track options before anything is launched
 static int plan_args(const rl_mcts *m, const char *name)
 {
+    if (m->prm.source == RL_MCTS_PURSUIT && !m->track && !m->has_points)
+        return fail(RL_ERR_INVALID, "%s: the track source needs a track (rl_mcts_attach_track) or explicit points", name);
+    if (m->prm.rollout_source == 1 && !m->track)
+        return fail(RL_ERR_INVALID, "%s: pursuit roll-outs need a track (rl_mcts_attach_track)", name);
+    if (m->track && plan_needs_lookahead(m, PLAN_VELOCITY, m->has_points) &&
+        (!std::isfinite(m->tp.lookahead) || !(m->tp.lookahead > 0.0)))
+        return fail(RL_ERR_INVALID, "%s: the track source without explicit points and pursuit roll-outs need a finite "
+                    "lookahead > 0", name);
     if (plan_mode(m) == PLAN_WAYPOINT && !m->has_points && (!std::isfinite(m->tp.lookahead) || !(m->tp.lookahead > 0.0)))
         return fail(RL_ERR_INVALID, "%s: the waypoint reward without explicit points needs a finite lookahead > 0", name);
     return RL_OK;
@@ -2598,11 +2628,12 @@ extern "C" int rl_mcts_reset(rl_mcts *m, const double *root_states, const double
 // iterations it0 ... it0 + n - 1 of every tree, enqueued on st: select, the act, the roll-outs and their crash
 // test, the backup.  base: the ray offset of the trees' reset.  lp: the call's Loop; the caller has sized m->rranges.
 // With a reward mode other than velocity the roll-outs also give their f64 positions, plan_term_kernel turns them into
-// the terms, and the backup sums those.
+// the terms, and the backup sums those.  rollout_source 1: rollout_pursuit_kernel stands where the roll-out kernel stood
+// and hands over the same outputs.
 static int mcts_iterations(rl_mcts *m, const Loop &lp, const MctsBufs &bufs, uint64_t base, long it0, int n, hipStream_t st)
 {
     const int K = m->prm.n_trees, L = m->prm.rollout_steps, B = m->prm.num_rays;
-    const bool terms = plan_mode(m) != PLAN_VELOCITY;
+    const bool terms = plan_mode(m) != PLAN_VELOCITY, pursuit = m->prm.rollout_source == 1;
     const TrackTable T = m->track ? track_table(m->track) : TrackTable{};
     PlanTrackParams tp = m->tp;
     tp.mode = plan_mode(m);
@@ -2615,10 +2646,13 @@ static int mcts_iterations(rl_mcts *m, const Loop &lp, const MctsBufs &bufs, uin
         int rc;
         if ((rc = launch("mcts_select_kernel", mcts_select_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->mp, b, (int)it)) ||
             (rc = mcts_act(m, lp, b, off, 0, st)) ||
-            (rc = terms ? launch("rollout_xy_kernel", rollout_xy_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, m->cstate,
-                                 m->actions, K, L, m->prm.action_every, m->prm.dt, m->rposes, m->vel, m->rxy)
-                        : launch("rollout_kernel", rollout_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, m->cstate,
-                                 m->actions, K, L, m->prm.action_every, m->prm.dt, m->rposes, nullptr, m->vel)) ||
+            (rc = pursuit ? launch("rollout_pursuit_kernel", rollout_pursuit_kernel, dim3((K + MCTS_TREES - 1) / MCTS_TREES),
+                                   dim3(64 * MCTS_TREES), 0, st, m->mp, b, T, m->tp, plan_roots_of(m), (int)it, m->prm.rollout_dev,
+                                   m->rposes, m->vel, m->rxy)
+                  : terms ? launch("rollout_xy_kernel", rollout_xy_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, m->cstate,
+                                   m->actions, K, L, m->prm.action_every, m->prm.dt, m->rposes, m->vel, m->rxy)
+                          : launch("rollout_kernel", rollout_kernel, dim3((K + 63) / 64), dim3(64), 0, st, m->c->P, m->cstate,
+                                   m->actions, K, L, m->prm.action_every, m->prm.dt, m->rposes, nullptr, m->vel)) ||
             (terms && (rc = launch("plan_term_kernel", plan_term_kernel, dim3(K), dim3(64 * PLAN_TERM_WAVES), 0, st, T, tp, L,
                                    m->cstate, m->rxy, m->vel, plan_roots_of(m), m->terms, nullptr, nullptr, nullptr))) ||
             (rc = crash_groups_device(m->h, lp.at(off + KB), m->rposes, K, L, m->prm.fov, B, m->edge, m->prm.crash_thresh, m->first,
@@ -2634,12 +2668,13 @@ extern "C" int rl_mcts_run(rl_mcts *m, int n_iterations)
     if (!m) return fail(RL_ERR_INVALID, "rl_mcts_run: null pointer");
     if (n_iterations < 0) return fail(RL_ERR_INVALID, "rl_mcts_run: n_iterations must be >= 0 (got %d)", n_iterations);
     const Loop lp(&m->mu, m->c, m->h, m->src);
+    int rc;
+    if ((rc = plan_args(m, "rl_mcts_run"))) return rc;
     if (!m->ready) return fail(RL_ERR_INVALID, "rl_mcts_run: reset the planner first (rl_mcts_reset)");
     if (1 + m->iters + (long)n_iterations > m->prm.max_nodes)
         return fail(RL_ERR_INVALID, "rl_mcts_run: %d more iterations exceed max_nodes = %d (%ld done since reset)",
                     n_iterations, m->prm.max_nodes, m->iters);
     const int K = m->prm.n_trees, L = m->prm.rollout_steps, B = m->prm.num_rays;
-    int rc;
     if ((rc = check_fan_args(m->h, K, m->prm.fov, B)) || (rc = check_fan_args(m->h, K * L, m->prm.fov, B))) return rc;
     if (n_iterations == 0) return RL_OK;
     HIPCHK(hipSetDevice(m->device));
@@ -2836,6 +2871,9 @@ extern "C" int rl_mcts_attach_track(rl_mcts *m, rl_track *t, const rl_plan_track
     if (t) {
         int rc = plan_track_args("rl_mcts_attach_track", p, m->has_points);
         if (rc) return rc;
+        if (plan_needs_lookahead(m, PLAN_VELOCITY, m->has_points) && (!std::isfinite(p->lookahead) || !(p->lookahead > 0.0)))
+            return fail(RL_ERR_INVALID, "rl_mcts_attach_track: the track source without explicit points and pursuit roll-outs "
+                        "need a finite lookahead > 0");
         if (t->device != m->device)
             return fail(RL_ERR_INVALID, "rl_mcts_attach_track: track (device %d) and planner (device %d) must share one device",
                         t->device, m->device);
@@ -2846,7 +2884,10 @@ extern "C" int rl_mcts_attach_track(rl_mcts *m, rl_track *t, const rl_plan_track
             (rc = m->terms.ensure(K * L)))
             return rc;
         m->tp = PlanTrackParams{p->reward_mode, p->window, p->goal_span, p->lookahead};
+    } else if (p && p->reward_mode != PLAN_VELOCITY && p->reward_mode != PLAN_WAYPOINT) {
+        return fail(RL_ERR_INVALID, "rl_mcts_attach_track: without a track reward_mode must be 0 or 1 (got %d)", p->reward_mode);
     }
+    if (!t) m->points_mode = p ? p->reward_mode : PLAN_WAYPOINT;     // (explicit points alone: the waypoint reward unless told)
     m->track = t;
     m->ready = false;                   // the roots of the new track are found at the next reset
     return RL_OK;

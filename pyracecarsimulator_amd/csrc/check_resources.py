@@ -75,6 +75,11 @@ BOUNDS = [
     # track-guided planning: the roots' wave and the term workgroup spill nothing, and eight waves share a SIMD
     ("scan::plan_root_kernel", {"scratch": 0, "occupancy": 8}),
     ("scan::plan_term_kernel", {"scratch": 0, "occupancy": 8}),
+    # the track steering the search: the one-lane answer and the roll-out's wave (searches in 64 lanes, the f64 car steps
+    # in lane 0) spill nothing.  The roll-out holds the search and the car step live at once: 199 VGPRs, two waves per
+    # SIMD, which is its whole 8-wave workgroup on a compute unit (rollout_kernel alone is 128 VGPRs)
+    ("scan::mcts_pursuit_answer_kernel", {"scratch": 0, "occupancy": 8}),
+    ("scan::rollout_pursuit_kernel", {"scratch": 0, "occupancy": 2}),
     # batched races: the outline raster, and the race scan's march with the other cars' cells folded into each sample
     ("scan::outline_cells_kernel", {"scratch": 0}),
     ("scan::race_fan_kernel<", {"scratch": 0}),

@@ -10,7 +10,9 @@ decisions enqueued at once, nothing leaving the device in between.
 
 ``MCTSPlanner.attach_track`` gives the planner a ``Track`` (include/scanlib_track_plan.h; kernels
 csrc/plan_track_kernels.h): every roll-out step's reward term becomes the reference's waypoint reward (mcts.py:233-234)
-or the track progress of the step, for ``run`` and for ``drive`` alike, with nothing new crossing to the host.
+or the track progress of the step, for ``run`` and for ``drive`` alike, with nothing new crossing to the host.  The track
+can also steer the search (kernels csrc/plan_pursuit_kernels.h): ``source="track"`` expands every node with the pure
+pursuit of the tree's track point, ``rollout="pursuit"`` steers every roll-out along the track's goal waypoints.
 
 ``MCTS`` is a drop-in for the reference class (scripts/mcts.py:83-148) on a ``RacecarSimulator``: ``mcts()`` plans
 from the simulator's state and returns the most visited root action; ``root`` holds the tree read back from the
@@ -25,7 +27,9 @@ import numpy as np
 
 from . import _lib
 
-SOURCES = {"fg": _lib.RL_MCTS_FG, "nn": _lib.RL_MCTS_NN, "random": _lib.RL_MCTS_RANDOM}
+SOURCES = {"fg": _lib.RL_MCTS_FG, "nn": _lib.RL_MCTS_NN, "random": _lib.RL_MCTS_RANDOM, "track": _lib.RL_MCTS_PURSUIT}
+#: who steers a roll-out (rl_mcts_params.rollout_source)
+ROLLOUTS = {"random": 0, "pursuit": 1}
 #: the reward term of a roll-out step (rl_plan_track_params.reward_mode)
 REWARDS = {"velocity": 0, "waypoint": 1, "progress": 2}
 MAX_TRACK_POINTS = 65536
@@ -107,6 +111,25 @@ def plan_track_args(reward="progress", lookahead=1.5, window=0, goal_span=0, poi
     return p
 
 
+def rollout_args(rollout="random", rollout_dev=0.1):
+    """The roll-out keywords of the planner checked (no library call): (rollout_source, rollout_dev)."""
+    if rollout not in ROLLOUTS:
+        raise ValueError("rollout must be one of %s" % sorted(ROLLOUTS))
+    dev = float(rollout_dev)
+    if not np.isfinite(dev) or dev < 0:
+        raise ValueError("rollout_dev must be finite and >= 0")
+    return ROLLOUTS[rollout], dev
+
+
+def steering_args(source, rollout, track, points):
+    """What a planner steered by the track needs before it searches (no library call): ``source="track"`` a track or
+    explicit points, ``rollout="pursuit"`` a track (a roll-out travels metres: one point does not help it)."""
+    if source == "track" and track is None and not points:
+        raise ValueError("source 'track' needs a track or a track point")
+    if rollout == "pursuit" and track is None:
+        raise ValueError("rollout 'pursuit' needs a track")
+
+
 def points_args(xy, n):
     """Explicit track points checked and laid out (no library call): float64 (n, 2), or one point for all."""
     p = np.asarray(xy, np.float64)
@@ -118,17 +141,24 @@ def points_args(xy, n):
 
 
 class MCTSPlanner(_lib.Handle):
-    """K trees of at most ``max_nodes`` nodes on one device.  ``method`` scans, ``source`` ("fg", "nn" or "random")
-    picks the expansion answer: ``followgap`` (a ``PyFollowGap``) for "fg", ``policy`` (a ``Policy``) for "nn".
-    The handles are borrowed: keep them alive as long as the planner."""
+    """K trees of at most ``max_nodes`` nodes on one device.  ``method`` scans, ``source`` ("fg", "nn", "random" or
+    "track") picks the expansion answer: ``followgap`` (a ``PyFollowGap``) for "fg", ``policy`` (a ``Policy``) for "nn",
+    the pure pursuit of the tree's track point for "track" (``attach_track`` or ``set_points`` before the reset).
+    ``rollout``: "random" (the reference's uniform steer) or "pursuit" (every roll-out action steers for the attached
+    track's goal waypoint, plus a uniform deviation of +-``rollout_dev`` rad).  The handles are borrowed: keep them
+    alive as long as the planner."""
     _destroy = "rl_mcts_destroy"
     _track, _points = None, False       # (the attached Track, kept alive here; are explicit points set)
+    _velocity_points = False            # (explicit points alone run the velocity reward, not the waypoint reward)
+    source, rollout = "fg", "random"
 
     def __init__(self, car, method, n_trees, max_nodes, fov, num_rays, edge, crash_thresh, source="fg",
                  followgap=None, policy=None, rollout_steps=200, action_every=10, speed=2.0, dt=0.01,
-                 scan_dist_to_base=0.275, C_ucb=0.5, crash_pen=-10.0, uni_dev=0.05, max_steer=None, max_speed=None):
+                 scan_dist_to_base=0.275, C_ucb=0.5, crash_pen=-10.0, uni_dev=0.05, max_steer=None, max_speed=None,
+                 rollout="random", rollout_dev=0.1):
         if source not in SOURCES:
             raise ValueError("source must be one of %s" % sorted(SOURCES))
+        rollout_source, rollout_dev = rollout_args(rollout, rollout_dev)
         edge = np.asarray(edge)
         if edge.dtype != np.float64 or edge.shape != (int(num_rays),):
             raise ValueError("edge must be float64 (num_rays,)")
@@ -141,8 +171,9 @@ class MCTSPlanner(_lib.Handle):
         p.max_steer = float(car.params["max_steer_ang"] if max_steer is None else max_steer)
         p.max_speed = float(car.params["max_speed"] if max_speed is None else max_speed)
         p.fov, p.num_rays, p.crash_thresh = float(fov), int(num_rays), float(crash_thresh)
+        p.rollout_source, p.rollout_dev = rollout_source, rollout_dev
         self.params = p
-        self.n_trees, self.max_nodes, self.source = int(n_trees), int(max_nodes), source
+        self.n_trees, self.max_nodes, self.source, self.rollout = int(n_trees), int(max_nodes), source, rollout
         self._keep = (car, method, followgap, policy)
         self._h = C.c_void_p()
         _lib.call("rl_mcts_create", car, method, followgap, policy, p, self._edge, self._h)
@@ -152,23 +183,34 @@ class MCTSPlanner(_lib.Handle):
         (per step the arc length gained, searched within ``window`` segments of the root's nearest segment; 0: all),
         "waypoint" (velocity over the distance to the tree's track point: the waypoint ``lookahead`` away from the
         root, findBestPoint's rule, looking ``goal_span`` waypoints ahead; 0: all) or "velocity" (today's reward).
-        Takes effect at the next ``reset`` or ``drive``."""
+        Takes effect at the next ``reset`` or ``drive``.  A planner with ``source="track"`` (without explicit points) or
+        ``rollout="pursuit"`` reads ``lookahead``, ``goal_span`` and ``window`` for its steering whatever the reward."""
         p = plan_track_args(reward, lookahead, window, goal_span, points=self._points)
         if track is None:
             raise ValueError("track must be a Track (detach_track() removes it)")
+        steers = (self.source == "track" and not self._points) or self.rollout == "pursuit"
+        if steers and (not np.isfinite(p.lookahead) or p.lookahead <= 0):
+            raise ValueError("lookahead must be finite and > 0")
         _lib.call("rl_mcts_attach_track", self, track, p)
         self._track = track
 
     def detach_track(self):
         _lib.call("rl_mcts_attach_track", self, None, None)
-        self._track = None
+        self._track, self._velocity_points = None, False
 
-    def set_points(self, xy):
+    def set_points(self, xy, reward="waypoint"):
         """One explicit track point per tree, float64 (K, 2) or (2,) for all (None removes them): the waypoint reward's
-        point, as the reference's constructor takes it.  Without a track the planner then runs the waypoint reward."""
+        point, as the reference's constructor takes it, and what ``source="track"`` pursues.  Without a track the planner
+        then runs the waypoint reward, or with ``reward="velocity"`` (no track attached) the velocity reward."""
+        if reward not in ("waypoint", "velocity"):
+            raise ValueError("reward of explicit points must be 'waypoint' or 'velocity'")
         p = None if xy is None else points_args(xy, self.n_trees)
         _lib.call("rl_mcts_set_points", self, p)
         self._points = p is not None
+        velocity = p is not None and reward == "velocity"
+        if self._track is None and velocity != self._velocity_points:
+            _lib.call("rl_mcts_attach_track", self, None, plan_track_args("velocity", points=True) if velocity else None)
+            self._velocity_points = velocity
 
     def read_track(self):
         """The current roots on the track, a dict: segment int32 (K,), s float64 (K,), goal int32 (K,) (-1: none), point
@@ -184,9 +226,11 @@ class MCTSPlanner(_lib.Handle):
         st = np.ascontiguousarray(np.asarray(root_states, np.float64).reshape(K, 11))
         ac = np.ascontiguousarray(np.broadcast_to(np.asarray(root_actions, np.float64), (K,)))
         sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, np.uint64), (K,)))
+        steering_args(self.source, self.rollout, self._track, self._points)
         _lib.call("rl_mcts_reset", self, st, ac, sd)
 
     def run(self, n_iterations):
+        steering_args(self.source, self.rollout, self._track, self._points)
         _lib.call("rl_mcts_run", self, n_iterations)
 
     def best(self):
@@ -220,6 +264,7 @@ class MCTSPlanner(_lib.Handle):
         K = self.n_trees
         if self._points:
             raise ValueError("a planner with explicit points cannot drive: attach a track instead")
+        steering_args(self.source, self.rollout, self._track, self._points)
         st, ac, sd, D, I, S, clip = drive_args(K, states, recent_actions, seeds, n_decisions, n_iterations,
                                                steps_per_decision, steer_clip)
         first, out, recent = np.empty(K, np.int32), np.empty((K, 11)), np.empty(K)
@@ -273,15 +318,25 @@ class MCTS:
     ``budget`` seconds of wall clock run chunks of iterations until the time is spent or ``max_nodes`` is reached,
     at least one iteration; ``n_iterations`` runs exactly that many instead (deterministic).  ``seed`` keys the
     draws.  ``source``: "fg" (the reference's live generateActionFromFG, PyFollowGap(10, 15.0, max_steer, 0.004)),
-    "nn" (``policy_session``, a ``Policy``) or "random".  ``with_global=True`` with a ``track_point`` (x, y) is the
+    "nn" (``policy_session``, a ``Policy``), "random" or "track" (the pure pursuit of ``track_point``, or of the goal
+    waypoint of ``track``, whether or not ``with_global`` asks for the waypoint reward).  ``track`` (a ``Track``) is
+    attached with the velocity reward (the waypoint reward with ``with_global=True``) and ``lookahead``, ``track_window``
+    and ``goal_span``; ``rollout="pursuit"`` needs it (``rollout_dev`` as ``MCTSPlanner``).  ``with_global=True`` with a ``track_point`` (x, y) is the
     reference's global-planner call (mcts_driver.py:224-227): every roll-out step is rewarded with its velocity over the
     distance to that point (mcts.py:233-234, 247-250, commented out upstream).  ``with_global=False``, the default,
     is the velocity reward, whatever ``track_point`` holds."""
 
     def __init__(self, simulator, policy_session, recent_action, roll_out_itr, budget=1.0, track_point=None,
-                 with_global=False, *, seed=0, n_iterations=None, source="fg", max_nodes=4097):
-        if with_global and track_point is None:
+                 with_global=False, *, seed=0, n_iterations=None, source="fg", max_nodes=4097, track=None, rollout="random",
+                 rollout_dev=0.1, lookahead=1.5, track_window=0, goal_span=0):
+        if with_global and track_point is None and track is None:
             raise ValueError("with_global=True needs a track_point")
+        if source not in SOURCES:
+            raise ValueError("source must be one of %s" % sorted(SOURCES))
+        rollout_args(rollout, rollout_dev)
+        steering_args(source, rollout, track, track_point is not None)
+        self.track, self.rollout, self.rollout_dev = track, rollout, rollout_dev
+        self.track_args = (lookahead, track_window, goal_span)
         self.point_to_follow = track_point
         self.with_global = with_global
         self.simulator = simulator
@@ -311,13 +366,16 @@ class MCTS:
                            policy=self.policy_session if self.source == "nn" else None,
                            rollout_steps=self.max_iterations, speed=self.speed, C_ucb=self.C, crash_pen=self.crash_pen,
                            scan_dist_to_base=sim.scan_dist_to_base, max_steer=sim.config["max_steer_ang"],
-                           max_speed=sim.config["max_speed"])
+                           max_speed=sim.config["max_speed"], rollout=self.rollout, rollout_dev=self.rollout_dev)
 
     def mcts(self):
         if self._planner is None:
             self._planner = self._make_planner()
-            if self.with_global:
-                self._planner.set_points(self.point_to_follow)
+            reward = "waypoint" if self.with_global else "velocity"
+            if self.point_to_follow is not None and (self.with_global or self.source == "track"):
+                self._planner.set_points(self.point_to_follow, reward=reward)
+            if self.track is not None:
+                self._planner.attach_track(self.track, reward, *self.track_args)
         pl = self._planner
         pl.reset(self.simulator.getState()[None, :], [self.action], [self.seed])
         cap = self.max_nodes - 1

@@ -320,20 +320,28 @@ class CarBatch(_lib.Handle):
     def plan_mcts(self, method, followgap_or_policy, root_states, n_iterations, seeds, fov, num_rays, edge,
                   crash_thresh, root_actions=0.0, source=None, rollout_steps=200, action_every=10, speed=2.0,
                   dt=0.01, scan_dist_to_base=0.275, C_ucb=0.5, crash_pen=-10.0, uni_dev=0.05, max_nodes=None,
-                  trees=False, track=None, track_reward="progress", lookahead=1.5, track_window=0, goal_span=0):
+                  trees=False, track=None, track_reward="progress", lookahead=1.5, track_window=0, goal_span=0,
+                  rollout="random", rollout_dev=0.1):
         """scripts/mcts.py's search for K trees at once (``rl_mcts_*``, one tree per root state): ``n_iterations``
         iterations each, every tree adding one node per iteration.  ``followgap_or_policy``: a ``PyFollowGap``
         (source "fg"), a ``Policy`` ("nn") or None ("random"); ``source`` overrides the choice.  root_states float64
         (K, 11), root_actions scalar or (K,), seeds uint64 (K,).  Returns (best root action float64 (K,), its visits
         int32 (K,), nodes per tree int32 (K,)) and with ``trees=True`` also the K node-array dicts of
         ``MCTSPlanner.read_tree``.  ``track`` (a ``Track``): the roll-outs are rewarded along it, ``track_reward``,
-        ``lookahead``, ``track_window`` and ``goal_span`` as ``MCTSPlanner.attach_track`` takes them."""
+        ``lookahead``, ``track_window`` and ``goal_span`` as ``MCTSPlanner.attach_track`` takes them
+        (``track_reward="velocity"`` attaches it for the steering alone).  ``source="track"`` (no handle:
+        ``followgap_or_policy`` None) expands with the pure pursuit of the track's goal waypoint, ``rollout="pursuit"``
+        steers the roll-outs along it with a deviation of +-``rollout_dev``; both need ``track``."""
+        from .mcts import rollout_args, steering_args
+        rollout_args(rollout, rollout_dev)
+        steering_args(source, rollout, track, False)
         root_states = np.asarray(root_states, np.float64).reshape(-1, 11)
         K = root_states.shape[0]
         n_iterations = int(n_iterations)
         pl = self._planner(method, followgap_or_policy, source, K, max_nodes or n_iterations + 1, fov, num_rays, edge,
                            crash_thresh, rollout_steps=rollout_steps, action_every=action_every, speed=speed, dt=dt,
-                           scan_dist_to_base=scan_dist_to_base, C_ucb=C_ucb, crash_pen=crash_pen, uni_dev=uni_dev)
+                           scan_dist_to_base=scan_dist_to_base, C_ucb=C_ucb, crash_pen=crash_pen, uni_dev=uni_dev,
+                           rollout=rollout, rollout_dev=rollout_dev)
         try:
             if track is not None:
                 pl.attach_track(track, track_reward, lookahead, track_window, goal_span)
@@ -350,18 +358,23 @@ class CarBatch(_lib.Handle):
                    crash_thresh, recent_actions=0.0, source=None, steps_per_decision=1, steer_clip=None,
                    rollout_steps=200, action_every=10, speed=2.0, dt=0.01, scan_dist_to_base=0.275, C_ucb=0.5,
                    crash_pen=-10.0, uni_dev=0.05, trace=False, track=None, track_reward="progress", lookahead=1.5,
-                   track_window=0, goal_span=0):
+                   track_window=0, goal_span=0, rollout="random", rollout_dev=0.1):
         """scripts/mcts_driver.py's closed loop for K cars at once (``rl_mcts_drive``): every car replans at each of
         ``n_decisions`` decisions (a fresh tree of ``n_iterations`` iterations from its state) and takes
         ``steps_per_decision`` steps with the most visited root action.  Source and handles as ``plan_mcts``; states
         float64 (K, 11), recent_actions scalar or (K,), seeds integers (K,).  Returns ``MCTSPlanner.drive``'s tuple.
-        ``track`` and its keywords as ``plan_mcts``: the roots are placed on it anew at every decision, on the device."""
+        ``track`` and its keywords as ``plan_mcts``: the roots are placed on it anew at every decision, on the device;
+        ``source="track"``, ``rollout`` and ``rollout_dev`` as ``plan_mcts``."""
+        from .mcts import rollout_args, steering_args
+        rollout_args(rollout, rollout_dev)
+        steering_args(source, rollout, track, False)
         states = np.asarray(states)
         if states.dtype != np.float64 or states.ndim != 2 or states.shape[1] != 11:
             raise ValueError("states must be float64 (K, 11)")
         pl = self._planner(method, followgap_or_policy, source, states.shape[0], int(n_iterations) + 1, fov, num_rays,
                            edge, crash_thresh, rollout_steps=rollout_steps, action_every=action_every, speed=speed,
-                           dt=dt, scan_dist_to_base=scan_dist_to_base, C_ucb=C_ucb, crash_pen=crash_pen, uni_dev=uni_dev)
+                           dt=dt, scan_dist_to_base=scan_dist_to_base, C_ucb=C_ucb, crash_pen=crash_pen, uni_dev=uni_dev,
+                           rollout=rollout, rollout_dev=rollout_dev)
         try:
             if track is not None:
                 pl.attach_track(track, track_reward, lookahead, track_window, goal_span)

@@ -268,12 +268,17 @@ class RacecarSimulator:
         return None
 
     def planMCTSMany(self, states, n_iterations, seeds=None, source="fg", policy=None, root_actions=0.0, track=None,
-                     track_reward="progress", lookahead=1.5, track_window=0, goal_span=0):
+                     track_reward="progress", lookahead=1.5, track_window=0, goal_span=0, rollout="random",
+                     rollout_dev=0.1):
         """scripts/mcts.py's search from each of R start states at once (one tree each, ``n_iterations`` iterations,
         roll-outs of ``batch_size`` steps) on this simulator's range method, edge table and ttc_thresh; ``source``
         "fg" (PyFollowGap(10, 15.0, max_steer_ang, 0.004)), "nn" (``policy``) or "random".  seeds: one per tree
         (default 0 ... R-1).  ``track`` (a ``Track``) and its keywords as ``CarBatch.plan_mcts``: the roll-outs are
-        rewarded along the track.  Returns ``CarBatch.plan_mcts``'s (best actions, their visits, nodes per tree)."""
+        rewarded along the track; ``source="track"`` and ``rollout="pursuit"`` (with ``rollout_dev``) let it steer the
+        search as well.  Returns ``CarBatch.plan_mcts``'s (best actions, their visits, nodes per tree)."""
+        from .mcts import rollout_args, steering_args
+        rollout_args(rollout, rollout_dev)
+        steering_args(source, rollout, track, False)
         states = np.asarray(states, dtype=np.float64).reshape(-1, 11)
         R = states.shape[0]
         seeds = np.arange(R, dtype=np.uint64) if seeds is None else np.asarray(seeds, np.uint64)
@@ -282,18 +287,23 @@ class RacecarSimulator:
                                   self.scan_fov, self.num_rays, self.edge_distances, self.ttc_thresh,
                                   root_actions=root_actions, source=source, rollout_steps=self.batch_size,
                                   scan_dist_to_base=self.scan_dist_to_base, track=track, track_reward=track_reward,
-                                  lookahead=lookahead, track_window=track_window, goal_span=goal_span)
+                                  lookahead=lookahead, track_window=track_window, goal_span=goal_span, rollout=rollout,
+                                  rollout_dev=rollout_dev)
 
     def driveMCTSMany(self, states, n_decisions, n_iterations, seeds=None, source="fg", policy=None, steer_clip=0.4189,
                       steps_per_decision=1, recent_actions=0.0, track=None, track_reward="progress", lookahead=1.5,
-                      track_window=0, goal_span=0):
+                      track_window=0, goal_span=0, rollout="random", rollout_dev=0.1):
         """scripts/mcts_driver.py's action callback (:207-264) for R cars at once: at each of ``n_decisions``
         decisions every car plans a fresh tree from its state (``planMCTSMany``'s search and source, seed
         ``seeds + d``), then takes ``steps_per_decision`` steps with the most visited root action; the recent action
         at the next root is that action clamped to +-``steer_clip`` (the driver's 0.4189; None: raw).  Returns
         ``CarBatch.drive_mcts``'s (first crash decision or -(n_decisions+1), final states, recent actions, actions
         (R, n_decisions), visits (R, n_decisions)); nothing leaves the GPU between decisions, with a ``track`` (keywords
-        as ``planMCTSMany``) neither: every decision's roots are placed on it on the device."""
+        as ``planMCTSMany``, ``source="track"`` and ``rollout="pursuit"`` included) neither: every decision's roots are
+        placed on it on the device."""
+        from .mcts import rollout_args, steering_args
+        rollout_args(rollout, rollout_dev)
+        steering_args(source, rollout, track, False)
         states = np.asarray(states, dtype=np.float64).reshape(-1, 11)
         R = states.shape[0]
         seeds = np.arange(R, dtype=np.uint64) if seeds is None else np.asarray(seeds, np.uint64)
@@ -303,7 +313,8 @@ class RacecarSimulator:
                                    recent_actions=recent_actions, source=source, steps_per_decision=steps_per_decision,
                                    steer_clip=steer_clip, rollout_steps=self.batch_size,
                                    scan_dist_to_base=self.scan_dist_to_base, track=track, track_reward=track_reward,
-                                   lookahead=lookahead, track_window=track_window, goal_span=goal_span)
+                                   lookahead=lookahead, track_window=track_window, goal_span=goal_span, rollout=rollout,
+                                  rollout_dev=rollout_dev)
 
     def particleFilter(self, n_particles, angles=None, motion_std=(0.05, 0.05, 0.02), resample_ratio=0.5,
                        sensor_model=None):
